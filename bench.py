@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- LM iterations/s (+ Jacobian Mnnz/s) of the MI355X hot path on a synthetic BAL-shaped problem.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps (plus the Jacobian throughput the metric names) and prints the line.
+--full adds the secondary measurements: the host-boundary rate, facto = :PCG beside the direct branch, the residual
+throughput, the per-kernel profile and rooflines, and the CPU baselines.  --dump-outputs DIR writes what the timed call
+returned after its last step (the iterate and its statistics) as DIR/<name>.npy, so that two builds can be compared.
 
 A "step" is one Levenberg-Marquardt iteration of src/lm.jl (factor + solve of the damped normal equations, trial
 residual, accept/reject; accepted steps add a Jacobian refresh), run with all stopping tolerances at zero so that
@@ -114,6 +119,12 @@ def parse():
                     help="torch.distributed backend: nccl (= RCCL, default) or gloo (host-staged all-reduce; rehearsal only)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (several ranks sharing one GPU need --backend gloo)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: host_boundary, pcg, residual throughput, per-kernel profile and "
+                         "rooflines, cpu_baseline / cpu_baseline_full (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned (iterate x, objective, dual_feas, "
+                         "lambda_final, counts) as DIR/<name>.npy; rank 0's part of x at N > 1")
     return ap.parse_args()
 
 
@@ -128,6 +139,30 @@ def lm_fixed_iterations(ba, fr, k, x=None, x_device_ptr=None):
     return ba.Levenberg_Marquardt(fr, FACTO, PERM, "None", False, x=x, ite_max=k - 1, restol=0.0, satol=0.0, srtol=0.0,
                                   oatol=0.0, ortol=0.0, atol=0.0, rtol=0.0, log=False, facto_type=FACTO_TYPE, pcg_tol=PCG_TOL,
                                   x_device_ptr=x_device_ptr)
+
+
+DUMP_BYTES_MAX = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+DUMP_SEED = 20261016            # fixed sample of x when x alone would exceed it
+
+
+def dump_outputs(out_dir, x, st):
+    """What the timed call hands its caller after the last step: the iterate x (device-resident; copied here) and the
+    statistics of GenericExecutionStats, float64 .npy files.  An x larger than the budget is written as a fixed, seeded
+    sample of its entries (x.npy) with their indices (x_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    cap = (DUMP_BYTES_MAX - 4096) // 16  # values + indices, room left for the scalars
+    if x.nbytes > DUMP_BYTES_MAX - 4096:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, size=cap, replace=False))
+        np.save(os.path.join(out_dir, "x_index.npy"), idx.astype(np.float64))
+        x = x[idx]
+    np.save(os.path.join(out_dir, "x.npy"), x)
+    np.save(os.path.join(out_dir, "objective.npy"), np.array([st.objective], dtype=np.float64))
+    np.save(os.path.join(out_dir, "dual_feas.npy"), np.array([st.dual_feas], dtype=np.float64))
+    np.save(os.path.join(out_dir, "lambda_final.npy"), np.array([st.lambda_final], dtype=np.float64))
+    # iter, n_accepted, n_rejected, n_residual, n_jacobian, n_factor, n_cg
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([st.iter, st.n_accepted, st.n_rejected, st.n_residual, st.n_jacobian,
+                                                            st.n_factor, st.n_cg], dtype=np.float64))
 
 
 def spawn_ranks(args):
@@ -201,7 +236,7 @@ def main():
     # ---- warmup (also allocates the LM workspace and builds the Schur task list) ---------------------------------------
     # The timed region starts with its input resident in HBM: x0 sits in device memory and the K iterations run through
     # ba_lm_solve_dev.  (The reference's boundary hands over host vectors; the rate through ba_lm_solve, with the upload of x0
-    # and the download of the solution inside the call, is measured once below and reported as `host_boundary`.)
+    # and the download of the solution inside the call, is measured once below and reported as `host_boundary` under --full.)
     x0_dev = torch.from_numpy(np.ascontiguousarray(arrays[3], dtype=np.float64)).cuda()
     x_work = torch.empty_like(x0_dev)
     if args.warmup > 0:
@@ -213,11 +248,17 @@ def main():
     st = lm_fixed_iterations(ba, fr, args.steps, x_device_ptr=x_work.data_ptr())
     barrier()
     elapsed = time.perf_counter() - t1
-    t1 = time.perf_counter()
-    st_host = lm_fixed_iterations(ba, fr, args.steps)  # the same K iterations from / to host memory
-    barrier()
-    elapsed_host = time.perf_counter() - t1
-    assert st_host.iter == st.iter and st_host.objective == st.objective, (st_host.objective, st.objective)
+    assert st.iter == args.steps, (st.iter, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_work.cpu().numpy(), st)
+    elapsed_host = None
+    if args.full:
+        t1 = time.perf_counter()
+        st_host = lm_fixed_iterations(ba, fr, args.steps)  # the same K iterations from / to host memory
+        barrier()
+        elapsed_host = time.perf_counter() - t1
+        assert st_host.iter == st.iter and st_host.objective == st.objective, (st_host.objective, st.objective)
+
     def max_over_ranks(v):
         if world <= 1:
             return v
@@ -226,13 +267,13 @@ def main():
         return float(t.item())
 
     elapsed = max_over_ranks(elapsed)
-    elapsed_host = max_over_ranks(elapsed_host)
-    assert st.iter == args.steps, (st.iter, args.steps)
+    if args.full:
+        elapsed_host = max_over_ranks(elapsed_host)
 
     # ---- the same K iterations by the matrix-free CG extension (facto = :PCG, relative residual 1e-8), reported beside the
     # headline (which stays on the reference's direct branch): the path that scales with the number of GPUs ------------------
     pcg_line = None
-    if FACTO != "PCG" and not args.no_pcg:
+    if args.full and FACTO != "PCG" and not args.no_pcg:
         def lm_pcg(k):
             return ba.Levenberg_Marquardt(fr, "PCG", "AMD", "None", False, ite_max=k - 1, restol=0.0, satol=0.0, srtol=0.0, oatol=0.0,
                                           ortol=0.0, atol=0.0, rtol=0.0, log=False, pcg_tol=1e-8)
@@ -276,28 +317,30 @@ def main():
     jac_gbs = jac_bytes / (jac_ms * 1e-3) / 1e9
 
     # ---- residual throughput (cons!): the same way; one launch = k_cam_pre (a few us) + k_residual --------------------------
-    r_dev = torch.empty(2 * nlp.nobs, dtype=torch.float64, device="cuda")
+    res_ms = res_gbs = None
+    if args.full:
+        r_dev = torch.empty(2 * nlp.nobs, dtype=torch.float64, device="cuda")
 
-    def res():
-        ba._lib.check(L.ba_residual_dev(nlp.handle, C.c_void_p(x_dev.data_ptr()), C.c_void_p(r_dev.data_ptr()), sp))
+        def res():
+            ba._lib.check(L.ba_residual_dev(nlp.handle, C.c_void_p(x_dev.data_ptr()), C.c_void_p(r_dev.data_ptr()), sp))
 
-    for _ in range(10):
-        res()
-    barrier()
-    e0.record(stream)
-    for _ in range(reps):
-        res()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    res_ms = max_over_ranks(e0.elapsed_time(e1) / reps)
-    # algorithmic bytes of cons!: 2 int64 indices + 2 doubles of pt2d + 2 doubles out + every parameter once
-    res_bytes = (48.0 + 8.0 * nvar_g / nobs_g) * nobs_g / world
-    res_gbs = res_bytes / (res_ms * 1e-3) / 1e9
-    del r_dev
+        for _ in range(10):
+            res()
+        barrier()
+        e0.record(stream)
+        for _ in range(reps):
+            res()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        res_ms = max_over_ranks(e0.elapsed_time(e1) / reps)
+        # algorithmic bytes of cons!: 2 int64 indices + 2 doubles of pt2d + 2 doubles out + every parameter once
+        res_bytes = (48.0 + 8.0 * nvar_g / nobs_g) * nobs_g / world
+        res_gbs = res_bytes / (res_ms * 1e-3) / 1e9
+        del r_dev
 
     # ---- per-kernel profile of the same K iterations (separate, synchronising run) ---------------------------------------
     prof = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         nlp.profile(True)
         lm_fixed_iterations(ba, fr, args.steps)
         prof = nlp.profile_get()
@@ -329,20 +372,22 @@ def main():
             ach_all = flops_all / ((ms + ms_rs) * 1e-3) / 1e12
             roof["all_pair_updates"] = dict(kernels="k_ldl_update + k_ldl_update_rs", achieved=ach_all, frac=ach_all / peak_tf,
                                             launches=calls + calls_rs, avg_launch_ms=(ms + ms_rs) / max(1, calls + calls_rs))
-    jac_traffic = pmc_traffic(args.workload, "k_jac_coord")  # measured at N = 1; a rank's launch moves its shard's share
-    roof_jac = dict(kernel="k_jac_coord", bound="hbm", achieved=jac_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=jac_gbs / HBM_PEAK_GBS, traffic=None if jac_traffic is None else jac_traffic / world,
-                    avg_launch_ms=jac_ms,
-                    bytes_per_obs=208.0 + 8.0 * nvar_g / nobs_g)
-    roof_res = dict(kernel="k_cam_pre + k_residual", bound="hbm", achieved=res_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=res_gbs / HBM_PEAK_GBS, traffic=None, avg_launch_ms=res_ms,
-                    bytes_per_obs=48.0 + 8.0 * nvar_g / nobs_g)
-    if roof is None:
-        roof = roof_jac
+    roof_jac = roof_res = None
+    if args.full:
+        jac_traffic = pmc_traffic(args.workload, "k_jac_coord")  # measured at N = 1; a rank's launch moves its shard's share
+        roof_jac = dict(kernel="k_jac_coord", bound="hbm", achieved=jac_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=jac_gbs / HBM_PEAK_GBS, traffic=None if jac_traffic is None else jac_traffic / world,
+                        avg_launch_ms=jac_ms,
+                        bytes_per_obs=208.0 + 8.0 * nvar_g / nobs_g)
+        roof_res = dict(kernel="k_cam_pre + k_residual", bound="hbm", achieved=res_gbs, peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=res_gbs / HBM_PEAK_GBS, traffic=None, avg_launch_ms=res_ms,
+                        bytes_per_obs=48.0 + 8.0 * nvar_g / nobs_g)
+        if roof is None:
+            roof = roof_jac
 
     # ---- CPU baseline: the oracle's restatement of the reference LM, bounded sample, rank 0 at N = 1 only ---------------
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         orc = ge.load_oracle()
         cores = orc.lib().orc_num_threads()
         t0 = time.time()
@@ -373,7 +418,7 @@ def main():
     # ---- one FULLY timed CPU iteration (no cap, no extrapolation) on a shape the oracle finishes, beside the GPU's time
     # on that same shape from this same process ------------------------------------------------------------------------
     cpu_full = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and args.cpu_full != "none":
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and args.cpu_full != "none":
         orc = ge.load_oracle()
         prob2 = ba.synthetic.make_named(args.cpu_full)
         nlp2 = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(prob2), device=local_rank, model_name=args.cpu_full)
@@ -431,21 +476,24 @@ def main():
                                          "pairs, factorisation distributed (panel broadcast), solves replicated")},
             "jacobian_mnnz_per_s": jac_mnnz,
             "jacobian_ms": jac_ms,
-            "host_boundary": {"value": args.steps / elapsed_host, "ms_per_step": 1e3 * elapsed_host / args.steps,
-                              "note": "the same K iterations through ba_lm_solve: x0 uploaded from and the solution downloaded to "
-                                      "pageable host memory inside the call (PCIe-inclusive; never `value`)"},
             "lm": {"accepted": st.n_accepted, "rejected": st.n_rejected, "objective": st.objective,
                    "n_jacobian": st.n_jacobian, "n_factor": st.n_factor, "n_cg": st.n_cg, "loop_s": st.loop_time},
-            "pcg": pcg_line,
-            "roofline": roof,
-            "roofline_traffic_source": pmc_stamp(args.workload),
-            "roofline_jacobian": roof_jac,
-            "roofline_residual": roof_res,
-            "cpu_baseline": cpu,
-            "cpu_baseline_full": cpu_full,
-            "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if v[1] > 0},
             "setup_s": t_setup,
         }
+        if args.full:
+            out.update({
+                "host_boundary": {"value": args.steps / elapsed_host, "ms_per_step": 1e3 * elapsed_host / args.steps,
+                                  "note": "the same K iterations through ba_lm_solve: x0 uploaded from and the solution downloaded "
+                                          "to pageable host memory inside the call (PCIe-inclusive; never `value`)"},
+                "pcg": pcg_line,
+                "roofline": roof,
+                "roofline_traffic_source": pmc_stamp(args.workload),
+                "roofline_jacobian": roof_jac,
+                "roofline_residual": roof_res,
+                "cpu_baseline": cpu,
+                "cpu_baseline_full": cpu_full,
+                "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if v[1] > 0},
+            })
         if FACTO != "PCG":
             tf, ff, sp = ba.schur_pattern(nlp)
             full, held, staging = ba.schur_memory(nlp)

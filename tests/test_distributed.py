@@ -191,7 +191,7 @@ def test_bench_two_ranks_launch_path(gpu_ok):
     shape; the objective after the fixed iterations equals the one-rank run's."""
     def run(extra):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.05", "--steps", "3", "--warmup", "1",
-               "--cpu-seconds", "0", "--cpu-full", "none", "--no-pcg"] + extra
+               "--cpu-seconds", "0", "--cpu-full", "none", "--no-pcg", "--full"] + extra
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
                            env=dict(os.environ, OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0"))
         assert r.returncode == 0, f"bench.py {' '.join(extra)} failed:\n{r.stdout[-1500:]}\n{r.stderr[-3000:]}"

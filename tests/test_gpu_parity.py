@@ -1027,15 +1027,15 @@ def test_pcg_only_handle_holds_nothing_of_the_size_of_S(ba, gpu_ok):
 
 
 def test_bench_line_contract(gpu_ok, tmp_path):
-    """`python bench.py` prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps, warmup,
-    ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus roofline, cpu_baseline and the
-    secondary facto = :PCG measurement; run here on a scaled-down Venice shape."""
+    """`python bench.py --full` prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps,
+    warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus roofline, cpu_baseline
+    and the secondary facto = :PCG measurement; run here on a scaled-down Venice shape."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "4", "--warmup", "1",
-                        "--cpu-seconds", "1", "--cpu-full", "none"], capture_output=True, text=True, timeout=600)
+                        "--cpu-seconds", "1", "--cpu-full", "none", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -1050,6 +1050,34 @@ def test_bench_line_contract(gpu_ok, tmp_path):
     assert roof["bound"] in ("hbm", "mfma") and roof["peak"] > 0 and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-12
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
     assert d["pcg"]["value"] > 0 and abs(d["pcg"]["objective"] - d["pcg"]["objective_direct"]) <= 1e-8 * d["pcg"]["objective_direct"]
+
+
+def test_bench_plain_line_and_dump(gpu_ok, tmp_path):
+    """A plain `python bench.py` (no --full) times the headline only: the same headline fields, none of the secondary
+    measurements; --dump-outputs writes what the timed call returned -- the iterate after the last step and its statistics,
+    float64 -- and the objective there is the one on the line."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "lm"):
+        assert key in d, key
+    for key in ("host_boundary", "pcg", "roofline", "cpu_baseline", "cpu_baseline_full", "kernel_ms"):
+        assert key not in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    x = np.load(out / "x.npy")
+    assert x.dtype == np.float64 and np.all(np.isfinite(x))
+    assert np.load(out / "objective.npy")[0] == d["lm"]["objective"]
+    counts = np.load(out / "counts.npy")
+    assert counts[0] == 3 and counts[1] == d["lm"]["accepted"] and counts[2] == d["lm"]["rejected"]
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 * 10 ** 6
 
 
 # ---- block-sparse reduced camera system (SURVEY 8f rank 4; the reference's sparse LDL' exploits the same sparsity, ------------

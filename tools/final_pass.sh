@@ -1,7 +1,8 @@
 set -e
 TAG=${TAG:-r04_h}
+export OUT=${OUT:-$PWD/tool_out}; mkdir -p "$OUT"
 bash tools/round_profiles.sh $TAG
-b() { name=$1; shift; python bench.py --cpu-seconds 0 --no-pcg "$@" > gpurun_out/${TAG}_bench_$name.json 2> gpurun_out/${TAG}_bench_$name.err; python -c "import sys,json; d=json.loads(open('gpurun_out/${TAG}_bench_$name.json').read().strip().splitlines()[-1]); print('$name', round(d['value'],2), round(d['ms_per_step'],2), d.get('schur_pattern',{}).get('camera_sequence'))"; }
+b() { name=$1; shift; python bench.py --full --cpu-seconds 0 --no-pcg "$@" > "$OUT/${TAG}_bench_$name.json" 2> "$OUT/${TAG}_bench_$name.err"; python -c "import sys,json; d=json.loads(open('$OUT/${TAG}_bench_$name.json').read().strip().splitlines()[-1]); print('$name', round(d['value'],2), round(d['ms_per_step'],2), d.get('schur_pattern',{}).get('camera_sequence'))"; }
 b venice_locality013 --locality 0.13
 b venice_locality013_shuffled --locality 0.13 --shuffle-cameras
 b venice_plane008 --plane-radius 0.08

@@ -1,4 +1,4 @@
-"""Print the headline fields of a bench.py JSON line: python tools/show_bench.py file.json"""
+"""Print the headline fields of a `bench.py --full` JSON line: python tools/show_bench.py file.json"""
 import json
 import sys
 
