@@ -21,6 +21,10 @@ class BAError(RuntimeError):
         self.code = code
 
 
+class BAArgError(BAError, ValueError):
+    """BA_ERR_ARG: an argument the library refuses (also a ValueError)."""
+
+
 class SQDException(BAError):
     """Zero pivot in the LDL' factorisation (reference: src/ldl_aux.jl:45-47,199)."""
 
@@ -57,7 +61,7 @@ SYMBOLS = [
     "ba_jac_structure_dev", "ba_jac_coord_dev", "ba_jac_coord_f32_dev", "ba_jtr_dev", "ba_dev_malloc", "ba_dev_free",
     "ba_memcpy_h2d", "ba_memcpy_d2h", "ba_memcpy_h2d_on", "ba_memcpy_d2h_on", "ba_synchronize", "ba_lm_solve", "ba_lm_solve_dev", "ba_comm_get_unique_id", "ba_lm_set_comm_rccl",
     "ba_lm_set_comm_hook", "ba_comm_stats", "ba_comm_stats_ops", "ba_dist_layout",
-    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
+    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
 ]
 
 _lib = None
@@ -112,6 +116,9 @@ def lib():
     L.ba_schur_ordering.argtypes = [i64, i64, i64, vp, vp, C.c_int, vp, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64)]
     L.ba_lm_set_ordering.argtypes = [vp, C.c_int]
     L.ba_lm_schur_ordering.argtypes = [vp, vp, C.POINTER(C.c_char_p)]
+    L.ba_lm_set_loss.argtypes = [vp, C.c_int, f64]
+    L.ba_lm_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(f64)]
+    L.ba_robust_eval.argtypes = [vp, vp, vp, C.POINTER(f64)]
     L.ba_profile_enable.argtypes = [vp, C.c_int]
     L.ba_profile_reset.argtypes = [vp]
     L.ba_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(f64), C.POINTER(i64), C.POINTER(C.c_int)]
@@ -126,6 +133,8 @@ def check(rc):
         msg = lib().ba_last_error().decode("utf-8", "replace")
         if rc == 4:
             raise SQDException(rc, msg)
+        if rc == 1:
+            raise BAArgError(rc, msg)
         raise BAError(rc, msg)
 
 
@@ -145,6 +154,30 @@ def device_count():
 
 
 ORDERINGS = {"AMD": 0, "Metis": 1, "natural": 2}
+
+# robust losses of the LM entries (ba_lm_set_loss): scipy's names
+LOSSES = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
+
+
+def loss_code(loss, f_scale):
+    """(BA_LOSS_* code, scale) of a loss name ("huber" or the symbol-style ":huber") and f_scale; ValueError for an unknown
+    name or a scale that is not finite and > 0 -- before any device call."""
+    name = loss[1:] if isinstance(loss, str) and loss.startswith(":") else loss
+    if name not in LOSSES:
+        raise ValueError(f"loss must be one of {', '.join(LOSSES)} (or :name), got {loss!r}")
+    try:
+        c = float(f_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"f_scale must be a finite number > 0, got {f_scale!r}") from None
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError(f"f_scale must be a finite number > 0, got {f_scale!r}")
+    return LOSSES[name], c
+
+
+def set_loss(handle, loss, f_scale):
+    """the handle's loss for its next LM calls (ba_lm_set_loss)"""
+    kind, c = loss_code(loss, f_scale)
+    check(lib().ba_lm_set_loss(handle, kind, c))
 
 
 def schur_ordering(cam_idx1, pnt_idx1, ncams, npnts, method="AMD"):

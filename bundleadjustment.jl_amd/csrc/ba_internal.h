@@ -94,6 +94,7 @@ enum ProfClass {
   PC_TRIAL,
   PC_REDUCE,
   PC_COMM,
+  PC_ROBUST,  // k_robust_scale (robust loss: reweighting of r and J)
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -184,6 +185,9 @@ struct ba_problem {
   size_t scratch_bytes[4] = {0, 0, 0, 0};
   // LM workspace (allocated at the first solve)
   struct LMWork *lm = nullptr;
+  // robust loss of the LM entries (ba_lm_set_loss): BA_LOSS_*, scale c > 0
+  int loss = BA_LOSS_LINEAR;
+  double loss_scale = 1.0;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

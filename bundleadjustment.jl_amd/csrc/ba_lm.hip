@@ -28,9 +28,10 @@ double wall() {
 }
 
 // scalar slots.  "sharded" sums are partial per rank and all-reduced; "replicated" ones are identical on every rank.
-// slots 0..2 are refreshed (and reduced) with the linearisation, slots 3..5 with every trial step
-enum { SH_RSQ = 0, SH_GP, SH_X_P, SH_RSQ_TRIAL, SH_MODEL, SH_DELTA_P, SH_COUNT = 8 };
-constexpr int SH_LIN_COUNT = 3, SH_TRIAL_FIRST = 3, SH_TRIAL_COUNT = 3;
+// slots 0..2 (3 under a robust loss) are refreshed (and reduced) with the linearisation, slots 4..6 with every trial step.
+// Robust loss (ba_lm_set_loss): SH_RSQ and SH_RSQ_TRIAL hold 2 f = sum c^2 rho(z) instead of |r|^2, SH_RTSQ |r~|^2
+enum { SH_RSQ = 0, SH_GP, SH_X_P, SH_RTSQ, SH_RSQ_TRIAL, SH_MODEL, SH_DELTA_P, SH_COUNT = 8 };
+constexpr int SH_LIN_COUNT = 3, SH_TRIAL_FIRST = 4, SH_TRIAL_COUNT = 3;
 enum { RP_DELTA_C = 0, RP_X_C, RP_GC, RP_COUNT = 8 };
 
 template <typename T>
@@ -229,7 +230,8 @@ struct LMWorkFull : LMWork {
   double *d_lambda = nullptr, *h_lambda = nullptr;  // device scalar, pinned staging
   int *h_flag = nullptr;                            // pinned copy of the pivot flag
   hipGraphExec_t g_step[2] = {nullptr, nullptr}, g_refresh[2] = {nullptr, nullptr};
-  int g_key = -1;  // normalize + 4 * facto_f32 + 8 * x_f32 the graphs were recorded for
+  int g_key = -1;  // graph_key(): normalize + 4 * facto_f32 + 8 * x_f32 + 16 * loss the graphs were recorded for
+  double g_scale = 1.0;  // ... and the loss scale (the robust kernels take loss and scale as launch arguments)
   int parity = 0;
   bool g_off = false;  // a recording failed on this handle: plain launches from then on
   // facto = PCG: block-Jacobi preconditioned conjugate gradients on the reduced camera system, S never formed (pcg_solve).
@@ -241,6 +243,7 @@ struct LMWorkFull : LMWork {
   int64_t n_cg = 0;   // CG iterations of the current solve
   double *cgx = nullptr, *cgr = nullptr, *cgz = nullptr, *cgp = nullptr, *cgq = nullptr, *cgt = nullptr;
   double *cgh = nullptr, *zero3 = nullptr, *blk45 = nullptr, *cg_scal = nullptr, *h_cg = nullptr;
+  double *rob_partial = nullptr;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
 };
 
 namespace {
@@ -333,6 +336,7 @@ static int lm_ensure(ba_problem *p) {
   BA_CHECK(dmalloc(&w->colscale, 9 * ncams));
   BA_CHECK(dmalloc(&w->partial, std::max<int64_t>(RED_BLOCKS, (npnts + 255) / 256)));  // k_wtv<true>: one partial per 256 points
   BA_CHECK(dmalloc(&w->partial_multi, (int64_t)SUMSQ_JOBS * RED_BLOCKS));
+  BA_CHECK(dmalloc(&w->rob_partial, (int64_t)2 * RED_BLOCKS));
   BA_HIP_CHECK(hipMalloc((void **)&w->cam_pnt, (size_t)(p->nobs > 0 ? p->nobs : 1) * sizeof(int)));
   BA_CHECK(launch_cam_pnt(p, w->cam_pnt, p->stream));
   BA_CHECK(dmalloc(&w->s.scal_rep, (int64_t)RP_COUNT));
@@ -749,8 +753,10 @@ static int reduce_camera_system(ba_problem *p, LMWorkFull *w, hipStream_t st, bo
   return comm_sum(p, w, w->s.off_rhs, w->npad, st);
 }
 
-// r, J and the normal-equation blocks at w->x; fills sharded/replicated scalars RSQ?, GP, GC, X_P, X_C
+// r, J and the normal-equation blocks at w->x; fills sharded/replicated scalars RSQ?, GP, GC, X_P, X_C (and RTSQ)
 // publish: the last reduction kernel also writes the controller's scalars to the pinned host buffers (recorded sequences)
+// Under a robust loss r and J are reweighted in place (r~, J~) before anything reads them; r must hold the plain residual at
+// w->x on entry (residual_too, or the trial residual of an accepted step)
 static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too, hipStream_t st, bool xf32 = false, bool publish = false) {
   if (xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
@@ -767,6 +773,8 @@ static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too
   } else {
     BA_CHECK(launch_jac_coord_f64(p, w->x, w->J, st));
   }
+  const bool robust = p->loss != BA_LOSS_LINEAR;  // (never with xf32: refused by ba_lm_solve)
+  if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
   // gc, the diagonal of the camera block (the column scalings need the global one) and the linearisation scalars are
@@ -775,12 +783,18 @@ static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too
   // |r|^2, |gp|^2, |x_points|^2 and -- of the all-reduced gc -- |gc|^2, |x_cameras|^2: one launch pair on one rank, two with a
   // communicator (the camera sums wait for the all-reduce); bit-identical to launch_sumsq per vector either way
   SumsqJobs jobs;
-  jobs.add(w->r, w->nequ, w->scal, SH_RSQ);
+  if (robust) {  // 2 f and |r~|^2 from k_robust_scale's partials
+    const int nb = robust_blocks(p->nobs);
+    jobs.add_sum(w->rob_partial, nb, w->scal, SH_RSQ);
+    jobs.add_sum(w->rob_partial + RED_BLOCKS, nb, w->scal, SH_RTSQ);
+  } else {
+    jobs.add(w->r, w->nequ, w->scal, SH_RSQ);
+  }
   jobs.add(w->gp, 3 * p->npnts, w->scal, SH_GP);
   jobs.add(w->x, 3 * p->npnts, w->scal, SH_X_P);
   if (p->comm.active()) {
     BA_CHECK(launch_sumsq_multi(p, &jobs, w->partial_multi, st));
-    BA_CHECK(comm_sum(p, w, w->s.off_gc, 2 * w->npad + SH_LIN_COUNT, st));
+    BA_CHECK(comm_sum(p, w, w->s.off_gc, 2 * w->npad + SH_LIN_COUNT + (robust ? 1 : 0), st));  // (SH_RTSQ follows SH_X_P)
     jobs = SumsqJobs();
   }
   if (w->f16) BA_CHECK(launch_col_sq(p, w->Hpp, w->hdiag, w->jn2, st));  // |J_j|^2 before the blocks are overwritten by scaled ones
@@ -1054,11 +1068,15 @@ static int trial_point(ba_problem *p, LMWorkFull *w, hipStream_t st, bool xf32 =
   } else {
     BA_CHECK(launch_residual_f64(p, w->x_trial, w->r_trial, st));
   }
-  if (!with_delta) return launch_sumsq(p, w->nequ, w->r_trial, w->partial, w->scal, SH_RSQ_TRIAL, st);
+  const bool robust = p->loss != BA_LOSS_LINEAR;  // (the line search, the only caller without with_delta, is refused then)
+  if (!with_delta && !robust) return launch_sumsq(p, w->nequ, w->r_trial, w->partial, w->scal, SH_RSQ_TRIAL, st);
   SumsqJobs jobs;
-  jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);
-  jobs.add(w->delta + 3 * p->npnts, w->n, w->s.scal_rep, RP_DELTA_C);
-  jobs.add(w->r_trial, w->nequ, w->scal, SH_RSQ_TRIAL);
+  if (with_delta) {
+    jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);
+    jobs.add(w->delta + 3 * p->npnts, w->n, w->s.scal_rep, RP_DELTA_C);
+  }
+  if (robust) jobs.add_robust(w->r_trial, p->nobs, w->scal, SH_RSQ_TRIAL, p->loss, p->loss_scale * p->loss_scale);  // 2 f(x + delta)
+  else jobs.add(w->r_trial, w->nequ, w->scal, SH_RSQ_TRIAL);
   if (publish_flag) jobs.publish(w->scal, SH_COUNT, w->s.h_sh, w->s.scal_rep, RP_COUNT, w->s.h_rp, publish_flag, w->h_flag);
   return launch_sumsq_multi(p, &jobs, w->partial_multi, st);
 }
@@ -1079,6 +1097,13 @@ static int check_pivot(ba_problem *p, LMWorkFull *w, hipStream_t st) {
 }
 
 // ---- recorded launch sequences ------------------------------------------------------------------------------------------
+// what a recorded sequence depends on besides the handle's buffers: the loss kind and scale are launch arguments of the
+// robust kernels, so a sequence recorded under one loss is never replayed under another
+static int graph_key(ba_problem *p, int normalize, bool facto_f32, bool xf32) {
+  return normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0) + 16 * p->loss;
+}
+static double graph_scale(ba_problem *p) { return p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0; }
+
 static bool graphs_allowed(ba_problem *p, LMWorkFull *w) {
   if (w->g_off || p->prof_on || p->comm.active() || w->f16 || w->pcg) return false;  // per-kernel events / communicator / Float16 path
   // the hoisted-diagonal schedule of large factorisations has a kernel wait for a flag raised by a kernel running
@@ -1128,14 +1153,15 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
     if (hoist_gave_up(w)) return trial_step(p, w, lambda, normalize, facto_f32, xf32, st);
     return BA_OK;
   }
-  const int key = normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0);
-  if (w->g_key != key) {
+  const int key = graph_key(p, normalize, facto_f32, xf32);
+  if (w->g_key != key || w->g_scale != graph_scale(p)) {
     for (int q = 0; q < 2; q++) {
       if (w->g_step[q]) (void)hipGraphExecDestroy(w->g_step[q]);
       if (w->g_refresh[q]) (void)hipGraphExecDestroy(w->g_refresh[q]);
       w->g_step[q] = w->g_refresh[q] = nullptr;
     }
     w->g_key = key;
+    w->g_scale = graph_scale(p);
   }
   if (facto_f32) BA_CHECK(ensure_f32(w));  // no allocation while recording
   hipGraphExec_t &g = w->g_step[w->parity];
@@ -1193,8 +1219,8 @@ static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t s
 static bool can_prefetch_trial(ba_problem *p, LMWorkFull *w, int normalize, bool facto_f32, bool xf32) {
   const char *e = getenv("BA_LM_PREFETCH");  // read per call: a test compares both forms in one process
   if ((e && e[0] == '0') || !graphs_allowed(p, w)) return false;
-  const int key = normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0);
-  return w->g_key == key && w->g_step[w->parity] && w->g_refresh[w->parity];
+  return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && w->g_step[w->parity] &&
+         w->g_refresh[w->parity];
 }
 static int accept_refresh_and_trial(LMWorkFull *w, double lambda, bool facto_f32, hipStream_t st) {
   BA_HIP_CHECK(hipGraphLaunch(w->g_refresh[w->parity], st));
@@ -1406,6 +1432,20 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     ba_set_error("ba_lm_solve: perm must be 0 (:AMD), 1 (:Metis) or 2 (the caller's camera numbering)");
     return BA_ERR_ARG;
   }
+  if (p->loss != BA_LOSS_LINEAR) {  // robust loss (ba_lm_set_loss): the combinations its model value is not defined for
+    if (o->variant == 1 && o->linesearch) {
+      ba_set_error("ba_lm_solve: a robust loss is not supported with linesearch = true (set the loss back to linear)");
+      return BA_ERR_ARG;
+    }
+    if (o->x_f32) {
+      ba_set_error("ba_lm_solve: a robust loss is not supported for a Float32 model (x_f32 = 1)");
+      return BA_ERR_ARG;
+    }
+    if (o->facto_type == 2) {
+      ba_set_error("ba_lm_solve: a robust loss is not supported with facto_type = Float16");
+      return BA_ERR_ARG;
+    }
+  }
   BA_HIP_CHECK(hipSetDevice(p->device));
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
@@ -1469,8 +1509,11 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   BA_CHECK(fetch_scalars(p, w, st));
   stats->n_residual++;
   stats->n_jacobian++;
+  // robust loss (ba_lm_set_loss; Float64 models only): SH_RSQ / SH_RSQ_TRIAL hold 2 f, so obj = f and norm_r = sqrt(2 f) enter
+  // the stopping tests as they are; pred = 1/2 |r~|^2 - 1/2 |J~ delta + r~|^2 and the model value dr2 = f - pred
+  const bool robust = p->loss != BA_LOSS_LINEAR;
   TS norm_r = norm_of(h_sh[SH_RSQ], W);
-  TS obj = ts::div(ts::mul(norm_r, norm_r), T_(2));
+  TS obj = robust ? half_of(h_sh[SH_RSQ]) : ts::div(ts::mul(norm_r, norm_r), T_(2));
   TS norm_Jtr = norm_of(h_sh[SH_GP] + h_rp[RP_GC], W);
   TS norm_x = norm_of(h_sh[SH_X_P] + h_rp[RP_X_C], W);
   if (V) {  // lm.jl:59: lambda = T(max(lambda, 1e10 / norm_Jtr))
@@ -1507,6 +1550,8 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
       break;
     }
     dr2 = half_of(h_sh[SH_MODEL]);  // 1/2 |delta_r|^2   (lm.jl:229)
+    const TS pred_r = ts::f64(0.5 * h_sh[SH_RTSQ] - 0.5 * h_sh[SH_MODEL]);  // (robust loss only)
+    if (robust) dr2 = ts::sub(obj, pred_r);
     TS obj_suiv = half_of(h_sh[SH_RSQ_TRIAL]);
     TS norm_rsuiv = norm_of(h_sh[SH_RSQ_TRIAL], W);
     if (!V) iter++;  // LevenbergMarquardt.jl:240
@@ -1517,7 +1562,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     bool step_accepted;
     int ntimes = 0;
     if (V) {
-      pred = ts::sub(obj, dr2);
+      pred = robust ? pred_r : ts::sub(obj, dr2);
       ared = ts::sub(obj, obj_suiv);
       step_accepted = ared.v >= 1e-4 * pred.v;  // lm.jl:257-259 (Float64 literal)
       double c_r = w->cr0();  // delta_r = -(J delta + c_r r)   (1; 1/mu in the Float16 branch)
@@ -1544,7 +1589,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
       }
       if (rc != BA_OK) break;
     } else {
-      step_accepted = ts::sub(obj_suiv, obj).v < 1e-4 * ts::sub(dr2, obj).v;  // LevenbergMarquardt.jl:243
+      step_accepted = ts::sub(obj_suiv, obj).v < 1e-4 * (robust ? -pred_r.v : ts::sub(dr2, obj).v);  // LevenbergMarquardt.jl:243
     }
     accepted = step_accepted;
     const TS nd = norm_of(h_sh[SH_DELTA_P] + h_rp[RP_DELTA_C], delta_w);

@@ -40,16 +40,54 @@ struct SchurChunk {
   int64_t nkeys = 0, nskeys = 0;
 };
 
-// up to six sums of squares in one launch pair (launch_sumsq_multi): vector, length, destination array and slot; the
-// second kernel (one workgroup) can also publish the controller's scalars to pinned host memory once every sum is in place
+// c^2 rho(s / c^2) of one observation's squared reprojection error s, and w = rho'(s / c^2) (robust loss, ba_lm_set_loss; c2 =
+// c^2).  scipy's functions (least_squares, loss=...), applied per observation.  Inlined everywhere: log1p / atan / sqrt in double
+// are ocml code, no call (tests/test_code_objects.py)
+__device__ __forceinline__ double robust_rho(int kind, double s, double c2, double *w) {
+  const double z = s / c2;
+  switch (kind) {
+    case BA_LOSS_HUBER:
+      if (z <= 1.0) {
+        *w = 1.0;
+        return c2 * z;
+      } else {
+        const double sz = sqrt(z);
+        *w = 1.0 / sz;
+        return c2 * (2.0 * sz - 1.0);
+      }
+    case BA_LOSS_SOFT_L1: {
+      const double t = sqrt(1.0 + z);
+      *w = 1.0 / t;
+      return c2 * (2.0 * z / (t + 1.0));  // = 2 (sqrt(1 + z) - 1) without the cancellation
+    }
+    case BA_LOSS_CAUCHY:
+      *w = 1.0 / (1.0 + z);
+      return c2 * log1p(z);
+    case BA_LOSS_ARCTAN:
+      *w = 1.0 / (1.0 + z * z);
+      return c2 * atan(z);
+    default:
+      *w = 1.0;
+      return s;
+  }
+}
+
+// up to six sums in one launch pair (launch_sumsq_multi): vector, length, destination array and slot; the second kernel (one
+// workgroup) can also publish the controller's scalars to pinned host memory once every sum is in place.  Kind of a job:
+// SJ_SQUARES sum v_i^2 (n entries); SJ_ROBUST sum c^2 rho(|r_o|^2 / c^2) over n observations of the interleaved residual v
+// under (loss, c2); SJ_SUM sum v_i (n entries: the per-block partials of a kernel of its own, e.g. k_robust_scale)
 constexpr int SUMSQ_JOBS = 6;
+enum { SJ_SQUARES = 0, SJ_ROBUST = 1, SJ_SUM = 2 };
 struct SumsqJobs {
   int count = 0;
   const double *v[SUMSQ_JOBS] = {};
   int64_t n[SUMSQ_JOBS] = {};
   double *out[SUMSQ_JOBS] = {};
   int slot[SUMSQ_JOBS] = {};
+  int kind[SUMSQ_JOBS] = {};
   int nb[SUMSQ_JOBS] = {};  // filled by the launcher
+  int loss = 0;             // SJ_ROBUST jobs: BA_LOSS_* and c^2
+  double c2 = 1.0;
   // publish (optional; as launch_publish): a[0..na) -> ha, b[0..nb2) -> hb, flag[0] -> hflag
   const double *pa = nullptr, *pb = nullptr;
   double *ha = nullptr, *hb = nullptr;
@@ -61,7 +99,18 @@ struct SumsqJobs {
     n[count] = len;
     out[count] = dst;
     slot[count] = s;
+    kind[count] = SJ_SQUARES;
     count++;
+  }
+  void add_robust(const double *r, int64_t nobs, double *dst, int s, int loss_, double c2_) {
+    add(r, nobs, dst, s);
+    kind[count - 1] = SJ_ROBUST;
+    loss = loss_;
+    c2 = c2_;
+  }
+  void add_sum(const double *vals, int64_t len, double *dst, int s) {
+    add(vals, len, dst, s);
+    kind[count - 1] = SJ_SUM;
   }
   void publish(const double *a, int na_, double *h_a, const double *b, int nb_, double *h_b, const int *flag, int *h_flag) {
     pa = a; na = na_; ha = h_a; pb = b; nb2 = nb_; hb = h_b; pflag = flag; hflag = h_flag;
@@ -126,6 +175,11 @@ int launch_sumsq(ba_problem *p, int64_t n, const double *d_v, double *d_partial,
 int launch_publish(const double *d_a, int na, double *h_a, const double *d_b, int nb, double *h_b, const int *d_flag, int *h_flag,
                    hipStream_t st);
 int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi /* SUMSQ_JOBS RED_BLOCKS */, hipStream_t st);
+// robust loss (ba_robust_kernels.hip): r <- sqrt(w) r and J <- sqrt(w) J per observation, in place (w = rho'(z) under the
+// handle's loss); d_w (optional) <- w.  Per-block partials of sum c^2 rho(z) at d_partial[0, nb) and of |r~|^2 at
+// d_partial[RED_BLOCKS, RED_BLOCKS + nb), nb = robust_blocks(nobs): a fixed grid, so a fixed summation tree
+int robust_blocks(int64_t nobs);
+int launch_robust_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, hipStream_t st);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,

@@ -819,7 +819,8 @@ __global__ __launch_bounds__(BLK) void k_sum_partials(int np, const double *__re
 }
 
 // Several sums of squares in ONE launch pair (the LM loop needs |r|^2, |gp|^2, |x_p|^2 ... one after the other: on small
-// problems every one of those two-kernel launches costs more in launch latency than in work).  Vector v owns the blocks
+// problems every one of those two-kernel launches costs more in launch latency than in work).  (A job may also be the robust
+// cost of a residual vector or a plain sum of partials: SumsqJobs::kind.)  Vector v owns the blocks
 // [v RED_BLOCKS, v RED_BLOCKS + nb_v) and sums exactly what k_sumsq would with a grid of nb_v blocks; the second kernel is
 // k_sum_partials per vector, one after the other in ONE workgroup: the results are bit-identical to the separate launches.
 __global__ __launch_bounds__(BLK) void k_sumsq_multi(SumsqJobs jobs, double *__restrict__ partial) {
@@ -830,7 +831,18 @@ __global__ __launch_bounds__(BLK) void k_sumsq_multi(SumsqJobs jobs, double *__r
   const double *__restrict__ x = jobs.v[v];
   const int64_t n = jobs.n[v];
   double acc = 0;
-  for (int64_t i = (int64_t)b * BLK + threadIdx.x; i < n; i += (int64_t)nb * BLK) acc += x[i] * x[i];
+  if (jobs.kind[v] == SJ_SQUARES) {
+    for (int64_t i = (int64_t)b * BLK + threadIdx.x; i < n; i += (int64_t)nb * BLK) acc += x[i] * x[i];
+  } else if (jobs.kind[v] == SJ_ROBUST) {  // n observations: one 16-byte residual pair per lane
+    const double2 *__restrict__ x2 = reinterpret_cast<const double2 *>(x);
+    for (int64_t o = (int64_t)b * BLK + threadIdx.x; o < n; o += (int64_t)nb * BLK) {
+      const double2 e = x2[o];
+      double w;
+      acc += robust_rho(jobs.loss, e.x * e.x + e.y * e.y, jobs.c2, &w);
+    }
+  } else {
+    for (int64_t i = (int64_t)b * BLK + threadIdx.x; i < n; i += (int64_t)nb * BLK) acc += x[i];
+  }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();

@@ -55,10 +55,19 @@ def _sym(s):
 def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=None, facto_type=None,
                         restol=None, satol=None, srtol=None, oatol=None, ortol=None, atol=None, rtol=None,
                         nu_d=None, nu_m=None, lam=None, delta_d=None, ite_max=None, max_time=None, verbose=False,
-                        log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None):
+                        log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0):
     """x_device_ptr (an extension for device-resident callers, e.g. bench.py): the address of nvar doubles of DEVICE memory
     holding x0; the loop then runs through ba_lm_solve_dev -- no host copy of the iterate on either side -- the solution
-    stays there and `solution` of the result is None."""
+    stays there and `solution` of the result is None.
+
+    loss / f_scale (an extension, scipy's least_squares names): minimise f = 1/2 sum_i c^2 rho(|r_i|^2 / c^2) over the
+    observations i, c = f_scale in pixels, rho one of "linear" (the default: 1/2 |r|^2, the reference's objective), "huber",
+    "soft_l1", "cauchy", "arctan" (":huber" symbols are accepted).  The step is the reweighted (IRLS) one, see ba_lm_set_loss
+    in include/ba_hip.h; `objective`, the log's f and |J'r| are then the robust f and its gradient norm.  Not with linesearch
+    = True, a Float32 model or facto_type = Float16 (ValueError)."""
+    kind, c = _lib.loss_code(loss, f_scale)
+    if kind != 0 and linesearch:
+        raise ValueError("a robust loss is not supported with linesearch = true")
     facto, perm, normalize = _sym(facto), _sym(perm), _sym(normalize)
     if facto not in _FACTO:
         raise ValueError(f"facto must be :QR, :LDL or :PCG (extension: matrix-free CG on the reduced camera system), got {facto!r}")
@@ -91,6 +100,8 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
         raise ValueError("facto = :PCG has its own scaling (block-Jacobi preconditioner): normalize must be :None")
     if facto == "PCG" and facto_type is not None and ft == 1 and not xf32:
         raise ValueError("facto = :PCG runs in Float64: facto_type = Float32 belongs to the direct branches")
+    if kind != 0 and (xf32 or ft == 2):
+        raise ValueError("a robust loss is not supported for a Float32 model or with facto_type = Float16")
 
     def d(v):
         return -1.0 if v is None else float(v)
@@ -108,6 +119,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
         rows.append((it, f, df, njtr, lmb, nd, rho, bool(acc)))
 
     cb = _lib.LOG_CB(_cb) if log else C.cast(None, _lib.LOG_CB)
+    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))  # every call: one without loss= runs the plain objective
     if x_device_ptr is not None:
         _lib.check(_lib.lib().ba_lm_solve_dev(nlp.handle, C.byref(o), C.c_void_p(int(x_device_ptr)), C.byref(st), cb, None))
     else:
@@ -127,11 +139,14 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     return out
 
 
-def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None):
+def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0):
     """One linear LM step from (x, lambda): delta, 1/2|J delta + r|^2, J'r  (ba_lm_step; facto_type=np.float32:
     ba_lm_step_f32, the reduced camera system factored in Float32 as src/lm.jl:170-173 does; pcg=(tol, max_iter):
-    ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result)."""
+    ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result).
+    loss / f_scale (see Levenberg_Marquardt; None = "linear"): the reweighted step, 1/2|J~ delta + r~|^2 and J~'r~."""
+    kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
     x = np.ascontiguousarray(x, dtype=np.float64)
+    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
     delta = np.empty(nlp.meta.nvar)
     jtr = np.empty(nlp.meta.nvar) if want_jtr else None
     half = C.c_double(0)

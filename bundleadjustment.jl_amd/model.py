@@ -169,6 +169,21 @@ class BALNLPModel:
         _lib.check(_lib.lib().ba_jtr(self._h, _lib.ptr(vals), _lib.ptr(r), _lib.ptr(out)))
         return out
 
+    # -- robust loss (an extension) -------------------------------------------------------------------------------
+    def robust_weights(self, x, loss, f_scale=1.0):
+        """(weights, cost) at x under a robust loss (ba_robust_eval): weights[i] = rho'(|r_i|^2 / c^2) per observation (a
+        weight below 1 marks an observation the loss discounts: an outlier candidate after a solve), cost = f(x) =
+        1/2 sum_i c^2 rho(|r_i|^2 / c^2); c = f_scale.  Sets the handle's loss, as every LM call does."""
+        kind, c = _lib.loss_code(loss, f_scale)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.meta.nvar,):
+            raise ValueError(f"x has length {x.shape}, expected {self.meta.nvar}")
+        _lib.check(_lib.lib().ba_lm_set_loss(self._h, kind, c))
+        w = np.empty(self.nobs)
+        cost = C.c_double(0)
+        _lib.check(_lib.lib().ba_robust_eval(self._h, _lib.ptr(x), _lib.ptr(w), C.byref(cost)))
+        return w, cost.value
+
     # -- per-kernel timing ---------------------------------------------------------------------------------------
     def profile(self, on=True):
         _lib.check(_lib.lib().ba_profile_enable(self._h, int(on)))

@@ -160,8 +160,8 @@ typedef struct ba_lm_stats {
   int n_accepted, n_rejected;
   int n_residual, n_jacobian, n_factor;
   int n_cg;    /* facto = 2: CG iterations over the whole solve */
-  double objective;    /* 1/2 |r|^2 at the returned x */
-  double dual_feas;    /* |J' r| (lm.jl:415; primal_feas in the old variant, LevenbergMarquardt.jl:384) */
+  double objective;    /* 1/2 |r|^2 at the returned x (robust loss: f, see ba_lm_set_loss) */
+  double dual_feas;    /* |J' r| (lm.jl:415; primal_feas in the old variant, LevenbergMarquardt.jl:384; robust loss: |J~'r~|) */
   double lambda_final;
   double elapsed_s;    /* whole call, host wall clock */
   double loop_s;       /* the while-loop only (what iter / time is quoted on) */
@@ -172,7 +172,8 @@ typedef struct ba_lm_stats {
 typedef void (*ba_log_cb)(void *ctx, int iter, double f, double df, double norm_jtr, double lambda,
                           double norm_delta, double rho, int accepted);
 
-/* x_inout: nvar doubles, x0 in, solution out (the `x=` keyword of src/lm.jl:20). */
+/* x_inout: nvar doubles, x0 in, solution out (the `x=` keyword of src/lm.jl:20).  Minimises under the handle's loss
+ * (ba_lm_set_loss; default linear, 1/2 |r|^2). */
 int ba_lm_solve(ba_problem *p, const ba_lm_opts *opts, double *x_inout, ba_lm_stats *stats, ba_log_cb cb,
                 void *cb_ctx);
 /* the same with the iterate resident on the device (d_x_inout: nvar doubles of device memory, e.g. from ba_dev_malloc): no
@@ -224,14 +225,17 @@ int ba_comm_stats_ops(ba_problem *p, int64_t *calls, int64_t *bytes);
 
 /* ---- single linear step, exposed for parity tests and profiling ------------------------------------
  * From (x, lambda): delta (nvar) solving (J'J + lambda I) delta = -J' r, and pred2 = 1/2 |J delta + r|^2
- * (== 1/2 |delta_r|^2 of the reference's augmented solve, src/lm.jl:229). */
+ * (== 1/2 |delta_r|^2 of the reference's augmented solve, src/lm.jl:229).
+ * Under a robust loss of the handle (ba_lm_set_loss) J and r are the reweighted J~ and r~: delta solves
+ * (J~'J~ + lambda I) delta = -J~'r~, half_sq_model = 1/2 |J~ delta + r~|^2 and jtr = J~'r~ (the gradient of the robust f). */
 int ba_lm_step(ba_problem *p, const double *x, double lambda, double *delta, double *half_sq_model,
                double *jtr /* nvar or NULL */);
 /* the same step with facto_type = Float32 (src/lm.jl:170-173, src/diffprecsions.jl:39-41): the reduced camera system is
- * rounded to Float32, factored and solved there; everything else stays Float64 */
+ * rounded to Float32, factored and solved there; everything else stays Float64.  Robust loss: as ba_lm_step (J~, r~) */
 int ba_lm_step_f32(ba_problem *p, const double *x, double lambda, double *delta, double *half_sq_model,
                    double *jtr /* nvar or NULL */);
-/* the same step by facto = PCG (see ba_lm_opts.facto): tol / max_iter as pcg_tol / pcg_max_iter; cg_iters_out may be NULL */
+/* the same step by facto = PCG (see ba_lm_opts.facto): tol / max_iter as pcg_tol / pcg_max_iter; cg_iters_out may be NULL.
+ * Robust loss: as ba_lm_step (J~, r~) */
 int ba_lm_step_pcg(ba_problem *p, const double *x, double lambda, double tol, int max_iter, double *delta,
                    double *half_sq_model, double *jtr, int *cg_iters_out);
 
@@ -264,6 +268,27 @@ int ba_schur_ordering(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t 
                       int method, int64_t *perm1, double *tile_fill, double *flop_fill, double *block_fill);
 int ba_lm_set_ordering(ba_problem *p, int method);
 int ba_lm_schur_ordering(ba_problem *p, int64_t *perm1, const char **name);
+
+/* ---- robust loss (an extension: the reference minimises 1/2 |r|^2 only) ------------------------------------------
+ * Observation i with the 2-vector residual r_i: s_i = |r_i|^2, z_i = s_i / c^2 (c = scale > 0, pixels: scipy's f_scale),
+ * f(x) = 1/2 sum_i c^2 rho(z_i) -- the loss acts on each observation's squared reprojection error, as Ceres' LossFunction
+ * does.  rho is scipy's function of the same name: linear z; huber z (z <= 1), 2 sqrt(z) - 1; soft_l1 2 (sqrt(1 + z) - 1);
+ * cauchy log1p(z); arctan atan(z).  The LM step is linearised in the first-order (IRLS) form: with w_i = rho'(z_i),
+ * r~_i = sqrt(w_i) r_i and J~_i = sqrt(w_i) J_i, so J~'r~ = grad f, and the step solves (J~'J~ + lambda I) delta = -J~'r~
+ * (normalize :J / :A scale the columns of J~).  The controller takes ared = f(x) - f(x + delta), pred = 1/2 |r~|^2 -
+ * 1/2 |J~ delta + r~|^2; its log's f and |J'r|, stats.objective and stats.dual_feas are the robust f and |J~'r~|.
+ *   ba_lm_set_loss : the loss of the handle's next ba_lm_solve / ba_lm_solve_dev / ba_lm_step / _f32 / _pcg (default
+ *                    BA_LOSS_LINEAR, which runs exactly the unweighted path).  kind outside BA_LOSS_*, a scale that is not
+ *                    finite or <= 0: BA_ERR_ARG.  ba_lm_solve refuses a non-linear loss together with linesearch = 1,
+ *                    x_f32 = 1 or facto_type = Float16 (BA_ERR_ARG).
+ *   ba_lm_get_loss : what the handle holds.
+ *   ba_robust_eval : at x, the weights rho'(z_i) (nobs, the caller's observation order; a weight below 1 marks an observation
+ *                    the loss discounts) and f, both under the handle's loss; either output may be NULL.  On a shard (see
+ *                    multi-GPU) the local observations only: f is this rank's part of the sum. */
+enum { BA_LOSS_LINEAR = 0, BA_LOSS_HUBER, BA_LOSS_SOFT_L1, BA_LOSS_CAUCHY, BA_LOSS_ARCTAN };
+int ba_lm_set_loss(ba_problem *p, int kind, double scale);
+int ba_lm_get_loss(const ba_problem *p, int *kind, double *scale);
+int ba_robust_eval(ba_problem *p, const double *x, double *weights /* nobs or NULL */, double *cost /* or NULL */);
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -8,6 +8,16 @@ include("BALHIP.jl")
 
 _tol(v) = v === nothing ? -1.0 : Float64(v)   # negative = "the variant's eps-derived default" (include/ba_hip.h)
 
+# robust loss (an extension, scipy's least_squares names): f = 1/2 sum_i c^2 rho(|r_i|^2 / c^2), c = f_scale (pixels);
+# include/ba_hip.h, ba_lm_set_loss.  Set on the handle at every call: a call without `loss` runs the plain objective.
+const BA_LOSSES = (:linear, :huber, :soft_l1, :cauchy, :arctan)
+function _ba_set_loss(nlp, loss :: Symbol, f_scale :: Real)
+  k = findfirst(==(loss), BA_LOSSES)
+  k === nothing && error("loss must be one of $(BA_LOSSES)")
+  (isfinite(f_scale) && f_scale > 0) || error("f_scale must be finite and > 0")
+  bacheck(ccall((:ba_lm_set_loss, libba), Cint, (Ptr{Cvoid}, Cint, Cdouble), nlp.handle, Cint(k - 1), Float64(f_scale)))
+end
+
 # one log row per iteration, the reference's columns (src/lm.jl:120-121,304)
 function _ba_log_row(ctx :: Ptr{Cvoid}, iter :: Cint, f :: Cdouble, df :: Cdouble, njtr :: Cdouble, lambda :: Cdouble,
                      ndelta :: Cdouble, rho :: Cdouble, acc :: Cint) :: Cvoid
@@ -17,7 +27,8 @@ end
 
 function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normalize :: Symbol, linesearch :: Bool,
                 x :: AbstractVector, facto_type :: DataType, restol, satol, srtol, oatol, ortol, atol, rtol, νd, νm, λ, δd,
-                ite_max :: Int, max_time :: Real, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1)
+                ite_max :: Int, max_time :: Real, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
+                loss :: Symbol = :linear, f_scale :: Real = 1.0)
   # :PCG is an extension of the HIP path (no counterpart in the reference): matrix-free conjugate gradients on the reduced
   # camera system, include/ba_hip.h, ba_lm_opts.facto
   facto in (:QR, :LDL, :PCG) || error("facto must be :QR, :LDL or :PCG")
@@ -34,6 +45,8 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
                ite_max, 0, T == Float32 ? 1 : 0, _tol(restol), _tol(satol), _tol(srtol), _tol(oatol), _tol(ortol),
                _tol(atol), _tol(rtol), _tol(νd), _tol(νm), _tol(λ), _tol(δd), Float64(max_time), Float64(pcg_tol),
                Cint(pcg_max_iter), Cint(perm == :Metis ? 1 : 0))
+  (loss != :linear && linesearch) && error("a robust loss is not supported with linesearch = true")
+  _ba_set_loss(nlp, loss, f_scale)
   st = BaLmStats()
   xd = Vector{Float64}(x)               # the ABI carries the iterate as doubles (exact for Float32 values)
   cb = @cfunction(_ba_log_row, Cvoid, (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cint))
@@ -63,9 +76,10 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              x :: AbstractVector = copy(model.meta.x0), facto_type :: DataType = eltype(x),
                              restol = nothing, satol = nothing, srtol = nothing, oatol = nothing, ortol = nothing,
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
-                             ite_max :: Int = 200, max_time :: Int = 3600, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1)
+                             ite_max :: Int = 200, max_time :: Int = 3600, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
+                             loss :: Symbol = :linear, f_scale = 1.0)
   return _ba_lm(model, 1, facto, perm, normalize, linesearch, x, facto_type, restol, satol, srtol, oatol, ortol, atol, rtol,
-                νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter)
+                νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter, loss, f_scale)
 end
 
 "src/LevenbergMarquardt.jl:16-26 -- the 4-argument method src/solve_ba.jl:26 calls (no linesearch, no facto_type)"
@@ -73,7 +87,7 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              x :: AbstractVector = copy(model.meta.x0),
                              restol = nothing, satol = nothing, srtol = nothing, oatol = nothing, ortol = nothing,
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
-                             ite_max :: Int = 100)
+                             ite_max :: Int = 100, loss :: Symbol = :linear, f_scale = 1.0)
   return _ba_lm(model, 0, facto, perm, normalize, false, x, eltype(x), restol, satol, srtol, oatol, ortol, atol, rtol,
-                νd, νm, λ, δd, ite_max, 3600)
+                νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale)
 end
