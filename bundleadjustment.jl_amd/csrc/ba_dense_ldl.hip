@@ -45,15 +45,13 @@ struct RT<float> {
 };
 #define BA_VT typedef typename RT<T>::v4 d4; typedef typename RT<T>::v2 d2;
 
-#ifndef BA_LDL_NT_C
-#define BA_LDL_NT_C 0
-#endif
-constexpr int NT_C = BA_LDL_NT_C;  // 1: bulk update reads / writes its C tiles non-temporally (measured neutral: 38.97 vs 39.0 ms at n = 16002)
+// (The bulk update's C tiles read / written non-temporally were measured neutral and removed: 38.97 vs 39.0 ms per LM
+// iteration at n = 16002, kernel 0.511 against 0.505 ms.)
 constexpr int KC = 16;       // K chunk of the GEMM kernels staged through LDS
 constexpr int LDK = KC + 2;  // row stride 36 dwords: 36i+2k hit distinct banks for the MFMA operand reads
-constexpr int DBUF = 0;  // 1: two LDS chunk buffers + one barrier per chunk; 0: one buffer + two barriers (measured faster:
-                         // 54.4 vs 52.3 TFLOP/s on the pair update, the barrier is not the limiter and 2x LDS costs occupancy slack)
-constexpr size_t GEMM_LDS_ELEMS = (size_t)(DBUF ? 2 : 1) * 2 * NB * LDK;
+// one LDS chunk buffer + two barriers per chunk (two buffers + one barrier measured slower: 52.3 vs 54.4 TFLOP/s on the pair
+// update, the barrier is not the limiter and 2x LDS costs occupancy slack)
+constexpr size_t GEMM_LDS_ELEMS = (size_t)2 * NB * LDK;
 
 
 // ---- diagonal tile ---------------------------------------------------------------------------------------------
@@ -68,10 +66,7 @@ constexpr size_t GEMM_LDS_ELEMS = (size_t)(DBUF ? 2 : 1) * 2 * NB * LDK;
 constexpr int LDA2 = 130;  // row stride 260 dwords = 4 mod 64: conflict-free MFMA operand reads
 constexpr int XDL = 18;
 constexpr int L16S = 18;   // row stride of the 16x16 multiplier block: 16-byte aligned rows for the row solves' paired reads
-#ifndef BA_DIAG_THREADS
-#define BA_DIAG_THREADS 512
-#endif
-constexpr int DIAG_THREADS = BA_DIAG_THREADS;  // k_ldl_diag: eight waves, two per SIMD (see diag_tile)
+constexpr int DIAG_THREADS = 512;  // k_ldl_diag: eight waves, two per SIMD (see diag_tile)
 constexpr size_t DIAG_LDS_ELEMS = (size_t)(NB * LDA2 + 8 * 16 * XDL + 2 * NB + 16 * L16S);
 
 // broadcast lane `src` (a compile-time constant after unrolling) of v to the whole wave: v_readlane_b32 into SGPRs
@@ -567,9 +562,8 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_ldl_diag2(T *__restrict__ SkkA
 // ---- 128 x 128 x (128 NP) tile product C = sum_p A_p * B_p' on the matrix cores ------------------------------------
 // A_p, B_p: contiguous row-major 128x128 tiles in global memory.  256 threads = 4 waves, wave w owns the 64x64
 // quadrant (w >> 1, w & 1) as 4x4 MFMA blocks (128 accumulator VGPRs).  K is consumed in chunks of KC = 16 staged
-// through two LDS buffers (row stride 18 doubles: conflict-free operand reads), one barrier per chunk: while chunk c is
-// multiplied, chunk c+1 moves registers -> other buffer and the global loads of chunk c+2 are in flight; two
-// workgroups per CU cover each other's barriers.
+// through one LDS buffer (row stride 18 doubles: conflict-free operand reads), two barriers per chunk: while chunk c is
+// multiplied, the global loads of chunk c+1 are in flight; two workgroups per CU cover each other's barriers.
 // YACC (forward substitution fused into the panel solve): threads 0..127 also accumulate yacc = sum_k B0[tid][k] bk[k]
 // from the B chunks as they pass through LDS.
 template <typename T, int NP, bool YACC = false>
@@ -591,36 +585,15 @@ __device__ inline void tile_gemm_abt(const T *__restrict__ A0, const T *__restri
     pb[it] = *reinterpret_cast<const d2 *>(B0 + (lrow + RPS * it) * NB + 2 * lc2);
   }
   constexpr int NCH = NP * (NB / KC);
-  constexpr int BUF = DBUF ? 2 * NB * LDK : 0;  // doubles per LDS buffer (A | B); sA/sB point at buffer 0
-  if (DBUF) {  // prologue: chunk 0 -> buffer 0, chunk 1 -> registers
+  for (int ch = 0; ch < NCH; ch++) {
+    __syncthreads();  // everybody has finished reading the previous chunk
 #pragma unroll
-    for (int it = 0; it < NLD; it++) {
+    for (int it = 0; it < NLD; it++) {  // registers -> LDS
       *reinterpret_cast<d2 *>(sA + (lrow + RPS * it) * LDK + 2 * lc2) = pa[it];
       *reinterpret_cast<d2 *>(sB + (lrow + RPS * it) * LDK + 2 * lc2) = pb[it];
     }
-    if (NCH > 1) {
-#pragma unroll
-      for (int it = 0; it < NLD; it++) {
-        pa[it] = *reinterpret_cast<const d2 *>(A0 + (lrow + RPS * it) * NB + KC + 2 * lc2);
-        pb[it] = *reinterpret_cast<const d2 *>(B0 + (lrow + RPS * it) * NB + KC + 2 * lc2);
-      }
-    }
-  }
-  for (int ch = 0; ch < NCH; ch++) {
-    // DBUF: buffer ch&1 is complete and everybody has finished reading the other one.  Single buffer: everybody has
-    // finished reading the previous chunk.
     __syncthreads();
-    T *cA = sA + (ch & 1) * BUF, *cB = sB + (ch & 1) * BUF;
-    if (DBUF ? (ch + 1 < NCH) : true) {  // registers -> LDS (DBUF: chunk ch+1 into the other buffer, overlapping the MFMAs)
-      T *nA = sA + ((ch + 1) & 1) * BUF, *nB = sB + ((ch + 1) & 1) * BUF;
-#pragma unroll
-      for (int it = 0; it < NLD; it++) {
-        *reinterpret_cast<d2 *>(nA + (lrow + RPS * it) * LDK + 2 * lc2) = pa[it];
-        *reinterpret_cast<d2 *>(nB + (lrow + RPS * it) * LDK + 2 * lc2) = pb[it];
-      }
-    }
-    if (!DBUF) __syncthreads();
-    const int nx = ch + (DBUF ? 2 : 1);
+    const int nx = ch + 1;
     if (nx < NCH) {  // next chunk -> registers, in flight while this chunk is multiplied
       const T *A = (NP == 2 && nx >= NB / KC) ? A1 : A0;
       const T *B = (NP == 2 && nx >= NB / KC) ? B1 : B0;
@@ -635,7 +608,7 @@ __device__ inline void tile_gemm_abt(const T *__restrict__ A0, const T *__restri
       if (tid < NB) {
         T ya = *yacc;
 #pragma unroll
-        for (int q = 0; q < KC; q++) ya += cB[tid * LDK + q] * bk[ch * KC + q];
+        for (int q = 0; q < KC; q++) ya += sB[tid * LDK + q] * bk[ch * KC + q];
         *yacc = ya;
       }
     }
@@ -643,9 +616,9 @@ __device__ inline void tile_gemm_abt(const T *__restrict__ A0, const T *__restri
     for (int kk = 0; kk < KC / 4; kk++) {
       T af[4], bf[4];
 #pragma unroll
-      for (int m = 0; m < 4; m++) af[m] = cA[(wr + 16 * m + fr) * LDK + kk * 4 + fk];
+      for (int m = 0; m < 4; m++) af[m] = sA[(wr + 16 * m + fr) * LDK + kk * 4 + fk];
 #pragma unroll
-      for (int n = 0; n < 4; n++) bf[n] = cB[(wc + 16 * n + fr) * LDK + kk * 4 + fk];
+      for (int n = 0; n < 4; n++) bf[n] = sB[(wc + 16 * n + fr) * LDK + kk * 4 + fk];
 #pragma unroll
       for (int m = 0; m < 4; m++)
 #pragma unroll
@@ -1286,7 +1259,7 @@ __device__ __forceinline__ void ldl_update_tile(T *__restrict__ S, const int64_t
 #pragma unroll
       for (int m = 0; m < 4; m++)
 #pragma unroll
-        for (int g = 0; g < 4; g++) cv[n2][m][g] = NT_C ? __builtin_nontemporal_load(&cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)]) : cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)];
+        for (int g = 0; g < 4; g++) cv[n2][m][g] = cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)];
 #pragma unroll
     for (int n2 = 0; n2 < 2; n2++)
 #pragma unroll
@@ -1294,8 +1267,7 @@ __device__ __forceinline__ void ldl_update_tile(T *__restrict__ S, const int64_t
 #pragma unroll
         for (int g = 0; g < 4; g++) {
           const T nv = cv[n2][m][g] - acc[m][2 * h + n2][g];
-          if (NT_C) __builtin_nontemporal_store(nv, &cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)]);
-          else cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)] = nv;
+          cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)] = nv;
         }
   }
 }
@@ -1839,8 +1811,7 @@ static int launch_col(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0, hipStr
 // is final (hoisted-diagonal schedule)
 // tiles up to which the pair update takes its row-split form (BA_LDL_UPDATE_RS_MAX; 0 disables)
 static int update_rs_max() {
-  const char *e = getenv("BA_LDL_UPDATE_RS_MAX");  // read per call: a test compares the two kernels in one process
-  return e ? atoi(e) : 320;
+  return env_int("BA_LDL_UPDATE_RS_MAX", 320);  // read per call: a test compares the two kernels in one process
 }
 
 template <typename T>
@@ -1864,10 +1835,9 @@ static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, int base, const T 
   // (Cutting the tiles of a partly filled last round into 64 x 64 quadrants, one workgroup each, was tried and removed:
   // 34.1-34.3 ms against 33.9-34.1 at n = 16 002.  A partial round does not cost a full one -- the quadrant kernel took
   // 39 us on average, which is what the big kernel's own last round costs.)
-  static const int blocked = [] { const char *e = getenv("BA_LDL_TRI_BLOCKED"); return e ? atoi(e) : TSB; }();
   hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S,
                      w->col_off, V0, V1, k, base, nt, nblk, ready, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
-                     ready_tiles, (const int *)nullptr, (const T *)nullptr, (const T *)nullptr, (const int2 *)nullptr, blocked);
+                     ready_tiles, (const int *)nullptr, (const T *)nullptr, (const T *)nullptr, (const int2 *)nullptr, TSB);
   return BA_OK;
 }
 
@@ -1926,7 +1896,7 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_p
   // the hoisted 59 us per pair grow as nt.  Measured: n = 16002 (nt 126) 37.1 -> 35.6 ms, n = 40000 (nt 313) 411 -> 418 ms;
   // the model's break-even is nt ~ 250.
   constexpr int HOIST_MAX_TILES = 224;
-  static const bool hoist_off = [] { const char *e = getenv("BA_LDL_HOIST"); return e && e[0] == '0'; }();
+  static const bool hoist_off = env_off("BA_LDL_HOIST");
   w->hoisting = !p->prof_on && !hoist_off && !w->hoist_disabled && !p->comm.active() && nt >= HOIST_MIN_TILES + 2 && nt <= HOIST_MAX_TILES;
   // the pivot flag: hoisted kernels read it (an earlier tile gave up) before tile 0 is factored -- cleared ahead of the
   // fork; in order, the first diagonal kernel clears it
@@ -1943,9 +1913,9 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_p
   // row-parallel kernel.  It pays while that update is long enough to hide the ~190 us of the hoisted workgroup (two
   // diagonal tiles and two 128^3 products in sequence): FUSE_MIN_TILES tile rows.  Shorter updates keep round 1's schedule
   // (one hoisted diagonal tile down to HOIST_MIN_TILES, strictly in order below that).  BA_LDL_FUSE=0 disables.
-  static const int fuse_min = [] { const char *e = getenv("BA_LDL_FUSE_MIN"); return e ? atoi(e) : 48; }();
-  static const bool fuse_off = [] { const char *e = getenv("BA_LDL_FUSE"); return e && e[0] == '0'; }();
-  auto fused = [&](int k) { return w->hoisting && !fuse_off && k >= 2 && k + 1 < nt && nt - k >= fuse_min; };
+  constexpr int FUSE_MIN_TILES = 48;
+  static const bool fuse_off = env_off("BA_LDL_FUSE");
+  auto fused = [&](int k) { return w->hoisting && !fuse_off && k >= 2 && k + 1 < nt && nt - k >= FUSE_MIN_TILES; };
   launch_diag(p, w, 0, st, nullptr, !w->hoisting);
   for (int k = 0, q = 0; k < nt; k += 2, q ^= 1) {
     T *V0 = Vs[q][0], *V1 = Vs[q][1];
@@ -2127,10 +2097,10 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
   const int npairs = (nt + 1) / 2;
   T *y = w->D + w->nt * NB;
   w->hoisting = false;
-  const char *la_env = getenv("BA_SPARSE_LOOKAHEAD");  // read per call: tests compare both schedules in one process
-  const bool lookahead = !p->prof_on && !(la_env && la_env[0] == '0');
-  const int la_min = [] { const char *e = getenv("BA_SPARSE_LOOKAHEAD_MIN"); return e ? atoi(e) : 96; }();  // (read per call: the tests force it to 1)
-  static const int rest_cus = [] { const char *e = getenv("BA_SPARSE_REST_CUS"); return e ? atoi(e) : 224; }();  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
+  // read per call: tests compare both schedules in one process, and force the minimum to 1
+  const bool lookahead = !p->prof_on && !env_off("BA_SPARSE_LOOKAHEAD");
+  const int la_min = env_int("BA_SPARSE_LOOKAHEAD_MIN", 96);
+  constexpr int REST_CUS = 224;  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
   bool pending[2] = {false, false};  // rest of pair q (slot q & 1) launched on the second stream and not yet joined
   auto join_rest = [&](int slot) -> int {
     if (pending[slot]) {
@@ -2201,8 +2171,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
   // index order.  Each tile still receives its updates in ascending pair order WITHIN a run; the frontier's tiles receive the
   // second run's updates before the late pairs of the first -- a different but fixed summation order
   // (BA_SPARSE_TWO_RUNS=0: one chain; never with per-kernel profiling, whose classes time single-run launches).
-  const char *tc_env = getenv("BA_SPARSE_TWO_RUNS");
-  const bool two = pat->a_clean > 0 && pat->b_clean > 0 && !p->prof_on && !(tc_env && tc_env[0] == '0');
+  const bool two = pat->a_clean > 0 && pat->b_clean > 0 && !p->prof_on && !env_off("BA_SPARSE_TWO_RUNS");
   std::vector<int> order;
   if (two) {
     BA_HIP_CHECK(hipMemsetAsync(w->flag, 0, sizeof(int), st));  // (no diagonal kernel of the two runs clears the pivot flag)
@@ -2253,7 +2222,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
         BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
         const RunPanel<T> qa2 = panel_of(ka, VA, w->prow + la + 1 + nla), qb2 = panel_of(kb, VB, w->prow + lb + 1 + nlb);
         const int ntile = rest_a + rest_b;
-        hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3((ntile + 1) / 2 < rest_cus ? (ntile + 1) / 2 : rest_cus), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
+        hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3((ntile + 1) / 2 < REST_CUS ? (ntile + 1) / 2 : REST_CUS), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
                            qa2, rest_a, qb2, rest_b, panel);
         BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
         pending[slot] = true;
@@ -2305,7 +2274,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
       BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
       {
         const int nblk = nrest * (nrest + 1) / 2;
-        hipLaunchKernelGGL(k_ldl_update_part<T>, dim3((nblk + 1) / 2 < rest_cus ? (nblk + 1) / 2 : rest_cus), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
+        hipLaunchKernelGGL(k_ldl_update_part<T>, dim3((nblk + 1) / 2 < REST_CUS ? (nblk + 1) / 2 : REST_CUS), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
                            V0, V1, k, nblk, rows2 + nlead);
       }
       BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
@@ -2516,8 +2485,7 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
   T *Vs[2][2] = {{w->V, w->V + panel}, {w->V + 2 * panel, w->V + 3 * panel}};
   BA_HIP_CHECK(hipMemsetAsync(w->flag, 0, sizeof(int), st));
   w->hoisting = false;
-  const char *la_env = getenv("BA_DIST_LOOKAHEAD");  // read per call: a test flips it between two factorisations of one process
-  const bool la_off = la_env && la_env[0] == '0';
+  const bool la_off = env_off("BA_DIST_LOOKAHEAD");  // read per call: a test flips it between two factorisations of one process
   const int M = (int)w->h_own_cols.size();
   auto own_from = [&](int base) {  // index of the first owned tile column >= base
     return (int)(std::lower_bound(w->h_own_cols.begin(), w->h_own_cols.end(), base) - w->h_own_cols.begin());
@@ -2728,11 +2696,10 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
         hipLaunchKernelGGL(k_bwd_pair<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k, w->lpair + c0);
       }
     };
-    const char *tc_env = getenv("BA_SPARSE_TWO_RUNS");  // (read per call: a test compares the sweeps in one process)
     int c_hi = pat->split + pat->b_clean;
     if (c_hi > 0 && 2 * c_hi - 1 >= nt) c_hi--;  // (a last single row stays with the rows behind the groups)
-    const char *b2_env = getenv("BA_SPARSE_BWD2");
-    if (pat->split > 0 && c_hi > pat->split && !(tc_env && tc_env[0] == '0') && !(b2_env && b2_env[0] == '0')) {
+    // (read per call: a test compares the sweeps in one process)
+    if (pat->split > 0 && c_hi > pat->split && !env_off("BA_SPARSE_TWO_RUNS") && !env_off("BA_SPARSE_BWD2")) {
       for (int q = npairs - 1; q >= c_hi; q--) single(q);
       const int both = std::min(pat->split, c_hi - pat->split);
       for (int i = 0; i < both; i++) {
@@ -2750,13 +2717,11 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
     BA_HIP_CHECK(hipGetLastError());
     return BA_OK;
   }
-  static const bool pair_off = [] { const char *e = getenv("BA_BWD_PAIR"); return e && e[0] == '0'; }();
   int k = nt - 1;
-  if (!pair_off)
-    for (; k >= 1; k -= 2)  // panels k, k-1 per launch; blocks: 1 + (k-1) tile rows below the pair
-      hipLaunchKernelGGL(k_bwd_pair<T>, dim3(k), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k);
-  for (; k >= 0; k--)
-    hipLaunchKernelGGL(k_bwd_step<T>, dim3(k + 1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k);
+  for (; k >= 1; k -= 2)  // panels k, k-1 per launch; blocks: 1 + (k-1) tile rows below the pair
+    hipLaunchKernelGGL(k_bwd_pair<T>, dim3(k), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k);
+  if (k == 0)  // an odd number of tile rows: the first one alone
+    hipLaunchKernelGGL(k_bwd_step<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, 0);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
@@ -2795,12 +2760,11 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   BA_HIP_CHECK(hipEventCreate(&e0));
   BA_HIP_CHECK(hipEventCreate(&e1));
   int zp = 0;
-  const bool fused = getenv("BA_LDL_SEPARATE_FORWARD") == nullptr;
-  for (int attempt = 0; attempt < 2; attempt++) {
+  for (int attempt = 0; attempt < 2; attempt++) {  // (the forward substitution rides along with the factorisation)
     BA_HIP_CHECK(hipEventRecord(e0, st));
-    rc = dense_ldl_factor<T>(&tmp, &w, st, nullptr, fused ? d_b : nullptr);
+    rc = dense_ldl_factor<T>(&tmp, &w, st, nullptr, d_b);
     BA_HIP_CHECK(hipEventRecord(e1, st));
-    if (rc == BA_OK) rc = dense_ldl_solve<T>(&tmp, &w, d_b, st, fused);
+    if (rc == BA_OK) rc = dense_ldl_solve<T>(&tmp, &w, d_b, st, true);
     BA_HIP_CHECK(hipMemcpy(&zp, w.flag, sizeof(int), hipMemcpyDeviceToHost));
     BA_HIP_CHECK(hipDeviceSynchronize());
     if (zp != 2 || w.hoist_disabled) break;

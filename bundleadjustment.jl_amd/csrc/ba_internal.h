@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,17 @@ void ba_set_error(const char *fmt, ...);
     int _rc = (expr);             \
     if (_rc != BA_OK) return _rc; \
   } while (0)
+
+// environment switches: env_off -- the variable is set to a value starting with '0'; env_int -- its value, or
+// dflt when it is not set
+inline bool env_off(const char *name) {
+  const char *e = getenv(name);
+  return e && e[0] == '0';
+}
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // ---- dense reduced-camera system ------------------------------------------------------------------
 // S is stored as the lower block triangle of NB x NB tiles, each tile contiguous row-major (128 KiB).  Tile (i,j),

@@ -135,20 +135,18 @@ int build_tasks(ba_problem *p, SchurTasks *T, const std::vector<int> &pos) {
     // (unsplit: 2.26); Venice-1778 unsplit / 8 / 32 / 128 -> 4.36 / 4.02 / 3.52 / 3.42 ms)
     int ch = 16;
     while (ch < 128 && ntasks / (2 * ch) >= 8192) ch *= 2;
-    if (const char *e = getenv("BA_SCHUR_CHUNK")) ch = atoi(e);  // 0 disables the split
     T->chunk = ch;
     std::vector<int> skey, skey_c0, ct0, ct1;
-    if (ch > 0)
-      for (int64_t k = 0; k < T->nkeys; k++) {
-        const int t0 = key_ptr[(size_t)k], t1 = key_ptr[(size_t)k + 1];
-        if (t1 - t0 <= 2 * ch) continue;
-        skey.push_back((int)k);
-        skey_c0.push_back((int)ct0.size());
-        for (int t = t0; t < t1; t += ch) {
-          ct0.push_back(t);
-          ct1.push_back(t + ch < t1 ? t + ch : t1);
-        }
+    for (int64_t k = 0; k < T->nkeys; k++) {
+      const int t0 = key_ptr[(size_t)k], t1 = key_ptr[(size_t)k + 1];
+      if (t1 - t0 <= 2 * ch) continue;
+      skey.push_back((int)k);
+      skey_c0.push_back((int)ct0.size());
+      for (int t = t0; t < t1; t += ch) {
+        ct0.push_back(t);
+        ct1.push_back(t + ch < t1 ? t + ch : t1);
       }
+    }
     skey_c0.push_back((int)ct0.size());
     T->nsplit = (int64_t)skey.size();
     T->nchunks = (int64_t)ct0.size();
@@ -264,7 +262,7 @@ int launch_convert(const A *in, B *out, int64_t n, hipStream_t st) {
 
 // BA_DIST_FACTOR=0: keep the whole reduced camera system on every rank (one all-reduce of S, replicated factorisation)
 static bool dist_factor_on(ba_problem *p) {
-  static const bool off = [] { const char *e = getenv("BA_DIST_FACTOR"); return e && e[0] == '0'; }();
+  static const bool off = env_off("BA_DIST_FACTOR");
   return p->comm.active() && !off;
 }
 
@@ -1110,8 +1108,7 @@ static bool graphs_allowed(ba_problem *p, LMWorkFull *w) {
   // beside it: only with real streams is that concurrency certain (and the graphs gain nothing at that size)
   // (the block-sparse list schedule never hoists and is bound by its chain of short launches: recorded at any size)
   if (w->ldl.nt >= 34 && !w->use_pattern) return false;  // = HOIST_MIN_TILES + 2 of dense_ldl_factor (above its HOIST_MAX_TILES graphs gain nothing either)
-  const char *e = getenv("BA_LM_GRAPH");
-  return !(e && e[0] == '0');
+  return !env_off("BA_LM_GRAPH");
 }
 
 template <typename F>
@@ -1217,8 +1214,7 @@ static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t s
 // trial write disjoint scalar slots, so one read of the pinned buffers serves both.  If the stopping tests that need the
 // refreshed |J'r| or |x| then end the loop, the prefetched step is dropped (never counted, x untouched).
 static bool can_prefetch_trial(ba_problem *p, LMWorkFull *w, int normalize, bool facto_f32, bool xf32) {
-  const char *e = getenv("BA_LM_PREFETCH");  // read per call: a test compares both forms in one process
-  if ((e && e[0] == '0') || !graphs_allowed(p, w)) return false;
+  if (env_off("BA_LM_PREFETCH") || !graphs_allowed(p, w)) return false;  // read per call: a test compares both forms in one process
   return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && w->g_step[w->parity] &&
          w->g_refresh[w->parity];
 }

@@ -527,7 +527,6 @@ static unsigned jac_grid(ba_problem *p, K kernel, int64_t nobs) {
   if (per_cu == 0) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLK, 0) != hipSuccess || per_cu < 1) per_cu = 2;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu < 1) ncu = 256;
-    if (const char *e = getenv("BA_JAC_BLOCKS_PER_CU")) per_cu = atoi(e) > 0 ? atoi(e) : per_cu;
     if (ncache < 32) cache[ncache++] = Entry{(const void *)kernel, p->device, per_cu, ncu};
   }
   const int64_t need = (nobs + 64 * (BLK / 64) - 1) / (64 * (BLK / 64));

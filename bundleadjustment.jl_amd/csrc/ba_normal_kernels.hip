@@ -60,16 +60,14 @@ __global__ __launch_bounds__(BLK) void k_point_blocks(int64_t npnts, const int *
 }
 
 // ---- camera side: one workgroup per camera, fixed-order tree ----------------------------------------------
-// MODE 0: Hcc (45, packed lower row-major) and gc = B' r (9).   MODE 1: gc only.
-// MODE 2: rhs = sum_a B_a' (A_a u_p(a) - r_a)   (u = U^-1 gp per point).   MODE 3 (PCG product): Hcc_c x_c + lam x_c + sum_a B_a' A_a u_p(a), x in `r`.
-template <int MODE>
+// Hcc (45, packed lower row-major) and gc = B' r (9).  (pnt0, u, lam and opos are not read: the argument list of the light
+// passes that this kernel once carried, now all in k_cam_blocks_st, is kept so that its code stays the same.)
 __global__ __launch_bounds__(BLK) void k_cam_blocks(const int *__restrict__ cam_ptr, const int *__restrict__ cam_obs,
-                                                     const int *__restrict__ pnt0, const double *__restrict__ J,
-                                                     const double *__restrict__ r, const double *__restrict__ u,
-                                                     double *__restrict__ Hcc, double *__restrict__ out9, double lam = 0.0,
-                                                     const int *__restrict__ opos = nullptr) {
-  // opos (MODE 2): the right-hand side of the camera system is written at the camera's block row of S (camera ordering)
-  constexpr int NACC = (MODE == 0) ? 54 : 9;
+                                                    const int *__restrict__ pnt0, const double *__restrict__ J,
+                                                    const double *__restrict__ r, const double *__restrict__ u,
+                                                    double *__restrict__ Hcc, double *__restrict__ out9, double lam = 0.0,
+                                                    const int *__restrict__ opos = nullptr) {
+  constexpr int NACC = 54;
   __shared__ double red[BLK / 64][NACC];
   const int c = blockIdx.x;
   double acc[NACC];
@@ -84,31 +82,14 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks(const int *__restrict__ cam_
       b0[i] = Jo[3 + i];
       b1[i] = Jo[15 + i];
     }
-    double w0, w1;
-    if (MODE == 2) {
-      const double *up = u + 3 * (int64_t)pnt0[o];
-      w0 = (Jo[0] * up[0] + Jo[1] * up[1] + Jo[2] * up[2]) - r[2 * o];
-      w1 = (Jo[12] * up[0] + Jo[13] * up[1] + Jo[14] * up[2]) - r[2 * o + 1];
-    } else if (MODE == 3) {
-      const double *up = u + 3 * (int64_t)pnt0[o];
-      w0 = Jo[0] * up[0] + Jo[1] * up[1] + Jo[2] * up[2];
-      w1 = Jo[12] * up[0] + Jo[13] * up[1] + Jo[14] * up[2];
-    } else {
-      w0 = r[2 * o];
-      w1 = r[2 * o + 1];
-    }
-    if (MODE == 0) {
-      int idx = 0;
+    const double w0 = r[2 * o], w1 = r[2 * o + 1];
+    int idx = 0;
 #pragma unroll
-      for (int i = 0; i < 9; i++)
+    for (int i = 0; i < 9; i++)
 #pragma unroll
-        for (int j = 0; j <= i; j++) acc[idx++] += b0[i] * b0[j] + b1[i] * b1[j];
+      for (int j = 0; j <= i; j++) acc[idx++] += b0[i] * b0[j] + b1[i] * b1[j];
 #pragma unroll
-      for (int i = 0; i < 9; i++) acc[45 + i] += b0[i] * w0 + b1[i] * w1;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 9; i++) acc[i] += b0[i] * w0 + b1[i] * w1;
-    }
+    for (int i = 0; i < 9; i++) acc[45 + i] += b0[i] * w0 + b1[i] * w1;
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
@@ -119,20 +100,8 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks(const int *__restrict__ cam_
   __syncthreads();
   if (threadIdx.x < NACC) {
     double v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    if (MODE == 0) {
-      if (threadIdx.x < 45) Hcc[45 * (int64_t)c + threadIdx.x] = v;
-      else out9[9 * (int64_t)c + threadIdx.x - 45] = v;
-    } else if (MODE == 3) {  // PCG product: + Hcc_c x_c + lam x_c, x handed over in `r` (Hcc packed lower, read only)
-      const int i = threadIdx.x;
-      const double *x = r + 9 * (int64_t)c;
-      const double *H = Hcc + 45 * (int64_t)c;
-      double s = 0;
-#pragma unroll
-      for (int j = 0; j < 9; j++) s += H[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i] * x[j];
-      out9[9 * (int64_t)c + i] = (s + v) + lam * x[i];
-    } else {
-      out9[9 * (int64_t)((MODE == 2 && opos) ? opos[c] : c) + threadIdx.x] = v;
-    }
+    if (threadIdx.x < 45) Hcc[45 * (int64_t)c + threadIdx.x] = v;
+    else out9[9 * (int64_t)c + threadIdx.x - 45] = v;
   }
 }
 
@@ -141,7 +110,7 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks(const int *__restrict__ cam_
 // Here a wave stages the rows of 64 observations into its LDS slot with 16-byte loads in which 12 consecutive lanes read
 // one whole row (12 instructions per 64 rows), and each lane then works on its row from LDS (row stride 25 doubles:
 // conflict-free).  rows == null: observations q0 .. q0+nrows-1 (contiguous); else observation rows[q0 + i].
-// Measured on Venice (bench.py kernel classes, ms per launch, plain -> staged): right-hand side pass (k_cam_blocks<2>)
+// Measured on Venice (bench.py kernel classes, ms per launch, plain -> staged): right-hand side pass (k_cam_blocks_st<2>)
 // 0.68 -> 0.47; back-substitution + model value in one staged pass 0.48 + 0.37 -> 0.76; but the 54-accumulator Hcc pass
 // 0.32 -> 0.50 and the point-block pass 0.27 -> 0.33 got SLOWER and keep their plain loads: the vector L1 already merges
 // the 24 strided loads of a wave, and the PMC "over-fetch" of those kernels (FETCH_SIZE x 2) overstates 8-byte loads.
@@ -208,8 +177,11 @@ __device__ inline void stage_rows_by_id(const double *__restrict__ J, const int 
   stage_commit(v, slot);
 }
 
-// camera side with staged rows: same work item, same summation order as k_cam_blocks (thread t of camera c takes list
-// positions t, t + 256, ...), hence the same bits
+// camera side with staged rows, the light passes (one workgroup per camera, thread t of camera c takes list positions t,
+// t + 256, ...; fixed-order tree as in k_cam_blocks):
+// MODE 1: gc = B' r (9).   MODE 2: rhs = sum_a B_a' (A_a u_p(a) - r_a)   (u = U^-1 gp per point); opos: the right-hand side
+// of the camera system is written at the camera's block row of S (camera ordering).
+// MODE 3 (PCG product): Hcc_c x_c + lam x_c + sum_a B_a' A_a u_p(a), x in `r`.
 template <int MODE>
 __global__ __launch_bounds__(BLK) void k_cam_blocks_st(const int *__restrict__ cam_ptr, const int *__restrict__ cam_obs,
                                                         const int *__restrict__ pnt0, const double *__restrict__ J,
@@ -217,7 +189,7 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks_st(const int *__restrict__ c
                                                         double *__restrict__ Hcc, double *__restrict__ out9, double lam = 0.0,
                                                         const int *__restrict__ cam_pnt = nullptr,
                                                         const int *__restrict__ opos = nullptr) {
-  constexpr int NACC = (MODE == 0) ? 54 : 9;
+  constexpr int NACC = 9;
   __shared__ double slots[(BLK / 64) * ST_WAVE_ELEMS];
   __shared__ double red[BLK / 64][NACC];
   const int c = blockIdx.x;
@@ -274,18 +246,8 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks_st(const int *__restrict__ c
         w0 = r[2 * o];
         w1 = r[2 * o + 1];
       }
-      if (MODE == 0) {
-        int idx = 0;
 #pragma unroll
-        for (int i = 0; i < 9; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) acc[idx++] += b0[i] * b0[j] + b1[i] * b1[j];
-#pragma unroll
-        for (int i = 0; i < 9; i++) acc[45 + i] += b0[i] * w0 + b1[i] * w1;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 9; i++) acc[i] += b0[i] * w0 + b1[i] * w1;
-      }
+      for (int i = 0; i < 9; i++) acc[i] += b0[i] * w0 + b1[i] * w1;
     }
     wave_lds_sync();  // the slot is rewritten by the next batch
   }
@@ -297,10 +259,7 @@ __global__ __launch_bounds__(BLK) void k_cam_blocks_st(const int *__restrict__ c
   __syncthreads();
   if (threadIdx.x < NACC) {
     double v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-    if (MODE == 0) {
-      if (threadIdx.x < 45) Hcc[45 * (int64_t)c + threadIdx.x] = v;
-      else out9[9 * (int64_t)c + threadIdx.x - 45] = v;
-    } else if (MODE == 3) {  // PCG product: + Hcc_c x_c + lam x_c, x handed over in `r` (Hcc packed lower, read only)
+    if (MODE == 3) {  // PCG product: + Hcc_c x_c + lam x_c, x handed over in `r` (Hcc packed lower, read only)
       const int i = threadIdx.x;
       const double *x = r + 9 * (int64_t)c;
       const double *H = Hcc + 45 * (int64_t)c;
@@ -392,10 +351,8 @@ __global__ __launch_bounds__(BLK) void k_obs_y(int64_t nobs, const int *__restri
 // B operand G[alpha][j] = Q_ab[alpha][:] B_b[:][j] with Q_ab = A_a Y_b.  Per task one coalesced load of
 // J_a (24), the camera rows of J_b (18) and Y_b (6) is staged in the wave's LDS slot.
 typedef double d4s __attribute__((ext_vector_type(4)));
-#ifndef BA_SCHUR_PF
-#define BA_SCHUR_PF 4  // task pairs in flight per wave (ring of LDS slots, see schur_accumulate)
-#endif
-constexpr int SCHUR_PF = BA_SCHUR_PF;
+// task pairs in flight per wave (ring of LDS slots, see schur_accumulate; depths 3 / 6 measured 2.67 / 2.82 ms against 2.62)
+constexpr int SCHUR_PF = 4;
 constexpr int SCHUR_SLOT = 128;                       // doubles per ring slot: 64 lanes x 16 bytes
 constexpr int SCHUR_RING = SCHUR_PF * SCHUR_SLOT;     // doubles per wave
 // sum over the tasks [t_begin, t_end) of B_a' (Q_ab B_b): lane (fr < 9, i = fk + 4 g < 9) gets element (i, j = fr) in acc[g]
@@ -1276,12 +1233,6 @@ __global__ __launch_bounds__(1024) void k_cg_beta_dir(int64_t n, int nb, const d
 
 static inline unsigned grid_for(int64_t n, int blk) { return (unsigned)((n + blk - 1) / blk); }
 
-// BA_STAGED=0: the scalar-load kernels of round 1 everywhere (A/B measurements)
-static bool staged_on() {
-  static const bool off = [] { const char *e = getenv("BA_STAGED"); return e && e[0] == '0'; }();
-  return !off;
-}
-
 int launch_point_blocks(ba_problem *p, const double *d_J, const double *d_r, double *d_Hpp, double *d_gp,
                         hipStream_t st) {
   if (p->npnts == 0) return BA_OK;
@@ -1302,13 +1253,10 @@ int launch_cam_blocks(ba_problem *p, const double *d_J, const double *d_r, doubl
   // the 54-accumulator Hcc pass is faster with plain per-lane loads (0.32 against 0.50 ms on Venice); the light passes
   // (J'r here, the right-hand side in launch_schur_rhs) are latency-bound and gain from the staged rows (0.68 -> 0.47 ms)
   if (d_Hcc)
-    hipLaunchKernelGGL(k_cam_blocks<0>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
+    hipLaunchKernelGGL(k_cam_blocks, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
                        d_r, (const double *)nullptr, d_Hcc, d_gc);
-  else if (staged_on())
-    hipLaunchKernelGGL(k_cam_blocks_st<1>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_r, (const double *)nullptr, (double *)nullptr, d_gc);
   else
-    hipLaunchKernelGGL(k_cam_blocks<1>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
+    hipLaunchKernelGGL(k_cam_blocks_st<1>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
                        d_r, (const double *)nullptr, (double *)nullptr, d_gc);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
@@ -1484,17 +1432,13 @@ int launch_schur_rhs(ba_problem *p, const double *d_J, const double *d_r, const 
                      hipStream_t st, const int *d_cam_pnt, const int *d_pos) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_SCHUR_RHS, st);
-  if (staged_on())
-    hipLaunchKernelGGL(k_cam_blocks_st<2>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_r, d_u, (double *)nullptr, d_rhs, 0.0, d_cam_pnt, d_pos);
-  else
-    hipLaunchKernelGGL(k_cam_blocks<2>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_r, d_u, (double *)nullptr, d_rhs, 0.0, d_pos);
+  hipLaunchKernelGGL(k_cam_blocks_st<2>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
+                     d_r, d_u, (double *)nullptr, d_rhs, 0.0, d_cam_pnt, d_pos);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
-// d_r_model != null (and the staged kernel applies): |J delta + cr r|^2 of the step is formed in the same pass ->
+// d_r_model != null (and the problem is point-sorted): |J delta + cr r|^2 of the step is formed in the same pass ->
 // d_scal[slot], *model_done = true.  d_partial then needs one entry per block of 256 points.
 int launch_backsub(ba_problem *p, const double *d_J, const double *d_Uinv, const double *d_u, const double *d_dc,
                    double *d_dp, hipStream_t st, const double *d_r_model, double cr, double *d_partial, double *d_scal,
@@ -1503,7 +1447,7 @@ int launch_backsub(ba_problem *p, const double *d_J, const double *d_Uinv, const
   if (p->npnts == 0) return BA_OK;
   ProfScope ps(p, PC_BACKSUB, st);
   const unsigned nb = grid_for(p->npnts, BLK);
-  if (p->point_sorted && staged_on()) {
+  if (p->point_sorted) {
     const bool with_model = d_r_model && d_partial && d_scal;
     // one lane per observation in both sweeps (k_wtv<true>; the first staged version walked a point's observations with one
     // lane: Venice 0.75 -> 0.33 ms, Dubrovnik 0.28 -> 0.10 ms per call)
@@ -1633,12 +1577,8 @@ int launch_wuw(ba_problem *p, const double *d_J, const double *d_h, const double
                hipStream_t st, const int *d_cam_pnt) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_SCHUR_RHS, st);
-  if (staged_on())
-    hipLaunchKernelGGL(k_cam_blocks_st<3>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_v, d_h, const_cast<double *>(d_Hcc), d_q, lam, d_cam_pnt);
-  else
-    hipLaunchKernelGGL(k_cam_blocks<3>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_v, d_h, const_cast<double *>(d_Hcc), d_q, lam);
+  hipLaunchKernelGGL(k_cam_blocks_st<3>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
+                     d_v, d_h, const_cast<double *>(d_Hcc), d_q, lam, d_cam_pnt);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(256, 2) void k_ldl_update_probe(T *__restrict__ S, 
 #pragma unroll
         for (int m = 0; m < 4; m++)
 #pragma unroll
-          for (int g = 0; g < 4; g++) cv[n2][m][g] = NT_C ? __builtin_nontemporal_load(&cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)]) : cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)];
+          for (int g = 0; g < 4; g++) cv[n2][m][g] = cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)];
     }
 #pragma unroll
     for (int n2 = 0; n2 < 2; n2++)
@@ -259,8 +259,7 @@ __global__ __launch_bounds__(256, 2) void k_ldl_update_probe(T *__restrict__ S, 
         for (int g = 0; g < 4; g++) {
           const T a = acc[m][2 * h + n2][g];
           const T nv = (DBG & 1) ? a : cv[n2][m][g] - a;
-          if (NT_C) __builtin_nontemporal_store(nv, &cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)]);
-          else cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)] = nv;
+          cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)] = nv;
         }
   }
   // tiles 0 .. ready_tiles-1 are (base,base) [, (base+1,base), (base+1,base+1)]: what the next pair's hoisted diagonal

@@ -317,3 +317,28 @@ def test_julia_shim_matches_header(ba):
     for needed in ("NLPModels.cons!", "NLPModels.jac_structure!", "NLPModels.jac_coord!", "function name(", "function readfile(",
                    "Vector{Float32}"):
         assert needed in src["BALNLPModelsHIP.jl"]
+
+
+def test_every_environment_switch_is_documented():
+    """The BA_* variables the library reads (getenv / env_off / env_int in csrc/, the micro-benchmarks of csrc/bench/ aside;
+    os.environ / os.getenv in the package's Python) are exactly the rows of DESIGN §8: no switch is read that is not
+    documented, and no documented switch is gone from the code."""
+    pkg = os.path.join(ROOT, "bundleadjustment.jl_amd")
+    csrc = os.path.join(pkg, "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".cpp", ".h")):
+            read |= set(re.findall(r"\b(?:getenv|env_off|env_int)\(\s*\"(BA_\w+)\"", open(os.path.join(csrc, f)).read()))
+    for f in os.listdir(pkg):
+        if f.endswith(".py"):
+            src = open(os.path.join(pkg, f)).read()
+            read |= set(re.findall(r"\bos\.(?:environ\.get|environ\.pop|environ\.setdefault|getenv)\(\s*[\"'](BA_\w+)", src))
+            read |= set(re.findall(r"\bos\.environ\[\s*[\"'](BA_\w+)", src))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = design[design.index("\n## 8."):design.index("\n## 9.")]
+    documented = set()
+    for row in re.findall(r"^\|([^|\n]*)\|", sec, re.M):
+        documented |= set(re.findall(r"`(BA_\w+)", row))
+    assert len(read) >= 10  # (the patterns still match the way the sources read them)
+    assert read == documented, (f"read but not in DESIGN §8: {sorted(read - documented)}; "
+                                f"in DESIGN §8 but not read: {sorted(documented - read)}")

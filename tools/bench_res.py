@@ -1,5 +1,5 @@
 """Residual / Jacobian launch time on the Venice shape: `reps` back-to-back launches on one stream, events on that stream.
-BA_CAM_FUSED=0 gives the separate k_cam_pre launch.  usage: python tools/bench_res.py [reps]"""
+usage: python tools/bench_res.py [reps]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -29,5 +29,5 @@ def timeit(fn):
 res = timeit(lambda: ba._lib.check(L.ba_residual_dev(nlp.handle, C.c_void_p(x.data_ptr()), C.c_void_p(r.data_ptr()), sp)))
 jac = timeit(lambda: ba._lib.check(L.ba_jac_coord_dev(nlp.handle, C.c_void_p(x.data_ptr()), C.c_void_p(v.data_ptr()), sp)))
 nb = (48 + 8 * (3 * p["npnts"] + 9 * p["ncams"]) / p["nobs"]) * p["nobs"]
-print(f"fused={os.environ.get('BA_CAM_FUSED', '1')} residual us {[round(t, 1) for t in res]} -> {nb / (min(res) * 1e-6) / 8e12:.3f} of HBM; "
+print(f"residual us {[round(t, 1) for t in res]} -> {nb / (min(res) * 1e-6) / 8e12:.3f} of HBM; "
       f"jacobian us {[round(t, 1) for t in jac]}")
