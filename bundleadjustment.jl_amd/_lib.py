@@ -61,7 +61,7 @@ SYMBOLS = [
     "ba_jac_structure_dev", "ba_jac_coord_dev", "ba_jac_coord_f32_dev", "ba_jtr_dev", "ba_dev_malloc", "ba_dev_free",
     "ba_memcpy_h2d", "ba_memcpy_d2h", "ba_memcpy_h2d_on", "ba_memcpy_d2h_on", "ba_synchronize", "ba_lm_solve", "ba_lm_solve_dev", "ba_comm_get_unique_id", "ba_lm_set_comm_rccl",
     "ba_lm_set_comm_hook", "ba_comm_stats", "ba_comm_stats_ops", "ba_dist_layout",
-    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
+    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
 ]
 
 _lib = None
@@ -119,6 +119,8 @@ def lib():
     L.ba_lm_set_loss.argtypes = [vp, C.c_int, f64]
     L.ba_lm_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(f64)]
     L.ba_robust_eval.argtypes = [vp, vp, vp, C.POINTER(f64)]
+    L.ba_lm_set_fixed.argtypes = [vp, vp, vp]
+    L.ba_lm_get_fixed.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.ba_profile_enable.argtypes = [vp, C.c_int]
     L.ba_profile_reset.argtypes = [vp]
     L.ba_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(f64), C.POINTER(i64), C.POINTER(C.c_int)]
@@ -178,6 +180,96 @@ def set_loss(handle, loss, f_scale):
     """the handle's loss for its next LM calls (ba_lm_set_loss)"""
     kind, c = loss_code(loss, f_scale)
     check(lib().ba_lm_set_loss(handle, kind, c))
+
+
+# fixed parameters of the LM entries (ba_lm_set_fixed): bit b of a camera's mask is component b of its block, in the
+# storage order r1 r2 r3 t1 t2 t3 k1 k2 f
+CAMERA_PARAMS = {"r": 0x007, "t": 0x038, "k1": 0x040, "k2": 0x080, "f": 0x100}
+CAMERA_ALL = 0x1FF
+
+
+def _fixed_set(v, n, what):
+    """boolean array of length n from 1-based indices or a boolean array of length n (n None: the checks that need no n)"""
+    a = np.asarray(v)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or (n is not None and a.shape[0] != n):
+            raise ValueError(f"{what}: a boolean array must have shape ({'n' if n is None else n},), got {a.shape}")
+        return a if n is not None else None
+    if a.size == 0:
+        return np.zeros(n, dtype=bool) if n is not None else None
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what}: 1-based integer indices or a boolean array, got dtype {a.dtype}, shape {a.shape}")
+    if a.min() < 1 or (n is not None and a.max() > n):
+        raise ValueError(f"{what}: 1-based indices must lie in 1..{'n' if n is None else n}, got {a.min()}..{a.max()}")
+    if n is None:
+        return None
+    out = np.zeros(n, dtype=bool)
+    out[a - 1] = True
+    return out
+
+
+def _camera_params(v, ncams):
+    """(ncams,) uint16 masks of fixed_camera_params: names applied to every camera, or a boolean (ncams, 9) array"""
+    if isinstance(v, str):
+        v = (v,)
+    a = np.asarray(v)
+    if a.dtype == np.bool_:
+        if a.ndim != 2 or a.shape[1] != 9 or (ncams is not None and a.shape[0] != ncams):
+            raise ValueError(f"fixed_camera_params: a boolean array must have shape ({'ncams' if ncams is None else ncams}, 9), "
+                             f"got {a.shape}")
+        return None if ncams is None else (a.astype(np.uint16) << np.arange(9, dtype=np.uint16)).sum(axis=1).astype(np.uint16)
+    m = 0
+    for name in v:
+        if not isinstance(name, str) or name not in CAMERA_PARAMS:
+            raise ValueError(f"fixed_camera_params: names among {', '.join(CAMERA_PARAMS)}, got {name!r}")
+        m |= CAMERA_PARAMS[name]
+    return None if ncams is None else np.full(ncams, m, dtype=np.uint16)
+
+
+def check_fixed(fixed_cameras=None, fixed_points=None, fixed_camera_params=None):
+    """the checks of fixed_masks that need no problem size (ValueError); True when the options select something"""
+    some = False
+    for v, what in ((fixed_cameras, "fixed_cameras"), (fixed_points, "fixed_points"), (fixed_camera_params, None)):
+        if v is None:
+            continue
+        if what is None:
+            _camera_params(v, None)
+        else:
+            _fixed_set(v, None, what)
+        a = np.asarray((v,) if isinstance(v, str) else v)
+        some = some or (bool(a.any()) if a.dtype == np.bool_ else a.size > 0)
+    return some
+
+
+def fixed_masks(ncams, npnts, fixed_cameras=None, fixed_points=None, fixed_camera_params=None):
+    """(cam_mask uint16[ncams], pnt_fixed uint8[npnts]) of ba_lm_set_fixed, host only.  fixed_cameras / fixed_points:
+    1-based indices (the Julia convention) or a boolean array of length ncams / npnts; a listed camera is fixed as a whole.
+    fixed_camera_params: names among "r", "t", "k1", "k2", "f", applied to every camera (("k1", "k2", "f"): calibrated
+    intrinsics), or a boolean (ncams, 9) array in block order (r1 r2 r3 t1 t2 t3 k1 k2 f).  The options are OR-ed.
+    ValueError for an index 0 or above n, a wrong shape or an unknown name."""
+    cam = np.zeros(ncams, dtype=np.uint16)
+    pnt = np.zeros(npnts, dtype=np.uint8)
+    if fixed_cameras is not None:
+        cam[_fixed_set(fixed_cameras, ncams, "fixed_cameras")] = CAMERA_ALL
+    if fixed_camera_params is not None:
+        cam |= _camera_params(fixed_camera_params, ncams)
+    if fixed_points is not None:
+        pnt[_fixed_set(fixed_points, npnts, "fixed_points")] = 1
+    return cam, pnt
+
+
+def set_fixed(handle, cam_mask, pnt_fixed):
+    """the handle's mask for its next LM calls (ba_lm_set_fixed); all-zero masks clear it"""
+    cam = np.ascontiguousarray(cam_mask, dtype=np.uint16)
+    pnt = np.ascontiguousarray(pnt_fixed, dtype=np.uint8)
+    check(lib().ba_lm_set_fixed(handle, ptr(cam) if cam.any() else None, ptr(pnt) if pnt.any() else None))
+
+
+def get_fixed(handle):
+    """(fixed camera components, fixed points) the handle holds (ba_lm_get_fixed)"""
+    nc, npt = C.c_int64(0), C.c_int64(0)
+    check(lib().ba_lm_get_fixed(handle, C.byref(nc), C.byref(npt)))
+    return nc.value, npt.value
 
 
 def schur_ordering(cam_idx1, pnt_idx1, ncams, npnts, method="AMD"):

@@ -18,7 +18,7 @@ void ba_set_error(const char *fmt, ...) {
 const char *const kProfNames[PC_COUNT] = {
     "k_residual", "k_jac_structure", "k_jac_coord", "k_point_blocks", "k_cam_blocks", "k_schur_prep",
     "k_schur_blocks", "k_schur_rhs", "k_ldl_diag", "k_ldl_trsm", "k_ldl_col", "k_ldl_update", "k_ldl_update_rs", "k_tri_solve",
-    "k_backsub", "k_model_sq", "k_reduce", "allreduce", "k_robust_scale"};
+    "k_backsub", "k_model_sq", "k_reduce", "allreduce", "k_robust_scale", "k_fix_mask"};
 
 extern "C" const char *ba_last_error(void) { return g_err; }
 
@@ -160,7 +160,7 @@ extern "C" void ba_problem_destroy(ba_problem *p) {
   lm_free(p);
   comm_free(p);
   void *ptrs[] = {p->cam0, p->pnt0, p->pt2d, p->pt2d_f32, p->pt_ptr, p->pt_obs, p->cam_ptr, p->cam_obs,
-                  p->scratch[0], p->scratch[1], p->scratch[2], p->scratch[3]};
+                  p->scratch[0], p->scratch[1], p->scratch[2], p->scratch[3], p->d_fix_cam, p->d_fix_pnt};
   for (void *q : ptrs)
     if (q) (void)hipFree(q);
   if (p->ev0) (void)hipEventDestroy(p->ev0);

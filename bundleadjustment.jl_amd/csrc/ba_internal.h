@@ -107,6 +107,7 @@ enum ProfClass {
   PC_REDUCE,
   PC_COMM,
   PC_ROBUST,  // k_robust_scale (robust loss: reweighting of r and J)
+  PC_FIXED,   // k_fix_mask (fixed parameters: zeroing of their columns of J)
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -200,6 +201,15 @@ struct ba_problem {
   // robust loss of the LM entries (ba_lm_set_loss): BA_LOSS_*, scale c > 0
   int loss = BA_LOSS_LINEAR;
   double loss_scale = 1.0;
+  // fixed parameters of the LM entries (ba_lm_set_fixed): host masks (empty: none of that kind), counts, and their device
+  // copies (allocated at the first upload, ncams / npnts entries: never reallocated), uploaded lazily (fix_dirty)
+  std::vector<uint16_t> h_fix_cam;
+  std::vector<uint8_t> h_fix_pnt;
+  int64_t fix_ncam = 0, fix_npnt = 0;  // fixed camera components, fixed points
+  uint16_t *d_fix_cam = nullptr;
+  uint8_t *d_fix_pnt = nullptr;
+  bool fix_dirty = false;
+  bool fix_on() const { return fix_ncam > 0 || fix_npnt > 0; }
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

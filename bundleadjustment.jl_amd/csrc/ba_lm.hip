@@ -228,8 +228,9 @@ struct LMWorkFull : LMWork {
   double *d_lambda = nullptr, *h_lambda = nullptr;  // device scalar, pinned staging
   int *h_flag = nullptr;                            // pinned copy of the pivot flag
   hipGraphExec_t g_step[2] = {nullptr, nullptr}, g_refresh[2] = {nullptr, nullptr};
-  int g_key = -1;  // graph_key(): normalize + 4 * facto_f32 + 8 * x_f32 + 16 * loss the graphs were recorded for
+  int g_key = -1;  // graph_key(): normalize + 4 * facto_f32 + 8 * x_f32 + 16 * loss + 128 / 256 * mask tables the graphs were recorded for
   double g_scale = 1.0;  // ... and the loss scale (the robust kernels take loss and scale as launch arguments)
+  const void *g_fix_cam = nullptr, *g_fix_pnt = nullptr;  // ... and the device tables of the mask k_fix_mask was recorded with
   int parity = 0;
   bool g_off = false;  // a recording failed on this handle: plain launches from then on
   // facto = PCG: block-Jacobi preconditioned conjugate gradients on the reduced camera system, S never formed (pcg_solve).
@@ -771,6 +772,7 @@ static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too
   } else {
     BA_CHECK(launch_jac_coord_f64(p, w->x, w->J, st));
   }
+  if (p->fix_on()) BA_CHECK(launch_fix_mask(p, w->J, st));  // fixed parameters (ba_lm_set_fixed): their columns of J to 0
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (never with xf32: refused by ba_lm_solve)
   if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
@@ -1096,11 +1098,14 @@ static int check_pivot(ba_problem *p, LMWorkFull *w, hipStream_t st) {
 
 // ---- recorded launch sequences ------------------------------------------------------------------------------------------
 // what a recorded sequence depends on besides the handle's buffers: the loss kind and scale are launch arguments of the
-// robust kernels, so a sequence recorded under one loss is never replayed under another
+// robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed parameters
+// decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables are launch arguments
 static int graph_key(ba_problem *p, int normalize, bool facto_f32, bool xf32) {
-  return normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0) + 16 * p->loss;
+  return normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0) + 16 * p->loss + 128 * (p->fix_ncam > 0 ? 1 : 0) +
+         256 * (p->fix_npnt > 0 ? 1 : 0);
 }
 static double graph_scale(ba_problem *p) { return p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0; }
+static bool graph_fix_same(ba_problem *p, LMWorkFull *w) { return w->g_fix_cam == p->d_fix_cam && w->g_fix_pnt == p->d_fix_pnt; }
 
 static bool graphs_allowed(ba_problem *p, LMWorkFull *w) {
   if (w->g_off || p->prof_on || p->comm.active() || w->f16 || w->pcg) return false;  // per-kernel events / communicator / Float16 path
@@ -1151,7 +1156,7 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
     return BA_OK;
   }
   const int key = graph_key(p, normalize, facto_f32, xf32);
-  if (w->g_key != key || w->g_scale != graph_scale(p)) {
+  if (w->g_key != key || w->g_scale != graph_scale(p) || !graph_fix_same(p, w)) {
     for (int q = 0; q < 2; q++) {
       if (w->g_step[q]) (void)hipGraphExecDestroy(w->g_step[q]);
       if (w->g_refresh[q]) (void)hipGraphExecDestroy(w->g_refresh[q]);
@@ -1159,6 +1164,8 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
     }
     w->g_key = key;
     w->g_scale = graph_scale(p);
+    w->g_fix_cam = p->d_fix_cam;
+    w->g_fix_pnt = p->d_fix_pnt;
   }
   if (facto_f32) BA_CHECK(ensure_f32(w));  // no allocation while recording
   hipGraphExec_t &g = w->g_step[w->parity];
@@ -1215,8 +1222,8 @@ static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t s
 // refreshed |J'r| or |x| then end the loop, the prefetched step is dropped (never counted, x untouched).
 static bool can_prefetch_trial(ba_problem *p, LMWorkFull *w, int normalize, bool facto_f32, bool xf32) {
   if (env_off("BA_LM_PREFETCH") || !graphs_allowed(p, w)) return false;  // read per call: a test compares both forms in one process
-  return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && w->g_step[w->parity] &&
-         w->g_refresh[w->parity];
+  return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && graph_fix_same(p, w) &&
+         w->g_step[w->parity] && w->g_refresh[w->parity];
 }
 static int accept_refresh_and_trial(LMWorkFull *w, double lambda, bool facto_f32, hipStream_t st) {
   BA_HIP_CHECK(hipGraphLaunch(w->g_refresh[w->parity], st));
@@ -1235,6 +1242,7 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
   }
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
+  BA_CHECK(fix_upload(p));
   LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
   hipStream_t st = p->stream;
   w->pcg = pcg;
@@ -1442,9 +1450,14 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
       return BA_ERR_ARG;
     }
   }
+  if (p->fix_on() && o->facto_type == 2) {
+    ba_set_error("ba_lm_solve: fixed parameters (ba_lm_set_fixed) are not supported with facto_type = Float16");
+    return BA_ERR_ARG;
+  }
   BA_HIP_CHECK(hipSetDevice(p->device));
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
+  BA_CHECK(fix_upload(p));
   LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
   hipStream_t st = p->stream;
   const int V = o->variant;
@@ -1512,7 +1525,21 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   TS obj = robust ? half_of(h_sh[SH_RSQ]) : ts::div(ts::mul(norm_r, norm_r), T_(2));
   TS norm_Jtr = norm_of(h_sh[SH_GP] + h_rp[RP_GC], W);
   TS norm_x = norm_of(h_sh[SH_X_P] + h_rp[RP_X_C], W);
-  if (V) {  // lm.jl:59: lambda = T(max(lambda, 1e10 / norm_Jtr))
+  // every parameter fixed (ba_lm_set_fixed): nothing to solve for -- return at x with status :first_order, iter 0, before the
+  // controller divides 0 by 0.  The cameras' mask is the same on every rank; the points are counted over the ranks.
+  bool all_fixed = false;
+  if (p->fix_ncam == 9 * p->ncams) {
+    double free_pts = (double)(p->npnts - p->fix_npnt);
+    if (p->comm.active()) {
+      BA_HIP_CHECK(hipMemcpyAsync(w->partial, &free_pts, sizeof(double), hipMemcpyHostToDevice, st));
+      BA_CHECK(comm_allreduce(p, w->partial, 1, st));
+      BA_HIP_CHECK(hipMemcpyAsync(&free_pts, w->partial, sizeof(double), hipMemcpyDeviceToHost, st));
+      BA_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    all_fixed = free_pts == 0;
+  }
+  if (all_fixed) norm_Jtr = T_(0);
+  if (V && !all_fixed) {  // lm.jl:59: lambda = T(max(lambda, 1e10 / norm_Jtr))
     lambda = ts::max(lambda, ts::div(ts::f64(1e10), norm_Jtr));
     lambda = T_(lambda.v);
   }
@@ -1520,7 +1547,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   TS norm_delta = T_(0), dr2 = T_(0), ared = T_(0), pred = T_(0);
   const TS eps_first = ts::add(atol, ts::mul(rtol, norm_Jtr));  // lm.jl:107
   TS old_obj = obj;
-  bool small_step = false, first_order = norm_Jtr.v < eps_first.v, small_residual = norm_r.v < restol.v;
+  bool small_step = false, first_order = all_fixed || norm_Jtr.v < eps_first.v, small_residual = norm_r.v < restol.v;
   bool small_obj_change = false, fail2 = false;
   int iter = 0;
   bool tired = iter > ite_max;

@@ -180,6 +180,10 @@ int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi /
 // d_partial[RED_BLOCKS, RED_BLOCKS + nb), nb = robust_blocks(nobs): a fixed grid, so a fixed summation tree
 int robust_blocks(int64_t nobs);
 int launch_robust_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, hipStream_t st);
+// fixed parameters (ba_fixed_kernels.hip): the handle's mask to the device when it changed (ba_lm_set_fixed); zeros into the
+// columns of J of the fixed parameters (no launch without a mask)
+int fix_upload(ba_problem *p);
+int launch_fix_mask(ba_problem *p, double *d_J, hipStream_t st);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,

@@ -55,7 +55,8 @@ def _sym(s):
 def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=None, facto_type=None,
                         restol=None, satol=None, srtol=None, oatol=None, ortol=None, atol=None, rtol=None,
                         nu_d=None, nu_m=None, lam=None, delta_d=None, ite_max=None, max_time=None, verbose=False,
-                        log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0):
+                        log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0,
+                        fixed_cameras=None, fixed_points=None, fixed_camera_params=None):
     """x_device_ptr (an extension for device-resident callers, e.g. bench.py): the address of nvar doubles of DEVICE memory
     holding x0; the loop then runs through ba_lm_solve_dev -- no host copy of the iterate on either side -- the solution
     stays there and `solution` of the result is None.
@@ -64,10 +65,18 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     observations i, c = f_scale in pixels, rho one of "linear" (the default: 1/2 |r|^2, the reference's objective), "huber",
     "soft_l1", "cauchy", "arctan" (":huber" symbols are accepted).  The step is the reweighted (IRLS) one, see ba_lm_set_loss
     in include/ba_hip.h; `objective`, the log's f and |J'r| are then the robust f and its gradient norm.  Not with linesearch
-    = True, a Float32 model or facto_type = Float16 (ValueError)."""
+    = True, a Float32 model or facto_type = Float16 (ValueError).
+
+    fixed_cameras / fixed_points / fixed_camera_params (an extension): parameters held at their values in x0, the solve
+    runs over the free entries only (see _lib.fixed_masks for the forms and ba_lm_set_fixed in include/ba_hip.h for the
+    semantics).  Set on the handle at every call: a call without them runs the unmasked path.  Not with facto_type =
+    Float16 (ValueError)."""
     kind, c = _lib.loss_code(loss, f_scale)
     if kind != 0 and linesearch:
         raise ValueError("a robust loss is not supported with linesearch = true")
+    masked = _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
+    if masked and facto_type is not None and np.dtype(facto_type) == np.float16:
+        raise ValueError("fixed parameters are not supported with facto_type = Float16")
     facto, perm, normalize = _sym(facto), _sym(perm), _sym(normalize)
     if facto not in _FACTO:
         raise ValueError(f"facto must be :QR, :LDL or :PCG (extension: matrix-free CG on the reduced camera system), got {facto!r}")
@@ -119,7 +128,9 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
         rows.append((it, f, df, njtr, lmb, nd, rho, bool(acc)))
 
     cb = _lib.LOG_CB(_cb) if log else C.cast(None, _lib.LOG_CB)
+    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))  # every call: one without loss= runs the plain objective
+    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)  # ... and one without fixed_* the unmasked path
     if x_device_ptr is not None:
         _lib.check(_lib.lib().ba_lm_solve_dev(nlp.handle, C.byref(o), C.c_void_p(int(x_device_ptr)), C.byref(st), cb, None))
     else:
@@ -139,14 +150,19 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     return out
 
 
-def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0):
+def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0, fixed_cameras=None,
+            fixed_points=None, fixed_camera_params=None):
     """One linear LM step from (x, lambda): delta, 1/2|J delta + r|^2, J'r  (ba_lm_step; facto_type=np.float32:
     ba_lm_step_f32, the reduced camera system factored in Float32 as src/lm.jl:170-173 does; pcg=(tol, max_iter):
     ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result).
-    loss / f_scale (see Levenberg_Marquardt; None = "linear"): the reweighted step, 1/2|J~ delta + r~|^2 and J~'r~."""
+    loss / f_scale (see Levenberg_Marquardt; None = "linear"): the reweighted step, 1/2|J~ delta + r~|^2 and J~'r~.
+    fixed_* (see Levenberg_Marquardt): the step over the free entries; the fixed entries of delta and J'r are exactly 0."""
     kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
+    _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
+    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     x = np.ascontiguousarray(x, dtype=np.float64)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
+    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
     delta = np.empty(nlp.meta.nvar)
     jtr = np.empty(nlp.meta.nvar) if want_jtr else None
     half = C.c_double(0)

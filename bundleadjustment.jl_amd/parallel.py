@@ -44,6 +44,16 @@ def shard_problem(arrays, rank, world):
     return (cam_l, pnt_l, pt2d_l, x0_l, ncams, pe - pb, len(sel)), info
 
 
+def shard_fixed_points(fixed_points, info):
+    """The shard's part of a global point mask (fixed_points of Levenberg_Marquardt / lm_step: 1-based global indices or a
+    boolean array of the global npnts) as the boolean array of the shard's own points, info["point_range"] of
+    shard_problem.  Every rank passes the global camera options unchanged."""
+    from . import _lib
+    pb, pe = info["point_range"]
+    _, glob = _lib.fixed_masks(0, info["npnts_global"], None, fixed_points, None)
+    return glob[pb:pe].astype(bool)
+
+
 def gather_solution(x_local, info, ncams, group=None):
     """Reassemble the global x = [points; cameras] from the shards (cameras are identical on every rank)."""
     import torch

@@ -289,6 +289,33 @@ enum { BA_LOSS_LINEAR = 0, BA_LOSS_HUBER, BA_LOSS_SOFT_L1, BA_LOSS_CAUCHY, BA_LO
 int ba_lm_set_loss(ba_problem *p, int kind, double scale);
 int ba_lm_get_loss(const ba_problem *p, int *kind, double *scale);
 int ba_robust_eval(ba_problem *p, const double *x, double *weights /* nobs or NULL */, double *cost /* or NULL */);
+
+/* ---- fixed parameters (an extension: the reference moves every entry of x) ---------------------------------------
+ * Granularity: a point is fixed as a whole (its 3 entries); a camera per component, by a 9-bit mask whose bit b is component
+ * b of the camera block in storage order r1 r2 r3 t1 t2 t3 k1 k2 f (Jacobian column 3 + b).
+ * The LM entries (ba_lm_step / _f32 / _pcg, ba_lm_solve, ba_lm_solve_dev) minimise over the free entries only: the columns
+ * of the fixed parameters are zeroed after every evaluation of J, so their gradient entries and their rows and columns of
+ * J'J are exactly 0 (the damping lambda stays on the diagonal) and their step is exactly 0.  The free part of the step
+ * solves (J_F'J_F + lambda I) delta_F = -J_F'r.  Fixed entries of x come back bit-identical to the input (x_f32 = 1: the
+ * Float32 rounding the model applies to x0); a fixed entry holding -0.0 may come back as +0.0.
+ * dual_feas / primal_feas, the log's |J'r| and the jtr output of ba_lm_step are the gradient over the free entries (the
+ * fixed entries of jtr are exactly 0).  |x| in the small-step test stays the norm of the whole iterate, fixed entries
+ * included: they are part of x.  If every parameter is fixed the solve returns at once: status BA_ST_FIRST_ORDER,
+ * iter = 0, x unchanged, objective at x, dual_feas = 0.
+ * A fully fixed camera keeps its 9 rows in the reduced camera system: they hold the (scaled) damping on the diagonal and
+ * zeros elsewhere, so the factorisation keeps its size.
+ * Combines with a robust loss, normalize :J / :A (a zero column keeps the scale 1), the line search, facto_type =
+ * Float32, :PCG, both variants, every perm, the block-sparse schedule and several ranks.  ba_lm_solve refuses a mask
+ * together with facto_type = Float16 (BA_ERR_ARG).  The model entries (ba_residual, ba_jac_coord, ba_jtr,
+ * ba_robust_eval) ignore the mask.
+ *   ba_lm_set_fixed : the mask of the handle's next LM steps and solves.  cam_mask: ncams entries, bits 0..8 (NULL: no
+ *                     camera component fixed); pnt_fixed: npnts entries, 0 / 1 (NULL: no point fixed).  On a shard (see
+ *                     multi-GPU): the shard's own points; every rank passes the same cam_mask.  Both NULL (or nothing
+ *                     set) clears the mask: the LM entries then run exactly the unmasked path.  A bit above 8 or a
+ *                     pnt_fixed value other than 0 / 1: BA_ERR_ARG.  Host only; uploaded when a step or solve runs.
+ *   ba_lm_get_fixed : the number of fixed camera components and of fixed points the handle holds (either may be NULL). */
+int ba_lm_set_fixed(ba_problem *p, const uint16_t *cam_mask, const uint8_t *pnt_fixed);
+int ba_lm_get_fixed(const ba_problem *p, int64_t *n_fixed_cam_params, int64_t *n_fixed_points);
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -18,6 +18,46 @@ function _ba_set_loss(nlp, loss :: Symbol, f_scale :: Real)
   bacheck(ccall((:ba_lm_set_loss, libba), Cint, (Ptr{Cvoid}, Cint, Cdouble), nlp.handle, Cint(k - 1), Float64(f_scale)))
 end
 
+# fixed parameters (an extension): include/ba_hip.h, ba_lm_set_fixed.  fixed_cameras / fixed_points: 1-based indices or a
+# Bool vector of length ncams / npnts; fixed_camera_params: names among (:r, :t, :k1, :k2, :f) applied to every camera, or a
+# Bool (ncams, 9) matrix in block order r1 r2 r3 t1 t2 t3 k1 k2 f.  OR-ed.  Set on the handle at every call.
+const BA_CAMERA_PARAMS = Dict(:r => 0x0007, :t => 0x0038, :k1 => 0x0040, :k2 => 0x0080, :f => 0x0100)
+function _ba_fixed_set(v, n :: Int, what)
+  v === nothing && return falses(n)
+  if eltype(v) == Bool
+    length(v) == n || error("$what: a Bool vector must have length $n")
+    return collect(v)
+  end
+  out = falses(n)
+  for i in v
+    (1 <= i <= n) || error("$what: 1-based indices must lie in 1..$n, got $i")
+    out[i] = true
+  end
+  return out
+end
+function _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, ft :: Int)
+  cam = zeros(UInt16, nlp.ncams)
+  cam[_ba_fixed_set(fixed_cameras, nlp.ncams, "fixed_cameras")] .= 0x01ff
+  if fixed_camera_params isa AbstractMatrix{Bool}
+    size(fixed_camera_params) == (nlp.ncams, 9) || error("fixed_camera_params: a Bool matrix must be ($(nlp.ncams), 9)")
+    for c in 1:nlp.ncams, b in 1:9
+      fixed_camera_params[c, b] && (cam[c] |= UInt16(1) << (b - 1))
+    end
+  elseif fixed_camera_params !== nothing
+    for name in fixed_camera_params
+      haskey(BA_CAMERA_PARAMS, name) || error("fixed_camera_params: names among $(keys(BA_CAMERA_PARAMS))")
+      cam .|= BA_CAMERA_PARAMS[name]
+    end
+  end
+  pnt = UInt8.(_ba_fixed_set(fixed_points, nlp.npnts, "fixed_points"))
+  masked = any(!=(0), cam) || any(!=(0), pnt)
+  (masked && ft == 2) && error("fixed parameters are not supported with facto_type = Float16")
+  GC.@preserve cam pnt begin
+    bacheck(ccall((:ba_lm_set_fixed, libba), Cint, (Ptr{Cvoid}, Ptr{UInt16}, Ptr{UInt8}), nlp.handle,
+                  any(!=(0), cam) ? pointer(cam) : Ptr{UInt16}(C_NULL), any(!=(0), pnt) ? pointer(pnt) : Ptr{UInt8}(C_NULL)))
+  end
+end
+
 # one log row per iteration, the reference's columns (src/lm.jl:120-121,304)
 function _ba_log_row(ctx :: Ptr{Cvoid}, iter :: Cint, f :: Cdouble, df :: Cdouble, njtr :: Cdouble, lambda :: Cdouble,
                      ndelta :: Cdouble, rho :: Cdouble, acc :: Cint) :: Cvoid
@@ -28,7 +68,8 @@ end
 function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normalize :: Symbol, linesearch :: Bool,
                 x :: AbstractVector, facto_type :: DataType, restol, satol, srtol, oatol, ortol, atol, rtol, νd, νm, λ, δd,
                 ite_max :: Int, max_time :: Real, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
-                loss :: Symbol = :linear, f_scale :: Real = 1.0)
+                loss :: Symbol = :linear, f_scale :: Real = 1.0, fixed_cameras = nothing, fixed_points = nothing,
+                fixed_camera_params = nothing)
   # :PCG is an extension of the HIP path (no counterpart in the reference): matrix-free conjugate gradients on the reduced
   # camera system, include/ba_hip.h, ba_lm_opts.facto
   facto in (:QR, :LDL, :PCG) || error("facto must be :QR, :LDL or :PCG")
@@ -47,6 +88,7 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
                Cint(pcg_max_iter), Cint(perm == :Metis ? 1 : 0))
   (loss != :linear && linesearch) && error("a robust loss is not supported with linesearch = true")
   _ba_set_loss(nlp, loss, f_scale)
+  _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, ft)
   st = BaLmStats()
   xd = Vector{Float64}(x)               # the ABI carries the iterate as doubles (exact for Float32 values)
   cb = @cfunction(_ba_log_row, Cvoid, (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cint))
@@ -77,9 +119,11 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              restol = nothing, satol = nothing, srtol = nothing, oatol = nothing, ortol = nothing,
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
                              ite_max :: Int = 200, max_time :: Int = 3600, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
-                             loss :: Symbol = :linear, f_scale = 1.0)
+                             loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
+                             fixed_camera_params = nothing)
   return _ba_lm(model, 1, facto, perm, normalize, linesearch, x, facto_type, restol, satol, srtol, oatol, ortol, atol, rtol,
-                νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter, loss, f_scale)
+                νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter, loss, f_scale, fixed_cameras, fixed_points,
+                fixed_camera_params)
 end
 
 "src/LevenbergMarquardt.jl:16-26 -- the 4-argument method src/solve_ba.jl:26 calls (no linesearch, no facto_type)"
@@ -87,7 +131,8 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              x :: AbstractVector = copy(model.meta.x0),
                              restol = nothing, satol = nothing, srtol = nothing, oatol = nothing, ortol = nothing,
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
-                             ite_max :: Int = 100, loss :: Symbol = :linear, f_scale = 1.0)
+                             ite_max :: Int = 100, loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing,
+                             fixed_points = nothing, fixed_camera_params = nothing)
   return _ba_lm(model, 0, facto, perm, normalize, false, x, eltype(x), restol, satol, srtol, oatol, ortol, atol, rtol,
-                νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale)
+                νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params)
 end
