@@ -46,21 +46,11 @@ extern "C" int ba_device_info(int dev, char *name, size_t name_cap, int *n_cu, s
 
 int ba_scratch(ba_problem *p, int slot, size_t bytes, void **out) {
   if (p->scratch_bytes[slot] < bytes) {
-    if (p->scratch[slot]) (void)hipFree(p->scratch[slot]);
-    p->scratch[slot] = nullptr;
     p->scratch_bytes[slot] = 0;
-    BA_HIP_CHECK(hipMalloc(&p->scratch[slot], bytes));
+    BA_CHECK(p->scratch[slot].alloc((int64_t)bytes));
     p->scratch_bytes[slot] = bytes;
   }
   *out = p->scratch[slot];
-  return BA_OK;
-}
-
-template <typename T>
-static int upload(T **d, const std::vector<T> &h) {
-  size_t bytes = (h.size() ? h.size() : 1) * sizeof(T);
-  BA_HIP_CHECK(hipMalloc((void **)d, bytes));
-  if (!h.empty()) BA_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   return BA_OK;
 }
 
@@ -122,31 +112,27 @@ extern "C" int ba_problem_create(int device, int64_t ncams, int64_t npnts, int64
       cam_obs[(size_t)cc[(size_t)p->h_cam0[(size_t)k]]++] = (int)k;
     }
   }
-  int rc = BA_OK;
-  do {
-    if ((rc = upload(&p->cam0, p->h_cam0)) != BA_OK) break;
-    if ((rc = upload(&p->pnt0, p->h_pnt0)) != BA_OK) break;
-    if ((rc = upload(&p->pt_ptr, p->h_pt_ptr)) != BA_OK) break;
-    if ((rc = upload(&p->pt_obs, p->h_pt_obs)) != BA_OK) break;
-    if ((rc = upload(&p->cam_ptr, cam_ptr)) != BA_OK) break;
-    if ((rc = upload(&p->cam_obs, cam_obs)) != BA_OK) break;
+  auto mirror = [&]() -> int {
+    BA_CHECK(upload(p->cam0, p->h_cam0));
+    BA_CHECK(upload(p->pnt0, p->h_pnt0));
+    BA_CHECK(upload(p->pt_ptr, p->h_pt_ptr));
+    BA_CHECK(upload(p->pt_obs, p->h_pt_obs));
+    BA_CHECK(upload(p->cam_ptr, cam_ptr));
+    BA_CHECK(upload(p->cam_obs, cam_obs));
     std::vector<double> h2((size_t)2 * nobs);
     std::vector<float> h2f((size_t)2 * nobs);
     for (int64_t k = 0; k < 2 * nobs; k++) {
       h2[(size_t)k] = pt2d[k];
       h2f[(size_t)k] = (float)pt2d[k];
     }
-    if ((rc = upload(&p->pt2d, h2)) != BA_OK) break;
-    if ((rc = upload(&p->pt2d_f32, h2f)) != BA_OK) break;
-    hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e != hipSuccess) {
-      ba_set_error("ba_problem_create: %s", hipGetErrorString(e));
-      rc = BA_ERR_HIP;
-    }
-  } while (0);
-  if (rc != BA_OK) {
+    BA_CHECK(upload(p->pt2d, h2));
+    BA_CHECK(upload(p->pt2d_f32, h2f));
+    BA_CHECK(p->stream.create(hipStreamNonBlocking));
+    BA_CHECK(p->ev0.create());
+    BA_CHECK(p->ev1.create());
+    return BA_OK;
+  };
+  if (const int rc = mirror(); rc != BA_OK) {
     ba_problem_destroy(p);
     return rc;
   }
@@ -157,16 +143,8 @@ extern "C" int ba_problem_create(int device, int64_t ncams, int64_t npnts, int64
 extern "C" void ba_problem_destroy(ba_problem *p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
-  lm_free(p);
   comm_free(p);
-  void *ptrs[] = {p->cam0, p->pnt0, p->pt2d, p->pt2d_f32, p->pt_ptr, p->pt_obs, p->cam_ptr, p->cam_obs,
-                  p->scratch[0], p->scratch[1], p->scratch[2], p->scratch[3], p->d_fix_cam, p->d_fix_pnt};
-  for (void *q : ptrs)
-    if (q) (void)hipFree(q);
-  if (p->ev0) (void)hipEventDestroy(p->ev0);
-  if (p->ev1) (void)hipEventDestroy(p->ev1);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
+  delete p;  // (the LM workspace first: ~ba_problem)
 }
 
 extern "C" int ba_problem_dims(const ba_problem *p, int64_t *ncams, int64_t *npnts, int64_t *nobs, int64_t *nvar,
@@ -306,13 +284,19 @@ extern "C" int ba_jtr(ba_problem *p, const double *vals, const double *r, double
 extern "C" int ba_dev_malloc(ba_problem *p, size_t bytes, void **d_ptr) {
   if (!p || !d_ptr) return BA_ERR_ARG;
   BA_HIP_CHECK(hipSetDevice(p->device));
-  BA_HIP_CHECK(hipMalloc(d_ptr, bytes ? bytes : 1));
+  if (bytes > (size_t)INT64_MAX) {
+    ba_set_error("ba_dev_malloc: %zu bytes", bytes);
+    return BA_ERR_HIP;
+  }
+  DevBuf<char> b;
+  BA_CHECK(b.alloc((int64_t)bytes));
+  *d_ptr = b.release();  // the caller's, until ba_dev_free
   return BA_OK;
 }
 extern "C" int ba_dev_free(ba_problem *p, void *d_ptr) {
   if (!p) return BA_ERR_ARG;
   BA_HIP_CHECK(hipSetDevice(p->device));
-  if (d_ptr) BA_HIP_CHECK(hipFree(d_ptr));
+  if (d_ptr) BA_HIP_CHECK(free_dev(d_ptr));
   return BA_OK;
 }
 // Copies between host and device memory are ORDERED ON A STREAM and complete on return: the copy is enqueued on `stream`

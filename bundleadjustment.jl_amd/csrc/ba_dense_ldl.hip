@@ -1649,7 +1649,7 @@ void dense_ldl_layout(int64_t nt, int world, std::vector<int64_t> *col_off, std:
 }
 
 template <typename T>
-int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, T *external_S, int world, int rank, bool lazy_S, bool own_only) {
+int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, int world, int rank, bool lazy_S, bool own_only) {
   int64_t nt = (n_unpadded + NB - 1) / NB;
   if (nt < 1) nt = 1;
   w->n = nt * NB;
@@ -1670,8 +1670,7 @@ int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, T *external_S, int worl
       w->hco()[j] = ((j / 2) % world == rank) ? w->hco()[j] - base : BA_NO_TILE;
     w->s_tiles = std::max<int64_t>(1, w->own_range[(size_t)rank + 1] - base);
   }
-  BA_HIP_CHECK(hipMalloc((void **)&w->col_tab, w->h_col_tab.size() * sizeof(int64_t)));
-  BA_HIP_CHECK(hipMemcpy(w->col_tab, w->h_col_tab.data(), w->h_col_tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  BA_CHECK(upload(w->col_tab, w->h_col_tab));
   w->col_off = w->col_tab + 1;
   // the tile columns this rank owns (pairs q with q % world == rank), ascending, with running tile counts
   w->h_own_cols.clear();
@@ -1681,92 +1680,43 @@ int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, T *external_S, int worl
       w->h_own_cols.push_back((int)j);
       w->h_own_pref.push_back(w->h_own_pref.back() + (nt - j));
     }
-  BA_HIP_CHECK(hipMalloc((void **)&w->own_cols, (w->h_own_cols.size() + 1) * sizeof(int)));
-  BA_HIP_CHECK(hipMalloc((void **)&w->own_pref, w->h_own_pref.size() * sizeof(int64_t)));
-  if (!w->h_own_cols.empty())
-    BA_HIP_CHECK(hipMemcpy(w->own_cols, w->h_own_cols.data(), w->h_own_cols.size() * sizeof(int), hipMemcpyHostToDevice));
-  BA_HIP_CHECK(hipMemcpy(w->own_pref, w->h_own_pref.data(), w->h_own_pref.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-  BA_HIP_CHECK(hipMalloc((void **)&w->flag_sum, sizeof(double)));
-  if (external_S) {
-    w->S = external_S;
-    w->own_S = false;
-  } else if (!lazy_S) {
-    BA_HIP_CHECK(hipMalloc((void **)&w->S, (size_t)w->s_tiles * NB * NB * sizeof(T)));
-    w->own_S = true;
-  }
-  if (!lazy_S) BA_HIP_CHECK(hipMalloc((void **)&w->V, (size_t)8 * nt * NB * NB * sizeof(T)));  // (two runs) x (two slots) x two panels of L*D
-  if (!lazy_S && w->own_only) {
-    BA_HIP_CHECK(hipMalloc((void **)&w->Lb, (size_t)4 * nt * NB * NB * sizeof(T)));  // their L = V D^-1
-    BA_HIP_CHECK(hipMalloc((void **)&w->bpart, (size_t)2 * nt * NB * sizeof(T)));
-  }
-  BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_chain, hipEventDisableTiming | hipEventReleaseToDevice));
-  BA_HIP_CHECK(hipMalloc((void **)&w->Linv, (size_t)nt * NB * NB * sizeof(T)));
+  BA_CHECK(upload(w->own_cols, w->h_own_cols, 1));
+  BA_CHECK(upload(w->own_pref, w->h_own_pref));
+  BA_CHECK(w->flag_sum.alloc(1));
+  if (!lazy_S) BA_CHECK(dense_ldl_alloc_S(w));
+  BA_CHECK(w->ev_chain.create(hipEventDisableTiming | hipEventReleaseToDevice));
+  BA_CHECK(w->Linv.alloc(nt * NB * NB));
   // k_ldl_diag writes the lower triangle of each inverse only; the consumers read whole tiles
   BA_HIP_CHECK(hipMemset(w->Linv, 0, (size_t)nt * NB * NB * sizeof(T)));
   BA_HIP_CHECK(hipDeviceSynchronize());  // (a null-stream memset is not ordered against the non-blocking streams that use Linv)
-  BA_HIP_CHECK(hipMalloc((void **)&w->D, (size_t)nt * NB * 2 * sizeof(T)));  // D | y scratch
-  BA_HIP_CHECK(hipMalloc((void **)&w->flag, sizeof(int)));
-  BA_HIP_CHECK(hipMalloc((void **)&w->ready, (size_t)nt * sizeof(int)));
-  BA_HIP_CHECK(hipStreamCreateWithFlags(&w->hoist, hipStreamNonBlocking));
+  BA_CHECK(w->D.alloc(nt * NB * 2));  // D | y scratch
+  BA_CHECK(w->flag.alloc(1));
+  BA_CHECK(w->ready.alloc(nt));
+  BA_CHECK(w->hoist.create(hipStreamNonBlocking));
   {  // the stream of the block-sparse schedule's look-ahead: lowest priority, so that the panel chain's kernels are placed first
     int lo = 0, hi = 0;
     BA_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    BA_HIP_CHECK(hipStreamCreateWithPriority(&w->rest, hipStreamNonBlocking, lo));
+    BA_CHECK(w->rest.create(hipStreamNonBlocking, lo));
   }
-  BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_top, hipEventDisableTiming | hipEventReleaseToDevice));
+  BA_CHECK(w->ev_top.create(hipEventDisableTiming | hipEventReleaseToDevice));
   // the distributed factorisation's events order work whose data LEAVES the device (panels handed to the transport):
   // default release scope, not hipEventReleaseToDevice as the single-GPU hoist events above
-  BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_dtop, hipEventDisableTiming));
-  BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_dchain, hipEventDisableTiming));
+  BA_CHECK(w->ev_dtop.create(hipEventDisableTiming));
+  BA_CHECK(w->ev_dchain.create(hipEventDisableTiming));
   for (int q = 0; q < 2; q++) {
-    BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_recv[q], hipEventDisableTiming));
-    BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_upd[q], hipEventDisableTiming));
+    BA_CHECK(w->ev_recv[q].create(hipEventDisableTiming));
+    BA_CHECK(w->ev_upd[q].create(hipEventDisableTiming));
   }
   return set_kernel_attrs<T>();
 }
 
 template <typename T>
 int dense_ldl_alloc_S(DenseLDLT<T> *w) {
-  if (!w->S) {
-    BA_HIP_CHECK(hipMalloc((void **)&w->S, (size_t)w->s_tiles * NB * NB * sizeof(T)));
-    w->own_S = true;
-  }
-  if (!w->V) BA_HIP_CHECK(hipMalloc((void **)&w->V, (size_t)8 * w->nt * NB * NB * sizeof(T)));
-  if (!w->Lb && w->own_only) BA_HIP_CHECK(hipMalloc((void **)&w->Lb, (size_t)4 * w->nt * NB * NB * sizeof(T)));
-  if (!w->bpart && w->own_only) BA_HIP_CHECK(hipMalloc((void **)&w->bpart, (size_t)2 * w->nt * NB * sizeof(T)));
+  if (!w->S) BA_CHECK(w->S.alloc(w->s_tiles * NB * NB));
+  if (!w->V) BA_CHECK(w->V.alloc(8 * w->nt * NB * NB));  // (two runs) x (two slots) x two panels of L*D
+  if (!w->Lb && w->own_only) BA_CHECK(w->Lb.alloc(4 * w->nt * NB * NB));  // their L = V D^-1
+  if (!w->bpart && w->own_only) BA_CHECK(w->bpart.alloc(2 * w->nt * NB));
   return BA_OK;
-}
-
-template <typename T>
-void dense_ldl_free(DenseLDLT<T> *w) {
-  if (w->own_S && w->S) (void)hipFree(w->S);
-  if (w->V) (void)hipFree(w->V);
-  if (w->Lb) (void)hipFree(w->Lb);
-  if (w->bpart) (void)hipFree(w->bpart);
-  if (w->Linv) (void)hipFree(w->Linv);
-  if (w->D) (void)hipFree(w->D);
-  if (w->flag) (void)hipFree(w->flag);
-  if (w->col_tab) (void)hipFree(w->col_tab);
-  if (w->own_cols) (void)hipFree(w->own_cols);
-  if (w->own_pref) (void)hipFree(w->own_pref);
-  if (w->flag_sum) (void)hipFree(w->flag_sum);
-  if (w->ready) (void)hipFree(w->ready);
-  if (w->prow) (void)hipFree(w->prow);
-  if (w->lcol) (void)hipFree(w->lcol);
-  if (w->lpair) (void)hipFree(w->lpair);
-  if (w->upd_ij) (void)hipFree(w->upd_ij);
-  if (w->own_tiles) (void)hipFree(w->own_tiles);
-  if (w->hoist) (void)hipStreamDestroy(w->hoist);
-  if (w->rest) (void)hipStreamDestroy(w->rest);
-  if (w->ev_top) (void)hipEventDestroy(w->ev_top);
-  if (w->ev_chain) (void)hipEventDestroy(w->ev_chain);
-  if (w->ev_dtop) (void)hipEventDestroy(w->ev_dtop);
-  if (w->ev_dchain) (void)hipEventDestroy(w->ev_dchain);
-  for (int q = 0; q < 2; q++) {
-    if (w->ev_recv[q]) (void)hipEventDestroy(w->ev_recv[q]);
-    if (w->ev_upd[q]) (void)hipEventDestroy(w->ev_upd[q]);
-  }
-  *w = DenseLDLT<T>();
 }
 
 template <typename T>
@@ -1973,10 +1923,9 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_p
 
 template <typename T>
 int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
-  for (void *q : {(void *)w->prow, (void *)w->lcol, (void *)w->lpair, (void *)w->upd_ij, (void *)w->own_tiles})
-    if (q) (void)hipFree(q);
-  w->prow = w->lcol = w->lpair = nullptr;
-  w->upd_ij = w->own_tiles = nullptr;
+  for (DevBuf<int> *q : {&w->prow, &w->lcol, &w->lpair}) q->reset();
+  w->upd_ij.reset();
+  w->own_tiles.reset();
   w->pat = pat;
   w->sparse = pat != nullptr;
   if (!pat) return BA_OK;
@@ -2030,8 +1979,7 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
           if (pat->prow[(size_t)l] > j) tiles.push_back(make_int2(pat->prow[(size_t)l], j));
       }
       BA_HIP_CHECK(hipMemcpy(w->own_pref, w->h_own_pref.data(), w->h_own_pref.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-      BA_HIP_CHECK(hipMalloc((void **)&w->own_tiles, (tiles.size() + 1) * sizeof(int2)));
-      if (!tiles.empty()) BA_HIP_CHECK(hipMemcpy(w->own_tiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice));
+      BA_CHECK(upload(w->own_tiles, tiles, 1));
       std::vector<int2> upd;
       const int npairs = (int)((nt + 1) / 2);
       w->h_upd_ptr.assign(1, 0);
@@ -2046,27 +1994,16 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
         }
         w->h_upd_ptr.push_back((int)upd.size());
       }
-      BA_HIP_CHECK(hipMalloc((void **)&w->upd_ij, (upd.size() + 1) * sizeof(int2)));
-      if (!upd.empty()) BA_HIP_CHECK(hipMemcpy(w->upd_ij, upd.data(), upd.size() * sizeof(int2), hipMemcpyHostToDevice));
+      BA_CHECK(upload(w->upd_ij, upd, 1));
     }
     w->h_col_tab.swap(tab);
-    if (w->col_tab) (void)hipFree(w->col_tab);
-    w->col_tab = nullptr;
-    BA_HIP_CHECK(hipMalloc((void **)&w->col_tab, w->h_col_tab.size() * sizeof(int64_t)));
-    BA_HIP_CHECK(hipMemcpy(w->col_tab, w->h_col_tab.data(), w->h_col_tab.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    BA_CHECK(upload(w->col_tab, w->h_col_tab));
     w->col_off = w->col_tab + 1;
-    if (w->S && w->own_S) {  // (a workspace allocated before its pattern was known: Float32 twin)
-      (void)hipFree(w->S);
-      w->S = nullptr;
-      BA_HIP_CHECK(hipMalloc((void **)&w->S, (size_t)w->s_tiles * NB * NB * sizeof(T)));
-    }
+    if (w->S) BA_CHECK(w->S.alloc(w->s_tiles * NB * NB));  // (a workspace allocated before its pattern was known: Float32 twin)
   }
-  BA_HIP_CHECK(hipMalloc((void **)&w->prow, (pat->prow.size() + 1) * sizeof(int)));
-  BA_HIP_CHECK(hipMalloc((void **)&w->lcol, (pat->lcol.size() + 1) * sizeof(int)));
-  if (!pat->prow.empty()) BA_HIP_CHECK(hipMemcpy(w->prow, pat->prow.data(), pat->prow.size() * sizeof(int), hipMemcpyHostToDevice));
-  if (!pat->lcol.empty()) BA_HIP_CHECK(hipMemcpy(w->lcol, pat->lcol.data(), pat->lcol.size() * sizeof(int), hipMemcpyHostToDevice));
-  BA_HIP_CHECK(hipMalloc((void **)&w->lpair, (pat->lpair.size() + 1) * sizeof(int)));
-  if (!pat->lpair.empty()) BA_HIP_CHECK(hipMemcpy(w->lpair, pat->lpair.data(), pat->lpair.size() * sizeof(int), hipMemcpyHostToDevice));
+  BA_CHECK(upload(w->prow, pat->prow, 1));
+  BA_CHECK(upload(w->lcol, pat->lcol, 1));
+  BA_CHECK(upload(w->lpair, pat->lpair, 1));
   return BA_OK;
 }
 
@@ -2737,8 +2674,7 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   BA_HIP_CHECK(hipSetDevice(device));
   ba_problem tmp;  // only used for its (disabled) profiling slots
   DenseLDLT<T> w;
-  int rc = dense_ldl_alloc<T>(&w, n, nullptr);
-  if (rc != BA_OK) return rc;
+  BA_CHECK(dense_ldl_alloc<T>(&w, n));
   const int64_t npad = w.n;
   std::vector<T> tiles((size_t)dense_ldl_tiles_doubles(n), (T)0);
   for (int64_t i = 0; i < npad; i++) {
@@ -2751,15 +2687,15 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   }
   std::vector<T> bb((size_t)npad, (T)0);
   for (int64_t i = 0; i < n; i++) bb[(size_t)i] = (T)b[i];
-  T *d_b = nullptr;
+  DevBuf<T> d_b;
   hipStream_t st = nullptr;
-  hipEvent_t e0, e1;
-  BA_HIP_CHECK(hipMalloc((void **)&d_b, (size_t)npad * sizeof(T)));
+  HipEvent e0, e1;
+  BA_CHECK(d_b.alloc(npad));
   BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(T), hipMemcpyHostToDevice));
   BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), (size_t)npad * sizeof(T), hipMemcpyHostToDevice));
-  BA_HIP_CHECK(hipEventCreate(&e0));
-  BA_HIP_CHECK(hipEventCreate(&e1));
-  int zp = 0;
+  BA_CHECK(e0.create());
+  BA_CHECK(e1.create());
+  int rc = BA_OK, zp = 0;
   for (int attempt = 0; attempt < 2; attempt++) {  // (the forward substitution rides along with the factorisation)
     BA_HIP_CHECK(hipEventRecord(e0, st));
     rc = dense_ldl_factor<T>(&tmp, &w, st, nullptr, d_b);
@@ -2778,10 +2714,6 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   if (factor_ms) *factor_ms = ms;
   BA_HIP_CHECK(hipMemcpy(bb.data(), d_b, (size_t)npad * sizeof(T), hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n; i++) x[i] = (double)bb[(size_t)i];
-  (void)hipFree(d_b);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  dense_ldl_free<T>(&w);
   if (rc == BA_OK && zp) {
     ba_set_error("dense LDL': exactly zero pivot");
     return BA_ERR_ZERO_PIVOT;
@@ -2800,12 +2732,10 @@ extern "C" int ba_dense_ldl_solve_f32(int device, int64_t n, const double *a_low
   return dense_solve_host<float>(device, n, a_lower_rowmajor, b, x, factor_ms);
 }
 
-template int dense_ldl_alloc<double>(DenseLDLT<double> *, int64_t, double *, int, int, bool, bool);
-template int dense_ldl_alloc<float>(DenseLDLT<float> *, int64_t, float *, int, int, bool, bool);
+template int dense_ldl_alloc<double>(DenseLDLT<double> *, int64_t, int, int, bool, bool);
+template int dense_ldl_alloc<float>(DenseLDLT<float> *, int64_t, int, int, bool, bool);
 template int dense_ldl_alloc_S<double>(DenseLDLT<double> *);
 template int dense_ldl_alloc_S<float>(DenseLDLT<float> *);
-template void dense_ldl_free<double>(DenseLDLT<double> *);
-template void dense_ldl_free<float>(DenseLDLT<float> *);
 template int dense_ldl_factor<double>(ba_problem *, DenseLDLT<double> *, hipStream_t, int *, double *);
 template int dense_ldl_factor<float>(ba_problem *, DenseLDLT<float> *, hipStream_t, int *, float *);
 template int dense_ldl_use_pattern<double>(DenseLDLT<double> *, const TilePattern *);

@@ -59,12 +59,12 @@ __global__ __launch_bounds__(FB) void k_fix_mask(int64_t nobs, const int *__rest
 int fix_upload(ba_problem *p) {
   if (!p->fix_dirty) return BA_OK;
   if (p->fix_ncam > 0) {
-    if (!p->d_fix_cam) BA_HIP_CHECK(hipMalloc((void **)&p->d_fix_cam, (size_t)(p->ncams > 0 ? p->ncams : 1) * sizeof(uint16_t)));
+    if (!p->d_fix_cam) BA_CHECK(p->d_fix_cam.alloc(p->ncams));
     BA_HIP_CHECK(hipMemcpyAsync(p->d_fix_cam, p->h_fix_cam.data(), (size_t)p->ncams * sizeof(uint16_t), hipMemcpyHostToDevice,
                                 p->stream));
   }
   if (p->fix_npnt > 0) {
-    if (!p->d_fix_pnt) BA_HIP_CHECK(hipMalloc((void **)&p->d_fix_pnt, (size_t)(p->npnts > 0 ? p->npnts : 1)));
+    if (!p->d_fix_pnt) BA_CHECK(p->d_fix_pnt.alloc(p->npnts));
     BA_HIP_CHECK(hipMemcpyAsync(p->d_fix_pnt, p->h_fix_pnt.data(), (size_t)p->npnts, hipMemcpyHostToDevice, p->stream));
   }
   BA_HIP_CHECK(hipStreamSynchronize(p->stream));  // (the host tables may change with the next ba_lm_set_fixed)

@@ -37,6 +37,94 @@ inline int env_int(const char *name, int dflt) {
   return e ? atoi(e) : dflt;
 }
 
+// ---- owners of device resources -------------------------------------------------------------------------------------------
+// Every device buffer, pinned host buffer, stream, event and graph the library creates is held by one of these and released
+// by it: when the owner is destroyed, reset, moved onto or filled again.  They are the only code that creates or releases
+// such a resource (tests/test_host.py).  Move-only; an owner converts to its raw handle, so launch sites and pointer
+// arithmetic read as with the raw one.  Views into an owner's memory stay raw pointers.  Release needs the handle's device
+// to be current: every path into a teardown sets it.
+template <typename H, hipError_t (*Release)(H)>
+class Owner {
+ public:
+  Owner() = default;
+  Owner(Owner &&o) noexcept : h_(o.release()) {}
+  Owner &operator=(Owner &&o) noexcept {
+    if (this != &o) {
+      reset();
+      h_ = o.release();
+    }
+    return *this;
+  }
+  ~Owner() { reset(); }
+  void reset() {
+    if (h_) (void)Release(h_);
+    h_ = nullptr;
+  }
+  H release() {  // the caller takes the handle over
+    H h = h_;
+    h_ = nullptr;
+    return h;
+  }
+  H *out() {  // for a call that creates the handle in place
+    reset();
+    return &h_;
+  }
+  operator H() const { return h_; }
+
+ protected:
+  H h_ = nullptr;
+};
+
+template <typename T>
+hipError_t free_dev(T *p) { return hipFree(p); }
+template <typename T>
+hipError_t free_pinned(T *p) { return hipHostFree(p); }
+
+// n elements of T in device memory, or (Pinned) in pinned host memory the device can address; n <= 0 allocates one
+template <typename T, bool Pinned = false>
+class Buf : public Owner<T *, Pinned ? free_pinned<T> : free_dev<T>> {
+ public:
+  int alloc(int64_t n) {
+    const size_t bytes = (size_t)(n > 0 ? n : 1) * sizeof(T);
+    if (Pinned) BA_HIP_CHECK(hipHostMalloc((void **)this->out(), bytes));
+    else BA_HIP_CHECK(hipMalloc((void **)this->out(), bytes));
+    return BA_OK;
+  }
+};
+template <typename T>
+using DevBuf = Buf<T>;
+template <typename T>
+using PinnedBuf = Buf<T, true>;
+
+class HipStream : public Owner<hipStream_t, hipStreamDestroy> {
+ public:
+  int create(unsigned flags) {
+    BA_HIP_CHECK(hipStreamCreateWithFlags(out(), flags));
+    return BA_OK;
+  }
+  int create(unsigned flags, int priority) {
+    BA_HIP_CHECK(hipStreamCreateWithPriority(out(), flags, priority));
+    return BA_OK;
+  }
+};
+class HipEvent : public Owner<hipEvent_t, hipEventDestroy> {
+ public:
+  int create(unsigned flags = hipEventDefault) {
+    BA_HIP_CHECK(hipEventCreateWithFlags(out(), flags));
+    return BA_OK;
+  }
+};
+using HipGraph = Owner<hipGraph_t, hipGraphDestroy>;
+using HipGraphExec = Owner<hipGraphExec_t, hipGraphExecDestroy>;
+
+// d <- a new device buffer of h.size() + extra elements (at least one) that starts with h
+template <typename T>
+int upload(DevBuf<T> &d, const std::vector<T> &h, size_t extra = 0) {
+  BA_CHECK(d.alloc((int64_t)(h.size() + extra)));
+  if (!h.empty()) BA_HIP_CHECK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+  return BA_OK;
+}
+
 // ---- dense reduced-camera system ------------------------------------------------------------------
 // S is stored as the lower block triangle of NB x NB tiles, each tile contiguous row-major (128 KiB).  Tile (i,j),
 // j <= i, sits at tile index col_off[j] + (i - j): a tile column is contiguous (rows j..nt-1).  Tile columns are taken
@@ -120,52 +208,51 @@ struct ProfSlot {
 template <typename T>
 struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*ncams padded to nt*NB
   int64_t n = 0, nt = 0;
-  T *S = nullptr;          // packed lower tiles (may alias the caller's reduce buffer)
-  T *V = nullptr;          // 4 x nt tiles: V_i = L_ik * D_k of two panel pairs (double-buffered for the look-ahead)
-  T *Linv = nullptr;       // nt tiles: inverse of each unit-lower diagonal tile
-  T *D = nullptr;          // nt*NB pivots (+ nt*NB scratch)
+  DevBuf<T> S;             // packed lower tiles
+  DevBuf<T> V;             // 4 x nt tiles: V_i = L_ik * D_k of two panel pairs (double-buffered for the look-ahead)
+  DevBuf<T> Linv;          // nt tiles: inverse of each unit-lower diagonal tile
+  DevBuf<T> D;             // nt*NB pivots (+ nt*NB scratch)
   int64_t *col_off = nullptr;           // device: tile column offsets (see tix)
   std::vector<int64_t> h_col_tab;       // host copy of the table: [head | nt column offsets | (compressed) nt x nt row positions]
-  int64_t *col_tab = nullptr;           // the device allocation (col_off = col_tab + 1)
+  DevBuf<int64_t> col_tab;              // the device allocation (col_off = col_tab + 1)
   const int64_t *hco() const { return h_col_tab.data() + 1; }
   int64_t *hco() { return h_col_tab.data() + 1; }
   std::vector<int64_t> own_range;       // world + 1 tile offsets: rank r owns tiles [own_range[r], own_range[r+1])
   int world = 1, rank = 0;              // distribution of the tile column pairs (owner of pair q: q % world)
   std::vector<int> h_own_cols;          // tile columns owned by this rank, ascending
   std::vector<int64_t> h_own_pref;      // h_own_pref[m] = tiles in the owned columns before h_own_cols[m]
-  int *own_cols = nullptr;              // device copies
-  int64_t *own_pref = nullptr;
-  double *flag_sum = nullptr;           // device double: the pivot flag on its way through the all-reduce
-  int *flag = nullptr;     // device int: set to 1 on an exactly zero pivot (2: a hoisted diagonal tile never became ready)
-  int *ready = nullptr;    // nt device ints: tile (k,k) has received its last trailing update (hoisted-diagonal schedule)
-  hipStream_t hoist = nullptr;   // second stream of the hoisted-diagonal schedule (no CU mask)
-  hipStream_t rest = nullptr;    // look-ahead of the block-sparse schedule: the rest of a pair's update (lowest priority)
-  hipEvent_t ev_top = nullptr;
+  DevBuf<int> own_cols;                 // device copies
+  DevBuf<int64_t> own_pref;
+  DevBuf<double> flag_sum;              // device double: the pivot flag on its way through the all-reduce
+  DevBuf<int> flag;        // device int: set to 1 on an exactly zero pivot (2: a hoisted diagonal tile never became ready)
+  DevBuf<int> ready;       // nt device ints: tile (k,k) has received its last trailing update (hoisted-diagonal schedule)
+  HipStream hoist;               // second stream of the hoisted-diagonal schedule (no CU mask)
+  HipStream rest;                // look-ahead of the block-sparse schedule: the rest of a pair's update (lowest priority)
+  HipEvent ev_top;
   bool hoist_disabled = false;   // a hoisted kernel once timed out (kernels serialised by a profiler): never again on this handle
   bool hoisting = false;         // the factorisation forks onto `hoist` (set by dense_ldl_factor's schedule choice)
-  bool own_S = true;
-  hipEvent_t ev_chain = nullptr;  // recorded behind each hoisted diagonal kernel
+  HipEvent ev_chain;              // recorded behind each hoisted diagonal kernel
   // distributed factorisation with look-ahead: panels of pair q received (transfer stream), update of pair q launched
-  hipEvent_t ev_recv[2] = {nullptr, nullptr}, ev_upd[2] = {nullptr, nullptr};
+  HipEvent ev_recv[2], ev_upd[2];
   // per-rank ownership of S (distributed factorisation): S holds this rank's tile columns only (s_tiles tiles), col_off /
   // hco() are rank-local offsets (negative for other ranks' columns), h_glob_off the owner-major global layout;
   // Lb: L = V D^-1 of the panel pairs in flight (the layout of V), bpart: partial products of the backward sweep
   bool own_only = false;
   int64_t s_tiles = 0;
   std::vector<int64_t> h_glob_off;
-  T *Lb = nullptr, *bpart = nullptr;
+  DevBuf<T> Lb, bpart;
   // block-sparse S (one GPU): the pattern's row / column lists on the device; null pattern = dense
   bool sparse = false;
   const TilePattern *pat = nullptr;
-  int *prow = nullptr, *lcol = nullptr, *lpair = nullptr;
+  DevBuf<int> prow, lcol, lpair;
   // ... on several ranks (per-rank ownership of the PATTERN's tile columns): tiles stored per tile column, the (i, j) of every
   // tile this rank stores in storage order (column scaling), and per tile column pair q the tiles (i, j) -- both in U_q, j
   // owned by this rank, sorted by (j, i) -- its trailing update touches here; the first h_upd_lead[q] of them lie in the next
   // pair's own tile columns (look-ahead of the distributed factorisation)
   std::vector<int64_t> h_col_cnt;
   std::vector<int> h_upd_ptr, h_upd_lead;
-  int2 *upd_ij = nullptr, *own_tiles = nullptr;
-  hipEvent_t ev_dtop = nullptr, ev_dchain = nullptr;  // distributed factorisation: fork behind the reduce of S, end of the owner's panel chain
+  DevBuf<int2> upd_ij, own_tiles;
+  HipEvent ev_dtop, ev_dchain;  // distributed factorisation: fork behind the reduce of S, end of the owner's panel chain
 };
 typedef DenseLDLT<double> DenseLDL;
 
@@ -180,23 +267,25 @@ struct BaComm {
   bool active() const { return hook != nullptr || nccl != nullptr; }  // a 1-rank communicator still exercises the path
 };
 
+void lm_free(ba_problem *p);  // the LM workspace (ba_lm.hip)
+
 struct ba_problem {
   int device = 0;
-  hipStream_t stream = nullptr;
+  HipStream stream;
   int64_t ncams = 0, npnts = 0, nobs = 0;
   // device mirrors (0-based int32)
-  int *cam0 = nullptr, *pnt0 = nullptr;
-  double *pt2d = nullptr;
-  float *pt2d_f32 = nullptr;
+  DevBuf<int> cam0, pnt0;
+  DevBuf<double> pt2d;
+  DevBuf<float> pt2d_f32;
   // observation lists sorted by point / by camera (stable) for the deterministic reductions
-  int *pt_ptr = nullptr, *pt_obs = nullptr;    // npnts+1, nobs
-  int *cam_ptr = nullptr, *cam_obs = nullptr;  // ncams+1, nobs
+  DevBuf<int> pt_ptr, pt_obs;    // npnts+1, nobs
+  DevBuf<int> cam_ptr, cam_obs;  // ncams+1, nobs
   bool point_sorted = false;                   // observations already grouped by point (BAL order)
   std::vector<int> h_cam0, h_pnt0, h_pt_ptr, h_pt_obs;
   // scratch for the host-pointer entries
-  void *scratch[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<char> scratch[4];
   size_t scratch_bytes[4] = {0, 0, 0, 0};
-  // LM workspace (allocated at the first solve)
+  // LM workspace (allocated at the first solve, ba_lm.hip; released by lm_free)
   struct LMWork *lm = nullptr;
   // robust loss of the LM entries (ba_lm_set_loss): BA_LOSS_*, scale c > 0
   int loss = BA_LOSS_LINEAR;
@@ -206,8 +295,8 @@ struct ba_problem {
   std::vector<uint16_t> h_fix_cam;
   std::vector<uint8_t> h_fix_pnt;
   int64_t fix_ncam = 0, fix_npnt = 0;  // fixed camera components, fixed points
-  uint16_t *d_fix_cam = nullptr;
-  uint8_t *d_fix_pnt = nullptr;
+  DevBuf<uint16_t> d_fix_cam;
+  DevBuf<uint8_t> d_fix_pnt;
   bool fix_dirty = false;
   bool fix_on() const { return fix_ncam > 0 || fix_npnt > 0; }
   // communication (multi-GPU)
@@ -216,7 +305,8 @@ struct ba_problem {
   // profiling
   bool prof_on = false;
   ProfSlot prof[PC_COUNT];
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  HipEvent ev0, ev1;
+  ~ba_problem() { lm_free(this); }
 };
 
 // RAII-less helper: times one kernel class with an event pair when profiling is on (synchronises).
@@ -258,13 +348,10 @@ int launch_cam_blocks(ba_problem *p, const double *d_J, const double *d_r, doubl
 
 // ---- dense LDL^T (ba_dense_ldl.hip) ---------------------------------------------------------------
 template <typename T>
-int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, T *external_S, int world = 1, int rank = 0, bool lazy_S = false,
-                    bool own_only = false);
+int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, int world = 1, int rank = 0, bool lazy_S = false, bool own_only = false);
 // lazy_S: the tiles of S (and the panel buffers V) are left out until dense_ldl_alloc_S
 template <typename T>
 int dense_ldl_alloc_S(DenseLDLT<T> *w);
-template <typename T>
-void dense_ldl_free(DenseLDLT<T> *w);
 int64_t dense_ldl_tiles_doubles(int64_t n_unpadded);  // number of ELEMENTS of the packed lower tiles
 // factor S in place (L below the diagonal tiles' diagonal, D separately); *zero_pivot set on exact zero pivot.
 // d_b != null: the forward substitution L y = b of that right-hand side (length nt*NB, clobbered) is fused into the
@@ -294,6 +381,3 @@ int comm_reduce_scatter(ba_problem *p, void *d_buf, int64_t count, bool f32, hip
 int comm_group_begin(ba_problem *p);  // RCCL: fuse the calls up to comm_group_end into one launch
 int comm_group_end(ba_problem *p);
 void comm_free(ba_problem *p);
-
-// ---- LM (ba_lm.hip) ---------------------------------------------------------------------------------
-void lm_free(ba_problem *p);

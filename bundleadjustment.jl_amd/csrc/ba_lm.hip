@@ -34,19 +34,6 @@ enum { SH_RSQ = 0, SH_GP, SH_X_P, SH_RTSQ, SH_RSQ_TRIAL, SH_MODEL, SH_DELTA_P, S
 constexpr int SH_LIN_COUNT = 3, SH_TRIAL_FIRST = 4, SH_TRIAL_COUNT = 3;
 enum { RP_DELTA_C = 0, RP_X_C, RP_GC, RP_COUNT = 8 };
 
-template <typename T>
-int dmalloc(T **ptr, int64_t count) {
-  BA_HIP_CHECK(hipMalloc((void **)ptr, (size_t)(count > 0 ? count : 1) * sizeof(T)));
-  return BA_OK;
-}
-
-template <typename T>
-int upload_vec(T **d, const std::vector<T> &h) {
-  BA_CHECK(dmalloc(d, (int64_t)h.size()));
-  if (!h.empty()) BA_HIP_CHECK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return BA_OK;
-}
-
 // Build the (camera_a >= camera_b)-sorted list of observation pairs sharing a point.  "Camera" here is the BLOCK ROW of S the
 // camera sits at: pos[c] under a fill-reducing camera ordering (empty: c itself).
 int build_tasks(ba_problem *p, SchurTasks *T, const std::vector<int> &pos) {
@@ -152,19 +139,19 @@ int build_tasks(ba_problem *p, SchurTasks *T, const std::vector<int> &pos) {
     T->nchunks = (int64_t)ct0.size();
     T->h_skey = skey;
     if (T->nsplit > 0) {
-      BA_CHECK(upload_vec(&T->skey, skey));
-      BA_CHECK(upload_vec(&T->skey_c0, skey_c0));
-      BA_CHECK(upload_vec(&T->chunk_t0, ct0));
-      BA_CHECK(upload_vec(&T->chunk_t1, ct1));
-      BA_CHECK(dmalloc(&T->partial, 81 * T->nchunks));
+      BA_CHECK(upload(T->skey, skey));
+      BA_CHECK(upload(T->skey_c0, skey_c0));
+      BA_CHECK(upload(T->chunk_t0, ct0));
+      BA_CHECK(upload(T->chunk_t1, ct1));
+      BA_CHECK(T->partial.alloc(81 * T->nchunks));
     }
   }
   T->h_key_cb = key_cb;
-  BA_CHECK(upload_vec(&T->key_ptr, key_ptr));
-  BA_CHECK(upload_vec(&T->key_ca, key_ca));
-  BA_CHECK(upload_vec(&T->key_cb, key_cb));
-  BA_CHECK(upload_vec(&T->task_a, sa));
-  BA_CHECK(upload_vec(&T->task_b, sb));
+  BA_CHECK(upload(T->key_ptr, key_ptr));
+  BA_CHECK(upload(T->key_ca, key_ca));
+  BA_CHECK(upload(T->key_cb, key_cb));
+  BA_CHECK(upload(T->task_a, sa));
+  BA_CHECK(upload(T->task_b, sb));
   return BA_OK;
 }
 
@@ -180,24 +167,43 @@ int64_t reduce_layout(ba_problem *p, int64_t *off_rhs, int64_t *off_gc, int64_t 
 }
 
 struct LMState {
-  double *red = nullptr;  // [rhs | gc | hdiag | sharded scalars]
-  bool own_red = false;
+  DevBuf<double> red;  // [rhs | gc | hdiag | sharded scalars]
   int64_t off_rhs = 0, off_gc = 0, off_scal = 0, red_doubles = 0;
-  double *scal_rep = nullptr;
-  double *h_sh = nullptr, *h_rp = nullptr;  // pinned
+  DevBuf<double> scal_rep;
+  PinnedBuf<double> h_sh, h_rp;
 };
 
 }  // namespace
 
-struct LMWorkFull : LMWork {
+// The LM workspace of a handle (ba_problem::lm): made by lm_ensure, released by lm_free.  The recorded launch sequences are
+// declared last, so they are destroyed before the buffers they reference.
+struct LMWork {
+  int64_t nvar = 0, nequ = 0, n = 0, npad = 0;  // n = 9*ncams
+  DevBuf<double> x, x_trial, delta;
+  DevBuf<double> r, r_trial, J;
+  DevBuf<double> Hpp, gp, Uinv, u;
+  DevBuf<double> Yobs;                   // 6/obs: U^-1 A_b' of the current damping
+  bool model_done = false;               // the step's model value was formed by the back-substitution pass
+  DevBuf<double> Hcc;
+  // views into s.red: gc (9*ncams), hdiag (npad: diag of the camera block of J'J summed over all ranks, for the column
+  // scalings), rhs (npad), scal (the SH_COUNT sharded scalars)
+  double *gc = nullptr, *hdiag = nullptr, *rhs = nullptr, *scal = nullptr;
+  DevBuf<double> colscale;               // nvar (normalize != None)
+  // facto_type = Float16: |J_j|^2, column norms, damping vector (nvar each), quantised J (24/obs) and r; allocated on first use
+  DevBuf<double> jn2, dcol, damp, Jq, rq;
+  DevBuf<double> partial;                // RED_BLOCKS
+  DevBuf<double> partial_multi;          // SUMSQ_JOBS x RED_BLOCKS (launch_sumsq_multi)
+  DevBuf<int> cam_pnt;                   // nobs: the point of every observation in camera order (pnt0[cam_obs[q]])
+  SchurTasks tasks;
+  DenseLDL ldl;
   LMState s;
   std::vector<SchurChunk> chunks;  // per-rank ownership of S: chunks of tile columns, assembled and reduced one by one
-  double *stage = nullptr;         // the chunk being assembled for another owner (stage_tiles tiles)
-  float *stage32 = nullptr;        // its Float32 copy when the reduce travels in Float32
+  DevBuf<double> stage;            // the chunk being assembled for another owner (stage_tiles tiles)
+  DevBuf<float> stage32;           // its Float32 copy when the reduce travels in Float32
   int64_t stage_tiles = 0;         // (reduce-scatter assembly: all the staging tiles, stage_bufs buffers of stage_tiles / stage_bufs)
   bool assembly_rs = false;        // chunks are reduce-scattered (one segment per owner) instead of reduced onto one owner
   int stage_bufs = 1;              // 2: chunk c+1 is assembled while chunk c travels (transfer stream)
-  hipEvent_t ev_stage_ready[2] = {nullptr, nullptr}, ev_stage_free[2] = {nullptr, nullptr};
+  HipEvent ev_stage_ready[2], ev_stage_free[2];
   TilePattern pattern;       // tile pattern of S after the symbolic factorisation (ensure_dense)
   bool use_pattern = false;  // the block-sparse list schedule is in use on this handle
   // fill-reducing camera ordering of the reduced camera system (`perm` of the reference's solvers, src/lm.jl:84-88): the
@@ -209,7 +215,7 @@ struct LMWorkFull : LMWork {
   int order_split = 0;  // the sequence eliminates from both ends: tile column pair at which the second run starts (0: one run)
   // facto_type = Float32 (src/lm.jl:170-173): Float32 copy of the reduced camera system, allocated on first use
   DenseLDLT<float> ldl32;
-  float *rhs32 = nullptr;
+  DevBuf<float> rhs32;
   bool have32 = false, last_f32 = false;
   // facto_type = Float16 (src/lm.jl:165-169): set per solve; J_lin / r_lin / cr0: what the model value of the current step is
   // evaluated on (the Float16-rounded scaled copies in that mode, J and r otherwise), see linear_step
@@ -221,13 +227,13 @@ struct LMWorkFull : LMWork {
   double cr0() const { return f16 ? 1.0 / (0.1 * 6.55e4) : 1.0; }
   // eltype(x) = Float32 runs (BALNLPModel(file, Float32), src/BALNLPModels.jl:91): x, r and J are produced by the Float32
   // kernels and widened; every iterate is rounded to Float32.  Buffers allocated on first use.
-  float *xf = nullptr, *rf = nullptr, *Jf = nullptr;
+  DevBuf<float> xf, rf, Jf;
   // hipGraph replay of the two launch sequences of the LM loop (launch-bound on small problems: LadyBug-49 issues ~60
   // kernels of a few microseconds per iteration).  x/x_trial and r/r_trial swap on an accepted step, so each sequence
-  // is recorded once per parity of the swap; the damping reaches the recorded kernels through d_lambda.
-  double *d_lambda = nullptr, *h_lambda = nullptr;  // device scalar, pinned staging
-  int *h_flag = nullptr;                            // pinned copy of the pivot flag
-  hipGraphExec_t g_step[2] = {nullptr, nullptr}, g_refresh[2] = {nullptr, nullptr};
+  // is recorded once per parity of the swap (g_step, g_refresh); the damping reaches the recorded kernels through d_lambda.
+  DevBuf<double> d_lambda;   // device scalar
+  PinnedBuf<double> h_lambda;  // its pinned staging
+  PinnedBuf<int> h_flag;     // pinned copy of the pivot flag
   int g_key = -1;  // graph_key(): normalize + 4 * facto_f32 + 8 * x_f32 + 16 * loss + 128 / 256 * mask tables the graphs were recorded for
   double g_scale = 1.0;  // ... and the loss scale (the robust kernels take loss and scale as launch arguments)
   const void *g_fix_cam = nullptr, *g_fix_pnt = nullptr;  // ... and the device tables of the mask k_fix_mask was recorded with
@@ -240,9 +246,11 @@ struct LMWorkFull : LMWork {
   double pcg_tol = 1e-8;
   int pcg_maxit = 0;  // 0: default
   int64_t n_cg = 0;   // CG iterations of the current solve
-  double *cgx = nullptr, *cgr = nullptr, *cgz = nullptr, *cgp = nullptr, *cgq = nullptr, *cgt = nullptr;
-  double *cgh = nullptr, *zero3 = nullptr, *blk45 = nullptr, *cg_scal = nullptr, *h_cg = nullptr;
-  double *rob_partial = nullptr;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
+  DevBuf<double> cgx, cgr, cgz, cgp, cgq, cgt;
+  DevBuf<double> cgh, zero3, blk45, cg_scal;
+  PinnedBuf<double> h_cg;
+  DevBuf<double> rob_partial;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
+  HipGraphExec g_step[2], g_refresh[2];
 };
 
 namespace {
@@ -259,6 +267,9 @@ int launch_convert(const A *in, B *out, int64_t n, hipStream_t st) {
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
+// the two directions the controller converts in, as plain functions: they take the workspace's owners as well
+int launch_convert(const double *in, float *out, int64_t n, hipStream_t st) { return launch_convert<double, float>(in, out, n, st); }
+int launch_convert(const float *in, double *out, int64_t n, hipStream_t st) { return launch_convert<float, double>(in, out, n, st); }
 }  // namespace
 
 // BA_DIST_FACTOR=0: keep the whole reduced camera system on every rank (one all-reduce of S, replicated factorisation)
@@ -267,52 +278,51 @@ static bool dist_factor_on(ba_problem *p) {
   return p->comm.active() && !off;
 }
 
-static int ensure_xf32(ba_problem *p, LMWorkFull *w) {
+static int ensure_xf32(ba_problem *p, LMWork *w) {
   if (w->xf) return BA_OK;
-  BA_HIP_CHECK(hipMalloc((void **)&w->xf, (size_t)(w->nvar > 0 ? w->nvar : 1) * sizeof(float)));
-  BA_HIP_CHECK(hipMalloc((void **)&w->rf, (size_t)(w->nequ > 0 ? w->nequ : 1) * sizeof(float)));
-  BA_HIP_CHECK(hipMalloc((void **)&w->Jf, (size_t)(p->nobs > 0 ? 24 * p->nobs : 1) * sizeof(float)));
+  BA_CHECK(w->xf.alloc(w->nvar));
+  BA_CHECK(w->rf.alloc(w->nequ));
+  BA_CHECK(w->Jf.alloc(24 * p->nobs));
   return BA_OK;
 }
 
-static int ensure_f32(LMWorkFull *w) {
+static int ensure_f32(LMWork *w) {
   if (w->have32) return BA_OK;
-  BA_CHECK(dense_ldl_alloc<float>(&w->ldl32, w->n, nullptr, w->ldl.world, w->ldl.rank, false, w->ldl.own_only));
-  if (w->ldl.own_only && !w->stage32) BA_HIP_CHECK(hipMalloc((void **)&w->stage32, (size_t)std::max<int64_t>(1, w->stage_tiles) * NB * NB * sizeof(float)));
+  BA_CHECK(dense_ldl_alloc<float>(&w->ldl32, w->n, w->ldl.world, w->ldl.rank, false, w->ldl.own_only));
+  if (w->ldl.own_only && !w->stage32) BA_CHECK(w->stage32.alloc(std::max<int64_t>(1, w->stage_tiles) * NB * NB));
   if (w->use_pattern) BA_CHECK(dense_ldl_use_pattern(&w->ldl32, &w->pattern));
-  BA_HIP_CHECK(hipMalloc((void **)&w->rhs32, (size_t)w->npad * sizeof(float)));
+  BA_CHECK(w->rhs32.alloc(w->npad));
   w->have32 = true;
   return BA_OK;
 }
 
-static int ensure_f16(ba_problem *p, LMWorkFull *w) {
+static int ensure_f16(ba_problem *p, LMWork *w) {
   if (w->Jq) return BA_OK;
-  BA_CHECK(dmalloc(&w->jn2, w->nvar));
-  BA_CHECK(dmalloc(&w->dcol, w->nvar));
-  BA_CHECK(dmalloc(&w->damp, w->nvar));
-  BA_CHECK(dmalloc(&w->Jq, 24 * p->nobs));
-  BA_CHECK(dmalloc(&w->rq, w->nequ));
+  BA_CHECK(w->jn2.alloc(w->nvar));
+  BA_CHECK(w->dcol.alloc(w->nvar));
+  BA_CHECK(w->damp.alloc(w->nvar));
+  BA_CHECK(w->Jq.alloc(24 * p->nobs));
+  BA_CHECK(w->rq.alloc(w->nequ));
   return BA_OK;
 }
 
 static int lm_ensure(ba_problem *p) {
   if (p->lm) return BA_OK;
-  LMWorkFull *w = new LMWorkFull();
+  LMWork *w = new LMWork();
   p->lm = w;
   const int64_t ncams = p->ncams, npnts = p->npnts, nobs = p->nobs;
   w->nvar = 9 * ncams + 3 * npnts;
   w->nequ = 2 * nobs;
   w->n = 9 * ncams;
   w->s.red_doubles = reduce_layout(p, &w->s.off_rhs, &w->s.off_gc, &w->s.off_scal);
-  BA_CHECK(dmalloc(&w->s.red, w->s.red_doubles));
-  w->s.own_red = true;
+  BA_CHECK(w->s.red.alloc(w->s.red_doubles));
   // with a communicator the tile column pairs of S are laid out by owner rank (one contiguous range per rank).  The tiles
   // themselves (n^2/2 doubles: 1 GB for Venice, 60 GB for Final-13682), the Schur task list and the per-observation Y blocks
   // are allocated by ensure_dense when a direct solve first needs them: a handle that only ever runs facto = :PCG never
   // holds anything of the size of S.
   // ... and with the distributed factorisation a rank holds ONLY its own tile columns of S (per-rank ownership): the other
   // ranks' contributions pass through a staging buffer of at most half that size, chunk by chunk (ensure_dense, linear_step)
-  BA_CHECK(dense_ldl_alloc(&w->ldl, w->n, (double *)nullptr, p->comm.active() ? p->comm.world : 1, p->comm.active() ? p->comm.rank : 0, true,
+  BA_CHECK(dense_ldl_alloc(&w->ldl, w->n, p->comm.active() ? p->comm.world : 1, p->comm.active() ? p->comm.rank : 0, true,
                            dist_factor_on(p)));
   w->npad = w->ldl.n;
   w->rhs = w->s.red + w->s.off_rhs;
@@ -321,29 +331,29 @@ static int lm_ensure(ba_problem *p) {
   w->scal = w->s.red + w->s.off_scal;
   BA_HIP_CHECK(hipMemset(w->s.red + w->s.off_rhs, 0, (size_t)(w->s.red_doubles - w->s.off_rhs) * sizeof(double)));
   BA_HIP_CHECK(hipDeviceSynchronize());  // (null-stream memset: not ordered against the handle's non-blocking stream)
-  BA_CHECK(dmalloc(&w->x, w->nvar));
-  BA_CHECK(dmalloc(&w->x_trial, w->nvar));
-  BA_CHECK(dmalloc(&w->delta, w->nvar));
-  BA_CHECK(dmalloc(&w->r, w->nequ));
-  BA_CHECK(dmalloc(&w->r_trial, w->nequ));
-  BA_CHECK(dmalloc(&w->J, 24 * nobs));
-  BA_CHECK(dmalloc(&w->Hpp, 6 * npnts));
-  BA_CHECK(dmalloc(&w->gp, 3 * npnts));
-  BA_CHECK(dmalloc(&w->Uinv, 6 * npnts));
-  BA_CHECK(dmalloc(&w->u, 3 * npnts));
-  BA_CHECK(dmalloc(&w->Hcc, 45 * ncams));
-  BA_CHECK(dmalloc(&w->colscale, 9 * ncams));
-  BA_CHECK(dmalloc(&w->partial, std::max<int64_t>(RED_BLOCKS, (npnts + 255) / 256)));  // k_wtv<true>: one partial per 256 points
-  BA_CHECK(dmalloc(&w->partial_multi, (int64_t)SUMSQ_JOBS * RED_BLOCKS));
-  BA_CHECK(dmalloc(&w->rob_partial, (int64_t)2 * RED_BLOCKS));
-  BA_HIP_CHECK(hipMalloc((void **)&w->cam_pnt, (size_t)(p->nobs > 0 ? p->nobs : 1) * sizeof(int)));
+  BA_CHECK(w->x.alloc(w->nvar));
+  BA_CHECK(w->x_trial.alloc(w->nvar));
+  BA_CHECK(w->delta.alloc(w->nvar));
+  BA_CHECK(w->r.alloc(w->nequ));
+  BA_CHECK(w->r_trial.alloc(w->nequ));
+  BA_CHECK(w->J.alloc(24 * nobs));
+  BA_CHECK(w->Hpp.alloc(6 * npnts));
+  BA_CHECK(w->gp.alloc(3 * npnts));
+  BA_CHECK(w->Uinv.alloc(6 * npnts));
+  BA_CHECK(w->u.alloc(3 * npnts));
+  BA_CHECK(w->Hcc.alloc(45 * ncams));
+  BA_CHECK(w->colscale.alloc(9 * ncams));
+  BA_CHECK(w->partial.alloc(std::max<int64_t>(RED_BLOCKS, (npnts + 255) / 256)));  // k_wtv<true>: one partial per 256 points
+  BA_CHECK(w->partial_multi.alloc((int64_t)SUMSQ_JOBS * RED_BLOCKS));
+  BA_CHECK(w->rob_partial.alloc((int64_t)2 * RED_BLOCKS));
+  BA_CHECK(w->cam_pnt.alloc(nobs));
   BA_CHECK(launch_cam_pnt(p, w->cam_pnt, p->stream));
-  BA_CHECK(dmalloc(&w->s.scal_rep, (int64_t)RP_COUNT));
-  BA_HIP_CHECK(hipHostMalloc((void **)&w->s.h_sh, SH_COUNT * sizeof(double)));
-  BA_HIP_CHECK(hipHostMalloc((void **)&w->s.h_rp, RP_COUNT * sizeof(double)));
-  BA_HIP_CHECK(hipHostMalloc((void **)&w->h_lambda, sizeof(double)));
-  BA_HIP_CHECK(hipHostMalloc((void **)&w->h_flag, sizeof(int)));
-  BA_CHECK(dmalloc(&w->d_lambda, (int64_t)1));
+  BA_CHECK(w->s.scal_rep.alloc(RP_COUNT));
+  BA_CHECK(w->s.h_sh.alloc(SH_COUNT));
+  BA_CHECK(w->s.h_rp.alloc(RP_COUNT));
+  BA_CHECK(w->h_lambda.alloc(1));
+  BA_CHECK(w->h_flag.alloc(1));
+  BA_CHECK(w->d_lambda.alloc(1));
   return BA_OK;
 }
 
@@ -353,7 +363,7 @@ static int lm_ensure(ba_problem *p) {
 // ever holds more of S than its own columns plus one chunk: <= 1.5 |S| / world (plus the panel buffers of the
 // factorisation).  A key's 9 x 9 block can straddle two tile columns: it is listed with both chunks and each stores the
 // elements that fall into its own columns (the offset table of the chunk marks the others).
-static int upload_chunk_tables(LMWorkFull *w, std::vector<std::vector<int64_t>> &cco, const std::vector<int> &col_chunk_of_col,
+static int upload_chunk_tables(LMWork *w, std::vector<std::vector<int64_t>> &cco, const std::vector<int> &col_chunk_of_col,
                                bool sparse);
 
 // Reduce-scatter form of the chunked assembly (default; BA_ASSEMBLY=reduce keeps the chunk-onto-one-owner form).  A chunk
@@ -364,7 +374,7 @@ static int upload_chunk_tables(LMWorkFull *w, std::vector<std::vector<int64_t>> 
 // two staging buffers chunk c travels on the transfer stream while chunk c+1 is assembled on the main one.  Slices per
 // owner: as many as keep all staging within about half a rank's share of S (4 world with two buffers), never finer than a
 // tile column; when two buffers would not fit (small problems) there is one and the transfer is in line.
-static int build_chunks_rs(ba_problem *p, LMWorkFull *w) {
+static int build_chunks_rs(ba_problem *p, LMWork *w) {
   const DenseLDL &l = w->ldl;
   const int64_t nt = l.nt;
   const int P = l.world, me = l.rank;
@@ -449,17 +459,17 @@ static int build_chunks_rs(ba_problem *p, LMWorkFull *w) {
       }
     }
     if (!any) continue;
-    w->chunks.push_back(ch);
+    w->chunks.push_back(std::move(ch));
     cco.push_back(table);
   }
   for (int q = 0; q < 2; q++) {
-    if (!w->ev_stage_ready[q]) BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_stage_ready[q], hipEventDisableTiming));
-    if (!w->ev_stage_free[q]) BA_HIP_CHECK(hipEventCreateWithFlags(&w->ev_stage_free[q], hipEventDisableTiming));
+    if (!w->ev_stage_ready[q]) BA_CHECK(w->ev_stage_ready[q].create(hipEventDisableTiming));
+    if (!w->ev_stage_free[q]) BA_CHECK(w->ev_stage_free[q].create(hipEventDisableTiming));
   }
   return upload_chunk_tables(w, cco, col_chunk, sparse);
 }
 
-static int build_chunks(ba_problem *p, LMWorkFull *w) {
+static int build_chunks(ba_problem *p, LMWork *w) {
   {
     const char *e = getenv("BA_ASSEMBLY");  // reduce: every chunk onto ONE owner (round 3's form); default: reduce-scatter
     if (!(e && e[0] == 'r' && e[1] == 'e' && e[2] == 'd' && e[3] == 'u' && e[4] == 'c' && e[5] == 'e' && e[6] == 0)) return build_chunks_rs(p, w);
@@ -486,9 +496,9 @@ static int build_chunks(ba_problem *p, LMWorkFull *w) {
     int64_t local = 0;  // tile offset inside rank r's own layout
     auto flush = [&]() {
       if (c.ntiles == 0) return;
-      w->chunks.push_back(c);
-      cco.push_back(table);
       if (r != l.rank) w->stage_tiles = std::max(w->stage_tiles, c.ntiles);
+      w->chunks.push_back(std::move(c));
+      cco.push_back(table);
       c = SchurChunk();
       c.owner = r;
       c.t0 = local;
@@ -509,7 +519,7 @@ static int build_chunks(ba_problem *p, LMWorkFull *w) {
 }
 
 // the keys of every chunk, its offset table on the device, the staging buffer
-static int upload_chunk_tables(LMWorkFull *w, std::vector<std::vector<int64_t>> &cco, const std::vector<int> &col_chunk, bool sparse) {
+static int upload_chunk_tables(LMWork *w, std::vector<std::vector<int64_t>> &cco, const std::vector<int> &col_chunk, bool sparse) {
   const DenseLDL &l = w->ldl;
   const int64_t nt = l.nt;
   const SchurTasks &T = w->tasks;
@@ -536,15 +546,15 @@ static int upload_chunk_tables(LMWorkFull *w, std::vector<std::vector<int64_t>> 
         with_head[0] = nt;
         std::copy(l.h_col_tab.begin() + 1 + nt, l.h_col_tab.end(), with_head.begin() + 1 + nt);
       }
-      BA_CHECK(upload_vec(&ch.cco_alloc, with_head));
+      BA_CHECK(upload(ch.cco_alloc, with_head));
       ch.cco = ch.cco_alloc + 1;
     }
-    BA_CHECK(upload_vec(&ch.keys, keys[c]));
-    BA_CHECK(upload_vec(&ch.skeys, skeys[c]));
+    BA_CHECK(upload(ch.keys, keys[c]));
+    BA_CHECK(upload(ch.skeys, skeys[c]));
     ch.nkeys = (int64_t)keys[c].size();
     ch.nskeys = (int64_t)skeys[c].size();
   }
-  BA_HIP_CHECK(hipMalloc((void **)&w->stage, (size_t)std::max<int64_t>(1, w->stage_tiles) * NB * NB * sizeof(double)));
+  BA_CHECK(w->stage.alloc(std::max<int64_t>(1, w->stage_tiles) * NB * NB));
   return BA_OK;
 }
 
@@ -552,20 +562,12 @@ static int upload_chunk_tables(LMWorkFull *w, std::vector<std::vector<int64_t>> 
 static int allreduce_flags(ba_problem *p, std::vector<unsigned char> *flags) {
   if (!p->comm.active() || flags->empty()) return BA_OK;
   std::vector<double> h(flags->begin(), flags->end());
-  double *d = nullptr;
-  BA_HIP_CHECK(hipMalloc((void **)&d, h.size() * sizeof(double)));
+  DevBuf<double> d;
+  BA_CHECK(d.alloc((int64_t)h.size()));
   BA_HIP_CHECK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  int rc = comm_allreduce(p, d, (int64_t)h.size(), p->stream);
-  if (rc == BA_OK) {
-    hipError_t e = hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) {
-      ba_set_error("allreduce_flags: %s", hipGetErrorString(e));
-      rc = BA_ERR_HIP;
-    }
-  }
-  (void)hipFree(d);
-  BA_CHECK(rc);
+  BA_CHECK(comm_allreduce(p, d, (int64_t)h.size(), p->stream));
+  BA_HIP_CHECK(hipMemcpyAsync(h.data(), d, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  BA_HIP_CHECK(hipStreamSynchronize(p->stream));
   for (size_t i = 0; i < h.size(); i++) (*flags)[i] = h[i] != 0.0;
   return BA_OK;
 }
@@ -578,10 +580,9 @@ static int allreduce_cam_graph(ba_problem *p, CamGraph *g) {
   const size_t nwords = g->bits.size(), ndbl = nwords * 8;
   const size_t slice = std::min<size_t>(ndbl, (size_t)16 << 20);
   std::vector<double> h(slice);
-  double *d = nullptr;
-  BA_HIP_CHECK(hipMalloc((void **)&d, slice * sizeof(double)));
-  int rc = BA_OK;
-  for (size_t off = 0; off < ndbl && rc == BA_OK; off += slice) {
+  DevBuf<double> d;
+  BA_CHECK(d.alloc((int64_t)slice));
+  for (size_t off = 0; off < ndbl; off += slice) {
     const size_t cnt = std::min(slice, ndbl - off);
     for (size_t i = 0; i < cnt; i++) {  // double off + i: byte ((off + i) & 7) of word (off + i) / 8
       const uint64_t byte = (g->bits[(off + i) >> 3] >> (8 * ((off + i) & 7))) & 0xff;
@@ -589,15 +590,10 @@ static int allreduce_cam_graph(ba_problem *p, CamGraph *g) {
       for (int b = 0; b < 8; b++) packed |= ((byte >> b) & 1) << (6 * b);
       h[i] = (double)packed;
     }
-    hipError_t e = hipMemcpyAsync(d, h.data(), cnt * sizeof(double), hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) rc = comm_allreduce(p, d, (int64_t)cnt, p->stream);
-    if (e == hipSuccess && rc == BA_OK) e = hipMemcpyAsync(h.data(), d, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess && rc == BA_OK) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) {
-      ba_set_error("allreduce_cam_graph: %s", hipGetErrorString(e));
-      rc = BA_ERR_HIP;
-    }
-    if (rc != BA_OK) break;
+    BA_HIP_CHECK(hipMemcpyAsync(d, h.data(), cnt * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    BA_CHECK(comm_allreduce(p, d, (int64_t)cnt, p->stream));
+    BA_HIP_CHECK(hipMemcpyAsync(h.data(), d, cnt * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    BA_HIP_CHECK(hipStreamSynchronize(p->stream));
     for (size_t i = 0; i < cnt; i++) {
       const uint64_t packed = (uint64_t)h[i];
       uint64_t byte = 0;
@@ -607,8 +603,7 @@ static int allreduce_cam_graph(ba_problem *p, CamGraph *g) {
       word = (word & ~((uint64_t)0xff << sh)) | (byte << sh);
     }
   }
-  (void)hipFree(d);
-  return rc;
+  return BA_OK;
 }
 
 // Fill-reducing ordering of the cameras inside the reduced camera system -- what `perm` asks of the reference's sparse
@@ -616,7 +611,7 @@ static int allreduce_cam_graph(ba_problem *p, CamGraph *g) {
 // depends on how the cameras are numbered; a BAL file promises nothing about that.  Cameras keep their numbers everywhere
 // else (x, J, Hcc, gc): only S, its right-hand side and its solution live in the new order (SchurTasks::cam_of / pos).
 // pos_out: block row of every camera, empty when the caller's numbering stays.
-static int order_cameras(ba_problem *p, LMWorkFull *w, std::vector<int> *pos_out) {
+static int order_cameras(ba_problem *p, LMWork *w, std::vector<int> *pos_out) {
   pos_out->clear();
   w->h_cam_perm.clear();
   w->order_name = "natural";
@@ -646,16 +641,16 @@ static int order_cameras(ba_problem *p, LMWorkFull *w, std::vector<int> *pos_out
   w->order_split = split;
   pos_out->resize((size_t)n);
   for (int64_t k = 0; k < n; k++) (*pos_out)[(size_t)perm[(size_t)k]] = (int)k;
-  BA_CHECK(upload_vec(&w->tasks.cam_of, perm));
-  BA_CHECK(upload_vec(&w->tasks.pos, *pos_out));
+  BA_CHECK(upload(w->tasks.cam_of, perm));
+  BA_CHECK(upload(w->tasks.pos, *pos_out));
   w->h_cam_perm.swap(perm);
   return BA_OK;
 }
 
 // what only the direct solves need: the tiles of S, the Schur task list, the per-observation Y blocks
-static int ensure_dense(ba_problem *p, LMWorkFull *w) {
+static int ensure_dense(ba_problem *p, LMWork *w) {
   if (w->ldl.S) return BA_OK;
-  BA_CHECK(dmalloc(&w->Yobs, 6 * p->nobs));
+  BA_CHECK(w->Yobs.alloc(6 * p->nobs));
   std::vector<int> pos;
   BA_CHECK(order_cameras(p, w, &pos));
   BA_CHECK(build_tasks(p, &w->tasks, pos));
@@ -677,53 +672,13 @@ static int ensure_dense(ba_problem *p, LMWorkFull *w) {
 }
 
 void lm_free(ba_problem *p) {
-  if (!p->lm) return;
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
-  dense_ldl_free(&w->ldl);
-  if (w->have32) {
-    dense_ldl_free(&w->ldl32);
-    (void)hipFree(w->rhs32);
-  }
-  for (SchurChunk &c : w->chunks) {
-    if (c.cco_alloc) (void)hipFree(c.cco_alloc);
-    if (c.keys) (void)hipFree(c.keys);
-    if (c.skeys) (void)hipFree(c.skeys);
-  }
-  for (int q = 0; q < 2; q++) {
-    if (w->ev_stage_ready[q]) (void)hipEventDestroy(w->ev_stage_ready[q]);
-    if (w->ev_stage_free[q]) (void)hipEventDestroy(w->ev_stage_free[q]);
-  }
-  if (w->stage) (void)hipFree(w->stage);
-  if (w->stage32) (void)hipFree(w->stage32);
-  if (w->xf) (void)hipFree(w->xf);
-  if (w->rf) (void)hipFree(w->rf);
-  if (w->Jf) (void)hipFree(w->Jf);
-  void *ptrs[] = {w->jn2, w->dcol, w->damp, w->Jq, w->rq, w->x, w->x_trial, w->delta, w->r, w->r_trial, w->J, w->Hpp, w->gp, w->Uinv, w->u, w->Hcc,
-                  w->partial, w->partial_multi, w->colscale, w->Yobs, w->s.scal_rep, w->tasks.key_ptr, w->tasks.key_ca, w->tasks.key_cb,
-                  w->tasks.task_a, w->tasks.task_b, w->tasks.skey, w->tasks.skey_c0, w->tasks.chunk_t0,
-                  w->tasks.chunk_t1, w->tasks.partial, w->tasks.cam_of, w->tasks.pos, w->s.own_red ? w->s.red : nullptr};
-  for (void *q : ptrs)
-    if (q) (void)hipFree(q);
-  for (int q = 0; q < 2; q++) {
-    if (w->g_step[q]) (void)hipGraphExecDestroy(w->g_step[q]);
-    if (w->g_refresh[q]) (void)hipGraphExecDestroy(w->g_refresh[q]);
-  }
-  for (double *q : {w->cgx, w->cgr, w->cgz, w->cgp, w->cgq, w->cgt, w->cgh, w->zero3, w->blk45, w->cg_scal})
-    if (q) (void)hipFree(q);
-  if (w->h_cg) (void)hipHostFree(w->h_cg);
-  if (w->cam_pnt) (void)hipFree(w->cam_pnt);
-  if (w->d_lambda) (void)hipFree(w->d_lambda);
-  if (w->h_lambda) (void)hipHostFree(w->h_lambda);
-  if (w->h_flag) (void)hipHostFree(w->h_flag);
-  if (w->s.h_sh) (void)hipHostFree(w->s.h_sh);
-  if (w->s.h_rp) (void)hipHostFree(w->s.h_rp);
-  delete w;
+  delete p->lm;
   p->lm = nullptr;
 }
 
 // all-reduce [off, off+count) of the reduce buffer over the ranks (no-op without a communicator; a communicator of one
 // rank is still called: lets one GPU exercise the path)
-static int comm_sum(ba_problem *p, LMWorkFull *w, int64_t off, int64_t count, hipStream_t st) {
+static int comm_sum(ba_problem *p, LMWork *w, int64_t off, int64_t count, hipStream_t st) {
   return comm_allreduce(p, w->s.red + off, count, st);
 }
 
@@ -733,7 +688,7 @@ static int comm_sum(ba_problem *p, LMWorkFull *w, int64_t off, int64_t count, hi
 // partial sums to Float32 first and the owners receive Float32 sums -- half the bytes of the largest transfer of the
 // iteration (Final-13682: 30 GB instead of 60); the sum of `world` rounded partials differs from the rounded sum by a few
 // Float32 ulps, the level of the factorisation itself.
-static int reduce_camera_system(ba_problem *p, LMWorkFull *w, hipStream_t st, bool s32 = false) {
+static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s32 = false) {
   if (!p->comm.active()) return BA_OK;
   if (!dist_factor_on(p)) {  // replicated: the whole S and the right-hand side everywhere
     BA_CHECK(comm_allreduce(p, w->ldl.S, w->ldl.s_tiles * NB * NB, st));
@@ -756,7 +711,7 @@ static int reduce_camera_system(ba_problem *p, LMWorkFull *w, hipStream_t st, bo
 // publish: the last reduction kernel also writes the controller's scalars to the pinned host buffers (recorded sequences)
 // Under a robust loss r and J are reweighted in place (r~, J~) before anything reads them; r must hold the plain residual at
 // w->x on entry (residual_too, or the trial residual of an accepted step)
-static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too, hipStream_t st, bool xf32 = false, bool publish = false) {
+static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, hipStream_t st, bool xf32 = false, bool publish = false) {
   if (xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
     if (residual_too) {
@@ -805,7 +760,7 @@ static int refresh_linearisation(ba_problem *p, LMWorkFull *w, bool residual_too
   return BA_OK;
 }
 
-static int fetch_scalars(ba_problem *p, LMWorkFull *w, hipStream_t st) {
+static int fetch_scalars(ba_problem *p, LMWork *w, hipStream_t st) {
   BA_CHECK(launch_publish(w->scal, SH_COUNT, w->s.h_sh, w->s.scal_rep, RP_COUNT, w->s.h_rp, nullptr, nullptr, st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
@@ -817,26 +772,26 @@ static int fetch_scalars(ba_problem *p, LMWorkFull *w, hipStream_t st) {
 // stop paying.  Here S = Hcc + lambda I - W U^-1 W' is applied, never formed: two sweeps over J per product (the
 // back-substitution pass by point, the right-hand-side pass by camera), preconditioned by its 9 x 9 diagonal blocks.  On
 // several ranks the product is summed by ONE all-reduce of 9 ncams doubles per CG iteration; everything else is replicated.
-static int ensure_pcg(ba_problem *p, LMWorkFull *w) {
-  if (w->cgx) return BA_OK;
-  auto dm = [](double **q, int64_t cnt) -> int {
-    BA_HIP_CHECK(hipMalloc((void **)q, (size_t)(cnt > 0 ? cnt : 1) * sizeof(double)));
-    BA_HIP_CHECK(hipMemset(*q, 0, (size_t)(cnt > 0 ? cnt : 1) * sizeof(double)));
+static int ensure_pcg(ba_problem *p, LMWork *w) {
+  if (w->h_cg) return BA_OK;  // (the last allocation: a failed call is redone whole)
+  auto dm = [](DevBuf<double> &q, int64_t cnt) -> int {
+    BA_CHECK(q.alloc(cnt));
+    BA_HIP_CHECK(hipMemset(q, 0, (size_t)(cnt > 0 ? cnt : 1) * sizeof(double)));
     return BA_OK;
   };
-  for (double **q : {&w->cgx, &w->cgr, &w->cgz, &w->cgp, &w->cgq, &w->cgt}) BA_CHECK(dm(q, w->npad));
-  BA_CHECK(dm(&w->cgh, 3 * p->npnts));
-  BA_CHECK(dm(&w->zero3, 3 * p->npnts));
-  BA_CHECK(dm(&w->blk45, 45 * p->ncams));
-  BA_CHECK(dm(&w->cg_scal, 8));
+  for (DevBuf<double> *q : {&w->cgx, &w->cgr, &w->cgz, &w->cgp, &w->cgq, &w->cgt}) BA_CHECK(dm(*q, w->npad));
+  BA_CHECK(dm(w->cgh, 3 * p->npnts));
+  BA_CHECK(dm(w->zero3, 3 * p->npnts));
+  BA_CHECK(dm(w->blk45, 45 * p->ncams));
+  BA_CHECK(dm(w->cg_scal, 8));
   BA_HIP_CHECK(hipDeviceSynchronize());  // (the null-stream memsets above are not ordered against the handle's stream)
-  BA_HIP_CHECK(hipHostMalloc((void **)&w->h_cg, 8 * sizeof(double)));
+  BA_CHECK(w->h_cg.alloc(8));
   return BA_OK;
 }
 
 // q = S v: the point sweep, then the camera sweep (which adds Hcc v and, on one rank, the damping); on several ranks the
 // partial products are summed by one all-reduce and every rank adds the damping to the full sum
-static int pcg_matvec(ba_problem *p, LMWorkFull *w, double lambda, const double *v, double *q, hipStream_t st) {
+static int pcg_matvec(ba_problem *p, LMWork *w, double lambda, const double *v, double *q, hipStream_t st) {
   const bool shared = p->comm.active();
   if (p->point_sorted) BA_CHECK(launch_wtv(p, w->J, w->Uinv, v, w->cgh, st));  // h = -U^-1 W' v
   else BA_CHECK(launch_backsub(p, w->J, w->Uinv, w->zero3, v, w->cgh, st));  // (observations not grouped by point)
@@ -846,7 +801,7 @@ static int pcg_matvec(ba_problem *p, LMWorkFull *w, double lambda, const double 
   return launch_axpy_s(p, w->n, lambda, v, q, st);
 }
 
-static int pcg_fetch(LMWorkFull *w, hipStream_t st) {
+static int pcg_fetch(LMWork *w, hipStream_t st) {
   BA_HIP_CHECK(hipMemcpyAsync(w->h_cg, w->cg_scal, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
@@ -854,7 +809,7 @@ static int pcg_fetch(LMWorkFull *w, hipStream_t st) {
 
 // S x = rhs (w->rhs in, solution out) to |r| <= pcg_tol |rhs| or pcg_maxit iterations.  alpha and beta are formed on the
 // device (k_cg_alpha, k_cg_beta_dir); the host reads the scalars once per iteration, for the stopping test.
-static int pcg_solve(ba_problem *p, LMWorkFull *w, double lambda, hipStream_t st) {
+static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   BA_CHECK(ensure_pcg(p, w));
   const int64_t n = w->n;
   const int maxit = w->pcg_maxit > 0 ? w->pcg_maxit : 1000;
@@ -889,7 +844,7 @@ static int pcg_solve(ba_problem *p, LMWorkFull *w, double lambda, hipStream_t st
 
 // delta = -(J'J + lambda I)^-1 J'r at the current linearisation; also |J delta + r|^2 -> SH_MODEL, |delta|^2
 // h_lambda (recorded sequences): pinned host scalar the first kernel copies into d_lambda
-static int linear_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize, hipStream_t st,
+static int linear_step(ba_problem *p, LMWork *w, double lambda, int normalize, hipStream_t st,
                        bool facto_f32 = false, const double *d_lambda = nullptr, const double *h_lambda = nullptr) {
   // d_lambda: the damping is read from device memory (recorded launches); `lambda` is then the multiplier 1
   // every rank holds partial Hcc / Schur sums; the lambda I of the camera block is added by rank 0 only
@@ -1041,7 +996,7 @@ static int linear_step(ba_problem *p, LMWorkFull *w, double lambda, int normaliz
 
 // cr: the model value is |J delta + cr r|^2 (1 outside the line search)
 // defer_delta: |delta_points|^2 and |delta_cameras|^2 are left to trial_point (one reduction pair with |r_trial|^2)
-static int step_scalars(ba_problem *p, LMWorkFull *w, hipStream_t st, double cr = -1.0, bool defer_delta = false) {
+static int step_scalars(ba_problem *p, LMWork *w, hipStream_t st, double cr = -1.0, bool defer_delta = false) {
   const bool first = cr < 0;  // the step as linear_step left it (the line search calls with a rescaled delta and its own cr)
   if (first) cr = w->cr0();
   if (!(first && w->model_done)) BA_CHECK(launch_model_sq(p, w->J_lin(), w->r_lin(), w->delta, w->partial, w->scal, SH_MODEL, st, cr));
@@ -1057,7 +1012,7 @@ static int step_scalars(ba_problem *p, LMWorkFull *w, hipStream_t st, double cr 
 
 // with_delta: the step's two norms ride with |r_trial|^2 (step_scalars was told to leave them); publish_flag: the reduction
 // also writes the controller's scalars and this pivot flag to the pinned host buffers (recorded sequences)
-static int trial_point(ba_problem *p, LMWorkFull *w, hipStream_t st, bool xf32 = false, bool with_delta = false,
+static int trial_point(ba_problem *p, LMWork *w, hipStream_t st, bool xf32 = false, bool with_delta = false,
                        const int *publish_flag = nullptr) {
   BA_CHECK(launch_axpy(p, w->nvar, w->x, w->delta, w->x_trial, st));
   if (xf32) {  // x_suiv is a Float32 vector in the reference: round, evaluate in Float32
@@ -1081,7 +1036,7 @@ static int trial_point(ba_problem *p, LMWorkFull *w, hipStream_t st, bool xf32 =
   return launch_sumsq_multi(p, &jobs, w->partial_multi, st);
 }
 
-static int check_pivot(ba_problem *p, LMWorkFull *w, hipStream_t st) {
+static int check_pivot(ba_problem *p, LMWork *w, hipStream_t st) {
   int h = 0;
   BA_HIP_CHECK(hipMemcpyAsync(&h, w->last_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
@@ -1105,9 +1060,9 @@ static int graph_key(ba_problem *p, int normalize, bool facto_f32, bool xf32) {
          256 * (p->fix_npnt > 0 ? 1 : 0);
 }
 static double graph_scale(ba_problem *p) { return p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0; }
-static bool graph_fix_same(ba_problem *p, LMWorkFull *w) { return w->g_fix_cam == p->d_fix_cam && w->g_fix_pnt == p->d_fix_pnt; }
+static bool graph_fix_same(ba_problem *p, LMWork *w) { return w->g_fix_cam == p->d_fix_cam && w->g_fix_pnt == p->d_fix_pnt; }
 
-static bool graphs_allowed(ba_problem *p, LMWorkFull *w) {
+static bool graphs_allowed(ba_problem *p, LMWork *w) {
   if (w->g_off || p->prof_on || p->comm.active() || w->f16 || w->pcg) return false;  // per-kernel events / communicator / Float16 path
   // the hoisted-diagonal schedule of large factorisations has a kernel wait for a flag raised by a kernel running
   // beside it: only with real streams is that concurrency certain (and the graphs gain nothing at that size)
@@ -1117,33 +1072,28 @@ static bool graphs_allowed(ba_problem *p, LMWorkFull *w) {
 }
 
 template <typename F>
-static int record_graph(hipStream_t st, hipGraphExec_t *out, F body) {
-  hipGraph_t g = nullptr;
+static int record_graph(hipStream_t st, HipGraphExec *out, F body) {
+  HipGraph g;
   BA_HIP_CHECK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-  int rc = body();
-  hipError_t e = hipStreamEndCapture(st, &g);
-  if (rc != BA_OK) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;
-  }
+  const int rc = body();
+  const hipError_t e = hipStreamEndCapture(st, g.out());
+  BA_CHECK(rc);
   BA_HIP_CHECK(e);
-  e = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  BA_HIP_CHECK(e);
+  BA_HIP_CHECK(hipGraphInstantiate(out->out(), g, nullptr, nullptr, 0));
   return BA_OK;
 }
 
 // A hoisted diagonal kernel of the dense factorisation gave up waiting for its flag: the kernels were not running side by
 // side (a counter-collecting profiler serialises them).  Switch the handle to the in-order schedule; the caller redoes
 // the step (S was consumed by the abandoned factorisation).
-static bool hoist_gave_up(LMWorkFull *w) {
+static bool hoist_gave_up(LMWork *w) {
   if (*w->h_flag != 2 || (w->ldl.hoist_disabled && w->ldl32.hoist_disabled)) return false;
   w->ldl.hoist_disabled = w->ldl32.hoist_disabled = true;
   return true;
 }
 
 // one trial step at damping `lambda`: linear solve, model decrease, trial residual, scalars and pivot flag to the host
-static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize, bool facto_f32, bool xf32,
+static int trial_step(ba_problem *p, LMWork *w, double lambda, int normalize, bool facto_f32, bool xf32,
                       hipStream_t st) {
   if (!graphs_allowed(p, w)) {
     BA_CHECK(linear_step(p, w, lambda, normalize, st, facto_f32));
@@ -1158,9 +1108,8 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
   const int key = graph_key(p, normalize, facto_f32, xf32);
   if (w->g_key != key || w->g_scale != graph_scale(p) || !graph_fix_same(p, w)) {
     for (int q = 0; q < 2; q++) {
-      if (w->g_step[q]) (void)hipGraphExecDestroy(w->g_step[q]);
-      if (w->g_refresh[q]) (void)hipGraphExecDestroy(w->g_refresh[q]);
-      w->g_step[q] = w->g_refresh[q] = nullptr;
+      w->g_step[q].reset();
+      w->g_refresh[q].reset();
     }
     w->g_key = key;
     w->g_scale = graph_scale(p);
@@ -1168,7 +1117,7 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
     w->g_fix_pnt = p->d_fix_pnt;
   }
   if (facto_f32) BA_CHECK(ensure_f32(w));  // no allocation while recording
-  hipGraphExec_t &g = w->g_step[w->parity];
+  HipGraphExec &g = w->g_step[w->parity];
   if (!g) {
     const int grc = record_graph(st, &g, [&]() -> int {
       BA_CHECK(linear_step(p, w, 1.0, normalize, st, facto_f32, w->d_lambda, w->h_lambda));
@@ -1178,7 +1127,7 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
     });
     if (grc != BA_OK) {  // recording is an optimisation: without it the same launches are issued one by one
       (void)hipGetLastError();
-      g = nullptr;
+      g.reset();
       w->g_off = true;
       return trial_step(p, w, lambda, normalize, facto_f32, xf32, st);
     }
@@ -1191,12 +1140,12 @@ static int trial_step(ba_problem *p, LMWorkFull *w, double lambda, int normalize
 }
 
 // after an accepted step (x/x_trial, r/r_trial already swapped): J, the normal-equation blocks, J'r, scalars to the host
-static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t st) {
+static int accept_refresh(ba_problem *p, LMWork *w, bool xf32, hipStream_t st) {
   if (!graphs_allowed(p, w)) {
     BA_CHECK(refresh_linearisation(p, w, false, st, xf32));
     return fetch_scalars(p, w, st);
   }
-  hipGraphExec_t &g = w->g_refresh[w->parity];
+  HipGraphExec &g = w->g_refresh[w->parity];
   if (!g) {
     const int grc = record_graph(st, &g, [&]() -> int {
       BA_CHECK(refresh_linearisation(p, w, false, st, xf32, true));  // (+ scalars to the host)
@@ -1204,7 +1153,7 @@ static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t s
     });
     if (grc != BA_OK) {
       (void)hipGetLastError();
-      g = nullptr;
+      g.reset();
       w->g_off = true;
       return accept_refresh(p, w, xf32, st);
     }
@@ -1220,12 +1169,12 @@ static int accept_refresh(ba_problem *p, LMWorkFull *w, bool xf32, hipStream_t s
 // (Dubrovnik: 31 + 79 us of a 3.0 ms iteration, LadyBug: the same of 0.44 ms; rocprofv3 kernel trace).  The refresh and the
 // trial write disjoint scalar slots, so one read of the pinned buffers serves both.  If the stopping tests that need the
 // refreshed |J'r| or |x| then end the loop, the prefetched step is dropped (never counted, x untouched).
-static bool can_prefetch_trial(ba_problem *p, LMWorkFull *w, int normalize, bool facto_f32, bool xf32) {
+static bool can_prefetch_trial(ba_problem *p, LMWork *w, int normalize, bool facto_f32, bool xf32) {
   if (env_off("BA_LM_PREFETCH") || !graphs_allowed(p, w)) return false;  // read per call: a test compares both forms in one process
   return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && graph_fix_same(p, w) &&
          w->g_step[w->parity] && w->g_refresh[w->parity];
 }
-static int accept_refresh_and_trial(LMWorkFull *w, double lambda, bool facto_f32, hipStream_t st) {
+static int accept_refresh_and_trial(LMWork *w, double lambda, bool facto_f32, hipStream_t st) {
   BA_HIP_CHECK(hipGraphLaunch(w->g_refresh[w->parity], st));
   *w->h_lambda = lambda;  // read by the trial sequence's first kernel; the previous trial sequence has completed
   w->last_f32 = facto_f32;
@@ -1243,7 +1192,7 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
   BA_CHECK(fix_upload(p));
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   hipStream_t st = p->stream;
   w->pcg = pcg;
   w->pcg_tol = tol > 0 ? tol : 1e-8;
@@ -1276,11 +1225,11 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
 }
 
 extern "C" int ba_lm_schur_memory(ba_problem *p, int64_t *tiles_full, int64_t *tiles_held, int64_t *tiles_staging) {
-  if (!p || !p->lm || !static_cast<LMWorkFull *>(p->lm)->ldl.S) {
+  if (!p || !p->lm || !p->lm->ldl.S) {
     ba_set_error("ba_lm_schur_memory: no direct solve has run on this handle yet");
     return BA_ERR_ARG;
   }
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   if (tiles_full) *tiles_full = w->ldl.nt * (w->ldl.nt + 1) / 2;
   if (tiles_held) *tiles_held = w->ldl.s_tiles;
   if (tiles_staging) *tiles_staging = w->ldl.own_only ? w->stage_tiles : 0;
@@ -1292,7 +1241,7 @@ extern "C" int ba_lm_schur_pattern(ba_problem *p, double *tile_fill, double *flo
     ba_set_error("ba_lm_schur_pattern: no direct solve has run on this handle yet");
     return BA_ERR_ARG;
   }
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   if (!w->ldl.S) {
     ba_set_error("ba_lm_schur_pattern: no direct solve has run on this handle yet");
     return BA_ERR_ARG;
@@ -1310,12 +1259,12 @@ static int set_ordering(ba_problem *p, int method) {
     return BA_ERR_ARG;
   }
   BA_CHECK(lm_ensure(p));
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   if (w->order_method == method) return BA_OK;
   if (w->ldl.S) {  // the task list, the pattern and the tiles depend on the order: start over
     lm_free(p);
     BA_CHECK(lm_ensure(p));
-    w = static_cast<LMWorkFull *>(p->lm);
+    w = p->lm;
   }
   w->order_method = method;
   return BA_OK;
@@ -1331,11 +1280,11 @@ extern "C" int ba_lm_set_ordering(ba_problem *p, int method) {
 }
 
 extern "C" int ba_lm_schur_ordering(ba_problem *p, int64_t *perm1, const char **name) {
-  if (!p || !p->lm || !static_cast<LMWorkFull *>(p->lm)->ldl.S) {
+  if (!p || !p->lm || !p->lm->ldl.S) {
     ba_set_error("ba_lm_schur_ordering: no direct solve has run on this handle yet");
     return BA_ERR_ARG;
   }
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   if (perm1)
     for (int64_t k = 0; k < p->ncams; k++) perm1[k] = (w->h_cam_perm.empty() ? k : (int64_t)w->h_cam_perm[(size_t)k]) + 1;
   if (name) *name = w->order_name;
@@ -1458,7 +1407,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
   BA_CHECK(fix_upload(p));
-  LMWorkFull *w = static_cast<LMWorkFull *>(p->lm);
+  LMWork *w = p->lm;
   hipStream_t st = p->stream;
   const int V = o->variant;
   // defaults: src/lm.jl:20-26 / src/LevenbergMarquardt.jl:21-26

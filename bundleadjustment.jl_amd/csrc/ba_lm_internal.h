@@ -1,4 +1,4 @@
-// Internal: LM workspace and launchers of the normal-equation kernels.
+// Internal: Schur task lists of the LM workspace and launchers of the normal-equation kernels.
 #pragma once
 #include "ba_internal.h"
 
@@ -13,18 +13,18 @@ constexpr int RED_BLOCKS = 1024;  // fixed number of partial sums => fixed summa
 // of tasks are summed by one wave as before.
 struct SchurTasks {
   int64_t nkeys = 0, ntasks = 0;
-  int *key_ptr = nullptr, *key_ca = nullptr, *key_cb = nullptr;  // device
-  int *task_a = nullptr, *task_b = nullptr;                       // device
+  DevBuf<int> key_ptr, key_ca, key_cb;                           // device
+  DevBuf<int> task_a, task_b;                                     // device
   int chunk = 0;                                                  // tasks per chunk; keys with more than 2 * chunk tasks are split
   int64_t nsplit = 0, nchunks = 0;
-  int *skey = nullptr, *skey_c0 = nullptr;                        // split keys: key id, first chunk (nsplit + 1 entries)
-  int *chunk_t0 = nullptr, *chunk_t1 = nullptr;                   // chunks: task range
-  double *partial = nullptr;                                      // nchunks x 81
+  DevBuf<int> skey, skey_c0;                                      // split keys: key id, first chunk (nsplit + 1 entries)
+  DevBuf<int> chunk_t0, chunk_t1;                                 // chunks: task range
+  DevBuf<double> partial;                                         // nchunks x 81
   std::vector<unsigned char> tile_occ;                            // host: nt x nt lower tile occupancy of S by the keys (before fill)
   // Fill-reducing camera ordering (ba_order.cpp): key_ca / key_cb are BLOCK ROWS of S; cam_of[k] (device; null = identity)
   // is the camera at block row k, pos its inverse.  Only the reduced camera system lives in that order: S, its right-hand
   // side and solution, the column scaling; x, J, Hcc, gc stay in the caller's camera order.
-  int *cam_of = nullptr, *pos = nullptr;
+  DevBuf<int> cam_of, pos;
   std::vector<int> h_key_cb, h_skey;                              // host copies (chunked assembly of a distributed run)
 };
 
@@ -35,8 +35,8 @@ struct SchurChunk {
   int64_t t0 = 0, ntiles = 0;
   int64_t seg = 0, my_t0 = 0, my_n = 0;  // reduce-scatter chunk: tiles per segment; where this rank's segment goes in its own S
   int64_t *cco = nullptr;  // device, nt entries (cco_alloc + 1: tix reads the table's head one entry before)
-  int64_t *cco_alloc = nullptr;
-  int *keys = nullptr, *skeys = nullptr;  // device: key ids / indices into the split-key list
+  DevBuf<int64_t> cco_alloc;
+  DevBuf<int> keys, skeys;  // device: key ids / indices into the split-key list
   int64_t nkeys = 0, nskeys = 0;
 };
 
@@ -115,31 +115,6 @@ struct SumsqJobs {
   void publish(const double *a, int na_, double *h_a, const double *b, int nb_, double *h_b, const int *flag, int *h_flag) {
     pa = a; na = na_; ha = h_a; pb = b; nb2 = nb_; hb = h_b; pflag = flag; hflag = h_flag;
   }
-};
-
-// scalar slots of LMWork::scal (device) / h_scal (pinned host)
-enum { SC_RSQ = 0, SC_RSQ_TRIAL, SC_MODEL, SC_DELTA, SC_XSQ, SC_JTR, SC_COUNT = 8 };
-
-struct LMWork {
-  int64_t nvar = 0, nequ = 0, n = 0, npad = 0;  // n = 9*ncams
-  double *x = nullptr, *x_trial = nullptr, *delta = nullptr;
-  double *r = nullptr, *r_trial = nullptr, *J = nullptr;
-  double *Hpp = nullptr, *gp = nullptr, *Uinv = nullptr, *u = nullptr;
-  double *Yobs = nullptr;                // 6/obs: U^-1 A_b' of the current damping
-  bool model_done = false;               // the step's model value was formed by the back-substitution pass
-  double *Hcc = nullptr, *gc = nullptr;  // gc: 9*ncams
-  double *hdiag = nullptr;               // npad: diag of the camera block of J'J summed over all ranks (column scalings)
-  double *rhs = nullptr;                 // npad
-  double *colscale = nullptr;            // nvar (normalize != None)
-  // facto_type = Float16: |J_j|^2, column norms, damping vector (nvar each), quantised J (24/obs) and r; allocated on first use
-  double *jn2 = nullptr, *dcol = nullptr, *damp = nullptr, *Jq = nullptr, *rq = nullptr;
-  double *partial = nullptr;             // RED_BLOCKS
-  double *partial_multi = nullptr;       // SUMSQ_JOBS x RED_BLOCKS (launch_sumsq_multi)
-  int *cam_pnt = nullptr;                // nobs: the point of every observation in camera order (pnt0[cam_obs[q]])
-  double *scal = nullptr;                // SC_COUNT device scalars
-  double *h_scal = nullptr;              // pinned host mirror
-  SchurTasks tasks;
-  DenseLDL ldl;
 };
 
 // d_lambda (optional device scalar): the damping used is lambda * d_lambda[0] (hipGraph replays, ba_lm.hip)

@@ -1026,6 +1026,44 @@ def test_pcg_only_handle_holds_nothing_of_the_size_of_S(ba, gpu_ok):
     m.close()
 
 
+def test_handle_lifecycle_returns_its_device_memory(ba, gpu_ok):
+    """Many cycles of: create a handle; LM runs under a robust loss, with fixed parameters, with facto_type = Float32 and
+    with facto = :PCG, the camera ordering switched between them (each switch after a direct solve rebuilds the workspace);
+    destroy the handle.  The device's free memory after the last cycle is back to within 1 MiB of its value after the first:
+    every buffer, stream, event and recorded sequence of a handle and its workspaces is released with it.  (The first
+    cycle warms the runtime's own pools up.  Before the owner types the robust loss's per-block partials, 16 KiB per
+    workspace, were never released.)"""
+    import time
+    import torch
+    p = ba.synthetic.make_problem(12, 400, 1800, seed=11)
+    arrays = ba.synthetic.as_arrays(p)
+    kw = dict(ite_max=2)
+
+    def cycle():
+        m = ba.BALNLPModel(arrays=arrays)
+        try:
+            fr = ba.FeasibilityResidual(m)
+            ba.Levenberg_Marquardt(fr, "LDL", "AMD", "None", False, loss="huber", f_scale=2.0, **kw)
+            ba.Levenberg_Marquardt(fr, "LDL", "Metis", "None", False, fixed_cameras=[1, 5], fixed_points=np.arange(1, 401, 9),
+                                   **kw)
+            ba.Levenberg_Marquardt(fr, "LDL", "natural", "J", False, facto_type=np.float32, **kw)
+            ba.Levenberg_Marquardt(fr, "PCG", "AMD", "None", False, **kw)
+        finally:
+            m.close()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info()[0]
+
+    cycles = 150
+    t0 = time.time()
+    free_first = cycle()
+    for _ in range(cycles - 1):
+        free_last = cycle()
+    lost = free_first - free_last
+    print(f"{cycles} cycles in {time.time() - t0:.1f} s; free device memory after the first {free_first / 2**20:.1f} MiB, after "
+          f"the last {free_last / 2**20:.1f} MiB ({lost / 2**10:.0f} KiB less)")
+    assert lost <= 2**20, f"{lost / 2**10:.0f} KiB of device memory not returned over {cycles - 1} handle lifecycles"
+
+
 def test_bench_line_contract(gpu_ok, tmp_path):
     """`python bench.py --full` prints ONE JSON line with the fields the driver reads (metric, value, unit, n_gpus, steps,
     warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.workload) plus roofline, cpu_baseline

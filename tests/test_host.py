@@ -342,3 +342,29 @@ def test_every_environment_switch_is_documented():
     assert len(read) >= 10  # (the patterns still match the way the sources read them)
     assert read == documented, (f"read but not in DESIGN §8: {sorted(read - documented)}; "
                                 f"in DESIGN §8 but not read: {sorted(documented - read)}")
+
+
+def test_device_resources_are_created_and_released_by_their_owners_only():
+    """Every device buffer, pinned buffer, stream, event and graph of the library has one owner (the owner types of
+    ba_internal.h), which releases what it holds: the calls that create or release such a resource appear in the product
+    sources (csrc/, the micro-benchmarks of csrc/bench/ aside) inside that section of ba_internal.h and nowhere else (a
+    release function is named there as a template argument as well)."""
+    csrc = os.path.join(ROOT, "bundleadjustment.jl_amd", "csrc")
+    calls = re.compile(r"\b(hipMalloc|hipHostMalloc|hipEventCreate\w*|hipStreamCreate\w*|hipFree|hipHostFree|hipEventDestroy|"
+                       r"hipStreamDestroy|hipGraphExecDestroy|hipGraphDestroy)\b")
+    comments = re.compile(r"//[^\n]*|/\*.*?\*/", re.S)
+    inside, outside = set(), []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".cpp", ".h")):
+            continue
+        src = comments.sub("", open(os.path.join(csrc, f)).read())
+        if f == "ba_internal.h":
+            full = open(os.path.join(csrc, f)).read()
+            begin = full.index("// ---- owners of device resources")
+            end = full.index("\n// ---- ", begin + 1)
+            inside = set(calls.findall(comments.sub("", full[begin:end])))
+            src = comments.sub("", full[:begin] + full[end:])
+        outside += [(f, c) for c in calls.findall(src)]
+    assert {"hipMalloc", "hipHostMalloc", "hipEventCreateWithFlags", "hipStreamCreateWithFlags", "hipFree", "hipHostFree",
+            "hipEventDestroy", "hipStreamDestroy", "hipGraphExecDestroy", "hipGraphDestroy"} <= inside  # (the section is where the pattern finds it)
+    assert not outside, f"device resources created or released outside the owner types of ba_internal.h: {outside}"
