@@ -196,6 +196,9 @@ enum ProfClass {
   PC_COMM,
   PC_ROBUST,  // k_robust_scale (robust loss: reweighting of r and J)
   PC_FIXED,   // k_fix_mask (fixed parameters: zeroing of their columns of J)
+  PC_COV_INV,     // covariance (ba_covariance): selected inversion of the factored S, with the rank check's diag(S) and min D_i / S_ii
+  PC_COV_CAMS,    // covariance: the cameras' 9 x 9 blocks (k_cov_cams)
+  PC_COV_POINTS,  // covariance: the points' 3 x 3 blocks (k_cov_points)
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];

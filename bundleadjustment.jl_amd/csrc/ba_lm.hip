@@ -1306,6 +1306,106 @@ extern "C" int ba_lm_step_f32(ba_problem *p, const double *x, double lambda, dou
   return lm_step_impl(p, x, lambda, delta, half_sq_model, jtr, true);
 }
 
+// Covariance at x: Sigma = (J~_F' J~_F + lambda I)^-1 under the handle's loss and mask, its cameras' 9 x 9 and points'
+// 3 x 3 diagonal blocks.  The reduced camera system is assembled as linear_step does, with a damping vector that is 1 on the
+// fixed entries and lambda on the free ones; its Float64 factor is inverted in place on the factor's pattern (selected
+// inversion); the point blocks follow from the camera pairs that share a point.  Every buffer the next LM step reads is
+// rebuilt by that step from its own x: the handle's later steps are unaffected.
+extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, double rank_tol, double *cam_cov, double *pnt_cov,
+                             double *min_rel_pivot) {
+  if (!p || !x) {
+    ba_set_error("ba_covariance: null argument");
+    return BA_ERR_ARG;
+  }
+  if (!std::isfinite(lambda) || lambda < 0) {
+    ba_set_error("ba_covariance: lambda must be finite and >= 0, got %g", lambda);
+    return BA_ERR_ARG;
+  }
+  if (std::isnan(rank_tol)) {
+    ba_set_error("ba_covariance: rank_tol is NaN (< 0: the default 1e-10, 0: no rank check)");
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("ba_covariance: one rank only (a communicator is attached to this handle)");
+    return BA_ERR_ARG;
+  }
+  const double tol = rank_tol < 0 ? 1e-10 : rank_tol;
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  BA_CHECK(lm_ensure(p));
+  BA_CHECK(fix_upload(p));
+  LMWork *w = p->lm;
+  hipStream_t st = p->stream;
+  w->pcg = false;
+  w->f16 = false;
+  BA_CHECK(ensure_dense(p, w));
+  const int64_t np3 = 3 * p->npnts;
+  std::vector<double> hdamp((size_t)w->nvar, lambda);
+  for (int64_t j = 0; j < p->npnts && p->fix_npnt > 0; j++)
+    if (p->h_fix_pnt[(size_t)j])
+      for (int q = 0; q < 3; q++) hdamp[(size_t)(3 * j + q)] = 1.0;
+  for (int64_t c = 0; c < p->ncams && p->fix_ncam > 0; c++)
+    for (int b = 0; b < 9; b++)
+      if ((p->h_fix_cam[(size_t)c] >> b) & 1u) hdamp[(size_t)(np3 + 9 * c + b)] = 1.0;
+  DevBuf<double> damp, sdiag, ratio, part, cams, pnts;
+  DevBuf<int> iota;
+  BA_CHECK(upload(damp, hdamp));
+  BA_CHECK(sdiag.alloc(w->npad));
+  BA_CHECK(ratio.alloc(1));
+  BA_HIP_CHECK(hipMemcpyAsync(w->x, x, (size_t)w->nvar * sizeof(double), hipMemcpyHostToDevice, st));
+  BA_CHECK(refresh_linearisation(p, w, true, st));
+  auto assemble_factor = [&]() -> int {
+    BA_CHECK(launch_schur_prep(p, lambda, w->Hpp, w->gp, w->Uinv, w->u, st, nullptr, damp));
+    BA_CHECK(launch_schur_blocks(p, &w->tasks, w->J, w->Uinv, w->Yobs, w->Hcc, lambda, w->ldl.S, w->ldl.col_off, w->n, w->npad, st,
+                                 nullptr, damp, w->ldl.s_tiles));
+    BA_CHECK(launch_cov_sdiag(p, &w->ldl, w->n, sdiag, nullptr, false, st));
+    BA_CHECK(dense_ldl_factor(p, &w->ldl, st, nullptr, (double *)nullptr));
+    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    BA_HIP_CHECK(hipStreamSynchronize(st));
+    return BA_OK;
+  };
+  BA_CHECK(assemble_factor());
+  if (hoist_gave_up(w)) BA_CHECK(assemble_factor());  // as lm_step_impl: the in-order schedule, the factorisation again
+  if (*w->h_flag == 2) {
+    ba_set_error("dense factorisation: a hoisted diagonal tile never became ready (internal scheduling error)");
+    return BA_ERR_HIP;
+  }
+  if (*w->h_flag) {
+    ba_set_error("ba_covariance: exactly zero pivot in the reduced camera system (fix a gauge, or pass lambda > 0)");
+    return BA_ERR_ZERO_PIVOT;
+  }
+  double h_ratio = 0;
+  BA_CHECK(launch_cov_sdiag(p, &w->ldl, w->n, sdiag, ratio, true, st));
+  BA_HIP_CHECK(hipMemcpyAsync(&h_ratio, ratio, sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  if (min_rel_pivot) *min_rel_pivot = h_ratio;
+  if (tol > 0 && !(h_ratio > tol)) {
+    ba_set_error("ba_covariance: the reduced camera system is numerically singular (min pivot / diagonal = %.3g <= rank_tol = %.3g): "
+                 "fix a gauge (ba_lm_set_fixed: e.g. one camera's pose and one translation component of another) or pass "
+                 "lambda > 0", h_ratio, tol);
+    return BA_ERR_ZERO_PIVOT;
+  }
+  if (!cam_cov && !pnt_cov) return BA_OK;
+  std::vector<int> h_iota((size_t)w->ldl.nt);
+  for (int64_t k = 0; k < w->ldl.nt; k++) h_iota[(size_t)k] = (int)k;
+  BA_CHECK(upload(iota, h_iota));
+  BA_CHECK(part.alloc(cov_part_tiles(w->ldl.nt) * NB * NB));
+  BA_CHECK(dense_ldl_selinv(p, &w->ldl, iota, part, st));
+  const uint16_t *fc = p->fix_ncam > 0 ? (const uint16_t *)p->d_fix_cam : nullptr;
+  const uint8_t *fp = p->fix_npnt > 0 ? (const uint8_t *)p->d_fix_pnt : nullptr;
+  if (cam_cov) {
+    BA_CHECK(cams.alloc(81 * p->ncams));
+    BA_CHECK(launch_cov_cams(p, &w->ldl, w->tasks.pos, fc, cams, st));
+    BA_HIP_CHECK(hipMemcpyAsync(cam_cov, cams, (size_t)81 * p->ncams * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  if (pnt_cov) {
+    BA_CHECK(pnts.alloc(9 * p->npnts));
+    BA_CHECK(launch_cov_points(p, &w->ldl, w->tasks.pos, w->J, w->Yobs, w->Uinv, fp, pnts, st));
+    BA_HIP_CHECK(hipMemcpyAsync(pnt_cov, pnts, (size_t)9 * p->npnts * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return BA_OK;
+}
+
 // A scalar with the width Julia's promotion rules give it: an operation rounds to Float32 exactly when both operands are
 // Float32 (Base promotion: Float32 op Float64 -> Float64).  Used by ba_lm_solve for Float32 models.
 namespace ts {

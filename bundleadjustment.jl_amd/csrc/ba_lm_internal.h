@@ -181,3 +181,15 @@ int launch_cg_step(ba_problem *p, const double *d_cg, const double *d_L45, const
 int launch_cg_beta_dir(ba_problem *p, int64_t n, const double *d_partial, double *d_cg, const double *d_z, double *d_p, int first,
                        hipStream_t st);
 int launch_wtv(ba_problem *p, const double *d_J, const double *d_Uinv, const double *d_v, double *d_h, hipStream_t st);
+
+// covariance at a solution (ba_cov_kernels.hip).  launch_cov_sdiag: before the factorisation diag(S) -> d_sd (n),
+// after it min_i D_i / S_ii -> d_ratio_out[0].  dense_ldl_selinv: S^-1 over the factor, in place (on the pattern of a block-sparse
+// S); d_iota: 0 .. nt-1 (the row lists of dense columns), d_part: cov_part_tiles(nt) tiles of partial sums.
+int launch_cov_sdiag(ba_problem *p, const DenseLDL *w, int64_t n, double *d_sd, double *d_ratio_out, bool after_factor, hipStream_t st);
+int64_t cov_part_tiles(int64_t nt);
+int dense_ldl_selinv(ba_problem *p, DenseLDL *w, const int *d_iota, double *d_part, hipStream_t st);
+// the cameras' 9 x 9 blocks (81 per camera, caller's order; d_pos: block row of a camera, null = identity) and the points'
+// 3 x 3 blocks (9 per point) of S^-1; fixed components / points 0 (either mask may be null)
+int launch_cov_cams(ba_problem *p, const DenseLDL *w, const int *d_pos, const uint16_t *d_fix_cam, double *d_out, hipStream_t st);
+int launch_cov_points(ba_problem *p, const DenseLDL *w, const int *d_pos, const double *d_J, const double *d_Y, const double *d_Uinv,
+                      const uint8_t *d_fix_pnt, double *d_out, hipStream_t st);

@@ -177,6 +177,50 @@ def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_
     return delta, half.value, jtr
 
 
+def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, fixed_points=None, fixed_camera_params=None,
+               rank_tol=None, cameras=True, points=True):
+    """Covariance at x (ba_covariance): the diagonal blocks of (J~_F'J~_F + lam I)^-1, J~ the Jacobian as lm_step sees it
+    under `loss` / `f_scale` and the fixed_* options (see Levenberg_Marquardt), F the free entries.  Returns (cam_cov (ncams,
+    9, 9) or None, pnt_cov (npnts, 3, 3) or None, min_rel_pivot): camera blocks in block order r1 r2 r3 t1 t2 t3 k1 k2 f,
+    rows and columns of fixed entries exactly 0, not scaled by a residual variance (multiply by 2 f / (nequ - n_free) for
+    that).  min_rel_pivot = min D_i / S_ii of the factored reduced camera system; at or below rank_tol (None: 1e-10, 0: no
+    check) it is numerically singular -- the gauge left free at lam = 0 -- and SQDException is raised (with the value as its
+    min_rel_pivot attribute).  Bad arguments raise ValueError before any device call."""
+    kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
+    _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
+    try:
+        lam = float(lam)
+    except (TypeError, ValueError):
+        raise ValueError(f"lam must be a finite number >= 0, got {lam!r}") from None
+    if not (np.isfinite(lam) and lam >= 0):
+        raise ValueError(f"lam must be a finite number >= 0, got {lam!r}")
+    if rank_tol is None:
+        tol = -1.0
+    else:
+        try:
+            tol = float(rank_tol)
+        except (TypeError, ValueError):
+            raise ValueError(f"rank_tol must be a finite number >= 0 (or None), got {rank_tol!r}") from None
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError(f"rank_tol must be a finite number >= 0 (or None), got {rank_tol!r}")
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
+    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
+    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
+    cam = np.empty((nlp.ncams, 9, 9)) if cameras else None
+    pnt = np.empty((nlp.npnts, 3, 3)) if points else None
+    piv = C.c_double(0)
+    try:
+        _lib.check(_lib.lib().ba_covariance(nlp.handle, _lib.ptr(x), lam, tol, _lib.ptr(cam) if cameras else None,
+                                            _lib.ptr(pnt) if points else None, C.byref(piv)))
+    except _lib.SQDException as e:
+        e.min_rel_pivot = piv.value
+        raise
+    return cam, pnt, piv.value
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

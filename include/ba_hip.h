@@ -316,6 +316,27 @@ int ba_robust_eval(ba_problem *p, const double *x, double *weights /* nobs or NU
  *   ba_lm_get_fixed : the number of fixed camera components and of fixed points the handle holds (either may be NULL). */
 int ba_lm_set_fixed(ba_problem *p, const uint16_t *cam_mask, const uint8_t *pnt_fixed);
 int ba_lm_get_fixed(const ba_problem *p, int64_t *n_fixed_cam_params, int64_t *n_fixed_points);
+
+/* ---- covariance at a solution (an extension: the reference has none) ------------------------------------------------
+ * At x, under the handle's loss (ba_lm_set_loss) and mask (ba_lm_set_fixed):  Sigma = (J~_F' J~_F + lambda I)^-1, J~ the
+ * Jacobian exactly as ba_lm_step sees it (reweighted under a robust loss, the columns of the fixed entries zeroed), F the free
+ * entries.  cam_cov (ncams * 81, or NULL): the 9 x 9 diagonal block of every camera, caller's camera order, row-major, block
+ * order r1 r2 r3 t1 t2 t3 k1 k2 f; pnt_cov (npnts * 9, or NULL): the 3 x 3 block of every point, row-major.  Rows and
+ * columns of fixed entries are exactly 0.  Sigma is not scaled by a residual variance: callers who want one multiply by the
+ * usual sigma^2 = 2 f / (nequ - n_free), f the objective at x (1/2 |r|^2, or the robust f) and n_free the free entries.
+ * Both blocks come from the point-eliminated reduced camera matrix S, assembled as the LM step does (damping 1 on the fixed
+ * entries, lambda on the free ones) and factored by the Float64 LDL' whatever facto a solve would use (:PCG included), with
+ * the handle's camera ordering and schedule (BA_SPARSE_S is honoured).
+ * Rank check: diag(S) is kept before the factorisation; min_rel_pivot (or NULL) receives min_i D_i / S_ii over the camera rows.
+ * A value at or below rank_tol (< 0: the default 1e-10; 0: no check) means S is numerically singular -- typically the
+ * 7-DoF similarity gauge left free -- and the call returns BA_ERR_ZERO_PIVOT (min_rel_pivot is still written); so does an
+ * exactly zero pivot.  Fix a gauge (e.g. one camera's pose and one translation component of another) or pass lambda > 0.
+ * lambda negative or not finite, rank_tol NaN, a handle with a communicator: BA_ERR_ARG.  The next ba_lm_step / ba_lm_solve
+ * on the handle gives the same bits as without this call in between. */
+int ba_covariance(ba_problem *p, const double *x, double lambda, double rank_tol,
+                  double *cam_cov /* ncams * 81, row-major 9x9 per camera, or NULL */,
+                  double *pnt_cov /* npnts * 9, row-major 3x3 per point, or NULL */,
+                  double *min_rel_pivot /* or NULL */);
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -136,3 +136,31 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
   return _ba_lm(model, 0, facto, perm, normalize, false, x, eltype(x), restol, satol, srtol, oatol, ortol, atol, rtol,
                 νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params)
 end
+
+"""
+    covariance(nlp, x; λ = 0.0, loss = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
+               fixed_camera_params = nothing, rank_tol = nothing)
+
+Covariance at `x` (an extension; include/ba_hip.h, ba_covariance): the diagonal blocks of (J̃_F'J̃_F + λI)⁻¹ under the loss
+and the fixed parameters given (keywords as Levenberg_Marquardt's).  Returns `(cam_cov, pnt_cov, min_rel_pivot)`:
+cam_cov[:, :, c] the 9 × 9 block of camera c (block order r1 r2 r3 t1 t2 t3 k1 k2 f), pnt_cov[:, :, i] the 3 × 3 block of
+point i; fixed rows and columns are 0.  Not scaled by a residual variance.  With the gauge free and λ = 0 the reduced
+camera system is singular: SQDException (rank_tol = nothing: the library's default, 0: no check).
+"""
+function covariance(nlp, x :: AbstractVector; λ :: Real = 0.0, loss :: Symbol = :linear, f_scale = 1.0,
+                    fixed_cameras = nothing, fixed_points = nothing, fixed_camera_params = nothing, rank_tol = nothing)
+  (isfinite(λ) && λ >= 0) || error("λ must be finite and >= 0")
+  _ba_set_loss(nlp, loss, f_scale)
+  _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, 0)
+  xv = Vector{Float64}(x)
+  cam = zeros(Float64, 81 * nlp.ncams)
+  pnt = zeros(Float64, 9 * nlp.npnts)
+  piv = Ref{Cdouble}(0.0)
+  bacheck(ccall((:ba_covariance, libba), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble},
+                                                Ref{Cdouble}),
+                nlp.handle, xv, Float64(λ), rank_tol === nothing ? -1.0 : Float64(rank_tol), cam, pnt, piv))
+  # the library's blocks are row-major; Julia is column-major: transpose each (they are symmetric up to rounding)
+  cc = permutedims(reshape(cam, 9, 9, nlp.ncams), (2, 1, 3))
+  pc = permutedims(reshape(pnt, 3, 3, nlp.npnts), (2, 1, 3))
+  return cc, pc, piv[]
+end
