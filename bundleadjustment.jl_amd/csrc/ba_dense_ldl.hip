@@ -1719,6 +1719,34 @@ int dense_ldl_alloc_S(DenseLDLT<T> *w) {
   return BA_OK;
 }
 
+// The tile rows of tile column pair q = (k, k+1): the c1 rows {k+1} + U_q below the diagonal tile of column k and, of them,
+// the c2 rows U_q below that of column k+1.  rows1 / rows2 are what the kernels take as `rows`: the pattern's device lists,
+// or null for a workspace without a pattern ("every tile row below the diagonal tile").  This is the one place that knows
+// which of the two it is; the schedules below are written once, over this view.
+struct PairRows {
+  int k, c1, c2;
+  const int *rows1, *rows2;
+  const int *h_rows1;  // host copy of rows1 (null: no pattern)
+  int row(int a) const { return h_rows1 ? h_rows1[a] : k + 1 + a; }  // tile row a of {k+1} + U_q (a + 1 of U_q)
+};
+
+template <typename T>
+static PairRows pair_rows(const DenseLDLT<T> *w, int q) {
+  PairRows r = {2 * q, 0, 0, nullptr, nullptr, nullptr};
+  if (const TilePattern *pat = w->pat) {
+    const int l0 = pat->prow_ptr[(size_t)q];
+    r.c1 = pat->prow_ptr[(size_t)q + 1] - l0;
+    r.rows1 = w->prow + l0;
+    r.rows2 = r.rows1 + 1;
+    r.h_rows1 = pat->prow.data() + l0;
+  } else {
+    r.c1 = std::max(0, (int)w->nt - r.k - 1);
+  }
+  r.c2 = r.c1 > 0 ? r.c1 - 1 : 0;
+  return r;
+}
+
+// ---- panel launchers: tile column k over `count` tile rows, `rows` as in PairRows ------------------------------------------
 template <typename T>
 static int launch_diag(ba_problem *p, DenseLDLT<T> *w, int k, hipStream_t st, const int *wait_ready = nullptr, bool clear_flag = false) {
   ProfScope ps(p, PC_LDL_DIAG, st);
@@ -1728,52 +1756,49 @@ static int launch_diag(ba_problem *p, DenseLDLT<T> *w, int k, hipStream_t st, co
   return BA_OK;
 }
 
-// b != null: forward substitution of b fused (y_k and b_i -= L_ik y_k); the last panel has no tile below it, its y_k
-// comes from the stand-alone forward step kernel.
+// the FWD instantiation of a panel kernel when a right-hand side rides along, the plain one otherwise
+template <typename K>
+static K fwd_kernel(const void *b, K with_fwd, K without) { return b ? with_fwd : without; }
+
+// b != null: forward substitution of b fused (y_k and b_i -= L_ik y_k); a panel with no tile below it has only its y_k,
+// which comes from the stand-alone forward step kernel.
 template <typename T>
-static int launch_trsm(ba_problem *p, DenseLDLT<T> *w, int k, T *V, T *b, hipStream_t st) {
-  const int m = (int)w->nt - k - 1;
+static int launch_trsm(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, T *V, T *b, hipStream_t st) {
   T *y = w->D + w->nt * NB;
-  if (m <= 0) {
+  if (count <= 0) {
     if (b) hipLaunchKernelGGL(k_fwd_step<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, b, y, k);
     return BA_OK;
   }
   ProfScope ps(p, PC_LDL_TRSM, st);
-  if (b)
-    hipLaunchKernelGGL((k_ldl_trsm_rs<T, true>), dim3(4 * m), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv + (int64_t)k * NB * NB,
-                       w->D + (int64_t)k * NB, V, k, b, y);
-  else
-    hipLaunchKernelGGL((k_ldl_trsm_rs<T, false>), dim3(4 * m), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv + (int64_t)k * NB * NB,
-                       w->D + (int64_t)k * NB, V, k, b, y);
+  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_trsm_rs<T, true>, k_ldl_trsm_rs<T, false>), dim3(4 * count), dim3(256), RS_LDS_ELEMS * sizeof(T),
+                     st, w->S, w->col_off, w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, b, y, rows);
   return BA_OK;
 }
 
 template <typename T>
-static int launch_col(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0, hipStream_t st) {
-  const int m = (int)w->nt - k - 1;
-  if (m <= 0) return BA_OK;
+static int launch_col(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, hipStream_t st) {
+  if (count <= 0) return BA_OK;
   ProfScope ps(p, PC_LDL_SYRK, st);
-  hipLaunchKernelGGL(k_ldl_col_rs<T>, dim3(4 * m), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, k);
+  hipLaunchKernelGGL(k_ldl_col_rs<T>, dim3(4 * count), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, k, rows);
   return BA_OK;
 }
 
-// pair update of the lower tiles (i, j), base <= j <= i, with panels k, k+1; `ready`: flag raised when tile (base, base)
-// is final (hoisted-diagonal schedule)
 // tiles up to which the pair update takes its row-split form (BA_LDL_UPDATE_RS_MAX; 0 disables)
 static int update_rs_max() {
   return env_int("BA_LDL_UPDATE_RS_MAX", 320);  // read per call: a test compares the two kernels in one process
 }
 
+// pair update with panels k, k+1 of the lower tiles (i, j), i >= j, over the `count` rows of U_q; `ready`: flag raised when
+// the first ready_tiles tiles are final (hoisted-diagonal schedule; never in the row-split form)
 template <typename T>
-static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, int base, const T *V0, const T *V1, hipStream_t st,
+static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, const T *V1, hipStream_t st,
                        int *ready = nullptr, int ready_tiles = 1) {
-  const int nt = (int)w->nt, m = nt - base;
-  if (m <= 0) return BA_OK;
-  const int nblk = m * (m + 1) / 2;
+  const int nblk = count * (count + 1) / 2;
+  if (nblk <= 0) return BA_OK;
   if (!ready && nblk <= update_rs_max()) {  // short update: row-split form (see k_ldl_update_rs)
     ProfScope ps(p, PC_LDL_UPDATE_RS, st);
-    hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * nblk), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, k, base, nblk,
-                       (const int *)nullptr);
+    hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * nblk), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, k, k + 2, nblk,
+                       rows);
     return BA_OK;
   }
   ProfScope ps(p, PC_LDL_UPDATE, st);
@@ -1786,8 +1811,8 @@ static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, int base, const T 
   // 34.1-34.3 ms against 33.9-34.1 at n = 16 002.  A partial round does not cost a full one -- the quadrant kernel took
   // 39 us on average, which is what the big kernel's own last round costs.)
   hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S,
-                     w->col_off, V0, V1, k, base, nt, nblk, ready, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
-                     ready_tiles, (const int *)nullptr, (const T *)nullptr, (const T *)nullptr, (const int2 *)nullptr, TSB);
+                     w->col_off, V0, V1, k, k + 2, (int)w->nt, nblk, ready, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
+                     ready_tiles, rows);
   return BA_OK;
 }
 
@@ -1796,12 +1821,8 @@ template <typename T>
 static int launch_pairdiag(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *b, hipStream_t st, const int *wait_ready, int need) {
   ProfScope ps(p, PC_LDL_DIAG, st);
   T *y = w->D + w->nt * NB;
-  if (b)
-    hipLaunchKernelGGL((k_ldl_pairdiag<T, true>), dim3(1), dim3(256), DIAG_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv, w->D,
-                       V0, k, (int)w->nt, w->flag, wait_ready, need, b, y);
-  else
-    hipLaunchKernelGGL((k_ldl_pairdiag<T, false>), dim3(1), dim3(256), DIAG_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv, w->D,
-                       V0, k, (int)w->nt, w->flag, wait_ready, need, b, y);
+  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_pairdiag<T, true>, k_ldl_pairdiag<T, false>), dim3(1), dim3(256), DIAG_LDS_ELEMS * sizeof(T), st,
+                     w->S, w->col_off, w->Linv, w->D, V0, k, (int)w->nt, w->flag, wait_ready, need, b, y);
   return BA_OK;
 }
 
@@ -1811,12 +1832,33 @@ static int launch_pairtrsm(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, 
   if (m <= 0) return BA_OK;
   ProfScope ps(p, PC_LDL_TRSM, st);
   const T *y = w->D + w->nt * NB;
-  if (b)
-    hipLaunchKernelGGL((k_ldl_pairtrsm<T, true>), dim3(4 * m), dim3(256), PT_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv,
-                       w->D, V0, V1, k, b, y);
-  else
-    hipLaunchKernelGGL((k_ldl_pairtrsm<T, false>), dim3(4 * m), dim3(256), PT_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, w->Linv,
-                       w->D, V0, V1, k, b, y);
+  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_pairtrsm<T, true>, k_ldl_pairtrsm<T, false>), dim3(4 * m), dim3(256), PT_LDS_ELEMS * sizeof(T), st,
+                     w->S, w->col_off, w->Linv, w->D, V0, V1, k, b, y);
+  return BA_OK;
+}
+
+// The panel chain: everything of pair r after its first diagonal tile -- panel solve of column k over {k+1} + U_q, column
+// update, diag(k+1), panel solve of column k+1 over U_q (b != null: the forward substitution rides along).  A caller whose
+// diag(k) is not done yet (hoisted, or launched behind the previous pair's update) launches it first.
+template <typename T>
+static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0, T *V1, T *b, hipStream_t st) {
+  launch_trsm(p, w, r.k, r.rows1, r.c1, V0, b, st);
+  if (r.c1 == 0) return BA_OK;  // last, single tile column: y_k only
+  launch_col(p, w, r.k, r.rows1, r.c1, V0, st);
+  launch_diag(p, w, r.k + 1, st);
+  launch_trsm(p, w, r.k + 1, r.rows2, r.c2, V1, b, st);
+  return BA_OK;
+}
+
+// the pivot flag read back for a caller that asks for it (0: fine; see DenseLDLT::flag); synchronises st
+template <typename T>
+static int read_pivot_flag(DenseLDLT<T> *w, hipStream_t st, int *zero_pivot) {
+  BA_HIP_CHECK(hipGetLastError());
+  if (!zero_pivot) return BA_OK;
+  int h = 0;
+  BA_HIP_CHECK(hipMemcpyAsync(&h, w->flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  *zero_pivot = h;
   return BA_OK;
 }
 
@@ -1838,8 +1880,6 @@ template <typename T>
 int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b) {
   if (w->sparse && !p->comm.active()) return dense_ldl_factor_sparse(p, w, st, zero_pivot, d_b);
   const int nt = (int)w->nt;
-  const int64_t panel = (int64_t)nt * NB * NB;
-  T *Vs[2][2] = {{w->V, w->V + panel}, {w->V + 2 * panel, w->V + 3 * panel}};
   constexpr int HOIST_MIN_TILES = 32;  // below ~2 rounds of tiles the update is shorter than wait + factor
   // The waiting workgroup keeps one CU of one XCD from the update, whose blocks the hardware deals round-robin to the
   // XCDs: that XCD runs 32/31 longer and the launch ends with it -- 3 % of the update time, which grows as nt^3 while
@@ -1867,45 +1907,31 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_p
   static const bool fuse_off = env_off("BA_LDL_FUSE");
   auto fused = [&](int k) { return w->hoisting && !fuse_off && k >= 2 && k + 1 < nt && nt - k >= FUSE_MIN_TILES; };
   launch_diag(p, w, 0, st, nullptr, !w->hoisting);
-  for (int k = 0, q = 0; k < nt; k += 2, q ^= 1) {
-    T *V0 = Vs[q][0], *V1 = Vs[q][1];
+  for (int k = 0, slot = 0; k < nt; k += 2, slot ^= 1) {
+    const PairRows r = pair_rows(w, k / 2);
+    T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
     const bool more = k + 2 < nt;
     const bool next_fused = more && fused(k + 2);
     const bool next_hoist1 = more && !next_fused && w->hoisting && (nt - k - 2 >= HOIST_MIN_TILES);
     const int need = (k + 3 < nt) ? 3 : 1;
     if (next_fused) {  // the next pair's leading tiles: waits in place for `need` tiles of this pair's trailing update
-      launch_pairdiag(p, w, k + 2, Vs[q ^ 1][0], d_b, w->hoist, w->ready + k + 2, need);
+      launch_pairdiag(p, w, k + 2, w->vpanel(slot ^ 1, 0), d_b, w->hoist, w->ready + k + 2, need);
       BA_HIP_CHECK(hipEventRecord(w->ev_chain, w->hoist));
     } else if (next_hoist1) {  // the next pair's first diagonal tile only
       launch_diag(p, w, k + 2, w->hoist, w->ready + k + 2);
       BA_HIP_CHECK(hipEventRecord(w->ev_chain, w->hoist));
     }
-    if (fused(k)) {
-      launch_pairtrsm(p, w, k, V0, V1, d_b, st);
-    } else {
-      launch_trsm(p, w, k, V0, d_b, st);  // diag(k) is done: first tile, hoisted, or the in-order branch below
-      if (k + 1 < nt) {
-        launch_col(p, w, k, V0, st);
-        launch_diag(p, w, k + 1, st);
-        launch_trsm(p, w, k + 1, V1, d_b, st);
-      }
-    }
+    if (fused(k)) launch_pairtrsm(p, w, k, V0, V1, d_b, st);
+    else panel_chain(p, w, r, V0, V1, d_b, st);  // diag(k) is done: first tile, hoisted, or the in-order branch below
     if (!more) break;
     const bool hoisted = next_fused || next_hoist1;
-    launch_pair(p, w, k, k + 2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1);
+    launch_pair(p, w, k, r.rows2, r.c2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1);
     if (hoisted)
       BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_chain, 0));  // join: the hoisted workgroup's outputs are written
     else
       launch_diag(p, w, k + 2, st);
   }
-  BA_HIP_CHECK(hipGetLastError());
-  if (zero_pivot) {
-    int h = 0;
-    BA_HIP_CHECK(hipMemcpyAsync(&h, w->flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    BA_HIP_CHECK(hipStreamSynchronize(st));
-    *zero_pivot = h;
-  }
-  return BA_OK;
+  return read_pivot_flag(w, st, zero_pivot);
 }
 
 // ---- block-sparse reduced camera system ---------------------------------------------------------------------------------
@@ -2026,6 +2052,22 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
 // with locality 0.13, whose rests are 120 tiles, two runs per launch: 16 / 48 / 96 / 160 / 256 -> 11.8 / 11.8 / 11.8 / 12.7 /
 // 12.7 ms; the Final shape is indifferent).  What shortens the chain itself: two independent runs of pairs advancing in
 // the same launches, below ("Two runs").
+constexpr int REST_CUS = 224;  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
+static int rest_grid(int ntile) { return (ntile + 1) / 2 < REST_CUS ? (ntile + 1) / 2 : REST_CUS; }  // two tiles per workgroup
+
+// The look-ahead's split of pair r's trailing update: the first nlead rows of U_q are the next pair's own tile columns
+// (k+2, k+3: at the head of the ascending list); the lead strip is the lead_tiles tiles of those columns, the rest the
+// rest_tiles lower tiles over the remaining rows.
+struct UpdateSplit {
+  int nlead, lead_tiles, rest_tiles;
+};
+static UpdateSplit update_split(const PairRows &r) {
+  int nlead = 0;
+  while (nlead < r.c2 && nlead < 2 && r.row(1 + nlead) < r.k + 4) nlead++;
+  const int nrest = r.c2 - nlead;
+  return {nlead, nlead == 0 ? 0 : (nlead == 1 ? r.c2 : 2 * r.c2 - 1), nrest * (nrest + 1) / 2};
+}
+
 template <typename T>
 int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b) {
   const int nt = (int)w->nt;
@@ -2037,7 +2079,6 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
   // read per call: tests compare both schedules in one process, and force the minimum to 1
   const bool lookahead = !p->prof_on && !env_off("BA_SPARSE_LOOKAHEAD");
   const int la_min = env_int("BA_SPARSE_LOOKAHEAD_MIN", 96);
-  constexpr int REST_CUS = 224;  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
   bool pending[2] = {false, false};  // rest of pair q (slot q & 1) launched on the second stream and not yet joined
   auto join_rest = [&](int slot) -> int {
     if (pending[slot]) {
@@ -2046,63 +2087,20 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
     }
     return BA_OK;
   };
-  auto launch_update = [&](hipStream_t s2, const T *V0, const T *V1, int k, const int *rows, int cnt) {
-    const int nblk = cnt * (cnt + 1) / 2;
-    if (nblk <= 0) return;
-    ProfScope ps(p, nblk <= update_rs_max() ? PC_LDL_UPDATE_RS : PC_LDL_UPDATE, s2);
-    if (nblk <= update_rs_max())
-      hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * nblk), dim3(256), RS_LDS_ELEMS * sizeof(T), s2, w->S, w->col_off, V0, V1, k, k + 2,
-                         nblk, rows, 0);
-    else
-      hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), s2, w->S,
-                         w->col_off, V0, V1, k, k + 2, nt, nblk, (int *)nullptr, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
-                         1, rows);
+  // the lead of pair q is on the main stream: its rest starts behind it on the second stream, beside the next chain
+  auto fork_rest = [&](int slot) -> int {
+    BA_HIP_CHECK(hipEventRecord(w->ev_recv[slot], st));  // both panels of pair q complete, its lead tiles updated
+    BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
+    return BA_OK;
   };
-  // the panel chain of pair q on stream s: diag(k), panel solve over {k+1} + U_q, column update, diag(k+1), panel solve over U_q
-  // (+ the forward substitution of d_b).  Returns the number of rows of U_q whose trailing update is still to do (0: none).
-  auto chain = [&](int q, hipStream_t s, T *V0, T *V1, bool clear_flag) -> int {
-    const int k = 2 * q;
-    const int l0 = pat->prow_ptr[(size_t)q], l1 = pat->prow_ptr[(size_t)q + 1];
-    const int c1 = l1 - l0;                      // {k+1} + U_q
-    const int c2 = c1 > 0 ? c1 - 1 : 0;          // U_q
-    const int *rows1 = w->prow + l0, *rows2 = w->prow + l0 + 1;
-    launch_diag(p, w, k, s, nullptr, clear_flag);
-    if (c1 == 0) {  // last, single tile column: y_k only
-      if (d_b) hipLaunchKernelGGL(k_fwd_step<T>, dim3(1), dim3(256), 0, s, w->S, w->col_off, w->Linv, d_b, y, k, (const int *)nullptr);
-      return 0;
-    }
-    {
-      ProfScope ps(p, PC_LDL_TRSM, s);
-      if (d_b)
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, true>), dim3(4 * c1), dim3(256), RS_LDS_ELEMS * sizeof(T), s, w->S, w->col_off,
-                           w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V0, k, d_b, y, rows1);
-      else
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, false>), dim3(4 * c1), dim3(256), RS_LDS_ELEMS * sizeof(T), s, w->S, w->col_off,
-                           w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V0, k, d_b, y, rows1);
-    }
-    {
-      ProfScope ps(p, PC_LDL_SYRK, s);
-      hipLaunchKernelGGL(k_ldl_col_rs<T>, dim3(4 * c1), dim3(256), RS_LDS_ELEMS * sizeof(T), s, w->S, w->col_off, V0, k, rows1);
-    }
-    launch_diag(p, w, k + 1, s);
-    if (c2 == 0) {
-      if (d_b) hipLaunchKernelGGL(k_fwd_step<T>, dim3(1), dim3(256), 0, s, w->S, w->col_off, w->Linv, d_b, y, k + 1, (const int *)nullptr);
-      return 0;
-    }
-    {
-      ProfScope ps(p, PC_LDL_TRSM, s);
-      if (d_b)
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, true>), dim3(4 * c2), dim3(256), RS_LDS_ELEMS * sizeof(T), s, w->S, w->col_off,
-                           w->Linv + (int64_t)(k + 1) * NB * NB, w->D + (int64_t)(k + 1) * NB, V1, k + 1, d_b, y, rows2);
-      else
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, false>), dim3(4 * c2), dim3(256), RS_LDS_ELEMS * sizeof(T), s, w->S, w->col_off,
-                           w->Linv + (int64_t)(k + 1) * NB * NB, w->D + (int64_t)(k + 1) * NB, V1, k + 1, d_b, y, rows2);
-    }
-    return c2;
+  auto rest_launched = [&](int slot) -> int {
+    BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
+    pending[slot] = true;
+    return BA_OK;
   };
   // Two runs (TilePattern::a_clean / b_clean: the ordering eliminated a profile from both ends, ba_order.cpp): the first
   // a_clean pairs and the b_clean pairs from `split` touch disjoint tiles, rows of the right-hand side and panel buffers
-  // (slot 0 / slot 1).  They advance together, pair i of either run in the SAME launches ("two runs per launch" above): one
+  // (run 0 / run 1).  They advance together, pair i of either run in the SAME launches ("two runs per launch" above): one
   // stream, no event, half the launches -- the kernels of a panel chain are a workgroup or a few dozen each and the latency of
   // a launch with two panels' worth of them is that of one.  The longer run finishes alone; every other pair follows below in
   // index order.  Each tile still receives its updates in ascending pair order WITHIN a run; the frontier's tiles receive the
@@ -2115,58 +2113,40 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
     const int both = std::min(pat->a_clean, pat->b_clean);
     for (int i = 0; i < both; i++) {
       const int slot = i & 1;
-      // panel buffers: run A takes panels 0..3 (two slots of two), run B panels 4..7; the slots alternate for the look-ahead
-      T *VA = w->V + 2 * slot * panel, *VB = w->V + (4 + 2 * slot) * panel;
-      const int qa = i, qb = pat->split + i, ka = 2 * qa, kb = 2 * qb;
-      const int la = pat->prow_ptr[(size_t)qa], lb = pat->prow_ptr[(size_t)qb];
-      const int c1a = pat->prow_ptr[(size_t)qa + 1] - la, c1b = pat->prow_ptr[(size_t)qb + 1] - lb;  // {k+1} + U_q: >= 2 inside a run
-      const int c2a = c1a - 1, c2b = c1b - 1;
+      const PairRows a = pair_rows(w, i), b = pair_rows(w, pat->split + i);  // (c1 >= 2 inside a run)
+      T *VA = w->vpanel(slot, 0, 0), *VB = w->vpanel(slot, 0, 1);  // the slots alternate for the look-ahead
       auto tile = [&](int k) { return w->S + tix(w->hco(), k, k) * NB * NB; };
       auto panel_of = [&](int k, T *V, const int *rows) { return RunPanel<T>{w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, rows}; };
+      auto diag2 = [&](int ka, int kb) {
+        hipLaunchKernelGGL(k_ldl_diag2<T>, dim3(2), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(T), st, tile(ka), w->Linv + (int64_t)ka * NB * NB,
+                           w->D + (int64_t)ka * NB, tile(kb), w->Linv + (int64_t)kb * NB * NB, w->D + (int64_t)kb * NB, w->flag);
+      };
+      auto trsm2 = [&](const RunPanel<T> &pa, int ca, const RunPanel<T> &pb, int cb) {
+        hipLaunchKernelGGL(fwd_kernel(d_b, k_ldl_trsm_rs2<T, true>, k_ldl_trsm_rs2<T, false>), dim3(4 * (ca + cb)), dim3(256),
+                           RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, pa, pb, 4 * ca, d_b, y);
+      };
       BA_CHECK(join_rest(slot));  // (the rests of the step two back read these panel buffers)
-      hipLaunchKernelGGL(k_ldl_diag2<T>, dim3(2), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(T), st, tile(ka), w->Linv + (int64_t)ka * NB * NB,
-                         w->D + (int64_t)ka * NB, tile(kb), w->Linv + (int64_t)kb * NB * NB, w->D + (int64_t)kb * NB, w->flag);
-      const RunPanel<T> a0 = panel_of(ka, VA, w->prow + la), b0 = panel_of(kb, VB, w->prow + lb);
-      if (d_b)
-        hipLaunchKernelGGL((k_ldl_trsm_rs2<T, true>), dim3(4 * (c1a + c1b)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * c1a, d_b, y);
-      else
-        hipLaunchKernelGGL((k_ldl_trsm_rs2<T, false>), dim3(4 * (c1a + c1b)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * c1a, d_b, y);
-      hipLaunchKernelGGL(k_ldl_col_rs2<T>, dim3(4 * (c1a + c1b)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * c1a);
-      hipLaunchKernelGGL(k_ldl_diag2<T>, dim3(2), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(T), st, tile(ka + 1),
-                         w->Linv + (int64_t)(ka + 1) * NB * NB, w->D + (int64_t)(ka + 1) * NB, tile(kb + 1), w->Linv + (int64_t)(kb + 1) * NB * NB,
-                         w->D + (int64_t)(kb + 1) * NB, w->flag);
-      const RunPanel<T> a1 = panel_of(ka + 1, VA + panel, w->prow + la + 1), b1 = panel_of(kb + 1, VB + panel, w->prow + lb + 1);
-      if (d_b)
-        hipLaunchKernelGGL((k_ldl_trsm_rs2<T, true>), dim3(4 * (c2a + c2b)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a1, b1, 4 * c2a, d_b, y);
-      else
-        hipLaunchKernelGGL((k_ldl_trsm_rs2<T, false>), dim3(4 * (c2a + c2b)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a1, b1, 4 * c2a, d_b, y);
+      diag2(a.k, b.k);
+      const RunPanel<T> a0 = panel_of(a.k, VA, a.rows1), b0 = panel_of(b.k, VB, b.rows1);
+      trsm2(a0, a.c1, b0, b.c1);
+      hipLaunchKernelGGL(k_ldl_col_rs2<T>, dim3(4 * (a.c1 + b.c1)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * a.c1);
+      diag2(a.k + 1, b.k + 1);
+      trsm2(panel_of(a.k + 1, VA + panel, a.rows2), a.c2, panel_of(b.k + 1, VB + panel, b.rows2), b.c2);
       // the two pair updates: panels (k, k+1) of either run over its U_q -- with the look-ahead of the single run (lead strips of
       // both runs first, both rests on a part of the chip beside the next step's chain) when the rests are long enough
-      auto nlead_of = [&](int l0, int c2, int k) {
-        int nl = 0;
-        while (nl < c2 && nl < 2 && pat->prow[(size_t)(l0 + 1 + nl)] < k + 4) nl++;
-        return nl;
-      };
-      const int nla = nlead_of(la, c2a, ka), nlb = nlead_of(lb, c2b, kb);
-      const int ra = c2a - nla, rb = c2b - nlb, rest_a = ra * (ra + 1) / 2, rest_b = rb * (rb + 1) / 2;
-      if (lookahead && i + 1 < both && rest_a + rest_b >= 2 * la_min) {
-        BA_CHECK(join_rest(slot ^ 1));
-        const int sa = nla == 0 ? 0 : (nla == 1 ? c2a : 2 * c2a - 1), sb = nlb == 0 ? 0 : (nlb == 1 ? c2b : 2 * c2b - 1);
-        const RunPanel<T> ua = panel_of(ka, VA, w->prow + la + 1), ub = panel_of(kb, VB, w->prow + lb + 1);
-        if (sa + sb > 0)
-          hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (sa + sb)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, ua, sa, ub, sb, panel, c2a, c2b);
-        BA_HIP_CHECK(hipEventRecord(w->ev_recv[slot], st));
-        BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
-        const RunPanel<T> qa2 = panel_of(ka, VA, w->prow + la + 1 + nla), qb2 = panel_of(kb, VB, w->prow + lb + 1 + nlb);
-        const int ntile = rest_a + rest_b;
-        hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3((ntile + 1) / 2 < REST_CUS ? (ntile + 1) / 2 : REST_CUS), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
-                           qa2, rest_a, qb2, rest_b, panel);
-        BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
-        pending[slot] = true;
+      const UpdateSplit sa = update_split(a), sb = update_split(b);
+      const RunPanel<T> ua = panel_of(a.k, VA, a.rows2), ub = panel_of(b.k, VB, b.rows2);
+      BA_CHECK(join_rest(slot ^ 1));
+      if (lookahead && i + 1 < both && sa.rest_tiles + sb.rest_tiles >= 2 * la_min) {
+        if (sa.lead_tiles + sb.lead_tiles > 0)
+          hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (sa.lead_tiles + sb.lead_tiles)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off,
+                             ua, sa.lead_tiles, ub, sb.lead_tiles, panel, a.c2, b.c2);
+        BA_CHECK(fork_rest(slot));
+        hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3(rest_grid(sa.rest_tiles + sb.rest_tiles)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
+                           panel_of(a.k, VA, a.rows2 + sa.nlead), sa.rest_tiles, panel_of(b.k, VB, b.rows2 + sb.nlead), sb.rest_tiles, panel);
+        BA_CHECK(rest_launched(slot));
       } else {
-        BA_CHECK(join_rest(slot ^ 1));
-        const RunPanel<T> ua = panel_of(ka, VA, w->prow + la + 1), ub = panel_of(kb, VB, w->prow + lb + 1);
-        const int na = c2a * (c2a + 1) / 2, nb2 = c2b * (c2b + 1) / 2;
+        const int na = a.c2 * (a.c2 + 1) / 2, nb2 = b.c2 * (b.c2 + 1) / 2;
         if (na + nb2 <= update_rs_max())
           hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (na + nb2)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, ua, na, ub, nb2, panel, 0, 0);
         else
@@ -2184,53 +2164,35 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
     for (int q = 0; q < npairs; q++) order.push_back(q);
   }
   for (size_t it = 0; it < order.size(); it++) {
-    const int q = order[it], k = 2 * q;
+    const PairRows r = pair_rows(w, order[it]);
     const int slot = (int)(it & 1);
-    T *V0 = w->V + 2 * slot * panel, *V1 = V0 + panel;
-    const int l0 = pat->prow_ptr[(size_t)q];
-    const int *rows2 = w->prow + l0 + 1;
+    T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
     BA_CHECK(join_rest(slot));  // (the rest of the pair two steps back read these panel buffers; joined long ago: see lead below)
-    const int c2 = chain(q, st, V0, V1, !two && q == 0);  // (in one chain the first diagonal kernel clears the pivot flag)
-    if (c2 == 0) continue;
-    // the rows of U_q that are the next pair's own tile columns (k+2, k+3): at the head of the ascending list
-    const bool next_adjacent = it + 1 < order.size() && order[it + 1] == q + 1;
-    int nlead = 0;
-    while (nlead < c2 && nlead < 2 && pat->prow[(size_t)(l0 + 1 + nlead)] < k + 4) nlead++;
-    const int nrest = c2 - nlead;
-    if (lookahead && next_adjacent && nrest * (nrest + 1) / 2 >= la_min) {
+    launch_diag(p, w, r.k, st, nullptr, !two && r.k == 0);  // (in one chain the first diagonal kernel clears the pivot flag)
+    panel_chain(p, w, r, V0, V1, d_b, st);
+    if (r.c2 == 0) continue;
+    const bool next_adjacent = it + 1 < order.size() && order[it + 1] == order[it] + 1;
+    const UpdateSplit s = update_split(r);
+    BA_CHECK(join_rest(slot ^ 1));  // rest(q-1) has updated the lead tiles too (and the next chain reads its columns)
+    if (lookahead && next_adjacent && s.rest_tiles >= la_min) {
       // the lead first, alone on the chip (beside the rest it takes as long as the whole update: measured), then the rest
       // beside the next chain
-      BA_CHECK(join_rest(slot ^ 1));  // rest(q-1) has updated the lead tiles too (and the next chain reads its columns)
-      if (nlead > 0) {
-        const int nblk = nlead == 1 ? c2 : 2 * c2 - 1;
+      if (s.nlead > 0) {
         ProfScope ps(p, PC_LDL_UPDATE_RS, st);
-        hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * nblk), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, k, k + 2,
-                           nblk, rows2, c2);
+        hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * s.lead_tiles), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, r.k,
+                           r.k + 2, s.lead_tiles, r.rows2, r.c2);
       }
-      BA_HIP_CHECK(hipEventRecord(w->ev_recv[slot], st));  // both panels of pair q complete, its lead tiles updated
-      BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
-      {
-        const int nblk = nrest * (nrest + 1) / 2;
-        hipLaunchKernelGGL(k_ldl_update_part<T>, dim3((nblk + 1) / 2 < REST_CUS ? (nblk + 1) / 2 : REST_CUS), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
-                           V0, V1, k, nblk, rows2 + nlead);
-      }
-      BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
-      pending[slot] = true;
+      BA_CHECK(fork_rest(slot));
+      hipLaunchKernelGGL(k_ldl_update_part<T>, dim3(rest_grid(s.rest_tiles)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off, V0, V1,
+                         r.k, s.rest_tiles, r.rows2 + s.nlead);
+      BA_CHECK(rest_launched(slot));
     } else {
-      BA_CHECK(join_rest(slot ^ 1));
-      launch_update(st, V0, V1, k, rows2, c2);
+      launch_pair(p, w, r.k, r.rows2, r.c2, V0, V1, st);
     }
   }
   BA_CHECK(join_rest(0));
   BA_CHECK(join_rest(1));
-  BA_HIP_CHECK(hipGetLastError());
-  if (zero_pivot) {
-    int h = 0;
-    BA_HIP_CHECK(hipMemcpyAsync(&h, w->flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    BA_HIP_CHECK(hipStreamSynchronize(st));
-    *zero_pivot = h;
-  }
-  return BA_OK;
+  return read_pivot_flag(w, st, zero_pivot);
 }
 
 // pair update (panels k, k+1) of the owned tile columns own_cols[m0 .. m1)
@@ -2243,8 +2205,8 @@ static int launch_pair_owned(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0,
   ProfScope ps(p, PC_LDL_UPDATE, st);
   const T *Lp0 = nullptr, *Lp1 = nullptr;
   if (w->own_only) {  // the panels' L tiles: the buffer that travels with the V buffer this pair uses
-    Lp0 = w->Lb + (V0 - w->V);
-    Lp1 = w->Lb + (V1 - w->V);
+    Lp0 = w->L_of(V0);
+    Lp1 = w->L_of(V1);
   }
   hipLaunchKernelGGL((k_ldl_update<T, 1, true>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st,
                      w->S, w->col_off, V0, V1, k, w->h_own_cols[(size_t)m0], (int)w->nt, nblk, (int *)nullptr, w->own_cols, w->own_pref, m0, m1,
@@ -2260,109 +2222,59 @@ static int launch_pair_list(ba_problem *p, DenseLDLT<T> *w, int q, const T *V0, 
   ProfScope ps(p, PC_LDL_UPDATE, st);
   hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S, w->col_off, V0, V1,
                      2 * q, 2 * q + 2, (int)w->nt, nblk, (int *)nullptr, (const int *)nullptr, (const int64_t *)nullptr, 0, 0, 1,
-                     (const int *)nullptr, (const T *)(w->Lb + (V0 - w->V)), (const T *)(w->Lb + (V1 - w->V)),
-                     (const int2 *)(w->upd_ij + w->h_upd_ptr[(size_t)q] + from));
+                     (const int *)nullptr, w->L_of(V0), w->L_of(V1), (const int2 *)(w->upd_ij + w->h_upd_ptr[(size_t)q] + from));
   return BA_OK;
 }
 
-// the panel chain of pair (k, k+1) on its owner (dense_ldl_factor's in-order chain, no right-hand side)
+// the panel chain of pair (k, k+1) on its owner, first diagonal tile included (no right-hand side)
 template <typename T>
 static int dist_chain(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, hipStream_t st) {
-  if (w->sparse) {  // over the pattern's row lists, as dense_ldl_factor_sparse
-    const TilePattern *pat = w->pat;
-    const int q = k / 2, l0 = pat->prow_ptr[(size_t)q], c1 = pat->prow_ptr[(size_t)q + 1] - l0, c2 = c1 > 0 ? c1 - 1 : 0;
-    launch_diag(p, w, k, st);
-    if (c1 > 0) {
-      {
-        ProfScope ps(p, PC_LDL_TRSM, st);
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, false>), dim3(4 * c1), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off,
-                           w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V0, k, (T *)nullptr, (T *)nullptr, w->prow + l0);
-      }
-      {
-        ProfScope ps(p, PC_LDL_SYRK, st);
-        hipLaunchKernelGGL(k_ldl_col_rs<T>, dim3(4 * c1), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, k, w->prow + l0);
-      }
-      launch_diag(p, w, k + 1, st);
-      if (c2 > 0) {
-        ProfScope ps(p, PC_LDL_TRSM, st);
-        hipLaunchKernelGGL((k_ldl_trsm_rs<T, false>), dim3(4 * c2), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off,
-                           w->Linv + (int64_t)(k + 1) * NB * NB, w->D + (int64_t)(k + 1) * NB, V1, k + 1, (T *)nullptr, (T *)nullptr,
-                           w->prow + l0 + 1);
-      }
-    }
-    BA_HIP_CHECK(hipGetLastError());
-    return BA_OK;
-  }
   launch_diag(p, w, k, st);
-  launch_trsm(p, w, k, V0, (T *)nullptr, st);
-  if (k + 1 < (int)w->nt) {
-    launch_col(p, w, k, V0, st);
-    launch_diag(p, w, k + 1, st);
-    launch_trsm(p, w, k + 1, V1, (T *)nullptr, st);
-  }
+  panel_chain(p, w, pair_rows(w, k / 2), V0, V1, (T *)nullptr, st);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
+// L = V D^-1 of tile column c over `count` tile rows; Lcol: where that column's L tiles live (see k_ldl_scale_panel)
+template <typename T>
+static void launch_scale_panel(DenseLDLT<T> *w, T *Lcol, const T *V, int c, const int *rows, int count, hipStream_t st) {
+  if (count > 0) hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(count), dim3(256), 0, st, Lcol, V, w->D + (int64_t)c * NB, c + 1, rows);
+}
+
 // pair (k, k+1) from its owner to everybody: V = L D of both panels, the two inverted diagonal tiles, the 256 pivots (one
-// grouped broadcast); the receivers rebuild L = V D^-1 in their copy of S
+// grouped broadcast); the receivers rebuild L = V D^-1
 template <typename T>
 static int dist_transfer(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, int owner, hipStream_t st) {
-  const int nt = (int)w->nt;
-  const bool two = k + 1 < nt;
-  if (w->sparse) {  // the pattern's tile rows only: one broadcast per run of consecutive rows (a band: one run per panel)
-    const TilePattern *pat = w->pat;
-    const int q = k / 2, l0 = pat->prow_ptr[(size_t)q], c1 = pat->prow_ptr[(size_t)q + 1] - l0, c2 = c1 > 0 ? c1 - 1 : 0;
-    BA_CHECK(comm_group_begin(p));
-    int rc = BA_OK;
-    auto bcast_rows = [&](T *V, int first, int cnt) {
-      for (int a = 0; a < cnt && rc == BA_OK;) {
-        int b = a + 1;
-        while (b < cnt && pat->prow[(size_t)(first + b)] == pat->prow[(size_t)(first + b - 1)] + 1) b++;
-        rc = comm_bcast(p, V + (int64_t)pat->prow[(size_t)(first + a)] * NB * NB, (int64_t)(b - a) * NB * NB * sizeof(T), owner, st);
-        a = b;
-      }
-    };
-    bcast_rows(V0, l0, c1);
-    if (two) bcast_rows(V1, l0 + 1, c2);
-    if (rc == BA_OK) rc = comm_bcast(p, w->Linv + (int64_t)k * NB * NB, (int64_t)(two ? 2 : 1) * NB * NB * sizeof(T), owner, st);
-    if (rc == BA_OK) rc = comm_bcast(p, w->D + (int64_t)k * NB, (int64_t)(two ? 2 : 1) * NB * sizeof(T), owner, st);
-    BA_CHECK(comm_group_end(p));
-    BA_CHECK(rc);
-    T *L0 = w->Lb + (V0 - w->V), *L1 = w->Lb + (V1 - w->V);
-    if (c1 > 0) hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(c1), dim3(256), 0, st, L0, V0, w->D + (int64_t)k * NB, 0, w->prow + l0);
-    if (two && c2 > 0)
-      hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(c2), dim3(256), 0, st, L1, V1, w->D + (int64_t)(k + 1) * NB, 0, w->prow + l0 + 1);
-    BA_HIP_CHECK(hipGetLastError());
-    return BA_OK;
-  }
-  const int rows0 = nt - k - 1, rows1 = nt - k - 2;  // tile rows below the diagonal tile of column k / k + 1
+  const bool two = k + 1 < (int)w->nt;
+  const PairRows r = pair_rows(w, k / 2);
   BA_CHECK(comm_group_begin(p));
   int rc = BA_OK;
-  if (rows0 > 0) rc = comm_bcast(p, V0 + (int64_t)(k + 1) * NB * NB, (int64_t)rows0 * NB * NB * sizeof(T), owner, st);
-  if (rc == BA_OK && two && rows1 > 0)
-    rc = comm_bcast(p, V1 + (int64_t)(k + 2) * NB * NB, (int64_t)rows1 * NB * NB * sizeof(T), owner, st);
+  // rows [first, first + cnt) of {k+1} + U_q: one broadcast per run of consecutive tile rows (no pattern, or a band: one run
+  // per panel)
+  auto bcast_rows = [&](T *V, int first, int cnt) {
+    for (int a = first; a < first + cnt && rc == BA_OK;) {
+      int b = a + 1;
+      while (b < first + cnt && r.row(b) == r.row(b - 1) + 1) b++;
+      rc = comm_bcast(p, V + (int64_t)r.row(a) * NB * NB, (int64_t)(b - a) * NB * NB * sizeof(T), owner, st);
+      a = b;
+    }
+  };
+  bcast_rows(V0, 0, r.c1);
+  if (two) bcast_rows(V1, 1, r.c2);
   if (rc == BA_OK) rc = comm_bcast(p, w->Linv + (int64_t)k * NB * NB, (int64_t)(two ? 2 : 1) * NB * NB * sizeof(T), owner, st);
   if (rc == BA_OK) rc = comm_bcast(p, w->D + (int64_t)k * NB, (int64_t)(two ? 2 : 1) * NB * sizeof(T), owner, st);
   BA_CHECK(comm_group_end(p));
   BA_CHECK(rc);
   if (w->own_only) {
-    // every rank (the owner too: one source for the update's operand) rebuilds L = V D^-1 of both panels in the panel
-    // buffer beside V; nothing of another rank's columns enters S
-    T *L0 = w->Lb + (V0 - w->V), *L1 = w->Lb + (V1 - w->V);
-    if (rows0 > 0) hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(rows0), dim3(256), 0, st, L0, V0, w->D + (int64_t)k * NB, k + 1);
-    if (two && rows1 > 0)
-      hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(rows1), dim3(256), 0, st, L1, V1, w->D + (int64_t)(k + 1) * NB, k + 2);
-    BA_HIP_CHECK(hipGetLastError());
-  } else if (owner != w->rank) {
-    if (rows0 > 0)
-      hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(rows0), dim3(256), 0, st, w->S + (w->hco()[k] - k) * NB * NB, V0,
-                         w->D + (int64_t)k * NB, k + 1);
-    if (two && rows1 > 0)
-      hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(rows1), dim3(256), 0, st, w->S + (w->hco()[k + 1] - (k + 1)) * NB * NB, V1,
-                         w->D + (int64_t)(k + 1) * NB, k + 2);
-    BA_HIP_CHECK(hipGetLastError());
+    // every rank (the owner too: one source for the update's operand) rebuilds L of both panels in the panel buffer beside
+    // V; nothing of another rank's columns enters S
+    launch_scale_panel(w, w->L_of(V0), V0, k, r.rows1, r.c1, st);
+    if (two) launch_scale_panel(w, w->L_of(V1), V1, k + 1, r.rows2, r.c2, st);
+  } else if (owner != w->rank) {  // replicated S: into this rank's copy of the two tile columns (the owner's holds L already)
+    launch_scale_panel(w, w->S + (w->hco()[k] - k) * NB * NB, V0, k, r.rows1, r.c1, st);
+    if (two) launch_scale_panel(w, w->S + (w->hco()[k + 1] - (k + 1)) * NB * NB, V1, k + 1, r.rows2, r.c2, st);
   }
+  BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
@@ -2372,24 +2284,12 @@ static int dist_transfer(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, in
 template <typename T>
 static int dist_forward_pair(DenseLDLT<T> *w, int k, T *V0, T *V1, T *d_b, hipStream_t st) {
   if (!d_b) return BA_OK;
-  const int nt = (int)w->nt;
-  T *y = w->D + (int64_t)nt * NB;
-  if (w->sparse) {
-    const TilePattern *pat = w->pat;
-    const int q = k / 2, l0 = pat->prow_ptr[(size_t)q], c1 = pat->prow_ptr[(size_t)q + 1] - l0, c2 = c1 > 0 ? c1 - 1 : 0;
-    hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + c1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, (const int *)(w->prow + l0),
-                       (const T *)(w->Lb + (V0 - w->V)));
-    if (k + 1 < nt)
-      hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + c2), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1,
-                         (const int *)(w->prow + l0 + 1), (const T *)(w->Lb + (V1 - w->V)));
-    BA_HIP_CHECK(hipGetLastError());
-    return BA_OK;
-  }
-  hipLaunchKernelGGL(k_fwd_step<T>, dim3(nt - k), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, (const int *)nullptr,
-                     (const T *)(w->Lb + (V0 - w->V)));
-  if (k + 1 < nt)
-    hipLaunchKernelGGL(k_fwd_step<T>, dim3(nt - k - 1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, (const int *)nullptr,
-                       (const T *)(w->Lb + (V1 - w->V)));
+  T *y = w->D + w->nt * NB;
+  const PairRows r = pair_rows(w, k / 2);
+  hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, r.rows1, (const T *)w->L_of(V0));
+  if (k + 1 < (int)w->nt)
+    hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c2), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, r.rows2,
+                       (const T *)w->L_of(V1));
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
@@ -2408,8 +2308,8 @@ static int dist_forward_pair(DenseLDLT<T> *w, int k, T *V0, T *V1, T *d_b, hipSt
 // transfer stream while update q runs.  Chain and broadcast of pair q+1 thus hide behind update q wherever that update is
 // the longer of the two (Final-13682 on 8 ranks: 2.4 ms of update per pair and rank against ~0.7 ms of chain and ~2 ms of
 // broadcast).  The arithmetic -- which tile receives which products in which order -- is that of the alternating
-// schedule: the results are bit-identical (tests/test_distributed.py).  Buffers: pair q's panels live in Vs[q & 1];
-// transfer q+1 may overwrite Vs[(q+1) & 1] only when update q-1 is through with it (ev_upd), update q+1 starts when
+// schedule: the results are bit-identical (tests/test_distributed.py).  Buffers: pair q's panels live in slot q & 1;
+// transfer q+1 may overwrite slot (q+1) & 1 only when update q-1 is through with it (ev_upd), update q+1 starts when
 // transfer q+1 has landed (ev_recv).
 template <typename T>
 int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
@@ -2418,8 +2318,6 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
     return BA_ERR_ARG;
   }
   const int nt = (int)w->nt, P = w->world, me = w->rank;
-  const int64_t panel = (int64_t)nt * NB * NB;
-  T *Vs[2][2] = {{w->V, w->V + panel}, {w->V + 2 * panel, w->V + 3 * panel}};
   BA_HIP_CHECK(hipMemsetAsync(w->flag, 0, sizeof(int), st));
   w->hoisting = false;
   const bool la_off = env_off("BA_DIST_LOOKAHEAD");  // read per call: a test flips it between two factorisations of one process
@@ -2435,7 +2333,7 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
   // are this rank's), 2 = what remains after part 1
   auto update_mine = [&](int q, const T *V0, const T *V1, int part, bool next_mine) -> int {
     const int k = 2 * q;
-    if (w->sparse) {
+    if (w->upd_ij) {  // this rank's tiles of the update are listed (a pattern)
       const int n = w->h_upd_ptr[(size_t)q + 1] - w->h_upd_ptr[(size_t)q], lead = next_mine ? w->h_upd_lead[(size_t)q] : 0;
       if (part == 1) return launch_pair_list(p, w, q, V0, V1, st, 0, lead);
       return launch_pair_list(p, w, q, V0, V1, st, part == 2 ? lead : 0, n);
@@ -2447,7 +2345,7 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
   };
   if (la_off || p->prof_on) {  // (per-kernel profiling times one launch at a time: nothing could overlap)
     for (int k = 0, q = 0; k < nt; k += 2, q++) {
-      T *V0 = Vs[q & 1][0], *V1 = Vs[q & 1][1];
+      T *V0 = w->vpanel(q & 1, 0), *V1 = w->vpanel(q & 1, 1);
       const int owner = q % P;
       if (owner == me) BA_CHECK(dist_chain(p, w, k, V0, V1, st));
       BA_CHECK(dist_transfer(p, w, k, V0, V1, owner, st));
@@ -2460,15 +2358,15 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
     BA_HIP_CHECK(hipEventRecord(w->ev_dtop, st));  // fork: behind the reduce of S
     BA_HIP_CHECK(hipStreamWaitEvent(cs, w->ev_dtop, 0));
     if (0 % P == me) {
-      BA_CHECK(dist_chain(p, w, 0, Vs[0][0], Vs[0][1], st));
+      BA_CHECK(dist_chain(p, w, 0, w->vpanel(0, 0), w->vpanel(0, 1), st));
       BA_HIP_CHECK(hipEventRecord(w->ev_dchain, st));
       BA_HIP_CHECK(hipStreamWaitEvent(cs, w->ev_dchain, 0));
     }
-    BA_CHECK(dist_transfer(p, w, 0, Vs[0][0], Vs[0][1], 0, cs));
+    BA_CHECK(dist_transfer(p, w, 0, w->vpanel(0, 0), w->vpanel(0, 1), 0, cs));
     BA_HIP_CHECK(hipEventRecord(w->ev_recv[0], cs));
     for (int k = 0, q = 0; k < nt; k += 2, q++) {
-      T *V0 = Vs[q & 1][0], *V1 = Vs[q & 1][1];
-      T *N0 = Vs[(q + 1) & 1][0], *N1 = Vs[(q + 1) & 1][1];
+      T *V0 = w->vpanel(q & 1, 0), *V1 = w->vpanel(q & 1, 1);
+      T *N0 = w->vpanel((q + 1) & 1, 0), *N1 = w->vpanel((q + 1) & 1, 1);
       BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_recv[q & 1], 0));  // pair q's panels are here (join of the transfer stream)
       BA_CHECK(dist_forward_pair(w, k, V0, V1, d_b, st));  // (ahead of update q, whose event frees this buffer for transfer q+2)
       if (k + 2 >= nt) break;
@@ -2480,7 +2378,7 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
       }
       BA_CHECK(update_mine(q, V0, V1, 2, next_mine));
       BA_HIP_CHECK(hipEventRecord(w->ev_upd[q & 1], st));
-      if (q >= 1) BA_HIP_CHECK(hipStreamWaitEvent(cs, w->ev_upd[(q + 1) & 1], 0));  // update q-1 has read Vs[(q+1)&1]
+      if (q >= 1) BA_HIP_CHECK(hipStreamWaitEvent(cs, w->ev_upd[(q + 1) & 1], 0));  // update q-1 has read slot (q+1)&1
       if (next_mine) BA_HIP_CHECK(hipStreamWaitEvent(cs, w->ev_dchain, 0));
       BA_CHECK(dist_transfer(p, w, k + 2, N0, N1, (q + 1) % P, cs));
       BA_HIP_CHECK(hipEventRecord(w->ev_recv[(q + 1) & 1], cs));
@@ -2575,19 +2473,11 @@ static int dense_ldl_bwd_dist(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_
   for (int k = last; k >= 0; k -= 2) {
     const int owner = (k / 2) % P;
     const bool two = k + 1 < nt;
-    if (owner == me && w->sparse) {  // the pair's pattern rows only
-      const TilePattern *pat = w->pat;
-      const int q = k / 2, l0 = pat->prow_ptr[(size_t)q], c1 = pat->prow_ptr[(size_t)q + 1] - l0, c2 = c1 > 0 ? c1 - 1 : 0;
-      if (c2 > 0)
-        hipLaunchKernelGGL(k_bwd_col_part<T>, dim3(2 * c2), dim3(256), 0, st, w->S, w->col_off, d_b, w->bpart, k, nt, (const int *)(w->prow + l0 + 1));
-      hipLaunchKernelGGL(k_bwd_col_final<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, w->bpart, d_b, k, nt,
-                         (const int *)(w->prow + l0 + 1), c2);
-      BA_HIP_CHECK(hipGetLastError());
-    } else if (owner == me) {
-      const int below = nt - k - 2;  // tile rows below the pair
-      if (below > 0)
-        hipLaunchKernelGGL(k_bwd_col_part<T>, dim3(2 * below), dim3(256), 0, st, w->S, w->col_off, d_b, w->bpart, k, nt);
-      hipLaunchKernelGGL(k_bwd_col_final<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, w->bpart, d_b, k, nt);
+    if (owner == me) {  // over the tile rows below the pair: U_q
+      const PairRows r = pair_rows(w, k / 2);
+      if (r.c2 > 0) hipLaunchKernelGGL(k_bwd_col_part<T>, dim3(2 * r.c2), dim3(256), 0, st, w->S, w->col_off, d_b, w->bpart, k, nt, r.rows2);
+      hipLaunchKernelGGL(k_bwd_col_final<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, w->bpart, d_b, k, nt, r.rows2,
+                         r.c2);
       BA_HIP_CHECK(hipGetLastError());
     }
     BA_CHECK(comm_bcast(p, d_b + (int64_t)k * NB, (int64_t)(two ? 2 : 1) * NB * sizeof(T), owner, st));

@@ -212,7 +212,8 @@ template <typename T>
 struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*ncams padded to nt*NB
   int64_t n = 0, nt = 0;
   DevBuf<T> S;             // packed lower tiles
-  DevBuf<T> V;             // 4 x nt tiles: V_i = L_ik * D_k of two panel pairs (double-buffered for the look-ahead)
+  DevBuf<T> V;             // 8 x nt tiles: V_i = L_ik * D_k, (two runs) x (two slots, alternating for the look-ahead) x two panels
+  T *vpanel(int slot, int j, int run = 0) { return V + (int64_t)(4 * run + 2 * slot + j) * nt * NB * NB; }  // panel j of a pair
   DevBuf<T> Linv;          // nt tiles: inverse of each unit-lower diagonal tile
   DevBuf<T> D;             // nt*NB pivots (+ nt*NB scratch)
   int64_t *col_off = nullptr;           // device: tile column offsets (see tix)
@@ -244,6 +245,7 @@ struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*nc
   int64_t s_tiles = 0;
   std::vector<int64_t> h_glob_off;
   DevBuf<T> Lb, bpart;
+  T *L_of(const T *v) { return Lb + (v - V); }  // the L buffer that travels with panel buffer v of V
   // block-sparse S (one GPU): the pattern's row / column lists on the device; null pattern = dense
   bool sparse = false;
   const TilePattern *pat = nullptr;

@@ -1036,19 +1036,24 @@ static int trial_point(ba_problem *p, LMWork *w, hipStream_t st, bool xf32 = fal
   return launch_sumsq_multi(p, &jobs, w->partial_multi, st);
 }
 
-static int check_pivot(ba_problem *p, LMWork *w, hipStream_t st) {
-  int h = 0;
-  BA_HIP_CHECK(hipMemcpyAsync(&h, w->last_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
+// a factorisation's pivot flag (DenseLDLT::flag) as an error; zero_pivot_msg: what an exactly zero pivot means to this caller
+static int pivot_flag_error(int h, const char *zero_pivot_msg = "reduced camera system: exactly zero pivot (SQDException in the reference)") {
   if (h == 2) {
     ba_set_error("dense factorisation: a hoisted diagonal tile never became ready (internal scheduling error)");
     return BA_ERR_HIP;
   }
   if (h) {
-    ba_set_error("reduced camera system: exactly zero pivot (SQDException in the reference)");
+    ba_set_error("%s", zero_pivot_msg);
     return BA_ERR_ZERO_PIVOT;
   }
   return BA_OK;
+}
+
+static int check_pivot(ba_problem *p, LMWork *w, hipStream_t st) {
+  int h = 0;
+  BA_HIP_CHECK(hipMemcpyAsync(&h, w->last_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return pivot_flag_error(h);
 }
 
 // ---- recorded launch sequences ------------------------------------------------------------------------------------------
@@ -1365,14 +1370,7 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   };
   BA_CHECK(assemble_factor());
   if (hoist_gave_up(w)) BA_CHECK(assemble_factor());  // as lm_step_impl: the in-order schedule, the factorisation again
-  if (*w->h_flag == 2) {
-    ba_set_error("dense factorisation: a hoisted diagonal tile never became ready (internal scheduling error)");
-    return BA_ERR_HIP;
-  }
-  if (*w->h_flag) {
-    ba_set_error("ba_covariance: exactly zero pivot in the reduced camera system (fix a gauge, or pass lambda > 0)");
-    return BA_ERR_ZERO_PIVOT;
-  }
+  BA_CHECK(pivot_flag_error(*w->h_flag, "ba_covariance: exactly zero pivot in the reduced camera system (fix a gauge, or pass lambda > 0)"));
   double h_ratio = 0;
   BA_CHECK(launch_cov_sdiag(p, &w->ldl, w->n, sdiag, ratio, true, st));
   BA_HIP_CHECK(hipMemcpyAsync(&h_ratio, ratio, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1611,16 +1609,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     else if ((rc = trial_step(p, w, lambda.v, o->normalize, facto_f32, xf32, st)) != BA_OK) break;  // lm.jl:154-254
     stats->n_factor++;
     stats->n_residual++;
-    if (*w->h_flag == 2) {
-      ba_set_error("dense factorisation: a hoisted diagonal tile never became ready (internal scheduling error)");
-      rc = BA_ERR_HIP;
-      break;
-    }
-    if (*w->h_flag) {
-      ba_set_error("reduced camera system: exactly zero pivot (SQDException in the reference)");
-      rc = BA_ERR_ZERO_PIVOT;
-      break;
-    }
+    if ((rc = pivot_flag_error(*w->h_flag)) != BA_OK) break;
     dr2 = half_of(h_sh[SH_MODEL]);  // 1/2 |delta_r|^2   (lm.jl:229)
     const TS pred_r = ts::f64(0.5 * h_sh[SH_RTSQ] - 0.5 * h_sh[SH_MODEL]);  // (robust loss only)
     if (robust) dr2 = ts::sub(obj, pred_r);
