@@ -1850,18 +1850,6 @@ static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0,
   return BA_OK;
 }
 
-// the pivot flag read back for a caller that asks for it (0: fine; see DenseLDLT::flag); synchronises st
-template <typename T>
-static int read_pivot_flag(DenseLDLT<T> *w, hipStream_t st, int *zero_pivot) {
-  BA_HIP_CHECK(hipGetLastError());
-  if (!zero_pivot) return BA_OK;
-  int h = 0;
-  BA_HIP_CHECK(hipMemcpyAsync(&h, w->flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  *zero_pivot = h;
-  return BA_OK;
-}
-
 // Two panels per pass over the trailing matrix:
 //   diag(k) trsm(k) | column update of tile column k+1 | diag(k+1) trsm(k+1) | pair update of everything right of k+1.
 //
@@ -1874,18 +1862,12 @@ static int read_pivot_flag(DenseLDLT<T> *w, hipStream_t st, int *zero_pivot) {
 // priority stream, bulk on a CU-masked stream -- measured 40-51 ms; masking only 1 / 2 / 4 of the 256 CUs off the bulk
 // stream for a hoisted diagonal kernel 42 / 46 / 59 ms: CU-masked streams are slow here, and that code is gone.)
 template <typename T>
-int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b);
+int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b);
 
 template <typename T>
-int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b) {
-  if (w->sparse && !p->comm.active()) return dense_ldl_factor_sparse(p, w, st, zero_pivot, d_b);
+int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
+  if (w->sparse && !p->comm.active()) return dense_ldl_factor_sparse(p, w, st, d_b);
   const int nt = (int)w->nt;
-  constexpr int HOIST_MIN_TILES = 32;  // below ~2 rounds of tiles the update is shorter than wait + factor
-  // The waiting workgroup keeps one CU of one XCD from the update, whose blocks the hardware deals round-robin to the
-  // XCDs: that XCD runs 32/31 longer and the launch ends with it -- 3 % of the update time, which grows as nt^3 while
-  // the hoisted 59 us per pair grow as nt.  Measured: n = 16002 (nt 126) 37.1 -> 35.6 ms, n = 40000 (nt 313) 411 -> 418 ms;
-  // the model's break-even is nt ~ 250.
-  constexpr int HOIST_MAX_TILES = 224;
   static const bool hoist_off = env_off("BA_LDL_HOIST");
   w->hoisting = !p->prof_on && !hoist_off && !w->hoist_disabled && !p->comm.active() && nt >= HOIST_MIN_TILES + 2 && nt <= HOIST_MAX_TILES;
   // the pivot flag: hoisted kernels read it (an earlier tile gave up) before tile 0 is factored -- cleared ahead of the
@@ -1931,7 +1913,8 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_p
     else
       launch_diag(p, w, k + 2, st);
   }
-  return read_pivot_flag(w, st, zero_pivot);
+  BA_HIP_CHECK(hipGetLastError());
+  return BA_OK;
 }
 
 // ---- block-sparse reduced camera system ---------------------------------------------------------------------------------
@@ -2069,7 +2052,7 @@ static UpdateSplit update_split(const PairRows &r) {
 }
 
 template <typename T>
-int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b) {
+int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
   const int nt = (int)w->nt;
   const TilePattern *pat = w->pat;
   const int64_t panel = (int64_t)nt * NB * NB;
@@ -2192,7 +2175,8 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int 
   }
   BA_CHECK(join_rest(0));
   BA_CHECK(join_rest(1));
-  return read_pivot_flag(w, st, zero_pivot);
+  BA_HIP_CHECK(hipGetLastError());
+  return BA_OK;
 }
 
 // pair update (panels k, k+1) of the owned tile columns own_cols[m0 .. m1)
@@ -2588,7 +2572,7 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   int rc = BA_OK, zp = 0;
   for (int attempt = 0; attempt < 2; attempt++) {  // (the forward substitution rides along with the factorisation)
     BA_HIP_CHECK(hipEventRecord(e0, st));
-    rc = dense_ldl_factor<T>(&tmp, &w, st, nullptr, d_b);
+    rc = dense_ldl_factor<T>(&tmp, &w, st, d_b);
     BA_HIP_CHECK(hipEventRecord(e1, st));
     if (rc == BA_OK) rc = dense_ldl_solve<T>(&tmp, &w, d_b, st, true);
     BA_HIP_CHECK(hipMemcpy(&zp, w.flag, sizeof(int), hipMemcpyDeviceToHost));
@@ -2626,8 +2610,8 @@ template int dense_ldl_alloc<double>(DenseLDLT<double> *, int64_t, int, int, boo
 template int dense_ldl_alloc<float>(DenseLDLT<float> *, int64_t, int, int, bool, bool);
 template int dense_ldl_alloc_S<double>(DenseLDLT<double> *);
 template int dense_ldl_alloc_S<float>(DenseLDLT<float> *);
-template int dense_ldl_factor<double>(ba_problem *, DenseLDLT<double> *, hipStream_t, int *, double *);
-template int dense_ldl_factor<float>(ba_problem *, DenseLDLT<float> *, hipStream_t, int *, float *);
+template int dense_ldl_factor<double>(ba_problem *, DenseLDLT<double> *, hipStream_t, double *);
+template int dense_ldl_factor<float>(ba_problem *, DenseLDLT<float> *, hipStream_t, float *);
 template int dense_ldl_use_pattern<double>(DenseLDLT<double> *, const TilePattern *);
 template int dense_ldl_use_pattern<float>(DenseLDLT<float> *, const TilePattern *);
 template int dense_ldl_factor_dist<double>(ba_problem *, DenseLDLT<double> *, hipStream_t, double *);

@@ -260,6 +260,13 @@ struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*nc
   HipEvent ev_dtop, ev_dchain;  // distributed factorisation: fork behind the reduce of S, end of the owner's panel chain
 };
 typedef DenseLDLT<double> DenseLDL;
+// the hoisted-diagonal schedule of dense_ldl_factor runs for HOIST_MIN_TILES + 2 <= nt <= HOIST_MAX_TILES
+constexpr int HOIST_MIN_TILES = 32;  // below ~2 rounds of tiles the update is shorter than wait + factor
+// The waiting workgroup keeps one CU of one XCD from the update, whose blocks the hardware deals round-robin to the
+// XCDs: that XCD runs 32/31 longer and the launch ends with it -- 3 % of the update time, which grows as nt^3 while
+// the hoisted 59 us per pair grow as nt.  Measured: n = 16002 (nt 126) 37.1 -> 35.6 ms, n = 40000 (nt 313) 411 -> 418 ms;
+// the model's break-even is nt ~ 250.
+constexpr int HOIST_MAX_TILES = 224;
 
 // transport of the cross-rank sums (ba_comm.hip): RCCL called directly, or a caller-supplied hook
 struct BaComm {
@@ -358,11 +365,11 @@ int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, int world = 1, int rank
 template <typename T>
 int dense_ldl_alloc_S(DenseLDLT<T> *w);
 int64_t dense_ldl_tiles_doubles(int64_t n_unpadded);  // number of ELEMENTS of the packed lower tiles
-// factor S in place (L below the diagonal tiles' diagonal, D separately); *zero_pivot set on exact zero pivot.
+// factor S in place (L below the diagonal tiles' diagonal, D separately); an exactly zero pivot sets DenseLDLT::flag.
 // d_b != null: the forward substitution L y = b of that right-hand side (length nt*NB, clobbered) is fused into the
 // panel solves; pass forward_done = true to dense_ldl_solve afterwards.
 template <typename T>
-int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, int *zero_pivot, T *d_b);
+int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b);
 // the same factorisation with the tile column pairs distributed over the ranks of p->comm (owner of pair q: q % world):
 // on entry rank r holds the (summed) tile columns it owns, on exit every rank holds the complete factor (L, Linv, D).
 // No fused forward substitution: call dense_ldl_solve(..., forward_done = false).

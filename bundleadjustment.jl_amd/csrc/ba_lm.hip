@@ -33,6 +33,10 @@ double wall() {
 enum { SH_RSQ = 0, SH_GP, SH_X_P, SH_RTSQ, SH_RSQ_TRIAL, SH_MODEL, SH_DELTA_P, SH_COUNT = 8 };
 constexpr int SH_LIN_COUNT = 3, SH_TRIAL_FIRST = 4, SH_TRIAL_COUNT = 3;
 enum { RP_DELTA_C = 0, RP_X_C, RP_GC, RP_COUNT = 8 };
+// (an all-reduce takes the slots of one refresh as one run: the linearisation's from slot 0, SH_RTSQ right behind them)
+static_assert(SH_RSQ == 0 && SH_X_P == SH_LIN_COUNT - 1 && SH_RTSQ == SH_LIN_COUNT, "linearisation slots: one run from slot 0");
+static_assert(SH_RSQ_TRIAL == SH_TRIAL_FIRST && SH_DELTA_P == SH_TRIAL_FIRST + SH_TRIAL_COUNT - 1, "trial slots: one run");
+static_assert(SH_RTSQ < SH_TRIAL_FIRST && SH_TRIAL_FIRST + SH_TRIAL_COUNT <= SH_COUNT, "the two runs do not overlap");
 
 // Build the (camera_a >= camera_b)-sorted list of observation pairs sharing a point.  "Camera" here is the BLOCK ROW of S the
 // camera sits at: pos[c] under a fill-reducing camera ordering (empty: c itself).
@@ -155,25 +159,40 @@ int build_tasks(ba_problem *p, SchurTasks *T, const std::vector<int> &pos) {
   return BA_OK;
 }
 
-// one device buffer [rhs(npad) | gc(npad) | hdiag(npad) | SH_COUNT scalars]: gc, hdiag and the first scalars are one
-// all-reduce.  (The tiles of S are their own allocation, made when the first direct solve needs them: ensure_dense.)
-int64_t reduce_layout(ba_problem *p, int64_t *off_rhs, int64_t *off_gc, int64_t *off_scal) {
-  const int64_t n = 9 * p->ncams;
-  const int64_t npad = ((n + NB - 1) / NB > 0 ? (n + NB - 1) / NB : 1) * NB;
-  if (off_rhs) *off_rhs = 0;
-  if (off_gc) *off_gc = npad;
-  if (off_scal) *off_scal = 3 * npad;
-  return 3 * npad + SH_COUNT;
-}
+}  // namespace
 
-struct LMState {
-  DevBuf<double> red;  // [rhs | gc | hdiag | sharded scalars]
-  int64_t off_rhs = 0, off_gc = 0, off_scal = 0, red_doubles = 0;
-  DevBuf<double> scal_rep;
-  PinnedBuf<double> h_sh, h_rp;
+// How the linear step of a solve is obtained.  Each entry point (lm_step_impl, lm_solve_impl, ba_covariance) fills it once,
+// whole, before its first launch; everything below reads it.
+struct StepMode {
+  int normalize = 0;       // column scaling of the camera system: 0 (:None), 1 (:J), 2 (:A)
+  bool facto_f32 = false;  // the reduced camera system is factored in Float32 (never under pcg)
+  bool xf32 = false;       // eltype(x) = Float32
+  bool f16 = false;        // facto_type = Float16
+  bool pcg = false;        // facto = PCG
+  double pcg_tol = 1e-8;
+  int pcg_maxit = 0;  // 0: default
 };
 
-}  // namespace
+// What a recorded sequence depends on besides the handle's buffers: the solve mode; the loss kind and scale, launch
+// arguments of the robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed
+// parameters, which decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables,
+// launch arguments too
+struct RecordedFor {
+  int bits = -1;  // normalize + 4 * facto_f32 + 8 * xf32 + 16 * loss + 128 / 256 * mask tables (-1: nothing recorded yet)
+  double loss_scale = 1.0;
+  const void *d_fix_cam = nullptr, *d_fix_pnt = nullptr;
+  bool operator==(const RecordedFor &o) const {
+    return bits == o.bits && loss_scale == o.loss_scale && d_fix_cam == o.d_fix_cam && d_fix_pnt == o.d_fix_pnt;
+  }
+};
+// hipGraph replay of the two launch sequences of the LM loop (launch-bound on small problems: LadyBug-49 issues ~60
+// kernels of a few microseconds per iteration).  x/x_trial and r/r_trial swap on an accepted step, so each sequence
+// is recorded once per parity of the swap (step, refresh); the damping reaches the recorded kernels through d_lambda.
+struct RecordedSequences {
+  RecordedFor made_for;
+  bool off = false;  // a recording failed on this handle: plain launches from then on
+  HipGraphExec step[2], refresh[2];
+};
 
 // The LM workspace of a handle (ba_problem::lm): made by lm_ensure, released by lm_free.  The recorded launch sequences are
 // declared last, so they are destroyed before the buffers they reference.
@@ -185,9 +204,12 @@ struct LMWork {
   DevBuf<double> Yobs;                   // 6/obs: U^-1 A_b' of the current damping
   bool model_done = false;               // the step's model value was formed by the back-substitution pass
   DevBuf<double> Hcc;
-  // views into s.red: gc (9*ncams), hdiag (npad: diag of the camera block of J'J summed over all ranks, for the column
-  // scalings), rhs (npad), scal (the SH_COUNT sharded scalars)
-  double *gc = nullptr, *hdiag = nullptr, *rhs = nullptr, *scal = nullptr;
+  // the reduce buffer and its views (lm_ensure): rhs (npad), gc (9*ncams), hdiag (npad: diag of the camera block of J'J summed over
+  // all ranks, for the column scalings), scal (the SH_COUNT sharded scalars); the replicated scalars; the pinned mirrors of both
+  DevBuf<double> red;
+  double *rhs = nullptr, *gc = nullptr, *hdiag = nullptr, *scal = nullptr;
+  DevBuf<double> scal_rep;
+  PinnedBuf<double> h_sh, h_rp;
   DevBuf<double> colscale;               // nvar (normalize != None)
   // facto_type = Float16: |J_j|^2, column norms, damping vector (nvar each), quantised J (24/obs) and r; allocated on first use
   DevBuf<double> jn2, dcol, damp, Jq, rq;
@@ -196,7 +218,6 @@ struct LMWork {
   DevBuf<int> cam_pnt;                   // nobs: the point of every observation in camera order (pnt0[cam_obs[q]])
   SchurTasks tasks;
   DenseLDL ldl;
-  LMState s;
   std::vector<SchurChunk> chunks;  // per-rank ownership of S: chunks of tile columns, assembled and reduced one by one
   DevBuf<double> stage;            // the chunk being assembled for another owner (stage_tiles tiles)
   DevBuf<float> stage32;           // its Float32 copy when the reduce travels in Float32
@@ -216,41 +237,32 @@ struct LMWork {
   // facto_type = Float32 (src/lm.jl:170-173): Float32 copy of the reduced camera system, allocated on first use
   DenseLDLT<float> ldl32;
   DevBuf<float> rhs32;
-  bool have32 = false, last_f32 = false;
-  // facto_type = Float16 (src/lm.jl:165-169): set per solve; J_lin / r_lin / cr0: what the model value of the current step is
+  StepMode mode;
+  // the pivot flag of the current mode's factorisation (under pcg: of its block-Jacobi preconditioner, pcg_solve)
+  int *pivot_flag() const { return mode.facto_f32 ? ldl32.flag : ldl.flag; }
+  // facto_type = Float16 (src/lm.jl:165-169): J_lin / r_lin / cr0: what the model value of the current step is
   // evaluated on (the Float16-rounded scaled copies in that mode, J and r otherwise), see linear_step
-  bool f16 = false;
-  // what the model value of a step is evaluated on: the Float16-rounded scaled copies in that branch, J and r otherwise
   // (looked up at call time: w->r / w->r_trial swap on accepted steps, a recorded graph must not pin them)
-  const double *J_lin() const { return f16 ? Jq : J; }
-  const double *r_lin() const { return f16 ? rq : r; }
-  double cr0() const { return f16 ? 1.0 / (0.1 * 6.55e4) : 1.0; }
+  const double *J_lin() const { return mode.f16 ? Jq : J; }
+  const double *r_lin() const { return mode.f16 ? rq : r; }
+  double cr0() const { return mode.f16 ? 1.0 / (0.1 * 6.55e4) : 1.0; }
   // eltype(x) = Float32 runs (BALNLPModel(file, Float32), src/BALNLPModels.jl:91): x, r and J are produced by the Float32
   // kernels and widened; every iterate is rounded to Float32.  Buffers allocated on first use.
   DevBuf<float> xf, rf, Jf;
-  // hipGraph replay of the two launch sequences of the LM loop (launch-bound on small problems: LadyBug-49 issues ~60
-  // kernels of a few microseconds per iteration).  x/x_trial and r/r_trial swap on an accepted step, so each sequence
-  // is recorded once per parity of the swap (g_step, g_refresh); the damping reaches the recorded kernels through d_lambda.
+  // the damping of the recorded sequences (RecordedSequences)
   DevBuf<double> d_lambda;   // device scalar
   PinnedBuf<double> h_lambda;  // its pinned staging
   PinnedBuf<int> h_flag;     // pinned copy of the pivot flag
-  int g_key = -1;  // graph_key(): normalize + 4 * facto_f32 + 8 * x_f32 + 16 * loss + 128 / 256 * mask tables the graphs were recorded for
-  double g_scale = 1.0;  // ... and the loss scale (the robust kernels take loss and scale as launch arguments)
-  const void *g_fix_cam = nullptr, *g_fix_pnt = nullptr;  // ... and the device tables of the mask k_fix_mask was recorded with
   int parity = 0;
-  bool g_off = false;  // a recording failed on this handle: plain launches from then on
   // facto = PCG: block-Jacobi preconditioned conjugate gradients on the reduced camera system, S never formed (pcg_solve).
   // Buffers allocated on first use: iterate, residual, preconditioned residual, direction, S * direction, W U^-1 W' part
   // (n each), point-side intermediate and a zero vector (3 npnts), the 9 x 9 diagonal blocks (45 per camera).
-  bool pcg = false;
-  double pcg_tol = 1e-8;
-  int pcg_maxit = 0;  // 0: default
   int64_t n_cg = 0;   // CG iterations of the current solve
   DevBuf<double> cgx, cgr, cgz, cgp, cgq, cgt;
   DevBuf<double> cgh, zero3, blk45, cg_scal;
   PinnedBuf<double> h_cg;
   DevBuf<double> rob_partial;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
-  HipGraphExec g_step[2], g_refresh[2];
+  RecordedSequences rec;
 };
 
 namespace {
@@ -287,12 +299,11 @@ static int ensure_xf32(ba_problem *p, LMWork *w) {
 }
 
 static int ensure_f32(LMWork *w) {
-  if (w->have32) return BA_OK;
+  if (w->rhs32) return BA_OK;  // (the last allocation: a failed call is redone whole)
   BA_CHECK(dense_ldl_alloc<float>(&w->ldl32, w->n, w->ldl.world, w->ldl.rank, false, w->ldl.own_only));
   if (w->ldl.own_only && !w->stage32) BA_CHECK(w->stage32.alloc(std::max<int64_t>(1, w->stage_tiles) * NB * NB));
   if (w->use_pattern) BA_CHECK(dense_ldl_use_pattern(&w->ldl32, &w->pattern));
   BA_CHECK(w->rhs32.alloc(w->npad));
-  w->have32 = true;
   return BA_OK;
 }
 
@@ -314,8 +325,6 @@ static int lm_ensure(ba_problem *p) {
   w->nvar = 9 * ncams + 3 * npnts;
   w->nequ = 2 * nobs;
   w->n = 9 * ncams;
-  w->s.red_doubles = reduce_layout(p, &w->s.off_rhs, &w->s.off_gc, &w->s.off_scal);
-  BA_CHECK(w->s.red.alloc(w->s.red_doubles));
   // with a communicator the tile column pairs of S are laid out by owner rank (one contiguous range per rank).  The tiles
   // themselves (n^2/2 doubles: 1 GB for Venice, 60 GB for Final-13682), the Schur task list and the per-observation Y blocks
   // are allocated by ensure_dense when a direct solve first needs them: a handle that only ever runs facto = :PCG never
@@ -325,11 +334,16 @@ static int lm_ensure(ba_problem *p) {
   BA_CHECK(dense_ldl_alloc(&w->ldl, w->n, p->comm.active() ? p->comm.world : 1, p->comm.active() ? p->comm.rank : 0, true,
                            dist_factor_on(p)));
   w->npad = w->ldl.n;
-  w->rhs = w->s.red + w->s.off_rhs;
-  w->gc = w->s.red + w->s.off_gc;
+  // one device buffer [rhs(npad) | gc(npad) | hdiag(npad) | SH_COUNT scalars].  gc, hdiag and the scalars refreshed with the
+  // linearisation are adjacent, in this order: one all-reduce (refresh_linearisation).  (The tiles of S are their own
+  // allocation, made when the first direct solve needs them: ensure_dense.)
+  const int64_t red_doubles = 3 * w->npad + SH_COUNT;
+  BA_CHECK(w->red.alloc(red_doubles));
+  w->rhs = w->red;
+  w->gc = w->rhs + w->npad;
   w->hdiag = w->gc + w->npad;
-  w->scal = w->s.red + w->s.off_scal;
-  BA_HIP_CHECK(hipMemset(w->s.red + w->s.off_rhs, 0, (size_t)(w->s.red_doubles - w->s.off_rhs) * sizeof(double)));
+  w->scal = w->hdiag + w->npad;
+  BA_HIP_CHECK(hipMemset(w->red, 0, (size_t)red_doubles * sizeof(double)));
   BA_HIP_CHECK(hipDeviceSynchronize());  // (null-stream memset: not ordered against the handle's non-blocking stream)
   BA_CHECK(w->x.alloc(w->nvar));
   BA_CHECK(w->x_trial.alloc(w->nvar));
@@ -348,9 +362,9 @@ static int lm_ensure(ba_problem *p) {
   BA_CHECK(w->rob_partial.alloc((int64_t)2 * RED_BLOCKS));
   BA_CHECK(w->cam_pnt.alloc(nobs));
   BA_CHECK(launch_cam_pnt(p, w->cam_pnt, p->stream));
-  BA_CHECK(w->s.scal_rep.alloc(RP_COUNT));
-  BA_CHECK(w->s.h_sh.alloc(SH_COUNT));
-  BA_CHECK(w->s.h_rp.alloc(RP_COUNT));
+  BA_CHECK(w->scal_rep.alloc(RP_COUNT));
+  BA_CHECK(w->h_sh.alloc(SH_COUNT));
+  BA_CHECK(w->h_rp.alloc(RP_COUNT));
   BA_CHECK(w->h_lambda.alloc(1));
   BA_CHECK(w->h_flag.alloc(1));
   BA_CHECK(w->d_lambda.alloc(1));
@@ -374,56 +388,45 @@ static int upload_chunk_tables(LMWork *w, std::vector<std::vector<int64_t>> &cco
 // two staging buffers chunk c travels on the transfer stream while chunk c+1 is assembled on the main one.  Slices per
 // owner: as many as keep all staging within about half a rank's share of S (4 world with two buffers), never finer than a
 // tile column; when two buffers would not fit (small problems) there is one and the transfer is in line.
-static int build_chunks_rs(ba_problem *p, LMWork *w) {
+// owner_cols[r]: the tile columns of rank r, ascending; col_tiles[j]: the tiles of column j (build_chunks)
+static int build_chunks_rs(LMWork *w, const std::vector<std::vector<int64_t>> &owner_cols, const std::vector<int64_t> &col_tiles) {
   const DenseLDL &l = w->ldl;
   const int64_t nt = l.nt;
   const int P = l.world, me = l.rank;
-  const bool sparse = w->use_pattern;
-  auto col_tiles = [&](int64_t j) { return sparse ? l.h_col_cnt[(size_t)j] : nt - j; };
   std::vector<int64_t> share((size_t)P, 0), local_off((size_t)nt, 0);
-  int64_t max_col = 1;
   for (int r = 0; r < P; r++) {
     int64_t run = 0;
-    for (int64_t j = 0; j < nt; j++)
-      if ((j / 2) % P == r) {
-        local_off[(size_t)j] = run;
-        run += col_tiles(j);
-        max_col = std::max(max_col, col_tiles(j));
-      }
+    for (int64_t j : owner_cols[(size_t)r]) {
+      local_off[(size_t)j] = run;
+      run += col_tiles[(size_t)j];
+    }
     share[(size_t)r] = run;
   }
   const int64_t max_share = *std::max_element(share.begin(), share.end());
   const int64_t budget = std::max<int64_t>(max_share / 2, 1);  // all staging together
-  auto plan = [&](int nsl, std::vector<std::vector<std::pair<int64_t, int64_t>>> *slices, int64_t *seg_out) {
-    // per owner: its columns in order cut into nsl runs of about share / nsl tiles; slices[r][c] = (first column index in
-    // the owner's list, one past the last); seg = the longest run
-    slices->assign((size_t)P, {});
-    int64_t seg = 1;
-    for (int r = 0; r < P; r++) {
-      std::vector<int64_t> cols;
-      for (int64_t j = 0; j < nt; j++)
-        if ((j / 2) % P == r) cols.push_back(j);
-      // cumulative boundaries: slice c ends with the first column at which the running count reaches (c + 1) / nsl of the
-      // share, so no slice exceeds its even part by more than one column
-      size_t a = 0;
-      int64_t run = 0;
-      for (int c = 0; c < nsl; c++) {
-        const int64_t goal = (share[(size_t)r] * (c + 1) + nsl - 1) / nsl;
-        size_t b = a;
-        int64_t n = 0;
-        while (b < cols.size() && (run + n < goal || c == nsl - 1)) n += col_tiles(cols[b++]);
-        (*slices)[(size_t)r].push_back({(int64_t)a, (int64_t)b});
-        seg = std::max(seg, n);
-        run += n;
-        a = b;
-      }
+  // per owner: its columns in order cut into nsl runs of about share / nsl tiles; slices[r][c] = (first column index in
+  // the owner's list, one past the last); seg = the longest run
+  const int nsl = 4 * P;
+  std::vector<std::vector<std::pair<int64_t, int64_t>>> slices((size_t)P);
+  int64_t seg = 1;
+  for (int r = 0; r < P; r++) {
+    const std::vector<int64_t> &cols = owner_cols[(size_t)r];
+    // cumulative boundaries: slice c ends with the first column at which the running count reaches (c + 1) / nsl of the
+    // share, so no slice exceeds its even part by more than one column
+    size_t a = 0;
+    int64_t run = 0;
+    for (int c = 0; c < nsl; c++) {
+      const int64_t goal = (share[(size_t)r] * (c + 1) + nsl - 1) / nsl;
+      size_t b = a;
+      int64_t n = 0;
+      while (b < cols.size() && (run + n < goal || c == nsl - 1)) n += col_tiles[(size_t)cols[b++]];
+      slices[(size_t)r].push_back({(int64_t)a, (int64_t)b});
+      seg = std::max(seg, n);
+      run += n;
+      a = b;
     }
-    *seg_out = seg;
-  };
-  std::vector<std::vector<std::pair<int64_t, int64_t>>> slices;
-  int64_t seg = 0;
-  int nsl = 4 * P, bufs = 2;
-  plan(nsl, &slices, &seg);
+  }
+  int bufs = 2;
   if (2 * P * seg > budget + 2 * nt) bufs = 1;  // two buffers do not fit (slices are whole tile columns): one, the transfer in line
   w->assembly_rs = true;
   w->stage_bufs = bufs;
@@ -439,9 +442,7 @@ static int build_chunks_rs(ba_problem *p, LMWork *w) {
     std::vector<int64_t> table((size_t)nt, BA_NO_TILE);
     bool any = false;
     for (int r = 0; r < P; r++) {
-      std::vector<int64_t> cols;
-      for (int64_t j = 0; j < nt; j++)
-        if ((j / 2) % P == r) cols.push_back(j);
+      const std::vector<int64_t> &cols = owner_cols[(size_t)r];
       const auto sl = slices[(size_t)r][(size_t)c];
       if (sl.first >= sl.second) continue;
       any = true;
@@ -451,7 +452,7 @@ static int build_chunks_rs(ba_problem *p, LMWork *w) {
         const int64_t j = cols[(size_t)a];
         table[(size_t)j] = (int64_t)r * seg + (local_off[(size_t)j] - t0);
         col_chunk[(size_t)j] = (int)w->chunks.size();
-        n += col_tiles(j);
+        n += col_tiles[(size_t)j];
       }
       if (r == me) {
         ch.my_t0 = t0;
@@ -466,22 +467,24 @@ static int build_chunks_rs(ba_problem *p, LMWork *w) {
     if (!w->ev_stage_ready[q]) BA_CHECK(w->ev_stage_ready[q].create(hipEventDisableTiming));
     if (!w->ev_stage_free[q]) BA_CHECK(w->ev_stage_free[q].create(hipEventDisableTiming));
   }
-  return upload_chunk_tables(w, cco, col_chunk, sparse);
+  return upload_chunk_tables(w, cco, col_chunk, w->use_pattern);
 }
 
 static int build_chunks(ba_problem *p, LMWork *w) {
-  {
-    const char *e = getenv("BA_ASSEMBLY");  // reduce: every chunk onto ONE owner (round 3's form); default: reduce-scatter
-    if (!(e && e[0] == 'r' && e[1] == 'e' && e[2] == 'd' && e[3] == 'u' && e[4] == 'c' && e[5] == 'e' && e[6] == 0)) return build_chunks_rs(p, w);
-  }
   const DenseLDL &l = w->ldl;
   const int64_t nt = l.nt;
   const int P = l.world;
-  const SchurTasks &T = w->tasks;
   // block-sparse S: a tile column holds the pattern's tiles only (h_col_cnt) and the chunk tables are compressed like the
   // workspace's own (head nt, column offsets, the shared nt x nt row positions)
   const bool sparse = w->use_pattern;
-  auto col_tiles = [&](int64_t j) { return sparse ? l.h_col_cnt[(size_t)j] : nt - j; };
+  std::vector<int64_t> col_tiles((size_t)nt);
+  std::vector<std::vector<int64_t>> owner_cols((size_t)P);
+  for (int64_t j = 0; j < nt; j++) {
+    col_tiles[(size_t)j] = sparse ? l.h_col_cnt[(size_t)j] : nt - j;
+    owner_cols[(size_t)((j / 2) % P)].push_back(j);
+  }
+  const char *e = getenv("BA_ASSEMBLY");  // reduce: every chunk onto ONE owner (round 3's form); default: reduce-scatter
+  if (!(e && strcmp(e, "reduce") == 0)) return build_chunks_rs(w, owner_cols, col_tiles);
   std::vector<int> col_chunk((size_t)nt, -1);
   std::vector<std::vector<int64_t>> cco;
   w->chunks.clear();
@@ -504,9 +507,8 @@ static int build_chunks(ba_problem *p, LMWork *w) {
       c.t0 = local;
       std::fill(table.begin(), table.end(), BA_NO_TILE);
     };
-    for (int64_t j = 0; j < nt; j++) {
-      if ((j / 2) % P != r) continue;
-      const int64_t colt = col_tiles(j);
+    for (int64_t j : owner_cols[(size_t)r]) {
+      const int64_t colt = col_tiles[(size_t)j];
       if (c.ntiles > 0 && c.ntiles + colt > target) flush();
       table[(size_t)j] = local - c.t0;  // offset of tile (j, j) inside the chunk's destination buffer
       col_chunk[(size_t)j] = (int)w->chunks.size();
@@ -676,23 +678,17 @@ void lm_free(ba_problem *p) {
   p->lm = nullptr;
 }
 
-// all-reduce [off, off+count) of the reduce buffer over the ranks (no-op without a communicator; a communicator of one
-// rank is still called: lets one GPU exercise the path)
-static int comm_sum(ba_problem *p, LMWork *w, int64_t off, int64_t count, hipStream_t st) {
-  return comm_allreduce(p, w->s.red + off, count, st);
-}
-
 // the partial sums of S held by every rank -> the complete tile columns on their owners (distributed factorisation), or
 // the complete S everywhere (replicated); the right-hand side is needed by every rank either way
 // s32: the factorisation will run in Float32 and nothing needs the Float64 sum (no column scaling): every rank rounds its
 // partial sums to Float32 first and the owners receive Float32 sums -- half the bytes of the largest transfer of the
 // iteration (Final-13682: 30 GB instead of 60); the sum of `world` rounded partials differs from the rounded sum by a few
 // Float32 ulps, the level of the factorisation itself.
-static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s32 = false) {
+static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s32) {
   if (!p->comm.active()) return BA_OK;
   if (!dist_factor_on(p)) {  // replicated: the whole S and the right-hand side everywhere
     BA_CHECK(comm_allreduce(p, w->ldl.S, w->ldl.s_tiles * NB * NB, st));
-    return comm_sum(p, w, w->s.off_rhs, w->npad, st);
+    return comm_allreduce(p, w->rhs, w->npad, st);
   }
   if (s32) BA_CHECK(launch_convert(w->ldl.S, w->ldl32.S, w->ldl.s_tiles * NB * NB, st));
   BA_CHECK(comm_group_begin(p));
@@ -704,27 +700,24 @@ static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s
   }
   BA_CHECK(comm_group_end(p));
   BA_CHECK(rc);
-  return comm_sum(p, w, w->s.off_rhs, w->npad, st);
+  return comm_allreduce(p, w->rhs, w->npad, st);
 }
 
 // r, J and the normal-equation blocks at w->x; fills sharded/replicated scalars RSQ?, GP, GC, X_P, X_C (and RTSQ)
-// publish: the last reduction kernel also writes the controller's scalars to the pinned host buffers (recorded sequences)
+// recorded: the last reduction kernel also writes the controller's scalars to the pinned host buffers
 // Under a robust loss r and J are reweighted in place (r~, J~) before anything reads them; r must hold the plain residual at
 // w->x on entry (residual_too, or the trial residual of an accepted step)
-static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, hipStream_t st, bool xf32 = false, bool publish = false) {
-  if (xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
+static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bool recorded, hipStream_t st) {
+  if (w->mode.xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
     if (residual_too) {
       BA_CHECK(launch_residual_f32(p, w->xf, w->rf, st));
       BA_CHECK(launch_convert(w->rf, w->r, w->nequ, st));
     }
-  } else if (residual_too) {
-    BA_CHECK(launch_residual_f64(p, w->x, w->r, st));
-  }
-  if (xf32) {
     BA_CHECK(launch_jac_coord_f32(p, w->xf, w->Jf, st));
     BA_CHECK(launch_convert(w->Jf, w->J, 24 * p->nobs, st));
   } else {
+    if (residual_too) BA_CHECK(launch_residual_f64(p, w->x, w->r, st));
     BA_CHECK(launch_jac_coord_f64(p, w->x, w->J, st));
   }
   if (p->fix_on()) BA_CHECK(launch_fix_mask(p, w->J, st));  // fixed parameters (ba_lm_set_fixed): their columns of J to 0
@@ -733,7 +726,7 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, hi
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
   // gc, the diagonal of the camera block (the column scalings need the global one) and the linearisation scalars are
-  // adjacent in the reduce buffer: one all-reduce
+  // adjacent in the reduce buffer (lm_ensure): one all-reduce
   BA_CHECK(launch_hcc_diag(p, w->Hcc, w->hdiag, st));
   // |r|^2, |gp|^2, |x_points|^2 and -- of the all-reduced gc -- |gc|^2, |x_cameras|^2: one launch pair on one rank, two with a
   // communicator (the camera sums wait for the all-reduce); bit-identical to launch_sumsq per vector either way
@@ -749,19 +742,19 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, hi
   jobs.add(w->x, 3 * p->npnts, w->scal, SH_X_P);
   if (p->comm.active()) {
     BA_CHECK(launch_sumsq_multi(p, &jobs, w->partial_multi, st));
-    BA_CHECK(comm_sum(p, w, w->s.off_gc, 2 * w->npad + SH_LIN_COUNT + (robust ? 1 : 0), st));  // (SH_RTSQ follows SH_X_P)
+    BA_CHECK(comm_allreduce(p, w->gc, 2 * w->npad + SH_LIN_COUNT + (robust ? 1 : 0), st));  // (+ SH_RTSQ)
     jobs = SumsqJobs();
   }
-  if (w->f16) BA_CHECK(launch_col_sq(p, w->Hpp, w->hdiag, w->jn2, st));  // |J_j|^2 before the blocks are overwritten by scaled ones
-  jobs.add(w->gc, w->n, w->s.scal_rep, RP_GC);
-  jobs.add(w->x + 3 * p->npnts, w->n, w->s.scal_rep, RP_X_C);
-  if (publish) jobs.publish(w->scal, SH_COUNT, w->s.h_sh, w->s.scal_rep, RP_COUNT, w->s.h_rp, nullptr, nullptr);
+  if (w->mode.f16) BA_CHECK(launch_col_sq(p, w->Hpp, w->hdiag, w->jn2, st));  // |J_j|^2 before the blocks are overwritten by scaled ones
+  jobs.add(w->gc, w->n, w->scal_rep, RP_GC);
+  jobs.add(w->x + 3 * p->npnts, w->n, w->scal_rep, RP_X_C);
+  if (recorded) jobs.publish(w->scal, SH_COUNT, w->h_sh, w->scal_rep, RP_COUNT, w->h_rp, nullptr, nullptr);
   BA_CHECK(launch_sumsq_multi(p, &jobs, w->partial_multi, st));
   return BA_OK;
 }
 
 static int fetch_scalars(ba_problem *p, LMWork *w, hipStream_t st) {
-  BA_CHECK(launch_publish(w->scal, SH_COUNT, w->s.h_sh, w->s.scal_rep, RP_COUNT, w->s.h_rp, nullptr, nullptr, st));
+  BA_CHECK(launch_publish(w->scal, SH_COUNT, w->h_sh, w->scal_rep, RP_COUNT, w->h_rp, nullptr, nullptr, st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
 }
@@ -812,7 +805,7 @@ static int pcg_fetch(LMWork *w, hipStream_t st) {
 static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   BA_CHECK(ensure_pcg(p, w));
   const int64_t n = w->n;
-  const int maxit = w->pcg_maxit > 0 ? w->pcg_maxit : 1000;
+  const int maxit = w->mode.pcg_maxit > 0 ? w->mode.pcg_maxit : 1000;
   BA_HIP_CHECK(hipMemsetAsync(w->ldl.flag, 0, sizeof(int), st));
   BA_CHECK(launch_schur_diag(p, w->J, w->Uinv, w->Hcc, w->blk45, st));
   BA_CHECK(comm_allreduce(p, w->blk45, 45 * p->ncams, st));
@@ -834,7 +827,7 @@ static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
       const double pq = w->h_cg[0], rr = w->h_cg[1];
       // p.q <= 0: S not positive definite along p (or NaN) -- alpha was 0, nothing moved; keep what there is, the LM test
       // judges the step
-      if (!(pq > 0) || !(rr == rr) || rr <= w->pcg_tol * w->pcg_tol * b2) break;
+      if (!(pq > 0) || !(rr == rr) || rr <= w->mode.pcg_tol * w->mode.pcg_tol * b2) break;
     }
   }
   w->n_cg += it < maxit ? it : maxit;
@@ -842,156 +835,181 @@ static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   return BA_OK;
 }
 
-// delta = -(J'J + lambda I)^-1 J'r at the current linearisation; also |J delta + r|^2 -> SH_MODEL, |delta|^2
-// h_lambda (recorded sequences): pinned host scalar the first kernel copies into d_lambda
-static int linear_step(ba_problem *p, LMWork *w, double lambda, int normalize, hipStream_t st,
-                       bool facto_f32 = false, const double *d_lambda = nullptr, const double *h_lambda = nullptr) {
-  // d_lambda: the damping is read from device memory (recorded launches); `lambda` is then the multiplier 1
-  // every rank holds partial Hcc / Schur sums; the lambda I of the camera block is added by rank 0 only
-  const double lam_diag = (p->rank == 0) ? lambda : 0.0;
-  const double *Jl = w->J, *rl = w->r, *damp = nullptr;
-  constexpr double MU16 = 0.1 * 6.55e4;  // lma_aux.jl:44-48
-  if (w->f16) {
-    // facto_type = Float16: columns scaled by their norms, entries and right-hand side rounded to Float16 (k_f16_cols); the
-    // normal-equation blocks are rebuilt from the rounded copies, the damping is per column
-    BA_CHECK(launch_f16_scale(p, lambda, MU16, w->jn2, w->J, w->r, w->dcol, w->damp, w->Jq, w->rq, st));
-    BA_CHECK(launch_point_blocks(p, w->Jq, w->rq, w->Hpp, w->gp, st));
-    BA_CHECK(launch_cam_blocks(p, w->Jq, w->rq, w->Hcc, w->gc, st));
-    Jl = w->Jq;
-    rl = w->rq;
-    damp = w->damp;
-    normalize = 0;  // lm.jl:156,232: no column scaling of J in the Float16 branch
-  }
+// ---- the linear step, part by part (linear_step below runs them in this order) ---------------------------------------------
+constexpr double MU16 = 0.1 * 6.55e4;  // lma_aux.jl:44-48
+// facto_type = Float16: columns scaled by their norms, entries and right-hand side rounded to Float16 (k_f16_cols); the
+// normal-equation blocks are rebuilt from the rounded copies (J_lin / r_lin from here on), the damping is per column (w->damp)
+static int f16_prepare(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
+  BA_CHECK(launch_f16_scale(p, lambda, MU16, w->jn2, w->J, w->r, w->dcol, w->damp, w->Jq, w->rq, st));
+  BA_CHECK(launch_point_blocks(p, w->Jq, w->rq, w->Hpp, w->gp, st));
+  return launch_cam_blocks(p, w->Jq, w->rq, w->Hcc, w->gc, st);
+}
+
+// U^-1 and u of every point at the damping; recorded: the damping is read from h_lambda and left in d_lambda on the way
+static int eliminate_points(ba_problem *p, LMWork *w, double lambda, const double *damp, bool recorded, hipStream_t st) {
   // (single-rank direct path: the right-hand side buffer is cleared by this kernel instead of a memset node of its own)
-  const bool rhs_here = !w->pcg && !w->ldl.own_only;
+  const bool rhs_here = !w->mode.pcg && !w->ldl.own_only;
   // recorded sequences read the damping from pinned host memory (h_lambda).  In k_schur_prep every wave would fetch that
   // scalar over PCIe -- unnoticeable for the few thousand waves of a small problem, where the saved copy node pays, but 15 k
   // waves on the Venice shape and 70 k on Final-13682's: there one thread copies it to device memory first
-  if (h_lambda && p->npnts > 200000) {
-    BA_CHECK(launch_publish(h_lambda, 1, const_cast<double *>(d_lambda), nullptr, 0, nullptr, nullptr, nullptr, st));
-    h_lambda = nullptr;
-  }
-  BA_CHECK(launch_schur_prep(p, lambda, w->Hpp, w->gp, w->Uinv, w->u, st, h_lambda ? h_lambda : d_lambda, damp,
-                             h_lambda ? const_cast<double *>(d_lambda) : nullptr, rhs_here ? w->rhs : nullptr, rhs_here ? w->npad : 0));
-  if (w->pcg) {  // the reduced camera system is applied, not formed (pcg_solve); no column scaling: block Jacobi has its own
-    BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
-    BA_CHECK(launch_schur_rhs(p, Jl, rl, w->u, w->rhs, st, w->cam_pnt));
-    BA_CHECK(comm_sum(p, w, w->s.off_rhs, w->npad, st));
-    w->last_f32 = false;
-    BA_CHECK(pcg_solve(p, w, lambda, st));
-    double *dcp = w->delta + 3 * p->npnts;
-    BA_HIP_CHECK(hipMemcpyAsync(dcp, w->rhs, (size_t)w->n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return launch_backsub(p, Jl, w->Uinv, w->u, dcp, w->delta, st, rl, w->cr0(), w->partial, w->scal, SH_MODEL, &w->model_done);
-  }
-  const bool dist = dist_factor_on(p);
-  const bool reduce32 = dist && facto_f32 && normalize == 0;
-  if (reduce32) BA_CHECK(ensure_f32(w));
-  if (w->ldl.own_only) {
-    // per-rank ownership of S: chunk by chunk -- this rank's share of the chunk's sums goes straight into its own tiles
-    // when it owns the chunk, else into the staging buffer -- and every chunk is reduced onto its owner at once
-    BA_CHECK(launch_schur_pre(p, &w->tasks, Jl, w->Uinv, w->Yobs, st));
-    if (w->assembly_rs) {
-      // reduce-scatter form (build_chunks_rs): every chunk is one slice of EVERY owner's columns, assembled into a staging
-      // buffer of `world` segments and reduce-scattered in place; the owner copies its segment into its tiles.  With two
-      // buffers the transfer of chunk c (transfer stream) runs beside the assembly of chunk c+1 (main stream).
-      const int bufs = w->stage_bufs, me = w->ldl.rank;
-      const int64_t buf_elems = (w->stage_tiles / bufs) * NB * NB;
-      hipStream_t ts = bufs == 2 ? w->ldl.hoist : st;
-      bool used[2] = {false, false};
-      int ci = 0;
-      for (const SchurChunk &c : w->chunks) {
-        const int b = bufs == 2 ? (ci++ & 1) : 0;
-        double *dst = w->stage + b * buf_elems;
-        if (bufs == 2 && used[b]) BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_stage_free[b], 0));  // its last transfer is through
-        BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, Jl, w->Yobs, w->Hcc, lam_diag, dst, w->n, p->rank == 0 ? w->npad : w->n, st,
-                                    d_lambda, damp));
-        const int64_t seg_elems = c.seg * NB * NB, my_elems = c.my_n * NB * NB;
-        float *d32 = reduce32 ? w->stage32 + b * buf_elems : nullptr;
-        if (reduce32) BA_CHECK(launch_convert(dst, d32, c.ntiles * NB * NB, st));
-        if (bufs == 2) {
-          BA_HIP_CHECK(hipEventRecord(w->ev_stage_ready[b], st));
-          BA_HIP_CHECK(hipStreamWaitEvent(ts, w->ev_stage_ready[b], 0));
-        }
-        BA_CHECK(comm_reduce_scatter(p, reduce32 ? (void *)d32 : (void *)dst, seg_elems, reduce32, ts));
-        if (my_elems > 0) {
-          if (reduce32)
-            BA_HIP_CHECK(hipMemcpyAsync(w->ldl32.S + c.my_t0 * NB * NB, d32 + (int64_t)me * seg_elems, (size_t)my_elems * sizeof(float),
-                                        hipMemcpyDeviceToDevice, ts));
-          else
-            BA_HIP_CHECK(hipMemcpyAsync(w->ldl.S + c.my_t0 * NB * NB, dst + (int64_t)me * seg_elems, (size_t)my_elems * sizeof(double),
-                                        hipMemcpyDeviceToDevice, ts));
-        }
-        if (bufs == 2) {
-          BA_HIP_CHECK(hipEventRecord(w->ev_stage_free[b], ts));
-          used[b] = true;
-        }
-      }
-      for (int b = 0; b < 2; b++)
-        if (used[b]) BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_stage_free[b], 0));
-    } else
-    for (const SchurChunk &c : w->chunks) {
-      const bool mine = c.owner == w->ldl.rank;
-      double *dest = mine ? w->ldl.S + c.t0 * NB * NB : w->stage;
-      BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, Jl, w->Yobs, w->Hcc, lam_diag, dest, w->n, p->rank == 0 ? w->npad : w->n, st,
-                                  d_lambda, damp));
-      if (reduce32) {  // Float32 factorisation without column scaling: the partial sums travel as Float32
-        float *d32 = mine ? w->ldl32.S + c.t0 * NB * NB : w->stage32;
-        BA_CHECK(launch_convert(dest, d32, c.ntiles * NB * NB, st));
-        BA_CHECK(comm_reduce_f32(p, d32, c.ntiles * NB * NB, c.owner, st));
-      } else {
-        BA_CHECK(comm_reduce(p, dest, c.ntiles * NB * NB, c.owner, st));
-      }
-    }
-    BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
-    BA_CHECK(launch_schur_rhs(p, Jl, rl, w->u, w->rhs, st, w->cam_pnt, w->tasks.pos));
-    BA_CHECK(comm_sum(p, w, w->s.off_rhs, w->npad, st));
-  } else {
-    BA_CHECK(launch_schur_blocks(p, &w->tasks, Jl, w->Uinv, w->Yobs, w->Hcc, lam_diag, w->ldl.S, w->ldl.col_off, w->n,
-                                 p->rank == 0 ? w->npad : w->n, st, d_lambda, damp, w->ldl.s_tiles));
-    BA_CHECK(launch_schur_rhs(p, Jl, rl, w->u, w->rhs, st, w->cam_pnt, w->tasks.pos));
-    BA_CHECK(reduce_camera_system(p, w, st, reduce32));
-  }
-  if (normalize != 0) {  // :J / :A column scaling of the camera system from the GLOBAL diagonal (refresh_linearisation)
-    BA_CHECK(launch_cam_scale(p, w->hdiag, normalize == 2 ? lambda : 0.0, w->colscale, st, d_lambda, w->tasks.pos));
-    if (w->ldl.own_only && w->use_pattern)
-      BA_CHECK(launch_scale_S_list(p, w->n, w->colscale, w->ldl.S, w->ldl.own_tiles,
-                                   w->ldl.own_range[(size_t)w->ldl.rank + 1] - w->ldl.own_range[(size_t)w->ldl.rank], st));
-    else if (w->ldl.own_only)
-      BA_CHECK(launch_scale_S_own(p, w->n, w->colscale, w->ldl.S, w->ldl.col_off, w->ldl.own_cols, w->ldl.own_pref,
-                                  (int)w->ldl.h_own_cols.size(), w->ldl.own_range[(size_t)w->ldl.rank + 1] - w->ldl.own_range[(size_t)w->ldl.rank], st));
-    else
-      BA_CHECK(launch_scale_S(p, w->n, w->ldl.nt, w->colscale, w->ldl.S, w->ldl.col_off, st));
-    BA_CHECK(launch_scale_vec(p, w->n, w->colscale, w->rhs, 1, st));
-  }
-  w->last_f32 = facto_f32;
-  if (facto_f32) {  // round the assembled system to Float32, factor and solve there, widen the solution
-    BA_CHECK(ensure_f32(w));
-    if (!reduce32) BA_CHECK(launch_convert(w->ldl.S, w->ldl32.S, w->ldl.s_tiles * NB * NB, st));
-    BA_CHECK(launch_convert(w->rhs, w->rhs32, w->npad, st));
-    if (dist) {
-      BA_CHECK(dense_ldl_factor_dist<float>(p, &w->ldl32, st, w->ldl32.own_only ? w->rhs32 : (float *)nullptr));
-      BA_CHECK(dense_ldl_solve<float>(p, &w->ldl32, w->rhs32, st, w->ldl32.own_only));
+  double *const hl = w->h_lambda, *const dl = w->d_lambda;
+  const bool from_host = recorded && p->npnts <= 200000;
+  if (recorded && !from_host) BA_CHECK(launch_publish(hl, 1, dl, nullptr, 0, nullptr, nullptr, nullptr, st));
+  return launch_schur_prep(p, lambda, w->Hpp, w->gp, w->Uinv, w->u, st, from_host ? hl : (recorded ? dl : nullptr), damp,
+                           from_host ? dl : nullptr, rhs_here ? w->rhs : nullptr, rhs_here ? w->npad : 0);
+}
+
+// facto = PCG: the reduced camera system is applied, not formed (pcg_solve); no column scaling: block Jacobi has its own
+static int pcg_step(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
+  BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
+  BA_CHECK(launch_schur_rhs(p, w->J_lin(), w->r_lin(), w->u, w->rhs, st, w->cam_pnt));
+  BA_CHECK(comm_allreduce(p, w->rhs, w->npad, st));
+  BA_CHECK(pcg_solve(p, w, lambda, st));
+  double *dcp = w->delta + 3 * p->npnts;
+  BA_HIP_CHECK(hipMemcpyAsync(dcp, w->rhs, (size_t)w->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  return launch_backsub(p, w->J_lin(), w->Uinv, w->u, dcp, w->delta, st, w->r_lin(), w->cr0(), w->partial, w->scal, SH_MODEL,
+                        &w->model_done);
+}
+
+// S of a rank that holds all of it: every 9 x 9 block straight into the tiles (this rank's partial sums: reduce_camera_system)
+static int assemble_local(ba_problem *p, LMWork *w, double lam_diag, const double *d_lambda, const double *damp, hipStream_t st) {
+  return launch_schur_blocks(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, w->Hcc, lam_diag, w->ldl.S, w->ldl.col_off, w->n,
+                             p->rank == 0 ? w->npad : w->n, st, d_lambda, damp, w->ldl.s_tiles);
+}
+
+// per-rank ownership of S: chunk by chunk -- this rank's share of the chunk's sums goes straight into its own tiles
+// when it owns the chunk, else into the staging buffer -- and every chunk is reduced onto its owner at once
+static int assemble_chunks_reduce(ba_problem *p, LMWork *w, double lam_diag, const double *d_lambda, const double *damp, bool reduce32,
+                                  hipStream_t st) {
+  for (const SchurChunk &c : w->chunks) {
+    const bool mine = c.owner == w->ldl.rank;
+    double *dest = mine ? w->ldl.S + c.t0 * NB * NB : w->stage;
+    BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, w->J_lin(), w->Yobs, w->Hcc, lam_diag, dest, w->n, p->rank == 0 ? w->npad : w->n, st,
+                                d_lambda, damp));
+    if (reduce32) {  // Float32 factorisation without column scaling: the partial sums travel as Float32
+      float *d32 = mine ? w->ldl32.S + c.t0 * NB * NB : w->stage32;
+      BA_CHECK(launch_convert(dest, d32, c.ntiles * NB * NB, st));
+      BA_CHECK(comm_reduce_f32(p, d32, c.ntiles * NB * NB, c.owner, st));
     } else {
-      BA_CHECK(dense_ldl_factor<float>(p, &w->ldl32, st, nullptr, w->rhs32));
-      BA_CHECK(dense_ldl_solve<float>(p, &w->ldl32, w->rhs32, st, true));
+      BA_CHECK(comm_reduce(p, dest, c.ntiles * NB * NB, c.owner, st));
     }
-    BA_CHECK(launch_convert(w->rhs32, w->rhs, w->npad, st));
-  } else if (dist) {
-    BA_CHECK(dense_ldl_factor_dist(p, &w->ldl, st, w->ldl.own_only ? w->rhs : (double *)nullptr));
-    BA_CHECK(dense_ldl_solve(p, &w->ldl, w->rhs, st, w->ldl.own_only));
-  } else {
-    BA_CHECK(dense_ldl_factor(p, &w->ldl, st, nullptr, w->rhs));  // forward substitution of rhs rides along
-    BA_CHECK(dense_ldl_solve(p, &w->ldl, w->rhs, st, true));
   }
+  return BA_OK;
+}
+
+// reduce-scatter form (build_chunks_rs): every chunk is one slice of EVERY owner's columns, assembled into a staging
+// buffer of `world` segments and reduce-scattered in place; the owner copies its segment into its tiles.  With two
+// buffers the transfer of chunk c (transfer stream) runs beside the assembly of chunk c+1 (main stream).
+static int assemble_chunks_rs(ba_problem *p, LMWork *w, double lam_diag, const double *d_lambda, const double *damp, bool reduce32,
+                              hipStream_t st) {
+  const int bufs = w->stage_bufs, me = w->ldl.rank;
+  const int64_t buf_elems = (w->stage_tiles / bufs) * NB * NB;
+  const size_t elem = reduce32 ? sizeof(float) : sizeof(double);
+  char *S_own = reduce32 ? (char *)(float *)w->ldl32.S : (char *)(double *)w->ldl.S;  // this rank's tiles, in the type that travels
+  hipStream_t ts = bufs == 2 ? w->ldl.hoist : st;
+  bool used[2] = {false, false};
+  int ci = 0;
+  for (const SchurChunk &c : w->chunks) {
+    const int b = bufs == 2 ? (ci++ & 1) : 0;
+    double *dst = w->stage + b * buf_elems;
+    if (bufs == 2 && used[b]) BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_stage_free[b], 0));  // its last transfer is through
+    BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, w->J_lin(), w->Yobs, w->Hcc, lam_diag, dst, w->n, p->rank == 0 ? w->npad : w->n, st,
+                                d_lambda, damp));
+    const int64_t seg_elems = c.seg * NB * NB, my_elems = c.my_n * NB * NB;
+    float *d32 = reduce32 ? w->stage32 + b * buf_elems : nullptr;
+    if (reduce32) BA_CHECK(launch_convert(dst, d32, c.ntiles * NB * NB, st));
+    char *sent = reduce32 ? (char *)d32 : (char *)dst;
+    if (bufs == 2) {
+      BA_HIP_CHECK(hipEventRecord(w->ev_stage_ready[b], st));
+      BA_HIP_CHECK(hipStreamWaitEvent(ts, w->ev_stage_ready[b], 0));
+    }
+    BA_CHECK(comm_reduce_scatter(p, sent, seg_elems, reduce32, ts));
+    if (my_elems > 0)
+      BA_HIP_CHECK(hipMemcpyAsync(S_own + (size_t)(c.my_t0 * NB * NB) * elem, sent + (size_t)((int64_t)me * seg_elems) * elem,
+                                  (size_t)my_elems * elem, hipMemcpyDeviceToDevice, ts));
+    if (bufs == 2) {
+      BA_HIP_CHECK(hipEventRecord(w->ev_stage_free[b], ts));
+      used[b] = true;
+    }
+  }
+  for (int b = 0; b < 2; b++)
+    if (used[b]) BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_stage_free[b], 0));
+  return BA_OK;
+}
+
+// :J / :A column scaling of the camera system from the GLOBAL diagonal (refresh_linearisation)
+static int scale_columns(ba_problem *p, LMWork *w, double lambda, const double *d_lambda, hipStream_t st) {
+  BA_CHECK(launch_cam_scale(p, w->hdiag, w->mode.normalize == 2 ? lambda : 0.0, w->colscale, st, d_lambda, w->tasks.pos));
+  const DenseLDL &l = w->ldl;
+  const int64_t own_tiles = l.own_only ? l.own_range[(size_t)l.rank + 1] - l.own_range[(size_t)l.rank] : 0;
+  if (l.own_only && w->use_pattern)
+    BA_CHECK(launch_scale_S_list(p, w->n, w->colscale, l.S, l.own_tiles, own_tiles, st));
+  else if (l.own_only)
+    BA_CHECK(launch_scale_S_own(p, w->n, w->colscale, l.S, l.col_off, l.own_cols, l.own_pref, (int)l.h_own_cols.size(), own_tiles, st));
+  else
+    BA_CHECK(launch_scale_S(p, w->n, l.nt, w->colscale, l.S, l.col_off, st));
+  return launch_scale_vec(p, w->n, w->colscale, w->rhs, 1, st);
+}
+
+// factor the assembled system and solve for rhs in place; the forward substitution of rhs rides along where it can
+template <typename T>
+static int factor_solve(ba_problem *p, DenseLDLT<T> *l, T *rhs, bool dist, hipStream_t st) {
+  if (dist) {
+    BA_CHECK(dense_ldl_factor_dist<T>(p, l, st, l->own_only ? rhs : (T *)nullptr));
+    return dense_ldl_solve<T>(p, l, rhs, st, l->own_only);
+  }
+  BA_CHECK(dense_ldl_factor<T>(p, l, st, rhs));
+  return dense_ldl_solve<T>(p, l, rhs, st, true);
+}
+
+// the solution in w->rhs (block rows of S, scaled columns) -> delta: cameras in camera order, points by back-substitution
+static int step_from_solution(ba_problem *p, LMWork *w, bool normalize, hipStream_t st) {
   double *dc = w->delta + 3 * p->npnts;
-  if (normalize != 0) BA_CHECK(launch_scale_vec(p, w->n, w->colscale, w->rhs, 1, st));  // dc = D^-1 dc'
+  if (normalize) BA_CHECK(launch_scale_vec(p, w->n, w->colscale, w->rhs, 1, st));  // dc = D^-1 dc'
   if (w->tasks.pos) BA_CHECK(launch_gather_cams(p, w->tasks.pos, w->rhs, dc, st));  // block rows of S -> camera order
   else BA_HIP_CHECK(hipMemcpyAsync(dc, w->rhs, (size_t)w->n * sizeof(double), hipMemcpyDeviceToDevice, st));
   // the model value of the step rides along with the back-substitution (not in the Float16 branch: its step is rescaled below)
-  BA_CHECK(launch_backsub(p, Jl, w->Uinv, w->u, dc, w->delta, st, w->f16 ? nullptr : rl, w->cr0(), w->partial, w->scal, SH_MODEL,
-                          &w->model_done));
-  if (w->f16) BA_CHECK(launch_scale_scalar(p, w->nvar, w->delta, 1.0 / MU16, st));  // the right-hand side was -Jh' r / mu
+  BA_CHECK(launch_backsub(p, w->J_lin(), w->Uinv, w->u, dc, w->delta, st, w->mode.f16 ? nullptr : w->r_lin(), w->cr0(), w->partial,
+                          w->scal, SH_MODEL, &w->model_done));
+  if (w->mode.f16) BA_CHECK(launch_scale_scalar(p, w->nvar, w->delta, 1.0 / MU16, st));  // the right-hand side was -Jh' r / mu
   return BA_OK;
+}
+
+// delta = -(J'J + lambda I)^-1 J'r at the current linearisation; also |J delta + r|^2 -> SH_MODEL, |delta|^2
+// recorded: the damping is read from device memory (h_lambda -> d_lambda, eliminate_points); `lambda` is then the multiplier 1
+static int linear_step(ba_problem *p, LMWork *w, double lambda, bool recorded, hipStream_t st) {
+  const StepMode &m = w->mode;
+  // every rank holds partial Hcc / Schur sums; the lambda I of the camera block is added by rank 0 only
+  const double lam_diag = (p->rank == 0) ? lambda : 0.0;
+  const double *const d_lambda = recorded ? (double *)w->d_lambda : nullptr, *const damp = m.f16 ? (double *)w->damp : nullptr;
+  const bool normalize = m.normalize != 0 && !m.f16;  // lm.jl:156,232: no column scaling of J in the Float16 branch
+  if (m.f16) BA_CHECK(f16_prepare(p, w, lambda, st));
+  BA_CHECK(eliminate_points(p, w, lambda, damp, recorded, st));
+  if (m.pcg) return pcg_step(p, w, lambda, st);
+  const bool dist = dist_factor_on(p);
+  const bool reduce32 = dist && m.facto_f32 && !normalize;
+  if (reduce32) BA_CHECK(ensure_f32(w));
+  if (w->ldl.own_only) {
+    BA_CHECK(launch_schur_pre(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, st));
+    if (w->assembly_rs) BA_CHECK(assemble_chunks_rs(p, w, lam_diag, d_lambda, damp, reduce32, st));
+    else BA_CHECK(assemble_chunks_reduce(p, w, lam_diag, d_lambda, damp, reduce32, st));
+    BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
+  } else {
+    BA_CHECK(assemble_local(p, w, lam_diag, d_lambda, damp, st));
+  }
+  BA_CHECK(launch_schur_rhs(p, w->J_lin(), w->r_lin(), w->u, w->rhs, st, w->cam_pnt, w->tasks.pos));
+  BA_CHECK(w->ldl.own_only ? comm_allreduce(p, w->rhs, w->npad, st) : reduce_camera_system(p, w, st, reduce32));
+  if (normalize) BA_CHECK(scale_columns(p, w, lambda, d_lambda, st));
+  if (m.facto_f32) {  // round the assembled system to Float32, factor and solve there, widen the solution
+    BA_CHECK(ensure_f32(w));
+    if (!reduce32) BA_CHECK(launch_convert(w->ldl.S, w->ldl32.S, w->ldl.s_tiles * NB * NB, st));
+    BA_CHECK(launch_convert(w->rhs, w->rhs32, w->npad, st));
+    BA_CHECK(factor_solve<float>(p, &w->ldl32, w->rhs32, dist, st));
+    BA_CHECK(launch_convert(w->rhs32, w->rhs, w->npad, st));
+  } else {
+    BA_CHECK(factor_solve<double>(p, &w->ldl, w->rhs, dist, st));
+  }
+  return step_from_solution(p, w, normalize, st);
 }
 
 // cr: the model value is |J delta + cr r|^2 (1 outside the line search)
@@ -1004,18 +1022,17 @@ static int step_scalars(ba_problem *p, LMWork *w, hipStream_t st, double cr = -1
   if (!defer_delta) {
     SumsqJobs jobs;
     jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);
-    jobs.add(w->delta + 3 * p->npnts, w->n, w->s.scal_rep, RP_DELTA_C);
+    jobs.add(w->delta + 3 * p->npnts, w->n, w->scal_rep, RP_DELTA_C);
     BA_CHECK(launch_sumsq_multi(p, &jobs, w->partial_multi, st));
   }
   return BA_OK;
 }
 
-// with_delta: the step's two norms ride with |r_trial|^2 (step_scalars was told to leave them); publish_flag: the reduction
-// also writes the controller's scalars and this pivot flag to the pinned host buffers (recorded sequences)
-static int trial_point(ba_problem *p, LMWork *w, hipStream_t st, bool xf32 = false, bool with_delta = false,
-                       const int *publish_flag = nullptr) {
+// with_delta: the step's two norms ride with |r_trial|^2 (step_scalars was told to leave them); recorded: the reduction
+// also writes the controller's scalars and the pivot flag to the pinned host buffers
+static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded, hipStream_t st) {
   BA_CHECK(launch_axpy(p, w->nvar, w->x, w->delta, w->x_trial, st));
-  if (xf32) {  // x_suiv is a Float32 vector in the reference: round, evaluate in Float32
+  if (w->mode.xf32) {  // x_suiv is a Float32 vector in the reference: round, evaluate in Float32
     BA_CHECK(launch_convert(w->x_trial, w->xf, w->nvar, st));
     BA_CHECK(launch_convert(w->xf, w->x_trial, w->nvar, st));
     BA_CHECK(launch_residual_f32(p, w->xf, w->rf, st));
@@ -1028,11 +1045,11 @@ static int trial_point(ba_problem *p, LMWork *w, hipStream_t st, bool xf32 = fal
   SumsqJobs jobs;
   if (with_delta) {
     jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);
-    jobs.add(w->delta + 3 * p->npnts, w->n, w->s.scal_rep, RP_DELTA_C);
+    jobs.add(w->delta + 3 * p->npnts, w->n, w->scal_rep, RP_DELTA_C);
   }
   if (robust) jobs.add_robust(w->r_trial, p->nobs, w->scal, SH_RSQ_TRIAL, p->loss, p->loss_scale * p->loss_scale);  // 2 f(x + delta)
   else jobs.add(w->r_trial, w->nequ, w->scal, SH_RSQ_TRIAL);
-  if (publish_flag) jobs.publish(w->scal, SH_COUNT, w->s.h_sh, w->s.scal_rep, RP_COUNT, w->s.h_rp, publish_flag, w->h_flag);
+  if (recorded) jobs.publish(w->scal, SH_COUNT, w->h_sh, w->scal_rep, RP_COUNT, w->h_rp, w->pivot_flag(), w->h_flag);
   return launch_sumsq_multi(p, &jobs, w->partial_multi, st);
 }
 
@@ -1049,30 +1066,40 @@ static int pivot_flag_error(int h, const char *zero_pivot_msg = "reduced camera 
   return BA_OK;
 }
 
-static int check_pivot(ba_problem *p, LMWork *w, hipStream_t st) {
-  int h = 0;
-  BA_HIP_CHECK(hipMemcpyAsync(&h, w->last_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  return pivot_flag_error(h);
+// A hoisted diagonal kernel of the dense factorisation gave up waiting for its flag: the kernels were not running side by
+// side (a counter-collecting profiler serialises them).  Switch the handle to the in-order schedule; the caller redoes
+// the step (S was consumed by the abandoned factorisation).
+static bool hoist_gave_up(LMWork *w) {
+  if (*w->h_flag != 2 || (w->ldl.hoist_disabled && w->ldl32.hoist_disabled)) return false;
+  w->ldl.hoist_disabled = w->ldl32.hoist_disabled = true;
+  return true;
+}
+
+// a step body that ends with the pivot flag in w->h_flag and the stream synchronised: once more when hoist_gave_up
+template <typename F>
+static int with_hoist_retry(LMWork *w, F body) {
+  BA_CHECK(body());
+  if (hoist_gave_up(w)) BA_CHECK(body());
+  return BA_OK;
 }
 
 // ---- recorded launch sequences ------------------------------------------------------------------------------------------
-// what a recorded sequence depends on besides the handle's buffers: the loss kind and scale are launch arguments of the
-// robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed parameters
-// decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables are launch arguments
-static int graph_key(ba_problem *p, int normalize, bool facto_f32, bool xf32) {
-  return normalize + 4 * (facto_f32 ? 1 : 0) + 8 * (xf32 ? 1 : 0) + 16 * p->loss + 128 * (p->fix_ncam > 0 ? 1 : 0) +
-         256 * (p->fix_npnt > 0 ? 1 : 0);
+// what sequences recorded now would be recorded for (RecordedFor)
+static RecordedFor recorded_for(ba_problem *p, LMWork *w) {
+  const StepMode &m = w->mode;
+  const int bits = m.normalize + 4 * (m.facto_f32 ? 1 : 0) + 8 * (m.xf32 ? 1 : 0) + 16 * p->loss + 128 * (p->fix_ncam > 0 ? 1 : 0) +
+                   256 * (p->fix_npnt > 0 ? 1 : 0);
+  return {bits, p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0, p->d_fix_cam, p->d_fix_pnt};
 }
-static double graph_scale(ba_problem *p) { return p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0; }
-static bool graph_fix_same(ba_problem *p, LMWork *w) { return w->g_fix_cam == p->d_fix_cam && w->g_fix_pnt == p->d_fix_pnt; }
+// are the recorded sequences those of the current handle state
+static bool recorded_current(ba_problem *p, LMWork *w) { return w->rec.made_for == recorded_for(p, w); }
 
 static bool graphs_allowed(ba_problem *p, LMWork *w) {
-  if (w->g_off || p->prof_on || p->comm.active() || w->f16 || w->pcg) return false;  // per-kernel events / communicator / Float16 path
+  if (w->rec.off || p->prof_on || p->comm.active() || w->mode.f16 || w->mode.pcg) return false;  // per-kernel events / communicator / Float16 path
   // the hoisted-diagonal schedule of large factorisations has a kernel wait for a flag raised by a kernel running
   // beside it: only with real streams is that concurrency certain (and the graphs gain nothing at that size)
   // (the block-sparse list schedule never hoists and is bound by its chain of short launches: recorded at any size)
-  if (w->ldl.nt >= 34 && !w->use_pattern) return false;  // = HOIST_MIN_TILES + 2 of dense_ldl_factor (above its HOIST_MAX_TILES graphs gain nothing either)
+  if (w->ldl.nt >= HOIST_MIN_TILES + 2 && !w->use_pattern) return false;  // (above HOIST_MAX_TILES graphs gain nothing either)
   return !env_off("BA_LM_GRAPH");
 }
 
@@ -1088,84 +1115,56 @@ static int record_graph(hipStream_t st, HipGraphExec *out, F body) {
   return BA_OK;
 }
 
-// A hoisted diagonal kernel of the dense factorisation gave up waiting for its flag: the kernels were not running side by
-// side (a counter-collecting profiler serialises them).  Switch the handle to the in-order schedule; the caller redoes
-// the step (S was consumed by the abandoned factorisation).
-static bool hoist_gave_up(LMWork *w) {
-  if (*w->h_flag != 2 || (w->ldl.hoist_disabled && w->ldl32.hoist_disabled)) return false;
-  w->ldl.hoist_disabled = w->ldl32.hoist_disabled = true;
-  return true;
+// replays the recorded form of `body` (recording it first when *g is empty) and waits for it.  Recording is an optimisation:
+// when it fails the handle is marked off (plain launches from now on) and the caller issues the launches of `body` itself
+template <typename F>
+static int replay(LMWork *w, HipGraphExec *g, hipStream_t st, F body) {
+  if (!*g && record_graph(st, g, body) != BA_OK) {
+    (void)hipGetLastError();
+    g->reset();
+    w->rec.off = true;
+    return BA_OK;
+  }
+  BA_HIP_CHECK(hipGraphLaunch(*g, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return BA_OK;
 }
 
 // one trial step at damping `lambda`: linear solve, model decrease, trial residual, scalars and pivot flag to the host
-static int trial_step(ba_problem *p, LMWork *w, double lambda, int normalize, bool facto_f32, bool xf32,
-                      hipStream_t st) {
-  if (!graphs_allowed(p, w)) {
-    BA_CHECK(linear_step(p, w, lambda, normalize, st, facto_f32));
+static int trial_step(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
+  auto launches = [&](double lam, bool recorded) -> int {
+    BA_CHECK(linear_step(p, w, lam, recorded, st));
     BA_CHECK(step_scalars(p, w, st, -1.0, true));
-    BA_CHECK(trial_point(p, w, st, xf32, true));
-    BA_CHECK(comm_sum(p, w, w->s.off_scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st));
-    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->last_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
-    BA_CHECK(fetch_scalars(p, w, st));  // (synchronises st)
-    if (hoist_gave_up(w)) return trial_step(p, w, lambda, normalize, facto_f32, xf32, st);
-    return BA_OK;
-  }
-  const int key = graph_key(p, normalize, facto_f32, xf32);
-  if (w->g_key != key || w->g_scale != graph_scale(p) || !graph_fix_same(p, w)) {
-    for (int q = 0; q < 2; q++) {
-      w->g_step[q].reset();
-      w->g_refresh[q].reset();
+    return trial_point(p, w, true, recorded, st);  // (recorded: + scalars and flag to the host)
+  };
+  if (graphs_allowed(p, w)) {
+    if (!recorded_current(p, w)) {
+      w->rec = RecordedSequences();  // (releases all four)
+      w->rec.made_for = recorded_for(p, w);
     }
-    w->g_key = key;
-    w->g_scale = graph_scale(p);
-    w->g_fix_cam = p->d_fix_cam;
-    w->g_fix_pnt = p->d_fix_pnt;
+    if (w->mode.facto_f32) BA_CHECK(ensure_f32(w));  // no allocation while recording
+    *w->h_lambda = lambda;  // read by the sequence's first kernel
+    BA_CHECK(replay(w, &w->rec.step[w->parity], st, [&]() -> int { return launches(1.0, true); }));
+    if (!w->rec.off) return BA_OK;  // (recorded sequences never hoist: graphs_allowed)
   }
-  if (facto_f32) BA_CHECK(ensure_f32(w));  // no allocation while recording
-  HipGraphExec &g = w->g_step[w->parity];
-  if (!g) {
-    const int grc = record_graph(st, &g, [&]() -> int {
-      BA_CHECK(linear_step(p, w, 1.0, normalize, st, facto_f32, w->d_lambda, w->h_lambda));
-      BA_CHECK(step_scalars(p, w, st, -1.0, true));
-      BA_CHECK(trial_point(p, w, st, xf32, true, facto_f32 ? w->ldl32.flag : w->ldl.flag));  // (+ scalars and flag to the host)
-      return BA_OK;
-    });
-    if (grc != BA_OK) {  // recording is an optimisation: without it the same launches are issued one by one
-      (void)hipGetLastError();
-      g.reset();
-      w->g_off = true;
-      return trial_step(p, w, lambda, normalize, facto_f32, xf32, st);
-    }
-  }
-  *w->h_lambda = lambda;
-  w->last_f32 = facto_f32;
-  BA_HIP_CHECK(hipGraphLaunch(g, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  return BA_OK;  // (recorded sequences never hoist: graphs_allowed)
+  return with_hoist_retry(w, [&]() -> int {
+    BA_CHECK(launches(lambda, false));
+    BA_CHECK(comm_allreduce(p, w->scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st));
+    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->pivot_flag(), sizeof(int), hipMemcpyDeviceToHost, st));
+    return fetch_scalars(p, w, st);  // (synchronises st)
+  });
 }
 
 // after an accepted step (x/x_trial, r/r_trial already swapped): J, the normal-equation blocks, J'r, scalars to the host
-static int accept_refresh(ba_problem *p, LMWork *w, bool xf32, hipStream_t st) {
-  if (!graphs_allowed(p, w)) {
-    BA_CHECK(refresh_linearisation(p, w, false, st, xf32));
-    return fetch_scalars(p, w, st);
+static int accept_refresh(ba_problem *p, LMWork *w, hipStream_t st) {
+  if (graphs_allowed(p, w)) {
+    BA_CHECK(replay(w, &w->rec.refresh[w->parity], st, [&]() -> int {
+      return refresh_linearisation(p, w, false, true, st);  // (+ scalars to the host)
+    }));
+    if (!w->rec.off) return BA_OK;
   }
-  HipGraphExec &g = w->g_refresh[w->parity];
-  if (!g) {
-    const int grc = record_graph(st, &g, [&]() -> int {
-      BA_CHECK(refresh_linearisation(p, w, false, st, xf32, true));  // (+ scalars to the host)
-      return BA_OK;
-    });
-    if (grc != BA_OK) {
-      (void)hipGetLastError();
-      g.reset();
-      w->g_off = true;
-      return accept_refresh(p, w, xf32, st);
-    }
-  }
-  BA_HIP_CHECK(hipGraphLaunch(g, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  return BA_OK;
+  BA_CHECK(refresh_linearisation(p, w, false, false, st));
+  return fetch_scalars(p, w, st);
 }
 
 // Recorded sequences only: the refresh after an accepted step and the NEXT trial step (its damping is known at the moment
@@ -1174,16 +1173,14 @@ static int accept_refresh(ba_problem *p, LMWork *w, bool xf32, hipStream_t st) {
 // (Dubrovnik: 31 + 79 us of a 3.0 ms iteration, LadyBug: the same of 0.44 ms; rocprofv3 kernel trace).  The refresh and the
 // trial write disjoint scalar slots, so one read of the pinned buffers serves both.  If the stopping tests that need the
 // refreshed |J'r| or |x| then end the loop, the prefetched step is dropped (never counted, x untouched).
-static bool can_prefetch_trial(ba_problem *p, LMWork *w, int normalize, bool facto_f32, bool xf32) {
+static bool can_prefetch_trial(ba_problem *p, LMWork *w) {
   if (env_off("BA_LM_PREFETCH") || !graphs_allowed(p, w)) return false;  // read per call: a test compares both forms in one process
-  return w->g_key == graph_key(p, normalize, facto_f32, xf32) && w->g_scale == graph_scale(p) && graph_fix_same(p, w) &&
-         w->g_step[w->parity] && w->g_refresh[w->parity];
+  return recorded_current(p, w) && w->rec.step[w->parity] && w->rec.refresh[w->parity];
 }
-static int accept_refresh_and_trial(LMWork *w, double lambda, bool facto_f32, hipStream_t st) {
-  BA_HIP_CHECK(hipGraphLaunch(w->g_refresh[w->parity], st));
+static int accept_refresh_and_trial(LMWork *w, double lambda, hipStream_t st) {
+  BA_HIP_CHECK(hipGraphLaunch(w->rec.refresh[w->parity], st));
   *w->h_lambda = lambda;  // read by the trial sequence's first kernel; the previous trial sequence has completed
-  w->last_f32 = facto_f32;
-  BA_HIP_CHECK(hipGraphLaunch(w->g_step[w->parity], st));
+  BA_HIP_CHECK(hipGraphLaunch(w->rec.step[w->parity], st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
 }
@@ -1199,23 +1196,26 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
   BA_CHECK(fix_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
-  w->pcg = pcg;
-  w->pcg_tol = tol > 0 ? tol : 1e-8;
-  w->pcg_maxit = max_iter > 0 ? max_iter : 0;
+  StepMode mode;
+  mode.facto_f32 = facto_f32;
+  mode.pcg = pcg;
+  mode.pcg_tol = tol > 0 ? tol : 1e-8;
+  mode.pcg_maxit = max_iter > 0 ? max_iter : 0;
+  w->mode = mode;
   w->n_cg = 0;
   if (!pcg) BA_CHECK(ensure_dense(p, w));
   BA_HIP_CHECK(hipMemcpyAsync(w->x, x, (size_t)w->nvar * sizeof(double), hipMemcpyHostToDevice, st));
-  w->f16 = false;
-  BA_CHECK(refresh_linearisation(p, w, true, st));
-  BA_CHECK(linear_step(p, w, lambda, 0, st, facto_f32));
-  {  // same fallback as the LM loop: a hoisted diagonal kernel that gave up -> in-order schedule, redo the step
-    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, facto_f32 ? w->ldl32.flag : w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  BA_CHECK(refresh_linearisation(p, w, true, false, st));
+  // same fallback as the LM loop: a hoisted diagonal kernel that gave up -> in-order schedule, redo the step
+  BA_CHECK(with_hoist_retry(w, [&]() -> int {
+    BA_CHECK(linear_step(p, w, lambda, false, st));
+    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->pivot_flag(), sizeof(int), hipMemcpyDeviceToHost, st));
     BA_HIP_CHECK(hipStreamSynchronize(st));
-    if (hoist_gave_up(w)) BA_CHECK(linear_step(p, w, lambda, 0, st, facto_f32));
-  }
-  BA_CHECK(check_pivot(p, w, st));
+    return BA_OK;
+  }));
+  BA_CHECK(pivot_flag_error(*w->h_flag));
   BA_CHECK(step_scalars(p, w, st));
-  BA_CHECK(comm_sum(p, w, w->s.off_scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st));
+  BA_CHECK(comm_allreduce(p, w->scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st));
   BA_CHECK(fetch_scalars(p, w, st));
   BA_HIP_CHECK(hipMemcpyAsync(delta, w->delta, (size_t)w->nvar * sizeof(double), hipMemcpyDeviceToHost, st));
   if (jtr) {
@@ -1223,9 +1223,8 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
     BA_HIP_CHECK(hipMemcpyAsync(jtr + 3 * p->npnts, w->gc, (size_t)w->n * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   BA_HIP_CHECK(hipStreamSynchronize(st));
-  if (half_sq_model) *half_sq_model = 0.5 * w->s.h_sh[SH_MODEL];
+  if (half_sq_model) *half_sq_model = 0.5 * w->h_sh[SH_MODEL];
   if (cg_iters) *cg_iters = (int)w->n_cg;
-  w->pcg = false;
   return BA_OK;
 }
 
@@ -1242,15 +1241,11 @@ extern "C" int ba_lm_schur_memory(ba_problem *p, int64_t *tiles_full, int64_t *t
 }
 
 extern "C" int ba_lm_schur_pattern(ba_problem *p, double *tile_fill, double *flop_fill, int *sparse_schedule) {
-  if (!p || !p->lm) {
+  if (!p || !p->lm || !p->lm->ldl.S) {
     ba_set_error("ba_lm_schur_pattern: no direct solve has run on this handle yet");
     return BA_ERR_ARG;
   }
   LMWork *w = p->lm;
-  if (!w->ldl.S) {
-    ba_set_error("ba_lm_schur_pattern: no direct solve has run on this handle yet");
-    return BA_ERR_ARG;
-  }
   if (tile_fill) *tile_fill = w->pattern.tile_fill;
   if (flop_fill) *flop_fill = w->pattern.flop_fill;
   if (sparse_schedule) *sparse_schedule = w->use_pattern ? 1 : 0;
@@ -1340,8 +1335,7 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   BA_CHECK(fix_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
-  w->pcg = false;
-  w->f16 = false;
+  w->mode = StepMode();
   BA_CHECK(ensure_dense(p, w));
   const int64_t np3 = 3 * p->npnts;
   std::vector<double> hdamp((size_t)w->nvar, lambda);
@@ -1357,19 +1351,16 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   BA_CHECK(sdiag.alloc(w->npad));
   BA_CHECK(ratio.alloc(1));
   BA_HIP_CHECK(hipMemcpyAsync(w->x, x, (size_t)w->nvar * sizeof(double), hipMemcpyHostToDevice, st));
-  BA_CHECK(refresh_linearisation(p, w, true, st));
-  auto assemble_factor = [&]() -> int {
+  BA_CHECK(refresh_linearisation(p, w, true, false, st));
+  BA_CHECK(with_hoist_retry(w, [&]() -> int {  // as lm_step_impl: the in-order schedule, the factorisation again
     BA_CHECK(launch_schur_prep(p, lambda, w->Hpp, w->gp, w->Uinv, w->u, st, nullptr, damp));
-    BA_CHECK(launch_schur_blocks(p, &w->tasks, w->J, w->Uinv, w->Yobs, w->Hcc, lambda, w->ldl.S, w->ldl.col_off, w->n, w->npad, st,
-                                 nullptr, damp, w->ldl.s_tiles));
+    BA_CHECK(assemble_local(p, w, lambda, nullptr, damp, st));  // (one rank: lam_diag = lambda)
     BA_CHECK(launch_cov_sdiag(p, &w->ldl, w->n, sdiag, nullptr, false, st));
-    BA_CHECK(dense_ldl_factor(p, &w->ldl, st, nullptr, (double *)nullptr));
-    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->ldl.flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    BA_CHECK(dense_ldl_factor(p, &w->ldl, st, (double *)nullptr));
+    BA_HIP_CHECK(hipMemcpyAsync(w->h_flag, w->pivot_flag(), sizeof(int), hipMemcpyDeviceToHost, st));
     BA_HIP_CHECK(hipStreamSynchronize(st));
     return BA_OK;
-  };
-  BA_CHECK(assemble_factor());
-  if (hoist_gave_up(w)) BA_CHECK(assemble_factor());  // as lm_step_impl: the in-order schedule, the factorisation again
+  }));
   BA_CHECK(pivot_flag_error(*w->h_flag, "ba_covariance: exactly zero pivot in the reduced camera system (fix a gauge, or pass lambda > 0)"));
   double h_ratio = 0;
   BA_CHECK(launch_cov_sdiag(p, &w->ldl, w->n, sdiag, ratio, true, st));
@@ -1427,25 +1418,8 @@ static inline TS sqrt(TS a) { return a.w == 32 ? f32(std::sqrt((float)a.v)) : f6
 static inline TS powi(TS a, int n) { return a.w == 32 ? f32(std::pow((float)a.v, (float)n)) : f64(std::pow(a.v, (double)n)); }
 }  // namespace ts
 
-static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bool x_on_device, ba_lm_stats *stats, ba_log_cb cb,
-                         void *cb_ctx);
-
-extern "C" int ba_lm_solve(ba_problem *p, const ba_lm_opts *o, double *x_inout, ba_lm_stats *stats, ba_log_cb cb,
-                           void *cb_ctx) {
-  return lm_solve_impl(p, o, x_inout, false, stats, cb, cb_ctx);
-}
-
-extern "C" int ba_lm_solve_dev(ba_problem *p, const ba_lm_opts *o, double *d_x_inout, ba_lm_stats *stats, ba_log_cb cb,
-                               void *cb_ctx) {
-  return lm_solve_impl(p, o, d_x_inout, true, stats, cb, cb_ctx);
-}
-
-static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bool x_on_device, ba_lm_stats *stats, ba_log_cb cb,
-                         void *cb_ctx) {
-  if (!p || !o || !x_inout || !stats) {
-    ba_set_error("ba_lm_solve: null argument");
-    return BA_ERR_ARG;
-  }
+// the option combinations ba_lm_solve refuses
+static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
   if (o->variant != 0 && o->variant != 1) {
     ba_set_error("ba_lm_solve: variant must be 0 (LevenbergMarquardt.jl) or 1 (lm.jl)");
     return BA_ERR_ARG;
@@ -1501,6 +1475,16 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     ba_set_error("ba_lm_solve: fixed parameters (ba_lm_set_fixed) are not supported with facto_type = Float16");
     return BA_ERR_ARG;
   }
+  return BA_OK;
+}
+
+static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bool x_on_device, ba_lm_stats *stats, ba_log_cb cb,
+                         void *cb_ctx) {
+  if (!p || !o || !x_inout || !stats) {
+    ba_set_error("ba_lm_solve: null argument");
+    return BA_ERR_ARG;
+  }
+  BA_CHECK(check_solve_opts(p, o));
   BA_HIP_CHECK(hipSetDevice(p->device));
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
@@ -1510,15 +1494,19 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   const int V = o->variant;
   // defaults: src/lm.jl:20-26 / src/LevenbergMarquardt.jl:21-26
   const bool xf32 = o->x_f32 != 0;  // eltype(x) = Float32: eps(T)-derived defaults, Float32 iterates and evaluations
+  StepMode mode;
+  mode.normalize = o->normalize;
+  mode.xf32 = xf32;
+  mode.f16 = V && o->facto_type == 2;
+  mode.facto_f32 = V && o->facto_type >= 1 && o->facto != 2;  // Float16 inputs are eliminated and factored in Float32
+  mode.pcg = o->facto == 2;
+  mode.pcg_tol = o->pcg_tol > 0 ? o->pcg_tol : 1e-8;
+  mode.pcg_maxit = o->pcg_max_iter > 0 ? o->pcg_max_iter : 0;
+  w->mode = mode;
   if (xf32) BA_CHECK(ensure_xf32(p, w));
-  w->f16 = V && o->facto_type == 2;
-  if (w->f16) BA_CHECK(ensure_f16(p, w));
-  const bool facto_f32 = V && o->facto_type >= 1 && o->facto != 2;  // Float16 inputs are eliminated and factored in Float32
-  w->pcg = o->facto == 2;
-  w->pcg_tol = o->pcg_tol > 0 ? o->pcg_tol : 1e-8;
-  w->pcg_maxit = o->pcg_max_iter > 0 ? o->pcg_max_iter : 0;
+  if (mode.f16) BA_CHECK(ensure_f16(p, w));
   w->n_cg = 0;
-  if (!w->pcg) BA_CHECK(ensure_dense(p, w));  // (here, not in linear_step: no allocation while a graph is being recorded)
+  if (!mode.pcg) BA_CHECK(ensure_dense(p, w));  // (here, not in linear_step: no allocation while a graph is being recorded)
   // Scalars carry the width Julia's promotion rules give them (TS: value + 32 | 64).  For a Float64 model everything is
   // a Float64 and the arithmetic below is plain double arithmetic.  For eltype(x) = Float32 (src/lm.jl:20-26,36-59):
   // norm() of a Float32 vector, obj = norm_r^2 / 2, pred, ared, rho are Float32; the eps(Float32)-derived default
@@ -1554,14 +1542,14 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
 
   memset(stats, 0, sizeof *stats);
   stats->status = BA_ST_UNKNOWN;
-  double *h_sh = w->s.h_sh, *h_rp = w->s.h_rp;
+  double *h_sh = w->h_sh, *h_rp = w->h_rp;
 
   BA_HIP_CHECK(hipMemcpyAsync(w->x, x_inout, (size_t)w->nvar * sizeof(double), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   if (xf32) {  // x0 is a Float32 vector at the reference's boundary; make sure of it
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
     BA_CHECK(launch_convert(w->xf, w->x, w->nvar, st));
   }
-  BA_CHECK(refresh_linearisation(p, w, true, st, xf32));  // r, J, J'r   (lm.jl:39-58)
+  BA_CHECK(refresh_linearisation(p, w, true, false, st));  // r, J, J'r   (lm.jl:39-58)
   BA_CHECK(fetch_scalars(p, w, st));
   stats->n_residual++;
   stats->n_jacobian++;
@@ -1606,7 +1594,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     if (V) iter++;                                                                           // lm.jl:127
     if (!V && cb) cb(cb_ctx, iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v, lambda.v, norm_delta.v, dr2.v, accepted);  // LevenbergMarquardt.jl:143-147
     if (have_trial) have_trial = false;  // submitted with the refresh of the step accepted last (accept_refresh_and_trial)
-    else if ((rc = trial_step(p, w, lambda.v, o->normalize, facto_f32, xf32, st)) != BA_OK) break;  // lm.jl:154-254
+    else if ((rc = trial_step(p, w, lambda.v, st)) != BA_OK) break;  // lm.jl:154-254
     stats->n_factor++;
     stats->n_residual++;
     if ((rc = pivot_flag_error(*w->h_flag)) != BA_OK) break;
@@ -1636,9 +1624,9 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
         if (delta_d.w == 64) delta_w = 64;
         if ((rc = launch_scale_scalar(p, w->nvar, w->delta, 1.0 / delta_d.v, st)) != BA_OK) break;
         if ((rc = step_scalars(p, w, st, c_r)) != BA_OK) break;
-        if ((rc = trial_point(p, w, st, xf32)) != BA_OK) break;
+        if ((rc = trial_point(p, w, false, false, st)) != BA_OK) break;
         stats->n_residual++;
-        if ((rc = comm_sum(p, w, w->s.off_scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st)) != BA_OK) break;
+        if ((rc = comm_allreduce(p, w->scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st)) != BA_OK) break;
         if ((rc = fetch_scalars(p, w, st)) != BA_OK) break;
         dr2 = half_of(h_sh[SH_MODEL]);
         obj_suiv = half_of(h_sh[SH_RSQ_TRIAL]);
@@ -1691,10 +1679,10 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
       obj = obj_suiv;
       // (what of the stopping tests is known before the refresh decides whether the next trial step goes out with it)
       const bool stop_known = norm_r.v < restol.v || ts::sub(old_obj, obj).v < ts::add(oatol, ts::mul(ortol, old_obj)).v || iter > ite_max;
-      if (!stop_known && can_prefetch_trial(p, w, o->normalize, facto_f32, xf32)) {
-        if ((rc = accept_refresh_and_trial(w, lambda.v, facto_f32, st)) != BA_OK) break;
+      if (!stop_known && can_prefetch_trial(p, w)) {
+        if ((rc = accept_refresh_and_trial(w, lambda.v, st)) != BA_OK) break;
         have_trial = true;
-      } else if ((rc = accept_refresh(p, w, xf32, st)) != BA_OK) break;  // J, J'r  (lm.jl:341,370)
+      } else if ((rc = accept_refresh(p, w, st)) != BA_OK) break;  // J, J'r  (lm.jl:341,370)
       stats->n_jacobian++;
       norm_Jtr = norm_of(h_sh[SH_GP] + h_rp[RP_GC], W);
       norm_x = norm_of(h_sh[SH_X_P] + h_rp[RP_X_C], W);
@@ -1725,7 +1713,6 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   stats->dual_feas = norm_Jtr.v;
   stats->lambda_final = lambda.v;
   stats->n_cg = (int)w->n_cg;
-  w->pcg = false;
   {
     hipError_t e = hipMemcpyAsync(x_inout, w->x, (size_t)w->nvar * sizeof(double), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1736,4 +1723,14 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   }
   stats->elapsed_s = wall() - t_start;
   return rc;  // a NaN step is not an error of the call: status :exception, as in the reference (lm.jl:297-302,401-402)
+}
+
+extern "C" int ba_lm_solve(ba_problem *p, const ba_lm_opts *o, double *x_inout, ba_lm_stats *stats, ba_log_cb cb,
+                           void *cb_ctx) {
+  return lm_solve_impl(p, o, x_inout, false, stats, cb, cb_ctx);
+}
+
+extern "C" int ba_lm_solve_dev(ba_problem *p, const ba_lm_opts *o, double *d_x_inout, ba_lm_stats *stats, ba_log_cb cb,
+                               void *cb_ctx) {
+  return lm_solve_impl(p, o, d_x_inout, true, stats, cb, cb_ctx);
 }
