@@ -61,7 +61,7 @@ SYMBOLS = [
     "ba_jac_structure_dev", "ba_jac_coord_dev", "ba_jac_coord_f32_dev", "ba_jtr_dev", "ba_dev_malloc", "ba_dev_free",
     "ba_memcpy_h2d", "ba_memcpy_d2h", "ba_memcpy_h2d_on", "ba_memcpy_d2h_on", "ba_synchronize", "ba_lm_solve", "ba_lm_solve_dev", "ba_comm_get_unique_id", "ba_lm_set_comm_rccl",
     "ba_lm_set_comm_hook", "ba_comm_stats", "ba_comm_stats_ops", "ba_dist_layout",
-    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_covariance", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
+    "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_lm_set_priors", "ba_lm_get_priors", "ba_prior_eval", "ba_covariance", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
 ]
 
 _lib = None
@@ -121,6 +121,9 @@ def lib():
     L.ba_robust_eval.argtypes = [vp, vp, vp, C.POINTER(f64)]
     L.ba_lm_set_fixed.argtypes = [vp, vp, vp]
     L.ba_lm_get_fixed.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.ba_lm_set_priors.argtypes = [vp] + [i64, vp, vp, vp] * 3
+    L.ba_lm_get_priors.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.ba_prior_eval.argtypes = [vp, vp, C.POINTER(f64), vp, vp, vp]
     L.ba_covariance.argtypes = [vp, vp, f64, f64, vp, vp, C.POINTER(f64)]
     L.ba_profile_enable.argtypes = [vp, C.c_int]
     L.ba_profile_reset.argtypes = [vp]
@@ -271,6 +274,98 @@ def get_fixed(handle):
     nc, npt = C.c_int64(0), C.c_int64(0)
     check(lib().ba_lm_get_fixed(handle, C.byref(nc), C.byref(npt)))
     return nc.value, npt.value
+
+
+# Gaussian priors of the LM entries (ba_lm_set_priors): (index, mu, info) per kind
+_PRIOR_KINDS = (("point_priors", 3), ("camera_priors", 9), ("centre_priors", 3))
+
+
+def _prior_lists(v, dim, n, what):
+    """(idx1 int64 (m,), mu float64 (m, dim), packed info float64 (m, dim (dim + 1) / 2)) of one (index, mu, info) option, or
+    None when it selects nothing.  index: 1-based indices or a boolean array of length n (n None: only the checks that need
+    no problem size); mu: (m, dim); info: full symmetric blocks (m, dim, dim), or standard deviations (m, dim) meaning
+    diag(1 / sigma^2), inf = unconstrained.  ValueError for anything else."""
+    if v is None:
+        return None
+    try:
+        index, mu, info = v
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: a tuple (index, mu, info)") from None
+    a = np.asarray(index)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or (n is not None and a.shape[0] != n):
+            raise ValueError(f"{what}: a boolean index array must have shape ({'n' if n is None else n},), got {a.shape}")
+        idx = np.flatnonzero(a).astype(np.int64) + 1
+    elif a.size == 0:
+        idx = np.zeros(0, dtype=np.int64)
+    else:
+        if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{what}: 1-based integer indices or a boolean array, got dtype {a.dtype}, shape {a.shape}")
+        idx = a.astype(np.int64)
+        if idx.min() < 1 or (n is not None and idx.max() > n):
+            raise ValueError(f"{what}: 1-based indices must lie in 1..{'n' if n is None else n}, got {idx.min()}..{idx.max()}")
+        if np.unique(idx).size != idx.size:
+            raise ValueError(f"{what}: an index may appear once")
+    m = idx.size
+    try:
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        info = np.asarray(info, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: mu and info must be numeric arrays") from None
+    if mu.shape != (m, dim):
+        raise ValueError(f"{what}: mu must have shape ({m}, {dim}), got {mu.shape}")
+    if not np.isfinite(mu).all():
+        raise ValueError(f"{what}: mu must be finite")
+    if info.shape == (m, dim, dim):
+        if not np.isfinite(info).all():
+            raise ValueError(f"{what}: info must be finite")
+        if not np.array_equal(info, info.transpose(0, 2, 1)):
+            raise ValueError(f"{what}: the information blocks must be symmetric")
+        full = info
+    elif info.shape == (m, dim):
+        if np.isnan(info).any() or (info <= 0).any():
+            raise ValueError(f"{what}: standard deviations must be > 0 (inf: unconstrained)")
+        full = np.zeros((m, dim, dim))
+        full[:, np.arange(dim), np.arange(dim)] = 1.0 / info ** 2
+    else:
+        raise ValueError(f"{what}: info must be symmetric blocks ({m}, {dim}, {dim}) or standard deviations ({m}, {dim}), "
+                         f"got {info.shape}")
+    d = np.einsum("kii->ki", full)
+    if (d < 0).any() or (full ** 2 > d[:, :, None] * d[:, None, :]).any():
+        raise ValueError(f"{what}: the information blocks must be positive semi-definite")
+    if m == 0:
+        return None
+    il, jl = np.tril_indices(dim)
+    return idx, mu, np.ascontiguousarray(full[:, il, jl])
+
+
+def check_priors(point_priors=None, camera_priors=None, centre_priors=None):
+    """the checks of set_priors that need no problem size (ValueError); True when the options select something"""
+    some = False
+    for (what, dim), v in zip(_PRIOR_KINDS, (point_priors, camera_priors, centre_priors)):
+        some = (_prior_lists(v, dim, None, what) is not None) or some
+    return some
+
+
+def set_priors(handle, ncams, npnts, point_priors=None, camera_priors=None, centre_priors=None):
+    """the handle's priors for its next LM calls (ba_lm_set_priors), host only; nothing given clears them"""
+    args = []
+    keep = []
+    for (what, dim), v, n in zip(_PRIOR_KINDS, (point_priors, camera_priors, centre_priors), (npnts, ncams, ncams)):
+        lists = _prior_lists(v, dim, n, what)
+        if lists is None:
+            args += [0, None, None, None]
+        else:
+            keep.append(lists)
+            args += [lists[0].size, ptr(lists[0]), ptr(lists[1]), ptr(lists[2])]
+    check(lib().ba_lm_set_priors(handle, *args))
+
+
+def get_priors(handle):
+    """(point, camera, centre) prior counts the handle holds (ba_lm_get_priors)"""
+    a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    check(lib().ba_lm_get_priors(handle, C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
 
 
 def schur_ordering(cam_idx1, pnt_idx1, ncams, npnts, method="AMD"):

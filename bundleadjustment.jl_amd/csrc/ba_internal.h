@@ -199,6 +199,7 @@ enum ProfClass {
   PC_COV_INV,     // covariance (ba_covariance): selected inversion of the factored S, with the rank check's diag(S) and min D_i / S_ii
   PC_COV_CAMS,    // covariance: the cameras' 9 x 9 blocks (k_cov_cams)
   PC_COV_POINTS,  // covariance: the points' 3 x 3 blocks (k_cov_points)
+  PC_PRIOR,       // Gaussian priors (ba_lm_set_priors): k_prior_*_lin at a linearisation, k_prior_*_rhs per linear step, k_prior_*_step per trial step
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -281,6 +282,16 @@ struct BaComm {
 
 void lm_free(ba_problem *p);  // the LM workspace (ba_lm.hip)
 
+// one kind of Gaussian prior of a handle (ba_lm_set_priors): the host lists as given (indices 0-based), their device copies
+struct PriorSet {
+  int64_t n = 0;
+  std::vector<int> h_idx;
+  std::vector<double> h_mu, h_info;
+  DevBuf<int> idx;
+  DevBuf<double> mu, info;
+};
+enum { PRI_PNT = 0, PRI_CAM, PRI_CTR, PRI_KINDS };
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -311,6 +322,18 @@ struct ba_problem {
   DevBuf<uint8_t> d_fix_pnt;
   bool fix_dirty = false;
   bool fix_on() const { return fix_ncam > 0 || fix_npnt > 0; }
+  // Gaussian priors of the LM entries (ba_lm_set_priors): points, cameras, camera centres; uploaded lazily (pri_dirty, prior_upload)
+  // with the buffers the prior kernels write: pri_d = d_k = h_k(x) - mu_k at the linearisation (3 / 9 / 3 per prior, kind after
+  // kind), pri_H = H_k of the centre priors (3 x 6 each, columns of fixed components zeroed), pri_val = three arrays of one value
+  // per prior (kind after kind): d'Lambda d at the linearisation, at the trial point, and the step's model term
+  PriorSet pri[PRI_KINDS];
+  bool pri_dirty = false;
+  DevBuf<double> pri_d, pri_H, pri_val;
+  int64_t pri_total() const { return pri[PRI_PNT].n + pri[PRI_CAM].n + pri[PRI_CTR].n; }
+  bool pri_on() const { return pri_total() > 0; }
+  double *pri_cost() const { return pri_val; }
+  double *pri_cost_trial() const { return pri_val + pri_total(); }
+  double *pri_model() const { return pri_val + 2 * pri_total(); }
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

@@ -176,13 +176,18 @@ struct StepMode {
 // What a recorded sequence depends on besides the handle's buffers: the solve mode; the loss kind and scale, launch
 // arguments of the robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed
 // parameters, which decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables,
-// launch arguments too
+// launch arguments too; the priors (ba_lm_set_priors): how many of each kind (which prior kernels are in the sequence, and
+// their grids) and their device buffers
 struct RecordedFor {
   int bits = -1;  // normalize + 4 * facto_f32 + 8 * xf32 + 16 * loss + 128 / 256 * mask tables (-1: nothing recorded yet)
   double loss_scale = 1.0;
   const void *d_fix_cam = nullptr, *d_fix_pnt = nullptr;
+  int64_t n_pri[PRI_KINDS] = {0, 0, 0};
+  const void *d_pri[PRI_KINDS][3] = {}, *d_pri_work[3] = {};
   bool operator==(const RecordedFor &o) const {
-    return bits == o.bits && loss_scale == o.loss_scale && d_fix_cam == o.d_fix_cam && d_fix_pnt == o.d_fix_pnt;
+    return bits == o.bits && loss_scale == o.loss_scale && d_fix_cam == o.d_fix_cam && d_fix_pnt == o.d_fix_pnt &&
+           memcmp(n_pri, o.n_pri, sizeof n_pri) == 0 && memcmp(d_pri, o.d_pri, sizeof d_pri) == 0 &&
+           memcmp(d_pri_work, o.d_pri_work, sizeof d_pri_work) == 0;
   }
 };
 // hipGraph replay of the two launch sequences of the LM loop (launch-bound on small problems: LadyBug-49 issues ~60
@@ -725,6 +730,8 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
+  // priors (ba_lm_set_priors): their terms into the diagonal blocks and the gradient, before anything reads either
+  BA_CHECK(launch_prior_lin(p, w->x, w->Hpp, w->gp, w->Hcc, w->gc, st));
   // gc, the diagonal of the camera block (the column scalings need the global one) and the linearisation scalars are
   // adjacent in the reduce buffer (lm_ensure): one all-reduce
   BA_CHECK(launch_hcc_diag(p, w->Hcc, w->hdiag, st));
@@ -737,6 +744,10 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
     jobs.add_sum(w->rob_partial + RED_BLOCKS, nb, w->scal, SH_RTSQ);
   } else {
     jobs.add(w->r, w->nequ, w->scal, SH_RSQ);
+  }
+  if (p->pri_on()) {  // + 2 f_prior where the controller reads 2 f (and |r~|^2, the zero-step model value)
+    jobs.add_sum(p->pri_cost(), p->pri_total(), w->scal, SH_RSQ, true);
+    if (robust) jobs.add_sum(p->pri_cost(), p->pri_total(), w->scal, SH_RTSQ, true);
   }
   jobs.add(w->gp, 3 * p->npnts, w->scal, SH_GP);
   jobs.add(w->x, 3 * p->npnts, w->scal, SH_X_P);
@@ -863,6 +874,7 @@ static int eliminate_points(ba_problem *p, LMWork *w, double lambda, const doubl
 static int pcg_step(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
   BA_CHECK(launch_schur_rhs(p, w->J_lin(), w->r_lin(), w->u, w->rhs, st, w->cam_pnt));
+  BA_CHECK(launch_prior_rhs(p, w->rhs, nullptr, st));  // - H'Lambda d of the camera and centre priors
   BA_CHECK(comm_allreduce(p, w->rhs, w->npad, st));
   BA_CHECK(pcg_solve(p, w, lambda, st));
   double *dcp = w->delta + 3 * p->npnts;
@@ -998,6 +1010,7 @@ static int linear_step(ba_problem *p, LMWork *w, double lambda, bool recorded, h
     BA_CHECK(assemble_local(p, w, lam_diag, d_lambda, damp, st));
   }
   BA_CHECK(launch_schur_rhs(p, w->J_lin(), w->r_lin(), w->u, w->rhs, st, w->cam_pnt, w->tasks.pos));
+  BA_CHECK(launch_prior_rhs(p, w->rhs, w->tasks.pos, st));  // - H'Lambda d of the camera and centre priors
   BA_CHECK(w->ldl.own_only ? comm_allreduce(p, w->rhs, w->npad, st) : reduce_camera_system(p, w, st, reduce32));
   if (normalize) BA_CHECK(scale_columns(p, w, lambda, d_lambda, st));
   if (m.facto_f32) {  // round the assembled system to Float32, factor and solve there, widen the solution
@@ -1020,9 +1033,13 @@ static int step_scalars(ba_problem *p, LMWork *w, hipStream_t st, double cr = -1
   if (!(first && w->model_done)) BA_CHECK(launch_model_sq(p, w->J_lin(), w->r_lin(), w->delta, w->partial, w->scal, SH_MODEL, st, cr));
   w->model_done = false;
   if (!defer_delta) {
+    // priors: their model term is added to SH_MODEL behind the observations' (with defer_delta: by trial_point, in one
+    // kernel with the priors' cost at the trial point)
+    BA_CHECK(launch_prior_step(p, w->delta, nullptr, st));
     SumsqJobs jobs;
     jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);
     jobs.add(w->delta + 3 * p->npnts, w->n, w->scal_rep, RP_DELTA_C);
+    if (p->pri_on()) jobs.add_sum(p->pri_model(), p->pri_total(), w->scal, SH_MODEL, true);
     BA_CHECK(launch_sumsq_multi(p, &jobs, w->partial_multi, st));
   }
   return BA_OK;
@@ -1041,6 +1058,10 @@ static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded,
     BA_CHECK(launch_residual_f64(p, w->x_trial, w->r_trial, st));
   }
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (the line search, the only caller without with_delta, is refused then)
+  if (!with_delta && p->pri_on()) {  // (only the line search calls without with_delta, and ba_lm_solve refuses it with priors)
+    ba_set_error("trial point of a rescaled step with priors (internal error: the line search is refused with priors)");
+    return BA_ERR_ARG;
+  }
   if (!with_delta && !robust) return launch_sumsq(p, w->nequ, w->r_trial, w->partial, w->scal, SH_RSQ_TRIAL, st);
   SumsqJobs jobs;
   if (with_delta) {
@@ -1049,6 +1070,13 @@ static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded,
   }
   if (robust) jobs.add_robust(w->r_trial, p->nobs, w->scal, SH_RSQ_TRIAL, p->loss, p->loss_scale * p->loss_scale);  // 2 f(x + delta)
   else jobs.add(w->r_trial, w->nequ, w->scal, SH_RSQ_TRIAL);
+  if (p->pri_on()) {
+    // the step's model term behind the observations' in SH_MODEL, 2 f_prior(x + delta) behind 2 f_obs in SH_RSQ_TRIAL (the
+    // jobs of one launch are summed in order)
+    BA_CHECK(launch_prior_step(p, w->delta, w->x_trial, st));
+    jobs.add_sum(p->pri_model(), p->pri_total(), w->scal, SH_MODEL, true);
+    jobs.add_sum(p->pri_cost_trial(), p->pri_total(), w->scal, SH_RSQ_TRIAL, true);
+  }
   if (recorded) jobs.publish(w->scal, SH_COUNT, w->h_sh, w->scal_rep, RP_COUNT, w->h_rp, w->pivot_flag(), w->h_flag);
   return launch_sumsq_multi(p, &jobs, w->partial_multi, st);
 }
@@ -1089,7 +1117,20 @@ static RecordedFor recorded_for(ba_problem *p, LMWork *w) {
   const StepMode &m = w->mode;
   const int bits = m.normalize + 4 * (m.facto_f32 ? 1 : 0) + 8 * (m.xf32 ? 1 : 0) + 16 * p->loss + 128 * (p->fix_ncam > 0 ? 1 : 0) +
                    256 * (p->fix_npnt > 0 ? 1 : 0);
-  return {bits, p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0, p->d_fix_cam, p->d_fix_pnt};
+  RecordedFor f;
+  f.bits = bits;
+  f.loss_scale = p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0;
+  f.d_fix_cam = p->d_fix_cam;
+  f.d_fix_pnt = p->d_fix_pnt;
+  if (p->pri_on()) {
+    for (int k = 0; k < PRI_KINDS; k++) {
+      const PriorSet &q = p->pri[k];
+      f.n_pri[k] = q.n;
+      if (q.n > 0) f.d_pri[k][0] = q.idx, f.d_pri[k][1] = q.mu, f.d_pri[k][2] = q.info;
+    }
+    f.d_pri_work[0] = p->pri_d, f.d_pri_work[1] = p->pri_H, f.d_pri_work[2] = p->pri_val;
+  }
+  return f;
 }
 // are the recorded sequences those of the current handle state
 static bool recorded_current(ba_problem *p, LMWork *w) { return w->rec.made_for == recorded_for(p, w); }
@@ -1191,9 +1232,14 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
     ba_set_error("ba_lm_step: null argument");
     return BA_ERR_ARG;
   }
+  if (p->pri_on() && p->comm.active()) {
+    ba_set_error("ba_lm_step: priors (ba_lm_set_priors) are not supported on a handle with a communicator");
+    return BA_ERR_ARG;
+  }
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
   BA_CHECK(fix_upload(p));
+  BA_CHECK(prior_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   StepMode mode;
@@ -1306,7 +1352,7 @@ extern "C" int ba_lm_step_f32(ba_problem *p, const double *x, double lambda, dou
   return lm_step_impl(p, x, lambda, delta, half_sq_model, jtr, true);
 }
 
-// Covariance at x: Sigma = (J~_F' J~_F + lambda I)^-1 under the handle's loss and mask, its cameras' 9 x 9 and points'
+// Covariance at x: Sigma = (J~_F' J~_F + sum_k H_k' Lambda_k H_k + lambda I)^-1 under the handle's loss, mask and priors, its cameras' 9 x 9 and points'
 // 3 x 3 diagonal blocks.  The reduced camera system is assembled as linear_step does, with a damping vector that is 1 on the
 // fixed entries and lambda on the free ones; its Float64 factor is inverted in place on the factor's pattern (selected
 // inversion); the point blocks follow from the camera pairs that share a point.  Every buffer the next LM step reads is
@@ -1333,6 +1379,7 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
   BA_CHECK(fix_upload(p));
+  BA_CHECK(prior_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   w->mode = StepMode();
@@ -1475,6 +1522,24 @@ static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
     ba_set_error("ba_lm_solve: fixed parameters (ba_lm_set_fixed) are not supported with facto_type = Float16");
     return BA_ERR_ARG;
   }
+  if (p->pri_on()) {  // priors (ba_lm_set_priors): the combinations their terms are not carried through
+    if (o->variant == 1 && o->linesearch) {
+      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported with linesearch = true");
+      return BA_ERR_ARG;
+    }
+    if (o->x_f32) {
+      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported for a Float32 model (x_f32 = 1)");
+      return BA_ERR_ARG;
+    }
+    if (o->facto_type == 2) {
+      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported with facto_type = Float16");
+      return BA_ERR_ARG;
+    }
+    if (p->comm.active()) {
+      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported on a handle with a communicator");
+      return BA_ERR_ARG;
+    }
+  }
   return BA_OK;
 }
 
@@ -1489,6 +1554,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
   BA_CHECK(fix_upload(p));
+  BA_CHECK(prior_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   const int V = o->variant;

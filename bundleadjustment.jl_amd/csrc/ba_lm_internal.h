@@ -72,11 +72,13 @@ __device__ __forceinline__ double robust_rho(int kind, double s, double c2, doub
   }
 }
 
-// up to six sums in one launch pair (launch_sumsq_multi): vector, length, destination array and slot; the second kernel (one
+// up to eight sums in one launch pair (launch_sumsq_multi): vector, length, destination array and slot; the second kernel (one
 // workgroup) can also publish the controller's scalars to pinned host memory once every sum is in place.  Kind of a job:
 // SJ_SQUARES sum v_i^2 (n entries); SJ_ROBUST sum c^2 rho(|r_o|^2 / c^2) over n observations of the interleaved residual v
-// under (loss, c2); SJ_SUM sum v_i (n entries: the per-block partials of a kernel of its own, e.g. k_robust_scale)
-constexpr int SUMSQ_JOBS = 6;
+// under (loss, c2); SJ_SUM sum v_i (n entries: the per-block partials of a kernel of its own, e.g. k_robust_scale).  A job
+// with acc set ADDS its sum to what the slot holds -- the value a job before it in the same launch, or a kernel before the
+// launch, left there (the prior terms, ba_prior_kernels.hip): the jobs are summed one after the other, in order
+constexpr int SUMSQ_JOBS = 8;
 enum { SJ_SQUARES = 0, SJ_ROBUST = 1, SJ_SUM = 2 };
 struct SumsqJobs {
   int count = 0;
@@ -85,6 +87,7 @@ struct SumsqJobs {
   double *out[SUMSQ_JOBS] = {};
   int slot[SUMSQ_JOBS] = {};
   int kind[SUMSQ_JOBS] = {};
+  int acc[SUMSQ_JOBS] = {};
   int nb[SUMSQ_JOBS] = {};  // filled by the launcher
   int loss = 0;             // SJ_ROBUST jobs: BA_LOSS_* and c^2
   double c2 = 1.0;
@@ -94,23 +97,30 @@ struct SumsqJobs {
   const int *pflag = nullptr;
   int *hflag = nullptr;
   int na = 0, nb2 = 0;
-  void add(const double *vec, int64_t len, double *dst, int s) {
+  // (a job past the last slot is counted, not stored: launch_sumsq_multi refuses a descriptor with count > SUMSQ_JOBS)
+  bool add(const double *vec, int64_t len, double *dst, int s) {
+    if (count >= SUMSQ_JOBS) {
+      count++;
+      return false;
+    }
     v[count] = vec;
     n[count] = len;
     out[count] = dst;
     slot[count] = s;
     kind[count] = SJ_SQUARES;
     count++;
+    return true;
   }
   void add_robust(const double *r, int64_t nobs, double *dst, int s, int loss_, double c2_) {
-    add(r, nobs, dst, s);
+    if (!add(r, nobs, dst, s)) return;
     kind[count - 1] = SJ_ROBUST;
     loss = loss_;
     c2 = c2_;
   }
-  void add_sum(const double *vals, int64_t len, double *dst, int s) {
-    add(vals, len, dst, s);
+  void add_sum(const double *vals, int64_t len, double *dst, int s, bool accumulate = false) {
+    if (!add(vals, len, dst, s)) return;
     kind[count - 1] = SJ_SUM;
+    acc[count - 1] = accumulate ? 1 : 0;
   }
   void publish(const double *a, int na_, double *h_a, const double *b, int nb_, double *h_b, const int *flag, int *h_flag) {
     pa = a; na = na_; ha = h_a; pb = b; nb2 = nb_; hb = h_b; pflag = flag; hflag = h_flag;
@@ -159,6 +169,17 @@ int launch_robust_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, do
 // columns of J of the fixed parameters (no launch without a mask)
 int fix_upload(ba_problem *p);
 int launch_fix_mask(ba_problem *p, double *d_J, hipStream_t st);
+// Gaussian priors (ba_prior_kernels.hip): the handle's lists to the device when they changed (ba_lm_set_priors).
+// launch_prior_lin: at x, d_k (and H_k of the centre priors) -> p->pri_d / pri_H, d_k'Lambda_k d_k -> p->pri_cost(), and
+// H_k'Lambda_k H_k / H_k'Lambda_k d_k ADDED into the diagonal blocks Hpp / Hcc and into gp / gc under the handle's mask.
+// launch_prior_step: d_delta != null: (H_k delta_k + d_k)'Lambda_k (H_k delta_k + d_k) at the stored linearisation ->
+// p->pri_model(); d_xt != null: d_k'Lambda_k d_k at xt -> p->pri_cost_trial().  No launch for a kind without priors.
+// launch_prior_rhs: behind launch_schur_rhs (which forms the camera right-hand side from J and r alone): H_k'Lambda_k d_k of
+// the camera and centre priors at the stored linearisation SUBTRACTED from d_rhs; d_pos: camera -> block row (or null).
+int prior_upload(ba_problem *p);
+int launch_prior_lin(ba_problem *p, const double *d_x, double *d_Hpp, double *d_gp, double *d_Hcc, double *d_gc, hipStream_t st);
+int launch_prior_step(ba_problem *p, const double *d_delta, const double *d_xt, hipStream_t st);
+int launch_prior_rhs(ba_problem *p, double *d_rhs, const int *d_pos, hipStream_t st);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,

@@ -814,7 +814,11 @@ __global__ __launch_bounds__(BLK) void k_sum_partials_multi(SumsqJobs jobs, cons
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) jobs.out[v][jobs.slot[v]] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (threadIdx.x == 0) {
+      const double sum = ((red[0] + red[1]) + red[2]) + red[3];
+      double *dst = jobs.out[v] + jobs.slot[v];
+      *dst = jobs.acc[v] ? *dst + sum : sum;
+    }
     __syncthreads();
   }
   if (jobs.ha) {  // the controller's scalars to pinned host memory (thread 0 wrote the sums: ordered by the barrier)
@@ -1494,6 +1498,10 @@ int launch_sumsq(ba_problem *p, int64_t n, const double *d_v, double *d_partial,
 
 int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi, hipStream_t st) {
   if (jobs->count <= 0) return BA_OK;
+  if (jobs->count > SUMSQ_JOBS) {
+    ba_set_error("reduction: %d sums asked of one launch that holds %d (internal error)", jobs->count, SUMSQ_JOBS);
+    return BA_ERR_ARG;
+  }
   ProfScope ps(p, PC_REDUCE, st);
   for (int v = 0; v < jobs->count; v++) {
     int nb = (int)((jobs->n[v] + BLK - 1) / BLK);

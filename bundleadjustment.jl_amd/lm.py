@@ -56,7 +56,8 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
                         restol=None, satol=None, srtol=None, oatol=None, ortol=None, atol=None, rtol=None,
                         nu_d=None, nu_m=None, lam=None, delta_d=None, ite_max=None, max_time=None, verbose=False,
                         log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0,
-                        fixed_cameras=None, fixed_points=None, fixed_camera_params=None):
+                        fixed_cameras=None, fixed_points=None, fixed_camera_params=None, point_priors=None,
+                        camera_priors=None, centre_priors=None):
     """x_device_ptr (an extension for device-resident callers, e.g. bench.py): the address of nvar doubles of DEVICE memory
     holding x0; the loop then runs through ba_lm_solve_dev -- no host copy of the iterate on either side -- the solution
     stays there and `solution` of the result is None.
@@ -70,10 +71,22 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     fixed_cameras / fixed_points / fixed_camera_params (an extension): parameters held at their values in x0, the solve
     runs over the free entries only (see _lib.fixed_masks for the forms and ba_lm_set_fixed in include/ba_hip.h for the
     semantics).  Set on the handle at every call: a call without them runs the unmasked path.  Not with facto_type =
-    Float16 (ValueError)."""
+    Float16 (ValueError).
+
+    point_priors / camera_priors / centre_priors (an extension): Gaussian priors (index, mu, info) on points, camera blocks
+    (r, t, k1, k2, f) and camera centres c = -R(r)' t, added to the objective as 1/2 (h(x) - mu)' info (h(x) - mu) -- ground
+    control points, calibration priors or an earlier solve's posterior, GPS positions (see _lib._prior_lists for the forms and
+    ba_lm_set_priors in include/ba_hip.h for the semantics).  `objective`, the log's f and |J'r| include them; they are not
+    passed through the robust loss.  Set on the handle at every call: a call without them runs the path without priors.  Not
+    with linesearch = True, a Float32 model or facto_type = Float16 (ValueError)."""
     kind, c = _lib.loss_code(loss, f_scale)
     if kind != 0 and linesearch:
         raise ValueError("a robust loss is not supported with linesearch = true")
+    with_priors = _lib.check_priors(point_priors, camera_priors, centre_priors)
+    if with_priors and linesearch:
+        raise ValueError("priors are not supported with linesearch = true")
+    if with_priors and facto_type is not None and np.dtype(facto_type) == np.float16:
+        raise ValueError("priors are not supported with facto_type = Float16")
     masked = _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
     if masked and facto_type is not None and np.dtype(facto_type) == np.float16:
         raise ValueError("fixed parameters are not supported with facto_type = Float16")
@@ -88,6 +101,8 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     if not isinstance(nlp, BALNLPModel):
         raise TypeError("model must be a FeasibilityResidual(BALNLPModel) or a BALNLPModel")
     xf32 = nlp.T is np.float32  # eltype(x) = Float32: facto_type defaults to it (lm.jl:20), eps(T) tolerances
+    if with_priors and xf32:
+        raise ValueError("priors are not supported for a Float32 model")
     variant = 0 if linesearch is None else 1
     if variant == 0 and (facto_type is not None or max_time is not None):
         raise TypeError("LevenbergMarquardt.jl's Levenberg_Marquardt has no facto_type / max_time keyword")
@@ -131,6 +146,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))  # every call: one without loss= runs the plain objective
     _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)  # ... and one without fixed_* the unmasked path
+    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)  # ... and without *_priors none
     if x_device_ptr is not None:
         _lib.check(_lib.lib().ba_lm_solve_dev(nlp.handle, C.byref(o), C.c_void_p(int(x_device_ptr)), C.byref(st), cb, None))
     else:
@@ -151,18 +167,21 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
 
 
 def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0, fixed_cameras=None,
-            fixed_points=None, fixed_camera_params=None):
+            fixed_points=None, fixed_camera_params=None, point_priors=None, camera_priors=None, centre_priors=None):
     """One linear LM step from (x, lambda): delta, 1/2|J delta + r|^2, J'r  (ba_lm_step; facto_type=np.float32:
     ba_lm_step_f32, the reduced camera system factored in Float32 as src/lm.jl:170-173 does; pcg=(tol, max_iter):
     ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result).
     loss / f_scale (see Levenberg_Marquardt; None = "linear"): the reweighted step, 1/2|J~ delta + r~|^2 and J~'r~.
-    fixed_* (see Levenberg_Marquardt): the step over the free entries; the fixed entries of delta and J'r are exactly 0."""
+    fixed_* (see Levenberg_Marquardt): the step over the free entries; the fixed entries of delta and J'r are exactly 0.
+    *_priors (see Levenberg_Marquardt): the step of the objective with the prior terms; they are in all three outputs."""
     kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
     _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
+    _lib.check_priors(point_priors, camera_priors, centre_priors)
     cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     x = np.ascontiguousarray(x, dtype=np.float64)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
     _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
+    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)
     delta = np.empty(nlp.meta.nvar)
     jtr = np.empty(nlp.meta.nvar) if want_jtr else None
     half = C.c_double(0)
@@ -178,9 +197,10 @@ def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_
 
 
 def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, fixed_points=None, fixed_camera_params=None,
-               rank_tol=None, cameras=True, points=True):
-    """Covariance at x (ba_covariance): the diagonal blocks of (J~_F'J~_F + lam I)^-1, J~ the Jacobian as lm_step sees it
-    under `loss` / `f_scale` and the fixed_* options (see Levenberg_Marquardt), F the free entries.  Returns (cam_cov (ncams,
+               rank_tol=None, cameras=True, points=True, point_priors=None, camera_priors=None, centre_priors=None):
+    """Covariance at x (ba_covariance): the diagonal blocks of (J~_F'J~_F + sum_k H_k' info_k H_k + lam I)^-1, J~ the Jacobian
+    as lm_step sees it under `loss` / `f_scale` and the fixed_* options, the sum over the *_priors (see Levenberg_Marquardt),
+    F the free entries.  Priors that fix the gauge softly make it well defined at lam = 0.  Returns (cam_cov (ncams,
     9, 9) or None, pnt_cov (npnts, 3, 3) or None, min_rel_pivot): camera blocks in block order r1 r2 r3 t1 t2 t3 k1 k2 f,
     rows and columns of fixed entries exactly 0, not scaled by a residual variance (multiply by 2 f / (nequ - n_free) for
     that).  min_rel_pivot = min D_i / S_ii of the factored reduced camera system; at or below rank_tol (None: 1e-10, 0: no
@@ -188,6 +208,7 @@ def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, f
     min_rel_pivot attribute).  Bad arguments raise ValueError before any device call."""
     kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
     _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
+    _lib.check_priors(point_priors, camera_priors, centre_priors)
     try:
         lam = float(lam)
     except (TypeError, ValueError):
@@ -209,6 +230,7 @@ def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, f
     cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
     _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
+    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)
     cam = np.empty((nlp.ncams, 9, 9)) if cameras else None
     pnt = np.empty((nlp.npnts, 3, 3)) if points else None
     piv = C.c_double(0)

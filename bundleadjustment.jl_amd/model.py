@@ -184,6 +184,20 @@ class BALNLPModel:
         _lib.check(_lib.lib().ba_robust_eval(self._h, _lib.ptr(x), _lib.ptr(w), C.byref(cost)))
         return w, cost.value
 
+    # -- Gaussian priors (an extension) ---------------------------------------------------------------------------
+    def prior_eval(self, x, point_priors=None, camera_priors=None, centre_priors=None):
+        """(cost, chi2_points, chi2_cameras, chi2_centres) at x (ba_prior_eval): chi2[k] = d_k' info_k d_k of every prior, d_k
+        = h_k(x) - mu_k, in the order given; cost = 1/2 of their sum, the priors' part of the LM objective.  The options are
+        (index, mu, info) as Levenberg_Marquardt's; sets the handle's priors, as every LM call does."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.meta.nvar,):
+            raise ValueError(f"x has length {x.shape}, expected {self.meta.nvar}")
+        _lib.set_priors(self._h, self.ncams, self.npnts, point_priors, camera_priors, centre_priors)
+        chi2 = [np.zeros(n) for n in _lib.get_priors(self._h)]
+        cost = C.c_double(0)
+        _lib.check(_lib.lib().ba_prior_eval(self._h, _lib.ptr(x), C.byref(cost), *[_lib.ptr(c) if c.size else None for c in chi2]))
+        return (cost.value, *chi2)
+
     # -- per-kernel timing ---------------------------------------------------------------------------------------
     def profile(self, on=True):
         _lib.check(_lib.lib().ba_profile_enable(self._h, int(on)))

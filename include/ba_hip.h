@@ -317,6 +317,45 @@ int ba_robust_eval(ba_problem *p, const double *x, double *weights /* nobs or NU
 int ba_lm_set_fixed(ba_problem *p, const uint16_t *cam_mask, const uint8_t *pnt_fixed);
 int ba_lm_get_fixed(const ba_problem *p, int64_t *n_fixed_cam_params, int64_t *n_fixed_points);
 
+/* ---- Gaussian priors (an extension: the reference has no soft constraint) ------------------------------------------------
+ * Three kinds of prior, each a sparse list of 1-based indices with a mean mu and a symmetric positive semi-definite information
+ * matrix Lambda, packed lower triangle row-major (3 x 3: xx xy yy xz yz zz, 6 per prior; 9 x 9: 45 per prior, the packing of the
+ * camera blocks, component order r1 r2 r3 t1 t2 t3 k1 k2 f):
+ *   point  : h(x) = X_p, the point (mu 3, Lambda 6)                    -- ground control points
+ *   camera : h(x) = C_c = (r, t, k1, k2, f), the camera block (mu 9, Lambda 45) -- calibration priors, an earlier solve's posterior
+ *   centre : h(x) = c(r, t) = -R(r)' t, the camera centre (mu 3, Lambda 6)     -- GPS positions; R the model's Rodrigues
+ *            rotation (theta = |r|, axis r / theta, as the residual evaluates it: no theta -> 0 branch), so P1(r, t, c) = R c + t = 0
+ * The objective becomes f(x) = f_obs(x) + 1/2 sum_k d_k' Lambda_k d_k, d_k = h_k(x) - mu_k; f_obs is 1/2 |r|^2 or the robust sum
+ * (ba_lm_set_loss): priors are NOT passed through the robust loss.  With H_k = dh_k/dx (the identity for point and camera
+ * priors; 3 x 6 on (r, t) for a centre prior, derived by hand, dc/dt = -R') a prior adds H_k' Lambda_k d_k to the gradient,
+ * H_k' Lambda_k H_k to the diagonal block of its point or camera in the Gauss-Newton matrix, and 1/2 (H_k delta_k + d_k)'
+ * Lambda_k (H_k delta_k + d_k) to the model value of a step.  Only diagonal blocks change: the reduced camera system keeps its
+ * pattern.  A zero row and column of Lambda leaves that component unconstrained ("GPS height only" is a valid prior).  A camera
+ * may carry a camera prior and a centre prior; an index may appear once per kind.
+ * stats.objective, stats.dual_feas, the log's f and |J'r|, the jtr output of ba_lm_step and its half_sq_model all include the
+ * prior terms.  Fixed parameters (ba_lm_set_fixed): the columns of H_k of fixed components are zeroed, a fixed point's prior
+ * adds nothing to its block and gradient (its cost, a constant, stays in f).  With no prior set every entry runs exactly
+ * the launch sequence without priors.
+ * Combines with both variants, :LDL / :QR / :PCG, facto_type = Float32, normalize :J / :A, every perm, the block-sparse schedule,
+ * robust losses and fixed parameters.  ba_lm_solve refuses priors together with linesearch = 1, x_f32 = 1, facto_type =
+ * Float16 or a communicator, and ba_lm_step / _f32 / _pcg refuse them on a handle with a communicator (BA_ERR_ARG; the message
+ * names the combination).  ba_covariance includes them (see there): soft constraints make the covariance of a gauge-free scene
+ * well defined at lambda = 0, and the blocks it returns, inverted, are the information of a camera or point prior of a later solve.
+ *   ba_lm_set_priors : the priors of the handle's next LM steps, solves and covariance calls.  All counts 0 clears them.  Host
+ *                      only; uploaded when a step or solve runs.  BA_ERR_ARG (the handle keeps what it had): an index out of
+ *                      range or repeated within a kind, a value that is not finite, a negative diagonal entry of Lambda, or
+ *                      Lambda_ij^2 > Lambda_ii Lambda_jj.
+ *   ba_lm_get_priors : the number of priors of each kind the handle holds (any may be NULL).
+ *   ba_prior_eval    : at x, cost = 1/2 sum_k d_k' Lambda_k d_k and d_k' Lambda_k d_k of every prior, kind by kind in the order
+ *                      given to ba_lm_set_priors; every output may be NULL.  Ignores the mask. */
+int ba_lm_set_priors(ba_problem *p,
+                     int64_t n_pnt, const int64_t *pnt_idx1, const double *pnt_mu /* 3 n */, const double *pnt_info /* 6 n */,
+                     int64_t n_cam, const int64_t *cam_idx1, const double *cam_mu /* 9 n */, const double *cam_info /* 45 n */,
+                     int64_t n_ctr, const int64_t *ctr_idx1, const double *ctr_mu /* 3 n */, const double *ctr_info /* 6 n */);
+int ba_lm_get_priors(const ba_problem *p, int64_t *n_pnt, int64_t *n_cam, int64_t *n_ctr);
+int ba_prior_eval(ba_problem *p, const double *x, double *cost /* or NULL */,
+                  double *chi2_pnt, double *chi2_cam, double *chi2_ctr /* d'Lambda d per prior, each may be NULL */);
+
 /* ---- covariance at a solution (an extension: the reference has none) ------------------------------------------------
  * At x, under the handle's loss (ba_lm_set_loss) and mask (ba_lm_set_fixed):  Sigma = (J~_F' J~_F + lambda I)^-1, J~ the
  * Jacobian exactly as ba_lm_step sees it (reweighted under a robust loss, the columns of the fixed entries zeroed), F the free
@@ -324,6 +363,8 @@ int ba_lm_get_fixed(const ba_problem *p, int64_t *n_fixed_cam_params, int64_t *n
  * order r1 r2 r3 t1 t2 t3 k1 k2 f; pnt_cov (npnts * 9, or NULL): the 3 x 3 block of every point, row-major.  Rows and
  * columns of fixed entries are exactly 0.  Sigma is not scaled by a residual variance: callers who want one multiply by the
  * usual sigma^2 = 2 f / (nequ - n_free), f the objective at x (1/2 |r|^2, or the robust f) and n_free the free entries.
+ * With priors on the handle (ba_lm_set_priors) it assembles as the step does:  Sigma = (J~_F' J~_F + sum_k H_k' Lambda_k H_k +
+ * lambda I)^-1.
  * Both blocks come from the point-eliminated reduced camera matrix S, assembled as the LM step does (damping 1 on the fixed
  * entries, lambda on the free ones) and factored by the Float64 LDL' whatever facto a solve would use (:PCG included), with
  * the handle's camera ordering and schedule (BA_SPARSE_S is honoured).

@@ -58,6 +58,79 @@ function _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, ft
   end
 end
 
+# Gaussian priors (an extension): include/ba_hip.h, ba_lm_set_priors.  Each of point_priors / camera_priors / centre_priors is
+# nothing or a tuple (index, mu, info): 1-based indices (each at most once), mu a (n, d) matrix (d = 3 / 9 / 3: a point, a camera
+# block r t k1 k2 f, a camera centre -R(r)'t), info either n symmetric positive semi-definite d x d matrices as a (d, d, n) array
+# or standard deviations as a (n, d) matrix (diag(1 / sigma^2), Inf = unconstrained).  Set on the handle at every call.
+function _ba_prior_lists(v, d :: Int, n :: Int, what)
+  v === nothing && return Int64[], Float64[], Float64[]
+  idx, mu, info = v
+  m = length(idx)
+  (all(i -> 1 <= i <= n, idx) && allunique(idx)) || error("$what: 1-based indices in 1..$n, each at most once")
+  size(mu) == (m, d) || error("$what: mu must be ($m, $d)")
+  all(isfinite, mu) || error("$what: mu must be finite")
+  full = zeros(Float64, d, d, m)
+  if ndims(info) == 3
+    size(info) == (d, d, m) || error("$what: info must be ($d, $d, $m)")
+    all(isfinite, info) || error("$what: info must be finite")
+    for k in 1:m
+      info[:, :, k] == transpose(info[:, :, k]) || error("$what: the information blocks must be symmetric")
+      full[:, :, k] .= info[:, :, k]
+    end
+  else
+    size(info) == (m, d) || error("$what: info must be ($d, $d, $m) blocks or ($m, $d) standard deviations")
+    all(s -> s > 0, info) || error("$what: standard deviations must be > 0 (Inf: unconstrained)")
+    for k in 1:m, i in 1:d
+      full[i, i, k] = 1.0 / info[k, i]^2
+    end
+  end
+  packed = Float64[]                    # lower triangle, row-major: the C layout
+  for k in 1:m, i in 1:d, j in 1:i
+    push!(packed, full[i, j, k])
+  end
+  return collect(Int64, idx), vec(permutedims(Float64.(mu))), packed
+end
+function _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, linesearch :: Bool, ft :: Int, T :: DataType)
+  pi, pm, pl = _ba_prior_lists(point_priors, 3, nlp.npnts, "point_priors")
+  ci, cm, cl = _ba_prior_lists(camera_priors, 9, nlp.ncams, "camera_priors")
+  ti, tm, tl = _ba_prior_lists(centre_priors, 3, nlp.ncams, "centre_priors")
+  if length(pi) + length(ci) + length(ti) > 0
+    linesearch && error("priors are not supported with linesearch = true")
+    ft == 2 && error("priors are not supported with facto_type = Float16")
+    T == Float32 && error("priors are not supported for a Float32 model")
+  end
+  GC.@preserve pi pm pl ci cm cl ti tm tl begin
+    bacheck(ccall((:ba_lm_set_priors, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}, Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble},
+                   Int64, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}),
+                  nlp.handle, length(pi), pi, pm, pl, length(ci), ci, cm, cl, length(ti), ti, tm, tl))
+  end
+end
+
+"(point, camera, centre) prior counts the handle holds (ba_lm_get_priors)"
+function prior_counts(nlp)
+  a, b, c = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+  bacheck(ccall((:ba_lm_get_priors, libba), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), nlp.handle, a, b, c))
+  return a[], b[], c[]
+end
+
+"""
+    prior_eval(nlp, x; point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
+
+`(cost, chi2_points, chi2_cameras, chi2_centres)` at `x` (ba_prior_eval): chi2[k] = d_k' info_k d_k of every prior in the order
+given, cost = half their sum, the priors' part of the LM objective.  Sets the handle's priors, as every LM call does.
+"""
+function prior_eval(nlp, x :: AbstractVector; point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
+  _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, false, 0, Float64)
+  np, nc, nt = prior_counts(nlp)
+  cp, cc, ct = zeros(np), zeros(nc), zeros(nt)
+  cost = Ref{Cdouble}(0.0)
+  xv = Vector{Float64}(x)
+  bacheck(ccall((:ba_prior_eval, libba), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                nlp.handle, xv, cost, cp, cc, ct))
+  return cost[], cp, cc, ct
+end
+
 # one log row per iteration, the reference's columns (src/lm.jl:120-121,304)
 function _ba_log_row(ctx :: Ptr{Cvoid}, iter :: Cint, f :: Cdouble, df :: Cdouble, njtr :: Cdouble, lambda :: Cdouble,
                      ndelta :: Cdouble, rho :: Cdouble, acc :: Cint) :: Cvoid
@@ -69,7 +142,7 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
                 x :: AbstractVector, facto_type :: DataType, restol, satol, srtol, oatol, ortol, atol, rtol, νd, νm, λ, δd,
                 ite_max :: Int, max_time :: Real, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
                 loss :: Symbol = :linear, f_scale :: Real = 1.0, fixed_cameras = nothing, fixed_points = nothing,
-                fixed_camera_params = nothing)
+                fixed_camera_params = nothing, point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
   # :PCG is an extension of the HIP path (no counterpart in the reference): matrix-free conjugate gradients on the reduced
   # camera system, include/ba_hip.h, ba_lm_opts.facto
   facto in (:QR, :LDL, :PCG) || error("facto must be :QR, :LDL or :PCG")
@@ -89,6 +162,7 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
   (loss != :linear && linesearch) && error("a robust loss is not supported with linesearch = true")
   _ba_set_loss(nlp, loss, f_scale)
   _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, ft)
+  _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, linesearch, ft, T)
   st = BaLmStats()
   xd = Vector{Float64}(x)               # the ABI carries the iterate as doubles (exact for Float32 values)
   cb = @cfunction(_ba_log_row, Cvoid, (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cint))
@@ -120,10 +194,11 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
                              ite_max :: Int = 200, max_time :: Int = 3600, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
                              loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
-                             fixed_camera_params = nothing)
+                             fixed_camera_params = nothing, point_priors = nothing, camera_priors = nothing,
+                             centre_priors = nothing)
   return _ba_lm(model, 1, facto, perm, normalize, linesearch, x, facto_type, restol, satol, srtol, oatol, ortol, atol, rtol,
                 νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter, loss, f_scale, fixed_cameras, fixed_points,
-                fixed_camera_params)
+                fixed_camera_params, point_priors, camera_priors, centre_priors)
 end
 
 "src/LevenbergMarquardt.jl:16-26 -- the 4-argument method src/solve_ba.jl:26 calls (no linesearch, no facto_type)"
@@ -132,26 +207,31 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              restol = nothing, satol = nothing, srtol = nothing, oatol = nothing, ortol = nothing,
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
                              ite_max :: Int = 100, loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing,
-                             fixed_points = nothing, fixed_camera_params = nothing)
+                             fixed_points = nothing, fixed_camera_params = nothing, point_priors = nothing,
+                             camera_priors = nothing, centre_priors = nothing)
   return _ba_lm(model, 0, facto, perm, normalize, false, x, eltype(x), restol, satol, srtol, oatol, ortol, atol, rtol,
-                νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params)
+                νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
+                point_priors, camera_priors, centre_priors)
 end
 
 """
     covariance(nlp, x; λ = 0.0, loss = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
-               fixed_camera_params = nothing, rank_tol = nothing)
+               fixed_camera_params = nothing, rank_tol = nothing, point_priors = nothing, camera_priors = nothing,
+               centre_priors = nothing)
 
-Covariance at `x` (an extension; include/ba_hip.h, ba_covariance): the diagonal blocks of (J̃_F'J̃_F + λI)⁻¹ under the loss
-and the fixed parameters given (keywords as Levenberg_Marquardt's).  Returns `(cam_cov, pnt_cov, min_rel_pivot)`:
+Covariance at `x` (an extension; include/ba_hip.h, ba_covariance): the diagonal blocks of (J̃_F'J̃_F + Σ H_k'Λ_k H_k + λI)⁻¹ under
+the loss, the fixed parameters and the priors given (keywords as Levenberg_Marquardt's).  Returns `(cam_cov, pnt_cov, min_rel_pivot)`:
 cam_cov[:, :, c] the 9 × 9 block of camera c (block order r1 r2 r3 t1 t2 t3 k1 k2 f), pnt_cov[:, :, i] the 3 × 3 block of
 point i; fixed rows and columns are 0.  Not scaled by a residual variance.  With the gauge free and λ = 0 the reduced
 camera system is singular: SQDException (rank_tol = nothing: the library's default, 0: no check).
 """
 function covariance(nlp, x :: AbstractVector; λ :: Real = 0.0, loss :: Symbol = :linear, f_scale = 1.0,
-                    fixed_cameras = nothing, fixed_points = nothing, fixed_camera_params = nothing, rank_tol = nothing)
+                    fixed_cameras = nothing, fixed_points = nothing, fixed_camera_params = nothing, rank_tol = nothing,
+                    point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
   (isfinite(λ) && λ >= 0) || error("λ must be finite and >= 0")
   _ba_set_loss(nlp, loss, f_scale)
   _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, 0)
+  _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, false, 0, Float64)
   xv = Vector{Float64}(x)
   cam = zeros(Float64, 81 * nlp.ncams)
   pnt = zeros(Float64, 9 * nlp.npnts)
