@@ -14,7 +14,7 @@ except ImportError:  # pragma: no cover
 from . import _lib
 from ._lib import BAArgError, BAError, SQDException, LOSSES, device_count
 from .lm import GenericExecutionStats, Levenberg_Marquardt, lm_step, covariance, schur_pattern, schur_memory, set_ordering, schur_ordering_used
-from ._lib import schur_ordering
+from ._lib import schur_ordering, tie_intrinsics
 from .model import BALNLPModel, FeasibilityResidual
 from .readfiles import name, readfile
 from . import synthetic
@@ -22,4 +22,4 @@ from . import parallel
 
 __all__ = ["BALNLPModel", "FeasibilityResidual", "Levenberg_Marquardt", "GenericExecutionStats", "readfile", "name",
            "BAError", "BAArgError", "SQDException", "LOSSES", "device_count", "synthetic", "parallel", "lm_step", "covariance", "schur_pattern", "schur_memory", "set_ordering", "schur_ordering_used",
-           "schur_ordering"]
+           "schur_ordering", "tie_intrinsics"]

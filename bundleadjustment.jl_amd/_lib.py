@@ -62,6 +62,7 @@ SYMBOLS = [
     "ba_memcpy_h2d", "ba_memcpy_d2h", "ba_memcpy_h2d_on", "ba_memcpy_d2h_on", "ba_synchronize", "ba_lm_solve", "ba_lm_solve_dev", "ba_comm_get_unique_id", "ba_lm_set_comm_rccl",
     "ba_lm_set_comm_hook", "ba_comm_stats", "ba_comm_stats_ops", "ba_dist_layout",
     "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_lm_set_priors", "ba_lm_get_priors", "ba_prior_eval", "ba_covariance", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
+    "ba_lm_set_shared_intrinsics", "ba_lm_get_shared_intrinsics", "ba_dense_ldl_solve_multi",
 ]
 
 _lib = None
@@ -130,6 +131,9 @@ def lib():
     L.ba_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(f64), C.POINTER(i64), C.POINTER(C.c_int)]
     L.ba_dense_ldl_solve.argtypes = [C.c_int, i64, vp, vp, vp, C.POINTER(f64)]
     L.ba_dense_ldl_solve_f32.argtypes = [C.c_int, i64, vp, vp, vp, C.POINTER(f64)]
+    L.ba_lm_set_shared_intrinsics.argtypes = [vp, vp]
+    L.ba_lm_get_shared_intrinsics.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(i64)]
+    L.ba_dense_ldl_solve_multi.argtypes = [C.c_int, i64, vp, C.c_int, vp, vp, C.POINTER(f64)]
     _lib = L
     return L
 
@@ -366,6 +370,110 @@ def get_priors(handle):
     a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     check(lib().ba_lm_get_priors(handle, C.byref(a), C.byref(b), C.byref(c)))
     return a.value, b.value, c.value
+
+
+# shared intrinsics of the LM entries (ba_lm_set_shared_intrinsics): calibration groups
+MAX_GROUPS = 8
+
+
+def _shared_groups(v, ncams=None):
+    """the members of every group of a grouping, as a list of 0-based camera index arrays (group g at g - 1), from either form:
+    an integer array of labels (0: own intrinsics, g in 1..8: member of group g) or a list of lists of 1-based camera indices.
+    ncams None: only the checks that need no problem size.  ValueError for a negative label, a label above 8, a gap in the
+    labels, an index outside 1..ncams, a camera in two groups or a wrong shape."""
+    if isinstance(v, (list, tuple)) and (len(v) == 0 or all(isinstance(g, (list, tuple, np.ndarray)) for g in v)):
+        if len(v) > MAX_GROUPS:
+            raise ValueError(f"shared_intrinsics: at most {MAX_GROUPS} groups, got {len(v)}")
+        groups = []
+        for g, members in enumerate(v, 1):
+            a = np.asarray(members)
+            if a.size == 0:
+                raise ValueError(f"shared_intrinsics: group {g} is empty (the labels may have no gap)")
+            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"shared_intrinsics: group {g}: 1-based integer camera indices, got dtype {a.dtype}, shape {a.shape}")
+            if a.min() < 1 or (ncams is not None and a.max() > ncams):
+                raise ValueError(f"shared_intrinsics: group {g}: 1-based indices must lie in 1..{'ncams' if ncams is None else ncams}, "
+                                 f"got {a.min()}..{a.max()}")
+            groups.append(a.astype(np.int64) - 1)
+        every = np.concatenate(groups) if groups else np.zeros(0, dtype=np.int64)
+        if np.unique(every).size != every.size:
+            raise ValueError("shared_intrinsics: a camera may belong to one group only")
+        return groups
+    a = np.asarray(v)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer) or (ncams is not None and a.shape[0] != ncams):
+        raise ValueError(f"shared_intrinsics: integer labels of shape ({'ncams' if ncams is None else ncams},) or a list of "
+                         f"lists of 1-based camera indices, got dtype {a.dtype}, shape {a.shape}")
+    if a.size and (a.min() < 0 or a.max() > MAX_GROUPS):
+        raise ValueError(f"shared_intrinsics: labels must lie in 0..{MAX_GROUPS} (0: own intrinsics), got {a.min()}..{a.max()}")
+    groups = [np.flatnonzero(a == g) for g in range(1, (int(a.max()) if a.size else 0) + 1)]
+    for g, mem in enumerate(groups, 1):
+        if mem.size == 0:
+            raise ValueError(f"shared_intrinsics: the labels have a gap: no camera in group {g}, but one in group {len(groups)}")
+    return groups
+
+
+def check_shared(shared_intrinsics):
+    """the checks of shared_labels that need no problem size (ValueError); True when the option ties something (a group of two
+    cameras or more)"""
+    return shared_intrinsics is not None and any(g.size >= 2 for g in _shared_groups(shared_intrinsics))
+
+
+def shared_labels(shared_intrinsics, ncams):
+    """int32 labels (ncams,) of a grouping in either form of _shared_groups -- 0: the camera keeps its own (k1, k2, f); g in
+    1..G <= 8: it shares them with the other members of group g -- or None when nothing is shared (None, all labels 0, only
+    groups of one camera).  ValueError as _shared_groups, before any device call."""
+    if shared_intrinsics is None:
+        return None
+    groups = _shared_groups(shared_intrinsics, int(ncams))
+    if not any(g.size >= 2 for g in groups):
+        return None
+    lab = np.zeros(int(ncams), dtype=np.int32)
+    for g, mem in enumerate(groups, 1):
+        lab[mem] = g
+    return lab
+
+
+def set_shared(handle, labels):
+    """the handle's grouping for its next LM calls (ba_lm_set_shared_intrinsics); None clears it"""
+    check(lib().ba_lm_set_shared_intrinsics(handle, None if labels is None else ptr(labels)))
+
+
+def get_shared(handle):
+    """(groups, members) the handle holds (ba_lm_get_shared_intrinsics)"""
+    g, m = C.c_int(0), C.c_int64(0)
+    check(lib().ba_lm_get_shared_intrinsics(handle, C.byref(g), C.byref(m)))
+    return g.value, m.value
+
+
+def tie_intrinsics(x, npnts, shared_intrinsics):
+    """A copy of x (layout [points; cameras]) in which the members of every group hold the (k1, k2, f) of the group's first
+    member (lowest camera index): what a step or solve with shared_intrinsics asks of its x."""
+    x = np.array(x, dtype=np.float64, copy=True)
+    npnts = int(npnts)
+    if x.ndim != 1 or (x.size - 3 * npnts) % 9 != 0 or x.size < 3 * npnts:
+        raise ValueError(f"tie_intrinsics: x must have 3 npnts + 9 ncams entries, got {x.shape} with npnts = {npnts}")
+    ncams = (x.size - 3 * npnts) // 9
+    lab = shared_labels(shared_intrinsics, ncams)
+    if lab is None:
+        return x
+    cams = x[3 * npnts:].reshape(ncams, 9)
+    for g in range(1, int(lab.max()) + 1):
+        mem = np.flatnonzero(lab == g)
+        if mem.size >= 2:
+            cams[mem[1:], 6:9] = cams[mem[0], 6:9]
+    return x
+
+
+def dense_ldl_solve_multi(A, B, device=0):
+    """Solve A X = B for the columns of B (n, nrhs) with ONE device LDL' and the multi-right-hand-side sweeps
+    (ba_dense_ldl_solve_multi); only the lower triangle of A is read.  -> (X (n, nrhs), factor_ms)"""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    Bc = np.ascontiguousarray(np.asarray(B, dtype=np.float64).T)  # column-major n x nrhs
+    nrhs, n = Bc.shape
+    X = np.zeros_like(Bc)
+    ms = C.c_double(0)
+    check(lib().ba_dense_ldl_solve_multi(device, n, ptr(A), nrhs, ptr(Bc), ptr(X), C.byref(ms)))
+    return np.ascontiguousarray(X.T), ms.value
 
 
 def schur_ordering(cam_idx1, pnt_idx1, ncams, npnts, method="AMD"):

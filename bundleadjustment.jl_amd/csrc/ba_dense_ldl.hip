@@ -1593,6 +1593,78 @@ __global__ __launch_bounds__(256) void k_bwd_pair2(const T *__restrict__ S, cons
 }
 
 
+// The sweeps over m right-hand sides at once (shared intrinsics, DESIGN §5g: the 3G border columns; ba_dense_ldl_solve_multi):
+// column-blocked twins of k_fwd_step / k_bwd_step, right-hand side blockIdx.y at b + blockIdx.y ld.  A chain of nt short launches
+// each way whatever m is -- which is why they exist.  One form for the dense and the block-sparse layout: workgroup x > 0 owns
+// tile row k + x (forward) or tile column x - 1 (backward) and leaves at once when the pattern has no such tile (it holds zeros).
+template <typename T>
+__global__ __launch_bounds__(256) void k_fwd_step_multi(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
+                                                         T *__restrict__ b, T *__restrict__ y, int k, int64_t ld) {
+  BA_VT
+  __shared__ T yk[NB];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int i = k + blockIdx.x;
+  const int64_t tik = blockIdx.x == 0 ? 0 : tix(co, i, k);
+  if (tik < 0) return;
+  b += (int64_t)blockIdx.y * ld;
+  y += (int64_t)blockIdx.y * ld;
+  const T *Lk = Linv + (int64_t)k * NB * NB;
+  const d2 bk = *reinterpret_cast<const d2 *>(b + (int64_t)k * NB + 2 * lane);
+  for (int rr = 0; rr < 32; rr++) {
+    int row = wv * 32 + rr;
+    d2 l = *reinterpret_cast<const d2 *>(Lk + row * NB + 2 * lane);
+    T s = wsum(l.x * bk.x + l.y * bk.y);
+    if (lane == 0) yk[row] = s;
+  }
+  __syncthreads();
+  if (blockIdx.x == 0) {
+    if (tid < NB) y[(int64_t)k * NB + tid] = yk[tid];
+    return;
+  }
+  const T *Lik = S + tik * NB * NB;
+  const T y0 = yk[2 * lane], y1 = yk[2 * lane + 1];
+  for (int rr = 0; rr < 32; rr++) {
+    int row = wv * 32 + rr;
+    d2 l = *reinterpret_cast<const d2 *>(Lik + row * NB + 2 * lane);
+    T s = wsum(l.x * y0 + l.y * y1);
+    if (lane == 0) b[(int64_t)i * NB + row] -= s;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_bwd_step_multi(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
+                                                         const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k, int64_t ld) {
+  __shared__ T zk[NB], xk[NB], part[2][NB];
+  const int tid = threadIdx.x;
+  const int c = tid & (NB - 1), half = tid >> 7;
+  const int j = (int)blockIdx.x - 1;  // 0 .. k-1
+  const int64_t tkj = blockIdx.x == 0 ? 0 : tix(co, k, j);
+  if (tkj < 0) return;
+  y += (int64_t)blockIdx.y * ld;
+  x += (int64_t)blockIdx.y * ld;
+  if (tid < NB) zk[tid] = y[(int64_t)k * NB + tid] / D[(int64_t)k * NB + tid];
+  __syncthreads();
+  {
+    const T *Lk = Linv + (int64_t)k * NB * NB;
+    T s = 0;
+    for (int r = half * 64; r < half * 64 + 64; r++) s += Lk[r * NB + c] * zk[r];
+    part[half][c] = s;
+  }
+  __syncthreads();
+  if (tid < NB) xk[tid] = part[0][tid] + part[1][tid];
+  __syncthreads();
+  if (blockIdx.x == 0) {
+    if (tid < NB) x[(int64_t)k * NB + tid] = xk[tid];
+    return;
+  }
+  const T *Lkj = S + tkj * NB * NB;
+  T s = 0;
+  for (int r = half * 64; r < half * 64 + 64; r++) s += Lkj[r * NB + c] * xk[r];
+  part[half][c] = s;
+  __syncthreads();
+  if (tid < NB) y[(int64_t)j * NB + tid] -= D[(int64_t)j * NB + tid] * (part[0][tid] + part[1][tid]);
+}
+
 }  // namespace
 
 int64_t dense_ldl_tiles_doubles(int64_t n_unpadded) {
@@ -2537,6 +2609,24 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
   return BA_OK;
 }
 
+// m right-hand sides through the factor at once (see k_fwd_step_multi): column c at d_B + c ld, overwritten by its solution
+template <typename T>
+int dense_ldl_solve_multi(ba_problem *p, DenseLDLT<T> *w, T *d_B, int64_t ld, int m, T *d_y, hipStream_t st) {
+  const int nt = (int)w->nt;
+  if (m <= 0) return BA_OK;
+  if (w->own_only || p->comm.active() || ld < w->n) {
+    ba_set_error("multi-right-hand-side solve: one rank holding all of S, column stride >= the padded order");
+    return BA_ERR_ARG;
+  }
+  ProfScope ps(p, PC_SHARED_SWEEP, st);
+  for (int k = 0; k < nt; k++)
+    hipLaunchKernelGGL(k_fwd_step_multi<T>, dim3(nt - k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_B, d_y, k, ld);
+  for (int k = nt - 1; k >= 0; k--)
+    hipLaunchKernelGGL(k_bwd_step_multi<T>, dim3(1 + k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, d_y, d_B, k, ld);
+  BA_HIP_CHECK(hipGetLastError());
+  return BA_OK;
+}
+
 // ---- C ABI: standalone dense solve (tests, roofline measurement) --------------------------------------------------------
 template <typename T>
 static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x,
@@ -2606,6 +2696,64 @@ extern "C" int ba_dense_ldl_solve_f32(int device, int64_t n, const double *a_low
   return dense_solve_host<float>(device, n, a_lower_rowmajor, b, x, factor_ms);
 }
 
+// one factorisation, then the multi-right-hand-side sweeps over all nrhs columns (B and X: n x nrhs, column-major)
+extern "C" int ba_dense_ldl_solve_multi(int device, int64_t n, const double *a_lower_rowmajor, int nrhs, const double *B, double *X,
+                                        double *factor_ms) {
+  if (n <= 0 || nrhs <= 0 || !a_lower_rowmajor || !B || !X) {
+    ba_set_error("ba_dense_ldl_solve_multi: bad argument");
+    return BA_ERR_ARG;
+  }
+  BA_HIP_CHECK(hipSetDevice(device));
+  ba_problem tmp;  // only used for its (disabled) profiling slots
+  DenseLDL w;
+  BA_CHECK(dense_ldl_alloc<double>(&w, n));
+  const int64_t npad = w.n;
+  std::vector<double> tiles((size_t)dense_ldl_tiles_doubles(n), 0.0);
+  for (int64_t i = 0; i < npad; i++) {
+    const int64_t ti = i / NB;
+    for (int64_t j = 0; j <= i; j++) {
+      const int64_t tj = j / NB;
+      const double v = (i < n) ? a_lower_rowmajor[i * n + j] : (i == j ? 1.0 : 0.0);
+      tiles[(size_t)((tix(w.hco(), ti, tj) * NB + (i - ti * NB)) * NB + (j - tj * NB))] = v;
+    }
+  }
+  std::vector<double> bb((size_t)(npad * nrhs), 0.0);
+  for (int c = 0; c < nrhs; c++)
+    for (int64_t i = 0; i < n; i++) bb[(size_t)(c * npad + i)] = B[(int64_t)c * n + i];
+  DevBuf<double> d_b, d_y;
+  hipStream_t st = nullptr;
+  HipEvent e0, e1;
+  BA_CHECK(d_b.alloc(npad * nrhs));
+  BA_CHECK(d_y.alloc(npad * nrhs));
+  BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice));
+  BA_CHECK(e0.create());
+  BA_CHECK(e1.create());
+  int rc = BA_OK, zp = 0;
+  for (int attempt = 0; attempt < 2; attempt++) {  // (as ba_dense_ldl_solve: once more in order when a hoisted kernel gave up)
+    BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice));
+    BA_HIP_CHECK(hipEventRecord(e0, st));
+    rc = dense_ldl_factor<double>(&tmp, &w, st, (double *)nullptr);
+    BA_HIP_CHECK(hipEventRecord(e1, st));
+    BA_HIP_CHECK(hipMemcpy(&zp, w.flag, sizeof(int), hipMemcpyDeviceToHost));
+    BA_HIP_CHECK(hipDeviceSynchronize());
+    if (zp != 2 || w.hoist_disabled) break;
+    w.hoist_disabled = true;
+  }
+  if (rc == BA_OK && !zp) rc = dense_ldl_solve_multi<double>(&tmp, &w, d_b, npad, nrhs, d_y, st);
+  BA_HIP_CHECK(hipDeviceSynchronize());
+  float ms = 0;
+  BA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  if (factor_ms) *factor_ms = ms;
+  BA_HIP_CHECK(hipMemcpy(bb.data(), d_b, bb.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int c = 0; c < nrhs; c++)
+    for (int64_t i = 0; i < n; i++) X[(int64_t)c * n + i] = bb[(size_t)(c * npad + i)];
+  if (rc == BA_OK && zp) {
+    ba_set_error("dense LDL': exactly zero pivot");
+    return BA_ERR_ZERO_PIVOT;
+  }
+  return rc;
+}
+
 template int dense_ldl_alloc<double>(DenseLDLT<double> *, int64_t, int, int, bool, bool);
 template int dense_ldl_alloc<float>(DenseLDLT<float> *, int64_t, int, int, bool, bool);
 template int dense_ldl_alloc_S<double>(DenseLDLT<double> *);
@@ -2618,3 +2766,4 @@ template int dense_ldl_factor_dist<double>(ba_problem *, DenseLDLT<double> *, hi
 template int dense_ldl_factor_dist<float>(ba_problem *, DenseLDLT<float> *, hipStream_t, float *);
 template int dense_ldl_solve<double>(ba_problem *, DenseLDLT<double> *, double *, hipStream_t, bool);
 template int dense_ldl_solve<float>(ba_problem *, DenseLDLT<float> *, float *, hipStream_t, bool);
+template int dense_ldl_solve_multi<double>(ba_problem *, DenseLDLT<double> *, double *, int64_t, int, double *, hipStream_t);

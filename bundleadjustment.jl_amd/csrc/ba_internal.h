@@ -200,6 +200,9 @@ enum ProfClass {
   PC_COV_CAMS,    // covariance: the cameras' 9 x 9 blocks (k_cov_cams)
   PC_COV_POINTS,  // covariance: the points' 3 x 3 blocks (k_cov_points)
   PC_PRIOR,       // Gaussian priors (ba_lm_set_priors): k_prior_*_lin at a linearisation, k_prior_*_rhs per linear step, k_prior_*_step per trial step
+  PC_SHARED_BORDER,  // shared intrinsics (ba_lm_set_shared_intrinsics): the border product S E_g, its E' reductions, the masking of S and the E' reductions / expansions of vectors
+  PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step_multi / k_bwd_step_multi; also ba_dense_ldl_solve_multi)
+  PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -334,6 +337,17 @@ struct ba_problem {
   double *pri_cost() const { return pri_val; }
   double *pri_cost_trial() const { return pri_val + pri_total(); }
   double *pri_model() const { return pri_val + 2 * pri_total(); }
+  // shared intrinsics of the LM entries (ba_lm_set_shared_intrinsics): the labels as kept (0 = own; groups with one member
+  // dropped, the others renumbered 1..grp_n in the order of their labels), the members of every group in ascending camera
+  // order (h_grp_mem[h_grp_ptr[g] .. h_grp_ptr[g + 1]), 0-based cameras; the first is the member that carries the group's
+  // entries of the z vector), and their device copies in camera order (uploaded lazily, shared_upload): grp_ptr, grp_row =
+  // 9 camera + 6 of every member.  grp_version counts the changes (the LM workspace keeps tables in the order of S).
+  std::vector<int> h_grp, h_grp_ptr, h_grp_mem;
+  int grp_n = 0;
+  int64_t grp_version = 0;
+  bool grp_dirty = false;
+  DevBuf<int> grp_ptr, grp_row;
+  bool grp_on() const { return grp_n > 0; }
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;
@@ -405,6 +419,11 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat);
 // solve S x = b for one right-hand side held in d_b (length nt*NB, overwritten by x)
 template <typename T>
 int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool forward_done);
+
+// the factor applied to m right-hand sides at once (one GPU, dense or block-sparse S): column c of d_B (ld = its stride, >= nt NB)
+// is overwritten by S^-1 of it; d_y: m * ld elements of scratch.  Forward and backward sweeps, nt launches each.
+template <typename T>
+int dense_ldl_solve_multi(ba_problem *p, DenseLDLT<T> *w, T *d_B, int64_t ld, int m, T *d_y, hipStream_t st);
 
 // ---- transport (ba_comm.hip): all on stream st, in place, no-ops without a communicator --------------------
 int comm_allreduce(ba_problem *p, double *d_buf, int64_t count, hipStream_t st);

@@ -267,6 +267,13 @@ struct LMWork {
   DevBuf<double> cgh, zero3, blk45, cg_scal;
   PinnedBuf<double> h_cg;
   DevBuf<double> rob_partial;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
+  // shared intrinsics (ba_lm_set_shared_intrinsics).  Direct path: the grouping's tables in the order of S (grp_row:
+  // the row of k1 of every member, grp_col: per row of S the column of z it belongs to or -1), made for grp_made_for =
+  // ba_problem::grp_version; the border B, Y = A^-1 B and the sweeps' scratch (24 columns of npad each), the small systems.
+  // :PCG: cge, the expanded direction.  All allocated on first use.
+  int64_t grp_made_for = -1;
+  DevBuf<int> grp_row, grp_col;
+  DevBuf<double> bord_B, bord_Y, bord_w, bord_small, cge;
   RecordedSequences rec;
 };
 
@@ -678,6 +685,33 @@ static int ensure_dense(ba_problem *p, LMWork *w) {
   return BA_OK;
 }
 
+// shared intrinsics, direct path: the grouping's tables in the order of S and the border buffers
+static int ensure_shared_direct(ba_problem *p, LMWork *w) {
+  if (!p->grp_on() || w->grp_made_for == p->grp_version) return BA_OK;
+  std::vector<int> pos;  // block row of a camera
+  if (!w->h_cam_perm.empty()) {
+    pos.resize(w->h_cam_perm.size());
+    for (size_t k = 0; k < pos.size(); k++) pos[(size_t)w->h_cam_perm[k]] = (int)k;
+  }
+  std::vector<int> row(p->h_grp_mem.size()), col((size_t)w->npad, -1);
+  for (int g = 0; g < p->grp_n; g++)
+    for (int m = p->h_grp_ptr[(size_t)g]; m < p->h_grp_ptr[(size_t)g + 1]; m++) {
+      const int c = p->h_grp_mem[(size_t)m];
+      row[(size_t)m] = 9 * (pos.empty() ? c : pos[(size_t)c]) + 6;
+      for (int q = 0; q < 3; q++) col[(size_t)(row[(size_t)m] + q)] = 3 * g + q;
+    }
+  BA_CHECK(upload(w->grp_row, row));
+  BA_CHECK(upload(w->grp_col, col));
+  if (!w->bord_small) {
+    BA_CHECK(w->bord_B.alloc(24 * w->npad));
+    BA_CHECK(w->bord_Y.alloc(24 * w->npad));
+    BA_CHECK(w->bord_w.alloc(24 * w->npad));
+    BA_CHECK(w->bord_small.alloc(SHARED_SMALL_DOUBLES));
+  }
+  w->grp_made_for = p->grp_version;
+  return BA_OK;
+}
+
 void lm_free(ba_problem *p) {
   delete p->lm;
   p->lm = nullptr;
@@ -732,6 +766,9 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
   // priors (ba_lm_set_priors): their terms into the diagonal blocks and the gradient, before anything reads either
   BA_CHECK(launch_prior_lin(p, w->x, w->Hpp, w->gp, w->Hcc, w->gc, st));
+  // shared intrinsics: the gradient over z -- a group's sum at its first member, exact zeros at the others (nothing but the
+  // gradient output and its norm reads gc)
+  if (p->grp_on()) BA_CHECK(launch_grp_reduce(p, p->grp_ptr, p->grp_row, w->gc, st));
   // gc, the diagonal of the camera block (the column scalings need the global one) and the linearisation scalars are
   // adjacent in the reduce buffer (lm_ensure): one all-reduce
   BA_CHECK(launch_hcc_diag(p, w->Hcc, w->hdiag, st));
@@ -793,6 +830,17 @@ static int ensure_pcg(ba_problem *p, LMWork *w) {
   return BA_OK;
 }
 
+// shared intrinsics: q = (E'(S_full - lambda I)E + lambda I) v for v over z: expand, the product without damping, reduce, damp
+static int pcg_matvec_shared(ba_problem *p, LMWork *w, double lambda, const double *v, double *q, hipStream_t st) {
+  BA_HIP_CHECK(hipMemcpyAsync(w->cge, v, (size_t)w->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  BA_CHECK(launch_grp_expand(p, p->grp_ptr, p->grp_row, w->cge, st));
+  if (p->point_sorted) BA_CHECK(launch_wtv(p, w->J, w->Uinv, w->cge, w->cgh, st));
+  else BA_CHECK(launch_backsub(p, w->J, w->Uinv, w->zero3, w->cge, w->cgh, st));
+  BA_CHECK(launch_wuw(p, w->J, w->cgh, w->Hcc, w->cge, 0.0, q, st, w->cam_pnt));
+  BA_CHECK(launch_grp_reduce(p, p->grp_ptr, p->grp_row, q, st));
+  return launch_axpy_s(p, w->n, lambda, v, q, st);
+}
+
 // q = S v: the point sweep, then the camera sweep (which adds Hcc v and, on one rank, the damping); on several ranks the
 // partial products are summed by one all-reduce and every rank adds the damping to the full sum
 static int pcg_matvec(ba_problem *p, LMWork *w, double lambda, const double *v, double *q, hipStream_t st) {
@@ -820,6 +868,11 @@ static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   BA_HIP_CHECK(hipMemsetAsync(w->ldl.flag, 0, sizeof(int), st));
   BA_CHECK(launch_schur_diag(p, w->J, w->Uinv, w->Hcc, w->blk45, st));
   BA_CHECK(comm_allreduce(p, w->blk45, 45 * p->ncams, st));
+  const bool shared = p->grp_on();  // shared intrinsics: the system over z, its vectors in the x layout (zeros at non-first members)
+  if (shared) {
+    if (!w->cge) BA_CHECK(w->cge.alloc(w->npad));
+    BA_CHECK(launch_grp_blk45(p, w->blk45, st));
+  }
   BA_CHECK(launch_pcg_factor(p, lambda, w->blk45, w->ldl.flag, st));  // a block that is not positive definite -> SQDException
   BA_HIP_CHECK(hipMemsetAsync(w->cgx, 0, (size_t)n * sizeof(double), st));
   BA_HIP_CHECK(hipMemcpyAsync(w->cgr, w->rhs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -830,7 +883,7 @@ static int pcg_solve(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   int it = 0;
   if (b2 > 0 && w->h_cg[2] == w->h_cg[2]) {
     for (it = 1; it <= maxit; it++) {
-      BA_CHECK(pcg_matvec(p, w, lambda, w->cgp, w->cgq, st));
+      BA_CHECK(shared ? pcg_matvec_shared(p, w, lambda, w->cgp, w->cgq, st) : pcg_matvec(p, w, lambda, w->cgp, w->cgq, st));
       BA_CHECK(launch_cg_alpha(p, n, w->cgp, w->cgq, w->cg_scal, st));
       BA_CHECK(launch_cg_step(p, w->cg_scal, w->blk45, w->cgp, w->cgq, w->cgx, w->cgr, w->cgz, w->cgt, 0, st));
       BA_CHECK(launch_cg_beta_dir(p, n, w->cgt, w->cg_scal, w->cgz, w->cgp, 0, st));
@@ -876,9 +929,11 @@ static int pcg_step(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
   BA_CHECK(launch_schur_rhs(p, w->J_lin(), w->r_lin(), w->u, w->rhs, st, w->cam_pnt));
   BA_CHECK(launch_prior_rhs(p, w->rhs, nullptr, st));  // - H'Lambda d of the camera and centre priors
   BA_CHECK(comm_allreduce(p, w->rhs, w->npad, st));
+  if (p->grp_on()) BA_CHECK(launch_grp_reduce(p, p->grp_ptr, p->grp_row, w->rhs, st));  // E' rhs
   BA_CHECK(pcg_solve(p, w, lambda, st));
   double *dcp = w->delta + 3 * p->npnts;
   BA_HIP_CHECK(hipMemcpyAsync(dcp, w->rhs, (size_t)w->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (p->grp_on()) BA_CHECK(launch_grp_expand(p, p->grp_ptr, p->grp_row, dcp, st));  // dx = E dz
   return launch_backsub(p, w->J_lin(), w->Uinv, w->u, dcp, w->delta, st, w->r_lin(), w->cr0(), w->partial, w->scal, SH_MODEL,
                         &w->model_done);
 }
@@ -1013,6 +1068,13 @@ static int linear_step(ba_problem *p, LMWork *w, double lambda, bool recorded, h
   BA_CHECK(launch_prior_rhs(p, w->rhs, w->tasks.pos, st));  // - H'Lambda d of the camera and centre priors
   BA_CHECK(w->ldl.own_only ? comm_allreduce(p, w->rhs, w->npad, st) : reduce_camera_system(p, w, st, reduce32));
   if (normalize) BA_CHECK(scale_columns(p, w, lambda, d_lambda, st));
+  // shared intrinsics (one rank, Float64, no column scaling, never recorded: all refused or excluded before): the bordered
+  // solve.  From S_full: the border B = S_full E_g without its member rows, C and rhs_y; S and rhs masked in place to A and rhs_a
+  const bool shared = p->grp_on();
+  if (shared) {
+    BA_CHECK(launch_border_prepare(p, &w->ldl, w->n, lambda, w->grp_row, w->grp_col, w->bord_B, w->rhs, w->bord_small, st));
+    BA_HIP_CHECK(hipMemcpyAsync(w->bord_Y, w->bord_B, (size_t)(3 * p->grp_n) * w->npad * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
   if (m.facto_f32) {  // round the assembled system to Float32, factor and solve there, widen the solution
     BA_CHECK(ensure_f32(w));
     if (!reduce32) BA_CHECK(launch_convert(w->ldl.S, w->ldl32.S, w->ldl.s_tiles * NB * NB, st));
@@ -1021,6 +1083,10 @@ static int linear_step(ba_problem *p, LMWork *w, double lambda, bool recorded, h
     BA_CHECK(launch_convert(w->rhs32, w->rhs, w->npad, st));
   } else {
     BA_CHECK(factor_solve<double>(p, &w->ldl, w->rhs, dist, st));
+  }
+  if (shared) {  // Y = A^-1 B in one pair of sweeps, then T = C - B'Y, y = T^-1 (rhs_y - B'a0) and the camera step a0 - Y y + E_g y
+    BA_CHECK(dense_ldl_solve_multi<double>(p, &w->ldl, w->bord_Y, w->npad, 3 * p->grp_n, w->bord_w, st));
+    BA_CHECK(launch_border_finish(p, &w->ldl, w->grp_col, w->bord_B, w->bord_Y, w->rhs, w->bord_small, st));
   }
   return step_from_solution(p, w, normalize, st);
 }
@@ -1136,7 +1202,7 @@ static RecordedFor recorded_for(ba_problem *p, LMWork *w) {
 static bool recorded_current(ba_problem *p, LMWork *w) { return w->rec.made_for == recorded_for(p, w); }
 
 static bool graphs_allowed(ba_problem *p, LMWork *w) {
-  if (w->rec.off || p->prof_on || p->comm.active() || w->mode.f16 || w->mode.pcg) return false;  // per-kernel events / communicator / Float16 path
+  if (w->rec.off || p->prof_on || p->comm.active() || w->mode.f16 || w->mode.pcg || p->grp_on()) return false;  // per-kernel events / communicator / Float16 path
   // the hoisted-diagonal schedule of large factorisations has a kernel wait for a flag raised by a kernel running
   // beside it: only with real streams is that concurrency certain (and the graphs gain nothing at that size)
   // (the block-sparse list schedule never hoists and is bound by its chain of short launches: recorded at any size)
@@ -1236,10 +1302,22 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
     ba_set_error("ba_lm_step: priors (ba_lm_set_priors) are not supported on a handle with a communicator");
     return BA_ERR_ARG;
   }
+  if (p->grp_on()) {  // shared intrinsics: what the step is not carried through, and what it asks of x and the mask
+    if (p->comm.active()) {
+      ba_set_error("ba_lm_step: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported on a handle with a communicator");
+      return BA_ERR_ARG;
+    }
+    if (facto_f32) {
+      ba_set_error("ba_lm_step_f32: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with facto_type = Float32");
+      return BA_ERR_ARG;
+    }
+    BA_CHECK(shared_check(p, x + 3 * p->npnts, "ba_lm_step"));
+  }
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
   BA_CHECK(fix_upload(p));
   BA_CHECK(prior_upload(p));
+  BA_CHECK(shared_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   StepMode mode;
@@ -1250,6 +1328,7 @@ static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *d
   w->mode = mode;
   w->n_cg = 0;
   if (!pcg) BA_CHECK(ensure_dense(p, w));
+  if (!pcg) BA_CHECK(ensure_shared_direct(p, w));
   BA_HIP_CHECK(hipMemcpyAsync(w->x, x, (size_t)w->nvar * sizeof(double), hipMemcpyHostToDevice, st));
   BA_CHECK(refresh_linearisation(p, w, true, false, st));
   // same fallback as the LM loop: a hoisted diagonal kernel that gave up -> in-order schedule, redo the step
@@ -1373,6 +1452,10 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   }
   if (p->comm.active()) {
     ba_set_error("ba_covariance: one rank only (a communicator is attached to this handle)");
+    return BA_ERR_ARG;
+  }
+  if (p->grp_on()) {
+    ba_set_error("ba_covariance: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported (clear the grouping)");
     return BA_ERR_ARG;
   }
   const double tol = rank_tol < 0 ? 1e-10 : rank_tol;
@@ -1540,6 +1623,28 @@ static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
       return BA_ERR_ARG;
     }
   }
+  if (p->grp_on()) {  // shared intrinsics (ba_lm_set_shared_intrinsics): the combinations the bordered solve is not carried through
+    if (p->comm.active()) {
+      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported on a handle with a communicator");
+      return BA_ERR_ARG;
+    }
+    if (o->x_f32) {
+      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported for a Float32 model (x_f32 = 1)");
+      return BA_ERR_ARG;
+    }
+    if (o->variant == 1 && o->facto_type != 0) {
+      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with facto_type = Float32 or Float16");
+      return BA_ERR_ARG;
+    }
+    if (o->normalize != 0) {
+      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with normalize = :J or :A");
+      return BA_ERR_ARG;
+    }
+    if (o->variant == 1 && o->linesearch) {
+      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with linesearch = true");
+      return BA_ERR_ARG;
+    }
+  }
   return BA_OK;
 }
 
@@ -1555,6 +1660,15 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
   BA_CHECK(fix_upload(p));
   BA_CHECK(prior_upload(p));
+  BA_CHECK(shared_upload(p));
+  if (p->grp_on()) {  // the members of a group must enter bit-identical (and agree in the mask)
+    std::vector<double> xc((size_t)(9 * p->ncams));
+    if (x_on_device) {
+      BA_HIP_CHECK(hipMemcpyAsync(xc.data(), x_inout + 3 * p->npnts, xc.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+      BA_HIP_CHECK(hipStreamSynchronize(p->stream));
+    }
+    BA_CHECK(shared_check(p, x_on_device ? xc.data() : x_inout + 3 * p->npnts, "ba_lm_solve"));
+  }
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   const int V = o->variant;
@@ -1573,6 +1687,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   if (mode.f16) BA_CHECK(ensure_f16(p, w));
   w->n_cg = 0;
   if (!mode.pcg) BA_CHECK(ensure_dense(p, w));  // (here, not in linear_step: no allocation while a graph is being recorded)
+  if (!mode.pcg) BA_CHECK(ensure_shared_direct(p, w));
   // Scalars carry the width Julia's promotion rules give them (TS: value + 32 | 64).  For a Float64 model everything is
   // a Float64 and the arithmetic below is plain double arithmetic.  For eltype(x) = Float32 (src/lm.jl:20-26,36-59):
   // norm() of a Float32 vector, obj = norm_r^2 / 2, pred, ared, rho are Float32; the eps(Float32)-derived default

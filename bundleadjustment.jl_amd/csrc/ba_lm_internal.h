@@ -180,6 +180,23 @@ int prior_upload(ba_problem *p);
 int launch_prior_lin(ba_problem *p, const double *d_x, double *d_Hpp, double *d_gp, double *d_Hcc, double *d_gc, hipStream_t st);
 int launch_prior_step(ba_problem *p, const double *d_delta, const double *d_xt, hipStream_t st);
 int launch_prior_rhs(ba_problem *p, double *d_rhs, const int *d_pos, hipStream_t st);
+// shared intrinsics (ba_shared_kernels.hip): the handle's grouping to the device when it changed
+// (ba_lm_set_shared_intrinsics); shared_check: what a step or solve refuses about x and the mask (xc: the camera part of x on the
+// host).  launch_grp_reduce / _expand: v <- E'v / E v in place on an x-layout camera vector; d_row: the index of k1 of every
+// member in v (p->grp_row in camera order, the workspace's table in the order of S).  launch_grp_blk45: the z-blocks of the
+// :PCG preconditioner.  launch_border_prepare: from the assembled S_full and rhs (order of S): B (3G columns of stride npad),
+// C and rhs_y -> d_small, then S and rhs masked in place (A, rhs_a).  launch_border_finish: from a0 (in d_a) and Y = A^-1 B the
+// camera step a + E_g y, in place; a non-positive pivot of T raises l->flag.  d_small: 2 * 25 * 24 doubles.
+constexpr int SHARED_SMALL_DOUBLES = 2 * 25 * 24;
+int shared_upload(ba_problem *p);
+int shared_check(const ba_problem *p, const double *xc, const char *who);
+int launch_grp_reduce(ba_problem *p, const int *d_gptr, const int *d_row, double *d_v, hipStream_t st);
+int launch_grp_expand(ba_problem *p, const int *d_gptr, const int *d_row, double *d_v, hipStream_t st);
+int launch_grp_blk45(ba_problem *p, double *d_blk45, hipStream_t st);
+int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double lambda, const int *d_row, const int *d_col, double *d_B,
+                          double *d_rhs, double *d_small, hipStream_t st);
+int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, const double *d_B, const double *d_Y, double *d_a,
+                         double *d_small, hipStream_t st);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,

@@ -48,6 +48,18 @@ class GenericExecutionStats:
                 f"  iterations: {self.iter}\n  elapsed time: {self.elapsed_time!r}")
 
 
+def _check_tied(x, npnts, labels):
+    """ValueError when the members of a group do not hold identical (k1, k2, f) in x (labels: _lib.shared_labels or None)"""
+    if labels is None:
+        return
+    tied = _lib.tie_intrinsics(x, npnts, labels)
+    bad = np.flatnonzero((tied.view(np.int64) != np.ascontiguousarray(x, dtype=np.float64).view(np.int64))[3 * npnts:])
+    if bad.size:
+        c = int(bad[0]) // 9
+        raise ValueError(f"shared_intrinsics: camera {c + 1} holds other (k1, k2, f) than the first member of its group "
+                         f"{int(labels[c])}: the members of a group must be identical in x (see tie_intrinsics)")
+
+
 def _sym(s):
     return s[1:] if isinstance(s, str) and s.startswith(":") else s
 
@@ -57,7 +69,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
                         nu_d=None, nu_m=None, lam=None, delta_d=None, ite_max=None, max_time=None, verbose=False,
                         log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0,
                         fixed_cameras=None, fixed_points=None, fixed_camera_params=None, point_priors=None,
-                        camera_priors=None, centre_priors=None):
+                        camera_priors=None, centre_priors=None, shared_intrinsics=None):
     """x_device_ptr (an extension for device-resident callers, e.g. bench.py): the address of nvar doubles of DEVICE memory
     holding x0; the loop then runs through ba_lm_solve_dev -- no host copy of the iterate on either side -- the solution
     stays there and `solution` of the result is None.
@@ -78,7 +90,23 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     control points, calibration priors or an earlier solve's posterior, GPS positions (see _lib._prior_lists for the forms and
     ba_lm_set_priors in include/ba_hip.h for the semantics).  `objective`, the log's f and |J'r| include them; they are not
     passed through the robust loss.  Set on the handle at every call: a call without them runs the path without priors.  Not
-    with linesearch = True, a Float32 model or facto_type = Float16 (ValueError)."""
+    with linesearch = True, a Float32 model or facto_type = Float16 (ValueError).
+
+    shared_intrinsics (an extension): calibration groups -- cameras that share one (k1, k2, f), estimated from all their
+    images: an array of ncams labels (0: own intrinsics, g in 1..8: member of group g) or a list of lists of 1-based camera
+    indices (see _lib.shared_labels for the forms and ba_lm_set_shared_intrinsics in include/ba_hip.h for the semantics).  The
+    members of a group must hold identical (k1, k2, f) in x0 (tie_intrinsics makes such an x) and come back identical;
+    dual_feas and the log's |J'r| are the gradient over the tied parameters.  Set on the handle at every call: a call without
+    it runs the untied path.  Not with facto_type = Float32 / Float16, a Float32 model, normalize :J / :A or linesearch = True
+    (ValueError)."""
+    tied = _lib.check_shared(shared_intrinsics)
+    if tied:
+        if linesearch:
+            raise ValueError("shared_intrinsics is not supported with linesearch = true")
+        if facto_type is not None and np.dtype(facto_type) != np.dtype(np.float64):
+            raise ValueError("shared_intrinsics is not supported with facto_type = Float32 or Float16")
+        if _sym(normalize) in ("J", "A"):
+            raise ValueError("shared_intrinsics is not supported with normalize = :J or :A")
     kind, c = _lib.loss_code(loss, f_scale)
     if kind != 0 and linesearch:
         raise ValueError("a robust loss is not supported with linesearch = true")
@@ -103,6 +131,9 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     xf32 = nlp.T is np.float32  # eltype(x) = Float32: facto_type defaults to it (lm.jl:20), eps(T) tolerances
     if with_priors and xf32:
         raise ValueError("priors are not supported for a Float32 model")
+    if tied and xf32:
+        raise ValueError("shared_intrinsics is not supported for a Float32 model (x_f32)")
+    labels = _lib.shared_labels(shared_intrinsics, nlp.ncams)
     variant = 0 if linesearch is None else 1
     if variant == 0 and (facto_type is not None or max_time is not None):
         raise TypeError("LevenbergMarquardt.jl's Levenberg_Marquardt has no facto_type / max_time keyword")
@@ -111,6 +142,8 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     x0 = None if x_device_ptr is not None else np.array(nlp.meta.x0 if x is None else x, dtype=np.float64, copy=True)
     if x0 is not None and x0.shape != (nlp.meta.nvar,):
         raise ValueError("x has the wrong length")
+    if x0 is not None:
+        _check_tied(x0, nlp.npnts, labels)
     if facto_type is not None and np.dtype(facto_type) not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.float16)):
         raise TypeError("facto_type must be Float64, Float32 or Float16")
     # ba_lm_opts.facto_type: 0 = eltype(x), 1 = Float32, 2 = Float16 (src/lm.jl:165-173)
@@ -147,6 +180,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))  # every call: one without loss= runs the plain objective
     _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)  # ... and one without fixed_* the unmasked path
     _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)  # ... and without *_priors none
+    _lib.set_shared(nlp.handle, labels)  # ... and without shared_intrinsics no grouping
     if x_device_ptr is not None:
         _lib.check(_lib.lib().ba_lm_solve_dev(nlp.handle, C.byref(o), C.c_void_p(int(x_device_ptr)), C.byref(st), cb, None))
     else:
@@ -167,21 +201,30 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
 
 
 def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0, fixed_cameras=None,
-            fixed_points=None, fixed_camera_params=None, point_priors=None, camera_priors=None, centre_priors=None):
+            fixed_points=None, fixed_camera_params=None, point_priors=None, camera_priors=None, centre_priors=None,
+            shared_intrinsics=None):
     """One linear LM step from (x, lambda): delta, 1/2|J delta + r|^2, J'r  (ba_lm_step; facto_type=np.float32:
     ba_lm_step_f32, the reduced camera system factored in Float32 as src/lm.jl:170-173 does; pcg=(tol, max_iter):
     ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result).
     loss / f_scale (see Levenberg_Marquardt; None = "linear"): the reweighted step, 1/2|J~ delta + r~|^2 and J~'r~.
     fixed_* (see Levenberg_Marquardt): the step over the free entries; the fixed entries of delta and J'r are exactly 0.
-    *_priors (see Levenberg_Marquardt): the step of the objective with the prior terms; they are in all three outputs."""
+    *_priors (see Levenberg_Marquardt): the step of the objective with the prior terms; they are in all three outputs.
+    shared_intrinsics (see Levenberg_Marquardt): the step over the tied parameters, expanded to the layout of x (the members of
+    a group receive identical steps); J'r holds a group's summed gradient at its first member and exact zeros at the other
+    members' (k1, k2, f).  Not with facto_type = Float32 (ValueError)."""
     kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
     _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
     _lib.check_priors(point_priors, camera_priors, centre_priors)
+    if _lib.check_shared(shared_intrinsics) and facto_type is not None and np.dtype(facto_type) != np.dtype(np.float64):
+        raise ValueError("shared_intrinsics is not supported with facto_type = Float32")
+    labels = _lib.shared_labels(shared_intrinsics, nlp.ncams)
     cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
     x = np.ascontiguousarray(x, dtype=np.float64)
+    _check_tied(x, nlp.npnts, labels)
     _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
     _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
     _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)
+    _lib.set_shared(nlp.handle, labels)
     delta = np.empty(nlp.meta.nvar)
     jtr = np.empty(nlp.meta.nvar) if want_jtr else None
     half = C.c_double(0)

@@ -13,6 +13,8 @@ import os
 
 import numpy as np
 
+from . import _lib
+
 # (ncams, npnts, nobs) of the configurations of BASELINE.json
 SHAPES = {
     "ladybug-49": (49, 7776, 31843),
@@ -85,7 +87,7 @@ def _cameras_in_the_plane(rng, ncams, npnts, nobs, radius):
     return pnt0, cam0[order]
 
 
-def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius=None):
+def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius=None, intrinsics_groups=None):
     """-> dict(cam_idx1, pnt_idx1, pt2d, x0, x_true, ncams, npnts, nobs) in the reference's conventions.
 
     plane_radius (None or a radius in the unit square): the cameras stand in the plane and a point is seen from one
@@ -96,7 +98,14 @@ def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius
     seen only by cameras of one window of round(w * ncams) consecutive cameras (window start uniform): cameras further
     apart than the window share no point, S is block-banded with half bandwidth w * ncams and its 9 x 9 block fill is
     about 2w - w^2 (schur_fill() measures it).  Real BAL problems lie in between (sequential captures: narrow band plus loop
-    closures); the default stays dense -- the worst case for the factorisation."""
+    closures); the default stays dense -- the worst case for the factorisation.
+
+    intrinsics_groups (None, or a grouping as Levenberg_Marquardt's shared_intrinsics takes it): the cameras of a group are one
+    physical device -- their true and initial (k1, k2, f) are those of the group's first member and pt2d is projected from
+    them.  The random draws are those of the default either way."""
+    labels = None
+    if intrinsics_groups is not None:
+        labels = _lib.shared_labels(intrinsics_groups, int(ncams))
     rng = np.random.default_rng(seed)
     # points in the unit ball
     g = rng.standard_normal((npnts, 3))
@@ -114,6 +123,8 @@ def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius
     k1 = -rng.uniform(0.0, 5.0, size=ncams) * 1e-7
     k2 = rng.uniform(0.0, 1.0, size=ncams) * 1e-12
     cams = np.column_stack([rvec, tvec, k1, k2, f])
+    if labels is not None:
+        cams = _lib.tie_intrinsics(cams.ravel(), 0, labels).reshape(ncams, 9)
     # observation graph
     if plane_radius is not None:
         if locality is not None:
@@ -147,6 +158,8 @@ def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius
     x_true = np.concatenate([pts.ravel(), cams.ravel()])
     pts0 = pts + rng.normal(0.0, 0.02, size=pts.shape)
     cams0 = cams * (1.0 + rng.normal(0.0, 1e-3, size=cams.shape))
+    if labels is not None:
+        cams0 = _lib.tie_intrinsics(cams0.ravel(), 0, labels).reshape(ncams, 9)
     x0 = np.concatenate([pts0.ravel(), cams0.ravel()])
     return dict(cam_idx1=cam0 + 1, pnt_idx1=pnt0 + 1, pt2d=np.ascontiguousarray(pt2d), x0=x0, x_true=x_true,
                 ncams=int(ncams), npnts=int(npnts), nobs=int(nobs))

@@ -356,6 +356,39 @@ int ba_lm_get_priors(const ba_problem *p, int64_t *n_pnt, int64_t *n_cam, int64_
 int ba_prior_eval(ba_problem *p, const double *x, double *cost /* or NULL */,
                   double *chi2_pnt, double *chi2_cam, double *chi2_ctr /* d'Lambda d per prior, each may be NULL */);
 
+/* ---- shared camera intrinsics: calibration groups (an extension: every camera of the reference has its own k1, k2, f) ----
+ * One physical camera takes many images: a grouping gives every camera a label, 0 = its own intrinsics, g in 1..G (G <= 8) =
+ * member of group g, which shares (k1, k2, f) with the group's other members.  A group with one member is dropped when the
+ * grouping is set (it behaves as label 0).  With z = x without the intrinsics of every non-first member ("first": the member
+ * with the lowest camera index) and x = E z, E copying a group's three values to all members, the LM entries minimise the
+ * handle's objective (1/2 |r|^2 or the robust f, plus the priors, at E z) over z: the step solves
+ * (E'HE + lambda I) dz = -E'g, H and g the Gauss-Newton matrix and gradient exactly as ba_lm_step forms them (reweighted,
+ * columns of fixed entries zeroed, prior terms added); the damping acts once per group parameter; dx = E dz.
+ * Every array keeps the layout of x:
+ *   x in     : the members of a group must hold bit-identical (k1, k2, f), else BA_ERR_ARG naming the first offending camera;
+ *   x out    : the members come back bit-identical (the same step added to the same value);
+ *   jtr, dual_feas, the log's |J'r| : the gradient over z -- a group's summed gradient at its first member's (k1, k2, f),
+ *              exactly 0 at the other members' (the convention of fixed entries);
+ *   |delta|, |x| of the small-step test : norms of the full x-layout vectors; half_sq_model, stats.objective : at dx = E dz;
+ *   fixed parameters : the mask bits of k1, k2, f must agree inside a group, else BA_ERR_ARG; a fixed shared component gets a
+ *              zero step and keeps its damping on the diagonal;
+ *   priors   : act on x = E z and reduce with E' like everything else: a calibration prior on one member is one on the group.
+ * :LDL / :QR (Float64) solve the reduced camera system over z as a bordered system: S is assembled as without a grouping, the
+ * 3G columns S E_g come from its tiles in one pass, the members' intrinsic rows and columns of S are replaced by the identity,
+ * that matrix is factored by the usual LDL' (handle's ordering, dense or block-sparse schedule), one multi-right-hand-side
+ * sweep applies it to the border, and a 3G x 3G Cholesky solve on the device closes the system (a non-positive pivot there:
+ * BA_ERR_ZERO_PIVOT).  :PCG applies E'(S - lambda I)E + lambda I by expand / product / reduce with z-blocks in its block-Jacobi
+ * preconditioner.  Such steps run unrecorded (no hipGraph replay).
+ * Refused (BA_ERR_ARG, the message names the combination): a communicator, facto_type Float32 or Float16, x_f32, normalize
+ * :J / :A, linesearch = 1, ba_covariance.  With no grouping set (or all labels 0) every entry runs exactly the launch sequence
+ * without one.
+ *   ba_lm_set_shared_intrinsics : the grouping of the handle's next LM steps and solves; group: ncams labels, NULL clears.
+ *                                 A negative label, a label above 8 or a gap in the labels (group g empty, a higher one not):
+ *                                 BA_ERR_ARG.  Host only; uploaded when a step or solve runs.
+ *   ba_lm_get_shared_intrinsics : the number of groups kept (two members or more) and of their members (either may be NULL). */
+int ba_lm_set_shared_intrinsics(ba_problem *p, const int32_t *group /* ncams; 0 = own, 1..G; NULL clears */);
+int ba_lm_get_shared_intrinsics(const ba_problem *p, int *n_groups, int64_t *n_members);
+
 /* ---- covariance at a solution (an extension: the reference has none) ------------------------------------------------
  * At x, under the handle's loss (ba_lm_set_loss) and mask (ba_lm_set_fixed):  Sigma = (J~_F' J~_F + lambda I)^-1, J~ the
  * Jacobian exactly as ba_lm_step sees it (reweighted under a robust loss, the columns of the fixed entries zeroed), F the free
@@ -400,6 +433,12 @@ int ba_dense_ldl_solve(int device, int64_t n, const double *a_lower_rowmajor, co
  * facto_type = Float32 does to the reduced camera system; src/lm.jl:170-173 does it to the augmented matrix) */
 int ba_dense_ldl_solve_f32(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x,
                            double *factor_ms);
+
+/* the same matrix against nrhs right-hand sides: ONE factorisation, then forward and backward sweeps that take all columns
+ * through every tile of the factor together (a chain of nt launches each way, whatever nrhs is) -- what the bordered solve of
+ * shared intrinsics runs on its 3G <= 24 border columns.  B and X: n x nrhs, column-major (X may be B) */
+int ba_dense_ldl_solve_multi(int device, int64_t n, const double *a_lower_rowmajor, int nrhs,
+                             const double *B /* n x nrhs, column-major */, double *X, double *factor_ms);
 
 #ifdef __cplusplus
 }

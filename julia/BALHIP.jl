@@ -77,3 +77,26 @@ end
 
 # BA_ST_* -> the status symbols of src/lm.jl:391-405 (index = code + 1)
 const BA_STATUS = (:small_step, :first_order, :small_residual, :acceptable, :neg_pred, :exception, :max_iter)
+
+# shared camera intrinsics (an extension): include/ba_hip.h, ba_lm_set_shared_intrinsics.  `group`: nothing (clears the grouping)
+# or ncams labels, 0 = the camera keeps its own (k1, k2, f), g in 1..8 = member of calibration group g.  The members of a group
+# must hold identical (k1, k2, f) in the x of the next solve.  Stays on the handle until it is set again.
+function set_shared_intrinsics(nlp, group)
+  if group === nothing
+    bacheck(ccall((:ba_lm_set_shared_intrinsics, libba), Cint, (Ptr{Cvoid}, Ptr{Int32}), nlp.handle, Ptr{Int32}(C_NULL)))
+    return nothing
+  end
+  length(group) == nlp.ncams || error("shared intrinsics: one label per camera ($(nlp.ncams)), got $(length(group))")
+  lab = collect(Int32, group)
+  GC.@preserve lab begin
+    bacheck(ccall((:ba_lm_set_shared_intrinsics, libba), Cint, (Ptr{Cvoid}, Ptr{Int32}), nlp.handle, pointer(lab)))
+  end
+  return nothing
+end
+
+"(groups, members) of the grouping the handle holds (ba_lm_get_shared_intrinsics)"
+function shared_intrinsics_counts(nlp)
+  g, m = Ref{Cint}(0), Ref{Int64}(0)
+  bacheck(ccall((:ba_lm_get_shared_intrinsics, libba), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), nlp.handle, g, m))
+  return Int(g[]), m[]
+end
