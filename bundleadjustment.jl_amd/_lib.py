@@ -464,6 +464,69 @@ def tie_intrinsics(x, npnts, shared_intrinsics):
     return x
 
 
+def _check_tied(x, npnts, labels):
+    """ValueError when the members of a group do not hold identical (k1, k2, f) in x (labels: shared_labels)"""
+    tied = tie_intrinsics(x, npnts, labels)
+    bad = np.flatnonzero((tied.view(np.int64) != np.ascontiguousarray(x, dtype=np.float64).view(np.int64))[3 * npnts:])
+    if bad.size:
+        c = int(bad[0]) // 9
+        raise ValueError(f"shared_intrinsics: camera {c + 1} holds other (k1, k2, f) than the first member of its group "
+                         f"{int(labels[c])}: the members of a group must be identical in x (see tie_intrinsics)")
+
+
+# the matrix of DESIGN §5h as Python sees it (the communicator and ba_covariance columns are the library's): per term the
+# attribute of ProblemTerms that says it is on, its name in a message, the uses it is not supported with in reporting order
+_REFUSED = (("tied", "shared_intrinsics is", ("linesearch", "facto_f32", "facto_f16", "normalize", "xf32")),
+            ("robust", "a robust loss is", ("linesearch", "xf32", "facto_f16")),
+            ("with_priors", "priors are", ("linesearch", "facto_f16", "xf32")),
+            ("masked", "fixed parameters are", ("facto_f16",)))
+
+
+class ProblemTerms:
+    """The optional terms of one LM call from its keywords: at construction the checks that need no problem size (ValueError
+    before anything touches a model or the device); refuse(): the options a term is not supported with; apply(): onto a handle."""
+
+    def __init__(self, loss="linear", f_scale=1.0, fixed_cameras=None, fixed_points=None, fixed_camera_params=None,
+                 point_priors=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
+        self.fixed = (fixed_cameras, fixed_points, fixed_camera_params)
+        self.priors = (point_priors, camera_priors, centre_priors)
+        self.shared, self.tied = shared_intrinsics, check_shared(shared_intrinsics)
+        self.kind, self.c = loss_code(loss, f_scale)
+        self.robust = self.kind != 0
+        self.with_priors = check_priors(*self.priors)
+        self.masked = check_fixed(*self.fixed)
+
+    def refuse(self, linesearch=False, facto_type=None, normalize="None", xf32=False):
+        """ValueError when a term that is on is not supported with one of these options"""
+        ft = facto_type if facto_type is None else np.dtype(facto_type)
+        uses = {"linesearch": (linesearch, "with linesearch = true"), "facto_f32": (ft == np.float32, "with facto_type = Float32"),
+                "facto_f16": (ft == np.float16, "with facto_type = Float16"), "xf32": (xf32, "for a Float32 model (x_f32)"),
+                "normalize": (normalize in ("J", "A", ":J", ":A"), "with normalize = :J or :A")}
+        for on, subject, refused in _REFUSED:
+            for use in refused:
+                if getattr(self, on) and uses[use][0]:
+                    raise ValueError(f"{subject} not supported {uses[use][1]}")
+
+    def set_loss(self, nlp):  # (alone: BALNLPModel.robust_weights, the rest of the handle stays)
+        check(lib().ba_lm_set_loss(nlp.handle, self.kind, self.c))
+
+    def set_priors(self, nlp):  # (alone: BALNLPModel.prior_eval)
+        set_priors(nlp.handle, nlp.ncams, nlp.npnts, *self.priors)
+
+    def apply(self, nlp, x=None, shared=True):
+        """Pack the terms for nlp's sizes (ValueError before the handle changes), check that x (if given) is tied as the grouping
+        asks, and set them on the handle: a term without its keyword is cleared.  shared=False leaves the handle's grouping."""
+        cam_mask, pnt_fixed = fixed_masks(nlp.ncams, nlp.npnts, *self.fixed)
+        labels = shared_labels(self.shared, nlp.ncams) if shared else None
+        if x is not None and labels is not None:
+            _check_tied(x, nlp.npnts, labels)
+        self.set_loss(nlp)
+        set_fixed(nlp.handle, cam_mask, pnt_fixed)
+        self.set_priors(nlp)
+        if shared:
+            set_shared(nlp.handle, labels)
+
+
 def dense_ldl_solve_multi(A, B, device=0):
     """Solve A X = B for the columns of B (n, nrhs) with ONE device LDL' and the multi-right-hand-side sweeps
     (ba_dense_ldl_solve_multi); only the lower triangle of A is read.  -> (X (n, nrhs), factor_ms)"""

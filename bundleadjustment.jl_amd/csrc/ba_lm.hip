@@ -1292,32 +1292,79 @@ static int accept_refresh_and_trial(LMWork *w, double lambda, hipStream_t st) {
   return BA_OK;
 }
 
+// ---- the optional terms of the LM problem: robust loss, fixed parameters, priors, shared intrinsics ---------------
+// What the terms ask of an entry before its first launch: the uses of the handle a term is not carried through (TERM_RULES,
+// check_terms), the device copies of their host tables (terms_upload), what a grouping asks of x (check_tied_x).
+enum TermCond { TC_LINESEARCH, TC_X_F32, TC_FACTO_F32, TC_FACTO_F16, TC_NORMALIZE, TC_COMM, TC_COVARIANCE, TC_COUNT };
+static const char *const TERM_COND_TEXT[TC_COUNT] = {
+    "with linesearch = true",    "for a Float32 model (x_f32 = 1)", "with facto_type = Float32",       "with facto_type = Float16",
+    "with normalize = :J or :A", "on a handle with a communicator", "by ba_covariance (clear it first)"};
+
+struct TermUse {  // how an entry is about to use the handle
+  const char *entry;
+  bool linesearch = false, x_f32 = false, facto_f32 = false, facto_f16 = false, normalize = false, comm = false, covariance = false;
+};
+
+struct TermRule {  // a row of the matrix of DESIGN §5h
+  const char *subject;             // the term and its setter, with the verb of the message
+  bool (*on)(const ba_problem *);  // is the term set on the handle?
+  TermCond refused[TC_COUNT + 1];  // the uses it is refused with, in the order they are reported; TC_COUNT ends the list
+};
+
+static const TermRule TERM_RULES[] = {
+    {"a robust loss (ba_lm_set_loss) is", [](const ba_problem *p) { return p->loss != BA_LOSS_LINEAR; },
+     {TC_LINESEARCH, TC_X_F32, TC_FACTO_F16, TC_COUNT}},
+    {"fixed parameters (ba_lm_set_fixed) are", [](const ba_problem *p) { return p->fix_on(); }, {TC_FACTO_F16, TC_COUNT}},
+    {"priors (ba_lm_set_priors) are", [](const ba_problem *p) { return p->pri_on(); },
+     {TC_LINESEARCH, TC_X_F32, TC_FACTO_F16, TC_COMM, TC_COUNT}},
+    {"shared intrinsics (ba_lm_set_shared_intrinsics) are", [](const ba_problem *p) { return p->grp_on(); },
+     {TC_COMM, TC_X_F32, TC_FACTO_F32, TC_FACTO_F16, TC_NORMALIZE, TC_LINESEARCH, TC_COVARIANCE, TC_COUNT}},
+};
+
+static int check_terms(const ba_problem *p, const TermUse &use) {
+  const bool is[TC_COUNT] = {use.linesearch, use.x_f32, use.facto_f32, use.facto_f16, use.normalize, use.comm, use.covariance};
+  for (const TermRule &t : TERM_RULES)
+    for (const TermCond *c = t.refused; t.on(p) && *c != TC_COUNT; c++)
+      if (is[*c]) {
+        ba_set_error("%s: %s not supported %s", use.entry, t.subject, TERM_COND_TEXT[*c]);
+        return BA_ERR_ARG;
+      }
+  return BA_OK;
+}
+
+int terms_upload(ba_problem *p) {
+  BA_CHECK(fix_upload(p));
+  BA_CHECK(prior_upload(p));
+  return shared_upload(p);
+}
+
+// what a grouping asks of x and of the mask (shared_check) on the camera part of x, fetched when x is on the device
+static int check_tied_x(ba_problem *p, const double *x, bool x_on_device, const char *entry) {
+  if (!p->grp_on()) return BA_OK;
+  const double *xc = x + 3 * p->npnts;
+  std::vector<double> host(x_on_device ? (size_t)(9 * p->ncams) : 0);
+  if (x_on_device) {
+    BA_HIP_CHECK(hipMemcpyAsync(host.data(), xc, host.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    BA_HIP_CHECK(hipStreamSynchronize(p->stream));
+    xc = host.data();
+  }
+  return shared_check(p, xc, entry);
+}
+
 static int lm_step_impl(ba_problem *p, const double *x, double lambda, double *delta, double *half_sq_model,
                         double *jtr, bool facto_f32, bool pcg = false, double tol = 0, int max_iter = 0, int *cg_iters = nullptr) {
   if (!p || !x || !delta) {
     ba_set_error("ba_lm_step: null argument");
     return BA_ERR_ARG;
   }
-  if (p->pri_on() && p->comm.active()) {
-    ba_set_error("ba_lm_step: priors (ba_lm_set_priors) are not supported on a handle with a communicator");
-    return BA_ERR_ARG;
-  }
-  if (p->grp_on()) {  // shared intrinsics: what the step is not carried through, and what it asks of x and the mask
-    if (p->comm.active()) {
-      ba_set_error("ba_lm_step: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported on a handle with a communicator");
-      return BA_ERR_ARG;
-    }
-    if (facto_f32) {
-      ba_set_error("ba_lm_step_f32: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with facto_type = Float32");
-      return BA_ERR_ARG;
-    }
-    BA_CHECK(shared_check(p, x + 3 * p->npnts, "ba_lm_step"));
-  }
+  TermUse use{pcg ? "ba_lm_step_pcg" : facto_f32 ? "ba_lm_step_f32" : "ba_lm_step"};
+  use.facto_f32 = facto_f32;
+  use.comm = p->comm.active();
+  BA_CHECK(check_terms(p, use));
+  BA_CHECK(check_tied_x(p, x, false, use.entry));
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
-  BA_CHECK(fix_upload(p));
-  BA_CHECK(prior_upload(p));
-  BA_CHECK(shared_upload(p));
+  BA_CHECK(terms_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   StepMode mode;
@@ -1454,15 +1501,13 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
     ba_set_error("ba_covariance: one rank only (a communicator is attached to this handle)");
     return BA_ERR_ARG;
   }
-  if (p->grp_on()) {
-    ba_set_error("ba_covariance: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported (clear the grouping)");
-    return BA_ERR_ARG;
-  }
+  TermUse use{"ba_covariance"};
+  use.covariance = true;
+  BA_CHECK(check_terms(p, use));
   const double tol = rank_tol < 0 ? 1e-10 : rank_tol;
   BA_HIP_CHECK(hipSetDevice(p->device));
   BA_CHECK(lm_ensure(p));
-  BA_CHECK(fix_upload(p));
-  BA_CHECK(prior_upload(p));
+  BA_CHECK(terms_upload(p));
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   w->mode = StepMode();
@@ -1548,7 +1593,7 @@ static inline TS sqrt(TS a) { return a.w == 32 ? f32(std::sqrt((float)a.v)) : f6
 static inline TS powi(TS a, int n) { return a.w == 32 ? f32(std::pow((float)a.v, (float)n)) : f64(std::pow(a.v, (double)n)); }
 }  // namespace ts
 
-// the option combinations ba_lm_solve refuses
+// the option combinations ba_lm_solve refuses: the options among themselves, then the terms on the handle (check_terms)
 static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
   if (o->variant != 0 && o->variant != 1) {
     ba_set_error("ba_lm_solve: variant must be 0 (LevenbergMarquardt.jl) or 1 (lm.jl)");
@@ -1587,65 +1632,14 @@ static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
     ba_set_error("ba_lm_solve: perm must be 0 (:AMD), 1 (:Metis) or 2 (the caller's camera numbering)");
     return BA_ERR_ARG;
   }
-  if (p->loss != BA_LOSS_LINEAR) {  // robust loss (ba_lm_set_loss): the combinations its model value is not defined for
-    if (o->variant == 1 && o->linesearch) {
-      ba_set_error("ba_lm_solve: a robust loss is not supported with linesearch = true (set the loss back to linear)");
-      return BA_ERR_ARG;
-    }
-    if (o->x_f32) {
-      ba_set_error("ba_lm_solve: a robust loss is not supported for a Float32 model (x_f32 = 1)");
-      return BA_ERR_ARG;
-    }
-    if (o->facto_type == 2) {
-      ba_set_error("ba_lm_solve: a robust loss is not supported with facto_type = Float16");
-      return BA_ERR_ARG;
-    }
-  }
-  if (p->fix_on() && o->facto_type == 2) {
-    ba_set_error("ba_lm_solve: fixed parameters (ba_lm_set_fixed) are not supported with facto_type = Float16");
-    return BA_ERR_ARG;
-  }
-  if (p->pri_on()) {  // priors (ba_lm_set_priors): the combinations their terms are not carried through
-    if (o->variant == 1 && o->linesearch) {
-      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported with linesearch = true");
-      return BA_ERR_ARG;
-    }
-    if (o->x_f32) {
-      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported for a Float32 model (x_f32 = 1)");
-      return BA_ERR_ARG;
-    }
-    if (o->facto_type == 2) {
-      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported with facto_type = Float16");
-      return BA_ERR_ARG;
-    }
-    if (p->comm.active()) {
-      ba_set_error("ba_lm_solve: priors (ba_lm_set_priors) are not supported on a handle with a communicator");
-      return BA_ERR_ARG;
-    }
-  }
-  if (p->grp_on()) {  // shared intrinsics (ba_lm_set_shared_intrinsics): the combinations the bordered solve is not carried through
-    if (p->comm.active()) {
-      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported on a handle with a communicator");
-      return BA_ERR_ARG;
-    }
-    if (o->x_f32) {
-      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported for a Float32 model (x_f32 = 1)");
-      return BA_ERR_ARG;
-    }
-    if (o->variant == 1 && o->facto_type != 0) {
-      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with facto_type = Float32 or Float16");
-      return BA_ERR_ARG;
-    }
-    if (o->normalize != 0) {
-      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with normalize = :J or :A");
-      return BA_ERR_ARG;
-    }
-    if (o->variant == 1 && o->linesearch) {
-      ba_set_error("ba_lm_solve: shared intrinsics (ba_lm_set_shared_intrinsics) are not supported with linesearch = true");
-      return BA_ERR_ARG;
-    }
-  }
-  return BA_OK;
+  TermUse use{"ba_lm_solve"};
+  use.linesearch = o->variant == 1 && o->linesearch;
+  use.x_f32 = o->x_f32 != 0;
+  use.facto_f32 = o->variant == 1 && o->facto_type == 1;
+  use.facto_f16 = o->variant == 1 && o->facto_type == 2;
+  use.normalize = o->normalize != 0;
+  use.comm = p->comm.active();
+  return check_terms(p, use);
 }
 
 static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bool x_on_device, ba_lm_stats *stats, ba_log_cb cb,
@@ -1658,17 +1652,8 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   BA_HIP_CHECK(hipSetDevice(p->device));
   const double t_start = wall();
   BA_CHECK(set_ordering(p, o->perm));  // (lm_ensure inside)
-  BA_CHECK(fix_upload(p));
-  BA_CHECK(prior_upload(p));
-  BA_CHECK(shared_upload(p));
-  if (p->grp_on()) {  // the members of a group must enter bit-identical (and agree in the mask)
-    std::vector<double> xc((size_t)(9 * p->ncams));
-    if (x_on_device) {
-      BA_HIP_CHECK(hipMemcpyAsync(xc.data(), x_inout + 3 * p->npnts, xc.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-      BA_HIP_CHECK(hipStreamSynchronize(p->stream));
-    }
-    BA_CHECK(shared_check(p, x_on_device ? xc.data() : x_inout + 3 * p->npnts, "ba_lm_solve"));
-  }
+  BA_CHECK(terms_upload(p));
+  BA_CHECK(check_tied_x(p, x_inout, x_on_device, "ba_lm_solve"));  // the members of a group must enter bit-identical
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   const int V = o->variant;

@@ -197,6 +197,8 @@ int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double la
                           double *d_rhs, double *d_small, hipStream_t st);
 int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, const double *d_B, const double *d_Y, double *d_a,
                          double *d_small, hipStream_t st);
+// the optional terms together (ba_lm.hip): fix_upload, prior_upload and shared_upload
+int terms_upload(ba_problem *p);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,

@@ -482,7 +482,7 @@ extern "C" int ba_prior_eval(ba_problem *p, const double *x, double *cost, doubl
   if (cost) *cost = 0.0;
   if (!p->pri_on()) return BA_OK;
   BA_HIP_CHECK(hipSetDevice(p->device));
-  BA_CHECK(prior_upload(p));
+  BA_CHECK(terms_upload(p));
   const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
   hipStream_t st = p->stream;
   double *dx, *dsum;

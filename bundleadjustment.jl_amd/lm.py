@@ -48,18 +48,6 @@ class GenericExecutionStats:
                 f"  iterations: {self.iter}\n  elapsed time: {self.elapsed_time!r}")
 
 
-def _check_tied(x, npnts, labels):
-    """ValueError when the members of a group do not hold identical (k1, k2, f) in x (labels: _lib.shared_labels or None)"""
-    if labels is None:
-        return
-    tied = _lib.tie_intrinsics(x, npnts, labels)
-    bad = np.flatnonzero((tied.view(np.int64) != np.ascontiguousarray(x, dtype=np.float64).view(np.int64))[3 * npnts:])
-    if bad.size:
-        c = int(bad[0]) // 9
-        raise ValueError(f"shared_intrinsics: camera {c + 1} holds other (k1, k2, f) than the first member of its group "
-                         f"{int(labels[c])}: the members of a group must be identical in x (see tie_intrinsics)")
-
-
 def _sym(s):
     return s[1:] if isinstance(s, str) and s.startswith(":") else s
 
@@ -99,25 +87,9 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     dual_feas and the log's |J'r| are the gradient over the tied parameters.  Set on the handle at every call: a call without
     it runs the untied path.  Not with facto_type = Float32 / Float16, a Float32 model, normalize :J / :A or linesearch = True
     (ValueError)."""
-    tied = _lib.check_shared(shared_intrinsics)
-    if tied:
-        if linesearch:
-            raise ValueError("shared_intrinsics is not supported with linesearch = true")
-        if facto_type is not None and np.dtype(facto_type) != np.dtype(np.float64):
-            raise ValueError("shared_intrinsics is not supported with facto_type = Float32 or Float16")
-        if _sym(normalize) in ("J", "A"):
-            raise ValueError("shared_intrinsics is not supported with normalize = :J or :A")
-    kind, c = _lib.loss_code(loss, f_scale)
-    if kind != 0 and linesearch:
-        raise ValueError("a robust loss is not supported with linesearch = true")
-    with_priors = _lib.check_priors(point_priors, camera_priors, centre_priors)
-    if with_priors and linesearch:
-        raise ValueError("priors are not supported with linesearch = true")
-    if with_priors and facto_type is not None and np.dtype(facto_type) == np.float16:
-        raise ValueError("priors are not supported with facto_type = Float16")
-    masked = _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
-    if masked and facto_type is not None and np.dtype(facto_type) == np.float16:
-        raise ValueError("fixed parameters are not supported with facto_type = Float16")
+    terms = _lib.ProblemTerms(loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params, point_priors, camera_priors,
+                              centre_priors, shared_intrinsics)
+    terms.refuse(linesearch=linesearch, facto_type=facto_type, normalize=normalize)
     facto, perm, normalize = _sym(facto), _sym(perm), _sym(normalize)
     if facto not in _FACTO:
         raise ValueError(f"facto must be :QR, :LDL or :PCG (extension: matrix-free CG on the reduced camera system), got {facto!r}")
@@ -129,11 +101,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     if not isinstance(nlp, BALNLPModel):
         raise TypeError("model must be a FeasibilityResidual(BALNLPModel) or a BALNLPModel")
     xf32 = nlp.T is np.float32  # eltype(x) = Float32: facto_type defaults to it (lm.jl:20), eps(T) tolerances
-    if with_priors and xf32:
-        raise ValueError("priors are not supported for a Float32 model")
-    if tied and xf32:
-        raise ValueError("shared_intrinsics is not supported for a Float32 model (x_f32)")
-    labels = _lib.shared_labels(shared_intrinsics, nlp.ncams)
+    terms.refuse(xf32=xf32)
     variant = 0 if linesearch is None else 1
     if variant == 0 and (facto_type is not None or max_time is not None):
         raise TypeError("LevenbergMarquardt.jl's Levenberg_Marquardt has no facto_type / max_time keyword")
@@ -142,8 +110,6 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     x0 = None if x_device_ptr is not None else np.array(nlp.meta.x0 if x is None else x, dtype=np.float64, copy=True)
     if x0 is not None and x0.shape != (nlp.meta.nvar,):
         raise ValueError("x has the wrong length")
-    if x0 is not None:
-        _check_tied(x0, nlp.npnts, labels)
     if facto_type is not None and np.dtype(facto_type) not in (np.dtype(np.float64), np.dtype(np.float32), np.dtype(np.float16)):
         raise TypeError("facto_type must be Float64, Float32 or Float16")
     # ba_lm_opts.facto_type: 0 = eltype(x), 1 = Float32, 2 = Float16 (src/lm.jl:165-173)
@@ -157,8 +123,6 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
         raise ValueError("facto = :PCG has its own scaling (block-Jacobi preconditioner): normalize must be :None")
     if facto == "PCG" and facto_type is not None and ft == 1 and not xf32:
         raise ValueError("facto = :PCG runs in Float64: facto_type = Float32 belongs to the direct branches")
-    if kind != 0 and (xf32 or ft == 2):
-        raise ValueError("a robust loss is not supported for a Float32 model or with facto_type = Float16")
 
     def d(v):
         return -1.0 if v is None else float(v)
@@ -176,11 +140,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
         rows.append((it, f, df, njtr, lmb, nd, rho, bool(acc)))
 
     cb = _lib.LOG_CB(_cb) if log else C.cast(None, _lib.LOG_CB)
-    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
-    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))  # every call: one without loss= runs the plain objective
-    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)  # ... and one without fixed_* the unmasked path
-    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)  # ... and without *_priors none
-    _lib.set_shared(nlp.handle, labels)  # ... and without shared_intrinsics no grouping
+    terms.apply(nlp, x0)  # every call: one without a term's keyword runs without that term
     if x_device_ptr is not None:
         _lib.check(_lib.lib().ba_lm_solve_dev(nlp.handle, C.byref(o), C.c_void_p(int(x_device_ptr)), C.byref(st), cb, None))
     else:
@@ -212,19 +172,12 @@ def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_
     shared_intrinsics (see Levenberg_Marquardt): the step over the tied parameters, expanded to the layout of x (the members of
     a group receive identical steps); J'r holds a group's summed gradient at its first member and exact zeros at the other
     members' (k1, k2, f).  Not with facto_type = Float32 (ValueError)."""
-    kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
-    _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
-    _lib.check_priors(point_priors, camera_priors, centre_priors)
-    if _lib.check_shared(shared_intrinsics) and facto_type is not None and np.dtype(facto_type) != np.dtype(np.float64):
-        raise ValueError("shared_intrinsics is not supported with facto_type = Float32")
-    labels = _lib.shared_labels(shared_intrinsics, nlp.ncams)
-    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
+    terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
+                              point_priors, camera_priors, centre_priors, shared_intrinsics)
+    f64 = facto_type is None or np.dtype(facto_type) == np.float64
+    terms.refuse(facto_type=None if f64 else np.float32)  # (the step has one other factorisation)
     x = np.ascontiguousarray(x, dtype=np.float64)
-    _check_tied(x, nlp.npnts, labels)
-    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
-    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
-    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)
-    _lib.set_shared(nlp.handle, labels)
+    terms.apply(nlp, x)
     delta = np.empty(nlp.meta.nvar)
     jtr = np.empty(nlp.meta.nvar) if want_jtr else None
     half = C.c_double(0)
@@ -249,9 +202,8 @@ def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, f
     that).  min_rel_pivot = min D_i / S_ii of the factored reduced camera system; at or below rank_tol (None: 1e-10, 0: no
     check) it is numerically singular -- the gauge left free at lam = 0 -- and SQDException is raised (with the value as its
     min_rel_pivot attribute).  Bad arguments raise ValueError before any device call."""
-    kind, c = _lib.loss_code("linear" if loss is None else loss, f_scale)
-    _lib.check_fixed(fixed_cameras, fixed_points, fixed_camera_params)
-    _lib.check_priors(point_priors, camera_priors, centre_priors)
+    terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
+                              point_priors, camera_priors, centre_priors)
     try:
         lam = float(lam)
     except (TypeError, ValueError):
@@ -270,10 +222,7 @@ def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, f
     x = np.ascontiguousarray(x, dtype=np.float64)
     if x.shape != (nlp.meta.nvar,):
         raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
-    cam_mask, pnt_fixed = _lib.fixed_masks(nlp.ncams, nlp.npnts, fixed_cameras, fixed_points, fixed_camera_params)
-    _lib.check(_lib.lib().ba_lm_set_loss(nlp.handle, kind, c))
-    _lib.set_fixed(nlp.handle, cam_mask, pnt_fixed)
-    _lib.set_priors(nlp.handle, nlp.ncams, nlp.npnts, point_priors, camera_priors, centre_priors)
+    terms.apply(nlp, shared=False)  # (a grouping left on the handle stays: ba_covariance refuses it)
     cam = np.empty((nlp.ncams, 9, 9)) if cameras else None
     pnt = np.empty((nlp.npnts, 3, 3)) if points else None
     piv = C.c_double(0)

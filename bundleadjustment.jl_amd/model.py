@@ -174,11 +174,11 @@ class BALNLPModel:
         """(weights, cost) at x under a robust loss (ba_robust_eval): weights[i] = rho'(|r_i|^2 / c^2) per observation (a
         weight below 1 marks an observation the loss discounts: an outlier candidate after a solve), cost = f(x) =
         1/2 sum_i c^2 rho(|r_i|^2 / c^2); c = f_scale.  Sets the handle's loss, as every LM call does."""
-        kind, c = _lib.loss_code(loss, f_scale)
+        terms = _lib.ProblemTerms(loss=loss, f_scale=f_scale)
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.shape != (self.meta.nvar,):
             raise ValueError(f"x has length {x.shape}, expected {self.meta.nvar}")
-        _lib.check(_lib.lib().ba_lm_set_loss(self._h, kind, c))
+        terms.set_loss(self)
         w = np.empty(self.nobs)
         cost = C.c_double(0)
         _lib.check(_lib.lib().ba_robust_eval(self._h, _lib.ptr(x), _lib.ptr(w), C.byref(cost)))
@@ -192,7 +192,7 @@ class BALNLPModel:
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.shape != (self.meta.nvar,):
             raise ValueError(f"x has length {x.shape}, expected {self.meta.nvar}")
-        _lib.set_priors(self._h, self.ncams, self.npnts, point_priors, camera_priors, centre_priors)
+        _lib.ProblemTerms(point_priors=point_priors, camera_priors=camera_priors, centre_priors=centre_priors).set_priors(self)
         chi2 = [np.zeros(n) for n in _lib.get_priors(self._h)]
         cost = C.c_double(0)
         _lib.check(_lib.lib().ba_prior_eval(self._h, _lib.ptr(x), C.byref(cost), *[_lib.ptr(c) if c.size else None for c in chi2]))

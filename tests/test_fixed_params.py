@@ -4,58 +4,21 @@ zeroed in J after every evaluation.  The references are numpy (the oracle's resi
 solve of (J_F'J_F + lambda I) delta_F = -J_F'r over the free columns) and scipy's least_squares on the free variables.  The
 first tests need no device (the Python layer refuses bad arguments before it makes a device call); the rest run on the GPU."""
 import ctypes as C
-import os
 import threading
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
+from _lm_ref import STEP_TOL, arrays, attach_loopback, env, fixed_vector, gauge_kw, jac, lm_opts, loopback_world, residual, reweighted, solve
 from _util import bits_report, parity_record, rel_err
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOOPBACK = os.path.join(ROOT, "tests", "helpers", "libba_loopback.so")
-_STEP_TOL = {1e3: 1e-12, 30.0: 1e-11, 1.0: 1e-11, 1e-2: 1e-9}  # test_lm_step_vs_oracle's limits at these lambda
 INTRINSICS = ("k1", "k2", "f")
-
-
-# ---- numpy reference -------------------------------------------------------------------------------------------------------
-def _arrays(p):
-    return (p["cam_idx1"], p["pnt_idx1"], p["pt2d"], p["x0"], p["ncams"], p["npnts"], p["nobs"])
-
-
-def _residual(orc, p, x):
-    return orc.residuals(p["cam_idx1"], p["pnt_idx1"], x, p["pt2d"], p["npnts"])
-
-
-def _jac(orc, p, x):
-    rows, cols = orc.jac_structure(p["cam_idx1"], p["pnt_idx1"], p["npnts"])
-    vals = orc.jac_coord(p["cam_idx1"], p["pnt_idx1"], x, p["npnts"])
-    nvar = 9 * p["ncams"] + 3 * p["npnts"]
-    return sp.csr_matrix((vals, (rows - 1, cols - 1)), shape=(2 * p["nobs"], nvar))
-
-
-def _fixed_vector(ba, p, kw):
-    """boolean over x = [points; cameras]: True where the options of kw fix the entry"""
-    cam, pnt = ba._lib.fixed_masks(p["ncams"], p["npnts"], kw.get("fixed_cameras"), kw.get("fixed_points"),
-                                   kw.get("fixed_camera_params"))
-    fixed_p = np.repeat(pnt.astype(bool), 3)
-    fixed_c = ((cam[:, None] >> np.arange(9)) & 1).astype(bool).ravel()
-    return np.concatenate([fixed_p, fixed_c])
-
-
-def _huber(r, c):
-    s = r[0::2] ** 2 + r[1::2] ** 2
-    return np.where(s <= c * c, 1.0, c / np.sqrt(np.maximum(s, c * c)))
 
 
 def _ref_step(orc, p, x, lam, fixed, loss=None, c=1.0):
     """delta (zeros on the fixed entries), 1/2 |J_F delta_F + r|^2, J_F'r (zeros on the fixed entries) of the dense solve
-    over the free columns; loss = "huber": the reweighted r~, J~ of test_robust_loss.py"""
-    r, J = _residual(orc, p, x), _jac(orc, p, x)
-    if loss == "huber":
-        sw = np.repeat(np.sqrt(_huber(r, c)), 2)
-        r, J = sw * r, sp.diags(sw) @ J
+    over the free columns; loss = "huber": the reweighted r~, J~ of _lm_ref.reweighted"""
+    r, J = reweighted(orc, p, x, loss, c)[:2] if loss == "huber" else (residual(orc, p, x), jac(orc, p, x))
     free = ~fixed
     JF = J[:, np.flatnonzero(free)]
     g = JF.T @ r
@@ -68,26 +31,6 @@ def _ref_step(orc, p, x, lam, fixed, loss=None, c=1.0):
     return d, 0.5 * (m @ m), gf
 
 
-def _solve(ba, m, variant=1, facto="LDL", normalize="None", **kw):
-    args = (facto, "AMD", normalize) + ((False,) if variant == 1 else ())
-    return ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), *args, **kw)
-
-
-def _env(name, value, fn):
-    old = os.environ.get(name)
-    if value is None:
-        os.environ.pop(name, None)
-    else:
-        os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
-
-
 def _step_masks(p):
     """the three masks of the step tests: intrinsics of every camera; camera 1 whole plus 20 % of the points; random
     per-camera components"""
@@ -97,14 +40,6 @@ def _step_masks(p):
     return {"intrinsics": dict(fixed_camera_params=INTRINSICS),
             "cam1+20%pts": dict(fixed_cameras=[1], fixed_points=pts),
             "random components": dict(fixed_camera_params=comp)}
-
-
-# gauge: camera 1's pose (r, t) and the first translation component of camera 2 -- the 7 DoF of a similarity transform
-def _gauge_kw(p):
-    comp = np.zeros((p["ncams"], 9), dtype=bool)
-    comp[0, :6] = True
-    comp[1, 3] = True
-    return dict(fixed_camera_params=comp)
 
 
 # ---- CPU: host masks and the refusals before any device call ----------------------------------------------------------------
@@ -200,12 +135,12 @@ def _check_step(ba, orc, m, p, lam, kw, tol, fixed, what, loss=None, c=1.0):
 def test_fixed_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, mask):
     p = small_prob
     kw = _step_masks(p)[mask]
-    fixed = _fixed_vector(ba, p, kw)
+    fixed = fixed_vector(ba, p, kw)
     assert 0 < fixed.sum() < len(fixed)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         worst = 0.0
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             e, _ = _check_step(ba, orc, m, p, lam, kw, tol, fixed, mask)
             worst = max(worst, e / tol)
         assert ba._lib.get_fixed(m.handle) == (int(fixed[3 * p["npnts"]:].sum()), int(fixed[:3 * p["npnts"]].sum()) // 3)
@@ -222,7 +157,7 @@ def test_fixed_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, mask):
         parity_record(f"fixed_step[{mask}]", worst_over_limit=worst, pcg=ep, f32=e32)
         # a call without fixed_* is the plain step again: the bits of a handle that never saw a mask
         d_plain = ba.lm_step(m, p["x0"], lam)[0]
-        fresh = ba.BALNLPModel(arrays=_arrays(p))
+        fresh = ba.BALNLPModel(arrays=arrays(p))
         d_fresh = ba.lm_step(fresh, p["x0"], lam)[0]
         fresh.close()
         rep = bits_report(d_plain, d_fresh, "unmasked step after masked ones vs a fresh handle")
@@ -236,10 +171,10 @@ def test_fixed_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, mask):
 def test_fixed_step_under_huber(ba, orc, small_prob, gpu_ok):
     p = small_prob
     kw = _step_masks(p)["cam1+20%pts"]
-    fixed = _fixed_vector(ba, p, kw)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    fixed = fixed_vector(ba, p, kw)
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             _check_step(ba, orc, m, p, lam, kw, tol, fixed, "huber", loss="huber", c=1.0)
     finally:
         m.close()
@@ -250,17 +185,17 @@ def test_fixed_step_block_sparse_schedule(ba, orc, gpu_ok):
     """BA_SPARSE_S=1 on a banded problem, whole cameras fixed inside the band (their rows of S hold only the damping)."""
     p = ba.synthetic.make_problem(300, 700, 3500, seed=5, locality=0.08)
     kw = dict(fixed_cameras=np.arange(100, 111), fixed_points=np.arange(1, 701, 7))
-    fixed = _fixed_vector(ba, p, kw)
+    fixed = fixed_vector(ba, p, kw)
     lam = 1.0
 
     def run():
-        m = ba.BALNLPModel(arrays=_arrays(p))
+        m = ba.BALNLPModel(arrays=arrays(p))
         try:
             return ba.lm_step(m, p["x0"], lam, **kw), ba.schur_pattern(m)
         finally:
             m.close()
 
-    (d, half, jtr), pat = _env("BA_SPARSE_S", "1", run)
+    (d, half, jtr), pat = env("BA_SPARSE_S", "1", run)
     assert pat[2], "the block-sparse list schedule was not used"
     d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, fixed)
     assert np.all(d[fixed] == 0.0) and np.all(jtr[fixed] == 0.0)
@@ -273,7 +208,7 @@ def test_fixed_step_block_sparse_schedule(ba, orc, gpu_ok):
 @pytest.mark.gpu
 def test_c_abi_refuses_bad_masks(ba, small_prob, gpu_ok):
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         L = ba._lib.lib()
         cam = np.zeros(p["ncams"], dtype=np.uint16)
@@ -292,8 +227,7 @@ def test_c_abi_refuses_bad_masks(ba, small_prob, gpu_ok):
         assert ba._lib.get_fixed(m.handle) == (3 * p["ncams"], 0)
         # the C entry refuses a mask with facto_type = Float16 (the Python layer does so before it: see the CPU tests)
         ba._lib.set_fixed(m.handle, *ba._lib.fixed_masks(p["ncams"], p["npnts"], [1]))
-        o = ba._lib.LMOpts(variant=1, facto_type=2, ite_max=-1, **{k: -1.0 for k in (
-            "restol", "satol", "srtol", "oatol", "ortol", "atol", "rtol", "nu_d", "nu_m", "lam", "delta_d", "max_time", "pcg_tol")})
+        o = lm_opts(ba, facto_type=2)
         x = p["x0"].copy()
         with pytest.raises(ba.BAArgError, match="Float16"):
             ba._lib.check(L.ba_lm_solve(m.handle, C.byref(o), ba._lib.ptr(x), C.byref(ba._lib.LMStats()),
@@ -327,8 +261,8 @@ def _scipy_free(orc, p, fixed):
         x[free] = xf
         return x
 
-    res = least_squares(lambda xf: _residual(orc, p, full(xf)), x_base[free],
-                        jac=lambda xf: _jac(orc, p, full(xf))[:, free].toarray(), method="trf", x_scale="jac",
+    res = least_squares(lambda xf: residual(orc, p, full(xf)), x_base[free],
+                        jac=lambda xf: jac(orc, p, full(xf))[:, free].toarray(), method="trf", x_scale="jac",
                         ftol=1e-15, xtol=1e-15, gtol=1e-15, max_nfev=500)
     out = (full(res.x), 0.5 * float(res.fun @ res.fun))
     _scipy_cache[key] = out
@@ -357,13 +291,13 @@ def test_fixed_solve_vs_scipy(ba, orc, gpu_ok, variant, facto, normalize):
     default stopping tests end a run at |J'r| <= cbrt(eps) |J'r_0|, which leaves x_F about 1e-5 from the minimum: the
     objective-change and first-order tests are tightened (TIGHT), as scipy's run is (1e-15)."""
     p = _solve_scene(ba)
-    kw = _gauge_kw(p)
+    kw = gauge_kw(p)
     kw["fixed_camera_params"][2, 6:] = True
     kw["fixed_points"] = np.arange(1, p["npnts"] + 1, 10)
-    fixed = _fixed_vector(ba, p, kw)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    fixed = fixed_vector(ba, p, kw)
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        st = _solve(ba, m, variant, facto, normalize, **TIGHT, **kw)
+        st = solve(ba, m, variant, facto, normalize, **TIGHT, **kw)
     finally:
         m.close()
     x = st.solution
@@ -376,7 +310,7 @@ def test_fixed_solve_vs_scipy(ba, orc, gpu_ok, variant, facto, normalize):
     parity_record(f"fixed_solve[{variant}-{facto}-{normalize}]", objective=eo, x_free=ex, iter=st.iter, status=st.status)
     assert eo <= OBJ_TOL, f"objective {st.objective!r} vs scipy {f_ref!r}: {eo:.3e}"
     assert ex <= X_TOL, f"x_F vs scipy: {ex:.3e}"
-    r = _residual(orc, p, x)
+    r = residual(orc, p, x)
     assert abs(st.objective - 0.5 * (r @ r)) <= 1e-12 * st.objective
 
 
@@ -386,9 +320,9 @@ def test_gauge_fixed_reaches_the_free_minimum(ba, gpu_ok):
     (4.8e-15 relative on an MI355X)."""
     p = _solve_scene(ba)
     out = {}
-    for name, kw in (("free", {}), ("gauge", _gauge_kw(p))):
-        m = ba.BALNLPModel(arrays=_arrays(p))
-        out[name] = _solve(ba, m, **TIGHT, **kw)
+    for name, kw in (("free", {}), ("gauge", gauge_kw(p))):
+        m = ba.BALNLPModel(arrays=arrays(p))
+        out[name] = solve(ba, m, **TIGHT, **kw)
         m.close()
     f0, f1 = out["free"].objective, out["gauge"].objective
     e = abs(f0 - f1) / f0
@@ -404,14 +338,14 @@ def test_motion_only(ba, orc, gpu_ok, variant):
     p["pt2d"] = orc.residuals(p["cam_idx1"], p["pnt_idx1"], p["x_true"], np.zeros(2 * p["nobs"]), p["npnts"])
     nP = 3 * p["npnts"]
     x0 = np.concatenate([p["x_true"][:nP], p["x0"][nP:]])
-    m = ba.BALNLPModel(arrays=_arrays(dict(p, x0=x0)))
+    m = ba.BALNLPModel(arrays=arrays(dict(p, x0=x0)))
     try:
-        st = _solve(ba, m, variant, x=x0, fixed_points=np.arange(1, p["npnts"] + 1), restol=0.0, **TIGHT)
+        st = solve(ba, m, variant, x=x0, fixed_points=np.arange(1, p["npnts"] + 1), restol=0.0, **TIGHT)
     finally:
         m.close()
     x = st.solution
     assert not bits_report(x[:nP], x0[:nP])
-    r = _residual(orc, p, x)
+    r = residual(orc, p, x)
     rms = float(np.sqrt(np.mean(r[0::2] ** 2 + r[1::2] ** 2)))
     ec = rel_err(x[nP:], p["x_true"][nP:])
     parity_record(f"fixed_motion_only[{variant}]", rms_px=rms, cameras=ec, iter=st.iter, status=st.status)
@@ -423,13 +357,13 @@ def test_motion_only(ba, orc, gpu_ok, variant):
 @pytest.mark.parametrize("variant", [1, 0])
 def test_everything_fixed(ba, orc, small_prob, gpu_ok, variant):
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        st = _solve(ba, m, variant, fixed_cameras=np.arange(1, p["ncams"] + 1), fixed_points=np.ones(p["npnts"], dtype=bool))
-        st2 = _solve(ba, m, variant, fixed_camera_params=("r", "t", "k1", "k2", "f"), fixed_points=np.arange(1, p["npnts"] + 1))
+        st = solve(ba, m, variant, fixed_cameras=np.arange(1, p["ncams"] + 1), fixed_points=np.ones(p["npnts"], dtype=bool))
+        st2 = solve(ba, m, variant, fixed_camera_params=("r", "t", "k1", "k2", "f"), fixed_points=np.arange(1, p["npnts"] + 1))
     finally:
         m.close()
-    r = _residual(orc, p, p["x0"])
+    r = residual(orc, p, p["x0"])
     for s in (st, st2):
         assert s.status == "first_order" and s.iter == 0, (s.status, s.iter)
         rep = bits_report(s.solution, p["x0"], "solution with everything fixed vs x0")
@@ -442,15 +376,15 @@ def test_everything_fixed(ba, orc, small_prob, gpu_ok, variant):
 @pytest.mark.parametrize("variant", [1, 0])
 def test_no_mask_changes_nothing(ba, small_prob, gpu_ok, variant):
     p = small_prob
-    fresh = ba.BALNLPModel(arrays=_arrays(p))
-    ref = _solve(ba, fresh, variant)
+    fresh = ba.BALNLPModel(arrays=arrays(p))
+    ref = solve(ba, fresh, variant)
     fresh.close()
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        _solve(ba, m, variant, fixed_camera_params=INTRINSICS, fixed_points=[1, 2, 3])  # the handle has seen a mask
+        solve(ba, m, variant, fixed_camera_params=INTRINSICS, fixed_points=[1, 2, 3])  # the handle has seen a mask
         for kw in ({}, dict(fixed_cameras=None, fixed_points=None, fixed_camera_params=None),
                    dict(fixed_cameras=[], fixed_points=[], fixed_camera_params=())):
-            st = _solve(ba, m, variant, **kw)
+            st = solve(ba, m, variant, **kw)
             rep = bits_report(ref.solution, st.solution, f"variant {variant}, {kw}: solution vs a fresh handle")
             assert not rep, rep
             assert st.log == ref.log and st.iter == ref.iter and st.objective == ref.objective
@@ -469,12 +403,12 @@ def test_no_stale_recorded_sequence(ba, small_prob, gpu_ok, prefetch):
            ("huber+B", dict(masks["cam1+20%pts"], loss="huber", f_scale=1.0)), ("none", {})]
 
     def run():
-        shared = ba.BALNLPModel(arrays=_arrays(p))
+        shared = ba.BALNLPModel(arrays=arrays(p))
         try:
             for name, kw in seq:
-                a = _solve(ba, shared, **kw)
-                fresh = ba.BALNLPModel(arrays=_arrays(p))
-                b = _solve(ba, fresh, **kw)
+                a = solve(ba, shared, **kw)
+                fresh = ba.BALNLPModel(arrays=arrays(p))
+                b = solve(ba, fresh, **kw)
                 fresh.close()
                 rep = bits_report(a.solution, b.solution, f"{name}: reused handle vs fresh handle")
                 assert not rep, rep
@@ -482,19 +416,19 @@ def test_no_stale_recorded_sequence(ba, small_prob, gpu_ok, prefetch):
         finally:
             shared.close()
 
-    _env("BA_LM_PREFETCH", prefetch, run)
+    env("BA_LM_PREFETCH", prefetch, run)
 
 
 @pytest.mark.gpu
 def test_float32_model_keeps_fixed_entries(ba, small_prob, gpu_ok):
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p), T=np.float32)
+    m = ba.BALNLPModel(arrays=arrays(p), T=np.float32)
     kw = dict(fixed_cameras=[2, 5], fixed_camera_params=INTRINSICS, fixed_points=np.arange(1, p["npnts"] + 1, 3))
     try:
-        st = _solve(ba, m, **kw)
+        st = solve(ba, m, **kw)
     finally:
         m.close()
-    fixed = _fixed_vector(ba, p, kw)
+    fixed = fixed_vector(ba, p, kw)
     x = np.asarray(st.solution)
     assert x.dtype == np.float32
     rep = bits_report(x[fixed], p["x0"].astype(np.float32)[fixed], "Float32 model: fixed entries vs float32(x0)")
@@ -502,22 +436,9 @@ def test_float32_model_keeps_fixed_entries(ba, small_prob, gpu_ok):
     assert st.iter > 0 and np.any(x[~fixed] != p["x0"].astype(np.float32)[~fixed])
 
 
-# ---- several ranks over the in-process loopback transport (fixture of test_gpu_determinism.py) -------------------------------
-@pytest.fixture(scope="module")
-def loopback(gpu_ok):
-    assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-    L = C.CDLL(LOOPBACK)
-    L.ba_loopback_create.restype = C.c_void_p
-    L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-    L.ba_loopback_destroy.argtypes = [C.c_void_p]
-    L.ba_loopback_rank.restype = C.c_void_p
-    L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-    return L
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("world", [2, 3])
-def test_loopback_fixed_step_equals_one_rank(ba, loopback, world):
+def test_loopback_fixed_step_equals_one_rank(ba, gpu_ok, world):
     """Observations sharded by point: every rank masks its own observations (its slice of the point mask, the global camera
     mask).  The step of the unsharded problem to 1e-9, the camera step bit-identical on every rank, fixed entries 0.  The
     mask is set on every shard BEFORE its communicator is attached."""
@@ -528,55 +449,52 @@ def test_loopback_fixed_step_equals_one_rank(ba, loopback, world):
     ref = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(prob))
     d_ref, half_ref, _ = ba.lm_step(ref, prob["x0"], lam, fixed_points=g_pts, **cam_kw)
     ref.close()
-    fixed = _fixed_vector(ba, prob, dict(cam_kw, fixed_points=g_pts))
+    fixed = fixed_vector(ba, prob, dict(cam_kw, fixed_points=g_pts))
     assert np.all(d_ref[fixed] == 0.0)
-    arrays = ba.synthetic.as_arrays(prob)
-    loop = loopback.ba_loopback_create(world, 64 << 20)
-    assert loop
-    hook = C.cast(loopback.ba_loopback_hook, ba._lib.COMM_CB)
+    whole = ba.synthetic.as_arrays(prob)
     models, shards = [], []
-    try:
-        for r in range(world):
-            local, info = ba.parallel.shard_problem(arrays, r, world)
-            m = ba.BALNLPModel(arrays=local, device=0)
-            models.append(m)
-            loc_pts = ba.parallel.shard_fixed_points(g_pts, info)
-            ba._lib.set_fixed(m.handle, *ba._lib.fixed_masks(local[4], local[5], cam_kw["fixed_cameras"], loc_pts,
-                                                             cam_kw["fixed_camera_params"]))
-            ba._lib.check(ba._lib.lib().ba_lm_set_comm_hook(m.handle, r, world, hook, loopback.ba_loopback_rank(loop, r)))
-            shards.append((local, info, loc_pts))
-        out, err = [None] * world, [None] * world
+    with loopback_world(world, 64 << 20) as (L, loop):
+        try:
+            for r in range(world):
+                local, info = ba.parallel.shard_problem(whole, r, world)
+                m = ba.BALNLPModel(arrays=local, device=0)
+                models.append(m)
+                loc_pts = ba.parallel.shard_fixed_points(g_pts, info)
+                ba._lib.set_fixed(m.handle, *ba._lib.fixed_masks(local[4], local[5], cam_kw["fixed_cameras"], loc_pts,
+                                                                 cam_kw["fixed_camera_params"]))
+                attach_loopback(ba, m, L, loop, r, world)
+                shards.append((local, info, loc_pts))
+            out, err = [None] * world, [None] * world
 
-        def run(r):
-            try:
-                out[r] = ba.lm_step(models[r], shards[r][0][3], lam, fixed_points=shards[r][2], **cam_kw)
-            except Exception as e:  # noqa: BLE001 -- reported below with the rank
-                err[r] = e
+            def run(r):
+                try:
+                    out[r] = ba.lm_step(models[r], shards[r][0][3], lam, fixed_points=shards[r][2], **cam_kw)
+                except Exception as e:  # noqa: BLE001 -- reported below with the rank
+                    err[r] = e
 
-        ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        bad = [(r, e) for r, e in enumerate(err) if e is not None]
-        assert not bad, f"rank(s) failed: {bad}"
-        npnts, ncams = prob["npnts"], prob["ncams"]
-        delta = np.zeros(3 * npnts + 9 * ncams)
-        cams = []
-        for r in range(world):
-            pb, pe = shards[r][1]["point_range"]
-            d = out[r][0]
-            delta[3 * pb:3 * pe] = d[:3 * (pe - pb)]
-            cams.append(d[3 * (pe - pb):].copy())
-        delta[3 * npnts:] = cams[0]
-        assert np.all(delta[fixed] == 0.0), f"{world} ranks: fixed entries of delta are not 0"
-        e = rel_err(delta, d_ref)
-        assert e <= 1e-9, f"{world} ranks: |delta - delta_one_rank| / |delta_one_rank| = {e:.3e}"
-        assert abs(out[0][1] - half_ref) <= 1e-10 * half_ref
-        for r in range(1, world):
-            rep = bits_report(cams[0], cams[r], f"masked camera step of rank 0 vs rank {r}")
-            assert not rep, rep
-    finally:
-        for m in models:
-            m.close()
-        loopback.ba_loopback_destroy(loop)
+            ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+            for t in ts:
+                t.start()
+            for t in ts:
+                t.join()
+            bad = [(r, e) for r, e in enumerate(err) if e is not None]
+            assert not bad, f"rank(s) failed: {bad}"
+            npnts, ncams = prob["npnts"], prob["ncams"]
+            delta = np.zeros(3 * npnts + 9 * ncams)
+            cams = []
+            for r in range(world):
+                pb, pe = shards[r][1]["point_range"]
+                d = out[r][0]
+                delta[3 * pb:3 * pe] = d[:3 * (pe - pb)]
+                cams.append(d[3 * (pe - pb):].copy())
+            delta[3 * npnts:] = cams[0]
+            assert np.all(delta[fixed] == 0.0), f"{world} ranks: fixed entries of delta are not 0"
+            e = rel_err(delta, d_ref)
+            assert e <= 1e-9, f"{world} ranks: |delta - delta_one_rank| / |delta_one_rank| = {e:.3e}"
+            assert abs(out[0][1] - half_ref) <= 1e-10 * half_ref
+            for r in range(1, world):
+                rep = bits_report(cams[0], cams[r], f"masked camera step of rank 0 vs rank {r}")
+                assert not rep, rep
+        finally:
+            for m in models:
+                m.close()

@@ -12,10 +12,8 @@ import threading
 import numpy as np
 import pytest
 
+from _lm_ref import Ranks, env, loopback  # noqa: F401 (loopback: a fixture)
 from _util import bits_report, digest, rel_err
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOOPBACK = os.path.join(ROOT, "tests", "helpers", "libba_loopback.so")
 
 pytestmark = pytest.mark.gpu
 
@@ -68,7 +66,6 @@ def test_lm_step_twice_same_bits_venice_scaled(ba, gpu_ok):
     assert h1 == h2 == h3, f"model value differs between runs: {h1!r} {h2!r} {h3!r}"
 
 
-
 @pytest.mark.parametrize("ncams,shuffle", [(1100, False), (1100, True), (1095, False)])
 def test_block_sparse_two_chains(ba, orc, gpu_ok, ncams, shuffle):
     """A profile eliminated from both ends (ba_order.cpp: "two-ended"): the list schedule runs the two independent runs of tile
@@ -94,16 +91,16 @@ def test_block_sparse_two_chains(ba, orc, gpu_ok, ncams, shuffle):
         return d1, d2, h1, h2, pat, perm, name
 
     a1, a2, ha1, ha2, pat, perm, name = step()
-    b1, _, hb1, _, _, _, _ = _env("BA_SPARSE_TWO_RUNS", "0", step)
+    b1, _, hb1, _, _, _, _ = env("BA_SPARSE_TWO_RUNS", "0", step)
     f1, f2, _, _, _, _, _ = step(np.float32)
     # the look-ahead inside the two-run phase (lead strips of both runs, both rests on a part of the chip beside the next step's
     # chain), forced on however short the rests are, against the two runs strictly in order: the same bits
-    l1, l2, _, _, _, _, _ = _env("BA_SPARSE_LOOKAHEAD_MIN", "1", step)
-    n1, _, _, _, _, _, _ = _env("BA_SPARSE_LOOKAHEAD", "0", step)
-    l32, _, _, _, _, _, _ = _env("BA_SPARSE_LOOKAHEAD_MIN", "1", lambda: step(np.float32))
-    n32, _, _, _, _, _, _ = _env("BA_SPARSE_LOOKAHEAD", "0", lambda: step(np.float32))
-    w1, _, _, _, _, _, _ = _env("BA_SPARSE_BWD2", "0", step)
-    w32, _, _, _, _, _, _ = _env("BA_SPARSE_BWD2", "0", lambda: step(np.float32))
+    l1, l2, _, _, _, _, _ = env("BA_SPARSE_LOOKAHEAD_MIN", "1", step)
+    n1, _, _, _, _, _, _ = env("BA_SPARSE_LOOKAHEAD", "0", step)
+    l32, _, _, _, _, _, _ = env("BA_SPARSE_LOOKAHEAD_MIN", "1", lambda: step(np.float32))
+    n32, _, _, _, _, _, _ = env("BA_SPARSE_LOOKAHEAD", "0", lambda: step(np.float32))
+    w1, _, _, _, _, _, _ = env("BA_SPARSE_BWD2", "0", step)
+    w32, _, _, _, _, _, _ = env("BA_SPARSE_BWD2", "0", lambda: step(np.float32))
     for tag, (x, y) in {"backward sweep, two groups per launch vs one pair per launch": (a1, w1), "Float32: the same": (f1, w32)}.items():
         rep = bits_report(x, y, tag)
         assert not rep, rep
@@ -124,7 +121,7 @@ def test_block_sparse_two_chains(ba, orc, gpu_ok, ncams, shuffle):
 
     def run(graph):
         m = ba.BALNLPModel(arrays=arrays)
-        st = _env("BA_LM_GRAPH", graph, lambda: ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, ite_max=4))
+        st = env("BA_LM_GRAPH", graph, lambda: ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, ite_max=4))
         m.close()
         return st
 
@@ -160,21 +157,6 @@ def test_lm_solve_with_the_iterate_on_the_device_same_bits(ba, gpu_ok):
     assert not rep, rep
 
 
-def _env(key, value, fn):
-    old = os.environ.get(key)
-    if value is None:
-        os.environ.pop(key, None)
-    else:
-        os.environ[key] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(key, None)
-        else:
-            os.environ[key] = old
-
-
 @pytest.mark.parametrize("shuffle", [False, True])
 def test_block_sparse_lookahead_same_bits_as_in_order(ba, gpu_ok, shuffle):
     """The list schedule of the block-sparse reduced camera system with its look-ahead (the rest of a pair's trailing update
@@ -198,7 +180,7 @@ def test_block_sparse_lookahead_same_bits_as_in_order(ba, gpu_ok, shuffle):
 
     def run(graph=None):
         m = ba.BALNLPModel(arrays=arrays)
-        st = _env("BA_LM_GRAPH", graph, lambda: ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, ite_max=5))
+        st = env("BA_LM_GRAPH", graph, lambda: ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, ite_max=5))
         m.close()
         return st
 
@@ -211,8 +193,8 @@ def test_block_sparse_lookahead_same_bits_as_in_order(ba, gpu_ok, shuffle):
 
 def _lookahead_checks(ba, step, run):
     for ft in (None, np.float32):
-        a1, a2, ha1, ha2, pat = _env("BA_SPARSE_S", "1", lambda: step(ft))
-        b1, b2, hb1, hb2, _ = _env("BA_SPARSE_LOOKAHEAD", "0", lambda: _env("BA_SPARSE_S", "1", lambda: step(ft)))
+        a1, a2, ha1, ha2, pat = env("BA_SPARSE_S", "1", lambda: step(ft))
+        b1, b2, hb1, hb2, _ = env("BA_SPARSE_LOOKAHEAD", "0", lambda: env("BA_SPARSE_S", "1", lambda: step(ft)))
         assert pat[2] and np.all(np.isfinite(a1))
         tag = "Float32" if ft is not None else "Float64"
         for name, (x, y) in {"look-ahead twice": (a1, a2), "in order twice": (b1, b2), "look-ahead vs in order": (a1, b1)}.items():
@@ -220,9 +202,9 @@ def _lookahead_checks(ba, step, run):
             assert not rep, rep
         assert ha1 == ha2 == hb1 == hb2
     # complete runs: recorded graphs (the forks and joins become graph edges) and plain launches, against the in-order schedule
-    s_graph = _env("BA_SPARSE_S", "1", lambda: run(None))
-    s_plain = _env("BA_SPARSE_S", "1", lambda: run("0"))
-    s_inord = _env("BA_SPARSE_LOOKAHEAD", "0", lambda: _env("BA_SPARSE_S", "1", lambda: run(None)))
+    s_graph = env("BA_SPARSE_S", "1", lambda: run(None))
+    s_plain = env("BA_SPARSE_S", "1", lambda: run("0"))
+    s_inord = env("BA_SPARSE_LOOKAHEAD", "0", lambda: env("BA_SPARSE_S", "1", lambda: run(None)))
     assert s_graph.iter == s_plain.iter == s_inord.iter and s_graph.log == s_plain.log == s_inord.log
     for name, (x, y) in {"graph vs plain launches": (s_graph.solution, s_plain.solution), "look-ahead vs in order": (s_graph.solution, s_inord.solution)}.items():
         rep = bits_report(x, y, f"solution of a 6-iteration run, {name}")
@@ -266,73 +248,6 @@ def test_prefetched_trial_step_same_rows_as_two_submissions(ba, gpu_ok, variant)
         rep = bits_report(a.solution, b.solution, f"{variant}: solution, prefetched trial steps vs {name}")
         assert not rep, rep
 
-# ---- several ranks in one process over the stream-ordered loopback transport ------------------------------------------------
-@pytest.fixture(scope="module")
-def loopback(gpu_ok):
-    assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-    L = C.CDLL(LOOPBACK)
-    L.ba_loopback_create.restype = C.c_void_p
-    L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-    L.ba_loopback_destroy.argtypes = [C.c_void_p]
-    L.ba_loopback_rank.restype = C.c_void_p
-    L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-    L.ba_loopback_ops.restype = C.c_long
-    L.ba_loopback_ops.argtypes = [C.c_void_p]
-    return L
-
-
-class _Ranks:
-    """`world` shards of one problem as handles in this process, attached to one loopback communicator."""
-
-    def __init__(self, ba, L, prob, world, stage_mb=64):
-        self.ba, self.L, self.world, self.prob = ba, L, world, prob
-        arrays = ba.synthetic.as_arrays(prob)
-        self.loop = L.ba_loopback_create(world, stage_mb << 20)
-        assert self.loop, "loopback communicator could not be created"
-        hook = C.cast(L.ba_loopback_hook, ba._lib.COMM_CB)
-        self.shards, self.models = [], []
-        for r in range(world):
-            local, info = ba.parallel.shard_problem(arrays, r, world)
-            m = ba.BALNLPModel(arrays=local, device=0)
-            ba._lib.check(ba._lib.lib().ba_lm_set_comm_hook(m.handle, r, world, hook, L.ba_loopback_rank(self.loop, r)))
-            self.shards.append((local, info))
-            self.models.append(m)
-
-    def step(self, lam, **kw):
-        """one sharded LM step, every rank on its own host thread -> (global delta from rank 0's cameras, per-rank camera
-        parts, model value)"""
-        out, err = [None] * self.world, [None] * self.world
-
-        def run(r):
-            try:
-                out[r] = self.ba.lm_step(self.models[r], self.shards[r][0][3], lam, **kw)
-            except Exception as e:  # noqa: BLE001 -- reported below with the rank
-                err[r] = e
-
-        ts = [threading.Thread(target=run, args=(r,)) for r in range(self.world)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        bad = [(r, e) for r, e in enumerate(err) if e is not None]
-        assert not bad, f"rank(s) failed: {bad}"
-        ncams, npnts = self.prob["ncams"], self.prob["npnts"]
-        delta = np.zeros(3 * npnts + 9 * ncams)
-        cams = []
-        for r in range(self.world):
-            pb, pe = self.shards[r][1]["point_range"]
-            d = out[r][0]
-            delta[3 * pb:3 * pe] = d[:3 * (pe - pb)]
-            cams.append(d[3 * (pe - pb):].copy())
-        delta[3 * npnts:] = cams[0]
-        return delta, cams, out[0][1]
-
-    def close(self):
-        for m in self.models:
-            m.close()
-        self.L.ba_loopback_destroy(self.loop)
-
-
 def _set_lookahead(on):
     if on:
         os.environ.pop("BA_DIST_LOOKAHEAD", None)
@@ -351,7 +266,7 @@ def test_loopback_sharded_step_equals_one_rank(ba, loopback, world):
     d32_ref, _, _ = ba.lm_step(ref, prob["x0"], 10.0, facto_type=np.float32)
     ref.close()
     _set_lookahead(True)
-    R = _Ranks(ba, loopback, prob, world)
+    R = Ranks(ba, loopback, prob, world)
     try:
         d, cams, half = R.step(10.0)
         e = rel_err(d, d_ref)
@@ -395,7 +310,7 @@ def test_loopback_lookahead_same_bits_as_alternating(ba, loopback, ncams, npnts,
     ref = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(prob))
     d_ref, _, _ = ba.lm_step(ref, prob["x0"], 10.0)
     ref.close()
-    R = _Ranks(ba, loopback, prob, 3, stage_mb=256)
+    R = Ranks(ba, loopback, prob, 3, stage_mb=256)
     try:
         runs = {}
         for tag, on in (("look-ahead, run 1", True), ("alternating", False), ("look-ahead, run 2", True)):
@@ -448,7 +363,7 @@ def test_loopback_block_sparse_on_several_ranks(ba, loopback, world, irregular):
         full_one, held_one, _ = ba.schur_memory(ref)
         ref.close()
         assert sparse_one and held_one < full_one
-        R = _Ranks(ba, loopback, prob, world, stage_mb=256)
+        R = Ranks(ba, loopback, prob, world, stage_mb=256)
         try:
             runs = {}
             for tag, on in (("look-ahead", True), ("alternating", False)):
@@ -504,7 +419,7 @@ def test_loopback_reduce_scatter_assembly_equals_reduce_onto_owner(ba, loopback,
         if form == "reduce":
             os.environ["BA_ASSEMBLY"] = "reduce"
         try:
-            R = _Ranks(ba, loopback, prob, world, stage_mb=512)
+            R = Ranks(ba, loopback, prob, world, stage_mb=512)
             try:
                 d, cams, _ = R.step(10.0)
                 d2, cams2, _ = R.step(10.0)
@@ -558,7 +473,7 @@ def test_loopback_camera_ordering_on_several_ranks(ba, loopback, scene):
     pat_ref, (perm_ref, name_ref) = ba.schur_pattern(ref), ba.schur_ordering_used(ref)
     ref.close()
     assert pat_ref[2] and name_ref != "natural"
-    R = _Ranks(ba, loopback, prob, 3, stage_mb=256)
+    R = Ranks(ba, loopback, prob, 3, stage_mb=256)
     try:
         d, cams, half = R.step(10.0)
         e = rel_err(d, d_ref)
@@ -586,7 +501,7 @@ def test_loopback_lm_runs_equal_one_rank(ba, loopback):
         want[norm] = ba.Levenberg_Marquardt(ba.FeasibilityResidual(ref), "LDL", "AMD", norm, False)
     ref.close()
     _set_lookahead(True)
-    R = _Ranks(ba, loopback, prob, 3)
+    R = Ranks(ba, loopback, prob, 3)
     try:
         for norm in ("None", "J", "A"):
             out, err = [None] * 3, [None] * 3

@@ -12,41 +12,13 @@ import pytest
 import scipy.sparse as sp
 from scipy.spatial.transform import Rotation
 
+from _lm_ref import (F32_TOL, PCG_TOL, STEP_TOL, arrays, attach_loopback, check_cov, env, fixed_vector, hessian, jac,
+                     kappa_jacobi, limit, lm_opts, loopback_world, ref_dense, residual, reweighted, schur, solve, sym)
 from _util import bits_report, parity_record, rel_err
-from test_covariance import _check, _hessian, _kappa, _ref_dense, _schur
-from test_robust_loss import _STEP_TOL, _jac, _residual, _reweighted
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import prior_ref as pr  # noqa: E402
-
-LOOPBACK = os.path.join(ROOT, "tests", "helpers", "libba_loopback.so")
-EPS = np.finfo(np.float64).eps
-F32_TOL = 5e-3  # the Float32-factor limit of tests/test_fixed_params.py and tests/test_robust_loss.py
-PCG_TOL = 1e-8  # their limit of the pcg=(1e-12, 5000) step
-
-
-def _arrays(p):
-    return (p["cam_idx1"], p["pnt_idx1"], p["pt2d"], p["x0"], p["ncams"], p["npnts"], p["nobs"])
-
-
-def _env(name, value, fn):
-    old = os.environ.get(name)
-    if value is None:
-        os.environ.pop(name, None)
-    else:
-        os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
-
-
-def _sym(M):
-    return 0.5 * (M + np.swapaxes(M, -1, -2))
 
 
 def _prior_set(p, offset=0.01, seed=5):
@@ -59,7 +31,7 @@ def _prior_set(p, offset=0.01, seed=5):
     cams = p["x_true"][np3:].reshape(-1, 9)
     pidx = np.arange(3, p["npnts"] + 1, max(1, p["npnts"] // 40))[:40]
     B = rng.standard_normal((len(pidx), 3, 3))
-    pinfo = _sym(1e4 * B @ np.swapaxes(B, 1, 2) + 1e3 * np.eye(3))
+    pinfo = sym(1e4 * B @ np.swapaxes(B, 1, 2) + 1e3 * np.eye(3))
     pmu = X[pidx - 1] + offset * rng.standard_normal((len(pidx), 3))
     cidx = np.array([2, 5, 9])
     sig = np.array([0.01, 0.01, 0.01, 0.05, 0.05, 0.05, 1.0, 1.0, 5.0])
@@ -69,7 +41,7 @@ def _prior_set(p, offset=0.01, seed=5):
         Q = np.linalg.qr(rng.standard_normal((9, 9)))[0]
         M = Q @ np.diag(rng.uniform(0.5, 2.0, 9)) @ Q.T
         D = keep / sig
-        cinfo[q] = _sym(D[:, None] * M * D[None, :])
+        cinfo[q] = sym(D[:, None] * M * D[None, :])
     cmu = cams[cidx - 1] + (offset / 0.01) * sig * keep * rng.standard_normal((len(cidx), 9))
     tidx = np.array([1, 6, 12, 7])
     tsig = np.full((4, 3), 0.01)
@@ -83,24 +55,12 @@ def _subsets(kw):
             "centre": {"centre_priors": kw["centre_priors"]}, "all": kw}
 
 
-def _fixed_vector(ba, p, kw):
-    cam, pnt = ba._lib.fixed_masks(p["ncams"], p["npnts"], kw.get("fixed_cameras"), kw.get("fixed_points"),
-                                   kw.get("fixed_camera_params"))
-    return np.concatenate([np.repeat(pnt.astype(bool), 3), ((cam[:, None] >> np.arange(9)) & 1).astype(bool).ravel()])
-
-
 def _ref_step(orc, p, x, lam, pri, fixed=None, loss="linear", c=1.0):
     """(delta, model, gradient, kappa of the Jacobi-scaled damped S with the priors) of the dense numpy solve"""
-    rt, Jt, _, _ = _reweighted(orc, p, x, loss, c)
+    rt, Jt, _, _ = reweighted(orc, p, x, loss, c)
     rows = pr.rows(x, p["ncams"], p["npnts"], fixed=fixed, **pri)
     d, mod, g, A = pr.step(Jt, rt, lam, rows, fixed)
     return d, mod, g, pr.kappa_jacobi_S(A, p["npnts"])[0]
-
-
-def _limit(tol, kappa):
-    """the project's limit of a step at this lambda, or 100 kappa eps where the conditioning of the damped reduced camera
-    system (priors included) is worse: the rule of tests/test_covariance.py::_check"""
-    return max(tol, 100.0 * kappa * EPS)
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
@@ -196,7 +156,7 @@ def test_c_abi_refuses_bad_lists_and_keeps_the_handle(ba, small_prob, gpu_ok):
     """ba_lm_set_priors through ctypes: index out of range / repeated, a value that is not finite, a negative diagonal entry,
     Lambda_ij^2 > Lambda_ii Lambda_jj -> BA_ERR_ARG, and the handle keeps what it had."""
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     L = ba._lib.lib()
     try:
         ba._lib.set_priors(m.handle, p["ncams"], p["npnts"], point_priors=_GOOD)
@@ -233,7 +193,7 @@ def test_prior_eval_against_numpy(ba, orc, small_prob, gpu_ok):
     small difference of large numbers: a centre carries a few ulps of |c| ~ 7 (1e-15), which is 1e-14 of such a d."""
     p = small_prob
     kw = _prior_set(p, offset=0.5)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         cost, cp, cc, ct = m.prior_eval(p["x0"], **kw)
         assert ba._lib.get_priors(m.handle) == (40, 3, 4)
@@ -259,8 +219,8 @@ def test_cleared_priors_leave_the_plain_bits(ba, small_prob, gpu_ok):
     """after calls with priors, calls without them give the bits of a handle that never had any: lm_step and robust_eval"""
     p = small_prob
     kw = _prior_set(p)
-    m = ba.BALNLPModel(arrays=_arrays(p))
-    fresh = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
+    fresh = ba.BALNLPModel(arrays=arrays(p))
     try:
         with_p = ba.lm_step(m, p["x0"], 1.0, **kw)
         m.prior_eval(p["x0"], **kw)
@@ -288,14 +248,14 @@ def test_cleared_priors_leave_the_plain_bits(ba, small_prob, gpu_ok):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kinds", ["point", "camera", "centre", "all"])
 def test_prior_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, kinds):
-    """The step of the augmented normal equations at the four lambda of _STEP_TOL: :LDL, facto_type = Float32 and
-    pcg = (1e-12, 5000).  Limits: _STEP_TOL / 5e-3 / 1e-8, or 100 kappa eps (Float64's eps, as tests/test_covariance.py::_check)
+    """The step of the augmented normal equations at the four lambda of STEP_TOL: :LDL, facto_type = Float32 and
+    pcg = (1e-12, 5000).  Limits: STEP_TOL / 5e-3 / 1e-8, or 100 kappa eps (Float64's eps, as tests/_lm_ref.py::check_cov)
     where that is larger -- for the Float32 factor it never is here: 5e-3 on every case."""
     p = small_prob
     pri = _subsets(_prior_set(p))[kinds]
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, pri)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, **pri)
             d32 = ba.lm_step(m, p["x0"], lam, facto_type=np.float32, **pri)[0]
@@ -303,7 +263,7 @@ def test_prior_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, kinds):
             e, e32, ep = rel_err(d, d_ref), rel_err(d32, d_ref), rel_err(dp, d_ref)
             em = abs(half - mod_ref) / mod_ref
             eg = float(np.linalg.norm(jtr - g_ref) / np.linalg.norm(g_ref))
-            lim, lim32, limp = _limit(tol, kappa), _limit(F32_TOL, kappa), _limit(PCG_TOL, kappa)
+            lim, lim32, limp = limit(tol, kappa), limit(F32_TOL, kappa), limit(PCG_TOL, kappa)
             print(f"prior_step[{kinds}] lambda {lam:g}: kappa {kappa:.3e}  LDL {e:.3e} (limit {lim:.1e})  f32 {e32:.3e} "
                   f"({lim32:.1e})  pcg {ep:.3e} ({limp:.1e}, {its} its)  model {em:.3e}  jtr {eg:.3e}")
             parity_record(f"prior_step[{kinds}-{lam:g}]", kappa=kappa, ldl=e, ldl_limit=lim, f32=e32, f32_limit=lim32, pcg=ep,
@@ -329,16 +289,16 @@ def test_prior_step_with_loss_and_fixed_mask(ba, orc, small_prob, gpu_ok, loss):
     comp = np.zeros((p["ncams"], 9), dtype=bool)
     comp[1, 6:] = True
     mask = dict(fixed_cameras=[6], fixed_points=[3, 50], fixed_camera_params=comp)
-    fixed = _fixed_vector(ba, p, mask)
+    fixed = fixed_vector(ba, p, mask)
     assert 3 in pri["point_priors"][0] and 6 in pri["centre_priors"][0] and 2 in pri["camera_priors"][0]
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, pri, fixed, loss, 1.0)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss=loss, f_scale=1.0, **mask, **pri)
             assert np.all(d[fixed] == 0.0), f"lambda {lam}: {np.count_nonzero(d[fixed])} fixed entries of delta are not 0"
             assert np.all(jtr[fixed] == 0.0), f"lambda {lam}: fixed entries of the gradient are not 0"
-            e, lim = rel_err(d, d_ref), _limit(tol, kappa)
+            e, lim = rel_err(d, d_ref), limit(tol, kappa)
             em = abs(half - mod_ref) / mod_ref
             eg = float(np.linalg.norm(jtr - g_ref) / np.linalg.norm(g_ref))
             print(f"prior_step_masked[{loss}] lambda {lam:g}: kappa {kappa:.3e}  step {e:.3e} (limit {lim:.1e})  model {em:.3e}  "
@@ -366,16 +326,16 @@ def test_prior_step_block_sparse_schedule(ba, orc, gpu_ok):
                point_priors=(pidx, p["x_true"][:np3].reshape(-1, 3)[pidx - 1], np.full((len(pidx), 3), 0.005)))
     lam = 1.0
     d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, pri)
-    lim = _limit(1e-10, kappa)
+    lim = limit(1e-10, kappa)
     for flag in ("1", "0"):
         def run():
-            m = ba.BALNLPModel(arrays=_arrays(p))
+            m = ba.BALNLPModel(arrays=arrays(p))
             try:
                 return ba.lm_step(m, p["x0"], lam, **pri), ba.schur_pattern(m)
             finally:
                 m.close()
 
-        (d, half, jtr), pat = _env("BA_SPARSE_S", flag, run)
+        (d, half, jtr), pat = env("BA_SPARSE_S", flag, run)
         assert pat[2] == (flag == "1"), "the schedule asked for was not used"
         e = rel_err(d, d_ref)
         print(f"prior_step_sparse[BA_SPARSE_S={flag}]: kappa {kappa:.3e}  step {e:.3e} (limit {lim:.1e})")
@@ -386,15 +346,14 @@ def test_prior_step_block_sparse_schedule(ba, orc, gpu_ok):
 
 
 def _objective_and_gradient(orc, p, x, pri):
-    r = _residual(orc, p, x)
+    r = residual(orc, p, x)
     rows = pr.rows(x, p["ncams"], p["npnts"], **pri)
-    g = _jac(orc, p, x).T @ r + pr.normal_terms(rows, len(x))[1]
+    g = jac(orc, p, x).T @ r + pr.normal_terms(rows, len(x))[1]
     return 0.5 * (r @ r) + pr.cost(rows), float(np.linalg.norm(g))
 
 
 def _solve(ba, m, variant, facto, normalize, **kw):
-    args = (facto, "AMD", normalize) + ((False,) if variant == 1 else ())
-    return ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), *args, oatol=0.0, ortol=0.0, **kw)
+    return solve(ba, m, variant, facto, normalize, oatol=0.0, ortol=0.0, **kw)
 
 
 @pytest.mark.gpu
@@ -403,7 +362,7 @@ def _solve(ba, m, variant, facto, normalize, **kw):
 def test_prior_solve(ba, orc, small_prob, gpu_ok, variant, facto, normalize):
     p = small_prob
     pri = _prior_set(p)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         st = _solve(ba, m, variant, facto, normalize, **pri)
         st2 = _solve(ba, m, variant, facto, normalize, **pri)
@@ -431,12 +390,12 @@ def test_prior_solve_with_huber(ba, orc, small_prob, gpu_ok, variant):
     """A complete solve with priors under a robust loss: the checks of test_prior_solve against the robust objective plus the
     priors, and -- variant 1 -- the gain ratio of the first log row against numpy.  Under a loss the controller predicts
     m(0) - m(delta) with m(0) = 1/2 |r~|^2 + f_prior (not f, which holds rho): the one place that reads the priors' share of
-    the zero-step model value.  Limit of the ratio: the step is numpy's to 1e-11 (_STEP_TOL) and both differences are of the
+    the zero-step model value.  Limit of the ratio: the step is numpy's to 1e-11 (STEP_TOL) and both differences are of the
     order of f itself at x0, so 1e-9 leaves two digits."""
     p = small_prob
     pri = _prior_set(p)
     loss, c = "huber", 1.0
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         st = _solve(ba, m, variant, "LDL", "None", loss=loss, f_scale=c, **pri)
         st2 = _solve(ba, m, variant, "LDL", "None", loss=loss, f_scale=c, **pri)
@@ -444,7 +403,7 @@ def test_prior_solve_with_huber(ba, orc, small_prob, gpu_ok, variant):
         m.close()
 
     def terms(x):
-        rt, Jt, _, f_obs = _reweighted(orc, p, x, loss, c)
+        rt, Jt, _, f_obs = reweighted(orc, p, x, loss, c)
         rows = pr.rows(x, p["ncams"], p["npnts"], **pri)
         return rt, Jt, rows, f_obs + pr.cost(rows)
 
@@ -488,11 +447,11 @@ def test_no_stale_recorded_sequence_with_priors(ba, small_prob, gpu_ok, prefetch
     seq = [a, {}, b, {"centre_priors": a["centre_priors"]}, {"point_priors": b["point_priors"]}, {}]
 
     def run():
-        shared = ba.BALNLPModel(arrays=_arrays(p))
+        shared = ba.BALNLPModel(arrays=arrays(p))
         try:
             for k, pri in enumerate(seq):
                 s1 = _solve(ba, shared, 1, "LDL", "None", **pri)
-                fresh = ba.BALNLPModel(arrays=_arrays(p))
+                fresh = ba.BALNLPModel(arrays=arrays(p))
                 s2 = _solve(ba, fresh, 1, "LDL", "None", **pri)
                 fresh.close()
                 rep = bits_report(s1.solution, s2.solution, f"solve {k} ({sorted(pri)}): reused handle vs fresh handle")
@@ -501,7 +460,7 @@ def test_no_stale_recorded_sequence_with_priors(ba, small_prob, gpu_ok, prefetch
         finally:
             shared.close()
 
-    _env("BA_LM_PREFETCH", prefetch, run)
+    env("BA_LM_PREFETCH", prefetch, run)
 
 
 @pytest.mark.gpu
@@ -518,8 +477,8 @@ def test_no_prior_kernel_without_priors(ba, small_prob, gpu_ok):
         m.profile(False)
         return st, prof
 
-    m = ba.BALNLPModel(arrays=_arrays(p))
-    fresh = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
+    fresh = ba.BALNLPModel(arrays=arrays(p))
     try:
         _, plain = profile(fresh)
         st_p, with_p = profile(m, **pri)
@@ -555,7 +514,7 @@ def test_centre_priors_make_the_covariance_well_defined(ba, orc, small_prob, gpu
     def pri(sel):
         return dict(centre_priors=(np.array(sel), np.stack([pr.centre(cams[i - 1]) for i in sel]), np.full((len(sel), 3), 0.01)))
 
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         with pytest.raises(ba.SQDException):
             ba.covariance(m, x, 0.0)
@@ -568,10 +527,10 @@ def test_centre_priors_make_the_covariance_well_defined(ba, orc, small_prob, gpu
     finally:
         m.close()
     rows = pr.rows(x, p["ncams"], p["npnts"], **pri([1, 6, 12]))
-    H = (_hessian(orc, p, x, 0.0, fixed) + sp.csr_matrix(pr.normal_terms(rows, len(x))[0])).tocsr()
-    ref_c, ref_p = _ref_dense(H, p, fixed)
-    S, _, _ = _schur(H, p)
-    _check("covariance_centre_priors", cov_c, cov_p, ref_c, ref_p, _kappa(S), fixed, p, min_rel_pivot=piv)
+    H = (hessian(orc, p, x, 0.0, fixed) + sp.csr_matrix(pr.normal_terms(rows, len(x))[0])).tocsr()
+    ref_c, ref_p = ref_dense(H, p, fixed)
+    S, _, _ = schur(H, p)
+    check_cov("covariance_centre_priors", cov_c, cov_p, ref_c, ref_p, kappa_jacobi(S), fixed, p, min_rel_pivot=piv)
     assert piv > 1e-10, piv
 
 
@@ -596,11 +555,11 @@ def test_control_points_bring_the_scene_back(ba, orc, small_prob, gpu_ok):
     p = dict(small_prob)
     npnts, np3, sigma = p["npnts"], 3 * p["npnts"], 1e-3
     xt = p["x_true"]
-    p["pt2d"] = p["pt2d"] + _residual(orc, p, xt)  # r = projection - pt2d: the observations of x_true, exactly
-    assert np.max(np.abs(_residual(orc, p, xt))) < 1e-9
+    p["pt2d"] = p["pt2d"] + residual(orc, p, xt)  # r = projection - pt2d: the observations of x_true, exactly
+    assert np.max(np.abs(residual(orc, p, xt))) < 1e-9
     Q = Rotation.from_rotvec([0.02, -0.03, 0.01]).as_matrix()
     x_start = _similarity(p["x0"], npnts, 1.03, Q, np.array([0.05, -0.02, 0.03]))
-    r0, r1 = _residual(orc, p, p["x0"]), _residual(orc, p, x_start)
+    r0, r1 = residual(orc, p, p["x0"]), residual(orc, p, x_start)
     assert abs(r0 @ r0 - r1 @ r1) <= 1e-9 * (r0 @ r0)  # the similarity changes no reprojection
     idx = np.array([1, 101, 201, 301])
     Xc = xt[:np3].reshape(-1, 3)[idx - 1]
@@ -612,7 +571,7 @@ def test_control_points_bring_the_scene_back(ba, orc, small_prob, gpu_ok):
 
     def fun(pri_):
         def f(x):
-            r, J = _residual(orc, p, x), _jac(orc, p, x).toarray()
+            r, J = residual(orc, p, x), jac(orc, p, x).toarray()
             rows = pr.rows(x, p["ncams"], npnts, **pri_)
             Ap, gp = pr.normal_terms(rows, len(x))
             return (0.5 * (r @ r) + pr.cost(rows), J.T @ r + gp, J.T @ J + Ap,
@@ -622,7 +581,7 @@ def test_control_points_bring_the_scene_back(ba, orc, small_prob, gpu_ok):
     ref_with, ref_without = rms(pr.lm_dense(fun(pri), x_start)[0]), rms(pr.lm_dense(fun({}), x_start)[0])
     print(f"control points, numpy LM: rms with priors {ref_with:.3e}, without {ref_without:.3e}")
     assert ref_with <= 3 * sigma < 10 * sigma < ref_without
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         st = ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, x=x_start, **pri)
         st0 = ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, x=x_start)
@@ -643,8 +602,8 @@ def test_refused_combinations_on_the_device(ba, small_prob, gpu_ok):
     p = small_prob
     pri = _prior_set(p)
     lib = ba._lib.lib()
-    m = ba.BALNLPModel(arrays=_arrays(p))
-    m32 = ba.BALNLPModel(arrays=_arrays(p), T=np.float32)
+    m = ba.BALNLPModel(arrays=arrays(p))
+    m32 = ba.BALNLPModel(arrays=arrays(p), T=np.float32)
     try:
         before = ba.lm_step(m, p["x0"], 1.0, **pri)
         nls = ba.FeasibilityResidual(m)
@@ -658,10 +617,7 @@ def test_refused_combinations_on_the_device(ba, small_prob, gpu_ok):
         assert ba._lib.get_priors(m.handle) == (40, 3, 4)
         x = np.array(p["x0"])
         for field, text in (("linesearch", "linesearch = true"), ("x_f32", "Float32 model"), ("facto_type", "Float16")):
-            o = ba._lib.LMOpts(variant=1, facto=0, normalize=0, linesearch=0, facto_type=0, ite_max=-1, verbose=0, x_f32=0,
-                               restol=-1, satol=-1, srtol=-1, oatol=-1, ortol=-1, atol=-1, rtol=-1, nu_d=-1, nu_m=-1, lam=-1,
-                               delta_d=-1, max_time=-1, pcg_tol=-1, pcg_max_iter=-1, perm=0)
-            setattr(o, field, 2 if field == "facto_type" else 1)
+            o = lm_opts(ba, **{field: 2 if field == "facto_type" else 1})
             st = ba._lib.LMStats()
             rc = lib.ba_lm_solve(m.handle, C.byref(o), ba._lib.ptr(x), C.byref(st), C.cast(None, ba._lib.LOG_CB), None)
             msg = lib.ba_last_error().decode()
@@ -671,30 +627,20 @@ def test_refused_combinations_on_the_device(ba, small_prob, gpu_ok):
         assert not bits_report(after[0], before[0], "step after the refusals")
         assert _solve(ba, m, 1, "LDL", "None", **pri).status in ("first_order", "small_step")
         # a communicator (attached before the handle's first solve, as documented)
-        assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-        L = C.CDLL(LOOPBACK)
-        L.ba_loopback_create.restype = C.c_void_p
-        L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-        L.ba_loopback_destroy.argtypes = [C.c_void_p]
-        L.ba_loopback_rank.restype = C.c_void_p
-        L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-        loop = L.ba_loopback_create(1, 16 << 20)
-        assert loop
-        mc = ba.BALNLPModel(arrays=_arrays(p))
-        try:
-            hook = C.cast(L.ba_loopback_hook, ba._lib.COMM_CB)
-            ba._lib.check(lib.ba_lm_set_comm_hook(mc.handle, 0, 1, hook, L.ba_loopback_rank(loop, 0)))
-            with pytest.raises(ba.BAArgError, match="priors.*communicator"):
-                ba.lm_step(mc, p["x0"], 1.0, **pri)
-            with pytest.raises(ba.BAArgError, match="priors.*communicator"):
-                ba.lm_step(mc, p["x0"], 1.0, pcg=(1e-8, 100), **pri)
-            with pytest.raises(ba.BAArgError, match="priors.*communicator"):
-                _solve(ba, mc, 1, "LDL", "None", **pri)
-            plain = ba.lm_step(mc, p["x0"], 1.0)  # without priors the handle still steps
-            assert np.all(np.isfinite(plain[0])) and rel_err(plain[0], before[0]) > 1e-6
-        finally:
-            mc.close()
-            L.ba_loopback_destroy(loop)
+        mc = ba.BALNLPModel(arrays=arrays(p))
+        with loopback_world(1, 16 << 20) as (L, loop):
+            try:
+                attach_loopback(ba, mc, L, loop, 0, 1)
+                with pytest.raises(ba.BAArgError, match="priors.*communicator"):
+                    ba.lm_step(mc, p["x0"], 1.0, **pri)
+                with pytest.raises(ba.BAArgError, match="priors.*communicator"):
+                    ba.lm_step(mc, p["x0"], 1.0, pcg=(1e-8, 100), **pri)
+                with pytest.raises(ba.BAArgError, match="priors.*communicator"):
+                    _solve(ba, mc, 1, "LDL", "None", **pri)
+                plain = ba.lm_step(mc, p["x0"], 1.0)  # without priors the handle still steps
+                assert np.all(np.isfinite(plain[0])) and rel_err(plain[0], before[0]) > 1e-6
+            finally:
+                mc.close()
     finally:
         m.close()
         m32.close()

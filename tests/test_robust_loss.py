@@ -5,97 +5,25 @@ J~ = sqrt(w) J, w = rho'(z).  The references are numpy: the oracle's residuals /
 device call); the rest run on the GPU."""
 import ctypes as C
 import math
-import os
-import threading
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
+from _lm_ref import STEP_TOL, Ranks, arrays, env, loopback, residual, reweighted, solve, weights_cost  # noqa: F401 (loopback: a fixture)
 from _util import bits_report, rel_err
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOOPBACK = os.path.join(ROOT, "tests", "helpers", "libba_loopback.so")
 LOSSES = ("linear", "huber", "soft_l1", "cauchy", "arctan")
-
-
-# ---- numpy reference -------------------------------------------------------------------------------------------------------
-def _rho(loss, z):
-    """(rho(z), rho'(z)) of scipy's losses"""
-    if loss == "linear":
-        return z, np.ones_like(z)
-    if loss == "huber":
-        sz = np.sqrt(np.maximum(z, 1.0))
-        return np.where(z <= 1.0, z, 2.0 * sz - 1.0), np.where(z <= 1.0, 1.0, 1.0 / sz)
-    if loss == "soft_l1":
-        t = np.sqrt(1.0 + z)
-        return 2.0 * z / (t + 1.0), 1.0 / t
-    if loss == "cauchy":
-        return np.log1p(z), 1.0 / (1.0 + z)
-    if loss == "arctan":
-        return np.arctan(z), 1.0 / (1.0 + z * z)
-    raise ValueError(loss)
-
-
-def _weights_cost(r, loss, c):
-    s = r[0::2] ** 2 + r[1::2] ** 2
-    if loss == "linear":
-        return np.ones_like(s), 0.5 * np.sum(s)
-    rho, w = _rho(loss, s / c ** 2)
-    return w, 0.5 * np.sum(c ** 2 * rho)
-
-
-def _residual(orc, p, x):
-    return orc.residuals(p["cam_idx1"], p["pnt_idx1"], x, p["pt2d"], p["npnts"])
-
-
-def _jac(orc, p, x):
-    rows, cols = orc.jac_structure(p["cam_idx1"], p["pnt_idx1"], p["npnts"])
-    vals = orc.jac_coord(p["cam_idx1"], p["pnt_idx1"], x, p["npnts"])
-    nvar = 9 * p["ncams"] + 3 * p["npnts"]
-    return sp.csr_matrix((vals, (rows - 1, cols - 1)), shape=(2 * p["nobs"], nvar))
-
-
-def _reweighted(orc, p, x, loss, c):
-    r = _residual(orc, p, x)
-    w, f = _weights_cost(r, loss, c)
-    sw = np.repeat(np.sqrt(w), 2)
-    return sw * r, sp.diags(sw) @ _jac(orc, p, x), w, f
 
 
 def _ref_step(orc, p, x, lam, loss, c):
     """delta, 1/2 |J~ delta + r~|^2, J~'r~ of the dense solve"""
-    rt, Jt, _, _ = _reweighted(orc, p, x, loss, c)
+    rt, Jt, _, _ = reweighted(orc, p, x, loss, c)
     g = Jt.T @ rt
     A = (Jt.T @ Jt).toarray()
     A[np.diag_indices_from(A)] += lam
     d = np.linalg.solve(A, -g)
     m = Jt @ d + rt
     return d, 0.5 * (m @ m), g
-
-
-def _arrays(p):
-    return (p["cam_idx1"], p["pnt_idx1"], p["pt2d"], p["x0"], p["ncams"], p["npnts"], p["nobs"])
-
-
-def _solve(ba, m, variant=1, **kw):
-    args = ("LDL", "AMD", "None") + ((False,) if variant == 1 else ())
-    return ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), *args, **kw)
-
-
-def _env(name, value, fn):
-    old = os.environ.get(name)
-    if value is None:
-        os.environ.pop(name, None)
-    else:
-        os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
 
 
 # ---- CPU: the Python layer refuses before any device call --------------------------------------------------------------------
@@ -140,7 +68,7 @@ def test_loss_names_and_c_abi_codes(ba):
 def _small_forced(p, orc):
     """small_prob with observations 0..9 exactly on their projection (s = 0) and 10..14 moved ~1e6 px away"""
     q = dict(p)
-    r = _residual(orc, p, p["x0"])
+    r = residual(orc, p, p["x0"])
     pt = p["pt2d"].copy()
     pt[:20] += r[:20]  # r = projection - pt2d
     pt[20:30] += np.array([1e6, -7e5, 3e5, 9e5, -1e6, 1e6, 2e5, -8e5, 6e5, 4e5])
@@ -154,23 +82,23 @@ def test_robust_eval_weights_and_cost(ba, orc, small_prob, gpu_ok, c):
     """ba_robust_eval against numpy for every loss.  The reference takes the device's own residual (which
     test_gpu_parity.py holds to the oracle's at its own limit): the comparison is of the loss pass, at 1e-14 per weight."""
     p = _small_forced(small_prob, orc)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         r = m.cons(p["x0"])
-        r_orc = _residual(orc, p, p["x0"])
+        r_orc = residual(orc, p, p["x0"])
         assert np.max(np.abs(r - r_orc) / (np.abs(p["pt2d"]) + np.abs(r_orc) + 1.0)) < 64 * 2.3e-16
         s = r[0::2] ** 2 + r[1::2] ** 2
         assert np.all(s[:10] < 1e-20) and np.all(s[10:15] > 1e10)
         for loss in LOSSES:
             w, f = m.robust_weights(p["x0"], loss, c)
-            w_ref, f_ref = _weights_cost(r, loss, c)
+            w_ref, f_ref = weights_cost(r, loss, c)
             e = np.max(np.abs(w - w_ref) / w_ref)
             assert e <= 1e-14, f"{loss}, c = {c}: weights, max relative error {e:.3e}"
             assert abs(f - f_ref) <= 1e-13 * f_ref, f"{loss}, c = {c}: cost {f!r} vs {f_ref!r}"
             if loss != "linear":
                 assert np.all(w[10:15] < 1.0) and np.all(w[:10] == 1.0)
             # the oracle's residual: the same to its agreement with the device
-            w2, f2 = _weights_cost(r_orc, loss, c)
+            w2, f2 = weights_cost(r_orc, loss, c)
             assert abs(f - f2) <= 1e-12 * f2
         kind, scale = C.c_int(-1), C.c_double(0)
         ba._lib.check(ba._lib.lib().ba_lm_get_loss(m.handle, C.byref(kind), C.byref(scale)))
@@ -179,16 +107,13 @@ def test_robust_eval_weights_and_cost(ba, orc, small_prob, gpu_ok, c):
         m.close()
 
 
-_STEP_TOL = {1e3: 1e-12, 30.0: 1e-11, 1.0: 1e-11, 1e-2: 1e-9}  # test_lm_step_vs_oracle's limits at these lambda
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("loss,c", [("huber", 1.0), ("soft_l1", 2.0), ("cauchy", 1.5)])
 def test_robust_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, loss, c):
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss=loss, f_scale=c)
             d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, loss, c)
             e = rel_err(d, d_ref)
@@ -203,7 +128,7 @@ def test_robust_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, loss, c):
         assert rel_err(d32, d_ref) <= 5e-3, f"{loss}: Float32-factor step {rel_err(d32, d_ref):.3e}"
         # a call without loss= is the plain step again: the bits of a handle that never saw a loss
         d_lin = ba.lm_step(m, p["x0"], lam)[0]
-        fresh = ba.BALNLPModel(arrays=_arrays(p))
+        fresh = ba.BALNLPModel(arrays=arrays(p))
         d_fresh = ba.lm_step(fresh, p["x0"], lam)[0]
         fresh.close()
         rep = bits_report(d_lin, d_fresh, "linear step after robust ones vs a fresh handle")
@@ -220,14 +145,14 @@ def test_robust_step_block_sparse_schedule(ba, orc, gpu_ok):
     lam, c = 1.0, 1.0
 
     def run():
-        m = ba.BALNLPModel(arrays=_arrays(p))
+        m = ba.BALNLPModel(arrays=arrays(p))
         try:
             out = ba.lm_step(m, p["x0"], lam, loss="huber", f_scale=c)
             return out, ba.schur_pattern(m)
         finally:
             m.close()
 
-    (d, half, jtr), pat = _env("BA_SPARSE_S", "1", run)
+    (d, half, jtr), pat = env("BA_SPARSE_S", "1", run)
     assert pat[2], "the block-sparse list schedule was not used"
     d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, "huber", c)
     e = rel_err(d, d_ref)
@@ -242,8 +167,8 @@ def test_linear_loss_changes_nothing(ba, small_prob, gpu_ok, variant):
     p = small_prob
     out = []
     for kw in ({}, {"loss": "linear"}, {"loss": ":linear", "f_scale": 3.0}):
-        m = ba.BALNLPModel(arrays=_arrays(p))
-        out.append(_solve(ba, m, variant, **kw))
+        m = ba.BALNLPModel(arrays=arrays(p))
+        out.append(solve(ba, m, variant, **kw))
         m.close()
     for st in out[1:]:
         rep = bits_report(out[0].solution, st.solution, f"variant {variant}: solution with loss = linear vs without loss=")
@@ -261,12 +186,12 @@ def test_no_stale_recorded_sequence(ba, small_prob, gpu_ok, prefetch):
     seq = [("linear", 1.0), ("huber", 1.0), ("huber", 3.0), ("cauchy", 2.0), ("linear", 1.0)]
 
     def run():
-        shared = ba.BALNLPModel(arrays=_arrays(p))
+        shared = ba.BALNLPModel(arrays=arrays(p))
         try:
             for loss, c in seq:
-                a = _solve(ba, shared, loss=loss, f_scale=c)
-                fresh = ba.BALNLPModel(arrays=_arrays(p))
-                b = _solve(ba, fresh, loss=loss, f_scale=c)
+                a = solve(ba, shared, loss=loss, f_scale=c)
+                fresh = ba.BALNLPModel(arrays=arrays(p))
+                b = solve(ba, fresh, loss=loss, f_scale=c)
                 fresh.close()
                 rep = bits_report(a.solution, b.solution, f"{loss} c = {c}: reused handle vs fresh handle")
                 assert not rep, rep
@@ -274,7 +199,7 @@ def test_no_stale_recorded_sequence(ba, small_prob, gpu_ok, prefetch):
         finally:
             shared.close()
 
-    _env("BA_LM_PREFETCH", prefetch, run)
+    env("BA_LM_PREFETCH", prefetch, run)
 
 
 @pytest.mark.gpu
@@ -285,15 +210,15 @@ def test_robust_solve(ba, orc, small_prob, gpu_ok, loss, c, variant):
     the relative-objective-change test ends these runs first (status :acceptable -- a numpy run of the same controller stops
     there too), so it is switched off (oatol = ortol = 0) and the run must end on the first-order or the small-step test."""
     p = small_prob
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        st = _solve(ba, m, variant, loss=loss, f_scale=c, oatol=0.0, ortol=0.0)
-        st2 = _solve(ba, m, variant, loss=loss, f_scale=c, oatol=0.0, ortol=0.0)
+        st = solve(ba, m, variant, loss=loss, f_scale=c, oatol=0.0, ortol=0.0)
+        st2 = solve(ba, m, variant, loss=loss, f_scale=c, oatol=0.0, ortol=0.0)
     finally:
         m.close()
     f_acc = [row[1] for row in st.log if row[7]]
     assert len(f_acc) >= 2 and all(b < a for a, b in zip(f_acc, f_acc[1:])), f"accepted rows: f not strictly decreasing {f_acc}"
-    rt, Jt, _, f_ref = _reweighted(orc, p, st.solution, loss, c)
+    rt, Jt, _, f_ref = reweighted(orc, p, st.solution, loss, c)
     assert abs(st.objective - f_ref) <= 1e-12 * f_ref, f"objective {st.objective!r} vs numpy {f_ref!r}"
     g = np.linalg.norm(Jt.T @ rt)
     feas = st.dual_feas if variant == 1 else st.primal_feas
@@ -328,7 +253,7 @@ def _outlier_problem(ba):
 
 
 def _inlier_rms(orc, p, x, inl):
-    r = _residual(orc, p, x).reshape(-1, 2)[inl]
+    r = residual(orc, p, x).reshape(-1, 2)[inl]
     return float(np.sqrt(np.mean(np.sum(r * r, axis=1))))
 
 
@@ -340,87 +265,20 @@ def test_robust_loss_resists_outliers(ba, orc, gpu_ok):
     5.3 x (a numpy IRLS run to the first-order test; the default stop here gives 4.8 x, the numpy run of the same controller
     4.8046 x as well): it is held to halving the linear loss's error."""
     q, clean, inl = _outlier_problem(ba)
-    m = ba.BALNLPModel(arrays=_arrays(clean))
-    st = _solve(ba, m)
+    m = ba.BALNLPModel(arrays=arrays(clean))
+    st = solve(ba, m)
     m.close()
     rms_clean = _inlier_rms(orc, q, st.solution, inl)
     got = {}
     for loss in ("linear", "huber", "cauchy"):
-        m = ba.BALNLPModel(arrays=_arrays(q))
-        st = _solve(ba, m, loss=loss, f_scale=2.0)
+        m = ba.BALNLPModel(arrays=arrays(q))
+        st = solve(ba, m, loss=loss, f_scale=2.0)
         m.close()
         got[loss] = _inlier_rms(orc, q, st.solution, inl)
     print(f"inlier RMS: clean {rms_clean:.4f} px; " + ", ".join(f"{k} {v:.4f} ({v / rms_clean:.3f} x)" for k, v in got.items()))
     assert got["cauchy"] <= 1.05 * rms_clean
     assert got["linear"] >= 1.5 * rms_clean
     assert got["huber"] <= 0.5 * got["linear"]
-
-
-# ---- several ranks over the in-process loopback transport (fixture of test_gpu_determinism.py) -------------------------------
-@pytest.fixture(scope="module")
-def loopback(gpu_ok):
-    assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-    L = C.CDLL(LOOPBACK)
-    L.ba_loopback_create.restype = C.c_void_p
-    L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-    L.ba_loopback_destroy.argtypes = [C.c_void_p]
-    L.ba_loopback_rank.restype = C.c_void_p
-    L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-    L.ba_loopback_ops.restype = C.c_long
-    L.ba_loopback_ops.argtypes = [C.c_void_p]
-    return L
-
-
-class _Ranks:
-    """`world` shards of one problem as handles in this process, attached to one loopback communicator."""
-
-    def __init__(self, ba, L, prob, world, stage_mb=64):
-        self.ba, self.L, self.world, self.prob = ba, L, world, prob
-        arrays = ba.synthetic.as_arrays(prob)
-        self.loop = L.ba_loopback_create(world, stage_mb << 20)
-        assert self.loop, "loopback communicator could not be created"
-        hook = C.cast(L.ba_loopback_hook, ba._lib.COMM_CB)
-        self.shards, self.models = [], []
-        for r in range(world):
-            local, info = ba.parallel.shard_problem(arrays, r, world)
-            m = ba.BALNLPModel(arrays=local, device=0)
-            ba._lib.check(ba._lib.lib().ba_lm_set_comm_hook(m.handle, r, world, hook, L.ba_loopback_rank(self.loop, r)))
-            self.shards.append((local, info))
-            self.models.append(m)
-
-    def step(self, lam, **kw):
-        """one sharded LM step, every rank on its own host thread -> (global delta from rank 0's cameras, per-rank camera
-        parts, model value)"""
-        out, err = [None] * self.world, [None] * self.world
-
-        def run(r):
-            try:
-                out[r] = self.ba.lm_step(self.models[r], self.shards[r][0][3], lam, **kw)
-            except Exception as e:  # noqa: BLE001 -- reported below with the rank
-                err[r] = e
-
-        ts = [threading.Thread(target=run, args=(r,)) for r in range(self.world)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        bad = [(r, e) for r, e in enumerate(err) if e is not None]
-        assert not bad, f"rank(s) failed: {bad}"
-        ncams, npnts = self.prob["ncams"], self.prob["npnts"]
-        delta = np.zeros(3 * npnts + 9 * ncams)
-        cams = []
-        for r in range(self.world):
-            pb, pe = self.shards[r][1]["point_range"]
-            d = out[r][0]
-            delta[3 * pb:3 * pe] = d[:3 * (pe - pb)]
-            cams.append(d[3 * (pe - pb):].copy())
-        delta[3 * npnts:] = cams[0]
-        return delta, cams, out[0][1]
-
-    def close(self):
-        for m in self.models:
-            m.close()
-        self.L.ba_loopback_destroy(self.loop)
 
 
 @pytest.mark.gpu
@@ -435,7 +293,7 @@ def test_loopback_huber_step_equals_one_rank(ba, loopback, world):
     d_ref, half_ref, _ = ba.lm_step(ref, prob["x0"], lam, loss="huber", f_scale=c)
     _, f_ref = ref.robust_weights(prob["x0"], "huber", c)
     ref.close()
-    R = _Ranks(ba, loopback, prob, world)
+    R = Ranks(ba, loopback, prob, world)
     try:
         d, cams, half = R.step(lam, loss="huber", f_scale=c)
         e = rel_err(d, d_ref)

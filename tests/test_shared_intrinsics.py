@@ -1,8 +1,8 @@
 """Shared camera intrinsics of the LM solve (ba_lm_set_shared_intrinsics, include/ba_hip.h): calibration groups whose
 members share one (k1, k2, f), x = E z.  The reference is numpy (tests/helpers/shared_ref.py): the oracle's residual and Jacobian,
 the reweighting, mask and prior rows of tests/test_priors.py, E as a scipy sparse matrix, the dense solve over z and a dense LM
-loop over z.  Step limit everywhere: max(tol, 100 kappa eps), the rule of tests/test_priors.py::_limit, kappa the condition number
-of the Jacobi-scaled reduced camera system over z; tol = _STEP_TOL[lambda] for :LDL and PCG_TOL for pcg = (1e-12, 5000).  Model
+loop over z.  Step limit everywhere: max(tol, 100 kappa eps), the rule of tests/_lm_ref.py::limit, kappa the condition number
+of the Jacobi-scaled reduced camera system over z; tol = STEP_TOL[lambda] for :LDL and PCG_TOL for pcg = (1e-12, 5000).  Model
 value and gradient: the relative limits of tests/test_priors.py::test_prior_step_vs_dense_numpy (1e-10, 1e-12; the PCG step's own
 model value 1e-7).  The first tests need no device; the rest run on the GPU."""
 import ctypes as C
@@ -12,9 +12,9 @@ import sys
 import numpy as np
 import pytest
 
+from _lm_ref import (PCG_TOL, STEP_TOL, arrays, attach_loopback, env, fixed_vector, jac, limit, lm_opts, loopback_world, residual,
+                     reweighted, sym)
 from _util import bits_report, parity_record, rel_err
-from test_priors import LOOPBACK, PCG_TOL, _arrays, _env, _fixed_vector, _limit, _sym
-from test_robust_loss import _STEP_TOL, _jac, _residual, _reweighted
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
@@ -40,7 +40,7 @@ def _ref(orc, p, groups, x, lam, pri=None, fixed=None, loss="linear", c=1.0, key
     """shared_ref.step at (x, lambda), computed once per key"""
     if key is not None and key in _cache:
         return _cache[key]
-    rt, Jt, _, _ = _reweighted(orc, p, x, loss, c)
+    rt, Jt, _, _ = reweighted(orc, p, x, loss, c)
     rows = pr.rows(x, p["ncams"], p["npnts"], fixed=fixed, **(pri or {}))
     out = sr.step(Jt, rt, lam, rows, groups, p["ncams"], p["npnts"], fixed)
     if key is not None:
@@ -151,13 +151,13 @@ def test_make_problem_default_is_unchanged_and_groups_share(ba, small_prob):
 @pytest.mark.parametrize("which", ["A", "B"])
 def test_reference_bordered_solve_agrees_with_dense_z(ba, orc, which):
     """shared_ref.bordered -- the algebra the device runs -- against shared_ref.step's dense solve over z, camera part of the
-    step, at every lambda of _STEP_TOL, within max(_STEP_TOL[lambda], 100 kappa eps)"""
+    step, at every lambda of STEP_TOL, within max(STEP_TOL[lambda], 100 kappa eps)"""
     p, groups = _scene(ba, which)
     np3 = 3 * p["npnts"]
-    for lam, tol in _STEP_TOL.items():
+    for lam, tol in STEP_TOL.items():
         ref = _ref(orc, p, groups, p["x0"], lam, key=(which, lam))
         a = sr.bordered(ref["H"], ref["g"], lam, groups, p["ncams"], p["npnts"])
-        e, lim = rel_err(a, ref["delta"][np3:]), _limit(tol, ref["kappa"])
+        e, lim = rel_err(a, ref["delta"][np3:]), limit(tol, ref["kappa"])
         print(f"bordered[{which}] lambda {lam:g}: kappa {ref['kappa']:.3e}  error {e:.3e} (limit {lim:.1e})")
         assert e <= lim
 
@@ -167,16 +167,16 @@ def test_reference_bordered_solve_agrees_with_dense_z(ba, orc, which):
 @pytest.mark.parametrize("which", ["A", "B"])
 def test_shared_step_vs_dense_numpy(ba, orc, gpu_ok, which):
     p, groups = _scene(ba, which)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             ref = _ref(orc, p, groups, p["x0"], lam, key=(which, lam))
             d, half, jtr = ba.lm_step(m, p["x0"], lam, shared_intrinsics=groups)
             dp, halfp, jtrp, its = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), shared_intrinsics=groups)
             e, ep = rel_err(d, ref["delta"]), rel_err(dp, ref["delta"])
             em = abs(half - ref["model"]) / ref["model"]
             eg = float(np.linalg.norm(jtr - ref["grad"]) / np.linalg.norm(ref["grad"]))
-            lim, limp = _limit(tol, ref["kappa"]), _limit(PCG_TOL, ref["kappa"])
+            lim, limp = limit(tol, ref["kappa"]), limit(PCG_TOL, ref["kappa"])
             print(f"shared_step[{which}] lambda {lam:g}: kappa {ref['kappa']:.3e}  LDL {e:.3e} (limit {lim:.1e})  pcg {ep:.3e} "
                   f"({limp:.1e}, {its} its)  model {em:.3e}  jtr {eg:.3e}")
             parity_record(f"shared_step[{which}-{lam:g}]", kappa=ref["kappa"], ldl=e, ldl_limit=lim, pcg=ep, pcg_limit=limp, model=em,
@@ -220,7 +220,7 @@ def test_no_grouping_paths_give_the_plain_bits(ba, gpu_ok):
     """all labels 0, None and groups of one camera run the plain path: delta, model and jtr bit-identical to the call without
     the keyword; after a shared step and a clear the plain bits are back, for the direct and the PCG entry"""
     p, groups = _scene(ba, "A")
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for kw in ({}, {"pcg": (1e-10, 200)}):
             plain = ba.lm_step(m, p["x0"], 1.0, **kw)
@@ -244,7 +244,7 @@ def test_no_grouping_paths_give_the_plain_bits(ba, gpu_ok):
 def test_c_abi_label_checks(ba, gpu_ok):
     p, _ = _scene(ba, "A")
     L = ba._lib.lib()
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lab, text in (([0, -1] + [0] * 10, "must be 0"), ([9, 9] + [0] * 10, "must be 0"), ([1, 1, 3, 3] + [0] * 8, "gap")):
             a = np.array(lab, dtype=np.int32)
@@ -265,15 +265,15 @@ def test_shared_step_with_fixed_intrinsics(ba, orc, gpu_ok):
     every = [list(range(1, p["ncams"] + 1))]
     x = ba.tie_intrinsics(p["x0"], p["npnts"], every)
     mask = dict(fixed_camera_params=("k1", "k2", "f"))
-    fixed = _fixed_vector(ba, p, mask)
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    fixed = fixed_vector(ba, p, mask)
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             ref = _ref(orc, p, every, x, lam, fixed=fixed)
             unshared = ba.lm_step(m, x, lam, **mask)
             for kw, t in (({}, tol), ({"pcg": (1e-12, 5000)}, PCG_TOL)):
                 d, half, jtr = ba.lm_step(m, x, lam, shared_intrinsics=every, **mask, **kw)[:3]
-                lim = _limit(t, ref["kappa"])
+                lim = limit(t, ref["kappa"])
                 e, e_ref = rel_err(d, unshared[0]), rel_err(d, ref["delta"])
                 print(f"shared_fixed lambda {lam:g} {'pcg' if kw else 'LDL'}: vs unshared {e:.3e}, vs numpy {e_ref:.3e} (limit {lim:.1e})")
                 assert e <= lim and e_ref <= lim
@@ -294,12 +294,12 @@ def test_shared_step_with_fixed_intrinsics(ba, orc, gpu_ok):
 @pytest.mark.gpu
 def test_shared_step_with_huber(ba, orc, gpu_ok):
     p, groups = _scene(ba, "A")
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             ref = _ref(orc, p, groups, p["x0"], lam, loss="huber", c=1.0)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss="huber", f_scale=1.0, shared_intrinsics=groups)
-            e, lim = rel_err(d, ref["delta"]), _limit(tol, ref["kappa"])
+            e, lim = rel_err(d, ref["delta"]), limit(tol, ref["kappa"])
             em = abs(half - ref["model"]) / ref["model"]
             eg = float(np.linalg.norm(jtr - ref["grad"]) / np.linalg.norm(ref["grad"]))
             print(f"shared_huber lambda {lam:g}: kappa {ref['kappa']:.3e}  step {e:.3e} (limit {lim:.1e})  model {em:.3e}  jtr {eg:.3e}")
@@ -321,20 +321,20 @@ def test_shared_step_with_priors(ba, orc, gpu_ok):
     cams = p["x_true"][np3:].reshape(-1, 9)
     Bm = rng.standard_normal((9, 9))
     scale = np.maximum(np.abs(cams[6]), 1e-3)
-    info = _sym((Bm @ Bm.T + 9 * np.eye(9)) / (0.01 * scale[:, None] * 0.01 * scale[None, :]))
+    info = sym((Bm @ Bm.T + 9 * np.eye(9)) / (0.01 * scale[:, None] * 0.01 * scale[None, :]))
     cidx = np.array([12, 31])
     pri = dict(camera_priors=(np.array([7]), cams[6][None] * (1 + 1e-3), info[None]),
                centre_priors=(cidx, np.stack([pr.centre(cams[i - 1]) for i in cidx]) + 0.01, np.full((2, 3), 0.01)))
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
-        for lam, tol in _STEP_TOL.items():
+        for lam, tol in STEP_TOL.items():
             ref = _ref(orc, p, groups, p["x0"], lam, pri=pri)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, shared_intrinsics=groups, **pri)
             dp, halfp, jtrp, its = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), shared_intrinsics=groups, **pri)
             e, ep = rel_err(d, ref["delta"]), rel_err(dp, ref["delta"])
             em = abs(half - ref["model"]) / ref["model"]
             eg = float(np.linalg.norm(jtr - ref["grad"]) / np.linalg.norm(ref["grad"]))
-            lim, limp = _limit(tol, ref["kappa"]), _limit(PCG_TOL, ref["kappa"])
+            lim, limp = limit(tol, ref["kappa"]), limit(PCG_TOL, ref["kappa"])
             print(f"shared_priors lambda {lam:g}: kappa {ref['kappa']:.3e}  LDL {e:.3e} (limit {lim:.1e})  pcg {ep:.3e} ({limp:.1e}, "
                   f"{its} its)  model {em:.3e}  jtr {eg:.3e}")
             parity_record(f"shared_priors[{lam:g}]", kappa=ref["kappa"], ldl=e, ldl_limit=lim, pcg=ep, pcg_limit=limp, model=em, jtr=eg)
@@ -357,16 +357,16 @@ def test_shared_step_block_sparse_schedule(ba, orc, gpu_ok):
     p["x0"] = ba.tie_intrinsics(p["x0"], p["npnts"], groups)
     lam = 1.0
     ref = _ref(orc, p, groups, p["x0"], lam)
-    lim = _limit(_STEP_TOL[lam], ref["kappa"])
+    lim = limit(STEP_TOL[lam], ref["kappa"])
     for flag in ("1", "0"):
         def run():
-            m = ba.BALNLPModel(arrays=_arrays(p))
+            m = ba.BALNLPModel(arrays=arrays(p))
             try:
                 return ba.lm_step(m, p["x0"], lam, shared_intrinsics=groups), ba.schur_pattern(m), ba.schur_ordering_used(m)[1]
             finally:
                 m.close()
 
-        (d, half, jtr), pat, order = _env("BA_SPARSE_S", flag, run)
+        (d, half, jtr), pat, order = env("BA_SPARSE_S", flag, run)
         assert pat[2] == (flag == "1"), "the schedule asked for was not used"
         e = rel_err(d, ref["delta"])
         print(f"shared_step_sparse[BA_SPARSE_S={flag}]: ordering {order}, kappa {ref['kappa']:.3e}  step {e:.3e} (limit {lim:.1e})")
@@ -379,7 +379,7 @@ def test_shared_step_block_sparse_schedule(ba, orc, gpu_ok):
 
 def _fun(orc, p):
     def f(x):
-        r, J = _residual(orc, p, x), _jac(orc, p, x).toarray()
+        r, J = residual(orc, p, x), jac(orc, p, x).toarray()
         return 0.5 * (r @ r), J.T @ r, J.T @ J, lambda d: 0.5 * np.sum((J @ d + r) ** 2)
     return f
 
@@ -395,7 +395,7 @@ def test_shared_solve(ba, orc, gpu_ok, variant, facto):
     if key not in _cache:
         _cache[key] = sr.lm_dense_z(_fun(orc, p), p["x0"], groups, p["ncams"], p["npnts"], variant=variant)
     x_ref, status_ref, it_ref, f_loop, g_loop = _cache[key]
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         args = (facto, "AMD", "None") + ((False,) if variant == 1 else ())
         kw = dict(pcg_tol=1e-13) if facto == "PCG" else {}
@@ -414,7 +414,7 @@ def test_shared_solve(ba, orc, gpu_ok, variant, facto):
     assert ef <= 1e-12, f"objective {st.objective!r} vs numpy {f!r}"
     assert eg <= 1e-10, f"|E'g| {feas!r} vs numpy {g_ref!r}"
     assert not bits_report(ba.tie_intrinsics(st.solution, p["npnts"], groups), st.solution, "members of a group in the solution")
-    assert f < 0.5 * np.sum(_residual(orc, p, p["x0"]) ** 2)
+    assert f < 0.5 * np.sum(residual(orc, p, p["x0"]) ** 2)
 
 
 @pytest.mark.gpu
@@ -423,7 +423,7 @@ def test_untied_x_is_refused(ba, gpu_ok):
     x = np.array(p["x0"])
     x[3 * p["npnts"] + 9 * 8 + 7] *= 1 + 1e-15  # k2 of camera 9, a member of group 2
     lib = ba._lib.lib()
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         with pytest.raises(ValueError, match="camera 9 "):
             ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, x=x, shared_intrinsics=groups)
@@ -433,21 +433,12 @@ def test_untied_x_is_refused(ba, gpu_ok):
         d, half = np.empty_like(x), C.c_double(0)
         assert lib.ba_lm_step(m.handle, ba._lib.ptr(x), 1.0, ba._lib.ptr(d), C.byref(half), None) == 1
         assert "camera 9 " in lib.ba_last_error().decode()
-        o = _opts(ba)
+        o = lm_opts(ba)
         st = ba._lib.LMStats()
         assert lib.ba_lm_solve(m.handle, C.byref(o), ba._lib.ptr(x), C.byref(st), C.cast(None, ba._lib.LOG_CB), None) == 1
         assert "camera 9 " in lib.ba_last_error().decode()
     finally:
         m.close()
-
-
-def _opts(ba, **kw):
-    o = ba._lib.LMOpts(variant=1, facto=0, normalize=0, linesearch=0, facto_type=0, ite_max=-1, verbose=0, x_f32=0, restol=-1,
-                       satol=-1, srtol=-1, oatol=-1, ortol=-1, atol=-1, rtol=-1, nu_d=-1, nu_m=-1, lam=-1, delta_d=-1, max_time=-1,
-                       pcg_tol=-1, pcg_max_iter=-1, perm=0)
-    for k, v in kw.items():
-        setattr(o, k, v)
-    return o
 
 
 @pytest.mark.gpu
@@ -456,8 +447,8 @@ def test_refused_combinations_on_the_device(ba, gpu_ok):
     BA_ERR_ARG, the message naming the combination; the handle steps as before afterwards"""
     p, groups = _scene(ba, "A")
     lib = ba._lib.lib()
-    m = ba.BALNLPModel(arrays=_arrays(p))
-    m32 = ba.BALNLPModel(arrays=_arrays(p), T=np.float32)
+    m = ba.BALNLPModel(arrays=arrays(p))
+    m32 = ba.BALNLPModel(arrays=arrays(p), T=np.float32)
     try:
         before = ba.lm_step(m, p["x0"], 1.0, shared_intrinsics=groups)
         with pytest.raises(ValueError, match="shared_intrinsics.*Float32 model"):
@@ -467,7 +458,7 @@ def test_refused_combinations_on_the_device(ba, gpu_ok):
         for kw, text in ((dict(linesearch=1), "linesearch = true"), (dict(x_f32=1), "Float32 model"), (dict(facto_type=1), "facto_type"),
                          (dict(facto_type=2), "facto_type"), (dict(normalize=1), "normalize"), (dict(normalize=2), "normalize")):
             st = ba._lib.LMStats()
-            o = _opts(ba, **kw)
+            o = lm_opts(ba, **kw)
             rc = lib.ba_lm_solve(m.handle, C.byref(o), ba._lib.ptr(x), C.byref(st), C.cast(None, ba._lib.LOG_CB), None)
             msg = lib.ba_last_error().decode()
             assert rc == 1 and "shared intrinsics" in msg and text in msg, (kw, rc, msg)
@@ -487,36 +478,26 @@ def test_refused_combinations_on_the_device(ba, gpu_ok):
         m.close()
         m32.close()
     # a communicator (attached before the handle's first solve, as documented)
-    assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-    L = C.CDLL(LOOPBACK)
-    L.ba_loopback_create.restype = C.c_void_p
-    L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-    L.ba_loopback_destroy.argtypes = [C.c_void_p]
-    L.ba_loopback_rank.restype = C.c_void_p
-    L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-    loop = L.ba_loopback_create(1, 16 << 20)
-    assert loop
-    mc = ba.BALNLPModel(arrays=_arrays(p))
-    try:
-        hook = C.cast(L.ba_loopback_hook, ba._lib.COMM_CB)
-        ba._lib.check(lib.ba_lm_set_comm_hook(mc.handle, 0, 1, hook, L.ba_loopback_rank(loop, 0)))
-        with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
-            ba.lm_step(mc, p["x0"], 1.0, shared_intrinsics=groups)
-        with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
-            ba.lm_step(mc, p["x0"], 1.0, pcg=(1e-8, 100), shared_intrinsics=groups)
-        with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
-            ba.Levenberg_Marquardt(ba.FeasibilityResidual(mc), "LDL", "AMD", "None", False, shared_intrinsics=groups)
-        plain = ba.lm_step(mc, p["x0"], 1.0)
-        assert np.all(np.isfinite(plain[0]))
-    finally:
-        mc.close()
-        L.ba_loopback_destroy(loop)
+    mc = ba.BALNLPModel(arrays=arrays(p))
+    with loopback_world(1, 16 << 20) as (L, loop):
+        try:
+            attach_loopback(ba, mc, L, loop, 0, 1)
+            with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
+                ba.lm_step(mc, p["x0"], 1.0, shared_intrinsics=groups)
+            with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
+                ba.lm_step(mc, p["x0"], 1.0, pcg=(1e-8, 100), shared_intrinsics=groups)
+            with pytest.raises(ba.BAArgError, match="shared intrinsics.*communicator"):
+                ba.Levenberg_Marquardt(ba.FeasibilityResidual(mc), "LDL", "AMD", "None", False, shared_intrinsics=groups)
+            plain = ba.lm_step(mc, p["x0"], 1.0)
+            assert np.all(np.isfinite(plain[0]))
+        finally:
+            mc.close()
 
 
 @pytest.mark.gpu
 def test_two_shared_steps_give_identical_bits(ba, gpu_ok):
     p, groups = _scene(ba, "B")
-    m = ba.BALNLPModel(arrays=_arrays(p))
+    m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for kw in ({}, {"pcg": (1e-10, 500)}):
             a = ba.lm_step(m, p["x0"], 1.0, shared_intrinsics=groups, **kw)
