@@ -1231,9 +1231,12 @@ __global__ __launch_bounds__(256) void k_ldl_pairdiag(T *__restrict__ S, const i
 }
 
 // one tile of the pair update: S_ij -= V0_i L_jk' + V1_i L_{j,k+1}' (K = 256) by the four waves of a workgroup
+// ticket != null (ticketed k_ldl_update): thread 0 draws from that counter between the K loop and the epilogue -- the
+// round trip hides behind the epilogue's loads and no register carries it through the K loop -- and returns the value
 template <typename T>
-__device__ __forceinline__ void ldl_update_tile(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0, const T *__restrict__ V1,
-                                       int k, int i, int j, T *lds, const T *__restrict__ Lp0, const T *__restrict__ Lp1) {
+__device__ __forceinline__ int ldl_update_tile(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0, const T *__restrict__ V1,
+                                      int k, int i, int j, T *lds, const T *__restrict__ Lp0, const T *__restrict__ Lp1,
+                                      int *__restrict__ ticket = nullptr) {
   BA_VT
   T *Sij = S + tix(co, i, j) * NB * NB;
   typename RT<T>::v4 acc[4][4];
@@ -1247,6 +1250,8 @@ __device__ __forceinline__ void ldl_update_tile(T *__restrict__ S, const int64_t
                         V1 + (int64_t)i * NB * NB, Lp1 ? Lp1 + (int64_t)j * NB * NB : S + tix(co, j, k + 1) * NB * NB, lds, acc);
   int tid2 = threadIdx.x;
   asm volatile("" : "+v"(tid2));  // keep the epilogue's address arithmetic out of the main loop's live ranges
+  int drawn = 0;
+  if (ticket && tid2 == 0) drawn = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const int lane = tid2 & 63, wv = (tid2 >> 6) & 3;
   const int wr = (wv >> 1) * 64, wc = (wv & 1) * 64;
   // epilogue: the 64 values of a lane are read-modify-written in two batches of 32 so that 32 loads are in flight at once
@@ -1270,6 +1275,7 @@ __device__ __forceinline__ void ldl_update_tile(T *__restrict__ S, const int64_t
           cbase[(16 * m + RT<T>::row(lane, g)) * NB + 16 * (2 * h + n2)] = nv;
         }
   }
+  return drawn;
 }
 
 // Bulk trailing update, two panels per pass:  S_ij -= V0_i L_jk' + V1_i L_{j,k+1}'  for the lower-triangular tile pairs
@@ -1292,13 +1298,75 @@ __global__ __launch_bounds__(256, 2) void k_ldl_update(T *__restrict__ S, const 
                                                         const int64_t *__restrict__ own_pref = nullptr, int m0 = 0,
                                                         int m_end = 0, int ready_tiles = 1, const int *__restrict__ rows = nullptr,
                                                         const T *__restrict__ Lp0 = nullptr, const T *__restrict__ Lp1 = nullptr,
-                                                        const int2 *__restrict__ tlist = nullptr, int blocked = TSB) {
+                                                        const int2 *__restrict__ tlist = nullptr, int blocked = TSB,
+                                                        int *__restrict__ tickets = nullptr) {
   // tlist (block-sparse S on several ranks): the tiles (i, j) of this launch, listed (the pattern's tiles of the pair's update
   // in the tile columns this rank owns)
   BA_VT
   static_assert(MODE == 1, "only the pair update is a tile-per-workgroup kernel");
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   T *lds = reinterpret_cast<T *>(smraw);
+  if constexpr (!OWN) {
+    // Ticketed form (tickets != null; plain dense or row-list enumeration only, and always the super-block enumeration:
+    // blocked == 0, the static form's row-major triangle, is taken as TSB): the grid is at most what the device holds
+    // at once, and every workgroup takes tiles until none is left -- ticket_tile / ticket_source, ba_internal.h.  The static
+    // map below gives each XCD an equal share; beside a hoisted workgroup, which keeps one CU of one XCD, that XCD finishes
+    // last and the launch ends with it.  Here its queue is emptied by the others.  A tile is updated by exactly one
+    // workgroup and nothing passes between workgroups, so the bits do not depend on who takes what.  Thread 0 sends the next
+    // draw off inside the current tile's update (ldl_update_tile) and hands the tile it gives over through an LDS word,
+    // alternating between two so that one barrier per tile is enough.
+    if (tickets) {
+      __shared__ int s_next[2], s_src[2];
+      int m_rows = (int)((sqrt(8.0 * (double)nblk + 1.0) - 1.0) * 0.5);  // nblk = m_rows (m_rows + 1) / 2 tiles
+      while ((m_rows + 1) * (m_rows + 2) / 2 <= nblk) m_rows++;
+      while (m_rows * (m_rows + 1) / 2 > nblk) m_rows--;
+      const int nready = ready ? ready_tiles : 0;
+      // HW_REG_XCC_ID (id 20), bits 3:0: the XCD this workgroup runs on (blockIdx % 8 only says which blocks share one)
+      const int xcd = (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | ((4 - 1) << 11)) & (TICKET_QUEUES - 1));
+      // s_next[par]: the tile of this round, or -1; s_src[par]: the source it came from (index into ticket_source), where the
+      // next draw goes.  Wave 0 turns a draw into a tile in scalar registers (nothing of it may live in vector registers
+      // through the K loop: the kernel has none to spare); from an empty source it goes on to the next one at once.
+      const bool wave0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0;
+      auto take = [&](int src, int drawn, int slot) {
+        const bool first = (threadIdx.x & 63) == 0;
+        int n_raw = __builtin_amdgcn_readfirstlane(drawn), t;
+        for (;;) {
+          t = ticket_tile(nblk, nready, ticket_source(xcd, src), n_raw);
+          if (t >= 0 || src == TICKET_QUEUES) break;
+          src++;
+          int v = 0;
+          if (first) v = __hip_atomic_fetch_add(tickets + ticket_source(xcd, src), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          n_raw = __builtin_amdgcn_readfirstlane(v);
+        }
+        if (first) {
+          s_next[slot] = t;
+          s_src[slot] = src;
+        }
+      };
+      if (wave0) {
+        int v = 0;
+        if (threadIdx.x == 0) v = __hip_atomic_fetch_add(tickets + TICKET_READY, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        take(0, v, 0);
+      }
+      const int sb = blocked > 0 ? blocked : TSB;
+      for (int par = 0;; par ^= 1) {
+        __syncthreads();
+        const int t = __builtin_amdgcn_readfirstlane(s_next[par]);
+        if (t < 0) return;  // every source is empty
+        const int src = __builtin_amdgcn_readfirstlane(s_src[par]);
+        int ii, jj;
+        tri_blocked(t, m_rows, &ii, &jj, sb);
+        const int n_raw = ldl_update_tile<T>(S, co, V0, V1, k, rows ? rows[ii] : base + ii, rows ? rows[jj] : base + jj, lds, Lp0, Lp1,
+                                             tickets + ticket_source(xcd, src));
+        if (ready && t < ready_tiles) {  // (as in the static form below)
+          __threadfence();
+          __syncthreads();
+          if (threadIdx.x == 0) __hip_atomic_fetch_add(ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (wave0) take(src, n_raw, par ^ 1);
+      }
+    }
+  }
   int i, j, tsel;
   {
     // chunked block -> XCD map: blocks b, b+8, ... share an XCD (round-robin dispatch); give each XCD a contiguous
@@ -1363,7 +1431,9 @@ template <typename T>
 constexpr size_t part_lds_bytes() { return 2 * gemm_priv_lds_bytes<T>(); }  // 147 KB: one workgroup per CU
 template <typename T>
 __global__ __launch_bounds__(512) void k_ldl_update_part(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0,
-                                                          const T *__restrict__ V1, int k, int nblk, const int *__restrict__ rows) {
+                                                          const T *__restrict__ V1, int k, int nblk, const int *__restrict__ rows,
+                                                          int base) {
+  // rows == null (dense_ldl_factor): tile rows base, base + 1, ...
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
   T *lds = reinterpret_cast<T *>(smraw + half * gemm_priv_lds_bytes<T>());
@@ -1372,7 +1442,7 @@ __global__ __launch_bounds__(512) void k_ldl_update_part(T *__restrict__ S, cons
     while ((ii + 1) * (ii + 2) / 2 <= t) ii++;
     while (ii * (ii + 1) / 2 > t) ii--;
     const int jj = t - ii * (ii + 1) / 2;
-    ldl_update_tile<T>(S, co, V0, V1, k, rows[ii], rows[jj], lds, nullptr, nullptr);
+    ldl_update_tile<T>(S, co, V0, V1, k, rows ? rows[ii] : base + ii, rows ? rows[jj] : base + jj, lds, nullptr, nullptr);
   }
 }
 
@@ -1764,6 +1834,13 @@ int dense_ldl_alloc(DenseLDLT<T> *w, int64_t n_unpadded, int world, int rank, bo
   BA_CHECK(w->D.alloc(nt * NB * 2));  // D | y scratch
   BA_CHECK(w->flag.alloc(1));
   BA_CHECK(w->ready.alloc(nt));
+  BA_CHECK(w->tickets.alloc((nt / 2 + 1) * TICKET_SLOTS));
+  {
+    int dev = 0, cus = 0;
+    BA_HIP_CHECK(hipGetDevice(&dev));
+    BA_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    w->wg_slots = 2 * std::max(cus, 1);  // __launch_bounds__(256, 2) and 73.7 KB of LDS: two workgroups per CU
+  }
   BA_CHECK(w->hoist.create(hipStreamNonBlocking));
   {  // the stream of the block-sparse schedule's look-ahead: lowest priority, so that the panel chain's kernels are placed first
     int lo = 0, hi = 0;
@@ -1864,7 +1941,7 @@ static int update_rs_max() {
 // the first ready_tiles tiles are final (hoisted-diagonal schedule; never in the row-split form)
 template <typename T>
 static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, const T *V1, hipStream_t st,
-                       int *ready = nullptr, int ready_tiles = 1) {
+                       int *ready = nullptr, int ready_tiles = 1, int *tickets = nullptr) {
   const int nblk = count * (count + 1) / 2;
   if (nblk <= 0) return BA_OK;
   if (!ready && nblk <= update_rs_max()) {  // short update: row-split form (see k_ldl_update_rs)
@@ -1882,9 +1959,12 @@ static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, i
   // (Cutting the tiles of a partly filled last round into 64 x 64 quadrants, one workgroup each, was tried and removed:
   // 34.1-34.3 ms against 33.9-34.1 at n = 16 002.  A partial round does not cost a full one -- the quadrant kernel took
   // 39 us on average, which is what the big kernel's own last round costs.)
-  hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S,
+  // tickets (dense_ldl_factor): this launch's counters, cleared -- persistent workgroups, at most what the device holds at once
+  // (beside a hoisted workgroup, which keeps one CU, two of them fewer: they would only start when the others leave)
+  const int grid = tickets ? std::min(std::max(w->wg_slots - (ready ? 2 : 0), 1), nblk) : ((nblk + 7) / 8) * 8;
+  hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(grid), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S,
                      w->col_off, V0, V1, k, k + 2, (int)w->nt, nblk, ready, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
-                     ready_tiles, rows);
+                     ready_tiles, rows, (const T *)nullptr, (const T *)nullptr, (const int2 *)nullptr, TSB, tickets);
   return BA_OK;
 }
 
@@ -1922,6 +2002,71 @@ static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0,
   return BA_OK;
 }
 
+// ---- look-ahead of one pair (dense_ldl_factor_sparse: "Look-ahead of one pair"; dense_ldl_factor below its fused zone) ------
+constexpr int REST_CUS = 224;  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
+// ... of dense_ldl_factor's tail, whose chain's panel solves have up to ~180 workgroups of their own, and the tiles of a rest
+// from which it forks (Venice, ms per LM iteration: 128 / 160 / 192 / 224 CUs -> 35.88 / 35.53-35.70 / 35.34-35.38 / 35.35-35.38;
+// 48 / 96 / 160 tiles -> 35.34-35.41 / 35.34-35.38 / 35.30-35.45: indifferent, the list schedule's value is kept)
+constexpr int TAIL_REST_CUS = 192, TAIL_AHEAD_MIN_TILES = 96;
+static int rest_grid(int ntile, int cus = REST_CUS) { return (ntile + 1) / 2 < cus ? (ntile + 1) / 2 : cus; }  // two tiles per workgroup
+
+// The look-ahead's split of pair r's trailing update: the first nlead rows of U_q are the next pair's own tile columns
+// (k+2, k+3: at the head of the ascending list); the lead strip is the lead_tiles tiles of those columns, the rest the
+// rest_tiles lower tiles over the remaining rows.
+struct UpdateSplit {
+  int nlead, lead_tiles, rest_tiles;
+};
+static UpdateSplit update_split(const PairRows &r) {
+  int nlead = 0;
+  while (nlead < r.c2 && nlead < 2 && r.row(1 + nlead) < r.k + 4) nlead++;
+  const int nrest = r.c2 - nlead;
+  return {nlead, nlead == 0 ? 0 : (nlead == 1 ? r.c2 : 2 * r.c2 - 1), nrest * (nrest + 1) / 2};
+}
+
+
+// The events of the look-ahead: rest(q) runs on w->rest behind ev_recv[slot] (the pair's panels complete, its lead tiles
+// updated) and is joined through ev_upd[slot], slot = the pair's panel buffers.
+template <typename T>
+struct RestAhead {
+  DenseLDLT<T> *w;
+  hipStream_t st;
+  bool pending[2] = {false, false};  // rest of the pair in that slot launched on the second stream and not yet joined
+  int join(int slot) {
+    if (pending[slot]) {
+      BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_upd[slot], 0));
+      pending[slot] = false;
+    }
+    return BA_OK;
+  }
+  // the lead of the pair is on the main stream: its rest starts behind it on the second stream, beside the next chain
+  int fork(int slot) {
+    BA_HIP_CHECK(hipEventRecord(w->ev_recv[slot], st));
+    BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
+    return BA_OK;
+  }
+  int launched(int slot) {
+    BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
+    pending[slot] = true;
+    return BA_OK;
+  }
+};
+
+// pair r's trailing update split for the look-ahead: the lead first, alone on the chip (beside the rest it takes as long as
+// the whole update: measured), then the rest on at most rest_cus CUs beside the next chain
+template <typename T>
+static int launch_pair_ahead(ba_problem *p, DenseLDLT<T> *w, RestAhead<T> &la, const PairRows &r, const UpdateSplit &s, int slot, const T *V0,
+                             const T *V1, int rest_cus) {
+  if (s.nlead > 0) {
+    ProfScope ps(p, PC_LDL_UPDATE_RS, la.st);
+    hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * s.lead_tiles), dim3(256), RS_LDS_ELEMS * sizeof(T), la.st, w->S, w->col_off, V0, V1, r.k,
+                       r.k + 2, s.lead_tiles, r.rows2, r.c2);
+  }
+  BA_CHECK(la.fork(slot));
+  hipLaunchKernelGGL(k_ldl_update_part<T>, dim3(rest_grid(s.rest_tiles, rest_cus)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off, V0,
+                     V1, r.k, s.rest_tiles, r.rows2 ? r.rows2 + s.nlead : nullptr, r.k + 2 + s.nlead);
+  return la.launched(slot);
+}
+
 // Two panels per pass over the trailing matrix:
 //   diag(k) trsm(k) | column update of tile column k+1 | diag(k+1) trsm(k+1) | pair update of everything right of k+1.
 //
@@ -1933,6 +2078,13 @@ static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0,
 // n = 16002).  Nothing throughput-bound is moved and no CU mask is involved.  (A full look-ahead -- whole panel chain on a
 // priority stream, bulk on a CU-masked stream -- measured 40-51 ms; masking only 1 / 2 / 4 of the 256 CUs off the bulk
 // stream for a hoisted diagonal kernel 42 / 46 / 59 ms: CU-masked streams are slow here, and that code is gone.)
+//
+// The schedule by zone, pair k of nt tile rows (defaults): nt - k >= FUSE_MIN_TILES: fused pair (hoisted k_ldl_pairdiag,
+// k_ldl_pairtrsm, whole update by tickets); below: chain in order, lead strip + diag(k+2) on the main stream, rest of the update
+// on w->rest beside the next chain (look-ahead; rests under TAIL_AHEAD_MIN_TILES tiles: whole update in order).  The last fused
+// pair keeps its whole update with the hoisted single diagonal tile.  nt < HOIST_MIN_TILES + 2: no hoisting, the look-ahead
+// over the whole factorisation (recorded into the caller's graph).  nt > HOIST_MAX_TILES: in order, whole updates, down to the
+// last FUSE_MIN_TILES tile rows, the look-ahead below.  BA_LDL_HOIST=0, or after a hoisted workgroup gave up: strictly in order.
 template <typename T>
 int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b);
 
@@ -1960,14 +2112,36 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
   constexpr int FUSE_MIN_TILES = 48;
   static const bool fuse_off = env_off("BA_LDL_FUSE");
   auto fused = [&](int k) { return w->hoisting && !fuse_off && k >= 2 && k + 1 < nt && nt - k >= FUSE_MIN_TILES; };
+  // Tickets of the bulk pair update (k_ldl_update; BA_LDL_TICKETS=0: its static map): one set of counters per pair, cleared
+  // here once -- in order and when the factorisation is recorded into a graph too.  Read per call: a test compares both.
+  const bool tickets_on = !env_off("BA_LDL_TICKETS") && (nt - 2) * (nt - 1) / 2 > update_rs_max();
+  if (tickets_on) BA_HIP_CHECK(hipMemsetAsync(w->tickets, 0, (size_t)(nt / 2 + 1) * TICKET_SLOTS * sizeof(int), st));
+  // Look-ahead below the fused zone (BA_LDL_TAIL_LOOKAHEAD=0 disables, read per call; never with per-kernel profiling or on
+  // a communicator): a pair that is not fused runs its whole chain in order, five launches of one to a few dozen workgroups,
+  // and its update no longer fills the chip.  There the update is split as in the list schedule (dense_ldl_factor_sparse,
+  // "Look-ahead of one pair": same events, same order of the updates on every tile, same bits): the lead strip -- tile
+  // columns k+2, k+3 -- and diag(k+2) on the main stream, the rest on w->rest beside the next pair's chain.  The last fused
+  // pair's update stays whole, and with BA_LDL_FUSE=0 the hoisted single diagonal tile keeps its schedule.  Rests shorter
+  // than BA_LDL_TAIL_LOOKAHEAD_MIN tiles stay in order.
+  // Where the line is: only pairs with nt - k < FUSE_MIN_TILES, whatever the reason a longer pair is not fused (nt above
+  // HOIST_MAX_TILES: its large updates fill the chip and stay whole, in order, through the ticketed kernel -- on a part of the
+  // chip they lose); and never with BA_LDL_HOIST=0 or after a hoisted workgroup gave up (hoist_disabled), which
+  // stay strictly in order at every size.
+  const bool tail_ahead = !p->prof_on && !p->comm.active() && !hoist_off && !w->hoist_disabled && !(w->hoisting && fuse_off) &&
+                          !env_off("BA_LDL_TAIL_LOOKAHEAD");
+  const int ahead_min = env_int("BA_LDL_TAIL_LOOKAHEAD_MIN", TAIL_AHEAD_MIN_TILES);
+  RestAhead<T> la{w, st};
   launch_diag(p, w, 0, st, nullptr, !w->hoisting);
   for (int k = 0, slot = 0; k < nt; k += 2, slot ^= 1) {
     const PairRows r = pair_rows(w, k / 2);
     T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
     const bool more = k + 2 < nt;
     const bool next_fused = more && fused(k + 2);
-    const bool next_hoist1 = more && !next_fused && w->hoisting && (nt - k - 2 >= HOIST_MIN_TILES);
+    const UpdateSplit s = update_split(r);
+    const bool ahead = tail_ahead && more && !fused(k) && !next_fused && nt - k < FUSE_MIN_TILES && s.rest_tiles >= std::max(ahead_min, 1);
+    const bool next_hoist1 = more && !next_fused && !ahead && w->hoisting && (nt - k - 2 >= HOIST_MIN_TILES);
     const int need = (k + 3 < nt) ? 3 : 1;
+    BA_CHECK(la.join(slot));  // (the rest of the pair two steps back read these panel buffers)
     if (next_fused) {  // the next pair's leading tiles: waits in place for `need` tiles of this pair's trailing update
       launch_pairdiag(p, w, k + 2, w->vpanel(slot ^ 1, 0), d_b, w->hoist, w->ready + k + 2, need);
       BA_HIP_CHECK(hipEventRecord(w->ev_chain, w->hoist));
@@ -1978,13 +2152,20 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
     if (fused(k)) launch_pairtrsm(p, w, k, V0, V1, d_b, st);
     else panel_chain(p, w, r, V0, V1, d_b, st);  // diag(k) is done: first tile, hoisted, or the in-order branch below
     if (!more) break;
+    BA_CHECK(la.join(slot ^ 1));  // rest(q-1) has updated this pair's tiles too
     const bool hoisted = next_fused || next_hoist1;
-    launch_pair(p, w, k, r.rows2, r.c2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1);
+    if (ahead)
+      BA_CHECK(launch_pair_ahead(p, w, la, r, s, slot, V0, V1, TAIL_REST_CUS));
+    else
+      launch_pair(p, w, k, r.rows2, r.c2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1,
+                  tickets_on ? w->tickets + (k / 2) * TICKET_SLOTS : nullptr);
     if (hoisted)
       BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_chain, 0));  // join: the hoisted workgroup's outputs are written
     else
-      launch_diag(p, w, k + 2, st);
+      launch_diag(p, w, k + 2, st);  // (with the look-ahead: behind the lead, beside the rest)
   }
+  BA_CHECK(la.join(0));
+  BA_CHECK(la.join(1));
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
@@ -2107,22 +2288,6 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
 // with locality 0.13, whose rests are 120 tiles, two runs per launch: 16 / 48 / 96 / 160 / 256 -> 11.8 / 11.8 / 11.8 / 12.7 /
 // 12.7 ms; the Final shape is indifferent).  What shortens the chain itself: two independent runs of pairs advancing in
 // the same launches, below ("Two runs").
-constexpr int REST_CUS = 224;  // CUs the rest may take (sweep: 128 / 192 / 224 -> 76.1 / 71.9 / 71.3 ms on the Final shape)
-static int rest_grid(int ntile) { return (ntile + 1) / 2 < REST_CUS ? (ntile + 1) / 2 : REST_CUS; }  // two tiles per workgroup
-
-// The look-ahead's split of pair r's trailing update: the first nlead rows of U_q are the next pair's own tile columns
-// (k+2, k+3: at the head of the ascending list); the lead strip is the lead_tiles tiles of those columns, the rest the
-// rest_tiles lower tiles over the remaining rows.
-struct UpdateSplit {
-  int nlead, lead_tiles, rest_tiles;
-};
-static UpdateSplit update_split(const PairRows &r) {
-  int nlead = 0;
-  while (nlead < r.c2 && nlead < 2 && r.row(1 + nlead) < r.k + 4) nlead++;
-  const int nrest = r.c2 - nlead;
-  return {nlead, nlead == 0 ? 0 : (nlead == 1 ? r.c2 : 2 * r.c2 - 1), nrest * (nrest + 1) / 2};
-}
-
 template <typename T>
 int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
   const int nt = (int)w->nt;
@@ -2134,25 +2299,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
   // read per call: tests compare both schedules in one process, and force the minimum to 1
   const bool lookahead = !p->prof_on && !env_off("BA_SPARSE_LOOKAHEAD");
   const int la_min = env_int("BA_SPARSE_LOOKAHEAD_MIN", 96);
-  bool pending[2] = {false, false};  // rest of pair q (slot q & 1) launched on the second stream and not yet joined
-  auto join_rest = [&](int slot) -> int {
-    if (pending[slot]) {
-      BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_upd[slot], 0));
-      pending[slot] = false;
-    }
-    return BA_OK;
-  };
-  // the lead of pair q is on the main stream: its rest starts behind it on the second stream, beside the next chain
-  auto fork_rest = [&](int slot) -> int {
-    BA_HIP_CHECK(hipEventRecord(w->ev_recv[slot], st));  // both panels of pair q complete, its lead tiles updated
-    BA_HIP_CHECK(hipStreamWaitEvent(w->rest, w->ev_recv[slot], 0));
-    return BA_OK;
-  };
-  auto rest_launched = [&](int slot) -> int {
-    BA_HIP_CHECK(hipEventRecord(w->ev_upd[slot], w->rest));
-    pending[slot] = true;
-    return BA_OK;
-  };
+  RestAhead<T> la{w, st};
   // Two runs (TilePattern::a_clean / b_clean: the ordering eliminated a profile from both ends, ba_order.cpp): the first
   // a_clean pairs and the b_clean pairs from `split` touch disjoint tiles, rows of the right-hand side and panel buffers
   // (run 0 / run 1).  They advance together, pair i of either run in the SAME launches ("two runs per launch" above): one
@@ -2180,7 +2327,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
         hipLaunchKernelGGL(fwd_kernel(d_b, k_ldl_trsm_rs2<T, true>, k_ldl_trsm_rs2<T, false>), dim3(4 * (ca + cb)), dim3(256),
                            RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, pa, pb, 4 * ca, d_b, y);
       };
-      BA_CHECK(join_rest(slot));  // (the rests of the step two back read these panel buffers)
+      BA_CHECK(la.join(slot));  // (the rests of the step two back read these panel buffers)
       diag2(a.k, b.k);
       const RunPanel<T> a0 = panel_of(a.k, VA, a.rows1), b0 = panel_of(b.k, VB, b.rows1);
       trsm2(a0, a.c1, b0, b.c1);
@@ -2191,15 +2338,15 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
       // both runs first, both rests on a part of the chip beside the next step's chain) when the rests are long enough
       const UpdateSplit sa = update_split(a), sb = update_split(b);
       const RunPanel<T> ua = panel_of(a.k, VA, a.rows2), ub = panel_of(b.k, VB, b.rows2);
-      BA_CHECK(join_rest(slot ^ 1));
+      BA_CHECK(la.join(slot ^ 1));
       if (lookahead && i + 1 < both && sa.rest_tiles + sb.rest_tiles >= 2 * la_min) {
         if (sa.lead_tiles + sb.lead_tiles > 0)
           hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (sa.lead_tiles + sb.lead_tiles)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off,
                              ua, sa.lead_tiles, ub, sb.lead_tiles, panel, a.c2, b.c2);
-        BA_CHECK(fork_rest(slot));
+        BA_CHECK(la.fork(slot));
         hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3(rest_grid(sa.rest_tiles + sb.rest_tiles)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
                            panel_of(a.k, VA, a.rows2 + sa.nlead), sa.rest_tiles, panel_of(b.k, VB, b.rows2 + sb.nlead), sb.rest_tiles, panel);
-        BA_CHECK(rest_launched(slot));
+        BA_CHECK(la.launched(slot));
       } else {
         const int na = a.c2 * (a.c2 + 1) / 2, nb2 = b.c2 * (b.c2 + 1) / 2;
         if (na + nb2 <= update_rs_max())
@@ -2209,8 +2356,8 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
                              ua, na, ub, nb2, panel);
       }
     }
-    BA_CHECK(join_rest(0));
-    BA_CHECK(join_rest(1));
+    BA_CHECK(la.join(0));
+    BA_CHECK(la.join(1));
     BA_HIP_CHECK(hipGetLastError());
     for (int q = both; q < pat->a_clean; q++) order.push_back(q);  // the longer run's remainder, then everything else
     for (int q = pat->a_clean; q < pat->split; q++) order.push_back(q);
@@ -2222,31 +2369,21 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
     const PairRows r = pair_rows(w, order[it]);
     const int slot = (int)(it & 1);
     T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
-    BA_CHECK(join_rest(slot));  // (the rest of the pair two steps back read these panel buffers; joined long ago: see lead below)
+    BA_CHECK(la.join(slot));  // (the rest of the pair two steps back read these panel buffers; joined long ago: see lead below)
     launch_diag(p, w, r.k, st, nullptr, !two && r.k == 0);  // (in one chain the first diagonal kernel clears the pivot flag)
     panel_chain(p, w, r, V0, V1, d_b, st);
     if (r.c2 == 0) continue;
     const bool next_adjacent = it + 1 < order.size() && order[it + 1] == order[it] + 1;
     const UpdateSplit s = update_split(r);
-    BA_CHECK(join_rest(slot ^ 1));  // rest(q-1) has updated the lead tiles too (and the next chain reads its columns)
+    BA_CHECK(la.join(slot ^ 1));  // rest(q-1) has updated the lead tiles too (and the next chain reads its columns)
     if (lookahead && next_adjacent && s.rest_tiles >= la_min) {
-      // the lead first, alone on the chip (beside the rest it takes as long as the whole update: measured), then the rest
-      // beside the next chain
-      if (s.nlead > 0) {
-        ProfScope ps(p, PC_LDL_UPDATE_RS, st);
-        hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * s.lead_tiles), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, r.k,
-                           r.k + 2, s.lead_tiles, r.rows2, r.c2);
-      }
-      BA_CHECK(fork_rest(slot));
-      hipLaunchKernelGGL(k_ldl_update_part<T>, dim3(rest_grid(s.rest_tiles)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off, V0, V1,
-                         r.k, s.rest_tiles, r.rows2 + s.nlead);
-      BA_CHECK(rest_launched(slot));
+      BA_CHECK(launch_pair_ahead(p, w, la, r, s, slot, V0, V1, REST_CUS));
     } else {
       launch_pair(p, w, r.k, r.rows2, r.c2, V0, V1, st);
     }
   }
-  BA_CHECK(join_rest(0));
-  BA_CHECK(join_rest(1));
+  BA_CHECK(la.join(0));
+  BA_CHECK(la.join(1));
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }

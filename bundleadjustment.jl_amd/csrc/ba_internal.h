@@ -167,6 +167,25 @@ __host__ __device__ inline void tri_blocked(int t, int m, int *ii, int *jj, int 
   }
 }
 
+// Tickets of the bulk pair update (k_ldl_update, plain dense form): its persistent workgroups draw the launch's nblk tiles
+// (indices of the enumeration above) from nine counters -- one queue per XCD, which covers the contiguous range of
+// per = ceil(nblk / 8) tiles that the static chunked map gives the blocks of one XCD, and the first-come counter
+// TICKET_READY for the first ready_tiles tiles (what a hoisted workgroup waits for; taken off queue 0's range).  The n-th
+// draw (n = the counter's value before its fetch_add) from source src is tile ticket_tile(...), or -1: that source is empty.
+// Every tile belongs to exactly one source and one n, so each is handed out once whatever the order of the draws.
+constexpr int TICKET_QUEUES = 8, TICKET_READY = TICKET_QUEUES;
+constexpr int TICKET_SLOTS = 16;  // ints per launch: the nine counters, padded to a 64-byte line
+__host__ __device__ inline int ticket_tile(int nblk, int ready_tiles, int src, int n) {
+  const int nready = ready_tiles < nblk ? ready_tiles : nblk;
+  if (src == TICKET_READY) return n < nready ? n : -1;
+  const int per = (nblk + TICKET_QUEUES - 1) / TICKET_QUEUES;
+  const int lo = src * per > nready ? src * per : nready;
+  const int hi = (src + 1) * per < nblk ? (src + 1) * per : nblk;
+  return n < hi - lo ? lo + n : -1;
+}
+// the sources a workgroup on XCD xcd draws from, in order: s = 0 the ready counter, then its own queue, then the others cyclically
+__host__ __device__ inline int ticket_source(int xcd, int s) { return s == 0 ? TICKET_READY : (xcd + s - 1) % TICKET_QUEUES; }
+
 __host__ __device__ inline int64_t tix(const int64_t *__restrict__ col_off, int64_t i, int64_t j) {
   const int64_t n = col_off[-1];
   return col_off[j] + (n ? col_off[n + i * n + j] : (i - j));
@@ -234,6 +253,8 @@ struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*nc
   DevBuf<double> flag_sum;              // device double: the pivot flag on its way through the all-reduce
   DevBuf<int> flag;        // device int: set to 1 on an exactly zero pivot (2: a hoisted diagonal tile never became ready)
   DevBuf<int> ready;       // nt device ints: tile (k,k) has received its last trailing update (hoisted-diagonal schedule)
+  DevBuf<int> tickets;     // TICKET_SLOTS ints per tile column pair: the counters of its ticketed pair update (ticket_tile)
+  int wg_slots = 0;        // workgroups of k_ldl_update the device holds at once (two per CU): grid of a ticketed launch
   HipStream hoist;               // second stream of the hoisted-diagonal schedule (no CU mask)
   HipStream rest;                // look-ahead of the block-sparse schedule: the rest of a pair's update (lowest priority)
   HipEvent ev_top;
@@ -269,7 +290,9 @@ constexpr int HOIST_MIN_TILES = 32;  // below ~2 rounds of tiles the update is s
 // The waiting workgroup keeps one CU of one XCD from the update, whose blocks the hardware deals round-robin to the
 // XCDs: that XCD runs 32/31 longer and the launch ends with it -- 3 % of the update time, which grows as nt^3 while
 // the hoisted 59 us per pair grow as nt.  Measured: n = 16002 (nt 126) 37.1 -> 35.6 ms, n = 40000 (nt 313) 411 -> 418 ms;
-// the model's break-even is nt ~ 250.
+// the model's break-even is nt ~ 250.  (Since then the update's workgroups draw tickets, ticket_tile above, and the other XCDs
+// empty that XCD's queue: at nt = 126 a launch takes 616 us in order, 652-655 beside the hoisted workgroup, 644-651 with
+// tickets -- most of the loss is not that XCD's share)
 constexpr int HOIST_MAX_TILES = 224;
 
 // transport of the cross-rank sums (ba_comm.hip): RCCL called directly, or a caller-supplied hook
