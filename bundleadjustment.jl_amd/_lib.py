@@ -63,6 +63,7 @@ SYMBOLS = [
     "ba_lm_set_comm_hook", "ba_comm_stats", "ba_comm_stats_ops", "ba_dist_layout",
     "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_lm_set_priors", "ba_lm_get_priors", "ba_prior_eval", "ba_covariance", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
     "ba_lm_set_shared_intrinsics", "ba_lm_get_shared_intrinsics", "ba_dense_ldl_solve_multi",
+    "ba_lm_set_obs_info", "ba_lm_get_obs_info",
 ]
 
 _lib = None
@@ -134,6 +135,8 @@ def lib():
     L.ba_lm_set_shared_intrinsics.argtypes = [vp, vp]
     L.ba_lm_get_shared_intrinsics.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(i64)]
     L.ba_dense_ldl_solve_multi.argtypes = [C.c_int, i64, vp, C.c_int, vp, vp, C.POINTER(f64)]
+    L.ba_lm_set_obs_info.argtypes = [vp, vp]
+    L.ba_lm_get_obs_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -474,12 +477,60 @@ def _check_tied(x, npnts, labels):
                          f"{int(labels[c])}: the members of a group must be identical in x (see tie_intrinsics)")
 
 
+# per-observation information of the LM entries (ba_lm_set_obs_info)
+def obs_info_pack(obs_info, nobs=None):
+    """(nobs, 3) float64 array xx xy yy of ba_lm_set_obs_info, host only, or None for None.  obs_info: standard deviations in
+    pixels, (nobs,) isotropic or (nobs, 2) sigma_x, sigma_y -- meaning diag(1 / sigma^2), inf = information 0 (the convention of
+    the priors' info) -- or the information matrices themselves, (nobs, 2, 2) symmetric positive semi-definite.  nobs None: only
+    the checks that need no problem size.  ValueError for another shape, sigma <= 0 or NaN, a block that is not finite, not
+    symmetric or not positive semi-definite."""
+    if obs_info is None:
+        return None
+    try:
+        a = np.asarray(obs_info, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("obs_info: a numeric array of standard deviations or information matrices") from None
+    n = "nobs" if nobs is None else int(nobs)
+    if not (a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 2) or (a.ndim == 3 and a.shape[1:] == (2, 2))) or \
+            (nobs is not None and a.shape[0] != int(nobs)):
+        raise ValueError(f"obs_info: standard deviations ({n},) or ({n}, 2), or information matrices ({n}, 2, 2), got {a.shape}")
+    out = np.zeros((a.shape[0], 3))
+    if a.ndim == 3:
+        if not np.isfinite(a).all():
+            raise ValueError("obs_info: the information matrices must be finite")
+        if not np.array_equal(a[:, 0, 1], a[:, 1, 0]):
+            raise ValueError("obs_info: the information matrices must be symmetric")
+        out[:, 0], out[:, 1], out[:, 2] = a[:, 0, 0], a[:, 0, 1], a[:, 1, 1]
+        if (out[:, 0] < 0).any() or (out[:, 2] < 0).any() or (out[:, 1] ** 2 > out[:, 0] * out[:, 2]).any():
+            raise ValueError("obs_info: the information matrices must be positive semi-definite")
+        return out
+    if np.isnan(a).any() or (a <= 0).any():
+        raise ValueError("obs_info: standard deviations must be > 0 (inf: the observation, or that direction, is dropped)")
+    s = a if a.ndim == 2 else np.stack([a, a], axis=1)
+    out[:, 0], out[:, 2] = 1.0 / s[:, 0] ** 2, 1.0 / s[:, 1] ** 2
+    return out
+
+
+def set_obs_info(handle, info3):
+    """the handle's information array for its next LM calls (ba_lm_set_obs_info); info3: obs_info_pack's array, None clears"""
+    a = None if info3 is None else np.ascontiguousarray(info3, dtype=np.float64)
+    check(lib().ba_lm_set_obs_info(handle, None if a is None else ptr(a)))
+
+
+def get_obs_info(handle):
+    """(observations with an information matrix: 0 or nobs, those with Lambda = 0) the handle holds (ba_lm_get_obs_info)"""
+    n, z = C.c_int64(0), C.c_int64(0)
+    check(lib().ba_lm_get_obs_info(handle, C.byref(n), C.byref(z)))
+    return n.value, z.value
+
+
 # the matrix of DESIGN §5h as Python sees it (the communicator and ba_covariance columns are the library's): per term the
 # attribute of ProblemTerms that says it is on, its name in a message, the uses it is not supported with in reporting order
 _REFUSED = (("tied", "shared_intrinsics is", ("linesearch", "facto_f32", "facto_f16", "normalize", "xf32")),
             ("robust", "a robust loss is", ("linesearch", "xf32", "facto_f16")),
             ("with_priors", "priors are", ("linesearch", "facto_f16", "xf32")),
-            ("masked", "fixed parameters are", ("facto_f16",)))
+            ("masked", "fixed parameters are", ("facto_f16",)),
+            ("weighted", "obs_info is", ("linesearch", "xf32", "facto_f16")))
 
 
 class ProblemTerms:
@@ -487,7 +538,7 @@ class ProblemTerms:
     before anything touches a model or the device); refuse(): the options a term is not supported with; apply(): onto a handle."""
 
     def __init__(self, loss="linear", f_scale=1.0, fixed_cameras=None, fixed_points=None, fixed_camera_params=None,
-                 point_priors=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
+                 point_priors=None, camera_priors=None, centre_priors=None, shared_intrinsics=None, obs_info=None):
         self.fixed = (fixed_cameras, fixed_points, fixed_camera_params)
         self.priors = (point_priors, camera_priors, centre_priors)
         self.shared, self.tied = shared_intrinsics, check_shared(shared_intrinsics)
@@ -495,6 +546,8 @@ class ProblemTerms:
         self.robust = self.kind != 0
         self.with_priors = check_priors(*self.priors)
         self.masked = check_fixed(*self.fixed)
+        self.info3 = obs_info_pack(obs_info)  # (packed once; its length is held to the problem's when it meets one)
+        self.weighted = self.info3 is not None
 
     def refuse(self, linesearch=False, facto_type=None, normalize="None", xf32=False):
         """ValueError when a term that is on is not supported with one of these options"""
@@ -513,11 +566,20 @@ class ProblemTerms:
     def set_priors(self, nlp):  # (alone: BALNLPModel.prior_eval)
         set_priors(nlp.handle, nlp.ncams, nlp.npnts, *self.priors)
 
+    def sized_info(self, nobs):
+        if self.info3 is not None and self.info3.shape[0] != int(nobs):
+            raise ValueError(f"obs_info: one entry per observation ({int(nobs)}), got {self.info3.shape[0]}")
+        return self.info3
+
+    def set_obs_info(self, nlp):  # (with set_loss: BALNLPModel.robust_weights)
+        set_obs_info(nlp.handle, self.sized_info(nlp.nobs))
+
     def apply(self, nlp, x=None, shared=True):
         """Pack the terms for nlp's sizes (ValueError before the handle changes), check that x (if given) is tied as the grouping
         asks, and set them on the handle: a term without its keyword is cleared.  shared=False leaves the handle's grouping."""
         cam_mask, pnt_fixed = fixed_masks(nlp.ncams, nlp.npnts, *self.fixed)
         labels = shared_labels(self.shared, nlp.ncams) if shared else None
+        info3 = self.sized_info(nlp.nobs)
         if x is not None and labels is not None:
             _check_tied(x, nlp.npnts, labels)
         self.set_loss(nlp)
@@ -525,6 +587,7 @@ class ProblemTerms:
         self.set_priors(nlp)
         if shared:
             set_shared(nlp.handle, labels)
+        set_obs_info(nlp.handle, info3)
 
 
 def dense_ldl_solve_multi(A, B, device=0):

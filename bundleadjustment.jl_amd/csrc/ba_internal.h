@@ -222,6 +222,7 @@ enum ProfClass {
   PC_SHARED_BORDER,  // shared intrinsics (ba_lm_set_shared_intrinsics): the border product S E_g, its E' reductions, the masking of S and the E' reductions / expansions of vectors
   PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step_multi / k_bwd_step_multi; also ba_dense_ldl_solve_multi)
   PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
+  PC_INFO,           // per-observation information (ba_lm_set_obs_info): k_info_whiten, the whitening of r and J (with the loss's reweighting)
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -371,6 +372,15 @@ struct ba_problem {
   bool grp_dirty = false;
   DevBuf<int> grp_ptr, grp_row;
   bool grp_on() const { return grp_n > 0; }
+  // per-observation information of the LM entries (ba_lm_set_obs_info): the factors L_i of Lambda_i = L_i L_i' (l00 l10 l11 per
+  // observation, caller's order; empty: none), how many Lambda_i are all zero, a count of the arrays set so far (a recorded
+  // sequence is keyed on it), and the device copy (allocated at the first upload, 3 nobs entries: never reallocated),
+  // uploaded lazily (info_dirty, info_upload)
+  std::vector<double> h_info;
+  bool info_set = false, info_dirty = false;
+  int64_t info_zero = 0, info_version = 0;
+  DevBuf<double> d_info;
+  bool info_on() const { return info_set; }
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

@@ -177,17 +177,20 @@ struct StepMode {
 // arguments of the robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed
 // parameters, which decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables,
 // launch arguments too; the priors (ba_lm_set_priors): how many of each kind (which prior kernels are in the sequence, and
-// their grids) and their device buffers
+// their grids) and their device buffers; the per-observation information (ba_lm_set_obs_info): whether k_info_whiten is in
+// the sequence, and which array it was recorded under
 struct RecordedFor {
-  int bits = -1;  // normalize + 4 * facto_f32 + 8 * xf32 + 16 * loss + 128 / 256 * mask tables (-1: nothing recorded yet)
+  int bits = -1;  // normalize + 4 * facto_f32 + 8 * xf32 + 16 * loss + 128 / 256 * mask tables + 512 * information (-1: nothing recorded yet)
   double loss_scale = 1.0;
   const void *d_fix_cam = nullptr, *d_fix_pnt = nullptr;
   int64_t n_pri[PRI_KINDS] = {0, 0, 0};
   const void *d_pri[PRI_KINDS][3] = {}, *d_pri_work[3] = {};
+  const void *d_info = nullptr;
+  int64_t info_version = 0;
   bool operator==(const RecordedFor &o) const {
     return bits == o.bits && loss_scale == o.loss_scale && d_fix_cam == o.d_fix_cam && d_fix_pnt == o.d_fix_pnt &&
            memcmp(n_pri, o.n_pri, sizeof n_pri) == 0 && memcmp(d_pri, o.d_pri, sizeof d_pri) == 0 &&
-           memcmp(d_pri_work, o.d_pri_work, sizeof d_pri_work) == 0;
+           memcmp(d_pri_work, o.d_pri_work, sizeof d_pri_work) == 0 && d_info == o.d_info && info_version == o.info_version;
   }
 };
 // hipGraph replay of the two launch sequences of the LM loop (launch-bound on small problems: LadyBug-49 issues ~60
@@ -745,7 +748,9 @@ static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s
 // r, J and the normal-equation blocks at w->x; fills sharded/replicated scalars RSQ?, GP, GC, X_P, X_C (and RTSQ)
 // recorded: the last reduction kernel also writes the controller's scalars to the pinned host buffers
 // Under a robust loss r and J are reweighted in place (r~, J~) before anything reads them; r must hold the plain residual at
-// w->x on entry (residual_too, or the trial residual of an accepted step)
+// w->x on entry (residual_too, or the trial residual of an accepted step).  With per-observation information
+// (ba_lm_set_obs_info) k_info_whiten takes the place of k_robust_scale: r^ and J^, the loss's reweighting on top in the same
+// pass; the trial residual of an accepted step is whitened already (trial_point)
 static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bool recorded, hipStream_t st) {
   if (w->mode.xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
@@ -761,7 +766,9 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   }
   if (p->fix_on()) BA_CHECK(launch_fix_mask(p, w->J, st));  // fixed parameters (ba_lm_set_fixed): their columns of J to 0
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (never with xf32: refused by ba_lm_solve)
-  if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
+  // (its partial sums are read under a loss only: the linear loss sums w->r below)
+  if (p->info_on()) BA_CHECK(launch_info_whiten(p, w->r, w->J, nullptr, robust ? (double *)w->rob_partial : nullptr, residual_too, true, st));
+  else if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
   // priors (ba_lm_set_priors): their terms into the diagonal blocks and the gradient, before anything reads either
@@ -1122,6 +1129,9 @@ static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded,
     BA_CHECK(launch_convert(w->rf, w->r_trial, w->nequ, st));
   } else {
     BA_CHECK(launch_residual_f64(p, w->x_trial, w->r_trial, st));
+    // per-observation information: the trial residual whitened in place, so the sums below (and, once the step is accepted,
+    // refresh_linearisation) see r^
+    BA_CHECK(launch_info_whiten(p, w->r_trial, nullptr, nullptr, nullptr, true, false, st));
   }
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (the line search, the only caller without with_delta, is refused then)
   if (!with_delta && p->pri_on()) {  // (only the line search calls without with_delta, and ba_lm_solve refuses it with priors)
@@ -1182,12 +1192,13 @@ static int with_hoist_retry(LMWork *w, F body) {
 static RecordedFor recorded_for(ba_problem *p, LMWork *w) {
   const StepMode &m = w->mode;
   const int bits = m.normalize + 4 * (m.facto_f32 ? 1 : 0) + 8 * (m.xf32 ? 1 : 0) + 16 * p->loss + 128 * (p->fix_ncam > 0 ? 1 : 0) +
-                   256 * (p->fix_npnt > 0 ? 1 : 0);
+                   256 * (p->fix_npnt > 0 ? 1 : 0) + 512 * (p->info_on() ? 1 : 0);
   RecordedFor f;
   f.bits = bits;
   f.loss_scale = p->loss != BA_LOSS_LINEAR ? p->loss_scale : 1.0;
   f.d_fix_cam = p->d_fix_cam;
   f.d_fix_pnt = p->d_fix_pnt;
+  if (p->info_on()) f.d_info = p->d_info, f.info_version = p->info_version;
   if (p->pri_on()) {
     for (int k = 0; k < PRI_KINDS; k++) {
       const PriorSet &q = p->pri[k];
@@ -1292,7 +1303,7 @@ static int accept_refresh_and_trial(LMWork *w, double lambda, hipStream_t st) {
   return BA_OK;
 }
 
-// ---- the optional terms of the LM problem: robust loss, fixed parameters, priors, shared intrinsics ---------------
+// ---- the optional terms of the LM problem: robust loss, fixed parameters, priors, shared intrinsics, information --
 // What the terms ask of an entry before its first launch: the uses of the handle a term is not carried through (TERM_RULES,
 // check_terms), the device copies of their host tables (terms_upload), what a grouping asks of x (check_tied_x).
 enum TermCond { TC_LINESEARCH, TC_X_F32, TC_FACTO_F32, TC_FACTO_F16, TC_NORMALIZE, TC_COMM, TC_COVARIANCE, TC_COUNT };
@@ -1319,6 +1330,8 @@ static const TermRule TERM_RULES[] = {
      {TC_LINESEARCH, TC_X_F32, TC_FACTO_F16, TC_COMM, TC_COUNT}},
     {"shared intrinsics (ba_lm_set_shared_intrinsics) are", [](const ba_problem *p) { return p->grp_on(); },
      {TC_COMM, TC_X_F32, TC_FACTO_F32, TC_FACTO_F16, TC_NORMALIZE, TC_LINESEARCH, TC_COVARIANCE, TC_COUNT}},
+    {"per-observation information (ba_lm_set_obs_info) is", [](const ba_problem *p) { return p->info_on(); },
+     {TC_LINESEARCH, TC_X_F32, TC_FACTO_F16, TC_COMM, TC_COUNT}},
 };
 
 static int check_terms(const ba_problem *p, const TermUse &use) {
@@ -1335,7 +1348,8 @@ static int check_terms(const ba_problem *p, const TermUse &use) {
 int terms_upload(ba_problem *p) {
   BA_CHECK(fix_upload(p));
   BA_CHECK(prior_upload(p));
-  return shared_upload(p);
+  BA_CHECK(shared_upload(p));
+  return info_upload(p);
 }
 
 // what a grouping asks of x and of the mask (shared_check) on the camera part of x, fetched when x is on the device

@@ -197,7 +197,15 @@ int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double la
                           double *d_rhs, double *d_small, hipStream_t st);
 int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, const double *d_B, const double *d_Y, double *d_a,
                          double *d_small, hipStream_t st);
-// the optional terms together (ba_lm.hip): fix_upload, prior_upload and shared_upload
+// per-observation information (ba_info_kernels.hip): the handle's factors to the device when they changed
+// (ba_lm_set_obs_info).  launch_info_whiten: r <- L' r (residual_plain: d_r holds the plain residual; else it is whitened
+// already and stays) and, d_J != null, J <- L' J per observation, in place; with_loss: the handle's loss on top, as
+// launch_robust_scale applies it, from |r^|^2 (d_w (optional) <- w); d_partial (optional): the two per-block partials of
+// launch_robust_scale, same layout and grid.  No launch without an array.
+int info_upload(ba_problem *p);
+int launch_info_whiten(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, bool residual_plain,
+                       bool with_loss, hipStream_t st);
+// the optional terms together (ba_lm.hip): fix_upload, prior_upload, shared_upload and info_upload
 int terms_upload(ba_problem *p);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);

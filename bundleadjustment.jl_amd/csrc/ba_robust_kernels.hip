@@ -143,13 +143,15 @@ extern "C" int ba_lm_get_loss(const ba_problem *p, int *kind, double *scale) {
   return BA_OK;
 }
 
-// r and J at x, k_robust_scale with the weights written out, the cost partials summed by the fixed tree of the LM loop
+// r and J at x, k_robust_scale with the weights written out, the cost partials summed by the fixed tree of the LM loop; with
+// per-observation information on the handle (ba_lm_set_obs_info) k_info_whiten in its place: w and f of r' Lambda r
 extern "C" int ba_robust_eval(ba_problem *p, const double *x, double *weights, double *cost) {
   if (!p || !x) {
     ba_set_error("ba_robust_eval: null argument");
     return BA_ERR_ARG;
   }
   BA_HIP_CHECK(hipSetDevice(p->device));
+  BA_CHECK(info_upload(p));
   const int64_t nvar = 9 * p->ncams + 3 * p->npnts, nobs = p->nobs;
   hipStream_t st = p->stream;
   double *dx, *dr, *dJ, *dw;
@@ -163,7 +165,8 @@ extern "C" int ba_robust_eval(ba_problem *p, const double *x, double *weights, d
   BA_HIP_CHECK(hipMemcpyAsync(dx, x, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
   BA_CHECK(launch_residual_f64(p, dx, dr, st));
   BA_CHECK(launch_jac_coord_f64(p, dx, dJ, st));
-  BA_CHECK(launch_robust_scale(p, dr, dJ, dw, dpart, st));
+  if (p->info_on()) BA_CHECK(launch_info_whiten(p, dr, dJ, dw, dpart, true, true, st));
+  else BA_CHECK(launch_robust_scale(p, dr, dJ, dw, dpart, st));
   SumsqJobs jobs;
   jobs.add_sum(dpart, robust_blocks(nobs), dout, 0);
   BA_CHECK(launch_sumsq_multi(p, &jobs, dmulti, st));

@@ -57,7 +57,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
                         nu_d=None, nu_m=None, lam=None, delta_d=None, ite_max=None, max_time=None, verbose=False,
                         log=True, pcg_tol=None, pcg_max_iter=None, x_device_ptr=None, loss="linear", f_scale=1.0,
                         fixed_cameras=None, fixed_points=None, fixed_camera_params=None, point_priors=None,
-                        camera_priors=None, centre_priors=None, shared_intrinsics=None):
+                        camera_priors=None, centre_priors=None, shared_intrinsics=None, obs_info=None):
     """x_device_ptr (an extension for device-resident callers, e.g. bench.py): the address of nvar doubles of DEVICE memory
     holding x0; the loop then runs through ba_lm_solve_dev -- no host copy of the iterate on either side -- the solution
     stays there and `solution` of the result is None.
@@ -86,9 +86,16 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
     members of a group must hold identical (k1, k2, f) in x0 (tie_intrinsics makes such an x) and come back identical;
     dual_feas and the log's |J'r| are the gradient over the tied parameters.  Set on the handle at every call: a call without
     it runs the untied path.  Not with facto_type = Float32 / Float16, a Float32 model, normalize :J / :A or linesearch = True
-    (ValueError)."""
+    (ValueError).
+
+    obs_info (an extension): the uncertainty of every observation -- standard deviations in pixels, (nobs,) isotropic or
+    (nobs, 2) sigma_x, sigma_y (inf: dropped), or 2 x 2 information matrices (nobs, 2, 2), symmetric positive semi-definite
+    (see _lib.obs_info_pack for the forms and ba_lm_set_obs_info in include/ba_hip.h for the semantics).  The objective becomes
+    1/2 sum_i r_i' Lambda_i r_i; a robust loss then acts on the Mahalanobis distance and f_scale is in units of sigma;
+    `objective`, the log's f and |J'r| are those of the whitened problem.  Set on the handle at every call: a call without
+    it runs the unweighted path.  Not with linesearch = True, a Float32 model or facto_type = Float16 (ValueError)."""
     terms = _lib.ProblemTerms(loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params, point_priors, camera_priors,
-                              centre_priors, shared_intrinsics)
+                              centre_priors, shared_intrinsics, obs_info)
     terms.refuse(linesearch=linesearch, facto_type=facto_type, normalize=normalize)
     facto, perm, normalize = _sym(facto), _sym(perm), _sym(normalize)
     if facto not in _FACTO:
@@ -162,7 +169,7 @@ def Levenberg_Marquardt(model, facto, perm, normalize, linesearch=None, *, x=Non
 
 def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_scale=1.0, fixed_cameras=None,
             fixed_points=None, fixed_camera_params=None, point_priors=None, camera_priors=None, centre_priors=None,
-            shared_intrinsics=None):
+            shared_intrinsics=None, obs_info=None):
     """One linear LM step from (x, lambda): delta, 1/2|J delta + r|^2, J'r  (ba_lm_step; facto_type=np.float32:
     ba_lm_step_f32, the reduced camera system factored in Float32 as src/lm.jl:170-173 does; pcg=(tol, max_iter):
     ba_lm_step_pcg, the step by preconditioned CG -- the CG iteration count is then appended to the result).
@@ -171,9 +178,10 @@ def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_
     *_priors (see Levenberg_Marquardt): the step of the objective with the prior terms; they are in all three outputs.
     shared_intrinsics (see Levenberg_Marquardt): the step over the tied parameters, expanded to the layout of x (the members of
     a group receive identical steps); J'r holds a group's summed gradient at its first member and exact zeros at the other
-    members' (k1, k2, f).  Not with facto_type = Float32 (ValueError)."""
+    members' (k1, k2, f).  Not with facto_type = Float32 (ValueError).
+    obs_info (see Levenberg_Marquardt): the step of the whitened problem; all three outputs are quantities of r^ and J^."""
     terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
-                              point_priors, camera_priors, centre_priors, shared_intrinsics)
+                              point_priors, camera_priors, centre_priors, shared_intrinsics, obs_info)
     f64 = facto_type is None or np.dtype(facto_type) == np.float64
     terms.refuse(facto_type=None if f64 else np.float32)  # (the step has one other factorisation)
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -193,17 +201,19 @@ def lm_step(nlp, x, lam, want_jtr=True, facto_type=None, pcg=None, loss=None, f_
 
 
 def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, fixed_points=None, fixed_camera_params=None,
-               rank_tol=None, cameras=True, points=True, point_priors=None, camera_priors=None, centre_priors=None):
+               rank_tol=None, cameras=True, points=True, point_priors=None, camera_priors=None, centre_priors=None,
+               obs_info=None):
     """Covariance at x (ba_covariance): the diagonal blocks of (J~_F'J~_F + sum_k H_k' info_k H_k + lam I)^-1, J~ the Jacobian
     as lm_step sees it under `loss` / `f_scale` and the fixed_* options, the sum over the *_priors (see Levenberg_Marquardt),
-    F the free entries.  Priors that fix the gauge softly make it well defined at lam = 0.  Returns (cam_cov (ncams,
+    F the free entries; obs_info (see Levenberg_Marquardt): J~ is whitened by the observations' information first, so the
+    result is in the units the sigmas were given in.  Priors that fix the gauge softly make it well defined at lam = 0.  Returns (cam_cov (ncams,
     9, 9) or None, pnt_cov (npnts, 3, 3) or None, min_rel_pivot): camera blocks in block order r1 r2 r3 t1 t2 t3 k1 k2 f,
     rows and columns of fixed entries exactly 0, not scaled by a residual variance (multiply by 2 f / (nequ - n_free) for
     that).  min_rel_pivot = min D_i / S_ii of the factored reduced camera system; at or below rank_tol (None: 1e-10, 0: no
     check) it is numerically singular -- the gauge left free at lam = 0 -- and SQDException is raised (with the value as its
     min_rel_pivot attribute).  Bad arguments raise ValueError before any device call."""
     terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
-                              point_priors, camera_priors, centre_priors)
+                              point_priors, camera_priors, centre_priors, obs_info=obs_info)
     try:
         lam = float(lam)
     except (TypeError, ValueError):

@@ -170,15 +170,17 @@ class BALNLPModel:
         return out
 
     # -- robust loss (an extension) -------------------------------------------------------------------------------
-    def robust_weights(self, x, loss, f_scale=1.0):
+    def robust_weights(self, x, loss, f_scale=1.0, obs_info=None):
         """(weights, cost) at x under a robust loss (ba_robust_eval): weights[i] = rho'(|r_i|^2 / c^2) per observation (a
         weight below 1 marks an observation the loss discounts: an outlier candidate after a solve), cost = f(x) =
-        1/2 sum_i c^2 rho(|r_i|^2 / c^2); c = f_scale.  Sets the handle's loss, as every LM call does."""
-        terms = _lib.ProblemTerms(loss=loss, f_scale=f_scale)
+        1/2 sum_i c^2 rho(|r_i|^2 / c^2); c = f_scale.  obs_info (see Levenberg_Marquardt): |r_i|^2 becomes r_i' Lambda_i r_i.
+        Sets the handle's loss and information, as every LM call does."""
+        terms = _lib.ProblemTerms(loss=loss, f_scale=f_scale, obs_info=obs_info)
         x = np.ascontiguousarray(x, dtype=np.float64)
         if x.shape != (self.meta.nvar,):
             raise ValueError(f"x has length {x.shape}, expected {self.meta.nvar}")
         terms.set_loss(self)
+        terms.set_obs_info(self)
         w = np.empty(self.nobs)
         cost = C.c_double(0)
         _lib.check(_lib.lib().ba_robust_eval(self._h, _lib.ptr(x), _lib.ptr(w), C.byref(cost)))

@@ -389,6 +389,31 @@ int ba_prior_eval(ba_problem *p, const double *x, double *cost /* or NULL */,
 int ba_lm_set_shared_intrinsics(ba_problem *p, const int32_t *group /* ncams; 0 = own, 1..G; NULL clears */);
 int ba_lm_get_shared_intrinsics(const ba_problem *p, int *n_groups, int64_t *n_members);
 
+/* ---- per-observation information matrices (an extension: every observation of the reference counts with the identity) ----
+ * Observation i carries a symmetric positive semi-definite 2 x 2 information matrix Lambda_i (the inverse covariance of its
+ * detection, pixels^-2), factored as Lambda_i = L_i L_i' with L_i lower triangular.  Inside the LM entries (ba_lm_step / _f32 /
+ * _pcg, ba_lm_solve, ba_lm_solve_dev, ba_covariance) "the residual" becomes r^_i = L_i' r_i and "the Jacobian" J^_i = L_i' J_i
+ * (the two rows of the 2 x 12 block are mixed): the objective is 1/2 sum_i r_i' Lambda_i r_i, under a robust loss
+ * 1/2 sum_i c^2 rho(r_i' Lambda_i r_i / c^2) -- the loss sees the Mahalanobis distance, its scale is in units of sigma.  Priors
+ * are not affected.  The whitening is linear and per observation, so J^ has the sparsity of J and everything downstream runs
+ * unchanged on r^ and J^: the mask, the robust reweighting, both block kinds, the Schur assembly (dense or block-sparse, every
+ * perm), facto_type = Float32, :PCG, normalize :J / :A, priors, the shared-intrinsics border, the covariance.  stats.objective,
+ * stats.dual_feas, the log's f and |J'r|, the jtr output of ba_lm_step and its half_sq_model are quantities of r^ and J^.
+ * Lambda_i = 0 drops the observation; a singular Lambda_i constrains one image direction only.
+ * ba_robust_eval honours the array too: its weights are rho'(r_i' Lambda_i r_i / c^2), its cost the objective above (also under
+ * the linear loss).  The model entries (ba_residual, ba_jac_coord, ba_jtr) ignore it, as they ignore the mask.
+ * Refused (BA_ERR_ARG, the message names the combination): linesearch = 1, x_f32 = 1, facto_type = Float16, a communicator.
+ * With nothing set every entry runs exactly the launch sequence without the term.
+ *   ba_lm_set_obs_info : the array of the handle's next LM steps, solves, covariance and ba_robust_eval calls: xx xy yy of
+ *                        every observation, caller's order; NULL clears.  An array of identities is kept as given.  Host only
+ *                        (validated and factored: l00 = sqrt(xx), l10 = xy / l00 (0 when xx = 0), l11 = sqrt(max(yy - l10^2,
+ *                        0))); uploaded when a step or solve runs.  BA_ERR_ARG (the handle keeps what it had): a value that is
+ *                        not finite, a negative diagonal entry, xy^2 > xx yy.
+ *   ba_lm_get_obs_info : n_set = nobs when an array is set, else 0; n_zero = the observations with Lambda = 0 (either may be
+ *                        NULL). */
+int ba_lm_set_obs_info(ba_problem *p, const double *info3 /* nobs * 3: xx xy yy per observation, caller's order; NULL clears */);
+int ba_lm_get_obs_info(const ba_problem *p, int64_t *n_set /* 0 or nobs */, int64_t *n_zero /* observations with Lambda == 0 */);
+
 /* ---- covariance at a solution (an extension: the reference has none) ------------------------------------------------
  * At x, under the handle's loss (ba_lm_set_loss) and mask (ba_lm_set_fixed):  Sigma = (J~_F' J~_F + lambda I)^-1, J~ the
  * Jacobian exactly as ba_lm_step sees it (reweighted under a robust loss, the columns of the fixed entries zeroed), F the free

@@ -100,3 +100,20 @@ function shared_intrinsics_counts(nlp)
   bacheck(ccall((:ba_lm_get_shared_intrinsics, libba), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), nlp.handle, g, m))
   return Int(g[]), m[]
 end
+
+# per-observation information matrices (an extension): include/ba_hip.h, ba_lm_set_obs_info.  `info3`: nothing (clears the array)
+# or a 3 x nobs Float64 matrix, column i = (xx, xy, yy) of the symmetric positive semi-definite Lambda_i of observation i, in the
+# model's observation order.  Stays on the handle until it is set again; Levenberg_Marquardt and covariance set it from their
+# `obs_info` keyword at every call (julia/LevenbergMarquardtHIP.jl).
+function set_obs_info(nlp, info3)
+  if info3 === nothing
+    bacheck(ccall((:ba_lm_set_obs_info, libba), Cint, (Ptr{Cvoid}, Ptr{Float64}), nlp.handle, Ptr{Float64}(C_NULL)))
+    return nothing
+  end
+  size(info3) == (3, nlp.nobs) || error("obs_info: a 3 x nobs ($(nlp.nobs)) matrix of (xx, xy, yy) columns, got $(size(info3))")
+  a = Matrix{Float64}(info3)
+  GC.@preserve a begin
+    bacheck(ccall((:ba_lm_set_obs_info, libba), Cint, (Ptr{Cvoid}, Ptr{Float64}), nlp.handle, pointer(a)))
+  end
+  return nothing
+end

@@ -131,6 +131,40 @@ function prior_eval(nlp, x :: AbstractVector; point_priors = nothing, camera_pri
   return cost[], cp, cc, ct
 end
 
+# per-observation information (an extension): include/ba_hip.h, ba_lm_set_obs_info.  obs_info: nothing, standard deviations in
+# pixels -- a vector (nobs, isotropic) or an (nobs, 2) matrix (sigma_x, sigma_y), Inf = information 0 -- or 2 x 2 x nobs symmetric
+# positive semi-definite information matrices.  Packed to the 3 x nobs (xx, xy, yy) layout of set_obs_info (julia/BALHIP.jl).  Set
+# on the handle at every call: a call without `obs_info` runs the unweighted path.
+function _ba_obs_info(obs_info, nobs :: Int)
+  obs_info === nothing && return nothing
+  a = Array{Float64}(obs_info)
+  out = zeros(Float64, 3, nobs)
+  if ndims(a) == 3 && size(a) == (2, 2, nobs)
+    all(isfinite, a) || error("obs_info: the information matrices must be finite")
+    a[1, 2, :] == a[2, 1, :] || error("obs_info: the information matrices must be symmetric")
+    out[1, :] = a[1, 1, :]; out[2, :] = a[1, 2, :]; out[3, :] = a[2, 2, :]
+    (any(out[1, :] .< 0) || any(out[3, :] .< 0) || any(out[2, :] .^ 2 .> out[1, :] .* out[3, :])) &&
+      error("obs_info: the information matrices must be positive semi-definite")
+  elseif (ndims(a) == 1 && length(a) == nobs) || (ndims(a) == 2 && size(a) == (nobs, 2))
+    (any(isnan, a) || any(a .<= 0)) && error("obs_info: standard deviations must be > 0 (Inf: dropped)")
+    out[1, :] = 1.0 ./ a[:, 1] .^ 2
+    out[3, :] = 1.0 ./ a[:, ndims(a)] .^ 2
+  else
+    error("obs_info: standard deviations (nobs) or (nobs, 2), or information matrices (2, 2, nobs), got $(size(a))")
+  end
+  return out
+end
+
+function _ba_set_obs_info(nlp, obs_info, linesearch :: Bool, ft :: Int, T :: DataType)
+  info3 = _ba_obs_info(obs_info, nlp.nobs)
+  if info3 !== nothing
+    linesearch && error("obs_info is not supported with linesearch = true")
+    ft == 2 && error("obs_info is not supported with facto_type = Float16")
+    T == Float32 && error("obs_info is not supported for a Float32 model")
+  end
+  set_obs_info(nlp, info3)
+end
+
 # one log row per iteration, the reference's columns (src/lm.jl:120-121,304)
 function _ba_log_row(ctx :: Ptr{Cvoid}, iter :: Cint, f :: Cdouble, df :: Cdouble, njtr :: Cdouble, lambda :: Cdouble,
                      ndelta :: Cdouble, rho :: Cdouble, acc :: Cint) :: Cvoid
@@ -142,7 +176,8 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
                 x :: AbstractVector, facto_type :: DataType, restol, satol, srtol, oatol, ortol, atol, rtol, νd, νm, λ, δd,
                 ite_max :: Int, max_time :: Real, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
                 loss :: Symbol = :linear, f_scale :: Real = 1.0, fixed_cameras = nothing, fixed_points = nothing,
-                fixed_camera_params = nothing, point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
+                fixed_camera_params = nothing, point_priors = nothing, camera_priors = nothing, centre_priors = nothing,
+                obs_info = nothing)
   # :PCG is an extension of the HIP path (no counterpart in the reference): matrix-free conjugate gradients on the reduced
   # camera system, include/ba_hip.h, ba_lm_opts.facto
   facto in (:QR, :LDL, :PCG) || error("facto must be :QR, :LDL or :PCG")
@@ -163,6 +198,7 @@ function _ba_lm(model, variant :: Int, facto :: Symbol, perm :: Symbol, normaliz
   _ba_set_loss(nlp, loss, f_scale)
   _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, ft)
   _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, linesearch, ft, T)
+  _ba_set_obs_info(nlp, obs_info, linesearch, ft, T)
   st = BaLmStats()
   xd = Vector{Float64}(x)               # the ABI carries the iterate as doubles (exact for Float32 values)
   cb = @cfunction(_ba_log_row, Cvoid, (Ptr{Cvoid}, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cdouble, Cint))
@@ -195,10 +231,10 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              ite_max :: Int = 200, max_time :: Int = 3600, pcg_tol :: Real = -1.0, pcg_max_iter :: Int = -1,
                              loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
                              fixed_camera_params = nothing, point_priors = nothing, camera_priors = nothing,
-                             centre_priors = nothing)
+                             centre_priors = nothing, obs_info = nothing)
   return _ba_lm(model, 1, facto, perm, normalize, linesearch, x, facto_type, restol, satol, srtol, oatol, ortol, atol, rtol,
                 νd, νm, λ, δd, ite_max, max_time, pcg_tol, pcg_max_iter, loss, f_scale, fixed_cameras, fixed_points,
-                fixed_camera_params, point_priors, camera_priors, centre_priors)
+                fixed_camera_params, point_priors, camera_priors, centre_priors, obs_info)
 end
 
 "src/LevenbergMarquardt.jl:16-26 -- the 4-argument method src/solve_ba.jl:26 calls (no linesearch, no facto_type)"
@@ -208,30 +244,31 @@ function Levenberg_Marquardt(model :: AbstractNLSModel, facto :: Symbol, perm ::
                              atol = nothing, rtol = nothing, νd = nothing, νm = nothing, λ = nothing, δd = nothing,
                              ite_max :: Int = 100, loss :: Symbol = :linear, f_scale = 1.0, fixed_cameras = nothing,
                              fixed_points = nothing, fixed_camera_params = nothing, point_priors = nothing,
-                             camera_priors = nothing, centre_priors = nothing)
+                             camera_priors = nothing, centre_priors = nothing, obs_info = nothing)
   return _ba_lm(model, 0, facto, perm, normalize, false, x, eltype(x), restol, satol, srtol, oatol, ortol, atol, rtol,
                 νd, νm, λ, δd, ite_max, 3600, -1.0, -1, loss, f_scale, fixed_cameras, fixed_points, fixed_camera_params,
-                point_priors, camera_priors, centre_priors)
+                point_priors, camera_priors, centre_priors, obs_info)
 end
 
 """
     covariance(nlp, x; λ = 0.0, loss = :linear, f_scale = 1.0, fixed_cameras = nothing, fixed_points = nothing,
                fixed_camera_params = nothing, rank_tol = nothing, point_priors = nothing, camera_priors = nothing,
-               centre_priors = nothing)
+               centre_priors = nothing, obs_info = nothing)
 
 Covariance at `x` (an extension; include/ba_hip.h, ba_covariance): the diagonal blocks of (J̃_F'J̃_F + Σ H_k'Λ_k H_k + λI)⁻¹ under
-the loss, the fixed parameters and the priors given (keywords as Levenberg_Marquardt's).  Returns `(cam_cov, pnt_cov, min_rel_pivot)`:
+the loss, the fixed parameters, the priors and the observations' information given (keywords as Levenberg_Marquardt's).  Returns `(cam_cov, pnt_cov, min_rel_pivot)`:
 cam_cov[:, :, c] the 9 × 9 block of camera c (block order r1 r2 r3 t1 t2 t3 k1 k2 f), pnt_cov[:, :, i] the 3 × 3 block of
 point i; fixed rows and columns are 0.  Not scaled by a residual variance.  With the gauge free and λ = 0 the reduced
 camera system is singular: SQDException (rank_tol = nothing: the library's default, 0: no check).
 """
 function covariance(nlp, x :: AbstractVector; λ :: Real = 0.0, loss :: Symbol = :linear, f_scale = 1.0,
                     fixed_cameras = nothing, fixed_points = nothing, fixed_camera_params = nothing, rank_tol = nothing,
-                    point_priors = nothing, camera_priors = nothing, centre_priors = nothing)
+                    point_priors = nothing, camera_priors = nothing, centre_priors = nothing, obs_info = nothing)
   (isfinite(λ) && λ >= 0) || error("λ must be finite and >= 0")
   _ba_set_loss(nlp, loss, f_scale)
   _ba_set_fixed(nlp, fixed_cameras, fixed_points, fixed_camera_params, 0)
   _ba_set_priors(nlp, point_priors, camera_priors, centre_priors, false, 0, Float64)
+  _ba_set_obs_info(nlp, obs_info, false, 0, Float64)
   xv = Vector{Float64}(x)
   cam = zeros(Float64, 81 * nlp.ncams)
   pnt = zeros(Float64, 9 * nlp.npnts)
