@@ -11,14 +11,13 @@
 
 namespace {
 
-constexpr int FB = 256;  // observations per workgroup = threads per workgroup
-constexpr int JV = 12;   // 16-byte vectors of J per observation (2 rows of 12 doubles)
+constexpr int FB = OBS_TILE;  // observations per workgroup = threads per workgroup
 
 // One workgroup = FB consecutive observations.  Thread t builds the 12-bit mask of fixed Jacobian columns of observation t
 // (bits 0..2 the point, bits 3..11 the camera components: column c of J is bit c) from the int32 camera / point index and the
 // small per-camera / per-point tables, and puts it in LDS.  A workgroup none of whose observations has a fixed column ends
 // there.  Otherwise the tile's 12 FB 16-byte vectors of J are visited by the whole workgroup, vector k FB + t by thread t
-// (contiguous across the lanes of a wave, as k_robust_scale streams them): vector e of an observation holds columns 2 (e % 6)
+// (contiguous across the lanes of a wave, as k_obs_scale streams them): vector e of an observation holds columns 2 (e % 6)
 // and 2 (e % 6) + 1 of row e / 6.  Only zeros are stored, and only where a column is fixed: 16 bytes when both columns of
 // the vector are fixed, 8 bytes when one is.  J itself is never read.  CAM / PNT: whether the camera / point table is
 // present (the indices of a kind without a table are not read).

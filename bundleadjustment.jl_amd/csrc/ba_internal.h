@@ -213,7 +213,7 @@ enum ProfClass {
   PC_TRIAL,
   PC_REDUCE,
   PC_COMM,
-  PC_ROBUST,  // k_robust_scale (robust loss: reweighting of r and J)
+  PC_ROBUST,  // "k_robust_scale": k_obs_scale on a handle without information (robust loss: reweighting of r and J)
   PC_FIXED,   // k_fix_mask (fixed parameters: zeroing of their columns of J)
   PC_COV_INV,     // covariance (ba_covariance): selected inversion of the factored S, with the rank check's diag(S) and min D_i / S_ii
   PC_COV_CAMS,    // covariance: the cameras' 9 x 9 blocks (k_cov_cams)
@@ -222,7 +222,7 @@ enum ProfClass {
   PC_SHARED_BORDER,  // shared intrinsics (ba_lm_set_shared_intrinsics): the border product S E_g, its E' reductions, the masking of S and the E' reductions / expansions of vectors
   PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step_multi / k_bwd_step_multi; also ba_dense_ldl_solve_multi)
   PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
-  PC_INFO,           // per-observation information (ba_lm_set_obs_info): k_info_whiten, the whitening of r and J (with the loss's reweighting)
+  PC_INFO,           // per-observation information (ba_lm_set_obs_info): "k_info_whiten": k_obs_scale on a handle with it, the whitening of r and J (with the loss's reweighting)
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];

@@ -177,8 +177,8 @@ struct StepMode {
 // arguments of the robust kernels, so a sequence recorded under one loss is never replayed under another; the mask of fixed
 // parameters, which decides whether (and which instantiation of) k_fix_mask is in the sequence, and its device tables,
 // launch arguments too; the priors (ba_lm_set_priors): how many of each kind (which prior kernels are in the sequence, and
-// their grids) and their device buffers; the per-observation information (ba_lm_set_obs_info): whether k_info_whiten is in
-// the sequence, and which array it was recorded under
+// their grids) and their device buffers; the per-observation information (ba_lm_set_obs_info): which instantiation of
+// k_obs_scale is in the sequence, and which array it was recorded under
 struct RecordedFor {
   int bits = -1;  // normalize + 4 * facto_f32 + 8 * xf32 + 16 * loss + 128 / 256 * mask tables + 512 * information (-1: nothing recorded yet)
   double loss_scale = 1.0;
@@ -269,7 +269,7 @@ struct LMWork {
   DevBuf<double> cgx, cgr, cgz, cgp, cgq, cgt;
   DevBuf<double> cgh, zero3, blk45, cg_scal;
   PinnedBuf<double> h_cg;
-  DevBuf<double> rob_partial;  // 2 RED_BLOCKS: per-block partials of k_robust_scale (cost, |r~|^2)
+  DevBuf<double> rob_partial;  // 2 RED_BLOCKS: per-block partials of k_obs_scale (cost, |r~|^2)
   // shared intrinsics (ba_lm_set_shared_intrinsics).  Direct path: the grouping's tables in the order of S (grp_row:
   // the row of k1 of every member, grp_col: per row of S the column of z it belongs to or -1), made for grp_made_for =
   // ba_problem::grp_version; the border B, Y = A^-1 B and the sweeps' scratch (24 columns of npad each), the small systems.
@@ -749,8 +749,8 @@ static int reduce_camera_system(ba_problem *p, LMWork *w, hipStream_t st, bool s
 // recorded: the last reduction kernel also writes the controller's scalars to the pinned host buffers
 // Under a robust loss r and J are reweighted in place (r~, J~) before anything reads them; r must hold the plain residual at
 // w->x on entry (residual_too, or the trial residual of an accepted step).  With per-observation information
-// (ba_lm_set_obs_info) k_info_whiten takes the place of k_robust_scale: r^ and J^, the loss's reweighting on top in the same
-// pass; the trial residual of an accepted step is whitened already (trial_point)
+// (ba_lm_set_obs_info) the same pass (k_obs_scale) whitens them: r^ and J^, the loss's reweighting on top; the trial residual
+// of an accepted step is whitened already (trial_point)
 static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bool recorded, hipStream_t st) {
   if (w->mode.xf32) {  // w->x holds Float32 values: evaluate with the Float32 kernels, widen (exact)
     BA_CHECK(launch_convert(w->x, w->xf, w->nvar, st));
@@ -767,8 +767,7 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   if (p->fix_on()) BA_CHECK(launch_fix_mask(p, w->J, st));  // fixed parameters (ba_lm_set_fixed): their columns of J to 0
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (never with xf32: refused by ba_lm_solve)
   // (its partial sums are read under a loss only: the linear loss sums w->r below)
-  if (p->info_on()) BA_CHECK(launch_info_whiten(p, w->r, w->J, nullptr, robust ? (double *)w->rob_partial : nullptr, residual_too, true, st));
-  else if (robust) BA_CHECK(launch_robust_scale(p, w->r, w->J, nullptr, w->rob_partial, st));
+  BA_CHECK(launch_obs_scale(p, w->r, w->J, nullptr, robust ? (double *)w->rob_partial : nullptr, residual_too, true, st));
   BA_CHECK(launch_point_blocks(p, w->J, w->r, w->Hpp, w->gp, st));
   BA_CHECK(launch_cam_blocks(p, w->J, w->r, w->Hcc, w->gc, st));
   // priors (ba_lm_set_priors): their terms into the diagonal blocks and the gradient, before anything reads either
@@ -782,8 +781,8 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   // |r|^2, |gp|^2, |x_points|^2 and -- of the all-reduced gc -- |gc|^2, |x_cameras|^2: one launch pair on one rank, two with a
   // communicator (the camera sums wait for the all-reduce); bit-identical to launch_sumsq per vector either way
   SumsqJobs jobs;
-  if (robust) {  // 2 f and |r~|^2 from k_robust_scale's partials
-    const int nb = robust_blocks(p->nobs);
+  if (robust) {  // 2 f and |r~|^2 from k_obs_scale's partials
+    const int nb = obs_blocks(p->nobs);
     jobs.add_sum(w->rob_partial, nb, w->scal, SH_RSQ);
     jobs.add_sum(w->rob_partial + RED_BLOCKS, nb, w->scal, SH_RTSQ);
   } else {
@@ -1131,7 +1130,7 @@ static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded,
     BA_CHECK(launch_residual_f64(p, w->x_trial, w->r_trial, st));
     // per-observation information: the trial residual whitened in place, so the sums below (and, once the step is accepted,
     // refresh_linearisation) see r^
-    BA_CHECK(launch_info_whiten(p, w->r_trial, nullptr, nullptr, nullptr, true, false, st));
+    BA_CHECK(launch_obs_scale(p, w->r_trial, nullptr, nullptr, nullptr, true, false, st));
   }
   const bool robust = p->loss != BA_LOSS_LINEAR;  // (the line search, the only caller without with_delta, is refused then)
   if (!with_delta && p->pri_on()) {  // (only the line search calls without with_delta, and ba_lm_solve refuses it with priors)

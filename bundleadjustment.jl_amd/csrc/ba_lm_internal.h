@@ -3,6 +3,10 @@
 #include "ba_internal.h"
 
 constexpr int RED_BLOCKS = 1024;  // fixed number of partial sums => fixed summation tree
+// the passes that stream the stored J (k_obs_scale, k_fix_mask): observations per tile = threads per workgroup, and 16-byte
+// vectors of J per observation (2 rows of 12 doubles)
+constexpr int OBS_TILE = 256;
+constexpr int JV = 12;
 
 // Schur task list (built once per problem on the host): all ordered observation pairs (a, b) of one point with
 // camera(a) >= camera(b), sorted by (camera(a), camera(b)); key k owns tasks [key_ptr[k], key_ptr[k+1]).
@@ -72,10 +76,16 @@ __device__ __forceinline__ double robust_rho(int kind, double s, double c2, doub
   }
 }
 
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
 // up to eight sums in one launch pair (launch_sumsq_multi): vector, length, destination array and slot; the second kernel (one
 // workgroup) can also publish the controller's scalars to pinned host memory once every sum is in place.  Kind of a job:
 // SJ_SQUARES sum v_i^2 (n entries); SJ_ROBUST sum c^2 rho(|r_o|^2 / c^2) over n observations of the interleaved residual v
-// under (loss, c2); SJ_SUM sum v_i (n entries: the per-block partials of a kernel of its own, e.g. k_robust_scale).  A job
+// under (loss, c2); SJ_SUM sum v_i (n entries: the per-block partials of a kernel of its own, e.g. k_obs_scale).  A job
 // with acc set ADDS its sum to what the slot holds -- the value a job before it in the same launch, or a kernel before the
 // launch, left there (the prior terms, ba_prior_kernels.hip): the jobs are summed one after the other, in order
 constexpr int SUMSQ_JOBS = 8;
@@ -160,11 +170,17 @@ int launch_sumsq(ba_problem *p, int64_t n, const double *d_v, double *d_partial,
 int launch_publish(const double *d_a, int na, double *h_a, const double *d_b, int nb, double *h_b, const int *d_flag, int *h_flag,
                    hipStream_t st);
 int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi /* SUMSQ_JOBS RED_BLOCKS */, hipStream_t st);
-// robust loss (ba_robust_kernels.hip): r <- sqrt(w) r and J <- sqrt(w) J per observation, in place (w = rho'(z) under the
-// handle's loss); d_w (optional) <- w.  Per-block partials of sum c^2 rho(z) at d_partial[0, nb) and of |r~|^2 at
-// d_partial[RED_BLOCKS, RED_BLOCKS + nb), nb = robust_blocks(nobs): a fixed grid, so a fixed summation tree
-int robust_blocks(int64_t nobs);
-int launch_robust_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, hipStream_t st);
+// the per-observation pass over r and J (ba_obs_kernels.hip; robust loss, and information: DESIGN §5i), in place.  With
+// information on the handle r <- L' r (residual_plain: d_r holds the plain residual; else it is whitened already and stays) and,
+// d_J != null, J <- L' J; with_loss: r <- sqrt(w) r and J <- sqrt(w) J on top, w = rho'(z) under the handle's loss from |r^|^2
+// (d_w (optional) <- w).  d_partial (optional): per-block partials of sum c^2 rho(z) at d_partial[0, nb) and of |r~|^2 at
+// d_partial[RED_BLOCKS, RED_BLOCKS + nb), nb = obs_blocks(nobs): a fixed grid, so a fixed summation tree; they are written
+// whenever asked for.  No launch where neither the loss nor the information acts and no partials are asked for.
+// info_upload: the handle's factors to the device when they changed (ba_lm_set_obs_info)
+int obs_blocks(int64_t nobs);
+int launch_obs_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, bool residual_plain, bool with_loss,
+                     hipStream_t st);
+int info_upload(ba_problem *p);
 // fixed parameters (ba_fixed_kernels.hip): the handle's mask to the device when it changed (ba_lm_set_fixed); zeros into the
 // columns of J of the fixed parameters (no launch without a mask)
 int fix_upload(ba_problem *p);
@@ -197,14 +213,6 @@ int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double la
                           double *d_rhs, double *d_small, hipStream_t st);
 int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, const double *d_B, const double *d_Y, double *d_a,
                          double *d_small, hipStream_t st);
-// per-observation information (ba_info_kernels.hip): the handle's factors to the device when they changed
-// (ba_lm_set_obs_info).  launch_info_whiten: r <- L' r (residual_plain: d_r holds the plain residual; else it is whitened
-// already and stays) and, d_J != null, J <- L' J per observation, in place; with_loss: the handle's loss on top, as
-// launch_robust_scale applies it, from |r^|^2 (d_w (optional) <- w); d_partial (optional): the two per-block partials of
-// launch_robust_scale, same layout and grid.  No launch without an array.
-int info_upload(ba_problem *p);
-int launch_info_whiten(ba_problem *p, double *d_r, double *d_J, double *d_w, double *d_partial, bool residual_plain,
-                       bool with_loss, hipStream_t st);
 // the optional terms together (ba_lm.hip): fix_upload, prior_upload, shared_upload and info_upload
 int terms_upload(ba_problem *p);
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st);

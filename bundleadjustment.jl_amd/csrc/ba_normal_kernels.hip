@@ -22,12 +22,6 @@ namespace {
 
 constexpr int BLK = 256;
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // ---- point side: Hpp (xx,xy,xz,yy,yz,zz) and gp = A' r ------------------------------------------------
 __global__ __launch_bounds__(BLK) void k_point_blocks(int64_t npnts, const int *__restrict__ pt_ptr,
                                                        const int *__restrict__ pt_obs, const double *__restrict__ J,

@@ -13,7 +13,7 @@ import pytest
 import scipy.sparse as sp
 
 from _lm_ref import (F32_TOL, PCG_TOL, STEP_TOL, arrays, attach_loopback, check_cov, env, fixed_vector, gauge_kw, jac, kappa_jacobi,
-                     limit, lm_opts, loopback_world, ref_dense, residual, schur, solve)
+                     limit, lm_opts, loopback_world, ref_dense, residual, schur, solve, weights_cost)
 from _util import bits_report, parity_record, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,8 +165,9 @@ def test_c_abi_refuses_bad_arrays_and_keeps_the_handle(ba, small_prob, gpu_ok):
 
 @pytest.mark.gpu
 def test_identity_gives_the_plain_bits(ba, orc, small_prob, gpu_ok):
-    """Lambda = I everywhere.  Linear loss: lm_step and a 5-iteration solve give the bits of the run without the keyword
-    (multiplying by 1.0 is exact, a zero l10 adds nothing).  Under huber the two passes round differently: equal within the
+    """Lambda = I everywhere.  lm_step and a 5-iteration solve give the bits of the run without the keyword (multiplying by
+    1.0 is exact, a zero l10 adds nothing), and so do lm_step and robust_weights under every robust loss: one pass (k_obs_scale)
+    applies the loss with and without information, in the same arithmetic.  The huber step is also held to numpy at the
     project's limit of the step."""
     p = small_prob
     eye = _identity(p)
@@ -184,14 +185,21 @@ def test_identity_gives_the_plain_bits(ba, orc, small_prob, gpu_ok):
             rep = bits_report(s1.solution, s2.solution, f"variant {variant}: 5 iterations with sigma = 1 vs no obs_info")
             assert not rep, rep
             assert s1.log == s2.log and s1.objective == s2.objective
-        for lam in (30.0, 1e-2):
-            tol = STEP_TOL[lam]
-            d_ref, _, _, kappa = _ref_step(orc, p, p["x0"], lam, eye, "huber", 1.0)
-            a = ba.lm_step(m, p["x0"], lam, loss="huber", f_scale=1.0, obs_info=eye)
-            b = ba.lm_step(plain, p["x0"], lam, loss="huber", f_scale=1.0)
-            e, lim = rel_err(a[0], b[0]), limit(tol, kappa)
-            print(f"obs_info identity, huber, lambda {lam:g}: step {e:.3e} (limit {lim:.1e}), vs numpy {rel_err(a[0], d_ref):.3e}")
-            assert e <= lim and rel_err(a[0], d_ref) <= lim
+        for loss in ("huber", "soft_l1", "cauchy", "arctan"):
+            for lam in (30.0, 1e-2):
+                a = ba.lm_step(m, p["x0"], lam, loss=loss, f_scale=1.0, obs_info=eye)
+                b = ba.lm_step(plain, p["x0"], lam, loss=loss, f_scale=1.0)
+                for got, want, name in zip(a, b, ("delta", "half_sq_model", "jtr")):
+                    rep = bits_report(np.atleast_1d(got), np.atleast_1d(want), f"{loss}, {name} at lambda {lam:g}: Lambda = I vs no obs_info")
+                    assert not rep, rep
+                if loss == "huber":
+                    d_ref, _, _, kappa = _ref_step(orc, p, p["x0"], lam, eye, "huber", 1.0)
+                    e, lim = rel_err(a[0], d_ref), limit(STEP_TOL[lam], kappa)
+                    print(f"obs_info identity, huber, lambda {lam:g}: step vs numpy {e:.3e} (limit {lim:.1e})")
+                    assert e <= lim
+            (wa, fa), (wb, fb) = m.robust_weights(p["x0"], loss, 1.0, obs_info=eye), plain.robust_weights(p["x0"], loss, 1.0)
+            rep = bits_report(wa, wb, f"{loss}: robust weights, Lambda = I vs no obs_info")
+            assert not rep and fa == fb, (rep, fa, fb)
     finally:
         m.close()
         plain.close()
@@ -382,7 +390,9 @@ def test_robust_eval_weights_and_cost_with_information(ba, small_prob, gpu_ok):
 @pytest.mark.gpu
 def test_robust_eval_many_tiles(ba, small_prob, gpu_ok):
     """nobs = 1024 * 256 + 300: more tiles than workgroups, so the loop over tiles runs more than once per workgroup, with a
-    tail.  145 copies of small_prob (their own cameras and points) and a 1444-observation scene behind them."""
+    tail.  145 copies of small_prob (their own cameras and points) and a 1444-observation scene behind them.  With information,
+    and huber without it (the instantiation without information reuses its LDS factors across the trips of the loop too) at the
+    limits of test_robust_eval_weights_and_cost; Lambda = I gives the bits of the run without information."""
     p, copies = small_prob, 145
     last = ba.synthetic.make_problem(12, 400, 1024 * 256 + 300 - copies * small_prob["nobs"], seed=12)
     parts = [p] * copies + [last]
@@ -397,6 +407,14 @@ def test_robust_eval_many_tiles(ba, small_prob, gpu_ok):
     m = ba.BALNLPModel(arrays=arrays(q))
     try:
         _check_eval(ba, m, q["x0"], info, ("linear", "huber"), 1.0, "obs_info_eval_many_tiles")
+        w, f = m.robust_weights(q["x0"], "huber", 1.0)
+        w_ref, f_ref = weights_cost(m.cons(q["x0"]), "huber", 1.0)
+        e, ef = float(np.max(np.abs(w - w_ref) / w_ref)), abs(f - f_ref) / f_ref
+        print(f"many tiles, huber without information: weights {e:.3e}, cost {ef:.3e}")
+        assert e <= 1e-14 and ef <= 1e-13, (e, ef)
+        wi, fi = m.robust_weights(q["x0"], "huber", 1.0, obs_info=_identity(q))
+        rep = bits_report(wi, w, "many tiles, huber: robust weights, Lambda = I vs no obs_info")
+        assert not rep and fi == f, (rep, fi, f)
     finally:
         m.close()
 

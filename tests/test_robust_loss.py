@@ -5,12 +5,17 @@ J~ = sqrt(w) J, w = rho'(z).  The references are numpy: the oracle's residuals /
 device call); the rest run on the GPU."""
 import ctypes as C
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 
 from _lm_ref import STEP_TOL, Ranks, arrays, env, loopback, residual, reweighted, solve, weights_cost  # noqa: F401 (loopback: a fixture)
 from _util import bits_report, rel_err
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import info_ref as ir  # noqa: E402
 
 LOSSES = ("linear", "huber", "soft_l1", "cauchy", "arctan")
 
@@ -103,6 +108,40 @@ def test_robust_eval_weights_and_cost(ba, orc, small_prob, gpu_ok, c):
         kind, scale = C.c_int(-1), C.c_double(0)
         ba._lib.check(ba._lib.lib().ba_lm_get_loss(m.handle, C.byref(kind), C.byref(scale)))
         assert (kind.value, scale.value) == (4, c)
+    finally:
+        m.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(4, 30, 100), (4, 70, 256), (6, 100, 512)], ids=["partial_tile", "one_tile", "two_tiles"])
+def test_robust_eval_tile_shapes(ba, gpu_ok, shape):
+    """The tile of 256 observations of k_obs_scale at its edges: one partial tile, exactly one full tile, two full tiles without
+    a tail.  Every loss, against numpy on the device's own residual at the limits of test_robust_eval_weights_and_cost: without
+    information, with a seeded array of information matrices, and with Lambda = I, which gives the bits of the run without
+    information.  The partial tile also through lm_step under huber (the J side of the tile), Lambda = I against none by bits."""
+    p = ba.synthetic.make_problem(*shape, seed=5)
+    info, eye = ir.random_info(p, 5), np.broadcast_to(np.eye(2), (p["nobs"], 2, 2)).copy()
+    m = ba.BALNLPModel(arrays=arrays(p))
+    try:
+        r = m.cons(p["x0"])
+        for loss in LOSSES:
+            w, f = m.robust_weights(p["x0"], loss, 1.0)
+            for what, (got_w, got_f), (w_ref, f_ref) in (
+                    ("plain", (w, f), weights_cost(r, loss, 1.0)),
+                    ("information", m.robust_weights(p["x0"], loss, 1.0, obs_info=info), ir.weights_cost(r, info, loss, 1.0))):
+                e, ef = float(np.max(np.abs(got_w - w_ref) / w_ref)), abs(got_f - f_ref) / f_ref
+                print(f"nobs {p['nobs']}, {loss}, {what}: weights {e:.3e}, cost {ef:.3e}")
+                assert e <= 1e-14, f"{loss}, {what}: weights, max relative error {e:.3e}"
+                assert ef <= 1e-13, f"{loss}, {what}: cost {got_f!r} vs {f_ref!r}"
+            wi, fi = m.robust_weights(p["x0"], loss, 1.0, obs_info=eye)
+            rep = bits_report(wi, w, f"{loss}: robust weights, Lambda = I vs no obs_info")
+            assert not rep and fi == f, (rep, fi, f)
+        if p["nobs"] == 100:
+            a = ba.lm_step(m, p["x0"], 30.0, loss="huber", f_scale=1.0, obs_info=eye)
+            b = ba.lm_step(m, p["x0"], 30.0, loss="huber", f_scale=1.0)
+            for got, want, name in zip(a, b, ("delta", "half_sq_model", "jtr")):
+                rep = bits_report(np.atleast_1d(got), np.atleast_1d(want), f"huber, {name}: Lambda = I vs no obs_info")
+                assert not rep, rep
     finally:
         m.close()
 

@@ -1,6 +1,6 @@
-"""Cost of per-observation information (ba_lm_set_obs_info) on BAL shapes: the time of the whitening pass k_info_whiten per call
-(per-kernel event timing, ba_profile_get) with an isotropic obs_info under the linear loss and under huber, beside the time of
-k_robust_scale of a huber solve without information on the same handle, and their algorithmic traffic (440 against 416 bytes
+"""Cost of per-observation information (ba_lm_set_obs_info) on BAL shapes: the time of the per-observation pass k_obs_scale per call
+(per-kernel event timing, ba_profile_get: class k_info_whiten) with an isotropic obs_info under the linear loss and under huber, beside
+its time in a huber solve without information on the same handle (class k_robust_scale), and their algorithmic traffic (440 against 416 bytes
 per observation: r and J read and written once, plus the three factors).  The pass also runs on the trial residual alone (40
 bytes per observation); the two kinds of call are told apart by one lm_step (one call, r and J) beside a solve of `iters`
 iterations.  One JSON object per shape on stdout; all of them to `out.json` when given.

@@ -1,4 +1,4 @@
-"""Cost of a robust loss (ba_lm_set_loss) on BAL shapes: the time of the reweighting pass k_robust_scale per call (per-kernel
+"""Cost of a robust loss (ba_lm_set_loss) on BAL shapes: the time of the reweighting pass (k_obs_scale, profile class k_robust_scale) per call (per-kernel
 event timing, ba_profile_get) and its algorithmic traffic (416 bytes per observation: r and J read and written once), and the
 ms per LM iteration of a huber solve against a linear one on the same handle (alternating, median of `reps` runs of `iters`
 iterations each, after a warm-up solve).  One JSON object per shape on stdout; all of them to `out.json` when given.
