@@ -2315,7 +2315,7 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
     const int both = std::min(pat->a_clean, pat->b_clean);
     for (int i = 0; i < both; i++) {
       const int slot = i & 1;
-      const PairRows a = pair_rows(w, i), b = pair_rows(w, pat->split + i);  // (c1 >= 2 inside a run)
+      const PairRows a = pair_rows(w, i), b = pair_rows(w, pat->split + i);  // (c1 >= 2, U_q not empty: tile_pattern_build ends a run before a shorter pair)
       T *VA = w->vpanel(slot, 0, 0), *VB = w->vpanel(slot, 0, 1);  // the slots alternate for the look-ahead
       auto tile = [&](int k) { return w->S + tix(w->hco(), k, k) * NB * NB; };
       auto panel_of = [&](int k, T *V, const int *rows) { return RunPanel<T>{w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, rows}; };

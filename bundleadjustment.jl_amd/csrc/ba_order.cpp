@@ -631,6 +631,15 @@ void tile_pattern_build(int64_t nt, std::vector<unsigned char> &occ /* nt x nt, 
     if (ac < 0) ac = a;
     int bc = 0;
     while (a + bc < npairs && !dirty[(size_t)(2 * (a + bc))] && (2 * (a + bc) + 1 >= nt || !dirty[(size_t)(2 * (a + bc) + 1)])) bc++;
+    // ... and a run ends before its first pair without a row below its own two (row list {k+1} alone, or empty: U_q is empty
+    // where a component of the camera graph ends on a pair boundary, and at the last pair).  The two-run launches of
+    // dense_ldl_factor_sparse give a run 4 |U_q| workgroups for its second panel solve and have no form for none; such a pair
+    // goes with the in-order pairs, whose panel chain has one.  A prefix of a clean run is clean.
+    auto rows_of = [&](int q) { return out->prow_ptr[(size_t)q + 1] - out->prow_ptr[(size_t)q]; };
+    for (int q = 0; q < ac; q++)
+      if (rows_of(q) < 2) ac = q;
+    for (int q = 0; q < bc; q++)
+      if (rows_of(a + q) < 2) bc = q;
     if (std::min(ac, bc) >= 4) {
       out->split = a;
       out->a_clean = ac;

@@ -18,7 +18,8 @@ struct TilePattern {
   double flop_fill = 1.0;           // trailing-update tiles of the pattern / of the dense factorisation
   // Two independent chains (elimination from both ends of a profile-ordered sequence, see cam_order): the pairs [0, a_clean)
   // and [split, split + b_clean) touch disjoint tiles and no other pair before `split` touches the second group's columns, so
-  // the two runs may factor side by side; all other pairs follow in index order.  0 / 0: one chain.
+  // the two runs may factor side by side; all other pairs follow in index order.  Every pair of a run has at least 2 rows in
+  // its list (U_q not empty): a run ends before its first shorter pair.  0 / 0: one chain.
   int split = 0, a_clean = 0, b_clean = 0;
 };
 

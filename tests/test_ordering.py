@@ -68,7 +68,8 @@ def test_hub_cameras_are_deferred(ba):
 
 
 def test_ordering_edge_cases(ba):
-    # two cameras, one point; a camera without observations; disconnected components
+    # two cameras, one point; a camera without observations; disconnected components (here: a permutation comes back; what
+    # the tile pattern and the factorisation make of scenes with several components: tests/test_block_sparse_scenes.py)
     perm, tf, ff, bf = ba.schur_ordering(np.array([1, 2]), np.array([1, 1]), 2, 1, "AMD")
     assert sorted(perm.tolist()) == [1, 2]
     cam = np.array([1, 2, 4, 5, 1, 2], dtype=np.int64)
@@ -84,7 +85,8 @@ def test_two_ended_elimination_of_a_long_profile(ba):
     """From 768 cameras on, the best profile sequence is also offered eliminated FROM BOTH ENDS (first half forwards, the
     cameras not adjacent to it backwards from the far end, the frontier last): two independent runs of tile column pairs, no
     fill beyond the band's own.  The fill must stay that of the one-ended sequence; that the runs are independent is checked
-    by the symbolic phase itself (and the factorisation's results by the GPU tests)."""
+    by the symbolic phase itself, re-derived from the row lists in tests/test_block_sparse_scenes.py (and the factorisation's
+    results by the GPU tests)."""
     p = ba.synthetic.make_problem(1100, 6000, 30000, seed=35, locality=0.1)
     q, _ = ba.synthetic.shuffle_cameras(p, seed=8)
     _, tf_nat, ff_nat, _ = ba.schur_ordering(p["cam_idx1"], p["pnt_idx1"], p["ncams"], p["npnts"], "natural")
