@@ -64,6 +64,7 @@ SYMBOLS = [
     "ba_lm_step", "ba_lm_step_f32", "ba_lm_step_pcg", "ba_lm_schur_pattern", "ba_lm_schur_memory", "ba_schur_ordering", "ba_lm_set_ordering", "ba_lm_schur_ordering", "ba_lm_set_loss", "ba_lm_get_loss", "ba_robust_eval", "ba_lm_set_fixed", "ba_lm_get_fixed", "ba_lm_set_priors", "ba_lm_get_priors", "ba_prior_eval", "ba_covariance", "ba_profile_enable", "ba_profile_reset", "ba_profile_get", "ba_dense_ldl_solve", "ba_dense_ldl_solve_f32",
     "ba_lm_set_shared_intrinsics", "ba_lm_get_shared_intrinsics", "ba_dense_ldl_solve_multi",
     "ba_lm_set_obs_info", "ba_lm_get_obs_info",
+    "ba_refine_points", "ba_refine_points_dev",
 ]
 
 _lib = None
@@ -137,6 +138,8 @@ def lib():
     L.ba_dense_ldl_solve_multi.argtypes = [C.c_int, i64, vp, C.c_int, vp, vp, C.POINTER(f64)]
     L.ba_lm_set_obs_info.argtypes = [vp, vp]
     L.ba_lm_get_obs_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.ba_refine_points.argtypes = [vp, vp, C.c_int, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int)]
+    L.ba_refine_points_dev.argtypes = [vp, vp, C.c_int, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
     _lib = L
     return L
 
@@ -522,6 +525,11 @@ def get_obs_info(handle):
     n, z = C.c_int64(0), C.c_int64(0)
     check(lib().ba_lm_get_obs_info(handle, C.byref(n), C.byref(z)))
     return n.value, z.value
+
+
+# states of ba_refine_points (BA_PT_*): the low bits of a point's status; BA_PT_BEHIND is OR-ed into it
+POINT_STATES = ("converged", "stalled", "max_iter", "fixed", "degenerate", "nonfinite")
+POINT_BEHIND = 0x80
 
 
 # the matrix of DESIGN §5h as Python sees it (the communicator and ba_covariance columns are the library's): per term the

@@ -223,6 +223,7 @@ enum ProfClass {
   PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step_multi / k_bwd_step_multi; also ba_dense_ldl_solve_multi)
   PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
   PC_INFO,           // per-observation information (ba_lm_set_obs_info): "k_info_whiten": k_obs_scale on a handle with it, the whitening of r and J (with the loss's reweighting)
+  PC_REFINE_POINTS,  // points with the cameras held (ba_refine_points): k_cam_pre and k_refine_points
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -319,6 +320,21 @@ struct PriorSet {
 };
 enum { PRI_PNT = 0, PRI_CAM, PRI_CTR, PRI_KINDS };
 
+// points with the cameras held (ba_refine_points, ba_point_kernels.hip): the point list split by degree once per problem
+// (wave_pts: degree > the tier threshold, one wave each; lane_pts: the others, one lane each, by descending degree), the
+// per-point lookup of the point priors (-1: none; rebuilt when ba_lm_set_priors changed them), the eight device counters of a
+// call (BA_PT_STATES states, the BEHIND flags, the most trials of a point) and the host entry's status / cost staging
+struct PointWork {
+  bool split = false;
+  int64_t n_lane = 0, n_wave = 0;
+  DevBuf<int> lane_pts, wave_pts;
+  DevBuf<int> pri_of;
+  int64_t pri_version = -1;
+  DevBuf<unsigned long long> counts;
+  DevBuf<uint8_t> status;
+  DevBuf<double> cost;
+};
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -355,6 +371,7 @@ struct ba_problem {
   // per prior (kind after kind): d'Lambda d at the linearisation, at the trial point, and the step's model term
   PriorSet pri[PRI_KINDS];
   bool pri_dirty = false;
+  int64_t pri_version = 0;  // counts the calls of ba_lm_set_priors (PointWork keeps a table derived from the point priors)
   DevBuf<double> pri_d, pri_H, pri_val;
   int64_t pri_total() const { return pri[PRI_PNT].n + pri[PRI_CAM].n + pri[PRI_CTR].n; }
   bool pri_on() const { return pri_total() > 0; }
@@ -381,6 +398,7 @@ struct ba_problem {
   int64_t info_zero = 0, info_version = 0;
   DevBuf<double> d_info;
   bool info_on() const { return info_set; }
+  PointWork pts;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;
@@ -419,6 +437,8 @@ int launch_residual_f32(ba_problem *p, const float *d_x, float *d_r, hipStream_t
 int launch_jac_structure(ba_problem *p, int64_t *d_rows, int64_t *d_cols, hipStream_t st);
 int launch_jac_coord_f64(ba_problem *p, const double *d_x, double *d_vals, hipStream_t st);
 int launch_jac_coord_f32(ba_problem *p, const float *d_x, float *d_vals, hipStream_t st);
+// the cam_pre rows of the cameras of d_x (CPAD doubles per camera) in the scratch the residual and Jacobian launchers use
+int launch_cam_pre_f64(ba_problem *p, const double *d_x, const double **d_cpre, hipStream_t st);
 
 // ---- launchers (ba_normal_kernels.hip) ----------------------------------------------------------
 // point side: H_pp (6/pt: xx,xy,xz,yy,yz,zz) and g_p (3/pt) from J, r.  Either output may be null.

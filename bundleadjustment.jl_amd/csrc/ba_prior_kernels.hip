@@ -458,6 +458,7 @@ extern "C" int ba_lm_set_priors(ba_problem *p, int64_t n_pnt, const int64_t *pnt
     p->pri[k].h_mu.swap(next[k].h_mu);
     p->pri[k].h_info.swap(next[k].h_info);
   }
+  p->pri_version++;
   p->pri_dirty = p->pri_on();  // (a handle whose priors are cleared keeps its device buffers, unused)
   return BA_OK;
 }

@@ -245,6 +245,58 @@ def covariance(nlp, x, lam=0.0, *, loss=None, f_scale=1.0, fixed_cameras=None, f
     return cam, pnt, piv.value
 
 
+def _opt_float(v, what):
+    """None, or a finite float (ValueError otherwise)"""
+    if v is None:
+        return None
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a finite number (or None), got {v!r}") from None
+    if not np.isfinite(f):
+        raise ValueError(f"{what} must be a finite number (or None), got {v!r}")
+    return f
+
+
+def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None,
+                  fixed_points=None, point_priors=None):
+    """The points of x with its cameras held (ba_refine_points): every point is an independent problem in 3 unknowns -- the
+    objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info` and `point_priors`, restricted to that point -- solved
+    by a Marquardt iteration of its own (accept test, damping and stopping test per point).  triangulate=True starts every
+    point from the linear triangulation of its rays instead of from x (the points of x are then not read): how an x0 is built
+    when only cameras are known.  max_iter (None: 50; 0: evaluate only -- with triangulate=True the triangulated points are
+    returned), xtol (None: 1e-10; |delta| <= xtol (|X| + xtol)), lam0 (None: 1e-4).  fixed_points are skipped.
+    Returns (x_new, info): x_new a copy of x with the points replaced (cameras and skipped points bit-identical); info a dict
+    with `status` (npnts names among _lib.POINT_STATES), `behind` (bool: at the returned point an observation sees it from
+    behind, P1.z >= 0), `cost_before`, `cost_after` (per point, cost_after <= cost_before), `counts` (points per status name,
+    plus "behind") and `iters_max`.  Bad arguments raise ValueError before any device call."""
+    terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_points=fixed_points, point_priors=point_priors,
+                              obs_info=obs_info)
+    if not isinstance(triangulate, (bool, np.bool_)):
+        raise ValueError(f"triangulate must be True or False, got {triangulate!r}")
+    if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
+        raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
+    tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
+    if (tol is not None and tol <= 0) or (l0 is not None and l0 <= 0):
+        raise ValueError(f"xtol and lam0 must be > 0 (or None), got {xtol!r} and {lam0!r}")
+    x = np.array(x, dtype=np.float64, copy=True)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    terms.apply(nlp, shared=False)  # (a grouping concerns the cameras: what the handle holds stays)
+    status = np.zeros(nlp.npnts, dtype=np.uint8)
+    cost = np.zeros((nlp.npnts, 2))
+    counts = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64)
+    its = C.c_int(0)
+    _lib.check(_lib.lib().ba_refine_points(nlp.handle, _lib.ptr(x), int(bool(triangulate)), -1 if max_iter is None else int(max_iter),
+                                           -1.0 if tol is None else tol, -1.0 if l0 is None else l0, _lib.ptr(status),
+                                           _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
+    names = np.array(_lib.POINT_STATES)
+    info = dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
+                cost_after=cost[:, 1].copy(), iters_max=its.value,
+                counts={**{n: int(c) for n, c in zip(_lib.POINT_STATES, counts)}, "behind": int(counts[-1])})
+    return x, info
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

@@ -436,6 +436,49 @@ int ba_covariance(ba_problem *p, const double *x, double lambda, double rank_tol
                   double *cam_cov /* ncams * 81, row-major 9x9 per camera, or NULL */,
                   double *pnt_cov /* npnts * 9, row-major 3x3 per point, or NULL */,
                   double *min_rel_pivot /* or NULL */);
+/* ---- points with the cameras held (an extension: the reference has no triangulation and no per-point solve) -------------
+ * With every camera entry of x held, point i is an independent least-squares problem in its 3 unknowns: the handle's objective
+ * restricted to that point,
+ *   f_i(X) = sum_{o in obs(i)} 1/2 c^2 rho(r^_o' r^_o / c^2) + 1/2 (X - mu)' Lambda (X - mu)
+ * rho and c from ba_lm_set_loss, r^ = L'r from ba_lm_set_obs_info (the plain r when none is set), the last term only for a point
+ * that carries a point prior (ba_lm_set_priors).  A point fixed by ba_lm_set_fixed is skipped (BA_PT_FIXED, its bits unchanged;
+ * its cost entries and the BEHIND flag are still evaluated).  Camera masks, camera and centre priors and shared intrinsics
+ * concern the cameras only and are ignored here.  No communicator is needed: on a shard (see multi-GPU) the call refines the
+ * shard's own points and the counts are local.
+ * init = 0 starts from the point in x.  init = 1 triangulates first and does not read the point in x: per observation with
+ * Lambda != 0 (otherwise unweighted) the measurement is undistorted by 8 fixed-point iterations of q <- u / (1 + k1 |q|^2 +
+ * k2 |q|^4), u = pt2d / f; the ray is d = R'(q_x, q_y, -1) / |.| through the centre c = -R't; X solves sum (I - dd') X =
+ * sum (I - dd') c by a 3 x 3 Cholesky.  A pivot <= 1e-12 trace, or fewer than two such observations: BA_PT_DEGENERATE.
+ * Iteration (Marquardt, per point): at X, w_o = rho'(z_o), H = sum w J^'J^ (+ Lambda), g = sum w J^'r^ (+ Lambda (X - mu)), J^ the
+ * whitened 2 x 3 point block; (H + lambda diag H) delta = -g by a 3 x 3 Cholesky (a failed or non-finite factorisation is a
+ * rejection); the step is accepted iff f_i(X + delta) <= f_i(X) (a non-finite cost is rejected), then lambda <- max(lambda / 10,
+ * 1e-12), else lambda <- 10 lambda.  States: CONVERGED after an accepted step with |delta| <= xtol (|X| + xtol), X the new point;
+ * STALLED when lambda > 1e12; MAX_ITER after max_iter trials; NONFINITE when the cost at the start is not finite (the point is
+ * unchanged, no flag); DEGENERATE as above and for a free point without an observation (unchanged, cost entries 0, no flag).
+ * BA_PT_BEHIND is OR-ed into the state when at the returned X an observation with Lambda != 0 has P1.z >= 0 (the BAL camera
+ * looks down -z: a point in front has P1.z < 0).
+ * max_iter < 0: 50; max_iter == 0 evaluates only (cost and flag written; with init = 0 x is untouched, with init = 1 it receives
+ * the triangulated points; state MAX_ITER); xtol <= 0: 1e-10; lambda0 <= 0: 1e-4.  xtol or lambda0 not finite, init outside
+ * 0 / 1: BA_ERR_ARG.
+ * cost[2 i] is f_i at the start (init = 1: at the triangulated point), cost[2 i + 1] at the returned point, never larger.
+ * counts[s] = points in state s, counts[BA_PT_STATES] = points flagged BEHIND.  iters_max: the most trials any point took.
+ * The camera part of x and every skipped or unchanged point come back bit-identical; two calls give the same bits; the next
+ * ba_lm_step / ba_lm_solve on the handle gives the same bits as without this call in between.
+ * ba_refine_points_dev: x, status and cost in device memory, enqueued on `stream` (NULL: the handle's); with counts and
+ * iters_max both NULL it does not synchronise, otherwise it waits for the stream to hand them over. */
+enum { BA_PT_CONVERGED = 0, BA_PT_STALLED = 1, BA_PT_MAX_ITER = 2, BA_PT_FIXED = 3,
+       BA_PT_DEGENERATE = 4, BA_PT_NONFINITE = 5, BA_PT_STATES = 6,
+       BA_PT_BEHIND = 0x80 /* flag OR-ed into the status */ };
+int ba_refine_points(ba_problem *p, double *x_inout /* nvar, host */, int init, int max_iter,
+                     double xtol, double lambda0,
+                     uint8_t *status /* npnts or NULL */, double *cost /* 2 npnts: before, after; or NULL */,
+                     int64_t *counts /* BA_PT_STATES + 1 (last: points flagged BEHIND) or NULL */,
+                     int *iters_max /* or NULL */);
+int ba_refine_points_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int init, int max_iter,
+                         double xtol, double lambda0,
+                         uint8_t *d_status /* npnts or NULL */, double *d_cost /* 2 npnts or NULL */,
+                         int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -117,3 +117,23 @@ function set_obs_info(nlp, info3)
   end
   return nothing
 end
+
+# points with the cameras held (an extension): include/ba_hip.h, ba_refine_points.  Refines the points of `x` in place under the
+# loss, information, point priors and fixed points the handle holds (set them with the setters above, or by an earlier
+# Levenberg_Marquardt call); `triangulate = true` starts every point from the linear triangulation of its rays.  Returns
+# (status :: Vector{UInt8} (BA_PT_* | 0x80 when behind a camera), cost :: 2 x npnts (before, after), counts :: Vector{Int64}
+# (the six states, then the points flagged behind), iters_max).
+function refine_points!(nlp, x :: Vector{Float64}; triangulate :: Bool = false, max_iter :: Integer = -1, xtol :: Real = -1.0,
+                        lam0 :: Real = -1.0)
+  status = zeros(UInt8, nlp.npnts)
+  cost = zeros(Float64, 2, nlp.npnts)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  GC.@preserve x status cost counts begin
+    bacheck(ccall((:ba_refine_points, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint}),
+                  nlp.handle, pointer(x), Cint(triangulate), Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status),
+                  pointer(cost), pointer(counts), iters))
+  end
+  return status, cost, counts, Int(iters[])
+end
