@@ -2187,7 +2187,8 @@ template <typename T>
 int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
   for (DevBuf<int> *q : {&w->prow, &w->lcol, &w->lpair}) q->reset();
   w->upd_ij.reset();
-  w->own_tiles.reset();
+  w->own_tiles.reset();  // (the layout changes: dense_ldl_list_tiles lists it again)
+  w->n_own_tiles = 0;
   w->pat = pat;
   w->sparse = pat != nullptr;
   if (!pat) return BA_OK;
@@ -2229,19 +2230,11 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
       if (co[j] >= 0) co[j] -= base;
     w->s_tiles = std::max<int64_t>(1, w->own_range[(size_t)me + 1] - base);
     if (w->own_only) {
-      // the running tile counts of the owned columns (k_ldl_update's OWN mode is not used with a pattern; the column scaling
-      // and the chunked assembly are), the stored tiles in storage order, and the update lists per pair
+      // the running tile counts of the owned columns (k_ldl_update's OWN mode is not used with a pattern; the chunked
+      // assembly is) and the update lists per pair
       w->h_own_pref.assign(1, 0);
-      std::vector<int2> tiles;
-      for (int j : w->h_own_cols) {
-        w->h_own_pref.push_back(w->h_own_pref.back() + w->h_col_cnt[(size_t)j]);
-        const int64_t q = j / 2;
-        tiles.push_back(make_int2(j, j));
-        for (int l = pat->prow_ptr[(size_t)q]; l < pat->prow_ptr[(size_t)q + 1]; l++)
-          if (pat->prow[(size_t)l] > j) tiles.push_back(make_int2(pat->prow[(size_t)l], j));
-      }
+      for (int j : w->h_own_cols) w->h_own_pref.push_back(w->h_own_pref.back() + w->h_col_cnt[(size_t)j]);
       BA_HIP_CHECK(hipMemcpy(w->own_pref, w->h_own_pref.data(), w->h_own_pref.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-      BA_CHECK(upload(w->own_tiles, tiles, 1));
       std::vector<int2> upd;
       const int npairs = (int)((nt + 1) / 2);
       w->h_upd_ptr.assign(1, 0);
@@ -2267,6 +2260,30 @@ int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat) {
   BA_CHECK(upload(w->lcol, pat->lcol, 1));
   BA_CHECK(upload(w->lpair, pat->lpair, 1));
   return BA_OK;
+}
+
+// own_tiles: the (i, j) of every tile the workspace stores, in storage order, read off its own offset table -- whatever the
+// layout (dense, owner-major, this rank's tile columns only, compressed).  The kernels that take one workgroup per stored tile
+// (k_scale_S_list, k_border_mask_S) rely on tile t of S being own_tiles[t]: the positions must be exactly 0 .. count - 1.
+int dense_ldl_list_tiles(DenseLDL *w) {
+  const int64_t nt = w->nt, *co = w->hco();
+  int64_t count = 0;
+  for (int64_t j = 0; j < nt; j++)
+    for (int64_t i = j; i < nt; i++) count += tix(co, i, j) >= 0;
+  std::vector<int2> tiles((size_t)count, make_int2(-1, -1));
+  for (int64_t j = 0; j < nt; j++)
+    for (int64_t i = j; i < nt; i++) {
+      const int64_t t = tix(co, i, j);
+      if (t < 0) continue;
+      if (t >= count || count > w->s_tiles || tiles[(size_t)t].x >= 0) {  // (count tiles, none past the end, none twice: a bijection)
+        ba_set_error("tile list: tile (%lld, %lld) at position %lld, taken or past the %lld stored tiles (internal error)", (long long)i,
+                     (long long)j, (long long)t, (long long)count);
+        return BA_ERR_ARG;
+      }
+      tiles[(size_t)t] = make_int2((int)i, (int)j);
+    }
+  w->n_own_tiles = count;
+  return upload(w->own_tiles, tiles, 1);
 }
 
 // The pair schedule over the pattern (see above); d_b != null: the forward substitution rides along.

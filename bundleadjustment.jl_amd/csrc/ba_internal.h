@@ -277,13 +277,16 @@ struct DenseLDLT {  // workspace of the blocked LDL^T in scalar type T, n = 9*nc
   bool sparse = false;
   const TilePattern *pat = nullptr;
   DevBuf<int> prow, lcol, lpair;
-  // ... on several ranks (per-rank ownership of the PATTERN's tile columns): tiles stored per tile column, the (i, j) of every
-  // tile this rank stores in storage order (column scaling), and per tile column pair q the tiles (i, j) -- both in U_q, j
-  // owned by this rank, sorted by (j, i) -- its trailing update touches here; the first h_upd_lead[q] of them lie in the next
-  // pair's own tile columns (look-ahead of the distributed factorisation)
+  // ... on several ranks (per-rank ownership of the PATTERN's tile columns): tiles stored per tile column, and per tile column
+  // pair q the tiles (i, j) -- both in U_q, j owned by this rank, sorted by (j, i) -- its trailing update touches here; the first
+  // h_upd_lead[q] of them lie in the next pair's own tile columns (look-ahead of the distributed factorisation)
   std::vector<int64_t> h_col_cnt;
   std::vector<int> h_upd_ptr, h_upd_lead;
-  DevBuf<int2> upd_ij, own_tiles;
+  DevBuf<int2> upd_ij;
+  // every layout: the (i, j) of the n_own_tiles tiles this workspace stores, in storage order (dense_ldl_list_tiles; the column
+  // scaling and the masking of the shared-intrinsics border walk it)
+  DevBuf<int2> own_tiles;
+  int64_t n_own_tiles = 0;
   HipEvent ev_dtop, ev_dchain;  // distributed factorisation: fork behind the reduce of S, end of the owner's panel chain
 };
 typedef DenseLDLT<double> DenseLDL;
@@ -469,6 +472,8 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
 // must outlive the workspace.
 template <typename T>
 int dense_ldl_use_pattern(DenseLDLT<T> *w, const TilePattern *pat);
+// DenseLDLT::own_tiles of the workspace's current layout (after dense_ldl_use_pattern, where a pattern is used)
+int dense_ldl_list_tiles(DenseLDLT<double> *w);
 // solve S x = b for one right-hand side held in d_b (length nt*NB, overwritten by x)
 template <typename T>
 int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool forward_done);

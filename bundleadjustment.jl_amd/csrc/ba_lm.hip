@@ -226,6 +226,7 @@ struct LMWork {
   DevBuf<int> cam_pnt;                   // nobs: the point of every observation in camera order (pnt0[cam_obs[q]])
   SchurTasks tasks;
   DenseLDL ldl;
+  SchurChunk whole;                // a rank that holds all of S: the whole matrix as one chunk (ensure_dense)
   std::vector<SchurChunk> chunks;  // per-rank ownership of S: chunks of tile columns, assembled and reduced one by one
   DevBuf<double> stage;            // the chunk being assembled for another owner (stage_tiles tiles)
   DevBuf<float> stage32;           // its Float32 copy when the reduce travels in Float32
@@ -666,7 +667,7 @@ static int order_cameras(ba_problem *p, LMWork *w, std::vector<int> *pos_out) {
 
 // what only the direct solves need: the tiles of S, the Schur task list, the per-observation Y blocks
 static int ensure_dense(ba_problem *p, LMWork *w) {
-  if (w->ldl.S) return BA_OK;
+  if (w->ldl.own_tiles) return BA_OK;  // (made behind S: a call that failed before it is redone whole)
   BA_CHECK(w->Yobs.alloc(6 * p->nobs));
   std::vector<int> pos;
   BA_CHECK(order_cameras(p, w, &pos));
@@ -684,7 +685,13 @@ static int ensure_dense(ba_problem *p, LMWork *w) {
   w->use_pattern = want && (!p->comm.active() || w->ldl.own_only);  // (several ranks: with per-rank ownership of S only)
   if (w->use_pattern) BA_CHECK(dense_ldl_use_pattern(&w->ldl, &w->pattern));  // (compressed layout: before S is allocated)
   BA_CHECK(dense_ldl_alloc_S(&w->ldl));
-  if (w->ldl.own_only) BA_CHECK(build_chunks(p, w));
+  // (the layout is final: the tile list of the column scaling and the border's masking; the Float32 twin is never scaled)
+  BA_CHECK(dense_ldl_list_tiles(&w->ldl));
+  if (w->ldl.own_only) return build_chunks(p, w);
+  w->whole.ntiles = w->ldl.s_tiles;
+  w->whole.cco = w->ldl.col_off;
+  w->whole.nkeys = w->tasks.nkeys;
+  w->whole.nskeys = w->tasks.nsplit;
   return BA_OK;
 }
 
@@ -779,7 +786,7 @@ static int refresh_linearisation(ba_problem *p, LMWork *w, bool residual_too, bo
   // adjacent in the reduce buffer (lm_ensure): one all-reduce
   BA_CHECK(launch_hcc_diag(p, w->Hcc, w->hdiag, st));
   // |r|^2, |gp|^2, |x_points|^2 and -- of the all-reduced gc -- |gc|^2, |x_cameras|^2: one launch pair on one rank, two with a
-  // communicator (the camera sums wait for the all-reduce); bit-identical to launch_sumsq per vector either way
+  // communicator (the camera sums wait for the all-reduce); the same bits per vector either way
   SumsqJobs jobs;
   if (robust) {  // 2 f and |r~|^2 from k_obs_scale's partials
     const int nb = obs_blocks(p->nobs);
@@ -944,10 +951,27 @@ static int pcg_step(ba_problem *p, LMWork *w, double lambda, hipStream_t st) {
                         &w->model_done);
 }
 
-// S of a rank that holds all of it: every 9 x 9 block straight into the tiles (this rank's partial sums: reduce_camera_system)
+// the 9 x 9 blocks of one chunk of S into dest, cleared first (behind launch_schur_pre; the unit diagonal of the padding rows
+// by rank 0)
+static int assemble_chunk(ba_problem *p, LMWork *w, const SchurChunk &c, double *dest, double lam_diag, const double *d_lambda,
+                          const double *damp, hipStream_t st) {
+  ProfScope ps(p, PC_SCHUR_S, st);
+  BA_HIP_CHECK(hipMemsetAsync(dest, 0, (size_t)c.ntiles * NB * NB * sizeof(double), st));
+  return launch_schur_chunk(p, &w->tasks, &c, w->J_lin(), w->Yobs, w->Hcc, lam_diag, dest, w->n, p->rank == 0 ? w->npad : w->n, st,
+                            d_lambda, damp, false);
+}
+
+// S of a rank that holds all of it: every 9 x 9 block straight into the tiles, the whole matrix as one chunk (this rank's
+// partial sums: reduce_camera_system).  One profiling scope over all of it.  The launches keep the order this assembly has
+// always had -- zero-fill of S, k_obs_y, short keys, partial sums of the split keys, their sums.  The order means nothing to
+// the result; the zero-fill behind k_obs_y and the partial sums ahead of the short keys were both tried on the Venice shape
+// and neither measured faster (the class time 0.2 % and 2 % above this order's, at a spread of 0.1 % and 1 %)
 static int assemble_local(ba_problem *p, LMWork *w, double lam_diag, const double *d_lambda, const double *damp, hipStream_t st) {
-  return launch_schur_blocks(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, w->Hcc, lam_diag, w->ldl.S, w->ldl.col_off, w->n,
-                             p->rank == 0 ? w->npad : w->n, st, d_lambda, damp, w->ldl.s_tiles);
+  ProfScope ps(p, PC_SCHUR_S, st);
+  BA_HIP_CHECK(hipMemsetAsync(w->ldl.S, 0, (size_t)w->whole.ntiles * NB * NB * sizeof(double), st));
+  BA_CHECK(launch_schur_pre(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, st, false));
+  return launch_schur_chunk(p, &w->tasks, &w->whole, w->J_lin(), w->Yobs, w->Hcc, lam_diag, w->ldl.S, w->n,
+                            p->rank == 0 ? w->npad : w->n, st, d_lambda, damp, true);
 }
 
 // per-rank ownership of S: chunk by chunk -- this rank's share of the chunk's sums goes straight into its own tiles
@@ -957,8 +981,7 @@ static int assemble_chunks_reduce(ba_problem *p, LMWork *w, double lam_diag, con
   for (const SchurChunk &c : w->chunks) {
     const bool mine = c.owner == w->ldl.rank;
     double *dest = mine ? w->ldl.S + c.t0 * NB * NB : w->stage;
-    BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, w->J_lin(), w->Yobs, w->Hcc, lam_diag, dest, w->n, p->rank == 0 ? w->npad : w->n, st,
-                                d_lambda, damp));
+    BA_CHECK(assemble_chunk(p, w, c, dest, lam_diag, d_lambda, damp, st));
     if (reduce32) {  // Float32 factorisation without column scaling: the partial sums travel as Float32
       float *d32 = mine ? w->ldl32.S + c.t0 * NB * NB : w->stage32;
       BA_CHECK(launch_convert(dest, d32, c.ntiles * NB * NB, st));
@@ -986,8 +1009,7 @@ static int assemble_chunks_rs(ba_problem *p, LMWork *w, double lam_diag, const d
     const int b = bufs == 2 ? (ci++ & 1) : 0;
     double *dst = w->stage + b * buf_elems;
     if (bufs == 2 && used[b]) BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_stage_free[b], 0));  // its last transfer is through
-    BA_CHECK(launch_schur_chunk(p, &w->tasks, &c, w->J_lin(), w->Yobs, w->Hcc, lam_diag, dst, w->n, p->rank == 0 ? w->npad : w->n, st,
-                                d_lambda, damp));
+    BA_CHECK(assemble_chunk(p, w, c, dst, lam_diag, d_lambda, damp, st));
     const int64_t seg_elems = c.seg * NB * NB, my_elems = c.my_n * NB * NB;
     float *d32 = reduce32 ? w->stage32 + b * buf_elems : nullptr;
     if (reduce32) BA_CHECK(launch_convert(dst, d32, c.ntiles * NB * NB, st));
@@ -1013,14 +1035,7 @@ static int assemble_chunks_rs(ba_problem *p, LMWork *w, double lam_diag, const d
 // :J / :A column scaling of the camera system from the GLOBAL diagonal (refresh_linearisation)
 static int scale_columns(ba_problem *p, LMWork *w, double lambda, const double *d_lambda, hipStream_t st) {
   BA_CHECK(launch_cam_scale(p, w->hdiag, w->mode.normalize == 2 ? lambda : 0.0, w->colscale, st, d_lambda, w->tasks.pos));
-  const DenseLDL &l = w->ldl;
-  const int64_t own_tiles = l.own_only ? l.own_range[(size_t)l.rank + 1] - l.own_range[(size_t)l.rank] : 0;
-  if (l.own_only && w->use_pattern)
-    BA_CHECK(launch_scale_S_list(p, w->n, w->colscale, l.S, l.own_tiles, own_tiles, st));
-  else if (l.own_only)
-    BA_CHECK(launch_scale_S_own(p, w->n, w->colscale, l.S, l.col_off, l.own_cols, l.own_pref, (int)l.h_own_cols.size(), own_tiles, st));
-  else
-    BA_CHECK(launch_scale_S(p, w->n, l.nt, w->colscale, l.S, l.col_off, st));
+  BA_CHECK(launch_scale_S_list(p, w->n, w->colscale, w->ldl.S, w->ldl.own_tiles, w->ldl.n_own_tiles, st));
   return launch_scale_vec(p, w->n, w->colscale, w->rhs, 1, st);
 }
 
@@ -1063,7 +1078,10 @@ static int linear_step(ba_problem *p, LMWork *w, double lambda, bool recorded, h
   const bool reduce32 = dist && m.facto_f32 && !normalize;
   if (reduce32) BA_CHECK(ensure_f32(w));
   if (w->ldl.own_only) {
-    BA_CHECK(launch_schur_pre(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, st));
+    {
+      ProfScope ps(p, PC_SCHUR_S, st);
+      BA_CHECK(launch_schur_pre(p, &w->tasks, w->J_lin(), w->Uinv, w->Yobs, st, true));
+    }
     if (w->assembly_rs) BA_CHECK(assemble_chunks_rs(p, w, lam_diag, d_lambda, damp, reduce32, st));
     else BA_CHECK(assemble_chunks_reduce(p, w, lam_diag, d_lambda, damp, reduce32, st));
     BA_HIP_CHECK(hipMemsetAsync(w->rhs, 0, (size_t)w->npad * sizeof(double), st));
@@ -1137,7 +1155,6 @@ static int trial_point(ba_problem *p, LMWork *w, bool with_delta, bool recorded,
     ba_set_error("trial point of a rescaled step with priors (internal error: the line search is refused with priors)");
     return BA_ERR_ARG;
   }
-  if (!with_delta && !robust) return launch_sumsq(p, w->nequ, w->r_trial, w->partial, w->scal, SH_RSQ_TRIAL, st);
   SumsqJobs jobs;
   if (with_delta) {
     jobs.add(w->delta, 3 * p->npnts, w->scal, SH_DELTA_P);

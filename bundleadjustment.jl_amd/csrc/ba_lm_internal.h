@@ -33,14 +33,16 @@ struct SchurTasks {
 };
 
 // one chunk of tile columns of the reduced camera matrix in a distributed run with per-rank ownership of S: the columns
-// [owner's local tile range t0 .. t0 + ntiles), the keys whose 9 x 9 blocks touch them, its offset table (negative: not here)
+// [owner's local tile range t0 .. t0 + ntiles), the keys whose 9 x 9 blocks touch them, its offset table (negative: not here).
+// A rank that holds all of S assembles it as ONE chunk (LMWork::whole): every tile, the workspace's own offset table, no key
+// lists -- the kernels then take every key (k_schur_blocks in its run-ahead loop) and every split key
 struct SchurChunk {
   int owner = 0;           // -1: a reduce-scatter chunk -- one segment per owner, `seg` tiles each, laid out by rank
   int64_t t0 = 0, ntiles = 0;
   int64_t seg = 0, my_t0 = 0, my_n = 0;  // reduce-scatter chunk: tiles per segment; where this rank's segment goes in its own S
-  int64_t *cco = nullptr;  // device, nt entries (cco_alloc + 1: tix reads the table's head one entry before)
+  const int64_t *cco = nullptr;  // device, nt entries (cco_alloc + 1: tix reads the table's head one entry before)
   DevBuf<int64_t> cco_alloc;
-  DevBuf<int> keys, skeys;  // device: key ids / indices into the split-key list
+  DevBuf<int> keys, skeys;  // device: key ids / indices into the split-key list (empty: all of them)
   int64_t nkeys = 0, nskeys = 0;
 };
 
@@ -142,19 +144,16 @@ int launch_schur_prep(ba_problem *p, double lambda, const double *d_Hpp, const d
                       double *d_u, hipStream_t st, const double *d_lambda = nullptr, const double *d_damp = nullptr,
                       double *d_lambda_copy = nullptr /* d_lambda (may be pinned host memory) is copied here */,
                       double *d_zero = nullptr, int64_t nzero = 0 /* cleared on the way */);
-int launch_schur_blocks(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y,
-                        const double *d_Hcc, double lambda, double *d_S, const int64_t *d_col_off, int64_t n, int64_t npad,
-                        hipStream_t st, const double *d_lambda = nullptr, const double *d_damp = nullptr, int64_t s_tiles = 0);
 // facto_type = Float16 (ba_normal_kernels.hip, k_f16_cols): |J_j|^2 of every column; column scaling + Float16 rounding
 int launch_col_sq(ba_problem *p, const double *d_Hpp, const double *d_hdiag, double *d_jn2, hipStream_t st);
 int launch_f16_scale(ba_problem *p, double lambda, double mu, const double *d_jn2, const double *d_J, const double *d_r,
                      double *d_dcol, double *d_damp, double *d_Jq, double *d_rq, hipStream_t st);
-int launch_schur_pre(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y, hipStream_t st);
+// (partials: the split keys' partial sums are formed by this launcher -- by exactly one of the two, see ba_normal_kernels.hip)
+int launch_schur_pre(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y, hipStream_t st,
+                     bool partials);
 int launch_schur_chunk(ba_problem *p, const SchurTasks *T, const SchurChunk *c, const double *d_J, const double *d_Y,
                        const double *d_Hcc, double lambda, double *dest, int64_t n, int64_t npad, hipStream_t st,
-                       const double *d_lambda = nullptr, const double *d_damp = nullptr);
-int launch_scale_S_own(ba_problem *p, int64_t n, const double *d_dsc, double *d_S, const int64_t *d_col_off, const int *d_own_cols,
-                       const int64_t *d_own_pref, int ncols, int64_t ntiles, hipStream_t st);
+                       const double *d_lambda, const double *d_damp, bool partials);
 int launch_scale_S_list(ba_problem *p, int64_t n, const double *d_dsc, double *d_S, const int2 *d_tiles, int64_t ntiles, hipStream_t st);
 int launch_schur_rhs(ba_problem *p, const double *d_J, const double *d_r, const double *d_u, double *d_rhs,
                      hipStream_t st, const int *d_cam_pnt = nullptr, const int *d_pos = nullptr /* block row of a camera */);
@@ -164,8 +163,6 @@ int launch_backsub(ba_problem *p, const double *d_J, const double *d_Uinv, const
                    double *d_scal = nullptr, int slot = 0, bool *model_done = nullptr);
 int launch_model_sq(ba_problem *p, const double *d_J, const double *d_r, const double *d_delta, double *d_partial,
                     double *d_scal, int slot, hipStream_t st, double cr = 1.0);
-int launch_sumsq(ba_problem *p, int64_t n, const double *d_v, double *d_partial, double *d_scal, int slot,
-                 hipStream_t st);
 // d_a[0..na), d_b[0..nb), d_flag[0] (optional) -> pinned host buffers, one launch
 int launch_publish(const double *d_a, int na, double *h_a, const double *d_b, int nb, double *h_b, const int *d_flag, int *h_flag,
                    hipStream_t st);
@@ -219,8 +216,6 @@ int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, 
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st);
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,
                      const double *d_lambda = nullptr, const int *d_pos = nullptr);
-int launch_scale_S(ba_problem *p, int64_t n, int64_t nt, const double *d_dsc, double *d_S, const int64_t *d_col_off,
-                   hipStream_t st);
 int launch_scale_scalar(ba_problem *p, int64_t n, double *d_v, double alpha, hipStream_t st);
 int launch_scale_vec(ba_problem *p, int64_t n, const double *d_s, double *d_v, int divide, hipStream_t st);
 

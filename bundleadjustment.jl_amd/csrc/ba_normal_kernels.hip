@@ -610,24 +610,6 @@ __global__ __launch_bounds__(BLK) void k_hcc_diag(int64_t ncams, const double *_
   hdiag[i] = Hcc[45 * c + j * (j + 1) / 2 + j];
 }
 
-// one workgroup per stored tile: S_ij /= d_i d_j   (padding rows/columns have d = 1)
-__global__ __launch_bounds__(BLK) void k_scale_S(int64_t n, int64_t nt, const double *__restrict__ dsc, double *__restrict__ S,
-                                                  const int64_t *__restrict__ co) {
-  const int64_t t = blockIdx.x;  // enumerates the lower tile pairs (ti >= tj) row by row; the storage order is co's
-  int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-  while (ti * (ti + 1) / 2 > t) ti--;
-  const int64_t tj = t - ti * (ti + 1) / 2;
-  const int64_t tt = tix(co, ti, tj);
-  if (tt < 0) return;  // (compressed block-sparse storage: not in the pattern)
-  double *T = S + tt * NB * NB;
-  for (int e = threadIdx.x; e < NB * NB; e += BLK) {
-    const int64_t r = ti * NB + (e >> 7), c = tj * NB + (e & (NB - 1));
-    const double dr = r < n ? dsc[r] : 1.0, dc = c < n ? dsc[c] : 1.0;
-    T[e] /= dr * dc;
-  }
-}
-
 // unit diagonal on the padding rows n..npad-1 so that the padded matrix stays factorisable
 __global__ void k_pad_diag(int64_t n, int64_t npad, double *S, const int64_t *co) {
   int64_t i = n + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -746,17 +728,6 @@ __global__ __launch_bounds__(BLK) void k_model_sq(int64_t nobs, int64_t npnts, c
   if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// sum of squares of a vector -> per-block partials (fixed grid => fixed summation tree)
-__global__ __launch_bounds__(BLK) void k_sumsq(int64_t n, const double *__restrict__ v, double *__restrict__ partial) {
-  __shared__ double red[BLK / 64];
-  double acc = 0;
-  for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n; i += (int64_t)gridDim.x * BLK) acc += v[i] * v[i];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // final stage: one block sums `np` partials into out[slot]
 __global__ __launch_bounds__(BLK) void k_sum_partials(int np, const double *__restrict__ partial, double *__restrict__ out,
                                                        int slot) {
@@ -772,8 +743,8 @@ __global__ __launch_bounds__(BLK) void k_sum_partials(int np, const double *__re
 // Several sums of squares in ONE launch pair (the LM loop needs |r|^2, |gp|^2, |x_p|^2 ... one after the other: on small
 // problems every one of those two-kernel launches costs more in launch latency than in work).  (A job may also be the robust
 // cost of a residual vector or a plain sum of partials: SumsqJobs::kind.)  Vector v owns the blocks
-// [v RED_BLOCKS, v RED_BLOCKS + nb_v) and sums exactly what k_sumsq would with a grid of nb_v blocks; the second kernel is
-// k_sum_partials per vector, one after the other in ONE workgroup: the results are bit-identical to the separate launches.
+// [v RED_BLOCKS, v RED_BLOCKS + nb_v), a grid-stride sum over nb_v blocks whatever else the launch carries; the second kernel is
+// k_sum_partials per vector, one after the other in ONE workgroup: a vector's sum does not depend on the jobs beside it.
 __global__ __launch_bounds__(BLK) void k_sumsq_multi(SumsqJobs jobs, double *__restrict__ partial) {
   __shared__ double red[BLK / 64];
   const int v = blockIdx.x / RED_BLOCKS, b = blockIdx.x % RED_BLOCKS;
@@ -1230,6 +1201,13 @@ __global__ __launch_bounds__(1024) void k_cg_beta_dir(int64_t n, int nb, const d
 
 
 static inline unsigned grid_for(int64_t n, int blk) { return (unsigned)((n + blk - 1) / blk); }
+// one wave per item (the Schur kernels: a key, a chunk of a long key, a split key), BLK / 64 items per workgroup; at most
+// 2^22 workgroups (x 256 lanes = 2^30 work-items), the waves stride over what is left
+static inline unsigned wave_grid(int64_t n) {
+  return (unsigned)std::min<int64_t>((n + BLK / 64 - 1) / (BLK / 64), (int64_t)1 << 22);
+}
+// workgroups of the first stage of a fixed-tree reduction over n items: one per BLK items, at least one, at most RED_BLOCKS
+static inline int red_blocks(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + BLK - 1) / BLK, 1), RED_BLOCKS); }
 
 int launch_point_blocks(ba_problem *p, const double *d_J, const double *d_r, double *d_Hpp, double *d_gp,
                         hipStream_t st) {
@@ -1275,104 +1253,48 @@ int launch_schur_prep(ba_problem *p, double lambda, const double *d_Hpp, const d
   return BA_OK;
 }
 
-int launch_schur_blocks(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y,
-                        const double *d_Hcc, double lambda, double *d_S, const int64_t *d_col_off, int64_t n, int64_t npad,
-                        hipStream_t st, const double *d_lambda, const double *d_damp, int64_t s_tiles) {
-  ProfScope ps(p, PC_SCHUR_S, st);
-  // s_tiles: the tiles S holds (the whole lower triangle, or only the pattern's with compressed block-sparse storage)
-  BA_HIP_CHECK(hipMemsetAsync(d_S, 0, (size_t)(s_tiles > 0 ? s_tiles * NB * NB : dense_ldl_tiles_doubles(n)) * sizeof(double), st));
-  if (p->nobs > 0)
-    hipLaunchKernelGGL(k_obs_y, dim3(grid_for(p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->pnt0, d_J, d_Uinv, d_Y);
-  if (T->nkeys > 0) {
-    int64_t nb = (T->nkeys + BLK / 64 - 1) / (BLK / 64);
-    if (nb > (int64_t)1 << 22) nb = (int64_t)1 << 22;  // 2^22 blocks x 256 lanes = 2^30 work-items
-    const double *damp_c = d_damp ? d_damp + 3 * p->npnts : (const double *)nullptr;
-    hipLaunchKernelGGL(k_schur_blocks, dim3((unsigned)nb), dim3(BLK), 0, st, T->nkeys, T->key_ptr,
-                       T->key_ca, T->key_cb, T->task_a, T->task_b, d_J, d_Y, d_Hcc, lambda, d_lambda, d_S, d_col_off, damp_c,
-                       T->nsplit > 0 ? 2 * T->chunk : 0, (const int *)nullptr, T->cam_of);
-    if (T->nsplit > 0) {  // long keys: chunk partials, then their fixed-order sums
-      int64_t nbc = (T->nchunks + BLK / 64 - 1) / (BLK / 64), nbs = (T->nsplit + BLK / 64 - 1) / (BLK / 64);
-      if (nbc > (int64_t)1 << 22) nbc = (int64_t)1 << 22;
-      if (nbs > (int64_t)1 << 22) nbs = (int64_t)1 << 22;
-      hipLaunchKernelGGL(k_schur_chunks, dim3((unsigned)nbc), dim3(BLK), 0, st, T->nchunks, T->chunk_t0, T->chunk_t1, T->task_a,
-                         T->task_b, d_J, d_Y, T->partial);
-      hipLaunchKernelGGL(k_schur_combine, dim3((unsigned)nbs), dim3(BLK), 0, st, T->nsplit, T->skey, T->skey_c0, T->key_ca,
-                         T->key_cb, T->partial, d_Hcc, lambda, d_lambda, d_S, d_col_off, damp_c, (const int *)nullptr, T->cam_of);
-    }
-  }
-  if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(grid_for(npad - n, BLK)), dim3(BLK), 0, st, n, npad, d_S, d_col_off);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+// long keys: the partial sums of their chunks (k_schur_combine adds them up in a fixed order)
+static void launch_schur_partials(const SchurTasks *T, const double *d_J, const double *d_Y, hipStream_t st) {
+  if (T->nsplit > 0)
+    hipLaunchKernelGGL(k_schur_chunks, dim3(wave_grid(T->nchunks)), dim3(BLK), 0, st, T->nchunks, T->chunk_t0, T->chunk_t1, T->task_a,
+                       T->task_b, d_J, d_Y, T->partial);
 }
 
-// Chunked assembly (per-rank ownership of S on several ranks): launch_schur_pre once per step -- the per-observation Y
-// blocks and the partial sums of the split keys -- then launch_schur_chunk per chunk of tile columns into `dest` (this
-// rank's own tiles, or the staging buffer whose content is reduced onto the chunk's owner), through the chunk's offset table.
-int launch_schur_pre(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y, hipStream_t st) {
-  ProfScope ps(p, PC_SCHUR_S, st);
+// The assembly of S: launch_schur_pre once per step -- the per-observation Y blocks -- then launch_schur_chunk per chunk of
+// tile columns into `dest`, through the chunk's offset table.  One rank: one chunk, the whole matrix into S itself (no key
+// lists: every key).  Per-rank ownership of S on several ranks: this rank's own tiles, or the staging buffer whose content is
+// reduced onto the chunk's owner.  (The callers clear `dest` -- the chunk's ntiles tiles -- and time the launches: PC_SCHUR_S.)
+// `partials`: which of the two forms the partial sums of the split keys, once per step: launch_schur_pre where several chunks
+// follow; the one chunk of one rank forms them itself, between its short keys and the sums -- the order that assembly was
+// measured and tuned in
+
+int launch_schur_pre(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y, hipStream_t st,
+                     bool partials) {
   if (p->nobs > 0)
     hipLaunchKernelGGL(k_obs_y, dim3(grid_for(p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->pnt0, d_J, d_Uinv, d_Y);
-  if (T->nsplit > 0) {
-    int64_t nbc = (T->nchunks + BLK / 64 - 1) / (BLK / 64);
-    if (nbc > (int64_t)1 << 22) nbc = (int64_t)1 << 22;
-    hipLaunchKernelGGL(k_schur_chunks, dim3((unsigned)nbc), dim3(BLK), 0, st, T->nchunks, T->chunk_t0, T->chunk_t1, T->task_a,
-                       T->task_b, d_J, d_Y, T->partial);
-  }
+  if (partials) launch_schur_partials(T, d_J, d_Y, st);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
 int launch_schur_chunk(ba_problem *p, const SchurTasks *T, const SchurChunk *c, const double *d_J, const double *d_Y,
                        const double *d_Hcc, double lambda, double *dest, int64_t n, int64_t npad, hipStream_t st,
-                       const double *d_lambda, const double *d_damp) {
-  ProfScope ps(p, PC_SCHUR_S, st);
-  BA_HIP_CHECK(hipMemsetAsync(dest, 0, (size_t)c->ntiles * NB * NB * sizeof(double), st));
+                       const double *d_lambda, const double *d_damp, bool partials) {
   const double *damp_c = d_damp ? d_damp + 3 * p->npnts : (const double *)nullptr;
-  if (c->nkeys > 0) {
-    int64_t nb = (c->nkeys + BLK / 64 - 1) / (BLK / 64);
-    if (nb > (int64_t)1 << 22) nb = (int64_t)1 << 22;
-    hipLaunchKernelGGL(k_schur_blocks, dim3((unsigned)nb), dim3(BLK), 0, st, c->nkeys, T->key_ptr, T->key_ca, T->key_cb, T->task_a,
+  if (c->nkeys > 0)
+    hipLaunchKernelGGL(k_schur_blocks, dim3(wave_grid(c->nkeys)), dim3(BLK), 0, st, c->nkeys, T->key_ptr, T->key_ca, T->key_cb, T->task_a,
                        T->task_b, d_J, d_Y, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, T->nsplit > 0 ? 2 * T->chunk : 0, c->keys, T->cam_of);
-  }
-  if (c->nskeys > 0) {
-    int64_t nbs = (c->nskeys + BLK / 64 - 1) / (BLK / 64);
-    if (nbs > (int64_t)1 << 22) nbs = (int64_t)1 << 22;
-    hipLaunchKernelGGL(k_schur_combine, dim3((unsigned)nbs), dim3(BLK), 0, st, c->nskeys, T->skey, T->skey_c0, T->key_ca, T->key_cb,
+  if (partials) launch_schur_partials(T, d_J, d_Y, st);
+  if (c->nskeys > 0)
+    hipLaunchKernelGGL(k_schur_combine, dim3(wave_grid(c->nskeys)), dim3(BLK), 0, st, c->nskeys, T->skey, T->skey_c0, T->key_ca, T->key_cb,
                        T->partial, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, c->skeys, T->cam_of);
-  }
   if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(grid_for(npad - n, BLK)), dim3(BLK), 0, st, n, npad, dest, c->cco);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
-// S_ij /= d_i d_j on the tile columns a rank owns (own_cols / own_pref as k_ldl_update's OWN mode; block = one tile)
-__global__ __launch_bounds__(BLK) void k_scale_S_own(int64_t n, const double *__restrict__ dsc, double *__restrict__ S,
-                                                      const int64_t *__restrict__ co, const int *__restrict__ own_cols,
-                                                      const int64_t *__restrict__ own_pref, int ncols) {
-  const int64_t t = blockIdx.x;
-  int lo = 0, hi = ncols;  // largest m with own_pref[m] <= t
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (own_pref[mid] <= t) lo = mid;
-    else hi = mid;
-  }
-  const int64_t tj = own_cols[lo], ti = tj + (t - own_pref[lo]);
-  double *T = S + tix(co, ti, tj) * NB * NB;
-  for (int e = threadIdx.x; e < NB * NB; e += BLK) {
-    const int64_t r = ti * NB + (e >> 7), c = tj * NB + (e & (NB - 1));
-    const double dr = r < n ? dsc[r] : 1.0, dc = c < n ? dsc[c] : 1.0;
-    T[e] /= dr * dc;
-  }
-}
-int launch_scale_S_own(ba_problem *p, int64_t n, const double *d_dsc, double *d_S, const int64_t *d_col_off, const int *d_own_cols,
-                       const int64_t *d_own_pref, int ncols, int64_t ntiles, hipStream_t st) {
-  if (ntiles <= 0 || ncols <= 0) return BA_OK;
-  hipLaunchKernelGGL(k_scale_S_own, dim3((unsigned)ntiles), dim3(BLK), 0, st, n, d_dsc, d_S, d_col_off, d_own_cols, d_own_pref, ncols);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
-}
-
-// the same over a list of stored tiles (block-sparse S with per-rank ownership): tile t of S is (tiles[t].x, tiles[t].y)
+// S_ij /= d_i d_j (padding rows / columns have d = 1), one workgroup per stored tile, over the workspace's list of them
+// (DenseLDLT::own_tiles, every storage layout): tile t of S is (tiles[t].x, tiles[t].y)
 __global__ __launch_bounds__(BLK) void k_scale_S_list(int64_t n, const double *__restrict__ dsc, double *__restrict__ S,
                                                        const int2 *__restrict__ tiles) {
   const int64_t t = blockIdx.x, ti = tiles[t].x, tj = tiles[t].y;
@@ -1419,13 +1341,6 @@ int launch_gather_cams(ba_problem *p, const int *d_pos, const double *d_src, dou
   return BA_OK;
 }
 
-int launch_scale_S(ba_problem *p, int64_t n, int64_t nt, const double *d_dsc, double *d_S, const int64_t *d_col_off,
-                   hipStream_t st) {
-  hipLaunchKernelGGL(k_scale_S, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(BLK), 0, st, n, nt, d_dsc, d_S, d_col_off);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
-}
-
 int launch_schur_rhs(ba_problem *p, const double *d_J, const double *d_r, const double *d_u, double *d_rhs,
                      hipStream_t st, const int *d_cam_pnt, const int *d_pos) {
   if (p->ncams == 0) return BA_OK;
@@ -1467,24 +1382,9 @@ int launch_backsub(ba_problem *p, const double *d_J, const double *d_Uinv, const
 int launch_model_sq(ba_problem *p, const double *d_J, const double *d_r, const double *d_delta, double *d_partial,
                     double *d_scal, int slot, hipStream_t st, double cr) {
   ProfScope ps(p, PC_TRIAL, st);
-  int nb = (int)((p->nobs + BLK - 1) / BLK);
-  if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-  if (nb < 1) nb = 1;
+  const int nb = red_blocks(p->nobs);
   hipLaunchKernelGGL(k_model_sq, dim3(nb), dim3(BLK), 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_J, d_r, d_delta,
                      cr, d_partial);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLK), 0, st, nb, d_partial, d_scal, slot);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
-}
-
-// |v|^2 -> scal[slot]
-int launch_sumsq(ba_problem *p, int64_t n, const double *d_v, double *d_partial, double *d_scal, int slot,
-                 hipStream_t st) {
-  ProfScope ps(p, PC_REDUCE, st);
-  int nb = (int)((n + BLK - 1) / BLK);
-  if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(k_sumsq, dim3(nb), dim3(BLK), 0, st, n, d_v, d_partial);
   hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLK), 0, st, nb, d_partial, d_scal, slot);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
@@ -1497,12 +1397,7 @@ int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi, 
     return BA_ERR_ARG;
   }
   ProfScope ps(p, PC_REDUCE, st);
-  for (int v = 0; v < jobs->count; v++) {
-    int nb = (int)((jobs->n[v] + BLK - 1) / BLK);
-    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-    if (nb < 1) nb = 1;
-    jobs->nb[v] = nb;
-  }
+  for (int v = 0; v < jobs->count; v++) jobs->nb[v] = red_blocks(jobs->n[v]);
   hipLaunchKernelGGL(k_sumsq_multi, dim3(jobs->count * RED_BLOCKS), dim3(BLK), 0, st, *jobs, d_partial_multi);
   hipLaunchKernelGGL(k_sum_partials_multi, dim3(1), dim3(BLK), 0, st, *jobs, (const double *)d_partial_multi);
   BA_HIP_CHECK(hipGetLastError());

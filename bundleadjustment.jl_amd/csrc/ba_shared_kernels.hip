@@ -130,20 +130,13 @@ __global__ __launch_bounds__(SB_T) void k_border_mask_vec(int64_t npad, int mz, 
   for (int l = 0; l < mz; l++) SB[(int64_t)l * npad + i] = 0.0;
 }
 
-// A: the member rows and columns of S replaced by identity rows and columns.  One workgroup per lower tile, enumerated row by
-// row as k_scale_S does (every storage layout of one rank: a tile outside a block-sparse pattern is skipped); only the
-// masked elements are stored
+// A: the member rows and columns of S replaced by identity rows and columns.  One workgroup per stored tile, over the
+// workspace's list of them as k_scale_S_list (tile t of S is (tiles[t].x, tiles[t].y)); only the masked elements are stored
 __global__ __launch_bounds__(SB_T) void k_border_mask_S(int64_t npad, const int *__restrict__ col, double *__restrict__ S,
-                                                         const int64_t *__restrict__ co) {
+                                                         const int2 *__restrict__ tiles) {
   __shared__ int any_r, any_c;
   __shared__ signed char mr[NB], mc[NB];
-  const int64_t t = blockIdx.x;
-  int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ti++;
-  while (ti * (ti + 1) / 2 > t) ti--;
-  const int64_t tj = t - ti * (ti + 1) / 2;
-  const int64_t tt = tix(co, ti, tj);
-  if (tt < 0) return;
+  const int64_t t = blockIdx.x, ti = tiles[t].x, tj = tiles[t].y;
   const int tid = threadIdx.x;
   if (tid == 0) any_r = any_c = 0;
   __syncthreads();
@@ -156,7 +149,7 @@ __global__ __launch_bounds__(SB_T) void k_border_mask_S(int64_t npad, const int 
   }
   __syncthreads();
   if (!any_r && !any_c) return;
-  double *T = S + tt * NB * NB;
+  double *T = S + t * NB * NB;
   for (int e = tid; e < NB * NB; e += SB_T) {
     const int r = e >> 7, c = e & (NB - 1);
     if (mr[r] || mc[c]) T[e] = (ti == tj && r == c) ? 1.0 : 0.0;
@@ -269,7 +262,7 @@ int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double la
   hipLaunchKernelGGL(k_border_product, dim3(row_blocks(npad), mz), dim3(SB_T), 0, st, n, npad, l->S, l->col_off, p->grp_ptr, d_row, d_B);
   hipLaunchKernelGGL(k_border_reduce, dim3(mz, mz + 1), dim3(SB_T), 0, st, npad, mz, lambda, p->grp_ptr, d_row, d_B, d_rhs, d_small);
   hipLaunchKernelGGL(k_border_mask_vec, dim3(row_blocks(npad)), dim3(SB_T), 0, st, npad, mz, d_col, d_B, d_rhs);
-  hipLaunchKernelGGL(k_border_mask_S, dim3((unsigned)(l->nt * (l->nt + 1) / 2)), dim3(SB_T), 0, st, npad, d_col, l->S, l->col_off);
+  hipLaunchKernelGGL(k_border_mask_S, dim3((unsigned)l->n_own_tiles), dim3(SB_T), 0, st, npad, d_col, l->S, l->own_tiles);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }

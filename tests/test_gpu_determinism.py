@@ -489,20 +489,32 @@ def test_loopback_camera_ordering_on_several_ranks(ba, loopback, scene):
         R.close()
 
 
-def test_loopback_lm_runs_equal_one_rank(ba, loopback):
+@pytest.mark.parametrize("storage", ["dense", "block-sparse"])
+def test_loopback_lm_runs_equal_one_rank(ba, loopback, storage):
     """Complete LM runs on 3 ranks of one process over the loopback transport (per-rank ownership of S, distributed
     factorisation and backward sweep, chunked assembly): lm.jl with and without column scaling -- the scaling uses the
     all-reduced diagonal of J'J and touches only the tiles a rank owns -- give the one-rank run's iterations, status and
-    objective."""
-    prob = ba.synthetic.make_problem(70, 500, 2400, seed=8)  # n = 630: 5 tile rows, pairs owned 0, 1, 2
-    ref = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(prob))
-    want = {}
-    for norm in ("None", "J", "A"):
-        want[norm] = ba.Levenberg_Marquardt(ba.FeasibilityResidual(ref), "LDL", "AMD", norm, False)
-    ref.close()
-    _set_lookahead(True)
-    R = Ranks(ba, loopback, prob, 3)
+    objective.  storage = block-sparse: the same on a banded problem with compressed block-sparse storage on every handle
+    (BA_SPARSE_S=1, the cameras in their own numbering), where a rank scales the pattern's tiles of its tile columns: 57
+    cameras (n = 513: 5 tile rows, the fewest with a tile column pair for every rank), a point's cameras within 14 consecutive
+    ones, so that only neighbouring tile rows share points (9 of the 15 lower tiles receive a block)."""
+    sparse = storage == "block-sparse"
+    if sparse:
+        prob = ba.synthetic.make_problem(57, 500, 2400, seed=8, locality=0.25)
+        os.environ["BA_SPARSE_S"] = "1"
+        os.environ["BA_CAM_ORDER"] = "natural"
+    else:
+        prob = ba.synthetic.make_problem(70, 500, 2400, seed=8)  # n = 630: 5 tile rows, pairs owned 0, 1, 2
+    R = None
     try:
+        ref = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(prob))
+        want = {}
+        for norm in ("None", "J", "A"):
+            want[norm] = ba.Levenberg_Marquardt(ba.FeasibilityResidual(ref), "LDL", "AMD", norm, False)
+        pat_ref = ba.schur_pattern(ref)
+        ref.close()
+        _set_lookahead(True)
+        R = Ranks(ba, loopback, prob, 3)
         for norm in ("None", "J", "A"):
             out, err = [None] * 3, [None] * 3
 
@@ -527,5 +539,12 @@ def test_loopback_lm_runs_equal_one_rank(ba, loopback):
             for r in (1, 2):
                 rep = bits_report(cam[0], cam[r], f"normalize {norm}: cameras of rank 0 vs rank {r}")
                 assert not rep, rep
+        if sparse:
+            for who, pat in [("one rank", pat_ref)] + [(f"rank {r}", ba.schur_pattern(m)) for r, m in enumerate(R.models)]:
+                assert pat[2] and pat[0] < 1, f"{who}: (tile fill, flop fill, list schedule) = {pat}"
     finally:
-        R.close()
+        if R is not None:
+            R.close()
+        if sparse:
+            os.environ.pop("BA_SPARSE_S", None)
+            os.environ.pop("BA_CAM_ORDER", None)
