@@ -1,44 +1,20 @@
-"""What the tests of the LM terms (robust loss, fixed parameters, covariance, priors, shared intrinsics) share: the numpy
-reference of the oracle's residual and Jacobian with the reweighting of a robust loss, the dense covariance references, the
-handle's options as vectors, the solve and option builders, and the in-process loopback communicator."""
-import contextlib
-import ctypes as C
-import os
-import threading
-
+"""The numpy reference of the LM term tests, and nothing else (the run plumbing is tests/_lm_run.py): the oracle's residual and
+Jacobian, whitened by the observations' information and reweighted under a robust loss; the rows of the Gaussian priors; the
+expansion E of calibration groups (x = E z); the normal equations formed once; ONE step that takes every term as an argument --
+absent terms are skipped, so an argument's neutral element gives the bits of the argument left out; ONE dense LM loop with the
+controllers of src/lm.jl and src/LevenbergMarquardt.jl; the covariance references; the tolerances and their rule.
+x = [points; cameras], camera block (r, t, k1, k2, f), indices 1-based, residual and rows of J interleaved (x, y per observation)."""
 import numpy as np
-import pytest
 import scipy.sparse as sp
 
 from _util import parity_record
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LOOPBACK = os.path.join(ROOT, "tests", "helpers", "libba_loopback.so")
 EPS = np.finfo(np.float64).eps
 C_BOUND = 100.0
 STEP_TOL = {1e3: 1e-12, 30.0: 1e-11, 1.0: 1e-11, 1e-2: 1e-9}  # test_lm_step_vs_oracle's limits at these lambda
 F32_TOL = 5e-3  # the Float32-factor limit of tests/test_fixed_params.py and tests/test_robust_loss.py
 PCG_TOL = 1e-8  # their limit of the pcg=(1e-12, 5000) step
-
-
-def arrays(p):
-    return (p["cam_idx1"], p["pnt_idx1"], p["pt2d"], p["x0"], p["ncams"], p["npnts"], p["nobs"])
-
-
-def env(name, value, fn):
-    """fn() with the environment variable set to value (None: unset), the variable restored afterwards"""
-    old = os.environ.get(name)
-    if value is None:
-        os.environ.pop(name, None)
-    else:
-        os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if old is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = old
+KINDS = ("point", "camera", "centre")
 
 
 def sym(M):
@@ -51,7 +27,7 @@ def limit(tol, kappa):
     return max(tol, C_BOUND * kappa * EPS)
 
 
-# ---- numpy reference: residual, Jacobian, reweighting ---------------------------------------------------------------------
+# ---- the two definitions: scipy's loss table, the header's factor of an information matrix ------------------------------------
 def rho(loss, z):
     """(rho(z), rho'(z)) of scipy's losses"""
     if loss == "linear":
@@ -69,14 +45,17 @@ def rho(loss, z):
     raise ValueError(loss)
 
 
-def weights_cost(r, loss, c):
-    s = r[0::2] ** 2 + r[1::2] ** 2
-    if loss == "linear":
-        return np.ones_like(s), 0.5 * np.sum(s)
-    rh, w = rho(loss, s / c ** 2)
-    return w, 0.5 * np.sum(c ** 2 * rh)
+def factor(info):
+    """(l00, l10, l11) of Lambda = L L', L lower triangular, from (n, 2, 2) blocks, as include/ba_hip.h defines it:
+    l00 = sqrt(xx), l10 = xy / l00 (0 when xx = 0), l11 = sqrt(max(yy - l10^2, 0))"""
+    xx, xy, yy = info[:, 0, 0], info[:, 0, 1], info[:, 1, 1]
+    l00 = np.sqrt(xx)
+    l10 = np.divide(xy, l00, out=np.zeros_like(xy), where=xx > 0)
+    l11 = np.sqrt(np.maximum(yy - l10 * l10, 0.0))
+    return l00, l10, l11
 
 
+# ---- residual, Jacobian, whitening, reweighting ---------------------------------------------------------------------------------
 def residual(orc, p, x):
     return orc.residuals(p["cam_idx1"], p["pnt_idx1"], x, p["pt2d"], p["npnts"])
 
@@ -88,52 +67,371 @@ def jac(orc, p, x):
     return sp.csr_matrix((vals, (rows - 1, cols - 1)), shape=(2 * p["nobs"], nvar))
 
 
-def reweighted(orc, p, x, loss, c):
-    """(r~, J~, w, f) under a loss: r~ = sqrt(w) r, J~ = sqrt(w) J, w = rho'(|r_i|^2 / c^2) per observation"""
-    r = residual(orc, p, x)
+def whiten_residual(r, info):
+    """r^ = L' r: (l00 r_x + l10 r_y, l11 r_y)"""
+    l00, l10, l11 = factor(info)
+    out = np.empty_like(r)
+    out[0::2] = l00 * r[0::2] + l10 * r[1::2]
+    out[1::2] = l11 * r[1::2]
+    return out
+
+
+def whitener(info):
+    """the sparse block-diagonal W with W r = r^ (and W J = J^)"""
+    l00, l10, l11 = factor(info)
+    n = len(l00)
+    even, odd = 2 * np.arange(n), 2 * np.arange(n) + 1
+    return sp.csr_matrix((np.concatenate([l00, l10, l11]), (np.concatenate([even, even, odd]), np.concatenate([even, odd, odd]))),
+                         shape=(2 * n, 2 * n))
+
+
+def weights_cost(r, loss="linear", c=1.0, info=None):
+    """(w, f) of a residual r (not whitened): w_i = rho'(r_i' Lambda_i r_i / c^2), f = 1/2 sum c^2 rho(.); Lambda = I without
+    info"""
+    if info is not None:
+        r = whiten_residual(r, info)
+    s = r[0::2] ** 2 + r[1::2] ** 2
+    if loss == "linear":
+        return np.ones_like(s), 0.5 * np.sum(s)
+    val, w = rho(loss, s / c ** 2)
+    return w, 0.5 * np.sum(c ** 2 * val)
+
+
+def linearise(orc, p, x, info=None, loss="linear", c=1.0):
+    """(r~, J~, w, f): the oracle's r and J at x, whitened where info is given (r^ = L' r, J^ = L' J), then reweighted under the
+    loss: r~ = sqrt(w) r^, J~ = sqrt(w) J^, w = rho'(|r^_i|^2 / c^2) per observation.  An absent term is no operation."""
+    r, J = residual(orc, p, x), jac(orc, p, x)
+    if info is not None:
+        W = whitener(info)
+        r, J = W @ r, W @ J
     w, f = weights_cost(r, loss, c)
-    sw = np.repeat(np.sqrt(w), 2)
-    return sw * r, sp.diags(sw) @ jac(orc, p, x), w, f
+    if loss != "linear":
+        sw = np.repeat(np.sqrt(w), 2)
+        r, J = sw * r, sp.diags(sw) @ J
+    J.sort_indices()  # (scipy's product leaves a row's entries in another order than jac(): J~ delta sums in the order of the row)
+    return r, J, w, f
 
 
-# ---- the handle's options as vectors and keywords -------------------------------------------------------------------------
-def fixed_vector(ba, p, kw):
-    """boolean over x = [points; cameras]: True where the options of kw fix the entry"""
-    cam, pnt = ba._lib.fixed_masks(p["ncams"], p["npnts"], kw.get("fixed_cameras"), kw.get("fixed_points"),
-                                   kw.get("fixed_camera_params"))
-    fixed_p = np.repeat(pnt.astype(bool), 3)
-    fixed_c = ((cam[:, None] >> np.arange(9)) & 1).astype(bool).ravel()
-    return np.concatenate([fixed_p, fixed_c])
+# ---- Gaussian priors (ba_lm_set_priors): the camera centre, the prior rows and their terms -------------------------------------
+def rotation(r):
+    """Rodrigues rotation of the rotation vector r, evaluated as the model does (theta = |r|, axis r / theta, no small-angle
+    branch); works for complex r (complex-step differentiation)"""
+    th = np.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2])
+    k = r / th
+    K = np.array([[0 * th, -k[2], k[1]], [k[2], 0 * th, -k[0]], [-k[1], k[0], 0 * th]])
+    return np.cos(th) * np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * np.outer(k, k)
 
 
-def gauge_kw(p):
-    """camera 1's pose (r, t) and the first translation component of camera 2: the 7 DoF of a similarity transform"""
-    comp = np.zeros((p["ncams"], 9), dtype=bool)
-    comp[0, :6] = True
-    comp[1, 3] = True
-    return dict(fixed_camera_params=comp)
+def centre(cam):
+    """camera centre c = -R(r)' t of a camera block: the point with P1(r, t, c) = R c + t = 0"""
+    return -rotation(cam[:3]).T @ cam[3:6]
 
 
-def solve(ba, m, variant=1, facto="LDL", normalize="None", **kw):
-    args = (facto, "AMD", normalize) + ((False,) if variant == 1 else ())
-    return ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), *args, **kw)
+def centre_jac(cam):
+    """dc/d(r, t), 3 x 6, by complex-step differentiation of centre() (exact to rounding: no difference is formed)"""
+    H = np.empty((3, 6))
+    for j in range(6):
+        z = np.array(cam[:6], dtype=complex)
+        z[j] += 1e-30j
+        H[:, j] = centre(z).imag / 1e-30
+    return H
 
 
-def lm_opts(ba, **kw):
-    """ba_lm_opts with every field at its default (lm.jl's variant, :LDL, :AMD), then the fields of kw"""
-    o = ba._lib.LMOpts(variant=1, facto=0, normalize=0, linesearch=0, facto_type=0, ite_max=-1, verbose=0, x_f32=0, restol=-1,
-                       satol=-1, srtol=-1, oatol=-1, ortol=-1, atol=-1, rtol=-1, nu_d=-1, nu_m=-1, lam=-1, delta_d=-1, max_time=-1,
-                       pcg_tol=-1, pcg_max_iter=-1, perm=0)
-    for k, v in kw.items():
-        setattr(o, k, v)
-    return o
+def centre_jac_fd(cam, h=1e-6):
+    """the same by central differences (the cross-check of centre_jac)"""
+    H = np.empty((3, 6))
+    for j in range(6):
+        a, b = np.array(cam[:6], dtype=float), np.array(cam[:6], dtype=float)
+        a[j] += h
+        b[j] -= h
+        H[:, j] = (centre(a) - centre(b)) / (2 * h)
+    return H
 
 
-# ---- covariance references (tests/test_covariance.py, the covariance test of tests/test_priors.py) ---------------------------
-def hessian(orc, p, x, lam, fixed, loss=None, c=1.0):
+def _lists(v):
+    if v is None:
+        return np.zeros(0, dtype=np.int64), np.zeros((0, 0)), np.zeros((0, 0, 0))
+    idx, mu, info = v
+    idx, mu, info = np.asarray(idx, dtype=np.int64), np.asarray(mu, dtype=float), np.asarray(info, dtype=float)
+    if info.ndim == 2:  # standard deviations
+        info = np.stack([np.diag(1.0 / s ** 2) for s in info])
+    return idx, mu, info
+
+
+def rows(x, ncams, npnts, point_priors=None, camera_priors=None, centre_priors=None):
+    """[(kind, cols, H, d, Lambda)] of every prior at x: cols the entries of x the prior acts on, H = dh/dx[cols],
+    d = h(x) - mu"""
+    out = []
+    np3 = 3 * npnts
+    for kind, v in zip(KINDS, (point_priors, camera_priors, centre_priors)):
+        idx, mu, info = _lists(v)
+        for q, i in enumerate(idx):
+            if kind == "point":
+                cols = np.arange(3 * (i - 1), 3 * i)
+                H, d = np.eye(3), x[cols] - mu[q]
+            elif kind == "camera":
+                cols = np.arange(np3 + 9 * (i - 1), np3 + 9 * i)
+                H, d = np.eye(9), x[cols] - mu[q]
+            else:
+                cols = np.arange(np3 + 9 * (i - 1), np3 + 9 * (i - 1) + 6)
+                cam = x[np3 + 9 * (i - 1):np3 + 9 * i]
+                H, d = centre_jac(cam), centre(cam) - mu[q]
+            out.append((kind, cols, H, d, info[q]))
+    return out
+
+
+def chi2(prior_rows):
+    """d' Lambda d per kind, in the order given"""
+    return {k: np.array([d @ L @ d for kind, _, _, d, L in prior_rows if kind == k]) for k in KINDS}
+
+
+def cost(prior_rows):
+    return 0.5 * sum(d @ L @ d for _, _, _, d, L in prior_rows)
+
+
+def normal_terms(prior_rows, nvar):
+    """(sum H' Lambda H dense nvar x nvar, sum H' Lambda d)"""
+    A, g = np.zeros((nvar, nvar)), np.zeros(nvar)
+    for _, cols, H, d, L in prior_rows:
+        A[np.ix_(cols, cols)] += H.T @ L @ H
+        g[cols] += H.T @ (L @ d)
+    return A, g
+
+
+def model(prior_rows, delta):
+    """1/2 sum (H delta + d)' Lambda (H delta + d)"""
+    return 0.5 * sum((H @ delta[cols] + d) @ L @ (H @ delta[cols] + d) for _, cols, H, d, L in prior_rows)
+
+
+# ---- shared intrinsics (ba_lm_set_shared_intrinsics, DESIGN §5g): x = E z -------------------------------------------------------
+def labels(groups, ncams):
+    """int labels (ncams,) of a list of lists of 1-based camera indices (or of an array of labels); groups of one camera -> 0"""
+    if len(groups) and np.ndim(groups[0]) == 0:
+        lab = np.array(groups, dtype=int)
+    else:
+        lab = np.zeros(ncams, dtype=int)
+        for g, mem in enumerate(groups, 1):
+            lab[np.asarray(mem) - 1] = g
+    for g in range(1, lab.max() + 1 if lab.size else 1):
+        if np.count_nonzero(lab == g) < 2:
+            lab[lab == g] = 0
+    return lab
+
+
+def expansion(groups, ncams, npnts):
+    """(E, keep): E (nvar x nz, scipy csr) copies a group's (k1, k2, f) -- held at its first member, the lowest camera index --
+    to every member; keep: the entries of x that are entries of z, ascending (z = x[keep])"""
+    lab = labels(groups, ncams)
+    nvar, np3 = 3 * npnts + 9 * ncams, 3 * npnts
+    owner = np.arange(nvar)
+    for g in np.unique(lab[lab > 0]):
+        mem = np.flatnonzero(lab == g)
+        for c in mem[1:]:
+            owner[np3 + 9 * c + 6:np3 + 9 * c + 9] = np3 + 9 * mem[0] + 6 + np.arange(3)
+    keep = np.flatnonzero(owner == np.arange(nvar))
+    col_of = -np.ones(nvar, dtype=int)
+    col_of[keep] = np.arange(keep.size)
+    E = sp.csr_matrix((np.ones(nvar), (np.arange(nvar), col_of[owner])), shape=(nvar, keep.size))
+    return E, keep
+
+
+def _tied(groups, ncams, npnts):
+    """expansion(), or (None, None) where nothing is tied (no groups, or groups of one camera only)"""
+    if groups is None or not labels(groups, ncams).any():
+        return None, None
+    return expansion(groups, ncams, npnts)
+
+
+def reduced(A, g, npnts):
+    """(S, rhs) of the point-eliminated system of A d = -g (points first)"""
+    np3 = 3 * npnts
+    U, W, V = A[:np3, :np3], A[:np3, np3:], A[np3:, np3:]
+    UiW, Uig = np.linalg.solve(U, W), np.linalg.solve(U, g[:np3])
+    return V - W.T @ UiW, -(g[np3:] - W.T @ Uig)
+
+
+def bordered(H, g, lam, groups, ncams, npnts):
+    """The camera part of the step by the bordered solve of DESIGN §5g, from the reduced camera system of the UNtied problem:
+    S_full = the point-eliminated H + lam I over all 9 ncams rows, M = the intrinsic rows of all members, E_g the 9 ncams x 3G
+    indicator of (group, component):  B = S_full E_g with its rows in M zeroed, C = E_g'(S_full - lam I)E_g + lam I, A = S_full
+    with rows and columns M replaced by the identity; A [Y | a0] = [B | rhs_a], T = C - B'Y, y = T^-1 (rhs_y - B'a0), a = a0 -
+    Y y, step = a + E_g y."""
+    lab = labels(groups, ncams)
+    n = 9 * ncams
+    A_full = H + lam * np.eye(H.shape[0])
+    S, rhs = reduced(A_full, g, npnts)
+    G = int(lab.max())
+    Eg = np.zeros((n, 3 * G))
+    for c in np.flatnonzero(lab > 0):
+        for q in range(3):
+            Eg[9 * c + 6 + q, 3 * (lab[c] - 1) + q] = 1.0
+    M = np.flatnonzero(Eg.sum(axis=1) > 0)
+    SB = S @ Eg
+    B = SB.copy()
+    B[M] = 0.0
+    C = Eg.T @ (S - lam * np.eye(n)) @ Eg + lam * np.eye(3 * G)
+    rhs_y = Eg.T @ rhs
+    A = S.copy()
+    A[M, :] = 0.0
+    A[:, M] = 0.0
+    A[M, M] = 1.0
+    rhs_a = rhs.copy()
+    rhs_a[M] = 0.0
+    sol = np.linalg.solve(A, np.column_stack([B, rhs_a]))
+    Y, a0 = sol[:, :-1], sol[:, -1]
+    T = C - B.T @ Y
+    y = np.linalg.solve(T, rhs_y - B.T @ a0)
+    return a0 - Y @ y + Eg @ y
+
+
+# ---- the normal equations and the step ------------------------------------------------------------------------------------------
+def normal_equations(orc, p, x, *, info=None, loss="linear", c=1.0, priors=None, dense=True):
+    """(H, g, J~, r~, prior rows) over x: H = J~'J~ + sum H_k' Lambda_k H_k without damping (a dense array, or scipy csr where
+    dense is False: the prior terms are dense, so that form takes no priors), g = J~'r~ + sum H_k' Lambda_k d_k"""
+    rt, Jt, _, _ = linearise(orc, p, x, info, loss, c)
+    prior_rows = rows(x, p["ncams"], p["npnts"], **priors) if priors else []
+    H, g = Jt.T @ Jt, Jt.T @ rt
+    if dense:
+        H = H.toarray()
+    if prior_rows:
+        assert dense, "prior rows are formed densely"
+        Hp, gp = normal_terms(prior_rows, len(x))
+        H, g = H + Hp, g + gp
+    return H, g, Jt, rt, prior_rows
+
+
+def step(orc, p, x, lam, *, info=None, loss="linear", c=1.0, fixed=None, priors=None, groups=None, solve="dense", zeroed=False):
+    """One LM step with every term as an argument: (E_F'(H + ...)E_F + lam I) dz_F = -E_F'g over the free entries of z (x = E z;
+    z = x without groups), zeros scattered to the fixed ones.  fixed: boolean over x (the members of a group agree).  zeroed:
+    the other form of the same step -- the fixed rows and columns zeroed, lam on their diagonal, the full system solved -- for
+    the one test whose reference would move by more than a tenth of its limit between the forms.
+    solve = "dense": the dense solve of that system; "schur": the point blocks eliminated through schur(), H kept sparse (the
+    scenes too large for a dense H; it takes info and loss only).  The two differ by about kappa eps.
+    -> dict: delta (x layout), model = 1/2 |J~ delta + r~|^2 + the priors' model term, grad = E'g in the x layout (a group's sum
+    at its first member, zeros at the others and at fixed entries), kappa of the Jacobi-scaled damped reduced camera system the
+    solve runs on; with groups also H, g (over x, no mask), E, keep and dz."""
+    npnts, ncams = p["npnts"], p["ncams"]
+    H, g, Jt, rt, prior_rows = normal_equations(orc, p, x, info=info, loss=loss, c=c, priors=priors, dense=solve == "dense")
+    E, keep = _tied(groups, ncams, npnts)
+    A, b, fz = H, g, fixed
+    assert solve == "dense" or (fixed is None and E is None)
+    if E is not None:
+        A = E.T @ (E.T @ H).T
+        A, b, fz = 0.5 * (A + A.T), E.T @ g, None if fixed is None else fixed[keep]
+    np3, free, bs = 3 * npnts, None, b
+    if fz is not None and zeroed:
+        A, bs = A * np.outer(~fz, ~fz), np.where(fz, 0.0, b)
+    elif fz is not None:  # the solve runs over the free columns only (points are fixed as a whole: the point blocks stay 3 x 3)
+        free = np.flatnonzero(~fz)
+        A, bs, np3 = A[np.ix_(free, free)], b[free], int(np.count_nonzero(~fz[:np3]))
+    if solve == "dense":
+        A = A.copy()
+        A[np.diag_indices_from(A)] += lam
+        ds = np.linalg.solve(A, -bs)
+        kappa = kappa_jacobi(reduced(A, bs, np3 // 3)[0])
+    else:
+        S, G, Ubi = schur((A + sp.diags(np.full(len(bs), float(lam)))).tocsr(), p)
+        u = np.einsum("pij,pj->pi", Ubi, bs[:np3].reshape(-1, 3)).ravel()
+        dc = np.linalg.solve(S, -(bs[np3:] - G.T @ bs[:np3]))
+        ds, kappa = np.concatenate([-u - G @ dc, dc]), kappa_jacobi(S)
+    dz, gz = ds, bs
+    if free is not None:
+        dz, gz = np.zeros(len(b)), np.zeros(len(b))
+        dz[free], gz[free] = ds, bs
+    delta, grad = dz, gz
+    if E is not None:
+        delta, grad = E @ dz, np.zeros(len(g))
+        grad[keep] = gz
+    m = Jt @ delta + rt
+    out = dict(delta=delta, model=0.5 * float(m @ m) + model(prior_rows, delta), grad=grad, kappa=kappa)
+    if E is not None:
+        out.update(H=H, g=g, E=E, keep=keep, dz=dz)
+    return out
+
+
+_steps = {}
+
+
+def step_once(key, *args, **kw):
+    """step(*args, **kw) computed once per key (a scene's name, lambda, ...), its arrays read-only: the tests of one file share
+    the steps of a scene"""
+    if key not in _steps:
+        _steps[key] = step(*args, **kw)
+        for v in _steps[key].values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+    return _steps[key]
+
+
+# ---- ONE dense LM loop -------------------------------------------------------------------------------------------------------
+def lm_dense(fun, x0, *, groups=None, ncams=None, npnts=None, variant=1, lam=None, ite_max=None, atol=None, rtol=None, satol=None,
+             srtol=None):
+    """Dense LM over z (x = E z; z = x without groups).  variant 1: the controller of src/lm.jl without line search; variant 0:
+    that of src/LevenbergMarquardt.jl; oatol = ortol = 0, and restol is never met on the scenes of the tests (noisy
+    observations).  fun(x) -> (f, gradient, Gauss-Newton matrix, model(delta) -> value), all over x; the loop reduces them with
+    E and damps with lam I over z.  |delta| and |x| of the small-step test are norms of E dz and E z, the first-order test reads
+    |E'g|.  -> (x, status, iterations, f, |E'g|)"""
+    V = variant
+    E, keep = _tied(groups, ncams, npnts)
+    if atol is None:
+        atol = np.sqrt(EPS) if V else 100 * np.sqrt(EPS)
+    if rtol is None:
+        rtol = EPS ** (1 / 3) if V else 1000 * np.sqrt(EPS)
+    satol = np.sqrt(EPS) if satol is None else satol
+    srtol = np.sqrt(EPS) if srtol is None else srtol
+    ite_max = (200 if V else 100) if ite_max is None else ite_max
+
+    def expand(z):
+        return z if E is None else E @ z
+
+    def at(z):
+        f, g, A, mod = fun(expand(z))
+        if E is None:
+            return f, g, A, mod
+        Az = E.T @ (E.T @ A).T
+        return f, E.T @ g, 0.5 * (Az + Az.T), mod
+
+    z = np.array(x0, dtype=float)
+    if E is not None:
+        z = z[keep]
+    f, g, A, mod = at(z)
+    if lam is None:
+        lam = 30.0 if V else 0.1
+    if V:
+        lam = max(lam, 1e10 / np.linalg.norm(g))
+    eps_first = atol + rtol * np.linalg.norm(g)
+    it, status = 0, "max_iter"
+    if np.linalg.norm(g) < eps_first:
+        return expand(z), "first_order", 0, f, float(np.linalg.norm(g))
+    while it <= ite_max:
+        it += 1
+        dz = np.linalg.solve(A + lam * np.eye(len(z)), -g)
+        d = expand(dz)
+        f_new = fun(expand(z + dz))[0]
+        pred, ared = f - mod(d), f - f_new
+        if (ared >= 1e-4 * pred) if V else (ared > 1e-4 * pred):  # lm.jl:259 / LevenbergMarquardt.jl:243
+            lam = lam / 3.0
+            if V:
+                if ared >= 0.9 * pred:
+                    lam = lam / 3.0
+                lam = max(1e-8, lam)
+            z = z + dz
+            f, g, A, mod = at(z)
+            if np.linalg.norm(d) < satol + srtol * np.linalg.norm(expand(z)):
+                status = "small_step"
+                break
+            if np.linalg.norm(g) < eps_first:
+                status = "first_order"
+                break
+        else:
+            lam = (max(lam, 1.0 / np.linalg.norm(d)) * 3.0) if V else lam * 3.0
+    return expand(z), status, it, f, float(np.linalg.norm(g))
+
+
+# ---- covariance references -----------------------------------------------------------------------------------------------------
+def hessian(orc, p, x, lam, fixed, loss=None, c=1.0, info=None):
     """J~_F'J~_F + diag(lam on the free entries, 1 on the fixed ones) (sparse; the fixed rows / columns hold only the 1)"""
-    J = reweighted(orc, p, x, loss, c)[1] if loss else jac(orc, p, x)
-    J = J @ sp.diags((~fixed).astype(float))
+    J = linearise(orc, p, x, info, loss or "linear", c)[1] @ sp.diags((~fixed).astype(float))
     return (J.T @ J + sp.diags(np.where(fixed, 1.0, lam))).tocsr()
 
 
@@ -149,7 +447,7 @@ def ref_dense(H, p, fixed):
 
 
 def schur(H, p):
-    """(S dense, U^-1 W sparse) of H = [[U W], [W' V]] (points first)"""
+    """(S dense, U^-1 W sparse, the blocks of U^-1) of H = [[U W], [W' V]] (points first)"""
     np3 = 3 * p["npnts"]
     U = H[:np3, :np3].tocoo()
     Ub = np.zeros((p["npnts"], 3, 3))
@@ -159,6 +457,26 @@ def schur(H, p):
     G = (sp.block_diag(list(Ubi), format="csr") @ W).tocsr()
     S = H[np3:, np3:].toarray() - (W.T @ G).toarray()
     return S, G, Ubi
+
+
+def ref_schur(H, p, fixed):
+    """camera and point blocks from the explicit Schur complement: Z = S^-1, Sigma_pp = U^-1 + (U^-1 W) Z (U^-1 W)'"""
+    S, G, Ubi = schur(H, p)
+    Z = np.linalg.inv(S)
+    cams = np.stack([Z[9 * c:9 * c + 9, 9 * c:9 * c + 9] for c in range(p["ncams"])])
+    npnts = p["npnts"]
+    pts = np.empty((npnts, 3, 3))
+    for a in range(0, npnts, 500):
+        b = min(npnts, a + 500)
+        Gc = G[3 * a:3 * b]
+        P = np.asarray(Gc @ Z).reshape(b - a, 3, -1)
+        Q = Gc.toarray().reshape(b - a, 3, -1)
+        pts[a:b] = Ubi[a:b] + np.einsum("irk,imk->irm", P, Q)
+    fp = fixed[:3 * npnts].reshape(npnts, 3)
+    fc = fixed[3 * npnts:].reshape(p["ncams"], 9)
+    cams[fc[:, :, None] | fc[:, None, :]] = 0.0
+    pts[fp[:, :, None] | fp[:, None, :]] = 0.0
+    return cams, pts, S, Z
 
 
 def _lmax(A, its=200):
@@ -203,98 +521,3 @@ def check_cov(test, cams, pts, ref_c, ref_p, kappa, fixed, p, **extra):
     assert np.all(np.isfinite(cams)) and np.all(np.isfinite(pts))
     assert ec <= bound, f"{test}: camera blocks {ec:.3e} > {C_BOUND:g} kappa eps = {bound:.3e} (kappa {kappa:.3e})"
     assert ep <= bound, f"{test}: point blocks {ep:.3e} > {C_BOUND:g} kappa eps = {bound:.3e} (kappa {kappa:.3e})"
-
-
-# ---- several ranks in one process over the stream-ordered loopback transport (tests/helpers/ba_loopback.hip) -----------------
-_loopback_lib = None
-
-
-def loopback_lib():
-    """the loopback transport's library, its ctypes signatures declared"""
-    global _loopback_lib
-    if _loopback_lib is None:
-        assert os.path.exists(LOOPBACK), f"{LOOPBACK} is missing: __graft_entry__.build() compiles it"
-        L = C.CDLL(LOOPBACK)
-        L.ba_loopback_create.restype = C.c_void_p
-        L.ba_loopback_create.argtypes = [C.c_int, C.c_size_t]
-        L.ba_loopback_destroy.argtypes = [C.c_void_p]
-        L.ba_loopback_rank.restype = C.c_void_p
-        L.ba_loopback_rank.argtypes = [C.c_void_p, C.c_int]
-        L.ba_loopback_ops.restype = C.c_long
-        L.ba_loopback_ops.argtypes = [C.c_void_p]
-        _loopback_lib = L
-    return _loopback_lib
-
-
-@contextlib.contextmanager
-def loopback_world(world, stage_bytes):
-    """(library, communicator) of `world` ranks with stage_bytes of staging each; destroyed on exit"""
-    L = loopback_lib()
-    loop = L.ba_loopback_create(world, stage_bytes)
-    assert loop, "loopback communicator could not be created"
-    try:
-        yield L, loop
-    finally:
-        L.ba_loopback_destroy(loop)
-
-
-def attach_loopback(ba, m, L, loop, rank, world):
-    """rank `rank` of the communicator as the handle's transport (before the handle's first solve)"""
-    hook = C.cast(L.ba_loopback_hook, ba._lib.COMM_CB)
-    ba._lib.check(ba._lib.lib().ba_lm_set_comm_hook(m.handle, rank, world, hook, L.ba_loopback_rank(loop, rank)))
-
-
-@pytest.fixture(scope="module")
-def loopback(gpu_ok):
-    return loopback_lib()
-
-
-class Ranks:
-    """`world` shards of one problem as handles in this process, attached to one loopback communicator."""
-
-    def __init__(self, ba, L, prob, world, stage_mb=64):
-        self.ba, self.L, self.world, self.prob = ba, L, world, prob
-        whole = ba.synthetic.as_arrays(prob)
-        self.loop = L.ba_loopback_create(world, stage_mb << 20)
-        assert self.loop, "loopback communicator could not be created"
-        self.shards, self.models = [], []
-        for r in range(world):
-            local, info = ba.parallel.shard_problem(whole, r, world)
-            m = ba.BALNLPModel(arrays=local, device=0)
-            attach_loopback(ba, m, L, self.loop, r, world)
-            self.shards.append((local, info))
-            self.models.append(m)
-
-    def step(self, lam, **kw):
-        """one sharded LM step, every rank on its own host thread -> (global delta from rank 0's cameras, per-rank camera
-        parts, model value)"""
-        out, err = [None] * self.world, [None] * self.world
-
-        def run(r):
-            try:
-                out[r] = self.ba.lm_step(self.models[r], self.shards[r][0][3], lam, **kw)
-            except Exception as e:  # noqa: BLE001 -- reported below with the rank
-                err[r] = e
-
-        ts = [threading.Thread(target=run, args=(r,)) for r in range(self.world)]
-        for t in ts:
-            t.start()
-        for t in ts:
-            t.join()
-        bad = [(r, e) for r, e in enumerate(err) if e is not None]
-        assert not bad, f"rank(s) failed: {bad}"
-        ncams, npnts = self.prob["ncams"], self.prob["npnts"]
-        delta = np.zeros(3 * npnts + 9 * ncams)
-        cams = []
-        for r in range(self.world):
-            pb, pe = self.shards[r][1]["point_range"]
-            d = out[r][0]
-            delta[3 * pb:3 * pe] = d[:3 * (pe - pb)]
-            cams.append(d[3 * (pe - pb):].copy())
-        delta[3 * npnts:] = cams[0]
-        return delta, cams, out[0][1]
-
-    def close(self):
-        for m in self.models:
-            m.close()
-        self.L.ba_loopback_destroy(self.loop)

@@ -4,37 +4,12 @@ Marquardt loop and the states.  Written from the text of the header, not from th
 Jacobian are derived here (P1 = R X + t, P2 = -P1.xy / P1.z, out = f (1 + k1 n + k2 n^2) P2, n = |P2|^2)."""
 import numpy as np
 
+from _lm_ref import factor, rho  # the two definitions this text shares with the LM reference: scipy's loss table, the header's factor
+
 CONVERGED, STALLED, MAX_ITER, FIXED, DEGENERATE, NONFINITE = range(6)
 BEHIND = 0x80
 UNDIST_ITERS = 8
 _PACK = ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))  # packed lower 3 x 3, row-major
-
-
-def rho(loss, z):
-    """(rho(z), rho'(z)) of scipy's losses"""
-    if loss == "linear":
-        return z, np.ones_like(z)
-    if loss == "huber":
-        sz = np.sqrt(np.maximum(z, 1.0))
-        return np.where(z <= 1.0, z, 2.0 * sz - 1.0), np.where(z <= 1.0, 1.0, 1.0 / sz)
-    if loss == "soft_l1":
-        t = np.sqrt(1.0 + z)
-        return 2.0 * z / (t + 1.0), 1.0 / t
-    if loss == "cauchy":
-        return np.log1p(z), 1.0 / (1.0 + z)
-    if loss == "arctan":
-        return np.arctan(z), 1.0 / (1.0 + z * z)
-    raise ValueError(loss)
-
-
-def info_factors(info):
-    """(nobs, 3) l00 l10 l11 of Lambda = L L' from (nobs, 2, 2) blocks, as ba_lm_set_obs_info factors them"""
-    xx, xy, yy = info[:, 0, 0], info[:, 0, 1], info[:, 1, 1]
-    l00 = np.sqrt(xx)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        l10 = np.where(xx > 0, xy / l00, 0.0)
-    l11 = np.sqrt(np.maximum(yy - l10 * l10, 0.0))
-    return np.stack([l00, l10, l11], axis=1)
 
 
 def rotations(cams):
@@ -60,7 +35,7 @@ class Scene:
         self.R = rotations(cams)[self.cam0]        # per observation
         self.t = cams[self.cam0, 3:6]
         self.k1, self.k2, self.f = cams[self.cam0, 6], cams[self.cam0, 7], cams[self.cam0, 8]
-        self.L = np.tile([1.0, 0.0, 1.0], (self.nobs, 1)) if info is None else info_factors(np.asarray(info, dtype=np.float64))
+        self.L = np.tile([1.0, 0.0, 1.0], (self.nobs, 1)) if info is None else np.stack(factor(np.asarray(info, dtype=np.float64)), axis=1)
         self.used = ~np.all(self.L == 0.0, axis=1)
         self.deg = np.bincount(self.pnt0, minlength=self.npnts)
 

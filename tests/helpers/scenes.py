@@ -2,7 +2,8 @@
 several problems merged into one -- a camera graph with several connected components -- and cameras that share no point with
 any other camera (tests/test_block_sparse_scenes.py); and observation graphs given point by point or camera pair by camera pair,
 so that a point's number of observations, where its rows fall against the kernels' 64-row batches and 64-point waves, and the
-length of a camera pair's task list are chosen, not drawn (tests/test_graph_boundaries.py)."""
+length of a camera pair's task list are chosen, not drawn (tests/test_graph_boundaries.py); and seeded arrays of per-observation
+information matrices with zero and rank-one blocks among them (tests/test_obs_info.py)."""
 import functools
 
 import numpy as np
@@ -179,3 +180,55 @@ def _scene(ba, name, shuffled):
 def scene(ba, name, shuffled=False):
     """The scene `name` of SCENES or BOUNDARY_SCENES, as generated or with its cameras renumbered at random (shuffle_cameras(seed=8)); built once."""
     return _scene(ba, name, bool(shuffled))
+
+
+# ---- seeded per-observation information matrices (tests/test_obs_info.py and the tests that combine the terms) --------------
+def blocks(sig1, sig2, angle):
+    """(n, 2, 2): rotations by `angle` of diag(1 / sig1^2, 1 / sig2^2), exactly symmetric"""
+    c, s = np.cos(angle), np.sin(angle)
+    a, b = 1.0 / np.asarray(sig1) ** 2, 1.0 / np.asarray(sig2) ** 2
+    out = np.empty((len(angle), 2, 2))
+    out[:, 0, 0] = c * c * a + s * s * b
+    out[:, 1, 1] = s * s * a + c * c * b
+    out[:, 0, 1] = out[:, 1, 0] = c * s * (a - b)
+    return out
+
+
+def random_info(p, seed, frac_zero=0.05, frac_rank1=0.05):
+    """Anisotropic information of every observation of p: random rotations of diag(1 / s1^2, 1 / s2^2), s in [0.5, 4]; about
+    frac_zero of them exactly 0 and about frac_rank1 rank one (u u' / s^2), drawn only among the observations a point can
+    spare: every point keeps at least two full-rank observations (full_rank_per_point checks it)."""
+    rng = np.random.default_rng(seed)
+    n = p["nobs"]
+    info = blocks(rng.uniform(0.5, 4.0, n), rng.uniform(0.5, 4.0, n), rng.uniform(0.0, np.pi, n))
+    pnt = np.asarray(p["pnt_idx1"]) - 1
+    spare = np.bincount(pnt, minlength=p["npnts"]) - 2  # observations a point can lose
+    kind = rng.random(n)
+    for o in rng.permutation(n):
+        if kind[o] < frac_zero + frac_rank1 and spare[pnt[o]] > 0:
+            spare[pnt[o]] -= 1
+            if kind[o] < frac_zero:
+                info[o] = 0.0
+            else:
+                th, s = rng.uniform(0.0, np.pi), rng.uniform(0.5, 4.0)
+                u = np.array([np.cos(th), np.sin(th)])
+                info[o] = np.outer(u, u) / s ** 2
+    return clip_psd(info)
+
+
+def clip_psd(info):
+    """the blocks with xy moved towards 0 by as many ulps as it takes for xy^2 <= xx yy to hold in floating point (a rank-one
+    block formed in floating point may miss it by one)"""
+    bad = info[:, 0, 1] ** 2 > info[:, 0, 0] * info[:, 1, 1]
+    while bad.any():
+        info[bad, 0, 1] = info[bad, 1, 0] = np.nextafter(info[bad, 0, 1], 0.0)
+        bad = info[:, 0, 1] ** 2 > info[:, 0, 0] * info[:, 1, 1]
+    return info
+
+
+def full_rank_per_point(p, info):
+    """the smallest number of full-rank (det > 1e-8 trace^2) observations any point has"""
+    det = info[:, 0, 0] * info[:, 1, 1] - info[:, 0, 1] ** 2
+    tr = info[:, 0, 0] + info[:, 1, 1]
+    full = det > 1e-8 * tr ** 2
+    return int(np.bincount(np.asarray(p["pnt_idx1"]) - 1, weights=full.astype(float), minlength=p["npnts"]).min())

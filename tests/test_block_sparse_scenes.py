@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_ref import env
+from _lm_run import env
 from _util import bits_report, rel_err
 from _util import parity_record as _report
 

@@ -8,31 +8,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _lm_ref import (C_BOUND, EPS, arrays, attach_loopback, block_errs, check_cov, env, fixed_vector, gauge_kw, hessian,
-                     kappa_jacobi, loopback_world, ref_dense, schur)
+from _lm_ref import C_BOUND, EPS, block_errs, check_cov, hessian, kappa_jacobi, ref_dense, ref_schur, schur
+from _lm_run import arrays, attach_loopback, env, fixed_vector, gauge_kw, loopback_world
 from _util import bits_report, parity_record
 
 INTRINSICS = ("k1", "k2", "f")
-
-
-def _ref_schur(H, p, fixed):
-    """camera and point blocks from the explicit Schur complement: Z = S^-1, Sigma_pp = U^-1 + (U^-1 W) Z (U^-1 W)'"""
-    S, G, Ubi = schur(H, p)
-    Z = np.linalg.inv(S)
-    cams = np.stack([Z[9 * c:9 * c + 9, 9 * c:9 * c + 9] for c in range(p["ncams"])])
-    npnts = p["npnts"]
-    pts = np.empty((npnts, 3, 3))
-    for a in range(0, npnts, 500):
-        b = min(npnts, a + 500)
-        Gc = G[3 * a:3 * b]
-        P = np.asarray(Gc @ Z).reshape(b - a, 3, -1)
-        Q = Gc.toarray().reshape(b - a, 3, -1)
-        pts[a:b] = Ubi[a:b] + np.einsum("irk,imk->irm", P, Q)
-    fp = fixed[:3 * npnts].reshape(npnts, 3)
-    fc = fixed[3 * npnts:].reshape(p["ncams"], 9)
-    cams[fc[:, :, None] | fc[:, None, :]] = 0.0
-    pts[fp[:, :, None] | fp[:, None, :]] = 0.0
-    return cams, pts, S, Z
 
 
 # ---- CPU: refusals before any device call -----------------------------------------------------------------------------------
@@ -173,7 +153,7 @@ def test_covariance_block_sparse_equals_dense_and_schur(ba, orc, gpu_ok, name):
     if name == "two-ended":
         assert order == "two-ended", order
     H = hessian(orc, p, p["x0"], lam, fixed)
-    ref_c, ref_p, S, Z = _ref_schur(H, p, fixed)
+    ref_c, ref_p, S, Z = ref_schur(H, p, fixed)
     kappa = kappa_jacobi(S, Z)
     check_cov(f"covariance_sparse[{name}]", cs, ps, ref_c, ref_p, kappa, fixed, p, tile_fill=pat_s[0], order=order,
            sparse_vs_dense_cam=block_errs(cs, cd), sparse_vs_dense_pnt=block_errs(ps, pd))

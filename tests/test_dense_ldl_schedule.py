@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _lm_ref import env
+from _lm_run import env
 from _util import bits_report
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

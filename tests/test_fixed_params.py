@@ -9,26 +9,11 @@ import threading
 import numpy as np
 import pytest
 
-from _lm_ref import STEP_TOL, arrays, attach_loopback, env, fixed_vector, gauge_kw, jac, lm_opts, loopback_world, residual, reweighted, solve
+from _lm_ref import STEP_TOL, jac, residual, step
+from _lm_run import arrays, attach_loopback, env, fixed_vector, gauge_kw, lm_opts, loopback_world, solve
 from _util import bits_report, parity_record, rel_err
 
 INTRINSICS = ("k1", "k2", "f")
-
-
-def _ref_step(orc, p, x, lam, fixed, loss=None, c=1.0):
-    """delta (zeros on the fixed entries), 1/2 |J_F delta_F + r|^2, J_F'r (zeros on the fixed entries) of the dense solve
-    over the free columns; loss = "huber": the reweighted r~, J~ of _lm_ref.reweighted"""
-    r, J = reweighted(orc, p, x, loss, c)[:2] if loss == "huber" else (residual(orc, p, x), jac(orc, p, x))
-    free = ~fixed
-    JF = J[:, np.flatnonzero(free)]
-    g = JF.T @ r
-    A = (JF.T @ JF).toarray()
-    A[np.diag_indices_from(A)] += lam
-    dF = np.linalg.solve(A, -g)
-    m = JF @ dF + r
-    d, gf = np.zeros(len(fixed)), np.zeros(len(fixed))
-    d[free], gf[free] = dF, g
-    return d, 0.5 * (m @ m), gf
 
 
 def _step_masks(p):
@@ -118,8 +103,11 @@ def test_fixed_c_abi_host_checks(ba):
 
 # ---- GPU: the step ---------------------------------------------------------------------------------------------------------
 def _check_step(ba, orc, m, p, lam, kw, tol, fixed, what, loss=None, c=1.0):
+    """against _lm_ref.step: delta and J_F'r with zeros on the fixed entries, 1/2 |J_F delta_F + r|^2, of the dense solve over
+    the free columns"""
     d, half, jtr = ba.lm_step(m, p["x0"], lam, **kw, **({"loss": loss, "f_scale": c} if loss else {}))
-    d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, fixed, loss, c)
+    ref = step(orc, p, p["x0"], lam, fixed=fixed, loss=loss or "linear", c=c)
+    d_ref, half_ref, g_ref = ref["delta"], ref["model"], ref["grad"]
     assert np.all(d[fixed] == 0.0), f"{what}, lambda {lam}: {np.count_nonzero(d[fixed])} fixed entries of delta are not 0"
     assert np.all(jtr[fixed] == 0.0), f"{what}, lambda {lam}: fixed entries of J'r are not 0"
     e = rel_err(d, d_ref)
@@ -145,7 +133,7 @@ def test_fixed_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, mask):
             worst = max(worst, e / tol)
         assert ba._lib.get_fixed(m.handle) == (int(fixed[3 * p["npnts"]:].sum()), int(fixed[:3 * p["npnts"]].sum()) // 3)
         lam = 1.0
-        d_ref, _, _ = _ref_step(orc, p, p["x0"], lam, fixed)
+        d_ref = step(orc, p, p["x0"], lam, fixed=fixed)["delta"]
         dp = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), **kw)[0]
         assert np.all(dp[fixed] == 0.0), f"{mask}: PCG step, fixed entries"
         ep = rel_err(dp, d_ref)
@@ -197,7 +185,8 @@ def test_fixed_step_block_sparse_schedule(ba, orc, gpu_ok):
 
     (d, half, jtr), pat = env("BA_SPARSE_S", "1", run)
     assert pat[2], "the block-sparse list schedule was not used"
-    d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, fixed)
+    ref = step(orc, p, p["x0"], lam, fixed=fixed)
+    d_ref, half_ref, g_ref = ref["delta"], ref["model"], ref["grad"]
     assert np.all(d[fixed] == 0.0) and np.all(jtr[fixed] == 0.0)
     e = rel_err(d, d_ref)
     assert e <= 1e-10, f"block-sparse masked step: {e:.3e}"

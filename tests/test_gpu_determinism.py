@@ -12,7 +12,7 @@ import threading
 import numpy as np
 import pytest
 
-from _lm_ref import Ranks, env, loopback  # noqa: F401 (loopback: a fixture)
+from _lm_run import Ranks, env, loopback  # noqa: F401 (loopback: a fixture)
 from _util import bits_report, digest, rel_err
 
 pytestmark = pytest.mark.gpu

@@ -18,8 +18,8 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_ref import (F32_TOL, PCG_TOL, STEP_TOL, Ranks, arrays, check_cov, fixed_vector, gauge_kw, hessian, jac, kappa_jacobi, limit,
-                     loopback, ref_dense, residual, schur)  # noqa: F401 -- loopback is a fixture
+from _lm_ref import F32_TOL, PCG_TOL, STEP_TOL, check_cov, hessian, jac, kappa_jacobi, limit, ref_dense, schur, step_once
+from _lm_run import Ranks, arrays, fixed_vector, gauge_kw, loopback  # noqa: F401 -- loopback is a fixture
 from _util import bits_report, parity_record, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,29 +122,10 @@ def test_scene_k128_has_its_key_lengths(ba):
 
 
 # ---- the dense numpy step -----------------------------------------------------------------------------------------------------
-_ref_cache = {}
-
-
 def reference(orc, p, name, lam):
-    """dict(delta, model, jtr, kappa) of the dense step (J'J + lam I) delta = -J'r through the explicit Schur complement of
-    tests/_lm_ref.py; once per (scene, lambda), read-only"""
-    if (name, lam) not in _ref_cache:
-        x = p["x0"]
-        np3 = 3 * p["npnts"]
-        H = hessian(orc, p, x, lam, np.zeros(len(x), dtype=bool))
-        S, G, Ubi = schur(H, p)
-        J, r = jac(orc, p, x), residual(orc, p, x)
-        g = J.T @ r
-        u = np.einsum("pij,pj->pi", Ubi, g[:np3].reshape(-1, 3)).ravel()
-        dc = np.linalg.solve(S, -(g[np3:] - G.T @ g[:np3]))
-        d = np.concatenate([-u - G @ dc, dc])
-        m = J @ d + r
-        out = dict(delta=d, model=0.5 * float(m @ m), jtr=g, kappa=kappa_jacobi(S))
-        for v in out.values():
-            if isinstance(v, np.ndarray):
-                v.setflags(write=False)
-        _ref_cache[(name, lam)] = out
-    return _ref_cache[(name, lam)]
+    """dict(delta, model, grad, kappa) of the step (J'J + lam I) delta = -J'r through the explicit Schur complement
+    (_lm_ref.step, solve="schur": scene K128 is too large for a dense solve); once per (scene, lambda), read-only"""
+    return step_once(("graph_boundaries", name, lam), orc, p, p["x0"], lam, solve="schur")
 
 
 def test_reference_step_solves_the_normal_equations(ba, orc):
@@ -155,8 +136,8 @@ def test_reference_step_solves_the_normal_equations(ba, orc):
     for lam in LAMBDAS:
         ref = reference(orc, p, "P", lam)
         J = jac(orc, p, p["x0"])
-        res = J.T @ (J @ ref["delta"]) + lam * ref["delta"] + ref["jtr"]
-        assert np.linalg.norm(res) <= 1e-12 * np.linalg.norm(ref["jtr"])
+        res = J.T @ (J @ ref["delta"]) + lam * ref["delta"] + ref["grad"]
+        assert np.linalg.norm(res) <= 1e-12 * np.linalg.norm(ref["grad"])
         assert np.all(ref["delta"][: 3 * p["npnts"]].reshape(-1, 3)[deg == 0] == 0.0)
         assert np.all(ref["delta"][3 * p["npnts"]:].reshape(-1, 9)[cdeg == 0] == 0.0)
 
@@ -170,7 +151,7 @@ def _check_step(tag, name, p, got, ref, lam, deg, cdeg):
     e, e32, ep = rel_err(d, d_ref), rel_err(d32, d_ref), rel_err(dp, d_ref)
     em = abs(half - ref["model"]) / ref["model"]
     emp = abs(halfp - ref["model"]) / ref["model"]
-    eg = float(np.linalg.norm(jtr - ref["jtr"]) / np.linalg.norm(ref["jtr"]))
+    eg = float(np.linalg.norm(jtr - ref["grad"]) / np.linalg.norm(ref["grad"]))
     lonely = np.flatnonzero(cdeg == 0)
     cams = lambda v: v[np3:].reshape(-1, 9)[lonely].ravel()  # noqa: E731
     ec, ec32, ecp = (float(np.linalg.norm(cams(v)) / np.linalg.norm(d_ref)) for v in (d, d32, dp))

@@ -1,6 +1,6 @@
 """Per-observation 2 x 2 information matrices of the LM solve (ba_lm_set_obs_info, include/ba_hip.h): observation i
 counts with Lambda_i = L_i L_i', the LM entries run on r^_i = L_i' r_i and J^_i = L_i' J_i.  The references are numpy
-(tests/helpers/info_ref.py): the oracle's residual and Jacobian whitened there, the dense solve of the normal equations.  Every
+(tests/_lm_ref.py): the oracle's residual and Jacobian whitened there, the dense solve of the normal equations.  Every
 limit is one the other term tests use (tests/_lm_ref.py: STEP_TOL, F32_TOL, PCG_TOL through limit(), check_cov; the figures of
 test_prior_step_vs_dense_numpy, test_robust_eval_weights_and_cost and test_robust_solve).  The first tests need no device; the
 rest run on the GPU.  small_prob has 1800 observations = 7 tiles of 256 and a tail of 8."""
@@ -10,27 +10,23 @@ import sys
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
-from _lm_ref import (F32_TOL, PCG_TOL, STEP_TOL, arrays, attach_loopback, check_cov, env, fixed_vector, gauge_kw, jac, kappa_jacobi,
-                     limit, lm_opts, loopback_world, ref_dense, residual, schur, solve, weights_cost)
+from _lm_ref import (F32_TOL, PCG_TOL, STEP_TOL, check_cov, factor, hessian, kappa_jacobi, limit, linearise, ref_dense, residual,
+                     schur, step, weights_cost, whiten_residual, whitener)
+from _lm_run import arrays, attach_loopback, env, fixed_vector, gauge_kw, lm_opts, loopback_world, solve
 from _util import bits_report, parity_record, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
-import info_ref as ir  # noqa: E402
-import prior_ref as pr  # noqa: E402
+from scenes import blocks, clip_psd, full_rank_per_point, random_info  # noqa: E402
 
 NAMES = ("ba_lm_set_obs_info", "ba_lm_get_obs_info")
 NOBS = 7
 
 
-def _ref_step(orc, p, x, lam, info, loss="linear", c=1.0, fixed=None, pri=None):
-    """(delta, model, gradient, kappa of the Jacobi-scaled damped S) of the dense numpy solve on the whitened r and J"""
-    rt, Jt, _, _ = ir.reweighted(orc, p, x, info, loss, c)
-    rows = pr.rows(x, p["ncams"], p["npnts"], fixed=fixed, **(pri or {}))
-    d, mod, g, A = pr.step(Jt, rt, lam, rows, fixed)
-    return d, mod, g, pr.kappa_jacobi_S(A, p["npnts"])[0]
+def _unpack(ref):
+    """(delta, model, gradient, kappa of the Jacobi-scaled damped S) of _lm_ref.step's record"""
+    return ref["delta"], ref["model"], ref["grad"], ref["kappa"]
 
 
 def _identity(p):
@@ -116,22 +112,22 @@ def test_seeded_array_packs_and_the_reference_factors_it(ba, small_prob):
     xx xy yy, and the reference's factor of it holds: L L' = Lambda to rounding, r^' r^ = r' Lambda r, every point keeps two
     full-rank observations."""
     p = small_prob
-    info = ir.random_info(p, 3)
+    info = random_info(p, 3)
     packed = ba._lib.obs_info_pack(info, p["nobs"])
     assert np.array_equal(packed, np.stack([info[:, 0, 0], info[:, 0, 1], info[:, 1, 1]], axis=1))
     assert ba._lib.ProblemTerms(obs_info=info).weighted
-    l00, l10, l11 = ir.factor(info)
+    l00, l10, l11 = factor(info)
     back = np.stack([l00 * l00, l00 * l10, l10 * l10 + l11 * l11], axis=1)
     want = np.stack([info[:, 0, 0], info[:, 0, 1], info[:, 1, 1]], axis=1)
     assert np.max(np.abs(back - want)) <= 4 * np.finfo(float).eps * np.max(want)
     zero = np.all(info.reshape(-1, 4) == 0.0, axis=1)
     assert 0.02 * p["nobs"] < zero.sum() < 0.08 * p["nobs"]
-    assert ir.full_rank_per_point(p, info) >= 2
+    assert full_rank_per_point(p, info) >= 2
     r = np.random.default_rng(0).standard_normal(2 * p["nobs"])
-    rh = ir.whiten_residual(r, info)
+    rh = whiten_residual(r, info)
     quad = np.einsum("ni,nij,nj->n", r.reshape(-1, 2), info, r.reshape(-1, 2))
     assert np.max(np.abs(rh[0::2] ** 2 + rh[1::2] ** 2 - quad)) <= 1e-13 * np.max(quad)
-    assert np.array_equal(ir.whitener(info) @ r, rh)
+    assert np.array_equal(whitener(info) @ r, rh)
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
@@ -193,7 +189,7 @@ def test_identity_gives_the_plain_bits(ba, orc, small_prob, gpu_ok):
                     rep = bits_report(np.atleast_1d(got), np.atleast_1d(want), f"{loss}, {name} at lambda {lam:g}: Lambda = I vs no obs_info")
                     assert not rep, rep
                 if loss == "huber":
-                    d_ref, _, _, kappa = _ref_step(orc, p, p["x0"], lam, eye, "huber", 1.0)
+                    d_ref, _, _, kappa = _unpack(step(orc, p, p["x0"], lam, info=eye, loss="huber", c=1.0))
                     e, lim = rel_err(a[0], d_ref), limit(STEP_TOL[lam], kappa)
                     print(f"obs_info identity, huber, lambda {lam:g}: step vs numpy {e:.3e} (limit {lim:.1e})")
                     assert e <= lim
@@ -216,7 +212,7 @@ def test_scaling_by_four_is_a_quarter_of_the_damping(ba, orc, small_prob, gpu_ok
         for lam in (30.0, 1.0, 1e-2):
             d, half, jtr = ba.lm_step(m, p["x0"], lam, obs_info=four)
             d0, half0, jtr0 = ba.lm_step(m, p["x0"], lam / 4)
-            kappa = _ref_step(orc, p, p["x0"], lam / 4, _identity(p))[3]
+            kappa = step(orc, p, p["x0"], lam / 4, info=_identity(p))["kappa"]
             e, lim = rel_err(d, d0), limit(STEP_TOL[lam], kappa)
             em, eg = abs(half - 4 * half0) / (4 * half0), rel_err(jtr, 4 * jtr0)
             print(f"obs_info 4 I, lambda {lam:g}: step {e:.3e} (limit {lim:.1e})  model {em:.3e}  jtr {eg:.3e}")
@@ -249,7 +245,7 @@ def test_zero_information_drops_the_observation(ba, orc, small_prob, gpu_ok):
             tol = STEP_TOL[lam]
             d, half, jtr = ba.lm_step(m, p["x0"], lam, obs_info=sig)
             dq, halfq, jtrq = ba.lm_step(mq, p["x0"], lam)
-            kappa = _ref_step(orc, q, p["x0"], lam, _identity(q))[3]
+            kappa = step(orc, q, p["x0"], lam, info=_identity(q))["kappa"]
             e, lim = rel_err(d, dq), limit(tol, kappa)
             print(f"obs_info dropping, lambda {lam:g}: step {e:.3e} (limit {lim:.1e})")
             assert e <= lim and abs(half - halfq) <= 1e-10 * halfq and rel_err(jtr, jtrq) <= 1e-12
@@ -267,13 +263,13 @@ def test_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok):
     """Anisotropic Lambda with zero and rank-one blocks, lambda in {30, 1, 1e-2}: :LDL, facto_type = Float32 and
     pcg = (1e-12, 5000) against the dense numpy solve, with the limits of test_prior_step_vs_dense_numpy."""
     p = small_prob
-    info = ir.random_info(p, 3)
-    assert ir.full_rank_per_point(p, info) >= 2
+    info = random_info(p, 3)
+    assert full_rank_per_point(p, info) >= 2
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam in (30.0, 1.0, 1e-2):
             tol = STEP_TOL[lam]
-            d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, info)
+            d_ref, mod_ref, g_ref, kappa = _unpack(step(orc, p, p["x0"], lam, info=info))
             d, half, jtr = ba.lm_step(m, p["x0"], lam, obs_info=info)
             d32 = ba.lm_step(m, p["x0"], lam, facto_type=np.float32, obs_info=info)[0]
             dp, halfp, _, its = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), obs_info=info)
@@ -301,8 +297,8 @@ def test_step_with_mask_huber_and_point_prior(ba, orc, small_prob, gpu_ok):
     """Every term in one call: fixed parameters, a huber loss (on the Mahalanobis distance), a point prior and the information.
     Fixed entries of delta and jtr are exactly 0, the free part is numpy's."""
     p = small_prob
-    info = ir.random_info(p, 4)
-    assert ir.full_rank_per_point(p, info) >= 2
+    info = random_info(p, 4)
+    assert full_rank_per_point(p, info) >= 2
     comp = np.zeros((p["ncams"], 9), dtype=bool)
     comp[1, 6:] = True
     mask = dict(fixed_cameras=[6], fixed_points=[3, 50], fixed_camera_params=comp)
@@ -313,7 +309,7 @@ def test_step_with_mask_huber_and_point_prior(ba, orc, small_prob, gpu_ok):
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam in (30.0, 1.0, 1e-2):
-            d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, info, "huber", 1.5, fixed, pri)
+            d_ref, mod_ref, g_ref, kappa = _unpack(step(orc, p, p["x0"], lam, info=info, loss="huber", c=1.5, fixed=fixed, priors=pri))
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss="huber", f_scale=1.5, obs_info=info, **mask, **pri)
             assert np.all(d[fixed] == 0.0) and np.all(jtr[fixed] == 0.0)
             e, lim = rel_err(d, d_ref), limit(STEP_TOL[lam], kappa)
@@ -322,7 +318,7 @@ def test_step_with_mask_huber_and_point_prior(ba, orc, small_prob, gpu_ok):
             print(f"obs_info_step_all_terms lambda {lam:g}: kappa {kappa:.3e}  step {e:.3e} (limit {lim:.1e})  model {em:.3e}  jtr {eg:.3e}")
             parity_record(f"obs_info_step_all_terms[{lam:g}]", kappa=kappa, ldl=e, ldl_limit=lim, model=em, jtr=eg)
             assert e <= lim and em <= 1e-10 and eg <= 1e-12
-        assert rel_err(d, _ref_step(orc, p, p["x0"], 1e-2, info, "linear", 1.0, fixed, pri)[0]) > 1e-6  # (the loss acts)
+        assert rel_err(d, step(orc, p, p["x0"], 1e-2, info=info, fixed=fixed, priors=pri)["delta"]) > 1e-6  # (the loss acts)
     finally:
         m.close()
 
@@ -331,8 +327,8 @@ def test_step_with_mask_huber_and_point_prior(ba, orc, small_prob, gpu_ok):
 def test_step_block_sparse_schedule(ba, orc, gpu_ok):
     """The scene and the switch of test_robust_step_block_sparse_schedule: the step on the block-sparse list schedule."""
     p = ba.synthetic.make_problem(300, 700, 3500, seed=5, locality=0.08)
-    info = ir.random_info(p, 5)
-    assert ir.full_rank_per_point(p, info) >= 2
+    info = random_info(p, 5)
+    assert full_rank_per_point(p, info) >= 2
     lam = 1.0
 
     def run():
@@ -344,7 +340,7 @@ def test_step_block_sparse_schedule(ba, orc, gpu_ok):
 
     (d, half, jtr), pat = env("BA_SPARSE_S", "1", run)
     assert pat[2], "the block-sparse list schedule was not used"
-    d_ref, mod_ref, g_ref, kappa = _ref_step(orc, p, p["x0"], lam, info)
+    d_ref, mod_ref, g_ref, kappa = _unpack(step(orc, p, p["x0"], lam, info=info))
     e, lim = rel_err(d, d_ref), limit(STEP_TOL[lam], kappa)
     print(f"obs_info_step_sparse: kappa {kappa:.3e}  step {e:.3e} (limit {lim:.1e})")
     parity_record("obs_info_step_sparse", kappa=kappa, step=e, limit=lim)
@@ -359,7 +355,7 @@ def _check_eval(ba, m, x, info, losses, c, what):
     r = m.cons(x)
     for loss in losses:
         w, f = m.robust_weights(x, loss, c, obs_info=info)
-        w_ref, f_ref = ir.weights_cost(r, info, loss, c)
+        w_ref, f_ref = weights_cost(r, loss, c, info)
         e, ef = float(np.max(np.abs(w - w_ref) / w_ref)), abs(f - f_ref) / f_ref
         print(f"{what}: {loss}, c = {c}: weights {e:.3e}, cost {ef:.3e}")
         parity_record(f"{what}[{loss}]", weights=e, cost=ef)
@@ -373,7 +369,7 @@ def _check_eval(ba, m, x, info, losses, c, what):
 def test_robust_eval_weights_and_cost_with_information(ba, small_prob, gpu_ok):
     """weights = rho'(r' Lambda r / c^2) and the cost, cauchy and the other losses; a call without the keyword is plain again"""
     p = small_prob
-    info = ir.random_info(p, 6)
+    info = random_info(p, 6)
     m, fresh = ba.BALNLPModel(arrays=arrays(p)), ba.BALNLPModel(arrays=arrays(p))
     try:
         _check_eval(ba, m, p["x0"], info, ("cauchy", "linear", "huber", "soft_l1", "arctan"), 2.0, "obs_info_eval")
@@ -403,7 +399,7 @@ def test_robust_eval_many_tiles(ba, small_prob, gpu_ok):
              x0=np.concatenate([s["x0"][:np3] for s in parts] + [s["x0"][np3:] for s in parts]),
              ncams=12 * len(parts), npnts=400 * len(parts), nobs=1024 * 256 + 300)
     assert len(q["cam_idx1"]) == q["nobs"] == 262444
-    info = ir.random_info(q, 7)
+    info = random_info(q, 7)
     m = ba.BALNLPModel(arrays=arrays(q))
     try:
         _check_eval(ba, m, q["x0"], info, ("linear", "huber"), 1.0, "obs_info_eval_many_tiles")
@@ -436,9 +432,9 @@ def test_solve_with_heteroscedastic_noise(ba, orc, small_prob, gpu_ok, variant, 
     of test_robust_solve (oatol = ortol = 0 as there).  Once with normalize = :J (the step entries have no such option), and
     there with anisotropic full blocks: sigma_i along a random direction, sigma_i / 2 across it."""
     p, sig = _noisy(ba, orc, small_prob, 21)
-    info = ir.blocks(sig, sig, np.zeros(p["nobs"]))
+    info = blocks(sig, sig, np.zeros(p["nobs"]))
     if normalize == "J":
-        sig = info = ir.clip_psd(ir.blocks(sig, 0.5 * sig, np.random.default_rng(22).uniform(0.0, np.pi, p["nobs"])))
+        sig = info = clip_psd(blocks(sig, 0.5 * sig, np.random.default_rng(22).uniform(0.0, np.pi, p["nobs"])))
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         st = solve(ba, m, variant, facto, normalize, obs_info=sig, oatol=0.0, ortol=0.0)
@@ -448,7 +444,7 @@ def test_solve_with_heteroscedastic_noise(ba, orc, small_prob, gpu_ok, variant, 
         m.close()
     f_acc = [row[1] for row in st.log if row[7]]
     assert len(f_acc) >= 2 and all(b < a for a, b in zip(f_acc, f_acc[1:])), f"accepted rows: f not strictly decreasing {f_acc}"
-    rt, Jt, _, f_ref = ir.reweighted(orc, p, st.solution, info)
+    rt, Jt, _, f_ref = linearise(orc, p, st.solution, info)
     g = np.linalg.norm(Jt.T @ rt)
     feas = st.dual_feas if variant == 1 else st.primal_feas
     ef, eg = abs(st.objective - f_ref) / f_ref, abs(feas - g) / g
@@ -461,7 +457,7 @@ def test_solve_with_heteroscedastic_noise(ba, orc, small_prob, gpu_ok, variant, 
     assert not rep, rep
     assert st.log == st2.log
     # the weighted solution has the lower weighted objective, the plain one the lower plain objective
-    assert f_ref < ir.reweighted(orc, p, plain.solution, info)[3]
+    assert f_ref < linearise(orc, p, plain.solution, info)[3]
 
 
 @pytest.mark.gpu
@@ -471,8 +467,8 @@ def test_covariance_with_information(ba, orc, small_prob, gpu_ok):
     p = small_prob
     kw = gauge_kw(p)
     fixed = fixed_vector(ba, p, kw)
-    info = ir.random_info(p, 8)
-    assert ir.full_rank_per_point(p, info) >= 2
+    info = random_info(p, 8)
+    assert full_rank_per_point(p, info) >= 2
     sigma = 2.0
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
@@ -481,15 +477,12 @@ def test_covariance_with_information(ba, orc, small_prob, gpu_ok):
         cams_0, pts_0, _ = ba.covariance(m, p["x0"], 0.0, **kw)
     finally:
         m.close()
-    J = ir.whitener(info) @ jac(orc, p, p["x0"]) @ sp.diags((~fixed).astype(float))
-    H = (J.T @ J + sp.diags(np.where(fixed, 1.0, 0.0))).tocsr()
+    H = hessian(orc, p, p["x0"], 0.0, fixed, info=info)
     ref_c, ref_p = ref_dense(H, p, fixed)
     S, _, _ = schur(H, p)
     check_cov("covariance_obs_info", cams, pts, ref_c, ref_p, kappa_jacobi(S), fixed, p, min_rel_pivot=piv)
     assert piv > 1e-10
-    J0 = jac(orc, p, p["x0"]) @ sp.diags((~fixed).astype(float))
-    S0, _, _ = schur(  # (kappa of the plain system, for the scaling statement)
-        (J0.T @ J0 + sp.diags(np.where(fixed, 1.0, 0.0))).tocsr(), p)
+    S0, _, _ = schur(hessian(orc, p, p["x0"], 0.0, fixed), p)  # (kappa of the plain system, for the scaling statement)
     check_cov("covariance_obs_info_one_sigma", cams_s, pts_s, sigma ** 2 * cams_0, sigma ** 2 * pts_0, kappa_jacobi(S0), fixed, p)
 
 
@@ -500,7 +493,7 @@ def test_no_stale_recorded_sequence_with_information(ba, small_prob, gpu_ok, pre
     same solve on a fresh handle -- a sequence recorded with or without information, or under one array, is never replayed
     under another setting."""
     p = small_prob
-    seq = [None, ir.random_info(p, 9), ir.random_info(p, 10), None]
+    seq = [None, random_info(p, 9), random_info(p, 10), None]
 
     def run():
         shared = ba.BALNLPModel(arrays=arrays(p))
@@ -527,7 +520,7 @@ def test_refused_combinations_at_the_c_entries(ba, small_prob, gpu_ok):
     untouched, and after clearing a plain step gives the bits from before."""
     p = small_prob
     lib = ba._lib.lib()
-    info3 = ba._lib.obs_info_pack(ir.random_info(p, 11), p["nobs"])
+    info3 = ba._lib.obs_info_pack(random_info(p, 11), p["nobs"])
     no_cb = C.cast(None, ba._lib.LOG_CB)
     m, mc = ba.BALNLPModel(arrays=arrays(p)), ba.BALNLPModel(arrays=arrays(p))
     m32 = ba.BALNLPModel(arrays=arrays(p), T=np.float32)
@@ -584,7 +577,7 @@ def test_profile_shows_the_pass_and_nothing_without_it(ba, small_prob, gpu_ok):
     """With information the class k_info_whiten appears (once per linearisation, once per trial step) and k_robust_scale does
     not, also under a loss; without it the classes and counts are those of a handle that never had any."""
     p = small_prob
-    info = ir.random_info(p, 12)
+    info = random_info(p, 12)
 
     def profile(m, **kw):
         m.profile(True)

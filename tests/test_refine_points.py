@@ -9,12 +9,12 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_ref import arrays, solve
+from _lm_run import arrays, solve
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
-import info_ref as ir  # noqa: E402
 import points_ref as pr  # noqa: E402
+from scenes import random_info  # noqa: E402
 
 XTOL = 1e-10
 TIER = 32  # PT_TIER of csrc/ba_point_kernels.hip
@@ -185,11 +185,11 @@ def _terms(ba, p, what):
         info[:, 0, 0] = info[:, 1, 1] = 1.0 / s ** 2
         return dict(obs_info=s), dict(info=info)
     if what == "info":  # full 2 x 2 blocks, some rank one, some exactly 0 (every point keeps two full-rank observations)
-        info = ir.random_info(p, 5)
+        info = random_info(p, 5)
         assert (np.abs(info).reshape(nobs, -1).max(axis=1) == 0).any()
         return dict(obs_info=info), dict(info=info)
     if what == "info_huber":
-        info = ir.random_info(p, 5)
+        info = random_info(p, 5)
         return dict(obs_info=info, loss="huber", f_scale=1.0, max_iter=1000), dict(info=info, loss="huber", c=1.0, max_iter=1000)
     if what == "prior":
         idx = np.array([2, 9, 30]) if n > 30 else np.array([0])
@@ -315,7 +315,7 @@ def test_max_iter_zero_evaluates_only(ba, gpu_ok, small_prob):
     try:
         x, info = ba.refine_points(m, p["x0"], max_iter=0)
         r = m.cons(p["x0"])
-        info3 = ir.random_info(p, 5)
+        info3 = random_info(p, 5)
         _, info_t = ba.refine_points(m, p["x0"], max_iter=0, loss="cauchy", f_scale=0.7, obs_info=info3)
         _, f_t = m.robust_weights(p["x0"], "cauchy", 0.7, obs_info=info3)
     finally:

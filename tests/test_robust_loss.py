@@ -11,24 +11,14 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_ref import STEP_TOL, Ranks, arrays, env, loopback, residual, reweighted, solve, weights_cost  # noqa: F401 (loopback: a fixture)
+from _lm_ref import STEP_TOL, linearise, residual, step, weights_cost
+from _lm_run import Ranks, arrays, env, loopback, solve  # noqa: F401 (loopback: a fixture)
 from _util import bits_report, rel_err
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import info_ref as ir  # noqa: E402
+import scenes  # noqa: E402
 
 LOSSES = ("linear", "huber", "soft_l1", "cauchy", "arctan")
-
-
-def _ref_step(orc, p, x, lam, loss, c):
-    """delta, 1/2 |J~ delta + r~|^2, J~'r~ of the dense solve"""
-    rt, Jt, _, _ = reweighted(orc, p, x, loss, c)
-    g = Jt.T @ rt
-    A = (Jt.T @ Jt).toarray()
-    A[np.diag_indices_from(A)] += lam
-    d = np.linalg.solve(A, -g)
-    m = Jt @ d + rt
-    return d, 0.5 * (m @ m), g
 
 
 # ---- CPU: the Python layer refuses before any device call --------------------------------------------------------------------
@@ -120,7 +110,7 @@ def test_robust_eval_tile_shapes(ba, gpu_ok, shape):
     information, with a seeded array of information matrices, and with Lambda = I, which gives the bits of the run without
     information.  The partial tile also through lm_step under huber (the J side of the tile), Lambda = I against none by bits."""
     p = ba.synthetic.make_problem(*shape, seed=5)
-    info, eye = ir.random_info(p, 5), np.broadcast_to(np.eye(2), (p["nobs"], 2, 2)).copy()
+    info, eye = scenes.random_info(p, 5), np.broadcast_to(np.eye(2), (p["nobs"], 2, 2)).copy()
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         r = m.cons(p["x0"])
@@ -128,7 +118,7 @@ def test_robust_eval_tile_shapes(ba, gpu_ok, shape):
             w, f = m.robust_weights(p["x0"], loss, 1.0)
             for what, (got_w, got_f), (w_ref, f_ref) in (
                     ("plain", (w, f), weights_cost(r, loss, 1.0)),
-                    ("information", m.robust_weights(p["x0"], loss, 1.0, obs_info=info), ir.weights_cost(r, info, loss, 1.0))):
+                    ("information", m.robust_weights(p["x0"], loss, 1.0, obs_info=info), weights_cost(r, loss, 1.0, info))):
                 e, ef = float(np.max(np.abs(got_w - w_ref) / w_ref)), abs(got_f - f_ref) / f_ref
                 print(f"nobs {p['nobs']}, {loss}, {what}: weights {e:.3e}, cost {ef:.3e}")
                 assert e <= 1e-14, f"{loss}, {what}: weights, max relative error {e:.3e}"
@@ -154,13 +144,14 @@ def test_robust_step_vs_dense_numpy(ba, orc, small_prob, gpu_ok, loss, c):
     try:
         for lam, tol in STEP_TOL.items():
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss=loss, f_scale=c)
-            d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, loss, c)
+            ref = step(orc, p, p["x0"], lam, loss=loss, c=c)
+            d_ref, half_ref, g_ref = ref["delta"], ref["model"], ref["grad"]
             e = rel_err(d, d_ref)
             assert e <= tol, f"{loss}, lambda {lam}: |d - d_ref| / |d_ref| = {e:.3e} (limit {tol:.0e})"
             assert abs(half - half_ref) <= 1e-9 * half_ref, f"{loss}, lambda {lam}: model {half!r} vs {half_ref!r}"
             assert np.max(np.abs(jtr - g_ref)) <= 1e-12 * np.max(np.abs(g_ref)), f"{loss}, lambda {lam}: J~'r~"
         lam = 1.0
-        d_ref, _, _ = _ref_step(orc, p, p["x0"], lam, loss, c)
+        d_ref = step(orc, p, p["x0"], lam, loss=loss, c=c)["delta"]
         dp = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), loss=loss, f_scale=c)[0]
         assert rel_err(dp, d_ref) <= 1e-8, f"{loss}: PCG step {rel_err(dp, d_ref):.3e}"
         d32 = ba.lm_step(m, p["x0"], lam, facto_type=np.float32, loss=loss, f_scale=c)[0]
@@ -193,7 +184,8 @@ def test_robust_step_block_sparse_schedule(ba, orc, gpu_ok):
 
     (d, half, jtr), pat = env("BA_SPARSE_S", "1", run)
     assert pat[2], "the block-sparse list schedule was not used"
-    d_ref, half_ref, g_ref = _ref_step(orc, p, p["x0"], lam, "huber", c)
+    ref = step(orc, p, p["x0"], lam, loss="huber", c=c)
+    d_ref, half_ref, g_ref = ref["delta"], ref["model"], ref["grad"]
     e = rel_err(d, d_ref)
     assert e <= 1e-10, f"block-sparse huber step: {e:.3e}"
     assert abs(half - half_ref) <= 1e-9 * half_ref
@@ -257,7 +249,7 @@ def test_robust_solve(ba, orc, small_prob, gpu_ok, loss, c, variant):
         m.close()
     f_acc = [row[1] for row in st.log if row[7]]
     assert len(f_acc) >= 2 and all(b < a for a, b in zip(f_acc, f_acc[1:])), f"accepted rows: f not strictly decreasing {f_acc}"
-    rt, Jt, _, f_ref = reweighted(orc, p, st.solution, loss, c)
+    rt, Jt, _, f_ref = linearise(orc, p, st.solution, loss=loss, c=c)
     assert abs(st.objective - f_ref) <= 1e-12 * f_ref, f"objective {st.objective!r} vs numpy {f_ref!r}"
     g = np.linalg.norm(Jt.T @ rt)
     feas = st.dual_feas if variant == 1 else st.primal_feas

@@ -1,5 +1,5 @@
 """Shared camera intrinsics of the LM solve (ba_lm_set_shared_intrinsics, include/ba_hip.h): calibration groups whose
-members share one (k1, k2, f), x = E z.  The reference is numpy (tests/helpers/shared_ref.py): the oracle's residual and Jacobian,
+members share one (k1, k2, f), x = E z.  The reference is numpy (tests/_lm_ref.py): the oracle's residual and Jacobian,
 the reweighting, mask and prior rows of tests/test_priors.py, E as a scipy sparse matrix, the dense solve over z and a dense LM
 loop over z.  Step limit everywhere: max(tol, 100 kappa eps), the rule of tests/_lm_ref.py::limit, kappa the condition number
 of the Jacobi-scaled reduced camera system over z; tol = STEP_TOL[lambda] for :LDL and PCG_TOL for pcg = (1e-12, 5000).  Model
@@ -7,19 +7,15 @@ value and gradient: the relative limits of tests/test_priors.py::test_prior_step
 model value 1e-7).  The first tests need no device; the rest run on the GPU."""
 import ctypes as C
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from _lm_ref import (PCG_TOL, STEP_TOL, arrays, attach_loopback, env, fixed_vector, jac, limit, lm_opts, loopback_world, residual,
-                     reweighted, sym)
+from _lm_ref import (PCG_TOL, STEP_TOL, bordered, centre, expansion, jac, labels, limit, lm_dense, residual, step, step_once, sym)
+from _lm_run import arrays, attach_loopback, env, fixed_vector, lm_opts, loopback_world
 from _util import bits_report, parity_record, rel_err
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
-import prior_ref as pr  # noqa: E402
-import shared_ref as sr  # noqa: E402
 
 GROUPS_A = [[1, 2, 3, 4, 5], [7, 9, 11, 12]]      # scene A: (12, 400, 1800, seed 11), one tile, n = 108
 GROUPS_B = [list(range(1, 41, 2)), [2, 4, 6]]      # scene B: (40, 400, 1800, seed 11), three tiles, the last one ragged
@@ -36,21 +32,15 @@ def _scene(ba, which):
     return _cache[which]
 
 
-def _ref(orc, p, groups, x, lam, pri=None, fixed=None, loss="linear", c=1.0, key=None):
-    """shared_ref.step at (x, lambda), computed once per key"""
-    if key is not None and key in _cache:
-        return _cache[key]
-    rt, Jt, _, _ = reweighted(orc, p, x, loss, c)
-    rows = pr.rows(x, p["ncams"], p["npnts"], fixed=fixed, **(pri or {}))
-    out = sr.step(Jt, rt, lam, rows, groups, p["ncams"], p["npnts"], fixed)
-    if key is not None:
-        _cache[key] = out
-    return out
+def _plain(ba, orc, which, lam):
+    """the step of scene `which` at x0 with its groups and no other term: shared between the tests, computed once"""
+    p, groups = _scene(ba, which)
+    return step_once(("shared", which, lam), orc, p, p["x0"], lam, groups=groups)
 
 
 def _member_rows(p, groups):
     """(first, others): the x indices of (k1, k2, f) of every group's first member and of its other members"""
-    lab = sr.labels(groups, p["ncams"])
+    lab = labels(groups, p["ncams"])
     np3 = 3 * p["npnts"]
     first, others = [], []
     for g in range(1, lab.max() + 1):
@@ -150,13 +140,13 @@ def test_make_problem_default_is_unchanged_and_groups_share(ba, small_prob):
 
 @pytest.mark.parametrize("which", ["A", "B"])
 def test_reference_bordered_solve_agrees_with_dense_z(ba, orc, which):
-    """shared_ref.bordered -- the algebra the device runs -- against shared_ref.step's dense solve over z, camera part of the
+    """_lm_ref.bordered -- the algebra the device runs -- against _lm_ref.step's dense solve over z, camera part of the
     step, at every lambda of STEP_TOL, within max(STEP_TOL[lambda], 100 kappa eps)"""
     p, groups = _scene(ba, which)
     np3 = 3 * p["npnts"]
     for lam, tol in STEP_TOL.items():
-        ref = _ref(orc, p, groups, p["x0"], lam, key=(which, lam))
-        a = sr.bordered(ref["H"], ref["g"], lam, groups, p["ncams"], p["npnts"])
+        ref = _plain(ba, orc, which, lam)
+        a = bordered(ref["H"], ref["g"], lam, groups, p["ncams"], p["npnts"])
         e, lim = rel_err(a, ref["delta"][np3:]), limit(tol, ref["kappa"])
         print(f"bordered[{which}] lambda {lam:g}: kappa {ref['kappa']:.3e}  error {e:.3e} (limit {lim:.1e})")
         assert e <= lim
@@ -170,7 +160,7 @@ def test_shared_step_vs_dense_numpy(ba, orc, gpu_ok, which):
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam, tol in STEP_TOL.items():
-            ref = _ref(orc, p, groups, p["x0"], lam, key=(which, lam))
+            ref = _plain(ba, orc, which, lam)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, shared_intrinsics=groups)
             dp, halfp, jtrp, its = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), shared_intrinsics=groups)
             e, ep = rel_err(d, ref["delta"]), rel_err(dp, ref["delta"])
@@ -269,7 +259,7 @@ def test_shared_step_with_fixed_intrinsics(ba, orc, gpu_ok):
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam, tol in STEP_TOL.items():
-            ref = _ref(orc, p, every, x, lam, fixed=fixed)
+            ref = step(orc, p, x, lam, groups=every, fixed=fixed)
             unshared = ba.lm_step(m, x, lam, **mask)
             for kw, t in (({}, tol), ({"pcg": (1e-12, 5000)}, PCG_TOL)):
                 d, half, jtr = ba.lm_step(m, x, lam, shared_intrinsics=every, **mask, **kw)[:3]
@@ -297,7 +287,7 @@ def test_shared_step_with_huber(ba, orc, gpu_ok):
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam, tol in STEP_TOL.items():
-            ref = _ref(orc, p, groups, p["x0"], lam, loss="huber", c=1.0)
+            ref = step(orc, p, p["x0"], lam, groups=groups, loss="huber", c=1.0)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, loss="huber", f_scale=1.0, shared_intrinsics=groups)
             e, lim = rel_err(d, ref["delta"]), limit(tol, ref["kappa"])
             em = abs(half - ref["model"]) / ref["model"]
@@ -306,7 +296,7 @@ def test_shared_step_with_huber(ba, orc, gpu_ok):
             parity_record(f"shared_huber[{lam:g}]", kappa=ref["kappa"], ldl=e, ldl_limit=lim, model=em, jtr=eg)
             assert e <= lim and em <= 1e-10 and eg <= 1e-12
             _check_conventions(p, groups, d, jtr, ref["g"])
-        assert rel_err(d, _ref(orc, p, groups, p["x0"], 1e-2, key=("A", 1e-2))["delta"]) > 1e-6  # (not the linear step)
+        assert rel_err(d, _plain(ba, orc, "A", 1e-2)["delta"]) > 1e-6  # (not the linear step)
     finally:
         m.close()
 
@@ -324,11 +314,11 @@ def test_shared_step_with_priors(ba, orc, gpu_ok):
     info = sym((Bm @ Bm.T + 9 * np.eye(9)) / (0.01 * scale[:, None] * 0.01 * scale[None, :]))
     cidx = np.array([12, 31])
     pri = dict(camera_priors=(np.array([7]), cams[6][None] * (1 + 1e-3), info[None]),
-               centre_priors=(cidx, np.stack([pr.centre(cams[i - 1]) for i in cidx]) + 0.01, np.full((2, 3), 0.01)))
+               centre_priors=(cidx, np.stack([centre(cams[i - 1]) for i in cidx]) + 0.01, np.full((2, 3), 0.01)))
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
         for lam, tol in STEP_TOL.items():
-            ref = _ref(orc, p, groups, p["x0"], lam, pri=pri)
+            ref = step(orc, p, p["x0"], lam, groups=groups, priors=pri)
             d, half, jtr = ba.lm_step(m, p["x0"], lam, shared_intrinsics=groups, **pri)
             dp, halfp, jtrp, its = ba.lm_step(m, p["x0"], lam, pcg=(1e-12, 5000), shared_intrinsics=groups, **pri)
             e, ep = rel_err(d, ref["delta"]), rel_err(dp, ref["delta"])
@@ -356,7 +346,7 @@ def test_shared_step_block_sparse_schedule(ba, orc, gpu_ok):
     p = dict(p)
     p["x0"] = ba.tie_intrinsics(p["x0"], p["npnts"], groups)
     lam = 1.0
-    ref = _ref(orc, p, groups, p["x0"], lam)
+    ref = step(orc, p, p["x0"], lam, groups=groups)
     lim = limit(STEP_TOL[lam], ref["kappa"])
     for flag in ("1", "0"):
         def run():
@@ -387,13 +377,13 @@ def _fun(orc, p):
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant,facto", [(1, "LDL"), (0, "LDL"), (1, "PCG"), (0, "PCG")])
 def test_shared_solve(ba, orc, gpu_ok, variant, facto):
-    """Scene A from the tied x0, oatol = ortol = 0: status and iteration count of shared_ref.lm_dense_z (the dense loop over z
+    """Scene A from the tied x0, oatol = ortol = 0: status and iteration count of _lm_ref.lm_dense (the dense loop over z
     with this variant's controller); objective and dual_feas against numpy at the returned x with the limits of
     tests/test_priors.py::test_prior_solve (1e-12, 1e-10), dual_feas being |E'g|; members bit-equal in the solution"""
     p, groups = _scene(ba, "A")
     key = ("solve", variant)
     if key not in _cache:
-        _cache[key] = sr.lm_dense_z(_fun(orc, p), p["x0"], groups, p["ncams"], p["npnts"], variant=variant)
+        _cache[key] = lm_dense(_fun(orc, p), p["x0"], groups=groups, ncams=p["ncams"], npnts=p["npnts"], variant=variant)
     x_ref, status_ref, it_ref, f_loop, g_loop = _cache[key]
     m = ba.BALNLPModel(arrays=arrays(p))
     try:
@@ -402,7 +392,7 @@ def test_shared_solve(ba, orc, gpu_ok, variant, facto):
         st = ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), *args, oatol=0.0, ortol=0.0, shared_intrinsics=groups, **kw)
     finally:
         m.close()
-    E, keep = sr.expansion(groups, p["ncams"], p["npnts"])
+    E, keep = expansion(groups, p["ncams"], p["npnts"])
     f, g, _, _ = _fun(orc, p)(st.solution)
     g_ref = float(np.linalg.norm(E.T @ g))
     feas = st.dual_feas if variant == 1 else st.primal_feas

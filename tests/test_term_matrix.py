@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _lm_ref import arrays, attach_loopback, lm_opts, loopback_world
+from _lm_run import arrays, attach_loopback, lm_opts, loopback_world
 from _util import bits_report
 
 CONDITIONS = ("linesearch", "x_f32", "facto_f32", "facto_f16", "normalize", "comm", "covariance")
