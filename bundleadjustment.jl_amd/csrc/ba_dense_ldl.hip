@@ -1519,56 +1519,90 @@ __device__ inline T wsum(T v) {
   return v;
 }
 
-// forward step k: y_k = Linv_k b_k (every workgroup recomputes it; block 0 stores it), then b_i -= L_ik y_k, i > k.
-template <typename T>
-__global__ __launch_bounds__(256) void k_fwd_step(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                   T *__restrict__ b, T *__restrict__ y, int k, const int *__restrict__ rows = nullptr,
-                                                   const T *__restrict__ Lcol = nullptr) {
+// The two tile-vector products of the sweeps, 256 threads on one 128 x 128 tile M.
+// Row-wise (forward): out[row] = sum_c M[row][c] v[c] (SUB: out[row] -= ...).  Wave wv takes rows 32 wv .. 32 wv + 31, a lane holds
+// v0 = v[2 lane], v1 = v[2 lane + 1], wsum reduces, lane 0 stores.
+template <typename T, bool SUB>
+__device__ __forceinline__ void tile_matvec(const T *__restrict__ M, const T v0, const T v1, T *__restrict__ out) {
   BA_VT
-  __shared__ T yk[NB];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const T *Lk = Linv + (int64_t)k * NB * NB;
-  const d2 bk = *reinterpret_cast<const d2 *>(b + (int64_t)k * NB + 2 * lane);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int rr = 0; rr < 32; rr++) {
     int row = wv * 32 + rr;
-    d2 l = *reinterpret_cast<const d2 *>(Lk + row * NB + 2 * lane);
-    T s = wsum(l.x * bk.x + l.y * bk.y);
-    if (lane == 0) yk[row] = s;
+    d2 l = *reinterpret_cast<const d2 *>(M + row * NB + 2 * lane);
+    T s = wsum(l.x * v0 + l.y * v1);
+    if (lane == 0) {
+      if (SUB) out[row] -= s;
+      else out[row] = s;
+    }
   }
+}
+// Transposed (backward): part[half][c] = sum over this half's 64 rows of M[r][c] v[r]; the caller adds the two halves behind a barrier.
+template <typename T>
+__device__ __forceinline__ void tile_matvec_t(const T *__restrict__ M, const T *v, T (*part)[NB]) {
+  const int c = threadIdx.x & (NB - 1), half = threadIdx.x >> 7;
+  T s = 0;
+  for (int r = half * 64; r < half * 64 + 64; r++) s += M[r * NB + c] * v[r];
+  part[half][c] = s;
+}
+
+// The steps of both sweeps take their right-hand side from blockIdx.y, at b + blockIdx.y ld (y and x likewise): a single one is
+// grid.y = 1, and m of them (shared intrinsics, DESIGN §5g: the 3G border columns; ba_dense_ldl_solve_multi) are still a chain of
+// nt short launches each way whatever m is.  One form for the dense and the block-sparse layout: workgroup x > 0 owns tile row
+// k + x (forward) or tile column cols[x - 1] or x - 1 (backward), and leaves at once -- before any barrier, the whole workgroup
+// -- when the pattern has no such tile (it holds zeros).  The tile look-up is the first thing a workgroup does, and the optional
+// arguments are tested so that the plain form pays no scalar load for them: as many dependent rounds of scalar loads ahead of
+// the first vector load as a kernel without the options has (one more round was +0.18 us per launch, +0.6 % of a 3-column sweep;
+// ld is an int so that the arguments fill 64 bytes: profiles/ldl_sweeps_one_step_parent_vs_new.txt).
+//
+// forward step k: y_k = Linv_k b_k (every workgroup recomputes it; block 0 stores it), then b_i -= L_ik y_k, i > k.
+// Lcol (per-rank ownership of S): the tiles of column k come from the panel buffer, rows[x - 1] (null: k + x) being workgroup x's.
+template <typename T>
+__global__ __launch_bounds__(256) void k_fwd_step(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
+                                                   T *__restrict__ b, T *__restrict__ y, int k, int ld = 0,
+                                                   const int *__restrict__ rows = nullptr, const T *__restrict__ Lcol = nullptr) {
+  BA_VT
+  __shared__ T yk[NB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  int i = k + blockIdx.x;
+  int64_t tik = 0;
+  if (Lcol) {
+    if (rows && blockIdx.x) i = rows[blockIdx.x - 1];
+  } else if (blockIdx.x) {
+    tik = tix(co, i, k);
+  }
+  if (tik < 0) return;
+  b += (int64_t)blockIdx.y * ld;
+  y += (int64_t)blockIdx.y * ld;
+  const d2 bk = *reinterpret_cast<const d2 *>(b + (int64_t)k * NB + 2 * lane);
+  tile_matvec<T, false>(Linv + (int64_t)k * NB * NB, bk.x, bk.y, yk);
   __syncthreads();
   if (blockIdx.x == 0) {
     if (tid < NB) y[(int64_t)k * NB + tid] = yk[tid];
     return;
   }
-  const int i = rows ? rows[blockIdx.x - 1] : k + blockIdx.x;
-  const T *Lik = Lcol ? Lcol + (int64_t)i * NB * NB : S + tix(co, i, k) * NB * NB;  // Lcol: panel buffer (per-rank ownership of S)
-  const T y0 = yk[2 * lane], y1 = yk[2 * lane + 1];
-  for (int rr = 0; rr < 32; rr++) {
-    int row = wv * 32 + rr;
-    d2 l = *reinterpret_cast<const d2 *>(Lik + row * NB + 2 * lane);
-    T s = wsum(l.x * y0 + l.y * y1);
-    if (lane == 0) b[(int64_t)i * NB + row] -= s;
-  }
+  tile_matvec<T, true>(Lcol ? Lcol + (int64_t)i * NB * NB : S + tik * NB * NB, yk[2 * lane], yk[2 * lane + 1], b + (int64_t)i * NB);
 }
 
 // backward step k: x_k = Linv_k' z_k with z = y / D (every workgroup recomputes it; block 0 stores it into b_k),
 // then y_j -= D_j (L_kj' x_k) ... expressed on z: z_j -= L_kj' x_k, i.e. y_j -= D_j * (L_kj' x_k), j < k.
 template <typename T>
 __global__ __launch_bounds__(256) void k_bwd_step(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                   const T *__restrict__ D, T *__restrict__ y,
-                                                   T *__restrict__ x, int k, const int *__restrict__ cols = nullptr) {
-  BA_VT
+                                                   const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k, int ld = 0,
+                                                   const int *__restrict__ cols = nullptr) {
   __shared__ T zk[NB], xk[NB], part[2][NB];
   const int tid = threadIdx.x;
-  const int c = tid & (NB - 1), half = tid >> 7;
+  int j = (int)blockIdx.x - 1;  // 0 .. k-1 (block-sparse S: the tile columns of row k's pattern)
+  int64_t tkj = 0;
+  if (blockIdx.x) {
+    if (cols) j = cols[blockIdx.x - 1];
+    tkj = tix(co, k, j);
+  }
+  if (tkj < 0) return;
+  y += (int64_t)blockIdx.y * ld;
+  x += (int64_t)blockIdx.y * ld;
   if (tid < NB) zk[tid] = y[(int64_t)k * NB + tid] / D[(int64_t)k * NB + tid];
   __syncthreads();
-  {
-    const T *Lk = Linv + (int64_t)k * NB * NB;
-    T s = 0;
-    for (int r = half * 64; r < half * 64 + 64; r++) s += Lk[r * NB + c] * zk[r];
-    part[half][c] = s;
-  }
+  tile_matvec_t(Linv + (int64_t)k * NB * NB, zk, part);
   __syncthreads();
   if (tid < NB) xk[tid] = part[0][tid] + part[1][tid];
   __syncthreads();
@@ -1576,11 +1610,7 @@ __global__ __launch_bounds__(256) void k_bwd_step(const T *__restrict__ S, const
     if (tid < NB) x[(int64_t)k * NB + tid] = xk[tid];
     return;
   }
-  const int j = cols ? cols[blockIdx.x - 1] : blockIdx.x - 1;  // 0 .. k-1 (block-sparse S: the tile columns of row k's pattern)
-  const T *Lkj = S + tix(co, k, j) * NB * NB;
-  T s = 0;
-  for (int r = half * 64; r < half * 64 + 64; r++) s += Lkj[r * NB + c] * xk[r];
-  part[half][c] = s;
+  tile_matvec_t(S + tkj * NB * NB, xk, part);
   __syncthreads();
   if (tid < NB) y[(int64_t)j * NB + tid] -= D[(int64_t)j * NB + tid] * (part[0][tid] + part[1][tid]);
 }
@@ -1595,11 +1625,6 @@ __device__ __forceinline__ void bwd_pair_body(const T *__restrict__ S, const int
   __shared__ T zk[NB], xk[NB], xk1[NB], part[2][NB];
   const int tid = threadIdx.x;
   const int c = tid & (NB - 1), half = tid >> 7;
-  auto matvec_t = [&](const T *M, const T *v) {  // part[half][c] = sum over this half's 64 rows of M[r][c] v[r]
-    T s = 0;
-    for (int r = half * 64; r < half * 64 + 64; r++) s += M[r * NB + c] * v[r];
-    part[half][c] = s;
-  };
   // the tile indices first (compressed block-sparse storage: a tile outside the pattern does not exist): their table
   // look-ups are dependent global loads, which left where they are used put three memory round trips on the chain of a
   // launch that has nothing to hide them behind (19 -> 32 us per launch on Venice when the tables came in)
@@ -1607,11 +1632,11 @@ __device__ __forceinline__ void bwd_pair_body(const T *__restrict__ S, const int
   const int64_t tkk = tix(co, k, k - 1), tkj = tix(co, k, j), tk1j = tix(co, k - 1, j);
   if (tid < NB) zk[tid] = y[(int64_t)k * NB + tid] / D[(int64_t)k * NB + tid];
   __syncthreads();
-  matvec_t(Linv + (int64_t)k * NB * NB, zk);
+  tile_matvec_t(Linv + (int64_t)k * NB * NB, zk, part);
   __syncthreads();
   if (tid < NB) xk[tid] = part[0][tid] + part[1][tid];
   __syncthreads();
-  if (tkk >= 0) matvec_t(S + tkk * NB * NB, xk);  // L_{k,k-1}' x_k
+  if (tkk >= 0) tile_matvec_t(S + tkk * NB * NB, xk, part);  // L_{k,k-1}' x_k
   else part[half][c] = 0;
   __syncthreads();
   if (tid < NB) {
@@ -1619,7 +1644,7 @@ __device__ __forceinline__ void bwd_pair_body(const T *__restrict__ S, const int
     zk[tid] = (y[(int64_t)(k - 1) * NB + tid] - d * (part[0][tid] + part[1][tid])) / d;
   }
   __syncthreads();
-  matvec_t(Linv + (int64_t)(k - 1) * NB * NB, zk);
+  tile_matvec_t(Linv + (int64_t)(k - 1) * NB * NB, zk, part);
   __syncthreads();
   if (tid < NB) xk1[tid] = part[0][tid] + part[1][tid];
   __syncthreads();
@@ -1632,15 +1657,17 @@ __device__ __forceinline__ void bwd_pair_body(const T *__restrict__ S, const int
   }
   // cols (block-sparse S): the tile columns in the pattern of row k or row k-1 (a tile outside the pattern holds zeros)
   const T *Lkj = S + tkj * NB * NB, *Lk1j = S + tk1j * NB * NB;
-  T s = 0;
-  if (tkj >= 0 && tk1j >= 0) {
+  if (tkj >= 0 && tk1j >= 0) {  // both in one loop: its own order of summation
+    T s = 0;
     for (int r = half * 64; r < half * 64 + 64; r++) s += Lkj[r * NB + c] * xk[r] + Lk1j[r * NB + c] * xk1[r];
+    part[half][c] = s;
   } else if (tkj >= 0) {
-    for (int r = half * 64; r < half * 64 + 64; r++) s += Lkj[r * NB + c] * xk[r];
+    tile_matvec_t(Lkj, xk, part);
   } else if (tk1j >= 0) {
-    for (int r = half * 64; r < half * 64 + 64; r++) s += Lk1j[r * NB + c] * xk1[r];
+    tile_matvec_t(Lk1j, xk1, part);
+  } else {
+    part[half][c] = 0;
   }
-  part[half][c] = s;
   __syncthreads();
   if (tid < NB) y[(int64_t)j * NB + tid] -= D[(int64_t)j * NB + tid] * (part[0][tid] + part[1][tid]);
 }
@@ -1660,79 +1687,6 @@ __global__ __launch_bounds__(256) void k_bwd_pair2(const T *__restrict__ S, cons
                                                     const int *__restrict__ cols_a, int na, int kc, const int *__restrict__ cols_c) {
   const bool second = (int)blockIdx.x >= na;
   bwd_pair_body<T>(S, co, Linv, D, y, x, second ? kc : ka, second ? cols_c : cols_a, (int)blockIdx.x - (second ? na : 0));
-}
-
-
-// The sweeps over m right-hand sides at once (shared intrinsics, DESIGN §5g: the 3G border columns; ba_dense_ldl_solve_multi):
-// column-blocked twins of k_fwd_step / k_bwd_step, right-hand side blockIdx.y at b + blockIdx.y ld.  A chain of nt short launches
-// each way whatever m is -- which is why they exist.  One form for the dense and the block-sparse layout: workgroup x > 0 owns
-// tile row k + x (forward) or tile column x - 1 (backward) and leaves at once when the pattern has no such tile (it holds zeros).
-template <typename T>
-__global__ __launch_bounds__(256) void k_fwd_step_multi(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                         T *__restrict__ b, T *__restrict__ y, int k, int64_t ld) {
-  BA_VT
-  __shared__ T yk[NB];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int i = k + blockIdx.x;
-  const int64_t tik = blockIdx.x == 0 ? 0 : tix(co, i, k);
-  if (tik < 0) return;
-  b += (int64_t)blockIdx.y * ld;
-  y += (int64_t)blockIdx.y * ld;
-  const T *Lk = Linv + (int64_t)k * NB * NB;
-  const d2 bk = *reinterpret_cast<const d2 *>(b + (int64_t)k * NB + 2 * lane);
-  for (int rr = 0; rr < 32; rr++) {
-    int row = wv * 32 + rr;
-    d2 l = *reinterpret_cast<const d2 *>(Lk + row * NB + 2 * lane);
-    T s = wsum(l.x * bk.x + l.y * bk.y);
-    if (lane == 0) yk[row] = s;
-  }
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    if (tid < NB) y[(int64_t)k * NB + tid] = yk[tid];
-    return;
-  }
-  const T *Lik = S + tik * NB * NB;
-  const T y0 = yk[2 * lane], y1 = yk[2 * lane + 1];
-  for (int rr = 0; rr < 32; rr++) {
-    int row = wv * 32 + rr;
-    d2 l = *reinterpret_cast<const d2 *>(Lik + row * NB + 2 * lane);
-    T s = wsum(l.x * y0 + l.y * y1);
-    if (lane == 0) b[(int64_t)i * NB + row] -= s;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_bwd_step_multi(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                         const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k, int64_t ld) {
-  __shared__ T zk[NB], xk[NB], part[2][NB];
-  const int tid = threadIdx.x;
-  const int c = tid & (NB - 1), half = tid >> 7;
-  const int j = (int)blockIdx.x - 1;  // 0 .. k-1
-  const int64_t tkj = blockIdx.x == 0 ? 0 : tix(co, k, j);
-  if (tkj < 0) return;
-  y += (int64_t)blockIdx.y * ld;
-  x += (int64_t)blockIdx.y * ld;
-  if (tid < NB) zk[tid] = y[(int64_t)k * NB + tid] / D[(int64_t)k * NB + tid];
-  __syncthreads();
-  {
-    const T *Lk = Linv + (int64_t)k * NB * NB;
-    T s = 0;
-    for (int r = half * 64; r < half * 64 + 64; r++) s += Lk[r * NB + c] * zk[r];
-    part[half][c] = s;
-  }
-  __syncthreads();
-  if (tid < NB) xk[tid] = part[0][tid] + part[1][tid];
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    if (tid < NB) x[(int64_t)k * NB + tid] = xk[tid];
-    return;
-  }
-  const T *Lkj = S + tkj * NB * NB;
-  T s = 0;
-  for (int r = half * 64; r < half * 64 + 64; r++) s += Lkj[r * NB + c] * xk[r];
-  part[half][c] = s;
-  __syncthreads();
-  if (tid < NB) y[(int64_t)j * NB + tid] -= D[(int64_t)j * NB + tid] * (part[0][tid] + part[1][tid]);
 }
 
 }  // namespace
@@ -2496,9 +2450,10 @@ static int dist_forward_pair(DenseLDLT<T> *w, int k, T *V0, T *V1, T *d_b, hipSt
   if (!d_b) return BA_OK;
   T *y = w->D + w->nt * NB;
   const PairRows r = pair_rows(w, k / 2);
-  hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, r.rows1, (const T *)w->L_of(V0));
+  hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, 0, r.rows1,
+                     (const T *)w->L_of(V0));
   if (k + 1 < (int)w->nt)
-    hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c2), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, r.rows2,
+    hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c2), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, 0, r.rows2,
                        (const T *)w->L_of(V1));
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
@@ -2616,13 +2571,10 @@ __global__ __launch_bounds__(256) void k_bwd_col_part(const T *__restrict__ S, c
   // part[(c - k) nt + i][:] = L_ic' x_i
   __shared__ T xi[NB], red[2][NB];
   const int c = k + (blockIdx.x & 1), i = rows ? rows[blockIdx.x >> 1] : k + 2 + (blockIdx.x >> 1);
-  const int tid = threadIdx.x, col = tid & (NB - 1), half = tid >> 7;
+  const int tid = threadIdx.x;
   if (tid < NB) xi[tid] = x[(int64_t)i * NB + tid];
   __syncthreads();
-  const T *L = S + tix(co, i, c) * NB * NB;
-  T s = 0;
-  for (int r = half * 64; r < half * 64 + 64; r++) s += L[r * NB + col] * xi[r];
-  red[half][col] = s;
+  tile_matvec_t(S + tix(co, i, c) * NB * NB, xi, red);
   __syncthreads();
   if (tid < NB) part[((int64_t)(c - k) * nt + i) * NB + tid] = red[0][tid] + red[1][tid];
 }
@@ -2634,13 +2586,8 @@ __global__ __launch_bounds__(256) void k_bwd_col_final(const T *__restrict__ S, 
                                                         int nrows = 0) {
   // rows / nrows: the tile rows below the pair that its pattern holds (block-sparse S); null: k + 2 .. nt - 1
   __shared__ T z[NB], xk1[NB], red[2][NB];
-  const int tid = threadIdx.x, col = tid & (NB - 1), half = tid >> 7;
+  const int tid = threadIdx.x;
   const bool two = k + 1 < nt;
-  auto matvec_t = [&](const T *M, const T *v) {  // red[half][col] = sum over this half's 64 rows of M[r][col] v[r]
-    T s = 0;
-    for (int r = half * 64; r < half * 64 + 64; r++) s += M[r * NB + col] * v[r];
-    red[half][col] = s;
-  };
   if (two) {  // x_{k+1} = Linv_{k+1}' (y_{k+1} / D_{k+1} - sum_{i > k+1} L_{i,k+1}' x_i)
     if (tid < NB) {
       T s = 0;
@@ -2651,14 +2598,14 @@ __global__ __launch_bounds__(256) void k_bwd_col_final(const T *__restrict__ S, 
       z[tid] = y[(int64_t)(k + 1) * NB + tid] / D[(int64_t)(k + 1) * NB + tid] - s;
     }
     __syncthreads();
-    matvec_t(Linv + (int64_t)(k + 1) * NB * NB, z);
+    tile_matvec_t(Linv + (int64_t)(k + 1) * NB * NB, z, red);
     __syncthreads();
     if (tid < NB) {
       xk1[tid] = red[0][tid] + red[1][tid];
       x[(int64_t)(k + 1) * NB + tid] = xk1[tid];
     }
     __syncthreads();
-    matvec_t(S + tix(co, k + 1, k) * NB * NB, xk1);  // the coupling tile L_{k+1,k}' x_{k+1}
+    tile_matvec_t(S + tix(co, k + 1, k) * NB * NB, xk1, red);  // the coupling tile L_{k+1,k}' x_{k+1}
     __syncthreads();
   }
   if (tid < NB) {
@@ -2670,7 +2617,7 @@ __global__ __launch_bounds__(256) void k_bwd_col_final(const T *__restrict__ S, 
     z[tid] = y[(int64_t)k * NB + tid] / D[(int64_t)k * NB + tid] - s;
   }
   __syncthreads();
-  matvec_t(Linv + (int64_t)k * NB * NB, z);
+  tile_matvec_t(Linv + (int64_t)k * NB * NB, z, red);
   __syncthreads();
   if (tid < NB) x[(int64_t)k * NB + tid] = red[0][tid] + red[1][tid];
 }
@@ -2727,7 +2674,8 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
       const int k = 2 * q + 1;
       if (k >= nt) {
         const int c0 = pat->lcol_ptr[(size_t)(nt - 1)], c1 = pat->lcol_ptr[(size_t)nt];
-        hipLaunchKernelGGL(k_bwd_step<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, nt - 1, w->lcol + c0);
+        hipLaunchKernelGGL(k_bwd_step<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, nt - 1,
+                           0, w->lcol + c0);
       } else {
         const int c0 = pat->lpair_ptr[(size_t)q], c1 = pat->lpair_ptr[(size_t)q + 1];
         hipLaunchKernelGGL(k_bwd_pair<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k, w->lpair + c0);
@@ -2763,30 +2711,34 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
   return BA_OK;
 }
 
-// m right-hand sides through the factor at once (see k_fwd_step_multi): column c at d_B + c ld, overwritten by its solution
+// m right-hand sides through the factor at once (see k_fwd_step): column c at d_B + c ld, overwritten by its solution
 template <typename T>
 int dense_ldl_solve_multi(ba_problem *p, DenseLDLT<T> *w, T *d_B, int64_t ld, int m, T *d_y, hipStream_t st) {
   const int nt = (int)w->nt;
   if (m <= 0) return BA_OK;
-  if (w->own_only || p->comm.active() || ld < w->n) {
+  if (w->own_only || p->comm.active() || ld < w->n || ld > INT32_MAX) {
     ba_set_error("multi-right-hand-side solve: one rank holding all of S, column stride >= the padded order");
     return BA_ERR_ARG;
   }
   ProfScope ps(p, PC_SHARED_SWEEP, st);
   for (int k = 0; k < nt; k++)
-    hipLaunchKernelGGL(k_fwd_step_multi<T>, dim3(nt - k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_B, d_y, k, ld);
+    hipLaunchKernelGGL(k_fwd_step<T>, dim3(nt - k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_B, d_y, k, (int)ld);
   for (int k = nt - 1; k >= 0; k--)
-    hipLaunchKernelGGL(k_bwd_step_multi<T>, dim3(1 + k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, d_y, d_B, k, ld);
+    hipLaunchKernelGGL(k_bwd_step<T>, dim3(1 + k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, d_y, d_B, k, (int)ld);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
 // ---- C ABI: standalone dense solve (tests, roofline measurement) --------------------------------------------------------
-template <typename T>
-static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x,
-                            double *factor_ms) {
-  if (n <= 0 || !a_lower_rowmajor || !b || !x) {
-    ba_set_error("ba_dense_ldl_solve: bad argument");
+// The driver under the three entry points: A (row-major, lower triangle read) into tiles, a ragged last tile padded with the
+// identity; B, X: n x nrhs column-major, padded to column stride w.n on the device.  rhs_rides: the forward substitution of
+// the (single) right-hand side rides along with the factorisation.  sweep(&tmp, &w, d_b, st) follows a factorisation without
+// a zero pivot and leaves the solution in d_b.
+template <typename T, typename Sweep>
+static int dense_solve_host(const char *name, int device, int64_t n, const double *a_lower_rowmajor, int nrhs, const double *B, double *X,
+                            double *factor_ms, bool rhs_rides, Sweep sweep) {
+  if (n <= 0 || nrhs <= 0 || !a_lower_rowmajor || !B || !X) {
+    ba_set_error("%s: bad argument", name);
     return BA_ERR_ARG;
   }
   BA_HIP_CHECK(hipSetDevice(device));
@@ -2803,35 +2755,36 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
       tiles[(size_t)((tix(w.hco(), ti, tj) * NB + (i - ti * NB)) * NB + (j - tj * NB))] = (T)v;
     }
   }
-  std::vector<T> bb((size_t)npad, (T)0);
-  for (int64_t i = 0; i < n; i++) bb[(size_t)i] = (T)b[i];
+  std::vector<T> bb((size_t)(npad * nrhs), (T)0);
+  for (int c = 0; c < nrhs; c++)
+    for (int64_t i = 0; i < n; i++) bb[(size_t)(c * npad + i)] = (T)B[(int64_t)c * n + i];
   DevBuf<T> d_b;
   hipStream_t st = nullptr;
   HipEvent e0, e1;
-  BA_CHECK(d_b.alloc(npad));
-  BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(T), hipMemcpyHostToDevice));
-  BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), (size_t)npad * sizeof(T), hipMemcpyHostToDevice));
+  BA_CHECK(d_b.alloc(npad * nrhs));
   BA_CHECK(e0.create());
   BA_CHECK(e1.create());
   int rc = BA_OK, zp = 0;
-  for (int attempt = 0; attempt < 2; attempt++) {  // (the forward substitution rides along with the factorisation)
+  for (int attempt = 0; attempt < 2; attempt++) {
+    BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(T), hipMemcpyHostToDevice));
+    BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), bb.size() * sizeof(T), hipMemcpyHostToDevice));
     BA_HIP_CHECK(hipEventRecord(e0, st));
-    rc = dense_ldl_factor<T>(&tmp, &w, st, d_b);
+    rc = dense_ldl_factor<T>(&tmp, &w, st, rhs_rides ? (T *)d_b : (T *)nullptr);
     BA_HIP_CHECK(hipEventRecord(e1, st));
-    if (rc == BA_OK) rc = dense_ldl_solve<T>(&tmp, &w, d_b, st, true);
     BA_HIP_CHECK(hipMemcpy(&zp, w.flag, sizeof(int), hipMemcpyDeviceToHost));
     BA_HIP_CHECK(hipDeviceSynchronize());
     if (zp != 2 || w.hoist_disabled) break;
     // a hoisted diagonal kernel gave up waiting (kernels serialised, e.g. under a counter-collecting profiler): redo in order
     w.hoist_disabled = true;
-    BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(T), hipMemcpyHostToDevice));
-    BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), (size_t)npad * sizeof(T), hipMemcpyHostToDevice));
   }
+  if (rc == BA_OK && !zp) rc = sweep(&tmp, &w, (T *)d_b, st);
+  BA_HIP_CHECK(hipDeviceSynchronize());
   float ms = 0;
   BA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
   if (factor_ms) *factor_ms = ms;
-  BA_HIP_CHECK(hipMemcpy(bb.data(), d_b, (size_t)npad * sizeof(T), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n; i++) x[i] = (double)bb[(size_t)i];
+  BA_HIP_CHECK(hipMemcpy(bb.data(), d_b, bb.size() * sizeof(T), hipMemcpyDeviceToHost));
+  for (int c = 0; c < nrhs; c++)
+    for (int64_t i = 0; i < n; i++) X[(int64_t)c * n + i] = (double)bb[(size_t)(c * npad + i)];
   if (rc == BA_OK && zp) {
     ba_set_error("dense LDL': exactly zero pivot");
     return BA_ERR_ZERO_PIVOT;
@@ -2839,73 +2792,33 @@ static int dense_solve_host(int device, int64_t n, const double *a_lower_rowmajo
   return rc;
 }
 
+// one right-hand side: its forward substitution rode along, the backward sweep follows
+template <typename T>
+static int dense_solve_single(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x, double *factor_ms) {
+  return dense_solve_host<T>("ba_dense_ldl_solve", device, n, a_lower_rowmajor, 1, b, x, factor_ms, true,
+                             [](ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st) { return dense_ldl_solve<T>(p, w, d_b, st, true); });
+}
+
 extern "C" int ba_dense_ldl_solve(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x,
                                   double *factor_ms) {
-  return dense_solve_host<double>(device, n, a_lower_rowmajor, b, x, factor_ms);
+  return dense_solve_single<double>(device, n, a_lower_rowmajor, b, x, factor_ms);
 }
 
 // same with the matrix and right-hand side rounded to Float32 and factored / solved in Float32 (facto_type = Float32)
 extern "C" int ba_dense_ldl_solve_f32(int device, int64_t n, const double *a_lower_rowmajor, const double *b, double *x,
                                       double *factor_ms) {
-  return dense_solve_host<float>(device, n, a_lower_rowmajor, b, x, factor_ms);
+  return dense_solve_single<float>(device, n, a_lower_rowmajor, b, x, factor_ms);
 }
 
 // one factorisation, then the multi-right-hand-side sweeps over all nrhs columns (B and X: n x nrhs, column-major)
 extern "C" int ba_dense_ldl_solve_multi(int device, int64_t n, const double *a_lower_rowmajor, int nrhs, const double *B, double *X,
                                         double *factor_ms) {
-  if (n <= 0 || nrhs <= 0 || !a_lower_rowmajor || !B || !X) {
-    ba_set_error("ba_dense_ldl_solve_multi: bad argument");
-    return BA_ERR_ARG;
-  }
-  BA_HIP_CHECK(hipSetDevice(device));
-  ba_problem tmp;  // only used for its (disabled) profiling slots
-  DenseLDL w;
-  BA_CHECK(dense_ldl_alloc<double>(&w, n));
-  const int64_t npad = w.n;
-  std::vector<double> tiles((size_t)dense_ldl_tiles_doubles(n), 0.0);
-  for (int64_t i = 0; i < npad; i++) {
-    const int64_t ti = i / NB;
-    for (int64_t j = 0; j <= i; j++) {
-      const int64_t tj = j / NB;
-      const double v = (i < n) ? a_lower_rowmajor[i * n + j] : (i == j ? 1.0 : 0.0);
-      tiles[(size_t)((tix(w.hco(), ti, tj) * NB + (i - ti * NB)) * NB + (j - tj * NB))] = v;
-    }
-  }
-  std::vector<double> bb((size_t)(npad * nrhs), 0.0);
-  for (int c = 0; c < nrhs; c++)
-    for (int64_t i = 0; i < n; i++) bb[(size_t)(c * npad + i)] = B[(int64_t)c * n + i];
-  DevBuf<double> d_b, d_y;
-  hipStream_t st = nullptr;
-  HipEvent e0, e1;
-  BA_CHECK(d_b.alloc(npad * nrhs));
-  BA_CHECK(d_y.alloc(npad * nrhs));
-  BA_HIP_CHECK(hipMemcpy(d_b, bb.data(), bb.size() * sizeof(double), hipMemcpyHostToDevice));
-  BA_CHECK(e0.create());
-  BA_CHECK(e1.create());
-  int rc = BA_OK, zp = 0;
-  for (int attempt = 0; attempt < 2; attempt++) {  // (as ba_dense_ldl_solve: once more in order when a hoisted kernel gave up)
-    BA_HIP_CHECK(hipMemcpy(w.S, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice));
-    BA_HIP_CHECK(hipEventRecord(e0, st));
-    rc = dense_ldl_factor<double>(&tmp, &w, st, (double *)nullptr);
-    BA_HIP_CHECK(hipEventRecord(e1, st));
-    BA_HIP_CHECK(hipMemcpy(&zp, w.flag, sizeof(int), hipMemcpyDeviceToHost));
-    BA_HIP_CHECK(hipDeviceSynchronize());
-    if (zp != 2 || w.hoist_disabled) break;
-    w.hoist_disabled = true;
-  }
-  if (rc == BA_OK && !zp) rc = dense_ldl_solve_multi<double>(&tmp, &w, d_b, npad, nrhs, d_y, st);
-  BA_HIP_CHECK(hipDeviceSynchronize());
-  float ms = 0;
-  BA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (factor_ms) *factor_ms = ms;
-  BA_HIP_CHECK(hipMemcpy(bb.data(), d_b, bb.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int c = 0; c < nrhs; c++)
-    for (int64_t i = 0; i < n; i++) X[(int64_t)c * n + i] = bb[(size_t)(c * npad + i)];
-  if (rc == BA_OK && zp) {
-    ba_set_error("dense LDL': exactly zero pivot");
-    return BA_ERR_ZERO_PIVOT;
-  }
-  return rc;
+  DevBuf<double> d_y;  // (outlives the driver's synchronisation behind the sweeps)
+  return dense_solve_host<double>("ba_dense_ldl_solve_multi", device, n, a_lower_rowmajor, nrhs, B, X, factor_ms, false,
+                                  [&](ba_problem *p, DenseLDL *w, double *d_b, hipStream_t st) {
+                                    BA_CHECK(d_y.alloc(w->n * nrhs));
+                                    return dense_ldl_solve_multi<double>(p, w, d_b, w->n, nrhs, d_y, st);
+                                  });
 }
 
 template int dense_ldl_alloc<double>(DenseLDLT<double> *, int64_t, int, int, bool, bool);

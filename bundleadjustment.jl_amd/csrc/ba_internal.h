@@ -220,7 +220,7 @@ enum ProfClass {
   PC_COV_POINTS,  // covariance: the points' 3 x 3 blocks (k_cov_points)
   PC_PRIOR,       // Gaussian priors (ba_lm_set_priors): k_prior_*_lin at a linearisation, k_prior_*_rhs per linear step, k_prior_*_step per trial step
   PC_SHARED_BORDER,  // shared intrinsics (ba_lm_set_shared_intrinsics): the border product S E_g, its E' reductions, the masking of S and the E' reductions / expansions of vectors
-  PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step_multi / k_bwd_step_multi; also ba_dense_ldl_solve_multi)
+  PC_SHARED_SWEEP,   // shared intrinsics: the multi-right-hand-side triangular sweeps (k_fwd_step / k_bwd_step with grid.y = the number of columns; also ba_dense_ldl_solve_multi)
   PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
   PC_INFO,           // per-observation information (ba_lm_set_obs_info): "k_info_whiten": k_obs_scale on a handle with it, the whitening of r and J (with the loss's reweighting)
   PC_REFINE_POINTS,  // points with the cameras held (ba_refine_points): k_cam_pre and k_refine_points

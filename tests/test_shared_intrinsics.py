@@ -206,6 +206,37 @@ def test_dense_ldl_solve_multi_vs_numpy(ba, gpu_ok, nrhs):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [128, 129, 300])
+def test_dense_ldl_solve_multi_columns_are_independent(ba, gpu_ok, n):
+    """One tile; two tiles, the second almost all padding; three with a ragged last.  Column c of the solve with four
+    right-hand sides has the bits of the solve with column c alone: one workgroup per (tile, column), the column picked by
+    the grid's y index and the stride, no atomics."""
+    rng = np.random.default_rng(n)
+    G = rng.standard_normal((n, n + 8))
+    A = G @ G.T + 0.5 * np.eye(n)
+    B = rng.standard_normal((n, 4))
+    X, _ = ba._lib.dense_ldl_solve_multi(A, B)
+    assert np.all(np.isfinite(X)) and np.linalg.norm(A @ X - B) <= 1e-8 * np.linalg.norm(B)
+    for c in range(4):
+        x, _ = ba._lib.dense_ldl_solve_multi(A, B[:, c:c + 1])
+        assert not bits_report(X[:, c], x[:, 0], f"n = {n}: column {c} of four vs alone")
+
+
+@pytest.mark.gpu
+def test_dense_ldl_solve_multi_zero_pivot(ba, gpu_ok):
+    """The zero matrix: the exception of ba_dense_ldl_solve on it, type and message; a good matrix afterwards solves."""
+    Z = np.zeros((4, 4))
+    with pytest.raises(ba.SQDException) as single:
+        ba._lib.dense_ldl_solve(Z, np.ones(4))
+    with pytest.raises(ba.SQDException) as multi:
+        ba._lib.dense_ldl_solve_multi(Z, np.ones((4, 1)))
+    assert type(multi.value) is type(single.value) and str(multi.value) == str(single.value)
+    assert "zero pivot" in str(multi.value)
+    X, _ = ba._lib.dense_ldl_solve_multi(np.diag([1.0, 2.0, 4.0, 8.0]), np.ones((4, 1)))
+    assert np.array_equal(X[:, 0], [1.0, 0.5, 0.25, 0.125])
+
+
+@pytest.mark.gpu
 def test_no_grouping_paths_give_the_plain_bits(ba, gpu_ok):
     """all labels 0, None and groups of one camera run the plain path: delta, model and jtr bit-identical to the call without
     the keyword; after a shared step and a clear the plain bits are back, for the direct and the PCG entry"""
