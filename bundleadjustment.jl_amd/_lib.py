@@ -65,6 +65,7 @@ SYMBOLS = [
     "ba_lm_set_shared_intrinsics", "ba_lm_get_shared_intrinsics", "ba_dense_ldl_solve_multi",
     "ba_lm_set_obs_info", "ba_lm_get_obs_info",
     "ba_refine_points", "ba_refine_points_dev",
+    "ba_refine_cameras", "ba_refine_cameras_dev",
 ]
 
 _lib = None
@@ -140,6 +141,8 @@ def lib():
     L.ba_lm_get_obs_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.ba_refine_points.argtypes = [vp, vp, C.c_int, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int)]
     L.ba_refine_points_dev.argtypes = [vp, vp, C.c_int, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
+    L.ba_refine_cameras.argtypes = [vp, vp, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int)]
+    L.ba_refine_cameras_dev.argtypes = [vp, vp, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
     _lib = L
     return L
 
@@ -527,7 +530,8 @@ def get_obs_info(handle):
     return n.value, z.value
 
 
-# states of ba_refine_points (BA_PT_*): the low bits of a point's status; BA_PT_BEHIND is OR-ed into it
+# states of ba_refine_points and ba_refine_cameras (BA_PT_*): the low bits of a point's or camera's status; BA_PT_BEHIND is OR-ed
+# into it
 POINT_STATES = ("converged", "stalled", "max_iter", "fixed", "degenerate", "nonfinite")
 POINT_BEHIND = 0x80
 

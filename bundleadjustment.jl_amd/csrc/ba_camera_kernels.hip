@@ -1,0 +1,457 @@
+// Cameras with the points held (ba_refine_cameras): a per-camera Marquardt iteration on the handle's objective
+// restricted to one camera.  gfx950 only.
+//
+// With every point entry of x held, camera c is an independent problem in at most 9 unknowns:
+//   f_c(C) = sum_{o in obs(c)} 1/2 c^2 rho(r^_o' r^_o / c^2) + 1/2 (C - mu)' Lambda_cam (C - mu)
+//            + 1/2 (c(C) - mu')' Lambda_ctr (c(C) - mu')
+// (rho, c: ba_lm_set_loss; r^ = L'r: ba_lm_set_obs_info; the second term for a camera with a camera prior, the third for one with
+// a centre prior, c(C) = -R(r)'t).  ONE launch runs the whole refinement: the iteration loop is inside k_refine_cameras.  The
+// residual and the camera columns of the Jacobian are the model's own device functions (ba_model_dev.h): jac_block is inlined
+// and only its columns 3..11 are used; the centre and its Jacobian are centre_of (ba_prior_dev.h).
+//
+// One 256-lane workgroup per camera, whatever its degree (the argument: DESIGN §5k).  The lanes stride over the camera's list
+// cam_ptr[c] .. cam_ptr[c + 1] of cam_obs, gather the held points from x and keep the 55 sums of an evaluation (f, g, the packed
+// lower H) in registers; the sums go through an xor butterfly inside each wave and through LDS across the four waves, always as
+// ((w0 + w1) + w2) + w3, so a camera's result depends on nothing but its own data and the order of its list.  Thread 0 then
+// runs the 9 x 9 algebra (priors, masking, damping, Cholesky, the two triangular solves, the scaled norms, the accept test) on
+// LDS-resident arrays and leaves the next trial camera and its cam_pre row in LDS for all lanes: the camera's trigonometry is
+// evaluated once per trial.  No floating-point atomics; the eight counters of a call are integers, added once per workgroup.
+#include <cmath>
+
+#include "ba_internal.h"
+#include "ba_lm_internal.h"
+
+namespace {
+
+#include "ba_model_dev.h"  // CPAD, cam_pre, project_pre, jac_block
+#include "ba_prior_dev.h"  // centre_of
+
+constexpr int CM_BLK = 256, CM_WAVES = CM_BLK / 64;
+constexpr int CM_SUMS = 55;                     // [f | g (9) | H (45, packed lower row-major)]
+constexpr int CM_G = 1, CM_H = 10;              // where g and H start
+constexpr int CM_COUNTERS = BA_PT_STATES + 2;   // [states | cameras flagged BEHIND | most trials of a camera]
+constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u;
+
+struct CamArgs {
+  const int *cam_ptr, *cam_obs, *pnt0;
+  const double *pt2d, *info;          // info: l00 l10 l11 per observation, or null
+  const uint16_t *mask;               // effective mask of held components per camera, or null
+  const int *cam_pri_of, *ctr_pri_of; // camera -> its camera / centre prior, -1: none; or null
+  const double *cam_mu, *cam_info, *ctr_mu, *ctr_info;
+  const double *x;                    // the whole vector (the points are read from it)
+  double *xc;                         // its camera part
+  uint8_t *status;                    // or null
+  double *cost;                       // or null
+  unsigned long long *counts;
+  int max_iter, kind;
+  double xtol, lambda0, c2;
+};
+
+struct CamShared {
+  double red[CM_WAVES][CM_SUMS + 1];  // the waves' sums of an evaluation
+  int redb[CM_WAVES], redu[CM_WAVES]; // ... an observation behind the camera, an observation with Lambda != 0
+  double C[9], Cn[9], P[12];          // the camera, the trial camera and the trial's cam_pre row
+  double S[CM_SUMS], Sn[CM_SUMS];     // f, g, H at C and at the trial (priors included)
+  double A[45], y[9], d[9], D[9];     // damped matrix / its Cholesky factor, the solves, D_j = sqrt(H_jj) of the step's H
+  double e[9], w[9], Hc[18], M[18];   // prior terms
+  int stop;
+};
+
+__device__ __forceinline__ double wave_all_sum(double v) {  // every lane receives the same bits (a + b == b + a)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// cam_pre row of the trial camera sh.Cn -> sh.P (one lane)
+__device__ __forceinline__ void trial_row(CamShared &sh) {
+  double C9[9], P[12];
+#pragma unroll
+  for (int i = 0; i < 9; i++) C9[i] = sh.Cn[i];
+  cam_pre<double>(C9, P);
+#pragma unroll
+  for (int i = 0; i < 12; i++) sh.P[i] = P[i];
+}
+
+// The observation sums of camera list [k0, k1) at the trial camera (row sh.P), all lanes: wave w's sums -> sh.red[w], whether
+// one of its observations with Lambda != 0 has P1.z >= 0 -> sh.redb[w], whether it has such an observation at all -> sh.redu[w]
+__device__ __forceinline__ void observation_sums(const CamArgs &a, CamShared &sh, int k0, int k1, int t) {
+  double P[12], acc[CM_SUMS];
+#pragma unroll
+  for (int i = 0; i < 12; i++) P[i] = sh.P[i];
+#pragma unroll
+  for (int i = 0; i < CM_SUMS; i++) acc[i] = 0.0;
+  int bh = 0, used = 0;
+  for (int k = k0 + t; k < k1; k += CM_BLK) {
+    const int o = a.cam_obs[k];
+    double l00 = 1.0, l10 = 0.0, l11 = 1.0;
+    if (a.info) l00 = a.info[3 * (int64_t)o], l10 = a.info[3 * (int64_t)o + 1], l11 = a.info[3 * (int64_t)o + 2];
+    if (l00 == 0.0 && l10 == 0.0 && l11 == 0.0) continue;  // Lambda = 0: the observation is dropped
+    used = 1;
+    const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
+    const double X[3] = {xp[0], xp[1], xp[2]};
+    const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
+    double out[2], J[24];
+    project_pre<double>(X, P, out);
+    jac_block<double>(X, P, J);  // (columns 3..11 of both rows are used: R, the point columns, is dead code)
+    {  // P1.z as jac_block forms it
+      const double kx = P[0], ky = P[1], kz = P[2], s = P[9], c = P[10];
+      const double d = kx * X[0] + ky * X[1] + kz * X[2];
+      const double z1 = ((c * X[2] + s * (kx * X[1] - ky * X[0])) + ((1 - c) * d) * kz) + P[5];
+      if (z1 >= 0.0) bh = 1;
+    }
+    const double ex = out[0] - m.x, ey = out[1] - m.y;
+    const double rx = l00 * ex + l10 * ey, ry = l11 * ey;
+    double w;
+    acc[0] += robust_rho(a.kind, rx * rx + ry * ry, a.c2, &w);
+    double j0[9], j1[9], wj0[9], wj1[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      j0[i] = l00 * J[3 + i] + l10 * J[15 + i];
+      j1[i] = l11 * J[15 + i];
+      wj0[i] = w * j0[i];
+      wj1[i] = w * j1[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+      acc[CM_G + i] += wj0[i] * rx + wj1[i] * ry;
+#pragma unroll
+      for (int j = 0; j <= i; j++) acc[CM_H + i * (i + 1) / 2 + j] += wj0[i] * j0[j] + wj1[i] * j1[j];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < CM_SUMS; i++) acc[i] = wave_all_sum(acc[i]);
+  bh = __any(bh) ? 1 : 0;
+  used = __any(used) ? 1 : 0;
+  if ((t & 63) == 0) {
+    const int wv = t >> 6;
+#pragma unroll
+    for (int i = 0; i < CM_SUMS; i++) sh.red[wv][i] = acc[i];
+    sh.redb[wv] = bh;
+    sh.redu[wv] = used;
+  }
+}
+
+// f, g, H at the trial camera -> sh.Sn: the waves' sums in wave order, then the camera prior qc and the centre prior qt (-1: none)
+// (one lane)
+__device__ __forceinline__ void trial_totals(const CamArgs &a, CamShared &sh, int qc, int qt) {
+  for (int i = 0; i < CM_SUMS; i++) sh.Sn[i] = ((sh.red[0][i] + sh.red[1][i]) + sh.red[2][i]) + sh.red[3][i];
+  sh.Sn[0] *= 0.5;
+  if (qc >= 0) {
+    const double *mu = a.cam_mu + 9 * (int64_t)qc, *L = a.cam_info + 45 * (int64_t)qc;
+    for (int i = 0; i < 9; i++) {
+      sh.e[i] = sh.Cn[i] - mu[i];
+      sh.w[i] = 0.0;
+    }
+    int tt = 0;
+    for (int i = 0; i < 9; i++)
+      for (int j = 0; j <= i; j++, tt++) {
+        const double v = L[tt];
+        sh.w[i] += v * sh.e[j];
+        if (j < i) sh.w[j] += v * sh.e[i];
+        sh.Sn[CM_H + tt] += v;
+      }
+    double q = 0.0;
+    for (int i = 0; i < 9; i++) {
+      q += sh.e[i] * sh.w[i];
+      sh.Sn[CM_G + i] += sh.w[i];
+    }
+    sh.Sn[0] += 0.5 * q;
+  }
+  if (qt >= 0) {
+    const double *mu = a.ctr_mu + 3 * (int64_t)qt, *L = a.ctr_info + 6 * (int64_t)qt;
+    double C6[6], ctr[3], H[18];
+#pragma unroll
+    for (int i = 0; i < 6; i++) C6[i] = sh.Cn[i];
+    centre_of<true>(C6, ctr, H);
+#pragma unroll
+    for (int i = 0; i < 18; i++) sh.Hc[i] = H[i];
+    const double e0 = ctr[0] - mu[0], e1 = ctr[1] - mu[1], e2 = ctr[2] - mu[2];
+    const double w0 = L[0] * e0 + L[1] * e1 + L[3] * e2, w1 = L[1] * e0 + L[2] * e1 + L[4] * e2, w2 = L[3] * e0 + L[4] * e1 + L[5] * e2;
+    sh.Sn[0] += 0.5 * (e0 * w0 + e1 * w1 + e2 * w2);
+    for (int j = 0; j < 6; j++) {  // M = Lambda H
+      const double h0 = sh.Hc[j], h1 = sh.Hc[6 + j], h2 = sh.Hc[12 + j];
+      sh.M[j] = L[0] * h0 + L[1] * h1 + L[3] * h2;
+      sh.M[6 + j] = L[1] * h0 + L[2] * h1 + L[4] * h2;
+      sh.M[12 + j] = L[3] * h0 + L[4] * h1 + L[5] * h2;
+    }
+    int tt = 0;  // (the leading 6 x 6 of the packed lower H is its first 21 entries)
+    for (int i = 0; i < 6; i++) {
+      for (int j = 0; j <= i; j++, tt++)
+        sh.Sn[CM_H + tt] += (sh.Hc[i] * sh.M[j] + sh.Hc[6 + i] * sh.M[6 + j]) + sh.Hc[12 + i] * sh.M[12 + j];
+      sh.Sn[CM_G + i] += (sh.Hc[i] * w0 + sh.Hc[6 + i] * w1) + sh.Hc[12 + i] * w2;
+    }
+  }
+}
+
+// (H + lam diag H) delta = -g at sh.S with the rows and columns of the held components fm replaced by the identity, by a 9 x 9
+// Cholesky: delta -> sh.d, D_j = sqrt(H_jj) (0: held) -> sh.D.  False: a pivot that is not positive or not finite, or a
+// delta that is not finite.  (one lane)
+__device__ __forceinline__ bool damped_step(CamShared &sh, unsigned fm, double lam) {
+  int tt = 0;
+  for (int i = 0; i < 9; i++)
+    for (int j = 0; j <= i; j++, tt++) {
+      const bool held = (((fm >> i) | (fm >> j)) & 1u) != 0;
+      double v = held ? (i == j ? 1.0 : 0.0) : sh.S[CM_H + tt];
+      if (i == j) v += lam * v;
+      sh.A[tt] = v;
+    }
+  for (int i = 0; i < 9; i++) {
+    const int ri = i * (i + 1) / 2;
+    for (int j = 0; j <= i; j++) {
+      const int rj = j * (j + 1) / 2;
+      double s = sh.A[ri + j];
+      for (int k = 0; k < j; k++) s -= sh.A[ri + k] * sh.A[rj + k];
+      if (i == j) {
+        if (!(s > 0.0) || !isfinite(s)) return false;
+        sh.A[ri + i] = sqrt(s);
+      } else {
+        sh.A[ri + j] = s / sh.A[rj + j];
+      }
+    }
+  }
+  for (int i = 0; i < 9; i++) {  // L y = -g
+    const int ri = i * (i + 1) / 2;
+    double s = ((fm >> i) & 1u) ? 0.0 : -sh.S[CM_G + i];
+    for (int k = 0; k < i; k++) s -= sh.A[ri + k] * sh.y[k];
+    sh.y[i] = s / sh.A[ri + i];
+  }
+  bool finite = true;
+  for (int i = 8; i >= 0; i--) {  // L' delta = y
+    double s = sh.y[i];
+    for (int k = i + 1; k < 9; k++) s -= sh.A[k * (k + 1) / 2 + i] * sh.d[k];
+    sh.d[i] = s / sh.A[i * (i + 1) / 2 + i];
+    finite = finite && isfinite(sh.d[i]);
+  }
+  for (int i = 0; i < 9; i++) sh.D[i] = ((fm >> i) & 1u) ? 0.0 : sqrt(sh.S[CM_H + i * (i + 1) / 2 + i]);
+  return finite;
+}
+
+// One camera per workgroup.  The control flow is uniform over the workgroup: thread 0 decides, sh.stop tells.
+__global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
+  __shared__ CamShared sh;
+  const int t = threadIdx.x;
+  const int c = (int)blockIdx.x;
+  const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
+  double *xc = a.xc + 9 * (int64_t)c;
+  const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  const int qc = a.cam_pri_of ? a.cam_pri_of[c] : -1, qt = a.ctr_pri_of ? a.ctr_pri_of[c] : -1;
+  // (thread 0's state)
+  int status = BA_PT_DEGENERATE, trials = 0, behind = 0;
+  bool write = false;
+  double fb = 0.0, lam = a.lambda0;
+  if (t == 0) {
+    for (int i = 0; i < 9; i++) sh.C[i] = sh.Cn[i] = xc[i];
+    trial_row(sh);
+    sh.stop = 0;
+  }
+  __syncthreads();
+  for (int it = -1;; it++) {  // it = -1: the evaluation at the start; it >= 0: the evaluation of a trial
+    observation_sums(a, sh, k0, k1, t);
+    __syncthreads();
+    if (t == 0) {
+      trial_totals(a, sh, qc, qt);
+      const int bn = sh.redb[0] | sh.redb[1] | sh.redb[2] | sh.redb[3];
+      const double fn = sh.Sn[0];
+      bool stop = false;
+      if (it < 0) {
+        const int used = sh.redu[0] | sh.redu[1] | sh.redu[2] | sh.redu[3];
+        for (int i = 0; i < CM_SUMS; i++) sh.S[i] = sh.Sn[i];
+        fb = fn;
+        behind = bn;
+        if (fm == CM_ALL) {
+          status = BA_PT_FIXED;
+          stop = true;
+        } else if (!used && qc < 0 && qt < 0) {  // nothing constrains the camera: DEGENERATE, cost entries 0, no flag
+          sh.S[0] = fb = 0.0;
+          behind = 0;
+          stop = true;
+        } else if (!isfinite(fn)) {
+          status = BA_PT_NONFINITE;
+          behind = 0;
+          stop = true;
+        } else {
+          status = BA_PT_MAX_ITER;
+          stop = a.max_iter == 0;
+        }
+      } else if (fn <= sh.S[0]) {  // accepted (false for a NaN)
+        for (int i = 0; i < 9; i++) sh.C[i] = sh.Cn[i];
+        for (int i = 0; i < CM_SUMS; i++) sh.S[i] = sh.Sn[i];
+        behind = bn;
+        write = true;
+        lam = fmax(lam / 10.0, 1e-12);
+        double nd = 0.0, nx = 0.0;
+        for (int i = 0; i < 9; i++) {
+          const double u = sh.D[i] * sh.d[i], v = sh.D[i] * sh.C[i];
+          nd += u * u;
+          nx += v * v;
+        }
+        if (sqrt(nd) <= a.xtol * (sqrt(nx) + a.xtol)) {
+          status = BA_PT_CONVERGED;
+          stop = true;
+        } else {
+          stop = trials >= a.max_iter;
+        }
+      } else {
+        lam *= 10.0;
+        if (lam > 1e12) {
+          status = BA_PT_STALLED;
+          stop = true;
+        } else {
+          stop = trials >= a.max_iter;
+        }
+      }
+      while (!stop) {  // the next trial; a step that cannot be solved is a rejected trial without an evaluation
+        trials++;
+        if (damped_step(sh, fm, lam)) {
+          for (int i = 0; i < 9; i++) sh.Cn[i] = ((fm >> i) & 1u) ? sh.C[i] : sh.C[i] + sh.d[i];
+          trial_row(sh);
+          break;
+        }
+        lam *= 10.0;
+        if (lam > 1e12) {
+          status = BA_PT_STALLED;
+          stop = true;
+        } else {
+          stop = trials >= a.max_iter;
+        }
+      }
+      sh.stop = stop ? 1 : 0;
+    }
+    __syncthreads();
+    if (sh.stop) break;
+  }
+  if (t == 0) {
+    const int st = status | (behind ? BA_PT_BEHIND : 0);
+    if (write)
+      for (int i = 0; i < 9; i++) xc[i] = sh.C[i];
+    if (a.status) a.status[c] = (uint8_t)st;
+    if (a.cost) a.cost[2 * (int64_t)c] = fb, a.cost[2 * (int64_t)c + 1] = sh.S[0];
+    atomicAdd(a.counts + status, 1ull);
+    if (behind) atomicAdd(a.counts + BA_PT_STATES, 1ull);
+    atomicMax(a.counts + BA_PT_STATES + 1, (unsigned long long)trials);
+  }
+}
+
+}  // namespace
+
+// the per-camera lookups of the priors (once per ba_lm_set_priors) and the effective mask (once per ba_lm_set_fixed /
+// ba_lm_set_shared_intrinsics)
+static int camera_tables(ba_problem *p) {
+  CameraWork &w = p->cams;
+  if (!w.counts) BA_CHECK(w.counts.alloc(CM_COUNTERS));
+  if (w.pri_version != p->pri_version) {
+    const PriorSet *sets[2] = {&p->pri[PRI_CAM], &p->pri[PRI_CTR]};
+    DevBuf<int> *out[2] = {&w.cam_pri_of, &w.ctr_pri_of};
+    for (int k = 0; k < 2; k++) {
+      if (sets[k]->n == 0) continue;
+      std::vector<int> of((size_t)p->ncams, -1);
+      for (int64_t q = 0; q < sets[k]->n; q++) of[(size_t)sets[k]->h_idx[(size_t)q]] = (int)q;
+      BA_CHECK(upload(*out[k], of));
+    }
+    w.pri_version = p->pri_version;
+  }
+  if (w.fix_version != p->fix_version || w.grp_version != p->grp_version) {
+    w.mask_on = p->fix_ncam > 0 || p->grp_on();
+    if (w.mask_on) {
+      std::vector<uint16_t> m((size_t)p->ncams, 0);
+      for (int64_t c = 0; c < p->ncams; c++) {
+        if (p->fix_ncam > 0) m[(size_t)c] = p->h_fix_cam[(size_t)c];
+        if (p->grp_on() && p->h_grp[(size_t)c] > 0) m[(size_t)c] |= (uint16_t)CM_INTRINSICS;
+      }
+      BA_CHECK(upload(w.mask, m));
+    }
+    w.fix_version = p->fix_version;
+    w.grp_version = p->grp_version;
+  }
+  return BA_OK;
+}
+
+static int camera_check(const char *who, ba_problem *p, const double *x, int *max_iter, double *xtol, double *lambda0) {
+  if (!p || (!x && p->npnts + p->ncams > 0)) {
+    ba_set_error("%s: null argument", who);
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
+    return BA_ERR_ARG;
+  }
+  if (!std::isfinite(*xtol) || !std::isfinite(*lambda0)) {
+    ba_set_error("%s: xtol and lambda0 must be finite (<= 0: the default), got %g and %g", who, *xtol, *lambda0);
+    return BA_ERR_ARG;
+  }
+  if (*max_iter < 0) *max_iter = 100;
+  if (*xtol <= 0) *xtol = 1e-10;
+  if (*lambda0 <= 0) *lambda0 = 1e-4;
+  return BA_OK;
+}
+
+// k_refine_cameras on st; the counters stay on the device (p->cams.counts)
+static int camera_launch(ba_problem *p, double *d_x, int max_iter, double xtol, double lambda0, uint8_t *d_status, double *d_cost,
+                         hipStream_t st) {
+  BA_CHECK(terms_upload(p));
+  BA_CHECK(camera_tables(p));
+  CameraWork &w = p->cams;
+  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, CM_COUNTERS * sizeof(unsigned long long), st));
+  if (p->ncams == 0) return BA_OK;
+  ProfScope ps(p, PC_REFINE_CAMERAS, st);
+  const PriorSet &cm = p->pri[PRI_CAM], &ct = p->pri[PRI_CTR];
+  CamArgs a;
+  a.cam_ptr = p->cam_ptr, a.cam_obs = p->cam_obs, a.pnt0 = p->pnt0;
+  a.pt2d = p->pt2d, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
+  a.mask = w.mask_on ? (const uint16_t *)w.mask : nullptr;
+  a.cam_pri_of = cm.n > 0 ? (const int *)w.cam_pri_of : nullptr, a.ctr_pri_of = ct.n > 0 ? (const int *)w.ctr_pri_of : nullptr;
+  a.cam_mu = cm.n > 0 ? (const double *)cm.mu : nullptr, a.cam_info = cm.n > 0 ? (const double *)cm.info : nullptr;
+  a.ctr_mu = ct.n > 0 ? (const double *)ct.mu : nullptr, a.ctr_info = ct.n > 0 ? (const double *)ct.info : nullptr;
+  a.x = d_x, a.xc = d_x + 3 * p->npnts, a.status = d_status, a.cost = d_cost, a.counts = w.counts;
+  a.max_iter = max_iter, a.kind = p->loss;
+  a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
+  hipLaunchKernelGGL(k_refine_cameras, dim3((unsigned)p->ncams), dim3(CM_BLK), 0, st, a);
+  BA_HIP_CHECK(hipGetLastError());
+  return BA_OK;
+}
+
+// the device counters -> the caller's (synchronises st)
+static int camera_counts(ba_problem *p, int64_t *counts, int *iters_max, hipStream_t st) {
+  if (!counts && !iters_max) return BA_OK;
+  unsigned long long h[CM_COUNTERS];
+  BA_HIP_CHECK(hipMemcpyAsync(h, p->cams.counts, sizeof h, hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  if (counts)
+    for (int s = 0; s <= BA_PT_STATES; s++) counts[s] = (int64_t)h[s];
+  if (iters_max) *iters_max = (int)h[BA_PT_STATES + 1];
+  return BA_OK;
+}
+
+extern "C" int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                                     double *d_cost, int64_t *counts, int *iters_max, void *stream) {
+  BA_CHECK(camera_check("ba_refine_cameras_dev", p, d_x_inout, &max_iter, &xtol, &lambda0));
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
+  BA_CHECK(camera_launch(p, d_x_inout, max_iter, xtol, lambda0, d_status, d_cost, st));
+  return camera_counts(p, counts, iters_max, st);
+}
+
+extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
+                                 double *cost, int64_t *counts, int *iters_max) {
+  BA_CHECK(camera_check("ba_refine_cameras", p, x_inout, &max_iter, &xtol, &lambda0));
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
+  hipStream_t st = p->stream;
+  CameraWork &w = p->cams;
+  double *dx;
+  BA_CHECK(ba_scratch(p, 0, (size_t)(nvar + 1) * sizeof(double), (void **)&dx));
+  if (status && !w.status) BA_CHECK(w.status.alloc(p->ncams));
+  if (cost && !w.cost) BA_CHECK(w.cost.alloc(2 * p->ncams));
+  BA_HIP_CHECK(hipMemcpyAsync(dx, x_inout, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
+  BA_CHECK(camera_launch(p, dx, max_iter, xtol, lambda0, status ? (uint8_t *)w.status : nullptr, cost ? (double *)w.cost : nullptr,
+                         st));
+  if (p->ncams > 0) {  // the cameras only: the point part of the caller's x is never written
+    BA_HIP_CHECK(hipMemcpyAsync(x_inout + 3 * p->npnts, dx + 3 * p->npnts, (size_t)9 * p->ncams * sizeof(double), hipMemcpyDeviceToHost,
+                                st));
+    if (status) BA_HIP_CHECK(hipMemcpyAsync(status, w.status, (size_t)p->ncams, hipMemcpyDeviceToHost, st));
+    if (cost) BA_HIP_CHECK(hipMemcpyAsync(cost, w.cost, (size_t)2 * p->ncams * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return camera_counts(p, counts, iters_max, st);
+}

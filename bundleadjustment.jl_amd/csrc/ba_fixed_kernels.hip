@@ -120,6 +120,7 @@ extern "C" int ba_lm_set_fixed(ba_problem *p, const uint16_t *cam_mask, const ui
   if (npnt > 0) p->h_fix_pnt.assign(pnt_fixed, pnt_fixed + p->npnts);
   else p->h_fix_pnt.clear();
   p->fix_dirty = p->fix_on();
+  p->fix_version++;
   return BA_OK;
 }
 

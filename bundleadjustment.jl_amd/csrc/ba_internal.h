@@ -224,6 +224,7 @@ enum ProfClass {
   PC_SHARED_SMALL,   // shared intrinsics: T = C - B'Y and the 3G x 3G Cholesky solve fused with the update of the camera step
   PC_INFO,           // per-observation information (ba_lm_set_obs_info): "k_info_whiten": k_obs_scale on a handle with it, the whitening of r and J (with the loss's reweighting)
   PC_REFINE_POINTS,  // points with the cameras held (ba_refine_points): k_cam_pre and k_refine_points
+  PC_REFINE_CAMERAS,  // cameras with the points held (ba_refine_cameras): k_refine_cameras
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -338,6 +339,21 @@ struct PointWork {
   DevBuf<double> cost;
 };
 
+// cameras with the points held (ba_refine_cameras, ba_camera_kernels.hip): per camera the index of its camera prior and of its
+// centre prior (-1: none; rebuilt when ba_lm_set_priors changed them) and the effective 9-bit mask of held components -- the
+// mask of ba_lm_set_fixed with the bits of (k1, k2, f) set for every member of a calibration group (rebuilt when
+// ba_lm_set_fixed or ba_lm_set_shared_intrinsics changed them) --, the eight device counters of a call and the host entry's
+// status / cost staging
+struct CameraWork {
+  DevBuf<int> cam_pri_of, ctr_pri_of;
+  DevBuf<uint16_t> mask;
+  bool mask_on = false;
+  int64_t pri_version = -1, fix_version = -1, grp_version = -1;
+  DevBuf<unsigned long long> counts;
+  DevBuf<uint8_t> status;
+  DevBuf<double> cost;
+};
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -367,6 +383,7 @@ struct ba_problem {
   DevBuf<uint16_t> d_fix_cam;
   DevBuf<uint8_t> d_fix_pnt;
   bool fix_dirty = false;
+  int64_t fix_version = 0;  // counts the calls of ba_lm_set_fixed (CameraWork keeps a table derived from the camera masks)
   bool fix_on() const { return fix_ncam > 0 || fix_npnt > 0; }
   // Gaussian priors of the LM entries (ba_lm_set_priors): points, cameras, camera centres; uploaded lazily (pri_dirty, prior_upload)
   // with the buffers the prior kernels write: pri_d = d_k = h_k(x) - mu_k at the linearisation (3 / 9 / 3 per prior, kind after
@@ -374,7 +391,7 @@ struct ba_problem {
   // per prior (kind after kind): d'Lambda d at the linearisation, at the trial point, and the step's model term
   PriorSet pri[PRI_KINDS];
   bool pri_dirty = false;
-  int64_t pri_version = 0;  // counts the calls of ba_lm_set_priors (PointWork keeps a table derived from the point priors)
+  int64_t pri_version = 0;  // counts the calls of ba_lm_set_priors (PointWork and CameraWork keep tables derived from the priors)
   DevBuf<double> pri_d, pri_H, pri_val;
   int64_t pri_total() const { return pri[PRI_PNT].n + pri[PRI_CAM].n + pri[PRI_CTR].n; }
   bool pri_on() const { return pri_total() > 0; }
@@ -402,6 +419,7 @@ struct ba_problem {
   DevBuf<double> d_info;
   bool info_on() const { return info_set; }
   PointWork pts;
+  CameraWork cams;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

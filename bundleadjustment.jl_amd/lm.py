@@ -297,6 +297,44 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
     return x, info
 
 
+def refine_cameras(nlp, x, *, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
+                   fixed_camera_params=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
+    """The cameras of x with its points held (ba_refine_cameras), the other half of refine_points: every camera is an independent
+    problem in at most 9 unknowns -- the objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info`, `camera_priors`
+    and `centre_priors`, restricted to that camera -- solved by a Marquardt iteration of its own (accept test, damping and
+    stopping test per camera).  max_iter (None: 100; 0: evaluate only), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
+    D_j = sqrt(H_jj): the predicted motion in pixels), lam0 (None: 1e-4).  fixed_camera_params hold components (("k1", "k2",
+    "f"): a pose-only refit); fixed_cameras are skipped; the members of the groups of shared_intrinsics keep their (k1, k2, f).
+    Returns (x_new, info): x_new a copy of x with the cameras replaced (points, held components and skipped cameras
+    bit-identical); info a dict with `status` (ncams names among _lib.POINT_STATES), `behind` (bool: at the returned camera an
+    observation sees its point from behind, P1.z >= 0), `cost_before`, `cost_after` (per camera, cost_after <= cost_before),
+    `counts` (cameras per status name, plus "behind") and `iters_max`.  Bad arguments raise ValueError before any device call."""
+    terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras=fixed_cameras,
+                              fixed_camera_params=fixed_camera_params, camera_priors=camera_priors, centre_priors=centre_priors,
+                              shared_intrinsics=shared_intrinsics, obs_info=obs_info)
+    if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
+        raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
+    tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
+    if (tol is not None and tol <= 0) or (l0 is not None and l0 <= 0):
+        raise ValueError(f"xtol and lam0 must be > 0 (or None), got {xtol!r} and {lam0!r}")
+    x = np.array(x, dtype=np.float64, copy=True)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    terms.apply(nlp)  # (x is not checked against the grouping: the members' intrinsics are held, whatever they are)
+    status = np.zeros(nlp.ncams, dtype=np.uint8)
+    cost = np.zeros((nlp.ncams, 2))
+    counts = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64)
+    its = C.c_int(0)
+    _lib.check(_lib.lib().ba_refine_cameras(nlp.handle, _lib.ptr(x), -1 if max_iter is None else int(max_iter),
+                                            -1.0 if tol is None else tol, -1.0 if l0 is None else l0, _lib.ptr(status),
+                                            _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
+    names = np.array(_lib.POINT_STATES)
+    info = dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
+                cost_after=cost[:, 1].copy(), iters_max=its.value,
+                counts={**{n: int(c) for n, c in zip(_lib.POINT_STATES, counts)}, "behind": int(counts[-1])})
+    return x, info
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

@@ -479,6 +479,49 @@ int ba_refine_points_dev(ba_problem *p, double *d_x_inout /* nvar, device */, in
                          uint8_t *d_status /* npnts or NULL */, double *d_cost /* 2 npnts or NULL */,
                          int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
 
+/* ---- cameras with the points held (an extension: the reference has no resection and no per-camera solve) ------------------
+ * The other half of ba_refine_points.  With every point entry of x held, camera c is an independent least-squares problem in at
+ * most 9 unknowns: the handle's objective restricted to that camera,
+ *   f_c(C) = sum_{o in obs(c)} 1/2 c^2 rho(r^_o' r^_o / c^2) + 1/2 (C - mu)' Lambda_cam (C - mu)
+ *            + 1/2 (c(C) - mu')' Lambda_ctr (c(C) - mu')
+ * rho and c from ba_lm_set_loss, r^ = L'r from ba_lm_set_obs_info (the plain r when none is set; an observation with Lambda = 0 is
+ * dropped), the second term only for a camera that carries a camera prior, the third only for one that carries a centre prior,
+ * c(C) = -R(r)'t as in ba_lm_set_priors (nonlinear: re-evaluated at every trial).
+ * Honoured: ba_lm_set_fixed -- a masked camera component is held: its step is exactly 0 and its bits come back unchanged; a
+ * camera with all 9 components held is skipped (BA_PT_FIXED; its cost entries and the BEHIND flag are still evaluated).  A
+ * grouping (ba_lm_set_shared_intrinsics): the (k1, k2, f) of every group member are held for this call as if masked and stay
+ * bit-identical -- the tied problem is not separable by camera, a pose-only refit is what a grouping leaves.  Ignored: fixed
+ * points and point priors (the points are held here anyway).  A handle with a communicator is refused (BA_ERR_ARG): a camera's
+ * observations are spread over the shards.
+ * Iteration (Marquardt, per camera): at C, w_o = rho'(z_o), H = sum w J^'J^ (+ Lambda_cam + H_ctr' Lambda_ctr H_ctr), g = sum w J^'r^
+ * (+ Lambda_cam (C - mu) + H_ctr' Lambda_ctr (c(C) - mu')), J^ the whitened 2 x 9 camera block, H_ctr = dc/d(r, t); the rows and
+ * columns of held components are replaced by the identity and g_j = 0 there; (H + lambda diag H) delta = -g by a 9 x 9 Cholesky
+ * (a pivot that is not positive or not finite, or a delta that is not finite, is a rejection); the step is accepted iff
+ * f_c(C + delta) <= f_c(C) (a non-finite cost is rejected), then lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.
+ * States (the BA_PT_* values): CONVERGED after an accepted step with |D delta| <= xtol (|D C| + xtol), D_j = sqrt(H_jj) of the H
+ * that produced the step, 0 on held components, C the new camera -- the block mixes units (f ~ 1e3, k2 ~ 1e-12), D delta is the
+ * predicted motion in pixels; STALLED when lambda > 1e12; MAX_ITER after max_iter trials; NONFINITE when the cost at the start
+ * is not finite (the camera is unchanged, no flag); DEGENERATE for a camera that is not FIXED and has no observation with
+ * Lambda != 0, no camera prior and no centre prior (unchanged, cost entries 0, no flag).  BA_PT_BEHIND is OR-ed into the state
+ * when at the returned camera an observation with Lambda != 0 has P1.z >= 0.
+ * max_iter < 0: 100; max_iter == 0 evaluates only (cost and flag written, x untouched, state MAX_ITER); xtol <= 0: 1e-10;
+ * lambda0 <= 0: 1e-4.  xtol or lambda0 not finite: BA_ERR_ARG.
+ * cost[2 c] is f_c at the start, cost[2 c + 1] at the returned camera, never larger.  counts[s] = cameras in state s,
+ * counts[BA_PT_STATES] = cameras flagged BEHIND.  iters_max: the most trials any camera took.
+ * The point part of x and every camera that is not moved come back bit-identical; a camera's result depends on its own data and
+ * the order of its observations only; two calls give the same bits; the next ba_lm_step / ba_lm_solve on the handle gives the
+ * same bits as without this call in between.
+ * ba_refine_cameras_dev: x, status and cost in device memory, enqueued on `stream` (NULL: the handle's); with counts and
+ * iters_max both NULL it does not synchronise, otherwise it waits for the stream to hand them over.
+ * Out of scope: a pose from scratch (DLT / P3P: an eigen-solve), Float32, refinement inside the LM loop, the tied
+ * (shared-intrinsics) problem over a group, several ranks. */
+int ba_refine_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
+                      uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
+                      int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
+int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int max_iter, double xtol, double lambda0,
+                          uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
+                          int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -137,3 +137,21 @@ function refine_points!(nlp, x :: Vector{Float64}; triangulate :: Bool = false, 
   end
   return status, cost, counts, Int(iters[])
 end
+
+# cameras with the points held (an extension): include/ba_hip.h, ba_refine_cameras.  Refines the cameras of `x` in place under the
+# loss, information, camera and centre priors, camera masks and grouping the handle holds (the members of a group keep their
+# k1, k2, f).  Returns (status :: Vector{UInt8} (BA_PT_* | 0x80 when a point lies behind the camera), cost :: 2 x ncams (before,
+# after), counts :: Vector{Int64} (the six states, then the cameras flagged behind), iters_max).
+function refine_cameras!(nlp, x :: Vector{Float64}; max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  GC.@preserve x status cost counts begin
+    bacheck(ccall((:ba_refine_cameras, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint}),
+                  nlp.handle, pointer(x), Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters))
+  end
+  return status, cost, counts, Int(iters[])
+end

@@ -1,0 +1,99 @@
+"""Cameras with the points held (ba_refine_cameras): time of the device-resident entry on the Dubrovnik and Venice
+shapes, against the fixed-point LM solve on the same scene.
+
+  refine   host clock around ba_refine_cameras_dev (no host copy, counts not fetched) + ba_synchronize, x restored before every
+           call outside the timed window; median of `reps` after a warm-up; and the event time of the launch
+           (profile class k_refine_cameras)
+  lm       one Levenberg_Marquardt(..., fixed_points=all) solve from the same x0 with the small-step test at the same tolerance
+           (srtol = xtol, every other test off): its loop time, iterations, and how far its cameras end from refine's (the
+           largest relative difference of a camera block)
+
+One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (or the file given).
+usage: python tools/bench_refine_cameras.py [out.json] [reps] [shape ...]"""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as ge  # noqa: E402
+
+XTOL = 1e-10
+HBM_ACHIEVABLE_TBPS = 6.3
+
+
+def measure(ba, name, reps):
+    L, lib = ba._lib.lib(), ba._lib
+    p = ba.synthetic.make_named(name)
+    n, nc, nvar = p["npnts"], p["ncams"], len(p["x0"])
+    m = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(p))
+    deg = np.bincount(p["cam_idx1"] - 1, minlength=nc)
+    row = {"shape": name, "ncams": nc, "npnts": n, "nobs": p["nobs"], "xtol": XTOL, "degree_min": int(deg.min()),
+           "degree_median": int(np.median(deg)), "degree_max": int(deg.max())}
+    # one evaluation reads per observation its list entry, its point index, its measurement and its point (4 + 4 + 16 + 24 bytes)
+    row["bytes_per_evaluation_MB"] = round(48.0 * p["nobs"] / 1e6, 2)
+    d_x = C.c_void_p()
+    lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
+    x0 = np.ascontiguousarray(p["x0"])
+    counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
+    lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+    lib.check(L.ba_refine_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, lib.ptr(counts), C.byref(its), None))  # warm-up
+    wall = []
+    for _ in range(reps):
+        lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+        t = time.perf_counter()
+        lib.check(L.ba_refine_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+        lib.check(L.ba_synchronize(m.handle))
+        wall.append(1e3 * (time.perf_counter() - t))
+    m.profile(True)
+    lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+    lib.check(L.ba_refine_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+    ev_ms = m.profile_get()["k_refine_cameras"][0]
+    m.profile(False)
+    lib.check(L.ba_dev_free(m.handle, d_x))
+    med = statistics.median(wall)
+    row["refine"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall], "launch_event_ms": round(ev_ms, 3),
+                     "iters_max": its.value, "counts": {k: int(v) for k, v in zip(lib.POINT_STATES + ("behind",), counts)},
+                     "cameras_per_s": round(nc / (med * 1e-3))}
+    # the time an HBM-bound kernel would need if every trial of the slowest camera streamed the whole scene once
+    row["hbm_floor_ms"] = round((its.value + 1) * 48.0 * p["nobs"] / (HBM_ACHIEVABLE_TBPS * 1e12) * 1e3, 4)
+    x_ref, info = ba.refine_cameras(m, x0, xtol=XTOL)
+    row["objective_refine"] = float(np.sum(info["cost_after"]))
+    t = time.perf_counter()
+    st = ba.Levenberg_Marquardt(ba.FeasibilityResidual(m), "LDL", "AMD", "None", False, fixed_points=np.arange(1, n + 1),
+                                srtol=XTOL, satol=0.0, oatol=0.0, ortol=0.0, atol=0.0, rtol=0.0, restol=0.0, ite_max=100, log=False)
+    Cl, Cr = st.solution[3 * n:].reshape(-1, 9), x_ref[3 * n:].reshape(-1, 9)
+    row["lm_fixed_points"] = {"status": st.status, "iterations": st.iter, "loop_ms": round(1e3 * st.loop_time, 2),
+                              "call_ms": round(1e3 * (time.perf_counter() - t), 2),
+                              "ms_per_iteration": round(1e3 * st.loop_time / max(st.iter, 1), 2), "objective": st.objective,
+                              "cameras_differ_rel": float(np.max(np.linalg.norm(Cl - Cr, axis=1) / np.linalg.norm(Cr, axis=1)))}
+    row["lm_loop_over_refine"] = round(row["lm_fixed_points"]["loop_ms"] / med, 1)
+    row["refine_over_hbm_floor"] = round(ev_ms / row["hbm_floor_ms"], 1)
+    m.close()
+    return row
+
+
+def main():
+    args = sys.argv[1:]
+    out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", "refine_cameras_bench.json")
+    reps = int(args.pop(0)) if args and args[0].isdigit() else 5
+    shapes = args or ["dubrovnik-356", "venice-1778"]
+    ba = ge.load_package()
+    if ba.device_count() < 1:
+        sys.exit("bench_refine_cameras: no HIP device visible (nothing is measured without one)")
+    rows = []
+    for name in shapes:
+        row = measure(ba, name, reps)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    with open(out, "w") as fh:
+        json.dump(rows, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
