@@ -65,7 +65,7 @@ SYMBOLS = [
     "ba_lm_set_shared_intrinsics", "ba_lm_get_shared_intrinsics", "ba_dense_ldl_solve_multi",
     "ba_lm_set_obs_info", "ba_lm_get_obs_info",
     "ba_refine_points", "ba_refine_points_dev",
-    "ba_refine_cameras", "ba_refine_cameras_dev",
+    "ba_refine_cameras", "ba_refine_cameras_dev", "ba_resect_cameras", "ba_resect_cameras_dev",
 ]
 
 _lib = None
@@ -143,6 +143,8 @@ def lib():
     L.ba_refine_points_dev.argtypes = [vp, vp, C.c_int, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
     L.ba_refine_cameras.argtypes = [vp, vp, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int)]
     L.ba_refine_cameras_dev.argtypes = [vp, vp, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
+    L.ba_resect_cameras.argtypes = L.ba_refine_cameras.argtypes
+    L.ba_resect_cameras_dev.argtypes = L.ba_refine_cameras_dev.argtypes
     _lib = L
     return L
 

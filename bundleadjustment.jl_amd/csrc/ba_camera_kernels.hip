@@ -16,6 +16,9 @@
 // runs the 9 x 9 algebra (priors, masking, damping, Cholesky, the two triangular solves, the scaled norms, the accept test) on
 // LDS-resident arrays and leaves the next trial camera and its cam_pre row in LDS for all lanes: the camera's trigonometry is
 // evaluated once per trial.  No floating-point atomics; the eight counters of a call are integers, added once per workgroup.
+//
+// ba_resect_cameras launches k_resect_cameras before it: the start pose of every camera whose pose is free, in
+// closed form from its 2D-3D correspondences (further down).
 #include <cmath>
 
 #include "ba_internal.h"
@@ -30,7 +33,8 @@ constexpr int CM_BLK = 256, CM_WAVES = CM_BLK / 64;
 constexpr int CM_SUMS = 55;                     // [f | g (9) | H (45, packed lower row-major)]
 constexpr int CM_G = 1, CM_H = 10;              // where g and H start
 constexpr int CM_COUNTERS = BA_PT_STATES + 2;   // [states | cameras flagged BEHIND | most trials of a camera]
-constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u;
+constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u, CM_POSE = 0x3Fu;
+enum { RS_DONE = 0, RS_SKIPPED = 1, RS_DEGENERATE = 2 };  // the byte per camera k_resect_cameras leaves for k_refine_cameras
 
 struct CamArgs {
   const int *cam_ptr, *cam_obs, *pnt0;
@@ -41,6 +45,7 @@ struct CamArgs {
   const double *x;                    // the whole vector (the points are read from it)
   double *xc;                         // its camera part
   uint8_t *status;                    // or null
+  uint8_t *resect;                    // what k_resect_cameras did per camera (RS_*), or null: no resection ran
   double *cost;                       // or null
   unsigned long long *counts;
   int max_iter, kind;
@@ -240,6 +245,14 @@ __global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
   int status = BA_PT_DEGENERATE, trials = 0, behind = 0;
   bool write = false;
   double fb = 0.0, lam = a.lambda0;
+  if (a.resect && a.resect[c] == RS_DEGENERATE) {  // no pose was found: DEGENERATE, the camera untouched, cost entries 0, no flag
+    if (t == 0) {
+      if (a.status) a.status[c] = (uint8_t)BA_PT_DEGENERATE;
+      if (a.cost) a.cost[2 * (int64_t)c] = 0.0, a.cost[2 * (int64_t)c + 1] = 0.0;
+      atomicAdd(a.counts + BA_PT_DEGENERATE, 1ull);
+    }
+    return;
+  }
   if (t == 0) {
     for (int i = 0; i < 9; i++) sh.C[i] = sh.Cn[i] = xc[i];
     trial_row(sh);
@@ -333,6 +346,346 @@ __global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
   }
 }
 
+// ---- linear resection (ba_resect_cameras): the start pose of a camera from its 2D-3D correspondences ------------
+// With P = R X + t the BAL projection gives q = -P.xy / P.z for the undistorted measurement q: P.x + q_x P.z = 0 and
+// P.y + q_y P.z = 0, two homogeneous linear equations in the 12 entries of [R | t].  On Hartley-normalised points X~ = s (X - m),
+// h = (X~, 1), the 12 x 12 normal matrix is M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]] with the 4 x 4 moments S0 = sum h h',
+// Sx = sum q_x h h', Sy = sum q_y h h', Sq = sum |q|^2 h h': 40 sums per lane, reduced as observation_sums reduces its 55.  The
+// eigenvector of M's smallest eigenvalue (cyclic Jacobi, M and the rotations in LDS) is gamma [R / s | R m + t].
+constexpr int RS_SUMS = 40;         // [S0 | Sx | Sy | Sq], each packed lower row-major (10)
+constexpr int RS_UNDIST_ITERS = 8;  // fixed-point iterations of q <- u / (1 + k1 |q|^2 + k2 |q|^4), as the triangulation's
+constexpr int RS_MIN_OBS = 6;       // 12 unknowns up to scale, two equations per observation
+constexpr int RS_SWEEPS = 30;       // cap of the Jacobi sweeps (12 x 12 and 3 x 3)
+
+struct RsShared {
+  double red[CM_WAVES][RS_SUMS];
+  int first[CM_WAVES];
+  double M[144], V[144];      // the normal matrix (its diagonal ends as the eigenvalues) and the accumulated rotations
+  double W[9], V3[9], sg[3];  // the 3 x 3 block A and its one-sided Jacobi SVD: W -> U Sigma, V3, the singular values
+  double U[9], R[9], a3[4], r[3];
+  int front, stop;
+};
+
+// The sums acc of all lanes -> every lane: xor butterfly per wave, LDS across the waves, ((w0 + w1) + w2) + w3
+template <int N>
+__device__ __forceinline__ void block_sums(double (&acc)[N], RsShared &sh, int t) {
+#pragma unroll
+  for (int i = 0; i < N; i++) acc[i] = wave_all_sum(acc[i]);
+  __syncthreads();  // (the readers of the sums before these are done)
+  if ((t & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; i++) sh.red[t >> 6][i] = acc[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < N; i++) acc[i] = ((sh.red[0][i] + sh.red[1][i]) + sh.red[2][i]) + sh.red[3][i];
+}
+
+__device__ __forceinline__ bool obs_used(const CamArgs &a, int o) {
+  if (!a.info) return true;
+  const double *l = a.info + 3 * (int64_t)o;
+  return !(l[0] == 0.0 && l[1] == 0.0 && l[2] == 0.0);
+}
+
+// Cyclic Jacobi on the symmetric n x n matrix A (row-major, both triangles kept), V <- the product of the rotations (the
+// columns end as eigenvectors, the diagonal of A as eigenvalues).  A rotation is skipped when |a_pq| <= 1e-18 sqrt(|a_pp a_qq|);
+// the sweeps end with the first sweep without a rotation or at RS_SWEEPS.  Called by the whole workgroup, A and V in LDS: every
+// lane reads the same three entries and takes the same decision, lane k < n updates element k of the two columns, then of the two
+// rows of A and of V, with a barrier between the phases.  Every element sees the operations of a one-lane loop over k.
+__device__ __forceinline__ int jacobi_eig(double *A, double *V, int n, int t) {
+  for (int i = t; i < n * n; i += CM_BLK) V[i] = (i / n == i % n) ? 1.0 : 0.0;
+  __syncthreads();
+  int sweeps = 0;
+#pragma nounroll
+  for (; sweeps < RS_SWEEPS; sweeps++) {
+    int rotated = 0;
+#pragma nounroll
+    for (int p = 0; p < n - 1; p++)
+#pragma nounroll
+      for (int q = p + 1; q < n; q++) {
+        const double apq = A[p * n + q], app = A[p * n + p], aqq = A[q * n + q];
+        if (!(fabs(apq) > 1e-18 * sqrt(fabs(app * aqq)))) continue;  // (uniform; also ends on a NaN)
+        rotated = 1;
+        const double th = (aqq - app) / (2.0 * apq);
+        const double tt = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+        __syncthreads();  // (every lane has read the three entries)
+        if (t < n) {  // A <- A G
+          const double akp = A[t * n + p], akq = A[t * n + q];
+          A[t * n + p] = cs * akp - sn * akq;
+          A[t * n + q] = sn * akp + cs * akq;
+        }
+        __syncthreads();
+        if (t < n) {  // A <- G' A with a_pq = a_qp = 0, V <- V G
+          const double apk = A[p * n + t], aqk = A[q * n + t];
+          A[p * n + t] = t == q ? 0.0 : cs * apk - sn * aqk;
+          A[q * n + t] = t == p ? 0.0 : sn * apk + cs * aqk;
+          const double vkp = V[t * n + p], vkq = V[t * n + q];
+          V[t * n + p] = cs * vkp - sn * vkq;
+          V[t * n + q] = sn * vkp + cs * vkq;
+        }
+        __syncthreads();
+      }
+    if (!rotated) break;
+  }
+  return sweeps;
+}
+
+// The nearest proper rotation of the 3 x 3 matrix sh.W (row-major) -> sh.R, its singular values -> sh.sg: one-sided Jacobi
+// (rotations of column pairs until they are orthogonal: W V3 = U Sigma), then R = U diag(1, 1, det(U V3')) V3' with the sign on
+// the smallest singular value -- its column of U is taken as the cross product of the other two, which is that sign and
+// needs no division by a singular value that may be 0.  (one lane)
+__device__ __forceinline__ void nearest_rotation(RsShared &sh) {
+  for (int i = 0; i < 9; i++) sh.V3[i] = (i / 3 == i % 3) ? 1.0 : 0.0;
+#pragma nounroll
+  for (int sweep = 0; sweep < RS_SWEEPS; sweep++) {
+    int rotated = 0;
+#pragma nounroll
+    for (int p = 0; p < 2; p++)
+#pragma nounroll
+      for (int q = p + 1; q < 3; q++) {
+        double al = 0.0, be = 0.0, ga = 0.0;
+        for (int i = 0; i < 3; i++) {
+          const double wp = sh.W[3 * i + p], wq = sh.W[3 * i + q];
+          al += wp * wp;
+          be += wq * wq;
+          ga += wp * wq;
+        }
+        if (!(fabs(ga) > 1e-16 * sqrt(al * be))) continue;
+        rotated = 1;
+        const double ze = (be - al) / (2.0 * ga);
+        const double tt = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(ze * ze + 1.0));
+        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+        for (int i = 0; i < 3; i++) {
+          const double wp = sh.W[3 * i + p], wq = sh.W[3 * i + q];
+          sh.W[3 * i + p] = cs * wp - sn * wq;
+          sh.W[3 * i + q] = sn * wp + cs * wq;
+          const double vp = sh.V3[3 * i + p], vq = sh.V3[3 * i + q];
+          sh.V3[3 * i + p] = cs * vp - sn * vq;
+          sh.V3[3 * i + q] = sn * vp + cs * vq;
+        }
+      }
+    if (!rotated) break;
+  }
+  int jm = 0;
+  for (int j = 0; j < 3; j++) {
+    sh.sg[j] = sqrt((sh.W[j] * sh.W[j] + sh.W[3 + j] * sh.W[3 + j]) + sh.W[6 + j] * sh.W[6 + j]);
+    if (sh.sg[j] < sh.sg[jm]) jm = j;
+  }
+  const int ja = (jm + 1) % 3, jb = (jm + 2) % 3;  // (ja, jb, jm) is a cyclic order: det U = +1 = det V3
+  for (int i = 0; i < 3; i++) {
+    sh.U[3 * i + ja] = sh.W[3 * i + ja] / sh.sg[ja];
+    sh.U[3 * i + jb] = sh.W[3 * i + jb] / sh.sg[jb];
+  }
+  for (int i = 0; i < 3; i++) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
+    sh.U[3 * i + jm] = sh.U[3 * i1 + ja] * sh.U[3 * i2 + jb] - sh.U[3 * i2 + ja] * sh.U[3 * i1 + jb];
+  }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++)
+      sh.R[3 * i + j] = (sh.U[3 * i] * sh.V3[3 * j] + sh.U[3 * i + 1] * sh.V3[3 * j + 1]) + sh.U[3 * i + 2] * sh.V3[3 * j + 2];
+}
+
+// The rotation vector of sh.R -> sh.r: theta = atan2(|w| / 2, (tr R - 1) / 2), w the skew part; the axis is w / |w|, and for
+// cos theta < 0 it comes from the diagonal of R + I (k_i^2 = (R_ii - cos) / (1 - cos) at the largest R_ii, the others from the
+// symmetric part, the sign from w); theta < 1e-12: (1e-12, 0, 0) -- the model has no theta -> 0 branch.  (one lane)
+__device__ __forceinline__ void rotation_vector(RsShared &sh) {
+  const double *R = sh.R;
+  const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
+  const double wn = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+  const double co = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  const double th = atan2(0.5 * wn, co);
+  if (th < 1e-12) {
+    sh.r[0] = 1e-12, sh.r[1] = 0.0, sh.r[2] = 0.0;
+  } else if (co >= 0.0) {
+    sh.r[0] = th * (w0 / wn), sh.r[1] = th * (w1 / wn), sh.r[2] = th * (w2 / wn);
+  } else {
+    int im = 0;
+    if (R[4] > R[0]) im = 1;
+    if (R[8] > R[4 * im]) im = 2;
+    const double ki = sqrt((R[4 * im] - co) / (1.0 - co));
+    for (int j = 0; j < 3; j++) sh.r[j] = j == im ? ki : 0.5 * (R[3 * im + j] + R[3 * j + im]) / ((1.0 - co) * ki);
+    const double sgn = (sh.r[0] * w0 + sh.r[1] * w1) + sh.r[2] * w2 < 0.0 ? -1.0 : 1.0;
+    const double kn = sqrt((sh.r[0] * sh.r[0] + sh.r[1] * sh.r[1]) + sh.r[2] * sh.r[2]);
+    for (int j = 0; j < 3; j++) sh.r[j] = th * (sgn * sh.r[j] / kn);
+  }
+}
+
+// One camera per workgroup: the pose (r, t) of xc from the camera's observations with Lambda != 0, its intrinsics and the held
+// points; the pose of x is not read.  a.resect[c] <- RS_DONE (pose written), RS_SKIPPED (a pose component is held: nothing is
+// done) or RS_DEGENERATE (nothing written).  The control flow is uniform over the workgroup.
+__global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
+  __shared__ RsShared sh;
+  const int t = threadIdx.x;
+  const int c = (int)blockIdx.x;
+  const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
+  double *xc = a.xc + 9 * (int64_t)c;
+  const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  if (fm & CM_POSE) {
+    if (t == 0) a.resect[c] = RS_SKIPPED;
+    return;
+  }
+  const double ck1 = xc[6], ck2 = xc[7], cf = xc[8];
+  // the provisional origin: the point of the first observation of the list with Lambda != 0
+  int first = k1;
+  for (int k = k0 + t; k < k1; k += CM_BLK)
+    if (obs_used(a, a.cam_obs[k])) {
+      first = k;
+      break;
+    }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
+  if ((t & 63) == 0) sh.first[t >> 6] = first;
+  __syncthreads();
+  first = min(min(sh.first[0], sh.first[1]), min(sh.first[2], sh.first[3]));
+  if (first >= k1 || !isfinite(cf) || cf == 0.0) {
+    if (t == 0) a.resect[c] = RS_DEGENERATE;
+    return;
+  }
+  double org[3];
+  {
+    const double *xp = a.x + 3 * (int64_t)a.pnt0[a.cam_obs[first]];
+    org[0] = xp[0], org[1] = xp[1], org[2] = xp[2];
+  }
+  // the number of used observations, their mean and their RMS distance from it
+  double mo[5] = {0, 0, 0, 0, 0};
+  for (int k = k0 + t; k < k1; k += CM_BLK) {
+    const int o = a.cam_obs[k];
+    if (!obs_used(a, o)) continue;
+    const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
+    const double d0 = xp[0] - org[0], d1 = xp[1] - org[1], d2 = xp[2] - org[2];
+    mo[0] += 1.0;
+    mo[1] += d0, mo[2] += d1, mo[3] += d2;
+    mo[4] += (d0 * d0 + d1 * d1) + d2 * d2;
+  }
+  block_sums<5>(mo, sh, t);
+  const double n = mo[0];
+  const double dm[3] = {mo[1] / n, mo[2] / n, mo[3] / n};
+  const double var = mo[4] / n - ((dm[0] * dm[0] + dm[1] * dm[1]) + dm[2] * dm[2]);
+  if (n < (double)RS_MIN_OBS || !(var > 0.0) || !isfinite(var)) {
+    if (t == 0) a.resect[c] = RS_DEGENERATE;
+    return;
+  }
+  const double sc = 1.0 / sqrt(var);
+  // the moments
+  double acc[RS_SUMS];
+#pragma unroll
+  for (int i = 0; i < RS_SUMS; i++) acc[i] = 0.0;
+  for (int k = k0 + t; k < k1; k += CM_BLK) {
+    const int o = a.cam_obs[k];
+    if (!obs_used(a, o)) continue;
+    const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
+    const double h[4] = {sc * ((xp[0] - org[0]) - dm[0]), sc * ((xp[1] - org[1]) - dm[1]), sc * ((xp[2] - org[2]) - dm[2]), 1.0};
+    const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
+    const double ux = m.x / cf, uy = m.y / cf;
+    double qx = ux, qy = uy;
+#pragma unroll
+    for (int it = 0; it < RS_UNDIST_ITERS; it++) {
+      const double n2 = qx * qx + qy * qy;
+      const double den = 1.0 + ck1 * n2 + ck2 * (n2 * n2);
+      qx = ux / den;
+      qy = uy / den;
+    }
+    const double q2 = qx * qx + qy * qy;
+    int tt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = 0; j <= i; j++, tt++) {
+        const double hh = h[i] * h[j];
+        acc[tt] += hh;
+        acc[10 + tt] += qx * hh;
+        acc[20 + tt] += qy * hh;
+        acc[30 + tt] += q2 * hh;
+      }
+  }
+  block_sums<RS_SUMS>(acc, sh, t);
+  if (t == 0) {
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < RS_SUMS; i++) ok = ok && isfinite(acc[i]);
+    // M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]] from the packed sums, which go through sh.red's first row so that the loops
+    // index LDS (a lane of another wave may still be reading that row in block_sums: its copy of the sums is not used again)
+#pragma unroll
+    for (int i = 0; i < RS_SUMS; i++) sh.red[0][i] = acc[i];
+    for (int i = 0; i < 4; i++)
+      for (int j = 0; j < 4; j++) {
+        const int hi = i > j ? i : j, lo = i > j ? j : i, tt = hi * (hi + 1) / 2 + lo;
+        const double s0 = sh.red[0][tt], sx = sh.red[0][10 + tt], sy = sh.red[0][20 + tt], sq = sh.red[0][30 + tt];
+        sh.M[i * 12 + j] = s0, sh.M[i * 12 + 4 + j] = 0.0, sh.M[i * 12 + 8 + j] = sx;
+        sh.M[(4 + i) * 12 + j] = 0.0, sh.M[(4 + i) * 12 + 4 + j] = s0, sh.M[(4 + i) * 12 + 8 + j] = sy;
+        sh.M[(8 + i) * 12 + j] = sx, sh.M[(8 + i) * 12 + 4 + j] = sy, sh.M[(8 + i) * 12 + 8 + j] = sq;
+      }
+    sh.stop = ok ? 0 : 1;
+  }
+  __syncthreads();
+  if (sh.stop) {
+    if (t == 0) a.resect[c] = RS_DEGENERATE;
+    return;
+  }
+  jacobi_eig(sh.M, sh.V, 12, t);
+  if (t == 0) {
+    int i1 = 0;
+    double l1 = sh.M[0], lmax = sh.M[0];
+    for (int i = 1; i < 12; i++) {
+      const double l = sh.M[13 * i];
+      if (l < l1) l1 = l, i1 = i;
+      lmax = fmax(lmax, l);
+    }
+    double l2 = lmax;
+    for (int i = 0; i < 12; i++)
+      if (i != i1) l2 = fmin(l2, sh.M[13 * i]);
+    const bool ok = isfinite(l1) && isfinite(lmax) && l2 > 1e-10 * lmax;
+    if (ok) {
+      for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) sh.W[3 * i + j] = sh.V[(4 * i + j) * 12 + i1];
+        sh.r[i] = sh.V[(4 * i + 3) * 12 + i1];  // b, until the rotation vector takes its place
+      }
+      for (int j = 0; j < 4; j++) sh.a3[j] = sh.V[(8 + j) * 12 + i1];
+    }
+    sh.front = 0;
+    sh.stop = ok ? 0 : 1;
+  }
+  __syncthreads();
+  if (sh.stop) {
+    if (t == 0) a.resect[c] = RS_DEGENERATE;
+    return;
+  }
+  {  // the used points in front of the camera under the eigenvector's sign: A3 . X~ + b3 < 0
+    int front = 0;
+    const double a0 = sh.a3[0], a1 = sh.a3[1], a2 = sh.a3[2], b3 = sh.a3[3];
+    for (int k = k0 + t; k < k1; k += CM_BLK) {
+      const int o = a.cam_obs[k];
+      if (!obs_used(a, o)) continue;
+      const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
+      const double z = ((a0 * (sc * ((xp[0] - org[0]) - dm[0])) + a1 * (sc * ((xp[1] - org[1]) - dm[1]))) +
+                        a2 * (sc * ((xp[2] - org[2]) - dm[2]))) + b3;
+      if (z < 0.0) front++;
+    }
+    if (front) atomicAdd(&sh.front, front);
+  }
+  __syncthreads();
+  if (t == 0) {
+    const double sgn = 2.0 * (double)sh.front >= n ? 1.0 : -1.0;
+    for (int i = 0; i < 9; i++) sh.W[i] *= sgn;
+    nearest_rotation(sh);
+    const double gam = sc * (((sh.sg[0] + sh.sg[1]) + sh.sg[2]) / 3.0);
+    double tr[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {  // t = b / gamma - R m, m = origin + mean
+      const double rm = (sh.R[3 * i] * (org[0] + dm[0]) + sh.R[3 * i + 1] * (org[1] + dm[1])) + sh.R[3 * i + 2] * (org[2] + dm[2]);
+      tr[i] = sgn * sh.r[i] / gam - rm;
+    }
+    rotation_vector(sh);
+    const bool ok = isfinite(sh.r[0]) && isfinite(sh.r[1]) && isfinite(sh.r[2]) && isfinite(tr[0]) && isfinite(tr[1]) && isfinite(tr[2]);
+    if (ok) {
+      xc[0] = sh.r[0], xc[1] = sh.r[1], xc[2] = sh.r[2];
+      xc[3] = tr[0], xc[4] = tr[1], xc[5] = tr[2];
+    }
+    a.resect[c] = ok ? RS_DONE : RS_DEGENERATE;
+  }
+}
+
 }  // namespace
 
 // the per-camera lookups of the priors (once per ba_lm_set_priors) and the effective mask (once per ba_lm_set_fixed /
@@ -386,15 +739,15 @@ static int camera_check(const char *who, ba_problem *p, const double *x, int *ma
   return BA_OK;
 }
 
-// k_refine_cameras on st; the counters stay on the device (p->cams.counts)
-static int camera_launch(ba_problem *p, double *d_x, int max_iter, double xtol, double lambda0, uint8_t *d_status, double *d_cost,
-                         hipStream_t st) {
+// (resect: k_resect_cameras, then) k_refine_cameras on st; the counters stay on the device (p->cams.counts)
+static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                         double *d_cost, hipStream_t st) {
   BA_CHECK(terms_upload(p));
   BA_CHECK(camera_tables(p));
   CameraWork &w = p->cams;
   BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, CM_COUNTERS * sizeof(unsigned long long), st));
   if (p->ncams == 0) return BA_OK;
-  ProfScope ps(p, PC_REFINE_CAMERAS, st);
+  if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
   const PriorSet &cm = p->pri[PRI_CAM], &ct = p->pri[PRI_CTR];
   CamArgs a;
   a.cam_ptr = p->cam_ptr, a.cam_obs = p->cam_obs, a.pnt0 = p->pnt0;
@@ -404,8 +757,15 @@ static int camera_launch(ba_problem *p, double *d_x, int max_iter, double xtol, 
   a.cam_mu = cm.n > 0 ? (const double *)cm.mu : nullptr, a.cam_info = cm.n > 0 ? (const double *)cm.info : nullptr;
   a.ctr_mu = ct.n > 0 ? (const double *)ct.mu : nullptr, a.ctr_info = ct.n > 0 ? (const double *)ct.info : nullptr;
   a.x = d_x, a.xc = d_x + 3 * p->npnts, a.status = d_status, a.cost = d_cost, a.counts = w.counts;
+  a.resect = resect ? (uint8_t *)w.resect : nullptr;
   a.max_iter = max_iter, a.kind = p->loss;
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
+  if (resect) {  // the start poses, written into d_x on the same stream
+    ProfScope ps(p, PC_RESECT_CAMERAS, st);
+    hipLaunchKernelGGL(k_resect_cameras, dim3((unsigned)p->ncams), dim3(CM_BLK), 0, st, a);
+    BA_HIP_CHECK(hipGetLastError());
+  }
+  ProfScope ps(p, PC_REFINE_CAMERAS, st);
   hipLaunchKernelGGL(k_refine_cameras, dim3((unsigned)p->ncams), dim3(CM_BLK), 0, st, a);
   BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
@@ -423,18 +783,18 @@ static int camera_counts(ba_problem *p, int64_t *counts, int *iters_max, hipStre
   return BA_OK;
 }
 
-extern "C" int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
-                                     double *d_cost, int64_t *counts, int *iters_max, void *stream) {
-  BA_CHECK(camera_check("ba_refine_cameras_dev", p, d_x_inout, &max_iter, &xtol, &lambda0));
+static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, bool resect, int max_iter, double xtol, double lambda0,
+                              uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, void *stream) {
+  BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, resect, max_iter, xtol, lambda0, d_status, d_cost, st));
   return camera_counts(p, counts, iters_max, st);
 }
 
-extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
-                                 double *cost, int64_t *counts, int *iters_max) {
-  BA_CHECK(camera_check("ba_refine_cameras", p, x_inout, &max_iter, &xtol, &lambda0));
+static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, bool resect, int max_iter, double xtol, double lambda0,
+                               uint8_t *status, double *cost, int64_t *counts, int *iters_max) {
+  BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
   hipStream_t st = p->stream;
@@ -444,8 +804,8 @@ extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, d
   if (status && !w.status) BA_CHECK(w.status.alloc(p->ncams));
   if (cost && !w.cost) BA_CHECK(w.cost.alloc(2 * p->ncams));
   BA_HIP_CHECK(hipMemcpyAsync(dx, x_inout, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
-  BA_CHECK(camera_launch(p, dx, max_iter, xtol, lambda0, status ? (uint8_t *)w.status : nullptr, cost ? (double *)w.cost : nullptr,
-                         st));
+  BA_CHECK(camera_launch(p, dx, resect, max_iter, xtol, lambda0, status ? (uint8_t *)w.status : nullptr,
+                         cost ? (double *)w.cost : nullptr, st));
   if (p->ncams > 0) {  // the cameras only: the point part of the caller's x is never written
     BA_HIP_CHECK(hipMemcpyAsync(x_inout + 3 * p->npnts, dx + 3 * p->npnts, (size_t)9 * p->ncams * sizeof(double), hipMemcpyDeviceToHost,
                                 st));
@@ -454,4 +814,26 @@ extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, d
   }
   BA_HIP_CHECK(hipStreamSynchronize(st));
   return camera_counts(p, counts, iters_max, st);
+}
+
+extern "C" int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                                     double *d_cost, int64_t *counts, int *iters_max, void *stream) {
+  return refine_cameras_dev("ba_refine_cameras_dev", p, d_x_inout, false, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+                            stream);
+}
+
+extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
+                                 double *cost, int64_t *counts, int *iters_max) {
+  return refine_cameras_host("ba_refine_cameras", p, x_inout, false, max_iter, xtol, lambda0, status, cost, counts, iters_max);
+}
+
+extern "C" int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                                     double *d_cost, int64_t *counts, int *iters_max, void *stream) {
+  return refine_cameras_dev("ba_resect_cameras_dev", p, d_x_inout, true, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+                            stream);
+}
+
+extern "C" int ba_resect_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
+                                 double *cost, int64_t *counts, int *iters_max) {
+  return refine_cameras_host("ba_resect_cameras", p, x_inout, true, max_iter, xtol, lambda0, status, cost, counts, iters_max);
 }

@@ -225,6 +225,7 @@ enum ProfClass {
   PC_INFO,           // per-observation information (ba_lm_set_obs_info): "k_info_whiten": k_obs_scale on a handle with it, the whitening of r and J (with the loss's reweighting)
   PC_REFINE_POINTS,  // points with the cameras held (ba_refine_points): k_cam_pre and k_refine_points
   PC_REFINE_CAMERAS,  // cameras with the points held (ba_refine_cameras): k_refine_cameras
+  PC_RESECT_CAMERAS,  // linear resection before it (ba_resect_cameras): k_resect_cameras
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -342,15 +343,15 @@ struct PointWork {
 // cameras with the points held (ba_refine_cameras, ba_camera_kernels.hip): per camera the index of its camera prior and of its
 // centre prior (-1: none; rebuilt when ba_lm_set_priors changed them) and the effective 9-bit mask of held components -- the
 // mask of ba_lm_set_fixed with the bits of (k1, k2, f) set for every member of a calibration group (rebuilt when
-// ba_lm_set_fixed or ba_lm_set_shared_intrinsics changed them) --, the eight device counters of a call and the host entry's
-// status / cost staging
+// ba_lm_set_fixed or ba_lm_set_shared_intrinsics changed them) --, the eight device counters of a call, the host entry's
+// status / cost staging and the byte per camera that k_resect_cameras leaves for k_refine_cameras (ba_resect_cameras)
 struct CameraWork {
   DevBuf<int> cam_pri_of, ctr_pri_of;
   DevBuf<uint16_t> mask;
   bool mask_on = false;
   int64_t pri_version = -1, fix_version = -1, grp_version = -1;
   DevBuf<unsigned long long> counts;
-  DevBuf<uint8_t> status;
+  DevBuf<uint8_t> status, resect;
   DevBuf<double> cost;
 };
 

@@ -297,12 +297,16 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
     return x, info
 
 
-def refine_cameras(nlp, x, *, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
+def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
                    fixed_camera_params=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
     """The cameras of x with its points held (ba_refine_cameras), the other half of refine_points: every camera is an independent
     problem in at most 9 unknowns -- the objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info`, `camera_priors`
     and `centre_priors`, restricted to that camera -- solved by a Marquardt iteration of its own (accept test, damping and
-    stopping test per camera).  max_iter (None: 100; 0: evaluate only), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
+    stopping test per camera).  resect=True starts every camera whose pose is free from the linear resection of its 2D-3D
+    correspondences instead of from x (ba_resect_cameras: the pose of x is then not read, NaN included; a camera with a held
+    pose component starts from x as before; fewer than 6 observations or a degenerate configuration: `degenerate`, untouched):
+    how new images are registered against a structure, and with refine_points(triangulate=True) how an x0 is built.
+    max_iter (None: 100; 0: evaluate only -- with resect=True the resected poses are returned), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
     D_j = sqrt(H_jj): the predicted motion in pixels), lam0 (None: 1e-4).  fixed_camera_params hold components (("k1", "k2",
     "f"): a pose-only refit); fixed_cameras are skipped; the members of the groups of shared_intrinsics keep their (k1, k2, f).
     Returns (x_new, info): x_new a copy of x with the cameras replaced (points, held components and skipped cameras
@@ -312,6 +316,8 @@ def refine_cameras(nlp, x, *, max_iter=None, xtol=None, lam0=None, loss=None, f_
     terms = _lib.ProblemTerms("linear" if loss is None else loss, f_scale, fixed_cameras=fixed_cameras,
                               fixed_camera_params=fixed_camera_params, camera_priors=camera_priors, centre_priors=centre_priors,
                               shared_intrinsics=shared_intrinsics, obs_info=obs_info)
+    if not isinstance(resect, (bool, np.bool_)):
+        raise ValueError(f"resect must be True or False, got {resect!r}")
     if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
         raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
     tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
@@ -325,9 +331,9 @@ def refine_cameras(nlp, x, *, max_iter=None, xtol=None, lam0=None, loss=None, f_
     cost = np.zeros((nlp.ncams, 2))
     counts = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64)
     its = C.c_int(0)
-    _lib.check(_lib.lib().ba_refine_cameras(nlp.handle, _lib.ptr(x), -1 if max_iter is None else int(max_iter),
-                                            -1.0 if tol is None else tol, -1.0 if l0 is None else l0, _lib.ptr(status),
-                                            _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
+    entry = _lib.lib().ba_resect_cameras if resect else _lib.lib().ba_refine_cameras
+    _lib.check(entry(nlp.handle, _lib.ptr(x), -1 if max_iter is None else int(max_iter), -1.0 if tol is None else tol,
+                     -1.0 if l0 is None else l0, _lib.ptr(status), _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
     names = np.array(_lib.POINT_STATES)
     info = dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
                 cost_after=cost[:, 1].copy(), iters_max=its.value,

@@ -513,12 +513,57 @@ int ba_refine_points_dev(ba_problem *p, double *d_x_inout /* nvar, device */, in
  * same bits as without this call in between.
  * ba_refine_cameras_dev: x, status and cost in device memory, enqueued on `stream` (NULL: the handle's); with counts and
  * iters_max both NULL it does not synchronise, otherwise it waits for the stream to hand them over.
- * Out of scope: a pose from scratch (DLT / P3P: an eigen-solve), Float32, refinement inside the LM loop, the tied
- * (shared-intrinsics) problem over a group, several ranks. */
+ * Out of scope: Float32, refinement inside the LM loop, the tied (shared-intrinsics) problem over a group, several ranks.  (A
+ * pose from scratch is ba_resect_cameras, below.) */
 int ba_refine_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
                       uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
                       int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
 int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int max_iter, double xtol, double lambda0,
+                          uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
+                          int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
+
+/* ---- linear camera resection as the start of ba_refine_cameras (an extension: the reference has no resection) --------------
+ * ba_refine_cameras started from a closed-form pose per camera, computed on the device from the camera's 2D-3D correspondences:
+ * what init = 1 (the triangulation) is to ba_refine_points.  Arguments, results, states, counts and refusals are those of
+ * ba_refine_cameras; only the start differs.
+ * Which cameras: a camera with all 9 components held is BA_PT_FIXED as before.  A camera with ANY pose component (mask bits 0..5
+ * of ba_lm_set_fixed) held is not resected: it starts from x exactly as in ba_refine_cameras and its result has those bits.
+ * Every other camera is resected, whatever its pose in x is (NaN included: the pose (r, t) of x is never read).  Held intrinsics
+ * (mask bits 6..8, the members of a group) do not prevent it.  Camera priors, centre priors, the loss and the whitening by the
+ * information (beyond the Lambda = 0 test) act only in the refinement that follows.
+ * The resection of camera c, its intrinsics (k1, k2, f) read from x and held:
+ *  1. Every observation o of c with Lambda_o != 0 is used, unweighted.  Its measurement is undistorted as in ba_refine_points:
+ *     u = pt2d / f, then 8 iterations of q <- u / (1 + k1 |q|^2 + k2 |q|^4).
+ *  2. With P = R X + t the BAL projection gives q = -P.xy / P.z: P.x + q_x P.z = 0 and P.y + q_y P.z = 0, two homogeneous linear
+ *     equations in the 12 entries of [R | t].  The points are normalised first (Hartley): X~ = s (X - m), m the mean of the used
+ *     points and 1 / s their RMS distance from m (the sums are taken about the first used point of the list, so that none
+ *     cancels); the unknown becomes gamma [R / s | R m + t].
+ *  3. With h = (X~, 1) the 12 x 12 normal matrix is M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]], S0 = sum h h', Sx = sum q_x h h',
+ *     Sy = sum q_y h h', Sq = sum |q|^2 h h'.
+ *  4. The eigenvector of the smallest eigenvalue of M (cyclic Jacobi sweeps), lambda_1 <= ... <= lambda_12.
+ *  5. BA_PT_DEGENERATE: fewer than 6 used observations; f not finite or zero; used points that all coincide; a moment that is
+ *     not finite; lambda_2 <= 1e-10 lambda_12 (coplanar points and other configurations with a second solution: the counterpart
+ *     of the triangulation's "pivot <= 1e-12 trace"); a recovered pose that is not finite.
+ *  6. The eigenvector is split into A (3 x 3, rows as found) and b (3), with the sign that puts the majority of the used points
+ *     in front (A_3 . X~ + b_3 < 0: the BAL camera looks down -z).  R = U diag(1, 1, det(U V')) V' from A = U Sigma V', the
+ *     nearest proper rotation; gamma = s mean(Sigma); t = b / gamma - R m.
+ *  7. r from R: theta = atan2(|w| / 2, (tr R - 1) / 2) with w the skew part of R, axis w / |w|; for cos theta < 0 the axis comes
+ *     from the diagonal of R + I (sign from w); theta < 1e-12 gives r = (1e-12, 0, 0) -- the model has no theta -> 0 branch and
+ *     evaluates NaN at r = 0.
+ *  8. The Marquardt iteration of ba_refine_cameras runs unchanged from that pose.
+ * A resected camera that is DEGENERATE comes back bit-unchanged, cost entries 0, no BEHIND flag (as a point the triangulation
+ * cannot place).  cost[2 c] is f_c at the resected pose.  max_iter == 0 writes the resected pose into x (state MAX_ITER, both
+ * cost entries f_c at that pose), as init = 1 with max_iter = 0 writes the triangulated points.  A camera whose cost at the
+ * resected pose is not finite is NONFINITE and keeps the resected pose.
+ * A camera's result depends on its own data and the order of its observations only (no floating-point atomics); two calls give
+ * the same bits; the next ba_lm_step / ba_lm_solve on the handle gives the same bits as without this call in between.  A handle
+ * with a communicator is refused (BA_ERR_ARG).
+ * Out of scope: RANSAC or other outlier rejection inside the linear solve (the robust loss acts in the refinement), unknown
+ * intrinsics (a full 3 x 4 DLT with RQ), minimal P3P, Float32, several ranks, resection inside the LM loop. */
+int ba_resect_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
+                      uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
+                      int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
+int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int max_iter, double xtol, double lambda0,
                           uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
                           int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
 

@@ -155,3 +155,32 @@ function refine_cameras!(nlp, x :: Vector{Float64}; max_iter :: Integer = -1, xt
   end
   return status, cost, counts, Int(iters[])
 end
+
+# linear camera resection as the start of refine_cameras! (an extension): include/ba_hip.h, ba_resect_cameras.  Every camera
+# whose pose is free starts from the closed-form pose of its 2D-3D correspondences (the pose entries of `x` are not read, NaN
+# included; fewer than 6 observations or a degenerate configuration: BA_PT_DEGENERATE, untouched); a camera with a held pose
+# component starts from `x` as in refine_cameras!.  `max_iter = 0` returns the resected poses.  Same return values.
+function resect_cameras!(nlp, x :: Vector{Float64}; max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  GC.@preserve x status cost counts begin
+    bacheck(ccall((:ba_resect_cameras, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint}),
+                  nlp.handle, pointer(x), Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters))
+  end
+  return status, cost, counts, Int(iters[])
+end
+
+# the device-resident form: d_x, d_status (or C_NULL) and d_cost (or C_NULL) are device pointers (ba_dev_malloc); enqueued on
+# `stream` (C_NULL: the handle's) and not synchronised -- counts and iters_max are not fetched
+function resect_cameras_dev!(nlp, d_x :: Ptr{Cvoid}; max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0,
+                             d_status :: Ptr{Cvoid} = C_NULL, d_cost :: Ptr{Cvoid} = C_NULL, stream :: Ptr{Cvoid} = C_NULL)
+  bacheck(ccall((:ba_resect_cameras_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint}, Ptr{Cvoid}),
+                nlp.handle, d_x, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), stream))
+  return nothing
+end

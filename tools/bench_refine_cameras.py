@@ -8,8 +8,14 @@ shapes, against the fixed-point LM solve on the same scene.
            (srtol = xtol, every other test off): its loop time, iterations, and how far its cameras end from refine's (the
            largest relative difference of a camera block)
 
-One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (or the file given).
-usage: python tools/bench_refine_cameras.py [out.json] [reps] [shape ...]"""
+  --resect the same clocks around ba_resect_cameras_dev from an x0 whose camera poses are all NaN: the linear
+           resection and the refinement from its poses; event times of both launches (profile classes k_resect_cameras and
+           k_refine_cameras), the states, the most trials, and the sum of the cameras' costs against that of the refinement from
+           the generator's x0.  No LM leg: nothing else starts from NaN poses.
+
+One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (--resect: profiles/resect_cameras_bench.json),
+or the file given.
+usage: python tools/bench_refine_cameras.py [--resect] [out.json] [reps] [shape ...]"""
 import ctypes as C
 import json
 import os
@@ -78,9 +84,54 @@ def measure(ba, name, reps):
     return row
 
 
+def measure_resect(ba, name, reps):
+    L, lib = ba._lib.lib(), ba._lib
+    p = ba.synthetic.make_named(name)
+    n, nc, nvar = p["npnts"], p["ncams"], len(p["x0"])
+    m = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(p))
+    deg = np.bincount(p["cam_idx1"] - 1, minlength=nc)
+    row = {"shape": name, "ncams": nc, "npnts": n, "nobs": p["nobs"], "xtol": XTOL, "degree_min": int(deg.min()),
+           "degree_median": int(np.median(deg)), "degree_max": int(deg.max())}
+    x0 = np.array(p["x0"], dtype=np.float64, copy=True)
+    x0[3 * n:].reshape(nc, 9)[:, :6] = np.nan
+    d_x = C.c_void_p()
+    lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
+    counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
+    lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+    lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, lib.ptr(counts), C.byref(its), None))  # warm-up
+    wall = []
+    for _ in range(reps):
+        lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+        t = time.perf_counter()
+        lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+        lib.check(L.ba_synchronize(m.handle))
+        wall.append(1e3 * (time.perf_counter() - t))
+    m.profile(True)
+    lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+    lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+    prof = m.profile_get()
+    m.profile(False)
+    lib.check(L.ba_dev_free(m.handle, d_x))
+    med = statistics.median(wall)
+    row["resect"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall],
+                     "k_resect_cameras_event_ms": round(prof["k_resect_cameras"][0], 3),
+                     "k_refine_cameras_event_ms": round(prof["k_refine_cameras"][0], 3), "iters_max": its.value,
+                     "counts": {k: int(v) for k, v in zip(lib.POINT_STATES + ("behind",), counts)}}
+    _, info = ba.refine_cameras(m, x0, resect=True, xtol=XTOL)
+    _, info0 = ba.refine_cameras(m, p["x0"], xtol=XTOL)
+    row["objective_resect"] = float(np.sum(info["cost_after"]))
+    row["objective_at_resected_poses"] = float(np.sum(info["cost_before"]))
+    row["objective_refine_from_x0"] = float(np.sum(info0["cost_after"]))
+    m.close()
+    return row
+
+
 def main():
     args = sys.argv[1:]
-    out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", "refine_cameras_bench.json")
+    resect = "--resect" in args
+    args = [a for a in args if a != "--resect"]
+    default = "resect_cameras_bench.json" if resect else "refine_cameras_bench.json"
+    out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", default)
     reps = int(args.pop(0)) if args and args[0].isdigit() else 5
     shapes = args or ["dubrovnik-356", "venice-1778"]
     ba = ge.load_package()
@@ -88,7 +139,7 @@ def main():
         sys.exit("bench_refine_cameras: no HIP device visible (nothing is measured without one)")
     rows = []
     for name in shapes:
-        row = measure(ba, name, reps)
+        row = (measure_resect if resect else measure)(ba, name, reps)
         print(json.dumps(row), flush=True)
         rows.append(row)
     with open(out, "w") as fh:
