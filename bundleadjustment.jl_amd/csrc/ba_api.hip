@@ -56,6 +56,25 @@ int ba_scratch(ba_problem *p, int slot, size_t bytes, void **out) {
   return BA_OK;
 }
 
+// ---- host side of the block refinements (ba_internal.h) -------------------------------------------------------------------
+int block_prior_lookup(const PriorSet &set, int64_t nblocks, DevBuf<int> &out) {
+  if (set.n == 0) return BA_OK;
+  std::vector<int> of((size_t)nblocks, -1);
+  for (int64_t q = 0; q < set.n; q++) of[(size_t)set.h_idx[(size_t)q]] = (int)q;
+  return upload(out, of);
+}
+
+int block_counts(const BlockWork &w, int64_t *counts, int *iters_max, hipStream_t st) {
+  if (!counts && !iters_max) return BA_OK;
+  unsigned long long h[BLOCK_COUNTERS];
+  BA_HIP_CHECK(hipMemcpyAsync(h, w.counts, sizeof h, hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  if (counts)
+    for (int s = 0; s <= BA_PT_STATES; s++) counts[s] = (int64_t)h[s];
+  if (iters_max) *iters_max = (int)h[BA_PT_STATES + 1];
+  return BA_OK;
+}
+
 extern "C" int ba_problem_create(int device, int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1,
                                  const int64_t *pnt_idx1, const double *pt2d, ba_problem **out) {
   if (!out) return BA_ERR_ARG;

@@ -19,6 +19,9 @@
 //
 // ba_resect_cameras launches k_resect_cameras before it: the start pose of every camera whose pose is free, in
 // closed form from its 2D-3D correspondences (further down).
+//
+// What this file has in common with ba_point_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
+// (argument check, prior lookups, counter read-back, the body of the host-pointer entries; BlockWork) in ba_internal.h / ba_api.hip.
 #include <cmath>
 
 #include "ba_internal.h"
@@ -28,11 +31,11 @@ namespace {
 
 #include "ba_model_dev.h"  // CPAD, cam_pre, project_pre, jac_block
 #include "ba_prior_dev.h"  // centre_of
+#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS
 
 constexpr int CM_BLK = 256, CM_WAVES = CM_BLK / 64;
 constexpr int CM_SUMS = 55;                     // [f | g (9) | H (45, packed lower row-major)]
 constexpr int CM_G = 1, CM_H = 10;              // where g and H start
-constexpr int CM_COUNTERS = BA_PT_STATES + 2;   // [states | cameras flagged BEHIND | most trials of a camera]
 constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u, CM_POSE = 0x3Fu;
 enum { RS_DONE = 0, RS_SKIPPED = 1, RS_DEGENERATE = 2 };  // the byte per camera k_resect_cameras leaves for k_refine_cameras
 
@@ -61,12 +64,6 @@ struct CamShared {
   double e[9], w[9], Hc[18], M[18];   // prior terms
   int stop;
 };
-
-__device__ __forceinline__ double wave_all_sum(double v) {  // every lane receives the same bits (a + b == b + a)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // cam_pre row of the trial camera sh.Cn -> sh.P (one lane)
 __device__ __forceinline__ void trial_row(CamShared &sh) {
@@ -99,12 +96,9 @@ __device__ __forceinline__ void observation_sums(const CamArgs &a, CamShared &sh
     double out[2], J[24];
     project_pre<double>(X, P, out);
     jac_block<double>(X, P, J);  // (columns 3..11 of both rows are used: R, the point columns, is dead code)
-    {  // P1.z as jac_block forms it
-      const double kx = P[0], ky = P[1], kz = P[2], s = P[9], c = P[10];
-      const double d = kx * X[0] + ky * X[1] + kz * X[2];
-      const double z1 = ((c * X[2] + s * (kx * X[1] - ky * X[0])) + ((1 - c) * d) * kz) + P[5];
-      if (z1 >= 0.0) bh = 1;
-    }
+    double z1;
+    p1_z(P, X, z1);
+    if (z1 >= 0.0) bh = 1;
     const double ex = out[0] - m.x, ey = out[1] - m.y;
     const double rx = l00 * ex + l10 * ey, ry = l11 * ey;
     double w;
@@ -353,7 +347,6 @@ __global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
 // Sx = sum q_x h h', Sy = sum q_y h h', Sq = sum |q|^2 h h': 40 sums per lane, reduced as observation_sums reduces its 55.  The
 // eigenvector of M's smallest eigenvalue (cyclic Jacobi, M and the rotations in LDS) is gamma [R / s | R m + t].
 constexpr int RS_SUMS = 40;         // [S0 | Sx | Sy | Sq], each packed lower row-major (10)
-constexpr int RS_UNDIST_ITERS = 8;  // fixed-point iterations of q <- u / (1 + k1 |q|^2 + k2 |q|^4), as the triangulation's
 constexpr int RS_MIN_OBS = 6;       // 12 unknowns up to scale, two equations per observation
 constexpr int RS_SWEEPS = 30;       // cap of the Jacobi sweeps (12 x 12 and 3 x 3)
 
@@ -580,7 +573,7 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
     const double ux = m.x / cf, uy = m.y / cf;
     double qx = ux, qy = uy;
 #pragma unroll
-    for (int it = 0; it < RS_UNDIST_ITERS; it++) {
+    for (int it = 0; it < UNDIST_ITERS; it++) {
       const double n2 = qx * qx + qy * qy;
       const double den = 1.0 + ck1 * n2 + ck2 * (n2 * n2);
       qx = ux / den;
@@ -692,16 +685,10 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
 // ba_lm_set_shared_intrinsics)
 static int camera_tables(ba_problem *p) {
   CameraWork &w = p->cams;
-  if (!w.counts) BA_CHECK(w.counts.alloc(CM_COUNTERS));
+  if (!w.counts) BA_CHECK(w.counts.alloc(BLOCK_COUNTERS));
   if (w.pri_version != p->pri_version) {
-    const PriorSet *sets[2] = {&p->pri[PRI_CAM], &p->pri[PRI_CTR]};
-    DevBuf<int> *out[2] = {&w.cam_pri_of, &w.ctr_pri_of};
-    for (int k = 0; k < 2; k++) {
-      if (sets[k]->n == 0) continue;
-      std::vector<int> of((size_t)p->ncams, -1);
-      for (int64_t q = 0; q < sets[k]->n; q++) of[(size_t)sets[k]->h_idx[(size_t)q]] = (int)q;
-      BA_CHECK(upload(*out[k], of));
-    }
+    BA_CHECK(block_prior_lookup(p->pri[PRI_CAM], p->ncams, w.cam_pri_of));
+    BA_CHECK(block_prior_lookup(p->pri[PRI_CTR], p->ncams, w.ctr_pri_of));
     w.pri_version = p->pri_version;
   }
   if (w.fix_version != p->fix_version || w.grp_version != p->grp_version) {
@@ -721,22 +708,11 @@ static int camera_tables(ba_problem *p) {
 }
 
 static int camera_check(const char *who, ba_problem *p, const double *x, int *max_iter, double *xtol, double *lambda0) {
-  if (!p || (!x && p->npnts + p->ncams > 0)) {
-    ba_set_error("%s: null argument", who);
-    return BA_ERR_ARG;
-  }
-  if (p->comm.active()) {
+  return block_check(who, p, x, 100, max_iter, xtol, lambda0, [&] {
+    if (!p->comm.active()) return BA_OK;
     ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
     return BA_ERR_ARG;
-  }
-  if (!std::isfinite(*xtol) || !std::isfinite(*lambda0)) {
-    ba_set_error("%s: xtol and lambda0 must be finite (<= 0: the default), got %g and %g", who, *xtol, *lambda0);
-    return BA_ERR_ARG;
-  }
-  if (*max_iter < 0) *max_iter = 100;
-  if (*xtol <= 0) *xtol = 1e-10;
-  if (*lambda0 <= 0) *lambda0 = 1e-4;
-  return BA_OK;
+  });
 }
 
 // (resect: k_resect_cameras, then) k_refine_cameras on st; the counters stay on the device (p->cams.counts)
@@ -745,7 +721,7 @@ static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, 
   BA_CHECK(terms_upload(p));
   BA_CHECK(camera_tables(p));
   CameraWork &w = p->cams;
-  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, CM_COUNTERS * sizeof(unsigned long long), st));
+  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
   if (p->ncams == 0) return BA_OK;
   if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
   const PriorSet &cm = p->pri[PRI_CAM], &ct = p->pri[PRI_CTR];
@@ -771,49 +747,23 @@ static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, 
   return BA_OK;
 }
 
-// the device counters -> the caller's (synchronises st)
-static int camera_counts(ba_problem *p, int64_t *counts, int *iters_max, hipStream_t st) {
-  if (!counts && !iters_max) return BA_OK;
-  unsigned long long h[CM_COUNTERS];
-  BA_HIP_CHECK(hipMemcpyAsync(h, p->cams.counts, sizeof h, hipMemcpyDeviceToHost, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  if (counts)
-    for (int s = 0; s <= BA_PT_STATES; s++) counts[s] = (int64_t)h[s];
-  if (iters_max) *iters_max = (int)h[BA_PT_STATES + 1];
-  return BA_OK;
-}
-
 static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, bool resect, int max_iter, double xtol, double lambda0,
                               uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, void *stream) {
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
   BA_CHECK(camera_launch(p, d_x_inout, resect, max_iter, xtol, lambda0, d_status, d_cost, st));
-  return camera_counts(p, counts, iters_max, st);
+  return block_counts(p->cams, counts, iters_max, st);
 }
 
 static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, bool resect, int max_iter, double xtol, double lambda0,
                                uint8_t *status, double *cost, int64_t *counts, int *iters_max) {
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
-  BA_HIP_CHECK(hipSetDevice(p->device));
-  const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
-  hipStream_t st = p->stream;
-  CameraWork &w = p->cams;
-  double *dx;
-  BA_CHECK(ba_scratch(p, 0, (size_t)(nvar + 1) * sizeof(double), (void **)&dx));
-  if (status && !w.status) BA_CHECK(w.status.alloc(p->ncams));
-  if (cost && !w.cost) BA_CHECK(w.cost.alloc(2 * p->ncams));
-  BA_HIP_CHECK(hipMemcpyAsync(dx, x_inout, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
-  BA_CHECK(camera_launch(p, dx, resect, max_iter, xtol, lambda0, status ? (uint8_t *)w.status : nullptr,
-                         cost ? (double *)w.cost : nullptr, st));
-  if (p->ncams > 0) {  // the cameras only: the point part of the caller's x is never written
-    BA_HIP_CHECK(hipMemcpyAsync(x_inout + 3 * p->npnts, dx + 3 * p->npnts, (size_t)9 * p->ncams * sizeof(double), hipMemcpyDeviceToHost,
-                                st));
-    if (status) BA_HIP_CHECK(hipMemcpyAsync(status, w.status, (size_t)p->ncams, hipMemcpyDeviceToHost, st));
-    if (cost) BA_HIP_CHECK(hipMemcpyAsync(cost, w.cost, (size_t)2 * p->ncams * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  return camera_counts(p, counts, iters_max, st);
+  // the cameras only: the point part of the caller's x is never written
+  return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
+                          [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
+                            return camera_launch(p, dx, resect, max_iter, xtol, lambda0, d_status, d_cost, st);
+                          });
 }
 
 extern "C" int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,

@@ -1,6 +1,7 @@
 // Internal declarations shared by the translation units of libba_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string>
@@ -325,34 +326,38 @@ struct PriorSet {
 };
 enum { PRI_PNT = 0, PRI_CAM, PRI_CTR, PRI_KINDS };
 
-// points with the cameras held (ba_refine_points, ba_point_kernels.hip): the point list split by degree once per problem
-// (wave_pts: degree > the tier threshold, one wave each; lane_pts: the others, one lane each, by descending degree), the
-// per-point lookup of the point priors (-1: none; rebuilt when ba_lm_set_priors changed them), the eight device counters of a
-// call (BA_PT_STATES states, the BEHIND flags, the most trials of a point) and the host entry's status / cost staging
-struct PointWork {
-  bool split = false;
-  int64_t n_lane = 0, n_wave = 0;
-  DevBuf<int> lane_pts, wave_pts;
-  DevBuf<int> pri_of;
-  int64_t pri_version = -1;
+// ---- block refinement (ba_refine_points, ba_refine_cameras, ba_resect_cameras) ------------------------------------------------
+// One side of x is held and every block of the other side -- a point, a camera -- is its own small Marquardt problem.  What a
+// call keeps whichever side it refines, and what the shared host code (block_* below) works on: the host entry's status /
+// cost staging and the eight device counters
+constexpr int BLOCK_COUNTERS = BA_PT_STATES + 2;  // [states | blocks flagged BEHIND | most trials of a block]
+struct BlockWork {
   DevBuf<unsigned long long> counts;
   DevBuf<uint8_t> status;
   DevBuf<double> cost;
 };
 
-// cameras with the points held (ba_refine_cameras, ba_camera_kernels.hip): per camera the index of its camera prior and of its
-// centre prior (-1: none; rebuilt when ba_lm_set_priors changed them) and the effective 9-bit mask of held components -- the
-// mask of ba_lm_set_fixed with the bits of (k1, k2, f) set for every member of a calibration group (rebuilt when
-// ba_lm_set_fixed or ba_lm_set_shared_intrinsics changed them) --, the eight device counters of a call, the host entry's
-// status / cost staging and the byte per camera that k_resect_cameras leaves for k_refine_cameras (ba_resect_cameras)
-struct CameraWork {
+// points with the cameras held (ba_point_kernels.hip): the point list split by degree once per problem (wave_pts: degree > the
+// tier threshold, one wave each; lane_pts: the others, one lane each, by descending degree) and the per-point lookup of the
+// point priors (block_prior_lookup; rebuilt when ba_lm_set_priors changed them)
+struct PointWork : BlockWork {
+  bool split = false;
+  int64_t n_lane = 0, n_wave = 0;
+  DevBuf<int> lane_pts, wave_pts;
+  DevBuf<int> pri_of;
+  int64_t pri_version = -1;
+};
+
+// cameras with the points held (ba_camera_kernels.hip): the per-camera lookups of the camera and of the centre priors (rebuilt
+// when ba_lm_set_priors changed them), the effective 9-bit mask of held components -- the mask of ba_lm_set_fixed with the bits
+// of (k1, k2, f) set for every member of a calibration group (rebuilt when ba_lm_set_fixed or ba_lm_set_shared_intrinsics
+// changed them) -- and the byte per camera that k_resect_cameras leaves for k_refine_cameras (ba_resect_cameras)
+struct CameraWork : BlockWork {
   DevBuf<int> cam_pri_of, ctr_pri_of;
   DevBuf<uint16_t> mask;
   bool mask_on = false;
   int64_t pri_version = -1, fix_version = -1, grp_version = -1;
-  DevBuf<unsigned long long> counts;
-  DevBuf<uint8_t> status, resect;
-  DevBuf<double> cost;
+  DevBuf<uint8_t> resect;
 };
 
 struct ba_problem {
@@ -452,6 +457,54 @@ struct ProfScope {
 };
 
 int ba_scratch(ba_problem *p, int slot, size_t bytes, void **out);
+
+// ---- host side of the block refinements (ba_api.hip; the two with a callable here) ----------------------------------------
+// out <- the table "block -> its prior of `set`, or -1" over nblocks blocks; nothing for an empty set
+int block_prior_lookup(const PriorSet &set, int64_t nblocks, DevBuf<int> &out);
+// the device counters of w -> the caller's (either may be null; synchronises st)
+int block_counts(const BlockWork &w, int64_t *counts, int *iters_max, hipStream_t st);
+
+// The argument tests of an entry, `who` in their messages: null arguments, then own() -- the entry's own refusal, BA_OK or an
+// error it has set --, then finite tolerances; values below their range become the defaults.
+template <typename Own>
+int block_check(const char *who, ba_problem *p, const double *x, int max_iter_default, int *max_iter, double *xtol, double *lambda0, Own own) {
+  if (!p || (!x && p->npnts + p->ncams > 0)) {
+    ba_set_error("%s: null argument", who);
+    return BA_ERR_ARG;
+  }
+  BA_CHECK(own());
+  if (!std::isfinite(*xtol) || !std::isfinite(*lambda0)) {
+    ba_set_error("%s: xtol and lambda0 must be finite (<= 0: the default), got %g and %g", who, *xtol, *lambda0);
+    return BA_ERR_ARG;
+  }
+  if (*max_iter < 0) *max_iter = max_iter_default;
+  if (*xtol <= 0) *xtol = 1e-10;
+  if (*lambda0 <= 0) *lambda0 = 1e-4;
+  return BA_OK;
+}
+
+// The body of a host-pointer entry: x into scratch, launch(d_x, d_status, d_cost, st), back the refined part of x (n blocks of
+// `per` doubles from `offset` on: the rest of the caller's x is never written) with its status and cost, then the counters.
+template <typename Launch>
+int block_host_entry(ba_problem *p, BlockWork &w, double *x_inout, int64_t n, int per, int64_t offset, uint8_t *status, double *cost,
+                     int64_t *counts, int *iters_max, Launch launch) {
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
+  hipStream_t st = p->stream;
+  double *dx;
+  BA_CHECK(ba_scratch(p, 0, (size_t)(nvar + 1) * sizeof(double), (void **)&dx));
+  if (status && !w.status) BA_CHECK(w.status.alloc(n));
+  if (cost && !w.cost) BA_CHECK(w.cost.alloc(2 * n));
+  BA_HIP_CHECK(hipMemcpyAsync(dx, x_inout, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
+  BA_CHECK(launch(dx, status ? (uint8_t *)w.status : nullptr, cost ? (double *)w.cost : nullptr, st));
+  if (n > 0) {
+    BA_HIP_CHECK(hipMemcpyAsync(x_inout + offset, dx + offset, (size_t)per * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (status) BA_HIP_CHECK(hipMemcpyAsync(status, w.status, (size_t)n, hipMemcpyDeviceToHost, st));
+    if (cost) BA_HIP_CHECK(hipMemcpyAsync(cost, w.cost, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return block_counts(w, counts, iters_max, st);
+}
 
 // ---- launchers (ba_model_kernels.hip) -----------------------------------------------------------
 int launch_residual_f64(ba_problem *p, const double *d_x, double *d_r, hipStream_t st);

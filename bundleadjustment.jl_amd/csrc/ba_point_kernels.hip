@@ -14,6 +14,9 @@
 // with an xor butterfly (every lane ends with the same bits, the wave then runs the 3 x 3 algebra uniformly).  A point is always
 // in the same tier and its sums have a fixed order, so the result of a point depends on nothing but its own data.  No
 // floating-point atomics; the eight counters of a call (states, BEHIND flags, most trials) are integers, added per workgroup.
+//
+// What this file has in common with ba_camera_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
+// (argument check, prior lookup, counter read-back, the body of the host-pointer entry; BlockWork) in ba_internal.h / ba_api.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -23,14 +26,13 @@
 namespace {
 
 #include "ba_model_dev.h"  // CPAD, project_pre, jac_block
+#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS
 
 constexpr int PT_BLK = 256;
 // Degree above which a point gets a wave.  The lanes of a wave wait for its slowest lane, whose time grows with degree x trials:
 // 32 bounds a lane's serial chain per evaluation at 32 observations, and a point above it keeps at least half of the lanes of its
 // own wave busy.  The lane tier's points are ordered by descending degree, so the lanes of one wave walk lists of similar length.
 constexpr int PT_TIER = 32;
-constexpr int PT_UNDIST_ITERS = 8;  // fixed-point iterations of q <- u / (1 + k1 |q|^2 + k2 |q|^4)
-constexpr int PT_COUNTERS = BA_PT_STATES + 2;  // [states | points flagged BEHIND | most trials of a point]
 
 struct PtArgs {
   const int *pt_ptr, *pt_obs, *cam0;
@@ -47,12 +49,6 @@ struct PtArgs {
   int init, max_iter, kind;
   double xtol, lambda0, c2;
 };
-
-__device__ __forceinline__ double wave_all_sum(double v) {  // every lane receives the same bits (a + b == b + a)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // A x = b by Cholesky, A symmetric 3 x 3 packed lower row-major (xx xy yy xz yz zz).  False when a pivot is not above piv_min or
 // the solution is not finite.
@@ -109,12 +105,9 @@ __device__ __forceinline__ void point_eval(const PtArgs &a, int k0, int k1, int 
     double out[2], J[24];
     project_pre<double>(X, ob.P, out);
     jac_block<double>(X, ob.P, J);  // (columns 0..2 of both rows are used: G and the intrinsics' columns are dead code)
-    {  // P1.z as jac_block forms it
-      const double kx = ob.P[0], ky = ob.P[1], kz = ob.P[2], s = ob.P[9], c = ob.P[10];
-      const double d = kx * X[0] + ky * X[1] + kz * X[2];
-      const double z1 = ((c * X[2] + s * (kx * X[1] - ky * X[0])) + ((1 - c) * d) * kz) + ob.P[5];
-      if (ob.used && z1 >= 0.0) bh = 1;
-    }
+    double z1;
+    p1_z(ob.P, X, z1);
+    if (ob.used && z1 >= 0.0) bh = 1;
     const double ex = out[0] - ob.mx, ey = out[1] - ob.my;
     const double rx = ob.l00 * ex + ob.l10 * ey, ry = ob.l11 * ey;
     double j0[3], j1[3];
@@ -174,7 +167,7 @@ __device__ __forceinline__ bool point_triangulate(const PtArgs &a, int k0, int k
     const double ux = ob.mx / ob.P[8], uy = ob.my / ob.P[8];
     double qx = ux, qy = uy;
 #pragma unroll
-    for (int it = 0; it < PT_UNDIST_ITERS; it++) {
+    for (int it = 0; it < UNDIST_ITERS; it++) {
       const double n2 = qx * qx + qy * qy;
       const double sc = 1.0 + ob.P[6] * n2 + ob.P[7] * (n2 * n2);
       qx = ux / sc;
@@ -307,9 +300,9 @@ __device__ __forceinline__ void refine_point(const PtArgs &a, int i, int lane, i
 // Workgroups [0, ceil(n_wave / 4)): one point of wave_pts per wave (they run longest and start first); the others: one point of
 // lane_pts per lane.
 __global__ __launch_bounds__(PT_BLK) void k_refine_points(PtArgs a) {
-  __shared__ unsigned cnt[PT_COUNTERS];
+  __shared__ unsigned cnt[BLOCK_COUNTERS];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (t < PT_COUNTERS) cnt[t] = 0;
+  if (t < BLOCK_COUNTERS) cnt[t] = 0;
   __syncthreads();
   const int nb_wave = (a.n_wave + PT_BLK / 64 - 1) / (PT_BLK / 64);
   int status = -1, trials = 0;
@@ -329,7 +322,7 @@ __global__ __launch_bounds__(PT_BLK) void k_refine_points(PtArgs a) {
     atomicMax(&cnt[BA_PT_STATES + 1], (unsigned)trials);
   }
   __syncthreads();
-  if (t < PT_COUNTERS && cnt[t] != 0) {
+  if (t < BLOCK_COUNTERS && cnt[t] != 0) {
     if (t == BA_PT_STATES + 1) atomicMax(a.counts + t, (unsigned long long)cnt[t]);
     else atomicAdd(a.counts + t, (unsigned long long)cnt[t]);
   }
@@ -361,38 +354,24 @@ static int point_tables(ba_problem *p) {
     });
     BA_CHECK(upload(w.wave_pts, std::vector<int>(order.begin(), order.begin() + nw)));
     BA_CHECK(upload(w.lane_pts, std::vector<int>(order.begin() + nw, order.end())));
-    BA_CHECK(w.counts.alloc(PT_COUNTERS));
+    BA_CHECK(w.counts.alloc(BLOCK_COUNTERS));
     w.n_wave = nw;
     w.n_lane = p->npnts - nw;
     w.split = true;
   }
-  const PriorSet &pt = p->pri[PRI_PNT];
-  if (pt.n > 0 && w.pri_version != p->pri_version) {
-    std::vector<int> of((size_t)p->npnts, -1);
-    for (int64_t q = 0; q < pt.n; q++) of[(size_t)pt.h_idx[(size_t)q]] = (int)q;
-    BA_CHECK(upload(w.pri_of, of));
+  if (w.pri_version != p->pri_version) {
+    BA_CHECK(block_prior_lookup(p->pri[PRI_PNT], p->npnts, w.pri_of));
     w.pri_version = p->pri_version;
   }
   return BA_OK;
 }
 
 static int refine_check(const char *who, ba_problem *p, const double *x, int init, int *max_iter, double *xtol, double *lambda0) {
-  if (!p || (!x && p->npnts + p->ncams > 0)) {
-    ba_set_error("%s: null argument", who);
-    return BA_ERR_ARG;
-  }
-  if (init != 0 && init != 1) {
+  return block_check(who, p, x, 50, max_iter, xtol, lambda0, [&] {
+    if (init == 0 || init == 1) return BA_OK;
     ba_set_error("%s: init must be 0 (start from the points of x) or 1 (triangulate first), got %d", who, init);
     return BA_ERR_ARG;
-  }
-  if (!std::isfinite(*xtol) || !std::isfinite(*lambda0)) {
-    ba_set_error("%s: xtol and lambda0 must be finite (<= 0: the default), got %g and %g", who, *xtol, *lambda0);
-    return BA_ERR_ARG;
-  }
-  if (*max_iter < 0) *max_iter = 50;
-  if (*xtol <= 0) *xtol = 1e-10;
-  if (*lambda0 <= 0) *lambda0 = 1e-4;
-  return BA_OK;
+  });
 }
 
 // k_cam_pre and k_refine_points on st; the counters stay on the device (p->pts.counts)
@@ -401,7 +380,7 @@ static int refine_launch(ba_problem *p, double *d_x, int init, int max_iter, dou
   BA_CHECK(terms_upload(p));
   BA_CHECK(point_tables(p));
   PointWork &w = p->pts;
-  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, PT_COUNTERS * sizeof(unsigned long long), st));
+  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
   if (p->npnts == 0) return BA_OK;
   ProfScope ps(p, PC_REFINE_POINTS, st);
   const double *cpre = nullptr;
@@ -424,46 +403,21 @@ static int refine_launch(ba_problem *p, double *d_x, int init, int max_iter, dou
   return BA_OK;
 }
 
-// the device counters -> the caller's (synchronises st)
-static int refine_counts(ba_problem *p, int64_t *counts, int *iters_max, hipStream_t st) {
-  if (!counts && !iters_max) return BA_OK;
-  unsigned long long h[PT_COUNTERS];
-  BA_HIP_CHECK(hipMemcpyAsync(h, p->pts.counts, sizeof h, hipMemcpyDeviceToHost, st));
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  if (counts)
-    for (int s = 0; s <= BA_PT_STATES; s++) counts[s] = (int64_t)h[s];
-  if (iters_max) *iters_max = (int)h[BA_PT_STATES + 1];
-  return BA_OK;
-}
-
 extern "C" int ba_refine_points_dev(ba_problem *p, double *d_x_inout, int init, int max_iter, double xtol, double lambda0,
                                     uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, void *stream) {
   BA_CHECK(refine_check("ba_refine_points_dev", p, d_x_inout, init, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
   BA_CHECK(refine_launch(p, d_x_inout, init, max_iter, xtol, lambda0, d_status, d_cost, st));
-  return refine_counts(p, counts, iters_max, st);
+  return block_counts(p->pts, counts, iters_max, st);
 }
 
 extern "C" int ba_refine_points(ba_problem *p, double *x_inout, int init, int max_iter, double xtol, double lambda0, uint8_t *status,
                                 double *cost, int64_t *counts, int *iters_max) {
   BA_CHECK(refine_check("ba_refine_points", p, x_inout, init, &max_iter, &xtol, &lambda0));
-  BA_HIP_CHECK(hipSetDevice(p->device));
-  const int64_t nvar = 9 * p->ncams + 3 * p->npnts;
-  hipStream_t st = p->stream;
-  PointWork &w = p->pts;
-  double *dx;
-  BA_CHECK(ba_scratch(p, 0, (size_t)(nvar + 1) * sizeof(double), (void **)&dx));
-  if (status && !w.status) BA_CHECK(w.status.alloc(p->npnts));
-  if (cost && !w.cost) BA_CHECK(w.cost.alloc(2 * p->npnts));
-  BA_HIP_CHECK(hipMemcpyAsync(dx, x_inout, (size_t)nvar * sizeof(double), hipMemcpyHostToDevice, st));
-  BA_CHECK(refine_launch(p, dx, init, max_iter, xtol, lambda0, status ? (uint8_t *)w.status : nullptr,
-                         cost ? (double *)w.cost : nullptr, st));
-  if (p->npnts > 0) {  // the points only: the camera part of the caller's x is never written
-    BA_HIP_CHECK(hipMemcpyAsync(x_inout, dx, (size_t)3 * p->npnts * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (status) BA_HIP_CHECK(hipMemcpyAsync(status, w.status, (size_t)p->npnts, hipMemcpyDeviceToHost, st));
-    if (cost) BA_HIP_CHECK(hipMemcpyAsync(cost, w.cost, (size_t)2 * p->npnts * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  BA_HIP_CHECK(hipStreamSynchronize(st));
-  return refine_counts(p, counts, iters_max, st);
+  // the points only: the camera part of the caller's x is never written
+  return block_host_entry(p, p->pts, x_inout, p->npnts, 3, 0, status, cost, counts, iters_max,
+                          [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
+                            return refine_launch(p, dx, init, max_iter, xtol, lambda0, d_status, d_cost, st);
+                          });
 }

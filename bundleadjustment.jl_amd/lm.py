@@ -258,6 +258,28 @@ def _opt_float(v, what):
     return f
 
 
+def _block_args(nlp, x, max_iter, xtol, lam0):
+    """The arguments refine_points and refine_cameras share, checked (ValueError) -> (a Float64 copy of x, (max_iter, xtol, lam0)
+    as the C entries take them: a negative value for None, the entry's default).  nlp is read last, for the length of x."""
+    if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
+        raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
+    tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
+    if (tol is not None and tol <= 0) or (l0 is not None and l0 <= 0):
+        raise ValueError(f"xtol and lam0 must be > 0 (or None), got {xtol!r} and {lam0!r}")
+    x = np.array(x, dtype=np.float64, copy=True)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    return x, (-1 if max_iter is None else int(max_iter), -1.0 if tol is None else tol, -1.0 if l0 is None else l0)
+
+
+def _block_info(status, cost, counts, its):
+    """the info dict of refine_points and refine_cameras from what the C entry filled"""
+    names = np.array(_lib.POINT_STATES)
+    return dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
+                cost_after=cost[:, 1].copy(), iters_max=its.value,
+                counts={**{n: int(c) for n, c in zip(_lib.POINT_STATES, counts)}, "behind": int(counts[-1])})
+
+
 def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None,
                   fixed_points=None, point_priors=None):
     """The points of x with its cameras held (ba_refine_points): every point is an independent problem in 3 unknowns -- the
@@ -274,27 +296,13 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
                               obs_info=obs_info)
     if not isinstance(triangulate, (bool, np.bool_)):
         raise ValueError(f"triangulate must be True or False, got {triangulate!r}")
-    if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
-        raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
-    tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
-    if (tol is not None and tol <= 0) or (l0 is not None and l0 <= 0):
-        raise ValueError(f"xtol and lam0 must be > 0 (or None), got {xtol!r} and {lam0!r}")
-    x = np.array(x, dtype=np.float64, copy=True)
-    if x.shape != (nlp.meta.nvar,):
-        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    x, args = _block_args(nlp, x, max_iter, xtol, lam0)
     terms.apply(nlp, shared=False)  # (a grouping concerns the cameras: what the handle holds stays)
-    status = np.zeros(nlp.npnts, dtype=np.uint8)
-    cost = np.zeros((nlp.npnts, 2))
-    counts = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64)
-    its = C.c_int(0)
-    _lib.check(_lib.lib().ba_refine_points(nlp.handle, _lib.ptr(x), int(bool(triangulate)), -1 if max_iter is None else int(max_iter),
-                                           -1.0 if tol is None else tol, -1.0 if l0 is None else l0, _lib.ptr(status),
-                                           _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
-    names = np.array(_lib.POINT_STATES)
-    info = dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
-                cost_after=cost[:, 1].copy(), iters_max=its.value,
-                counts={**{n: int(c) for n, c in zip(_lib.POINT_STATES, counts)}, "behind": int(counts[-1])})
-    return x, info
+    status, cost = np.zeros(nlp.npnts, dtype=np.uint8), np.zeros((nlp.npnts, 2))
+    counts, its = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64), C.c_int(0)
+    _lib.check(_lib.lib().ba_refine_points(nlp.handle, _lib.ptr(x), int(bool(triangulate)), *args, _lib.ptr(status), _lib.ptr(cost),
+                                           _lib.ptr(counts), C.byref(its)))
+    return x, _block_info(status, cost, counts, its)
 
 
 def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
@@ -318,27 +326,13 @@ def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None,
                               shared_intrinsics=shared_intrinsics, obs_info=obs_info)
     if not isinstance(resect, (bool, np.bool_)):
         raise ValueError(f"resect must be True or False, got {resect!r}")
-    if max_iter is not None and (not isinstance(max_iter, (int, np.integer)) or isinstance(max_iter, bool) or max_iter < 0):
-        raise ValueError(f"max_iter must be an integer >= 0 (or None), got {max_iter!r}")
-    tol, l0 = _opt_float(xtol, "xtol"), _opt_float(lam0, "lam0")
-    if (tol is not None and tol <= 0) or (l0 is not None and l0 <= 0):
-        raise ValueError(f"xtol and lam0 must be > 0 (or None), got {xtol!r} and {lam0!r}")
-    x = np.array(x, dtype=np.float64, copy=True)
-    if x.shape != (nlp.meta.nvar,):
-        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    x, args = _block_args(nlp, x, max_iter, xtol, lam0)
     terms.apply(nlp)  # (x is not checked against the grouping: the members' intrinsics are held, whatever they are)
-    status = np.zeros(nlp.ncams, dtype=np.uint8)
-    cost = np.zeros((nlp.ncams, 2))
-    counts = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64)
-    its = C.c_int(0)
+    status, cost = np.zeros(nlp.ncams, dtype=np.uint8), np.zeros((nlp.ncams, 2))
+    counts, its = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64), C.c_int(0)
     entry = _lib.lib().ba_resect_cameras if resect else _lib.lib().ba_refine_cameras
-    _lib.check(entry(nlp.handle, _lib.ptr(x), -1 if max_iter is None else int(max_iter), -1.0 if tol is None else tol,
-                     -1.0 if l0 is None else l0, _lib.ptr(status), _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
-    names = np.array(_lib.POINT_STATES)
-    info = dict(status=names[status & 0x7F], behind=(status & _lib.POINT_BEHIND) != 0, cost_before=cost[:, 0].copy(),
-                cost_after=cost[:, 1].copy(), iters_max=its.value,
-                counts={**{n: int(c) for n, c in zip(_lib.POINT_STATES, counts)}, "behind": int(counts[-1])})
-    return x, info
+    _lib.check(entry(nlp.handle, _lib.ptr(x), *args, _lib.ptr(status), _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
+    return x, _block_info(status, cost, counts, its)
 
 
 def schur_pattern(nlp):

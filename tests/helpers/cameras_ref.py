@@ -5,48 +5,24 @@ kernel: the BAL projection and its 2 x 9 camera Jacobian are derived here (P1 = 
 out = f (1 + k1 n + k2 n^2) P2, n = |P2|^2; d(R(r) X)/dr = -R [X]x (r r' + (R' - I) [r]x) / |r|^2, Gallego & Yezzi 2015)."""
 import numpy as np
 
-from _lm_ref import centre, centre_jac, factor, rho  # scipy's loss table, the header's factor, the centre and its Jacobian
+from _lm_ref import centre, centre_jac, rho  # noqa: F401 -- scipy's loss table, the centre and its Jacobian
+import block_ref as br
+from block_ref import BEHIND, CONVERGED, DEGENERATE, FIXED, MAX_ITER, NONFINITE, STALLED, rotations, skew  # noqa: F401
 
-CONVERGED, STALLED, MAX_ITER, FIXED, DEGENERATE, NONFINITE = range(6)
-BEHIND = 0x80
 INTRINSICS = np.array([False] * 6 + [True] * 3)
 
 
-def skew(v):
-    """(n, 3, 3) cross-product matrices of (n, 3) vectors"""
-    K = np.zeros((len(v), 3, 3))
-    K[:, 0, 1], K[:, 0, 2] = -v[:, 2], v[:, 1]
-    K[:, 1, 0], K[:, 1, 2] = v[:, 2], -v[:, 0]
-    K[:, 2, 0], K[:, 2, 1] = -v[:, 1], v[:, 0]
-    return K
-
-
-def rotations(r):
-    """(n, 3, 3) Rodrigues matrices of (n, 3) rotation vectors (theta = |r|, axis r / theta, no small-angle branch)"""
-    th = np.sqrt((r * r).sum(1))
-    k = r / th[:, None]
-    c, s = np.cos(th), np.sin(th)
-    return c[:, None, None] * np.eye(3) + s[:, None, None] * skew(k) + (1 - c)[:, None, None] * k[:, :, None] * k[:, None, :]
-
-
-class Scene:
-    """The held part of a problem: the observation lists, the measurements, the points of x and the information factors."""
+class Scene(br.Scene):
+    """... and the held points of x, per observation"""
 
     def __init__(self, p, x, info=None):
-        self.npnts, self.ncams, self.nobs = p["npnts"], p["ncams"], p["nobs"]
-        self.cam0 = np.asarray(p["cam_idx1"]) - 1
-        self.pnt0 = np.asarray(p["pnt_idx1"]) - 1
-        self.m = np.asarray(p["pt2d"], dtype=np.float64).reshape(-1, 2)
-        self.X = np.asarray(x[:3 * self.npnts], dtype=np.float64).reshape(self.npnts, 3)[self.pnt0]  # per observation
-        self.L = np.tile([1.0, 0.0, 1.0], (self.nobs, 1)) if info is None else np.stack(factor(np.asarray(info, dtype=np.float64)), axis=1)
-        self.used = ~np.all(self.L == 0.0, axis=1)
+        super().__init__(p, info)
+        self.X = np.asarray(x[:3 * self.npnts], dtype=np.float64).reshape(self.npnts, 3)[self.pnt0]
         self.nused = np.bincount(self.cam0, weights=self.used.astype(float), minlength=self.ncams)
 
     def csum(self, v):
         """per-camera sums of a per-observation array (nobs, ...)"""
-        flat = v.reshape(self.nobs, -1)
-        out = np.stack([np.bincount(self.cam0, weights=flat[:, j], minlength=self.ncams) for j in range(flat.shape[1])], axis=1)
-        return out.reshape((self.ncams,) + v.shape[1:])
+        return self.gsum(self.cam0, self.ncams, v)
 
 
 def cameras(p, x):
@@ -60,16 +36,7 @@ def evaluate(sc, C, loss="linear", c=1.0, cam_prior=None, ctr_prior=None):
         Co = C[sc.cam0]
         r, t, k1, k2, fo = Co[:, :3], Co[:, 3:6], Co[:, 6], Co[:, 7], Co[:, 8]
         R = rotations(r)
-        P1 = np.einsum("oij,oj->oi", R, sc.X) + t
-        P2 = -P1[:, :2] / P1[:, 2:3]
-        n = (P2 * P2).sum(1)
-        rr = 1.0 + k1 * n + k2 * n * n
-        e = (fo * rr)[:, None] * P2 - sc.m
-        D3 = fo[:, None, None] * (rr[:, None, None] * np.eye(2) + (2 * k1 + 4 * k2 * n)[:, None, None] * P2[:, :, None] * P2[:, None, :])
-        iz = 1.0 / P1[:, 2]
-        D2 = np.zeros((sc.nobs, 2, 3))
-        D2[:, 0, 0] = D2[:, 1, 1] = -iz
-        D2[:, 0, 2], D2[:, 1, 2] = P1[:, 0] * iz * iz, P1[:, 1] * iz * iz
+        P1, P2, n, rr, e, D3, D2 = br.project(R, sc.X, t, k1, k2, fo, sc.m)
         D32 = np.einsum("oab,obc->oac", D3, D2)
         th2 = (r * r).sum(1)
         inner = r[:, :, None] * r[:, None, :] + np.einsum("oij,ojk->oik", np.swapaxes(R, 1, 2) - np.eye(3), skew(r))
@@ -81,9 +48,7 @@ def evaluate(sc, C, loss="linear", c=1.0, cam_prior=None, ctr_prior=None):
         J[:, :, 7] = (fo * n * n)[:, None] * P2
         J[:, :, 8] = rr[:, None] * P2
         J[~np.isfinite(J).all(axis=(1, 2)) | (P1[:, 2] == 0)] = 0.0  # (the model's Jacobian: NaN -> 0)
-        l00, l10, l11 = sc.L[:, 0], sc.L[:, 1], sc.L[:, 2]
-        rh = np.stack([l00 * e[:, 0] + l10 * e[:, 1], l11 * e[:, 1]], axis=1)
-        Jh = np.stack([l00[:, None] * J[:, 0] + l10[:, None] * J[:, 1], l11[:, None] * J[:, 1]], axis=1)
+        rh, Jh = br.whiten(sc.L, e, J)
         rh[~sc.used] = 0.0  # Lambda = 0: dropped, whatever the projection gives
         Jh[~sc.used] = 0.0
         r_, w = rho(loss, (rh * rh).sum(1) / c ** 2)
@@ -153,52 +118,22 @@ def refine(p, x, max_iter=100, xtol=1e-10, lam0=1e-4, loss="linear", c=1.0, info
     nc = sc.ncams
     held = held_mask(p, held, groups)
     C0 = cameras(p, x).copy()
-    C = C0.copy()
     has_prior = np.zeros(nc, dtype=bool)
     for pr in (cam_prior, ctr_prior):
         if pr is not None:
             has_prior[np.asarray(pr[0])] = True
     fixed = held.all(axis=1)
     degenerate = ~fixed & (sc.nused == 0) & ~has_prior
-    f, H, g, behind = evaluate(sc, C, loss, c, cam_prior, ctr_prior)
-    cost = np.stack([f, f], axis=1)
-    nonfinite = ~fixed & ~degenerate & ~np.isfinite(f)
-    status = np.full(nc, MAX_ITER, dtype=np.int64)
-    status[fixed], status[degenerate], status[nonfinite] = FIXED, DEGENERATE, NONFINITE
-    active = ~fixed & ~degenerate & ~nonfinite
-    lam = np.full(nc, float(lam0))
-    trials = np.zeros(nc, dtype=np.int64)
     eye = np.eye(9, dtype=bool)
-    for _ in range(max_iter):
-        if not active.any():
-            break
-        trials[active] += 1
+
+    def solve(H, g, lam):
         hh = held[:, :, None] | held[:, None, :]
         A = np.where(hh, np.eye(9)[None], H)
         A = A + lam[:, None, None] * np.where(eye[None], A, 0.0)
-        b = np.where(held, 0.0, -g)
-        d, ok = chol_solve(A, b)
-        d = np.where(held, 0.0, d)
-        D = scales(H, held)
-        Cn = np.where((ok & active)[:, None] & ~held, C + d, C)
-        fn, Hn, gn, bn = evaluate(sc, Cn, loss, c, cam_prior, ctr_prior)
-        with np.errstate(invalid="ignore"):
-            acc = active & ok & (fn <= f)
-        rej = active & ~acc
-        C[acc], f[acc], H[acc], g[acc], behind[acc] = Cn[acc], fn[acc], Hn[acc], gn[acc], bn[acc]
-        lam[acc] = np.maximum(lam[acc] / 10.0, 1e-12)
-        with np.errstate(invalid="ignore"):
-            nd, nx = np.sqrt(((D * d) ** 2).sum(1)), np.sqrt(((D * C) ** 2).sum(1))
-            conv = acc & (nd <= xtol * (nx + xtol))
-        status[conv] = CONVERGED
-        lam[rej] *= 10.0
-        stall = rej & (lam > 1e12)
-        status[stall] = STALLED
-        active &= ~(conv | stall)
-    cost[:, 1] = f
-    cost[degenerate] = 0.0
-    behind = behind & ~degenerate & ~nonfinite
-    keep = degenerate | nonfinite | fixed
-    C[keep] = C0[keep]
+        d, ok = chol_solve(A, np.where(held, 0.0, -g))
+        return np.where(held, 0.0, d), ok
+
+    C, status, cost, trials, H = br.marquardt(C0.copy(), C0, lambda Ck: evaluate(sc, Ck, loss, c, cam_prior, ctr_prior), solve,
+                                              lambda H: scales(H, held), fixed, degenerate, held, max_iter, xtol, lam0)
     x[3 * sc.npnts:] = C.ravel()
-    return x, (status | np.where(behind, BEHIND, 0)).astype(np.uint8), cost, trials, scales(H, held)
+    return x, status, cost, trials, scales(H, held)

@@ -7,21 +7,11 @@ sweeps of its own."""
 import numpy as np
 
 import cameras_ref as cr
+from block_ref import undistort
 
 DONE, SKIPPED, DEGENERATE = 0, 1, 2
 MIN_OBS = 6
 POSE = np.array([True] * 6 + [False] * 3)
-
-
-def undistort(m, k1, k2, f):
-    """(n, 2) measurements -> normalised image points: u = m / f, 8 iterations of q <- u / (1 + k1 |q|^2 + k2 |q|^4)"""
-    with np.errstate(all="ignore"):
-        u = m / f
-        q = u.copy()
-        for _ in range(8):
-            n2 = (q * q).sum(1)
-            q = u / (1.0 + k1 * n2 + k2 * n2 * n2)[:, None]
-    return q
 
 
 def rotation_vector(R):

@@ -16,41 +16,20 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_run import arrays, attach_loopback, loopback_world, solve
+from _lm_run import attach_loopback, loopback_world, solve
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import cameras_ref as cr  # noqa: E402
-from scenes import _scene_from_lists, clip_psd, random_info  # noqa: E402
+from refine_util import _isolated, _model, bits, cam_prior_on, codes, only_camera, rel_cost, scaled, small_scene  # noqa: E402
+from scenes import clip_psd, random_info  # noqa: E402
 
 XTOL, XTOL_REF = 1e-10, 1e-13
 MAX_ITER = 400
 DEGREES = (0, 0, 1, 12, 63, 64, 65, 255, 256, 257, 600)
 DEGREES_POSE = (0, 0, 1, 3, 4, 5, 12, 63, 64, 65, 255, 256, 257, 600)
-# standard deviations of a camera prior, block order r t k1 k2 f: the scales of the generator's cameras
-PRIOR_SIGMA = np.array([1e-3] * 3 + [1e-2] * 3 + [1e-8, 1e-13, 1.0])
 POSE = np.array([False] * 6 + [True] * 3)
 _SCENES, _REFS, _SPREADS = {}, {}, {}
-
-
-def _isolated(ba, degrees, seed):
-    """isolated cameras with the given degrees, every point seen once"""
-    degrees = np.asarray(degrees, dtype=np.int64)
-    npnts = int(degrees.sum())
-    return _scene_from_lists(ba, len(degrees), npnts, np.arange(npnts, dtype=np.int64), np.repeat(np.arange(len(degrees)), degrees), seed)
-
-
-def only_camera(p, c):
-    """the scene that holds camera c (0-based) of p alone, with its points in their order"""
-    n = p["npnts"]
-    keep = (np.asarray(p["cam_idx1"]) - 1) == c
-    pnts, new = np.unique(np.asarray(p["pnt_idx1"])[keep] - 1, return_inverse=True)
-    out = dict(cam_idx1=np.ones(int(keep.sum()), dtype=np.int64), pnt_idx1=new.astype(np.int64) + 1,
-               pt2d=np.ascontiguousarray(np.asarray(p["pt2d"]).reshape(-1, 2)[keep].ravel()), ncams=1, npnts=len(pnts), nobs=int(keep.sum()))
-    for key in ("x0", "x_true"):
-        x = np.asarray(p[key])
-        out[key] = np.concatenate([x[:3 * n].reshape(n, 3)[pnts].ravel(), x[3 * n + 9 * c:3 * n + 9 * c + 9]])
-    return out
 
 
 def scene(ba, name):
@@ -60,24 +39,11 @@ def scene(ba, name):
         elif name == "boundary_pose":
             p = _isolated(ba, DEGREES_POSE, 52)
         elif name == "small":
-            p = ba.synthetic.make_problem(12, 400, 1800, seed=11)
+            p = small_scene(ba)
         elif name == "one":
             p = only_camera(_isolated(ba, (40, 40), 53), 0)
         _SCENES[name] = p
     return _SCENES[name]
-
-
-def cam_prior_on(p, idx, seed):
-    """full-rank camera priors on the cameras idx (0-based): mu = the true camera moved by 0.3 sigma, Lambda = S^-1 M S^-1 with
-    S = diag(PRIOR_SIGMA) and M a well-conditioned full symmetric matrix"""
-    rng = np.random.default_rng(seed)
-    idx = np.asarray(idx, dtype=np.int64)
-    true = cr.cameras(p, p["x_true"])[idx]
-    mu = true + 0.3 * PRIOR_SIGMA * rng.standard_normal((len(idx), 9))
-    B = rng.standard_normal((len(idx), 9, 9))
-    M = np.eye(9) + 0.05 * np.einsum("kij,klj->kil", B, B)
-    Lam = M / (PRIOR_SIGMA[:, None] * PRIOR_SIGMA[None, :])
-    return idx, mu, 0.5 * (Lam + Lam.transpose(0, 2, 1))
 
 
 def base_terms(ba, name):
@@ -176,18 +142,6 @@ def ref(ba, name, what, xtol):
     return _REFS[key]
 
 
-def scaled(D, C, C_ref):
-    return np.linalg.norm(D * (C - C_ref), axis=1) / (1.0 + np.linalg.norm(D * C_ref, axis=1))
-
-
-def rel_cost(after, cost_ref):
-    """relative difference of cost_after per camera; where the reference's minimum is numerically zero against its start (a
-    camera held by a prior alone: the minimum of a quadratic is exactly 0) the difference is taken against 1e-12 of the start"""
-    den = np.maximum(cost_ref[:, 1], 1e-12 * cost_ref[:, 0])
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return np.where(den > 0, np.abs(after - cost_ref[:, 1]) / den, 0.0)
-
-
 def perturbed(p, held=None, seed=1):
     """x0 with its cameras perturbed once more by 1e-3 relative (held components keep their values: they are data of the problem)"""
     x = np.array(p["x0"], copy=True)
@@ -218,15 +172,6 @@ def bounds(ba, name):
     """(cost bound, parameter bound) of a scene: 100 x spread (1) with the floor 1e-13, 10 x spread (2) with the floor 100 xtol"""
     s1, s2 = spreads(ba, name)
     return max(100 * s1, 1e-13), max(10 * s2, 100 * XTOL)
-
-
-def codes(ba, info):
-    names = list(ba._lib.POINT_STATES)
-    return (np.array([names.index(s) for s in info["status"]]) | np.where(info["behind"], cr.BEHIND, 0)).astype(np.uint8)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 # ---- CPU ------------------------------------------------------------------------------------------------------------------
@@ -319,10 +264,6 @@ def test_reference_stays_inside_its_own_bounds(ba, name, what):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _model(ba, p):
-    return ba.BALNLPModel(arrays=arrays(p))
-
-
 def _check_parity(ba, name, what):
     """a device run at xtol = 1e-10 against the reference at xtol = 1e-13 -> (x, info, the reference's tuple)"""
     p = scene(ba, name)

@@ -9,11 +9,12 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_run import arrays, solve
+from _lm_run import solve
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import points_ref as pr  # noqa: E402
+from refine_util import _model, codes, small_scene  # noqa: E402
 from scenes import random_info  # noqa: E402
 
 XTOL = 1e-10
@@ -26,7 +27,7 @@ def scene(ba, name):
         if name == "deg2":
             p = ba.synthetic.make_problem(5, 40, 80, seed=3)
         elif name == "small":
-            p = ba.synthetic.make_problem(12, 400, 1800, seed=11)
+            p = small_scene(ba)
         elif name == "high":
             p = ba.synthetic.make_problem(100, 60, 2700, seed=11)
         elif name == "one":
@@ -58,12 +59,6 @@ def pts(p, x):
 def rel(p, a, b):
     A, B = pts(p, a), pts(p, b)
     return np.linalg.norm(A - B, axis=1) / (1.0 + np.linalg.norm(B, axis=1))
-
-
-def codes(ba, info):
-    """uint8 status as the C entry returns it, from refine_points' info"""
-    names = list(ba._lib.POINT_STATES)
-    return (np.array([names.index(s) for s in info["status"]]) | np.where(info["behind"], pr.BEHIND, 0)).astype(np.uint8)
 
 
 def noise_free(ba, p):
@@ -122,10 +117,6 @@ def test_reference_sanity(ba, name, tri_tol):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _model(ba, p):
-    return ba.BALNLPModel(arrays=arrays(p))
-
-
 def _check_parity(ba, name, tag, dev_kw, ref_kw, init):
     """a device run at xtol = 1e-10 against the reference: states equal to the reference's at the same xtol, every free point
     within 100 xtol (1 + |X_ref|) of the reference run to xtol = 1e-13; points the reference leaves are left bit for bit"""

@@ -22,14 +22,14 @@ import sys
 import numpy as np
 import pytest
 
-from _lm_run import arrays, attach_loopback, loopback_world
+from _lm_run import attach_loopback, loopback_world
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import cameras_ref as cr  # noqa: E402
 import points_ref as pr  # noqa: E402
 import resect_ref as rr  # noqa: E402
-from test_refine_cameras import _isolated, bits, cam_prior_on, codes, only_camera, rel_cost, scaled  # noqa: E402
+from refine_util import _isolated, _model, bits, cam_prior_on, codes, only_camera, rel_cost, scaled, small_scene  # noqa: E402
 
 XTOL, XTOL_REF = 1e-10, 1e-13
 MAX_ITER = 400
@@ -311,14 +311,10 @@ def test_reference_stays_inside_its_own_bounds(ba, what):
         assert used[DEG == 12] == 5 and used[DEG == 63] == 6 and used[DEG == 64] == 0
 
 
-def _alternation_scene(ba):
-    return cached("small", lambda: ba.synthetic.make_problem(12, 400, 1800, seed=11))
-
-
 def test_reference_builds_an_x0_from_points_alone(ba):
     """The condition of the GPU test, on the reference first: from NaN poses, the resection (intrinsics held) and three rounds of
     points / cameras end within 1 % of what the same alternation reaches from the generator's x0 (294.6)."""
-    p = _alternation_scene(ba)
+    p = small_scene(ba)
     nc = p["ncams"]
     held = np.tile(~POSE, (nc, 1))
     total = lambda x: float(cr.evaluate(cr.Scene(p, x), cr.cameras(p, x))[0].sum())  # noqa: E731
@@ -341,10 +337,6 @@ def test_reference_builds_an_x0_from_points_alone(ba):
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------------
-def _model(ba, p):
-    return ba.BALNLPModel(arrays=arrays(p))
-
-
 def _run(ba, p, x, **kw):
     m = _model(ba, p)
     try:
@@ -580,7 +572,7 @@ def test_determinism_and_isolation(ba, gpu_ok):
     nc, nvar = p["ncams"], len(base)
     x0 = nan_poses(p, base)
     L = ba._lib.lib()
-    q = _alternation_scene(ba)
+    q = small_scene(ba)
     m, ms, plain = _model(ba, p), _model(ba, q), _model(ba, q)
     try:
         x1, i1 = ba.refine_cameras(m, x0, resect=True, xtol=XTOL, max_iter=MAX_ITER)
@@ -634,7 +626,7 @@ def test_an_x0_from_points_alone(ba, gpu_ok):
     """Every camera pose of x0 is NaN: the resection with (k1, k2, f) held, then three rounds of refine_points and refine_cameras.
     The objective never rises after the first call and ends within 1 % of what the same alternation reaches from the generator's
     own x0 (294.6)."""
-    p = _alternation_scene(ba)
+    p = small_scene(ba)
     m = _model(ba, p)
     try:
         ends = []
