@@ -738,13 +738,10 @@ static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, 
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
   if (resect) {  // the start poses, written into d_x on the same stream
     ProfScope ps(p, PC_RESECT_CAMERAS, st);
-    hipLaunchKernelGGL(k_resect_cameras, dim3((unsigned)p->ncams), dim3(CM_BLK), 0, st, a);
-    BA_HIP_CHECK(hipGetLastError());
+    BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a));
   }
   ProfScope ps(p, PC_REFINE_CAMERAS, st);
-  hipLaunchKernelGGL(k_refine_cameras, dim3((unsigned)p->ncams), dim3(CM_BLK), 0, st, a);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_refine_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a);
 }
 
 static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, bool resect, int max_iter, double xtol, double lambda0,

@@ -342,17 +342,15 @@ __global__ __launch_bounds__(CT) void k_cov_points(int64_t npnts, const int *__r
       if (lane == 3 * r + m) o9[3 * r + m] = u9[3 * r + m] + 0.5 * (s[3 * r + m] + s[3 * m + r]);
 }
 
-int cov_grid(int64_t n, int per) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }
+unsigned cov_grid(int64_t n, int per) { return std::max(1u, grid_for(n, per)); }
 
 }  // namespace
 
 int launch_cov_sdiag(ba_problem *p, const DenseLDL *w, int64_t n, double *d_sd, double *d_ratio_out, bool after_factor,
                      hipStream_t st) {
   ProfScope ps(p, PC_COV_INV, st);
-  if (!after_factor) hipLaunchKernelGGL(k_cov_sdiag, dim3(cov_grid(n, CT)), dim3(CT), 0, st, n, (const double *)w->S, w->col_off, d_sd);
-  else hipLaunchKernelGGL(k_cov_min_ratio, dim3(1), dim3(1024), 0, st, n, (const double *)w->D, (const double *)d_sd, d_ratio_out);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  if (!after_factor) return BA_LAUNCH(k_cov_sdiag, cov_grid(n, CT), CT, 0, st, n, w->S, w->col_off, d_sd);
+  return BA_LAUNCH(k_cov_min_ratio, 1, 1024, 0, st, n, w->D, d_sd, d_ratio_out);
 }
 
 int64_t cov_part_tiles(int64_t nt) { return COV_WG_TARGET + nt; }
@@ -363,7 +361,7 @@ int dense_ldl_selinv(ba_problem *p, DenseLDL *w, const int *d_iota, double *d_pa
   double *S = w->S;
   const int64_t *co = w->col_off;
   const TilePattern *pat = w->sparse ? w->pat : nullptr;
-  hipLaunchKernelGGL(k_cov_binv, dim3(nt), dim3(CT), 0, st, S, co, (const double *)w->Linv, (const double *)w->D);
+  BA_CHECK(BA_LAUNCH(k_cov_binv, nt, CT, 0, st, S, co, w->Linv, w->D));
   for (int k = nt - 1; k >= 0; k--) {
     const int *rows;
     int m;
@@ -377,41 +375,33 @@ int dense_ldl_selinv(ba_problem *p, DenseLDL *w, const int *d_iota, double *d_pa
     }
     int nch2 = 0;
     if (m > 0) {
-      hipLaunchKernelGGL(k_cov_panel, dim3(m), dim3(CT), 0, st, (const double *)S, co, (const double *)(w->Linv + (int64_t)k * NB * NB),
-                         rows, k, (double *)w->V);
+      BA_CHECK(BA_LAUNCH(k_cov_panel, m, CT, 0, st, S, co, w->Linv + (int64_t)k * NB * NB, rows, k, w->V));
       // split the sums of length m over nch workgroups per output tile: about COV_WG_TARGET workgroups in all
       int nch = std::min(m, std::max(1, (COV_WG_TARGET + m - 1) / m));
       const int ch = (m + nch - 1) / nch;
       nch = (m + ch - 1) / ch;
-      hipLaunchKernelGGL(k_cov_col, dim3(m * nch), dim3(CT), 0, st, S, co, rows, m, k, (const double *)w->V, nch, ch, d_part);
-      if (nch > 1) hipLaunchKernelGGL(k_cov_col_sum, dim3(16 * m), dim3(CT), 0, st, S, co, rows, k, nch, (const double *)d_part);
+      BA_CHECK(BA_LAUNCH(k_cov_col, m * nch, CT, 0, st, S, co, rows, m, k, w->V, nch, ch, d_part));
+      if (nch > 1) BA_CHECK(BA_LAUNCH(k_cov_col_sum, 16 * m, CT, 0, st, S, co, rows, k, nch, d_part));
       nch2 = std::min(m, 256);
       const int ch2 = (m + nch2 - 1) / nch2;
       nch2 = (m + ch2 - 1) / ch2;
-      hipLaunchKernelGGL(k_cov_diag, dim3(nch2), dim3(CT), 0, st, (const double *)S, co, rows, m, k, (const double *)w->V, ch2, d_part);
+      BA_CHECK(BA_LAUNCH(k_cov_diag, nch2, CT, 0, st, S, co, rows, m, k, w->V, ch2, d_part));
     }
-    hipLaunchKernelGGL(k_cov_diag_sum, dim3(NB * NB / CT), dim3(CT), 0, st, S, co, k, nch2, (const double *)d_part);
+    BA_CHECK(BA_LAUNCH(k_cov_diag_sum, NB * NB / CT, CT, 0, st, S, co, k, nch2, d_part));
   }
-  BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
 int launch_cov_cams(ba_problem *p, const DenseLDL *w, const int *d_pos, const uint16_t *d_fix_cam, double *d_out, hipStream_t st) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_COV_CAMS, st);
-  hipLaunchKernelGGL(k_cov_cams, dim3(cov_grid(81 * p->ncams, CT)), dim3(CT), 0, st, p->ncams, (const double *)w->S, w->col_off, d_pos,
-                     d_fix_cam, d_out);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cov_cams, cov_grid(81 * p->ncams, CT), CT, 0, st, p->ncams, w->S, w->col_off, d_pos, d_fix_cam, d_out);
 }
 
 int launch_cov_points(ba_problem *p, const DenseLDL *w, const int *d_pos, const double *d_J, const double *d_Y, const double *d_Uinv,
                       const uint8_t *d_fix_pnt, double *d_out, hipStream_t st) {
   if (p->npnts == 0) return BA_OK;
   ProfScope ps(p, PC_COV_POINTS, st);
-  hipLaunchKernelGGL(k_cov_points, dim3(cov_grid(p->npnts, CT / 64)), dim3(CT), 0, st, p->npnts, (const int *)p->pt_ptr,
-                     (const int *)p->pt_obs, (const int *)p->cam0, d_pos, d_J, d_Y, d_Uinv, (const double *)w->S, w->col_off, d_fix_pnt,
-                     d_out);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cov_points, cov_grid(p->npnts, CT / 64), CT, 0, st, p->npnts, p->pt_ptr, p->pt_obs, p->cam0, d_pos, d_J, d_Y, d_Uinv,
+                   w->S, w->col_off, d_fix_pnt, d_out);
 }

@@ -537,7 +537,7 @@ template <typename T>
 __global__ __launch_bounds__(DIAG_THREADS) void k_ldl_diag(T *__restrict__ Skk, T *__restrict__ Linv_k,
                                                    T *__restrict__ D_k, int *__restrict__ flag,
                                                    unsigned long long *__restrict__ stamps,
-                                                   const int *__restrict__ wait_ready, int clear_flag = 0) {
+                                                   const int *__restrict__ wait_ready, int clear_flag) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
   // first kernel of an in-order factorisation: the pivot flag is cleared here instead of by a memset node of its own (the
   // first pivot is behind the tile's load and a barrier)
@@ -837,7 +837,7 @@ template <typename T, bool FWD>
 __global__ __launch_bounds__(256) void k_ldl_trsm_rs(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv_k,
                                                       const T *__restrict__ D_k, T *__restrict__ V, int k,
                                                       T *__restrict__ b, T *__restrict__ y,
-                                                      const int *__restrict__ rows = nullptr) {
+                                                      const int *__restrict__ rows) {
   ldl_trsm_rs_body<T, FWD>(S, co, Linv_k, D_k, V, k, b, y, rows, (int)blockIdx.x);
 }
 
@@ -895,7 +895,7 @@ __device__ __forceinline__ void ldl_col_rs_body(T *__restrict__ S, const int64_t
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_ldl_col_rs(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0, int k,
-                                                     const int *__restrict__ rows = nullptr) {
+                                                     const int *__restrict__ rows) {
   ldl_col_rs_body<T>(S, co, V0, k, rows, (int)blockIdx.x);
 }
 template <typename T>
@@ -962,13 +962,13 @@ __device__ __forceinline__ void ldl_update_rs_body(T *__restrict__ S, const int6
 template <typename T>
 __global__ __launch_bounds__(256) void k_ldl_update_rs(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0,
                                                         const T *__restrict__ V1, int k, int base, int nblk,
-                                                        const int *__restrict__ rows, int lead_len = 0) {
+                                                        const int *__restrict__ rows, int lead_len) {
   ldl_update_rs_body<T>(S, co, V0, V1, k, base, nblk, rows, lead_len, (int)blockIdx.x);
 }
 // the pair updates of two runs in one launch (V: the run's first panel buffer, the second follows it at a panel's distance)
 template <typename T>
 __global__ __launch_bounds__(256) void k_ldl_update_rs2(T *__restrict__ S, const int64_t *__restrict__ co, RunPanel<T> a, int nblk_a,
-                                                         RunPanel<T> c, int nblk_c, int64_t panel, int lead_a = 0, int lead_c = 0) {
+                                                         RunPanel<T> c, int nblk_c, int64_t panel, int lead_a, int lead_c) {
   // lead_a / lead_c > 0: the run's launch part is the lead strip of its look-ahead (see k_ldl_update_rs)
   const bool second = (int)blockIdx.x >= 4 * nblk_a;
   const RunPanel<T> &r = second ? c : a;
@@ -1292,14 +1292,12 @@ __device__ __forceinline__ int ldl_update_tile(T *__restrict__ S, const int64_t 
 // with own_pref[m] = number of tiles in the columns before own_cols[m]; the columns >= base start at index m0.
 template <typename T, int MODE, bool OWN = false>
 __global__ __launch_bounds__(256, 2) void k_ldl_update(T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ V0,
-                                                        const T *__restrict__ V1, int k, int base, int nt,
-                                                        int nblk, int *__restrict__ ready,
-                                                        const int *__restrict__ own_cols = nullptr,
-                                                        const int64_t *__restrict__ own_pref = nullptr, int m0 = 0,
-                                                        int m_end = 0, int ready_tiles = 1, const int *__restrict__ rows = nullptr,
-                                                        const T *__restrict__ Lp0 = nullptr, const T *__restrict__ Lp1 = nullptr,
-                                                        const int2 *__restrict__ tlist = nullptr, int blocked = TSB,
-                                                        int *__restrict__ tickets = nullptr) {
+                                                        const T *__restrict__ V1, int k, int base, int nt, int nblk,
+                                                        int *__restrict__ ready, const int *__restrict__ own_cols,
+                                                        const int64_t *__restrict__ own_pref, int m0, int m_end, int ready_tiles,
+                                                        const int *__restrict__ rows, const T *__restrict__ Lp0,
+                                                        const T *__restrict__ Lp1, const int2 *__restrict__ tlist, int blocked,
+                                                        int *__restrict__ tickets) {
   // tlist (block-sparse S on several ranks): the tiles (i, j) of this launch, listed (the pattern's tiles of the pair's update
   // in the tile columns this rank owns)
   BA_VT
@@ -1491,7 +1489,7 @@ __global__ __launch_bounds__(256, 2) void k_ldl_update2(T *__restrict__ S, const
 // (rows i0..nt-1), with the owner's arithmetic (k_ldl_trsm_rs: xv * (1 / d)), so that every rank holds the same bits.
 template <typename T>
 __global__ __launch_bounds__(256) void k_ldl_scale_panel(T *__restrict__ Lcol, const T *__restrict__ V, const T *__restrict__ D_k, int i0,
-                                                          const int *__restrict__ rows = nullptr) {
+                                                          const int *__restrict__ rows) {
   // Lcol: where the L tiles of this tile column live, tile row i at Lcol + i NB^2 (a column of S is contiguous: S + (co[k] - k)
   // NB^2; with per-rank ownership of S: a panel buffer)
   BA_VT
@@ -1558,8 +1556,8 @@ __device__ __forceinline__ void tile_matvec_t(const T *__restrict__ M, const T *
 // Lcol (per-rank ownership of S): the tiles of column k come from the panel buffer, rows[x - 1] (null: k + x) being workgroup x's.
 template <typename T>
 __global__ __launch_bounds__(256) void k_fwd_step(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                   T *__restrict__ b, T *__restrict__ y, int k, int ld = 0,
-                                                   const int *__restrict__ rows = nullptr, const T *__restrict__ Lcol = nullptr) {
+                                                   T *__restrict__ b, T *__restrict__ y, int k, int ld,
+                                                   const int *__restrict__ rows, const T *__restrict__ Lcol) {
   BA_VT
   __shared__ T yk[NB];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1587,8 +1585,8 @@ __global__ __launch_bounds__(256) void k_fwd_step(const T *__restrict__ S, const
 // then y_j -= D_j (L_kj' x_k) ... expressed on z: z_j -= L_kj' x_k, i.e. y_j -= D_j * (L_kj' x_k), j < k.
 template <typename T>
 __global__ __launch_bounds__(256) void k_bwd_step(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
-                                                   const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k, int ld = 0,
-                                                   const int *__restrict__ cols = nullptr) {
+                                                   const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k, int ld,
+                                                   const int *__restrict__ cols) {
   __shared__ T zk[NB], xk[NB], part[2][NB];
   const int tid = threadIdx.x;
   int j = (int)blockIdx.x - 1;  // 0 .. k-1 (block-sparse S: the tile columns of row k's pattern)
@@ -1675,7 +1673,7 @@ __device__ __forceinline__ void bwd_pair_body(const T *__restrict__ S, const int
 template <typename T>
 __global__ __launch_bounds__(256) void k_bwd_pair(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
                                                    const T *__restrict__ D, T *__restrict__ y, T *__restrict__ x, int k,
-                                                   const int *__restrict__ cols = nullptr) {
+                                                   const int *__restrict__ cols) {
   bwd_pair_body<T>(S, co, Linv, D, y, x, k, cols, (int)blockIdx.x);
 }
 // The row pairs of TWO independent groups of tile columns in one launch (block-sparse S eliminated from both ends,
@@ -1851,12 +1849,11 @@ static PairRows pair_rows(const DenseLDLT<T> *w, int q) {
 
 // ---- panel launchers: tile column k over `count` tile rows, `rows` as in PairRows ------------------------------------------
 template <typename T>
-static int launch_diag(ba_problem *p, DenseLDLT<T> *w, int k, hipStream_t st, const int *wait_ready = nullptr, bool clear_flag = false) {
+[[nodiscard]] static int launch_diag(ba_problem *p, DenseLDLT<T> *w, int k, hipStream_t st, const int *wait_ready = nullptr,
+                                     bool clear_flag = false) {
   ProfScope ps(p, PC_LDL_DIAG, st);
-  hipLaunchKernelGGL(k_ldl_diag<T>, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(T), st, w->S + tix(w->hco(), k, k) * NB * NB,
-                     w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, w->flag, (unsigned long long *)nullptr,
-                     wait_ready, clear_flag ? 1 : 0);
-  return BA_OK;
+  return BA_LAUNCH(k_ldl_diag<T>, 1, DIAG_THREADS, DIAG_LDS_ELEMS * sizeof(T), st, w->S + tix(w->hco(), k, k) * NB * NB,
+                   w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, w->flag, nullptr, wait_ready, clear_flag ? 1 : 0);
 }
 
 // the FWD instantiation of a panel kernel when a right-hand side rides along, the plain one otherwise
@@ -1866,24 +1863,19 @@ static K fwd_kernel(const void *b, K with_fwd, K without) { return b ? with_fwd 
 // b != null: forward substitution of b fused (y_k and b_i -= L_ik y_k); a panel with no tile below it has only its y_k,
 // which comes from the stand-alone forward step kernel.
 template <typename T>
-static int launch_trsm(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, T *V, T *b, hipStream_t st) {
+[[nodiscard]] static int launch_trsm(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, T *V, T *b, hipStream_t st) {
   T *y = w->D + w->nt * NB;
-  if (count <= 0) {
-    if (b) hipLaunchKernelGGL(k_fwd_step<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, b, y, k);
-    return BA_OK;
-  }
+  if (count <= 0) return b ? BA_LAUNCH(k_fwd_step<T>, 1, 256, 0, st, w->S, w->col_off, w->Linv, b, y, k, 0, nullptr, nullptr) : BA_OK;
   ProfScope ps(p, PC_LDL_TRSM, st);
-  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_trsm_rs<T, true>, k_ldl_trsm_rs<T, false>), dim3(4 * count), dim3(256), RS_LDS_ELEMS * sizeof(T),
-                     st, w->S, w->col_off, w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, b, y, rows);
-  return BA_OK;
+  return BA_LAUNCH(fwd_kernel(b, k_ldl_trsm_rs<T, true>, k_ldl_trsm_rs<T, false>), 4 * count, 256, RS_LDS_ELEMS * sizeof(T), st, w->S,
+                   w->col_off, w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, b, y, rows);
 }
 
 template <typename T>
-static int launch_col(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, hipStream_t st) {
+[[nodiscard]] static int launch_col(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, hipStream_t st) {
   if (count <= 0) return BA_OK;
   ProfScope ps(p, PC_LDL_SYRK, st);
-  hipLaunchKernelGGL(k_ldl_col_rs<T>, dim3(4 * count), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, k, rows);
-  return BA_OK;
+  return BA_LAUNCH(k_ldl_col_rs<T>, 4 * count, 256, RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, k, rows);
 }
 
 // tiles up to which the pair update takes its row-split form (BA_LDL_UPDATE_RS_MAX; 0 disables)
@@ -1894,15 +1886,13 @@ static int update_rs_max() {
 // pair update with panels k, k+1 of the lower tiles (i, j), i >= j, over the `count` rows of U_q; `ready`: flag raised when
 // the first ready_tiles tiles are final (hoisted-diagonal schedule; never in the row-split form)
 template <typename T>
-static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, const T *V1, hipStream_t st,
-                       int *ready = nullptr, int ready_tiles = 1, int *tickets = nullptr) {
+[[nodiscard]] static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, int count, const T *V0, const T *V1,
+                                     hipStream_t st, int *ready = nullptr, int ready_tiles = 1, int *tickets = nullptr) {
   const int nblk = count * (count + 1) / 2;
   if (nblk <= 0) return BA_OK;
   if (!ready && nblk <= update_rs_max()) {  // short update: row-split form (see k_ldl_update_rs)
     ProfScope ps(p, PC_LDL_UPDATE_RS, st);
-    hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * nblk), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, k, k + 2, nblk,
-                       rows);
-    return BA_OK;
+    return BA_LAUNCH(k_ldl_update_rs<T>, 4 * nblk, 256, RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, V0, V1, k, k + 2, nblk, rows, 0);
   }
   ProfScope ps(p, PC_LDL_UPDATE, st);
   // (Round 3, tried and removed: the remainder of a launch beyond its full rounds of 512 tiles sent ahead in row-split form
@@ -1916,44 +1906,40 @@ static int launch_pair(ba_problem *p, DenseLDLT<T> *w, int k, const int *rows, i
   // tickets (dense_ldl_factor): this launch's counters, cleared -- persistent workgroups, at most what the device holds at once
   // (beside a hoisted workgroup, which keeps one CU, two of them fewer: they would only start when the others leave)
   const int grid = tickets ? std::min(std::max(w->wg_slots - (ready ? 2 : 0), 1), nblk) : ((nblk + 7) / 8) * 8;
-  hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(grid), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S,
-                     w->col_off, V0, V1, k, k + 2, (int)w->nt, nblk, ready, (const int *)nullptr, (const int64_t *)nullptr, 0, 0,
-                     ready_tiles, rows, (const T *)nullptr, (const T *)nullptr, (const int2 *)nullptr, TSB, tickets);
-  return BA_OK;
+  return BA_LAUNCH((k_ldl_update<T, 1>), grid, 256, gemm_priv_lds_bytes<T>(), st, w->S, w->col_off, V0, V1, k, k + 2, w->nt, nblk, ready,
+                   nullptr, nullptr, 0, 0, ready_tiles, rows, nullptr, nullptr, nullptr, TSB, tickets);
 }
 
 // the fused panel-pair kernels (see k_ldl_pairdiag): b != null: forward substitution rides along
 template <typename T>
-static int launch_pairdiag(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *b, hipStream_t st, const int *wait_ready, int need) {
+[[nodiscard]] static int launch_pairdiag(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *b, hipStream_t st, const int *wait_ready,
+                                         int need) {
   ProfScope ps(p, PC_LDL_DIAG, st);
   T *y = w->D + w->nt * NB;
-  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_pairdiag<T, true>, k_ldl_pairdiag<T, false>), dim3(1), dim3(256), DIAG_LDS_ELEMS * sizeof(T), st,
-                     w->S, w->col_off, w->Linv, w->D, V0, k, (int)w->nt, w->flag, wait_ready, need, b, y);
-  return BA_OK;
+  return BA_LAUNCH(fwd_kernel(b, k_ldl_pairdiag<T, true>, k_ldl_pairdiag<T, false>), 1, 256, DIAG_LDS_ELEMS * sizeof(T), st, w->S,
+                   w->col_off, w->Linv, w->D, V0, k, w->nt, w->flag, wait_ready, need, b, y);
 }
 
 template <typename T>
-static int launch_pairtrsm(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, T *b, hipStream_t st) {
+[[nodiscard]] static int launch_pairtrsm(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, T *b, hipStream_t st) {
   const int m = (int)w->nt - k - 2;
   if (m <= 0) return BA_OK;
   ProfScope ps(p, PC_LDL_TRSM, st);
   const T *y = w->D + w->nt * NB;
-  hipLaunchKernelGGL(fwd_kernel(b, k_ldl_pairtrsm<T, true>, k_ldl_pairtrsm<T, false>), dim3(4 * m), dim3(256), PT_LDS_ELEMS * sizeof(T), st,
-                     w->S, w->col_off, w->Linv, w->D, V0, V1, k, b, y);
-  return BA_OK;
+  return BA_LAUNCH(fwd_kernel(b, k_ldl_pairtrsm<T, true>, k_ldl_pairtrsm<T, false>), 4 * m, 256, PT_LDS_ELEMS * sizeof(T), st, w->S,
+                   w->col_off, w->Linv, w->D, V0, V1, k, b, y);
 }
 
 // The panel chain: everything of pair r after its first diagonal tile -- panel solve of column k over {k+1} + U_q, column
 // update, diag(k+1), panel solve of column k+1 over U_q (b != null: the forward substitution rides along).  A caller whose
 // diag(k) is not done yet (hoisted, or launched behind the previous pair's update) launches it first.
 template <typename T>
-static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0, T *V1, T *b, hipStream_t st) {
-  launch_trsm(p, w, r.k, r.rows1, r.c1, V0, b, st);
+[[nodiscard]] static int panel_chain(ba_problem *p, DenseLDLT<T> *w, const PairRows &r, T *V0, T *V1, T *b, hipStream_t st) {
+  BA_CHECK(launch_trsm(p, w, r.k, r.rows1, r.c1, V0, b, st));
   if (r.c1 == 0) return BA_OK;  // last, single tile column: y_k only
-  launch_col(p, w, r.k, r.rows1, r.c1, V0, st);
-  launch_diag(p, w, r.k + 1, st);
-  launch_trsm(p, w, r.k + 1, r.rows2, r.c2, V1, b, st);
-  return BA_OK;
+  BA_CHECK(launch_col(p, w, r.k, r.rows1, r.c1, V0, st));
+  BA_CHECK(launch_diag(p, w, r.k + 1, st));
+  return launch_trsm(p, w, r.k + 1, r.rows2, r.c2, V1, b, st);
 }
 
 // ---- look-ahead of one pair (dense_ldl_factor_sparse: "Look-ahead of one pair"; dense_ldl_factor below its fused zone) ------
@@ -2008,16 +1994,16 @@ struct RestAhead {
 // pair r's trailing update split for the look-ahead: the lead first, alone on the chip (beside the rest it takes as long as
 // the whole update: measured), then the rest on at most rest_cus CUs beside the next chain
 template <typename T>
-static int launch_pair_ahead(ba_problem *p, DenseLDLT<T> *w, RestAhead<T> &la, const PairRows &r, const UpdateSplit &s, int slot, const T *V0,
-                             const T *V1, int rest_cus) {
+[[nodiscard]] static int launch_pair_ahead(ba_problem *p, DenseLDLT<T> *w, RestAhead<T> &la, const PairRows &r, const UpdateSplit &s,
+                                           int slot, const T *V0, const T *V1, int rest_cus) {
   if (s.nlead > 0) {
     ProfScope ps(p, PC_LDL_UPDATE_RS, la.st);
-    hipLaunchKernelGGL(k_ldl_update_rs<T>, dim3(4 * s.lead_tiles), dim3(256), RS_LDS_ELEMS * sizeof(T), la.st, w->S, w->col_off, V0, V1, r.k,
-                       r.k + 2, s.lead_tiles, r.rows2, r.c2);
+    BA_CHECK(BA_LAUNCH(k_ldl_update_rs<T>, 4 * s.lead_tiles, 256, RS_LDS_ELEMS * sizeof(T), la.st, w->S, w->col_off, V0, V1, r.k, r.k + 2,
+                       s.lead_tiles, r.rows2, r.c2));
   }
   BA_CHECK(la.fork(slot));
-  hipLaunchKernelGGL(k_ldl_update_part<T>, dim3(rest_grid(s.rest_tiles, rest_cus)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off, V0,
-                     V1, r.k, s.rest_tiles, r.rows2 ? r.rows2 + s.nlead : nullptr, r.k + 2 + s.nlead);
+  BA_CHECK(BA_LAUNCH(k_ldl_update_part<T>, rest_grid(s.rest_tiles, rest_cus), 512, part_lds_bytes<T>(), w->rest, w->S, w->col_off, V0, V1,
+                     r.k, s.rest_tiles, r.rows2 ? r.rows2 + s.nlead : nullptr, r.k + 2 + s.nlead));
   return la.launched(slot);
 }
 
@@ -2085,7 +2071,7 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
                           !env_off("BA_LDL_TAIL_LOOKAHEAD");
   const int ahead_min = env_int("BA_LDL_TAIL_LOOKAHEAD_MIN", TAIL_AHEAD_MIN_TILES);
   RestAhead<T> la{w, st};
-  launch_diag(p, w, 0, st, nullptr, !w->hoisting);
+  BA_CHECK(launch_diag(p, w, 0, st, nullptr, !w->hoisting));
   for (int k = 0, slot = 0; k < nt; k += 2, slot ^= 1) {
     const PairRows r = pair_rows(w, k / 2);
     T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
@@ -2097,31 +2083,29 @@ int dense_ldl_factor(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b) {
     const int need = (k + 3 < nt) ? 3 : 1;
     BA_CHECK(la.join(slot));  // (the rest of the pair two steps back read these panel buffers)
     if (next_fused) {  // the next pair's leading tiles: waits in place for `need` tiles of this pair's trailing update
-      launch_pairdiag(p, w, k + 2, w->vpanel(slot ^ 1, 0), d_b, w->hoist, w->ready + k + 2, need);
+      BA_CHECK(launch_pairdiag(p, w, k + 2, w->vpanel(slot ^ 1, 0), d_b, w->hoist, w->ready + k + 2, need));
       BA_HIP_CHECK(hipEventRecord(w->ev_chain, w->hoist));
     } else if (next_hoist1) {  // the next pair's first diagonal tile only
-      launch_diag(p, w, k + 2, w->hoist, w->ready + k + 2);
+      BA_CHECK(launch_diag(p, w, k + 2, w->hoist, w->ready + k + 2));
       BA_HIP_CHECK(hipEventRecord(w->ev_chain, w->hoist));
     }
-    if (fused(k)) launch_pairtrsm(p, w, k, V0, V1, d_b, st);
-    else panel_chain(p, w, r, V0, V1, d_b, st);  // diag(k) is done: first tile, hoisted, or the in-order branch below
+    // (panel_chain: diag(k) is done: first tile, hoisted, or the in-order branch below)
+    BA_CHECK(fused(k) ? launch_pairtrsm(p, w, k, V0, V1, d_b, st) : panel_chain(p, w, r, V0, V1, d_b, st));
     if (!more) break;
     BA_CHECK(la.join(slot ^ 1));  // rest(q-1) has updated this pair's tiles too
     const bool hoisted = next_fused || next_hoist1;
     if (ahead)
       BA_CHECK(launch_pair_ahead(p, w, la, r, s, slot, V0, V1, TAIL_REST_CUS));
     else
-      launch_pair(p, w, k, r.rows2, r.c2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1,
-                  tickets_on ? w->tickets + (k / 2) * TICKET_SLOTS : nullptr);
+      BA_CHECK(launch_pair(p, w, k, r.rows2, r.c2, V0, V1, st, hoisted ? w->ready + k + 2 : nullptr, next_fused ? need : 1,
+                           tickets_on ? w->tickets + (k / 2) * TICKET_SLOTS : nullptr));
     if (hoisted)
       BA_HIP_CHECK(hipStreamWaitEvent(st, w->ev_chain, 0));  // join: the hoisted workgroup's outputs are written
     else
-      launch_diag(p, w, k + 2, st);  // (with the look-ahead: behind the lead, beside the rest)
+      BA_CHECK(launch_diag(p, w, k + 2, st));  // (with the look-ahead: behind the lead, beside the rest)
   }
   BA_CHECK(la.join(0));
-  BA_CHECK(la.join(1));
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return la.join(1);
 }
 
 // ---- block-sparse reduced camera system ---------------------------------------------------------------------------------
@@ -2291,45 +2275,45 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
       auto tile = [&](int k) { return w->S + tix(w->hco(), k, k) * NB * NB; };
       auto panel_of = [&](int k, T *V, const int *rows) { return RunPanel<T>{w->Linv + (int64_t)k * NB * NB, w->D + (int64_t)k * NB, V, k, rows}; };
       auto diag2 = [&](int ka, int kb) {
-        hipLaunchKernelGGL(k_ldl_diag2<T>, dim3(2), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(T), st, tile(ka), w->Linv + (int64_t)ka * NB * NB,
-                           w->D + (int64_t)ka * NB, tile(kb), w->Linv + (int64_t)kb * NB * NB, w->D + (int64_t)kb * NB, w->flag);
+        return BA_LAUNCH(k_ldl_diag2<T>, 2, DIAG_THREADS, DIAG_LDS_ELEMS * sizeof(T), st, tile(ka), w->Linv + (int64_t)ka * NB * NB,
+                         w->D + (int64_t)ka * NB, tile(kb), w->Linv + (int64_t)kb * NB * NB, w->D + (int64_t)kb * NB, w->flag);
       };
       auto trsm2 = [&](const RunPanel<T> &pa, int ca, const RunPanel<T> &pb, int cb) {
-        hipLaunchKernelGGL(fwd_kernel(d_b, k_ldl_trsm_rs2<T, true>, k_ldl_trsm_rs2<T, false>), dim3(4 * (ca + cb)), dim3(256),
-                           RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, pa, pb, 4 * ca, d_b, y);
+        return BA_LAUNCH(fwd_kernel(d_b, k_ldl_trsm_rs2<T, true>, k_ldl_trsm_rs2<T, false>), 4 * (ca + cb), 256, RS_LDS_ELEMS * sizeof(T), st,
+                         w->S, w->col_off, pa, pb, 4 * ca, d_b, y);
       };
       BA_CHECK(la.join(slot));  // (the rests of the step two back read these panel buffers)
-      diag2(a.k, b.k);
+      BA_CHECK(diag2(a.k, b.k));
       const RunPanel<T> a0 = panel_of(a.k, VA, a.rows1), b0 = panel_of(b.k, VB, b.rows1);
-      trsm2(a0, a.c1, b0, b.c1);
-      hipLaunchKernelGGL(k_ldl_col_rs2<T>, dim3(4 * (a.c1 + b.c1)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * a.c1);
-      diag2(a.k + 1, b.k + 1);
-      trsm2(panel_of(a.k + 1, VA + panel, a.rows2), a.c2, panel_of(b.k + 1, VB + panel, b.rows2), b.c2);
+      BA_CHECK(trsm2(a0, a.c1, b0, b.c1));
+      BA_CHECK(BA_LAUNCH(k_ldl_col_rs2<T>, 4 * (a.c1 + b.c1), 256, RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, a0, b0, 4 * a.c1));
+      BA_CHECK(diag2(a.k + 1, b.k + 1));
+      BA_CHECK(trsm2(panel_of(a.k + 1, VA + panel, a.rows2), a.c2, panel_of(b.k + 1, VB + panel, b.rows2), b.c2));
       // the two pair updates: panels (k, k+1) of either run over its U_q -- with the look-ahead of the single run (lead strips of
       // both runs first, both rests on a part of the chip beside the next step's chain) when the rests are long enough
       const UpdateSplit sa = update_split(a), sb = update_split(b);
       const RunPanel<T> ua = panel_of(a.k, VA, a.rows2), ub = panel_of(b.k, VB, b.rows2);
       BA_CHECK(la.join(slot ^ 1));
       if (lookahead && i + 1 < both && sa.rest_tiles + sb.rest_tiles >= 2 * la_min) {
-        if (sa.lead_tiles + sb.lead_tiles > 0)
-          hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (sa.lead_tiles + sb.lead_tiles)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off,
-                             ua, sa.lead_tiles, ub, sb.lead_tiles, panel, a.c2, b.c2);
+        BA_CHECK(BA_LAUNCH(k_ldl_update_rs2<T>, 4 * (sa.lead_tiles + sb.lead_tiles), 256, RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, ua,
+                           sa.lead_tiles, ub, sb.lead_tiles, panel, a.c2, b.c2));
         BA_CHECK(la.fork(slot));
-        hipLaunchKernelGGL(k_ldl_update_part2<T>, dim3(rest_grid(sa.rest_tiles + sb.rest_tiles)), dim3(512), part_lds_bytes<T>(), w->rest, w->S, w->col_off,
-                           panel_of(a.k, VA, a.rows2 + sa.nlead), sa.rest_tiles, panel_of(b.k, VB, b.rows2 + sb.nlead), sb.rest_tiles, panel);
+        BA_CHECK(BA_LAUNCH(k_ldl_update_part2<T>, rest_grid(sa.rest_tiles + sb.rest_tiles), 512, part_lds_bytes<T>(), w->rest, w->S,
+                           w->col_off, panel_of(a.k, VA, a.rows2 + sa.nlead), sa.rest_tiles, panel_of(b.k, VB, b.rows2 + sb.nlead),
+                           sb.rest_tiles, panel));
         BA_CHECK(la.launched(slot));
       } else {
         const int na = a.c2 * (a.c2 + 1) / 2, nb2 = b.c2 * (b.c2 + 1) / 2;
         if (na + nb2 <= update_rs_max())
-          hipLaunchKernelGGL(k_ldl_update_rs2<T>, dim3(4 * (na + nb2)), dim3(256), RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, ua, na, ub, nb2, panel, 0, 0);
+          BA_CHECK(BA_LAUNCH(k_ldl_update_rs2<T>, 4 * (na + nb2), 256, RS_LDS_ELEMS * sizeof(T), st, w->S, w->col_off, ua, na, ub, nb2, panel,
+                             0, 0));
         else
-          hipLaunchKernelGGL(k_ldl_update2<T>, dim3(((na + 7) / 8) * 8 + ((nb2 + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S, w->col_off,
-                             ua, na, ub, nb2, panel);
+          BA_CHECK(BA_LAUNCH(k_ldl_update2<T>, grid_for(na, 8) * 8 + grid_for(nb2, 8) * 8, 256, gemm_priv_lds_bytes<T>(), st, w->S, w->col_off,
+                             ua, na, ub, nb2, panel));
       }
     }
     BA_CHECK(la.join(0));
     BA_CHECK(la.join(1));
-    BA_HIP_CHECK(hipGetLastError());
     for (int q = both; q < pat->a_clean; q++) order.push_back(q);  // the longer run's remainder, then everything else
     for (int q = pat->a_clean; q < pat->split; q++) order.push_back(q);
     for (int q = pat->split + both; q < npairs; q++) order.push_back(q);
@@ -2341,8 +2325,8 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
     const int slot = (int)(it & 1);
     T *V0 = w->vpanel(slot, 0), *V1 = w->vpanel(slot, 1);
     BA_CHECK(la.join(slot));  // (the rest of the pair two steps back read these panel buffers; joined long ago: see lead below)
-    launch_diag(p, w, r.k, st, nullptr, !two && r.k == 0);  // (in one chain the first diagonal kernel clears the pivot flag)
-    panel_chain(p, w, r, V0, V1, d_b, st);
+    BA_CHECK(launch_diag(p, w, r.k, st, nullptr, !two && r.k == 0));  // (in one chain the first diagonal kernel clears the pivot flag)
+    BA_CHECK(panel_chain(p, w, r, V0, V1, d_b, st));
     if (r.c2 == 0) continue;
     const bool next_adjacent = it + 1 < order.size() && order[it + 1] == order[it] + 1;
     const UpdateSplit s = update_split(r);
@@ -2350,18 +2334,16 @@ int dense_ldl_factor_sparse(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d
     if (lookahead && next_adjacent && s.rest_tiles >= la_min) {
       BA_CHECK(launch_pair_ahead(p, w, la, r, s, slot, V0, V1, REST_CUS));
     } else {
-      launch_pair(p, w, r.k, r.rows2, r.c2, V0, V1, st);
+      BA_CHECK(launch_pair(p, w, r.k, r.rows2, r.c2, V0, V1, st));
     }
   }
   BA_CHECK(la.join(0));
-  BA_CHECK(la.join(1));
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return la.join(1);
 }
 
 // pair update (panels k, k+1) of the owned tile columns own_cols[m0 .. m1)
 template <typename T>
-static int launch_pair_owned(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0, const T *V1, hipStream_t st, int m0, int m1) {
+[[nodiscard]] static int launch_pair_owned(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0, const T *V1, hipStream_t st, int m0, int m1) {
   if (m0 >= m1) return BA_OK;
   const int64_t nblk64 = w->h_own_pref[(size_t)m1] - w->h_own_pref[(size_t)m0];
   if (nblk64 <= 0) return BA_OK;
@@ -2372,37 +2354,34 @@ static int launch_pair_owned(ba_problem *p, DenseLDLT<T> *w, int k, const T *V0,
     Lp0 = w->L_of(V0);
     Lp1 = w->L_of(V1);
   }
-  hipLaunchKernelGGL((k_ldl_update<T, 1, true>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st,
-                     w->S, w->col_off, V0, V1, k, w->h_own_cols[(size_t)m0], (int)w->nt, nblk, (int *)nullptr, w->own_cols, w->own_pref, m0, m1,
-                     1, (const int *)nullptr, Lp0, Lp1);
-  return BA_OK;
+  return BA_LAUNCH((k_ldl_update<T, 1, true>), grid_for(nblk, 8) * 8, 256, gemm_priv_lds_bytes<T>(), st, w->S, w->col_off, V0, V1, k,
+                   w->h_own_cols[(size_t)m0], w->nt, nblk, nullptr, w->own_cols, w->own_pref, m0, m1, 1, nullptr, Lp0, Lp1, nullptr, TSB,
+                   nullptr);
 }
 
 // the tiles [from, to) of pair q's update list (block-sparse S on several ranks: the pattern's tiles in this rank's columns)
 template <typename T>
-static int launch_pair_list(ba_problem *p, DenseLDLT<T> *w, int q, const T *V0, const T *V1, hipStream_t st, int from, int to) {
+[[nodiscard]] static int launch_pair_list(ba_problem *p, DenseLDLT<T> *w, int q, const T *V0, const T *V1, hipStream_t st, int from, int to) {
   const int nblk = to - from;
   if (nblk <= 0) return BA_OK;
   ProfScope ps(p, PC_LDL_UPDATE, st);
-  hipLaunchKernelGGL((k_ldl_update<T, 1>), dim3(((nblk + 7) / 8) * 8), dim3(256), gemm_priv_lds_bytes<T>(), st, w->S, w->col_off, V0, V1,
-                     2 * q, 2 * q + 2, (int)w->nt, nblk, (int *)nullptr, (const int *)nullptr, (const int64_t *)nullptr, 0, 0, 1,
-                     (const int *)nullptr, w->L_of(V0), w->L_of(V1), (const int2 *)(w->upd_ij + w->h_upd_ptr[(size_t)q] + from));
-  return BA_OK;
+  return BA_LAUNCH((k_ldl_update<T, 1>), grid_for(nblk, 8) * 8, 256, gemm_priv_lds_bytes<T>(), st, w->S, w->col_off, V0, V1, 2 * q,
+                   2 * q + 2, w->nt, nblk, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, w->L_of(V0), w->L_of(V1),
+                   w->upd_ij + w->h_upd_ptr[(size_t)q] + from, TSB, nullptr);
 }
 
 // the panel chain of pair (k, k+1) on its owner, first diagonal tile included (no right-hand side)
 template <typename T>
-static int dist_chain(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, hipStream_t st) {
-  launch_diag(p, w, k, st);
-  panel_chain(p, w, pair_rows(w, k / 2), V0, V1, (T *)nullptr, st);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+[[nodiscard]] static int dist_chain(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, hipStream_t st) {
+  BA_CHECK(launch_diag(p, w, k, st));
+  return panel_chain(p, w, pair_rows(w, k / 2), V0, V1, (T *)nullptr, st);
 }
 
 // L = V D^-1 of tile column c over `count` tile rows; Lcol: where that column's L tiles live (see k_ldl_scale_panel)
 template <typename T>
-static void launch_scale_panel(DenseLDLT<T> *w, T *Lcol, const T *V, int c, const int *rows, int count, hipStream_t st) {
-  if (count > 0) hipLaunchKernelGGL(k_ldl_scale_panel<T>, dim3(count), dim3(256), 0, st, Lcol, V, w->D + (int64_t)c * NB, c + 1, rows);
+[[nodiscard]] static int launch_scale_panel(DenseLDLT<T> *w, T *Lcol, const T *V, int c, const int *rows, int count, hipStream_t st) {
+  if (count <= 0) return BA_OK;
+  return BA_LAUNCH(k_ldl_scale_panel<T>, count, 256, 0, st, Lcol, V, w->D + (int64_t)c * NB, c + 1, rows);
 }
 
 // pair (k, k+1) from its owner to everybody: V = L D of both panels, the two inverted diagonal tiles, the 256 pivots (one
@@ -2432,13 +2411,12 @@ static int dist_transfer(ba_problem *p, DenseLDLT<T> *w, int k, T *V0, T *V1, in
   if (w->own_only) {
     // every rank (the owner too: one source for the update's operand) rebuilds L of both panels in the panel buffer beside
     // V; nothing of another rank's columns enters S
-    launch_scale_panel(w, w->L_of(V0), V0, k, r.rows1, r.c1, st);
-    if (two) launch_scale_panel(w, w->L_of(V1), V1, k + 1, r.rows2, r.c2, st);
+    BA_CHECK(launch_scale_panel(w, w->L_of(V0), V0, k, r.rows1, r.c1, st));
+    if (two) BA_CHECK(launch_scale_panel(w, w->L_of(V1), V1, k + 1, r.rows2, r.c2, st));
   } else if (owner != w->rank) {  // replicated S: into this rank's copy of the two tile columns (the owner's holds L already)
-    launch_scale_panel(w, w->S + (w->hco()[k] - k) * NB * NB, V0, k, r.rows1, r.c1, st);
-    if (two) launch_scale_panel(w, w->S + (w->hco()[k + 1] - (k + 1)) * NB * NB, V1, k + 1, r.rows2, r.c2, st);
+    BA_CHECK(launch_scale_panel(w, w->S + (w->hco()[k] - k) * NB * NB, V0, k, r.rows1, r.c1, st));
+    if (two) BA_CHECK(launch_scale_panel(w, w->S + (w->hco()[k + 1] - (k + 1)) * NB * NB, V1, k + 1, r.rows2, r.c2, st));
   }
-  BA_HIP_CHECK(hipGetLastError());
   return BA_OK;
 }
 
@@ -2450,13 +2428,9 @@ static int dist_forward_pair(DenseLDLT<T> *w, int k, T *V0, T *V1, T *d_b, hipSt
   if (!d_b) return BA_OK;
   T *y = w->D + w->nt * NB;
   const PairRows r = pair_rows(w, k / 2);
-  hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c1), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k, 0, r.rows1,
-                     (const T *)w->L_of(V0));
-  if (k + 1 < (int)w->nt)
-    hipLaunchKernelGGL(k_fwd_step<T>, dim3(1 + r.c2), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, 0, r.rows2,
-                       (const T *)w->L_of(V1));
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_fwd_step<T>, 1 + r.c1, 256, 0, st, w->S, w->col_off, w->Linv, d_b, y, k, 0, r.rows1, w->L_of(V0)));
+  if (k + 1 >= (int)w->nt) return BA_OK;
+  return BA_LAUNCH(k_fwd_step<T>, 1 + r.c2, 256, 0, st, w->S, w->col_off, w->Linv, d_b, y, k + 1, 0, r.rows2, w->L_of(V1));
 }
 
 // Distributed right-looking factorisation over the ranks of p->comm: tile column pair q = (2q, 2q+1) belongs to rank
@@ -2550,11 +2524,9 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
     }
   }
   // an exactly zero pivot is seen by the owner of that tile only: make the flag collective
-  hipLaunchKernelGGL(k_flag_to_double, dim3(1), dim3(1), 0, st, w->flag, w->flag_sum);
+  BA_CHECK(BA_LAUNCH(k_flag_to_double, 1, 1, 0, st, w->flag, w->flag_sum));
   BA_CHECK(comm_allreduce(p, w->flag_sum, 1, st));
-  hipLaunchKernelGGL(k_double_to_flag, dim3(1), dim3(1), 0, st, w->flag_sum, w->flag);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_double_to_flag, 1, 1, 0, st, w->flag_sum, w->flag);
 }
 
 // ---- backward sweep with per-rank ownership of S ---------------------------------------------------------------------------
@@ -2566,7 +2538,7 @@ int dense_ldl_factor_dist(ba_problem *p, DenseLDLT<T> *w, hipStream_t st, T *d_b
 // rode along with the panels, dist_forward_pair.)
 template <typename T>
 __global__ __launch_bounds__(256) void k_bwd_col_part(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ x,
-                                                       T *__restrict__ part, int k, int nt, const int *__restrict__ rows = nullptr) {
+                                                       T *__restrict__ part, int k, int nt, const int *__restrict__ rows) {
   // block b: tile row i = k + 2 + b / 2 (rows: the b / 2-th tile row of the pair's pattern) of column c = k + (b & 1):
   // part[(c - k) nt + i][:] = L_ic' x_i
   __shared__ T xi[NB], red[2][NB];
@@ -2582,8 +2554,8 @@ __global__ __launch_bounds__(256) void k_bwd_col_part(const T *__restrict__ S, c
 template <typename T>
 __global__ __launch_bounds__(256) void k_bwd_col_final(const T *__restrict__ S, const int64_t *__restrict__ co, const T *__restrict__ Linv,
                                                         const T *__restrict__ D, const T *__restrict__ y, const T *__restrict__ part,
-                                                        T *__restrict__ x, int k, int nt, const int *__restrict__ rows = nullptr,
-                                                        int nrows = 0) {
+                                                        T *__restrict__ x, int k, int nt, const int *__restrict__ rows,
+                                                        int nrows) {
   // rows / nrows: the tile rows below the pair that its pattern holds (block-sparse S); null: k + 2 .. nt - 1
   __shared__ T z[NB], xk1[NB], red[2][NB];
   const int tid = threadIdx.x;
@@ -2632,10 +2604,8 @@ static int dense_ldl_bwd_dist(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_
     const bool two = k + 1 < nt;
     if (owner == me) {  // over the tile rows below the pair: U_q
       const PairRows r = pair_rows(w, k / 2);
-      if (r.c2 > 0) hipLaunchKernelGGL(k_bwd_col_part<T>, dim3(2 * r.c2), dim3(256), 0, st, w->S, w->col_off, d_b, w->bpart, k, nt, r.rows2);
-      hipLaunchKernelGGL(k_bwd_col_final<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, w->bpart, d_b, k, nt, r.rows2,
-                         r.c2);
-      BA_HIP_CHECK(hipGetLastError());
+      BA_CHECK(BA_LAUNCH(k_bwd_col_part<T>, 2 * r.c2, 256, 0, st, w->S, w->col_off, d_b, w->bpart, k, nt, r.rows2));
+      BA_CHECK(BA_LAUNCH(k_bwd_col_final<T>, 1, 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, w->bpart, d_b, k, nt, r.rows2, r.c2));
     }
     BA_CHECK(comm_bcast(p, d_b + (int64_t)k * NB, (int64_t)(two ? 2 : 1) * NB * sizeof(T), owner, st));
   }
@@ -2656,7 +2626,7 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
   }
   if (!forward_done)
     for (int k = 0; k < nt; k++)
-      hipLaunchKernelGGL(k_fwd_step<T>, dim3(nt - k), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_b, y, k);
+      BA_CHECK(BA_LAUNCH(k_fwd_step<T>, nt - k, 256, 0, st, w->S, w->col_off, w->Linv, d_b, y, k, 0, nullptr, nullptr));
   if (w->sparse && !p->comm.active()) {  // block-sparse S: one tile row per launch over the tile columns of its pattern
     const TilePattern *pat = w->pat;
     if (!forward_done) {
@@ -2674,40 +2644,36 @@ int dense_ldl_solve(ba_problem *p, DenseLDLT<T> *w, T *d_b, hipStream_t st, bool
       const int k = 2 * q + 1;
       if (k >= nt) {
         const int c0 = pat->lcol_ptr[(size_t)(nt - 1)], c1 = pat->lcol_ptr[(size_t)nt];
-        hipLaunchKernelGGL(k_bwd_step<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, nt - 1,
-                           0, w->lcol + c0);
-      } else {
-        const int c0 = pat->lpair_ptr[(size_t)q], c1 = pat->lpair_ptr[(size_t)q + 1];
-        hipLaunchKernelGGL(k_bwd_pair<T>, dim3(1 + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k, w->lpair + c0);
+        return BA_LAUNCH(k_bwd_step<T>, 1 + (c1 - c0), 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, nt - 1, 0, w->lcol + c0);
       }
+      const int c0 = pat->lpair_ptr[(size_t)q], c1 = pat->lpair_ptr[(size_t)q + 1];
+      return BA_LAUNCH(k_bwd_pair<T>, 1 + (c1 - c0), 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k, w->lpair + c0);
     };
     int c_hi = pat->split + pat->b_clean;
     if (c_hi > 0 && 2 * c_hi - 1 >= nt) c_hi--;  // (a last single row stays with the rows behind the groups)
     // (read per call: a test compares the sweeps in one process)
     if (pat->split > 0 && c_hi > pat->split && !env_off("BA_SPARSE_TWO_RUNS") && !env_off("BA_SPARSE_BWD2")) {
-      for (int q = npairs - 1; q >= c_hi; q--) single(q);
+      for (int q = npairs - 1; q >= c_hi; q--) BA_CHECK(single(q));
       const int both = std::min(pat->split, c_hi - pat->split);
       for (int i = 0; i < both; i++) {
         const int qa = pat->split - 1 - i, qc = c_hi - 1 - i;
         const int a0 = pat->lpair_ptr[(size_t)qa], a1 = pat->lpair_ptr[(size_t)qa + 1];
         const int c0 = pat->lpair_ptr[(size_t)qc], c1 = pat->lpair_ptr[(size_t)qc + 1];
-        hipLaunchKernelGGL(k_bwd_pair2<T>, dim3(2 + (a1 - a0) + (c1 - c0)), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b,
-                           2 * qa + 1, w->lpair + a0, 1 + (a1 - a0), 2 * qc + 1, w->lpair + c0);
+        BA_CHECK(BA_LAUNCH(k_bwd_pair2<T>, 2 + (a1 - a0) + (c1 - c0), 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, 2 * qa + 1,
+                           w->lpair + a0, 1 + (a1 - a0), 2 * qc + 1, w->lpair + c0));
       }
-      for (int q = pat->split - 1 - both; q >= 0; q--) single(q);
-      for (int q = c_hi - 1 - both; q >= pat->split; q--) single(q);
+      for (int q = pat->split - 1 - both; q >= 0; q--) BA_CHECK(single(q));
+      for (int q = c_hi - 1 - both; q >= pat->split; q--) BA_CHECK(single(q));
     } else {
-      for (int q = npairs - 1; q >= 0; q--) single(q);
+      for (int q = npairs - 1; q >= 0; q--) BA_CHECK(single(q));
     }
-    BA_HIP_CHECK(hipGetLastError());
     return BA_OK;
   }
   int k = nt - 1;
   for (; k >= 1; k -= 2)  // panels k, k-1 per launch; blocks: 1 + (k-1) tile rows below the pair
-    hipLaunchKernelGGL(k_bwd_pair<T>, dim3(k), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k);
+    BA_CHECK(BA_LAUNCH(k_bwd_pair<T>, k, 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, k, nullptr));
   if (k == 0)  // an odd number of tile rows: the first one alone
-    hipLaunchKernelGGL(k_bwd_step<T>, dim3(1), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, 0);
-  BA_HIP_CHECK(hipGetLastError());
+    BA_CHECK(BA_LAUNCH(k_bwd_step<T>, 1, 256, 0, st, w->S, w->col_off, w->Linv, w->D, y, d_b, 0, 0, nullptr));
   return BA_OK;
 }
 
@@ -2722,10 +2688,9 @@ int dense_ldl_solve_multi(ba_problem *p, DenseLDLT<T> *w, T *d_B, int64_t ld, in
   }
   ProfScope ps(p, PC_SHARED_SWEEP, st);
   for (int k = 0; k < nt; k++)
-    hipLaunchKernelGGL(k_fwd_step<T>, dim3(nt - k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, d_B, d_y, k, (int)ld);
+    BA_CHECK(BA_LAUNCH(k_fwd_step<T>, dim3(nt - k, m), 256, 0, st, w->S, w->col_off, w->Linv, d_B, d_y, k, ld, nullptr, nullptr));
   for (int k = nt - 1; k >= 0; k--)
-    hipLaunchKernelGGL(k_bwd_step<T>, dim3(1 + k, m), dim3(256), 0, st, w->S, w->col_off, w->Linv, w->D, d_y, d_B, k, (int)ld);
-  BA_HIP_CHECK(hipGetLastError());
+    BA_CHECK(BA_LAUNCH(k_bwd_step<T>, dim3(1 + k, m), 256, 0, st, w->S, w->col_off, w->Linv, w->D, d_y, d_B, k, ld, nullptr));
   return BA_OK;
 }
 

@@ -74,19 +74,12 @@ int fix_upload(ba_problem *p) {
 int launch_fix_mask(ba_problem *p, double *d_J, hipStream_t st) {
   if (!p->fix_on() || p->nobs <= 0) return BA_OK;
   ProfScope ps(p, PC_FIXED, st);
-  const unsigned nb = (unsigned)((p->nobs + FB - 1) / FB);
+  const unsigned nb = grid_for(p->nobs, FB);
   const bool cam = p->fix_ncam > 0, pnt = p->fix_npnt > 0;
   if (cam && pnt)
-    hipLaunchKernelGGL((k_fix_mask<true, true>), dim3(nb), dim3(FB), 0, st, p->nobs, p->cam0, p->pnt0, p->d_fix_cam, p->d_fix_pnt,
-                       (double2 *)d_J);
-  else if (cam)
-    hipLaunchKernelGGL((k_fix_mask<true, false>), dim3(nb), dim3(FB), 0, st, p->nobs, p->cam0, p->pnt0, p->d_fix_cam,
-                       (const uint8_t *)nullptr, (double2 *)d_J);
-  else
-    hipLaunchKernelGGL((k_fix_mask<false, true>), dim3(nb), dim3(FB), 0, st, p->nobs, p->cam0, p->pnt0, (const uint16_t *)nullptr,
-                       p->d_fix_pnt, (double2 *)d_J);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+    return BA_LAUNCH((k_fix_mask<true, true>), nb, FB, 0, st, p->nobs, p->cam0, p->pnt0, p->d_fix_cam, p->d_fix_pnt, (double2 *)d_J);
+  if (cam) return BA_LAUNCH((k_fix_mask<true, false>), nb, FB, 0, st, p->nobs, p->cam0, p->pnt0, p->d_fix_cam, nullptr, (double2 *)d_J);
+  return BA_LAUNCH((k_fix_mask<false, true>), nb, FB, 0, st, p->nobs, p->cam0, p->pnt0, nullptr, p->d_fix_pnt, (double2 *)d_J);
 }
 
 extern "C" int ba_lm_set_fixed(ba_problem *p, const uint16_t *cam_mask, const uint8_t *pnt_fixed) {

@@ -11,6 +11,7 @@
 #include "ba_order.h"  // TilePattern, camera orderings (host only)
 
 void ba_set_error(const char *fmt, ...);
+#include "ba_launch.h"  // BA_LAUNCH: every kernel launch; grid_for
 
 #define BA_HIP_CHECK(expr)                                                                          \
   do {                                                                                              \

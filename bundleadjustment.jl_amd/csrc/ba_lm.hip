@@ -290,10 +290,7 @@ __global__ void k_convert(const A *__restrict__ in, B *__restrict__ out, int64_t
 template <typename A, typename B>
 int launch_convert(const A *in, B *out, int64_t n, hipStream_t st) {
   if (n <= 0) return BA_OK;
-  const int64_t blocks = std::min<int64_t>((n + 255) / 256, 1 << 16);
-  hipLaunchKernelGGL((k_convert<A, B>), dim3((unsigned)blocks), dim3(256), 0, st, in, out, n);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH((k_convert<A, B>), std::min(grid_for(n, 256), 1u << 16), 256, 0, st, in, out, n);
 }
 // the two directions the controller converts in, as plain functions: they take the workspace's owners as well
 int launch_convert(const double *in, float *out, int64_t n, hipStream_t st) { return launch_convert<double, float>(in, out, n, st); }

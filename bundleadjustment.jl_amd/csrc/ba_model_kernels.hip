@@ -340,7 +340,6 @@ __global__ __launch_bounds__(BLK) void k_residual(int64_t nobs, const int *__res
 
 }  // namespace
 
-static inline unsigned grid_for(int64_t n, int blk) { return (unsigned)((n + blk - 1) / blk); }
 // Persistent grid of k_jac_coord: as many workgroups as the device keeps resident (LDS: 3 per CU for double), never
 // more than there are batches of 64 observations.
 template <typename K>
@@ -371,9 +370,7 @@ static unsigned jac_grid(ba_problem *p, K kernel, int64_t nobs) {
 int launch_cam_pre_f64(ba_problem *p, const double *d_x, const double **d_cpre, hipStream_t st) {
   double *cpad = nullptr;
   BA_CHECK(ba_scratch(p, 3, (size_t)(p->ncams * CPAD + 2) * sizeof(double), (void **)&cpad));
-  if (p->ncams > 0)
-    hipLaunchKernelGGL(k_cam_pre<double>, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_x + 3 * p->npnts, cpad);
-  BA_HIP_CHECK(hipGetLastError());
+  BA_CHECK(BA_LAUNCH(k_cam_pre<double>, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_x + 3 * p->npnts, cpad));
   *d_cpre = cpad;
   return BA_OK;
 }
@@ -383,12 +380,8 @@ int launch_residual_f64(ba_problem *p, const double *d_x, double *d_r, hipStream
   ProfScope ps(p, PC_RESIDUAL, st);
   double *cpad = nullptr;
   BA_CHECK(ba_scratch(p, 3, (size_t)(p->ncams * CPAD + 2) * sizeof(double), (void **)&cpad));
-  hipLaunchKernelGGL(k_cam_pre<double>, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_x + 3 * p->npnts,
-                     cpad);
-  hipLaunchKernelGGL((k_residual<double, 2>), dim3(grid_for(p->nobs, BLK * 2)), dim3(BLK), 0, st, p->nobs, p->cam0, p->pnt0, d_x,
-                     (const double *)cpad, p->pt2d, d_r);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_cam_pre<double>, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_x + 3 * p->npnts, cpad));
+  return BA_LAUNCH((k_residual<double, 2>), grid_for(p->nobs, BLK * 2), BLK, 0, st, p->nobs, p->cam0, p->pnt0, d_x, cpad, p->pt2d, d_r);
 }
 
 int launch_residual_f32(ba_problem *p, const float *d_x, float *d_r, hipStream_t st) {
@@ -396,20 +389,14 @@ int launch_residual_f32(ba_problem *p, const float *d_x, float *d_r, hipStream_t
   ProfScope ps(p, PC_RESIDUAL, st);
   float *cpad = nullptr;
   BA_CHECK(ba_scratch(p, 3, (size_t)(p->ncams * CPAD + 2) * sizeof(double), (void **)&cpad));
-  hipLaunchKernelGGL(k_cam_pre<float>, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_x + 3 * p->npnts, cpad);
-  hipLaunchKernelGGL((k_residual<float, 2>), dim3(grid_for(p->nobs, BLK * 2)), dim3(BLK), 0, st, p->nobs, p->cam0, p->pnt0, d_x,
-                     (const float *)cpad, p->pt2d_f32, d_r);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_cam_pre<float>, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_x + 3 * p->npnts, cpad));
+  return BA_LAUNCH((k_residual<float, 2>), grid_for(p->nobs, BLK * 2), BLK, 0, st, p->nobs, p->cam0, p->pnt0, d_x, cpad, p->pt2d_f32, d_r);
 }
 
 int launch_jac_structure(ba_problem *p, int64_t *d_rows, int64_t *d_cols, hipStream_t st) {
   if (p->nobs == 0) return BA_OK;
   ProfScope ps(p, PC_JAC_STRUCTURE, st);
-  hipLaunchKernelGGL(k_jac_structure, dim3(grid_for(12 * p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->npnts, p->cam0,
-                     p->pnt0, d_rows, d_cols);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_jac_structure, grid_for(12 * p->nobs, BLK), BLK, 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_rows, d_cols);
 }
 
 int launch_jac_coord_f64(ba_problem *p, const double *d_x, double *d_vals, hipStream_t st) {
@@ -417,12 +404,9 @@ int launch_jac_coord_f64(ba_problem *p, const double *d_x, double *d_vals, hipSt
   ProfScope ps(p, PC_JAC_COORD, st);
   double *cpad = nullptr;
   BA_CHECK(ba_scratch(p, 3, (size_t)(p->ncams * CPAD + 2) * sizeof(double), (void **)&cpad));
-  hipLaunchKernelGGL(k_cam_pre<double>, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_x + 3 * p->npnts,
-                     cpad);
-  hipLaunchKernelGGL((k_jac_coord<double, 0>), dim3(jac_grid(p, k_jac_coord<double, 0>, p->nobs)), dim3(BLK), 0, st,
-                     p->nobs, p->npnts, p->cam0, p->pnt0, d_x, (const double *)cpad, d_vals);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_cam_pre<double>, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_x + 3 * p->npnts, cpad));
+  return BA_LAUNCH((k_jac_coord<double, 0>), jac_grid(p, k_jac_coord<double, 0>, p->nobs), BLK, 0, st, p->nobs, p->npnts, p->cam0,
+                   p->pnt0, d_x, cpad, d_vals);
 }
 
 int launch_jac_coord_f32(ba_problem *p, const float *d_x, float *d_vals, hipStream_t st) {
@@ -430,9 +414,7 @@ int launch_jac_coord_f32(ba_problem *p, const float *d_x, float *d_vals, hipStre
   ProfScope ps(p, PC_JAC_COORD, st);
   float *cpad = nullptr;
   BA_CHECK(ba_scratch(p, 3, (size_t)(p->ncams * CPAD + 2) * sizeof(double), (void **)&cpad));
-  hipLaunchKernelGGL(k_cam_pre<float>, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_x + 3 * p->npnts, cpad);
-  hipLaunchKernelGGL((k_jac_coord<float, 0>), dim3(jac_grid(p, k_jac_coord<float, 0>, p->nobs)), dim3(BLK), 0, st, p->nobs,
-                     p->npnts, p->cam0, p->pnt0, d_x, (const float *)cpad, d_vals);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_cam_pre<float>, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_x + 3 * p->npnts, cpad));
+  return BA_LAUNCH((k_jac_coord<float, 0>), jac_grid(p, k_jac_coord<float, 0>, p->nobs), BLK, 0, st, p->nobs, p->npnts, p->cam0,
+                   p->pnt0, d_x, cpad, d_vals);
 }

@@ -59,8 +59,8 @@ __global__ __launch_bounds__(BLK) void k_point_blocks(int64_t npnts, const int *
 __global__ __launch_bounds__(BLK) void k_cam_blocks(const int *__restrict__ cam_ptr, const int *__restrict__ cam_obs,
                                                     const int *__restrict__ pnt0, const double *__restrict__ J,
                                                     const double *__restrict__ r, const double *__restrict__ u,
-                                                    double *__restrict__ Hcc, double *__restrict__ out9, double lam = 0.0,
-                                                    const int *__restrict__ opos = nullptr) {
+                                                    double *__restrict__ Hcc, double *__restrict__ out9, double lam,
+                                                    const int *__restrict__ opos) {
   constexpr int NACC = 54;
   __shared__ double red[BLK / 64][NACC];
   const int c = blockIdx.x;
@@ -180,9 +180,8 @@ template <int MODE>
 __global__ __launch_bounds__(BLK) void k_cam_blocks_st(const int *__restrict__ cam_ptr, const int *__restrict__ cam_obs,
                                                         const int *__restrict__ pnt0, const double *__restrict__ J,
                                                         const double *__restrict__ r, const double *__restrict__ u,
-                                                        double *__restrict__ Hcc, double *__restrict__ out9, double lam = 0.0,
-                                                        const int *__restrict__ cam_pnt = nullptr,
-                                                        const int *__restrict__ opos = nullptr) {
+                                                        double *__restrict__ Hcc, double *__restrict__ out9, double lam,
+                                                        const int *__restrict__ cam_pnt, const int *__restrict__ opos) {
   constexpr int NACC = 9;
   __shared__ double slots[(BLK / 64) * ST_WAVE_ELEMS];
   __shared__ double red[BLK / 64][NACC];
@@ -455,8 +454,8 @@ __global__ __launch_bounds__(BLK, 6) void k_schur_blocks(int64_t nkeys, const in
                                                        const double *__restrict__ Hcc, double lambda,
                                                        const double *__restrict__ lam_dev, double *__restrict__ S,
                                                        const int64_t *__restrict__ co, const double *__restrict__ damp_c,
-                                                       int split_above, const int *__restrict__ klist = nullptr,
-                                                       const int *__restrict__ cam_of = nullptr) {
+                                                       int split_above, const int *__restrict__ klist,
+                                                       const int *__restrict__ cam_of) {
   // klist (per-rank ownership of S): the keys whose blocks touch the tile columns of the chunk being assembled; nkeys is
   // then the length of that list
   __shared__ __attribute__((aligned(16))) double ring[BLK / 64][SCHUR_RING];
@@ -567,8 +566,7 @@ __global__ __launch_bounds__(BLK) void k_schur_combine(int64_t nsplit, const int
                                                         const double *__restrict__ partial, const double *__restrict__ Hcc,
                                                         double lambda, const double *__restrict__ lam_dev, double *__restrict__ S,
                                                         const int64_t *__restrict__ co, const double *__restrict__ damp_c,
-                                                        const int *__restrict__ slist = nullptr,
-                                                        const int *__restrict__ cam_of = nullptr) {
+                                                        const int *__restrict__ slist, const int *__restrict__ cam_of) {
   if (lam_dev) lambda *= lam_dev[0];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   for (int64_t sq = (int64_t)blockIdx.x * (BLK / 64) + wv; sq < nsplit; sq += (int64_t)gridDim.x * (BLK / 64)) {
@@ -906,8 +904,8 @@ template <bool FULL>
 __global__ __launch_bounds__(BLK) void k_wtv(int64_t npnts, const int *__restrict__ pt_ptr, const int *__restrict__ cam0,
                                               const double *__restrict__ J, const double *__restrict__ Uinv,
                                               const double *__restrict__ v, double *__restrict__ h,
-                                              const double *__restrict__ u = nullptr, const double *__restrict__ r = nullptr,
-                                              double cr = 1.0, double *__restrict__ partial = nullptr) {
+                                              const double *__restrict__ u, const double *__restrict__ r, double cr,
+                                              double *__restrict__ partial) {
   // FULL: the back-substitution of the direct path, h = -(u + U^-1 W' v), and -- r != null -- the model value of the step in
   // a second sweep over the wave's rows, again one lane per observation: partial[blockIdx.x] = this block's part of
   // sum |A h + B v + cr r|^2
@@ -1200,7 +1198,6 @@ __global__ __launch_bounds__(1024) void k_cg_beta_dir(int64_t n, int nb, const d
 }  // namespace
 
 
-static inline unsigned grid_for(int64_t n, int blk) { return (unsigned)((n + blk - 1) / blk); }
 // one wave per item (the Schur kernels: a key, a chunk of a long key, a split key), BLK / 64 items per workgroup; at most
 // 2^22 workgroups (x 256 lanes = 2^30 work-items), the waves stride over what is left
 static inline unsigned wave_grid(int64_t n) {
@@ -1214,12 +1211,8 @@ int launch_point_blocks(ba_problem *p, const double *d_J, const double *d_r, dou
   if (p->npnts == 0) return BA_OK;
   ProfScope ps(p, PC_POINT_BLOCKS, st);
   if (p->point_sorted)
-    hipLaunchKernelGGL(k_point_blocks_lpo, dim3(grid_for(p->npnts, BLK)), dim3(BLK), 0, st, p->npnts, p->pt_ptr, d_J, d_r, d_Hpp, d_gp);
-  else
-    hipLaunchKernelGGL(k_point_blocks, dim3(grid_for(p->npnts, BLK)), dim3(BLK), 0, st, p->npnts, p->pt_ptr, p->pt_obs,
-                       d_J, d_r, d_Hpp, d_gp);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+    return BA_LAUNCH(k_point_blocks_lpo, grid_for(p->npnts, BLK), BLK, 0, st, p->npnts, p->pt_ptr, d_J, d_r, d_Hpp, d_gp);
+  return BA_LAUNCH(k_point_blocks, grid_for(p->npnts, BLK), BLK, 0, st, p->npnts, p->pt_ptr, p->pt_obs, d_J, d_r, d_Hpp, d_gp);
 }
 
 int launch_cam_blocks(ba_problem *p, const double *d_J, const double *d_r, double *d_Hcc, double *d_gc,
@@ -1229,13 +1222,10 @@ int launch_cam_blocks(ba_problem *p, const double *d_J, const double *d_r, doubl
   // the 54-accumulator Hcc pass is faster with plain per-lane loads (0.32 against 0.50 ms on Venice); the light passes
   // (J'r here, the right-hand side in launch_schur_rhs) are latency-bound and gain from the staged rows (0.68 -> 0.47 ms)
   if (d_Hcc)
-    hipLaunchKernelGGL(k_cam_blocks, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_r, (const double *)nullptr, d_Hcc, d_gc);
-  else
-    hipLaunchKernelGGL(k_cam_blocks_st<1>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                       d_r, (const double *)nullptr, (double *)nullptr, d_gc);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+    return BA_LAUNCH(k_cam_blocks, (unsigned)p->ncams, BLK, 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_r, nullptr, d_Hcc, d_gc,
+                     0.0, nullptr);
+  return BA_LAUNCH(k_cam_blocks_st<1>, (unsigned)p->ncams, BLK, 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_r, nullptr, nullptr,
+                   d_gc, 0.0, nullptr, nullptr);
 }
 
 int launch_schur_prep(ba_problem *p, double lambda, const double *d_Hpp, const double *d_gp, double *d_Uinv,
@@ -1247,17 +1237,15 @@ int launch_schur_prep(ba_problem *p, double lambda, const double *d_Hpp, const d
     return BA_OK;
   }
   ProfScope ps(p, PC_SCHUR_PREP, st);
-  hipLaunchKernelGGL(k_schur_prep, dim3(grid_for(p->npnts, BLK)), dim3(BLK), 0, st, p->npnts, lambda, d_lambda, d_Hpp,
-                     d_gp, d_Uinv, d_u, d_damp, d_lambda_copy, d_zero, nzero);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_schur_prep, grid_for(p->npnts, BLK), BLK, 0, st, p->npnts, lambda, d_lambda, d_Hpp, d_gp, d_Uinv, d_u, d_damp,
+                   d_lambda_copy, d_zero, nzero);
 }
 
 // long keys: the partial sums of their chunks (k_schur_combine adds them up in a fixed order)
-static void launch_schur_partials(const SchurTasks *T, const double *d_J, const double *d_Y, hipStream_t st) {
-  if (T->nsplit > 0)
-    hipLaunchKernelGGL(k_schur_chunks, dim3(wave_grid(T->nchunks)), dim3(BLK), 0, st, T->nchunks, T->chunk_t0, T->chunk_t1, T->task_a,
-                       T->task_b, d_J, d_Y, T->partial);
+[[nodiscard]] static int launch_schur_partials(const SchurTasks *T, const double *d_J, const double *d_Y, hipStream_t st) {
+  if (T->nsplit == 0) return BA_OK;
+  return BA_LAUNCH(k_schur_chunks, wave_grid(T->nchunks), BLK, 0, st, T->nchunks, T->chunk_t0, T->chunk_t1, T->task_a, T->task_b, d_J,
+                   d_Y, T->partial);
 }
 
 // The assembly of S: launch_schur_pre once per step -- the per-observation Y blocks -- then launch_schur_chunk per chunk of
@@ -1270,26 +1258,20 @@ static void launch_schur_partials(const SchurTasks *T, const double *d_J, const 
 
 int launch_schur_pre(ba_problem *p, const SchurTasks *T, const double *d_J, const double *d_Uinv, double *d_Y, hipStream_t st,
                      bool partials) {
-  if (p->nobs > 0)
-    hipLaunchKernelGGL(k_obs_y, dim3(grid_for(p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->pnt0, d_J, d_Uinv, d_Y);
-  if (partials) launch_schur_partials(T, d_J, d_Y, st);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_obs_y, grid_for(p->nobs, BLK), BLK, 0, st, p->nobs, p->pnt0, d_J, d_Uinv, d_Y));
+  return partials ? launch_schur_partials(T, d_J, d_Y, st) : BA_OK;
 }
 
 int launch_schur_chunk(ba_problem *p, const SchurTasks *T, const SchurChunk *c, const double *d_J, const double *d_Y,
                        const double *d_Hcc, double lambda, double *dest, int64_t n, int64_t npad, hipStream_t st,
                        const double *d_lambda, const double *d_damp, bool partials) {
-  const double *damp_c = d_damp ? d_damp + 3 * p->npnts : (const double *)nullptr;
-  if (c->nkeys > 0)
-    hipLaunchKernelGGL(k_schur_blocks, dim3(wave_grid(c->nkeys)), dim3(BLK), 0, st, c->nkeys, T->key_ptr, T->key_ca, T->key_cb, T->task_a,
-                       T->task_b, d_J, d_Y, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, T->nsplit > 0 ? 2 * T->chunk : 0, c->keys, T->cam_of);
-  if (partials) launch_schur_partials(T, d_J, d_Y, st);
-  if (c->nskeys > 0)
-    hipLaunchKernelGGL(k_schur_combine, dim3(wave_grid(c->nskeys)), dim3(BLK), 0, st, c->nskeys, T->skey, T->skey_c0, T->key_ca, T->key_cb,
-                       T->partial, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, c->skeys, T->cam_of);
-  if (npad > n) hipLaunchKernelGGL(k_pad_diag, dim3(grid_for(npad - n, BLK)), dim3(BLK), 0, st, n, npad, dest, c->cco);
-  BA_HIP_CHECK(hipGetLastError());
+  const double *damp_c = d_damp ? d_damp + 3 * p->npnts : nullptr;
+  BA_CHECK(BA_LAUNCH(k_schur_blocks, wave_grid(c->nkeys), BLK, 0, st, c->nkeys, T->key_ptr, T->key_ca, T->key_cb, T->task_a, T->task_b,
+                     d_J, d_Y, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, T->nsplit > 0 ? 2 * T->chunk : 0, c->keys, T->cam_of));
+  if (partials) BA_CHECK(launch_schur_partials(T, d_J, d_Y, st));
+  BA_CHECK(BA_LAUNCH(k_schur_combine, wave_grid(c->nskeys), BLK, 0, st, c->nskeys, T->skey, T->skey_c0, T->key_ca, T->key_cb,
+                     T->partial, d_Hcc, lambda, d_lambda, dest, c->cco, damp_c, c->skeys, T->cam_of));
+  if (npad > n) BA_CHECK(BA_LAUNCH(k_pad_diag, grid_for(npad - n, BLK), BLK, 0, st, n, npad, dest, c->cco));
   return BA_OK;
 }
 
@@ -1307,25 +1289,16 @@ __global__ __launch_bounds__(BLK) void k_scale_S_list(int64_t n, const double *_
 }
 int launch_scale_S_list(ba_problem *p, int64_t n, const double *d_dsc, double *d_S, const int2 *d_tiles, int64_t ntiles, hipStream_t st) {
   if (ntiles <= 0) return BA_OK;
-  hipLaunchKernelGGL(k_scale_S_list, dim3((unsigned)ntiles), dim3(BLK), 0, st, n, d_dsc, d_S, d_tiles);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_scale_S_list, (unsigned)ntiles, BLK, 0, st, n, d_dsc, d_S, d_tiles);
 }
 
 int launch_hcc_diag(ba_problem *p, const double *d_Hcc, double *d_hdiag, hipStream_t st) {
-  if (p->ncams == 0) return BA_OK;
-  hipLaunchKernelGGL(k_hcc_diag, dim3(grid_for(9 * p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_Hcc, d_hdiag);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_hcc_diag, grid_for(9 * p->ncams, BLK), BLK, 0, st, p->ncams, d_Hcc, d_hdiag);
 }
 
 int launch_cam_scale(ba_problem *p, const double *d_hdiag, double add, double *d_dsc, hipStream_t st,
                      const double *d_lambda, const int *d_pos) {
-  if (p->ncams == 0) return BA_OK;
-  hipLaunchKernelGGL(k_cam_scale, dim3(grid_for(9 * p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_hdiag, add, d_lambda,
-                     d_dsc, d_pos);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cam_scale, grid_for(9 * p->ncams, BLK), BLK, 0, st, p->ncams, d_hdiag, add, d_lambda, d_dsc, d_pos);
 }
 
 // dst[9 c + j] = src[9 pos[c] + j]: the camera part of the step back from the block rows of S to camera order
@@ -1335,20 +1308,15 @@ __global__ __launch_bounds__(BLK) void k_gather_cams(int64_t ncams, const int *_
   if (i < 9 * ncams) dst[i] = src[9 * (int64_t)pos[i / 9] + i % 9];
 }
 int launch_gather_cams(ba_problem *p, const int *d_pos, const double *d_src, double *d_dst, hipStream_t st) {
-  if (p->ncams == 0) return BA_OK;
-  hipLaunchKernelGGL(k_gather_cams, dim3(grid_for(9 * p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_pos, d_src, d_dst);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_gather_cams, grid_for(9 * p->ncams, BLK), BLK, 0, st, p->ncams, d_pos, d_src, d_dst);
 }
 
 int launch_schur_rhs(ba_problem *p, const double *d_J, const double *d_r, const double *d_u, double *d_rhs,
                      hipStream_t st, const int *d_cam_pnt, const int *d_pos) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_SCHUR_RHS, st);
-  hipLaunchKernelGGL(k_cam_blocks_st<2>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                     d_r, d_u, (double *)nullptr, d_rhs, 0.0, d_cam_pnt, d_pos);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cam_blocks_st<2>, (unsigned)p->ncams, BLK, 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_r, d_u, nullptr, d_rhs,
+                   0.0, d_cam_pnt, d_pos);
 }
 
 // d_r_model != null (and the problem is point-sorted): |J delta + cr r|^2 of the step is formed in the same pass ->
@@ -1364,18 +1332,15 @@ int launch_backsub(ba_problem *p, const double *d_J, const double *d_Uinv, const
     const bool with_model = d_r_model && d_partial && d_scal;
     // one lane per observation in both sweeps (k_wtv<true>; the first staged version walked a point's observations with one
     // lane: Venice 0.75 -> 0.33 ms, Dubrovnik 0.28 -> 0.10 ms per call)
-    hipLaunchKernelGGL(k_wtv<true>, dim3(nb), dim3(BLK), 0, st, p->npnts, p->pt_ptr, p->cam0, d_J, d_Uinv, d_dc, d_dp, d_u,
-                       with_model ? d_r_model : (const double *)nullptr, cr, d_partial);
+    BA_CHECK(BA_LAUNCH(k_wtv<true>, nb, BLK, 0, st, p->npnts, p->pt_ptr, p->cam0, d_J, d_Uinv, d_dc, d_dp, d_u,
+                       with_model ? d_r_model : nullptr, cr, d_partial));
     if (with_model) {
-      hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLK), 0, st, (int)nb, d_partial, d_scal, slot);
+      BA_CHECK(BA_LAUNCH(k_sum_partials, 1, BLK, 0, st, nb, d_partial, d_scal, slot));
       if (model_done) *model_done = true;
     }
-  } else {
-    hipLaunchKernelGGL(k_backsub, dim3(nb), dim3(BLK), 0, st, p->npnts, p->pt_ptr, p->pt_obs, p->cam0, d_J, d_Uinv, d_u, d_dc,
-                       d_dp);
+    return BA_OK;
   }
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_backsub, nb, BLK, 0, st, p->npnts, p->pt_ptr, p->pt_obs, p->cam0, d_J, d_Uinv, d_u, d_dc, d_dp);
 }
 
 // |J delta + cr r|^2 -> scal[slot]
@@ -1383,11 +1348,8 @@ int launch_model_sq(ba_problem *p, const double *d_J, const double *d_r, const d
                     double *d_scal, int slot, hipStream_t st, double cr) {
   ProfScope ps(p, PC_TRIAL, st);
   const int nb = red_blocks(p->nobs);
-  hipLaunchKernelGGL(k_model_sq, dim3(nb), dim3(BLK), 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_J, d_r, d_delta,
-                     cr, d_partial);
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(BLK), 0, st, nb, d_partial, d_scal, slot);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_model_sq, nb, BLK, 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_J, d_r, d_delta, cr, d_partial));
+  return BA_LAUNCH(k_sum_partials, 1, BLK, 0, st, nb, d_partial, d_scal, slot);
 }
 
 int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi, hipStream_t st) {
@@ -1398,10 +1360,8 @@ int launch_sumsq_multi(ba_problem *p, SumsqJobs *jobs, double *d_partial_multi, 
   }
   ProfScope ps(p, PC_REDUCE, st);
   for (int v = 0; v < jobs->count; v++) jobs->nb[v] = red_blocks(jobs->n[v]);
-  hipLaunchKernelGGL(k_sumsq_multi, dim3(jobs->count * RED_BLOCKS), dim3(BLK), 0, st, *jobs, d_partial_multi);
-  hipLaunchKernelGGL(k_sum_partials_multi, dim3(1), dim3(BLK), 0, st, *jobs, (const double *)d_partial_multi);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_sumsq_multi, jobs->count * RED_BLOCKS, BLK, 0, st, *jobs, d_partial_multi));
+  return BA_LAUNCH(k_sum_partials_multi, 1, BLK, 0, st, *jobs, d_partial_multi);
 }
 
 // The LM controller's scalars to pinned host memory by a kernel that addresses the host buffers directly (hipHostMalloc
@@ -1422,50 +1382,33 @@ int launch_publish(const double *d_a, int na, double *h_a, const double *d_b, in
     ba_set_error("launch_publish: more than 64 scalars");
     return BA_ERR_ARG;
   }
-  hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, st, d_a, na, h_a, d_b, nb, h_b, d_flag, h_flag);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_publish, 1, 64, 0, st, d_a, na, h_a, d_b, nb, h_b, d_flag, h_flag);
 }
 
 int launch_axpy(ba_problem *p, int64_t n, const double *d_x, const double *d_d, double *d_y, hipStream_t st) {
-  if (n == 0) return BA_OK;
-  hipLaunchKernelGGL(k_axpy, dim3(grid_for(n, BLK)), dim3(BLK), 0, st, n, d_x, d_d, d_y);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_axpy, grid_for(n, BLK), BLK, 0, st, n, d_x, d_d, d_y);
 }
 
 int launch_scale_scalar(ba_problem *p, int64_t n, double *d_v, double alpha, hipStream_t st) {
-  if (n == 0) return BA_OK;
-  hipLaunchKernelGGL(k_scale_scalar, dim3(grid_for(n, BLK)), dim3(BLK), 0, st, n, d_v, alpha);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_scale_scalar, grid_for(n, BLK), BLK, 0, st, n, d_v, alpha);
 }
 
 int launch_scale_vec(ba_problem *p, int64_t n, const double *d_s, double *d_v, int divide, hipStream_t st) {
-  if (n == 0) return BA_OK;
-  hipLaunchKernelGGL(k_scale_vec, dim3(grid_for(n, BLK)), dim3(BLK), 0, st, n, d_s, d_v, divide);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_scale_vec, grid_for(n, BLK), BLK, 0, st, n, d_s, d_v, divide);
 }
 
 // ---- facto_type = Float16 helpers (see k_f16_cols) ---------------------------------------------------------------------
 int launch_col_sq(ba_problem *p, const double *d_Hpp, const double *d_hdiag, double *d_jn2, hipStream_t st) {
   const int64_t nvar = 3 * p->npnts + 9 * p->ncams;
-  if (nvar == 0) return BA_OK;
-  hipLaunchKernelGGL(k_col_sq, dim3(grid_for(nvar, BLK)), dim3(BLK), 0, st, p->npnts, p->ncams, d_Hpp, d_hdiag, d_jn2);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_col_sq, grid_for(nvar, BLK), BLK, 0, st, p->npnts, p->ncams, d_Hpp, d_hdiag, d_jn2);
 }
 
 int launch_f16_scale(ba_problem *p, double lambda, double mu, const double *d_jn2, const double *d_J, const double *d_r,
                      double *d_dcol, double *d_damp, double *d_Jq, double *d_rq, hipStream_t st) {
   const int64_t nvar = 3 * p->npnts + 9 * p->ncams;
-  if (nvar > 0) hipLaunchKernelGGL(k_f16_cols, dim3(grid_for(nvar, BLK)), dim3(BLK), 0, st, nvar, d_jn2, lambda, mu, d_dcol, d_damp);
-  if (p->nobs > 0)
-    hipLaunchKernelGGL(k_f16_quantize, dim3(grid_for(p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_J,
-                       d_r, d_dcol, mu, d_Jq, d_rq);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_f16_cols, grid_for(nvar, BLK), BLK, 0, st, nvar, d_jn2, lambda, mu, d_dcol, d_damp));
+  return BA_LAUNCH(k_f16_quantize, grid_for(p->nobs, BLK), BLK, 0, st, p->nobs, p->npnts, p->cam0, p->pnt0, d_J, d_r, d_dcol, mu, d_Jq,
+                   d_rq);
 }
 
 // ---- PCG launchers ------------------------------------------------------------------------------------------------------
@@ -1474,61 +1417,42 @@ int launch_wuw(ba_problem *p, const double *d_J, const double *d_h, const double
                hipStream_t st, const int *d_cam_pnt) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_SCHUR_RHS, st);
-  hipLaunchKernelGGL(k_cam_blocks_st<3>, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J,
-                     d_v, d_h, const_cast<double *>(d_Hcc), d_q, lam, d_cam_pnt);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cam_blocks_st<3>, (unsigned)p->ncams, BLK, 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_v, d_h,
+                   const_cast<double *>(d_Hcc), d_q, lam, d_cam_pnt, nullptr);
 }
 int launch_schur_diag(ba_problem *p, const double *d_J, const double *d_Uinv, const double *d_Hcc, double *d_blk45, hipStream_t st) {
   if (p->ncams == 0) return BA_OK;
   ProfScope ps(p, PC_SCHUR_S, st);
-  hipLaunchKernelGGL(k_schur_diag, dim3((unsigned)p->ncams), dim3(BLK), 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_Uinv, d_Hcc,
-                     d_blk45);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_schur_diag, (unsigned)p->ncams, BLK, 0, st, p->cam_ptr, p->cam_obs, p->pnt0, d_J, d_Uinv, d_Hcc, d_blk45);
 }
 int launch_pcg_factor(ba_problem *p, double lambda, double *d_blk45, int *d_flag, hipStream_t st) {
-  hipLaunchKernelGGL(k_pcg_factor, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, lambda, d_blk45, d_flag);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_pcg_factor, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, lambda, d_blk45, d_flag);
 }
 int launch_axpy_s(ba_problem *p, int64_t n, double a, const double *d_x, double *d_y, hipStream_t st) {
-  if (n == 0) return BA_OK;
-  hipLaunchKernelGGL(k_axpy_s, dim3(grid_for(n, BLK)), dim3(BLK), 0, st, n, a, d_x, d_y);
-  return BA_OK;
+  return BA_LAUNCH(k_axpy_s, grid_for(n, BLK), BLK, 0, st, n, a, d_x, d_y);
 }
 int launch_cg_alpha(ba_problem *p, int64_t n, const double *d_p, const double *d_q, double *d_cg, hipStream_t st) {
   ProfScope ps(p, PC_REDUCE, st);
-  hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(1024), 0, st, n, d_p, d_q, d_cg);
-  return BA_OK;
+  return BA_LAUNCH(k_cg_alpha, 1, 1024, 0, st, n, d_p, d_q, d_cg);
 }
 // d_partial: 2 entries per block of 256 cameras
 int launch_cg_step(ba_problem *p, const double *d_cg, const double *d_L45, const double *d_p, const double *d_q, double *d_x,
                    double *d_r, double *d_z, double *d_partial, int first, hipStream_t st) {
-  if (p->ncams == 0) return BA_OK;
-  hipLaunchKernelGGL(k_cg_step, dim3(grid_for(p->ncams, BLK)), dim3(BLK), 0, st, p->ncams, d_cg, d_L45, d_p, d_q, d_x, d_r, d_z,
-                     d_partial, first);
-  return BA_OK;
+  return BA_LAUNCH(k_cg_step, grid_for(p->ncams, BLK), BLK, 0, st, p->ncams, d_cg, d_L45, d_p, d_q, d_x, d_r, d_z, d_partial, first);
 }
 int launch_cg_beta_dir(ba_problem *p, int64_t n, const double *d_partial, double *d_cg, const double *d_z, double *d_p, int first,
                        hipStream_t st) {
   ProfScope ps(p, PC_REDUCE, st);
-  hipLaunchKernelGGL(k_cg_beta_dir, dim3(1), dim3(1024), 0, st, n, (int)grid_for(p->ncams, BLK), d_partial, d_cg, d_z, d_p, first);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_cg_beta_dir, 1, 1024, 0, st, n, grid_for(p->ncams, BLK), d_partial, d_cg, d_z, d_p, first);
 }
 // h = -U^-1 W' v (the point sweep of the PCG product); observations grouped by point (BAL order)
 int launch_wtv(ba_problem *p, const double *d_J, const double *d_Uinv, const double *d_v, double *d_h, hipStream_t st) {
   if (p->npnts == 0) return BA_OK;
   ProfScope ps(p, PC_BACKSUB, st);
-  hipLaunchKernelGGL(k_wtv<false>, dim3(grid_for(p->npnts, BLK)), dim3(BLK), 0, st, p->npnts, p->pt_ptr, p->cam0, d_J, d_Uinv, d_v, d_h);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_wtv<false>, grid_for(p->npnts, BLK), BLK, 0, st, p->npnts, p->pt_ptr, p->cam0, d_J, d_Uinv, d_v, d_h, nullptr,
+                   nullptr, 1.0, nullptr);
 }
 // cam_pnt[q] = pnt0[cam_obs[q]]: the point of every observation in camera order (built once per problem)
 int launch_cam_pnt(ba_problem *p, int *d_cam_pnt, hipStream_t st) {
-  if (p->nobs == 0) return BA_OK;
-  hipLaunchKernelGGL(k_gather_int, dim3(grid_for(p->nobs, BLK)), dim3(BLK), 0, st, p->nobs, p->cam_obs, p->pnt0, d_cam_pnt);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_gather_int, grid_for(p->nobs, BLK), BLK, 0, st, p->nobs, p->cam_obs, p->pnt0, d_cam_pnt);
 }

@@ -155,15 +155,15 @@ struct ObsArgs {
 };
 
 template <int KIND, bool INFO, bool WEIGHTS>
-void launch_one(const ObsArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL((k_obs_scale<KIND, INFO, WEIGHTS>), dim3(obs_blocks(a.nobs)), dim3(OBS_TILE), 0, st, a.nobs, a.c2, a.L,
-                     (double2 *)a.r, (double2 *)a.J, a.w, a.partial, a.whiten_r);
+int launch_one(const ObsArgs &a, hipStream_t st) {
+  return BA_LAUNCH((k_obs_scale<KIND, INFO, WEIGHTS>), obs_blocks(a.nobs), OBS_TILE, 0, st, a.nobs, a.c2, a.L, (double2 *)a.r,
+                   (double2 *)a.J, a.w, a.partial, a.whiten_r);
 }
 
 template <int KIND>
-void launch_kind(bool info, const ObsArgs &a, hipStream_t st) {
-  if (info) a.w ? launch_one<KIND, true, true>(a, st) : launch_one<KIND, true, false>(a, st);
-  else a.w ? launch_one<KIND, false, true>(a, st) : launch_one<KIND, false, false>(a, st);
+int launch_kind(bool info, const ObsArgs &a, hipStream_t st) {
+  if (info) return a.w ? launch_one<KIND, true, true>(a, st) : launch_one<KIND, true, false>(a, st);
+  return a.w ? launch_one<KIND, false, true>(a, st) : launch_one<KIND, false, false>(a, st);
 }
 
 }  // namespace
@@ -183,14 +183,12 @@ int launch_obs_scale(ba_problem *p, double *d_r, double *d_J, double *d_w, doubl
   const ObsArgs a = {p->nobs, p->loss_scale * p->loss_scale, info ? (const double *)p->d_info : nullptr, d_r, d_J, d_w, d_partial,
                      residual_plain ? 1 : 0};
   switch (kind) {
-    case BA_LOSS_HUBER: launch_kind<BA_LOSS_HUBER>(info, a, st); break;
-    case BA_LOSS_SOFT_L1: launch_kind<BA_LOSS_SOFT_L1>(info, a, st); break;
-    case BA_LOSS_CAUCHY: launch_kind<BA_LOSS_CAUCHY>(info, a, st); break;
-    case BA_LOSS_ARCTAN: launch_kind<BA_LOSS_ARCTAN>(info, a, st); break;
-    default: launch_kind<BA_LOSS_LINEAR>(info, a, st); break;
+    case BA_LOSS_HUBER: return launch_kind<BA_LOSS_HUBER>(info, a, st);
+    case BA_LOSS_SOFT_L1: return launch_kind<BA_LOSS_SOFT_L1>(info, a, st);
+    case BA_LOSS_CAUCHY: return launch_kind<BA_LOSS_CAUCHY>(info, a, st);
+    case BA_LOSS_ARCTAN: return launch_kind<BA_LOSS_ARCTAN>(info, a, st);
+    default: return launch_kind<BA_LOSS_LINEAR>(info, a, st);
   }
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
 }
 
 extern "C" int ba_lm_set_loss(ba_problem *p, int kind, double scale) {

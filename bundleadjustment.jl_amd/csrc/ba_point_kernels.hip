@@ -397,10 +397,7 @@ static int refine_launch(ba_problem *p, double *d_x, int init, int max_iter, dou
   a.x = d_x, a.status = d_status, a.cost = d_cost, a.counts = w.counts;
   a.init = init, a.max_iter = max_iter, a.kind = p->loss;
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
-  const int64_t nb = (w.n_wave + PT_BLK / 64 - 1) / (PT_BLK / 64) + (w.n_lane + PT_BLK - 1) / PT_BLK;
-  hipLaunchKernelGGL(k_refine_points, dim3((unsigned)nb), dim3(PT_BLK), 0, st, a);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_refine_points, grid_for(w.n_wave, PT_BLK / 64) + grid_for(w.n_lane, PT_BLK), PT_BLK, 0, st, a);
 }
 
 extern "C" int ba_refine_points_dev(ba_problem *p, double *d_x_inout, int init, int max_iter, double xtol, double lambda0,

@@ -275,8 +275,6 @@ __global__ __launch_bounds__(PB) void k_prior_ctr_rhs(int64_t n, const int *__re
   for (int i = 0; i < 6; i++) out[i] -= (H[i] * w[0] + H[6 + i] * w[1]) + H[12 + i] * w[2];
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + PB - 1) / PB); }
-
 }  // namespace
 
 // the handle's priors to the device, once per change (ba_lm_set_priors marks them dirty), with the buffers the kernels write
@@ -305,17 +303,11 @@ int launch_prior_lin(ba_problem *p, const double *d_x, double *d_Hpp, double *d_
   const uint8_t *fp = p->fix_npnt > 0 ? (const uint8_t *)p->d_fix_pnt : nullptr;
   const double *xc = d_x + 3 * p->npnts;
   double *d = p->pri_d, *cost = p->pri_cost();
-  if (pt.n > 0)
-    hipLaunchKernelGGL(k_prior_point_lin, dim3(blocks_for(pt.n)), dim3(PB), 0, st, pt.n, pt.idx, pt.mu, pt.info, d_x, fp, d_Hpp, d_gp,
-                       d, cost);
-  if (cm.n > 0)
-    hipLaunchKernelGGL(k_prior_cam_lin, dim3(blocks_for(cm.n)), dim3(PB), 0, st, cm.n, cm.idx, cm.mu, cm.info, xc, fc, d_Hcc, d_gc,
-                       d + 3 * pt.n, cost + pt.n);
-  if (ct.n > 0)
-    hipLaunchKernelGGL(k_prior_ctr_lin, dim3(blocks_for(ct.n)), dim3(PB), 0, st, ct.n, ct.idx, ct.mu, ct.info, xc, fc, d_Hcc, d_gc,
-                       d + 3 * pt.n + 9 * cm.n, (double *)p->pri_H, cost + pt.n + cm.n);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_prior_point_lin, grid_for(pt.n, PB), PB, 0, st, pt.n, pt.idx, pt.mu, pt.info, d_x, fp, d_Hpp, d_gp, d, cost));
+  BA_CHECK(BA_LAUNCH(k_prior_cam_lin, grid_for(cm.n, PB), PB, 0, st, cm.n, cm.idx, cm.mu, cm.info, xc, fc, d_Hcc, d_gc, d + 3 * pt.n,
+                     cost + pt.n));
+  return BA_LAUNCH(k_prior_ctr_lin, grid_for(ct.n, PB), PB, 0, st, ct.n, ct.idx, ct.mu, ct.info, xc, fc, d_Hcc, d_gc,
+                   d + 3 * pt.n + 9 * cm.n, p->pri_H, cost + pt.n + cm.n);
 }
 
 int launch_prior_rhs(ba_problem *p, double *d_rhs, const int *d_pos, hipStream_t st) {
@@ -324,13 +316,9 @@ int launch_prior_rhs(ba_problem *p, double *d_rhs, const int *d_pos, hipStream_t
   ProfScope ps(p, PC_PRIOR, st);
   const uint16_t *fc = p->fix_ncam > 0 ? (const uint16_t *)p->d_fix_cam : nullptr;
   const double *d = p->pri_d;
-  if (cm.n > 0)
-    hipLaunchKernelGGL(k_prior_cam_rhs, dim3(blocks_for(cm.n)), dim3(PB), 0, st, cm.n, cm.idx, cm.info, d + 3 * pt.n, fc, d_pos, d_rhs);
-  if (ct.n > 0)
-    hipLaunchKernelGGL(k_prior_ctr_rhs, dim3(blocks_for(ct.n)), dim3(PB), 0, st, ct.n, ct.idx, ct.info, d + 3 * pt.n + 9 * cm.n,
-                       (const double *)p->pri_H, d_pos, d_rhs);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_prior_cam_rhs, grid_for(cm.n, PB), PB, 0, st, cm.n, cm.idx, cm.info, d + 3 * pt.n, fc, d_pos, d_rhs));
+  return BA_LAUNCH(k_prior_ctr_rhs, grid_for(ct.n, PB), PB, 0, st, ct.n, ct.idx, ct.info, d + 3 * pt.n + 9 * cm.n, p->pri_H, d_pos,
+                   d_rhs);
 }
 
 int launch_prior_step(ba_problem *p, const double *d_delta, const double *d_xt, hipStream_t st) {
@@ -340,17 +328,11 @@ int launch_prior_step(ba_problem *p, const double *d_delta, const double *d_xt, 
   const double *dc = d_delta ? d_delta + 3 * p->npnts : nullptr, *xc = d_xt ? d_xt + 3 * p->npnts : nullptr;
   const double *d = p->pri_d;
   double *model = p->pri_model(), *cost_t = p->pri_cost_trial();
-  if (pt.n > 0)
-    hipLaunchKernelGGL(k_prior_point_step, dim3(blocks_for(pt.n)), dim3(PB), 0, st, pt.n, pt.idx, pt.mu, pt.info, d, d_delta, d_xt,
-                       model, cost_t);
-  if (cm.n > 0)
-    hipLaunchKernelGGL(k_prior_cam_step, dim3(blocks_for(cm.n)), dim3(PB), 0, st, cm.n, cm.idx, cm.mu, cm.info, d + 3 * pt.n, dc, xc,
-                       model + pt.n, cost_t + pt.n);
-  if (ct.n > 0)
-    hipLaunchKernelGGL(k_prior_ctr_step, dim3(blocks_for(ct.n)), dim3(PB), 0, st, ct.n, ct.idx, ct.mu, ct.info,
-                       d + 3 * pt.n + 9 * cm.n, (const double *)p->pri_H, dc, xc, model + pt.n + cm.n, cost_t + pt.n + cm.n);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_prior_point_step, grid_for(pt.n, PB), PB, 0, st, pt.n, pt.idx, pt.mu, pt.info, d, d_delta, d_xt, model, cost_t));
+  BA_CHECK(BA_LAUNCH(k_prior_cam_step, grid_for(cm.n, PB), PB, 0, st, cm.n, cm.idx, cm.mu, cm.info, d + 3 * pt.n, dc, xc, model + pt.n,
+                     cost_t + pt.n));
+  return BA_LAUNCH(k_prior_ctr_step, grid_for(ct.n, PB), PB, 0, st, ct.n, ct.idx, ct.mu, ct.info, d + 3 * pt.n + 9 * cm.n, p->pri_H, dc, xc,
+                   model + pt.n + cm.n, cost_t + pt.n + cm.n);
 }
 
 // one kind's lists checked and copied to the handle's staging (dim: entries of h_k, 3 or 9)

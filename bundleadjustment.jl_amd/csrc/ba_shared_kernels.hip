@@ -229,29 +229,21 @@ __global__ __launch_bounds__(SB_T) void k_border_finish(int64_t npad, int mz, co
   a[i] = s;
 }
 
-unsigned row_blocks(int64_t n) { return (unsigned)((n + SB_T - 1) / SB_T); }
-
 }  // namespace
 
 int launch_grp_reduce(ba_problem *p, const int *d_gptr, const int *d_row, double *d_v, hipStream_t st) {
   ProfScope ps(p, PC_SHARED_BORDER, st);
-  hipLaunchKernelGGL(k_grp_reduce, dim3(3 * p->grp_n), dim3(SB_T), 0, st, d_gptr, d_row, d_v);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_grp_reduce, 3 * p->grp_n, SB_T, 0, st, d_gptr, d_row, d_v);
 }
 
 int launch_grp_expand(ba_problem *p, const int *d_gptr, const int *d_row, double *d_v, hipStream_t st) {
   ProfScope ps(p, PC_SHARED_BORDER, st);
-  hipLaunchKernelGGL(k_grp_expand, dim3(3 * p->grp_n), dim3(SB_T), 0, st, d_gptr, d_row, d_v);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_grp_expand, 3 * p->grp_n, SB_T, 0, st, d_gptr, d_row, d_v);
 }
 
 int launch_grp_blk45(ba_problem *p, double *d_blk45, hipStream_t st) {
   ProfScope ps(p, PC_SHARED_BORDER, st);
-  hipLaunchKernelGGL(k_grp_blk45, dim3(p->grp_n), dim3(SB_T), 0, st, p->grp_ptr, p->grp_row, d_blk45);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  return BA_LAUNCH(k_grp_blk45, p->grp_n, SB_T, 0, st, p->grp_ptr, p->grp_row, d_blk45);
 }
 
 int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double lambda, const int *d_row, const int *d_col, double *d_B,
@@ -259,12 +251,10 @@ int launch_border_prepare(ba_problem *p, const DenseLDL *l, int64_t n, double la
   ProfScope ps(p, PC_SHARED_BORDER, st);
   const int mz = 3 * p->grp_n;
   const int64_t npad = l->n;
-  hipLaunchKernelGGL(k_border_product, dim3(row_blocks(npad), mz), dim3(SB_T), 0, st, n, npad, l->S, l->col_off, p->grp_ptr, d_row, d_B);
-  hipLaunchKernelGGL(k_border_reduce, dim3(mz, mz + 1), dim3(SB_T), 0, st, npad, mz, lambda, p->grp_ptr, d_row, d_B, d_rhs, d_small);
-  hipLaunchKernelGGL(k_border_mask_vec, dim3(row_blocks(npad)), dim3(SB_T), 0, st, npad, mz, d_col, d_B, d_rhs);
-  hipLaunchKernelGGL(k_border_mask_S, dim3((unsigned)l->n_own_tiles), dim3(SB_T), 0, st, npad, d_col, l->S, l->own_tiles);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_border_product, dim3(grid_for(npad, SB_T), mz), SB_T, 0, st, n, npad, l->S, l->col_off, p->grp_ptr, d_row, d_B));
+  BA_CHECK(BA_LAUNCH(k_border_reduce, dim3(mz, mz + 1), SB_T, 0, st, npad, mz, lambda, p->grp_ptr, d_row, d_B, d_rhs, d_small));
+  BA_CHECK(BA_LAUNCH(k_border_mask_vec, grid_for(npad, SB_T), SB_T, 0, st, npad, mz, d_col, d_B, d_rhs));
+  return BA_LAUNCH(k_border_mask_S, (unsigned)l->n_own_tiles, SB_T, 0, st, npad, d_col, l->S, l->own_tiles);
 }
 
 int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, const double *d_B, const double *d_Y, double *d_a,
@@ -273,10 +263,8 @@ int launch_border_finish(ba_problem *p, const DenseLDL *l, const int *d_col, con
   const int mz = 3 * p->grp_n;
   const int64_t npad = l->n;
   double *Tt = d_small + (MZ_MAX + 1) * MZ_MAX;
-  hipLaunchKernelGGL(k_border_T, dim3(mz, mz + 1), dim3(SB_T), 0, st, npad, mz, d_B, d_Y, d_a, d_small, Tt);
-  hipLaunchKernelGGL(k_border_finish, dim3(row_blocks(npad)), dim3(SB_T), 0, st, npad, mz, Tt, d_Y, d_col, d_a, l->flag);
-  BA_HIP_CHECK(hipGetLastError());
-  return BA_OK;
+  BA_CHECK(BA_LAUNCH(k_border_T, dim3(mz, mz + 1), SB_T, 0, st, npad, mz, d_B, d_Y, d_a, d_small, Tt));
+  return BA_LAUNCH(k_border_finish, grid_for(npad, SB_T), SB_T, 0, st, npad, mz, Tt, d_Y, d_col, d_a, l->flag);
 }
 
 // the handle's grouping to the device, once per change (camera order: the vectors of the controller and of :PCG)

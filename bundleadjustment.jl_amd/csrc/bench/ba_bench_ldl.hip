@@ -376,7 +376,8 @@ extern "C" int ba_debug_update_bench(int nt, int variant, int reps, double *ms_o
       case 8321: hipLaunchKernelGGL((k_ldl_update_probe<double, 1, 8321>), dim3(grid), dim3(256), 0, 0, S, co, V0, V1, 0, 2, nt, nblk, (int *)nullptr); break;
       case 129: hipLaunchKernelGGL((k_ldl_update_probe<double, 1, 129>), dim3(grid), dim3(256), 0, 0, S, co, V0, V1, 0, 2, nt, nblk, (int *)nullptr); break;
       case 9: hipLaunchKernelGGL((k_ldl_update_probe<double, 1, 9>), dim3(grid), dim3(256), GEMM_LDS_ELEMS * sizeof(double), 0, S, co, V0, V1, 0, 2, nt, nblk, (int *)nullptr); break;
-      default: hipLaunchKernelGGL((k_ldl_update<double, 1>), dim3(grid), dim3(256), GEMM_PRIV_LDS_ELEMS * sizeof(double), 0, S, co, V0, V1, 0, 2, nt, nblk, (int *)nullptr);
+      default: hipLaunchKernelGGL((k_ldl_update<double, 1>), dim3(grid), dim3(256), GEMM_PRIV_LDS_ELEMS * sizeof(double), 0, S, co, V0, V1, 0, 2, nt, nblk, nullptr,
+                                  nullptr, nullptr, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, TSB, nullptr);
     }
   };
   {
@@ -455,7 +456,7 @@ extern "C" int ba_debug_update_seq(int nt, int n, const int *m_list, const int *
     const int m = m_list[q], nblk = m * (m + 1) / 2, grid = ((nblk + 7) / 8) * 8;
     BA_HIP_CHECK(hipEventRecord(ev[(size_t)2 * q], 0));
     hipLaunchKernelGGL((k_ldl_update<double, 1>), dim3(grid), dim3(256), GEMM_PRIV_LDS_ELEMS * sizeof(double), 0, S, co, V0, V1, 0,
-                       nt - m, nt, nblk, (int *)nullptr);
+                       nt - m, nt, nblk, nullptr, nullptr, nullptr, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, TSB, nullptr);
     BA_HIP_CHECK(hipEventRecord(ev[(size_t)2 * q + 1], 0));
   }
   BA_HIP_CHECK(hipDeviceSynchronize());
@@ -494,7 +495,7 @@ extern "C" int ba_debug_diag_stamps(double *cycles6, double *ms_out) {
   for (int rep = 0; rep < 3; rep++) {
     BA_HIP_CHECK(hipMemcpy(S, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     BA_HIP_CHECK(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_ldl_diag<double>, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(double), 0, S, Li, D, flag, rep == 2 ? st : nullptr, (const int *)nullptr);
+    hipLaunchKernelGGL(k_ldl_diag<double>, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(double), 0, S, Li, D, flag, rep == 2 ? st : nullptr, (const int *)nullptr, 0);
     BA_HIP_CHECK(hipEventRecord(e1, 0));
     BA_HIP_CHECK(hipEventSynchronize(e1));
     if (rep == 1) BA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -756,7 +757,7 @@ extern "C" int ba_debug_diag_busy(int n, int fill_blocks, int fill_iters, double
     BA_HIP_CHECK(hipEventRecord(ev[0], sa));
     for (int q = 0; q < n; q++) {  // (the kernel only reads S: every launch factors the same tile)
       hipLaunchKernelGGL(k_ldl_diag<double>, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_ELEMS * sizeof(double), sa, S, Li, D, flag,
-                         (unsigned long long *)nullptr, (const int *)nullptr);
+                         (unsigned long long *)nullptr, (const int *)nullptr, 0);
       BA_HIP_CHECK(hipEventRecord(ev[(size_t)q + 1], sa));
     }
     BA_HIP_CHECK(hipDeviceSynchronize());

@@ -368,3 +368,26 @@ def test_device_resources_are_created_and_released_by_their_owners_only():
     assert {"hipMalloc", "hipHostMalloc", "hipEventCreateWithFlags", "hipStreamCreateWithFlags", "hipFree", "hipHostFree",
             "hipEventDestroy", "hipStreamDestroy", "hipGraphExecDestroy", "hipGraphDestroy"} <= inside  # (the section is where the pattern finds it)
     assert not outside, f"device resources created or released outside the owner types of ba_internal.h: {outside}"
+
+
+def test_kernels_are_launched_through_the_one_checked_helper_only():
+    """Every kernel of the library is launched by ba_launch (ba_launch.h, reached through BA_LAUNCH), which skips an empty
+    grid and checks the launch: in the product sources (csrc/, the micro-benchmarks of csrc/bench/ aside) a launch call or
+    the <<< token appears in that header and nowhere else, and hipGetLastError there and once more -- the deliberate clear
+    after a failed recording, inside replay() of ba_lm.hip."""
+    csrc = os.path.join(ROOT, "bundleadjustment.jl_amd", "csrc")
+    launches = re.compile(r"\b(?:hipLaunchKernelGGL|hipLaunchKernel|hipModuleLaunchKernel)\b|<<<")
+    last_error = re.compile(r"\bhipGetLastError\b")
+    comments = re.compile(r"//[^\n]*|/\*.*?\*/", re.S)
+    src = {f: comments.sub("", open(os.path.join(csrc, f)).read())
+           for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".cpp", ".h"))}
+    assert len(src) >= 15 and "ba_launch.h" in src and "ba_lm.hip" in src
+    helper = src.pop("ba_launch.h")
+    assert launches.search(helper) and last_error.search(helper)  # (the patterns find the one launch and its check)
+    raw = [(f, m.group(0)) for f, s in src.items() for m in launches.finditer(s)]
+    assert not raw, f"kernels launched outside ba_launch.h: {raw}"
+    checks = [f for f, s in src.items() for _ in last_error.finditer(s)]
+    assert checks == ["ba_lm.hip"], f"hipGetLastError outside ba_launch.h: {checks} (one is expected, in replay() of ba_lm.hip)"
+    lm = src["ba_lm.hip"]
+    begin = lm.index("static int replay(")
+    assert last_error.search(lm[begin:lm.index("\n}\n", begin)]), "the one hipGetLastError of ba_lm.hip is not inside replay()"
