@@ -208,6 +208,9 @@ def test_dense_ldl_f32(ba, n, gpu_ok):
 
 
 def test_dense_ldl_indefinite_and_zero_pivot(ba, gpu_ok):
+    """Negative pivots on two tiles, a zero pivot at the first position of a 4 x 4 matrix.  Negative pivots in every tile of every
+    schedule and zero pivots in every block, tile, zone and precision are in tests/test_dense_ldl_exact.py, on systems whose
+    answer is known exactly."""
     # LDL' without pivoting accepts negative pivots (quasi-definite input), like src/ldl_aux.jl
     rng = np.random.default_rng(5)
     n = 150
