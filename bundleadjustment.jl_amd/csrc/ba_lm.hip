@@ -11,6 +11,8 @@
 //
 // One device->host copy of a handful of scalars per iteration drives the accept/reject logic, as the reference's
 // norm() calls do.  As in the reference, a rejected step only changes the damping: J, Hpp, Hcc, gp, gc are reused.
+// That logic -- defaults, accept tests, damping updates, stopping tests, log row, status -- is LMController
+// (ba_lm_controller.h, host only); lm_solve_impl here is the device loop that feeds it.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -18,6 +20,7 @@
 #include <cstring>
 
 #include "ba_internal.h"
+#include "ba_lm_controller.h"  // LMController: the scalar decisions of ba_lm_solve (host only)
 #include "ba_lm_internal.h"
 
 namespace {
@@ -1597,29 +1600,6 @@ extern "C" int ba_covariance(ba_problem *p, const double *x, double lambda, doub
   return BA_OK;
 }
 
-// A scalar with the width Julia's promotion rules give it: an operation rounds to Float32 exactly when both operands are
-// Float32 (Base promotion: Float32 op Float64 -> Float64).  Used by ba_lm_solve for Float32 models.
-namespace ts {
-struct TS {
-  double v;
-  int w;  // 32 | 64
-};
-static inline TS f32(double x) { return TS{(double)(float)x, 32}; }
-static inline TS f64(double x) { return TS{x, 64}; }
-static inline bool both32(TS a, TS b) { return a.w == 32 && b.w == 32; }
-static inline TS add(TS a, TS b) { return both32(a, b) ? f32((float)a.v + (float)b.v) : f64(a.v + b.v); }
-static inline TS sub(TS a, TS b) { return both32(a, b) ? f32((float)a.v - (float)b.v) : f64(a.v - b.v); }
-static inline TS mul(TS a, TS b) { return both32(a, b) ? f32((float)a.v * (float)b.v) : f64(a.v * b.v); }
-static inline TS div(TS a, TS b) { return both32(a, b) ? f32((float)a.v / (float)b.v) : f64(a.v / b.v); }
-static inline TS max(TS a, TS b) { return TS{a.v > b.v ? a.v : b.v, both32(a, b) ? 32 : 64}; }
-static inline TS sqrt(TS a) { return a.w == 32 ? f32(std::sqrt((float)a.v)) : f64(std::sqrt(a.v)); }
-// x^n with a variable Int n (lm.jl:308,331).  The reference ran on Julia 1.3 / 1.4 (.travis.yml:6-9), whose
-// ^(x::Float64, y::Integer) and ^(x::Float32, y::Integer) are llvm.pow of the exponent CONVERTED to the base's type
-// (base/math.jl there; power_by_squaring is the generic fallback for other number types and only became the float path in
-// Julia 1.8's pow_body): pow() / powf() of the rounded exponent is that operation.
-static inline TS powi(TS a, int n) { return a.w == 32 ? f32(std::pow((float)a.v, (float)n)) : f64(std::pow(a.v, (double)n)); }
-}  // namespace ts
-
 // the option combinations ba_lm_solve refuses: the options among themselves, then the terms on the handle (check_terms)
 static int check_solve_opts(const ba_problem *p, const ba_lm_opts *o) {
   if (o->variant != 0 && o->variant != 1) {
@@ -1684,8 +1664,7 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   LMWork *w = p->lm;
   hipStream_t st = p->stream;
   const int V = o->variant;
-  // defaults: src/lm.jl:20-26 / src/LevenbergMarquardt.jl:21-26
-  const bool xf32 = o->x_f32 != 0;  // eltype(x) = Float32: eps(T)-derived defaults, Float32 iterates and evaluations
+  const bool xf32 = o->x_f32 != 0;  // eltype(x) = Float32: Float32 iterates and evaluations
   StepMode mode;
   mode.normalize = o->normalize;
   mode.xf32 = xf32;
@@ -1700,38 +1679,6 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   w->n_cg = 0;
   if (!mode.pcg) BA_CHECK(ensure_dense(p, w));  // (here, not in linear_step: no allocation while a graph is being recorded)
   if (!mode.pcg) BA_CHECK(ensure_shared_direct(p, w));
-  // Scalars carry the width Julia's promotion rules give them (TS: value + 32 | 64).  For a Float64 model everything is
-  // a Float64 and the arithmetic below is plain double arithmetic.  For eltype(x) = Float32 (src/lm.jl:20-26,36-59):
-  // norm() of a Float32 vector, obj = norm_r^2 / 2, pred, ared, rho are Float32; the eps(Float32)-derived default
-  // tolerances and nu_d, nu_m, delta_d, lambda are Float32 VALUES whose expressions run in Float32, while a value the
-  // caller passes is a Float64 (the reference's own Float32 experiment passes Float64 literals, src/diffprecsions.jl:22) and
-  // promotes its expression; lambda = T(max(lambda, 1e10 / norm_Jtr)) (lm.jl:59) stays a Float32 until the first accepted
-  // step, whose `max(1.0e-8, lambda)` (lm.jl:337, a Float64 literal) makes it a Float64 for the rest of the run; in
-  // LevenbergMarquardt.jl only Float32 operations touch it.  The accept tests multiply by Float64 literals (lm.jl:259,335).
-  using ts::TS;
-  const int W = xf32 ? 32 : 64;
-  auto T_ = [&](double v) { return xf32 ? ts::f32(v) : ts::f64(v); };  // a value of type eltype(x)
-  const TS eps = T_(xf32 ? 1.1920928955078125e-07 : 2.220446049250313e-16), sq = ts::sqrt(eps);
-  const TS cbr = T_(std::pow(eps.v, 1.0 / 3.0));  // eltype(x)(eps^(1/3)): a Float64 power, converted
-  const TS c100 = ts::mul(T_(100), sq), c1000 = ts::mul(T_(1000), sq);
-  auto opt = [&](double given, TS dflt, bool positive) { return (positive ? given > 0 : given >= 0) ? ts::f64(given) : dflt; };
-  const TS restol = opt(o->restol, V ? cbr : c100, false), satol = opt(o->satol, sq, false), srtol = opt(o->srtol, sq, false);
-  const TS oatol = opt(o->oatol, sq, false), ortol = opt(o->ortol, V ? cbr : c1000, false);
-  const TS atol = opt(o->atol, V ? sq : c100, false), rtol = opt(o->rtol, V ? cbr : c1000, false);
-  const TS nu_d = opt(o->nu_d, T_(3), true), nu_m = opt(o->nu_m, T_(3), true), delta_d = opt(o->delta_d, T_(2), true);
-  TS lambda = opt(o->lambda, T_(V ? 30 : 0.1), true);
-  const int ite_max = o->ite_max >= 0 ? o->ite_max : (V ? 200 : 100);
-  const bool linesearch = V && o->linesearch;
-  const bool facto_qr = o->facto >= 1;  // same device solve; the branches differ in the line search's model value only
-                                        // (:PCG has no dr vector to recur on either: it re-evaluates like :QR)
-  // norm(v) from the device's sum of squares; 1/2 |v|^2 the way the reference forms it (norm(v)^2 / 2: for a Float32
-  // vector the norm is rounded to Float32 first; for Float64 the sum of squares is halved directly, as before)
-  auto norm_of = [&](double sumsq, int wd) { return wd == 32 ? ts::f32(std::sqrt(sumsq)) : ts::f64(std::sqrt(sumsq)); };
-  auto half_of = [&](double sumsq) {
-    if (!xf32) return ts::f64(0.5 * sumsq);
-    const TS n = ts::f32(std::sqrt(sumsq));
-    return ts::div(ts::mul(n, n), ts::f32(2));
-  };
 
   memset(stats, 0, sizeof *stats);
   stats->status = BA_ST_UNKNOWN;
@@ -1746,15 +1693,22 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
   BA_CHECK(fetch_scalars(p, w, st));
   stats->n_residual++;
   stats->n_jacobian++;
-  // robust loss (ba_lm_set_loss; Float64 models only): SH_RSQ / SH_RSQ_TRIAL hold 2 f, so obj = f and norm_r = sqrt(2 f) enter
-  // the stopping tests as they are; pred = 1/2 |r~|^2 - 1/2 |J~ delta + r~|^2 and the model value dr2 = f - pred
-  const bool robust = p->loss != BA_LOSS_LINEAR;
-  TS norm_r = norm_of(h_sh[SH_RSQ], W);
-  TS obj = robust ? half_of(h_sh[SH_RSQ]) : ts::div(ts::mul(norm_r, norm_r), T_(2));
-  TS norm_Jtr = norm_of(h_sh[SH_GP] + h_rp[RP_GC], W);
-  TS norm_x = norm_of(h_sh[SH_X_P] + h_rp[RP_X_C], W);
-  // every parameter fixed (ba_lm_set_fixed): nothing to solve for -- return at x with status :first_order, iter 0, before the
-  // controller divides 0 by 0.  The cameras' mask is the same on every rank; the points are counted over the ranks.
+  // the scalar side of the solve: every decision below is the controller's (ba_lm_controller.h), from the sums the device
+  // publishes; this loop submits the work and hands them over
+  LMController c(*o, p->loss != BA_LOSS_LINEAR, w->cr0());
+  auto sums = [&] {
+    return LMSums{h_sh[SH_RSQ], h_sh[SH_RTSQ], h_sh[SH_GP] + h_rp[RP_GC], h_sh[SH_X_P] + h_rp[RP_X_C], h_sh[SH_MODEL], h_sh[SH_RSQ_TRIAL],
+                  h_sh[SH_DELTA_P] + h_rp[RP_DELTA_C]};
+  };
+  auto emit = [&] {  // one log row, the reference's columns: to the caller's callback and, verbose, to stderr
+    const LMRow r = c.row();
+    if (cb) cb(cb_ctx, r.iter, r.f, r.df, r.norm_jtr, r.lambda, r.norm_delta, r.rho, r.accepted);
+    if (o->verbose)
+      fprintf(stderr, "%6d %14.7e %10.2e %10.2e %10.2e %10.2e %10.2e %s\n", r.iter, r.f, r.df, r.norm_jtr, r.lambda, r.norm_delta, r.rho,
+              V ? (r.accepted ? "acc" : "rej") : (r.accepted ? "true" : "false"));
+  };
+  // every parameter fixed (ba_lm_set_fixed): nothing to solve for.  The cameras' mask is the same on every rank; the points are
+  // counted over the ranks.
   bool all_fixed = false;
   if (p->fix_ncam == 9 * p->ncams) {
     double free_pts = (double)(p->npnts - p->fix_npnt);
@@ -1766,145 +1720,61 @@ static int lm_solve_impl(ba_problem *p, const ba_lm_opts *o, double *x_inout, bo
     }
     all_fixed = free_pts == 0;
   }
-  if (all_fixed) norm_Jtr = T_(0);
-  if (V && !all_fixed) {  // lm.jl:59: lambda = T(max(lambda, 1e10 / norm_Jtr))
-    lambda = ts::max(lambda, ts::div(ts::f64(1e10), norm_Jtr));
-    lambda = T_(lambda.v);
-  }
-
-  TS norm_delta = T_(0), dr2 = T_(0), ared = T_(0), pred = T_(0);
-  const TS eps_first = ts::add(atol, ts::mul(rtol, norm_Jtr));  // lm.jl:107
-  TS old_obj = obj;
-  bool small_step = false, first_order = all_fixed || norm_Jtr.v < eps_first.v, small_residual = norm_r.v < restol.v;
-  bool small_obj_change = false, fail2 = false;
-  int iter = 0;
-  bool tired = iter > ite_max;
-  bool accepted = false, have_trial = false;
+  c.start(sums(), all_fixed);
+  bool have_trial = false;
   int rc = BA_OK;
   const double t_loop = wall();
 
-  while (!(small_step || first_order || small_residual || small_obj_change || tired || fail2)) {
-    if (V) iter++;                                                                           // lm.jl:127
-    if (!V && cb) cb(cb_ctx, iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v, lambda.v, norm_delta.v, dr2.v, accepted);  // LevenbergMarquardt.jl:143-147
+  while (!c.done()) {
+    c.begin_iteration();
+    if (!V) emit();                      // LevenbergMarquardt.jl:143-147
     if (have_trial) have_trial = false;  // submitted with the refresh of the step accepted last (accept_refresh_and_trial)
-    else if ((rc = trial_step(p, w, lambda.v, st)) != BA_OK) break;  // lm.jl:154-254
+    else if ((rc = trial_step(p, w, c.lambda(), st)) != BA_OK) break;  // lm.jl:154-254
     stats->n_factor++;
     stats->n_residual++;
     if ((rc = pivot_flag_error(*w->h_flag)) != BA_OK) break;
-    dr2 = half_of(h_sh[SH_MODEL]);  // 1/2 |delta_r|^2   (lm.jl:229)
-    const TS pred_r = ts::f64(0.5 * h_sh[SH_RTSQ] - 0.5 * h_sh[SH_MODEL]);  // (robust loss only)
-    if (robust) dr2 = ts::sub(obj, pred_r);
-    TS obj_suiv = half_of(h_sh[SH_RSQ_TRIAL]);
-    TS norm_rsuiv = norm_of(h_sh[SH_RSQ_TRIAL], W);
-    if (!V) iter++;  // LevenbergMarquardt.jl:240
-    // the reference's delta is a Vector{Float32} for a Float32 model -- except under normalize = :A once lambda is a
-    // Float64 (delta /= sqrt(lambda), lm.jl:235-237) or behind a Float64 delta_d in the line search (lm.jl:266)
-    int delta_w = (xf32 && !(V && o->normalize == 2 && lambda.w == 64)) ? 32 : 64;
-
-    bool step_accepted;
-    int ntimes = 0;
-    if (V) {
-      pred = robust ? pred_r : ts::sub(obj, dr2);
-      ared = ts::sub(obj, obj_suiv);
-      step_accepted = ared.v >= 1e-4 * pred.v;  // lm.jl:257-259 (Float64 literal)
-      double c_r = w->cr0();  // delta_r = -(J delta + c_r r)   (1; 1/mu in the Float16 branch)
-      while (linesearch && !step_accepted && ntimes < 4) {  // lm.jl:264-295
-        // delta /= delta_d ; delta_r = (delta_r - r)/delta_d (lm.jl:277): with delta_r = -(J delta + c r) the update is
-        // c <- (c + 1)/delta_d, which stays 1 only for the default delta_d = 2 (the reference's comment at lm.jl:275-276
-        // assumes it; the code is followed, not the comment)
-        // The :QR branch recomputes |J delta + r|^2 instead (lm.jl:273): c stays 1 there.
-        if (!facto_qr) c_r = (c_r + 1.0) / delta_d.v;
-        if (delta_d.w == 64) delta_w = 64;
-        if ((rc = launch_scale_scalar(p, w->nvar, w->delta, 1.0 / delta_d.v, st)) != BA_OK) break;
-        if ((rc = step_scalars(p, w, st, c_r)) != BA_OK) break;
-        if ((rc = trial_point(p, w, false, false, st)) != BA_OK) break;
-        stats->n_residual++;
-        if ((rc = comm_allreduce(p, w->scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st)) != BA_OK) break;
-        if ((rc = fetch_scalars(p, w, st)) != BA_OK) break;
-        dr2 = half_of(h_sh[SH_MODEL]);
-        obj_suiv = half_of(h_sh[SH_RSQ_TRIAL]);
-        norm_rsuiv = norm_of(h_sh[SH_RSQ_TRIAL], W);
-        pred = ts::sub(obj, dr2);
-        ared = ts::sub(obj, obj_suiv);
-        step_accepted = ared.v >= 1e-4 * pred.v;
-        ntimes++;
-      }
-      if (rc != BA_OK) break;
-    } else {
-      step_accepted = ts::sub(obj_suiv, obj).v < 1e-4 * (robust ? -pred_r.v : ts::sub(dr2, obj).v);  // LevenbergMarquardt.jl:243
+    c.judge(sums());
+    while (c.wants_halving()) {  // lm.jl:264-295
+      const LMController::Halving h = c.halve();
+      if ((rc = launch_scale_scalar(p, w->nvar, w->delta, h.scale, st)) != BA_OK) break;
+      if ((rc = step_scalars(p, w, st, h.c_r)) != BA_OK) break;
+      if ((rc = trial_point(p, w, false, false, st)) != BA_OK) break;
+      stats->n_residual++;
+      if ((rc = comm_allreduce(p, w->scal + SH_TRIAL_FIRST, SH_TRIAL_COUNT, st)) != BA_OK) break;
+      if ((rc = fetch_scalars(p, w, st)) != BA_OK) break;
+      c.judge(sums());
     }
-    accepted = step_accepted;
-    const TS nd = norm_of(h_sh[SH_DELTA_P] + h_rp[RP_DELTA_C], delta_w);
+    if (rc != BA_OK) break;
+    if (!c.step_norm(sums())) continue;  // NaN step: the loop ends, status :exception (lm.jl:297-302)
+    if (V) emit();                       // lm.jl:304
 
-    if (V) {
-      norm_delta = nd;  // lm.jl:297-302
-      if (std::isnan(norm_delta.v)) {
-        fail2 = true;
-        continue;
-      }
-      const double rho = ts::div(ared, pred).v;
-      if (cb) cb(cb_ctx, iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v, lambda.v, norm_delta.v, rho,
-                 (step_accepted && dr2.v <= obj.v) ? 1 : 0);  // lm.jl:304
-      if (o->verbose)
-        fprintf(stderr, "%6d %14.7e %10.2e %10.2e %10.2e %10.2e %10.2e %s\n", iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v,
-                lambda.v, norm_delta.v, rho, (step_accepted && dr2.v <= obj.v) ? "acc" : "rej");
-    }
-
-    if (!step_accepted) {
+    if (!c.accepted()) {
       stats->n_rejected++;
-      if (V) lambda = ts::mul(ts::max(lambda, ts::div(norm_delta.w == 32 ? ts::f32(1) : ts::f64(1), norm_delta)), ts::powi(nu_m, ntimes + 1));  // lm.jl:308
-      else lambda = ts::mul(lambda, nu_m);                                                            // LevenbergMarquardt.jl:269
+      c.reject();
     } else {
       stats->n_accepted++;
-      if (V) {  // lm.jl:329-337
-        if (ntimes > 0) lambda = ts::div(lambda, ts::powi(nu_d, ntimes - 1));
-        else lambda = ts::div(lambda, nu_d);
-        if (ared.v >= 0.9 * pred.v) lambda = ts::div(lambda, nu_d);
-        lambda = ts::max(ts::f64(1.0e-8), lambda);  // the Float64 literal promotes lambda for the rest of the run
-      } else {
-        lambda = ts::div(lambda, nu_d);  // LevenbergMarquardt.jl:292
-      }
+      // (what of the stopping tests is known before the refresh decides whether the next trial step goes out with it)
+      const bool stop_known = c.accept();
       std::swap(w->x, w->x_trial);  // x .= x_suiv
       std::swap(w->r, w->r_trial);  // r .= r_suiv
       w->parity ^= 1;
-      old_obj = obj;
-      norm_r = norm_rsuiv;
-      obj = obj_suiv;
-      // (what of the stopping tests is known before the refresh decides whether the next trial step goes out with it)
-      const bool stop_known = norm_r.v < restol.v || ts::sub(old_obj, obj).v < ts::add(oatol, ts::mul(ortol, old_obj)).v || iter > ite_max;
       if (!stop_known && can_prefetch_trial(p, w)) {
-        if ((rc = accept_refresh_and_trial(w, lambda.v, st)) != BA_OK) break;
+        if ((rc = accept_refresh_and_trial(w, c.lambda(), st)) != BA_OK) break;
         have_trial = true;
       } else if ((rc = accept_refresh(p, w, st)) != BA_OK) break;  // J, J'r  (lm.jl:341,370)
       stats->n_jacobian++;
-      norm_Jtr = norm_of(h_sh[SH_GP] + h_rp[RP_GC], W);
-      norm_x = norm_of(h_sh[SH_X_P] + h_rp[RP_X_C], W);
-      if (!V) norm_delta = nd;  // LevenbergMarquardt.jl:352
-      small_step = norm_delta.v < ts::add(satol, ts::mul(srtol, norm_x)).v;  // lm.jl:375-379
-      first_order = norm_Jtr.v < eps_first.v;
-      small_residual = norm_r.v < restol.v;
-      small_obj_change = ts::sub(old_obj, obj).v < ts::add(oatol, ts::mul(ortol, old_obj)).v;
+      c.refreshed(sums());
     }
-    if (!V && o->verbose)
-      fprintf(stderr, "%6d %14.7e %10.2e %10.2e %10.2e %10.2e %10.2e %s\n", iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v,
-              lambda.v, nd.v, dr2.v, step_accepted ? "true" : "false");
-    tired = iter > ite_max;  // lm.jl:382
+    c.end_iteration();
   }
-  if (rc == BA_OK && !V && cb) cb(cb_ctx, iter, obj.v, ts::sub(old_obj, obj).v, norm_Jtr.v, lambda.v, norm_delta.v, dr2.v, accepted);
+  if (rc == BA_OK && !V) emit();  // LevenbergMarquardt.jl:368
   stats->loop_s = wall() - t_loop;
 
-  if (rc != BA_OK) {
-    stats->status = BA_ST_EXCEPTION;
-  } else if (small_step) stats->status = BA_ST_SMALL_STEP;  // lm.jl:391-405
-  else if (first_order) stats->status = BA_ST_FIRST_ORDER;
-  else if (small_residual) stats->status = BA_ST_SMALL_RESIDUAL;
-  else if (small_obj_change) stats->status = BA_ST_ACCEPTABLE;
-  else if (fail2) stats->status = BA_ST_EXCEPTION;
-  else if (tired) stats->status = BA_ST_MAX_ITER;
-  stats->iter = iter;
-  stats->objective = obj.v;
-  stats->dual_feas = norm_Jtr.v;
-  stats->lambda_final = lambda.v;
+  stats->status = rc != BA_OK ? BA_ST_EXCEPTION : c.status();
+  stats->iter = c.iter();
+  stats->objective = c.objective();
+  stats->dual_feas = c.dual_feas();
+  stats->lambda_final = c.lambda();
   stats->n_cg = (int)w->n_cg;
   {
     hipError_t e = hipMemcpyAsync(x_inout, w->x, (size_t)w->nvar * sizeof(double), x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
