@@ -45,6 +45,12 @@ class LMStats(C.Structure):
                 ("elapsed_s", C.c_double), ("loop_s", C.c_double)]
 
 
+class RansacOpts(C.Structure):
+    """ba_ransac_opts"""
+    _fields_ = [("threshold", C.c_double), ("hypotheses", C.c_int), ("sample", C.c_int), ("refits", C.c_int),
+                ("min_inliers", C.c_int), ("seed", C.c_uint64)]
+
+
 LOG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                      C.c_double, C.c_int)
 COMM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -66,6 +72,7 @@ SYMBOLS = [
     "ba_lm_set_obs_info", "ba_lm_get_obs_info",
     "ba_refine_points", "ba_refine_points_dev",
     "ba_refine_cameras", "ba_refine_cameras_dev", "ba_resect_cameras", "ba_resect_cameras_dev",
+    "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
 ]
 
 _lib = None
@@ -145,6 +152,9 @@ def lib():
     L.ba_refine_cameras_dev.argtypes = [vp, vp, C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp]
     L.ba_resect_cameras.argtypes = L.ba_refine_cameras.argtypes
     L.ba_resect_cameras_dev.argtypes = L.ba_refine_cameras_dev.argtypes
+    L.ba_ransac_cameras.argtypes = [vp, vp, C.POINTER(RansacOpts), C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp, vp, vp]
+    L.ba_ransac_cameras_dev.argtypes = L.ba_ransac_cameras.argtypes + [vp]
+    L.ba_ransac_sample.argtypes = [C.c_uint64, C.c_int, i64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -536,6 +546,63 @@ def get_obs_info(handle):
 # into it
 POINT_STATES = ("converged", "stalled", "max_iter", "fixed", "degenerate", "nonfinite")
 POINT_BEHIND = 0x80
+
+
+# the consensus stage of refine_cameras(resect=True, ransac=...) (ba_ransac_cameras): the options and their ranges
+RANSAC_KEYS = ("threshold", "hypotheses", "sample", "refits", "min_inliers", "seed")
+
+
+def ransac_opts(ransac):
+    """RansacOpts of the dict `ransac` -- threshold (pixels, required), hypotheses (None or <= 0: 128; at most 4096), sample
+    (None or <= 0: 6; 6..16), refits (None or < 0: 2; at most 8), min_inliers (None or <= 0: max(sample, 6); at least 6), seed
+    (0 .. 2^64 - 1, default 0) -- or ValueError, before any device call."""
+    if not isinstance(ransac, dict):
+        raise ValueError(f"ransac must be a dict with the keys {', '.join(RANSAC_KEYS)} (or None), got {ransac!r}")
+    unknown = [k for k in ransac if k not in RANSAC_KEYS]
+    if unknown:
+        raise ValueError(f"ransac: unknown key {unknown[0]!r} (keys: {', '.join(RANSAC_KEYS)})")
+    if "threshold" not in ransac:
+        raise ValueError("ransac: threshold (pixels) is required")
+    try:
+        tau = float(ransac["threshold"])
+    except (TypeError, ValueError):
+        raise ValueError(f"ransac: threshold must be a finite number > 0, got {ransac['threshold']!r}") from None
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError(f"ransac: threshold must be a finite number > 0, got {ransac['threshold']!r}")
+    ints = {}
+    for key, unset in (("hypotheses", 0), ("sample", 0), ("refits", -1), ("min_inliers", 0), ("seed", 0)):
+        v = ransac.get(key)
+        if v is None:
+            v = unset
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"ransac: {key} must be an integer (or None), got {v!r}")
+        ints[key] = int(v)
+    if ints["hypotheses"] > 4096:
+        raise ValueError(f"ransac: hypotheses must be <= 4096, got {ints['hypotheses']}")
+    if ints["sample"] > 0 and not 6 <= ints["sample"] <= 16:
+        raise ValueError(f"ransac: sample must lie in 6..16, got {ints['sample']}")
+    if ints["refits"] > 8:
+        raise ValueError(f"ransac: refits must be <= 8, got {ints['refits']}")
+    if 0 < ints["min_inliers"] < 6:
+        raise ValueError(f"ransac: min_inliers must be >= 6, got {ints['min_inliers']}")
+    if not 0 <= ints["seed"] < 1 << 64:
+        raise ValueError(f"ransac: seed must lie in 0 .. 2^64 - 1, got {ints['seed']}")
+    for key in ("hypotheses", "sample", "refits", "min_inliers"):
+        ints[key] = max(ints[key], -1)  # (any value below the range means "the default")
+    return RansacOpts(tau, ints["hypotheses"], ints["sample"], ints["refits"], ints["min_inliers"], ints["seed"])
+
+
+def ransac_sample(seed, hypothesis, degree, sample=6, used=None):
+    """The positions hypothesis `hypothesis` samples in an observation list of `degree` entries (ba_ransac_sample, host only):
+    an int64 array of `sample` positions in the order of their draws, or None when the hypothesis is void.  used: a boolean
+    array of length degree, or None (all used)."""
+    pos, n = np.zeros(16, dtype=np.int64), C.c_int(0)
+    u = None if used is None else np.ascontiguousarray(used, dtype=np.uint8)
+    if u is not None and u.shape != (int(degree),):
+        raise ValueError(f"used must have shape ({int(degree)},), got {u.shape}")
+    check(lib().ba_ransac_sample(int(seed), int(hypothesis), int(degree), None if u is None else ptr(u), int(sample), ptr(pos), C.byref(n)))
+    m = 6 if sample <= 0 else int(sample)
+    return pos[:m].copy() if n.value == m else None
 
 
 # the matrix of DESIGN §5h as Python sees it (the communicator and ba_covariance columns are the library's): per term the

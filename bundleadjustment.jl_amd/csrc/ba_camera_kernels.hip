@@ -18,7 +18,8 @@
 // evaluated once per trial.  No floating-point atomics; the eight counters of a call are integers, added once per workgroup.
 //
 // ba_resect_cameras launches k_resect_cameras before it: the start pose of every camera whose pose is free, in
-// closed form from its 2D-3D correspondences (further down).
+// closed form from its 2D-3D correspondences (further down).  ba_ransac_cameras puts the consensus kernels of
+// ba_ransac_kernels.hip in front of both and hands them its inlier set as information (ransac_launch, at the end).
 //
 // What this file has in common with ba_point_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
 // (argument check, prior lookups, counter read-back, the body of the host-pointer entries; BlockWork) in ba_internal.h / ba_api.hip.
@@ -31,7 +32,7 @@ namespace {
 
 #include "ba_model_dev.h"  // CPAD, cam_pre, project_pre, jac_block
 #include "ba_prior_dev.h"  // centre_of
-#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS
+#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS, RS_SWEEPS, nearest_rotation, rotation_vector
 
 constexpr int CM_BLK = 256, CM_WAVES = CM_BLK / 64;
 constexpr int CM_SUMS = 55;                     // [f | g (9) | H (45, packed lower row-major)]
@@ -348,7 +349,6 @@ __global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
 // eigenvector of M's smallest eigenvalue (cyclic Jacobi, M and the rotations in LDS) is gamma [R / s | R m + t].
 constexpr int RS_SUMS = 40;         // [S0 | Sx | Sy | Sq], each packed lower row-major (10)
 constexpr int RS_MIN_OBS = 6;       // 12 unknowns up to scale, two equations per observation
-constexpr int RS_SWEEPS = 30;       // cap of the Jacobi sweeps (12 x 12 and 3 x 3)
 
 struct RsShared {
   double red[CM_WAVES][RS_SUMS];
@@ -422,86 +422,6 @@ __device__ __forceinline__ int jacobi_eig(double *A, double *V, int n, int t) {
     if (!rotated) break;
   }
   return sweeps;
-}
-
-// The nearest proper rotation of the 3 x 3 matrix sh.W (row-major) -> sh.R, its singular values -> sh.sg: one-sided Jacobi
-// (rotations of column pairs until they are orthogonal: W V3 = U Sigma), then R = U diag(1, 1, det(U V3')) V3' with the sign on
-// the smallest singular value -- its column of U is taken as the cross product of the other two, which is that sign and
-// needs no division by a singular value that may be 0.  (one lane)
-__device__ __forceinline__ void nearest_rotation(RsShared &sh) {
-  for (int i = 0; i < 9; i++) sh.V3[i] = (i / 3 == i % 3) ? 1.0 : 0.0;
-#pragma nounroll
-  for (int sweep = 0; sweep < RS_SWEEPS; sweep++) {
-    int rotated = 0;
-#pragma nounroll
-    for (int p = 0; p < 2; p++)
-#pragma nounroll
-      for (int q = p + 1; q < 3; q++) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int i = 0; i < 3; i++) {
-          const double wp = sh.W[3 * i + p], wq = sh.W[3 * i + q];
-          al += wp * wp;
-          be += wq * wq;
-          ga += wp * wq;
-        }
-        if (!(fabs(ga) > 1e-16 * sqrt(al * be))) continue;
-        rotated = 1;
-        const double ze = (be - al) / (2.0 * ga);
-        const double tt = (ze >= 0.0 ? 1.0 : -1.0) / (fabs(ze) + sqrt(ze * ze + 1.0));
-        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-        for (int i = 0; i < 3; i++) {
-          const double wp = sh.W[3 * i + p], wq = sh.W[3 * i + q];
-          sh.W[3 * i + p] = cs * wp - sn * wq;
-          sh.W[3 * i + q] = sn * wp + cs * wq;
-          const double vp = sh.V3[3 * i + p], vq = sh.V3[3 * i + q];
-          sh.V3[3 * i + p] = cs * vp - sn * vq;
-          sh.V3[3 * i + q] = sn * vp + cs * vq;
-        }
-      }
-    if (!rotated) break;
-  }
-  int jm = 0;
-  for (int j = 0; j < 3; j++) {
-    sh.sg[j] = sqrt((sh.W[j] * sh.W[j] + sh.W[3 + j] * sh.W[3 + j]) + sh.W[6 + j] * sh.W[6 + j]);
-    if (sh.sg[j] < sh.sg[jm]) jm = j;
-  }
-  const int ja = (jm + 1) % 3, jb = (jm + 2) % 3;  // (ja, jb, jm) is a cyclic order: det U = +1 = det V3
-  for (int i = 0; i < 3; i++) {
-    sh.U[3 * i + ja] = sh.W[3 * i + ja] / sh.sg[ja];
-    sh.U[3 * i + jb] = sh.W[3 * i + jb] / sh.sg[jb];
-  }
-  for (int i = 0; i < 3; i++) {
-    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;
-    sh.U[3 * i + jm] = sh.U[3 * i1 + ja] * sh.U[3 * i2 + jb] - sh.U[3 * i2 + ja] * sh.U[3 * i1 + jb];
-  }
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++)
-      sh.R[3 * i + j] = (sh.U[3 * i] * sh.V3[3 * j] + sh.U[3 * i + 1] * sh.V3[3 * j + 1]) + sh.U[3 * i + 2] * sh.V3[3 * j + 2];
-}
-
-// The rotation vector of sh.R -> sh.r: theta = atan2(|w| / 2, (tr R - 1) / 2), w the skew part; the axis is w / |w|, and for
-// cos theta < 0 it comes from the diagonal of R + I (k_i^2 = (R_ii - cos) / (1 - cos) at the largest R_ii, the others from the
-// symmetric part, the sign from w); theta < 1e-12: (1e-12, 0, 0) -- the model has no theta -> 0 branch.  (one lane)
-__device__ __forceinline__ void rotation_vector(RsShared &sh) {
-  const double *R = sh.R;
-  const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
-  const double wn = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-  const double co = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-  const double th = atan2(0.5 * wn, co);
-  if (th < 1e-12) {
-    sh.r[0] = 1e-12, sh.r[1] = 0.0, sh.r[2] = 0.0;
-  } else if (co >= 0.0) {
-    sh.r[0] = th * (w0 / wn), sh.r[1] = th * (w1 / wn), sh.r[2] = th * (w2 / wn);
-  } else {
-    int im = 0;
-    if (R[4] > R[0]) im = 1;
-    if (R[8] > R[4 * im]) im = 2;
-    const double ki = sqrt((R[4 * im] - co) / (1.0 - co));
-    for (int j = 0; j < 3; j++) sh.r[j] = j == im ? ki : 0.5 * (R[3 * im + j] + R[3 * j + im]) / ((1.0 - co) * ki);
-    const double sgn = (sh.r[0] * w0 + sh.r[1] * w1) + sh.r[2] * w2 < 0.0 ? -1.0 : 1.0;
-    const double kn = sqrt((sh.r[0] * sh.r[0] + sh.r[1] * sh.r[1]) + sh.r[2] * sh.r[2]);
-    for (int j = 0; j < 3; j++) sh.r[j] = th * (sgn * sh.r[j] / kn);
-  }
 }
 
 // One camera per workgroup: the pose (r, t) of xc from the camera's observations with Lambda != 0, its intrinsics and the held
@@ -715,15 +635,10 @@ static int camera_check(const char *who, ba_problem *p, const double *x, int *ma
   });
 }
 
-// (resect: k_resect_cameras, then) k_refine_cameras on st; the counters stay on the device (p->cams.counts)
-static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
-                         double *d_cost, hipStream_t st) {
-  BA_CHECK(terms_upload(p));
-  BA_CHECK(camera_tables(p));
+// the arguments of k_resect_cameras / k_refine_cameras on d_x from the handle's terms (after terms_upload and camera_tables)
+static CamArgs camera_args(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                           double *d_cost) {
   CameraWork &w = p->cams;
-  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
-  if (p->ncams == 0) return BA_OK;
-  if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
   const PriorSet &cm = p->pri[PRI_CAM], &ct = p->pri[PRI_CTR];
   CamArgs a;
   a.cam_ptr = p->cam_ptr, a.cam_obs = p->cam_obs, a.pnt0 = p->pnt0;
@@ -736,6 +651,19 @@ static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, 
   a.resect = resect ? (uint8_t *)w.resect : nullptr;
   a.max_iter = max_iter, a.kind = p->loss;
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
+  return a;
+}
+
+// (resect: k_resect_cameras, then) k_refine_cameras on st; the counters stay on the device (p->cams.counts)
+static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                         double *d_cost, hipStream_t st) {
+  BA_CHECK(terms_upload(p));
+  BA_CHECK(camera_tables(p));
+  CameraWork &w = p->cams;
+  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
+  if (p->ncams == 0) return BA_OK;
+  if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
+  const CamArgs a = camera_args(p, d_x, resect, max_iter, xtol, lambda0, d_status, d_cost);
   if (resect) {  // the start poses, written into d_x on the same stream
     ProfScope ps(p, PC_RESECT_CAMERAS, st);
     BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a));
@@ -783,4 +711,137 @@ extern "C" int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout, int max_i
 extern "C" int ba_resect_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
                                  double *cost, int64_t *counts, int *iters_max) {
   return refine_cameras_host("ba_resect_cameras", p, x_inout, true, max_iter, xtol, lambda0, status, cost, counts, iters_max);
+}
+
+// ---- ba_ransac_cameras: a consensus stage in front of ba_resect_cameras ------------------------------------------
+// The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message
+static int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o) {
+  if (!in) {
+    ba_set_error("%s: null options", who);
+    return BA_ERR_ARG;
+  }
+  *o = *in;
+  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
+    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
+    return BA_ERR_ARG;
+  }
+  if (o->hypotheses <= 0) o->hypotheses = 128;
+  if (o->sample <= 0) o->sample = 6;
+  if (o->refits < 0) o->refits = 2;
+  if (o->hypotheses > 4096 || o->sample < 6 || o->sample > 16 || o->refits > 8) {
+    ba_set_error("%s: hypotheses must be <= 4096, sample in 6..16, refits <= 8, got %d, %d, %d", who, o->hypotheses, o->sample, o->refits);
+    return BA_ERR_ARG;
+  }
+  if (o->min_inliers <= 0) o->min_inliers = o->sample > 6 ? o->sample : 6;
+  if (o->min_inliers < 6) {
+    ba_set_error("%s: min_inliers must be >= 6 (<= 0: max(sample, 6)), got %d", who, o->min_inliers);
+    return BA_ERR_ARG;
+  }
+  return BA_OK;
+}
+
+// hypotheses -> select -> refits x (resect into the scratch cameras -> rescore) -> resect into d_x -> refine, on st without a host
+// synchronisation in between.  The set reaches k_resect_cameras and k_refine_cameras as information: the masked copy of the
+// factors (1 0 1 when the caller set none: the values the kernels use without an array), so both run unchanged.
+static int ransac_launch(ba_problem *p, double *d_x, const ba_ransac_opts &o, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+                         double *d_cost, hipStream_t st) {
+  BA_CHECK(terms_upload(p));
+  BA_CHECK(camera_tables(p));
+  CameraWork &w = p->cams;
+  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
+  if (p->ncams == 0) return BA_OK;
+  if (!w.resect) BA_CHECK(w.resect.alloc(p->ncams));
+  if (!w.rs_inlier) {
+    BA_CHECK(w.rs_inlier.alloc(p->nobs));
+    BA_CHECK(w.rs_info.alloc(3 * p->nobs));
+    BA_CHECK(w.rs_cams.alloc(9 * p->ncams));
+    BA_CHECK(w.rs_n.alloc(p->ncams));
+    BA_CHECK(w.rs_best.alloc(p->ncams));
+    BA_CHECK(w.rs_stopped.alloc(p->ncams));
+  }
+  if (w.hyp_cap < o.hypotheses) {
+    w.hyp_cap = 0;
+    BA_CHECK(w.hyp_pose.alloc(6 * p->ncams * o.hypotheses));
+    BA_CHECK(w.hyp_count.alloc(p->ncams * o.hypotheses));
+    w.hyp_cap = o.hypotheses;
+  }
+  const CamArgs a = camera_args(p, d_x, true, max_iter, xtol, lambda0, d_status, d_cost);
+  RansacArgs r;
+  r.cam_ptr = a.cam_ptr, r.cam_obs = a.cam_obs, r.pnt0 = a.pnt0, r.pt2d = a.pt2d, r.info = a.info, r.mask = a.mask;
+  r.x = a.x, r.xc = a.xc, r.hyp_pose = w.hyp_pose, r.hyp_count = w.hyp_count;
+  r.inlier = w.rs_inlier, r.stopped = w.rs_stopped, r.n_inliers = w.rs_n, r.best_hyp = w.rs_best;
+  r.hypotheses = o.hypotheses, r.sample = o.sample, r.min_inliers = o.min_inliers;
+  r.seed_mix = ransac_seed_mix(o.seed), r.tau2 = o.threshold * o.threshold;
+  {
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+    BA_CHECK(launch_ransac_hypotheses(r, p->ncams, st));
+    BA_CHECK(launch_ransac_select(r, p->ncams, st));
+  }
+  CamArgs fit = a;  // the fits on the set
+  fit.info = w.rs_info;
+  if (o.refits > 0) {  // their poses live in a scratch copy of the cameras (the intrinsics are read from it)
+    BA_HIP_CHECK(hipMemcpyAsync(w.rs_cams, a.xc, (size_t)(9 * p->ncams) * sizeof(double), hipMemcpyDeviceToDevice, st));
+    fit.xc = w.rs_cams;
+  }
+  for (int it = 0; it < o.refits; it++) {
+    {
+      ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+      BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
+    }
+    {
+      ProfScope ps(p, PC_RESECT_CAMERAS, st);
+      BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit));
+    }
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+    BA_CHECK(launch_ransac_rescore(r, p->ncams, w.rs_cams, w.resect, st));
+  }
+  fit.xc = a.xc;
+  {
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+    BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
+  }
+  {
+    ProfScope ps(p, PC_RESECT_CAMERAS, st);
+    BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit));
+  }
+  ProfScope ps(p, PC_REFINE_CAMERAS, st);
+  return BA_LAUNCH(k_refine_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit);
+}
+
+// the consensus results of the last ransac_launch -> the caller's arrays (each may be null), on st
+static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, hipMemcpyKind kind, hipStream_t st) {
+  const CameraWork &w = p->cams;
+  if (p->ncams == 0) return BA_OK;
+  if (inlier && p->nobs > 0) BA_HIP_CHECK(hipMemcpyAsync(inlier, w.rs_inlier, (size_t)p->nobs, kind, st));
+  if (n_inliers) BA_HIP_CHECK(hipMemcpyAsync(n_inliers, w.rs_n, (size_t)p->ncams * sizeof(int32_t), kind, st));
+  if (best_hyp) BA_HIP_CHECK(hipMemcpyAsync(best_hyp, w.rs_best, (size_t)p->ncams * sizeof(int32_t), kind, st));
+  return BA_OK;
+}
+
+extern "C" int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
+                                     double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
+                                     uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
+  const char *who = "ba_ransac_cameras_dev";
+  ba_ransac_opts o;
+  BA_CHECK(ransac_opts_check(who, opts, &o));
+  BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
+  BA_CHECK(ransac_launch(p, d_x_inout, o, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(ransac_results(p, d_inlier, d_n_inliers, d_best_hyp, hipMemcpyDeviceToDevice, st));
+  return block_counts(p->cams, counts, iters_max, st);
+}
+
+extern "C" int ba_ransac_cameras(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
+                                 uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers,
+                                 int32_t *best_hyp) {
+  const char *who = "ba_ransac_cameras";
+  ba_ransac_opts o;
+  BA_CHECK(ransac_opts_check(who, opts, &o));
+  BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
+  return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
+                          [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
+                            BA_CHECK(ransac_launch(p, dx, o, max_iter, xtol, lambda0, d_status, d_cost, st));
+                            return ransac_results(p, inlier, n_inliers, best_hyp, hipMemcpyDeviceToHost, st);
+                          });
 }

@@ -228,6 +228,7 @@ enum ProfClass {
   PC_REFINE_POINTS,  // points with the cameras held (ba_refine_points): k_cam_pre and k_refine_points
   PC_REFINE_CAMERAS,  // cameras with the points held (ba_refine_cameras): k_refine_cameras
   PC_RESECT_CAMERAS,  // linear resection before it (ba_resect_cameras): k_resect_cameras
+  PC_RANSAC_CAMERAS,  // consensus stage before that (ba_ransac_cameras): k_ransac_hypotheses, _select, _rescore, _mask_info
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -327,7 +328,7 @@ struct PriorSet {
 };
 enum { PRI_PNT = 0, PRI_CAM, PRI_CTR, PRI_KINDS };
 
-// ---- block refinement (ba_refine_points, ba_refine_cameras, ba_resect_cameras) ------------------------------------------------
+// ---- block refinement (ba_refine_points, ba_refine_cameras, ba_resect_cameras, ba_ransac_cameras) ------------------------------------------------
 // One side of x is held and every block of the other side -- a point, a camera -- is its own small Marquardt problem.  What a
 // call keeps whichever side it refines, and what the shared host code (block_* below) works on: the host entry's status /
 // cost staging and the eight device counters
@@ -352,14 +353,44 @@ struct PointWork : BlockWork {
 // cameras with the points held (ba_camera_kernels.hip): the per-camera lookups of the camera and of the centre priors (rebuilt
 // when ba_lm_set_priors changed them), the effective 9-bit mask of held components -- the mask of ba_lm_set_fixed with the bits
 // of (k1, k2, f) set for every member of a calibration group (rebuilt when ba_lm_set_fixed or ba_lm_set_shared_intrinsics
-// changed them) -- and the byte per camera that k_resect_cameras leaves for k_refine_cameras (ba_resect_cameras)
+// changed them) -- and the byte per camera that k_resect_cameras leaves for k_refine_cameras (ba_resect_cameras).
+// ba_ransac_cameras (allocated at its first call): per (camera, hypothesis) the pose and the inlier count, per observation the
+// inlier byte and the masked copy of the information factors, per camera the size of its set, the winning hypothesis and the
+// "stopped" byte of the refits, and the scratch copy of the cameras the refits resect into
 struct CameraWork : BlockWork {
   DevBuf<int> cam_pri_of, ctr_pri_of;
   DevBuf<uint16_t> mask;
   bool mask_on = false;
   int64_t pri_version = -1, fix_version = -1, grp_version = -1;
   DevBuf<uint8_t> resect;
+  DevBuf<double> hyp_pose, rs_info, rs_cams;
+  DevBuf<int> hyp_count, rs_n, rs_best;
+  DevBuf<uint8_t> rs_inlier, rs_stopped;
+  int64_t hyp_cap = 0;  // hypotheses per camera that hyp_pose and hyp_count hold
 };
+
+// what the consensus kernels of ba_ransac_cameras work on (ba_ransac_kernels.hip; launched from ba_camera_kernels.hip)
+struct RansacArgs {
+  const int *cam_ptr, *cam_obs, *pnt0;
+  const double *pt2d, *info;  // info: the caller's l00 l10 l11 per observation, or null
+  const uint16_t *mask;       // effective mask of held components per camera, or null
+  const double *x, *xc;       // the whole vector (the points are read from it) and its camera part (the intrinsics)
+  double *hyp_pose;           // 6 per (camera, hypothesis)
+  int *hyp_count;             // inliers per (camera, hypothesis), -1: void
+  uint8_t *inlier, *stopped;
+  int *n_inliers, *best_hyp;
+  int hypotheses, sample, min_inliers;
+  uint64_t seed_mix;          // mix(seed)
+  double tau2;
+};
+uint64_t ransac_seed_mix(uint64_t seed);  // mix(seed) of the header's sampling
+int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, hipStream_t st);
+int launch_ransac_select(const RansacArgs &a, int64_t ncams, hipStream_t st);
+// the whole list of every camera that has not stopped under the pose of `cams` (9 per camera); resect: the byte
+// k_resect_cameras left (2: no pose was found)
+int launch_ransac_rescore(const RansacArgs &a, int64_t ncams, const double *cams, const uint8_t *resect, hipStream_t st);
+// out (3 per observation) <- the caller's factors, or (1, 0, 1) when none is set, on the inliers; 0 elsewhere
+int launch_ransac_mask_info(const RansacArgs &a, int64_t nobs, double *out, hipStream_t st);
 
 struct ba_problem {
   int device = 0;

@@ -305,7 +305,7 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
     return x, _block_info(status, cost, counts, its)
 
 
-def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
+def refine_cameras(nlp, x, *, resect=False, ransac=None, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
                    fixed_camera_params=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
     """The cameras of x with its points held (ba_refine_cameras), the other half of refine_points: every camera is an independent
     problem in at most 9 unknowns -- the objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info`, `camera_priors`
@@ -314,6 +314,13 @@ def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None,
     correspondences instead of from x (ba_resect_cameras: the pose of x is then not read, NaN included; a camera with a held
     pose component starts from x as before; fewer than 6 observations or a degenerate configuration: `degenerate`, untouched):
     how new images are registered against a structure, and with refine_points(triangulate=True) how an x0 is built.
+    ransac=dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) with resect=True puts a consensus stage in front
+    (ba_ransac_cameras; _lib.ransac_opts for the ranges): `hypotheses` minimal samples of `sample` correspondences per camera are
+    resected and scored by their inliers (reprojection within `threshold` pixels, in front of the camera), the best one defines
+    the inlier set, up to `refits` linear refits on the set re-score it, and the resection and the refinement run on that set
+    only -- the result has the bits of resect=True with an obs_info that drops the outliers.  A camera whose best hypothesis has
+    fewer than `min_inliers` inliers is `degenerate`.  info then also holds `inliers` (bool, nobs), `n_inliers` and
+    `best_hypothesis` (per camera; -1: not attempted or no valid hypothesis).
     max_iter (None: 100; 0: evaluate only -- with resect=True the resected poses are returned), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
     D_j = sqrt(H_jj): the predicted motion in pixels), lam0 (None: 1e-4).  fixed_camera_params hold components (("k1", "k2",
     "f"): a pose-only refit); fixed_cameras are skipped; the members of the groups of shared_intrinsics keep their (k1, k2, f).
@@ -326,10 +333,20 @@ def refine_cameras(nlp, x, *, resect=False, max_iter=None, xtol=None, lam0=None,
                               shared_intrinsics=shared_intrinsics, obs_info=obs_info)
     if not isinstance(resect, (bool, np.bool_)):
         raise ValueError(f"resect must be True or False, got {resect!r}")
+    opts = None
+    if ransac is not None:
+        if not resect:
+            raise ValueError("ransac needs resect=True (the consensus stage stands in front of the linear resection)")
+        opts = _lib.ransac_opts(ransac)
     x, args = _block_args(nlp, x, max_iter, xtol, lam0)
     terms.apply(nlp)  # (x is not checked against the grouping: the members' intrinsics are held, whatever they are)
     status, cost = np.zeros(nlp.ncams, dtype=np.uint8), np.zeros((nlp.ncams, 2))
     counts, its = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64), C.c_int(0)
+    if opts is not None:
+        inlier, n_in, best = np.zeros(nlp.nobs, dtype=np.uint8), np.zeros(nlp.ncams, dtype=np.int32), np.zeros(nlp.ncams, dtype=np.int32)
+        _lib.check(_lib.lib().ba_ransac_cameras(nlp.handle, _lib.ptr(x), C.byref(opts), *args, _lib.ptr(status), _lib.ptr(cost),
+                                                _lib.ptr(counts), C.byref(its), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best)))
+        return x, dict(_block_info(status, cost, counts, its), inliers=inlier != 0, n_inliers=n_in, best_hypothesis=best)
     entry = _lib.lib().ba_resect_cameras if resect else _lib.lib().ba_refine_cameras
     _lib.check(entry(nlp.handle, _lib.ptr(x), *args, _lib.ptr(status), _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
     return x, _block_info(status, cost, counts, its)

@@ -165,6 +165,40 @@ def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius
                 ncams=int(ncams), npnts=int(npnts), nobs=int(nobs))
 
 
+def add_outliers(prob, n_per_camera=None, fraction=None, seed=0, r_min=100.0, r_max=500.0):
+    """Wrong matches for the consensus tests and benchmarks: (pt2d, is_outlier) -- a copy of prob's pt2d (nobs, 2) in which the
+    chosen detections are displaced by r_min..r_max pixels in a random direction, and the boolean mask of the chosen ones.
+    Give one of n_per_camera (an integer, or one per camera: that many detections of each camera, drawn without replacement
+    from its list) and fraction (that share of each camera's list, rounded down)."""
+    if (n_per_camera is None) == (fraction is None):
+        raise ValueError("add_outliers: give one of n_per_camera and fraction")
+    if not (0 <= r_min <= r_max and np.isfinite(r_max)):
+        raise ValueError(f"add_outliers: 0 <= r_min <= r_max < inf, got {r_min!r}, {r_max!r}")
+    ncams = int(prob["ncams"])
+    cam0 = np.asarray(prob["cam_idx1"]) - 1
+    deg = np.bincount(cam0, minlength=ncams)
+    if fraction is not None:
+        if not 0 <= fraction <= 1:
+            raise ValueError(f"add_outliers: fraction must lie in 0..1, got {fraction!r}")
+        count = np.floor(fraction * deg).astype(np.int64)
+    else:
+        count = np.broadcast_to(np.asarray(n_per_camera, dtype=np.int64), (ncams,))
+        if (count < 0).any() or (count > deg).any():
+            raise ValueError("add_outliers: n_per_camera must lie between 0 and the camera's degree")
+    rng = np.random.default_rng(seed)
+    order = np.argsort(cam0, kind="stable")
+    start = np.concatenate([[0], np.cumsum(deg)])
+    is_outlier = np.zeros(len(cam0), dtype=bool)
+    for c in range(ncams):
+        if count[c] > 0:
+            is_outlier[order[start[c]:start[c + 1]][rng.choice(deg[c], size=int(count[c]), replace=False)]] = True
+    pt2d = np.array(prob["pt2d"], dtype=np.float64, copy=True).reshape(-1, 2)
+    k = int(is_outlier.sum())
+    rad, ang = rng.uniform(r_min, r_max, k), rng.uniform(0.0, 2.0 * np.pi, k)
+    pt2d[is_outlier] += np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=1)
+    return pt2d, is_outlier
+
+
 def shuffle_cameras(prob, seed=0, sigma=None):
     """The same problem with its cameras renumbered at random: (problem, sigma) with camera c of `prob` called sigma[c]
     (0-based) in the result; observations stay in BAL order (by point, then by the NEW camera number).  A BAL file promises

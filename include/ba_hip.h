@@ -558,7 +558,8 @@ int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, i
  * A camera's result depends on its own data and the order of its observations only (no floating-point atomics); two calls give
  * the same bits; the next ba_lm_step / ba_lm_solve on the handle gives the same bits as without this call in between.  A handle
  * with a communicator is refused (BA_ERR_ARG).
- * Out of scope: RANSAC or other outlier rejection inside the linear solve (the robust loss acts in the refinement), unknown
+ * Out of scope: outlier rejection inside the linear solve (the robust loss acts in the refinement; the consensus stage in front
+ * of this entry is ba_ransac_cameras, below), unknown
  * intrinsics (a full 3 x 4 DLT with RQ), minimal P3P, Float32, several ranks, resection inside the LM loop. */
 int ba_resect_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
                       uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
@@ -566,6 +567,66 @@ int ba_resect_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_i
 int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int max_iter, double xtol, double lambda0,
                           uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
                           int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
+
+/* ---- outlier-robust camera resection: RANSAC before the linear pose (an extension) ------------------------------------------
+ * ba_resect_cameras with a consensus stage in front.  One wrong 2D-3D correspondence ruins the linear pose (every used
+ * observation enters the 12 x 12 normal matrix unweighted) and the robust loss only acts in the refinement that follows.  Here
+ * many minimal-sample hypotheses are solved and scored on the device, the best one per camera defines an inlier set, and the
+ * linear resection and the Marquardt refinement run on that set only.  The inlier mask comes back to the caller.
+ * Options (ba_ransac_opts): threshold tau in pixels, finite and > 0; hypotheses H (<= 0: 128; at most 4096); sample m (<= 0: 6;
+ * 6..16); refits (< 0: 2; at most 8); min_inliers (<= 0: max(m, 6); at least 6); seed.  Anything else is BA_ERR_ARG, as are
+ * NULL options.  A handle with a communicator is refused, as ba_resect_cameras refuses it.
+ * Which cameras: the rules of ba_resect_cameras.  A camera with all nine components held is BA_PT_FIXED; a camera with any pose
+ * component held is not attempted and starts from x.  For these: inlier = its used observations, n_inliers = their number,
+ * best_hyp = -1.  Every other camera is attempted; its pose in x is never read (NaN is fine).  "Used" means Lambda != 0 under
+ * ba_lm_set_obs_info; the information plays no other part in the consensus stage.
+ * Sampling (64-bit integer arithmetic only, identical on host and device): mix is splitmix64,
+ *   z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31
+ * (mix of 0 is 0xE220A8397B1DCDAF; mix of (that ^ 1) is 0x08B4FDA8C892B50E).  Hypothesis h of a camera of degree d has
+ * key = mix of (mix of seed ^ h); draw j = 0, 1, ... gives the position pos = ((mix of (key ^ j) >> 32) * d) >> 32 in the
+ * camera's observation list (caller's order).  A draw is skipped if its observation is not used or the position was already
+ * taken; the first m accepted positions, in the order of their draws, are the sample; fewer than m after 64 draws makes the
+ * hypothesis void.  The camera index does not enter: a camera's result depends on its own data, the order of its list and the
+ * options only.  ba_ransac_sample is this sampling alone, on the host (no device): `used` holds `degree` bytes or is NULL (all
+ * used), pos receives the n_taken <= m accepted positions (n_taken < m: void); sample <= 0: 6.
+ * Hypothesis: the pose of steps 1-7 of ba_resect_cameras applied to the m sampled observations in the order of their draws
+ * (the sums are taken about the first of them), intrinsics from x; a degenerate sample makes the hypothesis void.
+ * Inlier test: under a pose, observation o is an inlier iff it is used, P1.z < 0, and |project - pt2d|^2 <= tau^2 in raw pixels
+ * with the model's own projection.  A comparison with NaN fails.
+ * Selection: the score of a hypothesis is its inlier count over the camera's whole list; the best is the largest count, ties to
+ * the lowest h.  Without a valid hypothesis, or with a best count < min_inliers, the camera fails: its inlier bytes are 0,
+ * n_inliers = the best count (0 if none), best_hyp = that h or -1, state BA_PT_DEGENERATE, bit-unchanged, cost entries 0, no flag.
+ * Refits, up to `refits` times: the linear resection on the current set M; the whole list re-scored under that pose gives M';
+ * M' is adopted iff |M'| >= |M| and M' != M; otherwise (smaller, equal, or the refit was degenerate) M stays and the camera
+ * stops.  The poses of these rounds live in a scratch copy of the cameras, not in x.
+ * Finish: ba_resect_cameras with the observations outside the final set treated exactly as Lambda = 0 -- the linear resection on
+ * the set, then the Marquardt refinement of ba_refine_cameras on the set under the handle's loss, information, priors, mask and
+ * grouping; an outlier raises no BEHIND flag; max_iter == 0 returns the linear pose; states, costs, counts and iters_max as in
+ * that entry.  x, status and cost equal, bit for bit, those of ba_resect_cameras on the same handle whose information is the
+ * caller's with the outliers' entries set to 0 (the identity on the inliers when the caller set none).
+ * Outputs beyond those of ba_resect_cameras, each may be NULL: inlier (nobs bytes 0 / 1, caller's observation order), n_inliers
+ * (ncams: the size of the final set) and best_hyp (ncams).  In the _dev form they are device pointers and the call is enqueued
+ * on `stream`; it synchronises only to hand over counts / iters_max, as its sibling does.
+ * Two calls give the same bits (no floating-point atomics); the next ba_lm_step / ba_lm_solve on the handle gives the same bits
+ * as without the call.
+ * Out of scope: an adaptive hypothesis count, MSAC / LO-RANSAC scoring, minimal P3P samples, unknown intrinsics, Float32,
+ * several ranks. */
+typedef struct ba_ransac_opts {
+  double threshold;
+  int hypotheses, sample, refits, min_inliers;
+  uint64_t seed;
+} ba_ransac_opts;
+int ba_ransac_cameras(ba_problem *p, double *x_inout /* nvar, host */, const ba_ransac_opts *opts, int max_iter, double xtol,
+                      double lambda0, uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams or NULL */,
+                      int64_t *counts /* BA_PT_STATES + 1 or NULL */, int *iters_max /* or NULL */,
+                      uint8_t *inlier /* nobs or NULL */, int32_t *n_inliers /* ncams or NULL */, int32_t *best_hyp /* ncams or NULL */);
+int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, const ba_ransac_opts *opts /* host */, int max_iter,
+                          double xtol, double lambda0, uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
+                          int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */,
+                          uint8_t *d_inlier /* nobs or NULL */, int32_t *d_n_inliers /* ncams or NULL */,
+                          int32_t *d_best_hyp /* ncams or NULL */, void *stream);
+int ba_ransac_sample(uint64_t seed, int hypothesis, int64_t degree, const uint8_t *used /* degree, or NULL: all */, int sample,
+                     int64_t *pos /* sample */, int *n_taken);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

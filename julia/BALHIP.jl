@@ -184,3 +184,55 @@ function resect_cameras_dev!(nlp, d_x :: Ptr{Cvoid}; max_iter :: Integer = -1, x
                 Ptr{Cint}(C_NULL), stream))
   return nothing
 end
+
+# outlier-robust camera resection (an extension): include/ba_hip.h, ba_ransac_cameras.  resect_cameras! with a consensus stage in
+# front: `hypotheses` minimal samples of `sample` correspondences per camera are resected and scored by their inliers
+# (reprojection within `threshold` pixels, in front of the camera); the best one defines the inlier set, up to `refits` linear
+# refits re-score it, and the resection and the refinement run on that set only.  A value below its range means the default
+# (128, 6, 2, max(sample, 6)).  Returns what resect_cameras! returns, then the inlier mask (nobs, caller's observation order),
+# the size of every camera's set and its winning hypothesis (-1: not attempted or none valid).
+struct BaRansacOpts
+  threshold :: Cdouble
+  hypotheses :: Cint
+  sample :: Cint
+  refits :: Cint
+  min_inliers :: Cint
+  seed :: UInt64
+end
+
+function ransac_cameras!(nlp, x :: Vector{Float64}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                         refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                         xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  inlier = zeros(UInt8, nlp.nobs)
+  n_inliers = zeros(Int32, nlp.ncams)
+  best_hyp = zeros(Int32, nlp.ncams)
+  GC.@preserve x status cost counts inlier n_inliers best_hyp begin
+    bacheck(ccall((:ba_ransac_cameras, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, pointer(x), opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters, pointer(inlier), pointer(n_inliers), pointer(best_hyp)))
+  end
+  return status, cost, counts, Int(iters[]), inlier .!= 0, n_inliers, best_hyp
+end
+
+# the device-resident form: d_x and the outputs (each may be C_NULL) are device pointers (ba_dev_malloc); enqueued on `stream`
+# (C_NULL: the handle's) and not synchronised -- counts and iters_max are not fetched
+function ransac_cameras_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                             refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                             xtol :: Real = -1.0, lam0 :: Real = -1.0, d_status :: Ptr{Cvoid} = C_NULL, d_cost :: Ptr{Cvoid} = C_NULL,
+                             d_inlier :: Ptr{Cvoid} = C_NULL, d_n_inliers :: Ptr{Cvoid} = C_NULL, d_best_hyp :: Ptr{Cvoid} = C_NULL,
+                             stream :: Ptr{Cvoid} = C_NULL)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  bacheck(ccall((:ba_ransac_cameras_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                nlp.handle, d_x, opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
+  return nothing
+end

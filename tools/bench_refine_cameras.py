@@ -13,9 +13,15 @@ shapes, against the fixed-point LM solve on the same scene.
            k_refine_cameras), the states, the most trials, and the sum of the cameras' costs against that of the refinement from
            the generator's x0.  No LM leg: nothing else starts from NaN poses.
 
-One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (--resect: profiles/resect_cameras_bench.json),
-or the file given.
-usage: python tools/bench_refine_cameras.py [--resect] [out.json] [reps] [shape ...]"""
+  --ransac the same clocks around ba_ransac_cameras_dev (H = 128, m = 6, tau = 4 px, refits = 2) on the scene with 30 % of
+           every camera's detections displaced by synthetic.add_outliers, the true points held, from NaN poses: event times of
+           the consensus kernels (profile class k_ransac_cameras: hypotheses, select, rescore, mask), of the resections (the
+           refits and the final one) and of the refinement; the share of cameras whose mask equals the truth; and beside it the
+           --resect row of the outlier-free scene from the same session.
+
+One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (--resect: profiles/resect_cameras_bench.json,
+--ransac: profiles/ransac_cameras_bench.json), or the file given.
+usage: python tools/bench_refine_cameras.py [--resect | --ransac] [out.json] [reps] [shape ...]"""
 import ctypes as C
 import json
 import os
@@ -126,11 +132,67 @@ def measure_resect(ba, name, reps):
     return row
 
 
+RANSAC = dict(threshold=4.0, hypotheses=128, sample=6, refits=2, seed=0)
+OUTLIER_FRACTION = 0.3
+
+
+def measure_ransac(ba, name, reps):
+    L, lib = ba._lib.lib(), ba._lib
+    p = ba.synthetic.make_named(name)
+    n, nc, nvar, nobs = p["npnts"], p["ncams"], len(p["x0"]), p["nobs"]
+    pt2d, is_out = ba.synthetic.add_outliers(p, fraction=OUTLIER_FRACTION, seed=1)
+    q = dict(p, pt2d=np.ascontiguousarray(pt2d.ravel()))
+    m = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(q))
+    cam0 = p["cam_idx1"] - 1
+    deg = np.bincount(cam0, minlength=nc)
+    row = {"shape": name, "ncams": nc, "npnts": n, "nobs": nobs, "xtol": XTOL, "degree_min": int(deg.min()),
+           "degree_median": int(np.median(deg)), "degree_max": int(deg.max()), "outlier_fraction": OUTLIER_FRACTION,
+           "outliers": int(is_out.sum()), "options": RANSAC}
+    x0 = np.array(p["x_true"], dtype=np.float64, copy=True)  # the true points are held
+    x0[3 * n:].reshape(nc, 9)[:, :6] = np.nan
+    opts = lib.ransac_opts(RANSAC)
+    d_x = C.c_void_p()
+    lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
+    counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
+    tail = (None, None, None, None)
+
+    def call(cnt=None, it=None):
+        lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
+        t = time.perf_counter()
+        lib.check(L.ba_ransac_cameras_dev(m.handle, d_x, C.byref(opts), -1, XTOL, -1.0, None, None, cnt, it, *tail))
+        lib.check(L.ba_synchronize(m.handle))
+        return 1e3 * (time.perf_counter() - t)
+
+    call(lib.ptr(counts), C.byref(its))  # warm-up
+    wall = [call() for _ in range(reps)]
+    m.profile(True)
+    call()
+    prof = m.profile_get()
+    m.profile(False)
+    lib.check(L.ba_dev_free(m.handle, d_x))
+    med = statistics.median(wall)
+    x, info = ba.refine_cameras(m, x0, resect=True, ransac=RANSAC, xtol=XTOL)
+    same = np.bincount(cam0, weights=(info["inliers"] != ~is_out).astype(float), minlength=nc) == 0
+    C1, Ct = x[3 * n:].reshape(nc, 9), np.asarray(p["x_true"])[3 * n:].reshape(nc, 9)
+    row["ransac"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall],
+                     "k_ransac_cameras_event_ms": round(prof["k_ransac_cameras"][0], 3), "k_ransac_cameras_scopes": int(prof["k_ransac_cameras"][1]),
+                     "k_resect_cameras_event_ms": round(prof["k_resect_cameras"][0], 3), "k_resect_cameras_launches": int(prof["k_resect_cameras"][1]),
+                     "k_refine_cameras_event_ms": round(prof["k_refine_cameras"][0], 3), "iters_max": its.value,
+                     "counts": {k: int(v) for k, v in zip(lib.POINT_STATES + ("behind",), counts)},
+                     "cameras_with_the_true_mask": int(same.sum()), "share_with_the_true_mask": round(float(same.mean()), 4),
+                     "inliers_missed": int((~info["inliers"] & ~is_out).sum()), "outliers_kept": int((info["inliers"] & is_out).sum()),
+                     "pose_error_rel_max": float(np.max(np.linalg.norm((C1 - Ct)[:, :6], axis=1) / np.linalg.norm(Ct[:, :6], axis=1))),
+                     "objective": float(np.sum(info["cost_after"]))}
+    m.close()
+    row["resect_outlier_free"] = measure_resect(ba, name, reps)["resect"]
+    return row
+
+
 def main():
     args = sys.argv[1:]
-    resect = "--resect" in args
-    args = [a for a in args if a != "--resect"]
-    default = "resect_cameras_bench.json" if resect else "refine_cameras_bench.json"
+    resect, ransac = "--resect" in args, "--ransac" in args
+    args = [a for a in args if a not in ("--resect", "--ransac")]
+    default = "ransac_cameras_bench.json" if ransac else "resect_cameras_bench.json" if resect else "refine_cameras_bench.json"
     out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", default)
     reps = int(args.pop(0)) if args and args[0].isdigit() else 5
     shapes = args or ["dubrovnik-356", "venice-1778"]
@@ -139,7 +201,7 @@ def main():
         sys.exit("bench_refine_cameras: no HIP device visible (nothing is measured without one)")
     rows = []
     for name in shapes:
-        row = (measure_resect if resect else measure)(ba, name, reps)
+        row = (measure_ransac if ransac else measure_resect if resect else measure)(ba, name, reps)
         print(json.dumps(row), flush=True)
         rows.append(row)
     with open(out, "w") as fh:
