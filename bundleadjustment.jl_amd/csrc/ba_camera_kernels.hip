@@ -19,7 +19,7 @@
 //
 // ba_resect_cameras launches k_resect_cameras before it: the start pose of every camera whose pose is free, in
 // closed form from its 2D-3D correspondences (further down).  ba_ransac_cameras puts the consensus kernels of
-// ba_ransac_kernels.hip in front of both and hands them its inlier set as information (ransac_launch, at the end).
+// ba_ransac_kernels.hip in front of both and hands them its inlier set as information (ransac_consensus, on the host side).
 //
 // What this file has in common with ba_point_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
 // (argument check, prior lookups, counter read-back, the body of the host-pointer entries; BlockWork) in ba_internal.h / ba_api.hip.
@@ -32,12 +32,12 @@ namespace {
 
 #include "ba_model_dev.h"  // CPAD, cam_pre, project_pre, jac_block
 #include "ba_prior_dev.h"  // centre_of
-#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS, RS_SWEEPS, nearest_rotation, rotation_vector
+#include "ba_refine_dev.h"  // wave_all_sum, p1_z, the pieces of the linear resection
 
 constexpr int CM_BLK = 256, CM_WAVES = CM_BLK / 64;
 constexpr int CM_SUMS = 55;                     // [f | g (9) | H (45, packed lower row-major)]
 constexpr int CM_G = 1, CM_H = 10;              // where g and H start
-constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u, CM_POSE = 0x3Fu;
+constexpr unsigned CM_ALL = 0x1FFu, CM_INTRINSICS = 0x1C0u;  // (the pose components: POSE_MASK)
 enum { RS_DONE = 0, RS_SKIPPED = 1, RS_DEGENERATE = 2 };  // the byte per camera k_resect_cameras leaves for k_refine_cameras
 
 struct CamArgs {
@@ -342,21 +342,12 @@ __global__ __launch_bounds__(CM_BLK) void k_refine_cameras(CamArgs a) {
 }
 
 // ---- linear resection (ba_resect_cameras): the start pose of a camera from its 2D-3D correspondences ------------
-// With P = R X + t the BAL projection gives q = -P.xy / P.z for the undistorted measurement q: P.x + q_x P.z = 0 and
-// P.y + q_y P.z = 0, two homogeneous linear equations in the 12 entries of [R | t].  On Hartley-normalised points X~ = s (X - m),
-// h = (X~, 1), the 12 x 12 normal matrix is M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]] with the 4 x 4 moments S0 = sum h h',
-// Sx = sum q_x h h', Sy = sum q_y h h', Sq = sum |q|^2 h h': 40 sums per lane, reduced as observation_sums reduces its 55.  The
-// eigenvector of M's smallest eigenvalue (cyclic Jacobi, M and the rotations in LDS) is gamma [R / s | R m + t].
-constexpr int RS_SUMS = 40;         // [S0 | Sx | Sy | Sq], each packed lower row-major (10)
-constexpr int RS_MIN_OBS = 6;       // 12 unknowns up to scale, two equations per observation
-
+// The steps are those of ba_refine_dev.h; here the lanes of a workgroup stride over the camera's list, 40 sums per lane, reduced
+// as observation_sums reduces its 55.
 struct RsShared {
   double red[CM_WAVES][RS_SUMS];
-  int first[CM_WAVES];
-  double M[144], V[144];      // the normal matrix (its diagonal ends as the eigenvalues) and the accumulated rotations
-  double W[9], V3[9], sg[3];  // the 3 x 3 block A and its one-sided Jacobi SVD: W -> U Sigma, V3, the singular values
-  double U[9], R[9], a3[4], r[3];
-  int front, stop;
+  int first[CM_WAVES], front;
+  ResectScratch rs;
 };
 
 // The sums acc of all lanes -> every lane: xor butterfly per wave, LDS across the waves, ((w0 + w1) + w2) + w3
@@ -374,56 +365,6 @@ __device__ __forceinline__ void block_sums(double (&acc)[N], RsShared &sh, int t
   for (int i = 0; i < N; i++) acc[i] = ((sh.red[0][i] + sh.red[1][i]) + sh.red[2][i]) + sh.red[3][i];
 }
 
-__device__ __forceinline__ bool obs_used(const CamArgs &a, int o) {
-  if (!a.info) return true;
-  const double *l = a.info + 3 * (int64_t)o;
-  return !(l[0] == 0.0 && l[1] == 0.0 && l[2] == 0.0);
-}
-
-// Cyclic Jacobi on the symmetric n x n matrix A (row-major, both triangles kept), V <- the product of the rotations (the
-// columns end as eigenvectors, the diagonal of A as eigenvalues).  A rotation is skipped when |a_pq| <= 1e-18 sqrt(|a_pp a_qq|);
-// the sweeps end with the first sweep without a rotation or at RS_SWEEPS.  Called by the whole workgroup, A and V in LDS: every
-// lane reads the same three entries and takes the same decision, lane k < n updates element k of the two columns, then of the two
-// rows of A and of V, with a barrier between the phases.  Every element sees the operations of a one-lane loop over k.
-__device__ __forceinline__ int jacobi_eig(double *A, double *V, int n, int t) {
-  for (int i = t; i < n * n; i += CM_BLK) V[i] = (i / n == i % n) ? 1.0 : 0.0;
-  __syncthreads();
-  int sweeps = 0;
-#pragma nounroll
-  for (; sweeps < RS_SWEEPS; sweeps++) {
-    int rotated = 0;
-#pragma nounroll
-    for (int p = 0; p < n - 1; p++)
-#pragma nounroll
-      for (int q = p + 1; q < n; q++) {
-        const double apq = A[p * n + q], app = A[p * n + p], aqq = A[q * n + q];
-        if (!(fabs(apq) > 1e-18 * sqrt(fabs(app * aqq)))) continue;  // (uniform; also ends on a NaN)
-        rotated = 1;
-        const double th = (aqq - app) / (2.0 * apq);
-        const double tt = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-        __syncthreads();  // (every lane has read the three entries)
-        if (t < n) {  // A <- A G
-          const double akp = A[t * n + p], akq = A[t * n + q];
-          A[t * n + p] = cs * akp - sn * akq;
-          A[t * n + q] = sn * akp + cs * akq;
-        }
-        __syncthreads();
-        if (t < n) {  // A <- G' A with a_pq = a_qp = 0, V <- V G
-          const double apk = A[p * n + t], aqk = A[q * n + t];
-          A[p * n + t] = t == q ? 0.0 : cs * apk - sn * aqk;
-          A[q * n + t] = t == p ? 0.0 : sn * apk + cs * aqk;
-          const double vkp = V[t * n + p], vkq = V[t * n + q];
-          V[t * n + p] = cs * vkp - sn * vkq;
-          V[t * n + q] = sn * vkp + cs * vkq;
-        }
-        __syncthreads();
-      }
-    if (!rotated) break;
-  }
-  return sweeps;
-}
-
 // One camera per workgroup: the pose (r, t) of xc from the camera's observations with Lambda != 0, its intrinsics and the held
 // points; the pose of x is not read.  a.resect[c] <- RS_DONE (pose written), RS_SKIPPED (a pose component is held: nothing is
 // done) or RS_DEGENERATE (nothing written).  The control flow is uniform over the workgroup.
@@ -434,7 +375,7 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
   double *xc = a.xc + 9 * (int64_t)c;
   const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
-  if (fm & CM_POSE) {
+  if (fm & POSE_MASK) {
     if (t == 0) a.resect[c] = RS_SKIPPED;
     return;
   }
@@ -442,13 +383,14 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   // the provisional origin: the point of the first observation of the list with Lambda != 0
   int first = k1;
   for (int k = k0 + t; k < k1; k += CM_BLK)
-    if (obs_used(a, a.cam_obs[k])) {
+    if (obs_used(a.info, a.cam_obs[k])) {
       first = k;
       break;
     }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
   if ((t & 63) == 0) sh.first[t >> 6] = first;
+  if (t == 0) sh.front = 0;
   __syncthreads();
   first = min(min(sh.first[0], sh.first[1]), min(sh.first[2], sh.first[3]));
   if (first >= k1 || !isfinite(cf) || cf == 0.0) {
@@ -464,7 +406,7 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   double mo[5] = {0, 0, 0, 0, 0};
   for (int k = k0 + t; k < k1; k += CM_BLK) {
     const int o = a.cam_obs[k];
-    if (!obs_used(a, o)) continue;
+    if (!obs_used(a.info, o)) continue;
     const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
     const double d0 = xp[0] - org[0], d1 = xp[1] - org[1], d2 = xp[2] - org[2];
     mo[0] += 1.0;
@@ -473,127 +415,70 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   }
   block_sums<5>(mo, sh, t);
   const double n = mo[0];
-  const double dm[3] = {mo[1] / n, mo[2] / n, mo[3] / n};
-  const double var = mo[4] / n - ((dm[0] * dm[0] + dm[1] * dm[1]) + dm[2] * dm[2]);
-  if (n < (double)RS_MIN_OBS || !(var > 0.0) || !isfinite(var)) {
+  double dm[3], sc;
+  if (n < (double)RS_MIN_OBS || !hartley_stats(n, mo + 1, mo[4], dm, sc)) {
     if (t == 0) a.resect[c] = RS_DEGENERATE;
     return;
   }
-  const double sc = 1.0 / sqrt(var);
   // the moments
   double acc[RS_SUMS];
 #pragma unroll
   for (int i = 0; i < RS_SUMS; i++) acc[i] = 0.0;
   for (int k = k0 + t; k < k1; k += CM_BLK) {
     const int o = a.cam_obs[k];
-    if (!obs_used(a, o)) continue;
+    if (!obs_used(a.info, o)) continue;
     const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
-    const double h[4] = {sc * ((xp[0] - org[0]) - dm[0]), sc * ((xp[1] - org[1]) - dm[1]), sc * ((xp[2] - org[2]) - dm[2]), 1.0};
+    const double X[3] = {xp[0], xp[1], xp[2]};
     const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
-    const double ux = m.x / cf, uy = m.y / cf;
-    double qx = ux, qy = uy;
+    double h[4], qx, qy, term[RS_SUMS];
+    normalised_point(X, org, dm, sc, h);
+    undistort(m.x / cf, m.y / cf, ck1, ck2, qx, qy);
+    moment_terms(h, qx, qy, term);
 #pragma unroll
-    for (int it = 0; it < UNDIST_ITERS; it++) {
-      const double n2 = qx * qx + qy * qy;
-      const double den = 1.0 + ck1 * n2 + ck2 * (n2 * n2);
-      qx = ux / den;
-      qy = uy / den;
-    }
-    const double q2 = qx * qx + qy * qy;
-    int tt = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j <= i; j++, tt++) {
-        const double hh = h[i] * h[j];
-        acc[tt] += hh;
-        acc[10 + tt] += qx * hh;
-        acc[20 + tt] += qy * hh;
-        acc[30 + tt] += q2 * hh;
-      }
+    for (int i = 0; i < RS_SUMS; i++) acc[i] += term[i];
   }
   block_sums<RS_SUMS>(acc, sh, t);
   if (t == 0) {
     bool ok = true;
 #pragma unroll
-    for (int i = 0; i < RS_SUMS; i++) ok = ok && isfinite(acc[i]);
-    // M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]] from the packed sums, which go through sh.red's first row so that the loops
-    // index LDS (a lane of another wave may still be reading that row in block_sums: its copy of the sums is not used again)
-#pragma unroll
-    for (int i = 0; i < RS_SUMS; i++) sh.red[0][i] = acc[i];
-    for (int i = 0; i < 4; i++)
-      for (int j = 0; j < 4; j++) {
-        const int hi = i > j ? i : j, lo = i > j ? j : i, tt = hi * (hi + 1) / 2 + lo;
-        const double s0 = sh.red[0][tt], sx = sh.red[0][10 + tt], sy = sh.red[0][20 + tt], sq = sh.red[0][30 + tt];
-        sh.M[i * 12 + j] = s0, sh.M[i * 12 + 4 + j] = 0.0, sh.M[i * 12 + 8 + j] = sx;
-        sh.M[(4 + i) * 12 + j] = 0.0, sh.M[(4 + i) * 12 + 4 + j] = s0, sh.M[(4 + i) * 12 + 8 + j] = sy;
-        sh.M[(8 + i) * 12 + j] = sx, sh.M[(8 + i) * 12 + 4 + j] = sy, sh.M[(8 + i) * 12 + 8 + j] = sq;
-      }
-    sh.stop = ok ? 0 : 1;
+    for (int i = 0; i < RS_SUMS; i++) {
+      ok = ok && isfinite(acc[i]);
+      sh.rs.S[i] = acc[i];
+    }
+    sh.rs.ok = ok ? 1 : 0;
   }
   __syncthreads();
-  if (sh.stop) {
+  if (!sh.rs.ok) {
     if (t == 0) a.resect[c] = RS_DEGENERATE;
     return;
   }
-  jacobi_eig(sh.M, sh.V, 12, t);
-  if (t == 0) {
-    int i1 = 0;
-    double l1 = sh.M[0], lmax = sh.M[0];
-    for (int i = 1; i < 12; i++) {
-      const double l = sh.M[13 * i];
-      if (l < l1) l1 = l, i1 = i;
-      lmax = fmax(lmax, l);
-    }
-    double l2 = lmax;
-    for (int i = 0; i < 12; i++)
-      if (i != i1) l2 = fmin(l2, sh.M[13 * i]);
-    const bool ok = isfinite(l1) && isfinite(lmax) && l2 > 1e-10 * lmax;
-    if (ok) {
-      for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) sh.W[3 * i + j] = sh.V[(4 * i + j) * 12 + i1];
-        sh.r[i] = sh.V[(4 * i + 3) * 12 + i1];  // b, until the rotation vector takes its place
-      }
-      for (int j = 0; j < 4; j++) sh.a3[j] = sh.V[(8 + j) * 12 + i1];
-    }
-    sh.front = 0;
-    sh.stop = ok ? 0 : 1;
-  }
-  __syncthreads();
-  if (sh.stop) {
+  for (int e = t; e < 144; e += CM_BLK) sh.rs.M[e] = normal_matrix_entry(sh.rs.S, e);
+  jacobi12<__syncthreads>(sh.rs.M, sh.rs.V, t, CM_BLK);
+  int i1;
+  if (!smallest_eigenpair(sh.rs.M, i1)) {  // (every lane reads the same diagonal)
     if (t == 0) a.resect[c] = RS_DEGENERATE;
     return;
   }
-  {  // the used points in front of the camera under the eigenvector's sign: A3 . X~ + b3 < 0
+  {  // the used points in front of the camera under the eigenvector's sign
     int front = 0;
-    const double a0 = sh.a3[0], a1 = sh.a3[1], a2 = sh.a3[2], b3 = sh.a3[3];
     for (int k = k0 + t; k < k1; k += CM_BLK) {
       const int o = a.cam_obs[k];
-      if (!obs_used(a, o)) continue;
+      if (!obs_used(a.info, o)) continue;
       const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
-      const double z = ((a0 * (sc * ((xp[0] - org[0]) - dm[0])) + a1 * (sc * ((xp[1] - org[1]) - dm[1]))) +
-                        a2 * (sc * ((xp[2] - org[2]) - dm[2]))) + b3;
-      if (z < 0.0) front++;
+      const double X[3] = {xp[0], xp[1], xp[2]};
+      double h[4];
+      normalised_point(X, org, dm, sc, h);
+      if (front_z(sh.rs.V, i1, h) < 0.0) front++;
     }
     if (front) atomicAdd(&sh.front, front);
   }
   __syncthreads();
   if (t == 0) {
     const double sgn = 2.0 * (double)sh.front >= n ? 1.0 : -1.0;
-    for (int i = 0; i < 9; i++) sh.W[i] *= sgn;
-    nearest_rotation(sh);
-    const double gam = sc * (((sh.sg[0] + sh.sg[1]) + sh.sg[2]) / 3.0);
-    double tr[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++) {  // t = b / gamma - R m, m = origin + mean
-      const double rm = (sh.R[3 * i] * (org[0] + dm[0]) + sh.R[3 * i + 1] * (org[1] + dm[1])) + sh.R[3 * i + 2] * (org[2] + dm[2]);
-      tr[i] = sgn * sh.r[i] / gam - rm;
-    }
-    rotation_vector(sh);
-    const bool ok = isfinite(sh.r[0]) && isfinite(sh.r[1]) && isfinite(sh.r[2]) && isfinite(tr[0]) && isfinite(tr[1]) && isfinite(tr[2]);
+    const bool ok = pose_from_eigenvector(sh.rs, i1, sgn, sc, org, dm);
     if (ok) {
-      xc[0] = sh.r[0], xc[1] = sh.r[1], xc[2] = sh.r[2];
-      xc[3] = tr[0], xc[4] = tr[1], xc[5] = tr[2];
+      xc[0] = sh.rs.r[0], xc[1] = sh.rs.r[1], xc[2] = sh.rs.r[2];
+      xc[3] = sh.rs.tr[0], xc[4] = sh.rs.tr[1], xc[5] = sh.rs.tr[2];
     }
     a.resect[c] = ok ? RS_DONE : RS_DEGENERATE;
   }
@@ -654,22 +539,87 @@ static CamArgs camera_args(ba_problem *p, double *d_x, bool resect, int max_iter
   return a;
 }
 
-// (resect: k_resect_cameras, then) k_refine_cameras on st; the counters stay on the device (p->cams.counts)
-static int camera_launch(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
-                         double *d_cost, hipStream_t st) {
+static int launch_resect(ba_problem *p, const CamArgs &a, hipStream_t st) {
+  ProfScope ps(p, PC_RESECT_CAMERAS, st);
+  return BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a);
+}
+
+static int launch_refine(ba_problem *p, const CamArgs &a, hipStream_t st) {
+  ProfScope ps(p, PC_REFINE_CAMERAS, st);
+  return BA_LAUNCH(k_refine_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a);
+}
+
+// the arguments of the consensus kernels (ba_ransac_kernels.hip) from those of the camera kernels
+static RansacArgs ransac_args(ba_problem *p, const CamArgs &a, const ba_ransac_opts &o) {
+  CameraWork &w = p->cams;
+  RansacArgs r;
+  r.cam_ptr = a.cam_ptr, r.cam_obs = a.cam_obs, r.pnt0 = a.pnt0, r.pt2d = a.pt2d, r.info = a.info, r.mask = a.mask;
+  r.x = a.x, r.xc = a.xc, r.hyp_pose = w.hyp_pose, r.hyp_count = w.hyp_count;
+  r.inlier = w.rs_inlier, r.stopped = w.rs_stopped, r.n_inliers = w.rs_n, r.best_hyp = w.rs_best;
+  r.hypotheses = o.hypotheses, r.sample = o.sample, r.min_inliers = o.min_inliers;
+  r.seed_mix = ransac_seed_mix(o.seed), r.tau2 = o.threshold * o.threshold;
+  return r;
+}
+
+// The consensus stage of ba_ransac_cameras: hypotheses -> select -> refits x (mask -> resect into the scratch
+// cameras -> rescore) -> mask.  The set reaches k_resect_cameras and k_refine_cameras as information: w.rs_info, the masked copy
+// of the factors (1 0 1 when the caller set none: the values the kernels use without an array).
+static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opts &o, hipStream_t st) {
+  CameraWork &w = p->cams;
+  if (!w.rs_inlier) {
+    BA_CHECK(w.rs_inlier.alloc(p->nobs));
+    BA_CHECK(w.rs_info.alloc(3 * p->nobs));
+    BA_CHECK(w.rs_cams.alloc(9 * p->ncams));
+    BA_CHECK(w.rs_n.alloc(p->ncams));
+    BA_CHECK(w.rs_best.alloc(p->ncams));
+    BA_CHECK(w.rs_stopped.alloc(p->ncams));
+  }
+  if (w.hyp_cap < o.hypotheses) {
+    w.hyp_cap = 0;
+    BA_CHECK(w.hyp_pose.alloc(6 * p->ncams * o.hypotheses));
+    BA_CHECK(w.hyp_count.alloc(p->ncams * o.hypotheses));
+    w.hyp_cap = o.hypotheses;
+  }
+  const RansacArgs r = ransac_args(p, a, o);
+  {
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+    BA_CHECK(launch_ransac_hypotheses(r, p->ncams, st));
+    BA_CHECK(launch_ransac_select(r, p->ncams, st));
+  }
+  CamArgs fit = a;  // the refits on the set: their poses live in a scratch copy of the cameras (the intrinsics are read from it)
+  fit.info = w.rs_info, fit.xc = w.rs_cams;
+  if (o.refits > 0)
+    BA_HIP_CHECK(hipMemcpyAsync(w.rs_cams, a.xc, (size_t)(9 * p->ncams) * sizeof(double), hipMemcpyDeviceToDevice, st));
+  for (int it = 0; it < o.refits; it++) {
+    {
+      ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+      BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
+    }
+    BA_CHECK(launch_resect(p, fit, st));
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+    BA_CHECK(launch_ransac_rescore(r, p->ncams, w.rs_cams, w.resect, st));
+  }
+  ProfScope ps(p, PC_RANSAC_CAMERAS, st);
+  return launch_ransac_mask_info(r, p->nobs, w.rs_info, st);
+}
+
+// (ransac: the consensus stage, which leaves its set as information, then) (resect: k_resect_cameras, the start poses written
+// into d_x, then) k_refine_cameras, on st without a host synchronisation; the counters stay on the device (p->cams.counts)
+static int camera_launch(ba_problem *p, double *d_x, bool resect, const ba_ransac_opts *ransac, int max_iter, double xtol,
+                         double lambda0, uint8_t *d_status, double *d_cost, hipStream_t st) {
   BA_CHECK(terms_upload(p));
   BA_CHECK(camera_tables(p));
   CameraWork &w = p->cams;
   BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
   if (p->ncams == 0) return BA_OK;
   if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
-  const CamArgs a = camera_args(p, d_x, resect, max_iter, xtol, lambda0, d_status, d_cost);
-  if (resect) {  // the start poses, written into d_x on the same stream
-    ProfScope ps(p, PC_RESECT_CAMERAS, st);
-    BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a));
+  CamArgs a = camera_args(p, d_x, resect, max_iter, xtol, lambda0, d_status, d_cost);
+  if (ransac) {
+    BA_CHECK(ransac_consensus(p, a, *ransac, st));
+    a.info = w.rs_info;
   }
-  ProfScope ps(p, PC_REFINE_CAMERAS, st);
-  return BA_LAUNCH(k_refine_cameras, (unsigned)p->ncams, CM_BLK, 0, st, a);
+  if (resect) BA_CHECK(launch_resect(p, a, st));
+  return launch_refine(p, a, st);
 }
 
 static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, bool resect, int max_iter, double xtol, double lambda0,
@@ -677,7 +627,7 @@ static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout,
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, resect, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, resect, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
 
@@ -687,7 +637,7 @@ static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, 
   // the cameras only: the point part of the caller's x is never written
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            return camera_launch(p, dx, resect, max_iter, xtol, lambda0, d_status, d_cost, st);
+                            return camera_launch(p, dx, resect, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st);
                           });
 }
 
@@ -740,75 +690,7 @@ static int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransa
   return BA_OK;
 }
 
-// hypotheses -> select -> refits x (resect into the scratch cameras -> rescore) -> resect into d_x -> refine, on st without a host
-// synchronisation in between.  The set reaches k_resect_cameras and k_refine_cameras as information: the masked copy of the
-// factors (1 0 1 when the caller set none: the values the kernels use without an array), so both run unchanged.
-static int ransac_launch(ba_problem *p, double *d_x, const ba_ransac_opts &o, int max_iter, double xtol, double lambda0, uint8_t *d_status,
-                         double *d_cost, hipStream_t st) {
-  BA_CHECK(terms_upload(p));
-  BA_CHECK(camera_tables(p));
-  CameraWork &w = p->cams;
-  BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
-  if (p->ncams == 0) return BA_OK;
-  if (!w.resect) BA_CHECK(w.resect.alloc(p->ncams));
-  if (!w.rs_inlier) {
-    BA_CHECK(w.rs_inlier.alloc(p->nobs));
-    BA_CHECK(w.rs_info.alloc(3 * p->nobs));
-    BA_CHECK(w.rs_cams.alloc(9 * p->ncams));
-    BA_CHECK(w.rs_n.alloc(p->ncams));
-    BA_CHECK(w.rs_best.alloc(p->ncams));
-    BA_CHECK(w.rs_stopped.alloc(p->ncams));
-  }
-  if (w.hyp_cap < o.hypotheses) {
-    w.hyp_cap = 0;
-    BA_CHECK(w.hyp_pose.alloc(6 * p->ncams * o.hypotheses));
-    BA_CHECK(w.hyp_count.alloc(p->ncams * o.hypotheses));
-    w.hyp_cap = o.hypotheses;
-  }
-  const CamArgs a = camera_args(p, d_x, true, max_iter, xtol, lambda0, d_status, d_cost);
-  RansacArgs r;
-  r.cam_ptr = a.cam_ptr, r.cam_obs = a.cam_obs, r.pnt0 = a.pnt0, r.pt2d = a.pt2d, r.info = a.info, r.mask = a.mask;
-  r.x = a.x, r.xc = a.xc, r.hyp_pose = w.hyp_pose, r.hyp_count = w.hyp_count;
-  r.inlier = w.rs_inlier, r.stopped = w.rs_stopped, r.n_inliers = w.rs_n, r.best_hyp = w.rs_best;
-  r.hypotheses = o.hypotheses, r.sample = o.sample, r.min_inliers = o.min_inliers;
-  r.seed_mix = ransac_seed_mix(o.seed), r.tau2 = o.threshold * o.threshold;
-  {
-    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
-    BA_CHECK(launch_ransac_hypotheses(r, p->ncams, st));
-    BA_CHECK(launch_ransac_select(r, p->ncams, st));
-  }
-  CamArgs fit = a;  // the fits on the set
-  fit.info = w.rs_info;
-  if (o.refits > 0) {  // their poses live in a scratch copy of the cameras (the intrinsics are read from it)
-    BA_HIP_CHECK(hipMemcpyAsync(w.rs_cams, a.xc, (size_t)(9 * p->ncams) * sizeof(double), hipMemcpyDeviceToDevice, st));
-    fit.xc = w.rs_cams;
-  }
-  for (int it = 0; it < o.refits; it++) {
-    {
-      ProfScope ps(p, PC_RANSAC_CAMERAS, st);
-      BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
-    }
-    {
-      ProfScope ps(p, PC_RESECT_CAMERAS, st);
-      BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit));
-    }
-    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
-    BA_CHECK(launch_ransac_rescore(r, p->ncams, w.rs_cams, w.resect, st));
-  }
-  fit.xc = a.xc;
-  {
-    ProfScope ps(p, PC_RANSAC_CAMERAS, st);
-    BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
-  }
-  {
-    ProfScope ps(p, PC_RESECT_CAMERAS, st);
-    BA_CHECK(BA_LAUNCH(k_resect_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit));
-  }
-  ProfScope ps(p, PC_REFINE_CAMERAS, st);
-  return BA_LAUNCH(k_refine_cameras, (unsigned)p->ncams, CM_BLK, 0, st, fit);
-}
-
-// the consensus results of the last ransac_launch -> the caller's arrays (each may be null), on st
+// the consensus results of the last ransac_consensus -> the caller's arrays (each may be null), on st
 static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, hipMemcpyKind kind, hipStream_t st) {
   const CameraWork &w = p->cams;
   if (p->ncams == 0) return BA_OK;
@@ -827,7 +709,7 @@ extern "C" int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout, const ba_
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(ransac_launch(p, d_x_inout, o, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, true, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
   BA_CHECK(ransac_results(p, d_inlier, d_n_inliers, d_best_hyp, hipMemcpyDeviceToDevice, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
@@ -841,7 +723,7 @@ extern "C" int ba_ransac_cameras(ba_problem *p, double *x_inout, const ba_ransac
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            BA_CHECK(ransac_launch(p, dx, o, max_iter, xtol, lambda0, d_status, d_cost, st));
+                            BA_CHECK(camera_launch(p, dx, true, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
                             return ransac_results(p, inlier, n_inliers, best_hyp, hipMemcpyDeviceToHost, st);
                           });
 }

@@ -2,12 +2,13 @@
 //
 // k_ransac_hypotheses: grid (camera, hypotheses / 4), ONE WAVE PER HYPOTHESIS.  The usual call registers a handful of cameras
 // with thousands of correspondences each; one workgroup per camera, as k_resect_cameras has it, would leave the chip empty.
-// A wave draws its minimal sample (one draw per lane: the 64 draws of the header at once), takes the 40 moment sums of the
-// sampled observations through wave_all_sum, solves the 12 x 12 eigenproblem by cyclic Jacobi, recovers the pose as
-// k_resect_cameras does and counts the inliers of the camera's whole list in a strided pass.  The four waves of a workgroup never
-// meet: the matrix and the rotations of a wave live in its own LDS slab and the phases of a rotation are ordered inside the wave
-// (wave_sync: the LDS operations of one wave complete in order, the fence keeps the compiler from moving them), so the kernel has
-// no workgroup barrier and a wave whose sample is void or degenerate simply leaves.
+// A wave draws its minimal sample (one draw per lane: the 64 draws of the header at once), takes the 4 + 40 sums of the
+// sampled observations through wave_all_sum and then runs the linear resection of ba_refine_dev.h on its own LDS slab (a
+// ResectScratch): the very functions k_resect_cameras runs per workgroup, so the same sums give the same pose, bit for bit.
+// It counts the inliers of the camera's whole list in a strided pass.  The four waves of a workgroup never meet: the phases of
+// a Jacobi rotation are ordered inside the wave (jacobi12<wave_sync>: the LDS operations of one wave complete in order, the
+// fence keeps the compiler from moving them), so the kernel has no workgroup barrier and a wave whose sample is void or
+// degenerate simply leaves.
 // k_ransac_select (one workgroup per camera) picks the winner and writes the inlier bytes; k_ransac_rescore compares the set
 // a refit gives with the current one; k_ransac_mask_info hands the set to k_resect_cameras / k_refine_cameras as information.
 // All three kernels that test an observation call ransac_inlier, so a count never disagrees with the bytes.
@@ -33,43 +34,14 @@ constexpr int RN_SAMPLE_MIN = 6, RN_SAMPLE_MAX = 16;
 namespace {
 
 #include "ba_model_dev.h"   // cam_pre, project_pre
-#include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS, nearest_rotation, rotation_vector
+#include "ba_refine_dev.h"  // wave_all_sum, p1_z, obs_used, the pieces of the linear resection
 
 constexpr int RN_BLK = 256, RN_WAVES = RN_BLK / 64;
-constexpr unsigned RN_POSE = 0x3Fu;
-constexpr int RN_SUMS = 40;  // [S0 | Sx | Sy | Sq], each packed lower row-major (10): as k_resect_cameras
-
-// one wave's slab
-struct HypShared {
-  double M[144], V[144];  // the normal matrix (its diagonal ends as the eigenvalues) and the accumulated rotations
-  double S[RN_SUMS];      // the moment sums on their way into M
-  double W[9], V3[9], sg[3], U[9], R[9], r[3], tr[3];  // as RsShared of k_resect_cameras; tr: b, then the translation
-  int ok;
-};
-
-// orders the LDS accesses of the wave's lanes before it against those after it
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int wave_all_sum_int(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ bool ransac_used(const RansacArgs &a, int o) {
-  if (!a.info) return true;
-  const double *l = a.info + 3 * (int64_t)o;
-  return !(l[0] == 0.0 && l[1] == 0.0 && l[2] == 0.0);
-}
 
 // the inlier test of the header under the cam_pre row P: used, in front (P1.z < 0), within tau of its measurement in raw pixels
 // (a comparison with NaN fails)
 __device__ __forceinline__ bool ransac_inlier(const RansacArgs &a, const double P[12], int o) {
-  if (!ransac_used(a, o)) return false;
+  if (!obs_used(a.info, o)) return false;
   const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
   const double X[3] = {xp[0], xp[1], xp[2]};
   const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
@@ -86,52 +58,10 @@ __device__ __forceinline__ void pose_row(const double *pose, const double *xc, d
   cam_pre<double>(C9, P);
 }
 
-// Cyclic Jacobi on the symmetric 12 x 12 matrix A (row-major, both triangles kept) by ONE WAVE, A and V in its slab: the
-// rotations, the skip test and the sweep cap of jacobi_eig (ba_camera_kernels.hip).  Every lane reads the same three entries
-// and takes the same decision; lanes 0..11 update the two columns, then the two rows of A, lanes 16..27 the two columns of V.
-__device__ __forceinline__ void wave_jacobi12(double *A, double *V, int lane) {
-  for (int i = lane; i < 144; i += 64) V[i] = (i / 12 == i % 12) ? 1.0 : 0.0;
-  wave_sync();
-#pragma nounroll
-  for (int sweep = 0; sweep < RS_SWEEPS; sweep++) {
-    int rotated = 0;
-#pragma nounroll
-    for (int p = 0; p < 11; p++)
-#pragma nounroll
-      for (int q = p + 1; q < 12; q++) {
-        const double apq = A[p * 12 + q], app = A[p * 12 + p], aqq = A[q * 12 + q];
-        if (!(fabs(apq) > 1e-18 * sqrt(fabs(app * aqq)))) continue;  // (uniform; also ends on a NaN)
-        rotated = 1;
-        const double th = (aqq - app) / (2.0 * apq);
-        const double tt = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-        wave_sync();
-        if (lane < 12) {  // A <- A G
-          const double akp = A[lane * 12 + p], akq = A[lane * 12 + q];
-          A[lane * 12 + p] = cs * akp - sn * akq;
-          A[lane * 12 + q] = sn * akp + cs * akq;
-        } else if (lane >= 16 && lane < 28) {  // V <- V G
-          const int k = lane - 16;
-          const double vkp = V[k * 12 + p], vkq = V[k * 12 + q];
-          V[k * 12 + p] = cs * vkp - sn * vkq;
-          V[k * 12 + q] = sn * vkp + cs * vkq;
-        }
-        wave_sync();
-        if (lane < 12) {  // A <- G' A with a_pq = a_qp = 0
-          const double apk = A[p * 12 + lane], aqk = A[q * 12 + lane];
-          A[p * 12 + lane] = lane == q ? 0.0 : cs * apk - sn * aqk;
-          A[q * 12 + lane] = lane == p ? 0.0 : sn * apk + cs * aqk;
-        }
-        wave_sync();
-      }
-    if (!rotated) break;
-  }
-}
-
 // The pose of hypothesis h of camera c (list [k0, k1), intrinsics xc[6..8]) -> its cam_pre row P and pose[6]; false: void (too
 // few distinct used draws) or degenerate.  Called by a whole wave; the control flow is uniform over it.
-__device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, HypShared &sh, const double *xc, int h, int k0, int k1, int lane,
-                                                double pose[6], double P[12]) {
+__device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScratch &sh, const double *xc, int h, int k0, int k1,
+                                                int lane, double pose[6], double P[12]) {
   const int d = k1 - k0, m = a.sample;
   const double ck1 = xc[6], ck2 = xc[7], cf = xc[8];
   if (d <= 0 || !isfinite(cf) || cf == 0.0) return false;
@@ -139,7 +69,7 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, HypShared &
   const uint64_t key = ransac_mix(a.seed_mix ^ (uint64_t)h);
   const int pos = (int)ransac_draw(key, lane, d);  // < d
   const int o = a.cam_obs[k0 + pos];
-  bool accept = ransac_used(a, o);
+  bool accept = obs_used(a.info, o);
 #pragma nounroll
   for (int i = 0; i < RN_DRAWS - 1; i++) {
     const int pi = __shfl(pos, i, 64);
@@ -154,15 +84,7 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, HypShared &
     const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
     X[0] = xp[0], X[1] = xp[1], X[2] = xp[2];
     const double2 mm = reinterpret_cast<const double2 *>(a.pt2d)[o];
-    const double ux = mm.x / cf, uy = mm.y / cf;
-    qx = ux, qy = uy;
-#pragma unroll
-    for (int it = 0; it < UNDIST_ITERS; it++) {
-      const double n2 = qx * qx + qy * qy;
-      const double den = 1.0 + ck1 * n2 + ck2 * (n2 * n2);
-      qx = ux / den;
-      qy = uy / den;
-    }
+    undistort(mm.x / cf, mm.y / cf, ck1, ck2, qx, qy);
   }
   const double org[3] = {__shfl(X[0], first, 64), __shfl(X[1], first, 64), __shfl(X[2], first, 64)};
   // the mean of the sampled points and their RMS distance from it
@@ -174,81 +96,33 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, HypShared &
   }
 #pragma unroll
   for (int i = 0; i < 4; i++) mo[i] = wave_all_sum(mo[i]);
-  const double n = (double)m;
-  const double dm[3] = {mo[0] / n, mo[1] / n, mo[2] / n};
-  const double var = mo[3] / n - ((dm[0] * dm[0] + dm[1] * dm[1]) + dm[2] * dm[2]);
-  if (!(var > 0.0) || !isfinite(var)) return false;
-  const double sc = 1.0 / sqrt(var);
-  const double hh4[4] = {sc * ((X[0] - org[0]) - dm[0]), sc * ((X[1] - org[1]) - dm[1]), sc * ((X[2] - org[2]) - dm[2]), 1.0};
-  // the moments
-  double acc[RN_SUMS];
-  {
-    const double q2 = qx * qx + qy * qy;
-    int tt = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-      for (int j = 0; j <= i; j++, tt++) {
-        const double hh = take ? hh4[i] * hh4[j] : 0.0;
-        acc[tt] = hh;
-        acc[10 + tt] = qx * hh;
-        acc[20 + tt] = qy * hh;
-        acc[30 + tt] = q2 * hh;
-      }
-  }
+  double dm[3], sc;
+  if (!hartley_stats((double)m, mo, mo[3], dm, sc)) return false;
+  // the moments: a lane that takes no draw adds zeros
+  double hh[4] = {0.0, 0.0, 0.0, 0.0}, acc[RS_SUMS];
+  if (take) normalised_point(X, org, dm, sc, hh);
+  moment_terms(hh, qx, qy, acc);
   bool ok = true;
 #pragma unroll
-  for (int i = 0; i < RN_SUMS; i++) {
+  for (int i = 0; i < RS_SUMS; i++) {
     acc[i] = wave_all_sum(acc[i]);
     ok = ok && isfinite(acc[i]);
   }
   if (!ok) return false;
-  // M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]]: the sums go through the slab so that the fill indexes LDS, not registers
   if (lane == 0) {
 #pragma unroll
-    for (int i = 0; i < RN_SUMS; i++) sh.S[i] = acc[i];
+    for (int i = 0; i < RS_SUMS; i++) sh.S[i] = acc[i];
   }
   wave_sync();
-  for (int e = lane; e < 144; e += 64) {
-    const int row = e / 12, col = e % 12, br = row >> 2, bc = col >> 2, i = row & 3, j = col & 3;
-    const int hi = i > j ? i : j, lo = i > j ? j : i, tt = hi * (hi + 1) / 2 + lo;
-    double v = 0.0;
-    if (br == bc) v = br == 2 ? sh.S[30 + tt] : sh.S[tt];
-    else if (br == 2 || bc == 2) v = sh.S[10 * (1 + (br == 2 ? bc : br)) + tt];
-    sh.M[e] = v;
-  }
-  wave_sync();
-  wave_jacobi12(sh.M, sh.V, lane);
-  int i1 = 0;
-  double l1 = sh.M[0], lmax = sh.M[0];
-  for (int i = 1; i < 12; i++) {
-    const double l = sh.M[13 * i];
-    if (l < l1) l1 = l, i1 = i;
-    lmax = fmax(lmax, l);
-  }
-  double l2 = lmax;
-  for (int i = 0; i < 12; i++)
-    if (i != i1) l2 = fmin(l2, sh.M[13 * i]);
-  if (!(isfinite(l1) && isfinite(lmax) && l2 > 1e-10 * lmax)) return false;
-  // the points of the sample in front of the camera under the eigenvector's sign: A3 . X~ + b3 < 0
-  const double z = ((sh.V[8 * 12 + i1] * hh4[0] + sh.V[9 * 12 + i1] * hh4[1]) + sh.V[10 * 12 + i1] * hh4[2]) + sh.V[11 * 12 + i1];
-  const int front = __popcll(__ballot(take && z < 0.0));
+  for (int e = lane; e < 144; e += 64) sh.M[e] = normal_matrix_entry(sh.S, e);
+  jacobi12<wave_sync>(sh.M, sh.V, lane, 64);
+  int i1;
+  if (!smallest_eigenpair(sh.M, i1)) return false;
+  // the points of the sample in front of the camera under the eigenvector's sign
+  const int front = __popcll(__ballot(take && front_z(sh.V, i1, hh) < 0.0));
   if (lane == 0) {
     const double sgn = 2 * front >= m ? 1.0 : -1.0;
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) sh.W[3 * i + j] = sgn * sh.V[(4 * i + j) * 12 + i1];
-      sh.tr[i] = sh.V[(4 * i + 3) * 12 + i1];  // b, until the translation takes its place
-    }
-    nearest_rotation(sh);
-    const double gam = sc * (((sh.sg[0] + sh.sg[1]) + sh.sg[2]) / 3.0);
-    bool fin = true;
-    for (int i = 0; i < 3; i++) {  // t = b / gamma - R m, m = origin + mean
-      const double rm = (sh.R[3 * i] * (org[0] + dm[0]) + sh.R[3 * i + 1] * (org[1] + dm[1])) + sh.R[3 * i + 2] * (org[2] + dm[2]);
-      sh.tr[i] = sgn * sh.tr[i] / gam - rm;
-      fin = fin && isfinite(sh.tr[i]);
-    }
-    rotation_vector(sh);
-    sh.ok = fin && isfinite(sh.r[0]) && isfinite(sh.r[1]) && isfinite(sh.r[2]) ? 1 : 0;
+    sh.ok = pose_from_eigenvector(sh, i1, sgn, sc, org, dm) ? 1 : 0;
   }
   wave_sync();
   if (!sh.ok) return false;
@@ -259,11 +133,11 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, HypShared &
 }
 
 __global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses(RansacArgs a) {
-  __shared__ HypShared shs[RN_WAVES];
+  __shared__ ResectScratch shs[RN_WAVES];  // one wave's slab each
   const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
   const int c = (int)blockIdx.x, h = (int)blockIdx.y * RN_WAVES + wv;
   if (h >= a.hypotheses) return;
-  if ((a.mask ? (unsigned)a.mask[c] : 0u) & RN_POSE) return;  // not attempted: k_ransac_select reads nothing of it
+  if ((a.mask ? (unsigned)a.mask[c] : 0u) & POSE_MASK) return;  // not attempted: k_ransac_select reads nothing of it
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
   const int64_t slot = (int64_t)c * a.hypotheses + h;
   double pose[6], P[12];
@@ -298,11 +172,11 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
   __shared__ int red[RN_WAVES];
   const int t = (int)threadIdx.x, c = (int)blockIdx.x;
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
-  if ((a.mask ? (unsigned)a.mask[c] : 0u) & RN_POSE) {
+  if ((a.mask ? (unsigned)a.mask[c] : 0u) & POSE_MASK) {
     int n = 0;
     for (int k = k0 + t; k < k1; k += RN_BLK) {
       const int o = a.cam_obs[k];
-      const int u = ransac_used(a, o) ? 1 : 0;
+      const int u = obs_used(a.info, o) ? 1 : 0;
       a.inlier[o] = (uint8_t)u;
       n += u;
     }

@@ -2,10 +2,15 @@
 // §5j-§5m).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
-// Two more pieces are alike in both files and stay written out at their sites, because as shared functions they change the
-// kernels' instructions (tools/compare_code_objects.py against the build before): the load of an observation's information
-// factors with its "Lambda == 0" test (load_obs; observation_sums and obs_used) and the undistortion loop (point_triangulate;
-// k_resect_cameras), which share only its iteration count.
+// The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
+// the hypotheses of k_ransac_hypotheses (one wave per hypothesis) gather and reduce their 4 + 40 sums in their own way and
+// share every step after that -- the same functions, so the same bits from the same sums.
+//
+// Two pieces are alike in several places and stay written out at their sites, because as shared functions they change the
+// instructions of kernels that are to keep them (tools/compare_code_objects.py against the build before): the load of an
+// observation's information factors with its "Lambda == 0" test (load_obs of the point kernels; observation_sums of
+// k_refine_cameras; obs_used here) and the undistortion loop of point_triangulate, a copy of undistort below (with a call
+// of undistort in its place the disassembly of k_refine_points differs).
 #pragma once
 
 __device__ __forceinline__ double wave_all_sum(double v) {  // every lane receives the same bits (a + b == b + a)
@@ -24,16 +29,170 @@ __device__ __forceinline__ void p1_z(const double P[12], const double X[3], doub
 // fixed-point iterations of the undistortion q <- u / (1 + k1 |q|^2 + k2 |q|^4), u = pt2d / f (triangulation and resection)
 constexpr int UNDIST_ITERS = 8;
 
-// ---- pieces of the linear resection (k_resect_cameras; the hypotheses of ba_ransac_cameras) ----------------------------------
-// Sh: the LDS block of the caller, with the members W[9], V3[9], sg[3], U[9], R[9], r[3]
+__device__ __forceinline__ void undistort(double ux, double uy, double k1, double k2, double &qx, double &qy) {
+  qx = ux, qy = uy;
+#pragma unroll
+  for (int it = 0; it < UNDIST_ITERS; it++) {
+    const double n2 = qx * qx + qy * qy;
+    const double den = 1.0 + k1 * n2 + k2 * (n2 * n2);
+    qx = ux / den;
+    qy = uy / den;
+  }
+}
+
+// an observation with Lambda == 0 is dropped (info: l00 l10 l11 per observation, or null)
+__device__ __forceinline__ bool obs_used(const double *info, int o) {
+  if (!info) return true;
+  const double *l = info + 3 * (int64_t)o;
+  return !(l[0] == 0.0 && l[1] == 0.0 && l[2] == 0.0);
+}
+
+// orders the LDS accesses of the wave's lanes before it against those after it
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ int wave_all_sum_int(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// ---- the linear resection: the pose of a camera from 2D-3D correspondences ---------------------------------------
+// With P = R X + t the BAL projection gives q = -P.xy / P.z for the undistorted measurement q: P.x + q_x P.z = 0 and
+// P.y + q_y P.z = 0, two homogeneous linear equations in the 12 entries of [R | t].  On Hartley-normalised points X~ = s (X - m),
+// h = (X~, 1), the 12 x 12 normal matrix is M = [[S0, 0, Sx], [0, S0, Sy], [Sx, Sy, Sq]] with the 4 x 4 moments S0 = sum h h',
+// Sx = sum q_x h h', Sy = sum q_y h h', Sq = sum |q|^2 h h'.  The eigenvector of M's smallest eigenvalue (cyclic Jacobi, M and the
+// rotations in LDS) is gamma [R / s | R m + t].  A caller gathers its observations about a provisional origin, reduces the sums
+// of d = X - origin and |d|^2 (hartley_stats), then the 40 moment sums (moment_terms), and runs the steps below in their order.
+constexpr int RS_SUMS = 40;         // [S0 | Sx | Sy | Sq], each packed lower row-major (10)
+constexpr int RS_MIN_OBS = 6;       // 12 unknowns up to scale, two equations per observation
 constexpr int RS_SWEEPS = 30;       // cap of the Jacobi sweeps (12 x 12 and 3 x 3)
+constexpr unsigned POSE_MASK = 0x3Fu;  // the pose components in a camera's mask of held components: any of them, no resection
+
+// the LDS of one resection: one per workgroup in k_resect_cameras, one per wave in k_ransac_hypotheses
+struct ResectScratch {
+  double S[RS_SUMS];          // the moment sums on their way into M (the fill indexes LDS, not registers)
+  double M[144], V[144];      // the normal matrix (its diagonal ends as the eigenvalues) and the accumulated rotations
+  double W[9], V3[9], sg[3];  // the 3 x 3 block A and its one-sided Jacobi SVD: W -> U Sigma, V3, the singular values
+  double U[9], R[9], r[3], tr[3];  // r: the rotation vector; tr: b, then the translation
+  int ok;
+};
+
+// The mean dm of d and sc = 1 / (the RMS distance from it) from n, sum d and sum |d|^2; false: the points coincide or a sum
+// is not finite
+__device__ __forceinline__ bool hartley_stats(double n, const double sd[3], double sd2, double dm[3], double &sc) {
+  dm[0] = sd[0] / n, dm[1] = sd[1] / n, dm[2] = sd[2] / n;
+  const double var = sd2 / n - ((dm[0] * dm[0] + dm[1] * dm[1]) + dm[2] * dm[2]);
+  if (!(var > 0.0) || !isfinite(var)) return false;
+  sc = 1.0 / sqrt(var);
+  return true;
+}
+
+// h = (X~, 1) of the point X
+__device__ __forceinline__ void normalised_point(const double X[3], const double org[3], const double dm[3], double sc, double h[4]) {
+  h[0] = sc * ((X[0] - org[0]) - dm[0]), h[1] = sc * ((X[1] - org[1]) - dm[1]), h[2] = sc * ((X[2] - org[2]) - dm[2]), h[3] = 1.0;
+}
+
+// the 40 terms of one observation; the caller adds them up (k_resect_cameras) or takes them as they are (one draw per lane)
+__device__ __forceinline__ void moment_terms(const double h[4], double qx, double qy, double term[RS_SUMS]) {
+  const double q2 = qx * qx + qy * qy;
+  int tt = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+#pragma unroll
+    for (int j = 0; j <= i; j++, tt++) {
+      const double hh = h[i] * h[j];
+      term[tt] = hh;
+      term[10 + tt] = qx * hh;
+      term[20 + tt] = qy * hh;
+      term[30 + tt] = q2 * hh;
+    }
+}
+
+// element e (row-major) of M from the packed sums S
+__device__ __forceinline__ double normal_matrix_entry(const double *S, int e) {
+  const int row = e / 12, col = e % 12, br = row >> 2, bc = col >> 2, i = row & 3, j = col & 3;
+  const int hi = i > j ? i : j, lo = i > j ? j : i, tt = hi * (hi + 1) / 2 + lo;
+  if (br == bc) return br == 2 ? S[30 + tt] : S[tt];
+  if (br == 2 || bc == 2) return S[10 * (1 + (br == 2 ? bc : br)) + tt];
+  return 0.0;
+}
+
+// Cyclic Jacobi on the symmetric 12 x 12 matrix A (row-major, both triangles kept), V <- the product of the rotations (the
+// columns end as eigenvectors, the diagonal of A as eigenvalues).  A rotation is skipped when |a_pq| <= 1e-18 sqrt(|a_pp a_qq|);
+// the sweeps end with the first sweep without a rotation or at RS_SWEEPS.  Called by `lanes` lanes (lane: 0 .. lanes - 1) that
+// Sync orders -- a wave with wave_sync, a workgroup with __syncthreads -- A and V in LDS, A filled by those lanes (a Sync
+// comes before the first read).  Every lane reads the same three entries and takes the same decision; lanes 0..11 update element
+// k of the two columns of A while lanes 16..27 update it in the two columns of V, then lanes 0..11 the two rows of A, with a Sync
+// between the phases.  Every element sees the operations of a one-lane loop over k.  The two groups of the first phase run one
+// piece of code on a selected base pointer: as two branches they take turns inside their wave, an LDS round trip more per
+// rotation, which made k_resect_cameras 3 % slower than with the rotations updated in the second phase.
+template <void (*Sync)()>
+__device__ __forceinline__ void jacobi12(double *A, double *V, int lane, int lanes) {
+  for (int i = lane; i < 144; i += lanes) V[i] = (i / 12 == i % 12) ? 1.0 : 0.0;
+  Sync();
+#pragma nounroll
+  for (int sweep = 0; sweep < RS_SWEEPS; sweep++) {
+    int rotated = 0;
+#pragma nounroll
+    for (int p = 0; p < 11; p++)
+#pragma nounroll
+      for (int q = p + 1; q < 12; q++) {
+        const double apq = A[p * 12 + q], app = A[p * 12 + p], aqq = A[q * 12 + q];
+        if (!(fabs(apq) > 1e-18 * sqrt(fabs(app * aqq)))) continue;  // (uniform; also ends on a NaN)
+        rotated = 1;
+        const double th = (aqq - app) / (2.0 * apq);
+        const double tt = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+        Sync();  // (every lane has read the three entries)
+        if (lane < 12 || (lane >= 16 && lane < 28)) {  // A <- A G and V <- V G: one path, so the two do not take turns
+          double *T = lane < 12 ? A : V;
+          const int k = lane < 12 ? lane : lane - 16;
+          const double tkp = T[k * 12 + p], tkq = T[k * 12 + q];
+          T[k * 12 + p] = cs * tkp - sn * tkq;
+          T[k * 12 + q] = sn * tkp + cs * tkq;
+        }
+        Sync();
+        if (lane < 12) {  // A <- G' A with a_pq = a_qp = 0
+          const double apk = A[p * 12 + lane], aqk = A[q * 12 + lane];
+          A[p * 12 + lane] = lane == q ? 0.0 : cs * apk - sn * aqk;
+          A[q * 12 + lane] = lane == p ? 0.0 : sn * apk + cs * aqk;
+        }
+        Sync();
+      }
+    if (!rotated) break;
+  }
+}
+
+// i1 <- the index of the smallest eigenvalue on the diagonal of M; false: an eigenvalue that is not finite, or the second
+// smallest is not above 1e-10 of the largest (the eigenvector is not determined)
+__device__ __forceinline__ bool smallest_eigenpair(const double *M, int &i1) {
+  i1 = 0;
+  double l1 = M[0], lmax = M[0];
+  for (int i = 1; i < 12; i++) {
+    const double l = M[13 * i];
+    if (l < l1) l1 = l, i1 = i;
+    lmax = fmax(lmax, l);
+  }
+  double l2 = lmax;
+  for (int i = 0; i < 12; i++)
+    if (i != i1) l2 = fmin(l2, M[13 * i]);
+  return isfinite(l1) && isfinite(lmax) && l2 > 1e-10 * lmax;
+}
+
+// A3 . X~ + b3 of eigenvector i1: negative for a point in front of the camera under the eigenvector's sign
+__device__ __forceinline__ double front_z(const double *V, int i1, const double h[4]) {
+  return ((V[8 * 12 + i1] * h[0] + V[9 * 12 + i1] * h[1]) + V[10 * 12 + i1] * h[2]) + V[11 * 12 + i1];
+}
 
 // The nearest proper rotation of the 3 x 3 matrix sh.W (row-major) -> sh.R, its singular values -> sh.sg: one-sided Jacobi
 // (rotations of column pairs until they are orthogonal: W V3 = U Sigma), then R = U diag(1, 1, det(U V3')) V3' with the sign on
 // the smallest singular value -- its column of U is taken as the cross product of the other two, which is that sign and
 // needs no division by a singular value that may be 0.  (one lane)
-template <typename Sh>
-__device__ __forceinline__ void nearest_rotation(Sh &sh) {
+__device__ __forceinline__ void nearest_rotation(ResectScratch &sh) {
   for (int i = 0; i < 9; i++) sh.V3[i] = (i / 3 == i % 3) ? 1.0 : 0.0;
 #pragma nounroll
   for (int sweep = 0; sweep < RS_SWEEPS; sweep++) {
@@ -87,8 +246,7 @@ __device__ __forceinline__ void nearest_rotation(Sh &sh) {
 // The rotation vector of sh.R -> sh.r: theta = atan2(|w| / 2, (tr R - 1) / 2), w the skew part; the axis is w / |w|, and for
 // cos theta < 0 it comes from the diagonal of R + I (k_i^2 = (R_ii - cos) / (1 - cos) at the largest R_ii, the others from the
 // symmetric part, the sign from w); theta < 1e-12: (1e-12, 0, 0) -- the model has no theta -> 0 branch.  (one lane)
-template <typename Sh>
-__device__ __forceinline__ void rotation_vector(Sh &sh) {
+__device__ __forceinline__ void rotation_vector(ResectScratch &sh) {
   const double *R = sh.R;
   const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
   const double wn = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
@@ -108,4 +266,24 @@ __device__ __forceinline__ void rotation_vector(Sh &sh) {
     const double kn = sqrt((sh.r[0] * sh.r[0] + sh.r[1] * sh.r[1]) + sh.r[2] * sh.r[2]);
     for (int j = 0; j < 3; j++) sh.r[j] = th * (sgn * sh.r[j] / kn);
   }
+}
+
+// The pose from eigenvector i1 of sh.V = gamma [R / s | R m + t] under the sign sgn, with m = org + dm and s = sc: the rotation
+// vector -> sh.r, t = b / gamma - R m -> sh.tr, gamma = s mean(Sigma); false: a component that is not finite.  (one lane)
+__device__ __forceinline__ bool pose_from_eigenvector(ResectScratch &sh, int i1, double sgn, double sc, const double org[3],
+                                                      const double dm[3]) {
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) sh.W[3 * i + j] = sgn * sh.V[(4 * i + j) * 12 + i1];
+    sh.tr[i] = sh.V[(4 * i + 3) * 12 + i1];  // b, until the translation takes its place
+  }
+  nearest_rotation(sh);
+  const double gam = sc * (((sh.sg[0] + sh.sg[1]) + sh.sg[2]) / 3.0);
+  bool ok = true;
+  for (int i = 0; i < 3; i++) {
+    const double rm = (sh.R[3 * i] * (org[0] + dm[0]) + sh.R[3 * i + 1] * (org[1] + dm[1])) + sh.R[3 * i + 2] * (org[2] + dm[2]);
+    sh.tr[i] = sgn * sh.tr[i] / gam - rm;
+    ok = ok && isfinite(sh.tr[i]);
+  }
+  rotation_vector(sh);
+  return ok && isfinite(sh.r[0]) && isfinite(sh.r[1]) && isfinite(sh.r[2]);
 }
