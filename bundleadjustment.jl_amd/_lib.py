@@ -73,6 +73,7 @@ SYMBOLS = [
     "ba_refine_points", "ba_refine_points_dev",
     "ba_refine_cameras", "ba_refine_cameras_dev", "ba_resect_cameras", "ba_resect_cameras_dev",
     "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
+    "ba_resect_cameras_focal", "ba_resect_cameras_focal_dev", "ba_ransac_cameras_focal", "ba_ransac_cameras_focal_dev",
 ]
 
 _lib = None
@@ -154,6 +155,10 @@ def lib():
     L.ba_resect_cameras_dev.argtypes = L.ba_refine_cameras_dev.argtypes
     L.ba_ransac_cameras.argtypes = [vp, vp, C.POINTER(RansacOpts), C.c_int, f64, f64, vp, vp, vp, C.POINTER(C.c_int), vp, vp, vp]
     L.ba_ransac_cameras_dev.argtypes = L.ba_ransac_cameras.argtypes + [vp]
+    L.ba_resect_cameras_focal.argtypes = L.ba_resect_cameras.argtypes
+    L.ba_resect_cameras_focal_dev.argtypes = L.ba_resect_cameras_dev.argtypes
+    L.ba_ransac_cameras_focal.argtypes = L.ba_ransac_cameras.argtypes
+    L.ba_ransac_cameras_focal_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
     L.ba_ransac_sample.argtypes = [C.c_uint64, C.c_int, i64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     _lib = L
     return L

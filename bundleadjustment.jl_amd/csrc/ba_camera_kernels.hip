@@ -20,6 +20,8 @@
 // ba_resect_cameras launches k_resect_cameras before it: the start pose of every camera whose pose is free, in
 // closed form from its 2D-3D correspondences (further down).  ba_ransac_cameras puts the consensus kernels of
 // ba_ransac_kernels.hip in front of both and hands them its inlier set as information (ransac_consensus, on the host side).
+// The _focal entries are the same launches with CamArgs.focal set: a camera whose f is free gets it from the
+// resection's eigenvector as well, every other camera is handled as before.
 //
 // What this file has in common with ba_point_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
 // (argument check, prior lookups, counter read-back, the body of the host-pointer entries; BlockWork) in ba_internal.h / ba_api.hip.
@@ -50,6 +52,7 @@ struct CamArgs {
   double *xc;                         // its camera part
   uint8_t *status;                    // or null
   uint8_t *resect;                    // what k_resect_cameras did per camera (RS_*), or null: no resection ran
+  int focal;                          // the resection estimates f for every camera whose f is free (ba_resect_cameras_focal)
   double *cost;                       // or null
   unsigned long long *counts;
   int max_iter, kind;
@@ -367,7 +370,9 @@ __device__ __forceinline__ void block_sums(double (&acc)[N], RsShared &sh, int t
 
 // One camera per workgroup: the pose (r, t) of xc from the camera's observations with Lambda != 0, its intrinsics and the held
 // points; the pose of x is not read.  a.resect[c] <- RS_DONE (pose written), RS_SKIPPED (a pose component is held: nothing is
-// done) or RS_DEGENERATE (nothing written).  The control flow is uniform over the workgroup.
+// done) or RS_DEGENERATE (nothing written).  In focal mode (a.focal and the camera's f free) the intrinsics are not
+// read either: the measurements are scaled by the image scale, f comes out of the eigenvector and is written with the pose,
+// a free k1 / k2 as 0.  The control flow is uniform over the workgroup.
 __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   __shared__ RsShared sh;
   const int t = threadIdx.x;
@@ -379,7 +384,9 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
     if (t == 0) a.resect[c] = RS_SKIPPED;
     return;
   }
-  const double ck1 = xc[6], ck2 = xc[7], cf = xc[8];
+  const bool focal = focal_mode(a.focal, fm);
+  const double ck1 = xc[6], ck2 = xc[7];
+  double cf = xc[8];  // (focal mode: not used; the image scale takes its place)
   // the provisional origin: the point of the first observation of the list with Lambda != 0
   int first = k1;
   for (int k = k0 + t; k < k1; k += CM_BLK)
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   if (t == 0) sh.front = 0;
   __syncthreads();
   first = min(min(sh.first[0], sh.first[1]), min(sh.first[2], sh.first[3]));
-  if (first >= k1 || !isfinite(cf) || cf == 0.0) {
+  if (first >= k1 || (!focal && (!isfinite(cf) || cf == 0.0))) {
     if (t == 0) a.resect[c] = RS_DEGENERATE;
     return;
   }
@@ -402,8 +409,9 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
     const double *xp = a.x + 3 * (int64_t)a.pnt0[a.cam_obs[first]];
     org[0] = xp[0], org[1] = xp[1], org[2] = xp[2];
   }
-  // the number of used observations, their mean and their RMS distance from it
-  double mo[5] = {0, 0, 0, 0, 0};
+  // the number of used observations, their mean and their RMS distance from it; focal mode: sum |m|^2 as well, reduced on its
+  // own so that the calibrated path keeps its five sums
+  double mo[5] = {0, 0, 0, 0, 0}, sm2[1] = {0};
   for (int k = k0 + t; k < k1; k += CM_BLK) {
     const int o = a.cam_obs[k];
     if (!obs_used(a.info, o)) continue;
@@ -412,11 +420,16 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
     mo[0] += 1.0;
     mo[1] += d0, mo[2] += d1, mo[3] += d2;
     mo[4] += (d0 * d0 + d1 * d1) + d2 * d2;
+    if (focal) {
+      const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
+      sm2[0] += m.x * m.x + m.y * m.y;
+    }
   }
   block_sums<5>(mo, sh, t);
+  if (focal) block_sums<1>(sm2, sh, t);
   const double n = mo[0];
   double dm[3], sc;
-  if (n < (double)RS_MIN_OBS || !hartley_stats(n, mo + 1, mo[4], dm, sc)) {
+  if (n < (double)RS_MIN_OBS || !hartley_stats(n, mo + 1, mo[4], dm, sc) || (focal && !image_scale(n, sm2[0], cf))) {
     if (t == 0) a.resect[c] = RS_DEGENERATE;
     return;
   }
@@ -432,7 +445,8 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
     const double2 m = reinterpret_cast<const double2 *>(a.pt2d)[o];
     double h[4], qx, qy, term[RS_SUMS];
     normalised_point(X, org, dm, sc, h);
-    undistort(m.x / cf, m.y / cf, ck1, ck2, qx, qy);
+    if (focal) qx = m.x / cf, qy = m.y / cf;
+    else undistort(m.x / cf, m.y / cf, ck1, ck2, qx, qy);
     moment_terms(h, qx, qy, term);
 #pragma unroll
     for (int i = 0; i < RS_SUMS; i++) acc[i] += term[i];
@@ -475,16 +489,25 @@ __global__ __launch_bounds__(CM_BLK) void k_resect_cameras(CamArgs a) {
   __syncthreads();
   if (t == 0) {
     const double sgn = 2.0 * (double)sh.front >= n ? 1.0 : -1.0;
-    const bool ok = pose_from_eigenvector(sh.rs, i1, sgn, sc, org, dm);
+    const bool ok = (!focal || focal_from_eigenvector(sh.rs, i1, cf)) && pose_from_eigenvector(sh.rs, i1, sgn, sc, org, dm);
     if (ok) {
       xc[0] = sh.rs.r[0], xc[1] = sh.rs.r[1], xc[2] = sh.rs.r[2];
       xc[3] = sh.rs.tr[0], xc[4] = sh.rs.tr[1], xc[5] = sh.rs.tr[2];
+      if (focal) {  // f^ = a phi; a free k1 / k2 starts at 0, a held one keeps its bits (the linear stage ignores it)
+        if (!(fm & K1_HELD)) xc[6] = 0.0;
+        if (!(fm & K2_HELD)) xc[7] = 0.0;
+        xc[8] = sh.rs.f;
+      }
     }
     a.resect[c] = ok ? RS_DONE : RS_DEGENERATE;
   }
 }
 
 }  // namespace
+
+// where a call's cameras start: from x (ba_refine_cameras), from the linear resection with the intrinsics of x
+// (ba_resect_cameras, ba_ransac_cameras), or from the resection that estimates f as well (the _focal entries)
+enum CamStart { START_X = 0, START_RESECT, START_FOCAL };
 
 // the per-camera lookups of the priors (once per ba_lm_set_priors) and the effective mask (once per ba_lm_set_fixed /
 // ba_lm_set_shared_intrinsics)
@@ -521,7 +544,7 @@ static int camera_check(const char *who, ba_problem *p, const double *x, int *ma
 }
 
 // the arguments of k_resect_cameras / k_refine_cameras on d_x from the handle's terms (after terms_upload and camera_tables)
-static CamArgs camera_args(ba_problem *p, double *d_x, bool resect, int max_iter, double xtol, double lambda0, uint8_t *d_status,
+static CamArgs camera_args(ba_problem *p, double *d_x, CamStart start, int max_iter, double xtol, double lambda0, uint8_t *d_status,
                            double *d_cost) {
   CameraWork &w = p->cams;
   const PriorSet &cm = p->pri[PRI_CAM], &ct = p->pri[PRI_CTR];
@@ -533,7 +556,8 @@ static CamArgs camera_args(ba_problem *p, double *d_x, bool resect, int max_iter
   a.cam_mu = cm.n > 0 ? (const double *)cm.mu : nullptr, a.cam_info = cm.n > 0 ? (const double *)cm.info : nullptr;
   a.ctr_mu = ct.n > 0 ? (const double *)ct.mu : nullptr, a.ctr_info = ct.n > 0 ? (const double *)ct.info : nullptr;
   a.x = d_x, a.xc = d_x + 3 * p->npnts, a.status = d_status, a.cost = d_cost, a.counts = w.counts;
-  a.resect = resect ? (uint8_t *)w.resect : nullptr;
+  a.resect = start != START_X ? (uint8_t *)w.resect : nullptr;
+  a.focal = start == START_FOCAL ? 1 : 0;
   a.max_iter = max_iter, a.kind = p->loss;
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
   return a;
@@ -558,6 +582,7 @@ static RansacArgs ransac_args(ba_problem *p, const CamArgs &a, const ba_ransac_o
   r.inlier = w.rs_inlier, r.stopped = w.rs_stopped, r.n_inliers = w.rs_n, r.best_hyp = w.rs_best;
   r.hypotheses = o.hypotheses, r.sample = o.sample, r.min_inliers = o.min_inliers;
   r.seed_mix = ransac_seed_mix(o.seed), r.tau2 = o.threshold * o.threshold;
+  r.focal = a.focal;
   return r;
 }
 
@@ -576,7 +601,7 @@ static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opt
   }
   if (w.hyp_cap < o.hypotheses) {
     w.hyp_cap = 0;
-    BA_CHECK(w.hyp_pose.alloc(6 * p->ncams * o.hypotheses));
+    BA_CHECK(w.hyp_pose.alloc(RANSAC_HYP_DOUBLES * p->ncams * o.hypotheses));
     BA_CHECK(w.hyp_count.alloc(p->ncams * o.hypotheses));
     w.hyp_cap = o.hypotheses;
   }
@@ -586,7 +611,8 @@ static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opt
     BA_CHECK(launch_ransac_hypotheses(r, p->ncams, st));
     BA_CHECK(launch_ransac_select(r, p->ncams, st));
   }
-  CamArgs fit = a;  // the refits on the set: their poses live in a scratch copy of the cameras (the intrinsics are read from it)
+  // the refits on the set: their poses (focal mode: and f^) live in a scratch copy of the cameras (the intrinsics are read from it)
+  CamArgs fit = a;
   fit.info = w.rs_info, fit.xc = w.rs_cams;
   if (o.refits > 0)
     BA_HIP_CHECK(hipMemcpyAsync(w.rs_cams, a.xc, (size_t)(9 * p->ncams) * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -603,64 +629,76 @@ static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opt
   return launch_ransac_mask_info(r, p->nobs, w.rs_info, st);
 }
 
-// (ransac: the consensus stage, which leaves its set as information, then) (resect: k_resect_cameras, the start poses written
-// into d_x, then) k_refine_cameras, on st without a host synchronisation; the counters stay on the device (p->cams.counts)
-static int camera_launch(ba_problem *p, double *d_x, bool resect, const ba_ransac_opts *ransac, int max_iter, double xtol,
+// (ransac: the consensus stage, which leaves its set as information, then) (start != START_X: k_resect_cameras, the start poses
+// -- START_FOCAL: and focal lengths -- written into d_x, then) k_refine_cameras, on st without a host synchronisation; the
+// counters stay on the device (p->cams.counts)
+static int camera_launch(ba_problem *p, double *d_x, CamStart start, const ba_ransac_opts *ransac, int max_iter, double xtol,
                          double lambda0, uint8_t *d_status, double *d_cost, hipStream_t st) {
   BA_CHECK(terms_upload(p));
   BA_CHECK(camera_tables(p));
   CameraWork &w = p->cams;
   BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
   if (p->ncams == 0) return BA_OK;
-  if (resect && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
-  CamArgs a = camera_args(p, d_x, resect, max_iter, xtol, lambda0, d_status, d_cost);
+  if (start != START_X && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
+  CamArgs a = camera_args(p, d_x, start, max_iter, xtol, lambda0, d_status, d_cost);
   if (ransac) {
     BA_CHECK(ransac_consensus(p, a, *ransac, st));
     a.info = w.rs_info;
   }
-  if (resect) BA_CHECK(launch_resect(p, a, st));
+  if (start != START_X) BA_CHECK(launch_resect(p, a, st));
   return launch_refine(p, a, st);
 }
 
-static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, bool resect, int max_iter, double xtol, double lambda0,
+static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, CamStart start, int max_iter, double xtol, double lambda0,
                               uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, void *stream) {
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, resect, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, start, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
 
-static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, bool resect, int max_iter, double xtol, double lambda0,
+static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, CamStart start, int max_iter, double xtol, double lambda0,
                                uint8_t *status, double *cost, int64_t *counts, int *iters_max) {
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   // the cameras only: the point part of the caller's x is never written
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            return camera_launch(p, dx, resect, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st);
+                            return camera_launch(p, dx, start, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st);
                           });
 }
 
 extern "C" int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
                                      double *d_cost, int64_t *counts, int *iters_max, void *stream) {
-  return refine_cameras_dev("ba_refine_cameras_dev", p, d_x_inout, false, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+  return refine_cameras_dev("ba_refine_cameras_dev", p, d_x_inout, START_X, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
                             stream);
 }
 
 extern "C" int ba_refine_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
                                  double *cost, int64_t *counts, int *iters_max) {
-  return refine_cameras_host("ba_refine_cameras", p, x_inout, false, max_iter, xtol, lambda0, status, cost, counts, iters_max);
+  return refine_cameras_host("ba_refine_cameras", p, x_inout, START_X, max_iter, xtol, lambda0, status, cost, counts, iters_max);
 }
 
 extern "C" int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0, uint8_t *d_status,
                                      double *d_cost, int64_t *counts, int *iters_max, void *stream) {
-  return refine_cameras_dev("ba_resect_cameras_dev", p, d_x_inout, true, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+  return refine_cameras_dev("ba_resect_cameras_dev", p, d_x_inout, START_RESECT, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
                             stream);
 }
 
 extern "C" int ba_resect_cameras(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
                                  double *cost, int64_t *counts, int *iters_max) {
-  return refine_cameras_host("ba_resect_cameras", p, x_inout, true, max_iter, xtol, lambda0, status, cost, counts, iters_max);
+  return refine_cameras_host("ba_resect_cameras", p, x_inout, START_RESECT, max_iter, xtol, lambda0, status, cost, counts, iters_max);
+}
+
+extern "C" int ba_resect_cameras_focal_dev(ba_problem *p, double *d_x_inout, int max_iter, double xtol, double lambda0,
+                                           uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, void *stream) {
+  return refine_cameras_dev("ba_resect_cameras_focal_dev", p, d_x_inout, START_FOCAL, max_iter, xtol, lambda0, d_status, d_cost, counts,
+                            iters_max, stream);
+}
+
+extern "C" int ba_resect_cameras_focal(ba_problem *p, double *x_inout, int max_iter, double xtol, double lambda0, uint8_t *status,
+                                       double *cost, int64_t *counts, int *iters_max) {
+  return refine_cameras_host("ba_resect_cameras_focal", p, x_inout, START_FOCAL, max_iter, xtol, lambda0, status, cost, counts, iters_max);
 }
 
 // ---- ba_ransac_cameras: a consensus stage in front of ba_resect_cameras ------------------------------------------
@@ -700,30 +738,54 @@ static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, in
   return BA_OK;
 }
 
-extern "C" int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
-                                     double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
-                                     uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
-  const char *who = "ba_ransac_cameras_dev";
+static int ransac_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, CamStart start, const ba_ransac_opts *opts, int max_iter,
+                              double xtol, double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
+                              uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
   ba_ransac_opts o;
   BA_CHECK(ransac_opts_check(who, opts, &o));
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, true, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, start, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
   BA_CHECK(ransac_results(p, d_inlier, d_n_inliers, d_best_hyp, hipMemcpyDeviceToDevice, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
 
-extern "C" int ba_ransac_cameras(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
-                                 uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers,
-                                 int32_t *best_hyp) {
-  const char *who = "ba_ransac_cameras";
+static int ransac_cameras_host(const char *who, ba_problem *p, double *x_inout, CamStart start, const ba_ransac_opts *opts, int max_iter,
+                               double xtol, double lambda0, uint8_t *status, double *cost, int64_t *counts, int *iters_max,
+                               uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
   ba_ransac_opts o;
   BA_CHECK(ransac_opts_check(who, opts, &o));
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            BA_CHECK(camera_launch(p, dx, true, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+                            BA_CHECK(camera_launch(p, dx, start, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
                             return ransac_results(p, inlier, n_inliers, best_hyp, hipMemcpyDeviceToHost, st);
                           });
+}
+
+extern "C" int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
+    double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, uint8_t *d_inlier, int32_t *d_n_inliers,
+    int32_t *d_best_hyp, void *stream) {
+  return ransac_cameras_dev("ba_ransac_cameras_dev", p, d_x_inout, START_RESECT, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+                            d_inlier, d_n_inliers, d_best_hyp, stream);
+}
+
+extern "C" int ba_ransac_cameras(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
+    uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
+  return ransac_cameras_host("ba_ransac_cameras", p, x_inout, START_RESECT, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
+                             n_inliers, best_hyp);
+}
+
+extern "C" int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
+    double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, uint8_t *d_inlier, int32_t *d_n_inliers,
+    int32_t *d_best_hyp, void *stream) {
+  return ransac_cameras_dev("ba_ransac_cameras_focal_dev", p, d_x_inout, START_FOCAL, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+                            d_inlier, d_n_inliers, d_best_hyp, stream);
+}
+
+extern "C" int ba_ransac_cameras_focal(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
+    uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
+  return ransac_cameras_host("ba_ransac_cameras_focal", p, x_inout, START_FOCAL, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
+                             n_inliers, best_hyp);
 }

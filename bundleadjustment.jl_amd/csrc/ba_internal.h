@@ -375,14 +375,16 @@ struct RansacArgs {
   const double *pt2d, *info;  // info: the caller's l00 l10 l11 per observation, or null
   const uint16_t *mask;       // effective mask of held components per camera, or null
   const double *x, *xc;       // the whole vector (the points are read from it) and its camera part (the intrinsics)
-  double *hyp_pose;           // 6 per (camera, hypothesis)
+  double *hyp_pose;           // RANSAC_HYP_DOUBLES per (camera, hypothesis): r, t and the f it scores under
   int *hyp_count;             // inliers per (camera, hypothesis), -1: void
   uint8_t *inlier, *stopped;
   int *n_inliers, *best_hyp;
   int hypotheses, sample, min_inliers;
   uint64_t seed_mix;          // mix(seed)
   double tau2;
+  int focal;                  // a camera whose f is free estimates it per hypothesis (ba_ransac_cameras_focal)
 };
+constexpr int RANSAC_HYP_DOUBLES = 7;
 uint64_t ransac_seed_mix(uint64_t seed);  // mix(seed) of the header's sampling
 int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, hipStream_t st);
 int launch_ransac_select(const RansacArgs &a, int64_t ncams, hipStream_t st);

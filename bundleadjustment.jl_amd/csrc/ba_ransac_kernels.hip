@@ -13,6 +13,8 @@
 // a refit gives with the current one; k_ransac_mask_info hands the set to k_resect_cameras / k_refine_cameras as information.
 // All three kernels that test an observation call ransac_inlier, so a count never disagrees with the bytes.
 // No floating-point atomics, no integer ones either: every output has one writer.
+// Focal mode (RansacArgs.focal and the camera's f free; ba_ransac_cameras_focal): a hypothesis estimates f from its
+// own eigenvector and is scored under it -- its record carries that f, and the refits leave theirs in the scratch cameras.
 #include <cmath>
 
 #include "ba_internal.h"
@@ -52,19 +54,28 @@ __device__ __forceinline__ bool ransac_inlier(const RansacArgs &a, const double 
   return z1 < 0.0 && ex * ex + ey * ey <= a.tau2;
 }
 
-// cam_pre row of the camera (pose, the intrinsics of xc)
-__device__ __forceinline__ void pose_row(const double *pose, const double *xc, double P[12]) {
-  const double C9[9] = {pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], xc[6], xc[7], xc[8]};
+// cam_pre row of the camera (pose, k1, k2, f)
+__device__ __forceinline__ void pose_row(const double *pose, double k1, double k2, double f, double P[12]) {
+  const double C9[9] = {pose[0], pose[1], pose[2], pose[3], pose[4], pose[5], k1, k2, f};
   cam_pre<double>(C9, P);
 }
 
-// The pose of hypothesis h of camera c (list [k0, k1), intrinsics xc[6..8]) -> its cam_pre row P and pose[6]; false: void (too
-// few distinct used draws) or degenerate.  Called by a whole wave; the control flow is uniform over it.
-__device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScratch &sh, const double *xc, int h, int k0, int k1,
-                                                int lane, double pose[6], double P[12]) {
+// (k1, k2) a camera's hypotheses are undistorted with and scored under: those of xc; in focal mode, where nothing is undistorted,
+// a held one from xc and 0 for a free one (which is never read)
+__device__ __forceinline__ void scoring_distortion(const double *xc, bool focal, unsigned fm, double &k1, double &k2) {
+  k1 = (focal && !(fm & K1_HELD)) ? 0.0 : xc[6];
+  k2 = (focal && !(fm & K2_HELD)) ? 0.0 : xc[7];
+}
+
+// The pose of hypothesis h of camera c (list [k0, k1), intrinsics xc[6..8], mask fm) -> its cam_pre row P and pose[7]: r, t and
+// the f it is scored under -- that of xc, or in focal mode the estimate from the sample's own eigenvector; false:
+// void (too few distinct used draws) or degenerate.  Called by a whole wave; the control flow is uniform over it.
+__device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScratch &sh, const double *xc, bool focal, unsigned fm, int h,
+                                                int k0, int k1, int lane, double pose[RANSAC_HYP_DOUBLES], double P[12]) {
   const int d = k1 - k0, m = a.sample;
-  const double ck1 = xc[6], ck2 = xc[7], cf = xc[8];
-  if (d <= 0 || !isfinite(cf) || cf == 0.0) return false;
+  double ck1, ck2, cf = xc[8];  // (focal mode: cf is not used until the image scale takes its place)
+  scoring_distortion(xc, focal, fm, ck1, ck2);
+  if (d <= 0 || (!focal && (!isfinite(cf) || cf == 0.0))) return false;
   // the sample: lane j holds draw j; a draw counts unless its observation is not used or an earlier draw hit its position
   const uint64_t key = ransac_mix(a.seed_mix ^ (uint64_t)h);
   const int pos = (int)ransac_draw(key, lane, d);  // < d
@@ -79,12 +90,12 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScrat
   if (__popcll(taken) < m) return false;
   const bool take = accept && __popcll(taken & ((1ull << lane) - 1ull)) < m;
   const int first = __ffsll((long long)taken) - 1;  // the lane of the first accepted draw: the provisional origin
-  double X[3] = {0.0, 0.0, 0.0}, qx = 0.0, qy = 0.0;
+  double X[3] = {0.0, 0.0, 0.0}, mx = 0.0, my = 0.0;
   if (take) {
     const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
     X[0] = xp[0], X[1] = xp[1], X[2] = xp[2];
     const double2 mm = reinterpret_cast<const double2 *>(a.pt2d)[o];
-    undistort(mm.x / cf, mm.y / cf, ck1, ck2, qx, qy);
+    mx = mm.x, my = mm.y;
   }
   const double org[3] = {__shfl(X[0], first, 64), __shfl(X[1], first, 64), __shfl(X[2], first, 64)};
   // the mean of the sampled points and their RMS distance from it
@@ -98,9 +109,14 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScrat
   for (int i = 0; i < 4; i++) mo[i] = wave_all_sum(mo[i]);
   double dm[3], sc;
   if (!hartley_stats((double)m, mo, mo[3], dm, sc)) return false;
+  if (focal && !image_scale((double)m, wave_all_sum(mx * mx + my * my), cf)) return false;
   // the moments: a lane that takes no draw adds zeros
-  double hh[4] = {0.0, 0.0, 0.0, 0.0}, acc[RS_SUMS];
-  if (take) normalised_point(X, org, dm, sc, hh);
+  double hh[4] = {0.0, 0.0, 0.0, 0.0}, qx = 0.0, qy = 0.0, acc[RS_SUMS];
+  if (take) {
+    normalised_point(X, org, dm, sc, hh);
+    if (focal) qx = mx / cf, qy = my / cf;
+    else undistort(mx / cf, my / cf, ck1, ck2, qx, qy);
+  }
   moment_terms(hh, qx, qy, acc);
   bool ok = true;
 #pragma unroll
@@ -122,13 +138,14 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScrat
   const int front = __popcll(__ballot(take && front_z(sh.V, i1, hh) < 0.0));
   if (lane == 0) {
     const double sgn = 2 * front >= m ? 1.0 : -1.0;
-    sh.ok = pose_from_eigenvector(sh, i1, sgn, sc, org, dm) ? 1 : 0;
+    sh.ok = ((!focal || focal_from_eigenvector(sh, i1, cf)) && pose_from_eigenvector(sh, i1, sgn, sc, org, dm)) ? 1 : 0;
   }
   wave_sync();
   if (!sh.ok) return false;
   pose[0] = sh.r[0], pose[1] = sh.r[1], pose[2] = sh.r[2];
   pose[3] = sh.tr[0], pose[4] = sh.tr[1], pose[5] = sh.tr[2];
-  pose_row(pose, xc, P);
+  pose[6] = focal ? sh.f : cf;
+  pose_row(pose, ck1, ck2, pose[6], P);
   return true;
 }
 
@@ -137,12 +154,13 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses(RansacArgs a) {
   const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
   const int c = (int)blockIdx.x, h = (int)blockIdx.y * RN_WAVES + wv;
   if (h >= a.hypotheses) return;
-  if ((a.mask ? (unsigned)a.mask[c] : 0u) & POSE_MASK) return;  // not attempted: k_ransac_select reads nothing of it
+  const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  if (fm & POSE_MASK) return;  // not attempted: k_ransac_select reads nothing of it
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
   const int64_t slot = (int64_t)c * a.hypotheses + h;
-  double pose[6], P[12];
+  double pose[RANSAC_HYP_DOUBLES], P[12];
   int count = -1;
-  if (hypothesis_pose(a, shs[wv], a.xc + 9 * (int64_t)c, h, k0, k1, lane, pose, P)) {
+  if (hypothesis_pose(a, shs[wv], a.xc + 9 * (int64_t)c, focal_mode(a.focal, fm), fm, h, k0, k1, lane, pose, P)) {
     count = 0;
     for (int k = k0 + lane; k < k1; k += 64) count += ransac_inlier(a, P, a.cam_obs[k]) ? 1 : 0;
     count = wave_all_sum_int(count);
@@ -151,7 +169,7 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses(RansacArgs a) {
     a.hyp_count[slot] = count;
     if (count >= 0) {
 #pragma unroll
-      for (int i = 0; i < 6; i++) a.hyp_pose[6 * slot + i] = pose[i];
+      for (int i = 0; i < RANSAC_HYP_DOUBLES; i++) a.hyp_pose[RANSAC_HYP_DOUBLES * slot + i] = pose[i];
     }
   }
 }
@@ -172,7 +190,8 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
   __shared__ int red[RN_WAVES];
   const int t = (int)threadIdx.x, c = (int)blockIdx.x;
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
-  if ((a.mask ? (unsigned)a.mask[c] : 0u) & POSE_MASK) {
+  const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  if (fm & POSE_MASK) {
     int n = 0;
     for (int k = k0 + t; k < k1; k += RN_BLK) {
       const int o = a.cam_obs[k];
@@ -207,8 +226,10 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
     if (t == 0) a.n_inliers[c] = best_count, a.best_hyp[c] = best, a.stopped[c] = 1;
     return;
   }
-  double P[12];
-  pose_row(a.hyp_pose + 6 * ((int64_t)c * a.hypotheses + best), a.xc + 9 * (int64_t)c, P);
+  double P[12], ck1, ck2;  // the winner's row: its pose and the f it was scored under
+  const double *win = a.hyp_pose + RANSAC_HYP_DOUBLES * ((int64_t)c * a.hypotheses + best);
+  scoring_distortion(a.xc + 9 * (int64_t)c, focal_mode(a.focal, fm), fm, ck1, ck2);
+  pose_row(win, ck1, ck2, win[6], P);
   int n = 0;
   for (int k = k0 + t; k < k1; k += RN_BLK) {
     const int o = a.cam_obs[k];
@@ -220,8 +241,8 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
   if (t == 0) a.n_inliers[c] = n, a.best_hyp[c] = best, a.stopped[c] = 0;
 }
 
-// One camera per workgroup, after a refit on its set M wrote a pose into cams: M' = the inliers of the whole list under that
-// pose; adopted iff |M'| >= |M| and M' != M, otherwise (also when the refit found no pose) M stays and the camera stops.
+// One camera per workgroup, after a refit on its set M wrote a pose into cams (the scratch copy of the cameras: its intrinsics
+// are those of x, or in focal mode what the refit wrote): M' = the inliers of the whole list under that camera; adopted iff |M'| >= |M| and M' != M, otherwise (also when the refit found no pose) M stays and the camera stops.
 // Bit 1 of an inlier byte carries M' between the two passes; every thread rewrites the bytes it wrote.
 __global__ __launch_bounds__(RN_BLK) void k_ransac_rescore(RansacArgs a, const double *cams, const uint8_t *resect) {
   __shared__ int red[RN_WAVES];
@@ -234,7 +255,8 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_rescore(RansacArgs a, const d
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
   const int n_old = a.n_inliers[c];
   double P[12];
-  pose_row(cams + 9 * (int64_t)c, a.xc + 9 * (int64_t)c, P);
+  const double *cam = cams + 9 * (int64_t)c;
+  pose_row(cam, cam[6], cam[7], cam[8], P);
   int n = 0, diff = 0;
   for (int k = k0 + t; k < k1; k += RN_BLK) {
     const int o = a.cam_obs[k];

@@ -1,5 +1,5 @@
 // Device pieces shared by the block refinements (ba_point_kernels.hip, ba_camera_kernels.hip, ba_ransac_kernels.hip; DESIGN
-// §5j-§5m).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
+// §5j-§5n).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
 // The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
@@ -78,6 +78,7 @@ struct ResectScratch {
   double M[144], V[144];      // the normal matrix (its diagonal ends as the eigenvalues) and the accumulated rotations
   double W[9], V3[9], sg[3];  // the 3 x 3 block A and its one-sided Jacobi SVD: W -> U Sigma, V3, the singular values
   double U[9], R[9], r[3], tr[3];  // r: the rotation vector; tr: b, then the translation
+  double f;                   // focal mode: the estimate f^ = a phi
   int ok;
 };
 
@@ -266,6 +267,37 @@ __device__ __forceinline__ void rotation_vector(ResectScratch &sh) {
     const double kn = sqrt((sh.r[0] * sh.r[0] + sh.r[1] * sh.r[1]) + sh.r[2] * sh.r[2]);
     for (int j = 0; j < 3; j++) sh.r[j] = th * (sgn * sh.r[j] / kn);
   }
+}
+
+// ---- the focal mode of the linear resection: f is one more unknown ------------------------------------------------
+// The BAL principal point is the origin, so on raw measurements scaled by the image scale a = sqrt(sum |m|^2 / n), u = m / a,
+// the same two equations read phi P.x + u_x P.z = 0 and phi P.y + u_y P.z = 0 with phi = f / a: the same normal matrix with
+// q := u, whose eigenvector is gamma [phi A1; phi A2; A3 | phi b1, phi b2, b3].  The rows of A = R / s have one norm, which
+// gives phi from the three rows as found; with rows 1 and 2 divided by it the eigenvector is that of the calibrated case.
+constexpr unsigned FOCAL_HELD = 0x100u, K1_HELD = 0x40u, K2_HELD = 0x80u;  // in a camera's mask of held components
+
+// whether camera mask fm runs in focal mode under the call's flag: its f is free (a group member has the bit set)
+__device__ __forceinline__ bool focal_mode(int focal, unsigned fm) { return focal && !(fm & FOCAL_HELD); }
+
+// a from n and sum |m|^2; false: not finite or 0
+__device__ __forceinline__ bool image_scale(double n, double sm2, double &a) {
+  a = sqrt(sm2 / n);
+  return isfinite(a) && a != 0.0;
+}
+
+// phi = sqrt((|A1|^2 + |A2|^2) / (2 |A3|^2)) of eigenvector i1 of sh.V; rows 1 and 2 of [A | b] are divided by it in place and
+// f^ = a phi -> sh.f.  false: phi is not finite or not positive.  In front of pose_from_eigenvector.  (one lane)
+__device__ __forceinline__ bool focal_from_eigenvector(ResectScratch &sh, int i1, double a) {
+  double n2[3];
+  for (int i = 0; i < 3; i++) {
+    const double a0 = sh.V[(4 * i) * 12 + i1], a1 = sh.V[(4 * i + 1) * 12 + i1], a2 = sh.V[(4 * i + 2) * 12 + i1];
+    n2[i] = (a0 * a0 + a1 * a1) + a2 * a2;
+  }
+  const double phi = sqrt((n2[0] + n2[1]) / (2.0 * n2[2]));
+  if (!isfinite(phi) || !(phi > 0.0)) return false;
+  for (int e = 0; e < 8; e++) sh.V[e * 12 + i1] = sh.V[e * 12 + i1] / phi;
+  sh.f = a * phi;
+  return true;
 }
 
 // The pose from eigenvector i1 of sh.V = gamma [R / s | R m + t] under the sign sgn, with m = org + dm and s = sc: the rotation

@@ -305,7 +305,7 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
     return x, _block_info(status, cost, counts, its)
 
 
-def refine_cameras(nlp, x, *, resect=False, ransac=None, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
+def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
                    fixed_camera_params=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
     """The cameras of x with its points held (ba_refine_cameras), the other half of refine_points: every camera is an independent
     problem in at most 9 unknowns -- the objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info`, `camera_priors`
@@ -321,6 +321,12 @@ def refine_cameras(nlp, x, *, resect=False, ransac=None, max_iter=None, xtol=Non
     only -- the result has the bits of resect=True with an obs_info that drops the outliers.  A camera whose best hypothesis has
     fewer than `min_inliers` inliers is `degenerate`.  info then also holds `inliers` (bool, nobs), `n_inliers` and
     `best_hypothesis` (per camera; -1: not attempted or no valid hypothesis).
+    estimate_focal=True with resect=True (ba_resect_cameras_focal, with ransac ba_ransac_cameras_focal) registers images without
+    calibration: every camera whose pose and f are both free (f not in fixed_camera_params, the camera in no group of
+    shared_intrinsics) gets f from the linear stage along with its pose -- its (r, t, f) and free k1, k2 in x are not read, NaN
+    included; f is written into x_new, a free k1 / k2 starts the refinement at 0, a held one keeps its value and is ignored by
+    the linear stage.  Every hypothesis of the consensus stage then carries its own f.  A camera with f held or in a group is
+    resected with the intrinsics of x as without the flag.  On noisy data the linear f is only a start for the refinement.
     max_iter (None: 100; 0: evaluate only -- with resect=True the resected poses are returned), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
     D_j = sqrt(H_jj): the predicted motion in pixels), lam0 (None: 1e-4).  fixed_camera_params hold components (("k1", "k2",
     "f"): a pose-only refit); fixed_cameras are skipped; the members of the groups of shared_intrinsics keep their (k1, k2, f).
@@ -333,6 +339,11 @@ def refine_cameras(nlp, x, *, resect=False, ransac=None, max_iter=None, xtol=Non
                               shared_intrinsics=shared_intrinsics, obs_info=obs_info)
     if not isinstance(resect, (bool, np.bool_)):
         raise ValueError(f"resect must be True or False, got {resect!r}")
+    if not isinstance(estimate_focal, (bool, np.bool_)):
+        raise ValueError(f"estimate_focal must be True or False, got {estimate_focal!r}")
+    if estimate_focal and not resect:
+        raise ValueError("estimate_focal needs resect=True (the focal length comes out of the linear resection)")
+    focal = "_focal" if estimate_focal else ""
     opts = None
     if ransac is not None:
         if not resect:
@@ -344,10 +355,10 @@ def refine_cameras(nlp, x, *, resect=False, ransac=None, max_iter=None, xtol=Non
     counts, its = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64), C.c_int(0)
     if opts is not None:
         inlier, n_in, best = np.zeros(nlp.nobs, dtype=np.uint8), np.zeros(nlp.ncams, dtype=np.int32), np.zeros(nlp.ncams, dtype=np.int32)
-        _lib.check(_lib.lib().ba_ransac_cameras(nlp.handle, _lib.ptr(x), C.byref(opts), *args, _lib.ptr(status), _lib.ptr(cost),
+        _lib.check(getattr(_lib.lib(), "ba_ransac_cameras" + focal)(nlp.handle, _lib.ptr(x), C.byref(opts), *args, _lib.ptr(status), _lib.ptr(cost),
                                                 _lib.ptr(counts), C.byref(its), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best)))
         return x, dict(_block_info(status, cost, counts, its), inliers=inlier != 0, n_inliers=n_in, best_hypothesis=best)
-    entry = _lib.lib().ba_resect_cameras if resect else _lib.lib().ba_refine_cameras
+    entry = getattr(_lib.lib(), "ba_resect_cameras" + focal) if resect else _lib.lib().ba_refine_cameras
     _lib.check(entry(nlp.handle, _lib.ptr(x), *args, _lib.ptr(status), _lib.ptr(cost), _lib.ptr(counts), C.byref(its)))
     return x, _block_info(status, cost, counts, its)
 

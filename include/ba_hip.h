@@ -559,8 +559,8 @@ int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, i
  * the same bits; the next ba_lm_step / ba_lm_solve on the handle gives the same bits as without this call in between.  A handle
  * with a communicator is refused (BA_ERR_ARG).
  * Out of scope: outlier rejection inside the linear solve (the robust loss acts in the refinement; the consensus stage in front
- * of this entry is ba_ransac_cameras, below), unknown
- * intrinsics (a full 3 x 4 DLT with RQ), minimal P3P, Float32, several ranks, resection inside the LM loop. */
+ * of this entry is ba_ransac_cameras, below), unknown intrinsics beyond the focal length (an unknown f: ba_resect_cameras_focal,
+ * further down; a full 3 x 4 DLT with RQ is not provided), minimal P3P, Float32, several ranks, resection inside the LM loop. */
 int ba_resect_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
                       uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
                       int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
@@ -609,8 +609,8 @@ int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, i
  * on `stream`; it synchronises only to hand over counts / iters_max, as its sibling does.
  * Two calls give the same bits (no floating-point atomics); the next ba_lm_step / ba_lm_solve on the handle gives the same bits
  * as without the call.
- * Out of scope: an adaptive hypothesis count, MSAC / LO-RANSAC scoring, minimal P3P samples, unknown intrinsics, Float32,
- * several ranks. */
+ * Out of scope: an adaptive hypothesis count, MSAC / LO-RANSAC scoring, minimal P3P samples, unknown intrinsics beyond the focal
+ * length (an unknown f: ba_ransac_cameras_focal, further down), Float32, several ranks. */
 typedef struct ba_ransac_opts {
   double threshold;
   int hypotheses, sample, refits, min_inliers;
@@ -627,6 +627,65 @@ int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, c
                           int32_t *d_best_hyp /* ncams or NULL */, void *stream);
 int ba_ransac_sample(uint64_t seed, int hypothesis, int64_t degree, const uint8_t *used /* degree, or NULL: all */, int sample,
                      int64_t *pos /* sample */, int *n_taken);
+
+/* ---- camera resection with unknown focal length: linear stage and RANSAC (an extension) --------------------------------------
+ * ba_resect_cameras and ba_ransac_cameras for an image without calibration: f is estimated along with the pose.  The BAL
+ * principal point is the origin, so no general RQ decomposition is needed: the same 12 x 12 eigenproblem on raw pixels and one
+ * ratio of row norms afterwards.  Signatures, arguments, results, states, counts, defaults and refusals are those of the
+ * siblings (ba_ransac_opts unchanged); only what is said here differs.
+ * Which cameras run in focal mode: a camera whose pose is free (no mask bit 0..5 held) and whose f is free (mask bit 8 of
+ * ba_lm_set_fixed not held and the camera in no group of ba_lm_set_shared_intrinsics).  Every other camera is handled as the
+ * sibling handles it, in the same launch: a camera with all 9 components held is BA_PT_FIXED; a camera with a pose component
+ * held is not resected and starts from x; a camera with f held or in a group gets the calibrated resection of
+ * ba_resect_cameras, intrinsics read from x.  For a focal-mode camera the entries (r, t, f) of x are never read, nor are its
+ * free k1, k2: NaN is fine.
+ * The resection of a focal-mode camera c:
+ *  1. Every observation o of c with Lambda_o != 0 is used, unweighted, with its raw measurement m = pt2d.  The image scale is
+ *     a = sqrt(sum |m|^2 / n) over the n used observations; u = m / a.  The measurements are NOT centred: the principal point is
+ *     the origin and the structure diag(f, f, 1) must survive.  a not finite or 0: BA_PT_DEGENERATE.
+ *  2. The Hartley normalisation of the points, exactly as step 2 of ba_resect_cameras (sums about the first used point).
+ *  3. The 12 x 12 normal matrix of step 3 of ba_resect_cameras with q := u, its smallest eigenpair by the same Jacobi sweeps, and
+ *     the same degeneracy rules (fewer than 6 used observations; coinciding points; a moment that is not finite;
+ *     lambda_2 <= 1e-10 lambda_12).  No undistortion iterations run.
+ *  4. The eigenvector is gamma [phi A_1; phi A_2; A_3 | phi b_1, phi b_2, b_3] with [A | b] = [R / s | R m + t] and phi = f / a.
+ *     phi = sqrt((|A_1|^2 + |A_2|^2) / (2 |A_3|^2)) from the three rows as found; phi not finite or <= 0: BA_PT_DEGENERATE.
+ *     Rows 1 and 2 of A and b_1, b_2 are divided by phi; f^ = a phi.
+ *  5. Sign, nearest rotation, gamma, t and the rotation vector as steps 6-7 of ba_resect_cameras.
+ *  6. Written: the pose and f = f^; a free k1 or k2 is written as 0; a held k1 or k2 (mask bits 6, 7) keeps its bits -- the
+ *     linear stage ignores it (a limitation: with a large held distortion f^ and the pose are only a start for the
+ *     refinement).  A DEGENERATE camera comes back bit-unchanged, cost entries 0, no flag.
+ *  7. The Marquardt iteration of ba_refine_cameras runs unchanged from that camera: cost[2 c] is f_c at the camera just written;
+ *     max_iter == 0 returns the linear pose and f^ (state MAX_ITER); a camera whose cost there is not finite is NONFINITE and
+ *     keeps the written values.
+ * ba_ransac_cameras_focal: the consensus stage of ba_ransac_cameras with these changes.  Sampling: unchanged.  Hypothesis of a
+ * focal-mode camera: steps 1-5 on its m sampled observations in the order of their draws; it keeps its pose and its f^.  Inlier
+ * test: the model's own projection under (pose, k1', k2', f^), k' the held value from x or 0 if free.  Selection, ties,
+ * min_inliers and the refit rule: unchanged; the refits are focal resections on the current set into the scratch cameras,
+ * which then hold f^ and k', and the re-scoring reads the scratch camera's intrinsics.  Finish: ba_resect_cameras_focal with
+ * the observations outside the final set treated exactly as Lambda = 0.  x, status and cost equal, bit for bit, those of
+ * ba_resect_cameras_focal on the same handle whose information is the caller's with the outliers' entries set to 0.
+ * No floating-point atomics; two calls give the same bits; a camera's result depends on its own data and the order of its
+ * observations only; the next ba_lm_step / ba_lm_solve on the handle gives the same bits as without the call.  A handle with a
+ * communicator is refused (BA_ERR_ARG).  On noisy data the linear f^ is only a start (its relative error is 1e-2 at degree 255
+ * and can reach 0.7 at degree 6): the refinement behind it is what makes the estimate, as for the calibrated resection.
+ * Out of scope: k1 / k2 estimation in the linear stage, a principal point that is not the origin or a general K by RQ, a second
+ * calibrated pass after f^, minimal P3P or P4Pf solvers, MSAC or an adaptive hypothesis count, Float32, several ranks, the
+ * tied problem over a group. */
+int ba_resect_cameras_focal(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
+                            uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
+                            int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
+int ba_resect_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device */, int max_iter, double xtol, double lambda0,
+                                uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
+                                int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */, void *stream);
+int ba_ransac_cameras_focal(ba_problem *p, double *x_inout /* nvar, host */, const ba_ransac_opts *opts, int max_iter, double xtol,
+                            double lambda0, uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams or NULL */,
+                            int64_t *counts /* BA_PT_STATES + 1 or NULL */, int *iters_max /* or NULL */,
+                            uint8_t *inlier /* nobs or NULL */, int32_t *n_inliers /* ncams or NULL */, int32_t *best_hyp /* ncams or NULL */);
+int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device */, const ba_ransac_opts *opts /* host */,
+                                int max_iter, double xtol, double lambda0, uint8_t *d_status /* ncams or NULL */,
+                                double *d_cost /* 2 ncams or NULL */, int64_t *counts /* host, or NULL */,
+                                int *iters_max /* host, or NULL */, uint8_t *d_inlier /* nobs or NULL */,
+                                int32_t *d_n_inliers /* ncams or NULL */, int32_t *d_best_hyp /* ncams or NULL */, void *stream);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

@@ -236,3 +236,66 @@ function ransac_cameras_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypothes
                 Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
   return nothing
 end
+
+# camera resection with unknown focal length (an extension): include/ba_hip.h, ba_resect_cameras_focal / ba_ransac_cameras_focal.
+# resect_cameras! and ransac_cameras! for images without calibration: every camera whose pose and f are both free gets f from
+# the linear stage (and from every hypothesis) along with its pose -- its (r, t, f) and free k1, k2 in `x` are not read, NaN
+# included; f is written into `x`, a free k1 / k2 as 0 before the refinement.  A camera with f held or in a group is resected with
+# the intrinsics of `x`.  Arguments and return values are those of the siblings.
+function resect_cameras_focal!(nlp, x :: Vector{Float64}; max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  GC.@preserve x status cost counts begin
+    bacheck(ccall((:ba_resect_cameras_focal, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint}),
+                  nlp.handle, pointer(x), Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters))
+  end
+  return status, cost, counts, Int(iters[])
+end
+
+function resect_cameras_focal_dev!(nlp, d_x :: Ptr{Cvoid}; max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0,
+                                   d_status :: Ptr{Cvoid} = C_NULL, d_cost :: Ptr{Cvoid} = C_NULL, stream :: Ptr{Cvoid} = C_NULL)
+  bacheck(ccall((:ba_resect_cameras_focal_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint}, Ptr{Cvoid}),
+                nlp.handle, d_x, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), stream))
+  return nothing
+end
+
+function ransac_cameras_focal!(nlp, x :: Vector{Float64}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                               refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                               xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  inlier = zeros(UInt8, nlp.nobs)
+  n_inliers = zeros(Int32, nlp.ncams)
+  best_hyp = zeros(Int32, nlp.ncams)
+  GC.@preserve x status cost counts inlier n_inliers best_hyp begin
+    bacheck(ccall((:ba_ransac_cameras_focal, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, pointer(x), opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters, pointer(inlier), pointer(n_inliers), pointer(best_hyp)))
+  end
+  return status, cost, counts, Int(iters[]), inlier .!= 0, n_inliers, best_hyp
+end
+
+function ransac_cameras_focal_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                                   refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                                   xtol :: Real = -1.0, lam0 :: Real = -1.0, d_status :: Ptr{Cvoid} = C_NULL,
+                                   d_cost :: Ptr{Cvoid} = C_NULL, d_inlier :: Ptr{Cvoid} = C_NULL, d_n_inliers :: Ptr{Cvoid} = C_NULL,
+                                   d_best_hyp :: Ptr{Cvoid} = C_NULL, stream :: Ptr{Cvoid} = C_NULL)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  bacheck(ccall((:ba_ransac_cameras_focal_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                nlp.handle, d_x, opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
+  return nothing
+end

@@ -19,9 +19,14 @@ shapes, against the fixed-point LM solve on the same scene.
            refits and the final one) and of the refinement; the share of cameras whose mask equals the truth; and beside it the
            --resect row of the outlier-free scene from the same session.
 
+  --focal  with --resect (the default beside it) or --ransac: the _focal entries from an x0 whose cameras are NaN in all
+           nine entries -- f is estimated by the linear stage and by every hypothesis (m = 8).  The same clocks and event times,
+           and the relative error of f against the generator's cameras after the linear stage and after the refinement.
+
 One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (--resect: profiles/resect_cameras_bench.json,
---ransac: profiles/ransac_cameras_bench.json), or the file given.
-usage: python tools/bench_refine_cameras.py [--resect | --ransac] [out.json] [reps] [shape ...]"""
+--ransac: profiles/ransac_cameras_bench.json, --focal: profiles/resect_focal_bench.json, --focal --ransac:
+profiles/ransac_focal_bench.json), or the file given.
+usage: python tools/bench_refine_cameras.py [--resect | --ransac] [--focal] [out.json] [reps] [shape ...]"""
 import ctypes as C
 import json
 import os
@@ -90,8 +95,17 @@ def measure(ba, name, reps):
     return row
 
 
-def measure_resect(ba, name, reps):
+def focal_errors(x, p):
+    """relative error of f against the generator's cameras: median and largest over the cameras with a finite f"""
+    n, nc = p["npnts"], p["ncams"]
+    f, ft = x[3 * n:].reshape(nc, 9)[:, 8], np.asarray(p["x_true"])[3 * n:].reshape(nc, 9)[:, 8]
+    e = np.abs(f - ft)[np.isfinite(f)] / ft[np.isfinite(f)]
+    return {"median": float(np.median(e)), "max": float(e.max()), "cameras": int(e.size)}
+
+
+def measure_resect(ba, name, reps, focal=False):
     L, lib = ba._lib.lib(), ba._lib
+    entry = L.ba_resect_cameras_focal_dev if focal else L.ba_resect_cameras_dev
     p = ba.synthetic.make_named(name)
     n, nc, nvar = p["npnts"], p["ncams"], len(p["x0"])
     m = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(p))
@@ -99,22 +113,22 @@ def measure_resect(ba, name, reps):
     row = {"shape": name, "ncams": nc, "npnts": n, "nobs": p["nobs"], "xtol": XTOL, "degree_min": int(deg.min()),
            "degree_median": int(np.median(deg)), "degree_max": int(deg.max())}
     x0 = np.array(p["x0"], dtype=np.float64, copy=True)
-    x0[3 * n:].reshape(nc, 9)[:, :6] = np.nan
+    x0[3 * n:].reshape(nc, 9)[:, :(9 if focal else 6)] = np.nan
     d_x = C.c_void_p()
     lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
     counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
     lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
-    lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, lib.ptr(counts), C.byref(its), None))  # warm-up
+    lib.check(entry(m.handle, d_x, -1, XTOL, -1.0, None, None, lib.ptr(counts), C.byref(its), None))  # warm-up
     wall = []
     for _ in range(reps):
         lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
         t = time.perf_counter()
-        lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+        lib.check(entry(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
         lib.check(L.ba_synchronize(m.handle))
         wall.append(1e3 * (time.perf_counter() - t))
     m.profile(True)
     lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
-    lib.check(L.ba_resect_cameras_dev(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
+    lib.check(entry(m.handle, d_x, -1, XTOL, -1.0, None, None, None, None, None))
     prof = m.profile_get()
     m.profile(False)
     lib.check(L.ba_dev_free(m.handle, d_x))
@@ -123,8 +137,12 @@ def measure_resect(ba, name, reps):
                      "k_resect_cameras_event_ms": round(prof["k_resect_cameras"][0], 3),
                      "k_refine_cameras_event_ms": round(prof["k_refine_cameras"][0], 3), "iters_max": its.value,
                      "counts": {k: int(v) for k, v in zip(lib.POINT_STATES + ("behind",), counts)}}
-    _, info = ba.refine_cameras(m, x0, resect=True, xtol=XTOL)
+    x1, info = ba.refine_cameras(m, x0, resect=True, estimate_focal=focal, xtol=XTOL)
     _, info0 = ba.refine_cameras(m, p["x0"], xtol=XTOL)
+    if focal:
+        row["focal"] = True
+        row["f_error_linear"] = focal_errors(ba.refine_cameras(m, x0, resect=True, estimate_focal=True, max_iter=0)[0], p)
+        row["f_error_refined"] = focal_errors(x1, p)
     row["objective_resect"] = float(np.sum(info["cost_after"]))
     row["objective_at_resected_poses"] = float(np.sum(info["cost_before"]))
     row["objective_refine_from_x0"] = float(np.sum(info0["cost_after"]))
@@ -136,8 +154,10 @@ RANSAC = dict(threshold=4.0, hypotheses=128, sample=6, refits=2, seed=0)
 OUTLIER_FRACTION = 0.3
 
 
-def measure_ransac(ba, name, reps):
+def measure_ransac(ba, name, reps, focal=False):
     L, lib = ba._lib.lib(), ba._lib
+    entry = L.ba_ransac_cameras_focal_dev if focal else L.ba_ransac_cameras_dev
+    options = dict(RANSAC, sample=8) if focal else RANSAC
     p = ba.synthetic.make_named(name)
     n, nc, nvar, nobs = p["npnts"], p["ncams"], len(p["x0"]), p["nobs"]
     pt2d, is_out = ba.synthetic.add_outliers(p, fraction=OUTLIER_FRACTION, seed=1)
@@ -147,10 +167,10 @@ def measure_ransac(ba, name, reps):
     deg = np.bincount(cam0, minlength=nc)
     row = {"shape": name, "ncams": nc, "npnts": n, "nobs": nobs, "xtol": XTOL, "degree_min": int(deg.min()),
            "degree_median": int(np.median(deg)), "degree_max": int(deg.max()), "outlier_fraction": OUTLIER_FRACTION,
-           "outliers": int(is_out.sum()), "options": RANSAC}
+           "outliers": int(is_out.sum()), "options": options, "focal": focal}
     x0 = np.array(p["x_true"], dtype=np.float64, copy=True)  # the true points are held
-    x0[3 * n:].reshape(nc, 9)[:, :6] = np.nan
-    opts = lib.ransac_opts(RANSAC)
+    x0[3 * n:].reshape(nc, 9)[:, :(9 if focal else 6)] = np.nan
+    opts = lib.ransac_opts(options)
     d_x = C.c_void_p()
     lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
     counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
@@ -159,7 +179,7 @@ def measure_ransac(ba, name, reps):
     def call(cnt=None, it=None):
         lib.check(L.ba_memcpy_h2d(m.handle, d_x, lib.ptr(x0), 8 * nvar))
         t = time.perf_counter()
-        lib.check(L.ba_ransac_cameras_dev(m.handle, d_x, C.byref(opts), -1, XTOL, -1.0, None, None, cnt, it, *tail))
+        lib.check(entry(m.handle, d_x, C.byref(opts), -1, XTOL, -1.0, None, None, cnt, it, *tail))
         lib.check(L.ba_synchronize(m.handle))
         return 1e3 * (time.perf_counter() - t)
 
@@ -171,7 +191,7 @@ def measure_ransac(ba, name, reps):
     m.profile(False)
     lib.check(L.ba_dev_free(m.handle, d_x))
     med = statistics.median(wall)
-    x, info = ba.refine_cameras(m, x0, resect=True, ransac=RANSAC, xtol=XTOL)
+    x, info = ba.refine_cameras(m, x0, resect=True, estimate_focal=focal, ransac=options, xtol=XTOL)
     same = np.bincount(cam0, weights=(info["inliers"] != ~is_out).astype(float), minlength=nc) == 0
     C1, Ct = x[3 * n:].reshape(nc, 9), np.asarray(p["x_true"])[3 * n:].reshape(nc, 9)
     row["ransac"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall],
@@ -183,16 +203,21 @@ def measure_ransac(ba, name, reps):
                      "inliers_missed": int((~info["inliers"] & ~is_out).sum()), "outliers_kept": int((info["inliers"] & is_out).sum()),
                      "pose_error_rel_max": float(np.max(np.linalg.norm((C1 - Ct)[:, :6], axis=1) / np.linalg.norm(Ct[:, :6], axis=1))),
                      "objective": float(np.sum(info["cost_after"]))}
+    if focal:
+        row["f_error_refined"] = focal_errors(x, p)
     m.close()
-    row["resect_outlier_free"] = measure_resect(ba, name, reps)["resect"]
+    row["resect_outlier_free"] = measure_resect(ba, name, reps, focal)["resect"]
     return row
 
 
 def main():
     args = sys.argv[1:]
-    resect, ransac = "--resect" in args, "--ransac" in args
-    args = [a for a in args if a not in ("--resect", "--ransac")]
+    resect, ransac, focal = "--resect" in args, "--ransac" in args, "--focal" in args
+    resect = resect or (focal and not ransac)
+    args = [a for a in args if a not in ("--resect", "--ransac", "--focal")]
     default = "ransac_cameras_bench.json" if ransac else "resect_cameras_bench.json" if resect else "refine_cameras_bench.json"
+    if focal:
+        default = "ransac_focal_bench.json" if ransac else "resect_focal_bench.json"
     out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", default)
     reps = int(args.pop(0)) if args and args[0].isdigit() else 5
     shapes = args or ["dubrovnik-356", "venice-1778"]
@@ -201,7 +226,7 @@ def main():
         sys.exit("bench_refine_cameras: no HIP device visible (nothing is measured without one)")
     rows = []
     for name in shapes:
-        row = (measure_ransac if ransac else measure_resect if resect else measure)(ba, name, reps)
+        row = measure_ransac(ba, name, reps, focal) if ransac else measure_resect(ba, name, reps, focal) if resect else measure(ba, name, reps)
         print(json.dumps(row), flush=True)
         rows.append(row)
     with open(out, "w") as fh:
