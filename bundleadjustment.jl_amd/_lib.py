@@ -74,6 +74,7 @@ SYMBOLS = [
     "ba_refine_cameras", "ba_refine_cameras_dev", "ba_resect_cameras", "ba_resect_cameras_dev",
     "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
     "ba_resect_cameras_focal", "ba_resect_cameras_focal_dev", "ba_ransac_cameras_focal", "ba_ransac_cameras_focal_dev",
+    "ba_pair_matches", "ba_relative_pose",
 ]
 
 _lib = None
@@ -160,6 +161,8 @@ def lib():
     L.ba_ransac_cameras_focal.argtypes = L.ba_ransac_cameras.argtypes
     L.ba_ransac_cameras_focal_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
     L.ba_ransac_sample.argtypes = [C.c_uint64, C.c_int, i64, vp, C.c_int, vp, C.POINTER(C.c_int)]
+    L.ba_pair_matches.argtypes = [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.ba_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -557,10 +560,11 @@ POINT_BEHIND = 0x80
 RANSAC_KEYS = ("threshold", "hypotheses", "sample", "refits", "min_inliers", "seed")
 
 
-def ransac_opts(ransac):
+def ransac_opts(ransac, least=6):
     """RansacOpts of the dict `ransac` -- threshold (pixels, required), hypotheses (None or <= 0: 128; at most 4096), sample
     (None or <= 0: 6; 6..16), refits (None or < 0: 2; at most 8), min_inliers (None or <= 0: max(sample, 6); at least 6), seed
-    (0 .. 2^64 - 1, default 0) -- or ValueError, before any device call."""
+    (0 .. 2^64 - 1, default 0) -- or ValueError, before any device call.  least: the smallest sample and min_inliers of the
+    entry (6: the resection; 8: relative_pose, where it is also the default sample)."""
     if not isinstance(ransac, dict):
         raise ValueError(f"ransac must be a dict with the keys {', '.join(RANSAC_KEYS)} (or None), got {ransac!r}")
     unknown = [k for k in ransac if k not in RANSAC_KEYS]
@@ -584,12 +588,12 @@ def ransac_opts(ransac):
         ints[key] = int(v)
     if ints["hypotheses"] > 4096:
         raise ValueError(f"ransac: hypotheses must be <= 4096, got {ints['hypotheses']}")
-    if ints["sample"] > 0 and not 6 <= ints["sample"] <= 16:
-        raise ValueError(f"ransac: sample must lie in 6..16, got {ints['sample']}")
+    if ints["sample"] > 0 and not least <= ints["sample"] <= 16:
+        raise ValueError(f"ransac: sample must lie in {least}..16, got {ints['sample']}")
     if ints["refits"] > 8:
         raise ValueError(f"ransac: refits must be <= 8, got {ints['refits']}")
-    if 0 < ints["min_inliers"] < 6:
-        raise ValueError(f"ransac: min_inliers must be >= 6, got {ints['min_inliers']}")
+    if 0 < ints["min_inliers"] < least:
+        raise ValueError(f"ransac: min_inliers must be >= {least}, got {ints['min_inliers']}")
     if not 0 <= ints["seed"] < 1 << 64:
         raise ValueError(f"ransac: seed must lie in 0 .. 2^64 - 1, got {ints['seed']}")
     for key in ("hypotheses", "sample", "refits", "min_inliers"):
@@ -608,6 +612,96 @@ def ransac_sample(seed, hypothesis, degree, sample=6, used=None):
     check(lib().ba_ransac_sample(int(seed), int(hypothesis), int(degree), None if u is None else ptr(u), int(sample), ptr(pos), C.byref(n)))
     m = 6 if sample <= 0 else int(sample)
     return pos[:m].copy() if n.value == m else None
+
+
+# states of ba_relative_pose (BA_RP_*)
+PAIR_STATES = ("ok", "few_matches", "degenerate", "no_consensus")
+
+
+def _pairs(pairs, ncams=None):
+    """(a1, b1) int64 arrays of `pairs` (npairs, 2), 1-based cameras; ValueError for another shape, a dtype that is not integer, an
+    index below 1 (above ncams when given) or a pair of one camera"""
+    a = np.asarray(pairs)
+    if a.size == 0:
+        a = a.reshape(0, 2).astype(np.int64)
+    if a.ndim != 2 or a.shape[1] != 2 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"pairs must be an integer array of shape (npairs, 2) of 1-based cameras, got dtype {a.dtype}, shape {a.shape}")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 1 or (ncams is not None and a.max() > int(ncams))):
+        raise ValueError(f"pairs: 1-based cameras must lie in 1..{'ncams' if ncams is None else int(ncams)}, got {a.min()}..{a.max()}")
+    if (a[:, 0] == a[:, 1]).any():
+        raise ValueError("pairs: a pair holds two different cameras")
+    return np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
+
+
+def pair_matches(cam_idx1, pnt_idx1, ncams, npnts, pairs):
+    """The match lists of camera pairs (ba_pair_matches, host only): (match_ptr (npairs + 1), obs_a, obs_b), the observations
+    0-based.  The matches of pair (a, b) -- pairs[k], 1-based cameras -- are the points both cameras observe, ordered by a's list
+    (the caller's order), each with a's and b's first observation of the point."""
+    a1, b1 = _pairs(pairs, ncams)
+    cam = np.ascontiguousarray(cam_idx1, dtype=np.int64)
+    pnt = np.ascontiguousarray(pnt_idx1, dtype=np.int64)
+    if cam.ndim != 1 or cam.shape != pnt.shape:
+        raise ValueError(f"cam_idx1 and pnt_idx1 must be one-dimensional and of one length, got {cam.shape} and {pnt.shape}")
+    mp = np.zeros(len(a1) + 1, dtype=np.int64)
+    args = (int(ncams), int(npnts), len(cam), ptr(cam), ptr(pnt), len(a1), ptr(a1), ptr(b1), ptr(mp))
+    check(lib().ba_pair_matches(*args, None, None))
+    oa, ob = np.zeros(int(mp[-1]), dtype=np.int64), np.zeros(int(mp[-1]), dtype=np.int64)
+    check(lib().ba_pair_matches(*args, ptr(oa), ptr(ob)))
+    return mp, oa - 1, ob - 1
+
+
+def compose_relative(x, npnts, a, b, r, t, baseline=1.0):
+    """A copy of x (layout [points; cameras]) in which camera b (1-based) has the pose (R R_a, R t_a + baseline t) from camera a's
+    pose in x and the relative pose (r, t) of relative_pose: P_b = R P_a + baseline t.  The rotation vector is written by the rule
+    of the library's resection (theta < 1e-12: (1e-12, 0, 0)).  numpy, host only.  With camera a at the canonical pose
+    (r = (1e-12, 0, 0), t = 0) this seeds a reconstruction: camera b becomes (R, baseline t)."""
+    x = np.array(x, dtype=np.float64, copy=True)
+    npnts = int(npnts)
+    if x.ndim != 1 or (x.size - 3 * npnts) % 9 != 0 or x.size < 3 * npnts:
+        raise ValueError(f"compose_relative: x must have 3 npnts + 9 ncams entries, got {x.shape} with npnts = {npnts}")
+    ncams = (x.size - 3 * npnts) // 9
+    for c in (a, b):
+        if not isinstance(c, (int, np.integer)) or isinstance(c, (bool, np.bool_)) or not 1 <= c <= ncams:
+            raise ValueError(f"compose_relative: cameras are 1-based integers in 1..{ncams}, got {c!r}")
+    if a == b:
+        raise ValueError("compose_relative: a and b are two different cameras")
+    r, t = np.asarray(r, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    if r.shape != (3,) or t.shape != (3,):
+        raise ValueError(f"compose_relative: r and t must have shape (3,), got {r.shape} and {t.shape}")
+    cams = x[3 * npnts:].reshape(ncams, 9)
+
+    def rodrigues(v):
+        th = np.sqrt(v @ v)
+        k = v / th
+        K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        return np.cos(th) * np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * np.outer(k, k)
+
+    R = rodrigues(r)
+    Rb = R @ rodrigues(cams[a - 1, :3])
+    cams[b - 1, :3] = rotation_vector(Rb)
+    cams[b - 1, 3:6] = R @ cams[a - 1, 3:6] + float(baseline) * t
+    return x
+
+
+def rotation_vector(R):
+    """the rotation vector of a 3 x 3 rotation by the rule of the library's resection: theta = atan2(|w| / 2, (tr R - 1) / 2), w
+    the skew part, axis w / |w|; for cos theta < 0 the axis comes from the diagonal of R + I with the sign of w; theta < 1e-12:
+    (1e-12, 0, 0)"""
+    R = np.asarray(R, dtype=np.float64)
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    wn = np.sqrt(w @ w)
+    co = 0.5 * (np.trace(R) - 1.0)
+    th = np.arctan2(0.5 * wn, co)
+    if th < 1e-12:
+        return np.array([1e-12, 0.0, 0.0])
+    if co >= 0:
+        return th * w / wn
+    i = int(np.argmax(np.diag(R)))
+    ki = np.sqrt((R[i, i] - co) / (1.0 - co))
+    k = np.array([ki if j == i else 0.5 * (R[i, j] + R[j, i]) / ((1.0 - co) * ki) for j in range(3)])
+    k = k / np.sqrt(k @ k)
+    return th * (-k if k @ w < 0 else k)
 
 
 # the matrix of DESIGN §5h as Python sees it (the communicator and ba_covariance columns are the library's): per term the

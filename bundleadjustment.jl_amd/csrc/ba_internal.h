@@ -394,6 +394,43 @@ int launch_ransac_rescore(const RansacArgs &a, int64_t ncams, const double *cams
 // out (3 per observation) <- the caller's factors, or (1, 0, 1) when none is set, on the inliers; 0 elsewhere
 int launch_ransac_mask_info(const RansacArgs &a, int64_t nobs, double *out, hipStream_t st);
 
+// splitmix64: the one generator of the sampling (ba_ransac_sample), host and device
+__host__ __device__ inline uint64_t ransac_mix(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// list position of draw j of the hypothesis with key `key` in a list of d entries, d < 2^31
+__host__ __device__ inline int64_t ransac_draw(uint64_t key, int j, int64_t d) {
+  return (int64_t)(((ransac_mix(key ^ (uint64_t)j) >> 32) * (uint64_t)d) >> 32);
+}
+constexpr int RN_DRAWS = 64;  // draws per hypothesis: one per lane
+
+// ---- relative pose of camera pairs (ba_relative_pose; ba_pair_kernels.hip) -------------------------------------
+// The per-call device buffers (allocated at the first call, grown when a call needs more): per pair the first match of its
+// list, the six intrinsics (k1, k2, f of a, then of b), state, pose, set size, winner and "stopped" byte; per match its two
+// observations, its pair, the ray record (q_a, q_b, used: PAIR_RAY doubles) and the inlier byte; per (pair, hypothesis) the
+// pose (r, t) and the inlier count
+constexpr int PAIR_RAY = 5, PAIR_HYP_DOUBLES = 6;
+struct PairWork {
+  DevBuf<int> match_ptr, obs_a, obs_b, pair_of, hyp_count, n_inliers, best_hyp;
+  DevBuf<double> intr, rays, hyp_pose, pose;
+  DevBuf<uint8_t> inlier, stopped, status;
+  int64_t pair_cap = 0, match_cap = 0, hyp_cap = 0;
+};
+// what the kernels of ba_relative_pose work on
+struct PairArgs {
+  const int *match_ptr, *obs_a, *obs_b, *pair_of;
+  const double *intr, *pt2d, *info;  // info: the caller's l00 l10 l11 per observation, or null
+  double *rays, *hyp_pose, *pose;
+  int *hyp_count, *n_inliers, *best_hyp;
+  uint8_t *inlier, *stopped, *status;
+  int hypotheses, sample, min_inliers;  // hypotheses == 0: no consensus stage, the set is the used matches
+  uint64_t seed_mix;                    // mix(seed)
+  double tau2;
+};
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -460,6 +497,7 @@ struct ba_problem {
   bool info_on() const { return info_set; }
   PointWork pts;
   CameraWork cams;
+  PairWork pairs;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

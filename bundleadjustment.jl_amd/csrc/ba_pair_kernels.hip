@@ -1,0 +1,560 @@
+// Two-view relative pose (ba_pair_matches, ba_relative_pose; include/ba_hip.h, "relative pose of camera pairs").
+// gfx950 only.
+//
+// The host lists the matches of every pair (pair_match_lists: the points both cameras observe, ordered by camera a's list) and
+// uploads them with the six intrinsics of the pair; the poses and points of x never reach the device.
+// k_pair_rays: one lane per match undistorts both measurements ONCE into a 40-byte record (q_a, q_b, used): the H hypotheses of
+// a pair read that record and never repeat the 16 divisions per match.
+// k_pair_hypotheses: grid (pair, hypotheses / 4), ONE WAVE PER HYPOTHESIS on its own LDS slab (a PairScratch), the layout of
+// k_ransac_hypotheses: a wave draws its sample (one draw per lane), takes the 6 + 45 sums through wave_all_sum, runs the linear
+// fit of ba_refine_dev.h (jacobi12<wave_sync>: no workgroup barrier, a void or degenerate wave simply leaves) and counts the
+// inliers of the pair's whole list in a strided pass over the records.
+// k_pair_select (one workgroup per pair): the states that need no fit, the winner, its inlier bytes.
+// k_pair_fit (one workgroup per pair): the sums over the current set in a fixed order (strided partial sums per thread, the
+// butterfly of a wave, the four waves in order), the same linear fit, then either the re-scoring with the adopt rule of the
+// refits or, in the last launch, the returned pose.
+// All kernels that test a match call pair_inlier, so a count never disagrees with the bytes.  No atomics: every output has one
+// writer, two calls give the same bits.
+#include <cmath>
+
+#include "ba_internal.h"
+#include "ba_lm_internal.h"  // info_upload
+
+namespace {
+
+#include "ba_refine_dev.h"  // wave_all_sum, undistort, obs_used, jacobi12, the pieces of the linear fit
+
+constexpr int PR_BLK = 256, PR_WAVES = PR_BLK / 64;
+constexpr int PR_SAMPLE_MIN = 8, PR_SAMPLE_MAX = 16;
+
+__global__ __launch_bounds__(PR_BLK) void k_pair_rays(PairArgs a, int64_t nmatch) {
+  const int64_t k = (int64_t)blockIdx.x * PR_BLK + threadIdx.x;
+  if (k >= nmatch) return;
+  const double *in = a.intr + 6 * (int64_t)a.pair_of[k];
+  const int oa = a.obs_a[k], ob = a.obs_b[k];
+  const double2 ma = reinterpret_cast<const double2 *>(a.pt2d)[oa], mb = reinterpret_cast<const double2 *>(a.pt2d)[ob];
+  double *ray = a.rays + PAIR_RAY * k;
+  double qx, qy;
+  undistort(ma.x / in[2], ma.y / in[2], in[0], in[1], qx, qy);
+  ray[0] = qx, ray[1] = qy;
+  undistort(mb.x / in[5], mb.y / in[5], in[3], in[4], qx, qy);
+  ray[2] = qx, ray[3] = qy;
+  ray[4] = (obs_used(a.info, oa) && obs_used(a.info, ob)) ? 1.0 : 0.0;
+}
+
+// The linear fit of hypothesis h of a pair (matches [k0, k1), intrinsics in) -> sh.rs.r, sh.t; false: void (too few distinct used
+// draws) or degenerate.  Called by a whole wave; the control flow is uniform over it.
+__device__ __forceinline__ bool pair_hypothesis(const PairArgs &a, PairScratch &sh, const double *in, int h, int k0, int k1, int lane) {
+  const int d = k1 - k0, m = a.sample;
+  if (d <= 0 || !pair_focals_ok(in)) return false;
+  // the sample: lane j holds draw j; a draw counts unless its match is not used or an earlier draw hit its position
+  const uint64_t key = ransac_mix(a.seed_mix ^ (uint64_t)h);
+  const int pos = (int)ransac_draw(key, lane, d);  // < d
+  const double *ray = a.rays + PAIR_RAY * (int64_t)(k0 + pos);
+  bool accept = ray[4] != 0.0;
+#pragma nounroll
+  for (int i = 0; i < RN_DRAWS - 1; i++) {
+    const int pi = __shfl(pos, i, 64);
+    if (i < lane && pi == pos) accept = false;
+  }
+  const unsigned long long taken = __ballot(accept);
+  if (__popcll(taken) < m) return false;
+  const bool take = accept && __popcll(taken & ((1ull << lane) - 1ull)) < m;
+  const int first = __ffsll((long long)taken) - 1;  // the lane of the first accepted draw: the provisional origin
+  double qax = 0.0, qay = 0.0, qbx = 0.0, qby = 0.0;
+  if (take) qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
+  const double oa[2] = {__shfl(qax, first, 64), __shfl(qay, first, 64)}, ob[2] = {__shfl(qbx, first, 64), __shfl(qby, first, 64)};
+  // the mean of each image's points and their RMS distance from it
+  double mo[6] = {0, 0, 0, 0, 0, 0};
+  if (take) {
+    const double ax = qax - oa[0], ay = qay - oa[1], bx = qbx - ob[0], by = qby - ob[1];
+    mo[0] = ax, mo[1] = ay, mo[2] = ax * ax + ay * ay;
+    mo[3] = bx, mo[4] = by, mo[5] = bx * bx + by * by;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) mo[i] = wave_all_sum(mo[i]);
+  double dma[3], dmb[3], sa, sb;
+  if (!image_stats((double)m, mo[0], mo[1], mo[2], dma, sa) || !image_stats((double)m, mo[3], mo[4], mo[5], dmb, sb)) return false;
+  // the 45 sums: a lane that takes no draw adds zeros
+  double da[3] = {0.0, 0.0, 0.0}, db[3] = {0.0, 0.0, 0.0}, acc[EP_SUMS];
+  if (take) {
+    normalised_ray(qax, qay, oa, dma, sa, da);
+    normalised_ray(qbx, qby, ob, dmb, sb, db);
+  }
+  epipolar_terms(da, db, acc);
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < EP_SUMS; i++) {
+    acc[i] = wave_all_sum(acc[i]);
+    ok = ok && isfinite(acc[i]);
+  }
+  if (!ok) return false;
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < EP_SUMS; i++) sh.S[i] = acc[i];
+  }
+  wave_sync();
+  const double tr = epipolar_trace(sh.S);
+  for (int e = lane; e < 144; e += 64) sh.rs.M[e] = epipolar_matrix_entry(sh.S, tr, e);
+  jacobi12<wave_sync>(sh.rs.M, sh.rs.V, lane, 64);
+  int i1;
+  if (!smallest_eigenpair<9>(sh.rs.M, i1)) return false;
+  if (lane == 0) {
+    const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
+    essential_candidates(sh, i1, ca, sa, cb, sb);
+  }
+  wave_sync();
+  // the matches of the sample in front of both cameras, per candidate
+  int cnt[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    double al, be;
+    pair_depths(sh.Rc + 9 * (c >> 1), sh.tn, (c & 1) ? -1.0 : 1.0, qax, qay, qbx, qby, al, be);
+    cnt[c] = __popcll(__ballot(take && al > 0.0 && be > 0.0));
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) sh.cnt[c] = cnt[c];
+    sh.ok = pair_pose_winner(sh) ? 1 : 0;
+  }
+  wave_sync();
+  return sh.ok != 0;
+}
+
+__global__ __launch_bounds__(PR_BLK) void k_pair_hypotheses(PairArgs a) {
+  __shared__ PairScratch shs[PR_WAVES];  // one wave's slab each
+  const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+  const int pr = (int)blockIdx.x, h = (int)blockIdx.y * PR_WAVES + wv;
+  if (h >= a.hypotheses) return;
+  const int k0 = a.match_ptr[pr], k1 = a.match_ptr[pr + 1];
+  const double *in = a.intr + 6 * (int64_t)pr;
+  const int64_t slot = (int64_t)pr * a.hypotheses + h;
+  PairScratch &sh = shs[wv];
+  int count = -1;
+  if (pair_hypothesis(a, sh, in, h, k0, k1, lane)) {
+    PairPose P;
+    pair_pose_of(sh.rs.r, sh.t, P);
+    count = 0;
+    for (int k = k0 + lane; k < k1; k += 64) count += pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0;
+    count = wave_all_sum_int(count);
+    if (lane < 3) {
+      a.hyp_pose[PAIR_HYP_DOUBLES * slot + lane] = sh.rs.r[lane];
+      a.hyp_pose[PAIR_HYP_DOUBLES * slot + 3 + lane] = sh.t[lane];
+    }
+  }
+  if (lane == 0) a.hyp_count[slot] = count;
+}
+
+// the sum of v over the workgroup -> every thread (red: PR_WAVES ints; a barrier on either side)
+__device__ __forceinline__ int pair_block_sum_int(int v, int *red, int t) {
+  v = wave_all_sum_int(v);
+  __syncthreads();
+  if ((t & 63) == 0) red[t >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// a pair that ends here: its state, no inlier, n matches counted, winner h (or -1)
+__device__ __forceinline__ void pair_fails(const PairArgs &a, int pr, int k0, int k1, int t, int state, int n, int h) {
+  for (int k = k0 + t; k < k1; k += PR_BLK) a.inlier[k] = 0;
+  if (t == 0) a.status[pr] = (uint8_t)state, a.n_inliers[pr] = n, a.best_hyp[pr] = h, a.stopped[pr] = 1;
+}
+
+// One pair per workgroup: FEW_MATCHES (fewer than 8 used matches), DEGENERATE (a focal length that is not finite or 0), without
+// a consensus stage the set of the used matches, with one the winner among the hypotheses (the largest count, ties to the lowest
+// h; none, or a count below min_inliers: NO_CONSENSUS) and its inlier bytes.
+__global__ __launch_bounds__(PR_BLK) void k_pair_select(PairArgs a) {
+  __shared__ long long redk[PR_WAVES];
+  __shared__ int red[PR_WAVES];
+  const int t = (int)threadIdx.x, pr = (int)blockIdx.x;
+  const int k0 = a.match_ptr[pr], k1 = a.match_ptr[pr + 1];
+  const double *in = a.intr + 6 * (int64_t)pr;
+  int nu = 0;
+  for (int k = k0 + t; k < k1; k += PR_BLK) nu += a.rays[PAIR_RAY * (int64_t)k + 4] != 0.0 ? 1 : 0;
+  nu = pair_block_sum_int(nu, red, t);
+  if (nu < EP_MIN_MATCHES) return pair_fails(a, pr, k0, k1, t, BA_RP_FEW_MATCHES, 0, -1);
+  if (!pair_focals_ok(in)) return pair_fails(a, pr, k0, k1, t, BA_RP_DEGENERATE, 0, -1);
+  if (a.hypotheses == 0) {
+    for (int k = k0 + t; k < k1; k += PR_BLK) a.inlier[k] = a.rays[PAIR_RAY * (int64_t)k + 4] != 0.0 ? 1 : 0;
+    if (t == 0) a.status[pr] = BA_RP_OK, a.n_inliers[pr] = nu, a.best_hyp[pr] = -1, a.stopped[pr] = 0;
+    return;
+  }
+  // key = (count + 1) << 12 | (4095 - h): the largest key is the largest count at the lowest h; 0: no valid hypothesis
+  long long key = 0;
+  for (int h = t; h < a.hypotheses; h += PR_BLK) {
+    const int cnt = a.hyp_count[(int64_t)pr * a.hypotheses + h];
+    if (cnt >= 0) {
+      const long long kk = ((long long)(cnt + 1) << 12) | (long long)(4095 - h);
+      key = kk > key ? kk : key;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long other = __shfl_xor(key, off, 64);
+    key = other > key ? other : key;
+  }
+  if ((t & 63) == 0) redk[t >> 6] = key;
+  __syncthreads();
+  for (int w = 0; w < PR_WAVES; w++) key = redk[w] > key ? redk[w] : key;
+  const int best = key ? 4095 - (int)(key & 4095) : -1, best_count = key ? (int)(key >> 12) - 1 : 0;
+  if (!key || best_count < a.min_inliers) return pair_fails(a, pr, k0, k1, t, BA_RP_NO_CONSENSUS, best_count, best);
+  const double *win = a.hyp_pose + PAIR_HYP_DOUBLES * ((int64_t)pr * a.hypotheses + best);
+  PairPose P;
+  pair_pose_of(win, win + 3, P);
+  int n = 0;
+  for (int k = k0 + t; k < k1; k += PR_BLK) {
+    const int in_ = pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0;
+    a.inlier[k] = (uint8_t)in_;
+    n += in_;
+  }
+  n = pair_block_sum_int(n, red, t);
+  if (t == 0) a.status[pr] = BA_RP_OK, a.n_inliers[pr] = n, a.best_hyp[pr] = best, a.stopped[pr] = 0;
+}
+
+// the LDS of k_pair_fit: the fit's scratch, the four waves' partial sums, the first match of the set
+struct PairFitShared {
+  PairScratch ps;
+  double part[PR_WAVES][EP_SUMS];
+  double st[6];
+  int red[PR_WAVES];
+};
+
+// part[wave][i] <- the wave's sum of v (every lane passes its partial sum); the caller puts a barrier behind the last of them
+__device__ __forceinline__ void pair_wave_part(PairFitShared &sh, int i, double v, int t) {
+  v = wave_all_sum(v);
+  if ((t & 63) == 0) sh.part[t >> 6][i] = v;
+}
+
+// One pair per workgroup: the linear fit on its current set M (the inlier bytes).  final == 0, a round of the refits: M' = the
+// inliers of the whole list under the fit; adopted iff |M'| >= |M| and M' != M, otherwise (also when the fit is degenerate) M
+// stays and the pair stops.  Bit 1 of an inlier byte carries M' between the two passes; every thread rewrites the bytes it wrote.
+// final != 0: the pose of the fit -> a.pose, or the state DEGENERATE.
+__global__ __launch_bounds__(PR_BLK) void k_pair_fit(PairArgs a, int final) {
+  __shared__ PairFitShared sh;
+  const int t = (int)threadIdx.x, pr = (int)blockIdx.x;
+  if (a.status[pr] != BA_RP_OK || (!final && a.stopped[pr])) return;
+  const int k0 = a.match_ptr[pr], k1 = a.match_ptr[pr + 1];
+  const double *in = a.intr + 6 * (int64_t)pr;
+  const int n_old = a.n_inliers[pr];
+  PairScratch &ps = sh.ps;
+  // the first match of the set: the provisional origin
+  int first = k1;
+  for (int k = k0 + t; k < k1; k += PR_BLK)
+    if ((a.inlier[k] & 1) && k < first) first = k;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const int other = __shfl_xor(first, off, 64);
+    first = other < first ? other : first;
+  }
+  if ((t & 63) == 0) sh.red[t >> 6] = first;
+  __syncthreads();
+  for (int w = 0; w < PR_WAVES; w++) first = sh.red[w] < first ? sh.red[w] : first;
+  bool ok = first < k1;  // (every decision below is taken on values all threads share)
+  double oa[2] = {0.0, 0.0}, ob[2] = {0.0, 0.0}, dma[3], dmb[3], sa = 0.0, sb = 0.0;
+  if (ok) {
+    const double *r0 = a.rays + PAIR_RAY * (int64_t)first;
+    oa[0] = r0[0], oa[1] = r0[1], ob[0] = r0[2], ob[1] = r0[3];
+    double mo[6] = {0, 0, 0, 0, 0, 0};
+    for (int k = k0 + t; k < k1; k += PR_BLK)
+      if (a.inlier[k] & 1) {
+        const double *ray = a.rays + PAIR_RAY * (int64_t)k;
+        const double ax = ray[0] - oa[0], ay = ray[1] - oa[1], bx = ray[2] - ob[0], by = ray[3] - ob[1];
+        mo[0] += ax, mo[1] += ay, mo[2] += ax * ax + ay * ay;
+        mo[3] += bx, mo[4] += by, mo[5] += bx * bx + by * by;
+      }
+#pragma unroll
+    for (int i = 0; i < 6; i++) pair_wave_part(sh, i, mo[i], t);
+    __syncthreads();
+    if (t < 6) sh.st[t] = ((sh.part[0][t] + sh.part[1][t]) + sh.part[2][t]) + sh.part[3][t];
+    __syncthreads();
+    ok = image_stats((double)n_old, sh.st[0], sh.st[1], sh.st[2], dma, sa) && image_stats((double)n_old, sh.st[3], sh.st[4], sh.st[5], dmb, sb);
+  }
+  if (ok) {
+    double acc[EP_SUMS];
+#pragma unroll
+    for (int i = 0; i < EP_SUMS; i++) acc[i] = 0.0;
+    for (int k = k0 + t; k < k1; k += PR_BLK)
+      if (a.inlier[k] & 1) {
+        const double *ray = a.rays + PAIR_RAY * (int64_t)k;
+        double da[3], db[3], term[EP_SUMS];
+        normalised_ray(ray[0], ray[1], oa, dma, sa, da);
+        normalised_ray(ray[2], ray[3], ob, dmb, sb, db);
+        epipolar_terms(da, db, term);
+#pragma unroll
+        for (int i = 0; i < EP_SUMS; i++) acc[i] += term[i];
+      }
+#pragma unroll
+    for (int i = 0; i < EP_SUMS; i++) pair_wave_part(sh, i, acc[i], t);
+    __syncthreads();
+    if (t < EP_SUMS) ps.S[t] = ((sh.part[0][t] + sh.part[1][t]) + sh.part[2][t]) + sh.part[3][t];
+    __syncthreads();
+    for (int i = 0; i < EP_SUMS; i++) ok = ok && isfinite(ps.S[i]);
+  }
+  if (ok) {
+    const double tr = epipolar_trace(ps.S);
+    for (int e = t; e < 144; e += PR_BLK) ps.rs.M[e] = epipolar_matrix_entry(ps.S, tr, e);
+    jacobi12<__syncthreads>(ps.rs.M, ps.rs.V, t, PR_BLK);
+    int i1;
+    ok = smallest_eigenpair<9>(ps.rs.M, i1);
+    if (ok) {
+      if (t == 0) {
+        const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
+        essential_candidates(ps, i1, ca, sa, cb, sb);
+      }
+      __syncthreads();
+      int cnt[4] = {0, 0, 0, 0};
+      for (int k = k0 + t; k < k1; k += PR_BLK)
+        if (a.inlier[k] & 1) {
+          const double *ray = a.rays + PAIR_RAY * (int64_t)k;
+#pragma unroll
+          for (int c = 0; c < 4; c++) {
+            double al, be;
+            pair_depths(ps.Rc + 9 * (c >> 1), ps.tn, (c & 1) ? -1.0 : 1.0, ray[0], ray[1], ray[2], ray[3], al, be);
+            cnt[c] += (al > 0.0 && be > 0.0) ? 1 : 0;
+          }
+        }
+#pragma unroll
+      for (int c = 0; c < 4; c++) cnt[c] = pair_block_sum_int(cnt[c], sh.red, t);
+      if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) ps.cnt[c] = cnt[c];
+        ps.ok = pair_pose_winner(ps) ? 1 : 0;
+      }
+      __syncthreads();
+      ok = ps.ok != 0;
+    }
+  }
+  if (final) {
+    if (t == 0 && !ok) a.status[pr] = BA_RP_DEGENERATE;
+    if (ok && t < 3) a.pose[6 * (int64_t)pr + t] = ps.rs.r[t], a.pose[6 * (int64_t)pr + 3 + t] = ps.t[t];
+    return;
+  }
+  if (!ok) {
+    if (t == 0) a.stopped[pr] = 1;
+    return;
+  }
+  PairPose P;
+  pair_pose_of(ps.rs.r, ps.t, P);
+  int n = 0, diff = 0;
+  for (int k = k0 + t; k < k1; k += PR_BLK) {
+    const int in_ = pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0, old = a.inlier[k] & 1;
+    a.inlier[k] = (uint8_t)(old | (in_ << 1));
+    n += in_;
+    diff += in_ != old ? 1 : 0;
+  }
+  n = pair_block_sum_int(n, sh.red, t);
+  diff = pair_block_sum_int(diff, sh.red, t);
+  const bool adopt = n >= n_old && diff > 0;
+  for (int k = k0 + t; k < k1; k += PR_BLK) {
+    const int b = a.inlier[k];
+    a.inlier[k] = (uint8_t)(adopt ? (b >> 1) & 1 : b & 1);
+  }
+  if (t == 0) {
+    if (adopt) a.n_inliers[pr] = n;
+    else a.stopped[pr] = 1;
+  }
+}
+
+// The match lists of the pairs (a, b) (1-based) over the observation lists cam / pnt (indices with the given base): the walk of
+// the header.  ptr: npairs + 1 offsets; oa, ob (either both or neither): the 0-based observations of every match.
+// BA_ERR_ARG (message with `who`): a pair with a == b or an index outside 1..ncams, an observation index out of range.
+template <typename I>
+int pair_match_lists(const char *who, int64_t ncams, int64_t npnts, int64_t nobs, const I *cam, const I *pnt, int64_t base, int64_t npairs,
+                     const int64_t *pair_a1, const int64_t *pair_b1, std::vector<int64_t> &ptr, std::vector<int64_t> *oa, std::vector<int64_t> *ob) {
+  for (int64_t k = 0; k < nobs; k++) {
+    const int64_t c = (int64_t)cam[k] - base, q = (int64_t)pnt[k] - base;
+    if (c < 0 || c >= ncams || q < 0 || q >= npnts) {
+      ba_set_error("%s: observation %lld has a camera or point index out of range", who, (long long)k + 1);
+      return BA_ERR_ARG;
+    }
+  }
+  for (int64_t i = 0; i < npairs; i++)
+    if (pair_a1[i] < 1 || pair_a1[i] > ncams || pair_b1[i] < 1 || pair_b1[i] > ncams || pair_a1[i] == pair_b1[i]) {
+      ba_set_error("%s: pair %lld is (%lld, %lld): two different cameras in 1..%lld", who, (long long)i + 1, (long long)pair_a1[i],
+                   (long long)pair_b1[i], (long long)ncams);
+      return BA_ERR_ARG;
+    }
+  // every camera's observations in the caller's order
+  std::vector<int64_t> cptr((size_t)ncams + 1, 0), cobs((size_t)nobs);
+  for (int64_t k = 0; k < nobs; k++) cptr[(size_t)((int64_t)cam[k] - base) + 1]++;
+  for (int64_t c = 0; c < ncams; c++) cptr[(size_t)c + 1] += cptr[(size_t)c];
+  {
+    std::vector<int64_t> at(cptr.begin(), cptr.end() - 1);
+    for (int64_t k = 0; k < nobs; k++) cobs[(size_t)at[(size_t)((int64_t)cam[k] - base)]++] = k;
+  }
+  // seen_a[P] / seen_b[P] == i + 1: pair i has met point P in that camera's list; first_b[P]: b's first observation of it
+  std::vector<int64_t> seen_a((size_t)npnts, 0), seen_b((size_t)npnts, 0), first_b((size_t)npnts, 0);
+  ptr.assign((size_t)npairs + 1, 0);
+  for (int64_t i = 0; i < npairs; i++) {
+    const int64_t ca = pair_a1[i] - 1, cb = pair_b1[i] - 1;
+    for (int64_t j = cptr[(size_t)cb]; j < cptr[(size_t)cb + 1]; j++) {
+      const int64_t o = cobs[(size_t)j], q = (int64_t)pnt[o] - base;
+      if (seen_b[(size_t)q] != i + 1) seen_b[(size_t)q] = i + 1, first_b[(size_t)q] = o;
+    }
+    int64_t n = 0;
+    for (int64_t j = cptr[(size_t)ca]; j < cptr[(size_t)ca + 1]; j++) {
+      const int64_t o = cobs[(size_t)j], q = (int64_t)pnt[o] - base;
+      if (seen_a[(size_t)q] == i + 1) continue;
+      seen_a[(size_t)q] = i + 1;
+      if (seen_b[(size_t)q] != i + 1) continue;
+      n++;
+      if (oa) oa->push_back(o), ob->push_back(first_b[(size_t)q]);
+    }
+    ptr[(size_t)i + 1] = ptr[(size_t)i] + n;
+  }
+  return BA_OK;
+}
+
+// The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message
+int pair_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o) {
+  *o = *in;
+  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
+    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
+    return BA_ERR_ARG;
+  }
+  if (o->hypotheses <= 0) o->hypotheses = 128;
+  if (o->sample <= 0) o->sample = PR_SAMPLE_MIN;
+  if (o->refits < 0) o->refits = 2;
+  if (o->hypotheses > 4096 || o->sample < PR_SAMPLE_MIN || o->sample > PR_SAMPLE_MAX || o->refits > 8) {
+    ba_set_error("%s: hypotheses must be <= 4096, sample in %d..%d, refits <= 8, got %d, %d, %d", who, PR_SAMPLE_MIN, PR_SAMPLE_MAX,
+                 o->hypotheses, o->sample, o->refits);
+    return BA_ERR_ARG;
+  }
+  if (o->min_inliers <= 0) o->min_inliers = o->sample > EP_MIN_MATCHES ? o->sample : EP_MIN_MATCHES;
+  if (o->min_inliers < EP_MIN_MATCHES) {
+    ba_set_error("%s: min_inliers must be >= %d (<= 0: max(sample, %d)), got %d", who, EP_MIN_MATCHES, EP_MIN_MATCHES, o->min_inliers);
+    return BA_ERR_ARG;
+  }
+  return BA_OK;
+}
+
+// d <- h (n elements, d holds at least n) on st; the host vector outlives the call's synchronisation
+template <typename T>
+int pair_upload(T *d, const std::vector<T> &h, hipStream_t st) {
+  if (!h.empty()) BA_HIP_CHECK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  return BA_OK;
+}
+
+// the buffers of a call with npairs pairs, nmatch matches and H hypotheses per pair: grown, never shrunk
+int pair_buffers(PairWork &w, int64_t npairs, int64_t nmatch, int64_t H) {
+  if (w.pair_cap < npairs) {
+    w.pair_cap = 0;
+    BA_CHECK(w.match_ptr.alloc(npairs + 1));
+    BA_CHECK(w.intr.alloc(6 * npairs));
+    BA_CHECK(w.pose.alloc(6 * npairs));
+    BA_CHECK(w.n_inliers.alloc(npairs));
+    BA_CHECK(w.best_hyp.alloc(npairs));
+    BA_CHECK(w.stopped.alloc(npairs));
+    BA_CHECK(w.status.alloc(npairs));
+    w.pair_cap = npairs;
+    w.hyp_cap = 0;  // (the hypothesis records are per pair)
+  }
+  if (w.match_cap < nmatch || !w.rays) {
+    w.match_cap = 0;
+    BA_CHECK(w.obs_a.alloc(nmatch));
+    BA_CHECK(w.obs_b.alloc(nmatch));
+    BA_CHECK(w.pair_of.alloc(nmatch));
+    BA_CHECK(w.rays.alloc(PAIR_RAY * nmatch));
+    BA_CHECK(w.inlier.alloc(nmatch));
+    w.match_cap = nmatch;
+  }
+  if (w.hyp_cap < w.pair_cap * H) {
+    w.hyp_cap = 0;
+    BA_CHECK(w.hyp_pose.alloc(PAIR_HYP_DOUBLES * w.pair_cap * H));
+    BA_CHECK(w.hyp_count.alloc(w.pair_cap * H));
+    w.hyp_cap = w.pair_cap * H;
+  }
+  return BA_OK;
+}
+
+}  // namespace
+
+extern "C" int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1, int64_t npairs,
+                               const int64_t *pair_a1, const int64_t *pair_b1, int64_t *match_ptr, int64_t *obs_a1, int64_t *obs_b1) {
+  if (ncams < 0 || npnts < 0 || nobs < 0 || npairs < 0 || (nobs > 0 && (!cam_idx1 || !pnt_idx1)) || (npairs > 0 && (!pair_a1 || !pair_b1)) ||
+      !match_ptr || (obs_a1 == nullptr) != (obs_b1 == nullptr)) {
+    ba_set_error("ba_pair_matches: null argument or negative size (obs_a1 and obs_b1: both or neither)");
+    return BA_ERR_ARG;
+  }
+  std::vector<int64_t> ptr, oa, ob;
+  BA_CHECK(pair_match_lists("ba_pair_matches", ncams, npnts, nobs, cam_idx1, pnt_idx1, 1, npairs, pair_a1, pair_b1, ptr, obs_a1 ? &oa : nullptr,
+                            obs_a1 ? &ob : nullptr));
+  for (size_t i = 0; i < ptr.size(); i++) match_ptr[i] = ptr[i];
+  for (size_t k = 0; k < oa.size(); k++) obs_a1[k] = oa[k] + 1, obs_b1[k] = ob[k] + 1;
+  return BA_OK;
+}
+
+extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                const ba_ransac_opts *opts, double *pose, uint8_t *status, int64_t *match_ptr, uint8_t *inlier,
+                                int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
+  const char *who = "ba_relative_pose";
+  ba_ransac_opts o = {};
+  if (opts) BA_CHECK(pair_opts_check(who, opts, &o));
+  if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !pose || !status))) {
+    ba_set_error("%s: null argument or npairs < 0", who);
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
+    return BA_ERR_ARG;
+  }
+  std::vector<int64_t> ptr, oa, ob;
+  BA_CHECK(pair_match_lists(who, p->ncams, p->npnts, p->nobs, p->h_cam0.data(), p->h_pnt0.data(), 0, npairs, pair_a1, pair_b1, ptr, &oa, &ob));
+  const int64_t nmatch = ptr[(size_t)npairs];
+  if (nmatch > (int64_t)INT32_MAX) {
+    ba_set_error("%s: %lld matches: more than 2^31 - 1", who, (long long)nmatch);
+    return BA_ERR_ARG;
+  }
+  if (match_ptr)
+    for (size_t i = 0; i < ptr.size(); i++) match_ptr[i] = ptr[i];
+  if (counts)
+    for (int s = 0; s < BA_RP_STATES; s++) counts[s] = 0;
+  if (npairs == 0) return BA_OK;
+  // what the device reads: the lists as int32 and the six intrinsics of every pair
+  std::vector<int> h_ptr(ptr.begin(), ptr.end()), h_oa(oa.begin(), oa.end()), h_ob(ob.begin(), ob.end()), h_pair((size_t)nmatch);
+  std::vector<double> h_intr((size_t)(6 * npairs));
+  for (int64_t i = 0; i < npairs; i++) {
+    for (int64_t k = ptr[(size_t)i]; k < ptr[(size_t)i + 1]; k++) h_pair[(size_t)k] = (int)i;
+    const double *ca = x + 3 * p->npnts + 9 * (pair_a1[i] - 1), *cb = x + 3 * p->npnts + 9 * (pair_b1[i] - 1);
+    for (int j = 0; j < 3; j++) h_intr[(size_t)(6 * i + j)] = ca[6 + j], h_intr[(size_t)(6 * i + 3 + j)] = cb[6 + j];
+  }
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  BA_CHECK(info_upload(p));
+  PairWork &w = p->pairs;
+  BA_CHECK(pair_buffers(w, npairs, nmatch, opts ? o.hypotheses : 0));
+  BA_CHECK(pair_upload((int *)w.match_ptr, h_ptr, st));
+  BA_CHECK(pair_upload((int *)w.obs_a, h_oa, st));
+  BA_CHECK(pair_upload((int *)w.obs_b, h_ob, st));
+  BA_CHECK(pair_upload((int *)w.pair_of, h_pair, st));
+  BA_CHECK(pair_upload((double *)w.intr, h_intr, st));
+  PairArgs a;
+  a.match_ptr = w.match_ptr, a.obs_a = w.obs_a, a.obs_b = w.obs_b, a.pair_of = w.pair_of;
+  a.intr = w.intr, a.pt2d = p->pt2d, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
+  a.rays = w.rays, a.hyp_pose = w.hyp_pose, a.pose = w.pose;
+  a.hyp_count = w.hyp_count, a.n_inliers = w.n_inliers, a.best_hyp = w.best_hyp;
+  a.inlier = w.inlier, a.stopped = w.stopped, a.status = w.status;
+  a.hypotheses = opts ? o.hypotheses : 0, a.sample = o.sample, a.min_inliers = o.min_inliers;
+  a.seed_mix = ransac_seed_mix(o.seed), a.tau2 = o.threshold * o.threshold;
+  BA_CHECK(BA_LAUNCH(k_pair_rays, grid_for(nmatch, PR_BLK), PR_BLK, 0, st, a, nmatch));
+  if (opts) BA_CHECK(BA_LAUNCH(k_pair_hypotheses, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
+  BA_CHECK(BA_LAUNCH(k_pair_select, (unsigned)npairs, PR_BLK, 0, st, a));
+  for (int it = 0; opts && it < o.refits; it++) BA_CHECK(BA_LAUNCH(k_pair_fit, (unsigned)npairs, PR_BLK, 0, st, a, 0));
+  BA_CHECK(BA_LAUNCH(k_pair_fit, (unsigned)npairs, PR_BLK, 0, st, a, 1));
+  std::vector<double> h_pose((size_t)(6 * npairs));
+  std::vector<uint8_t> h_status((size_t)npairs);
+  BA_HIP_CHECK(hipMemcpyAsync(h_pose.data(), w.pose, h_pose.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_status.data(), w.status, h_status.size(), hipMemcpyDeviceToHost, st));
+  if (inlier && nmatch > 0) BA_HIP_CHECK(hipMemcpyAsync(inlier, w.inlier, (size_t)nmatch, hipMemcpyDeviceToHost, st));
+  if (n_inliers) BA_HIP_CHECK(hipMemcpyAsync(n_inliers, w.n_inliers, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (best_hyp) BA_HIP_CHECK(hipMemcpyAsync(best_hyp, w.best_hyp, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < npairs; i++) {
+    const uint8_t s = h_status[(size_t)i];
+    status[i] = s;
+    if (counts && s < BA_RP_STATES) counts[s]++;
+    if (s == BA_RP_OK)  // (a pair in any other state leaves its six entries as the caller filled them)
+      for (int j = 0; j < 6; j++) pose[6 * i + j] = h_pose[(size_t)(6 * i + j)];
+  }
+  return BA_OK;
+}

@@ -19,18 +19,7 @@
 
 #include "ba_internal.h"
 
-// splitmix64: the one generator of the sampling, host and device
-__host__ __device__ inline uint64_t ransac_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-// list position of draw j of the hypothesis with key `key` in a list of d entries, d < 2^31
-__host__ __device__ inline int64_t ransac_draw(uint64_t key, int j, int64_t d) {
-  return (int64_t)(((ransac_mix(key ^ (uint64_t)j) >> 32) * (uint64_t)d) >> 32);
-}
-constexpr int RN_DRAWS = 64;  // draws per hypothesis: one per lane
+// (ransac_mix, ransac_draw and RN_DRAWS -- splitmix64, the one generator of the sampling, host and device -- are in ba_internal.h)
 constexpr int RN_SAMPLE_MIN = 6, RN_SAMPLE_MAX = 16;
 
 namespace {

@@ -1,5 +1,5 @@
-// Device pieces shared by the block refinements (ba_point_kernels.hip, ba_camera_kernels.hip, ba_ransac_kernels.hip; DESIGN
-// §5j-§5n).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
+// Device pieces shared by the block refinements and the relative pose (ba_point_kernels.hip, ba_camera_kernels.hip,
+// ba_ransac_kernels.hip, ba_pair_kernels.hip).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
 // The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
@@ -169,17 +169,19 @@ __device__ __forceinline__ void jacobi12(double *A, double *V, int lane, int lan
 }
 
 // i1 <- the index of the smallest eigenvalue on the diagonal of M; false: an eigenvalue that is not finite, or the second
-// smallest is not above 1e-10 of the largest (the eigenvector is not determined)
+// smallest is not above 1e-10 of the largest (the eigenvector is not determined).  N: the leading N of the 12 are looked at (the
+// 9 x 9 matrix of the relative pose sits in the 12 x 12 with three spare diagonal entries that no rotation touches).
+template <int N = 12>
 __device__ __forceinline__ bool smallest_eigenpair(const double *M, int &i1) {
   i1 = 0;
   double l1 = M[0], lmax = M[0];
-  for (int i = 1; i < 12; i++) {
+  for (int i = 1; i < N; i++) {
     const double l = M[13 * i];
     if (l < l1) l1 = l, i1 = i;
     lmax = fmax(lmax, l);
   }
   double l2 = lmax;
-  for (int i = 0; i < 12; i++)
+  for (int i = 0; i < N; i++)
     if (i != i1) l2 = fmin(l2, M[13 * i]);
   return isfinite(l1) && isfinite(lmax) && l2 > 1e-10 * lmax;
 }
@@ -318,4 +320,172 @@ __device__ __forceinline__ bool pose_from_eigenvector(ResectScratch &sh, int i1,
   }
   rotation_vector(sh);
   return ok && isfinite(sh.r[0]) && isfinite(sh.r[1]) && isfinite(sh.r[2]);
+}
+
+// ---- the eight-point relative pose: the pose of camera b against camera a from their 2D-2D matches ----------------
+// P_b = R P_a + t, |t| = 1.  The BAL camera looks down -z: the ray of an undistorted measurement q is d = (q_x, q_y, -1) and a
+// point in front is P = alpha d, alpha > 0.  d_b' E d_a = 0 with E = [t]x R is linear in the 9 entries of E: on Hartley-normalised
+// rays d~ = (s (q - c), -1) the 9 x 9 normal matrix is M = sum a a', a = d~_b (x) d~_a (row-major e~), and the eigenvector of its
+// smallest eigenvalue is E~.  M sits in the 12 x 12 of jacobi12 with trace(M) on the three spare diagonal entries and zeros beside
+// them (a rotation with a_pq = 0 is skipped: the spare entries never move).  A caller gathers its matches about the first of the
+// set, reduces the 6 sums of the two images (image_stats), then the 45 sums (epipolar_terms), and runs the steps below in their
+// order: k_pair_hypotheses per wave, k_pair_fit per workgroup -- the same functions, so the same bits from the same sums.
+constexpr int EP_SUMS = 45;        // M packed lower row-major
+constexpr int EP_MIN_MATCHES = 8;  // 9 unknowns up to scale, one equation per match
+
+// the LDS of one fit: one per workgroup in k_pair_fit, one per wave in k_pair_hypotheses
+struct PairScratch {
+  ResectScratch rs;    // M, V (the 12 x 12), the 3 x 3 SVD of E, the winner's R and rotation vector r
+  double S[EP_SUMS];   // the sums on their way into M
+  double Rc[18];       // the two candidate rotations U Rz(+90) V', U Rz(-90) V'
+  double tn[3], t[3];  // the unit left null direction of E; the winner's translation (+ or - tn)
+  int cnt[4];          // matches of the set in front under candidate c: rotation c >> 1, sign of t: c & 1
+  int ok;
+};
+
+// both focal lengths of a pair's intrinsics (k1, k2, f of a, then of b) are finite and not 0
+__device__ __forceinline__ bool pair_focals_ok(const double *in) {
+  return isfinite(in[2]) && in[2] != 0.0 && isfinite(in[5]) && in[5] != 0.0;
+}
+
+// The Hartley normalisation of one image from n, the sums of d = q - origin and of |d|^2: the mean dm of d and s = sqrt(2) / (the
+// RMS distance from it); false: the image points coincide or a sum is not finite
+__device__ __forceinline__ bool image_stats(double n, double sx, double sy, double s2, double dm[3], double &s) {
+  const double sd[3] = {sx, sy, 0.0};
+  double sc;
+  if (!hartley_stats(n, sd, s2, dm, sc)) return false;
+  s = sqrt(2.0) * sc;
+  return true;
+}
+
+// d~ = (s (q - c), -1) of the image point q, c = org + dm
+__device__ __forceinline__ void normalised_ray(double qx, double qy, const double org[2], const double dm[3], double s, double d[3]) {
+  d[0] = s * ((qx - org[0]) - dm[0]), d[1] = s * ((qy - org[1]) - dm[1]), d[2] = -1.0;
+}
+
+// the 45 terms of one match; the caller adds them up (a lane without a match passes zeros)
+__device__ __forceinline__ void epipolar_terms(const double da[3], const double db[3], double term[EP_SUMS]) {
+  double a[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++) a[3 * i + j] = db[i] * da[j];
+  int tt = 0;
+#pragma unroll
+  for (int i = 0; i < 9; i++)
+#pragma unroll
+    for (int j = 0; j <= i; j++, tt++) term[tt] = a[i] * a[j];
+}
+
+// trace(M) from the packed sums
+__device__ __forceinline__ double epipolar_trace(const double *S) {
+  double tr = 0.0;
+  for (int i = 0; i < 9; i++) tr += S[i * (i + 1) / 2 + i];
+  return tr;
+}
+
+// element e (row-major) of the 12 x 12 that holds M, tr = trace(M)
+__device__ __forceinline__ double epipolar_matrix_entry(const double *S, double tr, int e) {
+  const int row = e / 12, col = e % 12;
+  if (row >= 9 || col >= 9) return row == col ? tr : 0.0;
+  const int hi = row > col ? row : col, lo = row > col ? col : row;
+  return S[hi * (hi + 1) / 2 + lo];
+}
+
+// From eigenvector i1 of sh.rs.V = E~: E = T_b' E~ T_a with T = [[s, 0, s c_x], [0, s, s c_y], [0, 0, 1]] (d~ = T d: the third entry of d is -1), its SVD by
+// nearest_rotation (U and V3 proper rotations, the column jm of the smallest singular value by cross product), the candidate
+// rotations R = U Rz(+-90) V3' with Rz in the plane of the two large singular directions -> sh.Rc, the unit left null direction
+// -> sh.tn.  A zero singular value among the two large ones leaves NaN, which no match is in front of.  (one lane)
+__device__ __forceinline__ void essential_candidates(PairScratch &sh, int i1, const double ca[2], double sa, const double cb[2], double sb) {
+  ResectScratch &rs = sh.rs;
+  for (int i = 0; i < 3; i++) {  // G = E~ T_a
+    const double e0 = rs.V[(3 * i) * 12 + i1], e1 = rs.V[(3 * i + 1) * 12 + i1], e2 = rs.V[(3 * i + 2) * 12 + i1];
+    rs.W[3 * i] = e0 * sa, rs.W[3 * i + 1] = e1 * sa, rs.W[3 * i + 2] = e2 + sa * (e0 * ca[0] + e1 * ca[1]);
+  }
+  for (int j = 0; j < 3; j++) {  // E = T_b' G
+    const double g0 = rs.W[j], g1 = rs.W[3 + j], g2 = rs.W[6 + j];
+    rs.W[j] = sb * g0, rs.W[3 + j] = sb * g1, rs.W[6 + j] = g2 + sb * (cb[0] * g0 + cb[1] * g1);
+  }
+  nearest_rotation(rs);
+  int jm = 0;
+  for (int j = 0; j < 3; j++)
+    if (rs.sg[j] < rs.sg[jm]) jm = j;
+  const int ja = (jm + 1) % 3, jb = (jm + 2) % 3;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      const double plane = rs.U[3 * i + jb] * rs.V3[3 * j + ja] - rs.U[3 * i + ja] * rs.V3[3 * j + jb];
+      const double axis = rs.U[3 * i + jm] * rs.V3[3 * j + jm];
+      sh.Rc[3 * i + j] = axis + plane;
+      sh.Rc[9 + 3 * i + j] = axis - plane;
+    }
+  const double u0 = rs.U[jm], u1 = rs.U[3 + jm], u2 = rs.U[6 + jm];
+  const double un = sqrt((u0 * u0 + u1 * u1) + u2 * u2);
+  sh.tn[0] = u0 / un, sh.tn[1] = u1 / un, sh.tn[2] = u2 / un;
+}
+
+// (alpha, beta) of alpha R d_a + t = beta d_b from its 2 x 2 normal equations, d = (q, -1); t = sgn tn
+__device__ __forceinline__ void pair_depths(const double *R, const double *tn, double sgn, double qax, double qay, double qbx, double qby,
+                                            double &al, double &be) {
+  const double u0 = (R[0] * qax + R[1] * qay) - R[2], u1 = (R[3] * qax + R[4] * qay) - R[5], u2 = (R[6] * qax + R[7] * qay) - R[8];
+  const double t0 = sgn * tn[0], t1 = sgn * tn[1], t2 = sgn * tn[2];
+  const double uu = (u0 * u0 + u1 * u1) + u2 * u2, vv = (qbx * qbx + qby * qby) + 1.0;
+  const double uv = (u0 * qbx + u1 * qby) - u2, ut = (u0 * t0 + u1 * t1) + u2 * t2, vt = (qbx * t0 + qby * t1) - t2;
+  const double det = uu * vv - uv * uv;
+  al = (uv * vt - ut * vv) / det;
+  be = (uu * vt - uv * ut) / det;
+}
+
+// The winner among the four candidates from sh.cnt: the most matches in front, ties to the first; its rotation vector -> sh.rs.r,
+// its translation -> sh.t.  false: no match in front of any candidate, or a component that is not finite.  (one lane)
+__device__ __forceinline__ bool pair_pose_winner(PairScratch &sh) {
+  int best = 0;
+  for (int c = 1; c < 4; c++)
+    if (sh.cnt[c] > sh.cnt[best]) best = c;
+  if (sh.cnt[best] <= 0) return false;
+  const double sgn = (best & 1) ? -1.0 : 1.0;
+  for (int i = 0; i < 9; i++) sh.rs.R[i] = sh.Rc[9 * (best >> 1) + i];
+  bool ok = true;
+  for (int i = 0; i < 3; i++) {
+    sh.t[i] = sgn * sh.tn[i];
+    ok = ok && isfinite(sh.t[i]);
+  }
+  rotation_vector(sh.rs);
+  return ok && isfinite(sh.rs.r[0]) && isfinite(sh.rs.r[1]) && isfinite(sh.rs.r[2]);
+}
+
+// what a lane scores matches under: R of the rotation vector r (Rodrigues, no small-angle branch: rotation_vector never returns
+// 0), t, and the clean E = [t]x R rebuilt from them
+struct PairPose {
+  double R[9], t[3], E[9];
+};
+__device__ __forceinline__ void pair_pose_of(const double *r, const double *t, PairPose &P) {
+  const double th = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+  const double kx = r[0] / th, ky = r[1] / th, kz = r[2] / th;
+  const double c = cos(th), s = sin(th), v = 1.0 - c;
+  P.R[0] = c + v * kx * kx, P.R[1] = v * kx * ky - s * kz, P.R[2] = v * kx * kz + s * ky;
+  P.R[3] = v * ky * kx + s * kz, P.R[4] = c + v * ky * ky, P.R[5] = v * ky * kz - s * kx;
+  P.R[6] = v * kz * kx - s * ky, P.R[7] = v * kz * ky + s * kx, P.R[8] = c + v * kz * kz;
+  P.t[0] = t[0], P.t[1] = t[1], P.t[2] = t[2];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    P.E[j] = t[1] * P.R[6 + j] - t[2] * P.R[3 + j];
+    P.E[3 + j] = t[2] * P.R[j] - t[0] * P.R[6 + j];
+    P.E[6 + j] = t[0] * P.R[3 + j] - t[1] * P.R[j];
+  }
+}
+
+// The inlier test of the header on a ray record (q_a, q_b, used) under P: used, alpha > 0, beta > 0 and the Sampson distance in
+// pixels^2 within tau^2 (a comparison with NaN fails).  The one test of every kernel that tests a match.
+__device__ __forceinline__ bool pair_inlier(const double *ray, const PairPose &P, double fa, double fb, double tau2) {
+  if (ray[4] == 0.0) return false;
+  const double qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
+  double al, be;
+  pair_depths(P.R, P.t, 1.0, qax, qay, qbx, qby, al, be);
+  if (!(al > 0.0 && be > 0.0)) return false;
+  const double l0 = (P.E[0] * qax + P.E[1] * qay) - P.E[2], l1 = (P.E[3] * qax + P.E[4] * qay) - P.E[5];
+  const double l2 = (P.E[6] * qax + P.E[7] * qay) - P.E[8];
+  const double m0 = (P.E[0] * qbx + P.E[3] * qby) - P.E[6], m1 = (P.E[1] * qbx + P.E[4] * qby) - P.E[7];
+  const double num = (qbx * l0 + qby * l1) - l2;
+  const double den = (l0 * l0 + l1 * l1) / (fb * fb) + (m0 * m0 + m1 * m1) / (fa * fa);
+  return num * num / den <= tau2;
 }

@@ -363,6 +363,51 @@ def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, m
     return x, _block_info(status, cost, counts, its)
 
 
+def pair_matches(problem, pairs):
+    """The match lists of camera pairs (ba_pair_matches; host only, no device): problem is a BALNLPModel or a dict with cam_idx1,
+    pnt_idx1, ncams and npnts (what synthetic.make_problem returns); pairs is (npairs, 2), 1-based cameras.
+    Returns (match_ptr, obs_a, obs_b), 0-based: the matches of pair k are obs_a[match_ptr[k]:match_ptr[k + 1]] (camera a's
+    observations, in the order of a's list) and obs_b (camera b's first observation of the same point)."""
+    if isinstance(problem, dict):
+        cam, pnt, ncams, npnts = problem["cam_idx1"], problem["pnt_idx1"], problem["ncams"], problem["npnts"]
+    else:
+        cam, pnt, ncams, npnts = problem.cams_indices, problem.pnts_indices, problem.ncams, problem.npnts
+    return _lib.pair_matches(cam, pnt, ncams, npnts, pairs)
+
+
+def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None):
+    """The relative pose of camera pairs from their 2D-2D matches (ba_relative_pose): the eight-point essential matrix, with
+    ransac=dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) behind a consensus stage (_lib.ransac_opts with
+    sample in 8..16, default 8, and min_inliers >= 8).  pairs: (npairs, 2), 1-based cameras (a, b).  Of x only (k1, k2, f) of the
+    pairs' cameras are read: the poses and the points may be NaN.  obs_info: as in Levenberg_Marquardt, here only "information 0
+    drops the observation" -- a match is used iff both its observations are.
+    Returns a dict: `r`, `t` (npairs, 3): P_b = R(r) P_a + t with |t| = 1, NaN where the pair has no pose; `status` (names among
+    _lib.PAIR_STATES); `match_ptr` and, per match in the order of pair_matches, `inliers` (bool); `n_inliers`; `best_hypothesis`
+    (-1: none); `counts` (pairs per state).  compose_relative turns (r, t) into camera b's pose.  On noisy data the eight-point
+    fit is only a start for the refinement that follows.  Bad arguments raise ValueError before any device call."""
+    opts = None if ransac is None else _lib.ransac_opts(ransac, least=8)
+    info3 = _lib.obs_info_pack(obs_info)
+    a1, b1 = _lib._pairs(pairs, nlp.ncams)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    if info3 is not None and info3.shape[0] != nlp.nobs:
+        raise ValueError(f"obs_info: one entry per observation ({nlp.nobs}), got {info3.shape[0]}")
+    n = len(a1)
+    mp = np.zeros(n + 1, dtype=np.int64)  # (the counting form: the size of the inlier array)
+    _lib.check(_lib.lib().ba_pair_matches(nlp.ncams, nlp.npnts, nlp.nobs, _lib.ptr(nlp.cams_indices), _lib.ptr(nlp.pnts_indices), n, _lib.ptr(a1),
+                                          _lib.ptr(b1), _lib.ptr(mp), None, None))
+    _lib.set_obs_info(nlp.handle, info3)
+    pose, status = np.full((n, 6), np.nan), np.zeros(n, dtype=np.uint8)
+    inlier, n_in, best = np.zeros(int(mp[-1]), dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    counts, mp2 = np.zeros(len(_lib.PAIR_STATES), dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    _lib.check(_lib.lib().ba_relative_pose(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), None if opts is None else C.byref(opts),
+                                           _lib.ptr(pose), _lib.ptr(status), _lib.ptr(mp2), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best),
+                                           _lib.ptr(counts)))
+    return dict(r=pose[:, :3].copy(), t=pose[:, 3:].copy(), status=np.array(_lib.PAIR_STATES)[status], match_ptr=mp2, inliers=inlier != 0,
+                n_inliers=n_in, best_hypothesis=best, counts={s: int(c) for s, c in zip(_lib.PAIR_STATES, counts)})
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

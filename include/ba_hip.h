@@ -687,6 +687,82 @@ int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device
                                 int *iters_max /* host, or NULL */, uint8_t *d_inlier /* nobs or NULL */,
                                 int32_t *d_n_inliers /* ncams or NULL */, int32_t *d_best_hyp /* ncams or NULL */, void *stream);
 
+/* ---- relative pose of camera pairs: the eight-point essential matrix with RANSAC (an extension) ------------------------------
+ * The entries above need posed cameras or placed points to start from.  This one needs neither: from the detections alone it
+ * gives the pose of camera b against camera a of a pair, from the points both observe, robust against wrong matches.  With
+ * compose_relative of the Python package the two cameras are posed, ba_refine_points triangulates the first points,
+ * ba_ransac_cameras registers further cameras, and the LM solve refines.
+ * ba_pair_matches (host only, no handle, no device): the match list of every pair (a, b), 1-based cameras.  Walk camera a's
+ * observations in the caller's order: an observation of point P is a match iff it is a's first observation of P and b observes
+ * P; its partner is b's first observation of P in the caller's order.  The matches of a pair are thus ordered by a's list and a
+ * point gives at most one.  match_ptr receives npairs + 1 offsets; obs_a1 / obs_b1 (both or neither: with both NULL the call
+ * only counts) the 1-based observations of every match.  a == b, an index out of range, a NULL array: BA_ERR_ARG; npairs == 0
+ * is fine; a pair may repeat and a camera may appear in many pairs.
+ * ba_relative_pose: x is a host vector of which only (k1, k2, f) of the pairs' cameras are read; its poses and points never are
+ * (NaN is fine).  From the handle only ba_lm_set_obs_info is honoured, and only through the test Lambda != 0: a match is USED iff
+ * both its observations are.  Loss, mask, priors and grouping are ignored.  A handle with a communicator is refused.
+ * Conventions: P_a = R_a X + t_a, P_b = R_b X + t_b; the relative pose is P_b = R P_a + t with |t| = 1 (the scale cannot be
+ * observed).  The BAL camera looks down -z: the ray of an undistorted measurement q is d = (q_x, q_y, -1) and a point in front
+ * is P = alpha d with alpha > 0.  The epipolar constraint is d_b' E d_a = 0 with E = [t]x R.
+ * The linear fit on a set of n matches:
+ *  1. q_a, q_b of a match: the undistortion of ba_resect_cameras (u = pt2d / f, 8 iterations) with each camera's intrinsics.
+ *     f not finite or 0 for either camera: the pair is BA_RP_DEGENERATE.
+ *  2. Hartley normalisation per image: c = the mean of q, s = sqrt(2) / (the RMS distance from c), the sums taken about the first
+ *     match of the set; d~ = (s (q - c), -1).  Coinciding image points or a sum that is not finite: degenerate.
+ *  3. M = sum a a' (9 x 9) with a = d~_b (x) d~_a, the row-major entries of E~.
+ *  4. The eigenvector of M's smallest eigenvalue by the cyclic Jacobi sweeps of ba_resect_cameras.  An eigenvalue that is not
+ *     finite, or lambda_2 <= 1e-10 lambda_9: degenerate.  This is the known limit of the method: all points on a plane (or a
+ *     ruled quadric through both centres), a pure rotation (no baseline), and fewer than 8 matches in general position.
+ *  5. E = T_b' E~ T_a with T = [[s, 0, s c_x], [0, s, s c_y], [0, 0, 1]] (d~ = T d: the third entry of d is -1).
+ *  6. The one-sided Jacobi SVD of E as in ba_resect_cameras: U and V proper rotations, the column of the smallest singular value
+ *     by cross product.  The four candidates are R = U Rz(+90) V', U Rz(-90) V' (Rz turning in the plane of the two large singular
+ *     directions) with t = + or - the left null direction of E, in the order (R+, t), (R+, -t), (R-, t), (R-, -t).
+ *  7. Cheirality: for a candidate and a match, (alpha, beta) solve the 2 x 2 normal equations of alpha R d_a + t = beta d_b; the
+ *     match is in front iff alpha > 0 and beta > 0 (a comparison with NaN fails).  The candidate with the most matches of the set
+ *     in front wins, ties to the first; a best count of 0: degenerate.
+ *  8. r = the rotation vector of the winner's R (the rule of ba_resect_cameras: theta < 1e-12 gives (1e-12, 0, 0)) and its t.
+ *     Everything downstream uses the clean E_h = [t]x R rebuilt from (r, t).
+ * Inlier test of a match under (r, t): it is used, alpha > 0, beta > 0, and its Sampson distance in pixels^2,
+ *   (d_b' E_h d_a)^2 / (((E_h d_a)_1^2 + (E_h d_a)_2^2) / f_b^2 + ((E_h' d_b)_1^2 + (E_h' d_b)_2^2) / f_a^2), is <= tau^2.
+ * States: BA_RP_FEW_MATCHES -- fewer than 8 used matches; BA_RP_DEGENERATE -- a focal length as in step 1, or the final fit is
+ * degenerate; BA_RP_NO_CONSENSUS -- below; BA_RP_OK.  Only a pair that is BA_RP_OK has its six entries of pose written (r, then
+ * t); the others keep what the caller put there.  counts[s] = pairs in state s.
+ * opts == NULL: no consensus stage -- the set is every used match (inlier = used, best_hyp = -1) and the pose is the linear fit on it.
+ * opts != NULL (ba_ransac_opts unchanged; the rules of ba_ransac_cameras with these ranges): threshold tau in pixels, finite and
+ * > 0; hypotheses H (<= 0: 128; at most 4096); sample m (<= 0: 8; 8..16); refits (< 0: 2; at most 8); min_inliers (<= 0:
+ * max(m, 8); at least 8); seed.  Sampling: exactly ba_ransac_sample(seed, h, degree = the number of matches of the pair, used, m)
+ * on the pair's match list; the pair's index does not enter.  Hypothesis h = the linear fit on the m sampled matches in the order
+ * of their draws; a degenerate sample is void.  Score = the inlier count over the pair's whole list; the best hypothesis has the
+ * largest count, ties to the lowest h.  No valid hypothesis, or a best count < min_inliers: BA_RP_NO_CONSENSUS, the inlier bytes
+ * 0, n_inliers = the best count (0 if none), best_hyp = that h or -1.  Otherwise the winner's inliers are the set M.  Refits, up
+ * to `refits` times: the linear fit on M; the whole list re-scored under it gives M'; M' is adopted iff |M'| >= |M| and
+ * M' != M; otherwise (also when the fit is degenerate) M stays and the pair stops.  Finish: the linear fit on the final set is
+ * the returned pose; inlier = the set, n_inliers = its size.  A pair that is FEW_MATCHES or DEGENERATE by a focal length has
+ * inlier bytes 0, n_inliers = 0, best_hyp = -1.
+ * Outputs, each may be NULL except pose and status: match_ptr (npairs + 1 offsets into the match lists, those of
+ * ba_pair_matches), inlier (one byte per match, in that order), n_inliers, best_hyp, counts.
+ * No floating-point atomics and one writer per output: two calls give the same bits, and a pair's result depends on its own
+ * matches, their order, the two cameras' intrinsics and the options only.  The next ba_lm_step / ba_lm_solve on the handle gives
+ * the bits it gives without this call.  npairs == 0 returns BA_OK.
+ * On noisy data the eight-point fit is only a start: on a narrow field of view (the generator's unit ball seen from distance
+ * 5..7, 30 % wrong matches, tau = 2 px) the final set is the true one for most pairs at 0.05 px of noise and for about half of
+ * them at 0.1 px, whatever the refits; the refinement behind it (the triangulation, the resections and the LM solve on the
+ * seeded x) is what makes the estimate.
+ * Out of scope: the five-point solver; a non-linear refinement of the pair; unknown focal lengths; homographies and planar
+ * scenes; MSAC or an adaptive hypothesis count; the choice of the initial pair; Float32; several ranks; a device-resident entry. */
+enum { BA_RP_OK = 0, BA_RP_FEW_MATCHES = 1, BA_RP_DEGENERATE = 2, BA_RP_NO_CONSENSUS = 3, BA_RP_STATES = 4 };
+int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1,
+                    int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                    int64_t *match_ptr /* npairs + 1 */, int64_t *obs_a1 /* match_ptr[npairs] or NULL */,
+                    int64_t *obs_b1 /* same */);
+int ba_relative_pose(ba_problem *p, const double *x /* nvar, host: only (k1, k2, f) of the pairs' cameras are read */,
+                     int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                     const ba_ransac_opts *opts /* NULL: no consensus stage, the linear fit on all used matches */,
+                     double *pose /* 6 npairs: rotation vector r, unit translation t */, uint8_t *status /* npairs */,
+                     int64_t *match_ptr /* npairs + 1, or NULL */, uint8_t *inlier /* one byte per match, or NULL */,
+                     int32_t *n_inliers /* npairs or NULL */, int32_t *best_hyp /* npairs or NULL */,
+                     int64_t *counts /* BA_RP_STATES or NULL */);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

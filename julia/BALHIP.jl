@@ -299,3 +299,53 @@ function ransac_cameras_focal_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hy
                 Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
   return nothing
 end
+
+# relative pose of camera pairs (an extension): include/ba_hip.h, ba_pair_matches / ba_relative_pose.  pair_matches lists the
+# points two cameras both observe (host only): pairs_a, pairs_b are 1-based cameras; returns match_ptr (npairs + 1 offsets) and the
+# 1-based observations of every match in camera a and in camera b.  relative_pose gives P_b = R(r) P_a + t, |t| = 1, per pair by
+# the eight-point algorithm; with a threshold (pixels) a consensus stage stands in front (a value below its range means the
+# default: 128 hypotheses, samples of 8, 2 refits, min_inliers = max(sample, 8)).  Of `x` only (k1, k2, f) of the pairs' cameras
+# are read.  Returns pose (6 x npairs: r, then t; NaN where the state is not 0), status (BA_RP_*), match_ptr, the inlier mask per
+# match, the size of every pair's set, its winning hypothesis (-1: none) and the pairs per state.
+function pair_matches(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64})
+  npairs = length(pairs_a)
+  cam = Vector{Int64}(nlp.cams_indices)
+  pnt = Vector{Int64}(nlp.pnts_indices)
+  match_ptr = zeros(Int64, npairs + 1)
+  sig = (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64})
+  GC.@preserve cam pnt pairs_a pairs_b match_ptr begin
+    bacheck(ccall((:ba_pair_matches, libba), Cint, sig, nlp.ncams, nlp.npnts, nlp.nobs, pointer(cam), pointer(pnt), npairs,
+                  pointer(pairs_a), pointer(pairs_b), pointer(match_ptr), Ptr{Int64}(C_NULL), Ptr{Int64}(C_NULL)))
+  end
+  obs_a = zeros(Int64, match_ptr[end])
+  obs_b = zeros(Int64, match_ptr[end])
+  GC.@preserve cam pnt pairs_a pairs_b match_ptr obs_a obs_b begin
+    bacheck(ccall((:ba_pair_matches, libba), Cint, sig, nlp.ncams, nlp.npnts, nlp.nobs, pointer(cam), pointer(pnt), npairs,
+                  pointer(pairs_a), pointer(pairs_b), pointer(match_ptr), pointer(obs_a), pointer(obs_b)))
+  end
+  return match_ptr, obs_a, obs_b
+end
+
+function relative_pose(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64};
+                       threshold :: Union{Real, Nothing} = nothing, hypotheses :: Integer = 0, sample :: Integer = 0,
+                       refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0)
+  npairs = length(pairs_a)
+  match_ptr, _, _ = pair_matches(nlp, pairs_a, pairs_b)
+  pose = fill(NaN, 6, npairs)
+  status = zeros(UInt8, npairs)
+  inlier = zeros(UInt8, match_ptr[end])
+  n_inliers = zeros(Int32, npairs)
+  best_hyp = zeros(Int32, npairs)
+  counts = zeros(Int64, 4)
+  opts = Ref(BaRansacOpts(Cdouble(threshold === nothing ? 1.0 : threshold), Cint(hypotheses), Cint(sample), Cint(refits),
+                          Cint(min_inliers), UInt64(seed)))
+  GC.@preserve x pairs_a pairs_b opts pose status match_ptr inlier n_inliers best_hyp counts begin
+    optr = threshold === nothing ? Ptr{BaRansacOpts}(C_NULL) : Base.unsafe_convert(Ptr{BaRansacOpts}, opts)
+    bacheck(ccall((:ba_relative_pose, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{BaRansacOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int64},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                  nlp.handle, pointer(x), npairs, pointer(pairs_a), pointer(pairs_b), optr, pointer(pose), pointer(status),
+                  pointer(match_ptr), pointer(inlier), pointer(n_inliers), pointer(best_hyp), pointer(counts)))
+  end
+  return pose, status, match_ptr, inlier .!= 0, n_inliers, best_hyp, counts
+end
