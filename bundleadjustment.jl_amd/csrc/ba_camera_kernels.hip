@@ -702,32 +702,6 @@ extern "C" int ba_resect_cameras_focal(ba_problem *p, double *x_inout, int max_i
 }
 
 // ---- ba_ransac_cameras: a consensus stage in front of ba_resect_cameras ------------------------------------------
-// The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message
-static int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o) {
-  if (!in) {
-    ba_set_error("%s: null options", who);
-    return BA_ERR_ARG;
-  }
-  *o = *in;
-  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
-    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
-    return BA_ERR_ARG;
-  }
-  if (o->hypotheses <= 0) o->hypotheses = 128;
-  if (o->sample <= 0) o->sample = 6;
-  if (o->refits < 0) o->refits = 2;
-  if (o->hypotheses > 4096 || o->sample < 6 || o->sample > 16 || o->refits > 8) {
-    ba_set_error("%s: hypotheses must be <= 4096, sample in 6..16, refits <= 8, got %d, %d, %d", who, o->hypotheses, o->sample, o->refits);
-    return BA_ERR_ARG;
-  }
-  if (o->min_inliers <= 0) o->min_inliers = o->sample > 6 ? o->sample : 6;
-  if (o->min_inliers < 6) {
-    ba_set_error("%s: min_inliers must be >= 6 (<= 0: max(sample, 6)), got %d", who, o->min_inliers);
-    return BA_ERR_ARG;
-  }
-  return BA_OK;
-}
-
 // the consensus results of the last ransac_consensus -> the caller's arrays (each may be null), on st
 static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, hipMemcpyKind kind, hipStream_t st) {
   const CameraWork &w = p->cams;
@@ -742,7 +716,7 @@ static int ransac_cameras_dev(const char *who, ba_problem *p, double *d_x_inout,
                               double xtol, double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
                               uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
   ba_ransac_opts o;
-  BA_CHECK(ransac_opts_check(who, opts, &o));
+  BA_CHECK(ransac_opts_check(who, opts, &o, RS_MIN_OBS));
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
@@ -755,7 +729,7 @@ static int ransac_cameras_host(const char *who, ba_problem *p, double *x_inout, 
                                double xtol, double lambda0, uint8_t *status, double *cost, int64_t *counts, int *iters_max,
                                uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
   ba_ransac_opts o;
-  BA_CHECK(ransac_opts_check(who, opts, &o));
+  BA_CHECK(ransac_opts_check(who, opts, &o, RS_MIN_OBS));
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {

@@ -406,6 +406,11 @@ __host__ __device__ inline int64_t ransac_draw(uint64_t key, int j, int64_t d) {
   return (int64_t)(((ransac_mix(key ^ (uint64_t)j) >> 32) * (uint64_t)d) >> 32);
 }
 constexpr int RN_DRAWS = 64;  // draws per hypothesis: one per lane
+// the limits of ba_ransac_opts: the largest sample, hypotheses per list (the selection key holds h in 12 bits) and refits
+constexpr int RN_SAMPLE_MAX = 16, RN_HYP_MAX = 4096, RN_REFITS_MAX = 8;
+// The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message.  least: the smallest
+// sample and set of the caller's fit (RS_MIN_OBS of the resection, EP_MIN_MATCHES of the relative pose)
+int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *out, int least);
 
 // ---- relative pose of camera pairs (ba_relative_pose; ba_pair_kernels.hip) -------------------------------------
 // The per-call device buffers (allocated at the first call, grown when a call needs more): per pair the first match of its

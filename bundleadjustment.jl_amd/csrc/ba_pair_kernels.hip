@@ -7,12 +7,15 @@
 // a pair read that record and never repeat the 16 divisions per match.
 // k_pair_hypotheses: grid (pair, hypotheses / 4), ONE WAVE PER HYPOTHESIS on its own LDS slab (a PairScratch), the layout of
 // k_ransac_hypotheses: a wave draws its sample (one draw per lane), takes the 6 + 45 sums through wave_all_sum, runs the linear
-// fit of ba_refine_dev.h (jacobi12<wave_sync>: no workgroup barrier, a void or degenerate wave simply leaves) and counts the
-// inliers of the pair's whole list in a strided pass over the records.
+// fit of ba_refine_dev.h (essential_from_sums<wave_sync>: no workgroup barrier, a void or degenerate wave simply leaves) and
+// counts the inliers of the pair's whole list in a strided pass over the records.
 // k_pair_select (one workgroup per pair): the states that need no fit, the winner, its inlier bytes.
 // k_pair_fit (one workgroup per pair): the sums over the current set in a fixed order (strided partial sums per thread, the
-// butterfly of a wave, the four waves in order), the same linear fit, then either the re-scoring with the adopt rule of the
-// refits or, in the last launch, the returned pose.
+// butterfly of a wave, the four waves in order), the same linear fit (essential_from_sums<__syncthreads>), then either the
+// re-scoring with the adopt rule of the refits or, in the last launch, the returned pose.
+// The sample, the winner, the marking of a set and the adopt rule are those of ba_consensus_dev.h, shared with
+// ba_ransac_cameras, and the options go through its ransac_opts_check; this file keeps whether a match is used, the sums of a
+// fit, the cheirality counts and the states of k_pair_select.
 // All kernels that test a match call pair_inlier, so a count never disagrees with the bytes.  No atomics: every output has one
 // writer, two calls give the same bits.
 #include <cmath>
@@ -22,10 +25,10 @@
 
 namespace {
 
-#include "ba_refine_dev.h"  // wave_all_sum, undistort, obs_used, jacobi12, the pieces of the linear fit
+#include "ba_refine_dev.h"     // wave_all_sum, undistort, obs_used, jacobi12, the pieces of the linear fit
+#include "ba_consensus_dev.h"  // the sample, the winner, the set and the adopt rule: shared with ba_ransac_kernels.hip
 
-constexpr int PR_BLK = 256, PR_WAVES = PR_BLK / 64;
-constexpr int PR_SAMPLE_MIN = 8, PR_SAMPLE_MAX = 16;
+constexpr int PR_BLK = CS_BLK, PR_WAVES = CS_WAVES;
 
 __global__ __launch_bounds__(PR_BLK) void k_pair_rays(PairArgs a, int64_t nmatch) {
   const int64_t k = (int64_t)blockIdx.x * PR_BLK + threadIdx.x;
@@ -47,20 +50,12 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_rays(PairArgs a, int64_t nmatch
 __device__ __forceinline__ bool pair_hypothesis(const PairArgs &a, PairScratch &sh, const double *in, int h, int k0, int k1, int lane) {
   const int d = k1 - k0, m = a.sample;
   if (d <= 0 || !pair_focals_ok(in)) return false;
-  // the sample: lane j holds draw j; a draw counts unless its match is not used or an earlier draw hit its position
-  const uint64_t key = ransac_mix(a.seed_mix ^ (uint64_t)h);
-  const int pos = (int)ransac_draw(key, lane, d);  // < d
+  // the sample: lane j holds draw j
+  const int pos = sample_position(a.seed_mix, h, lane, d);
   const double *ray = a.rays + PAIR_RAY * (int64_t)(k0 + pos);
-  bool accept = ray[4] != 0.0;
-#pragma nounroll
-  for (int i = 0; i < RN_DRAWS - 1; i++) {
-    const int pi = __shfl(pos, i, 64);
-    if (i < lane && pi == pos) accept = false;
-  }
-  const unsigned long long taken = __ballot(accept);
-  if (__popcll(taken) < m) return false;
-  const bool take = accept && __popcll(taken & ((1ull << lane) - 1ull)) < m;
-  const int first = __ffsll((long long)taken) - 1;  // the lane of the first accepted draw: the provisional origin
+  bool take;
+  int first;
+  if (!sample_take(pos, ray[4] != 0.0, lane, m, take, first)) return false;
   double qax = 0.0, qay = 0.0, qbx = 0.0, qby = 0.0;
   if (take) qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
   const double oa[2] = {__shfl(qax, first, 64), __shfl(qay, first, 64)}, ob[2] = {__shfl(qbx, first, 64), __shfl(qby, first, 64)};
@@ -94,16 +89,8 @@ __device__ __forceinline__ bool pair_hypothesis(const PairArgs &a, PairScratch &
     for (int i = 0; i < EP_SUMS; i++) sh.S[i] = acc[i];
   }
   wave_sync();
-  const double tr = epipolar_trace(sh.S);
-  for (int e = lane; e < 144; e += 64) sh.rs.M[e] = epipolar_matrix_entry(sh.S, tr, e);
-  jacobi12<wave_sync>(sh.rs.M, sh.rs.V, lane, 64);
-  int i1;
-  if (!smallest_eigenpair<9>(sh.rs.M, i1)) return false;
-  if (lane == 0) {
-    const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
-    essential_candidates(sh, i1, ca, sa, cb, sb);
-  }
-  wave_sync();
+  const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
+  if (!essential_from_sums<wave_sync>(sh, lane, 64, ca, sa, cb, sb)) return false;
   // the matches of the sample in front of both cameras, per candidate
   int cnt[4];
 #pragma unroll
@@ -145,15 +132,6 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_hypotheses(PairArgs a) {
   if (lane == 0) a.hyp_count[slot] = count;
 }
 
-// the sum of v over the workgroup -> every thread (red: PR_WAVES ints; a barrier on either side)
-__device__ __forceinline__ int pair_block_sum_int(int v, int *red, int t) {
-  v = wave_all_sum_int(v);
-  __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // a pair that ends here: its state, no inlier, n matches counted, winner h (or -1)
 __device__ __forceinline__ void pair_fails(const PairArgs &a, int pr, int k0, int k1, int t, int state, int n, int h) {
   for (int k = k0 + t; k < k1; k += PR_BLK) a.inlier[k] = 0;
@@ -161,8 +139,8 @@ __device__ __forceinline__ void pair_fails(const PairArgs &a, int pr, int k0, in
 }
 
 // One pair per workgroup: FEW_MATCHES (fewer than 8 used matches), DEGENERATE (a focal length that is not finite or 0), without
-// a consensus stage the set of the used matches, with one the winner among the hypotheses (the largest count, ties to the lowest
-// h; none, or a count below min_inliers: NO_CONSENSUS) and its inlier bytes.
+// a consensus stage the set of the used matches, with one the winner among the hypotheses (consensus_winner; none, or a count
+// below min_inliers: NO_CONSENSUS) and its inlier bytes.
 __global__ __launch_bounds__(PR_BLK) void k_pair_select(PairArgs a) {
   __shared__ long long redk[PR_WAVES];
   __shared__ int red[PR_WAVES];
@@ -171,7 +149,7 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_select(PairArgs a) {
   const double *in = a.intr + 6 * (int64_t)pr;
   int nu = 0;
   for (int k = k0 + t; k < k1; k += PR_BLK) nu += a.rays[PAIR_RAY * (int64_t)k + 4] != 0.0 ? 1 : 0;
-  nu = pair_block_sum_int(nu, red, t);
+  nu = block_sum_int(nu, red, t);
   if (nu < EP_MIN_MATCHES) return pair_fails(a, pr, k0, k1, t, BA_RP_FEW_MATCHES, 0, -1);
   if (!pair_focals_ok(in)) return pair_fails(a, pr, k0, k1, t, BA_RP_DEGENERATE, 0, -1);
   if (a.hypotheses == 0) {
@@ -179,35 +157,15 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_select(PairArgs a) {
     if (t == 0) a.status[pr] = BA_RP_OK, a.n_inliers[pr] = nu, a.best_hyp[pr] = -1, a.stopped[pr] = 0;
     return;
   }
-  // key = (count + 1) << 12 | (4095 - h): the largest key is the largest count at the lowest h; 0: no valid hypothesis
-  long long key = 0;
-  for (int h = t; h < a.hypotheses; h += PR_BLK) {
-    const int cnt = a.hyp_count[(int64_t)pr * a.hypotheses + h];
-    if (cnt >= 0) {
-      const long long kk = ((long long)(cnt + 1) << 12) | (long long)(4095 - h);
-      key = kk > key ? kk : key;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long other = __shfl_xor(key, off, 64);
-    key = other > key ? other : key;
-  }
-  if ((t & 63) == 0) redk[t >> 6] = key;
-  __syncthreads();
-  for (int w = 0; w < PR_WAVES; w++) key = redk[w] > key ? redk[w] : key;
-  const int best = key ? 4095 - (int)(key & 4095) : -1, best_count = key ? (int)(key >> 12) - 1 : 0;
-  if (!key || best_count < a.min_inliers) return pair_fails(a, pr, k0, k1, t, BA_RP_NO_CONSENSUS, best_count, best);
+  int best, best_count;
+  consensus_winner(a.hyp_count + (int64_t)pr * a.hypotheses, a.hypotheses, t, redk, best, best_count);
+  if (best < 0 || best_count < a.min_inliers) return pair_fails(a, pr, k0, k1, t, BA_RP_NO_CONSENSUS, best_count, best);
   const double *win = a.hyp_pose + PAIR_HYP_DOUBLES * ((int64_t)pr * a.hypotheses + best);
   PairPose P;
   pair_pose_of(win, win + 3, P);
-  int n = 0;
-  for (int k = k0 + t; k < k1; k += PR_BLK) {
-    const int in_ = pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0;
-    a.inlier[k] = (uint8_t)in_;
-    n += in_;
-  }
-  n = pair_block_sum_int(n, red, t);
+  const int n = consensus_mark(
+      k0, k1, a.inlier, red, t, [](int k) { return k; },
+      [&](int k) { return pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2); });
   if (t == 0) a.status[pr] = BA_RP_OK, a.n_inliers[pr] = n, a.best_hyp[pr] = best, a.stopped[pr] = 0;
 }
 
@@ -225,10 +183,9 @@ __device__ __forceinline__ void pair_wave_part(PairFitShared &sh, int i, double 
   if ((t & 63) == 0) sh.part[t >> 6][i] = v;
 }
 
-// One pair per workgroup: the linear fit on its current set M (the inlier bytes).  final == 0, a round of the refits: M' = the
-// inliers of the whole list under the fit; adopted iff |M'| >= |M| and M' != M, otherwise (also when the fit is degenerate) M
-// stays and the pair stops.  Bit 1 of an inlier byte carries M' between the two passes; every thread rewrites the bytes it wrote.
-// final != 0: the pose of the fit -> a.pose, or the state DEGENERATE.
+// One pair per workgroup: the linear fit on its current set M (the inlier bytes).  final == 0, a round of the refits: the adopt
+// rule of consensus_rescore on the whole list under the fit; M stays and the pair stops when M' is not adopted, and when the fit
+// is degenerate.  final != 0: the pose of the fit -> a.pose, or the state DEGENERATE.
 __global__ __launch_bounds__(PR_BLK) void k_pair_fit(PairArgs a, int final) {
   __shared__ PairFitShared sh;
   const int t = (int)threadIdx.x, pr = (int)blockIdx.x;
@@ -291,38 +248,30 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_fit(PairArgs a, int final) {
     for (int i = 0; i < EP_SUMS; i++) ok = ok && isfinite(ps.S[i]);
   }
   if (ok) {
-    const double tr = epipolar_trace(ps.S);
-    for (int e = t; e < 144; e += PR_BLK) ps.rs.M[e] = epipolar_matrix_entry(ps.S, tr, e);
-    jacobi12<__syncthreads>(ps.rs.M, ps.rs.V, t, PR_BLK);
-    int i1;
-    ok = smallest_eigenpair<9>(ps.rs.M, i1);
-    if (ok) {
-      if (t == 0) {
-        const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
-        essential_candidates(ps, i1, ca, sa, cb, sb);
-      }
-      __syncthreads();
-      int cnt[4] = {0, 0, 0, 0};
-      for (int k = k0 + t; k < k1; k += PR_BLK)
-        if (a.inlier[k] & 1) {
-          const double *ray = a.rays + PAIR_RAY * (int64_t)k;
+    const double ca[2] = {oa[0] + dma[0], oa[1] + dma[1]}, cb[2] = {ob[0] + dmb[0], ob[1] + dmb[1]};
+    ok = essential_from_sums<__syncthreads>(ps, t, PR_BLK, ca, sa, cb, sb);
+  }
+  if (ok) {  // the matches of the set in front of both cameras, per candidate
+    int cnt[4] = {0, 0, 0, 0};
+    for (int k = k0 + t; k < k1; k += PR_BLK)
+      if (a.inlier[k] & 1) {
+        const double *ray = a.rays + PAIR_RAY * (int64_t)k;
 #pragma unroll
-          for (int c = 0; c < 4; c++) {
-            double al, be;
-            pair_depths(ps.Rc + 9 * (c >> 1), ps.tn, (c & 1) ? -1.0 : 1.0, ray[0], ray[1], ray[2], ray[3], al, be);
-            cnt[c] += (al > 0.0 && be > 0.0) ? 1 : 0;
-          }
+        for (int c = 0; c < 4; c++) {
+          double al, be;
+          pair_depths(ps.Rc + 9 * (c >> 1), ps.tn, (c & 1) ? -1.0 : 1.0, ray[0], ray[1], ray[2], ray[3], al, be);
+          cnt[c] += (al > 0.0 && be > 0.0) ? 1 : 0;
         }
-#pragma unroll
-      for (int c = 0; c < 4; c++) cnt[c] = pair_block_sum_int(cnt[c], sh.red, t);
-      if (t == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; c++) ps.cnt[c] = cnt[c];
-        ps.ok = pair_pose_winner(ps) ? 1 : 0;
       }
-      __syncthreads();
-      ok = ps.ok != 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) cnt[c] = block_sum_int(cnt[c], sh.red, t);
+    if (t == 0) {
+#pragma unroll
+      for (int c = 0; c < 4; c++) ps.cnt[c] = cnt[c];
+      ps.ok = pair_pose_winner(ps) ? 1 : 0;
     }
+    __syncthreads();
+    ok = ps.ok != 0;
   }
   if (final) {
     if (t == 0 && !ok) a.status[pr] = BA_RP_DEGENERATE;
@@ -335,22 +284,11 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_fit(PairArgs a, int final) {
   }
   PairPose P;
   pair_pose_of(ps.rs.r, ps.t, P);
-  int n = 0, diff = 0;
-  for (int k = k0 + t; k < k1; k += PR_BLK) {
-    const int in_ = pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0, old = a.inlier[k] & 1;
-    a.inlier[k] = (uint8_t)(old | (in_ << 1));
-    n += in_;
-    diff += in_ != old ? 1 : 0;
-  }
-  n = pair_block_sum_int(n, sh.red, t);
-  diff = pair_block_sum_int(diff, sh.red, t);
-  const bool adopt = n >= n_old && diff > 0;
-  for (int k = k0 + t; k < k1; k += PR_BLK) {
-    const int b = a.inlier[k];
-    a.inlier[k] = (uint8_t)(adopt ? (b >> 1) & 1 : b & 1);
-  }
+  const int n = consensus_rescore(
+      k0, k1, n_old, a.inlier, sh.red, t, [](int k) { return k; },
+      [&](int k) { return pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2); });
   if (t == 0) {
-    if (adopt) a.n_inliers[pr] = n;
+    if (n >= 0) a.n_inliers[pr] = n;
     else a.stopped[pr] = 1;
   }
 }
@@ -401,29 +339,6 @@ int pair_match_lists(const char *who, int64_t ncams, int64_t npnts, int64_t nobs
       if (oa) oa->push_back(o), ob->push_back(first_b[(size_t)q]);
     }
     ptr[(size_t)i + 1] = ptr[(size_t)i] + n;
-  }
-  return BA_OK;
-}
-
-// The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message
-int pair_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o) {
-  *o = *in;
-  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
-    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
-    return BA_ERR_ARG;
-  }
-  if (o->hypotheses <= 0) o->hypotheses = 128;
-  if (o->sample <= 0) o->sample = PR_SAMPLE_MIN;
-  if (o->refits < 0) o->refits = 2;
-  if (o->hypotheses > 4096 || o->sample < PR_SAMPLE_MIN || o->sample > PR_SAMPLE_MAX || o->refits > 8) {
-    ba_set_error("%s: hypotheses must be <= 4096, sample in %d..%d, refits <= 8, got %d, %d, %d", who, PR_SAMPLE_MIN, PR_SAMPLE_MAX,
-                 o->hypotheses, o->sample, o->refits);
-    return BA_ERR_ARG;
-  }
-  if (o->min_inliers <= 0) o->min_inliers = o->sample > EP_MIN_MATCHES ? o->sample : EP_MIN_MATCHES;
-  if (o->min_inliers < EP_MIN_MATCHES) {
-    ba_set_error("%s: min_inliers must be >= %d (<= 0: max(sample, %d)), got %d", who, EP_MIN_MATCHES, EP_MIN_MATCHES, o->min_inliers);
-    return BA_ERR_ARG;
   }
   return BA_OK;
 }
@@ -489,7 +404,7 @@ extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, 
                                 int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
   const char *who = "ba_relative_pose";
   ba_ransac_opts o = {};
-  if (opts) BA_CHECK(pair_opts_check(who, opts, &o));
+  if (opts) BA_CHECK(ransac_opts_check(who, opts, &o, EP_MIN_MATCHES));
   if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !pose || !status))) {
     ba_set_error("%s: null argument or npairs < 0", who);
     return BA_ERR_ARG;

@@ -12,6 +12,10 @@
 // k_ransac_select (one workgroup per camera) picks the winner and writes the inlier bytes; k_ransac_rescore compares the set
 // a refit gives with the current one; k_ransac_mask_info hands the set to k_resect_cameras / k_refine_cameras as information.
 // All three kernels that test an observation call ransac_inlier, so a count never disagrees with the bytes.
+// The rules a consensus call's result hangs on -- which draws are the sample, which hypothesis wins, when a refit's set is
+// adopted -- are in ba_consensus_dev.h, shared with ba_relative_pose; this file keeps the geometry of a hypothesis
+// (hypothesis_pose from the sums onward), the inlier test and the branch of a camera that is not attempted.  The check of the
+// options of both entries (ransac_opts_check) and ba_ransac_sample are at the end of the file.
 // No floating-point atomics, no integer ones either: every output has one writer.
 // Focal mode (RansacArgs.focal and the camera's f free; ba_ransac_cameras_focal): a hypothesis estimates f from its
 // own eigenvector and is scored under it -- its record carries that f, and the refits leave theirs in the scratch cameras.
@@ -19,15 +23,16 @@
 
 #include "ba_internal.h"
 
-// (ransac_mix, ransac_draw and RN_DRAWS -- splitmix64, the one generator of the sampling, host and device -- are in ba_internal.h)
-constexpr int RN_SAMPLE_MIN = 6, RN_SAMPLE_MAX = 16;
+// (ransac_mix, ransac_draw, RN_DRAWS and the limits of the options -- splitmix64, the one generator of the sampling, host and
+// device -- are in ba_internal.h)
 
 namespace {
 
-#include "ba_model_dev.h"   // cam_pre, project_pre
-#include "ba_refine_dev.h"  // wave_all_sum, p1_z, obs_used, the pieces of the linear resection
+#include "ba_model_dev.h"      // cam_pre, project_pre
+#include "ba_refine_dev.h"     // wave_all_sum, p1_z, obs_used, the pieces of the linear resection
+#include "ba_consensus_dev.h"  // the sample, the winner, the set and the adopt rule: shared with ba_pair_kernels.hip
 
-constexpr int RN_BLK = 256, RN_WAVES = RN_BLK / 64;
+constexpr int RN_BLK = CS_BLK, RN_WAVES = CS_WAVES;
 
 // the inlier test of the header under the cam_pre row P: used, in front (P1.z < 0), within tau of its measurement in raw pixels
 // (a comparison with NaN fails)
@@ -65,20 +70,11 @@ __device__ __forceinline__ bool hypothesis_pose(const RansacArgs &a, ResectScrat
   double ck1, ck2, cf = xc[8];  // (focal mode: cf is not used until the image scale takes its place)
   scoring_distortion(xc, focal, fm, ck1, ck2);
   if (d <= 0 || (!focal && (!isfinite(cf) || cf == 0.0))) return false;
-  // the sample: lane j holds draw j; a draw counts unless its observation is not used or an earlier draw hit its position
-  const uint64_t key = ransac_mix(a.seed_mix ^ (uint64_t)h);
-  const int pos = (int)ransac_draw(key, lane, d);  // < d
-  const int o = a.cam_obs[k0 + pos];
-  bool accept = obs_used(a.info, o);
-#pragma nounroll
-  for (int i = 0; i < RN_DRAWS - 1; i++) {
-    const int pi = __shfl(pos, i, 64);
-    if (i < lane && pi == pos) accept = false;
-  }
-  const unsigned long long taken = __ballot(accept);
-  if (__popcll(taken) < m) return false;
-  const bool take = accept && __popcll(taken & ((1ull << lane) - 1ull)) < m;
-  const int first = __ffsll((long long)taken) - 1;  // the lane of the first accepted draw: the provisional origin
+  // the sample: lane j holds draw j
+  const int pos = sample_position(a.seed_mix, h, lane, d), o = a.cam_obs[k0 + pos];
+  bool take;
+  int first;
+  if (!sample_take(pos, obs_used(a.info, o), lane, m, take, first)) return false;
   double X[3] = {0.0, 0.0, 0.0}, mx = 0.0, my = 0.0;
   if (take) {
     const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
@@ -163,54 +159,23 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses(RansacArgs a) {
   }
 }
 
-// the sum of v over the workgroup -> every thread (red: RN_WAVES ints; a barrier on either side)
-__device__ __forceinline__ int block_sum_int(int v, int *red, int t) {
-  v = wave_all_sum_int(v);
-  __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// One camera per workgroup: the winner among its hypotheses (the largest count, ties to the lowest h), its inlier bytes, the
-// size of the set, the winner's index and the "stopped" byte.  A camera that is not attempted: its used observations, -1, stopped.
+// One camera per workgroup: the winner among its hypotheses (consensus_winner), its inlier bytes, the size of the set, the
+// winner's index and the "stopped" byte.  A camera that is not attempted: its used observations, -1, stopped.
 __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
   __shared__ long long redk[RN_WAVES];
   __shared__ int red[RN_WAVES];
   const int t = (int)threadIdx.x, c = (int)blockIdx.x;
   const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1];
   const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  const auto obs_of = [&](int k) { return a.cam_obs[k]; };
   if (fm & POSE_MASK) {
-    int n = 0;
-    for (int k = k0 + t; k < k1; k += RN_BLK) {
-      const int o = a.cam_obs[k];
-      const int u = obs_used(a.info, o) ? 1 : 0;
-      a.inlier[o] = (uint8_t)u;
-      n += u;
-    }
-    n = block_sum_int(n, red, t);
+    const int n = consensus_mark(k0, k1, a.inlier, red, t, obs_of, [&](int o) { return obs_used(a.info, o); });
     if (t == 0) a.n_inliers[c] = n, a.best_hyp[c] = -1, a.stopped[c] = 1;
     return;
   }
-  // key = (count + 1) << 12 | (4095 - h): the largest key is the largest count at the lowest h; 0: no valid hypothesis
-  long long key = 0;
-  for (int h = t; h < a.hypotheses; h += RN_BLK) {
-    const int cnt = a.hyp_count[(int64_t)c * a.hypotheses + h];
-    if (cnt >= 0) {
-      const long long kk = ((long long)(cnt + 1) << 12) | (long long)(4095 - h);
-      key = kk > key ? kk : key;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const long long other = __shfl_xor(key, off, 64);
-    key = other > key ? other : key;
-  }
-  if ((t & 63) == 0) redk[t >> 6] = key;
-  __syncthreads();
-  for (int w = 0; w < RN_WAVES; w++) key = redk[w] > key ? redk[w] : key;
-  const int best = key ? 4095 - (int)(key & 4095) : -1, best_count = key ? (int)(key >> 12) - 1 : 0;
-  if (!key || best_count < a.min_inliers) {  // the camera fails: no inlier, the finish finds it DEGENERATE
+  int best, best_count;
+  consensus_winner(a.hyp_count + (int64_t)c * a.hypotheses, a.hypotheses, t, redk, best, best_count);
+  if (best < 0 || best_count < a.min_inliers) {  // the camera fails: no inlier, the finish finds it DEGENERATE
     for (int k = k0 + t; k < k1; k += RN_BLK) a.inlier[a.cam_obs[k]] = 0;
     if (t == 0) a.n_inliers[c] = best_count, a.best_hyp[c] = best, a.stopped[c] = 1;
     return;
@@ -219,20 +184,13 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
   const double *win = a.hyp_pose + RANSAC_HYP_DOUBLES * ((int64_t)c * a.hypotheses + best);
   scoring_distortion(a.xc + 9 * (int64_t)c, focal_mode(a.focal, fm), fm, ck1, ck2);
   pose_row(win, ck1, ck2, win[6], P);
-  int n = 0;
-  for (int k = k0 + t; k < k1; k += RN_BLK) {
-    const int o = a.cam_obs[k];
-    const int in = ransac_inlier(a, P, o) ? 1 : 0;
-    a.inlier[o] = (uint8_t)in;
-    n += in;
-  }
-  n = block_sum_int(n, red, t);
+  const int n = consensus_mark(k0, k1, a.inlier, red, t, obs_of, [&](int o) { return ransac_inlier(a, P, o); });
   if (t == 0) a.n_inliers[c] = n, a.best_hyp[c] = best, a.stopped[c] = 0;
 }
 
 // One camera per workgroup, after a refit on its set M wrote a pose into cams (the scratch copy of the cameras: its intrinsics
-// are those of x, or in focal mode what the refit wrote): M' = the inliers of the whole list under that camera; adopted iff |M'| >= |M| and M' != M, otherwise (also when the refit found no pose) M stays and the camera stops.
-// Bit 1 of an inlier byte carries M' between the two passes; every thread rewrites the bytes it wrote.
+// are those of x, or in focal mode what the refit wrote): the adopt rule of consensus_rescore on the whole list under that
+// camera; M stays and the camera stops when M' is not adopted, and when the refit found no pose.
 __global__ __launch_bounds__(RN_BLK) void k_ransac_rescore(RansacArgs a, const double *cams, const uint8_t *resect) {
   __shared__ int red[RN_WAVES];
   const int t = (int)threadIdx.x, c = (int)blockIdx.x;
@@ -246,24 +204,10 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_rescore(RansacArgs a, const d
   double P[12];
   const double *cam = cams + 9 * (int64_t)c;
   pose_row(cam, cam[6], cam[7], cam[8], P);
-  int n = 0, diff = 0;
-  for (int k = k0 + t; k < k1; k += RN_BLK) {
-    const int o = a.cam_obs[k];
-    const int in = ransac_inlier(a, P, o) ? 1 : 0, old = a.inlier[o] & 1;
-    a.inlier[o] = (uint8_t)(old | (in << 1));
-    n += in;
-    diff += in != old ? 1 : 0;
-  }
-  n = block_sum_int(n, red, t);
-  diff = block_sum_int(diff, red, t);
-  const bool adopt = n >= n_old && diff > 0;
-  for (int k = k0 + t; k < k1; k += RN_BLK) {
-    const int o = a.cam_obs[k];
-    const int b = a.inlier[o];
-    a.inlier[o] = (uint8_t)(adopt ? (b >> 1) & 1 : b & 1);
-  }
+  const int n = consensus_rescore(
+      k0, k1, n_old, a.inlier, red, t, [&](int k) { return a.cam_obs[k]; }, [&](int o) { return ransac_inlier(a, P, o); });
   if (t == 0) {
-    if (adopt) a.n_inliers[c] = n;
+    if (n >= 0) a.n_inliers[c] = n;
     else a.stopped[c] = 1;
   }
 }
@@ -299,12 +243,38 @@ int launch_ransac_mask_info(const RansacArgs &a, int64_t nobs, double *out, hipS
   return BA_LAUNCH(k_ransac_mask_info, grid_for(nobs, RN_BLK), RN_BLK, 0, st, a, nobs, out);
 }
 
+int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o, int least) {
+  if (!in) {
+    ba_set_error("%s: null options", who);
+    return BA_ERR_ARG;
+  }
+  *o = *in;
+  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
+    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
+    return BA_ERR_ARG;
+  }
+  if (o->hypotheses <= 0) o->hypotheses = 128;
+  if (o->sample <= 0) o->sample = least;
+  if (o->refits < 0) o->refits = 2;
+  if (o->hypotheses > RN_HYP_MAX || o->sample < least || o->sample > RN_SAMPLE_MAX || o->refits > RN_REFITS_MAX) {
+    ba_set_error("%s: hypotheses must be <= %d, sample in %d..%d, refits <= %d, got %d, %d, %d", who, RN_HYP_MAX, least, RN_SAMPLE_MAX,
+                 RN_REFITS_MAX, o->hypotheses, o->sample, o->refits);
+    return BA_ERR_ARG;
+  }
+  if (o->min_inliers <= 0) o->min_inliers = o->sample;  // (>= least)
+  if (o->min_inliers < least) {
+    ba_set_error("%s: min_inliers must be >= %d (<= 0: max(sample, %d)), got %d", who, least, least, o->min_inliers);
+    return BA_ERR_ARG;
+  }
+  return BA_OK;
+}
+
 // the sampling alone, on the host (no device is touched)
 extern "C" int ba_ransac_sample(uint64_t seed, int hypothesis, int64_t degree, const uint8_t *used, int sample, int64_t *pos,
                                 int *n_taken) {
-  if (sample <= 0) sample = RN_SAMPLE_MIN;
-  if (!pos || !n_taken || hypothesis < 0 || degree < 0 || degree > (int64_t)INT32_MAX || sample < RN_SAMPLE_MIN || sample > RN_SAMPLE_MAX) {
-    ba_set_error("ba_ransac_sample: null argument, hypothesis < 0, degree outside 0..2^31 - 1 or sample outside %d..%d", RN_SAMPLE_MIN,
+  if (sample <= 0) sample = RS_MIN_OBS;
+  if (!pos || !n_taken || hypothesis < 0 || degree < 0 || degree > (int64_t)INT32_MAX || sample < RS_MIN_OBS || sample > RN_SAMPLE_MAX) {
+    ba_set_error("ba_ransac_sample: null argument, hypothesis < 0, degree outside 0..2^31 - 1 or sample outside %d..%d", RS_MIN_OBS,
                  RN_SAMPLE_MAX);
     return BA_ERR_ARG;
   }

@@ -328,8 +328,9 @@ __device__ __forceinline__ bool pose_from_eigenvector(ResectScratch &sh, int i1,
 // rays d~ = (s (q - c), -1) the 9 x 9 normal matrix is M = sum a a', a = d~_b (x) d~_a (row-major e~), and the eigenvector of its
 // smallest eigenvalue is E~.  M sits in the 12 x 12 of jacobi12 with trace(M) on the three spare diagonal entries and zeros beside
 // them (a rotation with a_pq = 0 is skipped: the spare entries never move).  A caller gathers its matches about the first of the
-// set, reduces the 6 sums of the two images (image_stats), then the 45 sums (epipolar_terms), and runs the steps below in their
-// order: k_pair_hypotheses per wave, k_pair_fit per workgroup -- the same functions, so the same bits from the same sums.
+// set, reduces the 6 sums of the two images (image_stats), then the 45 sums (epipolar_terms), runs essential_from_sums and counts
+// the matches in front of each candidate (pair_depths) for pair_pose_winner: k_pair_hypotheses per wave, k_pair_fit per
+// workgroup -- the same functions, so the same bits from the same sums.
 constexpr int EP_SUMS = 45;        // M packed lower row-major
 constexpr int EP_MIN_MATCHES = 8;  // 9 unknowns up to scale, one equation per match
 
@@ -421,6 +422,22 @@ __device__ __forceinline__ void essential_candidates(PairScratch &sh, int i1, co
   const double u0 = rs.U[jm], u1 = rs.U[3 + jm], u2 = rs.U[6 + jm];
   const double un = sqrt((u0 * u0 + u1 * u1) + u2 * u2);
   sh.tn[0] = u0 / un, sh.tn[1] = u1 / un, sh.tn[2] = u2 / un;
+}
+
+// The fit from the 45 sums sh.S (all finite, a Sync behind their writes) of rays normalised with (c, s) per image: M, its smallest
+// eigenvector, the candidates of essential_candidates (lane 0; a Sync behind them).  false: the eigenvector is not determined.
+// Called by `lanes` lanes (t: 0 .. lanes - 1) that Sync orders, as jacobi12; the result is uniform over them.
+template <void (*Sync)()>
+__device__ __forceinline__ bool essential_from_sums(PairScratch &sh, int t, int lanes, const double ca[2], double sa, const double cb[2],
+                                                    double sb) {
+  const double tr = epipolar_trace(sh.S);
+  for (int e = t; e < 144; e += lanes) sh.rs.M[e] = epipolar_matrix_entry(sh.S, tr, e);
+  jacobi12<Sync>(sh.rs.M, sh.rs.V, t, lanes);
+  int i1;
+  if (!smallest_eigenpair<9>(sh.rs.M, i1)) return false;
+  if (t == 0) essential_candidates(sh, i1, ca, sa, cb, sb);
+  Sync();
+  return true;
 }
 
 // (alpha, beta) of alpha R d_a + t = beta d_b from its 2 x 2 normal equations, d = (q, -1); t = sgn tn
