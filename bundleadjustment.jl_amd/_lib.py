@@ -74,7 +74,7 @@ SYMBOLS = [
     "ba_refine_cameras", "ba_refine_cameras_dev", "ba_resect_cameras", "ba_resect_cameras_dev",
     "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
     "ba_resect_cameras_focal", "ba_resect_cameras_focal_dev", "ba_ransac_cameras_focal", "ba_ransac_cameras_focal_dev",
-    "ba_pair_matches", "ba_relative_pose",
+    "ba_pair_matches", "ba_relative_pose", "ba_relative_pose_five_point", "ba_five_point",
 ]
 
 _lib = None
@@ -163,6 +163,8 @@ def lib():
     L.ba_ransac_sample.argtypes = [C.c_uint64, C.c_int, i64, vp, C.c_int, vp, C.POINTER(C.c_int)]
     L.ba_pair_matches.argtypes = [i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     L.ba_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
+    L.ba_relative_pose_five_point.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
+    L.ba_five_point.argtypes = [vp, i64, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -560,11 +562,14 @@ POINT_BEHIND = 0x80
 RANSAC_KEYS = ("threshold", "hypotheses", "sample", "refits", "min_inliers", "seed")
 
 
-def ransac_opts(ransac, least=6):
+def ransac_opts(ransac, least=6, most=16, least_set=None):
     """RansacOpts of the dict `ransac` -- threshold (pixels, required), hypotheses (None or <= 0: 128; at most 4096), sample
     (None or <= 0: 6; 6..16), refits (None or < 0: 2; at most 8), min_inliers (None or <= 0: max(sample, 6); at least 6), seed
     (0 .. 2^64 - 1, default 0) -- or ValueError, before any device call.  least: the smallest sample and min_inliers of the
-    entry (6: the resection; 8: relative_pose, where it is also the default sample)."""
+    entry (6: the resection; 8: relative_pose, where it is also the default sample).  most: the largest sample; least_set: the
+    smallest min_inliers where it is not `least` (relative_pose_five_point: least = most = 5, a sample of exactly 5, and
+    least_set = 8, the sets of the eight-point fits behind it)."""
+    least_set = least if least_set is None else least_set
     if not isinstance(ransac, dict):
         raise ValueError(f"ransac must be a dict with the keys {', '.join(RANSAC_KEYS)} (or None), got {ransac!r}")
     unknown = [k for k in ransac if k not in RANSAC_KEYS]
@@ -588,12 +593,13 @@ def ransac_opts(ransac, least=6):
         ints[key] = int(v)
     if ints["hypotheses"] > 4096:
         raise ValueError(f"ransac: hypotheses must be <= 4096, got {ints['hypotheses']}")
-    if ints["sample"] > 0 and not least <= ints["sample"] <= 16:
-        raise ValueError(f"ransac: sample must lie in {least}..16, got {ints['sample']}")
+    if ints["sample"] > 0 and not least <= ints["sample"] <= most:
+        want = f"be {least}" if least == most else f"lie in {least}..{most}"
+        raise ValueError(f"ransac: sample must {want}, got {ints['sample']}")
     if ints["refits"] > 8:
         raise ValueError(f"ransac: refits must be <= 8, got {ints['refits']}")
-    if 0 < ints["min_inliers"] < least:
-        raise ValueError(f"ransac: min_inliers must be >= {least}, got {ints['min_inliers']}")
+    if 0 < ints["min_inliers"] < least_set:
+        raise ValueError(f"ransac: min_inliers must be >= {least_set}, got {ints['min_inliers']}")
     if not 0 <= ints["seed"] < 1 << 64:
         raise ValueError(f"ransac: seed must lie in 0 .. 2^64 - 1, got {ints['seed']}")
     for key in ("hypotheses", "sample", "refits", "min_inliers"):

@@ -409,8 +409,10 @@ constexpr int RN_DRAWS = 64;  // draws per hypothesis: one per lane
 // the limits of ba_ransac_opts: the largest sample, hypotheses per list (the selection key holds h in 12 bits) and refits
 constexpr int RN_SAMPLE_MAX = 16, RN_HYP_MAX = 4096, RN_REFITS_MAX = 8;
 // The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message.  least: the smallest
-// sample and set of the caller's fit (RS_MIN_OBS of the resection, EP_MIN_MATCHES of the relative pose)
-int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *out, int least);
+// sample and set of the caller's fit (RS_MIN_OBS of the resection, EP_MIN_MATCHES of the relative pose).  Where the sample of
+// a hypothesis and the fit of a set differ (the five-point entry: a sample of exactly 5, sets of 8 for the eight-point fits
+// behind it) least_set is the smallest set and most the largest sample; 0: least and RN_SAMPLE_MAX.
+int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *out, int least, int least_set = 0, int most = 0);
 
 // ---- relative pose of camera pairs (ba_relative_pose; ba_pair_kernels.hip) -------------------------------------
 // The per-call device buffers (allocated at the first call, grown when a call needs more): per pair the first match of its
@@ -423,6 +425,10 @@ struct PairWork {
   DevBuf<double> intr, rays, hyp_pose, pose;
   DevBuf<uint8_t> inlier, stopped, status;
   int64_t pair_cap = 0, match_cap = 0, hyp_cap = 0;
+  // ba_five_point: the tuples (n x 5 x 2 per image), their solutions (n x 10 x 9) and counts
+  DevBuf<double> five_qa, five_qb, five_E;
+  DevBuf<int> five_n;
+  int64_t five_cap = 0;
 };
 // what the kernels of ba_relative_pose work on
 struct PairArgs {

@@ -1,4 +1,4 @@
-// Two-view relative pose (ba_pair_matches, ba_relative_pose; include/ba_hip.h, "relative pose of camera pairs").
+// Two-view relative pose (ba_pair_matches, ba_relative_pose, ba_relative_pose_five_point, ba_five_point; include/ba_hip.h, "relative pose of camera pairs").
 // gfx950 only.
 //
 // The host lists the matches of every pair (pair_match_lists: the points both cameras observe, ordered by camera a's list) and
@@ -9,6 +9,9 @@
 // k_ransac_hypotheses: a wave draws its sample (one draw per lane), takes the 6 + 45 sums through wave_all_sum, runs the linear
 // fit of ba_refine_dev.h (essential_from_sums<wave_sync>: no workgroup barrier, a void or degenerate wave simply leaves) and
 // counts the inliers of the pair's whole list in a strided pass over the records.
+// k_pair_hypotheses5 (ba_relative_pose_five_point): the same layout with the five-point solver of ba_refine_dev.h as the
+// generator: every real essential matrix through five sampled matches is scored, the best is the hypothesis.  k_five_point
+// (ba_five_point) runs that solver alone, one wave per tuple.
 // k_pair_select (one workgroup per pair): the states that need no fit, the winner, its inlier bytes.
 // k_pair_fit (one workgroup per pair): the sums over the current set in a fixed order (strided partial sums per thread, the
 // butterfly of a wave, the four waves in order), the same linear fit (essential_from_sums<__syncthreads>), then either the
@@ -130,6 +133,96 @@ __global__ __launch_bounds__(PR_BLK) void k_pair_hypotheses(PairArgs a) {
     }
   }
   if (lane == 0) a.hyp_count[slot] = count;
+}
+
+// the LDS of one wave of the five-point kernels: the fit's scratch (the null space goes through its 12 x 12) and the solver's
+struct FiveSlab {
+  PairScratch ps;
+  FiveScratch fs;
+};
+
+// Hypothesis h of a pair from the five-point solver (ba_relative_pose_five_point), the layout of k_pair_hypotheses:
+// the wave draws five matches, solves for the essential matrices through them (five_point_solve) and takes every real solution
+// through the second half of the eight-point fit -- the SVD, the four candidates, the cheirality vote over the five, the rotation
+// vector -- and through one strided pass over the pair's records.  The hypothesis is the solution with the largest count, ties to
+// the one found first; no sample, no solution or no solution with a match in front: void.
+__global__ __launch_bounds__(PR_BLK) void k_pair_hypotheses5(PairArgs a) {
+  __shared__ FiveSlab shs[PR_WAVES];  // one wave's slab each
+  const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+  const int pr = (int)blockIdx.x, h = (int)blockIdx.y * PR_WAVES + wv;
+  if (h >= a.hypotheses) return;
+  const int k0 = a.match_ptr[pr], k1 = a.match_ptr[pr + 1];
+  const double *in = a.intr + 6 * (int64_t)pr;
+  const int64_t slot = (int64_t)pr * a.hypotheses + h;
+  PairScratch &sh = shs[wv].ps;
+  FiveScratch &fs = shs[wv].fs;
+  const int d = k1 - k0;
+  int best = -1;
+  double keep = 0.0;  // lanes 0..2: r of the best solution so far, lanes 3..5: its t
+  bool take = false;
+  int first = 0;
+  const int pos = d > 0 ? sample_position(a.seed_mix, h, lane, d) : 0;
+  const double *ray = a.rays + PAIR_RAY * (int64_t)(k0 + pos);
+  if (d > 0 && pair_focals_ok(in) && sample_take(pos, ray[4] != 0.0, lane, FP_POINTS, take, first)) {
+    double qax = 0.0, qay = 0.0, qbx = 0.0, qby = 0.0, da[3] = {0.0, 0.0, 0.0}, db[3] = {0.0, 0.0, 0.0};
+    if (take) {
+      qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
+      da[0] = qax, da[1] = qay, da[2] = -1.0, db[0] = qbx, db[1] = qby, db[2] = -1.0;
+    }
+    const int n_sol = five_point_solve(sh, fs, da, db, lane);
+#pragma nounroll
+    for (int s = 0; s < n_sol; s++) {
+      if (lane == 0) {
+        for (int e = 0; e < 9; e++) sh.rs.W[e] = fs.E[9 * s + e];
+        essential_decompose(sh);
+      }
+      wave_sync();
+      int cnt[4];
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        double al, be;
+        pair_depths(sh.Rc + 9 * (c >> 1), sh.tn, (c & 1) ? -1.0 : 1.0, qax, qay, qbx, qby, al, be);
+        cnt[c] = __popcll(__ballot(take && al > 0.0 && be > 0.0));
+      }
+      if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) sh.cnt[c] = cnt[c];
+        sh.ok = pair_pose_winner(sh) ? 1 : 0;
+      }
+      wave_sync();
+      if (sh.ok != 0) {
+        PairPose P;
+        pair_pose_of(sh.rs.r, sh.t, P);
+        int count = 0;
+        for (int k = k0 + lane; k < k1; k += 64) count += pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, in[2], in[5], a.tau2) ? 1 : 0;
+        count = wave_all_sum_int(count);
+        if (count > best) {
+          best = count;
+          if (lane < 3) keep = sh.rs.r[lane];
+          else if (lane < 6) keep = sh.t[lane - 3];
+        }
+      }
+      wave_sync();  // (lane 0 writes the next solution over what the wave has read)
+    }
+  }
+  if (best >= 0 && lane < PAIR_HYP_DOUBLES) a.hyp_pose[PAIR_HYP_DOUBLES * slot + lane] = keep;
+  if (lane == 0) a.hyp_count[slot] = best;
+}
+
+// ba_five_point: one wave per tuple, lane j < 5 holds match j; E: 10 x 9 per tuple, the unused slots NaN
+__global__ __launch_bounds__(PR_BLK) void k_five_point(int64_t n, const double *qa, const double *qb, double *E, int *n_sol) {
+  __shared__ FiveSlab shs[PR_WAVES];
+  const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * PR_WAVES + wv;
+  if (i >= n) return;
+  double da[3] = {0.0, 0.0, 0.0}, db[3] = {0.0, 0.0, 0.0};
+  if (lane < FP_POINTS) {
+    const int64_t at = 2 * (FP_POINTS * i + lane);
+    da[0] = qa[at], da[1] = qa[at + 1], da[2] = -1.0, db[0] = qb[at], db[1] = qb[at + 1], db[2] = -1.0;
+  }
+  const int ns = five_point_solve(shs[wv].ps, shs[wv].fs, da, db, lane);
+  for (int e = lane; e < 9 * FP_MAX_SOL; e += 64) E[9 * FP_MAX_SOL * i + e] = e < 9 * ns ? shs[wv].fs.E[e] : __longlong_as_double(0x7ff8000000000000ll);
+  if (lane == 0) n_sol[i] = ns;
 }
 
 // a pair that ends here: its state, no inlier, n matches counted, winner h (or -1)
@@ -399,12 +492,15 @@ extern "C" int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const
   return BA_OK;
 }
 
-extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
-                                const ba_ransac_opts *opts, double *pose, uint8_t *status, int64_t *match_ptr, uint8_t *inlier,
-                                int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
-  const char *who = "ba_relative_pose";
+namespace {
+
+// ba_relative_pose (five == false) and ba_relative_pose_five_point (five == true): one host path, the hypothesis kernel differs
+int relative_pose_call(const char *who, bool five, ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1,
+                       const int64_t *pair_b1, const ba_ransac_opts *opts, double *pose, uint8_t *status, int64_t *match_ptr,
+                       uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
   ba_ransac_opts o = {};
-  if (opts) BA_CHECK(ransac_opts_check(who, opts, &o, EP_MIN_MATCHES));
+  if (five) BA_CHECK(ransac_opts_check(who, opts, &o, FP_POINTS, EP_MIN_MATCHES, FP_POINTS));
+  else if (opts) BA_CHECK(ransac_opts_check(who, opts, &o, EP_MIN_MATCHES));
   if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !pose || !status))) {
     ba_set_error("%s: null argument or npairs < 0", who);
     return BA_ERR_ARG;
@@ -452,7 +548,8 @@ extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, 
   a.hypotheses = opts ? o.hypotheses : 0, a.sample = o.sample, a.min_inliers = o.min_inliers;
   a.seed_mix = ransac_seed_mix(o.seed), a.tau2 = o.threshold * o.threshold;
   BA_CHECK(BA_LAUNCH(k_pair_rays, grid_for(nmatch, PR_BLK), PR_BLK, 0, st, a, nmatch));
-  if (opts) BA_CHECK(BA_LAUNCH(k_pair_hypotheses, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
+  if (five) BA_CHECK(BA_LAUNCH(k_pair_hypotheses5, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
+  else if (opts) BA_CHECK(BA_LAUNCH(k_pair_hypotheses, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
   BA_CHECK(BA_LAUNCH(k_pair_select, (unsigned)npairs, PR_BLK, 0, st, a));
   for (int it = 0; opts && it < o.refits; it++) BA_CHECK(BA_LAUNCH(k_pair_fit, (unsigned)npairs, PR_BLK, 0, st, a, 0));
   BA_CHECK(BA_LAUNCH(k_pair_fit, (unsigned)npairs, PR_BLK, 0, st, a, 1));
@@ -471,5 +568,52 @@ extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, 
     if (s == BA_RP_OK)  // (a pair in any other state leaves its six entries as the caller filled them)
       for (int j = 0; j < 6; j++) pose[6 * i + j] = h_pose[(size_t)(6 * i + j)];
   }
+  return BA_OK;
+}
+
+}  // namespace
+
+extern "C" int ba_relative_pose(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                const ba_ransac_opts *opts, double *pose, uint8_t *status, int64_t *match_ptr, uint8_t *inlier,
+                                int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
+  return relative_pose_call("ba_relative_pose", false, p, x, npairs, pair_a1, pair_b1, opts, pose, status, match_ptr, inlier, n_inliers,
+                            best_hyp, counts);
+}
+
+extern "C" int ba_relative_pose_five_point(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                           const ba_ransac_opts *opts, double *pose, uint8_t *status, int64_t *match_ptr,
+                                           uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
+  return relative_pose_call("ba_relative_pose_five_point", true, p, x, npairs, pair_a1, pair_b1, opts, pose, status, match_ptr, inlier,
+                            n_inliers, best_hyp, counts);
+}
+
+extern "C" int ba_five_point(ba_problem *p, int64_t n, const double *qa, const double *qb, double *E, int32_t *n_sol) {
+  if (!p || n < 0 || (n > 0 && (!qa || !qb || !E || !n_sol))) {
+    ba_set_error("ba_five_point: null argument or n < 0");
+    return BA_ERR_ARG;
+  }
+  if (n > (int64_t)INT32_MAX / (9 * FP_MAX_SOL)) {
+    ba_set_error("ba_five_point: %lld tuples: more than %lld", (long long)n, (long long)(INT32_MAX / (9 * FP_MAX_SOL)));
+    return BA_ERR_ARG;
+  }
+  if (n == 0) return BA_OK;
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  PairWork &w = p->pairs;
+  if (w.five_cap < n) {
+    w.five_cap = 0;
+    BA_CHECK(w.five_qa.alloc(2 * FP_POINTS * n));
+    BA_CHECK(w.five_qb.alloc(2 * FP_POINTS * n));
+    BA_CHECK(w.five_E.alloc(9 * FP_MAX_SOL * n));
+    BA_CHECK(w.five_n.alloc(n));
+    w.five_cap = n;
+  }
+  const size_t in_bytes = (size_t)(2 * FP_POINTS * n) * sizeof(double);
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.five_qa, qa, in_bytes, hipMemcpyHostToDevice, st));
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.five_qb, qb, in_bytes, hipMemcpyHostToDevice, st));
+  BA_CHECK(BA_LAUNCH(k_five_point, grid_for(n, PR_WAVES), PR_BLK, 0, st, n, w.five_qa, w.five_qb, w.five_E, w.five_n));
+  BA_HIP_CHECK(hipMemcpyAsync(E, w.five_E, (size_t)(9 * FP_MAX_SOL * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(n_sol, w.five_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
 }

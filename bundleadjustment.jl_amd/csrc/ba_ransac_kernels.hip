@@ -243,7 +243,9 @@ int launch_ransac_mask_info(const RansacArgs &a, int64_t nobs, double *out, hipS
   return BA_LAUNCH(k_ransac_mask_info, grid_for(nobs, RN_BLK), RN_BLK, 0, st, a, nobs, out);
 }
 
-int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o, int least) {
+int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts *o, int least, int least_set, int most) {
+  if (least_set <= 0) least_set = least;
+  if (most <= 0) most = RN_SAMPLE_MAX;
   if (!in) {
     ba_set_error("%s: null options", who);
     return BA_ERR_ARG;
@@ -256,14 +258,18 @@ int ransac_opts_check(const char *who, const ba_ransac_opts *in, ba_ransac_opts 
   if (o->hypotheses <= 0) o->hypotheses = 128;
   if (o->sample <= 0) o->sample = least;
   if (o->refits < 0) o->refits = 2;
-  if (o->hypotheses > RN_HYP_MAX || o->sample < least || o->sample > RN_SAMPLE_MAX || o->refits > RN_REFITS_MAX) {
-    ba_set_error("%s: hypotheses must be <= %d, sample in %d..%d, refits <= %d, got %d, %d, %d", who, RN_HYP_MAX, least, RN_SAMPLE_MAX,
-                 RN_REFITS_MAX, o->hypotheses, o->sample, o->refits);
+  if (o->hypotheses > RN_HYP_MAX || o->sample < least || o->sample > most || o->refits > RN_REFITS_MAX) {
+    if (least == most)
+      ba_set_error("%s: hypotheses must be <= %d, sample must be %d, refits <= %d, got %d, %d, %d", who, RN_HYP_MAX, least, RN_REFITS_MAX,
+                   o->hypotheses, o->sample, o->refits);
+    else
+      ba_set_error("%s: hypotheses must be <= %d, sample in %d..%d, refits <= %d, got %d, %d, %d", who, RN_HYP_MAX, least, most,
+                   RN_REFITS_MAX, o->hypotheses, o->sample, o->refits);
     return BA_ERR_ARG;
   }
-  if (o->min_inliers <= 0) o->min_inliers = o->sample;  // (>= least)
-  if (o->min_inliers < least) {
-    ba_set_error("%s: min_inliers must be >= %d (<= 0: max(sample, %d)), got %d", who, least, least, o->min_inliers);
+  if (o->min_inliers <= 0) o->min_inliers = o->sample > least_set ? o->sample : least_set;  // (>= least_set)
+  if (o->min_inliers < least_set) {
+    ba_set_error("%s: min_inliers must be >= %d (<= 0: max(sample, %d)), got %d", who, least_set, least_set, o->min_inliers);
     return BA_ERR_ARG;
   }
   return BA_OK;

@@ -1,5 +1,5 @@
 // Device pieces shared by the block refinements and the relative pose (ba_point_kernels.hip, ba_camera_kernels.hip,
-// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5o).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
+// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5p).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
 // The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
@@ -424,6 +424,28 @@ __device__ __forceinline__ void essential_candidates(PairScratch &sh, int i1, co
   sh.tn[0] = u0 / un, sh.tn[1] = u1 / un, sh.tn[2] = u2 / un;
 }
 
+// The second half of essential_candidates from E in sh.rs.W (row-major; overwritten) on, for the five-point solver, which
+// enters with each of its solutions.  A copy: with a call of it in essential_candidates the disassembly of k_pair_fit differs
+// (tools/compare_code_objects.py against the build before).  (one lane)
+__device__ __forceinline__ void essential_decompose(PairScratch &sh) {
+  ResectScratch &rs = sh.rs;
+  nearest_rotation(rs);
+  int jm = 0;
+  for (int j = 0; j < 3; j++)
+    if (rs.sg[j] < rs.sg[jm]) jm = j;
+  const int ja = (jm + 1) % 3, jb = (jm + 2) % 3;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) {
+      const double plane = rs.U[3 * i + jb] * rs.V3[3 * j + ja] - rs.U[3 * i + ja] * rs.V3[3 * j + jb];
+      const double axis = rs.U[3 * i + jm] * rs.V3[3 * j + jm];
+      sh.Rc[3 * i + j] = axis + plane;
+      sh.Rc[9 + 3 * i + j] = axis - plane;
+    }
+  const double u0 = rs.U[jm], u1 = rs.U[3 + jm], u2 = rs.U[6 + jm];
+  const double un = sqrt((u0 * u0 + u1 * u1) + u2 * u2);
+  sh.tn[0] = u0 / un, sh.tn[1] = u1 / un, sh.tn[2] = u2 / un;
+}
+
 // The fit from the 45 sums sh.S (all finite, a Sync behind their writes) of rays normalised with (c, s) per image: M, its smallest
 // eigenvector, the candidates of essential_candidates (lane 0; a Sync behind them).  false: the eigenvector is not determined.
 // Called by `lanes` lanes (t: 0 .. lanes - 1) that Sync orders, as jacobi12; the result is uniform over them.
@@ -505,4 +527,289 @@ __device__ __forceinline__ bool pair_inlier(const double *ray, const PairPose &P
   const double num = (qbx * l0 + qby * l1) - l2;
   const double den = (l0 * l0 + l1 * l1) / (fb * fb) + (m0 * m0 + m1 * m1) / (fa * fa);
   return num * num / den <= tau2;
+}
+
+// ---- the five-point relative pose: the essential matrices through five matches -----------------------------------
+// Rays are raw, d = (q, -1) in both images.  The 5 x 9 system a_k = d_b (x) d_a has a four-dimensional null space; its basis
+// X, Y, Z, W is the eigenvectors of the four smallest eigenvalues of sum a a' (the 45 sums of epipolar_terms in jacobi12), and
+// E = x X + y Y + z Z + W.  det E = 0 and 2 E E' E - tr(E E') E = 0 are ten cubics in the 20 monomials of (x, y, z), columns in
+// the order x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1.  Gauss-Jordan on the first ten columns
+// leaves each of them as a polynomial in the last ten; (row x^2z) - z (row x^2), (row y^2z) - z (row y^2) and
+// (row xyz) - z (row xy) hold no monomial of the first ten: B(z) (x, y, 1)' = 0 with a 3 x 3 matrix of polynomials of degree
+// 3, 3, 4 in z.  det B(z) has degree 10; its roots come from the simultaneous iteration of Aberth and Ehrlich, one root per lane,
+// and a root is real when its imaginary part is within 1e-7 of its modulus.  (x, y) is the null vector of B at the root, and
+// (x, y, z) takes two Gauss-Newton steps on the ten cubics (five_polish).
+constexpr int FP_POINTS = 5, FP_MAX_SOL = 10, FP_ROOT_ITERS = 100;
+constexpr int FP_ROWS = 10, FP_COLS = 20, FP_BROW = 13;  // a row of B: x (4 coefficients, ascending), y (4), 1 (5)
+
+// the LDS of one solve, beside the wave's PairScratch (whose S, M and V the null space goes through)
+struct FiveScratch {
+  double N[36];                 // X, Y, Z, W: 3 x 3 row-major each
+  double C[FP_ROWS * FP_COLS];  // the ten cubics
+  double B[3 * FP_BROW];
+  double P[11];                 // det B(z), ascending
+  double E[9 * FP_MAX_SOL];     // the real solutions, |E|_F = 1
+};
+
+// the variables (0: x, 1: y, 2: z, 3: the constant 1) of monomial m in the column order above, two bits each
+__device__ __forceinline__ int five_monomial(int m) {
+  // (a | b << 2 | c << 4) per monomial, six bits each: monomials 0..9 and 10..19
+  const unsigned long long lo = 0ull | (21ull << 6) | (16ull << 12) | (20ull << 18) | (32ull << 24) | (48ull << 30) | (37ull << 36) |
+                                (53ull << 42) | (36ull << 48) | (52ull << 54);
+  const unsigned long long hi = 40ull | (56ull << 6) | (60ull << 12) | (41ull << 18) | (57ull << 24) | (61ull << 30) | (42ull << 36) |
+                                (58ull << 42) | (62ull << 48) | (63ull << 54);
+  return (int)(((m < 10 ? lo : hi) >> (6 * (m < 10 ? m : m - 10))) & 63ull);
+}
+
+// The trilinear form of constraint `row` on the 3 x 3 matrices A, B, C (LDS): row 0, the determinant with row 0 of A, row 1 of
+// B and row 2 of C; rows 1..9, entry (i, j) of 2 A B' C - tr(A B') C.
+__device__ __forceinline__ double five_form(int row, const double *A, const double *B, const double *C) {
+  if (row == 0)
+    return (A[0] * (B[4] * C[8] - B[5] * C[7]) + A[1] * (B[5] * C[6] - B[3] * C[8])) + A[2] * (B[3] * C[7] - B[4] * C[6]);
+  const int i = (row - 1) / 3, j = (row - 1) % 3;
+  double tr = 0.0, v = 0.0;
+#pragma unroll
+  for (int l = 0; l < 3; l++) {
+    const double ab = (A[3 * i] * B[3 * l] + A[3 * i + 1] * B[3 * l + 1]) + A[3 * i + 2] * B[3 * l + 2];  // (A B')_il
+    v += ab * C[3 * l + j];
+    tr += (A[3 * l] * B[3 * l] + A[3 * l + 1] * B[3 * l + 1]) + A[3 * l + 2] * B[3 * l + 2];
+  }
+  return 2.0 * v - tr * C[3 * i + j];
+}
+
+// p(z) and p'(z) of the polynomial P (11 coefficients, ascending; LDS) at the complex z
+__device__ __forceinline__ void five_horner(const double *P, double zr, double zi, double &pr, double &pi, double &dr, double &di) {
+  pr = P[10], pi = 0.0, dr = 0.0, di = 0.0;
+#pragma unroll
+  for (int i = 9; i >= 0; i--) {
+    const double tr = (dr * zr - di * zi) + pr, ti = (dr * zi + di * zr) + pi;
+    dr = tr, di = ti;
+    const double ur = (pr * zr - pi * zi) + P[i], ui = pr * zi + pi * zr;
+    pr = ur, pi = ui;
+  }
+}
+
+// v^e for e in 0..3 and its derivative, from v, v^2, v^3
+__device__ __forceinline__ double five_power(int e, double v, double v2, double v3) { return e == 0 ? 1.0 : (e == 1 ? v : (e == 2 ? v2 : v3)); }
+__device__ __forceinline__ double five_slope(int e, double v, double v2) { return e == 0 ? 0.0 : (e == 1 ? 1.0 : (e == 2 ? 2.0 * v : 3.0 * v2)); }
+
+// Two Gauss-Newton steps on the ten cubics C (10 x 20, LDS; any row-equivalent form) in (x, y, z): a root of the degree-10
+// determinant carries the conditioning of that polynomial, the cubics carry the solution's own.  A step that is not finite is
+// not taken.  (one lane per root)
+__device__ __forceinline__ void five_polish(const double *C, double &x, double &y, double &z) {
+#pragma nounroll
+  for (int it = 0; it < 2; it++) {
+    const double x2 = x * x, x3 = x2 * x, y2 = y * y, y3 = y2 * y, z2 = z * z, z3 = z2 * z;
+    double axx = 0.0, axy = 0.0, axz = 0.0, ayy = 0.0, ayz = 0.0, azz = 0.0, gx = 0.0, gy = 0.0, gz = 0.0;
+#pragma nounroll
+    for (int i = 0; i < FP_ROWS; i++) {
+      double f = 0.0, fx = 0.0, fy = 0.0, fz = 0.0;
+#pragma nounroll
+      for (int m = 0; m < FP_COLS; m++) {
+        const int code = five_monomial(m), a = code & 3, b = (code >> 2) & 3, c = (code >> 4) & 3;
+        const int ex = (a == 0) + (b == 0) + (c == 0), ey = (a == 1) + (b == 1) + (c == 1), ez = (a == 2) + (b == 2) + (c == 2);
+        const double px = five_power(ex, x, x2, x3), py = five_power(ey, y, y2, y3), pz = five_power(ez, z, z2, z3);
+        const double w = C[FP_COLS * i + m];
+        f += w * (px * py * pz);
+        fx += w * (five_slope(ex, x, x2) * py * pz);
+        fy += w * (px * five_slope(ey, y, y2) * pz);
+        fz += w * (px * py * five_slope(ez, z, z2));
+      }
+      axx += fx * fx, axy += fx * fy, axz += fx * fz, ayy += fy * fy, ayz += fy * fz, azz += fz * fz;
+      gx += fx * f, gy += fy * f, gz += fz * f;
+    }
+    // (J'J) step = J'f by cofactors
+    const double c00 = ayy * azz - ayz * ayz, c01 = axz * ayz - axy * azz, c02 = axy * ayz - axz * ayy;
+    const double c11 = axx * azz - axz * axz, c12 = axy * axz - axx * ayz, c22 = axx * ayy - axy * axy;
+    const double det = (axx * c00 + axy * c01) + axz * c02;
+    const double sx = ((c00 * gx + c01 * gy) + c02 * gz) / det, sy = ((c01 * gx + c11 * gy) + c12 * gz) / det;
+    const double sz = ((c02 * gx + c12 * gy) + c22 * gz) / det;
+    if (isfinite(sx) && isfinite(sy) && isfinite(sz)) x -= sx, y -= sy, z -= sz;
+  }
+}
+
+// The essential matrices through the wave's five matches: a lane with take holds one match as the rays da, db = (q, -1), every
+// other lane passes zeros.  Returns the number of real solutions (0..10; 0 also for sums that are not finite, a null space that
+// is not four-dimensional -- lambda_5 <= 1e-12 lambda_9 -- and a pivot that is 0 or not finite), fs.E[9 s ..] the solutions in
+// the order of the lanes that hold their roots, a wave_sync behind them.  Called by a whole wave; the result is uniform over it.
+__device__ __forceinline__ int five_point_solve(PairScratch &sh, FiveScratch &fs, const double da[3], const double db[3], int lane) {
+  {
+    double acc[EP_SUMS];
+    epipolar_terms(da, db, acc);
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < EP_SUMS; i++) {
+      acc[i] = wave_all_sum(acc[i]);
+      ok = ok && isfinite(acc[i]);
+    }
+    if (!ok) return 0;
+    if (lane == 0) {
+#pragma unroll
+      for (int i = 0; i < EP_SUMS; i++) sh.S[i] = acc[i];
+    }
+  }
+  wave_sync();
+  const double tr = epipolar_trace(sh.S);
+  for (int e = lane; e < 144; e += 64) sh.rs.M[e] = epipolar_matrix_entry(sh.S, tr, e);
+  jacobi12<wave_sync>(sh.rs.M, sh.rs.V, lane, 64);
+  {  // lane j < 9 ranks eigenvalue j (ties to the lower index); ranks 0..3 are the basis, 4 is lambda_5, 8 is lambda_9
+    const int j = lane < 9 ? lane : 8;
+    const double lam = sh.rs.M[13 * j];
+    int rank = 0;
+    for (int k = 0; k < 9; k++) {
+      const double lk = sh.rs.M[13 * k];
+      rank += (lk < lam || (lk == lam && k < j)) ? 1 : 0;
+    }
+    if (__ballot(lane < 9 && !isfinite(lam))) return 0;
+    const unsigned long long at5 = __ballot(lane < 9 && rank == 4), at9 = __ballot(lane < 9 && rank == 8);
+    if (!at5 || !at9) return 0;
+    const double l5 = __shfl(lam, __ffsll((long long)at5) - 1, 64), l9 = __shfl(lam, __ffsll((long long)at9) - 1, 64);
+    if (!(l5 > 1e-12 * l9)) return 0;
+    if (lane < 9 && rank < 4)
+      for (int e = 0; e < 9; e++) fs.N[9 * rank + e] = sh.rs.V[e * 12 + j];
+  }
+  wave_sync();
+  // the coefficient of monomial (a, b, c) in constraint `row`: the form summed over the orders of (a, b, c), each distinct order once
+#pragma nounroll
+  for (int e = lane; e < FP_ROWS * FP_COLS; e += 64) {
+    const int row = e / FP_COLS, code = five_monomial(e % FP_COLS);
+    const double *A = fs.N + 9 * (code & 3), *B = fs.N + 9 * ((code >> 2) & 3), *C = fs.N + 9 * ((code >> 4) & 3);
+    const double sum = ((((five_form(row, A, B, C) + five_form(row, A, C, B)) + five_form(row, B, A, C)) + five_form(row, B, C, A)) +
+                        five_form(row, C, A, B)) + five_form(row, C, B, A);
+    const double w = (A == B && B == C) ? 1.0 / 6.0 : ((A == B || B == C) ? 0.5 : 1.0);  // (a <= b <= c)
+    fs.C[e] = w * sum;
+  }
+  wave_sync();
+  // Gauss-Jordan with partial pivoting on the first ten columns, lanes over columns
+#pragma nounroll
+  for (int s = 0; s < FP_ROWS; s++) {
+    double col[FP_ROWS];
+    int pr = s;
+    double big = -1.0;
+#pragma unroll
+    for (int r = 0; r < FP_ROWS; r++) {
+      col[r] = fs.C[r * FP_COLS + s];
+      if (r >= s && fabs(col[r]) > big) big = fabs(col[r]), pr = r;
+    }
+    const double piv = fs.C[pr * FP_COLS + s], head = fs.C[s * FP_COLS + s];
+    if (!(fabs(piv) > 0.0) || !isfinite(piv)) return 0;  // (uniform)
+    wave_sync();  // (every lane has read column s)
+    if (lane < FP_COLS) {
+      const double down = fs.C[s * FP_COLS + lane], up = fs.C[pr * FP_COLS + lane] / piv;
+#pragma unroll
+      for (int r = 0; r < FP_ROWS; r++) {
+        if (r == s) continue;
+        const double f = r == pr ? head : col[r], old = r == pr ? down : fs.C[r * FP_COLS + lane];
+        fs.C[r * FP_COLS + lane] = old - f * up;
+      }
+      fs.C[s * FP_COLS + lane] = up;
+    }
+    wave_sync();
+  }
+  if (lane < 3) {  // row `lane` of B from the rows (4, 5), (6, 7), (8, 9)
+    const double *a = fs.C + (4 + 2 * lane) * FP_COLS, *b = a + FP_COLS;
+    double *o = fs.B + FP_BROW * lane;
+    o[0] = a[12], o[1] = a[11] - b[12], o[2] = a[10] - b[11], o[3] = -b[10];
+    o[4] = a[15], o[5] = a[14] - b[15], o[6] = a[13] - b[14], o[7] = -b[13];
+    o[8] = a[19], o[9] = a[18] - b[19], o[10] = a[17] - b[18], o[11] = a[16] - b[17], o[12] = -b[16];
+  }
+  wave_sync();
+  if (lane < 11) {  // coefficient `lane` of det B = sum over the rows r of B1_r (Bx_r' By_r'' - Bx_r'' By_r'), (r, r', r'') cyclic
+    double v = 0.0;
+#pragma nounroll
+    for (int r = 0; r < 3; r++) {
+      const double *b0 = fs.B + FP_BROW * r, *b1 = fs.B + FP_BROW * ((r + 1) % 3), *b2 = fs.B + FP_BROW * ((r + 2) % 3);
+      for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+          const int k = lane - i - j;
+          if (k >= 0 && k <= 4) v += b0[8 + k] * (b1[i] * b2[4 + j] - b2[i] * b1[4 + j]);
+        }
+    }
+    fs.P[lane] = v;
+  }
+  wave_sync();
+  bool fin = true;
+  for (int i = 0; i < 11; i++) fin = fin && isfinite(fs.P[i]);
+  if (!fin || fs.P[10] == 0.0) return 0;
+  // the ten roots, lane k < 10 holds root k: from a circle of the roots' geometric mean modulus
+  const int k = lane < 10 ? lane : 9;
+  double zr, zi;
+  {
+    const double g = fabs(fs.P[0] / fs.P[10]);
+    const double rad = g > 0.0 ? exp(log(g) / 10.0) : 1.0;
+    const double th = 0.4 + 0.62831853071795865 * (double)k;
+    zr = rad * cos(th), zi = rad * sin(th);
+  }
+#pragma nounroll
+  for (int it = 0; it < FP_ROOT_ITERS; it++) {
+    double pr, pi, dr, di;
+    five_horner(fs.P, zr, zi, pr, pi, dr, di);
+    const double dn = dr * dr + di * di;
+    double wr = (pr * dr + pi * di) / dn, wi = (pi * dr - pr * di) / dn;  // p / p'
+    if (pr == 0.0 && pi == 0.0) wr = 0.0, wi = 0.0;
+    double sr = 0.0, si = 0.0;  // the sum of 1 / (z_k - z_j) over the other roots
+#pragma unroll
+    for (int j = 0; j < 10; j++) {
+      const double ar = zr - __shfl(zr, j, 64), ai = zi - __shfl(zi, j, 64);
+      const double an = ar * ar + ai * ai;
+      if (j != k && an > 0.0) sr += ar / an, si -= ai / an;  // (two iterates that coincide do not repel each other)
+    }
+    const double er = 1.0 - (wr * sr - wi * si), ei = -(wr * si + wi * sr), en = er * er + ei * ei;
+    const double stepr = (wr * er + wi * ei) / en, stepi = (wi * er - wr * ei) / en;
+    zr -= stepr, zi -= stepi;
+    const bool moving = !(stepr * stepr + stepi * stepi <= 1e-20 * (zr * zr + zi * zi));
+    if (!__ballot(lane < 10 && moving)) break;
+  }
+  // a real root: two Newton steps on the real axis, (x, y) from the pair of rows of B(z) whose cross product is the largest
+  double E[9];
+  bool real = lane < 10 && isfinite(zr) && isfinite(zi) && fabs(zi) <= 1e-7 * sqrt(zr * zr + zi * zi);
+  if (real) {
+    double z = zr;
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+      double pr, pi, dr, di;
+      five_horner(fs.P, z, 0.0, pr, pi, dr, di);
+      const double step = pr / dr;
+      if (isfinite(step)) z -= step;
+    }
+    double b[9];
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const double *o = fs.B + FP_BROW * r;
+      b[3 * r] = ((o[3] * z + o[2]) * z + o[1]) * z + o[0];
+      b[3 * r + 1] = ((o[7] * z + o[6]) * z + o[5]) * z + o[4];
+      b[3 * r + 2] = (((o[12] * z + o[11]) * z + o[10]) * z + o[9]) * z + o[8];
+    }
+    double cx = 0.0, cy = 0.0, cz = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      const int r1 = (r + 1) % 3;
+      const double x = b[3 * r + 1] * b[3 * r1 + 2] - b[3 * r + 2] * b[3 * r1 + 1];
+      const double y = b[3 * r + 2] * b[3 * r1] - b[3 * r] * b[3 * r1 + 2];
+      const double w = b[3 * r] * b[3 * r1 + 1] - b[3 * r + 1] * b[3 * r1];
+      if (r == 0 || fabs(w) > fabs(cz)) cx = x, cy = y, cz = w;
+    }
+    double x = cx / cz, y = cy / cz;
+    five_polish(fs.C, x, y, z);
+    double n2 = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+      E[e] = ((x * fs.N[e] + y * fs.N[9 + e]) + z * fs.N[18 + e]) + fs.N[27 + e];
+      n2 += E[e] * E[e];
+    }
+    const double nrm = sqrt(n2);
+#pragma unroll
+    for (int e = 0; e < 9; e++) {
+      E[e] = E[e] / nrm;
+      real = real && isfinite(E[e]);
+    }
+  }
+  const unsigned long long found = __ballot(real);
+  if (real) {
+    const int slot = __popcll(found & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int e = 0; e < 9; e++) fs.E[9 * slot + e] = E[e];
+  }
+  wave_sync();
+  return __popcll(found);
 }

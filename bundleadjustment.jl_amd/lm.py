@@ -385,7 +385,11 @@ def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None):
     _lib.PAIR_STATES); `match_ptr` and, per match in the order of pair_matches, `inliers` (bool); `n_inliers`; `best_hypothesis`
     (-1: none); `counts` (pairs per state).  compose_relative turns (r, t) into camera b's pose.  On noisy data the eight-point
     fit is only a start for the refinement that follows.  Bad arguments raise ValueError before any device call."""
-    opts = None if ransac is None else _lib.ransac_opts(ransac, least=8)
+    return _relative_pose("ba_relative_pose", None if ransac is None else _lib.ransac_opts(ransac, least=8), nlp, x, pairs, obs_info)
+
+
+def _relative_pose(entry, opts, nlp, x, pairs, obs_info):
+    """the call of ba_relative_pose and of ba_relative_pose_five_point behind the check of their options"""
     info3 = _lib.obs_info_pack(obs_info)
     a1, b1 = _lib._pairs(pairs, nlp.ncams)
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -401,11 +405,38 @@ def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None):
     pose, status = np.full((n, 6), np.nan), np.zeros(n, dtype=np.uint8)
     inlier, n_in, best = np.zeros(int(mp[-1]), dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     counts, mp2 = np.zeros(len(_lib.PAIR_STATES), dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
-    _lib.check(_lib.lib().ba_relative_pose(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), None if opts is None else C.byref(opts),
-                                           _lib.ptr(pose), _lib.ptr(status), _lib.ptr(mp2), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best),
-                                           _lib.ptr(counts)))
+    _lib.check(getattr(_lib.lib(), entry)(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), None if opts is None else C.byref(opts),
+                                          _lib.ptr(pose), _lib.ptr(status), _lib.ptr(mp2), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best),
+                                          _lib.ptr(counts)))
     return dict(r=pose[:, :3].copy(), t=pose[:, 3:].copy(), status=np.array(_lib.PAIR_STATES)[status], match_ptr=mp2, inliers=inlier != 0,
                 n_inliers=n_in, best_hypothesis=best, counts={s: int(c) for s, c in zip(_lib.PAIR_STATES, counts)})
+
+
+def relative_pose_five_point(nlp, x, pairs, *, ransac, obs_info=None):
+    """relative_pose with the five-point minimal solver as the hypothesis generator of the consensus stage
+    (ba_relative_pose_five_point): every real essential matrix through five sampled matches is a candidate; the winner, the
+    refits and the final eight-point fit on the consensus set are those of relative_pose, and so is the returned dict.  ransac
+    is required: dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) with sample 5 (the default; nothing else
+    is taken) and min_inliers >= 8 (default 8).  This is the entry for noisy detections: eight noisy matches give a poor
+    hypothesis, five give a good one.  Bad arguments raise ValueError before any device call."""
+    if ransac is None:
+        raise ValueError("relative_pose_five_point: ransac is required (the five-point solver is the hypothesis generator of the consensus stage)")
+    return _relative_pose("ba_relative_pose_five_point", _lib.ransac_opts(ransac, least=5, most=5, least_set=8), nlp, x, pairs, obs_info)
+
+
+def five_point(nlp, qa, qb):
+    """The essential matrices through five matches (ba_five_point), n independent problems: qa, qb (n, 5, 2) are undistorted
+    image points already divided by f, the ray of a point is (q, -1).  Returns (E, n_sol): E (n, 10, 3, 3) holds the real
+    solutions of a problem first, each with Frobenius norm 1 (d_b' E d_a = 0), NaN in the unused slots; n_sol (n,) their number.
+    Neither the sign of a solution nor the order of the solutions is specified.  nlp supplies the device and the stream.
+    Bad arguments raise ValueError before any device call."""
+    qa, qb = np.ascontiguousarray(qa, dtype=np.float64), np.ascontiguousarray(qb, dtype=np.float64)
+    if qa.ndim != 3 or qa.shape[1:] != (5, 2) or qb.shape != qa.shape:
+        raise ValueError(f"five_point: qa and qb must both have shape (n, 5, 2), got {qa.shape} and {qb.shape}")
+    n = qa.shape[0]
+    E, n_sol = np.full((n, 10, 3, 3), np.nan), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.lib().ba_five_point(nlp.handle, n, _lib.ptr(qa), _lib.ptr(qb), _lib.ptr(E), _lib.ptr(n_sol)))
+    return E, n_sol
 
 
 def schur_pattern(nlp):

@@ -748,7 +748,8 @@ int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device
  * 5..7, 30 % wrong matches, tau = 2 px) the final set is the true one for most pairs at 0.05 px of noise and for about half of
  * them at 0.1 px, whatever the refits; the refinement behind it (the triangulation, the resections and the LM solve on the
  * seeded x) is what makes the estimate.
- * Out of scope: the five-point solver; a non-linear refinement of the pair; unknown focal lengths; homographies and planar
+ * The remedy is the five-point minimal solver as the hypothesis generator: ba_relative_pose_five_point, below.
+ * Out of scope: a non-linear refinement of the pair; unknown focal lengths; homographies and planar
  * scenes; MSAC or an adaptive hypothesis count; the choice of the initial pair; Float32; several ranks; a device-resident entry. */
 enum { BA_RP_OK = 0, BA_RP_FEW_MATCHES = 1, BA_RP_DEGENERATE = 2, BA_RP_NO_CONSENSUS = 3, BA_RP_STATES = 4 };
 int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1,
@@ -762,6 +763,45 @@ int ba_relative_pose(ba_problem *p, const double *x /* nvar, host: only (k1, k2,
                      int64_t *match_ptr /* npairs + 1, or NULL */, uint8_t *inlier /* one byte per match, or NULL */,
                      int32_t *n_inliers /* npairs or NULL */, int32_t *best_hyp /* npairs or NULL */,
                      int64_t *counts /* BA_RP_STATES or NULL */);
+
+/* ---- the five-point essential matrix as the minimal solver of the two-view consensus stage (an extension) ----------
+ * ba_relative_pose_five_point: ba_relative_pose with another hypothesis generator.  Arguments, outputs, states (FEW_MATCHES is
+ * still "fewer than 8 used matches": the refits and the final fit are eight-point fits), the communicator refusal, the inlier
+ * test, the winner, the refits with their adopt rule and the final linear fit are those of ba_relative_pose.  What differs:
+ *   opts must not be NULL (BA_ERR_ARG, "null options"): without a consensus stage there is nothing five-point about the call.
+ *   sample (<= 0: 5) must be 5; min_inliers (<= 0: 8) at least 8; threshold, hypotheses, refits and seed as above.
+ *   The sample of hypothesis h is what the sampler of ba_ransac_sample gives for m = 5 on the pair's match list.
+ *   Hypothesis h: every real essential matrix through the five sampled matches (ba_five_point, below) is a candidate.  A
+ *   candidate goes through steps 6-8 of the linear fit above (its SVD, the four (R, t), the cheirality vote over the five
+ *   matches, the rotation vector) and is scored by its inlier count over the pair's whole list.  The hypothesis is the candidate
+ *   with the largest count, ties to the candidate found first.  No sample, a degenerate null space, no real solution, or no
+ *   candidate with a match in front: the hypothesis is void.
+ * The eight-point fit on a whole inlier set is not what fails on noisy data; eight noisy matches are.  With five-point
+ * hypotheses the consensus set at the generator's 0.5 px is the true one for most pairs.
+ * ba_five_point: the solver alone, n independent problems, one wave each.  qa, qb: five undistorted image points per problem and
+ * image, already divided by f; the ray is d = (q, -1).  E: per problem ten slots of 3 x 3 row-major matrices, the real solutions
+ * first, each with |E|_F = 1, the unused slots NaN; n_sol: their number, 0..10.  The sign of a solution and the order of the
+ * solutions are not specified; two calls give the same bits, and a problem's result does not depend on the others of the call.
+ * The solver: the null space of the 5 x 9 system a_k = d_b (x) d_a on raw rays (no Hartley normalisation) as the eigenvectors
+ * X, Y, Z, W of the four smallest eigenvalues of sum a a' (the Jacobi sweeps above); lambda_5 <= 1e-12 lambda_9 or a sum that is
+ * not finite: 0 solutions.  E = x X + y Y + z Z + W; det E = 0 and 2 E E' E - tr(E E') E = 0 are ten cubics in 20 monomials;
+ * Gauss-Jordan with partial pivoting on the 10 x 20 (a pivot that is 0 or not finite: 0 solutions); the 3 x 3 polynomial matrix
+ * in z and its determinant of degree 10; its roots by a simultaneous complex iteration (Aberth-Ehrlich), a root being real when
+ * |Im z| <= 1e-7 |z|; a real root takes two Newton steps on the real axis; x and y from the null vector of the 3 x 3 at the
+ * root; then (x, y, z) takes two Gauss-Newton steps on the ten eliminated cubics (a step that is not finite is not taken): a
+ * root of the degree-10 polynomial carries that polynomial's conditioning, the cubics carry the solution's own, and without
+ * these steps an ill-conditioned tuple is wrong at 1e-4.  A derivative of the polynomial that vanishes at an iterate makes the
+ * iteration fail: the tuple then has no solution.  The handle supplies the device, the stream and the buffers; a handle with a
+ * communicator is fine.  n == 0 returns BA_OK. */
+int ba_relative_pose_five_point(ba_problem *p, const double *x /* nvar, host: only (k1, k2, f) of the pairs' cameras are read */,
+                                int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                const ba_ransac_opts *opts /* not NULL */,
+                                double *pose /* 6 npairs: rotation vector r, unit translation t */, uint8_t *status /* npairs */,
+                                int64_t *match_ptr /* npairs + 1, or NULL */, uint8_t *inlier /* one byte per match, or NULL */,
+                                int32_t *n_inliers /* npairs or NULL */, int32_t *best_hyp /* npairs or NULL */,
+                                int64_t *counts /* BA_RP_STATES or NULL */);
+int ba_five_point(ba_problem *p, int64_t n, const double *qa /* n x 5 x 2 */, const double *qb /* n x 5 x 2 */,
+                  double *E /* n x 10 x 9 */, int32_t *n_sol /* n */);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

@@ -349,3 +349,44 @@ function relative_pose(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pair
   end
   return pose, status, match_ptr, inlier .!= 0, n_inliers, best_hyp, counts
 end
+
+# The same with the five-point minimal solver as the hypothesis generator (ba_relative_pose_five_point): every real essential
+# matrix through five sampled matches is a candidate; the winner, the refits and the final eight-point fit on the consensus set
+# are those of relative_pose, and so is what is returned.  The threshold is required; the sample is 5, min_inliers at least 8.
+function relative_pose_five_point(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64};
+                                  threshold :: Real, hypotheses :: Integer = 0, refits :: Integer = -1,
+                                  min_inliers :: Integer = 0, seed :: Integer = 0)
+  npairs = length(pairs_a)
+  match_ptr, _, _ = pair_matches(nlp, pairs_a, pairs_b)
+  pose = fill(NaN, 6, npairs)
+  status = zeros(UInt8, npairs)
+  inlier = zeros(UInt8, match_ptr[end])
+  n_inliers = zeros(Int32, npairs)
+  best_hyp = zeros(Int32, npairs)
+  counts = zeros(Int64, 4)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(5), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  GC.@preserve x pairs_a pairs_b opts pose status match_ptr inlier n_inliers best_hyp counts begin
+    bacheck(ccall((:ba_relative_pose_five_point, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{BaRansacOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int64},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                  nlp.handle, pointer(x), npairs, pointer(pairs_a), pointer(pairs_b), Base.unsafe_convert(Ptr{BaRansacOpts}, opts),
+                  pointer(pose), pointer(status), pointer(match_ptr), pointer(inlier), pointer(n_inliers), pointer(best_hyp),
+                  pointer(counts)))
+  end
+  return pose, status, match_ptr, inlier .!= 0, n_inliers, best_hyp, counts
+end
+
+# The solver alone (ba_five_point): qa, qb are 2 x 5 x n, undistorted image points already divided by f (the ray is (q, -1)).
+# Returns E (3 x 3 x 10 x n in C's row-major order: E[j, i, s, k] is entry (i, j) of solution s of problem k; |E|_F = 1, NaN in
+# the unused slots) and the number of real solutions of every problem.
+function five_point(nlp, qa :: Array{Float64, 3}, qb :: Array{Float64, 3})
+  size(qa) == size(qb) && size(qa, 1) == 2 && size(qa, 2) == 5 || error("five_point: qa and qb must both be 2 x 5 x n")
+  n = size(qa, 3)
+  E = fill(NaN, 3, 3, 10, n)
+  n_sol = zeros(Int32, n)
+  GC.@preserve qa qb E n_sol begin
+    bacheck(ccall((:ba_five_point, libba), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                  nlp.handle, n, pointer(qa), pointer(qb), pointer(E), pointer(n_sol)))
+  end
+  return E, n_sol
+end
