@@ -51,6 +51,12 @@ class RansacOpts(C.Structure):
                 ("min_inliers", C.c_int), ("seed", C.c_uint64)]
 
 
+class PairRefineOpts(C.Structure):
+    """ba_pair_refine_opts"""
+    _fields_ = [("max_iter", C.c_int), ("xtol", C.c_double), ("lambda0", C.c_double), ("loss", C.c_int), ("f_scale", C.c_double),
+                ("threshold", C.c_double), ("rounds", C.c_int)]
+
+
 LOG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                      C.c_double, C.c_int)
 COMM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -75,6 +81,7 @@ SYMBOLS = [
     "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
     "ba_resect_cameras_focal", "ba_resect_cameras_focal_dev", "ba_ransac_cameras_focal", "ba_ransac_cameras_focal_dev",
     "ba_pair_matches", "ba_relative_pose", "ba_relative_pose_five_point", "ba_five_point",
+    "ba_refine_relative_pose",
 ]
 
 _lib = None
@@ -165,6 +172,7 @@ def lib():
     L.ba_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
     L.ba_relative_pose_five_point.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
     L.ba_five_point.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.ba_refine_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(PairRefineOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -622,6 +630,40 @@ def ransac_sample(seed, hypothesis, degree, sample=6, used=None):
 
 # states of ba_relative_pose (BA_RP_*)
 PAIR_STATES = ("ok", "few_matches", "degenerate", "no_consensus")
+
+# states of ba_refine_relative_pose (BA_RR_*) and the keys of the `refine=` dict of relative_pose*
+PAIR_REFINE_STATES = ("converged", "stalled", "max_iter", "nonfinite", "skipped")
+PAIR_REFINE_KEYS = ("max_iter", "xtol", "lam0", "loss", "f_scale", "threshold", "rounds")
+
+
+def pair_refine_opts(max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, threshold=None, rounds=None):
+    """PairRefineOpts of the options of refine_relative_pose -- max_iter (None or < 0: 50), xtol (None or <= 0: 1e-10), lam0 (None
+    or <= 0: 1e-4), loss (None: "linear"; a name of LOSSES) with f_scale (pixels, finite and > 0), threshold (pixels, required,
+    finite and > 0), rounds (None or < 0: 2; at most 8) -- or ValueError, before any device call"""
+    ints = {}
+    for key, v in (("max_iter", max_iter), ("rounds", rounds)):
+        v = -1 if v is None else v
+        if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)):
+            raise ValueError(f"refine_relative_pose: {key} must be an integer (or None), got {v!r}")
+        ints[key] = max(int(v), -1)
+    if ints["rounds"] > 8:
+        raise ValueError(f"refine_relative_pose: rounds must be <= 8, got {ints['rounds']}")
+    reals = {}
+    for key, v, positive in (("xtol", xtol, False), ("lam0", lam0, False), ("f_scale", f_scale, True), ("threshold", threshold, True)):
+        if v is None and not positive:
+            v = 0.0
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"refine_relative_pose: {key} must be a finite number, got {v!r}") from None
+        if not np.isfinite(v) or (positive and not v > 0):
+            raise ValueError(f"refine_relative_pose: {key} must be a finite number{' > 0' if positive else ''}, got {v!r}")
+        reals[key] = v
+    loss = "linear" if loss is None else loss
+    if not isinstance(loss, str) or loss not in LOSSES:
+        raise ValueError(f"refine_relative_pose: loss must be one of {', '.join(LOSSES)}, got {loss!r}")
+    return PairRefineOpts(ints["max_iter"], reals["xtol"], reals["lam0"], LOSSES[loss], reals["f_scale"], reals["threshold"],
+                          ints["rounds"])
 
 
 def _pairs(pairs, ncams=None):

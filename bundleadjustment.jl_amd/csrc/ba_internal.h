@@ -429,6 +429,11 @@ struct PairWork {
   DevBuf<double> five_qa, five_qb, five_E;
   DevBuf<int> five_n;
   int64_t five_cap = 0;
+  // ba_refine_relative_pose: per pair the state, the two cost entries, |M'| under the returned pose and the trials
+  DevBuf<uint8_t> rr_state;
+  DevBuf<double> rr_cost;
+  DevBuf<int> rr_consistent, rr_iters;
+  int64_t rr_cap = 0;
 };
 // what the kernels of ba_relative_pose work on
 struct PairArgs {
@@ -441,6 +446,19 @@ struct PairArgs {
   uint64_t seed_mix;                    // mix(seed)
   double tau2;
 };
+// what k_pair_refine takes beside them (ba_refine_relative_pose; the options with their defaults filled in)
+struct PairRefineArgs {
+  uint8_t *state;
+  double *cost;
+  int *n_consistent, *iters;
+  int max_iter, loss, all_used;  // all_used: the caller gave no set, it is every used match
+  double xtol, lambda0, c2;
+};
+// the limits of ba_pair_refine_opts
+constexpr int RR_MAX_ITER_DEFAULT = 50, RR_ROUNDS_DEFAULT = 2, RR_ROUNDS_MAX = 8;
+constexpr double RR_XTOL_DEFAULT = 1e-10, RR_LAMBDA0_DEFAULT = 1e-4;
+// The options as k_pair_refine takes them (defaults filled in), or BA_ERR_ARG with `who` in the message
+int pair_refine_opts_check(const char *who, const ba_pair_refine_opts *in, ba_pair_refine_opts *out);
 
 struct ba_problem {
   int device = 0;

@@ -1,4 +1,4 @@
-// Two-view relative pose (ba_pair_matches, ba_relative_pose, ba_relative_pose_five_point, ba_five_point; include/ba_hip.h, "relative pose of camera pairs").
+// Two-view relative pose (ba_pair_matches, ba_relative_pose, ba_relative_pose_five_point, ba_five_point, ba_refine_relative_pose; include/ba_hip.h, "relative pose of camera pairs").
 // gfx950 only.
 //
 // The host lists the matches of every pair (pair_match_lists: the points both cameras observe, ordered by camera a's list) and
@@ -16,6 +16,9 @@
 // k_pair_fit (one workgroup per pair): the sums over the current set in a fixed order (strided partial sums per thread, the
 // butterfly of a wave, the four waves in order), the same linear fit (essential_from_sums<__syncthreads>), then either the
 // re-scoring with the adopt rule of the refits or, in the last launch, the returned pose.
+// k_pair_refine (ba_refine_relative_pose; one workgroup per pair, the layout of k_pair_fit): the Marquardt iteration
+// on the Sampson error of the pair's set, the whole loop of a round in one launch -- the 21 sums of a trial in the same fixed
+// order, the 5 x 5 Cholesky and the retraction by one thread in LDS -- then the list re-scored under the refined pose.
 // The sample, the winner, the marking of a set and the adopt rule are those of ba_consensus_dev.h, shared with
 // ba_ransac_cameras, and the options go through its ransac_opts_check; this file keeps whether a match is used, the sums of a
 // fit, the cheirality counts and the states of k_pair_select.
@@ -276,6 +279,185 @@ __device__ __forceinline__ void pair_wave_part(PairFitShared &sh, int i, double 
   if ((t & 63) == 0) sh.part[t >> 6][i] = v;
 }
 
+// the LDS of k_pair_refine
+struct PairRefineShared {
+  PairFitShared fit;           // the waves' partial sums, the integer sums, and (ps.rs) the scratch of rotation_vector
+  double S[RP_SUMS];           // F, g, H at the current pose
+  double R[9], t[3], E[9];     // the current pose
+  double B[6], G[9 * RP_DOF];  // its tangent basis and the five dE
+  double Rn[9], tn[3], En[9];  // the trial pose
+  double delta[RP_DOF], L[RP_HESS], W[9], ret[6];
+  double Fn;
+  int ok;
+};
+
+// out[i] <- the sum of acc[i] over the workgroup in the fixed order of k_pair_fit, i < N; a barrier behind it
+template <int N>
+__device__ __forceinline__ void pair_refine_reduce(PairRefineShared &sh, const double (&acc)[N], double *out, int t) {
+#pragma unroll
+  for (int i = 0; i < N; i++) pair_wave_part(sh.fit, i, acc[i], t);
+  __syncthreads();
+  if (t < N) out[t] = ((sh.fit.part[0][t] + sh.fit.part[1][t]) + sh.fit.part[2][t]) + sh.fit.part[3][t];
+  __syncthreads();
+}
+
+// sh.S <- F = 1/2 sum c^2 rho(e^2 / c^2), g = sum w J'e, H = sum w J'J over the set at the current pose (sh.E, sh.G), w = rho'
+__device__ __forceinline__ void pair_refine_sums(const PairArgs &a, const PairRefineArgs &q, PairRefineShared &sh, int k0, int k1, double fa,
+                                                 double fb, int t) {
+  double acc[RP_SUMS];
+#pragma unroll
+  for (int i = 0; i < RP_SUMS; i++) acc[i] = 0.0;
+  for (int k = k0 + t; k < k1; k += PR_BLK)
+    if (a.inlier[k] & 1) {
+      const double *ray = a.rays + PAIR_RAY * (int64_t)k;
+      double l[2], m[2], n, D, J[RP_DOF], w;
+      const double e = pair_sampson_signed(ray, sh.E, fa, fb, l, m, n, D);
+      pair_sampson_jacobian(ray, sh.G, fa, fb, l, m, n, D, J);
+      acc[0] += 0.5 * robust_rho(q.loss, e * e, q.c2, &w);
+      int tt = 1 + RP_DOF;
+#pragma unroll
+      for (int i = 0; i < RP_DOF; i++) {
+        const double wj = w * J[i];
+        acc[1 + i] += wj * e;
+#pragma unroll
+        for (int j = 0; j <= i; j++, tt++) acc[tt] += wj * J[j];
+      }
+    }
+  pair_refine_reduce<RP_SUMS>(sh, acc, sh.S, t);
+}
+
+// sh.Fn <- F over the set at the trial pose (sh.En)
+__device__ __forceinline__ void pair_refine_cost(const PairArgs &a, const PairRefineArgs &q, PairRefineShared &sh, int k0, int k1, double fa,
+                                                 double fb, int t) {
+  double acc[1] = {0.0};
+  for (int k = k0 + t; k < k1; k += PR_BLK)
+    if (a.inlier[k] & 1) {
+      double l[2], m[2], n, D, w;
+      const double e = pair_sampson_signed(a.rays + PAIR_RAY * (int64_t)k, sh.En, fa, fb, l, m, n, D);
+      acc[0] += 0.5 * robust_rho(q.loss, e * e, q.c2, &w);
+    }
+  pair_refine_reduce<1>(sh, acc, &sh.Fn, t);
+}
+
+// One pair per workgroup (ba_refine_relative_pose): the Marquardt iteration of the header on the pair's current set M
+// (the inlier bytes) from its current pose (a.pose), the whole loop in this launch; then |M'|, the set of the whole list under
+// the refined pose.  round 0 first takes the caller's set down to its used members and decides SKIPPED.  final == 0: M' goes
+// through the adopt rule of consensus_rescore; the pair stops when it is not adopted.  Every decision is taken on values all
+// threads share: they come out of LDS behind a barrier.
+__global__ __launch_bounds__(PR_BLK) void k_pair_refine(PairArgs a, PairRefineArgs q, int round, int final) {
+  __shared__ PairRefineShared sh;
+  const int t = (int)threadIdx.x, pr = (int)blockIdx.x;
+  const int k0 = a.match_ptr[pr], k1 = a.match_ptr[pr + 1];
+  const double *in = a.intr + 6 * (int64_t)pr;
+  double *pose = a.pose + 6 * (int64_t)pr;
+  int n_set;
+  if (round == 0) {
+    int n = 0;
+    for (int k = k0 + t; k < k1; k += PR_BLK) {
+      const int member = ((q.all_used || (a.inlier[k] & 1)) && a.rays[PAIR_RAY * (int64_t)k + 4] != 0.0) ? 1 : 0;
+      a.inlier[k] = (uint8_t)member;
+      n += member;
+    }
+    n_set = block_sum_int(n, sh.fit.red, t);
+    const bool skip = a.status[pr] != BA_RP_OK || !pair_focals_ok(in) || n_set < RP_MIN_SET;
+    if (t == 0) {
+      a.stopped[pr] = skip ? 1 : 0, a.n_inliers[pr] = n_set;
+      q.state[pr] = BA_RR_SKIPPED, q.iters[pr] = 0, q.n_consistent[pr] = 0;
+      q.cost[2 * (int64_t)pr] = 0.0, q.cost[2 * (int64_t)pr + 1] = 0.0;
+    }
+    if (skip) return;
+  } else {
+    if (a.stopped[pr]) return;
+    n_set = a.n_inliers[pr];
+  }
+  const double fa = in[2], fb = in[5];
+  if (t == 0) {
+    PairPose P;
+    pair_pose_of(pose, pose + 3, P);
+#pragma unroll
+    for (int e = 0; e < 9; e++) sh.R[e] = P.R[e], sh.E[e] = P.E[e];
+#pragma unroll
+    for (int e = 0; e < 3; e++) sh.t[e] = P.t[e];
+    pair_tangent(sh.R, sh.t, sh.B, sh.G, sh.W);
+  }
+  __syncthreads();
+  pair_refine_sums(a, q, sh, k0, k1, fa, fb, t);
+  double F = sh.S[0];
+  if (round == 0 && t == 0) q.cost[2 * (int64_t)pr] = F;
+  if (!isfinite(F)) {
+    if (t == 0) q.state[pr] = BA_RR_NONFINITE, q.cost[2 * (int64_t)pr + 1] = F, a.stopped[pr] = 1;
+    return;
+  }
+  int state = BA_RR_MAX_ITER, trials = 0;
+  bool fresh = true, moved = false;  // fresh: sh.S holds the sums of the current pose
+  double lam = q.lambda0;
+#pragma nounroll
+  for (int it = 0; it < q.max_iter; it++) {
+    trials = it + 1;
+    __syncthreads();  // (every thread has read the last trial's ok, Fn and delta)
+    if (!fresh) pair_refine_sums(a, q, sh, k0, k1, fa, fb, t);
+    fresh = true;
+    if (t == 0) {
+      const bool ok = pair_step(sh.S, lam, sh.L, sh.delta);
+      if (ok) pair_retract(sh.R, sh.t, sh.B, sh.delta, sh.Rn, sh.tn, sh.En, sh.W);
+      sh.ok = ok ? 1 : 0;
+    }
+    __syncthreads();
+    bool accept = false;
+    if (sh.ok) {
+      pair_refine_cost(a, q, sh, k0, k1, fa, fb, t);
+      accept = isfinite(sh.Fn) && sh.Fn <= F;
+    }
+    if (accept) {
+      F = sh.Fn;
+      if (t == 0) {
+        for (int e = 0; e < 9; e++) sh.R[e] = sh.Rn[e], sh.E[e] = sh.En[e];
+        for (int e = 0; e < 3; e++) sh.t[e] = sh.tn[e];
+        pair_tangent(sh.R, sh.t, sh.B, sh.G, sh.W);
+      }
+      fresh = false, moved = true;
+      lam = fmax(lam / 10.0, 1e-12);
+      double nd = 0.0;
+#pragma unroll
+      for (int i = 0; i < RP_DOF; i++) nd += sh.delta[i] * sh.delta[i];
+      if (sqrt(nd) <= q.xtol) {
+        state = BA_RR_CONVERGED;
+        break;
+      }
+    } else {
+      lam *= 10.0;
+      if (lam > 1e12) {
+        state = BA_RR_STALLED;
+        break;
+      }
+    }
+  }
+  if (t == 0) {
+    if (moved) {  // (a pose that no step moved keeps its bits)
+      for (int e = 0; e < 9; e++) sh.fit.ps.rs.R[e] = sh.R[e];
+      rotation_vector(sh.fit.ps.rs);
+      for (int e = 0; e < 3; e++) pose[e] = sh.fit.ps.rs.r[e], pose[3 + e] = sh.t[e];
+    }
+    for (int e = 0; e < 6; e++) sh.ret[e] = pose[e];
+    q.state[pr] = (uint8_t)state, q.cost[2 * (int64_t)pr + 1] = F, q.iters[pr] += trials;
+  }
+  __syncthreads();
+  PairPose P;
+  pair_pose_of(sh.ret, sh.ret + 3, P);
+  int nc = 0;
+  for (int k = k0 + t; k < k1; k += PR_BLK) nc += pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, fa, fb, a.tau2) ? 1 : 0;
+  nc = block_sum_int(nc, sh.fit.red, t);
+  if (t == 0) q.n_consistent[pr] = nc;
+  if (final) return;
+  const int n = consensus_rescore(
+      k0, k1, n_set, a.inlier, sh.fit.red, t, [](int k) { return k; },
+      [&](int k) { return pair_inlier(a.rays + PAIR_RAY * (int64_t)k, P, fa, fb, a.tau2); });
+  if (t == 0) {
+    if (n >= 0) a.n_inliers[pr] = n;
+    else a.stopped[pr] = 1;
+  }
+}
+
 // One pair per workgroup: the linear fit on its current set M (the inlier bytes).  final == 0, a round of the refits: the adopt
 // rule of consensus_rescore on the whole list under the fit; M stays and the pair stops when M' is not adopted, and when the fit
 // is degenerate.  final != 0: the pose of the fit -> a.pose, or the state DEGENERATE.
@@ -475,6 +657,43 @@ int pair_buffers(PairWork &w, int64_t npairs, int64_t nmatch, int64_t H) {
   return BA_OK;
 }
 
+// the host copies of what a call uploads: they outlive the call's synchronisation
+struct PairUpload {
+  std::vector<int> ptr, oa, ob, pair;
+  std::vector<double> intr;
+};
+
+// What every entry with match lists does first on the device: the lists (ptr, oa, ob of pair_match_lists) as int32 and the six
+// intrinsics of every pair uploaded into the buffers (grown for H hypotheses per pair), the handle's information array, the
+// pointers of `a`, and the ray records (k_pair_rays).  npairs > 0.
+int pair_front(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1, const std::vector<int64_t> &ptr,
+               const std::vector<int64_t> &oa, const std::vector<int64_t> &ob, int64_t H, PairUpload &h, PairArgs &a) {
+  const int64_t nmatch = ptr[(size_t)npairs];
+  h.ptr.assign(ptr.begin(), ptr.end()), h.oa.assign(oa.begin(), oa.end()), h.ob.assign(ob.begin(), ob.end());
+  h.pair.resize((size_t)nmatch), h.intr.resize((size_t)(6 * npairs));
+  for (int64_t i = 0; i < npairs; i++) {
+    for (int64_t k = ptr[(size_t)i]; k < ptr[(size_t)i + 1]; k++) h.pair[(size_t)k] = (int)i;
+    const double *ca = x + 3 * p->npnts + 9 * (pair_a1[i] - 1), *cb = x + 3 * p->npnts + 9 * (pair_b1[i] - 1);
+    for (int j = 0; j < 3; j++) h.intr[(size_t)(6 * i + j)] = ca[6 + j], h.intr[(size_t)(6 * i + 3 + j)] = cb[6 + j];
+  }
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  BA_CHECK(info_upload(p));
+  PairWork &w = p->pairs;
+  BA_CHECK(pair_buffers(w, npairs, nmatch, H));
+  BA_CHECK(pair_upload((int *)w.match_ptr, h.ptr, st));
+  BA_CHECK(pair_upload((int *)w.obs_a, h.oa, st));
+  BA_CHECK(pair_upload((int *)w.obs_b, h.ob, st));
+  BA_CHECK(pair_upload((int *)w.pair_of, h.pair, st));
+  BA_CHECK(pair_upload((double *)w.intr, h.intr, st));
+  a.match_ptr = w.match_ptr, a.obs_a = w.obs_a, a.obs_b = w.obs_b, a.pair_of = w.pair_of;
+  a.intr = w.intr, a.pt2d = p->pt2d, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
+  a.rays = w.rays, a.hyp_pose = w.hyp_pose, a.pose = w.pose;
+  a.hyp_count = w.hyp_count, a.n_inliers = w.n_inliers, a.best_hyp = w.best_hyp;
+  a.inlier = w.inlier, a.stopped = w.stopped, a.status = w.status;
+  return BA_LAUNCH(k_pair_rays, grid_for(nmatch, PR_BLK), PR_BLK, 0, st, a, nmatch);
+}
+
 }  // namespace
 
 extern "C" int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1, int64_t npairs,
@@ -521,33 +740,13 @@ int relative_pose_call(const char *who, bool five, ba_problem *p, const double *
   if (counts)
     for (int s = 0; s < BA_RP_STATES; s++) counts[s] = 0;
   if (npairs == 0) return BA_OK;
-  // what the device reads: the lists as int32 and the six intrinsics of every pair
-  std::vector<int> h_ptr(ptr.begin(), ptr.end()), h_oa(oa.begin(), oa.end()), h_ob(ob.begin(), ob.end()), h_pair((size_t)nmatch);
-  std::vector<double> h_intr((size_t)(6 * npairs));
-  for (int64_t i = 0; i < npairs; i++) {
-    for (int64_t k = ptr[(size_t)i]; k < ptr[(size_t)i + 1]; k++) h_pair[(size_t)k] = (int)i;
-    const double *ca = x + 3 * p->npnts + 9 * (pair_a1[i] - 1), *cb = x + 3 * p->npnts + 9 * (pair_b1[i] - 1);
-    for (int j = 0; j < 3; j++) h_intr[(size_t)(6 * i + j)] = ca[6 + j], h_intr[(size_t)(6 * i + 3 + j)] = cb[6 + j];
-  }
-  BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = p->stream;
-  BA_CHECK(info_upload(p));
   PairWork &w = p->pairs;
-  BA_CHECK(pair_buffers(w, npairs, nmatch, opts ? o.hypotheses : 0));
-  BA_CHECK(pair_upload((int *)w.match_ptr, h_ptr, st));
-  BA_CHECK(pair_upload((int *)w.obs_a, h_oa, st));
-  BA_CHECK(pair_upload((int *)w.obs_b, h_ob, st));
-  BA_CHECK(pair_upload((int *)w.pair_of, h_pair, st));
-  BA_CHECK(pair_upload((double *)w.intr, h_intr, st));
-  PairArgs a;
-  a.match_ptr = w.match_ptr, a.obs_a = w.obs_a, a.obs_b = w.obs_b, a.pair_of = w.pair_of;
-  a.intr = w.intr, a.pt2d = p->pt2d, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
-  a.rays = w.rays, a.hyp_pose = w.hyp_pose, a.pose = w.pose;
-  a.hyp_count = w.hyp_count, a.n_inliers = w.n_inliers, a.best_hyp = w.best_hyp;
-  a.inlier = w.inlier, a.stopped = w.stopped, a.status = w.status;
+  PairUpload up;
+  PairArgs a = {};
+  BA_CHECK(pair_front(p, x, npairs, pair_a1, pair_b1, ptr, oa, ob, opts ? o.hypotheses : 0, up, a));
   a.hypotheses = opts ? o.hypotheses : 0, a.sample = o.sample, a.min_inliers = o.min_inliers;
   a.seed_mix = ransac_seed_mix(o.seed), a.tau2 = o.threshold * o.threshold;
-  BA_CHECK(BA_LAUNCH(k_pair_rays, grid_for(nmatch, PR_BLK), PR_BLK, 0, st, a, nmatch));
   if (five) BA_CHECK(BA_LAUNCH(k_pair_hypotheses5, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
   else if (opts) BA_CHECK(BA_LAUNCH(k_pair_hypotheses, dim3((unsigned)npairs, grid_for(o.hypotheses, PR_WAVES)), PR_BLK, 0, st, a));
   BA_CHECK(BA_LAUNCH(k_pair_select, (unsigned)npairs, PR_BLK, 0, st, a));
@@ -615,5 +814,111 @@ extern "C" int ba_five_point(ba_problem *p, int64_t n, const double *qa, const d
   BA_HIP_CHECK(hipMemcpyAsync(E, w.five_E, (size_t)(9 * FP_MAX_SOL * n) * sizeof(double), hipMemcpyDeviceToHost, st));
   BA_HIP_CHECK(hipMemcpyAsync(n_sol, w.five_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   BA_HIP_CHECK(hipStreamSynchronize(st));
+  return BA_OK;
+}
+
+int pair_refine_opts_check(const char *who, const ba_pair_refine_opts *in, ba_pair_refine_opts *o) {
+  if (!in) {
+    ba_set_error("%s: null options", who);
+    return BA_ERR_ARG;
+  }
+  *o = *in;
+  if (!std::isfinite(o->xtol) || !std::isfinite(o->lambda0)) {
+    ba_set_error("%s: xtol and lambda0 must be finite (<= 0: %g and %g), got %g, %g", who, RR_XTOL_DEFAULT, RR_LAMBDA0_DEFAULT, o->xtol,
+                 o->lambda0);
+    return BA_ERR_ARG;
+  }
+  if (o->loss < BA_LOSS_LINEAR || o->loss > BA_LOSS_ARCTAN || !std::isfinite(o->f_scale) || !(o->f_scale > 0)) {
+    ba_set_error("%s: loss must be one of BA_LOSS_* and f_scale finite and > 0 (pixels), got %d, %g", who, o->loss, o->f_scale);
+    return BA_ERR_ARG;
+  }
+  if (!std::isfinite(o->threshold) || !(o->threshold > 0)) {
+    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, o->threshold);
+    return BA_ERR_ARG;
+  }
+  if (o->max_iter < 0) o->max_iter = RR_MAX_ITER_DEFAULT;
+  if (o->xtol <= 0) o->xtol = RR_XTOL_DEFAULT;
+  if (o->lambda0 <= 0) o->lambda0 = RR_LAMBDA0_DEFAULT;
+  if (o->rounds < 0) o->rounds = RR_ROUNDS_DEFAULT;
+  if (o->rounds > RR_ROUNDS_MAX) {
+    ba_set_error("%s: rounds must be <= %d, got %d", who, RR_ROUNDS_MAX, o->rounds);
+    return BA_ERR_ARG;
+  }
+  return BA_OK;
+}
+
+extern "C" int ba_refine_relative_pose(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                       const ba_pair_refine_opts *opts, double *pose_inout, const uint8_t *status_in, uint8_t *inlier_inout,
+                                       uint8_t *state, double *cost, int32_t *n_inliers, int32_t *n_consistent, int32_t *iters,
+                                       int64_t *counts) {
+  const char *who = "ba_refine_relative_pose";
+  ba_pair_refine_opts o = {};
+  BA_CHECK(pair_refine_opts_check(who, opts, &o));
+  if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !pose_inout || !state))) {
+    ba_set_error("%s: null argument or npairs < 0", who);
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
+    return BA_ERR_ARG;
+  }
+  std::vector<int64_t> ptr, oa, ob;
+  BA_CHECK(pair_match_lists(who, p->ncams, p->npnts, p->nobs, p->h_cam0.data(), p->h_pnt0.data(), 0, npairs, pair_a1, pair_b1, ptr, &oa, &ob));
+  const int64_t nmatch = ptr[(size_t)npairs];
+  if (nmatch > (int64_t)INT32_MAX) {
+    ba_set_error("%s: %lld matches: more than 2^31 - 1", who, (long long)nmatch);
+    return BA_ERR_ARG;
+  }
+  if (counts)
+    for (int s = 0; s < BA_RR_STATES; s++) counts[s] = 0;
+  if (npairs == 0) return BA_OK;
+  hipStream_t st = p->stream;
+  PairWork &w = p->pairs;
+  PairUpload up;
+  PairArgs a = {};
+  BA_CHECK(pair_front(p, x, npairs, pair_a1, pair_b1, ptr, oa, ob, 0, up, a));
+  if (w.rr_cap < npairs) {
+    w.rr_cap = 0;
+    BA_CHECK(w.rr_state.alloc(npairs));
+    BA_CHECK(w.rr_cost.alloc(2 * npairs));
+    BA_CHECK(w.rr_consistent.alloc(npairs));
+    BA_CHECK(w.rr_iters.alloc(npairs));
+    w.rr_cap = npairs;
+  }
+  a.tau2 = o.threshold * o.threshold;
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.pose, pose_inout, (size_t)(6 * npairs) * sizeof(double), hipMemcpyHostToDevice, st));
+  if (status_in) BA_HIP_CHECK(hipMemcpyAsync((uint8_t *)w.status, status_in, (size_t)npairs, hipMemcpyHostToDevice, st));
+  else BA_HIP_CHECK(hipMemsetAsync((uint8_t *)w.status, BA_RP_OK, (size_t)npairs, st));
+  if (inlier_inout && nmatch > 0) BA_HIP_CHECK(hipMemcpyAsync((uint8_t *)w.inlier, inlier_inout, (size_t)nmatch, hipMemcpyHostToDevice, st));
+  PairRefineArgs q;
+  q.state = w.rr_state, q.cost = w.rr_cost, q.n_consistent = w.rr_consistent, q.iters = w.rr_iters;
+  q.max_iter = o.max_iter, q.loss = o.loss, q.all_used = inlier_inout ? 0 : 1;
+  q.xtol = o.xtol, q.lambda0 = o.lambda0, q.c2 = o.f_scale * o.f_scale;
+  for (int round = 0; round <= o.rounds; round++)
+    BA_CHECK(BA_LAUNCH(k_pair_refine, (unsigned)npairs, PR_BLK, 0, st, a, q, round, round == o.rounds ? 1 : 0));
+  std::vector<double> h_pose((size_t)(6 * npairs)), h_cost((size_t)(2 * npairs));
+  std::vector<uint8_t> h_state((size_t)npairs), h_inlier((size_t)nmatch);
+  std::vector<int32_t> h_n((size_t)npairs), h_nc((size_t)npairs), h_it((size_t)npairs);
+  BA_HIP_CHECK(hipMemcpyAsync(h_pose.data(), w.pose, h_pose.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_cost.data(), w.rr_cost, h_cost.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_state.data(), w.rr_state, h_state.size(), hipMemcpyDeviceToHost, st));
+  if (inlier_inout && nmatch > 0) BA_HIP_CHECK(hipMemcpyAsync(h_inlier.data(), w.inlier, (size_t)nmatch, hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_n.data(), w.n_inliers, h_n.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_nc.data(), w.rr_consistent, h_nc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_it.data(), w.rr_iters, h_it.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < npairs; i++) {
+    const uint8_t s = h_state[(size_t)i];
+    state[i] = s;
+    if (counts && s < BA_RR_STATES) counts[s]++;
+    if (cost) cost[2 * i] = h_cost[(size_t)(2 * i)], cost[2 * i + 1] = h_cost[(size_t)(2 * i + 1)];
+    if (iters) iters[i] = h_it[(size_t)i];
+    if (s == BA_RR_SKIPPED) continue;  // (its pose, inlier bytes and counts stay as the caller filled them)
+    for (int j = 0; j < 6; j++) pose_inout[6 * i + j] = h_pose[(size_t)(6 * i + j)];
+    if (inlier_inout)
+      for (int64_t k = ptr[(size_t)i]; k < ptr[(size_t)i + 1]; k++) inlier_inout[k] = h_inlier[(size_t)k];
+    if (n_inliers) n_inliers[i] = h_n[(size_t)i];
+    if (n_consistent) n_consistent[i] = h_nc[(size_t)i];
+  }
   return BA_OK;
 }

@@ -1,5 +1,5 @@
 // Device pieces shared by the block refinements and the relative pose (ba_point_kernels.hip, ba_camera_kernels.hip,
-// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5p).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
+// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5q).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
 // The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
@@ -812,4 +812,131 @@ __device__ __forceinline__ int five_point_solve(PairScratch &sh, FiveScratch &fs
   }
   wave_sync();
   return __popcll(found);
+}
+
+// ---- the non-linear refinement of a pair: Marquardt steps on the signed Sampson residual in 5 unknowns -------------
+// The pose is (R, unit t); a step is delta = (d_omega, d_tau): R+ = exp([d_omega]x) R, t+ = (t + B d_tau) / |t + B d_tau| with
+// B = [b1 b2] a basis of the plane across t.  The residual of a match is e = n / sqrt(D), n = d_b' E d_a,
+// D = ((E d_a)_1^2 + (E d_a)_2^2) / f_b^2 + ((E' d_b)_1^2 + (E' d_b)_2^2) / f_a^2: e^2 is the Sampson distance of pair_inlier.
+// With dE = G for a unit step in one unknown, dn = d_b' G d_a, d(E d_a) = G d_a, d(E' d_b) = G' d_b, and
+// de = dn / sqrt(D) - n dD / (2 D^(3/2)).  The five G of a pose are G_omega_j = [t]x [e_j]x R and G_tau_j = [b_j]x R
+// (pair_tangent): one lane writes them when the pose moves, every lane reads them for each of its matches.
+constexpr int RP_DOF = 5;
+constexpr int RP_HESS = RP_DOF * (RP_DOF + 1) / 2;  // H packed lower row-major
+constexpr int RP_SUMS = 1 + RP_DOF + RP_HESS;      // F, g, H
+constexpr int RP_MIN_SET = RP_DOF;                 // the smallest set that is refined
+
+// e of a match under E (row-major); l <- the first two entries of E d_a, m <- of E' d_b, n and D as above
+__device__ __forceinline__ double pair_sampson_signed(const double *ray, const double *E, double fa, double fb, double l[2], double m[2],
+                                                      double &n, double &D) {
+  const double qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
+  l[0] = (E[0] * qax + E[1] * qay) - E[2], l[1] = (E[3] * qax + E[4] * qay) - E[5];
+  const double l2 = (E[6] * qax + E[7] * qay) - E[8];
+  m[0] = (E[0] * qbx + E[3] * qby) - E[6], m[1] = (E[1] * qbx + E[4] * qby) - E[7];
+  n = (qbx * l[0] + qby * l[1]) - l2;
+  D = (l[0] * l[0] + l[1] * l[1]) / (fb * fb) + (m[0] * m[0] + m[1] * m[1]) / (fa * fa);
+  return n / sqrt(D);
+}
+
+// J[j] <- de / d delta_j of the match from the five G (9 entries each, row-major) and what pair_sampson_signed left
+__device__ __forceinline__ void pair_sampson_jacobian(const double *ray, const double *G, double fa, double fb, const double l[2],
+                                                      const double m[2], double n, double D, double J[RP_DOF]) {
+  const double qax = ray[0], qay = ray[1], qbx = ray[2], qby = ray[3];
+  const double rD = sqrt(D), half = n / (2.0 * (D * rD));
+#pragma unroll
+  for (int j = 0; j < RP_DOF; j++) {
+    const double *g = G + 9 * j;
+    const double dl0 = (g[0] * qax + g[1] * qay) - g[2], dl1 = (g[3] * qax + g[4] * qay) - g[5], dl2 = (g[6] * qax + g[7] * qay) - g[8];
+    const double dm0 = (g[0] * qbx + g[3] * qby) - g[6], dm1 = (g[1] * qbx + g[4] * qby) - g[7];
+    const double dn = (qbx * dl0 + qby * dl1) - dl2;
+    const double dD = 2.0 * (l[0] * dl0 + l[1] * dl1) / (fb * fb) + 2.0 * (m[0] * dm0 + m[1] * dm1) / (fa * fa);
+    J[j] = dn / rD - half * dD;
+  }
+}
+
+// out (row-major 3 x 3) <- [v]x R
+__device__ __forceinline__ void cross_rows(const double *v, const double *R, double *out) {
+  for (int c = 0; c < 3; c++) {
+    out[c] = v[1] * R[6 + c] - v[2] * R[3 + c];
+    out[3 + c] = v[2] * R[c] - v[0] * R[6 + c];
+    out[6 + c] = v[0] * R[3 + c] - v[1] * R[c];
+  }
+}
+
+// The basis B of the plane across t and the five G of the pose (R, t) -> B (b1, b2), G; W: 9 doubles of scratch.  b1 = (e_i x t)
+// / |e_i x t| with i the index of the smallest |t_i|, ties to the lowest; b2 = t x b1.  (one lane, on LDS)
+__device__ __forceinline__ void pair_tangent(const double *R, const double *t, double *B, double *G, double *W) {
+  int i = 0;
+  if (fabs(t[1]) < fabs(t[i])) i = 1;
+  if (fabs(t[2]) < fabs(t[i])) i = 2;
+  const int i1 = (i + 1) % 3, i2 = (i + 2) % 3;  // e_i x t = -t_{i+2} e_{i+1} + t_{i+1} e_{i+2}
+  const double bn = sqrt(t[i1] * t[i1] + t[i2] * t[i2]);
+  B[i] = 0.0, B[i1] = -t[i2] / bn, B[i2] = t[i1] / bn;
+  B[3] = t[1] * B[2] - t[2] * B[1], B[4] = t[2] * B[0] - t[0] * B[2], B[5] = t[0] * B[1] - t[1] * B[0];
+  for (int j = 0; j < 3; j++) {
+    const double e[3] = {j == 0 ? 1.0 : 0.0, j == 1 ? 1.0 : 0.0, j == 2 ? 1.0 : 0.0};
+    cross_rows(e, R, W);
+    cross_rows(t, W, G + 9 * j);
+  }
+  cross_rows(B, R, G + 27);
+  cross_rows(B + 3, R, G + 36);
+}
+
+// (R, t) moved by delta -> Rn, tn, En = [tn]x Rn; exp([w]x) = I + a [w]x + b [w]x^2 with a = sin(th) / th and
+// b = (sin(th / 2) / (th / 2))^2 / 2, th = |w| (th == 0: a = 1, b = 1 / 2).  (one lane, on LDS)
+__device__ __forceinline__ void pair_retract(const double *R, const double *t, const double *B, const double *delta, double *Rn, double *tn,
+                                             double *En, double *W) {
+  const double w[3] = {delta[0], delta[1], delta[2]};
+  const double th = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+  double ca = 1.0, cb = 0.5;
+  if (th > 0.0) {
+    const double sh = sin(0.5 * th) / (0.5 * th);
+    ca = sin(th) / th, cb = 0.5 * (sh * sh);
+  }
+  cross_rows(w, R, W);    // [w]x R
+  cross_rows(w, W, Rn);   // [w]x^2 R
+  for (int e = 0; e < 9; e++) Rn[e] = (R[e] + ca * W[e]) + cb * Rn[e];
+  double u[3];
+  for (int i = 0; i < 3; i++) u[i] = (t[i] + B[i] * delta[3]) + B[3 + i] * delta[4];
+  const double un = sqrt((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+  // (a step too small to move t leaves its bits: the retraction of 0 is the identity, also where |t| is an ulp off 1 -- without
+  // this a t whose renormalised copy costs an ulp more rejects every trial from there on and the pair ends STALLED at its minimum)
+  const bool still = u[0] == t[0] && u[1] == t[1] && u[2] == t[2];
+  for (int i = 0; i < 3; i++) tn[i] = still ? t[i] : u[i] / un;
+  cross_rows(tn, Rn, En);
+}
+
+// (H + lam diag H) delta = -g by Cholesky; S: the sums (F, g, H packed lower row-major); L: 15 doubles of scratch.  false: a pivot
+// that is not > 0 or a delta that is not finite.  (one lane, on LDS)
+__device__ __forceinline__ bool pair_step(const double *S, double lam, double *L, double *delta) {
+  const double *g = S + 1, *H = S + 1 + RP_DOF;
+#pragma nounroll
+  for (int i = 0; i < RP_DOF; i++)
+#pragma nounroll
+    for (int j = 0; j <= i; j++) {
+      double s = H[i * (i + 1) / 2 + j];
+      if (i == j) s += lam * s;
+      for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
+      if (i == j) {
+        if (!(s > 0.0) || !isfinite(s)) return false;
+        L[i * (i + 1) / 2 + i] = sqrt(s);
+      } else {
+        L[i * (i + 1) / 2 + j] = s / L[j * (j + 1) / 2 + j];
+      }
+    }
+#pragma nounroll
+  for (int i = 0; i < RP_DOF; i++) {  // L y = -g
+    double s = -g[i];
+    for (int k = 0; k < i; k++) s -= L[i * (i + 1) / 2 + k] * delta[k];
+    delta[i] = s / L[i * (i + 1) / 2 + i];
+  }
+  bool ok = true;
+#pragma nounroll
+  for (int i = RP_DOF - 1; i >= 0; i--) {  // L' delta = y
+    double s = delta[i];
+    for (int k = i + 1; k < RP_DOF; k++) s -= L[k * (k + 1) / 2 + i] * delta[k];
+    delta[i] = s / L[i * (i + 1) / 2 + i];
+    ok = ok && isfinite(delta[i]);
+  }
+  return ok;
 }

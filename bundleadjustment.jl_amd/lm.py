@@ -375,7 +375,7 @@ def pair_matches(problem, pairs):
     return _lib.pair_matches(cam, pnt, ncams, npnts, pairs)
 
 
-def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None):
+def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None, **chain):
     """The relative pose of camera pairs from their 2D-2D matches (ba_relative_pose): the eight-point essential matrix, with
     ransac=dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) behind a consensus stage (_lib.ransac_opts with
     sample in 8..16, default 8, and min_inliers >= 8).  pairs: (npairs, 2), 1-based cameras (a, b).  Of x only (k1, k2, f) of the
@@ -384,12 +384,39 @@ def relative_pose(nlp, x, pairs, *, ransac=None, obs_info=None):
     Returns a dict: `r`, `t` (npairs, 3): P_b = R(r) P_a + t with |t| = 1, NaN where the pair has no pose; `status` (names among
     _lib.PAIR_STATES); `match_ptr` and, per match in the order of pair_matches, `inliers` (bool); `n_inliers`; `best_hypothesis`
     (-1: none); `counts` (pairs per state).  compose_relative turns (r, t) into camera b's pose.  On noisy data the eight-point
-    fit is only a start for the refinement that follows.  Bad arguments raise ValueError before any device call."""
-    return _relative_pose("ba_relative_pose", None if ransac is None else _lib.ransac_opts(ransac, least=8), nlp, x, pairs, obs_info)
+    fit is only a start for the refinement that follows: refine=dict(...) (the one further keyword; None: no refinement) chains
+    refine_relative_pose behind the call, the dict holding its options (_lib.PAIR_REFINE_KEYS), threshold defaulting to the
+    ransac threshold.  Bad arguments raise ValueError before any device call."""
+    refine = _refine_option("relative_pose", chain, ransac)
+    return _relative_pose("ba_relative_pose", None if ransac is None else _lib.ransac_opts(ransac, least=8), nlp, x, pairs, obs_info, refine)
 
 
-def _relative_pose(entry, opts, nlp, x, pairs, obs_info):
-    """the call of ba_relative_pose and of ba_relative_pose_five_point behind the check of their options"""
+def _refine_option(who, chain, ransac):
+    """the keyword arguments of refine_relative_pose from the `refine=` of relative_pose* (None: no refinement).  `refine` arrives
+    in **chain: the keyword-only defaults of relative_pose* are pinned by their tests, and None is today's call, bit for bit."""
+    unknown = [k for k in chain if k != "refine"]
+    if unknown:
+        raise TypeError(f"{who}() got an unexpected keyword argument {unknown[0]!r}")
+    refine = chain.get("refine")
+    if refine is None:
+        return None
+    if not isinstance(refine, dict):
+        raise ValueError(f"refine must be a dict with the keys {', '.join(_lib.PAIR_REFINE_KEYS)} (or None), got {refine!r}")
+    unknown = [k for k in refine if k not in _lib.PAIR_REFINE_KEYS]
+    if unknown:
+        raise ValueError(f"refine: unknown key {unknown[0]!r} (keys: {', '.join(_lib.PAIR_REFINE_KEYS)})")
+    refine = dict(refine)
+    if "threshold" not in refine:
+        if not isinstance(ransac, dict) or "threshold" not in ransac:
+            raise ValueError("refine: threshold (pixels) is required where there is no ransac threshold")
+        refine["threshold"] = ransac["threshold"]
+    _lib.pair_refine_opts(**refine)
+    return refine
+
+
+def _relative_pose(entry, opts, nlp, x, pairs, obs_info, refine=None):
+    """the call of ba_relative_pose and of ba_relative_pose_five_point behind the check of their options; refine: the keyword
+    arguments of the refine_relative_pose that follows, or None"""
     info3 = _lib.obs_info_pack(obs_info)
     a1, b1 = _lib._pairs(pairs, nlp.ncams)
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -408,20 +435,74 @@ def _relative_pose(entry, opts, nlp, x, pairs, obs_info):
     _lib.check(getattr(_lib.lib(), entry)(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), None if opts is None else C.byref(opts),
                                           _lib.ptr(pose), _lib.ptr(status), _lib.ptr(mp2), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best),
                                           _lib.ptr(counts)))
-    return dict(r=pose[:, :3].copy(), t=pose[:, 3:].copy(), status=np.array(_lib.PAIR_STATES)[status], match_ptr=mp2, inliers=inlier != 0,
+    info = dict(r=pose[:, :3].copy(), t=pose[:, 3:].copy(), status=np.array(_lib.PAIR_STATES)[status], match_ptr=mp2, inliers=inlier != 0,
                 n_inliers=n_in, best_hypothesis=best, counts={s: int(c) for s, c in zip(_lib.PAIR_STATES, counts)})
+    return info if refine is None else refine_relative_pose(nlp, x, pairs, info, obs_info=obs_info, **refine)
 
 
-def relative_pose_five_point(nlp, x, pairs, *, ransac, obs_info=None):
+def relative_pose_five_point(nlp, x, pairs, *, ransac, obs_info=None, **chain):
     """relative_pose with the five-point minimal solver as the hypothesis generator of the consensus stage
     (ba_relative_pose_five_point): every real essential matrix through five sampled matches is a candidate; the winner, the
     refits and the final eight-point fit on the consensus set are those of relative_pose, and so is the returned dict.  ransac
     is required: dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) with sample 5 (the default; nothing else
     is taken) and min_inliers >= 8 (default 8).  This is the entry for noisy detections: eight noisy matches give a poor
-    hypothesis, five give a good one.  Bad arguments raise ValueError before any device call."""
+    hypothesis, five give a good one.  refine=dict(...) as in relative_pose.  Bad arguments raise ValueError before any device
+    call."""
     if ransac is None:
         raise ValueError("relative_pose_five_point: ransac is required (the five-point solver is the hypothesis generator of the consensus stage)")
-    return _relative_pose("ba_relative_pose_five_point", _lib.ransac_opts(ransac, least=5, most=5, least_set=8), nlp, x, pairs, obs_info)
+    opts = _lib.ransac_opts(ransac, least=5, most=5, least_set=8)
+    refine = _refine_option("relative_pose_five_point", chain, ransac)
+    return _relative_pose("ba_relative_pose_five_point", opts, nlp, x, pairs, obs_info, refine)
+
+
+def refine_relative_pose(nlp, x, pairs, info, *, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, threshold, rounds=None,
+                         obs_info=None):
+    """The non-linear refinement of the relative pose of camera pairs on their inlier sets (ba_refine_relative_pose): per pair a
+    Marquardt iteration on the robustified Sampson error over the five degrees of freedom of (R, unit t), then the pair's list
+    re-scored under the result; `rounds` further rounds adopt the re-scored set by the rule of the refits and refine on it.
+    info: the dict relative_pose* returned for the same nlp, x, pairs and obs_info; its `r`, `t`, `status` and `inliers` are
+    read.  max_iter (None: 50; 0 evaluates only), xtol (None: 1e-10, on |delta| in radians), lam0 (None: 1e-4), loss (None:
+    "linear") with f_scale in pixels, threshold (pixels, required: the tau of the inlier test), rounds (None: 2; at most 8).
+    Returns a dict with the keys of info -- `r`, `t`, `inliers` (the set the last refinement ran on) and `n_inliers` replaced for
+    every pair that is not skipped -- plus `refine_status` (names among _lib.PAIR_REFINE_STATES), `cost_before`, `cost_after`,
+    `n_consistent` (the matches that pass the inlier test under the returned pose), `iters` and `refine_counts` (pairs per
+    state).  Bad arguments raise ValueError before any device call."""
+    opts = _lib.pair_refine_opts(max_iter, xtol, lam0, loss, f_scale, threshold, rounds)
+    info3 = _lib.obs_info_pack(obs_info)
+    a1, b1 = _lib._pairs(pairs, nlp.ncams)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    if info3 is not None and info3.shape[0] != nlp.nobs:
+        raise ValueError(f"obs_info: one entry per observation ({nlp.nobs}), got {info3.shape[0]}")
+    if not isinstance(info, dict) or any(k not in info for k in ("r", "t", "status", "inliers")):
+        raise ValueError("info must be the dict of relative_pose or relative_pose_five_point (r, t, status, inliers are read)")
+    n = len(a1)
+    mp = np.zeros(n + 1, dtype=np.int64)
+    _lib.check(_lib.lib().ba_pair_matches(nlp.ncams, nlp.npnts, nlp.nobs, _lib.ptr(nlp.cams_indices), _lib.ptr(nlp.pnts_indices), n, _lib.ptr(a1),
+                                          _lib.ptr(b1), _lib.ptr(mp), None, None))
+    r, t = np.asarray(info["r"], dtype=np.float64), np.asarray(info["t"], dtype=np.float64)
+    names = np.asarray(info["status"])
+    inlier = np.ascontiguousarray(np.asarray(info["inliers"]) != 0, dtype=np.uint8)
+    if r.shape != (n, 3) or t.shape != (n, 3) or names.shape != (n,):
+        raise ValueError(f"info: r and t must have shape ({n}, 3) and status ({n},), got {r.shape}, {t.shape}, {names.shape}")
+    if inlier.shape != (int(mp[-1]),):
+        raise ValueError(f"info: inliers must hold one entry per match ({int(mp[-1])}), got {inlier.shape}")
+    if not np.isin(names, _lib.PAIR_STATES).all():
+        raise ValueError(f"info: status must hold names among {', '.join(_lib.PAIR_STATES)}")
+    status = np.array([_lib.PAIR_STATES.index(s) for s in names], dtype=np.uint8)
+    pose = np.ascontiguousarray(np.concatenate([r, t], axis=1))
+    _lib.set_obs_info(nlp.handle, info3)
+    state, cost = np.zeros(n, dtype=np.uint8), np.zeros((n, 2))
+    n_in = np.array(info["n_inliers"], dtype=np.int32) if "n_inliers" in info else np.zeros(n, dtype=np.int32)
+    n_con, its = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    counts = np.zeros(len(_lib.PAIR_REFINE_STATES), dtype=np.int64)
+    _lib.check(_lib.lib().ba_refine_relative_pose(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), C.byref(opts), _lib.ptr(pose),
+                                                  _lib.ptr(status), _lib.ptr(inlier), _lib.ptr(state), _lib.ptr(cost), _lib.ptr(n_in),
+                                                  _lib.ptr(n_con), _lib.ptr(its), _lib.ptr(counts)))
+    return dict(info, r=pose[:, :3].copy(), t=pose[:, 3:].copy(), inliers=inlier != 0, n_inliers=n_in,
+                refine_status=np.array(_lib.PAIR_REFINE_STATES)[state], cost_before=cost[:, 0].copy(), cost_after=cost[:, 1].copy(),
+                n_consistent=n_con, iters=its, refine_counts={s: int(c) for s, c in zip(_lib.PAIR_REFINE_STATES, counts)})
 
 
 def five_point(nlp, qa, qb):

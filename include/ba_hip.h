@@ -749,7 +749,8 @@ int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device
  * them at 0.1 px, whatever the refits; the refinement behind it (the triangulation, the resections and the LM solve on the
  * seeded x) is what makes the estimate.
  * The remedy is the five-point minimal solver as the hypothesis generator: ba_relative_pose_five_point, below.
- * Out of scope: a non-linear refinement of the pair; unknown focal lengths; homographies and planar
+ * The non-linear refinement of the pair on its final set is ba_refine_relative_pose, further down.
+ * Out of scope: unknown focal lengths; homographies and planar
  * scenes; MSAC or an adaptive hypothesis count; the choice of the initial pair; Float32; several ranks; a device-resident entry. */
 enum { BA_RP_OK = 0, BA_RP_FEW_MATCHES = 1, BA_RP_DEGENERATE = 2, BA_RP_NO_CONSENSUS = 3, BA_RP_STATES = 4 };
 int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1,
@@ -802,6 +803,65 @@ int ba_relative_pose_five_point(ba_problem *p, const double *x /* nvar, host: on
                                 int64_t *counts /* BA_RP_STATES or NULL */);
 int ba_five_point(ba_problem *p, int64_t n, const double *qa /* n x 5 x 2 */, const double *qb /* n x 5 x 2 */,
                   double *E /* n x 10 x 9 */, int32_t *n_sol /* n */);
+
+/* ---- non-linear refinement of the relative pose on its consensus set (an extension) ---------------------------------
+ * ba_refine_relative_pose: what ba_refine_points is to a point and ba_refine_cameras to a camera.  The pose ba_relative_pose*
+ * returns is the eight-point fit on the final set; on 20..50 noisy inliers of a narrow field that linear fit is often not even
+ * consistent with the set it is returned with.  This entry minimises, per pair and over the five degrees of freedom of
+ * (R, t with |t| = 1), the robustified Sampson error over the pair's inlier set, and re-scores the pair's list under the result.
+ * x, the pairs, the match lists, the rays (step 1 above), "used" (Lambda != 0 on both observations, the only thing honoured of
+ * the handle) and the communicator refusal are those of ba_relative_pose.  pose_inout: (r, t) per pair, read and written; t is
+ * taken as given, it is the caller's to pass a unit t.  status_in: the BA_RP_* of the pairs (NULL: all BA_RP_OK).  inlier_inout:
+ * one byte per match in the order of ba_pair_matches; the set M of a pair is the USED matches among those with a byte != 0
+ * (NULL: every used match, and no bytes are returned).
+ * Residual of a match: e = n / sqrt(D), n = d_b' E d_a, D = ((E d_a)_1^2 + (E d_a)_2^2) / f_b^2 + ((E' d_b)_1^2 + (E' d_b)_2^2) /
+ * f_a^2, E = [t]x R: the signed square root of the Sampson distance of the inlier test, in pixels.
+ * Objective: F(R, t) = 1/2 sum over M of c^2 rho(e^2 / c^2), rho and c = f_scale (pixels) the losses of ba_lm_set_loss (opts.loss:
+ * BA_LOSS_*).  Cheirality is not part of the objective; it stays in the inlier test.
+ * Local parameters delta = (d_omega, d_tau) in R^3 x R^2: R+ = exp([d_omega]x) R; t+ = (t + B d_tau) / |t + B d_tau| with
+ * B = [b1 b2], b1 = (e_i x t) / |e_i x t| for i the index of the smallest |t_i| (ties to the lowest), b2 = t x b1.  A step too
+ * small to move any component of t leaves t as it is (the retraction of 0 is the identity, bit for bit).
+ * Jacobian, analytic and exact: dE/d omega_j = [t]x [e_j]x R, dE/d tau_j = [b_j]x R, and de = dn / sqrt(D) - n dD / (2 D^(3/2))
+ * with the derivative of D included.
+ * Step: w = rho'(e^2 / c^2) per match, H = sum w J'J, g = sum w J'e (the reweighting of ba_refine_points); (H + lambda diag H)
+ * delta = -g by a 5 x 5 Cholesky; a pivot that is not > 0 or a delta that is not finite is a rejection.  The trial is accepted
+ * iff F+ is finite and F+ <= F; then lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.
+ * States: BA_RR_CONVERGED -- an accepted step with |delta|_2 <= xtol (radians on both parts); BA_RR_STALLED -- lambda > 1e12;
+ * BA_RR_MAX_ITER; BA_RR_NONFINITE -- F at the start is not finite, the pose is untouched; BA_RR_SKIPPED -- the pair's status_in
+ * is not BA_RP_OK, a focal length is not finite or is 0, or M has fewer than 5 members: the pose, the inlier bytes, n_inliers and
+ * n_consistent come back as the caller filled them, the cost entries are 0.
+ * Options: max_iter (< 0: 50; 0 evaluates only and gives BA_RR_MAX_ITER with the pose's bits unchanged); xtol (<= 0: 1e-10);
+ * lambda0 (<= 0: 1e-4); loss with f_scale finite and > 0; threshold tau in pixels, finite and > 0; rounds (< 0: 2; at most 8).
+ * A value that is not finite, an unknown loss, rounds > 8, NULL options: BA_ERR_ARG.
+ * Returned pose: r = the rotation vector of the final R by the rule of step 8 above, t = the final unit t; a pose that no
+ * accepted step moved keeps its bits.
+ * Rounds: round j = 0 .. rounds refines on the current set M from the current pose, then scores the pair's whole list under the
+ * refined (r, t) with the inlier test above: M'.  If j < rounds, M' is adopted iff |M'| >= |M| and M' != M (the adopt rule of
+ * the refits) and round j + 1 refines on it; otherwise the pair stops.
+ * Per pair: pose_inout = the pose of the last refinement; inlier_inout = the set that refinement ran on, n_inliers its size;
+ * n_consistent = |M'| under the returned pose; cost[2] = F before the first trial on the incoming set and F at the returned
+ * pose on the returned set; iters = the trials summed over the rounds; state = that of the last refinement.
+ * counts[s] = pairs in state s.  Every output but pose_inout and state may be NULL.
+ * One 256-lane workgroup per pair runs the whole iteration of a round in one launch; rounds + 1 launches.  No atomics and one
+ * writer per output: two calls give the same bits, a pair alone gives the bits it gives among many, and the next ba_lm_step /
+ * ba_lm_solve on the handle gives the bits it gives without this call.  npairs == 0 returns BA_OK.
+ * Out of scope: refining focal lengths or distortion with the pair; a device-resident entry; Float32; several ranks. */
+enum { BA_RR_CONVERGED = 0, BA_RR_STALLED = 1, BA_RR_MAX_ITER = 2, BA_RR_NONFINITE = 3, BA_RR_SKIPPED = 4, BA_RR_STATES = 5 };
+typedef struct ba_pair_refine_opts {
+  int max_iter;     /* < 0: 50 */
+  double xtol;      /* <= 0: 1e-10 */
+  double lambda0;   /* <= 0: 1e-4 */
+  int loss;         /* BA_LOSS_* */
+  double f_scale;   /* c in pixels, > 0 */
+  double threshold; /* tau in pixels, > 0 */
+  int rounds;       /* < 0: 2; at most 8 */
+} ba_pair_refine_opts;
+int ba_refine_relative_pose(ba_problem *p, const double *x /* nvar, host: only (k1, k2, f) of the pairs' cameras are read */,
+                            int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1, const ba_pair_refine_opts *opts,
+                            double *pose_inout /* 6 npairs */, const uint8_t *status_in /* npairs, BA_RP_*; NULL: all OK */,
+                            uint8_t *inlier_inout /* per match in ba_pair_matches order; NULL: every used match */,
+                            uint8_t *state /* npairs */, double *cost /* 2 npairs */, int32_t *n_inliers, int32_t *n_consistent,
+                            int32_t *iters, int64_t *counts /* BA_RR_STATES */);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

@@ -390,3 +390,47 @@ function five_point(nlp, qa :: Array{Float64, 3}, qb :: Array{Float64, 3})
   end
   return E, n_sol
 end
+
+# struct ba_pair_refine_opts (include/ba_hip.h)
+struct BaPairRefineOpts
+  max_iter :: Cint
+  xtol :: Cdouble
+  lambda0 :: Cdouble
+  loss :: Cint
+  f_scale :: Cdouble
+  threshold :: Cdouble
+  rounds :: Cint
+end
+
+# The non-linear refinement of the relative pose on its consensus set (ba_refine_relative_pose): per pair a Marquardt iteration
+# on the robustified Sampson error over the five degrees of freedom of (R, unit t), then the pair's list re-scored under the
+# result; `rounds` further rounds adopt the re-scored set by the rule of the refits.  pose (6 x npairs), status and inlier are
+# what relative_pose / relative_pose_five_point returned for the same pairs; loss is a BA_LOSS_* value.  A value below its
+# range means the default (50, 1e-10, 1e-4, 2).  Returns the refined pose, the state of every pair (BA_RR_*), the set the last
+# refinement ran on, the cost before and after (2 x npairs), the sizes of the sets, the matches consistent with the returned
+# pose, the trials and the pairs per state.
+function refine_relative_pose(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64},
+                              pose :: Matrix{Float64}, status :: Vector{UInt8}, inlier :: AbstractVector{Bool};
+                              threshold :: Real, max_iter :: Integer = -1, xtol :: Real = -1.0, lam0 :: Real = -1.0,
+                              loss :: Integer = 0, f_scale :: Real = 1.0, rounds :: Integer = -1)
+  npairs = length(pairs_a)
+  size(pose) == (6, npairs) && length(status) == npairs || error("refine_relative_pose: pose must be 6 x npairs, status npairs")
+  pose = copy(pose)
+  bytes = Vector{UInt8}(inlier)
+  state = zeros(UInt8, npairs)
+  cost = zeros(Float64, 2, npairs)
+  n_inliers = zeros(Int32, npairs)
+  n_consistent = zeros(Int32, npairs)
+  iters = zeros(Int32, npairs)
+  counts = zeros(Int64, 5)
+  opts = Ref(BaPairRefineOpts(Cint(max_iter), Cdouble(xtol), Cdouble(lam0), Cint(loss), Cdouble(f_scale), Cdouble(threshold), Cint(rounds)))
+  GC.@preserve x pairs_a pairs_b opts pose status bytes state cost n_inliers n_consistent iters counts begin
+    bacheck(ccall((:ba_refine_relative_pose, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{BaPairRefineOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{UInt8},
+                   Ptr{UInt8}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                  nlp.handle, pointer(x), npairs, pointer(pairs_a), pointer(pairs_b), Base.unsafe_convert(Ptr{BaPairRefineOpts}, opts),
+                  pointer(pose), pointer(status), pointer(bytes), pointer(state), pointer(cost), pointer(n_inliers),
+                  pointer(n_consistent), pointer(iters), pointer(counts)))
+  end
+  return pose, state, bytes .!= 0, cost, n_inliers, n_consistent, iters, counts
+end
