@@ -81,6 +81,7 @@ SYMBOLS = [
     "ba_ransac_cameras", "ba_ransac_cameras_dev", "ba_ransac_sample",
     "ba_resect_cameras_focal", "ba_resect_cameras_focal_dev", "ba_ransac_cameras_focal", "ba_ransac_cameras_focal_dev",
     "ba_pair_matches", "ba_relative_pose", "ba_relative_pose_five_point", "ba_five_point",
+    "ba_ransac_cameras_p3p", "ba_ransac_cameras_p3p_dev", "ba_p3p",
     "ba_refine_relative_pose",
 ]
 
@@ -172,6 +173,9 @@ def lib():
     L.ba_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
     L.ba_relative_pose_five_point.argtypes = [vp, vp, i64, vp, vp, C.POINTER(RansacOpts), vp, vp, vp, vp, vp, vp, vp]
     L.ba_five_point.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.ba_ransac_cameras_p3p.argtypes = L.ba_ransac_cameras.argtypes
+    L.ba_ransac_cameras_p3p_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
+    L.ba_p3p.argtypes = [vp, i64, vp, vp, vp, vp]
     L.ba_refine_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(PairRefineOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
@@ -576,7 +580,8 @@ def ransac_opts(ransac, least=6, most=16, least_set=None):
     (0 .. 2^64 - 1, default 0) -- or ValueError, before any device call.  least: the smallest sample and min_inliers of the
     entry (6: the resection; 8: relative_pose, where it is also the default sample).  most: the largest sample; least_set: the
     smallest min_inliers where it is not `least` (relative_pose_five_point: least = most = 5, a sample of exactly 5, and
-    least_set = 8, the sets of the eight-point fits behind it)."""
+    least_set = 8, the sets of the eight-point fits behind it; refine_cameras(minimal="p3p"): least = most = 3 and least_set = 6,
+    the sets of the linear resection behind it)."""
     least_set = least if least_set is None else least_set
     if not isinstance(ransac, dict):
         raise ValueError(f"ransac must be a dict with the keys {', '.join(RANSAC_KEYS)} (or None), got {ransac!r}")

@@ -587,9 +587,10 @@ static RansacArgs ransac_args(ba_problem *p, const CamArgs &a, const ba_ransac_o
 }
 
 // The consensus stage of ba_ransac_cameras: hypotheses -> select -> refits x (mask -> resect into the scratch
-// cameras -> rescore) -> mask.  The set reaches k_resect_cameras and k_refine_cameras as information: w.rs_info, the masked copy
-// of the factors (1 0 1 when the caller set none: the values the kernels use without an array).
-static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opts &o, hipStream_t st) {
+// cameras -> rescore) -> mask; gen: what solves a hypothesis, the one thing ba_ransac_cameras_p3p changes.  The set
+// reaches k_resect_cameras and k_refine_cameras as information: w.rs_info, the masked copy of the factors (1 0 1 when the caller
+// set none: the values the kernels use without an array).
+static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opts &o, RansacGen gen, hipStream_t st) {
   CameraWork &w = p->cams;
   if (!w.rs_inlier) {
     BA_CHECK(w.rs_inlier.alloc(p->nobs));
@@ -608,7 +609,7 @@ static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opt
   const RansacArgs r = ransac_args(p, a, o);
   {
     ProfScope ps(p, PC_RANSAC_CAMERAS, st);
-    BA_CHECK(launch_ransac_hypotheses(r, p->ncams, st));
+    BA_CHECK(launch_ransac_hypotheses(r, p->ncams, gen, st));
     BA_CHECK(launch_ransac_select(r, p->ncams, st));
   }
   // the refits on the set: their poses (focal mode: and f^) live in a scratch copy of the cameras (the intrinsics are read from it)
@@ -632,8 +633,8 @@ static int ransac_consensus(ba_problem *p, const CamArgs &a, const ba_ransac_opt
 // (ransac: the consensus stage, which leaves its set as information, then) (start != START_X: k_resect_cameras, the start poses
 // -- START_FOCAL: and focal lengths -- written into d_x, then) k_refine_cameras, on st without a host synchronisation; the
 // counters stay on the device (p->cams.counts)
-static int camera_launch(ba_problem *p, double *d_x, CamStart start, const ba_ransac_opts *ransac, int max_iter, double xtol,
-                         double lambda0, uint8_t *d_status, double *d_cost, hipStream_t st) {
+static int camera_launch(ba_problem *p, double *d_x, CamStart start, const ba_ransac_opts *ransac, RansacGen gen, int max_iter,
+                         double xtol, double lambda0, uint8_t *d_status, double *d_cost, hipStream_t st) {
   BA_CHECK(terms_upload(p));
   BA_CHECK(camera_tables(p));
   CameraWork &w = p->cams;
@@ -642,7 +643,7 @@ static int camera_launch(ba_problem *p, double *d_x, CamStart start, const ba_ra
   if (start != START_X && !w.resect) BA_CHECK(w.resect.alloc(p->ncams));
   CamArgs a = camera_args(p, d_x, start, max_iter, xtol, lambda0, d_status, d_cost);
   if (ransac) {
-    BA_CHECK(ransac_consensus(p, a, *ransac, st));
+    BA_CHECK(ransac_consensus(p, a, *ransac, gen, st));
     a.info = w.rs_info;
   }
   if (start != START_X) BA_CHECK(launch_resect(p, a, st));
@@ -654,7 +655,7 @@ static int refine_cameras_dev(const char *who, ba_problem *p, double *d_x_inout,
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, start, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, start, nullptr, GEN_LINEAR, max_iter, xtol, lambda0, d_status, d_cost, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
 
@@ -664,7 +665,7 @@ static int refine_cameras_host(const char *who, ba_problem *p, double *x_inout, 
   // the cameras only: the point part of the caller's x is never written
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            return camera_launch(p, dx, start, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st);
+                            return camera_launch(p, dx, start, nullptr, GEN_LINEAR, max_iter, xtol, lambda0, d_status, d_cost, st);
                           });
 }
 
@@ -712,28 +713,34 @@ static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, in
   return BA_OK;
 }
 
-static int ransac_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, CamStart start, const ba_ransac_opts *opts, int max_iter,
+// the options of an entry under its generator: P3P takes samples of exactly 3; the sets are those of the linear resection
+static int ransac_cameras_opts(const char *who, RansacGen gen, const ba_ransac_opts *opts, ba_ransac_opts *o) {
+  if (gen == GEN_P3P) return ransac_opts_check(who, opts, o, RS_P3P_SAMPLE, RS_MIN_OBS, RS_P3P_SAMPLE);
+  return ransac_opts_check(who, opts, o, RS_MIN_OBS);
+}
+
+static int ransac_cameras_dev(const char *who, ba_problem *p, double *d_x_inout, CamStart start, RansacGen gen, const ba_ransac_opts *opts, int max_iter,
                               double xtol, double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
                               uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
   ba_ransac_opts o;
-  BA_CHECK(ransac_opts_check(who, opts, &o, RS_MIN_OBS));
+  BA_CHECK(ransac_cameras_opts(who, gen, opts, &o));
   BA_CHECK(camera_check(who, p, d_x_inout, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(camera_launch(p, d_x_inout, start, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(camera_launch(p, d_x_inout, start, &o, gen, max_iter, xtol, lambda0, d_status, d_cost, st));
   BA_CHECK(ransac_results(p, d_inlier, d_n_inliers, d_best_hyp, hipMemcpyDeviceToDevice, st));
   return block_counts(p->cams, counts, iters_max, st);
 }
 
-static int ransac_cameras_host(const char *who, ba_problem *p, double *x_inout, CamStart start, const ba_ransac_opts *opts, int max_iter,
+static int ransac_cameras_host(const char *who, ba_problem *p, double *x_inout, CamStart start, RansacGen gen, const ba_ransac_opts *opts, int max_iter,
                                double xtol, double lambda0, uint8_t *status, double *cost, int64_t *counts, int *iters_max,
                                uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
   ba_ransac_opts o;
-  BA_CHECK(ransac_opts_check(who, opts, &o, RS_MIN_OBS));
+  BA_CHECK(ransac_cameras_opts(who, gen, opts, &o));
   BA_CHECK(camera_check(who, p, x_inout, &max_iter, &xtol, &lambda0));
   return block_host_entry(p, p->cams, x_inout, p->ncams, 9, 3 * p->npnts, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            BA_CHECK(camera_launch(p, dx, start, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+                            BA_CHECK(camera_launch(p, dx, start, &o, gen, max_iter, xtol, lambda0, d_status, d_cost, st));
                             return ransac_results(p, inlier, n_inliers, best_hyp, hipMemcpyDeviceToHost, st);
                           });
 }
@@ -741,25 +748,39 @@ static int ransac_cameras_host(const char *who, ba_problem *p, double *x_inout, 
 extern "C" int ba_ransac_cameras_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
     double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, uint8_t *d_inlier, int32_t *d_n_inliers,
     int32_t *d_best_hyp, void *stream) {
-  return ransac_cameras_dev("ba_ransac_cameras_dev", p, d_x_inout, START_RESECT, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+  return ransac_cameras_dev("ba_ransac_cameras_dev", p, d_x_inout, START_RESECT, GEN_LINEAR, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
                             d_inlier, d_n_inliers, d_best_hyp, stream);
 }
 
 extern "C" int ba_ransac_cameras(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
     uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
-  return ransac_cameras_host("ba_ransac_cameras", p, x_inout, START_RESECT, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
+  return ransac_cameras_host("ba_ransac_cameras", p, x_inout, START_RESECT, GEN_LINEAR, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
                              n_inliers, best_hyp);
 }
 
 extern "C" int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
     double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, uint8_t *d_inlier, int32_t *d_n_inliers,
     int32_t *d_best_hyp, void *stream) {
-  return ransac_cameras_dev("ba_ransac_cameras_focal_dev", p, d_x_inout, START_FOCAL, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
+  return ransac_cameras_dev("ba_ransac_cameras_focal_dev", p, d_x_inout, START_FOCAL, GEN_LINEAR, opts, max_iter, xtol, lambda0, d_status, d_cost, counts, iters_max,
                             d_inlier, d_n_inliers, d_best_hyp, stream);
 }
 
 extern "C" int ba_ransac_cameras_focal(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
     uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
-  return ransac_cameras_host("ba_ransac_cameras_focal", p, x_inout, START_FOCAL, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
+  return ransac_cameras_host("ba_ransac_cameras_focal", p, x_inout, START_FOCAL, GEN_LINEAR, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max, inlier,
                              n_inliers, best_hyp);
+}
+
+// ---- ba_ransac_cameras_p3p: the same call with P3P on three correspondences as the hypothesis generator ------------
+extern "C" int ba_ransac_cameras_p3p_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
+    double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max, uint8_t *d_inlier, int32_t *d_n_inliers,
+    int32_t *d_best_hyp, void *stream) {
+  return ransac_cameras_dev("ba_ransac_cameras_p3p_dev", p, d_x_inout, START_RESECT, GEN_P3P, opts, max_iter, xtol, lambda0, d_status, d_cost, counts,
+                            iters_max, d_inlier, d_n_inliers, d_best_hyp, stream);
+}
+
+extern "C" int ba_ransac_cameras_p3p(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
+    uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp) {
+  return ransac_cameras_host("ba_ransac_cameras_p3p", p, x_inout, START_RESECT, GEN_P3P, opts, max_iter, xtol, lambda0, status, cost, counts, iters_max,
+                             inlier, n_inliers, best_hyp);
 }

@@ -367,6 +367,10 @@ struct CameraWork : BlockWork {
   DevBuf<int> hyp_count, rs_n, rs_best;
   DevBuf<uint8_t> rs_inlier, rs_stopped;
   int64_t hyp_cap = 0;  // hypotheses per camera that hyp_pose and hyp_count hold
+  // ba_p3p: the triples (n x 3 x 2 image points, n x 3 x 3 world points), their poses (n x 4 x 6) and counts
+  DevBuf<double> p3_q, p3_X, p3_pose;
+  DevBuf<int> p3_n;
+  int64_t p3_cap = 0;
 };
 
 // what the consensus kernels of ba_ransac_cameras work on (ba_ransac_kernels.hip; launched from ba_camera_kernels.hip)
@@ -386,7 +390,9 @@ struct RansacArgs {
 };
 constexpr int RANSAC_HYP_DOUBLES = 7;
 uint64_t ransac_seed_mix(uint64_t seed);  // mix(seed) of the header's sampling
-int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, hipStream_t st);
+// what solves a hypothesis: the linear resection of the sample (ba_ransac_cameras, _focal) or P3P (ba_ransac_cameras_p3p)
+enum RansacGen { GEN_LINEAR = 0, GEN_P3P };
+int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, RansacGen gen, hipStream_t st);
 int launch_ransac_select(const RansacArgs &a, int64_t ncams, hipStream_t st);
 // the whole list of every camera that has not stopped under the pose of `cams` (9 per camera); resect: the byte
 // k_resect_cameras left (2: no pose was found)
@@ -406,6 +412,7 @@ __host__ __device__ inline int64_t ransac_draw(uint64_t key, int j, int64_t d) {
   return (int64_t)(((ransac_mix(key ^ (uint64_t)j) >> 32) * (uint64_t)d) >> 32);
 }
 constexpr int RN_DRAWS = 64;  // draws per hypothesis: one per lane
+constexpr int RS_P3P_SAMPLE = 3;  // the sample of a P3P hypothesis (ba_ransac_cameras_p3p)
 // the limits of ba_ransac_opts: the largest sample, hypotheses per list (the selection key holds h in 12 bits) and refits
 constexpr int RN_SAMPLE_MAX = 16, RN_HYP_MAX = 4096, RN_REFITS_MAX = 8;
 // The options as the kernels take them (defaults filled in), or BA_ERR_ARG with `who` in the message.  least: the smallest

@@ -9,13 +9,16 @@
 // a Jacobi rotation are ordered inside the wave (jacobi12<wave_sync>: the LDS operations of one wave complete in order, the
 // fence keeps the compiler from moving them), so the kernel has no workgroup barrier and a wave whose sample is void or
 // degenerate simply leaves.
+// k_ransac_hypotheses_p3p (ba_ransac_cameras_p3p) is the same grid with another generator: three draws, the P3P
+// solver of ba_refine_dev.h in every lane's registers, one scoring pass per solution; no LDS.  k_p3p (ba_p3p) runs that solver
+// alone, one problem per lane.
 // k_ransac_select (one workgroup per camera) picks the winner and writes the inlier bytes; k_ransac_rescore compares the set
 // a refit gives with the current one; k_ransac_mask_info hands the set to k_resect_cameras / k_refine_cameras as information.
 // All three kernels that test an observation call ransac_inlier, so a count never disagrees with the bytes.
 // The rules a consensus call's result hangs on -- which draws are the sample, which hypothesis wins, when a refit's set is
 // adopted -- are in ba_consensus_dev.h, shared with ba_relative_pose; this file keeps the geometry of a hypothesis
 // (hypothesis_pose from the sums onward), the inlier test and the branch of a camera that is not attempted.  The check of the
-// options of both entries (ransac_opts_check) and ba_ransac_sample are at the end of the file.
+// options of both entries (ransac_opts_check), ba_ransac_sample and ba_p3p are at the end of the file.
 // No floating-point atomics, no integer ones either: every output has one writer.
 // Focal mode (RansacArgs.focal and the camera's f free; ba_ransac_cameras_focal): a hypothesis estimates f from its
 // own eigenvector and is scored under it -- its record carries that f, and the refits leave theirs in the scratch cameras.
@@ -159,6 +162,98 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses(RansacArgs a) {
   }
 }
 
+// Hypothesis h of a camera from the P3P solver (ba_ransac_cameras_p3p), the grid and the layout of
+// k_ransac_hypotheses: the wave draws three correspondences, every lane takes all three (shuffles from the lanes of the draws)
+// and runs p3p_solve on them in its own registers -- 64 times the same bits, which costs the time of one and needs neither LDS
+// nor an exchange -- and every solution is scored in one strided pass over the camera's list.  The hypothesis is the solution
+// with the largest count, ties to the first in ascending order of the quartic's root; no sample, no solution: void.  The
+// intrinsics are those of x; there is no focal mode.
+__global__ __launch_bounds__(RN_BLK) void k_ransac_hypotheses_p3p(RansacArgs a) {
+  const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+  const int c = (int)blockIdx.x, h = (int)blockIdx.y * RN_WAVES + wv;
+  if (h >= a.hypotheses) return;
+  const unsigned fm = a.mask ? (unsigned)a.mask[c] : 0u;
+  if (fm & POSE_MASK) return;  // not attempted: k_ransac_select reads nothing of it
+  const int k0 = a.cam_ptr[c], k1 = a.cam_ptr[c + 1], d = k1 - k0;
+  const int64_t slot = (int64_t)c * a.hypotheses + h;
+  const double *xc = a.xc + 9 * (int64_t)c;
+  const double ck1 = xc[6], ck2 = xc[7], cf = xc[8];
+  int best = -1;
+  double keep[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (d > 0 && isfinite(cf) && cf != 0.0) {
+    const int pos = sample_position(a.seed_mix, h, lane, d), o = a.cam_obs[k0 + pos];
+    bool take;
+    int first;
+    if (sample_take(pos, obs_used(a.info, o), lane, P3_POINTS, take, first)) {
+      double Xl[3] = {0.0, 0.0, 0.0}, qx = 0.0, qy = 0.0;
+      if (take) {
+        const double *xp = a.x + 3 * (int64_t)a.pnt0[o];
+        Xl[0] = xp[0], Xl[1] = xp[1], Xl[2] = xp[2];
+        const double2 mm = reinterpret_cast<const double2 *>(a.pt2d)[o];
+        undistort(mm.x / cf, mm.y / cf, ck1, ck2, qx, qy);
+      }
+      unsigned long long from = __ballot(take);  // the lanes of the three draws, in their order
+      double q[P3_POINTS][2], X[P3_POINTS][3];
+#pragma unroll
+      for (int i = 0; i < P3_POINTS; i++) {
+        const int l = __ffsll((long long)from) - 1;
+        from &= from - 1ull;
+        q[i][0] = __shfl(qx, l, 64), q[i][1] = __shfl(qy, l, 64);
+        X[i][0] = __shfl(Xl[0], l, 64), X[i][1] = __shfl(Xl[1], l, 64), X[i][2] = __shfl(Xl[2], l, 64);
+      }
+      double pose[P3_MAX_SOL][6];
+      const unsigned found = p3p_solve(q, X, pose);  // (uniform over the wave)
+#pragma unroll
+      for (int s = 0; s < P3_MAX_SOL; s++) {
+        if (!((found >> s) & 1u)) continue;
+        double P[12];
+        pose_row(pose[s], ck1, ck2, cf, P);
+        int count = 0;
+        for (int k = k0 + lane; k < k1; k += 64) count += ransac_inlier(a, P, a.cam_obs[k]) ? 1 : 0;
+        count = wave_all_sum_int(count);
+        if (count > best) {
+          best = count;
+#pragma unroll
+          for (int i = 0; i < 6; i++) keep[i] = pose[s][i];
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    a.hyp_count[slot] = best;
+    if (best >= 0) {
+#pragma unroll
+      for (int i = 0; i < 6; i++) a.hyp_pose[RANSAC_HYP_DOUBLES * slot + i] = keep[i];
+      a.hyp_pose[RANSAC_HYP_DOUBLES * slot + 6] = cf;
+    }
+  }
+}
+
+// ba_p3p: one problem per lane (p3p_solve is one lane's work, as in the hypothesis kernel); pose: 4 x 6 per problem, the
+// solutions first, the unused slots NaN
+__global__ __launch_bounds__(RN_BLK) void k_p3p(int64_t n, const double *q, const double *X, double *pose, int *n_sol) {
+  const int64_t i = (int64_t)blockIdx.x * RN_BLK + threadIdx.x;
+  if (i >= n) return;
+  double ql[P3_POINTS][2], Xl[P3_POINTS][3], sol[P3_MAX_SOL][6];
+#pragma unroll
+  for (int k = 0; k < P3_POINTS; k++) {
+    ql[k][0] = q[6 * i + 2 * k], ql[k][1] = q[6 * i + 2 * k + 1];
+    Xl[k][0] = X[9 * i + 3 * k], Xl[k][1] = X[9 * i + 3 * k + 1], Xl[k][2] = X[9 * i + 3 * k + 2];
+  }
+  const unsigned found = p3p_solve(ql, Xl, sol);
+  double *out = pose + 6 * P3_MAX_SOL * i;
+  int ns = 0;
+#pragma unroll
+  for (int s = 0; s < P3_MAX_SOL; s++) {
+    if (!((found >> s) & 1u)) continue;
+#pragma unroll
+    for (int e = 0; e < 6; e++) out[6 * ns + e] = sol[s][e];
+    ns++;
+  }
+  for (int e = 6 * ns; e < 6 * P3_MAX_SOL; e++) out[e] = __longlong_as_double(0x7ff8000000000000ll);
+  n_sol[i] = ns;
+}
+
 // One camera per workgroup: the winner among its hypotheses (consensus_winner), its inlier bytes, the size of the set, the
 // winner's index and the "stopped" byte.  A camera that is not attempted: its used observations, -1, stopped.
 __global__ __launch_bounds__(RN_BLK) void k_ransac_select(RansacArgs a) {
@@ -227,8 +322,10 @@ __global__ __launch_bounds__(RN_BLK) void k_ransac_mask_info(RansacArgs a, int64
 
 uint64_t ransac_seed_mix(uint64_t seed) { return ransac_mix(seed); }
 
-int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, hipStream_t st) {
-  return BA_LAUNCH(k_ransac_hypotheses, dim3((unsigned)ncams, grid_for(a.hypotheses, RN_WAVES)), RN_BLK, 0, st, a);
+int launch_ransac_hypotheses(const RansacArgs &a, int64_t ncams, RansacGen gen, hipStream_t st) {
+  const dim3 grid((unsigned)ncams, grid_for(a.hypotheses, RN_WAVES));
+  if (gen == GEN_P3P) return BA_LAUNCH(k_ransac_hypotheses_p3p, grid, RN_BLK, 0, st, a);
+  return BA_LAUNCH(k_ransac_hypotheses, grid, RN_BLK, 0, st, a);
 }
 
 int launch_ransac_select(const RansacArgs &a, int64_t ncams, hipStream_t st) {
@@ -293,5 +390,39 @@ extern "C" int ba_ransac_sample(uint64_t seed, int hypothesis, int64_t degree, c
     if (!skip) pos[n++] = q;
   }
   *n_taken = n;
+  return BA_OK;
+}
+
+// the P3P solver alone; the handle supplies the device, the stream and the buffers
+extern "C" int ba_p3p(ba_problem *p, int64_t n, const double *q, const double *X, double *pose, int32_t *n_sol) {
+  if (!p || n < 0 || (n > 0 && (!q || !X || !pose || !n_sol))) {
+    ba_set_error("ba_p3p: null argument or n < 0");
+    return BA_ERR_ARG;
+  }
+  if (n > (int64_t)INT32_MAX / (6 * P3_MAX_SOL)) {
+    ba_set_error("ba_p3p: %lld problems: more than %lld", (long long)n, (long long)(INT32_MAX / (6 * P3_MAX_SOL)));
+    return BA_ERR_ARG;
+  }
+  if (n == 0) return BA_OK;
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  CameraWork &w = p->cams;
+  if (w.p3_cap < n) {
+    w.p3_cap = 0;
+    BA_CHECK(w.p3_q.alloc(2 * P3_POINTS * n));
+    BA_CHECK(w.p3_X.alloc(3 * P3_POINTS * n));
+    BA_CHECK(w.p3_pose.alloc(6 * P3_MAX_SOL * n));
+    BA_CHECK(w.p3_n.alloc(n));
+    w.p3_cap = n;
+  }
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.p3_q, q, (size_t)(2 * P3_POINTS * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.p3_X, X, (size_t)(3 * P3_POINTS * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  {
+    ProfScope ps(p, PC_RANSAC_CAMERAS, st);  // (the class of the consensus kernels: the solver is their generator)
+    BA_CHECK(BA_LAUNCH(k_p3p, grid_for(n, RN_BLK), RN_BLK, 0, st, n, w.p3_q, w.p3_X, w.p3_pose, w.p3_n));
+  }
+  BA_HIP_CHECK(hipMemcpyAsync(pose, w.p3_pose, (size_t)(6 * P3_MAX_SOL * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(n_sol, w.p3_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
   return BA_OK;
 }

@@ -1,5 +1,5 @@
 // Device pieces shared by the block refinements and the relative pose (ba_point_kernels.hip, ba_camera_kernels.hip,
-// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5q).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
+// ba_ransac_kernels.hip, ba_pair_kernels.hip; DESIGN §5j-§5r).  Included inside the including file's unnamed namespace; gfx950 only.  These files are built without FMA contraction:
 // the operand order and the parentheses here are those of the model's device functions and must stay.
 //
 // The linear resection is written once, further down: k_resect_cameras (one workgroup per camera) and
@@ -812,6 +812,241 @@ __device__ __forceinline__ int five_point_solve(PairScratch &sh, FiveScratch &fs
   }
   wave_sync();
   return __popcll(found);
+}
+
+// ---- P3P: the poses of a calibrated camera through three 2D-3D correspondences ---------------------------------------
+// Unit rays j_i = (q_i, -1) / |(q_i, -1)|, depths s_i > 0 with R X_i + t = s_i j_i.  The three cosine laws between the points,
+// divided by s_1^2 with u = s_2 / s_1 and v = s_3 / s_1, are two quadrics in u whose coefficients are polynomials in v,
+//   u^2 + b1 u + c1 = 0,  b1 = -2 cg,    c1 = 1 - (c^2 / b^2) w(v)
+//   u^2 + b2 u + c2 = 0,  b2 = -2 ca v,  c2 = v^2 - (a^2 / b^2) w(v),   w(v) = v^2 - 2 cb v + 1
+// (a, b, c the sides across X_1, X_2, X_3; ca = j_2.j_3, cb = j_1.j_3, cg = j_1.j_2).  Their resultant in u,
+// (c2 - c1)^2 - (b2 - b1) (b1 c2 - b2 c1), is a quartic in v.  Everything lives in the registers of ONE LANE: k_p3p gives every
+// lane a problem of its own, and the 64 lanes of a wave of k_ransac_hypotheses_p3p all solve the wave's one sample and hold the
+// same bits -- the same code on both paths, no LDS and no exchange between lanes.  All loops over the four roots are unrolled,
+// so that no array is indexed by a variable (an indexed private array would go to scratch).
+constexpr int P3_POINTS = 3, P3_MAX_SOL = 4, P3_ROOT_ITERS = 100;
+
+// rotation_vector on registers: the same arithmetic with the row of the largest diagonal entry taken by selection, not by
+// index.  (A copy: rotation_vector itself works on the LDS of a ResectScratch, and a change to it changes k_resect_cameras.)
+__device__ __forceinline__ void rotation_vector_reg(const double R[9], double r[3]) {
+  const double w0 = R[7] - R[5], w1 = R[2] - R[6], w2 = R[3] - R[1];
+  const double wn = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
+  const double co = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  const double th = atan2(0.5 * wn, co);
+  if (th < 1e-12) {
+    r[0] = 1e-12, r[1] = 0.0, r[2] = 0.0;
+  } else if (co >= 0.0) {
+    r[0] = th * (w0 / wn), r[1] = th * (w1 / wn), r[2] = th * (w2 / wn);
+  } else {
+    int im = 0;
+    double dmax = R[0];
+    if (R[4] > dmax) im = 1, dmax = R[4];
+    if (R[8] > dmax) im = 2, dmax = R[8];
+    const double ki = sqrt((dmax - co) / (1.0 - co));
+    // the symmetric part of row im
+    const double s0 = im == 0 ? R[0] + R[0] : (im == 1 ? R[3] + R[1] : R[6] + R[2]);
+    const double s1 = im == 0 ? R[1] + R[3] : (im == 1 ? R[4] + R[4] : R[7] + R[5]);
+    const double s2 = im == 0 ? R[2] + R[6] : (im == 1 ? R[5] + R[7] : R[8] + R[8]);
+    r[0] = im == 0 ? ki : 0.5 * s0 / ((1.0 - co) * ki);
+    r[1] = im == 1 ? ki : 0.5 * s1 / ((1.0 - co) * ki);
+    r[2] = im == 2 ? ki : 0.5 * s2 / ((1.0 - co) * ki);
+    const double sgn = (r[0] * w0 + r[1] * w1) + r[2] * w2 < 0.0 ? -1.0 : 1.0;
+    const double kn = sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    r[0] = th * (sgn * r[0] / kn), r[1] = th * (sgn * r[1] / kn), r[2] = th * (sgn * r[2] / kn);
+  }
+}
+
+// p(z) and p'(z) of the quartic P (ascending) at the complex z
+__device__ __forceinline__ void p3p_horner(const double P[5], double zr, double zi, double &pr, double &pi, double &dr, double &di) {
+  pr = P[4], pi = 0.0, dr = 0.0, di = 0.0;
+#pragma unroll
+  for (int i = 3; i >= 0; i--) {
+    const double tr = (dr * zr - di * zi) + pr, ti = (dr * zi + di * zr) + pi;
+    dr = tr, di = ti;
+    const double ur = (pr * zr - pi * zi) + P[i], ui = pr * zi + pi * zr;
+    pr = ur, pi = ui;
+  }
+}
+
+// the orthonormal frame of (p2 - p1, p3 - p1), its vectors the columns of F (row-major): e1 along the first, e3 along their
+// cross product, e2 = e3 x e1
+__device__ __forceinline__ void p3p_frame(const double p1[3], const double p2[3], const double p3[3], double F[9]) {
+  const double a0 = p2[0] - p1[0], a1 = p2[1] - p1[1], a2 = p2[2] - p1[2];
+  const double b0 = p3[0] - p1[0], b1 = p3[1] - p1[1], b2 = p3[2] - p1[2];
+  const double an = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  const double e10 = a0 / an, e11 = a1 / an, e12 = a2 / an;
+  const double n0 = e11 * b2 - e12 * b1, n1 = e12 * b0 - e10 * b2, n2 = e10 * b1 - e11 * b0;
+  const double nn = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  const double e30 = n0 / nn, e31 = n1 / nn, e32 = n2 / nn;
+  const double e20 = e31 * e12 - e32 * e11, e21 = e32 * e10 - e30 * e12, e22 = e30 * e11 - e31 * e10;
+  F[0] = e10, F[1] = e20, F[2] = e30;
+  F[3] = e11, F[4] = e21, F[5] = e31;
+  F[6] = e12, F[7] = e22, F[8] = e32;
+}
+
+// The poses through the three correspondences (q_i, X_i): q the undistorted image points, already divided by f.  pose[k], k in
+// 0..3: r and t of the solution at the k-th real root of the quartic in ascending order (the complex ones last); returns the
+// mask of the k whose pose is a solution (v > 0, u > 0, every component finite) -- 0 for a side that is 0 or not finite, three
+// points on a line (|(X2 - X1) x (X3 - X1)| <= 1e-12 c b), a quartic that is not finite or has no leading coefficient.  The
+// caller takes the set bits in ascending k.  (one lane)
+__device__ __forceinline__ unsigned p3p_solve(const double q[P3_POINTS][2], const double X[P3_POINTS][3], double pose[P3_MAX_SOL][6]) {
+  double j[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double n = sqrt((q[i][0] * q[i][0] + q[i][1] * q[i][1]) + 1.0);
+    j[i][0] = q[i][0] / n, j[i][1] = q[i][1] / n, j[i][2] = -1.0 / n;
+  }
+  double e21[3], e31[3], e32[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) e21[i] = X[1][i] - X[0][i], e31[i] = X[2][i] - X[0][i], e32[i] = X[2][i] - X[1][i];
+  const double a = sqrt((e32[0] * e32[0] + e32[1] * e32[1]) + e32[2] * e32[2]);
+  const double b = sqrt((e31[0] * e31[0] + e31[1] * e31[1]) + e31[2] * e31[2]);
+  const double c = sqrt((e21[0] * e21[0] + e21[1] * e21[1]) + e21[2] * e21[2]);
+  if (!(a > 0.0) || !(b > 0.0) || !(c > 0.0) || !isfinite(a) || !isfinite(b) || !isfinite(c)) return 0u;
+  {
+    const double n0 = e21[1] * e31[2] - e21[2] * e31[1], n1 = e21[2] * e31[0] - e21[0] * e31[2], n2 = e21[0] * e31[1] - e21[1] * e31[0];
+    if (!(sqrt((n0 * n0 + n1 * n1) + n2 * n2) > 1e-12 * c * b)) return 0u;
+  }
+  const double ca = (j[1][0] * j[2][0] + j[1][1] * j[2][1]) + j[1][2] * j[2][2];
+  const double cb = (j[0][0] * j[2][0] + j[0][1] * j[2][1]) + j[0][2] * j[2][2];
+  const double cg = (j[0][0] * j[1][0] + j[0][1] * j[1][1]) + j[0][2] * j[1][2];
+  const double A = (c * c) / (b * b), B = (a * a) / (b * b);
+  // c1, c2 (ascending in v); D = c2 - c1; E = b2 - b1 = E0 + E1 v; G = b1 c2 - b2 c1
+  const double c1[3] = {1.0 - A, 2.0 * A * cb, -A}, c2[3] = {-B, 2.0 * B * cb, 1.0 - B};
+  const double D[3] = {c2[0] - c1[0], c2[1] - c1[1], c2[2] - c1[2]};
+  const double E0 = 2.0 * cg, E1 = -2.0 * ca;
+  const double G[4] = {-E0 * c2[0], -E0 * c2[1] - E1 * c1[0], -E0 * c2[2] - E1 * c1[1], -E1 * c1[2]};
+  double P[5];
+  P[0] = D[0] * D[0] - E0 * G[0];
+  P[1] = 2.0 * (D[0] * D[1]) - (E0 * G[1] + E1 * G[0]);
+  P[2] = (2.0 * (D[0] * D[2]) + D[1] * D[1]) - (E0 * G[2] + E1 * G[1]);
+  P[3] = 2.0 * (D[1] * D[2]) - (E0 * G[3] + E1 * G[2]);
+  P[4] = D[2] * D[2] - E1 * G[3];
+  bool fin = true;
+#pragma unroll
+  for (int i = 0; i < 5; i++) fin = fin && isfinite(P[i]);
+  if (!fin || P[4] == 0.0) return 0u;
+  // the four roots by the simultaneous iteration of Aberth and Ehrlich, from a circle of their geometric mean modulus
+  double zr[4], zi[4];
+  {
+    const double g = fabs(P[0] / P[4]);
+    const double rad = g > 0.0 ? exp(log(g) / 4.0) : 1.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const double th = 0.4 + 1.5707963267948966 * (double)k;
+      zr[k] = rad * cos(th), zi[k] = rad * sin(th);
+    }
+  }
+#pragma nounroll
+  for (int it = 0; it < P3_ROOT_ITERS; it++) {
+    double stepr[4], stepi[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      double pr, pi, dr, di;
+      p3p_horner(P, zr[k], zi[k], pr, pi, dr, di);
+      const double dn = dr * dr + di * di;
+      double wr = (pr * dr + pi * di) / dn, wi = (pi * dr - pr * di) / dn;  // p / p'
+      if (pr == 0.0 && pi == 0.0) wr = 0.0, wi = 0.0;
+      double sr = 0.0, si = 0.0;  // the sum of 1 / (z_k - z_j) over the other roots
+#pragma unroll
+      for (int l = 0; l < 4; l++) {
+        if (l == k) continue;
+        const double ar = zr[k] - zr[l], ai = zi[k] - zi[l];
+        const double an = ar * ar + ai * ai;
+        if (an > 0.0) sr += ar / an, si -= ai / an;  // (two iterates that coincide do not repel each other)
+      }
+      const double er = 1.0 - (wr * sr - wi * si), ei = -(wr * si + wi * sr), en = er * er + ei * ei;
+      stepr[k] = (wr * er + wi * ei) / en, stepi[k] = (wi * er - wr * ei) / en;
+    }
+    bool moving = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      zr[k] -= stepr[k], zi[k] -= stepi[k];
+      moving = moving || !(stepr[k] * stepr[k] + stepi[k] * stepi[k] <= 1e-20 * (zr[k] * zr[k] + zi[k] * zi[k]));
+    }
+    if (!moving) break;
+  }
+  // a real root takes two Newton steps on the real axis; a complex one sorts last
+  const double inf = __builtin_inf();
+  double v[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const bool real = isfinite(zr[k]) && isfinite(zi[k]) && fabs(zi[k]) <= 1e-7 * sqrt(zr[k] * zr[k] + zi[k] * zi[k]);
+    double z = zr[k];
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+      double pr, pi, dr, di;
+      p3p_horner(P, z, 0.0, pr, pi, dr, di);
+      const double step = pr / dr;
+      if (isfinite(step)) z -= step;
+    }
+    v[k] = real ? z : inf;
+  }
+#define P3_ORDER(i, k)                 \
+  {                                    \
+    const double lo = v[i], hi = v[k]; \
+    const bool sw = lo > hi;           \
+    v[i] = sw ? hi : lo;               \
+    v[k] = sw ? lo : hi;               \
+  }
+  P3_ORDER(0, 1) P3_ORDER(2, 3) P3_ORDER(0, 2) P3_ORDER(1, 3) P3_ORDER(1, 2)
+#undef P3_ORDER
+  double Fw[9];
+  p3p_frame(X[0], X[1], X[2], Fw);
+  const double a2 = a * a, b2 = b * b, cc2 = c * c;
+  unsigned found = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const double vk = v[k];
+    if (!(vk < inf)) continue;  // (a complex root: uniform over the wave of a hypothesis, which all hold the same roots)
+    bool ok = true;
+    const double wv = (vk * vk - 2.0 * cb * vk) + 1.0;
+    const double c1v = 1.0 - A * wv, c2v = vk * vk - B * wv;
+    const double den = -(E0 + E1 * vk);  // b1 - b2
+    double u = (c2v - c1v) / den;
+    if (den == 0.0 || !isfinite(u)) {  // the root of the first quadric that satisfies the second better
+      const double disc = cg * cg - c1v, sq = sqrt(disc > 0.0 ? disc : 0.0);
+      const double ua = cg + sq, ub = cg - sq;
+      const double fa = fabs((ua * ua - 2.0 * ca * vk * ua) + c2v), fb = fabs((ub * ub - 2.0 * ca * vk * ub) + c2v);
+      u = fb < fa ? ub : ua;
+    }
+    ok = ok && vk > 0.0 && u > 0.0;
+    double s1 = b / sqrt(wv), s2 = u * s1, s3 = vk * s1;
+    // two Gauss-Newton steps on the three cosine laws
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+      const double f1 = ((s2 * s2 + s3 * s3) - 2.0 * ca * (s2 * s3)) - a2;
+      const double f2 = ((s1 * s1 + s3 * s3) - 2.0 * cb * (s1 * s3)) - b2;
+      const double f3 = ((s1 * s1 + s2 * s2) - 2.0 * cg * (s1 * s2)) - cc2;
+      // J = 2 [[0, m01, m02], [m10, 0, m12], [m20, m21, 0]]
+      const double m01 = s2 - ca * s3, m02 = s3 - ca * s2;
+      const double m10 = s1 - cb * s3, m12 = s3 - cb * s1;
+      const double m20 = s1 - cg * s2, m21 = s2 - cg * s1;
+      const double det = 2.0 * (m01 * (m12 * m20) + m02 * (m10 * m21));
+      const double d1 = ((-(m12 * m21)) * f1 + (m02 * m21) * f2 + (m01 * m12) * f3) / det;
+      const double d2 = ((m12 * m20) * f1 + (-(m02 * m20)) * f2 + (m02 * m10) * f3) / det;
+      const double d3 = ((m10 * m21) * f1 + (m01 * m20) * f2 + (-(m01 * m10)) * f3) / det;
+      if (isfinite(d1) && isfinite(d2) && isfinite(d3)) s1 -= d1, s2 -= d2, s3 -= d3;
+    }
+    const double Y1[3] = {s1 * j[0][0], s1 * j[0][1], s1 * j[0][2]};
+    const double Y2[3] = {s2 * j[1][0], s2 * j[1][1], s2 * j[1][2]};
+    const double Y3[3] = {s3 * j[2][0], s3 * j[2][1], s3 * j[2][2]};
+    double Fc[9], R[9];
+    p3p_frame(Y1, Y2, Y3, Fc);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int l = 0; l < 3; l++) R[3 * i + l] = (Fc[3 * i] * Fw[3 * l] + Fc[3 * i + 1] * Fw[3 * l + 1]) + Fc[3 * i + 2] * Fw[3 * l + 2];
+    rotation_vector_reg(R, pose[k]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      pose[k][3 + i] = Y1[i] - ((R[3 * i] * X[0][0] + R[3 * i + 1] * X[0][1]) + R[3 * i + 2] * X[0][2]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) ok = ok && isfinite(pose[k][i]);
+    if (ok) found |= 1u << k;
+  }
+  return found;
 }
 
 // ---- the non-linear refinement of a pair: Marquardt steps on the signed Sampson residual in 5 unknowns -------------

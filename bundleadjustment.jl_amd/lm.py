@@ -305,7 +305,7 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
     return x, _block_info(status, cost, counts, its)
 
 
-def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
+def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, minimal=None, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None, fixed_cameras=None,
                    fixed_camera_params=None, camera_priors=None, centre_priors=None, shared_intrinsics=None):
     """The cameras of x with its points held (ba_refine_cameras), the other half of refine_points: every camera is an independent
     problem in at most 9 unknowns -- the objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info`, `camera_priors`
@@ -327,6 +327,12 @@ def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, m
     included; f is written into x_new, a free k1 / k2 starts the refinement at 0, a held one keeps its value and is ignored by
     the linear stage.  Every hypothesis of the consensus stage then carries its own f.  A camera with f held or in a group is
     resected with the intrinsics of x as without the flag.  On noisy data the linear f is only a start for the refinement.
+    minimal="p3p" with resect=True and ransac= (ba_ransac_cameras_p3p) draws three correspondences per hypothesis instead of six and
+    solves them exactly: every real P3P pose (up to four) is scored and the best is the hypothesis.  A sample is clean with
+    probability w^3 instead of w^6 at inlier share w, which is what registers a camera at 60-70 % wrong matches.  `sample` must be
+    3 (or unset); min_inliers is still at least 6, the winner, the refits and the finish are those of the ransac= call, and so
+    is the returned dict.  It needs the intrinsics of x (a camera whose f is not finite or 0 is `degenerate`) and excludes
+    estimate_focal=True.  None: the six-point linear hypotheses.
     max_iter (None: 100; 0: evaluate only -- with resect=True the resected poses are returned), xtol (None: 1e-10; |D delta| <= xtol (|D C| + xtol) with
     D_j = sqrt(H_jj): the predicted motion in pixels), lam0 (None: 1e-4).  fixed_camera_params hold components (("k1", "k2",
     "f"): a pose-only refit); fixed_cameras are skipped; the members of the groups of shared_intrinsics keep their (k1, k2, f).
@@ -343,12 +349,18 @@ def refine_cameras(nlp, x, *, resect=False, estimate_focal=False, ransac=None, m
         raise ValueError(f"estimate_focal must be True or False, got {estimate_focal!r}")
     if estimate_focal and not resect:
         raise ValueError("estimate_focal needs resect=True (the focal length comes out of the linear resection)")
-    focal = "_focal" if estimate_focal else ""
+    if minimal is not None and not (isinstance(minimal, str) and minimal == "p3p"):
+        raise ValueError(f'minimal must be "p3p" or None, got {minimal!r}')
+    if minimal is not None and (not resect or ransac is None):
+        raise ValueError('minimal="p3p" needs resect=True and ransac= (P3P is the hypothesis generator of the consensus stage)')
+    if minimal is not None and estimate_focal:
+        raise ValueError('minimal="p3p" excludes estimate_focal=True (P3P needs the focal length; P4Pf is not provided)')
+    focal = "_p3p" if minimal is not None else ("_focal" if estimate_focal else "")
     opts = None
     if ransac is not None:
         if not resect:
             raise ValueError("ransac needs resect=True (the consensus stage stands in front of the linear resection)")
-        opts = _lib.ransac_opts(ransac)
+        opts = _lib.ransac_opts(ransac, least=3, most=3, least_set=6) if minimal is not None else _lib.ransac_opts(ransac)
     x, args = _block_args(nlp, x, max_iter, xtol, lam0)
     terms.apply(nlp)  # (x is not checked against the grouping: the members' intrinsics are held, whatever they are)
     status, cost = np.zeros(nlp.ncams, dtype=np.uint8), np.zeros((nlp.ncams, 2))
@@ -518,6 +530,22 @@ def five_point(nlp, qa, qb):
     E, n_sol = np.full((n, 10, 3, 3), np.nan), np.zeros(n, dtype=np.int32)
     _lib.check(_lib.lib().ba_five_point(nlp.handle, n, _lib.ptr(qa), _lib.ptr(qb), _lib.ptr(E), _lib.ptr(n_sol)))
     return E, n_sol
+
+
+def p3p(nlp, q, X):
+    """The poses of a calibrated camera through three 2D-3D correspondences (ba_p3p), n independent problems: q (n, 3, 2) are
+    undistorted image points already divided by f (the ray of a point is (q, -1)), X (n, 3, 3) their world points.  Returns
+    (poses, n_sol): poses (n, 4, 6) holds the solutions (r, t) of a problem first, in ascending order of the root of the
+    quartic they come from, NaN in the unused slots; n_sol (n,) their number, 0..4 (0: two points coincide, the three lie on a
+    line, or an entry is not finite).  nlp supplies the device and the stream.  Bad arguments raise ValueError before any device
+    call."""
+    q, X = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(X, dtype=np.float64)
+    if q.ndim != 3 or q.shape[1:] != (3, 2) or X.shape != (q.shape[0], 3, 3):
+        raise ValueError(f"p3p: q must have shape (n, 3, 2) and X (n, 3, 3), got {q.shape} and {X.shape}")
+    n = q.shape[0]
+    poses, n_sol = np.full((n, 4, 6), np.nan), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.lib().ba_p3p(nlp.handle, n, _lib.ptr(q), _lib.ptr(X), _lib.ptr(poses), _lib.ptr(n_sol)))
+    return poses, n_sol
 
 
 def schur_pattern(nlp):

@@ -560,7 +560,7 @@ int ba_refine_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, i
  * with a communicator is refused (BA_ERR_ARG).
  * Out of scope: outlier rejection inside the linear solve (the robust loss acts in the refinement; the consensus stage in front
  * of this entry is ba_ransac_cameras, below), unknown intrinsics beyond the focal length (an unknown f: ba_resect_cameras_focal,
- * further down; a full 3 x 4 DLT with RQ is not provided), minimal P3P, Float32, several ranks, resection inside the LM loop. */
+ * further down; a full 3 x 4 DLT with RQ is not provided), Float32, several ranks, resection inside the LM loop. */
 int ba_resect_cameras(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
                       uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
                       int64_t *counts /* BA_PT_STATES + 1 (last: cameras flagged BEHIND) or NULL */, int *iters_max /* or NULL */);
@@ -609,8 +609,9 @@ int ba_resect_cameras_dev(ba_problem *p, double *d_x_inout /* nvar, device */, i
  * on `stream`; it synchronises only to hand over counts / iters_max, as its sibling does.
  * Two calls give the same bits (no floating-point atomics); the next ba_lm_step / ba_lm_solve on the handle gives the same bits
  * as without the call.
- * Out of scope: an adaptive hypothesis count, MSAC / LO-RANSAC scoring, minimal P3P samples, unknown intrinsics beyond the focal
- * length (an unknown f: ba_ransac_cameras_focal, further down), Float32, several ranks. */
+ * Out of scope: an adaptive hypothesis count, MSAC / LO-RANSAC scoring, unknown intrinsics beyond the focal
+ * length (an unknown f: ba_ransac_cameras_focal, further down), Float32, several ranks.  (Minimal samples of three: ba_ransac_cameras_p3p,
+ * further down.) */
 typedef struct ba_ransac_opts {
   double threshold;
   int hypotheses, sample, refits, min_inliers;
@@ -669,7 +670,7 @@ int ba_ransac_sample(uint64_t seed, int hypothesis, int64_t degree, const uint8_
  * communicator is refused (BA_ERR_ARG).  On noisy data the linear f^ is only a start (its relative error is 1e-2 at degree 255
  * and can reach 0.7 at degree 6): the refinement behind it is what makes the estimate, as for the calibrated resection.
  * Out of scope: k1 / k2 estimation in the linear stage, a principal point that is not the origin or a general K by RQ, a second
- * calibrated pass after f^, minimal P3P or P4Pf solvers, MSAC or an adaptive hypothesis count, Float32, several ranks, the
+ * calibrated pass after f^, a minimal P4Pf solver (P3P with the f of x: ba_ransac_cameras_p3p, further down), MSAC or an adaptive hypothesis count, Float32, several ranks, the
  * tied problem over a group. */
 int ba_resect_cameras_focal(ba_problem *p, double *x_inout /* nvar, host */, int max_iter, double xtol, double lambda0,
                             uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams: before, after; or NULL */,
@@ -862,6 +863,56 @@ int ba_refine_relative_pose(ba_problem *p, const double *x /* nvar, host: only (
                             uint8_t *inlier_inout /* per match in ba_pair_matches order; NULL: every used match */,
                             uint8_t *state /* npairs */, double *cost /* 2 npairs */, int32_t *n_inliers, int32_t *n_consistent,
                             int32_t *iters, int64_t *counts /* BA_RR_STATES */);
+
+/* ---- P3P minimal samples for the consensus stage of the camera resection (an extension) ------------------------------
+ * ba_ransac_cameras_p3p: ba_ransac_cameras with another hypothesis generator.  Arguments, outputs, states, the communicator
+ * refusal, the sampling rule, the inlier test, the winner, the refits with their adopt rule (linear resections on the set) and
+ * the finish -- with its bit-for-bit contract with ba_resect_cameras under an information that drops the outliers -- are those of
+ * ba_ransac_cameras.  What differs:
+ *   sample (<= 0: 3) must be 3; min_inliers (<= 0: 6) at least 6: the refits and the finish are still the linear resection, which
+ *   needs six.  threshold, hypotheses, refits and seed as there; NULL options are BA_ERR_ARG.
+ *   The intrinsics (k1, k2, f) are read from x.  A camera whose f is not finite or is 0 has only void hypotheses and ends
+ *   BA_PT_DEGENERATE.  There is no focal mode.
+ *   The sample of hypothesis h is what the sampling rule above gives for m = 3 on the camera's list.  (ba_ransac_sample itself
+ *   keeps refusing m < 6.)
+ *   Hypothesis h: the three sampled measurements are undistorted with the camera's intrinsics (the fixed-point iteration of
+ *   ba_resect_cameras on pt2d / f); every solution of ba_p3p (below) on them, in its order, is a candidate; a candidate is scored
+ *   by its inlier count over the camera's whole list under (pose, k1, k2, f); the hypothesis is the candidate with the largest
+ *   count, ties to the first.  Its record is that of ba_ransac_cameras.  No sample, a degenerate sample, no candidate: void.
+ * A sample of three is clean with probability w^3 at inlier share w where a sample of six has w^6: at 65 % wrong matches 128
+ * hypotheses of six hold no clean one, 128 of three hold several.
+ * ba_p3p: the solver alone, n independent problems, one lane each.  q: three undistorted image points per problem, already
+ * divided by f; X: their world points.  pose: per problem four slots of (r, t) with R X_i + t = s_i j_i, s_i > 0; the solutions
+ * first, in ascending order of the root v of the quartic below, the unused slots NaN.  n_sol: their number, 0..4.  Two calls
+ * give the same bits; a problem's result does not depend on the others of the call.  n == 0 returns BA_OK; the handle supplies
+ * the device, the stream and the buffers, and a handle with a communicator is fine.
+ * The solver: unit rays j_i = (q_i, -1) / |(q_i, -1)|; sides a = |X_2 - X_3|, b = |X_1 - X_3|, c = |X_1 - X_2| -- a side that
+ * is 0 or not finite, or |(X_2 - X_1) x (X_3 - X_1)| <= 1e-12 c b: 0 solutions; ca = j_2.j_3, cb = j_1.j_3, cg = j_1.j_2.  With
+ * the depths s_2 = u s_1 and s_3 = v s_1 the three cosine laws are two quadrics in u,
+ *   u^2 - 2 cg u + 1 - (c^2 / b^2) w(v) = 0   and   u^2 - 2 ca v u + v^2 - (a^2 / b^2) w(v) = 0,   w(v) = v^2 - 2 cb v + 1,
+ * u^2 + b_1 u + c_1 and u^2 + b_2 u + c_2 for short; their resultant (c_2 - c_1)^2 - (b_2 - b_1) (b_1 c_2 - b_2 c_1) is a quartic in
+ * v (a coefficient that is not finite or a leading coefficient 0: 0 solutions).  Its roots by the simultaneous complex iteration of
+ * ba_five_point at degree 4, a root being real when |Im z| <= 1e-7 |z|; a real root takes two Newton steps on the real axis.  The
+ * real roots in ascending order: u = (c_2 - c_1)(v) / (b_1 - b_2)(v) -- when that denominator is 0 or the quotient is not
+ * finite, the root cg +- sqrt(max(cg^2 - c_1(v), 0)) of the first quadric at which the second is smaller in magnitude (ties: +);
+ * a root with v <= 0 or u <= 0 gives no solution; s_1 = b / sqrt(w(v)); (s_1, s_2, s_3) take two Newton steps on the three
+ * cosine laws (a step that is not finite is not taken); Y_i = s_i j_i; on either side the orthonormal frame of (P_2 - P_1,
+ * P_3 - P_1) -- e_1 along the first, e_3 along e_1 x (P_3 - P_1), e_2 = e_3 x e_1, as columns of F; R = F_cam F_world',
+ * t = Y_1 - R X_1; r the rotation vector of step 7 of ba_resect_cameras.  A pose with a component that is not finite is no
+ * solution.
+ * Out of scope: P4Pf and other unknown-focal minimal solvers, a finish from the hypothesis's pose for sets smaller than six, MSAC
+ * or LO-RANSAC scoring, an adaptive hypothesis count, an early exit of the scoring pass, Float32, several ranks. */
+int ba_ransac_cameras_p3p(ba_problem *p, double *x_inout /* nvar, host */, const ba_ransac_opts *opts, int max_iter, double xtol,
+                          double lambda0, uint8_t *status /* ncams or NULL */, double *cost /* 2 ncams or NULL */,
+                          int64_t *counts /* BA_PT_STATES + 1 or NULL */, int *iters_max /* or NULL */,
+                          uint8_t *inlier /* nobs or NULL */, int32_t *n_inliers /* ncams or NULL */, int32_t *best_hyp /* ncams or NULL */);
+int ba_ransac_cameras_p3p_dev(ba_problem *p, double *d_x_inout /* nvar, device */, const ba_ransac_opts *opts /* host */, int max_iter,
+                              double xtol, double lambda0, uint8_t *d_status /* ncams or NULL */, double *d_cost /* 2 ncams or NULL */,
+                              int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */,
+                              uint8_t *d_inlier /* nobs or NULL */, int32_t *d_n_inliers /* ncams or NULL */,
+                              int32_t *d_best_hyp /* ncams or NULL */, void *stream);
+int ba_p3p(ba_problem *p, int64_t n, const double *q /* n x 3 x 2 */, const double *X /* n x 3 x 3 */,
+           double *pose /* n x 4 x 6 */, int32_t *n_sol /* n */);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

@@ -391,6 +391,60 @@ function five_point(nlp, qa :: Array{Float64, 3}, qb :: Array{Float64, 3})
   return E, n_sol
 end
 
+# P3P minimal samples for the consensus stage of the camera resection (an extension): include/ba_hip.h, ba_ransac_cameras_p3p.
+# ransac_cameras! with three correspondences per hypothesis instead of six, solved exactly: every real P3P pose (up to four) is
+# scored and the best is the hypothesis.  `sample` must be 3 (or below its range: the default 3), min_inliers is still at least
+# 6; the intrinsics of `x` are read.  Arguments and return values are those of ransac_cameras!.
+function ransac_cameras_p3p!(nlp, x :: Vector{Float64}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                             refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                             xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  status = zeros(UInt8, nlp.ncams)
+  cost = zeros(Float64, 2, nlp.ncams)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  inlier = zeros(UInt8, nlp.nobs)
+  n_inliers = zeros(Int32, nlp.ncams)
+  best_hyp = zeros(Int32, nlp.ncams)
+  GC.@preserve x status cost counts inlier n_inliers best_hyp begin
+    bacheck(ccall((:ba_ransac_cameras_p3p, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, pointer(x), opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters, pointer(inlier), pointer(n_inliers), pointer(best_hyp)))
+  end
+  return status, cost, counts, Int(iters[]), inlier .!= 0, n_inliers, best_hyp
+end
+
+function ransac_cameras_p3p_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                                 refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                                 xtol :: Real = -1.0, lam0 :: Real = -1.0, d_status :: Ptr{Cvoid} = C_NULL,
+                                 d_cost :: Ptr{Cvoid} = C_NULL, d_inlier :: Ptr{Cvoid} = C_NULL, d_n_inliers :: Ptr{Cvoid} = C_NULL,
+                                 d_best_hyp :: Ptr{Cvoid} = C_NULL, stream :: Ptr{Cvoid} = C_NULL)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  bacheck(ccall((:ba_ransac_cameras_p3p_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                nlp.handle, d_x, opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
+  return nothing
+end
+
+# The solver alone (ba_p3p): q is 2 x 3 x n, undistorted image points already divided by f (the ray is (q, -1)); X is 3 x 3 x n,
+# X[:, i, k] the world point of correspondence i of problem k.  Returns pose (6 x 4 x n: pose[:, s, k] is (r, t) of solution s of
+# problem k, in ascending order of the quartic's root, NaN in the unused slots) and the number of solutions of every problem.
+function p3p(nlp, q :: Array{Float64, 3}, X :: Array{Float64, 3})
+  size(q, 1) == 2 && size(q, 2) == 3 && size(X) == (3, 3, size(q, 3)) || error("p3p: q must be 2 x 3 x n and X 3 x 3 x n")
+  n = size(q, 3)
+  pose = fill(NaN, 6, 4, n)
+  n_sol = zeros(Int32, n)
+  GC.@preserve q X pose n_sol begin
+    bacheck(ccall((:ba_p3p, libba), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                  nlp.handle, n, pointer(q), pointer(X), pointer(pose), pointer(n_sol)))
+  end
+  return pose, n_sol
+end
+
 # struct ba_pair_refine_opts (include/ba_hip.h)
 struct BaPairRefineOpts
   max_iter :: Cint

@@ -23,10 +23,16 @@ shapes, against the fixed-point LM solve on the same scene.
            nine entries -- f is estimated by the linear stage and by every hypothesis (m = 8).  The same clocks and event times,
            and the relative error of f against the generator's cameras after the linear stage and after the refinement.
 
+  --p3p    with --ransac: ba_ransac_cameras_p3p_dev (m = 3, everything else as --ransac) on the same scene, the same
+           clocks, event times and shares; the outlier-free --resect row is left out (the --ransac run beside it has it).
+  --outliers FRACTION   with --ransac: the share of every camera's detections that is displaced (default 0.3)
+  --exact  with --ransac: the detections that are not displaced are the exact projections of the true scene, not the
+           generator's (0.5 px of noise)
+
 One JSON object per shape on stdout; all of them to profiles/refine_cameras_bench.json (--resect: profiles/resect_cameras_bench.json,
 --ransac: profiles/ransac_cameras_bench.json, --focal: profiles/resect_focal_bench.json, --focal --ransac:
-profiles/ransac_focal_bench.json), or the file given.
-usage: python tools/bench_refine_cameras.py [--resect | --ransac] [--focal] [out.json] [reps] [shape ...]"""
+profiles/ransac_focal_bench.json, --ransac --p3p: profiles/ransac_p3p_run.json), or the file given.
+usage: python tools/bench_refine_cameras.py [--resect | --ransac [--p3p] [--outliers FRACTION] [--exact]] [--focal] [out.json] [reps] [shape ...]"""
 import ctypes as C
 import json
 import os
@@ -154,23 +160,26 @@ RANSAC = dict(threshold=4.0, hypotheses=128, sample=6, refits=2, seed=0)
 OUTLIER_FRACTION = 0.3
 
 
-def measure_ransac(ba, name, reps, focal=False):
+def measure_ransac(ba, name, reps, focal=False, p3p=False, fraction=OUTLIER_FRACTION, exact=False):
     L, lib = ba._lib.lib(), ba._lib
-    entry = L.ba_ransac_cameras_focal_dev if focal else L.ba_ransac_cameras_dev
-    options = dict(RANSAC, sample=8) if focal else RANSAC
+    entry = L.ba_ransac_cameras_p3p_dev if p3p else L.ba_ransac_cameras_focal_dev if focal else L.ba_ransac_cameras_dev
+    options = dict(RANSAC, sample=3) if p3p else dict(RANSAC, sample=8) if focal else RANSAC
     p = ba.synthetic.make_named(name)
     n, nc, nvar, nobs = p["npnts"], p["ncams"], len(p["x0"]), p["nobs"]
-    pt2d, is_out = ba.synthetic.add_outliers(p, fraction=OUTLIER_FRACTION, seed=1)
+    if exact:
+        X, Cm = np.asarray(p["x_true"][:3 * n]).reshape(n, 3), np.asarray(p["x_true"][3 * n:]).reshape(nc, 9)
+        p = dict(p, pt2d=np.ascontiguousarray(ba.synthetic.project(X[p["pnt_idx1"] - 1], Cm[p["cam_idx1"] - 1]).ravel()))
+    pt2d, is_out = ba.synthetic.add_outliers(p, fraction=fraction, seed=1)
     q = dict(p, pt2d=np.ascontiguousarray(pt2d.ravel()))
     m = ba.BALNLPModel(arrays=ba.synthetic.as_arrays(q))
     cam0 = p["cam_idx1"] - 1
     deg = np.bincount(cam0, minlength=nc)
     row = {"shape": name, "ncams": nc, "npnts": n, "nobs": nobs, "xtol": XTOL, "degree_min": int(deg.min()),
-           "degree_median": int(np.median(deg)), "degree_max": int(deg.max()), "outlier_fraction": OUTLIER_FRACTION,
-           "outliers": int(is_out.sum()), "options": options, "focal": focal}
+           "degree_median": int(np.median(deg)), "degree_max": int(deg.max()), "outlier_fraction": fraction,
+           "outliers": int(is_out.sum()), "options": options, "focal": focal, "p3p": p3p, "exact": exact}
     x0 = np.array(p["x_true"], dtype=np.float64, copy=True)  # the true points are held
     x0[3 * n:].reshape(nc, 9)[:, :(9 if focal else 6)] = np.nan
-    opts = lib.ransac_opts(options)
+    opts = lib.ransac_opts(options, least=3, most=3, least_set=6) if p3p else lib.ransac_opts(options)
     d_x = C.c_void_p()
     lib.check(L.ba_dev_malloc(m.handle, 8 * nvar, C.byref(d_x)))
     counts, its = np.zeros(7, dtype=np.int64), C.c_int(0)
@@ -191,7 +200,7 @@ def measure_ransac(ba, name, reps, focal=False):
     m.profile(False)
     lib.check(L.ba_dev_free(m.handle, d_x))
     med = statistics.median(wall)
-    x, info = ba.refine_cameras(m, x0, resect=True, estimate_focal=focal, ransac=options, xtol=XTOL)
+    x, info = ba.refine_cameras(m, x0, resect=True, estimate_focal=focal, ransac=options, minimal="p3p" if p3p else None, xtol=XTOL)
     same = np.bincount(cam0, weights=(info["inliers"] != ~is_out).astype(float), minlength=nc) == 0
     C1, Ct = x[3 * n:].reshape(nc, 9), np.asarray(p["x_true"])[3 * n:].reshape(nc, 9)
     row["ransac"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall],
@@ -206,18 +215,30 @@ def measure_ransac(ba, name, reps, focal=False):
     if focal:
         row["f_error_refined"] = focal_errors(x, p)
     m.close()
-    row["resect_outlier_free"] = measure_resect(ba, name, reps, focal)["resect"]
+    if not p3p:
+        row["resect_outlier_free"] = measure_resect(ba, name, reps, focal)["resect"]
     return row
 
 
 def main():
     args = sys.argv[1:]
-    resect, ransac, focal = "--resect" in args, "--ransac" in args, "--focal" in args
+    resect, ransac, focal, p3p, exact = ("--" + w in args for w in ("resect", "ransac", "focal", "p3p", "exact"))
     resect = resect or (focal and not ransac)
-    args = [a for a in args if a not in ("--resect", "--ransac", "--focal")]
+    fraction = OUTLIER_FRACTION
+    if "--outliers" in args:
+        at = args.index("--outliers")
+        fraction = float(args[at + 1])
+        del args[at:at + 2]
+    if (p3p or exact or fraction != OUTLIER_FRACTION) and not ransac:
+        sys.exit("bench_refine_cameras: --p3p, --outliers and --exact go with --ransac")
+    if p3p and focal:
+        sys.exit("bench_refine_cameras: --p3p needs the focal length (no --focal)")
+    args = [a for a in args if a not in ("--resect", "--ransac", "--focal", "--p3p", "--exact")]
     default = "ransac_cameras_bench.json" if ransac else "resect_cameras_bench.json" if resect else "refine_cameras_bench.json"
     if focal:
         default = "ransac_focal_bench.json" if ransac else "resect_focal_bench.json"
+    if p3p:
+        default = "ransac_p3p_run.json"
     out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", default)
     reps = int(args.pop(0)) if args and args[0].isdigit() else 5
     shapes = args or ["dubrovnik-356", "venice-1778"]
@@ -226,7 +247,7 @@ def main():
         sys.exit("bench_refine_cameras: no HIP device visible (nothing is measured without one)")
     rows = []
     for name in shapes:
-        row = measure_ransac(ba, name, reps, focal) if ransac else measure_resect(ba, name, reps, focal) if resect else measure(ba, name, reps)
+        row = measure_ransac(ba, name, reps, focal, p3p, fraction, exact) if ransac else measure_resect(ba, name, reps, focal) if resect else measure(ba, name, reps)
         print(json.dumps(row), flush=True)
         rows.append(row)
     with open(out, "w") as fh:
