@@ -83,6 +83,7 @@ SYMBOLS = [
     "ba_pair_matches", "ba_relative_pose", "ba_relative_pose_five_point", "ba_five_point",
     "ba_ransac_cameras_p3p", "ba_ransac_cameras_p3p_dev", "ba_p3p",
     "ba_refine_relative_pose",
+    "ba_ransac_points", "ba_ransac_points_dev",
 ]
 
 _lib = None
@@ -175,6 +176,8 @@ def lib():
     L.ba_five_point.argtypes = [vp, i64, vp, vp, vp, vp]
     L.ba_ransac_cameras_p3p.argtypes = L.ba_ransac_cameras.argtypes
     L.ba_ransac_cameras_p3p_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
+    L.ba_ransac_points.argtypes = L.ba_ransac_cameras.argtypes
+    L.ba_ransac_points_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
     L.ba_p3p.argtypes = [vp, i64, vp, vp, vp, vp]
     L.ba_refine_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(PairRefineOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
@@ -581,7 +584,8 @@ def ransac_opts(ransac, least=6, most=16, least_set=None):
     entry (6: the resection; 8: relative_pose, where it is also the default sample).  most: the largest sample; least_set: the
     smallest min_inliers where it is not `least` (relative_pose_five_point: least = most = 5, a sample of exactly 5, and
     least_set = 8, the sets of the eight-point fits behind it; refine_cameras(minimal="p3p"): least = most = 3 and least_set = 6,
-    the sets of the linear resection behind it)."""
+    the sets of the linear resection behind it; refine_points(triangulate=True, ransac=): least = most = least_set = 2, two
+    rays are a hypothesis and the smallest set the triangulation takes)."""
     least_set = least if least_set is None else least_set
     if not isinstance(ransac, dict):
         raise ValueError(f"ransac must be a dict with the keys {', '.join(RANSAC_KEYS)} (or None), got {ransac!r}")

@@ -20,7 +20,8 @@ const char *const kProfNames[PC_COUNT] = {
     "k_schur_blocks", "k_schur_rhs", "k_ldl_diag", "k_ldl_trsm", "k_ldl_col", "k_ldl_update", "k_ldl_update_rs", "k_tri_solve",
     "k_backsub", "k_model_sq", "k_reduce", "allreduce", "k_robust_scale", "k_fix_mask",
     "k_cov_selinv", "k_cov_cams", "k_cov_points", "k_prior", "k_shared_border", "k_tri_solve_multi", "k_shared_small",
-    "k_info_whiten", "k_refine_points", "k_refine_cameras", "k_resect_cameras", "k_ransac_cameras"};
+    "k_info_whiten", "k_refine_points", "k_refine_cameras", "k_resect_cameras", "k_ransac_cameras",
+    "k_ransac_points"};
 
 extern "C" const char *ba_last_error(void) { return g_err; }
 

@@ -229,6 +229,7 @@ enum ProfClass {
   PC_REFINE_CAMERAS,  // cameras with the points held (ba_refine_cameras): k_refine_cameras
   PC_RESECT_CAMERAS,  // linear resection before it (ba_resect_cameras): k_resect_cameras
   PC_RANSAC_CAMERAS,  // consensus stage before that (ba_ransac_cameras): k_ransac_hypotheses, _select, _rescore, _mask_info
+  PC_RANSAC_POINTS,   // consensus stage before the triangulation (ba_ransac_points): k_cam_pre, k_ransac_points, k_ransac_mask_info
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -328,7 +329,7 @@ struct PriorSet {
 };
 enum { PRI_PNT = 0, PRI_CAM, PRI_CTR, PRI_KINDS };
 
-// ---- block refinement (ba_refine_points, ba_refine_cameras, ba_resect_cameras, ba_ransac_cameras) ------------------------------------------------
+// ---- block refinement (ba_refine_points, ba_refine_cameras, ba_resect_cameras, ba_ransac_cameras, ba_ransac_points) ------------------------------------------------
 // One side of x is held and every block of the other side -- a point, a camera -- is its own small Marquardt problem.  What a
 // call keeps whichever side it refines, and what the shared host code (block_* below) works on: the host entry's status /
 // cost staging and the eight device counters
@@ -341,13 +342,18 @@ struct BlockWork {
 
 // points with the cameras held (ba_point_kernels.hip): the point list split by degree once per problem (wave_pts: degree > the
 // tier threshold, one wave each; lane_pts: the others, one lane each, by descending degree) and the per-point lookup of the
-// point priors (block_prior_lookup; rebuilt when ba_lm_set_priors changed them)
+// point priors (block_prior_lookup; rebuilt when ba_lm_set_priors changed them).
+// ba_ransac_points (allocated at its first call): per observation the inlier byte and the masked copy of the information
+// factors, per point the size of its set and the winning hypothesis -- nothing per hypothesis
 struct PointWork : BlockWork {
   bool split = false;
   int64_t n_lane = 0, n_wave = 0;
   DevBuf<int> lane_pts, wave_pts;
   DevBuf<int> pri_of;
   int64_t pri_version = -1;
+  DevBuf<uint8_t> rs_inlier;
+  DevBuf<double> rs_info;
+  DevBuf<int> rs_n, rs_best;
 };
 
 // cameras with the points held (ba_camera_kernels.hip): the per-camera lookups of the camera and of the centre priors (rebuilt

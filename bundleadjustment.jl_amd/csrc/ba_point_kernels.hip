@@ -17,6 +17,9 @@
 //
 // What this file has in common with ba_camera_kernels.hip is written once: the device pieces in ba_refine_dev.h, the host side
 // (argument check, prior lookup, counter read-back, the body of the host-pointer entry; BlockWork) in ba_internal.h / ba_api.hip.
+//
+// ba_ransac_points puts a consensus stage in front: k_ransac_points, further down, finds every point's inlier set in
+// one launch, k_ransac_mask_info (ba_ransac_kernels.hip) turns the set into information and k_refine_points runs unchanged on it.
 #include <algorithm>
 #include <cmath>
 
@@ -27,6 +30,7 @@ namespace {
 
 #include "ba_model_dev.h"  // CPAD, project_pre, jac_block
 #include "ba_refine_dev.h"  // wave_all_sum, p1_z, UNDIST_ITERS
+#include "ba_consensus_dev.h"  // sample_position: the draws of k_ransac_points are those of the camera side
 
 constexpr int PT_BLK = 256;
 // Degree above which a point gets a wave.  The lanes of a wave wait for its slowest lane, whose time grows with degree x trials:
@@ -297,6 +301,325 @@ __device__ __forceinline__ void refine_point(const PtArgs &a, int i, int lane, i
   trials_out = trials;
 }
 
+// ---- the consensus stage of ba_ransac_points (include/ba_hip.h, "outlier-robust triangulation") ---------------------
+// k_ransac_points, in the grid of k_refine_points: hypotheses, selection, marking and refits of a point in ONE launch.  The
+// camera side (ba_ransac_kernels.hip) has a few thousand long lists and gives every hypothesis a wave and a slot of a table in
+// global memory; here there are a million short lists, a table would be npnts x H ints, and a hypothesis is a 3 x 3 solve on two
+// rays: the running best (count, h, X) of a list stays in registers and nothing per hypothesis is stored.
+//   lane tier   the lane runs its point's hypotheses one after the other; its set is a 32-bit mask in a register (d <= PT_TIER)
+//               and the inlier bytes are written once, at the end.
+//   wave tier   the 64 lanes take 64 hypotheses at a time: each lane triangulates its own pair, then all lanes walk the point's
+//               list in lockstep -- every lane loads the same camera row and the same measurement -- and count under their own X.
+//               One max-reduction over the key of consensus_winner (count above inverted h) picks the winner and its X comes
+//               from its lane by shuffle.  The refits are the wave-strided triangulation and a strided re-score, the set in the
+//               inlier bytes with bit 1 carrying M' between the two passes (the rule of consensus_rescore, at wave scope: every
+//               lane rewrites the bytes it wrote).
+// The sampling is that of the camera side (sample_position: the same key and draws) with the skip rule and the 64-draw limit of
+// sample_take run by one lane, since a lane owns a hypothesis here.  Integer results only cross lanes; every output has one
+// writer; no LDS.  The finish is k_refine_points itself on the masked information (k_ransac_mask_info).
+struct PtConsensus {
+  uint8_t *inlier;            // nobs
+  int *n_inliers, *best_hyp;  // npnts
+  int hypotheses, min_inliers, refits;
+  uint64_t seed_mix;  // mix(seed)
+  double tau2;
+};
+
+// What one observation adds to the sums of the linear triangulation: a copy of the loop body of point_triangulate, which stays
+// as it is (k_refine_points is the finish and keeps its code).
+__device__ __forceinline__ void ray_terms(const PtObs &ob, double A[6], double b[3]) {
+  const double kx = ob.P[0], ky = ob.P[1], kz = ob.P[2], s = ob.P[9], c = ob.P[10];
+  const double ux = ob.mx / ob.P[8], uy = ob.my / ob.P[8];
+  double qx = ux, qy = uy;
+#pragma unroll
+  for (int it = 0; it < UNDIST_ITERS; it++) {
+    const double n2 = qx * qx + qy * qy;
+    const double sc = 1.0 + ob.P[6] * n2 + ob.P[7] * (n2 * n2);
+    qx = ux / sc;
+    qy = uy / sc;
+  }
+  const double v[3] = {qx, qy, -1.0}, t[3] = {ob.P[3], ob.P[4], ob.P[5]}, kk[3] = {kx, ky, kz};
+  const double kv = kx * v[0] + ky * v[1] + kz * v[2], kt = kx * t[0] + ky * t[1] + kz * t[2];
+  const double xv[3] = {ky * v[2] - kz * v[1], kz * v[0] - kx * v[2], kx * v[1] - ky * v[0]};
+  const double xt[3] = {ky * t[2] - kz * t[1], kz * t[0] - kx * t[2], kx * t[1] - ky * t[0]};
+  double d[3], cc[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    d[i] = c * v[i] - s * xv[i] + (1 - c) * kv * kk[i];
+    cc[i] = -(c * t[i] - s * xt[i] + (1 - c) * kt * kk[i]);
+  }
+  const double inv = 1.0 / sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+#pragma unroll
+  for (int i = 0; i < 3; i++) d[i] *= inv;
+  const double dc = d[0] * cc[0] + d[1] * cc[1] + d[2] * cc[2];
+  A[0] = 1.0 - d[0] * d[0];
+  A[1] = -d[1] * d[0];
+  A[2] = 1.0 - d[1] * d[1];
+  A[3] = -d[2] * d[0];
+  A[4] = -d[2] * d[1];
+  A[5] = 1.0 - d[2] * d[2];
+#pragma unroll
+  for (int i = 0; i < 3; i++) b[i] = cc[i] - d[i] * dc;
+}
+
+// the linear triangulation on the entries of [k0, k1) that are used and that pick(k) keeps: the sums and the solve of
+// point_triangulate
+template <bool WAVE, typename Pick>
+__device__ __forceinline__ bool triangulate_picked(const PtArgs &a, int k0, int k1, int lane, Pick pick, double X[3]) {
+  double A[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0}, n = 0.0;
+  for (int k = k0 + (WAVE ? lane : 0); k < k1; k += (WAVE ? 64 : 1)) {
+    PtObs ob;
+    load_obs(a, k, ob);
+    if (!ob.used || !pick(k)) continue;
+    double At[6], bt[3];
+    ray_terms(ob, At, bt);
+#pragma unroll
+    for (int i = 0; i < 6; i++) A[i] += At[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) b[i] += bt[i];
+    n += 1.0;
+  }
+  if (WAVE) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) A[i] = wave_all_sum(A[i]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) b[i] = wave_all_sum(b[i]);
+    n = wave_all_sum(n);
+  }
+  if (n < 2.0) return false;
+  return chol3_solve(A, b, 1e-12 * (A[0] + A[2] + A[5]), X);
+}
+
+// the inlier test of the header under the point X: used, in front (P1.z < 0), within tau of its measurement in raw pixels (a
+// comparison with NaN fails)
+__device__ __forceinline__ bool point_inlier(const PtObs &ob, const double X[3], double tau2) {
+  double out[2], z1;
+  project_pre<double>(X, ob.P, out);
+  p1_z(ob.P, X, z1);
+  const double ex = out[0] - ob.mx, ey = out[1] - ob.my;
+  return ob.used && z1 < 0.0 && ex * ex + ey * ey <= tau2;
+}
+
+// the pair (pa < pb) of rank h < d (d - 1) / 2 in the order (0,1), (0,2), ..., (0,d-1), (1,2), ...: row pa starts at rank
+// pa (2 d - pa - 1) / 2; the square root gives the row within one, the two loops settle it
+__device__ __forceinline__ void pair_unrank(int h, int d, int &pa, int &pb) {
+  const double s = 2.0 * d - 1.0;
+  int r = (int)((s - sqrt(fmax(s * s - 8.0 * h, 0.0))) * 0.5);
+  r = r < 0 ? 0 : (r > d - 2 ? d - 2 : r);
+  while (r < d - 2 && (r + 1) * (2 * d - r - 2) / 2 <= h) r++;
+  while (r > 0 && r * (2 * d - r - 1) / 2 > h) r--;
+  pa = r;
+  pb = r + 1 + (h - r * (2 * d - r - 1) / 2);
+}
+
+// The sample of hypothesis h in a list of d entries, m = 2, by one lane: draw j = 0, 1, ... of sample_position; a draw is skipped
+// when its entry is not used or an earlier draw hit its position; the first two that count are the sample; fewer after RN_DRAWS
+// draws: void.
+__device__ __forceinline__ bool sample_pair(const PtArgs &a, uint64_t seed_mix, int h, int k0, int d, int &pa, int &pb) {
+  int n = 0;
+  pa = pb = -1;
+  for (int j = 0; j < RN_DRAWS && n < 2; j++) {
+    const int pos = sample_position(seed_mix, h, j, d);
+    if (pos == pa || !obs_used(a.info, a.pt_obs[k0 + pos])) continue;
+    if (n == 0) pa = pos;
+    else pb = pos;
+    n++;
+  }
+  return n == 2;
+}
+
+// Hypothesis h of the list [k0, k0 + d): its two list positions (exhaustive: the pair of rank h; otherwise the sample) and the
+// linear triangulation on them; false: void.  next: the exhaustive enumeration advances (pa, pb) from the pair of rank h - 1
+// instead of unranking (the lane tier walks h in order).
+template <bool NEXT>
+__device__ __forceinline__ bool hypothesis_point(const PtArgs &a, const PtConsensus &c, bool exhaustive, int h, int k0, int d, int &pa,
+                                                 int &pb, double X[3]) {
+  if (exhaustive) {
+    if (NEXT) {
+      if (++pb >= d) pa++, pb = pa + 1;
+    } else {
+      pair_unrank(h, d, pa, pb);
+    }
+  } else if (!sample_pair(a, c.seed_mix, h, k0, d, pa, pb)) {
+    return false;
+  }
+  PtObs oa, ob;
+  load_obs(a, k0 + pa, oa);
+  load_obs(a, k0 + pb, ob);
+  if (!oa.used || !ob.used) return false;
+  double A[6], b[3], At[6], bt[3];
+  ray_terms(oa, A, b);
+  ray_terms(ob, At, bt);
+#pragma unroll
+  for (int i = 0; i < 6; i++) A[i] += At[i];
+#pragma unroll
+  for (int i = 0; i < 3; i++) b[i] += bt[i];
+  return chol3_solve(A, b, 1e-12 * (A[0] + A[2] + A[5]), X);
+}
+
+// a point that is not attempted: its set is its used observations
+template <bool WAVE>
+__device__ __forceinline__ void consensus_skip(const PtArgs &a, const PtConsensus &c, int i, int k0, int k1, int lane) {
+  int n = 0;
+  for (int k = k0 + (WAVE ? lane : 0); k < k1; k += (WAVE ? 64 : 1)) {
+    const int o = a.pt_obs[k];
+    const int u = obs_used(a.info, o) ? 1 : 0;
+    c.inlier[o] = (uint8_t)u;
+    n += u;
+  }
+  if (WAVE) n = wave_all_sum_int(n);
+  if (!WAVE || lane == 0) c.n_inliers[i] = n, c.best_hyp[i] = -1;
+}
+
+// lane tier: one point per lane, d <= PT_TIER
+__device__ __forceinline__ void consensus_point_lane(const PtArgs &a, const PtConsensus &c, int i) {
+  static_assert(PT_TIER <= 32, "the set of a lane-tier point is a 32-bit mask");
+  const int k0 = a.pt_ptr[i], k1 = a.pt_ptr[i + 1], d = k1 - k0;
+  if (a.fixed != nullptr && a.fixed[i] != 0) {
+    consensus_skip<false>(a, c, i, k0, k1, 0);
+    return;
+  }
+  const int npairs = d * (d - 1) / 2;
+  const bool exhaustive = npairs <= c.hypotheses;
+  const int nh = exhaustive ? npairs : c.hypotheses;
+  int best = -1, best_count = -1, pa = 0, pb = 0;
+  double Xb[3] = {0, 0, 0};
+  for (int h = 0; h < nh; h++) {
+    double X[3];
+    if (!hypothesis_point<true>(a, c, exhaustive, h, k0, d, pa, pb, X)) continue;
+    int cnt = 0;
+    for (int k = k0; k < k1; k++) {
+      PtObs ob;
+      load_obs(a, k, ob);
+      cnt += point_inlier(ob, X, c.tau2) ? 1 : 0;
+    }
+    if (cnt > best_count) {  // (h ascends: a tie stays with the lower h)
+      best = h, best_count = cnt;
+      Xb[0] = X[0], Xb[1] = X[1], Xb[2] = X[2];
+    }
+  }
+  unsigned M = 0;
+  int n = best_count < 0 ? 0 : best_count;
+  if (best >= 0 && best_count >= c.min_inliers) {
+    for (int k = k0; k < k1; k++) {
+      PtObs ob;
+      load_obs(a, k, ob);
+      if (point_inlier(ob, Xb, c.tau2)) M |= 1u << (k - k0);
+    }
+    for (int r = 0; r < c.refits; r++) {
+      double Xn[3];
+      if (!triangulate_picked<false>(a, k0, k1, 0, [&](int k) { return ((M >> (k - k0)) & 1u) != 0; }, Xn)) break;
+      unsigned M2 = 0;
+      for (int k = k0; k < k1; k++) {
+        PtObs ob;
+        load_obs(a, k, ob);
+        if (point_inlier(ob, Xn, c.tau2)) M2 |= 1u << (k - k0);
+      }
+      const int n2 = __popc(M2);
+      if (n2 < n || M2 == M) break;
+      M = M2, n = n2;
+    }
+  }
+  for (int k = k0; k < k1; k++) c.inlier[a.pt_obs[k]] = (uint8_t)((M >> (k - k0)) & 1u);
+  c.n_inliers[i] = n, c.best_hyp[i] = best;
+}
+
+// wave tier: one point per wave (the control flow is wave-uniform)
+__device__ __forceinline__ void consensus_point_wave(const PtArgs &a, const PtConsensus &c, int i, int lane) {
+  static_assert(RN_HYP_MAX == 1 << 12, "the selection key holds h in 12 bits");
+  const int k0 = a.pt_ptr[i], k1 = a.pt_ptr[i + 1], d = k1 - k0;
+  if (a.fixed != nullptr && a.fixed[i] != 0) {
+    consensus_skip<true>(a, c, i, k0, k1, lane);
+    return;
+  }
+  const long long npairs = (long long)d * (d - 1) / 2;
+  const bool exhaustive = npairs <= (long long)c.hypotheses;
+  const int nh = exhaustive ? (int)npairs : c.hypotheses;
+  long long key = 0;  // this lane's best: count + 1 above the inverted h (consensus_winner), 0: none
+  double Xb[3] = {0, 0, 0};
+  for (int base = 0; base < nh; base += 64) {
+    const int h = base + lane;
+    int pa = 0, pb = 0;
+    double X[3] = {0, 0, 0};
+    const bool ok = h < nh && hypothesis_point<false>(a, c, exhaustive, h, k0, d, pa, pb, X);
+    if (!__any(ok)) continue;
+    int cnt = 0;
+    for (int k = k0; k < k1; k++) {  // (the same entry in every lane)
+      PtObs ob;
+      load_obs(a, k, ob);
+      cnt += point_inlier(ob, X, c.tau2) ? 1 : 0;
+    }
+    const long long kk = ((long long)(cnt + 1) << 12) | (long long)(4095 - h);
+    if (ok && kk > key) {
+      key = kk;
+      Xb[0] = X[0], Xb[1] = X[1], Xb[2] = X[2];
+    }
+  }
+  long long top = key;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long other = __shfl_xor(top, off, 64);
+    top = other > top ? other : top;
+  }
+  const int best = top ? 4095 - (int)(top & 4095) : -1, best_count = top ? (int)(top >> 12) - 1 : 0;
+  if (best < 0 || best_count < c.min_inliers) {
+    for (int k = k0 + lane; k < k1; k += 64) c.inlier[a.pt_obs[k]] = 0;
+    if (lane == 0) c.n_inliers[i] = best_count, c.best_hyp[i] = best;
+    return;
+  }
+  const int src = __ffsll((long long)__ballot(key == top)) - 1;  // (the keys of two lanes differ in h: one lane)
+  double Xw[3] = {__shfl(Xb[0], src, 64), __shfl(Xb[1], src, 64), __shfl(Xb[2], src, 64)};
+  int n = 0;
+  for (int k = k0 + lane; k < k1; k += 64) {
+    PtObs ob;
+    load_obs(a, k, ob);
+    const int in = point_inlier(ob, Xw, c.tau2) ? 1 : 0;
+    c.inlier[a.pt_obs[k]] = (uint8_t)in;
+    n += in;
+  }
+  n = wave_all_sum_int(n);
+  for (int r = 0; r < c.refits; r++) {
+    double Xn[3];
+    if (!triangulate_picked<true>(a, k0, k1, lane, [&](int k) { return (c.inlier[a.pt_obs[k]] & 1) != 0; }, Xn)) break;
+    int n2 = 0, diff = 0;
+    for (int k = k0 + lane; k < k1; k += 64) {
+      PtObs ob;
+      load_obs(a, k, ob);
+      const int o = a.pt_obs[k];
+      const int in = point_inlier(ob, Xn, c.tau2) ? 1 : 0, old = c.inlier[o] & 1;
+      c.inlier[o] = (uint8_t)(old | (in << 1));
+      n2 += in;
+      diff += in != old ? 1 : 0;
+    }
+    n2 = wave_all_sum_int(n2);
+    diff = wave_all_sum_int(diff);
+    const bool adopt = n2 >= n && diff > 0;
+    for (int k = k0 + lane; k < k1; k += 64) {
+      const int o = a.pt_obs[k];
+      const int b = c.inlier[o];
+      c.inlier[o] = (uint8_t)(adopt ? (b >> 1) & 1 : b & 1);
+    }
+    if (!adopt) break;
+    n = n2;
+  }
+  if (lane == 0) c.n_inliers[i] = n, c.best_hyp[i] = best;
+}
+
+// the grid of k_refine_points: the wave tier's workgroups first
+__global__ __launch_bounds__(PT_BLK) void k_ransac_points(PtArgs a, PtConsensus c) {
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int nb_wave = (a.n_wave + PT_BLK / 64 - 1) / (PT_BLK / 64);
+  if ((int)blockIdx.x < nb_wave) {
+    const int idx = (int)blockIdx.x * (PT_BLK / 64) + wv;  // (wave-uniform)
+    if (idx < a.n_wave) consensus_point_wave(a, c, a.wave_pts[idx], lane);
+  } else {
+    const int64_t idx = (int64_t)((int)blockIdx.x - nb_wave) * PT_BLK + t;
+    if (idx < a.n_lane) consensus_point_lane(a, c, a.lane_pts[idx]);
+  }
+}
+
+// (k_ransac_points stands in front of k_refine_points in this file so that the latter stays the last symbol of the code object,
+// as it was: tools/compare_code_objects.py then shows it unchanged line for line.)
 // Workgroups [0, ceil(n_wave / 4)): one point of wave_pts per wave (they run longest and start first); the others: one point of
 // lane_pts per lane.
 __global__ __launch_bounds__(PT_BLK) void k_refine_points(PtArgs a) {
@@ -374,21 +697,25 @@ static int refine_check(const char *who, ba_problem *p, const double *x, int ini
   });
 }
 
-// k_cam_pre and k_refine_points on st; the counters stay on the device (p->pts.counts)
-static int refine_launch(ba_problem *p, double *d_x, int init, int max_iter, double xtol, double lambda0, uint8_t *d_status,
-                         double *d_cost, hipStream_t st) {
+// (ransac: k_ransac_points and k_ransac_mask_info, which leave the set as information, then) k_refine_points on st, behind
+// k_cam_pre; the counters stay on the device (p->pts.counts)
+static int refine_launch(ba_problem *p, double *d_x, int init, const ba_ransac_opts *ransac, int max_iter, double xtol, double lambda0,
+                         uint8_t *d_status, double *d_cost, hipStream_t st) {
   BA_CHECK(terms_upload(p));
   BA_CHECK(point_tables(p));
   PointWork &w = p->pts;
   BA_HIP_CHECK(hipMemsetAsync(w.counts, 0, BLOCK_COUNTERS * sizeof(unsigned long long), st));
   if (p->npnts == 0) return BA_OK;
-  ProfScope ps(p, PC_REFINE_POINTS, st);
-  const double *cpre = nullptr;
-  BA_CHECK(launch_cam_pre_f64(p, d_x, &cpre, st));
+  if (ransac && !w.rs_inlier) {
+    BA_CHECK(w.rs_inlier.alloc(p->nobs));
+    BA_CHECK(w.rs_info.alloc(3 * p->nobs));
+    BA_CHECK(w.rs_n.alloc(p->npnts));
+    BA_CHECK(w.rs_best.alloc(p->npnts));
+  }
   const PriorSet &pt = p->pri[PRI_PNT];
   PtArgs a;
   a.pt_ptr = p->pt_ptr, a.pt_obs = p->pt_obs, a.cam0 = p->cam0;
-  a.pt2d = p->pt2d, a.cpre = cpre, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
+  a.pt2d = p->pt2d, a.cpre = nullptr, a.info = p->info_on() ? (const double *)p->d_info : nullptr;
   a.fixed = p->fix_npnt > 0 ? (const uint8_t *)p->d_fix_pnt : nullptr;
   a.pri_of = pt.n > 0 ? (const int *)w.pri_of : nullptr;
   a.pri_mu = pt.n > 0 ? (const double *)pt.mu : nullptr, a.pri_info = pt.n > 0 ? (const double *)pt.info : nullptr;
@@ -397,7 +724,25 @@ static int refine_launch(ba_problem *p, double *d_x, int init, int max_iter, dou
   a.x = d_x, a.status = d_status, a.cost = d_cost, a.counts = w.counts;
   a.init = init, a.max_iter = max_iter, a.kind = p->loss;
   a.xtol = xtol, a.lambda0 = lambda0, a.c2 = p->loss_scale * p->loss_scale;
-  return BA_LAUNCH(k_refine_points, grid_for(w.n_wave, PT_BLK / 64) + grid_for(w.n_lane, PT_BLK), PT_BLK, 0, st, a);
+  const unsigned grid = grid_for(w.n_wave, PT_BLK / 64) + grid_for(w.n_lane, PT_BLK);
+  if (ransac) {
+    // the consensus stage: the set reaches k_refine_points as information -- w.rs_info, the masked copy of the factors (1 0 1
+    // when the caller set none: the values the kernel uses without an array)
+    ProfScope ps(p, PC_RANSAC_POINTS, st);
+    BA_CHECK(launch_cam_pre_f64(p, d_x, &a.cpre, st));
+    PtConsensus c;
+    c.inlier = w.rs_inlier, c.n_inliers = w.rs_n, c.best_hyp = w.rs_best;
+    c.hypotheses = ransac->hypotheses, c.min_inliers = ransac->min_inliers, c.refits = ransac->refits;
+    c.seed_mix = ransac_seed_mix(ransac->seed), c.tau2 = ransac->threshold * ransac->threshold;
+    BA_CHECK(BA_LAUNCH(k_ransac_points, grid, PT_BLK, 0, st, a, c));
+    RansacArgs r = {};
+    r.inlier = w.rs_inlier, r.info = a.info;
+    BA_CHECK(launch_ransac_mask_info(r, p->nobs, w.rs_info, st));
+    a.info = w.rs_info;
+  }
+  ProfScope ps(p, PC_REFINE_POINTS, st);
+  if (!ransac) BA_CHECK(launch_cam_pre_f64(p, d_x, &a.cpre, st));  // (behind the consensus stage the rows are there)
+  return BA_LAUNCH(k_refine_points, grid, PT_BLK, 0, st, a);
 }
 
 extern "C" int ba_refine_points_dev(ba_problem *p, double *d_x_inout, int init, int max_iter, double xtol, double lambda0,
@@ -405,7 +750,7 @@ extern "C" int ba_refine_points_dev(ba_problem *p, double *d_x_inout, int init, 
   BA_CHECK(refine_check("ba_refine_points_dev", p, d_x_inout, init, &max_iter, &xtol, &lambda0));
   BA_HIP_CHECK(hipSetDevice(p->device));
   hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
-  BA_CHECK(refine_launch(p, d_x_inout, init, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(refine_launch(p, d_x_inout, init, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st));
   return block_counts(p->pts, counts, iters_max, st);
 }
 
@@ -415,6 +760,48 @@ extern "C" int ba_refine_points(ba_problem *p, double *x_inout, int init, int ma
   // the points only: the camera part of the caller's x is never written
   return block_host_entry(p, p->pts, x_inout, p->npnts, 3, 0, status, cost, counts, iters_max,
                           [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
-                            return refine_launch(p, dx, init, max_iter, xtol, lambda0, d_status, d_cost, st);
+                            return refine_launch(p, dx, init, nullptr, max_iter, xtol, lambda0, d_status, d_cost, st);
+                          });
+}
+
+// ---- ba_ransac_points: a consensus stage in front of ba_refine_points(init = 1) ------------------------------------
+// the consensus results of the last call -> the caller's arrays (each may be null), on st
+static int ransac_results(ba_problem *p, uint8_t *inlier, int32_t *n_inliers, int32_t *best_hyp, hipMemcpyKind kind, hipStream_t st) {
+  const PointWork &w = p->pts;
+  if (p->npnts == 0) return BA_OK;
+  if (inlier && p->nobs > 0) BA_HIP_CHECK(hipMemcpyAsync(inlier, w.rs_inlier, (size_t)p->nobs, kind, st));
+  if (n_inliers) BA_HIP_CHECK(hipMemcpyAsync(n_inliers, w.rs_n, (size_t)p->npnts * sizeof(int32_t), kind, st));
+  if (best_hyp) BA_HIP_CHECK(hipMemcpyAsync(best_hyp, w.rs_best, (size_t)p->npnts * sizeof(int32_t), kind, st));
+  return BA_OK;
+}
+
+// the options (a sample of exactly two observations, a set of at least two), then the refusals of ba_refine_points
+static int ransac_check(const char *who, ba_problem *p, const double *x, const ba_ransac_opts *opts, ba_ransac_opts *o, int *max_iter,
+                        double *xtol, double *lambda0) {
+  BA_CHECK(ransac_opts_check(who, opts, o, 2, 2, 2));
+  return refine_check(who, p, x, 1, max_iter, xtol, lambda0);
+}
+
+extern "C" int ba_ransac_points_dev(ba_problem *p, double *d_x_inout, const ba_ransac_opts *opts, int max_iter, double xtol,
+                                    double lambda0, uint8_t *d_status, double *d_cost, int64_t *counts, int *iters_max,
+                                    uint8_t *d_inlier, int32_t *d_n_inliers, int32_t *d_best_hyp, void *stream) {
+  ba_ransac_opts o;
+  BA_CHECK(ransac_check("ba_ransac_points_dev", p, d_x_inout, opts, &o, &max_iter, &xtol, &lambda0));
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)p->stream;
+  BA_CHECK(refine_launch(p, d_x_inout, 1, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+  BA_CHECK(ransac_results(p, d_inlier, d_n_inliers, d_best_hyp, hipMemcpyDeviceToDevice, st));
+  return block_counts(p->pts, counts, iters_max, st);
+}
+
+extern "C" int ba_ransac_points(ba_problem *p, double *x_inout, const ba_ransac_opts *opts, int max_iter, double xtol, double lambda0,
+                                uint8_t *status, double *cost, int64_t *counts, int *iters_max, uint8_t *inlier, int32_t *n_inliers,
+                                int32_t *best_hyp) {
+  ba_ransac_opts o;
+  BA_CHECK(ransac_check("ba_ransac_points", p, x_inout, opts, &o, &max_iter, &xtol, &lambda0));
+  return block_host_entry(p, p->pts, x_inout, p->npnts, 3, 0, status, cost, counts, iters_max,
+                          [&](double *dx, uint8_t *d_status, double *d_cost, hipStream_t st) {
+                            BA_CHECK(refine_launch(p, dx, 1, &o, max_iter, xtol, lambda0, d_status, d_cost, st));
+                            return ransac_results(p, inlier, n_inliers, best_hyp, hipMemcpyDeviceToHost, st);
                           });
 }

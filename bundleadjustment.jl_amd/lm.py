@@ -281,13 +281,21 @@ def _block_info(status, cost, counts, its):
 
 
 def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0, obs_info=None,
-                  fixed_points=None, point_priors=None):
+                  fixed_points=None, point_priors=None, ransac=None):
     """The points of x with its cameras held (ba_refine_points): every point is an independent problem in 3 unknowns -- the
     objective of Levenberg_Marquardt under `loss` / `f_scale`, `obs_info` and `point_priors`, restricted to that point -- solved
     by a Marquardt iteration of its own (accept test, damping and stopping test per point).  triangulate=True starts every
     point from the linear triangulation of its rays instead of from x (the points of x are then not read): how an x0 is built
     when only cameras are known.  max_iter (None: 50; 0: evaluate only -- with triangulate=True the triangulated points are
     returned), xtol (None: 1e-10; |delta| <= xtol (|X| + xtol)), lam0 (None: 1e-4).  fixed_points are skipped.
+    ransac=dict(threshold=, hypotheses=, refits=, min_inliers=, seed=) with triangulate=True puts a consensus stage in front
+    (ba_ransac_points; _lib.ransac_opts for the ranges, `sample` 2 or unset): every pair of a point's observations -- `hypotheses`
+    random pairs where the point has more pairs than that -- is triangulated and scored by its inliers (reprojection within
+    `threshold` pixels, in front of the camera), the best pair defines the point's inlier set, up to `refits` triangulations on
+    the set re-score it, and the triangulation and the refinement run on that set only -- the result has the bits of
+    triangulate=True with an obs_info that drops the outliers.  A point whose best pair has fewer than `min_inliers` (None: 2)
+    inliers is `degenerate`.  info then also holds `inliers` (bool, nobs), `n_inliers` and `best_hypothesis` (per point; -1: not
+    attempted or no valid pair).
     Returns (x_new, info): x_new a copy of x with the points replaced (cameras and skipped points bit-identical); info a dict
     with `status` (npnts names among _lib.POINT_STATES), `behind` (bool: at the returned point an observation sees it from
     behind, P1.z >= 0), `cost_before`, `cost_after` (per point, cost_after <= cost_before), `counts` (points per status name,
@@ -296,10 +304,20 @@ def refine_points(nlp, x, *, triangulate=False, max_iter=None, xtol=None, lam0=N
                               obs_info=obs_info)
     if not isinstance(triangulate, (bool, np.bool_)):
         raise ValueError(f"triangulate must be True or False, got {triangulate!r}")
+    opts = None
+    if ransac is not None:
+        if not triangulate:
+            raise ValueError("ransac needs triangulate=True (the consensus stage stands in front of the linear triangulation)")
+        opts = _lib.ransac_opts(ransac, least=2, most=2, least_set=2)
     x, args = _block_args(nlp, x, max_iter, xtol, lam0)
     terms.apply(nlp, shared=False)  # (a grouping concerns the cameras: what the handle holds stays)
     status, cost = np.zeros(nlp.npnts, dtype=np.uint8), np.zeros((nlp.npnts, 2))
     counts, its = np.zeros(len(_lib.POINT_STATES) + 1, dtype=np.int64), C.c_int(0)
+    if opts is not None:
+        inlier, n_in, best = np.zeros(nlp.nobs, dtype=np.uint8), np.zeros(nlp.npnts, dtype=np.int32), np.zeros(nlp.npnts, dtype=np.int32)
+        _lib.check(_lib.lib().ba_ransac_points(nlp.handle, _lib.ptr(x), C.byref(opts), *args, _lib.ptr(status), _lib.ptr(cost),
+                                               _lib.ptr(counts), C.byref(its), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best)))
+        return x, dict(_block_info(status, cost, counts, its), inliers=inlier != 0, n_inliers=n_in, best_hypothesis=best)
     _lib.check(_lib.lib().ba_refine_points(nlp.handle, _lib.ptr(x), int(bool(triangulate)), *args, _lib.ptr(status), _lib.ptr(cost),
                                            _lib.ptr(counts), C.byref(its)))
     return x, _block_info(status, cost, counts, its)

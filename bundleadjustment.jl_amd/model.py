@@ -206,13 +206,13 @@ class BALNLPModel:
         _lib.check(_lib.lib().ba_profile_reset(self._h))
 
     def profile_get(self):
-        cap = 32
+        cap = 64  # (at least the library's number of kernel classes: ba_profile_get fills no more than cap)
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         calls = (C.c_int64 * cap)()
         n = C.c_int(0)
         _lib.check(_lib.lib().ba_profile_get(self._h, cap, names, ms, calls, C.byref(n)))
-        return {names[i].decode(): (ms[i], calls[i]) for i in range(n.value)}
+        return {names[i].decode(): (ms[i], calls[i]) for i in range(min(n.value, cap))}
 
 
 class FeasibilityResidual:

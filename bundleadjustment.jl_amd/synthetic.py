@@ -165,31 +165,28 @@ def make_problem(ncams, npnts, nobs, seed=BASE_SEED, locality=None, plane_radius
                 ncams=int(ncams), npnts=int(npnts), nobs=int(nobs))
 
 
-def add_outliers(prob, n_per_camera=None, fraction=None, seed=0, r_min=100.0, r_max=500.0):
-    """Wrong matches for the consensus tests and benchmarks: (pt2d, is_outlier) -- a copy of prob's pt2d (nobs, 2) in which the
-    chosen detections are displaced by r_min..r_max pixels in a random direction, and the boolean mask of the chosen ones.
-    Give one of n_per_camera (an integer, or one per camera: that many detections of each camera, drawn without replacement
-    from its list) and fraction (that share of each camera's list, rounded down)."""
-    if (n_per_camera is None) == (fraction is None):
-        raise ValueError("add_outliers: give one of n_per_camera and fraction")
+def _displace_per_group(who, per, group0, ngroups, prob, n_per_group, fraction, seed, r_min, r_max):
+    """add_outliers and add_point_outliers: the observations grouped by group0 (0-based camera or point of every observation),
+    the chosen ones of every group drawn without replacement from its list, then displaced -- one generator, the groups in
+    ascending order, then all radii, then all angles"""
+    if (n_per_group is None) == (fraction is None):
+        raise ValueError(f"{who}: give one of n_per_{per} and fraction")
     if not (0 <= r_min <= r_max and np.isfinite(r_max)):
-        raise ValueError(f"add_outliers: 0 <= r_min <= r_max < inf, got {r_min!r}, {r_max!r}")
-    ncams = int(prob["ncams"])
-    cam0 = np.asarray(prob["cam_idx1"]) - 1
-    deg = np.bincount(cam0, minlength=ncams)
+        raise ValueError(f"{who}: 0 <= r_min <= r_max < inf, got {r_min!r}, {r_max!r}")
+    deg = np.bincount(group0, minlength=ngroups)
     if fraction is not None:
         if not 0 <= fraction <= 1:
-            raise ValueError(f"add_outliers: fraction must lie in 0..1, got {fraction!r}")
+            raise ValueError(f"{who}: fraction must lie in 0..1, got {fraction!r}")
         count = np.floor(fraction * deg).astype(np.int64)
     else:
-        count = np.broadcast_to(np.asarray(n_per_camera, dtype=np.int64), (ncams,))
+        count = np.broadcast_to(np.asarray(n_per_group, dtype=np.int64), (ngroups,))
         if (count < 0).any() or (count > deg).any():
-            raise ValueError("add_outliers: n_per_camera must lie between 0 and the camera's degree")
+            raise ValueError(f"{who}: n_per_{per} must lie between 0 and the {per}'s degree")
     rng = np.random.default_rng(seed)
-    order = np.argsort(cam0, kind="stable")
+    order = np.argsort(group0, kind="stable")
     start = np.concatenate([[0], np.cumsum(deg)])
-    is_outlier = np.zeros(len(cam0), dtype=bool)
-    for c in range(ncams):
+    is_outlier = np.zeros(len(group0), dtype=bool)
+    for c in range(ngroups):
         if count[c] > 0:
             is_outlier[order[start[c]:start[c + 1]][rng.choice(deg[c], size=int(count[c]), replace=False)]] = True
     pt2d = np.array(prob["pt2d"], dtype=np.float64, copy=True).reshape(-1, 2)
@@ -197,6 +194,23 @@ def add_outliers(prob, n_per_camera=None, fraction=None, seed=0, r_min=100.0, r_
     rad, ang = rng.uniform(r_min, r_max, k), rng.uniform(0.0, 2.0 * np.pi, k)
     pt2d[is_outlier] += np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=1)
     return pt2d, is_outlier
+
+
+def add_outliers(prob, n_per_camera=None, fraction=None, seed=0, r_min=100.0, r_max=500.0):
+    """Wrong matches for the consensus tests and benchmarks: (pt2d, is_outlier) -- a copy of prob's pt2d (nobs, 2) in which the
+    chosen detections are displaced by r_min..r_max pixels in a random direction, and the boolean mask of the chosen ones.
+    Give one of n_per_camera (an integer, or one per camera: that many detections of each camera, drawn without replacement
+    from its list) and fraction (that share of each camera's list, rounded down)."""
+    return _displace_per_group("add_outliers", "camera", np.asarray(prob["cam_idx1"]) - 1, int(prob["ncams"]), prob, n_per_camera,
+                               fraction, seed, r_min, r_max)
+
+
+def add_point_outliers(prob, n_per_point=None, fraction=None, seed=0, r_min=100.0, r_max=500.0):
+    """The per-track twin of add_outliers, for the consensus stage of refine_points(triangulate=True, ransac=...): (pt2d,
+    is_outlier) with n_per_point detections of every point's track (an integer, or one per point), or the share `fraction` of
+    it rounded down, displaced by r_min..r_max pixels in a random direction."""
+    return _displace_per_group("add_point_outliers", "point", np.asarray(prob["pnt_idx1"]) - 1, int(prob["npnts"]), prob, n_per_point,
+                               fraction, seed, r_min, r_max)
 
 
 def shuffle_cameras(prob, seed=0, sigma=None):

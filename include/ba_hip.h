@@ -914,6 +914,59 @@ int ba_ransac_cameras_p3p_dev(ba_problem *p, double *d_x_inout /* nvar, device *
 int ba_p3p(ba_problem *p, int64_t n, const double *q /* n x 3 x 2 */, const double *X /* n x 3 x 3 */,
            double *pose /* n x 4 x 6 */, int32_t *n_sol /* n */);
 
+/* ---- outlier-robust triangulation: RANSAC before the linear point (an extension) -----------------------------------
+ * ba_refine_points with init = 1 and a consensus stage in front.  The linear triangulation sums (I - dd') over every used
+ * observation of a point, unweighted: one wrong match in a track moves the point arbitrarily, the robust loss of the refinement
+ * then starts from that point, and a camera registered next by ba_ransac_cameras is scored against it.  Here every point's
+ * two-view hypotheses are triangulated and scored on the device, the best one defines the point's inlier set, and the
+ * triangulation and the Marquardt refinement run on that set only.  The inlier mask comes back to the caller.
+ * Options (ba_ransac_opts): threshold tau in pixels, finite and > 0; hypotheses H (<= 0: 128; at most 4096); sample (<= 0: 2;
+ * anything else but 2 is refused); refits (< 0: 2; at most 8); min_inliers (<= 0: 2; at least 2 -- a caller who wants a third
+ * view to confirm a point asks for 3); seed.  Anything else is BA_ERR_ARG, as are NULL options.  The other refusals are those of
+ * ba_refine_points; as there, no communicator is needed and a shard works on its own points.
+ * Which points: a point fixed by ba_lm_set_fixed is BA_PT_FIXED and not attempted: inlier = its used observations, n_inliers =
+ * their number, best_hyp = -1.  Every other point is attempted; its entries in x are never read (NaN is fine).  "Used" means
+ * Lambda != 0 under ba_lm_set_obs_info; the information plays no other part in the consensus stage, and point priors play none:
+ * they act in the finish.
+ * Hypotheses of a point: its list is its observations in the caller's order, its degree d counts the unused entries too, and
+ * n = d (d - 1) / 2.
+ *   n <= H: the enumeration is exhaustive.  Hypothesis h < n is the pair (a, b) of list positions, a < b, of rank h in the order
+ *   (0,1), (0,2), ..., (0,d-1), (1,2), ...; a hypothesis with h >= n is void, a pair with an unused member is void; the seed is
+ *   not read.
+ *   n > H: the sampling of ba_ransac_cameras with m = 2 on the point's list -- the same key, the same draws, the same skip rule
+ *   and the same limit of 64 draws.  The point index does not enter.
+ *   The point of a hypothesis is the linear triangulation of ba_refine_points, step for step, on those two observations.  A
+ *   pivot <= 1e-12 trace or a result that is not finite makes the hypothesis void.
+ * Inlier test: under a point X, observation o is an inlier iff it is used, P1.z < 0 under its camera of x, and
+ * |project - pt2d|^2 <= tau^2 in raw pixels with the model's own projection.  A comparison with NaN fails.
+ * Selection: the score of a hypothesis is its inlier count over the point's whole list; the best is the largest count, ties to
+ * the lowest h.  Without a valid hypothesis, or with a best count < min_inliers, the point fails: its inlier bytes are 0,
+ * n_inliers = the best count (0 if none), best_hyp = that h or -1, state BA_PT_DEGENERATE, bit-unchanged, cost entries 0, no flag.
+ * Refits, up to `refits` times: the linear triangulation on the current set M; the whole list re-scored under that point gives
+ * M'; M' is adopted iff |M'| >= |M| and M' != M; otherwise (smaller, equal, or the refit was degenerate) M stays and the point
+ * stops.
+ * Finish: ba_refine_points(init = 1) with the observations outside the final set treated exactly as Lambda = 0 -- the linear
+ * triangulation on the set, then the Marquardt refinement on the set under the handle's loss, information and point priors; an
+ * outlier raises no BEHIND flag; max_iter == 0 returns the linear triangulation on the set; states, costs, counts and iters_max
+ * as in that entry.  x, status and cost equal, bit for bit, those of ba_refine_points(init = 1) on the same handle whose
+ * information is the caller's with the outliers' entries set to 0 (the identity on the inliers when the caller set none).
+ * Outputs beyond those of ba_refine_points, each may be NULL: inlier (nobs bytes 0 / 1, caller's observation order), n_inliers
+ * (npnts: the size of the final set) and best_hyp (npnts).  In the _dev form they are device pointers and the call is enqueued
+ * on `stream`; it synchronises only to hand over counts / iters_max, as its sibling does.
+ * Two calls give the same bits (no floating-point atomics); the next ba_lm_step / ba_lm_solve on the handle gives the same bits
+ * as without the call; a point's result depends on its own list, the cameras and the options only; the camera part of x comes
+ * back bit-identical.
+ * Out of scope: an adaptive hypothesis count, MSAC scoring, a minimum triangulation angle, Float32, several ranks. */
+int ba_ransac_points(ba_problem *p, double *x_inout /* nvar, host */, const ba_ransac_opts *opts, int max_iter, double xtol,
+                     double lambda0, uint8_t *status /* npnts or NULL */, double *cost /* 2 npnts or NULL */,
+                     int64_t *counts /* BA_PT_STATES + 1 or NULL */, int *iters_max /* or NULL */,
+                     uint8_t *inlier /* nobs or NULL */, int32_t *n_inliers /* npnts or NULL */, int32_t *best_hyp /* npnts or NULL */);
+int ba_ransac_points_dev(ba_problem *p, double *d_x_inout /* nvar, device */, const ba_ransac_opts *opts /* host */, int max_iter,
+                         double xtol, double lambda0, uint8_t *d_status /* npnts or NULL */, double *d_cost /* 2 npnts or NULL */,
+                         int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */,
+                         uint8_t *d_inlier /* nobs or NULL */, int32_t *d_n_inliers /* npnts or NULL */,
+                         int32_t *d_best_hyp /* npnts or NULL */, void *stream);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

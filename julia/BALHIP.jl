@@ -430,6 +430,47 @@ function ransac_cameras_p3p_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypo
   return nothing
 end
 
+# Outlier-robust triangulation (an extension): include/ba_hip.h, ba_ransac_points.  refine_points with init = 1 and a consensus
+# stage in front: every pair of a point's observations (`hypotheses` random pairs where it has more) is triangulated and scored
+# by its inliers, the best pair defines the point's set, and the triangulation and the refinement run on the set only.  `sample`
+# must be 2 (or below its range: the default 2), min_inliers at least 2 (the default).  The points of `x` are not read; they are
+# replaced.  Returns the status, cost, counts and trials of refine_points, then the inlier mask (nobs), the size of every point's
+# set and its winning hypothesis (-1: not attempted or none valid).
+function ransac_points!(nlp, x :: Vector{Float64}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                        refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                        xtol :: Real = -1.0, lam0 :: Real = -1.0)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  status = zeros(UInt8, nlp.npnts)
+  cost = zeros(Float64, 2, nlp.npnts)
+  counts = zeros(Int64, 7)
+  iters = Ref{Cint}(0)
+  inlier = zeros(UInt8, nlp.nobs)
+  n_inliers = zeros(Int32, nlp.npnts)
+  best_hyp = zeros(Int32, nlp.npnts)
+  GC.@preserve x status cost counts inlier n_inliers best_hyp begin
+    bacheck(ccall((:ba_ransac_points, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{UInt8}, Ptr{Float64}, Ptr{Int64}, Ref{Cint},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, pointer(x), opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), pointer(status), pointer(cost),
+                  pointer(counts), iters, pointer(inlier), pointer(n_inliers), pointer(best_hyp)))
+  end
+  return status, cost, counts, Int(iters[]), inlier .!= 0, n_inliers, best_hyp
+end
+
+function ransac_points_dev!(nlp, d_x :: Ptr{Cvoid}; threshold :: Real, hypotheses :: Integer = 0, sample :: Integer = 0,
+                            refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, max_iter :: Integer = -1,
+                            xtol :: Real = -1.0, lam0 :: Real = -1.0, d_status :: Ptr{Cvoid} = C_NULL,
+                            d_cost :: Ptr{Cvoid} = C_NULL, d_inlier :: Ptr{Cvoid} = C_NULL, d_n_inliers :: Ptr{Cvoid} = C_NULL,
+                            d_best_hyp :: Ptr{Cvoid} = C_NULL, stream :: Ptr{Cvoid} = C_NULL)
+  opts = Ref(BaRansacOpts(Cdouble(threshold), Cint(hypotheses), Cint(sample), Cint(refits), Cint(min_inliers), UInt64(seed)))
+  bacheck(ccall((:ba_ransac_points_dev, libba), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ref{BaRansacOpts}, Cint, Cdouble, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Ptr{Cint},
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                nlp.handle, d_x, opts, Cint(max_iter), Cdouble(xtol), Cdouble(lam0), d_status, d_cost, Ptr{Int64}(C_NULL),
+                Ptr{Cint}(C_NULL), d_inlier, d_n_inliers, d_best_hyp, stream))
+  return nothing
+end
+
 # The solver alone (ba_p3p): q is 2 x 3 x n, undistorted image points already divided by f (the ray is (q, -1)); X is 3 x 3 x n,
 # X[:, i, k] the world point of correspondence i of problem k.  Returns pose (6 x 4 x n: pose[:, s, k] is (r, t) of solution s of
 # problem k, in ascending order of the quartic's root, NaN in the unused slots) and the number of solutions of every problem.
