@@ -84,6 +84,7 @@ SYMBOLS = [
     "ba_ransac_cameras_p3p", "ba_ransac_cameras_p3p_dev", "ba_p3p",
     "ba_refine_relative_pose",
     "ba_ransac_points", "ba_ransac_points_dev",
+    "ba_homography", "ba_decompose_homography", "ba_homography_pose",
 ]
 
 _lib = None
@@ -180,6 +181,9 @@ def lib():
     L.ba_ransac_points_dev.argtypes = L.ba_ransac_cameras_dev.argtypes
     L.ba_p3p.argtypes = [vp, i64, vp, vp, vp, vp]
     L.ba_refine_relative_pose.argtypes = [vp, vp, i64, vp, vp, C.POINTER(PairRefineOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ba_homography.argtypes = L.ba_relative_pose.argtypes
+    L.ba_decompose_homography.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.ba_homography_pose.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -639,6 +643,9 @@ def ransac_sample(seed, hypothesis, degree, sample=6, used=None):
 
 # states of ba_relative_pose (BA_RP_*)
 PAIR_STATES = ("ok", "few_matches", "degenerate", "no_consensus")
+
+# states of ba_homography (BA_HG_*): the names of PAIR_STATES; few_matches is "fewer than 4 used matches" here
+HOMOGRAPHY_STATES = PAIR_STATES
 
 # states of ba_refine_relative_pose (BA_RR_*) and the keys of the `refine=` dict of relative_pose*
 PAIR_REFINE_STATES = ("converged", "stalled", "max_iter", "nonfinite", "skipped")

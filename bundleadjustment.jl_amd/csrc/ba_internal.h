@@ -230,6 +230,7 @@ enum ProfClass {
   PC_RESECT_CAMERAS,  // linear resection before it (ba_resect_cameras): k_resect_cameras
   PC_RANSAC_CAMERAS,  // consensus stage before that (ba_ransac_cameras): k_ransac_hypotheses, _select, _rescore, _mask_info
   PC_RANSAC_POINTS,   // consensus stage before the triangulation (ba_ransac_points): k_cam_pre, k_ransac_points, k_ransac_mask_info
+  PC_HOMOGRAPHY,      // homography of camera pairs (ba_homography): k_pair_rays, k_pair_hypotheses_h, k_pair_select_h, k_pair_fit_h
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -447,6 +448,17 @@ struct PairWork {
   DevBuf<double> rr_cost;
   DevBuf<int> rr_consistent, rr_iters;
   int64_t rr_cap = 0;
+  // ba_homography: H per (pair, hypothesis) and per pair (9 doubles each)
+  DevBuf<double> hg_hyp, hg_H;
+  int64_t hg_hyp_cap = 0, hg_cap = 0;
+  // ba_homography_pose: per pair the parallax, the number of poses, two poses (r, unit t), their normals and supports
+  DevBuf<double> hp_parallax, hp_pose, hp_normal;
+  DevBuf<int> hp_n, hp_support;
+  int64_t hp_cap = 0;
+  // ba_decompose_homography: the matrices (n x 9), their solutions (n x 4 x 9, n x 4 x 3, n x 4 x 3), counts and parallaxes
+  DevBuf<double> hd_H, hd_R, hd_t, hd_normal, hd_parallax;
+  DevBuf<int> hd_n;
+  int64_t hd_cap = 0;
 };
 // what the kernels of ba_relative_pose work on
 struct PairArgs {
@@ -459,6 +471,23 @@ struct PairArgs {
   uint64_t seed_mix;                    // mix(seed)
   double tau2;
 };
+// what the kernels of ba_homography and ba_homography_pose take beside them (PairArgs keeps its layout: the kernels of
+// ba_relative_pose keep their kernel arguments)
+struct HomArgs {
+  double *hyp_H, *H;  // 9 per (pair, hypothesis); 9 per pair
+  // ba_homography_pose
+  double *parallax, *pose2, *normal2;
+  int *n_pose, *support2;
+};
+constexpr int HG_MIN_MATCHES = 4;          // 8 unknowns, two independent equations per match: the least sample and the least set
+constexpr int HG_MIN_INLIERS_DEFAULT = 8;  // min_inliers <= 0
+constexpr int HG_DOUBLES = 9;              // H per hypothesis and per pair, row-major
+// the launches of ba_homography_kernels.hip (the entries are in ba_pair_kernels.hip, with the match lists and k_pair_rays)
+int launch_hom_hypotheses(const PairArgs &a, const HomArgs &q, int64_t npairs, hipStream_t st);
+int launch_hom_select(const PairArgs &a, const HomArgs &q, int64_t npairs, hipStream_t st);
+int launch_hom_fit(const PairArgs &a, const HomArgs &q, int64_t npairs, int final, hipStream_t st);
+int launch_hom_pose(const PairArgs &a, const HomArgs &q, int64_t npairs, hipStream_t st);
+int launch_hom_decompose(int64_t n, const double *H, double *R, double *t, double *normal, int *n_sol, double *parallax, hipStream_t st);
 // what k_pair_refine takes beside them (ba_refine_relative_pose; the options with their defaults filled in)
 struct PairRefineArgs {
   uint8_t *state;

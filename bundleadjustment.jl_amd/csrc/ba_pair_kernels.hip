@@ -922,3 +922,192 @@ extern "C" int ba_refine_relative_pose(ba_problem *p, const double *x, int64_t n
   }
   return BA_OK;
 }
+
+// ---- the homography of a pair: the entries ----------------------------------------------------------------------------
+namespace {
+
+// the per-pair buffers of ba_homography and ba_homography_pose, grown for npairs pairs and Hn hypotheses per pair
+int homography_buffers(PairWork &w, int64_t npairs, int64_t Hn, bool pose) {
+  if (w.hg_cap < npairs) {
+    w.hg_cap = 0;
+    BA_CHECK(w.hg_H.alloc(HG_DOUBLES * npairs));
+    w.hg_cap = npairs;
+  }
+  if (w.hg_hyp_cap < npairs * Hn) {
+    w.hg_hyp_cap = 0;
+    BA_CHECK(w.hg_hyp.alloc(HG_DOUBLES * npairs * Hn));
+    w.hg_hyp_cap = npairs * Hn;
+  }
+  if (pose && w.hp_cap < npairs) {
+    w.hp_cap = 0;
+    BA_CHECK(w.hp_parallax.alloc(npairs));
+    BA_CHECK(w.hp_pose.alloc(12 * npairs));
+    BA_CHECK(w.hp_normal.alloc(6 * npairs));
+    BA_CHECK(w.hp_n.alloc(npairs));
+    BA_CHECK(w.hp_support.alloc(2 * npairs));
+    w.hp_cap = npairs;
+  }
+  return BA_OK;
+}
+
+}  // namespace
+
+extern "C" int ba_homography(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                             const ba_ransac_opts *opts, double *H, uint8_t *status, int64_t *match_ptr, uint8_t *inlier,
+                             int32_t *n_inliers, int32_t *best_hyp, int64_t *counts) {
+  const char *who = "ba_homography";
+  ba_ransac_opts o = {};
+  if (opts) {
+    ba_ransac_opts in = *opts;
+    if (in.min_inliers <= 0) in.min_inliers = HG_MIN_INLIERS_DEFAULT;
+    if (in.min_inliers < HG_MIN_MATCHES) {
+      ba_set_error("%s: min_inliers must be >= %d (<= 0: %d), got %d", who, HG_MIN_MATCHES, HG_MIN_INLIERS_DEFAULT, in.min_inliers);
+      return BA_ERR_ARG;
+    }
+    BA_CHECK(ransac_opts_check(who, &in, &o, HG_MIN_MATCHES, HG_MIN_MATCHES, RN_SAMPLE_MAX));
+  }
+  if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !H || !status))) {
+    ba_set_error("%s: null argument or npairs < 0", who);
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
+    return BA_ERR_ARG;
+  }
+  std::vector<int64_t> ptr, oa, ob;
+  BA_CHECK(pair_match_lists(who, p->ncams, p->npnts, p->nobs, p->h_cam0.data(), p->h_pnt0.data(), 0, npairs, pair_a1, pair_b1, ptr, &oa, &ob));
+  const int64_t nmatch = ptr[(size_t)npairs];
+  if (nmatch > (int64_t)INT32_MAX) {
+    ba_set_error("%s: %lld matches: more than 2^31 - 1", who, (long long)nmatch);
+    return BA_ERR_ARG;
+  }
+  if (match_ptr)
+    for (size_t i = 0; i < ptr.size(); i++) match_ptr[i] = ptr[i];
+  if (counts)
+    for (int s = 0; s < BA_HG_STATES; s++) counts[s] = 0;
+  if (npairs == 0) return BA_OK;
+  hipStream_t st = p->stream;
+  PairWork &w = p->pairs;
+  PairUpload up;
+  PairArgs a = {};
+  HomArgs q = {};
+  const int Hn = opts ? o.hypotheses : 0;
+  BA_CHECK(homography_buffers(w, npairs, Hn, false));
+  q.hyp_H = w.hg_hyp, q.H = w.hg_H;
+  {
+    ProfScope ps(p, PC_HOMOGRAPHY, st);
+    BA_CHECK(pair_front(p, x, npairs, pair_a1, pair_b1, ptr, oa, ob, Hn, up, a));  // (Hn: the counts of the hypotheses)
+    a.hypotheses = Hn, a.sample = o.sample, a.min_inliers = o.min_inliers;
+    a.seed_mix = ransac_seed_mix(o.seed), a.tau2 = o.threshold * o.threshold;
+    if (opts) BA_CHECK(launch_hom_hypotheses(a, q, npairs, st));
+    BA_CHECK(launch_hom_select(a, q, npairs, st));
+    for (int it = 0; opts && it < o.refits; it++) BA_CHECK(launch_hom_fit(a, q, npairs, 0, st));
+    BA_CHECK(launch_hom_fit(a, q, npairs, 1, st));
+  }
+  std::vector<double> h_H((size_t)(HG_DOUBLES * npairs));
+  std::vector<uint8_t> h_status((size_t)npairs);
+  BA_HIP_CHECK(hipMemcpyAsync(h_H.data(), w.hg_H, h_H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(h_status.data(), w.status, h_status.size(), hipMemcpyDeviceToHost, st));
+  if (inlier && nmatch > 0) BA_HIP_CHECK(hipMemcpyAsync(inlier, w.inlier, (size_t)nmatch, hipMemcpyDeviceToHost, st));
+  if (n_inliers) BA_HIP_CHECK(hipMemcpyAsync(n_inliers, w.n_inliers, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (best_hyp) BA_HIP_CHECK(hipMemcpyAsync(best_hyp, w.best_hyp, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < npairs; i++) {
+    const uint8_t s = h_status[(size_t)i];
+    status[i] = s;
+    if (counts && s < BA_HG_STATES) counts[s]++;
+    if (s == BA_HG_OK)  // (a pair in any other state leaves its nine entries as the caller filled them)
+      for (int j = 0; j < HG_DOUBLES; j++) H[HG_DOUBLES * i + j] = h_H[(size_t)(HG_DOUBLES * i + j)];
+  }
+  return BA_OK;
+}
+
+// the decomposition alone; the handle supplies the device, the stream and the buffers
+extern "C" int ba_decompose_homography(ba_problem *p, int64_t n, const double *H, double *R, double *t, double *normal, int32_t *n_sol,
+                                       double *parallax) {
+  if (!p || n < 0 || (n > 0 && (!H || !R || !t || !normal || !n_sol || !parallax))) {
+    ba_set_error("ba_decompose_homography: null argument or n < 0");
+    return BA_ERR_ARG;
+  }
+  if (n > (int64_t)INT32_MAX / 36) {
+    ba_set_error("ba_decompose_homography: %lld problems: more than %lld", (long long)n, (long long)(INT32_MAX / 36));
+    return BA_ERR_ARG;
+  }
+  if (n == 0) return BA_OK;
+  BA_HIP_CHECK(hipSetDevice(p->device));
+  hipStream_t st = p->stream;
+  PairWork &w = p->pairs;
+  if (w.hd_cap < n) {
+    w.hd_cap = 0;
+    BA_CHECK(w.hd_H.alloc(9 * n));
+    BA_CHECK(w.hd_R.alloc(36 * n));
+    BA_CHECK(w.hd_t.alloc(12 * n));
+    BA_CHECK(w.hd_normal.alloc(12 * n));
+    BA_CHECK(w.hd_parallax.alloc(n));
+    BA_CHECK(w.hd_n.alloc(n));
+    w.hd_cap = n;
+  }
+  BA_HIP_CHECK(hipMemcpyAsync((double *)w.hd_H, H, (size_t)(9 * n) * sizeof(double), hipMemcpyHostToDevice, st));
+  {
+    ProfScope ps(p, PC_HOMOGRAPHY, st);
+    BA_CHECK(launch_hom_decompose(n, w.hd_H, w.hd_R, w.hd_t, w.hd_normal, w.hd_n, w.hd_parallax, st));
+  }
+  BA_HIP_CHECK(hipMemcpyAsync(R, w.hd_R, (size_t)(36 * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(t, w.hd_t, (size_t)(12 * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(normal, w.hd_normal, (size_t)(12 * n) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(n_sol, w.hd_n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(parallax, w.hd_parallax, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return BA_OK;
+}
+
+extern "C" int ba_homography_pose(ba_problem *p, const double *x, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                                  const double *H, const uint8_t *status_in, const uint8_t *inlier, double threshold, double *parallax,
+                                  int32_t *n_pose, double *pose, double *normal, int32_t *support) {
+  const char *who = "ba_homography_pose";
+  if (!std::isfinite(threshold) || !(threshold > 0)) {
+    ba_set_error("%s: threshold must be finite and > 0 (pixels), got %g", who, threshold);
+    return BA_ERR_ARG;
+  }
+  if (!p || npairs < 0 || (npairs > 0 && (!x || !pair_a1 || !pair_b1 || !H || !inlier || !parallax || !n_pose || !pose))) {
+    ba_set_error("%s: null argument or npairs < 0", who);
+    return BA_ERR_ARG;
+  }
+  if (p->comm.active()) {
+    ba_set_error("%s: not supported on a handle with a communicator (a camera's observations are spread over the shards)", who);
+    return BA_ERR_ARG;
+  }
+  std::vector<int64_t> ptr, oa, ob;
+  BA_CHECK(pair_match_lists(who, p->ncams, p->npnts, p->nobs, p->h_cam0.data(), p->h_pnt0.data(), 0, npairs, pair_a1, pair_b1, ptr, &oa, &ob));
+  const int64_t nmatch = ptr[(size_t)npairs];
+  if (nmatch > (int64_t)INT32_MAX) {
+    ba_set_error("%s: %lld matches: more than 2^31 - 1", who, (long long)nmatch);
+    return BA_ERR_ARG;
+  }
+  if (npairs == 0) return BA_OK;
+  hipStream_t st = p->stream;
+  PairWork &w = p->pairs;
+  PairUpload up;
+  PairArgs a = {};
+  HomArgs q = {};
+  BA_CHECK(homography_buffers(w, npairs, 0, true));
+  q.hyp_H = w.hg_hyp, q.H = w.hg_H;
+  q.parallax = w.hp_parallax, q.pose2 = w.hp_pose, q.normal2 = w.hp_normal, q.n_pose = w.hp_n, q.support2 = w.hp_support;
+  {
+    ProfScope ps(p, PC_HOMOGRAPHY, st);
+    BA_CHECK(pair_front(p, x, npairs, pair_a1, pair_b1, ptr, oa, ob, 0, up, a));
+    a.tau2 = threshold * threshold;
+    BA_HIP_CHECK(hipMemcpyAsync((double *)w.hg_H, H, (size_t)(HG_DOUBLES * npairs) * sizeof(double), hipMemcpyHostToDevice, st));
+    if (status_in) BA_HIP_CHECK(hipMemcpyAsync((uint8_t *)w.status, status_in, (size_t)npairs, hipMemcpyHostToDevice, st));
+    else BA_HIP_CHECK(hipMemsetAsync((uint8_t *)w.status, BA_HG_OK, (size_t)npairs, st));
+    if (nmatch > 0) BA_HIP_CHECK(hipMemcpyAsync((uint8_t *)w.inlier, inlier, (size_t)nmatch, hipMemcpyHostToDevice, st));
+    BA_CHECK(launch_hom_pose(a, q, npairs, st));
+  }
+  BA_HIP_CHECK(hipMemcpyAsync(parallax, w.hp_parallax, (size_t)npairs * sizeof(double), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(n_pose, w.hp_n, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipMemcpyAsync(pose, w.hp_pose, (size_t)(12 * npairs) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (normal) BA_HIP_CHECK(hipMemcpyAsync(normal, w.hp_normal, (size_t)(6 * npairs) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (support) BA_HIP_CHECK(hipMemcpyAsync(support, w.hp_support, (size_t)(2 * npairs) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  BA_HIP_CHECK(hipStreamSynchronize(st));
+  return BA_OK;
+}

@@ -566,6 +566,162 @@ def p3p(nlp, q, X):
     return poses, n_sol
 
 
+def _pair_call_args(who, nlp, x, pairs, obs_info):
+    """what the pair-level entries check and count before they call the library: (x, a1, b1, info3, match_ptr)"""
+    info3 = _lib.obs_info_pack(obs_info)
+    a1, b1 = _lib._pairs(pairs, nlp.ncams)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    if x.shape != (nlp.meta.nvar,):
+        raise ValueError(f"x must have shape ({nlp.meta.nvar},), got {x.shape}")
+    if info3 is not None and info3.shape[0] != nlp.nobs:
+        raise ValueError(f"obs_info: one entry per observation ({nlp.nobs}), got {info3.shape[0]}")
+    mp = np.zeros(len(a1) + 1, dtype=np.int64)
+    _lib.check(_lib.lib().ba_pair_matches(nlp.ncams, nlp.npnts, nlp.nobs, _lib.ptr(nlp.cams_indices), _lib.ptr(nlp.pnts_indices), len(a1),
+                                          _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(mp), None, None))
+    return x, a1, b1, info3, mp
+
+
+def homography(nlp, x, pairs, *, ransac=None, obs_info=None):
+    """The homography of camera pairs from their 2D-2D matches (ba_homography): the second two-view model, for matches on one
+    plane and for pairs without a baseline, where the eight-point fit of relative_pose* is degenerate or arbitrary.  d_b ~ H d_a
+    for the rays d = (q, -1).  ransac=dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) puts the consensus
+    stage of relative_pose in front (sample in 4..16, default 4; min_inliers at least 4, default 8); None: the linear fit on all
+    used matches.  pairs, x and obs_info as in relative_pose.
+    Returns the dict of relative_pose with `H` (npairs, 3, 3; sigma_2 = 1, the sign under which the points are in front; NaN
+    where the pair has none) in place of `r`, `t`: `status` (names among _lib.HOMOGRAPHY_STATES; few_matches: fewer than 4 used
+    matches), `match_ptr`, `inliers`, `n_inliers`, `best_hypothesis`, `counts`.  Bad arguments raise ValueError before any device
+    call."""
+    opts = None if ransac is None else _lib.ransac_opts(ransac, least=4, most=16, least_set=4)
+    x, a1, b1, info3, mp = _pair_call_args("homography", nlp, x, pairs, obs_info)
+    n = len(a1)
+    _lib.set_obs_info(nlp.handle, info3)
+    H, status = np.full((n, 3, 3), np.nan), np.zeros(n, dtype=np.uint8)
+    inlier, n_in, best = np.zeros(int(mp[-1]), dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    counts, mp2 = np.zeros(len(_lib.HOMOGRAPHY_STATES), dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    _lib.check(_lib.lib().ba_homography(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), None if opts is None else C.byref(opts),
+                                        _lib.ptr(H), _lib.ptr(status), _lib.ptr(mp2), _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best),
+                                        _lib.ptr(counts)))
+    return dict(H=H, status=np.array(_lib.HOMOGRAPHY_STATES)[status], match_ptr=mp2, inliers=inlier != 0, n_inliers=n_in,
+                best_hypothesis=best, counts={s: int(c) for s, c in zip(_lib.HOMOGRAPHY_STATES, counts)})
+
+
+def decompose_homography(nlp, H):
+    """The decomposition of homographies H = R + t n' / d (ba_decompose_homography), n independent problems: H (n, 3, 3), its sign
+    as given (homography returns the sign under which the points are in front).  Returns (R, t, normal, n_sol, parallax): R
+    (n, 4, 3, 3), t (n, 4, 3) in units of the plane distance d, normal (n, 4, 3) in camera a's frame, NaN in the unused slots;
+    n_sol (n,) 0 (H not finite), 1 (a rotation: t = 0, normal = 0) or 4, in the order (+), -(+), (-), -(-) of the header;
+    parallax (n,) = sigma_1 - sigma_3 at sigma_2 = 1, which is |t| / d.  nlp supplies the device and the stream.  Bad arguments
+    raise ValueError before any device call."""
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    if H.ndim != 3 or H.shape[1:] != (3, 3):
+        raise ValueError(f"decompose_homography: H must have shape (n, 3, 3), got {H.shape}")
+    n = H.shape[0]
+    R, t, normal = np.full((n, 4, 3, 3), np.nan), np.full((n, 4, 3), np.nan), np.full((n, 4, 3), np.nan)
+    n_sol, parallax = np.zeros(n, dtype=np.int32), np.full(n, np.nan)
+    _lib.check(_lib.lib().ba_decompose_homography(nlp.handle, n, _lib.ptr(H), _lib.ptr(R), _lib.ptr(t), _lib.ptr(normal), _lib.ptr(n_sol),
+                                                  _lib.ptr(parallax)))
+    return R, t, normal, n_sol, parallax
+
+
+def homography_pose(nlp, x, pairs, info, *, threshold, obs_info=None):
+    """The pose of planar pairs from their homographies (ba_homography_pose).  info: the dict homography returned for the same
+    nlp, x, pairs and obs_info (`H`, `status` and `inliers` are read); threshold (pixels, required): the tau of the support count.
+    Per pair that is "ok": H is decomposed, and the candidates whose plane lies in front of camera a for more than half of the
+    set are kept in solver order, at most two.  Returns a dict: `parallax` (npairs,) = |t| / d; `n_pose` (0..2); `r`, `t`
+    (npairs, 2, 3: the rotation vector and the unit translation of each candidate), `normal` (npairs, 2, 3), NaN in the unused
+    slots; `support` (npairs, 2): the matches of the pair's whole list that pass the inlier test of relative_pose under the
+    candidate, -1 in the unused slots -- off-plane matches tell the two apart, and on a pure plane the counts tie.  A pair
+    without a baseline has n_pose = 1 with its r, t NaN and support -1.  Bad arguments raise ValueError before any device call."""
+    try:
+        tau = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"homography_pose: threshold must be a finite number > 0, got {threshold!r}") from None
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError(f"homography_pose: threshold must be a finite number > 0, got {threshold!r}")
+    x, a1, b1, info3, mp = _pair_call_args("homography_pose", nlp, x, pairs, obs_info)
+    if not isinstance(info, dict) or any(k not in info for k in ("H", "status", "inliers")):
+        raise ValueError("info must be the dict of homography (H, status, inliers are read)")
+    n = len(a1)
+    H, names = np.ascontiguousarray(info["H"], dtype=np.float64), np.asarray(info["status"])
+    inlier = np.ascontiguousarray(np.asarray(info["inliers"]) != 0, dtype=np.uint8)
+    if H.shape != (n, 3, 3) or names.shape != (n,):
+        raise ValueError(f"info: H must have shape ({n}, 3, 3) and status ({n},), got {H.shape}, {names.shape}")
+    if inlier.shape != (int(mp[-1]),):
+        raise ValueError(f"info: inliers must hold one entry per match ({int(mp[-1])}), got {inlier.shape}")
+    if not np.isin(names, _lib.HOMOGRAPHY_STATES).all():
+        raise ValueError(f"info: status must hold names among {', '.join(_lib.HOMOGRAPHY_STATES)}")
+    status = np.array([_lib.HOMOGRAPHY_STATES.index(s) for s in names], dtype=np.uint8)
+    _lib.set_obs_info(nlp.handle, info3)
+    parallax, n_pose = np.full(n, np.nan), np.zeros(n, dtype=np.int32)
+    pose, normal, support = np.full((n, 2, 6), np.nan), np.full((n, 2, 3), np.nan), np.full((n, 2), -1, dtype=np.int32)
+    _lib.check(_lib.lib().ba_homography_pose(nlp.handle, _lib.ptr(x), n, _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(H), _lib.ptr(status),
+                                             _lib.ptr(inlier), tau, _lib.ptr(parallax), _lib.ptr(n_pose), _lib.ptr(pose), _lib.ptr(normal),
+                                             _lib.ptr(support)))
+    return dict(parallax=parallax, n_pose=n_pose, r=pose[:, :, :3].copy(), t=pose[:, :, 3:].copy(), normal=normal, support=support)
+
+
+TWO_VIEW_MODELS = ("general", "planar", "rotation", "none")
+
+
+def two_view(nlp, x, pairs, *, ransac, ratio=0.8, min_parallax=0.05, refine=None, obs_info=None):
+    """Which two-view model explains each pair, its pose, and the order in which the pairs can seed a reconstruction.  Runs
+    relative_pose_five_point and homography under the same ransac options (sample forced to 5 and 4), then homography_pose with
+    the ransac threshold.  With n_E and n_H the sizes of the two consensus sets, `model` is per pair
+      "general"   n_H < ratio n_E: the pose of the essential stage (refine=dict(...) as in relative_pose_five_point);
+      "planar"    n_H >= ratio n_E and parallax >= min_parallax: r, t of the homography candidate with the larger support, ties
+                  to the first with `ambiguous` True; both candidates are in `candidates`;
+      "rotation"  n_H >= ratio n_E and parallax < min_parallax: r is valid, t is NaN -- the pair has no baseline and must not
+                  seed a reconstruction;
+      "none"      neither stage found a consensus.
+    ratio and min_parallax are the caller's choices; the defaults are conventions (0.8 is COLMAP's H/E inlier ratio for a
+    planar pair), not thresholds measured here.
+    Returns a dict: `model`, `r`, `t` (npairs, 3; NaN where there is none), `ambiguous`, `candidates` (the dict of
+    homography_pose), `n_general`, `n_planar` (the two set sizes, 0 without a consensus), `parallax`, `normal` (npairs, 3: of the
+    chosen planar candidate), `off_plane` (the matches in the essential set that are not in the homography's), `general` and
+    `planar` (the dicts of the two stages) and `seed_order`: the indices of the pairs with a translation, general before planar,
+    by off_plane and then n_inliers descending, ties by pair index.  Bad arguments raise ValueError before any device call."""
+    if ransac is None:
+        raise ValueError("two_view: ransac is required (both models are fitted by the consensus stage)")
+    _lib.ransac_opts(ransac, least=4, most=16, least_set=4)  # (the keys and the shared ranges, before either stage runs)
+    for name, v in (("ratio", ratio), ("min_parallax", min_parallax)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+            raise ValueError(f"two_view: {name} must be a finite number >= 0, got {v!r}")
+    gen = relative_pose_five_point(nlp, x, pairs, ransac=dict(ransac, sample=5, min_inliers=max(int(ransac.get("min_inliers") or 0), 8)),
+                                   obs_info=obs_info, refine=refine)
+    pla = homography(nlp, x, pairs, ransac=dict(ransac, sample=4), obs_info=obs_info)
+    cand = homography_pose(nlp, x, pairs, pla, threshold=ransac["threshold"], obs_info=obs_info)
+    n = len(gen["status"])
+    ok_e, ok_h = gen["status"] == "ok", pla["status"] == "ok"
+    n_e, n_h = np.where(ok_e, gen["n_inliers"], 0).astype(np.int64), np.where(ok_h, pla["n_inliers"], 0).astype(np.int64)
+    mp = gen["match_ptr"]
+    off = np.array([int((gen["inliers"][mp[k]:mp[k + 1]] & ~pla["inliers"][mp[k]:mp[k + 1]]).sum()) if ok_e[k] else 0 for k in range(n)],
+                   dtype=np.int64)
+    model = np.full(n, "none", dtype=object)
+    r, t, normal = np.full((n, 3), np.nan), np.full((n, 3), np.nan), np.full((n, 3), np.nan)
+    ambiguous = np.zeros(n, dtype=bool)
+    for k in range(n):
+        explains = ok_h[k] and n_h[k] >= ratio * n_e[k]
+        if explains and cand["parallax"][k] < min_parallax:
+            model[k] = "rotation"
+            r[k] = cand["r"][k, 0]  # (of the first candidate: at no parallax they share the rotation)
+        elif explains and cand["n_pose"][k] > 0:
+            model[k] = "planar"
+            pick = 0
+            if cand["n_pose"][k] == 2:
+                s0, s1 = cand["support"][k]
+                pick, ambiguous[k] = (1 if s1 > s0 else 0), bool(s0 == s1)
+            r[k], t[k], normal[k] = cand["r"][k, pick], cand["t"][k, pick], cand["normal"][k, pick]
+        elif ok_e[k]:
+            model[k] = "general"
+            r[k], t[k] = gen["r"][k], gen["t"][k]
+    rank = {"general": 0, "planar": 1}
+    n_in = np.where(model == "general", n_e, n_h)
+    seeds = [k for k in range(n) if model[k] in rank]
+    seed_order = np.array(sorted(seeds, key=lambda k: (rank[model[k]], -off[k], -n_in[k], k)), dtype=np.int64)
+    return dict(model=model.astype(str), r=r, t=t, ambiguous=ambiguous, candidates=cand, n_general=n_e, n_planar=n_h,
+                parallax=cand["parallax"], normal=normal, off_plane=off, general=gen, planar=pla, seed_order=seed_order)
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

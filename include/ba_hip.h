@@ -751,8 +751,9 @@ int ba_ransac_cameras_focal_dev(ba_problem *p, double *d_x_inout /* nvar, device
  * seeded x) is what makes the estimate.
  * The remedy is the five-point minimal solver as the hypothesis generator: ba_relative_pose_five_point, below.
  * The non-linear refinement of the pair on its final set is ba_refine_relative_pose, further down.
- * Out of scope: unknown focal lengths; homographies and planar
- * scenes; MSAC or an adaptive hypothesis count; the choice of the initial pair; Float32; several ranks; a device-resident entry. */
+ * Planar scenes and pairs without a baseline are the business of ba_homography and ba_homography_pose, further down, and the
+ * choice of the initial pair that of two_view of the Python package.
+ * Out of scope: unknown focal lengths; MSAC or an adaptive hypothesis count; Float32; several ranks; a device-resident entry. */
 enum { BA_RP_OK = 0, BA_RP_FEW_MATCHES = 1, BA_RP_DEGENERATE = 2, BA_RP_NO_CONSENSUS = 3, BA_RP_STATES = 4 };
 int ba_pair_matches(int64_t ncams, int64_t npnts, int64_t nobs, const int64_t *cam_idx1, const int64_t *pnt_idx1,
                     int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
@@ -966,6 +967,78 @@ int ba_ransac_points_dev(ba_problem *p, double *d_x_inout /* nvar, device */, co
                          int64_t *counts /* host, or NULL */, int *iters_max /* host, or NULL */,
                          uint8_t *d_inlier /* nobs or NULL */, int32_t *d_n_inliers /* npnts or NULL */,
                          int32_t *d_best_hyp /* npnts or NULL */, void *stream);
+
+/* ---- homography of camera pairs: consensus, decomposition and the pose of a planar pair (an extension) ---------------
+ * The final fit of ba_relative_pose* is the eight-point fit, which is degenerate on the points of one plane and arbitrary on noisy
+ * ones, and a pair without a baseline (a camera turned on the spot) passes the essential-matrix consensus with a meaningless t.
+ * The second two-view model covers both: for matches on a plane n' P_a = d (n the unit normal in camera a's frame, d > 0 the
+ * distance of camera a's centre) the rays obey d_b ~ H d_a with H = R + t n' / d, and with t = 0 every match does.
+ * ba_homography: the arguments, the match lists, "used" (Lambda != 0 on both observations), the rays (step 1 of ba_relative_pose:
+ * q_a, q_b, d = (q, -1); a focal length that is not finite or 0: BA_HG_DEGENERATE), the communicator refusal, the optional outputs,
+ * npairs == 0 and the guarantees (no atomics, one writer per output, two calls give the same bits, a pair alone gives the bits it
+ * gives among many, the next ba_lm_step / ba_lm_solve gives the bits it gives without the call) are those of ba_relative_pose.
+ * States: BA_HG_FEW_MATCHES -- fewer than 4 used matches; BA_HG_DEGENERATE -- a focal length, or the final fit is degenerate;
+ * BA_HG_NO_CONSENSUS; BA_HG_OK.  Only a pair that is BA_HG_OK has its nine entries of H written (row-major); the others keep
+ * what the caller put there.
+ * The linear fit on a set of n >= 4 matches:
+ *  1. Hartley normalisation per image, exactly steps 1-2 of ba_relative_pose: the sums about the first match of the set,
+ *     d~ = T d = (s (q - c), -1).  Coinciding image points or a sum that is not finite: degenerate.
+ *  2. M = sum A'A (9 x 9, 45 packed sums) with A = [d~_b]x (x) d~_a' (3 x 9), the three rows of d~_b x (H~ d~_a) = 0 in the
+ *     row-major entries of H~; A'A = (|d~_b|^2 I - d~_b d~_b') (x) (d~_a d~_a') is what is summed.
+ *  3. H~ = the eigenvector of M's smallest eigenvalue by the cyclic Jacobi sweeps of ba_resect_cameras.  An eigenvalue that is not
+ *     finite, or lambda_2 <= 1e-10 lambda_9: degenerate (three of four sampled points on a line, among others).
+ *  4. H = T_b^-1 H~ T_a with T = [[s, 0, s c_x], [0, s, s c_y], [0, 0, 1]]; its singular values by the one-sided 3 x 3 Jacobi SVD
+ *     of ba_resect_cameras.  sigma_3 <= 1e-6 sigma_1, or one that is not finite: degenerate.  H is divided by sigma_2.
+ *  5. The sign: H is negated iff fewer than half of the set have d_b' H d_a > 0 (a comparison with NaN counts as not positive)
+ *     or, at exactly half, det H < 0: a tie goes to the sign of a homography with both centres on one side of the plane, never to
+ *     the arbitrary sign of the eigenvector.
+ * Inlier test of a match under H: it is used; m = H d_a has m_3 < 0 and m' = adj(H) d_b has m'_3 < 0 (the adjugate: no division,
+ * and the ratios below need no scale); both transfer errors in pixels^2, f_b^2 |q_b + m_1:2 / m_3|^2 and
+ * f_a^2 |q_a + m'_1:2 / m'_3|^2, are <= tau^2.  A comparison with NaN fails.
+ * opts == NULL: no consensus stage -- the set is every used match (inlier = used, best_hyp = -1), H the linear fit on it.
+ * opts != NULL: the consensus stage of ba_relative_pose in everything but the ranges -- sample m (<= 0: 4; 4..16); min_inliers
+ * (<= 0: 8; at least 4); threshold, hypotheses (<= 4096), refits (<= 8) and seed as there.  Sampling is exactly
+ * ba_ransac_sample(seed, h, degree, used, m) on the pair's list (the rule: that host entry itself takes m >= 6 only).
+ * Hypothesis h = the linear fit on the m sampled matches, a degenerate sample is void; score = the inlier count over the whole
+ * list; the winner (ties to the lowest h), BA_HG_NO_CONSENSUS (its inlier bytes, n_inliers and best_hyp), the refits with the
+ * adopt rule (M' adopted iff |M'| >= |M| and M' != M) and the finish are as there: the fit on the final set is the returned H.
+ * ba_decompose_homography: the solver alone, n independent problems, one lane each, in registers.  The sign of H is taken as
+ * given (ba_homography returns the sign under which the points are in front).  SVD of H by the one-sided Jacobi sweeps, sigma_1
+ * >= sigma_2 >= sigma_3, H V = U Sigma; v_1 and v_3 are signed so that their entry of the largest magnitude is positive (ties to
+ * the lowest index) and v_2 = v_3 x v_1, so V is proper.  An entry or a singular value that is not finite, or sigma_2 = 0:
+ * n_sol = 0.  H is divided by sigma_2; parallax = sigma_1 - sigma_3, which is |t| / d for H = R + t n' / d.
+ * sigma_1^2 - sigma_3^2 <= 1e-12: n_sol = 1, the rotation-only case -- R = [H v_1 / sigma_1, H v_2, their cross product] V', the
+ * nearest rotation of H, t = 0, normal = 0.  Otherwise n_sol = 4, the solutions of Ma, Soatto, Kosecka and Sastry (An Invitation
+ * to 3-D Vision, Alg. 5.2): u+- = (sqrt(1 - sigma_3^2) v_1 +- sqrt(sigma_1^2 - 1) v_3) / sqrt(sigma_1^2 - sigma_3^2) (a negative
+ * radicand is taken as 0), U = [v_2, u, v_2 x u], W = [H v_2, H u, H v_2 x H u], R = W U', n = v_2 x u, t = (H - R) n in units of
+ * d; each comes with (R, -t, -n); the order is (+), -(+), (-), -(-).  The unused slots are NaN.
+ * ba_homography_pose: the pose of a planar pair.  For every pair that is BA_HG_OK in status_in (NULL: all) H is decomposed; of the
+ * four solutions those whose normal has n' d_a > 0 for more than half of the set (the inlier bytes of ba_homography: the plane
+ * is in front of camera a) are kept in solver order, at most two.  Per kept candidate: r by the rotation-vector rule of
+ * ba_resect_cameras, t / |t|, the normal, and support = the count of the inlier test of ba_relative_pose (Sampson <= tau^2 with
+ * tau = threshold, both depths > 0) over the pair's WHOLE list under that pose: the matches off the plane tell the two
+ * candidates apart, and on a pure plane the counts tie.  The rotation-only case returns n_pose = 1: r is valid, t and the normal are
+ * NaN and support is -1.  Every other pair: n_pose = 0, parallax NaN.  Unused entries of pose and normal are NaN, of support -1.
+ * normal and support may be NULL.
+ * Out of scope: a non-linear refinement of H; the choice between the two planar candidates without off-plane matches; MSAC;
+ * Float32; several ranks; a device-resident entry.  The choice of the initial pair is two_view of the Python package. */
+enum { BA_HG_OK = 0, BA_HG_FEW_MATCHES = 1, BA_HG_DEGENERATE = 2, BA_HG_NO_CONSENSUS = 3, BA_HG_STATES = 4 };
+int ba_homography(ba_problem *p, const double *x /* nvar, host: only (k1, k2, f) of the pairs' cameras are read */,
+                  int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                  const ba_ransac_opts *opts /* NULL: the linear fit on all used matches */,
+                  double *H /* 9 npairs, row-major */, uint8_t *status /* npairs */,
+                  int64_t *match_ptr /* npairs + 1, or NULL */, uint8_t *inlier /* one byte per match, or NULL */,
+                  int32_t *n_inliers /* npairs or NULL */, int32_t *best_hyp /* npairs or NULL */,
+                  int64_t *counts /* BA_HG_STATES or NULL */);
+int ba_decompose_homography(ba_problem *p, int64_t n, const double *H /* n x 9 */, double *R /* n x 4 x 9 */,
+                            double *t /* n x 4 x 3, in units of the plane distance */, double *normal /* n x 4 x 3 */,
+                            int32_t *n_sol /* n: 0, 1 or 4 */, double *parallax /* n */);
+int ba_homography_pose(ba_problem *p, const double *x /* nvar, host: only (k1, k2, f) of the pairs' cameras are read */,
+                       int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1, const double *H /* 9 npairs */,
+                       const uint8_t *status_in /* npairs or NULL */, const uint8_t *inlier /* the set of H, one byte per match */,
+                       double threshold, double *parallax /* npairs */, int32_t *n_pose /* npairs: 0..2 */,
+                       double *pose /* npairs x 2 x 6: r, unit t */, double *normal /* npairs x 2 x 3 or NULL */,
+                       int32_t *support /* npairs x 2 or NULL */);
 
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated

@@ -391,6 +391,79 @@ function five_point(nlp, qa :: Array{Float64, 3}, qb :: Array{Float64, 3})
   return E, n_sol
 end
 
+# Homography of camera pairs (an extension): include/ba_hip.h, ba_homography / ba_decompose_homography / ba_homography_pose.
+# homography is relative_pose with the second two-view model, d_b ~ H d_a, for matches on one plane and pairs without a
+# baseline: with a threshold (pixels) the consensus stage stands in front (samples of 4..16, default 4; min_inliers at least 4,
+# default 8).  Returns H (3 x 3 x npairs in C's row-major order: H[j, i, k] is entry (i, j) of pair k; sigma_2 = 1; NaN where the
+# state is not 0), status (BA_HG_*), match_ptr, the inlier mask per match, the size of every pair's set, its winning hypothesis
+# and the pairs per state.
+function homography(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64};
+                    threshold :: Union{Real, Nothing} = nothing, hypotheses :: Integer = 0, sample :: Integer = 0,
+                    refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0)
+  npairs = length(pairs_a)
+  match_ptr, _, _ = pair_matches(nlp, pairs_a, pairs_b)
+  H = fill(NaN, 3, 3, npairs)
+  status = zeros(UInt8, npairs)
+  inlier = zeros(UInt8, match_ptr[end])
+  n_inliers = zeros(Int32, npairs)
+  best_hyp = zeros(Int32, npairs)
+  counts = zeros(Int64, 4)
+  opts = Ref(BaRansacOpts(Cdouble(threshold === nothing ? 1.0 : threshold), Cint(hypotheses), Cint(sample), Cint(refits),
+                          Cint(min_inliers), UInt64(seed)))
+  GC.@preserve x pairs_a pairs_b opts H status match_ptr inlier n_inliers best_hyp counts begin
+    optr = threshold === nothing ? Ptr{BaRansacOpts}(C_NULL) : Base.unsafe_convert(Ptr{BaRansacOpts}, opts)
+    bacheck(ccall((:ba_homography, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{BaRansacOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int64},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}),
+                  nlp.handle, pointer(x), npairs, pointer(pairs_a), pointer(pairs_b), optr, pointer(H), pointer(status),
+                  pointer(match_ptr), pointer(inlier), pointer(n_inliers), pointer(best_hyp), pointer(counts)))
+  end
+  return H, status, match_ptr, inlier .!= 0, n_inliers, best_hyp, counts
+end
+
+# The decomposition alone (ba_decompose_homography): H is 3 x 3 x n in C's row-major order, its sign as given.  Returns R
+# (3 x 3 x 4 x n, row-major like H), t (3 x 4 x n, in units of the plane distance), the normals (3 x 4 x n), NaN in the unused
+# slots, the number of solutions of every problem (0, 1: a rotation, or 4) and the parallax |t| / d.
+function decompose_homography(nlp, H :: Array{Float64, 3})
+  size(H, 1) == 3 && size(H, 2) == 3 || error("decompose_homography: H must be 3 x 3 x n")
+  n = size(H, 3)
+  R = fill(NaN, 3, 3, 4, n)
+  t = fill(NaN, 3, 4, n)
+  normal = fill(NaN, 3, 4, n)
+  n_sol = zeros(Int32, n)
+  parallax = fill(NaN, n)
+  GC.@preserve H R t normal n_sol parallax begin
+    bacheck(ccall((:ba_decompose_homography, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                  nlp.handle, n, pointer(H), pointer(R), pointer(t), pointer(normal), pointer(n_sol), pointer(parallax)))
+  end
+  return R, t, normal, n_sol, parallax
+end
+
+# The pose of planar pairs (ba_homography_pose) from what homography returned (H, status, the inlier mask): per pair the
+# parallax, the number of candidates (0..2), their poses (6 x 2 x npairs: r, then the unit t), their normals (3 x 2 x npairs) and
+# their supports (2 x npairs: the inliers of relative_pose's test over the pair's whole list; -1 in the unused slots).  A pair
+# without a baseline has one candidate with its r and NaN for t.
+function homography_pose(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}, H :: Array{Float64, 3},
+                         status :: Vector{UInt8}, inlier :: AbstractVector{Bool}; threshold :: Real)
+  npairs = length(pairs_a)
+  size(H) == (3, 3, npairs) && length(status) == npairs || error("homography_pose: H must be 3 x 3 x npairs and status npairs")
+  bytes = Vector{UInt8}(inlier)
+  parallax = fill(NaN, npairs)
+  n_pose = zeros(Int32, npairs)
+  pose = fill(NaN, 6, 2, npairs)
+  normal = fill(NaN, 3, 2, npairs)
+  support = fill(Int32(-1), 2, npairs)
+  GC.@preserve x pairs_a pairs_b H status bytes parallax n_pose pose normal support begin
+    bacheck(ccall((:ba_homography_pose, libba), Cint,
+                  (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}, Ptr{UInt8}, Cdouble, Ptr{Float64},
+                   Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                  nlp.handle, pointer(x), npairs, pointer(pairs_a), pointer(pairs_b), pointer(H), pointer(status), pointer(bytes),
+                  Cdouble(threshold), pointer(parallax), pointer(n_pose), pointer(pose), pointer(normal), pointer(support)))
+  end
+  return parallax, n_pose, pose, normal, support
+end
+
 # P3P minimal samples for the consensus stage of the camera resection (an extension): include/ba_hip.h, ba_ransac_cameras_p3p.
 # ransac_cameras! with three correspondences per hypothesis instead of six, solved exactly: every real P3P pose (up to four) is
 # scored and the best is the hypothesis.  `sample` must be 3 (or below its range: the default 3), min_inliers is still at least

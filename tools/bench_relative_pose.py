@@ -20,8 +20,13 @@ translation direction against the generator, the share of the OK pairs within 1 
 n_inliers (for the unrefined pose from an evaluate-only call, max_iter = 0) and the state counts.  To
 profiles/relative_pose_refine_bench.json, where the rows of the other generator are kept.
 
+--homography: the same shapes, scenes and options through homography (samples of 4) next to relative_pose (samples of
+8) and relative_pose_five_point (samples of 5) on one handle -- wall time of each call, the event time of the homography's
+kernels (profile class k_homography) and the wall time of homography_pose on its result -- to profiles/homography_bench.json.
+These scenes are general, not planar: the times are what the stage costs, the counts say how rarely it finds a consensus there.
+
 One JSON object per shape on stdout; all of them to profiles/relative_pose_bench.json, or the file given.
-usage: python tools/bench_relative_pose.py [--five-point] [--refine] [out.json] [reps]"""
+usage: python tools/bench_relative_pose.py [--five-point] [--refine] [--homography] [out.json] [reps]"""
 import json
 import os
 import statistics
@@ -108,6 +113,26 @@ def measure_refine(ba, name, p, pairs, options, reps, five):
     return rows
 
 
+def measure_homography(ba, name, p, pairs, options, reps, five=False):
+    q, m, x, Ct = prepare(ba, p)
+    mp, _, _ = ba.pair_matches(q, pairs)
+    row = {"shape": name, "entry": "homography", "pairs": int(len(pairs)), "matches": int(mp[-1]), "outlier_fraction": OUTLIER_FRACTION,
+           "hypotheses": options["hypotheses"], "refits": options["refits"], "threshold": options["threshold"]}
+    for key, entry, sample in (("eight_point", ba.relative_pose, 8), ("five_point", ba.relative_pose_five_point, 5), ("homography", ba.homography, 4)):
+        info, med, wall = timed(lambda: entry(m, x, pairs, ransac=dict(options, sample=sample)), reps)
+        row[key] = {"sample": sample, "call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall], "counts": info["counts"],
+                    "hypotheses_per_s": round(len(pairs) * options["hypotheses"] / (med * 1e-3))}
+    m.profile(True)
+    info = ba.homography(m, x, pairs, ransac=dict(options, sample=4))
+    ms, calls = m.profile_get()["k_homography"]
+    m.profile(False)
+    row["homography"]["kernels_event_ms"] = round(ms, 3)
+    _, med, wall = timed(lambda: ba.homography_pose(m, x, pairs, info, threshold=options["threshold"]), reps)
+    row["homography_pose"] = {"call_ms_median": round(med, 3), "call_ms_all": [round(v, 3) for v in wall]}
+    m.close()
+    return row
+
+
 def measure(ba, name, p, pairs, options, reps, five=False):
     q, m, x, Ct = prepare(ba, p)
     n, nc = p["npnts"], p["ncams"]
@@ -144,9 +169,9 @@ def measure(ba, name, p, pairs, options, reps, five=False):
 
 def main():
     args = sys.argv[1:]
-    five, refine = "--five-point" in args, "--refine" in args
-    args = [a for a in args if a not in ("--five-point", "--refine")]
-    default = "relative_pose_refine_bench.json" if refine else "relative_pose_five_point_bench.json" if five else "relative_pose_bench.json"
+    five, refine, hom = "--five-point" in args, "--refine" in args, "--homography" in args
+    args = [a for a in args if a not in ("--five-point", "--refine", "--homography")]
+    default = "homography_bench.json" if hom else "relative_pose_refine_bench.json" if refine else "relative_pose_five_point_bench.json" if five else "relative_pose_bench.json"
     out = args.pop(0) if args and args[0].endswith(".json") else os.path.join(ROOT, "profiles", default)
     reps = int(args.pop(0)) if args and args[0].isdigit() else 3
     ba, _ = _benchlib.load()
@@ -158,7 +183,7 @@ def main():
         rows = [r for r in json.load(open(out)) if r.get("entry") != mine]
 
     def add(*a):
-        new = measure_refine(ba, *a) if refine else [measure(ba, *a)]
+        new = [measure_homography(ba, *a)] if hom else measure_refine(ba, *a) if refine else [measure(ba, *a)]
         for row in new:
             print(json.dumps(row), flush=True)
         rows.extend(new)
