@@ -57,6 +57,12 @@ class PairRefineOpts(C.Structure):
                 ("threshold", C.c_double), ("rounds", C.c_int)]
 
 
+class RotavgOpts(C.Structure):
+    """ba_rotavg_opts"""
+    _fields_ = [("loss", C.c_int), ("max_sweeps", C.c_int), ("loops", C.c_int), ("min_support", C.c_int), ("f_scale", C.c_double),
+                ("damping", C.c_double), ("xtol", C.c_double), ("loop_threshold", C.c_double)]
+
+
 LOG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                      C.c_double, C.c_int)
 COMM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -85,6 +91,7 @@ SYMBOLS = [
     "ba_refine_relative_pose",
     "ba_ransac_points", "ba_ransac_points_dev",
     "ba_homography", "ba_decompose_homography", "ba_homography_pose",
+    "ba_rotation_loops", "ba_view_graph_forest", "ba_average_rotations",
 ]
 
 _lib = None
@@ -184,6 +191,9 @@ def lib():
     L.ba_homography.argtypes = L.ba_relative_pose.argtypes
     L.ba_decompose_homography.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     L.ba_homography_pose.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
+    L.ba_rotation_loops.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, vp, vp]
+    L.ba_view_graph_forest.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ba_average_rotations.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RotavgOpts)] + [vp] * 12
     _lib = L
     return L
 
@@ -680,6 +690,10 @@ def pair_refine_opts(max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0
         raise ValueError(f"refine_relative_pose: loss must be one of {', '.join(LOSSES)}, got {loss!r}")
     return PairRefineOpts(ints["max_iter"], reals["xtol"], reals["lam0"], LOSSES[loss], reals["f_scale"], reals["threshold"],
                           ints["rounds"])
+
+
+# states of ba_average_rotations (BA_RA_*), per camera
+ROTAVG_STATES = ("ok", "root", "fixed", "isolated")
 
 
 def _pairs(pairs, ncams=None):

@@ -231,6 +231,7 @@ enum ProfClass {
   PC_RANSAC_CAMERAS,  // consensus stage before that (ba_ransac_cameras): k_ransac_hypotheses, _select, _rescore, _mask_info
   PC_RANSAC_POINTS,   // consensus stage before the triangulation (ba_ransac_points): k_cam_pre, k_ransac_points, k_ransac_mask_info
   PC_HOMOGRAPHY,      // homography of camera pairs (ba_homography): k_pair_rays, k_pair_hypotheses_h, k_pair_select_h, k_pair_fit_h
+  PC_ROTAVG,          // "k_rotation_averaging" (ba_rotation_loops, ba_average_rotations): k_rotation_loops, k_rotavg_sweep, k_rotavg_edges, k_rotavg_sum, k_rotavg_finish
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -502,6 +503,25 @@ constexpr double RR_XTOL_DEFAULT = 1e-10, RR_LAMBDA0_DEFAULT = 1e-4;
 // The options as k_pair_refine takes them (defaults filled in), or BA_ERR_ARG with `who` in the message
 int pair_refine_opts_check(const char *who, const ba_pair_refine_opts *in, ba_pair_refine_opts *out);
 
+// ---- rotation averaging over the view graph (ba_rotation_loops, ba_average_rotations; ba_rotavg_kernels.hip) ---------
+// The per-call device buffers, each grown when a call needs more.  Per pair: its cameras
+// (0-based), the rotation vector and the 3 x 3 of it, the flags used / kept / "r is finite", the weight, the loop counts, the
+// residual, rho' and the cost term.  Per camera: the CSR adjacency (ptr; nbr and edge per entry), the two buffers of the
+// simultaneous update, the start (the gauge returns to it), held or not, the component, the root whose gauge is restored, the
+// returned rotation vector.  cost: before, after.  delta: one slot per sweep.
+// a device buffer that is grown when a call needs more (cap: the elements it holds)
+template <typename T>
+struct GrowBuf {
+  DevBuf<T> d;
+  int64_t cap = 0;
+  operator T *() const { return d; }
+};
+struct RotavgWork {
+  GrowBuf<int> pa, pb, adj_ptr, adj_nbr, adj_edge, n_loops, support, comp, root;
+  GrowBuf<uint8_t> used, kept, finite, fixed;
+  GrowBuf<double> r_rel, Rrel, weight, residual, edge_weight, term, R[2], Rstart, r, cost, delta;
+};
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -569,6 +589,7 @@ struct ba_problem {
   PointWork pts;
   CameraWork cams;
   PairWork pairs;
+  RotavgWork rotavg;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

@@ -722,6 +722,201 @@ def two_view(nlp, x, pairs, *, ransac, ratio=0.8, min_parallax=0.05, refine=None
                 parallax=cand["parallax"], normal=normal, off_plane=off, general=gen, planar=pla, seed_order=seed_order)
 
 
+def _view_graph_args(who, pairs, used=None, weights=None, r=None):
+    """The arguments of the view-graph entries that need no model, checked (ValueError): (a1, b1, used as bytes or None,
+    weights or None, r or None).  A pair of cameras listed twice, in either orientation, is refused."""
+    a1, b1 = _lib._pairs(pairs)
+    n = len(a1)
+    key = np.sort(np.minimum(a1, b1) * (max(int(a1.max()), int(b1.max())) + 1) + np.maximum(a1, b1)) if n else a1
+    if n and (key[1:] == key[:-1]).any():
+        raise ValueError(f"{who}: a pair of cameras is listed twice")
+    if used is not None:
+        used = np.asarray(used)
+        if used.dtype != np.bool_ or used.shape != (n,):
+            raise ValueError(f"{who}: used must be a boolean array of shape ({n},), got dtype {used.dtype}, shape {used.shape}")
+        used = np.ascontiguousarray(used, dtype=np.uint8)
+    if weights is not None:
+        try:
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: weights must be numbers") from None
+        if weights.shape != (n,) or not np.isfinite(weights).all() or (weights < 0).any():
+            raise ValueError(f"{who}: weights must have shape ({n},) and be finite and >= 0")
+    if r is not None:
+        try:
+            r = np.ascontiguousarray(r, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: r must be numbers") from None
+        if r.shape != (n, 3):
+            raise ValueError(f"{who}: r must have shape ({n}, 3), one rotation vector per pair, got {r.shape}")
+    return a1, b1, used, weights, r
+
+
+def _in_range(who, a1, b1, ncams):
+    if a1.size and max(int(a1.max()), int(b1.max())) > int(ncams):
+        raise ValueError(f"{who}: pairs: 1-based cameras must lie in 1..{int(ncams)}, got {max(int(a1.max()), int(b1.max()))}")
+
+
+def _angle(who, key, v):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: {key} (radians) must be a finite number > 0, got {v!r}") from None
+    if not (np.isfinite(f) and f > 0):
+        raise ValueError(f"{who}: {key} (radians) must be a finite number > 0, got {v!r}")
+    return f
+
+
+def rotation_loops(nlp, pairs, r, *, threshold, used=None):
+    """The loop consistency of a view graph (ba_rotation_loops).  pairs (npairs, 2), 1-based cameras; r (npairs, 3): the rotation
+    vector of pair (a, b) with R_b = R R_a, the `r` of relative_pose* and two_view.  For every used pair (a, b) and every camera
+    c for which (a, c) and (b, c) are both used pairs, the rotation around the triangle should be the identity: returns
+    (n_loops, support), the number of triangles of a pair and of those whose angle is <= threshold (radians).  used (npairs,)
+    boolean, default "r is finite" (a pair whose r is not finite is never used); an unused pair gets 0, 0.  nlp supplies the
+    device, the stream and ncams.  Bad arguments, a pair listed twice among them, raise ValueError before any device call."""
+    tau = _angle("rotation_loops", "threshold", threshold)
+    a1, b1, used, _, r = _view_graph_args("rotation_loops", pairs, used=used, r=r)
+    _in_range("rotation_loops", a1, b1, nlp.ncams)
+    n = len(a1)
+    n_loops, support = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.lib().ba_rotation_loops(nlp.handle, n, _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(r), None if used is None else _lib.ptr(used),
+                                            tau, _lib.ptr(n_loops), _lib.ptr(support)))
+    return n_loops, support
+
+
+def view_graph_forest(ncams, pairs, *, used=None, support=None, weights=None, fixed_cameras=None):
+    """The maximum spanning forest of a view graph (ba_view_graph_forest; host only, no device): the used pairs under the total
+    order `support` descending, `weights` descending, pair index ascending, under which the forest is unique.  The root of a
+    component is its lowest fixed camera where it has one, else the camera with the largest sum of the weights of its used
+    pairs, ties to the lowest index.  Returns a dict: `component` (ncams,: the components numbered in the order of their lowest
+    camera, -1 for a camera without a used pair), `parent_pair` (ncams,: the 0-based pair to the parent, -1 for roots and cameras
+    outside the graph), `order` (the 1-based cameras breadth first from the roots, component after component, neighbours
+    ascending), `roots` (1-based, one per component), `n_components`.  Bad arguments raise ValueError."""
+    who = "view_graph_forest"
+    if not isinstance(ncams, (int, np.integer)) or isinstance(ncams, (bool, np.bool_)) or ncams < 0:
+        raise ValueError(f"{who}: ncams must be an integer >= 0, got {ncams!r}")
+    ncams = int(ncams)
+    a1, b1, used, weights, _ = _view_graph_args(who, pairs, used=used, weights=weights)
+    _in_range(who, a1, b1, ncams)
+    n = len(a1)
+    if support is not None:
+        support = np.asarray(support)
+        if support.shape != (n,) or not np.issubdtype(support.dtype, np.integer):
+            raise ValueError(f"{who}: support must be an integer array of shape ({n},), got dtype {support.dtype}, shape {support.shape}")
+        support = np.ascontiguousarray(support, dtype=np.int32)
+    fixed = None if fixed_cameras is None else np.ascontiguousarray(_lib._fixed_set(fixed_cameras, ncams, "fixed_cameras"), dtype=np.uint8)
+    component, parent, order, roots = (np.zeros(ncams, dtype=np.int32), np.zeros(ncams, dtype=np.int64), np.zeros(ncams, dtype=np.int64),
+                                       np.zeros(ncams, dtype=np.int64))
+    n_order, n_comp = C.c_int64(0), C.c_int64(0)
+    opt = lambda a: None if a is None else _lib.ptr(a)  # noqa: E731
+    _lib.check(_lib.lib().ba_view_graph_forest(ncams, n, _lib.ptr(a1), _lib.ptr(b1), opt(used), opt(support), opt(weights), opt(fixed),
+                                               _lib.ptr(component), _lib.ptr(parent), _lib.ptr(order), C.byref(n_order), C.byref(n_comp),
+                                               _lib.ptr(roots)))
+    return dict(component=component, parent_pair=parent, order=order[:n_order.value].copy(), roots=roots[:n_comp.value].copy(),
+                n_components=n_comp.value)
+
+
+LOOPS_KEYS = ("threshold", "min_support")
+
+
+def _rotavg_opts(loops, loss, f_scale, damping, max_sweeps, xtol):
+    """RotavgOpts of the options of average_rotations, or ValueError"""
+    who = "average_rotations"
+    o = _lib.RotavgOpts()
+    loss = "linear" if loss is None else loss
+    if not isinstance(loss, str) or loss not in _lib.LOSSES:
+        raise ValueError(f"{who}: loss must be one of {', '.join(_lib.LOSSES)}, got {loss!r}")
+    o.loss = _lib.LOSSES[loss]
+    if o.loss != 0 and f_scale is None:
+        raise ValueError(f"{who}: f_scale (radians) is required under the loss {loss!r}")
+    o.f_scale = 1.0 if f_scale is None else _angle(who, "f_scale", f_scale)
+    d = 0.8 if damping is None else _opt_float(damping, f"{who}: damping")
+    if not 0 < d <= 1:
+        raise ValueError(f"{who}: damping must lie in (0, 1], got {damping!r}")
+    o.damping = d
+    if max_sweeps is None:
+        max_sweeps = 1000
+    if not isinstance(max_sweeps, (int, np.integer)) or isinstance(max_sweeps, (bool, np.bool_)) or not 1 <= max_sweeps <= 100000:
+        raise ValueError(f"{who}: max_sweeps must be an integer in 1..100000 (or None), got {max_sweeps!r}")
+    o.max_sweeps = int(max_sweeps)
+    o.xtol = 1e-6 if xtol is None else _opt_float(xtol, f"{who}: xtol")
+    o.loops = 0
+    if loops is not None:
+        if not isinstance(loops, dict) or any(k not in LOOPS_KEYS for k in loops) or "threshold" not in loops:
+            raise ValueError(f"{who}: loops must be a dict with the keys {', '.join(LOOPS_KEYS)} (threshold is required), got {loops!r}")
+        o.loops, o.loop_threshold = 1, _angle(who, "loops: threshold", loops["threshold"])
+        ms = loops.get("min_support", 1)
+        if not isinstance(ms, (int, np.integer)) or isinstance(ms, (bool, np.bool_)) or ms < 1:
+            raise ValueError(f"{who}: loops: min_support must be an integer >= 1, got {ms!r}")
+        o.min_support = int(ms)
+    return o
+
+
+def average_rotations(nlp, pairs, r, *, weights=None, used=None, loops=None, r0=None, fixed_cameras=None, loss=None, f_scale=None,
+                      damping=None, max_sweeps=None, xtol=None):
+    """Robust rotation averaging over a view graph (ba_average_rotations): the absolute rotation of every camera from all pairs
+    at once.  pairs (npairs, 2), 1-based cameras; r (npairs, 3): the rotation vector of pair (a, b) with R_b = R R_a, the `r` of
+    relative_pose* and two_view.  All angles are radians.
+    weights (npairs,) >= 0, default 1 (n_inliers is the natural choice).  used (npairs,) boolean, default "r is finite".
+    loops=dict(threshold=, min_support=1): rotation_loops first; a used pair with triangles of which fewer than min_support
+    close is dropped (a pair without a triangle cannot be checked and is kept), and the support becomes the first key of the
+    spanning forest.  loss: a name of LOSSES (default linear) with f_scale = c in radians, required unless the loss is linear.
+    damping in (0, 1], default 0.8; max_sweeps default 1000, at most 100000; xtol default 1e-6, <= 0 runs exactly max_sweeps.
+    r0 (ncams, 3): the start, finite for every camera with a used pair -- a warm start, or with fixed_cameras (1-based or
+    boolean; held at r0, which is then required) a registration against an earlier solve.  Without r0 the start is composed
+    along the maximum spanning forest of the kept pairs from R = I at each root.
+    The sweeps update all cameras at once: each moves by `damping` times the weighted mean of the rotation vectors that its
+    kept pairs ask for, the weights w rho'(theta^2 / c^2).  The host reads the largest step after every 8 sweeps and stops
+    after the first batch that holds a sweep with a step <= xtol.  The gauge is free during the sweeps; afterwards every
+    component without a fixed camera is turned so that its root is back at its start.  The rotations of different components
+    are unrelated to each other.
+    Returns a dict: `r` (ncams, 3; NaN for a camera without a kept pair), `status` (names among _lib.ROTAVG_STATES: "fixed" for
+    a held camera, "root" for the root of a component without one), `component`, `kept` (npairs,), `n_loops` and `support`
+    (with loops), `residual` (npairs,: the angle of R_k R_a R_b' for every pair with a finite r inside one component, else NaN:
+    a dropped pair can be re-admitted by it), `edge_weight` (rho' on kept pairs, else 0), `sweeps`, `delta` (sweeps,),
+    `cost_before`, `cost_after` (half the sum of w c^2 rho over the kept pairs), `counts`.  nlp supplies the device, the stream
+    and ncams.  Bad arguments raise ValueError before any device call."""
+    who = "average_rotations"
+    o = _rotavg_opts(loops, loss, f_scale, damping, max_sweeps, xtol)
+    a1, b1, used, weights, r = _view_graph_args(who, pairs, used=used, weights=weights, r=r)
+    if fixed_cameras is not None:
+        _lib._fixed_set(fixed_cameras, None, "fixed_cameras")
+        if r0 is None and np.asarray(fixed_cameras).size and np.asarray(fixed_cameras).any():
+            raise ValueError(f"{who}: fixed_cameras are held at r0, which is required with them")
+    if r0 is not None:
+        try:
+            r0 = np.ascontiguousarray(r0, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: r0 must be numbers") from None
+        if r0.ndim != 2 or r0.shape[1] != 3:
+            raise ValueError(f"{who}: r0 must have shape (ncams, 3), got {r0.shape}")
+        in_use = np.isfinite(r).all(axis=1) if used is None else (used != 0) & np.isfinite(r).all(axis=1)
+        touched = np.unique(np.concatenate([a1[in_use], b1[in_use]])) - 1
+        if touched.size and (touched.max() >= len(r0) or not np.isfinite(r0[touched]).all()):
+            raise ValueError(f"{who}: r0 must be finite for every camera that has a used pair")
+    ncams, n = nlp.ncams, len(a1)
+    _in_range(who, a1, b1, ncams)
+    if r0 is not None and r0.shape != (ncams, 3):
+        raise ValueError(f"{who}: r0 must have shape ({ncams}, 3), got {r0.shape}")
+    fixed = None if fixed_cameras is None else np.ascontiguousarray(_lib._fixed_set(fixed_cameras, ncams, "fixed_cameras"), dtype=np.uint8)
+    out_r, status, component = np.full((ncams, 3), np.nan), np.zeros(ncams, dtype=np.uint8), np.zeros(ncams, dtype=np.int32)
+    kept, n_loops, support = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    residual, edge_weight = np.full(n, np.nan), np.zeros(n)
+    sweeps, delta, cost = C.c_int32(0), np.zeros(o.max_sweeps), np.zeros(2)
+    counts = np.zeros(len(_lib.ROTAVG_STATES), dtype=np.int64)
+    opt = lambda a: None if a is None else _lib.ptr(a)  # noqa: E731
+    _lib.check(_lib.lib().ba_average_rotations(nlp.handle, n, _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(r), opt(weights), opt(used), opt(r0),
+                                               opt(fixed), C.byref(o), _lib.ptr(out_r), _lib.ptr(status), _lib.ptr(component),
+                                               _lib.ptr(kept), _lib.ptr(n_loops), _lib.ptr(support), _lib.ptr(residual),
+                                               _lib.ptr(edge_weight), C.byref(sweeps), _lib.ptr(delta), _lib.ptr(cost), _lib.ptr(counts)))
+    info = dict(r=out_r, status=np.array(_lib.ROTAVG_STATES)[status], component=component, kept=kept != 0, residual=residual,
+                edge_weight=edge_weight, sweeps=sweeps.value, delta=delta[:sweeps.value].copy(), cost_before=float(cost[0]),
+                cost_after=float(cost[1]), counts={s: int(c) for s, c in zip(_lib.ROTAVG_STATES, counts)})
+    if loops is not None:
+        info.update(n_loops=n_loops, support=support)
+    return info
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

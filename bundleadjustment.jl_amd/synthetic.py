@@ -213,6 +213,68 @@ def add_point_outliers(prob, n_per_point=None, fraction=None, seed=0, r_min=100.
                                fraction, seed, r_min, r_max)
 
 
+def rotation_matrices(v):
+    """(n, 3, 3) rotation matrices of the rotation vectors v (n, 3): Rodrigues, the identity at |v| = 0"""
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 3)
+    th = np.sqrt((v * v).sum(axis=1))
+    k = v / np.where(th > 0, th, 1.0)[:, None]
+    K = np.zeros((len(v), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -k[:, 2], k[:, 1], k[:, 2], -k[:, 0], -k[:, 1], k[:, 0]
+    c, s = np.cos(th)[:, None, None], np.sin(th)[:, None, None]
+    return c * np.eye(3) + s * K + (1.0 - c) * k[:, :, None] * k[:, None, :]
+
+
+def rotation_vectors(M):
+    """(n, 3) rotation vectors of the rotation matrices M (n, 3, 3) by the rule of _lib.rotation_vector, all at once"""
+    M = np.asarray(M, dtype=np.float64).reshape(-1, 3, 3)
+    n = len(M)
+    w = np.stack([M[:, 2, 1] - M[:, 1, 2], M[:, 0, 2] - M[:, 2, 0], M[:, 1, 0] - M[:, 0, 1]], axis=1)
+    wn = np.sqrt((w * w).sum(axis=1))
+    co = 0.5 * (np.trace(M, axis1=1, axis2=2) - 1.0)
+    th = np.arctan2(0.5 * wn, co)
+    out = np.tile([1e-12, 0.0, 0.0], (n, 1))
+    near = (th >= 1e-12) & (co >= 0)
+    out[near] = (th[near] / wn[near])[:, None] * w[near]
+    far = np.flatnonzero((th >= 1e-12) & (co < 0))
+    if far.size:  # the axis from the row of the largest diagonal entry of the symmetric part, with the sign of w
+        F, cf = M[far], co[far]
+        i = np.argmax(np.diagonal(F, axis1=1, axis2=2), axis=1)
+        rows = np.arange(len(far))
+        ki = np.sqrt((F[rows, i, i] - cf) / (1.0 - cf))
+        k = 0.5 * (F[rows, i, :] + F[rows, :, i]) / ((1.0 - cf) * ki)[:, None]
+        k[rows, i] = ki
+        k /= np.sqrt((k * k).sum(axis=1))[:, None]
+        k[(k * w[far]).sum(axis=1) < 0] *= -1.0
+        out[far] = th[far, None] * k
+    return out
+
+
+def relative_rotations(x, npnts, pairs, noise=0.0, outlier_fraction=0.0, seed=0):
+    """A view graph for rotation averaging from the cameras of x (layout [points; cameras]): (r, gross).  r (npairs, 3) is the
+    rotation vector of pair (a, b) -- pairs (npairs, 2), 1-based cameras -- with R_b = R R_a: the true R_b R_a' multiplied on the
+    left by Exp of a normal vector of standard deviation `noise` (radians).  The share `outlier_fraction` of the pairs (rounded
+    down, drawn without replacement) is multiplied instead by a rotation about a uniform axis by an angle uniform in
+    30..180 degrees; gross (npairs,) marks them.  Rotation vectors are written by the rule of _lib.rotation_vector."""
+    a1, b1 = _lib._pairs(pairs)
+    cams = np.asarray(x, dtype=np.float64)[3 * int(npnts):].reshape(-1, 9)
+    if a1.size and max(a1.max(), b1.max()) > len(cams):
+        raise ValueError(f"relative_rotations: pairs name camera {max(a1.max(), b1.max())} of {len(cams)}")
+    if not (np.isfinite(noise) and noise >= 0 and 0 <= outlier_fraction <= 1):
+        raise ValueError(f"relative_rotations: noise >= 0 and outlier_fraction in 0..1, got {noise!r}, {outlier_fraction!r}")
+    rng = np.random.default_rng(seed)
+    n = len(a1)
+    R = rotation_matrices(cams[:, :3])
+    rel = R[b1 - 1] @ np.transpose(R[a1 - 1], (0, 2, 1))
+    left = rotation_matrices(rng.normal(0.0, 1.0, (n, 3)) * noise)
+    gross = np.zeros(n, dtype=bool)
+    gross[rng.choice(n, size=int(outlier_fraction * n), replace=False)] = True
+    axis = rng.normal(size=(n, 3))
+    axis /= np.linalg.norm(axis, axis=1)[:, None]
+    angle = rng.uniform(np.pi / 6, np.pi, size=n)
+    left[gross] = rotation_matrices(axis * angle[:, None])[gross]
+    return rotation_vectors(left @ rel), gross
+
+
 def shuffle_cameras(prob, seed=0, sigma=None):
     """The same problem with its cameras renumbered at random: (problem, sigma) with camera c of `prob` called sigma[c]
     (0-based) in the result; observations stay in BAL order (by point, then by the NEW camera number).  A BAL file promises

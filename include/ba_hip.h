@@ -1040,6 +1040,81 @@ int ba_homography_pose(ba_problem *p, const double *x /* nvar, host: only (k1, k
                        double *pose /* npairs x 2 x 6: r, unit t */, double *normal /* npairs x 2 x 3 or NULL */,
                        int32_t *support /* npairs x 2 or NULL */);
 
+/* ---- rotation averaging over the view graph (an extension) -----------------------------------------------------------
+ * A view graph is a list of camera pairs with a relative rotation each, some of them wrong.  Pair k is (a, b), 1-based cameras;
+ * r_rel[k] is the rotation vector of R_k with R_b = R_k R_a, the r that ba_relative_pose* return.  R_{i->j} is R_k where the pair
+ * is listed as (i, j) and R_k' where it is listed as (j, i).  All angles are radians.  The angle of a rotation matrix M is
+ * atan2(|w| / 2, (tr M - 1) / 2), w its skew part (the rule of ba_resect_cameras' rotation vector).  Every entry refuses, on the
+ * host and before any device call (BA_ERR_ARG): a camera outside 1..ncams, a pair of one camera, a pair of cameras listed twice
+ * in either orientation.  used: one byte per pair or NULL (all); a pair whose r_rel is not finite is never used.
+ * ba_rotation_loops: for every used pair k = (a, b) and every camera c for which (a, c) and (b, c) are both used pairs,
+ * L = R_{c->a} R_{b->c} R_{a->b}; n_loops[k] counts these triangles and support[k] those with angle L <= threshold (finite, > 0).
+ * An unused pair gets 0, 0.  One wave per pair over a CSR adjacency sorted by neighbour; integer counts, no atomics.
+ * ba_view_graph_forest: host only, no handle, no device.  The maximum spanning forest of the used pairs under the total order
+ * support descending (NULL: all equal), weight descending (NULL: all 1; finite, >= 0), pair index ascending -- unique under that
+ * order.  component[c]: the components numbered 0, 1, .. in the order of their lowest camera, -1 for a camera without a used
+ * pair.  The root of a component: its lowest fixed camera (fixed: one byte per camera or NULL) where it has one, else the camera
+ * with the largest sum of the weights of its used pairs (summed in pair order), ties to the lowest index.  parent_pair[c]: the
+ * 0-based pair that joins c to its parent, -1 for roots and cameras outside the graph.  order (n_order entries, 1-based): the
+ * cameras breadth first from the roots, component after component, the neighbours of a camera in ascending order.  roots
+ * (n_components entries, 1-based).
+ * ba_average_rotations: the absolute rotation of every camera from all pairs at once, R_b ~ R_k R_a.
+ *  1. kept = used.  With opts->loops != 0: ba_rotation_loops at opts->loop_threshold first; a used pair with n_loops > 0 and
+ *     support < min_support (<= 0: 1) is dropped; a pair without a triangle cannot be checked and is kept.
+ *  2. The forest of the kept pairs (key: the support with loops, else the weight alone; the fixed cameras).
+ *  3. Start: r0 != NULL: Exp of r0 (finite for every camera with a used pair, else BA_ERR_ARG).  r0 == NULL: the root gets I and
+ *     a child R_{parent->child} R_parent along the forest.  fixed cameras are held at r0, which is then required.
+ *  4. Sweeps, simultaneous over the cameras (one wave per camera reads R_in, writes R_out).  For camera i and every kept pair e with
+ *     neighbour j: P = R_{j->i} R_j, v_e = Log of P R_i', theta_e = |v_e|, omega_e = w_e rho'(theta_e^2 / c^2) with the loss of
+ *     ba_lm_set_loss (c = f_scale in radians).  delta_i = sum omega_e v_e / sum omega_e, R_i <- Exp of (damping delta_i) times R_i; a
+ *     fixed camera, or one with sum omega = 0 (or NaN), keeps its R.  Log is theta w / |w| with the branch near pi of the
+ *     rotation-vector rule and 0 for theta < 1e-12; Exp is Rodrigues, I at 0.  The sums are taken in a fixed order.
+ *     delta[s] = the largest |damping delta_i| of sweep s.  damping in (0, 1] (0: 0.8): below 1 it removes the eigenvalue -1 that
+ *     a bipartite graph gives the simultaneous update.
+ *  5. The host launches batches of min(8, remaining) sweeps and reads their delta; it stops after the first batch that holds a
+ *     sweep with delta <= xtol (xtol <= 0: exactly max_sweeps sweeps; max_sweeps <= 0: 1000, at most 100000).  The result is the
+ *     state after that whole batch; *sweeps is their number, delta holds that many values (room for max_sweeps, or NULL).
+ *  6. The gauge is free during the sweeps.  Afterwards every component without a fixed camera is multiplied on the right by
+ *     R_root' R_root,start: its root returns to its start.  The rotations of two components are unrelated.
+ *  7. residual[k] = the angle of R_k R_a R_b' for every pair with a finite r_rel whose cameras lie in one component, else NaN (a
+ *     dropped pair can be re-admitted by it); edge_weight[k] = rho' on a kept pair, else 0.  cost[0] at the start and cost[1] at
+ *     the result: the sum over the kept pairs of w c^2 rho(theta^2 / c^2) / 2.  r (3 per camera) by the rotation-vector rule
+ *     ((1e-12, 0, 0) for the identity), NaN for a camera outside the graph.
+ * status: BA_RA_ISOLATED -- no kept pair; BA_RA_FIXED -- held at r0 (the root of its component or not); BA_RA_ROOT -- the
+ * root of a component without a fixed camera; BA_RA_OK.  counts: cameras per state.  n_loops and support (NULL, or npairs: 0 without loops).
+ * Deterministic: two calls give the same bits; the maximum of a sweep is an unsigned 64-bit atomic maximum on the bits of a
+ * non-negative double, which does not depend on the order.  The next ba_lm_step / ba_lm_solve gives the bits it gives without
+ * the call.  A simultaneous update needs sweeps growing with the square of the graph's diameter.
+ * Out of scope: translation averaging, camera centres, a linear solve of the step, Float32, several ranks. */
+enum { BA_RA_OK = 0, BA_RA_ROOT = 1, BA_RA_FIXED = 2, BA_RA_ISOLATED = 3, BA_RA_STATES = 4 };
+typedef struct ba_rotavg_opts {
+  int loss;              /* BA_LOSS_* */
+  int max_sweeps;        /* <= 0: 1000; at most 100000 */
+  int loops;             /* != 0: the loop filter of step 1 */
+  int min_support;       /* <= 0: 1 */
+  double f_scale;        /* c, radians; finite and > 0 unless the loss is linear */
+  double damping;        /* (0, 1]; 0: 0.8 */
+  double xtol;           /* radians; <= 0: exactly max_sweeps sweeps */
+  double loop_threshold; /* radians; finite and > 0 with loops */
+} ba_rotavg_opts;
+int ba_rotation_loops(ba_problem *p, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                      const double *r_rel /* 3 npairs */, const uint8_t *used /* npairs or NULL */, double threshold,
+                      int32_t *n_loops /* npairs */, int32_t *support /* npairs */);
+int ba_view_graph_forest(int64_t ncams, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                         const uint8_t *used /* npairs or NULL */, const int32_t *support /* npairs or NULL */,
+                         const double *weights /* npairs or NULL */, const uint8_t *fixed /* ncams or NULL */,
+                         int32_t *component /* ncams */, int64_t *parent_pair /* ncams */, int64_t *order /* ncams */,
+                         int64_t *n_order, int64_t *n_components, int64_t *roots /* ncams */);
+int ba_average_rotations(ba_problem *p, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                         const double *r_rel /* 3 npairs */, const double *weights /* npairs or NULL */,
+                         const uint8_t *used /* npairs or NULL */, const double *r0 /* 3 ncams or NULL */,
+                         const uint8_t *fixed /* ncams or NULL */, const ba_rotavg_opts *opts, double *r /* 3 ncams */,
+                         uint8_t *status /* ncams */, int32_t *component /* ncams */, uint8_t *kept /* npairs */,
+                         int32_t *n_loops /* npairs or NULL */, int32_t *support /* npairs or NULL */,
+                         double *residual /* npairs */, double *edge_weight /* npairs */, int32_t *sweeps,
+                         double *delta /* max_sweeps or NULL */, double *cost /* 2 or NULL */,
+                         int64_t *counts /* BA_RA_STATES or NULL */);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

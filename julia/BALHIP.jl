@@ -602,3 +602,113 @@ function refine_relative_pose(nlp, x :: Vector{Float64}, pairs_a :: Vector{Int64
   end
   return pose, state, bytes .!= 0, cost, n_inliers, n_consistent, iters, counts
 end
+
+# ---- rotation averaging over the view graph (an extension): include/ba_hip.h, "rotation averaging" ----------------------------
+# Pair k is (pairs_a[k], pairs_b[k]), 1-based cameras; r (3 x npairs) is the rotation vector of R_k with R_b = R_k R_a, the r of
+# relative_pose.  All angles are radians.  A pair of cameras listed twice, in either orientation, is refused.
+
+# struct ba_rotavg_opts (include/ba_hip.h)
+struct BaRotavgOpts
+  loss :: Cint
+  max_sweeps :: Cint
+  loops :: Cint
+  min_support :: Cint
+  f_scale :: Cdouble
+  damping :: Cdouble
+  xtol :: Cdouble
+  loop_threshold :: Cdouble
+end
+
+_used_bytes(used, npairs) = used === nothing ? UInt8[] : (length(used) == npairs ? Vector{UInt8}(used) : error("used must hold one entry per pair"))
+_or_null(v, T) = isempty(v) ? Ptr{T}(C_NULL) : pointer(v)
+
+# The loop consistency of the pairs (ba_rotation_loops): per pair the triangles through it among the used pairs and those
+# whose rotation around the triangle is within `threshold` of the identity.  used: nothing ("r is finite") or one Bool per pair.
+function rotation_loops(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}, r :: Matrix{Float64}; threshold :: Real, used = nothing)
+  npairs = length(pairs_a)
+  length(pairs_b) == npairs && size(r) == (3, npairs) || error("rotation_loops: pairs_a, pairs_b of one length and r 3 x npairs")
+  bytes = _used_bytes(used, npairs)
+  n_loops = zeros(Int32, npairs)
+  support = zeros(Int32, npairs)
+  GC.@preserve pairs_a pairs_b r bytes n_loops support begin
+    bacheck(ccall((:ba_rotation_loops, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}, Cdouble, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, npairs, pointer(pairs_a), pointer(pairs_b), pointer(r), _or_null(bytes, UInt8), Cdouble(threshold),
+                  pointer(n_loops), pointer(support)))
+  end
+  return n_loops, support
+end
+
+# The maximum spanning forest of the used pairs (ba_view_graph_forest; host only) under the order support descending, weight
+# descending, pair index ascending.  Returns component (0-based ids in the order of the lowest camera, -1: no used pair),
+# parent_pair (0-based pair, -1: root or outside the graph), order (1-based cameras, breadth first from the roots) and roots
+# (1-based).  fixed: nothing or one Bool per camera (the lowest fixed camera of a component is its root).
+function view_graph_forest(ncams :: Integer, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}; used = nothing,
+                           support :: Vector{Int32} = Int32[], weights :: Vector{Float64} = Float64[], fixed = nothing)
+  npairs = length(pairs_a)
+  length(pairs_b) == npairs || error("view_graph_forest: pairs_a and pairs_b of one length")
+  (isempty(support) || length(support) == npairs) && (isempty(weights) || length(weights) == npairs) ||
+    error("view_graph_forest: support and weights hold one entry per pair")
+  bytes = _used_bytes(used, npairs)
+  held = fixed === nothing ? UInt8[] : (length(fixed) == ncams ? Vector{UInt8}(fixed) : error("fixed must hold one entry per camera"))
+  component = zeros(Int32, ncams)
+  parent_pair = zeros(Int64, ncams)
+  order = zeros(Int64, ncams)
+  roots = zeros(Int64, ncams)
+  n_order = Ref{Int64}(0)
+  n_components = Ref{Int64}(0)
+  GC.@preserve pairs_a pairs_b bytes support weights held component parent_pair order roots begin
+    bacheck(ccall((:ba_view_graph_forest, libba), Cint,
+                  (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int64},
+                   Ptr{Int64}, Ref{Int64}, Ref{Int64}, Ptr{Int64}),
+                  Int64(ncams), npairs, pointer(pairs_a), pointer(pairs_b), _or_null(bytes, UInt8), _or_null(support, Int32),
+                  _or_null(weights, Float64), _or_null(held, UInt8), pointer(component), pointer(parent_pair), pointer(order),
+                  n_order, n_components, pointer(roots)))
+  end
+  return component, parent_pair, order[1:n_order[]], roots[1:n_components[]]
+end
+
+# Robust rotation averaging (ba_average_rotations): the absolute rotation of every camera from all pairs at once.  loss is a
+# BA_LOSS_* value with f_scale = c in radians; loop_threshold > 0 runs the loop filter first (a pair with triangles of which
+# fewer than min_support close is dropped); r0 (3 x ncams) is a start of the caller's, required with fixed (one Bool per camera,
+# held at r0).  Returns r (3 x ncams, NaN for a camera without a kept pair), the state of every camera (BA_RA_*), its
+# component, the kept pairs, the loop counts, the residual and the weight of every pair, the sweeps, the largest step of every
+# sweep, the cost before and after, and the cameras per state.  The rotations of different components are unrelated.
+function average_rotations(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}, r :: Matrix{Float64};
+                           weights :: Vector{Float64} = Float64[], used = nothing, loop_threshold :: Real = 0.0,
+                           min_support :: Integer = 1, r0 :: Matrix{Float64} = zeros(3, 0), fixed = nothing, loss :: Integer = 0,
+                           f_scale :: Real = 0.0, damping :: Real = 0.8, max_sweeps :: Integer = 1000, xtol :: Real = 1e-6)
+  npairs = length(pairs_a)
+  ncams = nlp.ncams
+  length(pairs_b) == npairs && size(r) == (3, npairs) || error("average_rotations: pairs_a, pairs_b of one length and r 3 x npairs")
+  isempty(weights) || length(weights) == npairs || error("average_rotations: weights hold one entry per pair")
+  isempty(r0) || size(r0) == (3, ncams) || error("average_rotations: r0 must be 3 x ncams")
+  1 <= max_sweeps <= 100000 || error("average_rotations: max_sweeps in 1..100000")
+  bytes = _used_bytes(used, npairs)
+  held = fixed === nothing ? UInt8[] : (length(fixed) == ncams ? Vector{UInt8}(fixed) : error("fixed must hold one entry per camera"))
+  opts = Ref(BaRotavgOpts(Cint(loss), Cint(max_sweeps), Cint(loop_threshold > 0), Cint(min_support), Cdouble(f_scale), Cdouble(damping),
+                          Cdouble(xtol), Cdouble(loop_threshold)))
+  out = fill(NaN, 3, ncams)
+  status = zeros(UInt8, ncams)
+  component = zeros(Int32, ncams)
+  kept = zeros(UInt8, npairs)
+  n_loops = zeros(Int32, npairs)
+  support = zeros(Int32, npairs)
+  residual = fill(NaN, npairs)
+  edge_weight = zeros(Float64, npairs)
+  sweeps = Ref{Int32}(0)
+  delta = zeros(Float64, max_sweeps)
+  cost = zeros(Float64, 2)
+  counts = zeros(Int64, 4)
+  GC.@preserve pairs_a pairs_b r weights bytes r0 held opts out status component kept n_loops support residual edge_weight delta cost counts begin
+    bacheck(ccall((:ba_average_rotations, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{UInt8},
+                   Ptr{BaRotavgOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                   Ref{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                  nlp.handle, npairs, pointer(pairs_a), pointer(pairs_b), pointer(r), _or_null(weights, Float64), _or_null(bytes, UInt8),
+                  _or_null(r0, Float64), _or_null(held, UInt8), Base.unsafe_convert(Ptr{BaRotavgOpts}, opts), pointer(out),
+                  pointer(status), pointer(component), pointer(kept), pointer(n_loops), pointer(support), pointer(residual),
+                  pointer(edge_weight), sweeps, pointer(delta), pointer(cost), pointer(counts)))
+  end
+  return out, status, component, kept .!= 0, n_loops, support, residual, edge_weight, Int(sweeps[]), delta[1:sweeps[]], cost, counts
+end
