@@ -13,7 +13,7 @@ except ImportError:  # pragma: no cover
     _torch = None
 from . import _lib
 from ._lib import BAArgError, BAError, SQDException, LOSSES, device_count
-from .lm import GenericExecutionStats, Levenberg_Marquardt, lm_step, covariance, refine_points, refine_cameras, pair_matches, relative_pose, relative_pose_five_point, refine_relative_pose, five_point, p3p, homography, decompose_homography, homography_pose, two_view, rotation_loops, view_graph_forest, average_rotations, schur_pattern, schur_memory, set_ordering, schur_ordering_used
+from .lm import GenericExecutionStats, Levenberg_Marquardt, lm_step, covariance, refine_points, refine_cameras, pair_matches, relative_pose, relative_pose_five_point, refine_relative_pose, five_point, p3p, homography, decompose_homography, homography_pose, two_view, rotation_loops, view_graph_forest, average_rotations, translation_loops, average_translations, translation_directions, camera_translations, schur_pattern, schur_memory, set_ordering, schur_ordering_used
 from ._lib import schur_ordering, tie_intrinsics, compose_relative
 from .model import BALNLPModel, FeasibilityResidual
 from .readfiles import name, readfile
@@ -21,5 +21,5 @@ from . import synthetic
 from . import parallel
 
 __all__ = ["BALNLPModel", "FeasibilityResidual", "Levenberg_Marquardt", "GenericExecutionStats", "readfile", "name",
-           "BAError", "BAArgError", "SQDException", "LOSSES", "device_count", "synthetic", "parallel", "lm_step", "covariance", "refine_points", "refine_cameras", "pair_matches", "relative_pose", "relative_pose_five_point", "refine_relative_pose", "five_point", "p3p", "homography", "decompose_homography", "homography_pose", "two_view", "rotation_loops", "view_graph_forest", "average_rotations", "schur_pattern", "schur_memory", "set_ordering", "schur_ordering_used",
+           "BAError", "BAArgError", "SQDException", "LOSSES", "device_count", "synthetic", "parallel", "lm_step", "covariance", "refine_points", "refine_cameras", "pair_matches", "relative_pose", "relative_pose_five_point", "refine_relative_pose", "five_point", "p3p", "homography", "decompose_homography", "homography_pose", "two_view", "rotation_loops", "view_graph_forest", "average_rotations", "translation_loops", "average_translations", "translation_directions", "camera_translations", "schur_pattern", "schur_memory", "set_ordering", "schur_ordering_used",
            "schur_ordering", "tie_intrinsics", "compose_relative"]

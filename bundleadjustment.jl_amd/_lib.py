@@ -63,6 +63,13 @@ class RotavgOpts(C.Structure):
                 ("damping", C.c_double), ("xtol", C.c_double), ("loop_threshold", C.c_double)]
 
 
+class TransavgOpts(C.Structure):
+    """ba_transavg_opts"""
+    _fields_ = [("loss", C.c_int), ("loops", C.c_int), ("min_support", C.c_int), ("max_iterations", C.c_int), ("max_cg", C.c_int),
+                ("f_scale", C.c_double), ("loop_threshold", C.c_double), ("min_ratio", C.c_double), ("ftol", C.c_double),
+                ("cg_tol", C.c_double), ("lambda0", C.c_double)]
+
+
 LOG_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                      C.c_double, C.c_int)
 COMM_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p)
@@ -92,6 +99,7 @@ SYMBOLS = [
     "ba_ransac_points", "ba_ransac_points_dev",
     "ba_homography", "ba_decompose_homography", "ba_homography_pose",
     "ba_rotation_loops", "ba_view_graph_forest", "ba_average_rotations",
+    "ba_translation_loops", "ba_average_translations", "ba_transavg_lm_decide",
 ]
 
 _lib = None
@@ -194,6 +202,9 @@ def lib():
     L.ba_rotation_loops.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, vp, vp]
     L.ba_view_graph_forest.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ba_average_rotations.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RotavgOpts)] + [vp] * 12
+    L.ba_translation_loops.argtypes = L.ba_rotation_loops.argtypes
+    L.ba_average_translations.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(TransavgOpts)] + [vp] * 13
+    L.ba_transavg_lm_decide.argtypes = [C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, vp, vp]
     _lib = L
     return L
 
@@ -694,6 +705,8 @@ def pair_refine_opts(max_iter=None, xtol=None, lam0=None, loss=None, f_scale=1.0
 
 # states of ba_average_rotations (BA_RA_*), per camera
 ROTAVG_STATES = ("ok", "root", "fixed", "isolated")
+# states of ba_average_translations (BA_TA_*), per camera: the same four
+TRANSAVG_STATES = ROTAVG_STATES
 
 
 def _pairs(pairs, ncams=None):

@@ -232,6 +232,7 @@ enum ProfClass {
   PC_RANSAC_POINTS,   // consensus stage before the triangulation (ba_ransac_points): k_cam_pre, k_ransac_points, k_ransac_mask_info
   PC_HOMOGRAPHY,      // homography of camera pairs (ba_homography): k_pair_rays, k_pair_hypotheses_h, k_pair_select_h, k_pair_fit_h
   PC_ROTAVG,          // "k_rotation_averaging" (ba_rotation_loops, ba_average_rotations): k_rotation_loops, k_rotavg_sweep, k_rotavg_edges, k_rotavg_sum, k_rotavg_finish
+  PC_TRANSAVG,        // "k_translation_averaging" (ba_translation_loops, ba_average_translations): every kernel of ba_transavg_kernels.hip
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -522,6 +523,37 @@ struct RotavgWork {
   GrowBuf<double> r_rel, Rrel, weight, residual, edge_weight, term, R[2], Rstart, r, cost, delta;
 };
 
+// b <- at least n elements
+template <typename T>
+inline int grow(GrowBuf<T> &b, int64_t n) {
+  if (b.cap >= n && b.d) return BA_OK;
+  b.cap = 0;
+  BA_CHECK(b.d.alloc(n));
+  b.cap = n > 0 ? n : 1;
+  return BA_OK;
+}
+
+// b <- the host vector h
+template <typename T>
+inline int put(GrowBuf<T> &b, const std::vector<T> &h, hipStream_t st) {
+  BA_CHECK(grow(b, (int64_t)h.size()));
+  if (!h.empty()) BA_HIP_CHECK(hipMemcpyAsync((T *)b, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+  return BA_OK;
+}
+
+// ---- translation averaging over the view graph (ba_translation_loops, ba_average_translations; ba_transavg_kernels.hip)
+// The per-call device buffers.  Per pair: its cameras (0-based), the direction as given and normalised, the flags used / kept /
+// "the direction is usable", the weight, the loop counts, the two linearisations (current and trial: A 6, g 3, the cost term),
+// the residual and rho'.  Per camera: the CSR adjacency, the two positions (current, trial), held or not, the component, the
+// gathered gradient, lambda diag H, the preconditioner (6), "takes part in the solve", and the vectors of the conjugate
+// gradient (x, r, z, p, q: 3 each) with the per-camera terms of its dot products.  sc: the scalars of a solve (rz, |r0|_M,
+// alpha, the bound |r|_M has to reach); st: done, iterations; cost: before, after, trial.
+struct TransavgWork {
+  GrowBuf<int> pa, pb, adj_ptr, adj_nbr, adj_edge, n_loops, support, comp, st;
+  GrowBuf<uint8_t> used, kept, finite, fixed, active;
+  GrowBuf<double> dir_in, dir, weight, A[2], g[2], term[2], residual, edge_weight, c[2], gc, dg, Minv, x, r, z, p, q, part, sc, cost;
+};
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -590,6 +622,7 @@ struct ba_problem {
   CameraWork cams;
   PairWork pairs;
   RotavgWork rotavg;
+  TransavgWork transavg;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

@@ -196,24 +196,6 @@ __global__ __launch_bounds__(RA_BLK) void k_rotavg_finish(int ncams, const int *
   r[3 * (int64_t)c] = v[0], r[3 * (int64_t)c + 1] = v[1], r[3 * (int64_t)c + 2] = v[2];
 }
 
-// b <- at least n elements
-template <typename T>
-int grow(GrowBuf<T> &b, int64_t n) {
-  if (b.cap >= n && b.d) return BA_OK;
-  b.cap = 0;
-  BA_CHECK(b.d.alloc(n));
-  b.cap = n > 0 ? n : 1;
-  return BA_OK;
-}
-
-// b <- the host vector h
-template <typename T>
-int put(GrowBuf<T> &b, const std::vector<T> &h, hipStream_t st) {
-  BA_CHECK(grow(b, (int64_t)h.size()));
-  if (!h.empty()) BA_HIP_CHECK(hipMemcpyAsync((T *)b, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return BA_OK;
-}
-
 // what both entries check and upload: the pairs (0-based), "r is finite", used = the caller's (or all) and finite, the table of
 // the relative rotations
 struct RotavgInput {

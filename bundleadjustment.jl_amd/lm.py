@@ -917,6 +917,191 @@ def average_rotations(nlp, pairs, r, *, weights=None, used=None, loops=None, r0=
     return info
 
 
+def _directions(who, directions, n):
+    try:
+        d = np.ascontiguousarray(directions, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: directions must be numbers") from None
+    if d.shape != (n, 3):
+        raise ValueError(f"{who}: directions must have shape ({n}, 3), one baseline direction per pair, got {d.shape}")
+    return d
+
+
+def translation_directions(pairs, t, r_abs):
+    """The baseline directions of a view graph in the world frame, on the host: d_k = -R_b' t_k for pair k = (a, b), with the unit
+    t of relative_pose* and two_view (P_b = R P_a + t) and r_abs (ncams, 3) the rotation vectors of average_rotations.  d_k points
+    from the centre of a to the centre of b.  A pair whose t, or whose camera b's rotation, is not finite gets NaN (such a pair is
+    never used by average_translations).  Returns (npairs, 3)."""
+    who = "translation_directions"
+    a1, b1 = _lib._pairs(pairs)
+    try:
+        t, r_abs = np.asarray(t, dtype=np.float64), np.asarray(r_abs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: t and r_abs must be numbers") from None
+    if t.shape != (len(a1), 3) or r_abs.ndim != 2 or r_abs.shape[1] != 3:
+        raise ValueError(f"{who}: t must have shape ({len(a1)}, 3) and r_abs (ncams, 3), got {t.shape}, {r_abs.shape}")
+    _in_range(who, a1, b1, len(r_abs))
+    from .synthetic import rotation_matrices
+    rb = r_abs[b1 - 1]
+    ok = np.isfinite(rb).all(axis=1)
+    R = rotation_matrices(np.where(ok[:, None], rb, 0.0))
+    d = -np.einsum("kji,kj->ki", R, t)
+    d[~ok] = np.nan
+    return d
+
+
+def camera_translations(r_abs, centres):
+    """T = -R C per camera, the translation of the BAL camera model (P = R X + T), from the rotation vectors r_abs (ncams, 3) and
+    the centres (ncams, 3) of average_translations; on the host.  Returns (ncams, 3)."""
+    who = "camera_translations"
+    try:
+        r_abs, centres = np.asarray(r_abs, dtype=np.float64), np.asarray(centres, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: r_abs and centres must be numbers") from None
+    if r_abs.ndim != 2 or r_abs.shape[1] != 3 or centres.shape != r_abs.shape:
+        raise ValueError(f"{who}: r_abs and centres must both have shape (ncams, 3), got {r_abs.shape}, {centres.shape}")
+    from .synthetic import rotation_matrices
+    ok = np.isfinite(r_abs).all(axis=1)
+    T = -np.einsum("kij,kj->ki", rotation_matrices(np.where(ok[:, None], r_abs, 0.0)), centres)
+    T[~ok] = np.nan
+    return T
+
+
+def translation_loops(nlp, pairs, directions, *, used=None, threshold):
+    """The loop consistency of the baseline directions of a view graph (ba_translation_loops).  pairs (npairs, 2), 1-based
+    cameras; directions (npairs, 3): the direction from the centre of a to the centre of b in the world frame
+    (translation_directions), normalised on the device.  For every used pair (a, b) and every camera c for which (a, c) and
+    (c, b) are both used pairs, the direction a -> b lies on the shorter great-circle arc between the directions a -> c and
+    c -> b: returns (n_loops, support), the number of triangles of a pair that can be checked (a triangle whose other two
+    directions are opposite cannot) and of those whose distance to the arc is <= threshold (radians).  used (npairs,) boolean,
+    default "the direction is finite with a norm >= 1e-12" (another pair is never used); an unused pair gets 0, 0.  nlp supplies
+    the device, the stream and ncams.  Bad arguments, a pair listed twice among them, raise ValueError before any device call."""
+    who = "translation_loops"
+    tau = _angle(who, "threshold", threshold)
+    a1, b1, used, _, _ = _view_graph_args(who, pairs, used=used)
+    d = _directions(who, directions, len(a1))
+    _in_range(who, a1, b1, nlp.ncams)
+    n = len(a1)
+    n_loops, support = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.lib().ba_translation_loops(nlp.handle, n, _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(d), None if used is None else _lib.ptr(used),
+                                               tau, _lib.ptr(n_loops), _lib.ptr(support)))
+    return n_loops, support
+
+
+TRANSLATION_LOOPS_KEYS = ("threshold", "min_support", "min_ratio")
+
+
+def _count(who, key, v, lo, hi):
+    if not isinstance(v, (int, np.integer)) or isinstance(v, (bool, np.bool_)) or not lo <= v <= hi:
+        raise ValueError(f"{who}: {key} must be an integer in {lo}..{hi} (or None), got {v!r}")
+    return int(v)
+
+
+def _transavg_opts(loops, loss, f_scale, max_iterations, ftol, cg_tol, max_cg):
+    """TransavgOpts of the options of average_translations, or ValueError"""
+    who = "average_translations"
+    o = _lib.TransavgOpts()
+    loss = "linear" if loss is None else loss
+    if not isinstance(loss, str) or loss not in _lib.LOSSES:
+        raise ValueError(f"{who}: loss must be one of {', '.join(_lib.LOSSES)}, got {loss!r}")
+    o.loss = _lib.LOSSES[loss]
+    if o.loss != 0 and f_scale is None:
+        raise ValueError(f"{who}: f_scale (chordal units) is required under the loss {loss!r}")
+    o.f_scale = 1.0 if f_scale is None else _angle(who, "f_scale", f_scale)
+    o.max_iterations = 50 if max_iterations is None else _count(who, "max_iterations", max_iterations, 1, 100000)
+    o.max_cg = 500 if max_cg is None else _count(who, "max_cg", max_cg, 1, 100000)
+    for key, v, default in (("ftol", ftol, 1e-10), ("cg_tol", cg_tol, 1e-6)):
+        f = default if v is None else _opt_float(v, f"{who}: {key}")
+        if not f > 0:
+            raise ValueError(f"{who}: {key} must be a finite number > 0 (or None), got {v!r}")
+        setattr(o, key, f)
+    o.lambda0 = 1e-3
+    o.loops = 0
+    if loops is not None:
+        if not isinstance(loops, dict) or any(k not in TRANSLATION_LOOPS_KEYS for k in loops) or "threshold" not in loops:
+            raise ValueError(f"{who}: loops must be a dict with the keys {', '.join(TRANSLATION_LOOPS_KEYS)} (threshold is required), "
+                             f"got {loops!r}")
+        o.loops, o.loop_threshold = 1, _angle(who, "loops: threshold", loops["threshold"])
+        o.min_support = _count(who, "loops: min_support", loops.get("min_support", 1), 1, 2 ** 31 - 1)
+        ratio = _opt_float(loops.get("min_ratio", 0.34), f"{who}: loops: min_ratio")
+        if ratio is None or not 0 <= ratio <= 1:
+            raise ValueError(f"{who}: loops: min_ratio must lie in [0, 1] (0: off), got {loops.get('min_ratio')!r}")
+        o.min_ratio = ratio
+    return o
+
+
+def average_translations(nlp, pairs, directions, *, weights=None, used=None, loops=None, c0=None, fixed_cameras=None, loss=None,
+                         f_scale=None, max_iterations=None, ftol=None, cg_tol=None, max_cg=None):
+    """Robust translation averaging over a view graph (ba_average_translations): the centre of every camera from the baseline
+    directions of all pairs at once, up to a shift and a scale per component.  pairs (npairs, 2), 1-based cameras; directions
+    (npairs, 3): the direction from the centre of a to the centre of b in the world frame (translation_directions), normalised
+    on the device.
+    weights (npairs,) >= 0, default 1.  used (npairs,) boolean, default "the direction is finite with a norm >= 1e-12".
+    loops=dict(threshold=, min_support=1, min_ratio=0.34): translation_loops first; a used pair with checked triangles is
+    dropped if fewer than min_support, or fewer than min_ratio of them, close (a pair without a checked triangle is kept), and
+    the support becomes the first key of the spanning forest.  loss: a name of LOSSES (default linear) on the chord
+    |u^ - d|, with f_scale = c in its units (about radians for small angles), required unless the loss is linear.
+    c0 (ncams, 3): the start, finite for every camera with a used pair -- a warm start, or with fixed_cameras (1-based or
+    boolean; held at c0, which is then required) a registration against an earlier solve.  Without c0 the root of every
+    component is at 0 and the other cameras follow along the maximum spanning forest of the kept pairs with baselines of length 1.
+    The solve is Levenberg-Marquardt on F = sum w c^2 rho(|u^_k - d_k|^2 / c^2) / 2, u_k = C_b - C_a: every iteration solves
+    (H + lambda diag H) delta = -g on the device by conjugate gradients under the cameras' 3 x 3 diagonal blocks, to
+    |r|_M <= cg_tol |r0|_M (default 1e-6) or max_cg iterations (default 500); a trial is accepted iff F decreases
+    (lambda / 3, else 4 lambda); it stops when F changes by at most ftol F (default 1e-10), after max_iterations (default 50) or
+    when lambda passes 1e8.  Afterwards every component without a fixed camera is moved so that its root is back at its start
+    and scaled about it so that the mean length of its kept baselines is that of the start.  The centres of different
+    components are unrelated to each other.
+    Returns a dict: `c` (ncams, 3; NaN for a camera without a kept pair), `status` (names among _lib.TRANSAVG_STATES),
+    `component`, `kept` (npairs,), `n_loops` and `support` (with loops), `residual` (npairs,: the angle between C_b - C_a and the
+    direction for every pair with a usable direction inside one component, else NaN: a dropped pair can be re-admitted by it),
+    `edge_weight` (rho' on kept pairs, else 0), `iterations`, `cg_iterations` (their total), `trace` (iterations, 4: the cost of
+    the trial, lambda, the conjugate-gradient iterations, accepted), `cost_before`, `cost_after`, `counts`.  nlp supplies the
+    device, the stream and ncams.  Bad arguments raise ValueError before any device call."""
+    who = "average_translations"
+    o = _transavg_opts(loops, loss, f_scale, max_iterations, ftol, cg_tol, max_cg)
+    a1, b1, used, weights, _ = _view_graph_args(who, pairs, used=used, weights=weights)
+    d = _directions(who, directions, len(a1))
+    if fixed_cameras is not None:
+        _lib._fixed_set(fixed_cameras, None, "fixed_cameras")
+        if c0 is None and np.asarray(fixed_cameras).size and np.asarray(fixed_cameras).any():
+            raise ValueError(f"{who}: fixed_cameras are held at c0, which is required with them")
+    if c0 is not None:
+        try:
+            c0 = np.ascontiguousarray(c0, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: c0 must be numbers") from None
+        if c0.ndim != 2 or c0.shape[1] != 3:
+            raise ValueError(f"{who}: c0 must have shape (ncams, 3), got {c0.shape}")
+        with np.errstate(invalid="ignore", over="ignore"):
+            usable = np.isfinite(d).all(axis=1) & (np.sqrt((d * d).sum(axis=1)) >= 1e-12)
+        in_use = usable if used is None else (used != 0) & usable
+        touched = np.unique(np.concatenate([a1[in_use], b1[in_use]])) - 1
+        if touched.size and (touched.max() >= len(c0) or not np.isfinite(c0[touched]).all()):
+            raise ValueError(f"{who}: c0 must be finite for every camera that has a used pair")
+    ncams, n = nlp.ncams, len(a1)
+    _in_range(who, a1, b1, ncams)
+    if c0 is not None and c0.shape != (ncams, 3):
+        raise ValueError(f"{who}: c0 must have shape ({ncams}, 3), got {c0.shape}")
+    fixed = None if fixed_cameras is None else np.ascontiguousarray(_lib._fixed_set(fixed_cameras, ncams, "fixed_cameras"), dtype=np.uint8)
+    out_c, status, component = np.full((ncams, 3), np.nan), np.zeros(ncams, dtype=np.uint8), np.zeros(ncams, dtype=np.int32)
+    kept, n_loops, support = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    residual, edge_weight = np.full(n, np.nan), np.zeros(n)
+    its, cg, trace, cost = C.c_int32(0), C.c_int32(0), np.zeros((o.max_iterations, 4)), np.zeros(2)
+    counts = np.zeros(len(_lib.TRANSAVG_STATES), dtype=np.int64)
+    opt = lambda a: None if a is None else _lib.ptr(a)  # noqa: E731
+    _lib.check(_lib.lib().ba_average_translations(nlp.handle, n, _lib.ptr(a1), _lib.ptr(b1), _lib.ptr(d), opt(weights), opt(used), opt(c0),
+                                                  opt(fixed), C.byref(o), _lib.ptr(out_c), _lib.ptr(status), _lib.ptr(component),
+                                                  _lib.ptr(kept), _lib.ptr(n_loops), _lib.ptr(support), _lib.ptr(residual),
+                                                  _lib.ptr(edge_weight), C.byref(its), C.byref(cg), _lib.ptr(trace), _lib.ptr(cost),
+                                                  _lib.ptr(counts)))
+    info = dict(c=out_c, status=np.array(_lib.TRANSAVG_STATES)[status], component=component, kept=kept != 0, residual=residual,
+                edge_weight=edge_weight, iterations=its.value, cg_iterations=cg.value, trace=trace[:its.value].copy(),
+                cost_before=float(cost[0]), cost_after=float(cost[1]), counts={s: int(c) for s, c in zip(_lib.TRANSAVG_STATES, counts)})
+    if loops is not None:
+        info.update(n_loops=n_loops, support=support)
+    return info
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

@@ -275,6 +275,34 @@ def relative_rotations(x, npnts, pairs, noise=0.0, outlier_fraction=0.0, seed=0)
     return rotation_vectors(left @ rel), gross
 
 
+def relative_translations(x, npnts, pairs, noise=0.0, outlier_fraction=0.0, seed=0):
+    """The baselines of a view graph for translation averaging from the cameras of x (layout [points; cameras]): (t, gross).
+    t (npairs, 3) is the unit translation of pair (a, b) -- pairs (npairs, 2), 1-based cameras -- in the frame and with the sign
+    of relative_pose: P_b = R P_a + |baseline| t, that is T_b - R_b R_a' T_a normalised, which is -R_b (C_b - C_a) / |C_b - C_a|
+    in the cameras' centres.  A normal vector of standard deviation `noise` (radians, for small values) is added to the unit
+    vector, which is normalised again.  The share `outlier_fraction` of the pairs (rounded down, drawn without replacement) gets
+    a direction uniform on the sphere instead; gross (npairs,) marks them."""
+    a1, b1 = _lib._pairs(pairs)
+    cams = np.asarray(x, dtype=np.float64)[3 * int(npnts):].reshape(-1, 9)
+    if a1.size and max(a1.max(), b1.max()) > len(cams):
+        raise ValueError(f"relative_translations: pairs name camera {max(a1.max(), b1.max())} of {len(cams)}")
+    if not (np.isfinite(noise) and noise >= 0 and 0 <= outlier_fraction <= 1):
+        raise ValueError(f"relative_translations: noise >= 0 and outlier_fraction in 0..1, got {noise!r}, {outlier_fraction!r}")
+    rng = np.random.default_rng(seed)
+    n = len(a1)
+    R = rotation_matrices(cams[:, :3])
+    rel = R[b1 - 1] @ np.transpose(R[a1 - 1], (0, 2, 1))
+    t = cams[b1 - 1, 3:6] - np.einsum("kij,kj->ki", rel, cams[a1 - 1, 3:6])
+    t = t / np.linalg.norm(t, axis=1)[:, None]
+    t = t + rng.normal(0.0, 1.0, (n, 3)) * noise
+    t = t / np.linalg.norm(t, axis=1)[:, None]
+    gross = np.zeros(n, dtype=bool)
+    gross[rng.choice(n, size=int(outlier_fraction * n), replace=False)] = True
+    wild = rng.normal(size=(n, 3))
+    t[gross] = (wild / np.linalg.norm(wild, axis=1)[:, None])[gross]
+    return t, gross
+
+
 def shuffle_cameras(prob, seed=0, sigma=None):
     """The same problem with its cameras renumbered at random: (problem, sigma) with camera c of `prob` called sigma[c]
     (0-based) in the result; observations stay in BAL order (by point, then by the NEW camera number).  A BAL file promises

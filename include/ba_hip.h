@@ -1115,6 +1115,92 @@ int ba_average_rotations(ba_problem *p, int64_t npairs, const int64_t *pair_a1, 
                          double *delta /* max_sweeps or NULL */, double *cost /* 2 or NULL */,
                          int64_t *counts /* BA_RA_STATES or NULL */);
 
+/* ---- translation averaging over the view graph (an extension) --------------------------------------------------------
+ * Camera centres from the baseline directions of the pairs.  Pair k is (a, b), 1-based cameras; dir[k] (3 per pair) is the
+ * direction of the baseline in the world frame, d_k ~ (C_b - C_a) / |C_b - C_a|: -R_b' t_k with the unit t of ba_relative_pose*
+ * (P_b = R P_a + t) and the R_b of ba_average_rotations.  dir need not be normalised: d = dir / sqrt((x x + y y) + z z) on the
+ * device.  The direction from i to j is d_k where the pair is listed as (i, j) and -d_k where it is listed as (j, i).  Angles are
+ * radians; the angle between two vectors is atan2(|x cross y|, x . y).  Every entry refuses, on the host and before any device
+ * call (BA_ERR_ARG), what the rotation section refuses: a camera outside 1..ncams, a pair of one camera, a pair of cameras listed
+ * twice in either orientation.  used: one byte per pair or NULL (all); a pair whose dir is not finite or has a norm < 1e-12 is
+ * never used.
+ * ba_translation_loops: for every used pair k = (a, b) and every camera c for which (a, c) and (c, b) are both used pairs, with
+ * d1 the direction a -> c and d2 the direction c -> b, d_k lies in the plane of the triangle between the two: e = the angular
+ * distance of d_k to the shorter great-circle arc from d1 to d2.  n = d1 cross d2.  |n| < 1e-6 and d1 . d2 > 0: the arc is the
+ * point d1, e = the angle between d_k and d1.  |n| < 1e-6 and d1 . d2 <= 0: the triangle cannot be checked and is not counted.
+ * Otherwise n^ = n / |n|, q = d_k - (d_k . n^) n^; if (d1 cross q) . n^ >= 0 and (q cross d2) . n^ >= 0 then
+ * e = asin min(1, |d_k . n^|), else e = min(angle(d_k, d1), angle(d_k, d2)).  n_loops[k] counts the checked triangles,
+ * support[k] those with e <= threshold (finite, > 0).  An unused pair gets 0, 0.  One wave per pair over a CSR adjacency sorted
+ * by neighbour; integer counts, no atomics.
+ * ba_average_translations: the centre of every camera from all pairs at once, up to the gauge (a shift and a scale per
+ * component).
+ *  1. kept = used.  With opts->loops != 0: ba_translation_loops at opts->loop_threshold first; a used pair with n_loops > 0 is
+ *     dropped if support < min_support (<= 0: 1) or if (double)support < min_ratio * (double)n_loops -- one IEEE double product
+ *     and one comparison of doubles; min_ratio in [0, 1], 0: off.  A pair without a checked triangle is kept.
+ *  2. The forest of the kept pairs by the rules of ba_view_graph_forest (key: the support with loops, else the weight alone;
+ *     the fixed cameras).
+ *  3. Start: c0 != NULL: c0 (finite for every camera with a used pair, else BA_ERR_ARG).  c0 == NULL: the root at 0 and
+ *     child = parent + the direction parent -> child along the forest, so every tree baseline has length 1.  fixed cameras are held
+ *     at c0, which is then required.
+ *  4. Cost: F(c) = sum over the kept pairs of w_k c^2 rho(|u^_k - d_k|^2 / c^2) / 2, u_k = c_b - c_a, u^ = u / |u|, rho the loss
+ *     of ba_lm_set_loss with c = f_scale in units of the chord (about radians for small angles).  A kept pair with |u_k| < 1e-12
+ *     has no direction: it adds w_k c^2 rho(4 / c^2) / 2 to the cost and nothing to the linearisation of that iteration.
+ *  5. Linearisation: r_k = u^_k - d_k, omega_k = w_k rho', A_k = (omega_k / |u_k|^2)(I - u^ u^'), g_k = (omega_k / |u_k|)(I - u^ u^') r_k.
+ *     Camera i: g_i = the sum of -g_k over the pairs it is first in and +g_k over those it is second in, D_i = the sum of A_k.
+ *     The system is (H + lambda diag H) delta = -g, H delta at camera i = sum A_k (delta_i - delta_j); a fixed camera has
+ *     delta = 0.  Preconditioner: the inverse (by cofactors) of D_i + lambda diag D_i.  A block with det <= 1e-12 tr^3 is
+ *     singular (fewer than two edges that are not parallel and no damping on some axis): that camera has delta_i = 0 in this solve.
+ *  6. Preconditioned conjugate gradients from delta = 0, on the device: one wave per camera for the product, per-camera terms
+ *     of the dot products summed in camera order by one workgroup; alpha, beta and |r|_M = sqrt(r' M r) stay on the device.  The
+ *     iteration after which |r|_M <= cg_tol |r0|_M (or is NaN) is the last; so is one with p' H p <= 0, whose step is not taken;
+ *     g = 0 takes no iteration.  The host launches batches of min(16, remaining) iterations and reads the stop flag and the
+ *     count after each; the iterations of a batch after the last are no-ops, so the result does not depend on the batch.  At
+ *     most max_cg iterations (<= 0: 500; at most 100000).
+ *  7. Levenberg-Marquardt on the host (ba_transavg_lm_decide, host only, is the rule): lambda starts at lambda0 (<= 0: 1e-3).  The
+ *     trial c + delta is accepted iff F(trial) < F; then lambda <- max(lambda / 3, 1e-9), else lambda <- 4 lambda.  The solve
+ *     stops after the iteration at which, the first that holds, |F - F(trial)| <= ftol F (<= 0: 1e-10; stop 1), the new
+ *     lambda > 1e8 (stop 2), or max_iterations (<= 0: 50; at most 100000) are done (stop 3).  trace: one row of four per iteration:
+ *     F(trial), the lambda of the solve, its conjugate-gradient iterations, accepted (room for 4 max_iterations, or NULL).
+ *  8. Gauge: a component with a fixed camera is left as solved.  A component without one is moved so that its root is back at
+ *     its start and scaled about the root so that the mean length of its kept baselines is that of the start (host arithmetic,
+ *     sums in pair order).  The centres of two components are unrelated.
+ *  9. residual[k] = the angle between u^_k and d_k for every pair with a usable dir whose cameras lie in one component (NaN else,
+ *     and for |u_k| < 1e-12); edge_weight[k] = rho' on a kept pair, else 0; cost[0] = F at the start, cost[1] at the result; c (3
+ *     per camera) is NaN for a camera outside the graph; status, component and counts as in ba_average_rotations (BA_TA_* =
+ *     BA_RA_*).  n_loops and support: NULL, or npairs (0 without loops).
+ * Deterministic: two calls give the same bits.  The next ba_lm_step / ba_lm_solve gives the bits it gives without the call.
+ * Out of scope: a 1DSfM-style 1-D filter of the pairs, pairwise baseline lengths, Float32, several ranks, moving the sweeps of
+ * ba_average_rotations onto the conjugate gradient. */
+enum { BA_TA_OK = 0, BA_TA_ROOT = 1, BA_TA_FIXED = 2, BA_TA_ISOLATED = 3, BA_TA_STATES = 4 };
+typedef struct ba_transavg_opts {
+  int loss;              /* BA_LOSS_* */
+  int loops;             /* != 0: the loop filter of step 1 */
+  int min_support;       /* <= 0: 1 */
+  int max_iterations;    /* <= 0: 50; at most 100000 */
+  int max_cg;            /* <= 0: 500; at most 100000 */
+  double f_scale;        /* c, chordal units; finite and > 0 unless the loss is linear */
+  double loop_threshold; /* radians; finite and > 0 with loops */
+  double min_ratio;      /* [0, 1]; 0: off */
+  double ftol;           /* <= 0: 1e-10 */
+  double cg_tol;         /* <= 0: 1e-6 */
+  double lambda0;        /* <= 0: 1e-3 */
+} ba_transavg_opts;
+int ba_translation_loops(ba_problem *p, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                         const double *dir /* 3 npairs */, const uint8_t *used /* npairs or NULL */, double threshold,
+                         int32_t *n_loops /* npairs */, int32_t *support /* npairs */);
+int ba_average_translations(ba_problem *p, int64_t npairs, const int64_t *pair_a1, const int64_t *pair_b1,
+                            const double *dir /* 3 npairs */, const double *weights /* npairs or NULL */,
+                            const uint8_t *used /* npairs or NULL */, const double *c0 /* 3 ncams or NULL */,
+                            const uint8_t *fixed /* ncams or NULL */, const ba_transavg_opts *opts, double *c /* 3 ncams */,
+                            uint8_t *status /* ncams */, int32_t *component /* ncams */, uint8_t *kept /* npairs */,
+                            int32_t *n_loops /* npairs or NULL */, int32_t *support /* npairs or NULL */,
+                            double *residual /* npairs */, double *edge_weight /* npairs */, int32_t *iterations,
+                            int32_t *cg_iterations, double *trace /* 4 max_iterations or NULL */, double *cost /* 2 or NULL */,
+                            int64_t *counts /* BA_TA_STATES or NULL */);
+/* The rule of step 7, host only: returns accepted (0 / 1); *lambda_next and *stop (0, or 1..3 as above) may be NULL. */
+int ba_transavg_lm_decide(double F, double F_trial, double lambda, int iteration /* 1-based */, int max_iterations, double ftol,
+                          double *lambda_next, int *stop);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -712,3 +712,91 @@ function average_rotations(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int6
   end
   return out, status, component, kept .!= 0, n_loops, support, residual, edge_weight, Int(sweeps[]), delta[1:sweeps[]], cost, counts
 end
+
+# ---- translation averaging over the view graph (an extension): include/ba_hip.h, "translation averaging" ------------------------
+# Pair k is (pairs_a[k], pairs_b[k]), 1-based cameras; dir (3 x npairs) is the direction of the baseline in the world frame, from
+# the centre of a to the centre of b: -R_b' t with the unit t of relative_pose and the R_b of average_rotations.  It need not be
+# normalised.  Angles are radians.  A pair of cameras listed twice, in either orientation, is refused.
+
+# struct ba_transavg_opts (include/ba_hip.h)
+struct BaTransavgOpts
+  loss :: Cint
+  loops :: Cint
+  min_support :: Cint
+  max_iterations :: Cint
+  max_cg :: Cint
+  f_scale :: Cdouble
+  loop_threshold :: Cdouble
+  min_ratio :: Cdouble
+  ftol :: Cdouble
+  cg_tol :: Cdouble
+  lambda0 :: Cdouble
+end
+
+# The loop consistency of the directions (ba_translation_loops): per pair (a, b) the triangles (a, c, b) among the used pairs
+# that can be checked and those in which the direction a -> b lies within `threshold` of the shorter arc between the directions
+# a -> c and c -> b.  used: nothing ("dir is finite with a norm >= 1e-12") or one Bool per pair.
+function translation_loops(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}, dir :: Matrix{Float64}; threshold :: Real, used = nothing)
+  npairs = length(pairs_a)
+  length(pairs_b) == npairs && size(dir) == (3, npairs) || error("translation_loops: pairs_a, pairs_b of one length and dir 3 x npairs")
+  bytes = _used_bytes(used, npairs)
+  n_loops = zeros(Int32, npairs)
+  support = zeros(Int32, npairs)
+  GC.@preserve pairs_a pairs_b dir bytes n_loops support begin
+    bacheck(ccall((:ba_translation_loops, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}, Cdouble, Ptr{Int32}, Ptr{Int32}),
+                  nlp.handle, npairs, pointer(pairs_a), pointer(pairs_b), pointer(dir), _or_null(bytes, UInt8), Cdouble(threshold),
+                  pointer(n_loops), pointer(support)))
+  end
+  return n_loops, support
+end
+
+# Robust translation averaging (ba_average_translations): the centre of every camera from the directions of all pairs at once, up
+# to a shift and a scale per component.  loss is a BA_LOSS_* value with f_scale = c in units of the chord; loop_threshold > 0 runs
+# the loop filter first (a pair with checked triangles of which fewer than min_support, or fewer than min_ratio of them, close is
+# dropped); c0 (3 x ncams) is a start of the caller's, required with fixed (one Bool per camera, held at c0).  Returns c (3 x
+# ncams, NaN for a camera without a kept pair), the state of every camera (BA_TA_*), its component, the kept pairs, the loop
+# counts, the residual and the weight of every pair, the iterations, the conjugate-gradient iterations, the trace (4 x
+# iterations: cost of the trial, lambda, conjugate-gradient iterations, accepted), the cost before and after, and the cameras
+# per state.  The centres of different components are unrelated.
+function average_translations(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{Int64}, dir :: Matrix{Float64};
+                              weights :: Vector{Float64} = Float64[], used = nothing, loop_threshold :: Real = 0.0,
+                              min_support :: Integer = 1, min_ratio :: Real = 0.34, c0 :: Matrix{Float64} = zeros(3, 0), fixed = nothing,
+                              loss :: Integer = 0, f_scale :: Real = 0.0, max_iterations :: Integer = 50, ftol :: Real = 1e-10,
+                              cg_tol :: Real = 1e-6, max_cg :: Integer = 500, lambda0 :: Real = 1e-3)
+  npairs = length(pairs_a)
+  ncams = nlp.ncams
+  length(pairs_b) == npairs && size(dir) == (3, npairs) || error("average_translations: pairs_a, pairs_b of one length and dir 3 x npairs")
+  isempty(weights) || length(weights) == npairs || error("average_translations: weights hold one entry per pair")
+  isempty(c0) || size(c0) == (3, ncams) || error("average_translations: c0 must be 3 x ncams")
+  1 <= max_iterations <= 100000 && 1 <= max_cg <= 100000 || error("average_translations: max_iterations and max_cg in 1..100000")
+  bytes = _used_bytes(used, npairs)
+  held = fixed === nothing ? UInt8[] : (length(fixed) == ncams ? Vector{UInt8}(fixed) : error("fixed must hold one entry per camera"))
+  opts = Ref(BaTransavgOpts(Cint(loss), Cint(loop_threshold > 0), Cint(min_support), Cint(max_iterations), Cint(max_cg), Cdouble(f_scale),
+                            Cdouble(loop_threshold), Cdouble(min_ratio), Cdouble(ftol), Cdouble(cg_tol), Cdouble(lambda0)))
+  out = fill(NaN, 3, ncams)
+  status = zeros(UInt8, ncams)
+  component = zeros(Int32, ncams)
+  kept = zeros(UInt8, npairs)
+  n_loops = zeros(Int32, npairs)
+  support = zeros(Int32, npairs)
+  residual = fill(NaN, npairs)
+  edge_weight = zeros(Float64, npairs)
+  iterations = Ref{Int32}(0)
+  cg_iterations = Ref{Int32}(0)
+  trace = zeros(Float64, 4, max_iterations)
+  cost = zeros(Float64, 2)
+  counts = zeros(Int64, 4)
+  GC.@preserve pairs_a pairs_b dir weights bytes c0 held opts out status component kept n_loops support residual edge_weight trace cost counts begin
+    bacheck(ccall((:ba_average_translations, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Float64}, Ptr{UInt8},
+                   Ptr{BaTransavgOpts}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                   Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                  nlp.handle, npairs, pointer(pairs_a), pointer(pairs_b), pointer(dir), _or_null(weights, Float64), _or_null(bytes, UInt8),
+                  _or_null(c0, Float64), _or_null(held, UInt8), Base.unsafe_convert(Ptr{BaTransavgOpts}, opts), pointer(out),
+                  pointer(status), pointer(component), pointer(kept), pointer(n_loops), pointer(support), pointer(residual),
+                  pointer(edge_weight), iterations, cg_iterations, pointer(trace), pointer(cost), pointer(counts)))
+  end
+  return out, status, component, kept .!= 0, n_loops, support, residual, edge_weight, Int(iterations[]), Int(cg_iterations[]),
+         trace[:, 1:iterations[]], cost, counts
+end
