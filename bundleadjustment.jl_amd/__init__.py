@@ -13,8 +13,8 @@ except ImportError:  # pragma: no cover
     _torch = None
 from . import _lib
 from ._lib import BAArgError, BAError, SQDException, LOSSES, device_count
-from .lm import GenericExecutionStats, Levenberg_Marquardt, lm_step, covariance, refine_points, refine_cameras, pair_matches, relative_pose, relative_pose_five_point, refine_relative_pose, five_point, p3p, homography, decompose_homography, homography_pose, two_view, rotation_loops, view_graph_forest, average_rotations, translation_loops, average_translations, translation_directions, camera_translations, schur_pattern, schur_memory, set_ordering, schur_ordering_used
-from ._lib import schur_ordering, tie_intrinsics, compose_relative
+from .lm import GenericExecutionStats, Levenberg_Marquardt, lm_step, covariance, refine_points, refine_cameras, pair_matches, relative_pose, relative_pose_five_point, refine_relative_pose, five_point, p3p, homography, decompose_homography, homography_pose, two_view, rotation_loops, view_graph_forest, average_rotations, translation_loops, average_translations, translation_directions, camera_translations, similarity, schur_pattern, schur_memory, set_ordering, schur_ordering_used
+from ._lib import schur_ordering, tie_intrinsics, compose_relative, apply_similarity, camera_centres
 from .model import BALNLPModel, FeasibilityResidual
 from .readfiles import name, readfile
 from . import synthetic
@@ -22,4 +22,4 @@ from . import parallel
 
 __all__ = ["BALNLPModel", "FeasibilityResidual", "Levenberg_Marquardt", "GenericExecutionStats", "readfile", "name",
            "BAError", "BAArgError", "SQDException", "LOSSES", "device_count", "synthetic", "parallel", "lm_step", "covariance", "refine_points", "refine_cameras", "pair_matches", "relative_pose", "relative_pose_five_point", "refine_relative_pose", "five_point", "p3p", "homography", "decompose_homography", "homography_pose", "two_view", "rotation_loops", "view_graph_forest", "average_rotations", "translation_loops", "average_translations", "translation_directions", "camera_translations", "schur_pattern", "schur_memory", "set_ordering", "schur_ordering_used",
-           "schur_ordering", "tie_intrinsics", "compose_relative"]
+           "schur_ordering", "tie_intrinsics", "compose_relative", "similarity", "apply_similarity", "camera_centres"]

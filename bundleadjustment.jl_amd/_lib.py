@@ -100,6 +100,7 @@ SYMBOLS = [
     "ba_homography", "ba_decompose_homography", "ba_homography_pose",
     "ba_rotation_loops", "ba_view_graph_forest", "ba_average_rotations",
     "ba_translation_loops", "ba_average_translations", "ba_transavg_lm_decide",
+    "ba_similarity",
 ]
 
 _lib = None
@@ -199,6 +200,7 @@ def lib():
     L.ba_homography.argtypes = L.ba_relative_pose.argtypes
     L.ba_decompose_homography.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
     L.ba_homography_pose.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
+    L.ba_similarity.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(RansacOpts), C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.ba_rotation_loops.argtypes = [vp, i64, vp, vp, vp, vp, C.c_double, vp, vp]
     L.ba_view_graph_forest.argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ba_average_rotations.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RotavgOpts)] + [vp] * 12
@@ -668,6 +670,9 @@ PAIR_STATES = ("ok", "few_matches", "degenerate", "no_consensus")
 # states of ba_homography (BA_HG_*): the names of PAIR_STATES; few_matches is "fewer than 4 used matches" here
 HOMOGRAPHY_STATES = PAIR_STATES
 
+# states of ba_similarity (BA_SM_*), per problem; few_rows is "fewer than 3 used rows"
+SIMILARITY_STATES = ("ok", "few_rows", "degenerate", "no_consensus")
+
 # states of ba_refine_relative_pose (BA_RR_*) and the keys of the `refine=` dict of relative_pose*
 PAIR_REFINE_STATES = ("converged", "stalled", "max_iter", "nonfinite", "skipped")
 PAIR_REFINE_KEYS = ("max_iter", "xtol", "lam0", "loss", "f_scale", "threshold", "rounds")
@@ -772,6 +777,67 @@ def compose_relative(x, npnts, a, b, r, t, baseline=1.0):
     Rb = R @ rodrigues(cams[a - 1, :3])
     cams[b - 1, :3] = rotation_vector(Rb)
     cams[b - 1, 3:6] = R @ cams[a - 1, 3:6] + float(baseline) * t
+    return x
+
+
+def _rodrigues(v):
+    """the rotation matrix of the rotation vector v (the model's formula: no theta -> 0 branch)"""
+    th = np.sqrt(v @ v)
+    k = v / th
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    return np.cos(th) * np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * np.outer(k, k)
+
+
+def _x_parts(who, x, npnts):
+    """(a copy of x, its points (npnts, 3), its cameras (ncams, 9)) -- views into the copy -- or ValueError"""
+    x = np.array(x, dtype=np.float64, copy=True)
+    npnts = int(npnts)
+    if x.ndim != 1 or npnts < 0 or x.size < 3 * npnts or (x.size - 3 * npnts) % 9 != 0:
+        raise ValueError(f"{who}: x must have 3 npnts + 9 ncams entries, got {x.shape} with npnts = {npnts}")
+    return x, x[:3 * npnts].reshape(npnts, 3), x[3 * npnts:].reshape(-1, 9)
+
+
+def _subset(who, name, idx1, n):
+    """0-based indices of the 1-based integer array idx1 (None: all n), or ValueError"""
+    if idx1 is None:
+        return np.arange(n)
+    a = np.asarray(idx1)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer) or a.min() < 1 or a.max() > n:
+        raise ValueError(f"{who}: {name} must be a one-dimensional array of 1-based integers in 1..{n}, got dtype {a.dtype}, shape {a.shape}")
+    return np.unique(a.astype(np.int64)) - 1
+
+
+def camera_centres(x, npnts):
+    """The centres -R' t of the cameras of x (layout [points; cameras]), shape (ncams, 3).  numpy, host only."""
+    _, _, cams = _x_parts("camera_centres", x, npnts)
+    return np.array([-_rodrigues(c[:3]).T @ c[3:6] for c in cams]).reshape(-1, 3)
+
+
+def apply_similarity(x, npnts, s, r, t, *, cameras=None, points=None):
+    """A copy of x (layout [points; cameras]) moved by the similarity (s, r, t) of `similarity`: a point X becomes s Q X + t with
+    Q the rotation of r; a camera (R, t_c) becomes (R Q', s t_c - R Q' t), so that its centre C becomes s Q C + t and R X + t_c
+    of every point is multiplied by s: the intrinsics are untouched and every reprojection is unchanged.  The rotation vector
+    is written by the rule of compose_relative.  cameras, points: 1-based index arrays that move only one component or one
+    sub-model (None: all).  numpy, host only."""
+    who = "apply_similarity"
+    x, pts, cams = _x_parts(who, x, npnts)
+    try:
+        s, r, t = float(s), np.asarray(r, dtype=np.float64), np.asarray(t, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: s must be a number, r and t arrays of numbers") from None
+    if r.shape != (3,) or t.shape != (3,):
+        raise ValueError(f"{who}: r and t must have shape (3,), got {r.shape} and {t.shape}")
+    if not (np.isfinite(s) and s > 0 and np.isfinite(r).all() and np.isfinite(t).all() and r @ r > 0):
+        raise ValueError(f"{who}: s must be finite and > 0, r finite and not 0, t finite, got {s!r}, {r!r}, {t!r}")
+    ci, pi = _subset(who, "cameras", cameras, len(cams)), _subset(who, "points", points, len(pts))
+    Q = _rodrigues(r)
+    pts[pi] = s * (pts[pi] @ Q.T) + t
+    for c in ci:
+        Rn = _rodrigues(cams[c, :3]) @ Q.T
+        cams[c, :3] = rotation_vector(Rn)
+        cams[c, 3:6] = s * cams[c, 3:6] - Rn @ t
     return x
 
 

@@ -21,7 +21,7 @@ const char *const kProfNames[PC_COUNT] = {
     "k_backsub", "k_model_sq", "k_reduce", "allreduce", "k_robust_scale", "k_fix_mask",
     "k_cov_selinv", "k_cov_cams", "k_cov_points", "k_prior", "k_shared_border", "k_tri_solve_multi", "k_shared_small",
     "k_info_whiten", "k_refine_points", "k_refine_cameras", "k_resect_cameras", "k_ransac_cameras",
-    "k_ransac_points", "k_homography", "k_rotation_averaging", "k_translation_averaging"};
+    "k_ransac_points", "k_homography", "k_rotation_averaging", "k_translation_averaging", "k_similarity"};
 
 extern "C" const char *ba_last_error(void) { return g_err; }
 

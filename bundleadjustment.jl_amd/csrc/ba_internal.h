@@ -233,6 +233,7 @@ enum ProfClass {
   PC_HOMOGRAPHY,      // homography of camera pairs (ba_homography): k_pair_rays, k_pair_hypotheses_h, k_pair_select_h, k_pair_fit_h
   PC_ROTAVG,          // "k_rotation_averaging" (ba_rotation_loops, ba_average_rotations): k_rotation_loops, k_rotavg_sweep, k_rotavg_edges, k_rotavg_sum, k_rotavg_finish
   PC_TRANSAVG,        // "k_translation_averaging" (ba_translation_loops, ba_average_translations): every kernel of ba_transavg_kernels.hip
+  PC_SIMILARITY,        // "k_similarity" (ba_similarity): k_similarity_hypotheses, k_similarity_select, k_similarity_fit
   PC_COUNT
 };
 extern const char *const kProfNames[PC_COUNT];
@@ -554,6 +555,28 @@ struct TransavgWork {
   GrowBuf<double> dir_in, dir, weight, A[2], g[2], term[2], residual, edge_weight, c[2], gc, dg, Minv, x, r, z, p, q, part, sc, cost;
 };
 
+// ---- similarity alignment of reconstructions (ba_similarity; ba_similarity_kernels.hip) ------------------------------
+// The per-call device buffers.  Per problem: the first row of its list, state, set size, winner, "stopped" byte, the returned
+// (s, r, t) and rms; per row its record (src, dst, used: 7 doubles, packed on the host) and the inlier byte; per (problem,
+// hypothesis) the fit (s, R, t: 13 doubles) and the inlier count
+struct SimilarityWork {
+  GrowBuf<int> row_ptr, hyp_count, n_inliers, best_hyp;
+  GrowBuf<double> rows, hyp, sim, rms;
+  GrowBuf<uint8_t> inlier, stopped, status;
+};
+// what the kernels of ba_similarity work on
+struct SimArgs {
+  const int *row_ptr;
+  const double *rows;
+  double *hyp, *sim, *rms;
+  int *hyp_count, *n_inliers, *best_hyp;
+  uint8_t *inlier, *stopped, *status;
+  int hypotheses, sample, min_inliers, with_scale;  // hypotheses == 0: no consensus stage, the set is the used rows
+  uint64_t seed_mix;                                // mix(seed)
+  double tau2;
+};
+constexpr int SM_MIN_ROWS = 3;  // three rows that are not collinear fix a similarity: the least sample and the least set
+
 struct ba_problem {
   int device = 0;
   HipStream stream;
@@ -623,6 +646,7 @@ struct ba_problem {
   PairWork pairs;
   RotavgWork rotavg;
   TransavgWork transavg;
+  SimilarityWork similarity;
   // communication (multi-GPU)
   int rank = 0, world = 1;
   BaComm comm;

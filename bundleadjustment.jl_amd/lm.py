@@ -1102,6 +1102,59 @@ def average_translations(nlp, pairs, directions, *, weights=None, used=None, loo
     return info
 
 
+def similarity(nlp, src, dst, *, offsets=None, used=None, ransac=None, scale=True):
+    """Robust similarity alignment of 3D-3D correspondences (ba_similarity): (s, R, t) with dst ~ s R src + t, which brings a
+    reconstruction into the frame of its ground control, of GPS centres or of another model.  src, dst (n, 3); offsets
+    (nprob + 1,), 0-based, starting at 0 and not decreasing with offsets[-1] = n: problem k owns the rows offsets[k] ..
+    offsets[k + 1] (None: one problem of all rows) -- many problems in one call merge sub-models or the components of a view
+    graph.  used (n,) boolean, default all; a row with a number that is not finite is never used (the NaN centres of
+    average_translations drop out this way).
+    ransac=dict(threshold=, hypotheses=, sample=, refits=, min_inliers=, seed=) puts the consensus stage of refine_cameras in front
+    (threshold in the units of dst; sample in 3..16, default 3; min_inliers at least 3, default max(sample, 3)): minimal samples,
+    the winner by its inlier count |s R src + t - dst| <= threshold, refits on the set; None: the fit on all used rows.
+    scale=False fixes s = 1 (a rigid alignment).
+    Returns a dict: `s` (nprob,), `r` (nprob, 3: the rotation vector of R), `t` (nprob, 3), all NaN where the problem is not ok;
+    `status` (names among _lib.SIMILARITY_STATES; few_rows: fewer than 3 used rows; degenerate: collinear rows), `inliers` (n,)
+    bool, `n_inliers`, `best_hypothesis` (-1: none), `rms` (of the residual over the final set; NaN where not ok), `counts`
+    (problems per state).  _lib.apply_similarity moves x by (s, r, t).  nlp supplies the device, the stream and the buffers: no
+    model data is read.  Bad arguments raise ValueError before any device call."""
+    who = "similarity"
+    opts = None if ransac is None else _lib.ransac_opts(ransac, least=3, most=16, least_set=3)
+    if not isinstance(scale, (bool, np.bool_)):
+        raise ValueError(f"{who}: scale must be True or False, got {scale!r}")
+    try:
+        src, dst = np.ascontiguousarray(src, dtype=np.float64), np.ascontiguousarray(dst, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: src and dst must be numbers") from None
+    if src.ndim != 2 or src.shape[1] != 3 or dst.shape != src.shape:
+        raise ValueError(f"{who}: src and dst must have one shape (n, 3), got {src.shape} and {dst.shape}")
+    n = src.shape[0]
+    if offsets is None:
+        ptr = np.array([0, n], dtype=np.int64)
+    else:
+        ptr = np.asarray(offsets)
+        if ptr.ndim != 1 or ptr.size < 1 or not np.issubdtype(ptr.dtype, np.integer):
+            raise ValueError(f"{who}: offsets must be an integer array of shape (nprob + 1,), got dtype {ptr.dtype}, shape {ptr.shape}")
+        ptr = np.ascontiguousarray(ptr, dtype=np.int64)
+        if ptr[0] != 0 or ptr[-1] != n or (np.diff(ptr) < 0).any():
+            raise ValueError(f"{who}: offsets are 0-based, start at 0, do not decrease and end at n = {n}, got {ptr[0]} .. {ptr[-1]}")
+    if used is not None:
+        used = np.asarray(used)
+        if used.shape != (n,) or used.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"{who}: used must be a boolean array of shape ({n},), got dtype {used.dtype}, shape {used.shape}")
+        used = np.ascontiguousarray(used != 0, dtype=np.uint8)
+    nprob = len(ptr) - 1
+    sim, status = np.full((nprob, 7), np.nan), np.zeros(nprob, dtype=np.uint8)
+    inlier, n_in, best = np.zeros(n, dtype=np.uint8), np.zeros(nprob, dtype=np.int32), np.zeros(nprob, dtype=np.int32)
+    rms, counts = np.full(nprob, np.nan), np.zeros(len(_lib.SIMILARITY_STATES), dtype=np.int64)
+    _lib.check(_lib.lib().ba_similarity(nlp.handle, nprob, _lib.ptr(ptr), _lib.ptr(src), _lib.ptr(dst), None if used is None else _lib.ptr(used),
+                                        None if opts is None else C.byref(opts), 1 if scale else 0, _lib.ptr(sim), _lib.ptr(status),
+                                        _lib.ptr(inlier), _lib.ptr(n_in), _lib.ptr(best), _lib.ptr(rms), _lib.ptr(counts)))
+    return dict(s=sim[:, 0].copy(), r=sim[:, 1:4].copy(), t=sim[:, 4:7].copy(), status=np.array(_lib.SIMILARITY_STATES)[status],
+                inliers=inlier != 0, n_inliers=n_in, best_hypothesis=best, rms=rms,
+                counts={s: int(c) for s, c in zip(_lib.SIMILARITY_STATES, counts)})
+
+
 def schur_pattern(nlp):
     """(tile_fill, flop_fill, sparse_schedule) of the reduced camera system of a handle that has run a direct solve
     (ba_lm_schur_pattern): the fraction of the lower 128 x 128 tiles in the factor's pattern, the fraction of the dense

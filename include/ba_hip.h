@@ -1201,6 +1201,61 @@ int ba_average_translations(ba_problem *p, int64_t npairs, const int64_t *pair_a
 int ba_transavg_lm_decide(double F, double F_trial, double lambda, int iteration /* 1-based */, int max_iterations, double ftol,
                           double *lambda_next, int *stop);
 
+/* ---- similarity alignment of reconstructions: scale, rotation, shift with RANSAC (an extension) ----------------------
+ * Every product of the front end lives in a frame of its own: ba_average_translations returns centres up to a shift and a scale
+ * per component, a seeded reconstruction has a baseline of 1, and the priors of ba_lm_set_priors (ground control, GPS, an earlier
+ * solve) live in the caller's frame.  ba_similarity brings one into the other from 3D-3D correspondences, some of them wrong.
+ * Problem k owns the rows row_ptr[k] .. row_ptr[k + 1] (0-based, row_ptr[0] = 0, not decreasing), n = row_ptr[nprob], and asks
+ * for (s, R, t) with dst ~ s R src + t: many problems in one call merge sub-models or the components of a view graph, one problem
+ * is georeferencing.  The handle supplies the device, the stream and the buffers, as for ba_decompose_homography: no model data
+ * is read.  A handle with a communicator is refused, as the siblings refuse it; nprob == 0 returns 0; n >= 2^31 is BA_ERR_ARG (the
+ * kernels index rows with int); a NULL p, row_ptr, sim or status, and a NULL src or dst with n > 0, are BA_ERR_ARG.
+ * Used rows: a row is used iff `used` is NULL or its byte is non-zero, and all six of its numbers are finite (the cameras that
+ * ba_average_translations leaves at NaN drop out this way).  Fewer than 3 used rows: BA_SM_FEW_ROWS.
+ * Options (ba_ransac_opts, reused): threshold tau in the units of dst, finite and > 0; hypotheses H (<= 0: 128; at most 4096);
+ * sample m (<= 0: 3; 3..16); refits (< 0: 2; at most 8); min_inliers (<= 0: max(m, 3); at least 3); seed as the siblings.
+ * Anything else is BA_ERR_ARG.
+ * The fit of a set M of m >= 3 rows -- the one definition for hypotheses, refits and the final fit:
+ *  1. o = the first row of M: for a hypothesis the first of its draws, for a set the lowest list index.  a_k = src_k - src_o and
+ *     b_k = dst_k - dst_o.
+ *  2. One pass forms 16 sums: sum a (3), sum b (3), sum |a|^2 (1), sum b a' (9).
+ *  3. m_a = sum a / m and m_b = sum b / m; v_a = sum |a|^2 - m |m_a|^2 and K = sum b a' - m m_b m_a'.
+ *  4. K = U Sigma V' by the one-sided 3 x 3 Jacobi SVD of ba_resect_cameras (rotations of column pairs of K until they are
+ *     orthogonal: K V = U Sigma, V a product of rotations).  R is the nearest proper rotation it defines: the sign goes on the
+ *     smallest singular value, whose column of U is taken as the cross product of the other two (in cyclic order, so det U = +1).
+ *     d = -1 where that turned the column against K V's own, else +1; R = U V'.
+ *  5. s = (sigma_1 + sigma_2 + d sigma_3) / v_a when with_scale is set, else 1 (sigma_1 >= sigma_2 >= sigma_3).
+ *  6. t = (dst_o + m_b) - s R (src_o + m_a).
+ * Degenerate (void as a hypothesis, BA_SM_DEGENERATE as the final fit): any of the 16 sums is not finite; v_a <= 0;
+ * sigma_2 <= 1e-10 sigma_1 (collinear rows) or a singular value that is not finite; s is not finite or <= 0.  Coplanar rows are
+ * not degenerate.
+ * Inlier test of a row under (s, R, t): it is used and |s R src + t - dst|^2 <= tau^2.  A comparison with NaN fails.
+ * opts == NULL: no consensus stage -- the set is every used row (inlier = used, best_hyp = -1), the fit on it is returned.
+ * opts != NULL: the consensus stage of ba_ransac_cameras.  Sampling is exactly ba_ransac_sample(seed, h, degree, used, m) on the
+ * problem's list in the caller's order (the rule: that host entry itself takes m >= 6 only).  Hypothesis h = the fit on the m
+ * sampled rows in the order of their draws, a degenerate sample is void; score = the inlier count over the whole list; the winner
+ * is the largest count, ties to the lowest h.  Without a valid hypothesis, or with a best count < min_inliers:
+ * BA_SM_NO_CONSENSUS, inlier bytes 0, n_inliers = the best count (0 if none), best_hyp = that h or -1.  Refits, up to `refits`
+ * times: the fit on the current set M; the whole list re-scored under it gives M'; M' is adopted iff |M'| >= |M| and M' != M,
+ * otherwise (smaller, equal, or the refit was degenerate) M stays and the problem stops.  The fit on the final set is returned.
+ * Outputs: only a problem that is BA_SM_OK has its seven entries of sim written -- s, the rotation vector of R by the rule of
+ * ba_resect_cameras (theta < 1e-12: (1e-12, 0, 0)), t; the others keep what the caller put there.  inlier (n bytes 0 / 1), n_inliers
+ * (the size of the final set; 0 for BA_SM_FEW_ROWS), best_hyp, rms (the root mean square of |s R src + t - dst| over the final
+ * set under the returned fit; NaN where the problem is not BA_SM_OK) and counts (problems per state) may each be NULL.
+ * Two calls give the same bits: the sums run in a fixed order (strided partial sums per thread, the butterfly of a wave, the four
+ * waves in order), there are no floating-point atomics and every output has one writer; a problem alone gives the bits it gives
+ * among many; the next ba_lm_step / ba_lm_solve on the handle gives the bits it gives without the call.
+ * Out of scope: per-row weights or covariances; MSAC or LO-RANSAC scoring; an adaptive hypothesis count; reflections; Float32;
+ * several ranks. */
+enum { BA_SM_OK = 0, BA_SM_FEW_ROWS = 1, BA_SM_DEGENERATE = 2, BA_SM_NO_CONSENSUS = 3, BA_SM_STATES = 4 };
+int ba_similarity(ba_problem *p, int64_t nprob, const int64_t *row_ptr /* nprob + 1 */,
+                  const double *src /* 3 n */, const double *dst /* 3 n */, const uint8_t *used /* n or NULL */,
+                  const ba_ransac_opts *opts /* NULL: the fit on all used rows */, int with_scale,
+                  double *sim /* 7 nprob: s, rotation vector r, t */, uint8_t *status /* nprob */,
+                  uint8_t *inlier /* n or NULL */, int32_t *n_inliers /* nprob or NULL */,
+                  int32_t *best_hyp /* nprob or NULL */, double *rms /* nprob or NULL */,
+                  int64_t *counts /* BA_SM_STATES or NULL */);
+
 /* What a handle holds of the reduced camera matrix, in 128 x 128 tiles of its scalar type (Float64; a Float32 factorisation
  * adds half of that again): tiles_full = the whole lower triangle, nt (nt + 1) / 2; tiles_held = what this handle allocated
  * for S; tiles_staging = the staging buffer of the chunked assembly.  One GPU (and BA_DIST_FACTOR=0): held = full,

@@ -800,3 +800,39 @@ function average_translations(nlp, pairs_a :: Vector{Int64}, pairs_b :: Vector{I
   return out, status, component, kept .!= 0, n_loops, support, residual, edge_weight, Int(iterations[]), Int(cg_iterations[]),
          trace[:, 1:iterations[]], cost, counts
 end
+
+# Similarity alignment of reconstructions (an extension): include/ba_hip.h, ba_similarity.  (s, R, t) with dst ~ s R src + t from
+# 3D-3D correspondences: src, dst are 3 x n, offsets (0-based, nprob + 1 entries from 0 to n) split them into independent
+# problems (empty: one problem of all rows), used holds one Bool per row (nothing: all; a row with a number that is not finite
+# is never used).  With a threshold (the units of dst) the consensus stage stands in front (samples of 3..16, default 3;
+# min_inliers at least 3); with_scale = false fixes s = 1.  Returns sim (7 x nprob: s, the rotation vector, t; NaN where the
+# state is not 0), status (BA_SM_*), the inlier mask per row, the size of every problem's set, its winning hypothesis, the rms
+# of the residual over the set and the problems per state.
+function similarity(nlp, src :: Matrix{Float64}, dst :: Matrix{Float64}; offsets :: Vector{Int64} = Int64[], used = nothing,
+                    threshold :: Union{Real, Nothing} = nothing, hypotheses :: Integer = 0, sample :: Integer = 0,
+                    refits :: Integer = -1, min_inliers :: Integer = 0, seed :: Integer = 0, with_scale :: Bool = true)
+  n = size(src, 2)
+  size(src, 1) == 3 && size(dst) == size(src) || error("similarity: src and dst must be 3 x n")
+  row_ptr = isempty(offsets) ? Int64[0, n] : offsets
+  row_ptr[1] == 0 && row_ptr[end] == n && issorted(row_ptr) || error("similarity: offsets run from 0 to n and do not decrease")
+  nprob = length(row_ptr) - 1
+  bytes = _used_bytes(used, n)
+  sim = fill(NaN, 7, nprob)
+  status = zeros(UInt8, nprob)
+  inlier = zeros(UInt8, n)
+  n_inliers = zeros(Int32, nprob)
+  best_hyp = zeros(Int32, nprob)
+  rms = fill(NaN, nprob)
+  counts = zeros(Int64, 4)
+  opts = Ref(BaRansacOpts(Cdouble(threshold === nothing ? 1.0 : threshold), Cint(hypotheses), Cint(sample), Cint(refits),
+                          Cint(min_inliers), UInt64(seed)))
+  GC.@preserve row_ptr src dst bytes opts sim status inlier n_inliers best_hyp rms counts begin
+    optr = threshold === nothing ? Ptr{BaRansacOpts}(C_NULL) : Base.unsafe_convert(Ptr{BaRansacOpts}, opts)
+    bacheck(ccall((:ba_similarity, libba), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{UInt8}, Ptr{BaRansacOpts}, Cint, Ptr{Float64}, Ptr{UInt8},
+                   Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}),
+                  nlp.handle, nprob, pointer(row_ptr), pointer(src), pointer(dst), _or_null(bytes, UInt8), optr, Cint(with_scale),
+                  pointer(sim), pointer(status), pointer(inlier), pointer(n_inliers), pointer(best_hyp), pointer(rms), pointer(counts)))
+  end
+  return sim, status, inlier .!= 0, n_inliers, best_hyp, rms, counts
+end
